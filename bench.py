@@ -6,6 +6,12 @@ FASTQ scan -> 2-bit encode -> hash -> dedup -> insert for ~1e9 k-mers per GPU of
 synthetic reads (generateFakeSequences.py shape) already resident in HBM; with
 N > 1 ranks (one process per GPU, reads sharded, weak scaling) the step ends
 with the table merge over RCCL.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line (stage
+times and the roofline come from those steps).  --full adds what takes time of
+its own: the --check outside the timed region (tsxcount_amd/verify.py) and the
+reference's CPU baseline.  --dump-outputs DIR writes what the last timed step
+left in the table(s) as .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -181,6 +187,47 @@ def run_check(args, m, T, TD, dist, torch, dist_on, sharded, world, rank, red, d
     return ok, detail
 
 
+DUMP_READS = 256   # reads whose k-mers --dump-outputs looks up (a fixed spread over rank 0's shard)
+
+
+def dump_outputs(out_dir, args, m, T, dist, torch, dist_on, red, zipf):
+    """--dump-outputs: what a caller of the timed path gets back from the table(s) its last step filled, in float64.
+      distinct.npy, count_sum.npy  the table's totals (summed over ranks), shape (1,)
+      sample_kmers.npy             the k-mers of DUMP_READS fixed reads of rank 0's shard, in window order, duplicates
+                                   kept: [n, 2 * key limbs], every 64-bit limb as its low and high 32-bit halves
+      sample_counts.npy            getKmerCounts of those k-mers [n] (summed over ranks: non-owners answer 0)
+    The inputs follow from --seed and the sizes alone, so the files of two builds compare entry by entry.
+    Collective under dist_on: every rank calls it, rank 0 writes."""
+    import numpy as np
+    from tsxcount_amd import synth, verify
+    ids = verify.sample_read_ids(0, args.reads, DUMP_READS)
+    if zipf:
+        pick, start = synth.zipf_reads(args.seed, args.reads, args.zipf_read_len,
+                                       synth.zipf_thresholds(args.zipf_templates, args.zipf_a))
+        seqs = [synth.zipf_template(args.seed, int(pick[r]), int(start[r]), args.zipf_read_len) for r in ids]
+    else:
+        seqs = []
+        for r in ids:
+            nrand, na = synth.read_lengths(args.seed, int(r), 1)
+            seqs.append(synth.read_sequence(args.seed, int(r), int(nrand[0]), int(na[0])))
+    kmers = np.concatenate([verify.kmers_of(s, args.k) for s in seqs])
+    kmers = kmers[:(48 << 20) // (8 * (2 * kmers.shape[1] + 1))]     # the files stay well below 64 MB at any k
+    st = m.stats()
+    vals = np.concatenate([m.getKmerCounts(kmers).astype(np.int64), [st["distinct"], st["count_sum"]]])
+    if dist_on:
+        t = torch.from_numpy(vals).to(red)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        vals = t.cpu().numpy()
+    if int(os.environ.get("RANK", "0")) != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    halves = np.stack([kmers & np.uint64(0xFFFFFFFF), kmers >> np.uint64(32)], axis=2).reshape(len(kmers), -1)
+    np.save(os.path.join(out_dir, "sample_kmers.npy"), halves.astype(np.float64))
+    np.save(os.path.join(out_dir, "sample_counts.npy"), vals[:-2].astype(np.float64))
+    np.save(os.path.join(out_dir, "distinct.npy"), vals[-2:-1].astype(np.float64))
+    np.save(os.path.join(out_dir, "count_sum.npy"), vals[-1:].astype(np.float64))
+
+
 def self_launch(n):
     """Start n ranks of this script through torch.distributed.run as a child process; returns its exit code.
     Nothing here imports torch or touches the GPU."""
@@ -234,10 +281,15 @@ def main():
                          "on (by the one-GPU simulations of a step, DESIGN.md section 6), else shard, else tables")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL (one GPU per rank); gloo only to rehearse N > 1 on a single GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--check-reads", type=int, default=1000, help="reads whose k-mers the check looks up one by one")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the --check (totals, polyA, sample lookups, second table) and, on "
+                         "one GPU, the reference's CPU baseline; a plain run does neither")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left in the table(s) to DIR/*.npy (float64; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--check-reads", type=int, default=1000, help="--full: reads whose k-mers the check looks up one by one")
     ap.add_argument("--no-cross-check", action="store_true",
-                    help="skip the second table (other insert path) of the check")
+                    help="--full: skip the second table (other insert path) of the check")
     ap.add_argument("--workload", default="reads", choices=["reads", "zipf"],
                     help="reads: generateFakeSequences.py shape (the BASELINE metric); zipf: BASELINE config 4 -- windows of "
                          "Zipf(1.2)-picked template sequences (one GPU; give --k 63)")
@@ -251,6 +303,8 @@ def main():
     if not argv and "TSX_BENCH_ARGV" in os.environ:      # a rank started by self_launch()
         argv = json.loads(os.environ["TSX_BENCH_ARGV"])
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # One process per GPU.  Under a launcher (python -m torch.distributed.run sets WORLD_SIZE) this process is one
     # rank.  A bare `python bench.py --gpus N` with N > 1 starts the N ranks itself -- as CHILD processes, before
@@ -382,8 +436,13 @@ def main():
         kmers_total = kmers_rank
 
     st = m.stats()
-    check_ok, check_detail = run_check(args, m, T, TD, dist, torch, dist_on, sharded, world, rank, red, dev, local_rank,
-                                       text, nbytes, kmers_rank, kmers_total, first)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, args, m, T, dist, torch, dist_on, red, zipf)
+    check, check_detail = "not run (--full)", None
+    if args.full:
+        check_ok, check_detail = run_check(args, m, T, TD, dist, torch, dist_on, sharded, world, rank, red, dev, local_rank,
+                                           text, nbytes, kmers_rank, kmers_total, first)
+        check = "pass" if check_ok else "FAIL"
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -486,7 +545,7 @@ def main():
                                       (", built in %d slabs of 2^32 slots" % (1 << slab_bits)) if slab_bits else "",
                                       how if world > 1 else ""),
                        "k": args.k, "l": args.l, "kmers_per_gpu": kmers_rank, "fastq_bytes_per_gpu": nbytes,
-                       "distinct_rank0": st["distinct"], "check": "pass" if check_ok else "FAIL",
+                       "distinct_rank0": st["distinct"], "check": check,
                        "check_detail": check_detail},
             "roofline": {"bound": "hbm", "kernel": names[dom],
                          "achieved": achieved,
@@ -502,7 +561,7 @@ def main():
                                         "achieved": path_bytes / (path_ms * 1e-3) / 1e9 if path_ms > 0 else 0.0,
                                         "frac": (path_bytes / (path_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if path_ms > 0 else 0.0}},
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.k, args.seed)
         elif world > 1:
             out["cpu_baseline"] = None

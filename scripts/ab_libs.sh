@@ -1,5 +1,6 @@
 # A/B of library builds on one box (experiments): scripts/_libs/lib_<name>.so copied over the in-tree library in turn.
 # BENCH_EXTRA: further bench.py options (e.g. "--k 63").
+BENCH_EXTRA="--full $BENCH_EXTRA"   # the lines below print the check
 cp tsxcount_amd/lib/libtsxcount_hip.so /tmp/orig.so
 for v in "$@"; do
   cp scripts/_libs/lib_$v.so tsxcount_amd/lib/libtsxcount_hip.so

@@ -1,4 +1,5 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+BENCH_ARGS="--full $BENCH_ARGS"   # the last line printed is the check
 rm -rf gpurun_out/profq; mkdir -p gpurun_out/profq
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profq -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline $BENCH_ARGS > gpurun_out/profq/bench.log 2>&1
 echo rc=$?
