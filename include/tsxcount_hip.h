@@ -107,8 +107,28 @@ int tsx_hip_create_shard(tsx_hip_map **out, int k, int l, int storagebits, int o
                          uint64_t hash_seed, int device, int shard_bits, int shard_index);
 void tsx_hip_destroy(tsx_hip_map *m);
 int tsx_hip_get_layout(const tsx_hip_map *m, tsx_hip_layout *out);
-/* Zero the table, the secondary array and the counters. */
+/* Zero the table, the secondary array and the counters (the counting mode stays). */
 int tsx_hip_clear(tsx_hip_map *m);
+
+/*
+ * Canonical counting (jellyfish -C; no reference counterpart): a k-mer x and its reverse complement rc(x) share
+ * one counter, so reads from both strands count as one sequence.  The key of the pair is min(h(x), h(rc x)) of
+ * the hash mapping (the scan kernels roll the hash of the reverse complement alongside); a palindrome (x == rc(x),
+ * even k) counts once per occurrence.  Every count and lookup entry point then works on pairs: a query for either
+ * strand returns the pair's count, add_kmers adds to the pair, and the dumps report the LEXICOGRAPHICALLY smaller
+ * strand (A < C < G < T, base 0 first).  The complement is taken on the 2-bit code (c -> 3 - c), so non-ACGT bytes
+ * stay deterministic.  The multi-GPU merge (tsx_hip_group_merge) works on canonical tables; the sharded and
+ * minimizer exchanges do not: tsx_hip_shard_*, tsx_hip_mini_* and tsx_hip_add_hashed_device refuse a canonical map
+ * (TSX_HIP_EINVAL; the *_supported queries answer 0).
+ *   set_canonical    on = 1 canonical, 0 forward (the default).  Only on an empty table -- just created or after
+ *                    tsx_hip_clear -- and not on a map created with shard_bits > 0: TSX_HIP_EINVAL otherwise.
+ *   canonical        the mode: 1 or 0.
+ *   canonical_host   CPU only: out[i] = the lexicographically smaller of kmers[i] and its reverse complement, both
+ *                    in the tsx_hip_encode layout (key_limbs(k) words per k-mer; out may equal kmers).
+ */
+int tsx_hip_set_canonical(tsx_hip_map *m, int on);
+int tsx_hip_canonical(const tsx_hip_map *m);
+int tsx_hip_canonical_host(int k, const uint64_t *kmers, size_t n, uint64_t *out);
 /* Wait for everything queued on the map's stream and report sticky errors
  * (TSX_HIP_EFULL / TSX_HIP_EOVERFLOW / TSX_HIP_ELOCK) raised by earlier inserts. */
 int tsx_hip_sync(tsx_hip_map *m);
@@ -366,6 +386,9 @@ tsx_hip_map *tsx_hip_group_map(tsx_hip_group *g, int rank);
 const char *tsx_hip_group_comm_name(const tsx_hip_group *g);   /* "rccl" or "copy" */
 const char *tsx_hip_group_last_error(void);
 int tsx_hip_group_set_record_lines(tsx_hip_group *g, int lines);
+/* tsx_hip_set_canonical on every rank's table (an empty group only); lookups then route the canonical form of a
+ * k-mer to its owner.  Refused together with the minimizer exchange (either order): TSX_HIP_EINVAL. */
+int tsx_hip_group_set_canonical(tsx_hip_group *g, int on);
 /* exchange 0 (default): every GPU counts its shard into its own table, the tables are merged afterwards (any k);
  * exchange 1: the minimizer exchange (20 <= k <= 32, at most 16 GPUs) -- strip descriptions travel to the GPU that owns
  * their k-mers' minimizer BEFORE anything is built, nothing is merged (tsx_hip_group_merge is then a no-op), lookups go to

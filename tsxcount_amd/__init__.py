@@ -101,6 +101,10 @@ def lib():
     L.tsx_hip_destroy.restype = None
     L.tsx_hip_get_layout.argtypes = [vp, ctypes.POINTER(Layout)]
     L.tsx_hip_clear.argtypes = [vp]
+    L.tsx_hip_set_canonical.argtypes = [vp, ci]
+    L.tsx_hip_canonical.argtypes = [vp]
+    L.tsx_hip_canonical_host.argtypes = [ci, u64p, sz, u64p]
+    L.tsx_hip_group_set_canonical.argtypes = [vp, ci]
     L.tsx_hip_sync.argtypes = [vp]
     L.tsx_hip_count_fastq_host.argtypes = [vp, ctypes.c_char_p, sz]
     L.tsx_hip_count_fastq_device.argtypes = [vp, vp, sz, vp]
@@ -187,6 +191,27 @@ def decode(limbs, k):
     return buf.value.decode()
 
 
+_COMP = str.maketrans("ACGT", "TGCA")
+
+
+def revcomp(seq):
+    """Reverse complement of an ACGT string (other bytes: see canonical())."""
+    return seq[::-1].translate(_COMP)
+
+
+def canonical(kmers, k):
+    """The lexicographically smaller of each k-mer and its reverse complement (A < C < G < T), what a canonical
+    table's dump reports.  A string gives a string; encoded limbs ((n, key_limbs) or flat) give limbs
+    (tsx_hip_canonical_host: the complement is taken on the 2-bit code, so any byte has one)."""
+    if isinstance(kmers, (str, bytes)):
+        return decode(canonical(encode(kmers, k), k), k)
+    a = np.ascontiguousarray(kmers, dtype=np.uint64)
+    out = np.zeros_like(a)
+    n = a.size // key_limbs(k)
+    _check(lib().tsx_hip_canonical_host(k, _p(a), n, _p(out)))
+    return out
+
+
 def encode_many(seqs, k):
     out = np.zeros((len(seqs), key_limbs(k)), dtype=np.uint64)
     for i, s in enumerate(seqs):
@@ -202,7 +227,7 @@ class TSXHashMapHIP:
     """
 
     def __init__(self, iL, iStorageBits, iK, iThreads=0, hash_seed=1, overflow_l=0, device=0, shard_bits=0,
-                 shard_index=0):
+                 shard_index=0, canonical=False):
         self._h = ctypes.c_void_p()
         self._lib = lib()
         _check(self._lib.tsx_hip_create_shard(ctypes.byref(self._h), iK, iL, iStorageBits, overflow_l,
@@ -210,6 +235,17 @@ class TSXHashMapHIP:
         self.layout = Layout()
         _check(self._lib.tsx_hip_get_layout(self._h, ctypes.byref(self.layout)))
         self.k, self.l, self.wk, self.device = iK, iL, self.layout.key_limbs, device
+        if canonical:
+            self.set_canonical(True)
+
+    @property
+    def canonical(self):
+        """True when x and its reverse complement share one counter (tsx_hip_set_canonical)."""
+        return self._lib.tsx_hip_canonical(self.handle) == 1
+
+    def set_canonical(self, on=True):
+        """Canonical counting on or off; an empty table only (just created or after clear())."""
+        _check(self._lib.tsx_hip_set_canonical(self.handle, 1 if on else 0))
 
     def close(self):
         h = getattr(self, "_h", None)
@@ -399,7 +435,8 @@ class TSXHashMapHIPGroup:
     into record shards, every GPU counts its own, the tables are merged (comm "rccl": RCCL, one GPU per rank; "copy":
     device copies, ranks may share a GPU), lookups go to the owner of each k-mer."""
 
-    def __init__(self, gpus, iL, iStorageBits, iK, hash_seed=1, devices=None, comm="rccl", exchange="merge"):
+    def __init__(self, gpus, iL, iStorageBits, iK, hash_seed=1, devices=None, comm="rccl", exchange="merge",
+                 canonical=False):
         self._lib = lib()
         self._h = ctypes.c_void_p()
         dv = (ctypes.c_int * gpus)(*devices) if devices is not None else None
@@ -407,6 +444,9 @@ class TSXHashMapHIPGroup:
                                             {"rccl": 0, "copy": 1}[comm])
         self._check(rc)
         self.k, self.wk, self.gpus = iK, key_limbs(iK), gpus
+        if canonical:   # (the minimizer exchange refuses it)
+            self._check(self._lib.tsx_hip_group_set_canonical(self._h, 1))
+        self.canonical = bool(canonical)
         if exchange != "merge":      # "mini": the minimizer exchange (20 <= k <= 32), nothing is merged afterwards
             self._check(self._lib.tsx_hip_group_set_exchange(self._h, {"merge": 0, "mini": 1}[exchange]))
         self.exchange = exchange

@@ -144,6 +144,88 @@ __device__ __forceinline__ void hash_apply(const TableParams &p, LutPtr lut, con
     }
 }
 
+// Canonical counting (tsx_hip_set_canonical): a k-mer x and its reverse complement rc(x) share one counter.  The
+// key of the pair is min(h(x), h(rc x)) as a WK-limb number (h is a bijection, so that is one representative per
+// pair); what a dump reports is the lexicographically smaller of the two k-mers (A < C < G < T, base 0 first).
+// The complement works on the 2-bit code (c -> 3 - c), whatever byte produced it.
+__host__ __device__ __forceinline__ uint64_t reverse_bases64(uint64_t v) {   // base i of 32 -> base 31 - i
+    v = __builtin_bitreverse64(v);
+    return ((v >> 1) & 0x5555555555555555ULL) | ((v & 0x5555555555555555ULL) << 1);
+}
+// rc(x) for a k-mer of n = 2k bits in WK limbs (UBigInt layout: base i in bits 2i, 2i+1).
+template <int WK>
+__host__ __device__ __forceinline__ void revcomp(const uint64_t (&x)[WK], int n, uint64_t (&r)[WK]) {
+    uint64_t y[WK];
+#pragma unroll
+    for (int t = 0; t < WK; ++t) y[t] = ~reverse_bases64(x[WK - 1 - t]);
+    const int s = 64 * WK - n;   // 0 .. 62
+#pragma unroll
+    for (int t = 0; t < WK; ++t) {
+        uint64_t v = y[t];
+        if (s) v = (y[t] >> s) | ((t + 1 < WK) ? (y[t + 1] << (64 - s)) : 0ULL);
+        r[t] = v;
+    }
+    r[WK - 1] &= (n & 63) ? ((1ULL << (n & 63)) - 1ULL) : ~0ULL;
+}
+// a < b as WK-limb numbers (the order of canonical keys)
+template <int WK>
+__host__ __device__ __forceinline__ bool key_less(const uint64_t (&a)[WK], const uint64_t (&b)[WK]) {
+    bool lt = false, eq = true;
+#pragma unroll
+    for (int t = WK - 1; t >= 0; --t) {
+        lt = lt || (eq && a[t] < b[t]);
+        eq = eq && a[t] == b[t];
+    }
+    return lt;
+}
+// h = min(h, hr)
+template <int WK>
+__host__ __device__ __forceinline__ void key_min(uint64_t (&h)[WK], const uint64_t (&hr)[WK]) {
+    const bool take = key_less<WK>(hr, h);
+#pragma unroll
+    for (int t = 0; t < WK; ++t) h[t] = take ? hr[t] : h[t];
+}
+// x = the lexicographically smaller of x and rc(x): the first base (from base 0) where they differ decides.
+template <int WK>
+__host__ __device__ __forceinline__ void lex_canonical(uint64_t (&x)[WK], int n) {
+    uint64_t r[WK];
+    revcomp<WK>(x, n, r);
+    bool decided = false, take = false;
+#pragma unroll
+    for (int t = 0; t < WK; ++t) {
+        const uint64_t d = x[t] ^ r[t];
+        if (!decided && d) {
+            const int b = __builtin_ctzll(d) & ~1;
+            take = ((r[t] >> b) & 3ULL) < ((x[t] >> b) & 3ULL);
+            decided = true;
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < WK; ++t) x[t] = take ? r[t] : x[t];
+}
+
+// The key a k-mer is counted under: h(x), or in canonical mode min(h(x), h(rc x)).
+template <bool CANON, int WK, typename LutPtr>
+__device__ __forceinline__ void hash_key(const TableParams &p, LutPtr lut, const uint64_t (&x)[WK], uint64_t (&h)[WK]) {
+    hash_apply<WK>(p, lut, x, h);
+    if constexpr (CANON) {
+        uint64_t r[WK], hr[WK];
+        revcomp<WK>(x, p.n, r);
+        hash_apply<WK>(p, lut, r, hr);
+        key_min<WK>(h, hr);
+    }
+}
+
+// The mirror roll (canonical walks, one-limb keys): the reverse complement of the next window is
+// rc(x') = comp(in) + z^2 (rc(x) - comp(out) z^(2k-2)), so h(rc x') = z^2 h(rc x) + c comp(in) - c comp(out) z^2k:
+// a shift the other way and one lookup in the 64-entry table p.roll[MROLL1_AT + (top two bits of h(rc x) | out << 2 |
+// in << 4)] (tsxcount_hip.hip: make_mapping).  idx is the index of the forward roll, whose out / in fields it reuses.
+// Multi-limb keys keep their mirror table at p.roll + 64 * WK.
+static constexpr int MROLL1_AT = 64 + 256;   // behind the forward roll and the 4-bit-group LUT
+__device__ __forceinline__ uint64_t mirror_step(const TableParams &p, const uint64_t *s_mroll, uint64_t hr, uint32_t idx) {
+    return ((hr << 2) & p.top_mask) ^ s_mroll[((uint32_t)(hr >> (p.n - 2)) & 3u) | (idx & 60u)];
+}
+
 // Secondary (count overflow) array: open addressing keyed by slot position.
 __device__ inline void sec_add(const TableParams &p, uint64_t pos, uint64_t carry) {
     pos += p.pos_base;

@@ -203,7 +203,8 @@ __device__ __forceinline__ bool kmer_eq(const uint64_t (&a)[WK], const uint64_t 
 //      table;
 //   4. after a barrier the claimant of each dedup slot issues ONE global
 //      insert carrying the slot's total.
-template <int WK>
+// CANON (canonical counting): the key of a k-mer is min(h(x), h(rc x)); the LDS dedup still merges equal k-mers only.
+template <int WK, bool CANON = false>
 __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableParams p, const uint8_t *buf, uint64_t n,
                                                          uint64_t own_end, int head_open,
                                                          const uint32_t *tile_line, uint64_t ntiles, int dbg) {
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableP
                 const uint32_t runlen = (above ? (uint32_t)__builtin_ctzll(above) : (uint32_t)(63 - lane)) + 1u;
                 added += valid ? 1ULL : 0ULL;
                 if (leader) {
-                    hash_apply<WK>(p, (const uint64_t *)s_lut, x, hk[j]);
+                    hash_key<CANON, WK>(p, (const uint64_t *)s_lut, x, hk[j]);
                     uint32_t slot = (uint32_t)(mix64(hk[j][0] ^ (WK > 1 ? hk[j][WK - 1] : 0)) >> 40) & (DSLOTS - 1);
                     slot_of[j] = -2; direct_cnt[j] = runlen;
                     for (int pr = 0; pr < DPROBES; ++pr) {
@@ -496,6 +497,9 @@ __global__ __launch_bounds__(NT, 5) void strip_desc_kernel(TableParams p, const 
 // walk_log_kernel: the walk into a key log, fed from strip descriptions (strip_desc_kernel above) -- one description per lane, every lane busy, no barrier after the set-up (a wave reads descriptor
 // regions w, w + G, ... and appends to its own log region; the histogram is the wave's).  Used where the keys must
 // come out as a packed log: sharded scans (histogram by owner) and tables that need one radix level.
+// CANON (canonical counting): the hash of the reverse complement rolls alongside (mirror_step) and the key of a
+// position is the smaller of the two.
+template <bool CANON = false>
 __global__ __launch_bounds__(NT, 4) void walk_log_kernel(TableParams p, const uint4 *desc, uint64_t desc_cap,
                                                          const unsigned long long *desc_cnt, uint32_t nregions, int dbg,
                                                          uint64_t *log, uint64_t log_cap, unsigned long long *log_cnt,
@@ -510,7 +514,8 @@ __global__ __launch_bounds__(NT, 4) void walk_log_kernel(TableParams p, const ui
     __shared__ uint64_t s_hot_key[(NT / 64) * HOT_N];
     __shared__ uint32_t s_hot_cnt[(NT / 64) * HOT_N];
     __shared__ uint32_t s_hist[(NT / 64) * 512];  // fan-out <= 512
-    __shared__ uint64_t s_roll[64];
+    __shared__ uint64_t s_roll[CANON ? 128 : 64];   // CANON: the mirror roll behind the forward one
+    uint64_t *const s_mroll = s_roll + 64;
     __shared__ uint64_t s_homh[4];
     extern __shared__ uint64_t s_lut[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -518,10 +523,17 @@ __global__ __launch_bounds__(NT, 4) void walk_log_kernel(TableParams p, const ui
     for (int i = tid; i < lut_words; i += NT) s_lut[i] = p.lut[i];
     for (int i = tid; i < (NT / 64) * 512; i += NT) s_hist[i] = 0;
     if (tid < 64) s_roll[tid] = p.roll[tid];
+    if (CANON && tid < 64) s_mroll[tid] = p.roll[MROLL1_AT + tid];
     if (tid < 4) {
         const uint64_t x[1] = {(0x5555555555555555ULL * (uint64_t)tid) & p.top_mask};
         uint64_t hh[1];
         hash_apply<1>(p, p.lut, x, hh);
+        if constexpr (CANON) {   // A^k and T^k are one key, and so are C^k and G^k
+            const uint64_t xc[1] = {(0x5555555555555555ULL * (uint64_t)(3 - tid)) & p.top_mask};
+            uint64_t hc[1];
+            hash_apply<1>(p, p.lut, xc, hc);
+            hh[0] = min(hh[0], hc[0]);
+        }
         s_homh[tid] = hh[0];
     }
     if (tid < (NT / 64) * HOT_N) { s_hot_key[tid] = 0; s_hot_cnt[tid] = 0; }
@@ -570,12 +582,18 @@ __global__ __launch_bounds__(NT, 4) void walk_log_kernel(TableParams p, const ui
                 const uint32_t vw = (t < 2u) ? d2.z : d2.w;
                 vm = (vw >> ((t & 1u) * 16u)) & 0xFFFFu;
             }
-            uint64_t h = 0;
+            uint64_t h = 0, hr = 0;
             if (vm) {
                 const uint64_t x[1] = {((uint64_t)cw0 | ((uint64_t)cw1 << 32)) & p.top_mask};
                 uint64_t hh[1];
                 hash_apply<1>(p, (const uint64_t *)s_lut, x, hh);
                 h = hh[0];
+                if constexpr (CANON) {
+                    uint64_t r[1];
+                    revcomp<1>(x, p.n, r);
+                    hash_apply<1>(p, (const uint64_t *)s_lut, r, hh);
+                    hr = hh[0];
+                }
             }
             uint32_t inc;
             {
@@ -646,6 +664,7 @@ __global__ __launch_bounds__(NT, 4) void walk_log_kernel(TableParams p, const ui
                         for (int j = 0; j < 8; ++j) {
                             const uint32_t idx = ((uint32_t)h & 3u) | (__builtin_amdgcn_ubfe(cw0, 2u * j, 2u) << 2) |
                                                  (__builtin_amdgcn_ubfe(inc, 2u * j, 2u) << 4);
+                            if constexpr (CANON) hr = mirror_step(p, s_mroll, hr, idx);
                             h = (h >> 2) ^ s_roll[idx];
                         }
                     }
@@ -654,10 +673,11 @@ __global__ __launch_bounds__(NT, 4) void walk_log_kernel(TableParams p, const ui
                 uint64_t hs[8];
     #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    hs[j] = h;
+                    hs[j] = CANON ? min(h, hr) : h;
                     if (j0 + j < 15) {
                         const uint32_t idx = ((uint32_t)h & 3u) | (__builtin_amdgcn_ubfe(cw0, 2u * (j0 + j), 2u) << 2) |
                                              (__builtin_amdgcn_ubfe(inc, 2u * (j0 + j), 2u) << 4);
+                        if constexpr (CANON) hr = mirror_step(p, s_mroll, hr, idx);
                         h = (h >> 2) ^ s_roll[idx];
                     }
                 }
@@ -859,7 +879,8 @@ __global__ __launch_bounds__(NT, 4) void strip_desc_wide_kernel(TableParams p, c
     }
 }
 
-template <int WK>
+// CANON: as walk_log_kernel, with the WK-limb mirror roll.
+template <int WK, bool CANON = false>
 __global__ __launch_bounds__(NT, 2) void walk_log_wide_kernel(TableParams p, const uint4 *desc, uint64_t desc_cap,
                                                               const unsigned long long *desc_cnt, uint32_t nregions, int dbg,
                                                               uint64_t *log, uint64_t log_cap, unsigned long long *log_cnt,
@@ -870,7 +891,8 @@ __global__ __launch_bounds__(NT, 2) void walk_log_wide_kernel(TableParams p, con
     __shared__ uint64_t s_hot_key[(NT / 64) * HOT_N * WK];
     __shared__ uint32_t s_hot_cnt[(NT / 64) * HOT_N];
     __shared__ uint32_t s_hist[(NT / 64) * 512];
-    __shared__ uint64_t s_roll[64 * WK];
+    __shared__ uint64_t s_roll[CANON ? 128 * WK : 64 * WK];   // CANON: the mirror roll behind the forward one
+    uint64_t *const s_mroll = s_roll + 64 * WK;
     __shared__ uint64_t s_homh[4 * WK];
     extern __shared__ uint64_t s_lut[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -878,12 +900,15 @@ __global__ __launch_bounds__(NT, 2) void walk_log_wide_kernel(TableParams p, con
     for (int i = tid; i < lut_words; i += NT) s_lut[i] = p.lut[i];
     for (int i = tid; i < (NT / 64) * 512; i += NT) s_hist[i] = 0;
     for (int i = tid; i < 64 * WK; i += NT) s_roll[i] = p.roll[i];
+    if constexpr (CANON)
+        for (int i = tid; i < 64 * WK; i += NT) s_mroll[i] = p.roll[64 * WK + i];
+    const uint32_t tsh = (uint32_t)(p.n - 2 - 64 * (WK - 1));   // the top two bits of a key: bits tsh, tsh + 1 of limb WK - 1
     if (tid < 4) {
         uint64_t x[WK], hh[WK];
 #pragma unroll
         for (int t = 0; t < WK; ++t) x[t] = 0x5555555555555555ULL * (uint64_t)tid;
         x[WK - 1] &= p.top_mask;
-        hash_apply<WK>(p, p.lut, x, hh);
+        hash_key<CANON, WK>(p, p.lut, x, hh);
 #pragma unroll
         for (int t = 0; t < WK; ++t) s_homh[tid * WK + t] = hh[t];
     }
@@ -911,23 +936,32 @@ __global__ __launch_bounds__(NT, 2) void walk_log_wide_kernel(TableParams p, con
                 }
             }
             const uint32_t cw0 = w[0], inc = w[2 * WK], vm = w[2 * WK + 1];
-            uint64_t h[WK];
+            uint64_t h[WK], hr[WK];
 #pragma unroll
-            for (int t = 0; t < WK; ++t) h[t] = 0;
+            for (int t = 0; t < WK; ++t) { h[t] = 0; hr[t] = 0; }
             if (vm) {
                 uint64_t x[WK];
 #pragma unroll
                 for (int t = 0; t < WK; ++t) x[t] = (uint64_t)w[2 * t] | ((uint64_t)w[2 * t + 1] << 32);
                 hash_apply<WK>(p, (const uint64_t *)s_lut, x, h);
+                if constexpr (CANON) {
+                    uint64_t r[WK];
+                    revcomp<WK>(x, p.n, r);
+                    hash_apply<WK>(p, (const uint64_t *)s_lut, r, hr);
+                }
             }
             uint32_t homcnt = 0;   // four 8-bit counters: homopolymer k-mers of base b seen in this strip
             for (uint32_t j = 0; j < 16; ++j) {
                 const bool valid = (vm >> j) & 1u;
                 const uint32_t ob = __builtin_amdgcn_ubfe(cw0, 2u * j, 2u);
-                bool hom = valid && h[0] == s_homh[ob * WK];
+                uint64_t kc[WK];   // the key of this position
+#pragma unroll
+                for (int t = 0; t < WK; ++t) kc[t] = h[t];
+                if constexpr (CANON) key_min<WK>(kc, hr);
+                bool hom = valid && kc[0] == s_homh[ob * WK];
                 if (hom) {
     #pragma unroll
-                    for (int t = 1; t < WK; ++t) hom &= (h[t] == s_homh[ob * WK + t]);
+                    for (int t = 1; t < WK; ++t) hom &= (kc[t] == s_homh[ob * WK + t]);
                 }
                 homcnt += hom ? (1u << (8u * ob)) : 0u;
                 const bool em = valid && !hom;
@@ -938,12 +972,12 @@ __global__ __launch_bounds__(NT, 2) void walk_log_wide_kernel(TableParams p, con
                         if (at < cap32) {
                             uint64_t *o = my_log + (uint64_t)at * RW;
     #pragma unroll
-                            for (int t = 0; t < RW; ++t) o[t] = (t < WK) ? h[t < WK ? t : 0] : 0ULL;
-                            atomicAdd(&my_hist[(uint32_t)(h[0] >> hist_shift) & (hist_nb - 1)], 1u);
+                            for (int t = 0; t < RW; ++t) o[t] = (t < WK) ? kc[t < WK ? t : 0] : 0ULL;
+                            atomicAdd(&my_hist[(uint32_t)(kc[0] >> hist_shift) & (hist_nb - 1)], 1u);
                         } else if (!(dbg & 1)) {
                             uint64_t rec[RW];
     #pragma unroll
-                            for (int t = 0; t < RW; ++t) rec[t] = (t < WK) ? h[t < WK ? t : 0] : 0ULL;
+                            for (int t = 0; t < RW; ++t) rec[t] = (t < WK) ? kc[t < WK ? t : 0] : 0ULL;
                             defer_append<RW>(pk, rec, 1);   // region full
                         }
                     }
@@ -951,6 +985,16 @@ __global__ __launch_bounds__(NT, 2) void walk_log_wide_kernel(TableParams p, con
                 }
                 if (j < 15) {
                     const uint32_t idx = ((uint32_t)h[0] & 3u) | (ob << 2) | (__builtin_amdgcn_ubfe(inc, 2u * j, 2u) << 4);
+                    if constexpr (CANON) {   // the mirror roll: h(rc x') = z^2 h(rc x) + ... (mirror_step, tsx_device.h)
+                        const uint32_t midx = ((uint32_t)(hr[WK - 1] >> tsh) & 3u) | (idx & 60u);
+    #pragma unroll
+                        for (int t = WK - 1; t >= 0; --t) {
+                            uint64_t v = hr[t] << 2;
+                            if (t > 0) v |= hr[t - 1] >> 62;
+                            if (t == WK - 1) v &= p.top_mask;
+                            hr[t] = v ^ s_mroll[midx * WK + t];
+                        }
+                    }
     #pragma unroll
                     for (int t = 0; t < WK; ++t) {
                         uint64_t v = h[t] >> 2;
@@ -1004,7 +1048,7 @@ __global__ __launch_bounds__(NT, 2) void walk_log_wide_kernel(TableParams p, con
 
 
 // addKmer for encoded k-mers already on the device (API batches, merge inserts).
-template <int WK>
+template <int WK, bool CANON = false>
 __global__ __launch_bounds__(NT) void add_kmers_kernel(TableParams p, const uint64_t *kmers,
                                                        const uint64_t *counts, uint64_t n) {
     unsigned long long added = 0;
@@ -1015,7 +1059,7 @@ __global__ __launch_bounds__(NT) void add_kmers_kernel(TableParams p, const uint
         x[WK - 1] &= p.top_mask;
         const uint64_t d = counts ? counts[i] : 1ULL;
         if (d == 0) continue;
-        hash_apply<WK>(p, p.lut, x, h);
+        hash_key<CANON, WK>(p, p.lut, x, h);
         if (p.lg != p.l && owner_shard<WK>(p, h) != p.shard) continue;  // another GPU's slot range
         insert_key<WK>(p, h, d);
         added += d;
@@ -1024,7 +1068,7 @@ __global__ __launch_bounds__(NT) void add_kmers_kernel(TableParams p, const uint
     if ((threadIdx.x & 63) == 0 && added) atomicAdd(&p.stats[ST_KMERS], added);
 }
 
-template <int WK>
+template <int WK, bool CANON = false>
 __global__ __launch_bounds__(NT) void get_counts_kernel(TableParams p, const uint64_t *kmers, uint64_t n,
                                                         uint64_t *out, uint64_t *pos_out) {
     for (uint64_t i = (uint64_t)blockIdx.x * NT + threadIdx.x; i < n; i += (uint64_t)gridDim.x * NT) {
@@ -1032,7 +1076,7 @@ __global__ __launch_bounds__(NT) void get_counts_kernel(TableParams p, const uin
 #pragma unroll
         for (int t = 0; t < WK; ++t) x[t] = kmers[i * WK + t];
         x[WK - 1] &= p.top_mask;
-        hash_apply<WK>(p, p.lut, x, h);
+        hash_key<CANON, WK>(p, p.lut, x, h);
         out[i] = lookup_key<WK>(p, h, pos_out ? pos_out + i : nullptr);
     }
 }
@@ -1122,7 +1166,8 @@ __device__ __forceinline__ int owner_of(const uint64_t *x, int wk, int nranks) {
 // mode 1: write k-mer + count at seg_cursor[owner]++ (cursors preset to segment starts)
 // One atomic per (wave, owner present in the wave): the lanes that share an owner are found
 // with ballots and take consecutive places behind the leader's atomicAdd.
-template <int WK>
+// CANON: the k-mer reported is the lexicographically smaller strand of the stored pair.
+template <int WK, bool CANON = false>
 __global__ __launch_bounds__(NT) void dump_kernel(TableParams p, int nranks, int mode, uint64_t *kmers_out,
                                                   uint64_t *counts_out, uint64_t cap,
                                                   unsigned long long *seg, uint64_t slot_lo, uint64_t slot_hi) {
@@ -1137,6 +1182,7 @@ __global__ __launch_bounds__(NT) void dump_kernel(TableParams p, int nranks, int
         int own = 0;
         if (occ) {
             slot_to_kmer<WK>(p, pos, x, c);
+            if constexpr (CANON) lex_canonical<WK>(x, p.n);
             own = (nranks > 1) ? owner_of(x, WK, nranks) : 0;
         }
         uint64_t todo = __ballot(occ);

@@ -388,6 +388,7 @@ extern "C" int tsx_hip_group_set_exchange(tsx_hip_group *g, int mode) {
     if (!g || (mode != 0 && mode != 1)) return TSX_HIP_EINVAL;
     if (mode == 1) {
         if (g->n > 16) { g_multi_error = "minimizer exchange: at most 16 GPUs"; return TSX_HIP_EINVAL; }
+        if (tsx_hip_canonical(g->maps[0]) == 1) { g_multi_error = "minimizer exchange: no canonical counting (owners are strand-dependent)"; return TSX_HIP_EINVAL; }
         for (tsx_hip_map *m : g->maps)
             if (!tsx_hip_mini_supported(m)) { g_multi_error = "minimizer exchange: 20 <= k <= 32 and a table split by two radix levels"; return TSX_HIP_EINVAL; }
     }
@@ -395,6 +396,16 @@ extern "C" int tsx_hip_group_set_exchange(tsx_hip_group *g, int mode) {
     return TSX_HIP_OK;
 }
 extern "C" int tsx_hip_group_exchange(const tsx_hip_group *g) { return g ? g->exchange : 0; }
+
+// Canonical counting on every rank's table.  The merge dumps the canonical strand of every pair and re-inserts it with
+// tsx_hip_add_kmers_device, and lookups route the canonical strand (tsx_hip_owner_host): both work as they are.
+extern "C" int tsx_hip_group_set_canonical(tsx_hip_group *g, int on) {
+    if (!g) return TSX_HIP_EINVAL;
+    if (on && g->exchange == 1) { g_multi_error = "canonical counting: not with the minimizer exchange"; return TSX_HIP_EINVAL; }
+    for (tsx_hip_map *m : g->maps)
+        if (tsx_hip_set_canonical(m, on) != TSX_HIP_OK) { g_multi_error = "canonical counting: the tables must be empty"; return TSX_HIP_EINVAL; }
+    return TSX_HIP_OK;
+}
 
 namespace {
 struct MiniShared {

@@ -642,7 +642,9 @@ __global__ __launch_bounds__(256) void desc_pack_kernel(const uint4 *desc, uint6
 // window by the 4-bit-group LUT, 15 rolls, the keys into the level-1 rings, bursts to the workgroup's sub-lists.
 // A batch = 512 strips = up to 8192 keys: four flushes per batch (one per four positions).  Workgroup g takes
 // the descriptor regions g, g + G, ... (a region = what one wave of strip_desc_kernel wrote).
-template <int NT>   // 512 threads, two workgroups per CU (up to 256 level-1 lists); 1024 threads where 512 lists leave room for one
+// CANON (canonical counting): the hash of the reverse complement rolls alongside (mirror_step, tsx_device.h) and the
+// key of a position is the smaller of the two; the homopolymer keys are those of the pairs A/T and C/G.
+template <int NT, bool CANON = false>   // 512 threads, two workgroups per CU (up to 256 level-1 lists); 1024 threads where 512 lists leave room for one
 __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const uint4 *desc, uint64_t desc_cap,
                                                             const unsigned long long *desc_cnt, uint32_t nregions, int dbg,
                                                             uint64_t *dst, uint64_t dst_cap, unsigned long long *dst_cnt,
@@ -657,8 +659,9 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
     constexpr int HOT_N = 8;
     __shared__ uint64_t s_hot_key[(NT / 64) * HOT_N];
     __shared__ uint32_t s_hot_cnt[(NT / 64) * HOT_N];
-    __shared__ uint64_t s_roll[64];
+    __shared__ uint64_t s_roll[CANON ? 128 : 64];   // CANON: the mirror roll behind the forward one
     __shared__ uint64_t s_lut4[256];
+    uint64_t *const s_mroll = s_roll + 64;
     __shared__ uint64_t s_homh[4];
     __shared__ uint32_t s_njobs[2];
     __shared__ uint32_t s_ovn;
@@ -688,10 +691,17 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
     };
     if (tid < 64) s_roll[tid] = p.roll[tid];
     if (tid < 256) s_lut4[tid] = p.roll[64 + tid];
+    if (CANON && tid < 64) s_mroll[tid] = p.roll[MROLL1_AT + tid];
     if (tid < 4) {
         const uint64_t x = (0x5555555555555555ULL * (uint64_t)tid) & p.top_mask;
         uint64_t hh = 0;
         for (int grp = 0; grp < 16; ++grp) hh ^= p.roll[64 + grp * 16 + ((x >> (4 * grp)) & 15u)];
+        if constexpr (CANON) {   // A^k and T^k are one key, and so are C^k and G^k
+            const uint64_t xc = (0x5555555555555555ULL * (uint64_t)(3 - tid)) & p.top_mask;
+            uint64_t hc = 0;
+            for (int grp = 0; grp < 16; ++grp) hc ^= p.roll[64 + grp * 16 + ((xc >> (4 * grp)) & 15u)];
+            hh = min(hh, hc);
+        }
         s_homh[tid] = hh;
     }
     if (tid < (NT / 64) * HOT_N) { s_hot_key[tid] = 0; s_hot_cnt[tid] = 0; }
@@ -825,13 +835,19 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
                 vm = (vw >> ((t & 1u) * 16u)) & 0xFFFFu;
             }
             const bool wave_has = __ballot(vm != 0u) != 0ULL;   // only the last batch of a region has idle waves
-            uint64_t h = 0;
+            uint64_t h = 0, hr = 0;
             uint32_t inc = 0, single = 0;
             if (wave_has) {
                 const uint64_t lo = (uint64_t)cw0 | ((uint64_t)cw1 << 32), hi = cw2;
                 if (vm) {
                     const uint64_t x = lo & p.top_mask;
                     for (uint32_t grp = 0; grp < ngrp; ++grp) h ^= s_lut4[grp * 16u + ((uint32_t)(x >> (4u * grp)) & 15u)];
+                    if constexpr (CANON) {
+                        const uint64_t xa[1] = {x};
+                        uint64_t r[1];
+                        revcomp<1>(xa, p.n, r);
+                        for (uint32_t grp = 0; grp < ngrp; ++grp) hr ^= s_lut4[grp * 16u + ((uint32_t)(r[0] >> (4u * grp)) & 15u)];
+                    }
                 }
                 {
                     const uint32_t o = 2u * k, ws = o >> 5, sh = o & 31u;
@@ -898,10 +914,11 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
                     uint64_t hs[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        hs[j] = h;
+                        hs[j] = CANON ? min(h, hr) : h;
                         if (j0 + j < 15) {
                             const uint32_t idx = ((uint32_t)h & 3u) | (__builtin_amdgcn_ubfe(cw0, 2u * (j0 + j), 2u) << 2) |
                                                  (__builtin_amdgcn_ubfe(inc, 2u * (j0 + j), 2u) << 4);
+                            if constexpr (CANON) hr = mirror_step(p, s_mroll, hr, idx);
                             h = (h >> 2) ^ s_roll[idx];
                         }
                     }

@@ -65,6 +65,10 @@ struct tsx_hip_map {
     size_t ovq_queues = 0;
     uint64_t roll[64] = {0};             // one-limb keys: sliding-window hash update table
     std::vector<uint64_t> roll_wide;     // multi-limb keys: the same, key_limbs words per entry
+    uint64_t mroll[64] = {0};            // the mirror roll of the reverse complement's hash (canonical walks)
+    std::vector<uint64_t> mroll_wide;
+    bool canon = false;                  // canonical counting (tsx_hip_set_canonical)
+    bool used = false;                   // something was inserted since the map was created or cleared
     // FASTQ scratch
     uint32_t *d_tile = nullptr; uint64_t tile_cap = 0;
     uint32_t *d_carry = nullptr;
@@ -294,6 +298,17 @@ static int make_mapping(tsx_hip_map *m) {
             const int hb = idx & 3, out = (idx >> 2) & 3, in = (idx >> 4) & 3;
             m->roll[idx] = (A[out] >> 2) ^ E[(hb ^ (int)(A[out] & 3ULL)) & 3] ^ C[in];
         }
+        // mirror roll: h(rc x') = z^2 h(rc x) + c comp(in) - c comp(out) z^n, indexed by the top two bits of h(rc x)
+        // (which z^2 pushes out: T[e] = e z^n reduced), out and in
+        uint64_t T[4], D[4];
+        for (int v = 0; v < 4; ++v) {
+            T[v] = ((v & 1) ? plow : 0ULL) ^ ((v & 2) ? gf_mulz(plow, plow, n) : 0ULL);
+            D[v] = gf_mulz(gf_mulz(C[v], plow, n), plow, n);
+        }
+        for (int idx = 0; idx < 64; ++idx) {
+            const int hb = idx & 3, out = (idx >> 2) & 3, in = (idx >> 4) & 3;
+            m->mroll[idx] = T[hb] ^ D[3 - out] ^ A[3 - in];
+        }
     } else {
         const uint8_t *e = GF_POLY_EXP[n / 2 - 1];
         Big plow = big_zero();
@@ -334,6 +349,23 @@ static int make_mapping(tsx_hip_map *m) {
             big_xor(r, E[(hb ^ (int)(A[out].w[0] & 3ULL)) & 3]);
             big_xor(r, C[in]);
             for (int t = 0; t < wk; ++t) m->roll_wide[(size_t)idx * wk + t] = r.w[t];
+        }
+        // mirror roll, as for one-limb keys
+        Big T[4], D[4];
+        const Big plowz = big_mulz(plow, plow, n);
+        for (int v = 0; v < 4; ++v) {
+            T[v] = big_zero();
+            if (v & 1) big_xor(T[v], plow);
+            if (v & 2) big_xor(T[v], plowz);
+            D[v] = big_mulz(big_mulz(C[v], plow, n), plow, n);
+        }
+        m->mroll_wide.assign((size_t)64 * wk, 0);
+        for (int idx = 0; idx < 64; ++idx) {
+            const int hb = idx & 3, out = (idx >> 2) & 3, in = (idx >> 4) & 3;
+            Big r = T[hb];
+            big_xor(r, D[3 - out]);
+            big_xor(r, A[3 - in]);
+            for (int t = 0; t < wk; ++t) m->mroll_wide[(size_t)idx * wk + t] = r.w[t];
         }
     }
     // Inverse by Gauss-Jordan on [A | I], A[r][c] = coefficient of input bit c in output bit r
@@ -522,10 +554,13 @@ extern "C" int tsx_hip_create_shard(tsx_hip_map **out, int k, int l, int storage
                     lut4[grp * 16 + v] = y;
                 }
         }
-        HIP_TRY_C(hipMalloc((void **)&m->d_roll, bytes + lut4.size() * 8));
+        // the mirror roll of the canonical walks behind both (MROLL1_AT / 64 * key_limbs words in, tsx_device.h)
+        const void *msrc = (p.wk == 1) ? (const void *)m->mroll : (const void *)m->mroll_wide.data();
+        HIP_TRY_C(hipMalloc((void **)&m->d_roll, 2 * bytes + lut4.size() * 8));
         HIP_TRY_C(hipMemcpy(m->d_roll, src, bytes, hipMemcpyHostToDevice));
         if (!lut4.empty())
             HIP_TRY_C(hipMemcpy(m->d_roll + 64, lut4.data(), lut4.size() * 8, hipMemcpyHostToDevice));
+        HIP_TRY_C(hipMemcpy(m->d_roll + 64 * p.wk + lut4.size(), msrc, bytes, hipMemcpyHostToDevice));
         p.roll = m->d_roll;
     }
     rc = clear_impl(m, true);
@@ -595,6 +630,7 @@ static int clear_impl(tsx_hip_map *m, bool full) {
     HIP_TRY(hipMemsetAsync(m->p.seg_dirty, 0, (size_t)(m->lay.slots >> m->p.S), m->stream));
     HIP_TRY(hipEventRecord(m->clear_ev, m->stream));
     m->clear_ev_set = true;
+    m->used = false;   // (the counting mode stays)
     return TSX_HIP_OK;
 }
 
@@ -609,6 +645,38 @@ static int ensure_zeroed(tsx_hip_map *m, hipStream_t st) {
 extern "C" int tsx_hip_clear(tsx_hip_map *m) {
     if (!m) return TSX_HIP_EINVAL;
     return clear_impl(m, false);
+}
+
+// Canonical counting is chosen per table before anything is inserted: a table that mixed both modes would
+// hold a k-mer under two keys.  A table sharded by slot range is filled by the exchanges, which have no canonical form.
+extern "C" int tsx_hip_set_canonical(tsx_hip_map *m, int on) {
+    if (!m || m->used || (on && m->p.lg != m->p.l)) return TSX_HIP_EINVAL;
+    m->canon = on != 0;
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_canonical(const tsx_hip_map *m) {
+    if (!m) return TSX_HIP_EINVAL;
+    return m->canon ? 1 : 0;
+}
+
+extern "C" int tsx_hip_canonical_host(int k, const uint64_t *kmers, size_t n, uint64_t *out) {
+    if (k < 1 || k > 127 || ((!kmers || !out) && n)) return TSX_HIP_EINVAL;
+    const int wk = (2 * k + 63) / 64;
+    const uint64_t top = ((2 * k) & 63) ? ((1ULL << ((2 * k) & 63)) - 1ULL) : ~0ULL;
+    for (size_t i = 0; i < n; ++i) {
+        uint64_t x[4] = {0, 0, 0, 0};
+        for (int t = 0; t < wk; ++t) x[t] = kmers[i * wk + t];
+        x[wk - 1] &= top;
+        switch (wk) {
+            case 1: lex_canonical<1>(*reinterpret_cast<uint64_t(*)[1]>(x), 2 * k); break;
+            case 2: lex_canonical<2>(*reinterpret_cast<uint64_t(*)[2]>(x), 2 * k); break;
+            case 3: lex_canonical<3>(*reinterpret_cast<uint64_t(*)[3]>(x), 2 * k); break;
+            default: lex_canonical<4>(x, 2 * k); break;
+        }
+        for (int t = 0; t < wk; ++t) out[i * wk + t] = x[t];
+    }
+    return TSX_HIP_OK;
 }
 
 static int read_stats(tsx_hip_map *m, unsigned long long *st) {
@@ -661,6 +729,9 @@ static inline int grid_for(const tsx_hip_map *m, uint64_t work_items, int per_cu
         case 3: { constexpr int WKV = 3; CALL; } break; \
         default: { constexpr int WKV = 4; CALL; } break; \
     }
+// The kernels that make hashed keys in two forms: CANV = canonical counting (tsx_hip_set_canonical) or not.
+#define DISPATCH_CANON(m, CALL)                                                    \
+    if ((m)->canon) { constexpr bool CANV = true; CALL; } else { constexpr bool CANV = false; CALL; }
 
 // ---- partitioned path: plan, scratch, launches ------------------------------------
 struct PartPlan {
@@ -840,6 +911,10 @@ static int plan_partition(tsx_hip_map *m, uint64_t maxrec, int g, bool own_log, 
         HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
         HIP_TRY(hipFuncSetAttribute((const void *)walk_log_wide_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10));
         HIP_TRY(hipFuncSetAttribute((const void *)walk_log_wide_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10));
+        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<SP_NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+        HIP_TRY(hipFuncSetAttribute((const void *)walk_log_wide_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10));
+        HIP_TRY(hipFuncSetAttribute((const void *)walk_log_wide_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10));
         m->attr_done = true;
     }
     return TSX_HIP_OK;
@@ -1124,8 +1199,9 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
     if (!use_part) {
         int rcz = ensure_zeroed(m, st);
         if (rcz != TSX_HIP_OK) return rcz;
-        DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV>), dim3(g3), dim3(NT), lut_bytes, st, m->p, d_text, n,
-                                          own_end, head_open, (const uint32_t *)m->d_tile, ntiles, m->dbg));
+        DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV>), dim3(g3), dim3(NT), lut_bytes, st,
+                                                            m->p, d_text, n, own_end, head_open, (const uint32_t *)m->d_tile,
+                                                            ntiles, m->dbg)));
         HIP_TRY(hipGetLastError());
         if (ev) for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i], st));
         return TSX_HIP_OK;
@@ -1188,16 +1264,19 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
             hipLaunchKernelGGL(strip_desc_kernel<false>, dim3(gd), dim3(NT), 0, st, pp, d_text, n, own_end, head_open,
                                (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[0], desc_cap, pl.c_log, (unsigned long long *)nullptr, lng);
             HIP_TRY(hipGetLastError());
-            if (lds > ((size_t)80 << 10))   // 512 lists: one workgroup per CU, 1024 threads
-                hipLaunchKernelGGL(walk_part_kernel<1024>, dim3(pl.G1), dim3(1024), lds, st, pp, (const uint4 *)m->d_buf[0], desc_cap,
+            if (lds > ((size_t)80 << 10)) {   // 512 lists: one workgroup per CU, 1024 threads
+                DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<1024, CANV>), dim3(pl.G1), dim3(1024), lds, st, pp,
+                                   (const uint4 *)m->d_buf[0], desc_cap,
                                    (const unsigned long long *)pl.c_log, (uint32_t)gdreg, m->dbg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
                                    (uint32_t)(p.l - pl.b1), m->d_ovq + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt + nq2, OVQ_CAP,
-                                   (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, local_fq);
-            else
-                hipLaunchKernelGGL(walk_part_kernel<SP_NT>, dim3(pl.G1), dim3(SP_NT), lds, st, pp, (const uint4 *)m->d_buf[0], desc_cap,
+                                   (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, local_fq));
+            } else {
+                DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<SP_NT, CANV>), dim3(pl.G1), dim3(SP_NT), lds, st, pp,
+                                   (const uint4 *)m->d_buf[0], desc_cap,
                                    (const unsigned long long *)pl.c_log, (uint32_t)gdreg, m->dbg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
                                    (uint32_t)(p.l - pl.b1), m->d_ovq + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt + nq2, OVQ_CAP,
-                                   (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, local_fq);
+                                   (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, local_fq));
+            }
         }
     } else if (p.wk == 1) {
         // key log form (sharded scans, one-level tables), the scan in two kernels as well: descriptions into buffer 1
@@ -1216,9 +1295,10 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
                            (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], desc_cap, m->d_desc_cnt,
                            (unsigned long long *)nullptr, 0);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(walk_log_kernel, dim3(gs), dim3(NT), lut_bytes, st, pp, (const uint4 *)m->d_buf[1], desc_cap,
+        DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_kernel<CANV>), dim3(gs), dim3(NT), lut_bytes, st, pp,
+                           (const uint4 *)m->d_buf[1], desc_cap,
                            (const unsigned long long *)m->d_desc_cnt, (uint32_t)gdreg, m->dbg, m->d_buf[0], pl.log_cap,
-                           pl.c_log, pl.d_hist, hist_nb, hist_shift, (uint64_t)0, 0, 0, (unsigned long long *)nullptr);
+                           pl.c_log, pl.d_hist, hist_nb, hist_shift, (uint64_t)0, 0, 0, (unsigned long long *)nullptr));
     } else {
         // multi-limb keys, two kernels as well: descriptions (first k-mer + entering bases + validity) into buffer 1,
         // then the walk with every lane busy
@@ -1236,9 +1316,10 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
 #define TSX_WIDE2(WKV)                                                                                                      \
         hipLaunchKernelGGL((strip_desc_wide_kernel<WKV>), dim3(gd), dim3(NT), 0, st, pp, d_text, n, own_end, head_open,      \
                            (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], desc_cap, m->d_desc_cnt);              \
-        hipLaunchKernelGGL((walk_log_wide_kernel<WKV>), dim3(gs), dim3(NT), lut_bytes, st, pp, (const uint4 *)m->d_buf[1],   \
+        DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_wide_kernel<WKV, CANV>), dim3(gs), dim3(NT), lut_bytes, st, pp,     \
+                           (const uint4 *)m->d_buf[1],                                                                       \
                            desc_cap, (const unsigned long long *)m->d_desc_cnt, (uint32_t)gdreg, m->dbg, m->d_buf[0],        \
-                           pl.log_cap, pl.c_log, pl.d_hist, hist_nb, hist_shift)
+                           pl.log_cap, pl.c_log, pl.d_hist, hist_nb, hist_shift))
         switch (p.wk) {
             case 2: TSX_WIDE2(2); break;
             case 3: TSX_WIDE2(3); break;
@@ -1279,6 +1360,8 @@ extern "C" int tsx_hip_shard_scan_window_device(tsx_hip_map *m, const void *dev_
                                                 size_t own_cap_keys, void *dev_send_counts, void *dev_hot_keys,
                                                 void *dev_hot_counts, size_t hot_cap, void *dev_hot_n,
                                                 void *dev_key_sum, void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_send || !dev_send_counts ||
         !dev_hot_keys || !dev_hot_counts || !dev_hot_n || win_off > n_total || win_len > n_total - win_off)
         return TSX_HIP_EINVAL;
@@ -1307,11 +1390,14 @@ extern "C" int tsx_hip_shard_scan_window_device(tsx_hip_map *m, const void *dev_
 extern "C" int tsx_hip_shard_scan_device(tsx_hip_map *m, const void *dev_text, size_t n, void *dev_send,
                                          size_t send_cap_keys, void *dev_send_counts, void *dev_hot_keys,
                                          void *dev_hot_counts, size_t hot_cap, void *dev_hot_n, void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     return tsx_hip_shard_scan_window_device(m, dev_text, n, 0, n, dev_send, send_cap_keys, nullptr, 0, dev_send_counts,
                                             dev_hot_keys, dev_hot_counts, hot_cap, dev_hot_n, nullptr, stream);
 }
 
 extern "C" int tsx_hip_shard_send_capacity(tsx_hip_map *m, size_t text_bytes, size_t *keys_out) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
     if (!m || !keys_out) return TSX_HIP_EINVAL;
     const uint64_t ntiles = (text_bytes + TILE - 1) / TILE;
     const int g = (int)std::max<uint64_t>(1, std::min<uint64_t>(ntiles, (uint64_t)m->cus * SCAN_WG_PER_CU)) * (NT / 64);
@@ -1324,6 +1410,8 @@ extern "C" int tsx_hip_shard_send_capacity(tsx_hip_map *m, size_t text_bytes, si
 extern "C" int tsx_hip_shard_build_pieces_device(tsx_hip_map *m, const void *dev_keys, const uint64_t *piece_off,
                                                  const uint64_t *piece_cnt, size_t npieces, void *dev_key_sum,
                                                  void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     if (!m || !dev_keys || ((uintptr_t)dev_keys & 7) || (npieces && (!piece_off || !piece_cnt))) return TSX_HIP_EINVAL;
     unsigned long long *key_sum = (unsigned long long *)dev_key_sum;
     uint64_t n_keys = 0;
@@ -1399,6 +1487,8 @@ extern "C" int tsx_hip_shard_build_pieces_device(tsx_hip_map *m, const void *dev
 
 extern "C" int tsx_hip_shard_build_device(tsx_hip_map *m, const void *dev_keys, size_t n_keys, void *dev_key_sum,
                                           void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     if (!m || (!dev_keys && n_keys)) return TSX_HIP_EINVAL;
     if (n_keys == 0) return TSX_HIP_OK;
     const uint64_t off = 0, cnt = n_keys;
@@ -1408,17 +1498,21 @@ extern "C" int tsx_hip_shard_build_device(tsx_hip_map *m, const void *dev_keys, 
 // ---- sharded run, level 1 window by window ------------------------------------------------------------------
 // The keys of exchange window w are partitioned by level 1 as soon as they have arrived (the exchange of the later
 // windows is still running); only level 2 and the build wait for the last window.
-extern "C" int tsx_hip_shard_l1_supported(tsx_hip_map *m) {
+static int l1_supported(tsx_hip_map *m) {
     if (!m || !can_partition(m) || m->p.wk != 1 || m->p.W != 1) return 0;
     const int nsegbits = m->p.l - m->p.S;
     const int b1 = std::min(9, (nsegbits <= 8) ? nsegbits : (nsegbits + 1) / 2);
     return nsegbits - b1 > 0 ? 1 : 0;
 }
 
+extern "C" int tsx_hip_shard_l1_supported(tsx_hip_map *m) { return (m && m->canon) ? 0 : l1_supported(m); }
+
 extern "C" int tsx_hip_shard_l1_window_device(tsx_hip_map *m, const void *dev_keys, size_t n_keys, uint32_t window,
                                               uint32_t nwindows, size_t est_total_keys, void *dev_key_sum, void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     if (!m || (!dev_keys && n_keys) || ((uintptr_t)dev_keys & 7) || nwindows == 0 || window >= nwindows) return TSX_HIP_EINVAL;
-    if (!tsx_hip_shard_l1_supported(m)) return TSX_HIP_EINVAL;
+    if (!l1_supported(m)) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
     if (!m->sh_pl) m->sh_pl = new PartPlan();
@@ -1480,6 +1574,7 @@ extern "C" int tsx_hip_shard_l1_window_device(tsx_hip_map *m, const void *dev_ke
 // descriptions are ALL-GATHERED, and every GPU walks all of them, keeping the keys it owns
 // (tsx_hip_shard_walk_device): N x the rolling work, N/8 of the traffic of the key exchange -- a quarter at N = 2.
 extern "C" int tsx_hip_shard_desc_capacity(tsx_hip_map *m, size_t text_bytes, int long_desc, size_t *descs_out) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
     if (!m || !descs_out) return TSX_HIP_EINVAL;
     // one description per 16 (long: 64) start positions at most; a long one is 32 bytes, a short one 16
     *descs_out = text_bytes / (long_desc ? 64 : 16) + 4096;
@@ -1489,10 +1584,12 @@ extern "C" int tsx_hip_shard_desc_capacity(tsx_hip_map *m, size_t text_bytes, in
 extern "C" int tsx_hip_shard_desc_window_device(tsx_hip_map *m, const void *dev_text, size_t n_total, size_t win_off,
                                                 size_t win_len, int long_desc, void *dev_desc, size_t desc_cap,
                                                 void *dev_count, void *dev_kmer_sum, void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_desc || ((uintptr_t)dev_desc & 15) ||
         !dev_count || win_off > n_total || win_len > n_total - win_off)
         return TSX_HIP_EINVAL;
-    if (!tsx_hip_shard_l1_supported(m)) return TSX_HIP_EINVAL;
+    if (!l1_supported(m)) return TSX_HIP_EINVAL;
     if (win_len >= ((size_t)4 << 30)) return TSX_HIP_ERANGE;
     if (desc_cap < win_len / (long_desc ? 64 : 16) + 1) return TSX_HIP_ERANGE;
     HIP_TRY(hipSetDevice(m->device));
@@ -1524,11 +1621,13 @@ static size_t mini_part_cap(const tsx_hip_map *m, size_t text_bytes, uint32_t np
     return text_bytes / 8 / nparts + 65536 + 4096 + (size_t)2 * MZ_CHUNK * (size_t)m->cus * MZ_WG_PER_CU;
 }
 extern "C" int tsx_hip_mini_part_capacity(tsx_hip_map *m, size_t text_bytes, uint32_t nparts, size_t *descs_per_owner_out) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
     if (!m || !descs_per_owner_out || nparts == 0) return TSX_HIP_EINVAL;
     *descs_per_owner_out = mini_part_cap(m, text_bytes, nparts);
     return TSX_HIP_OK;
 }
 extern "C" int tsx_hip_mini_capacity(tsx_hip_map *m, size_t text_bytes, int nranks, size_t *descs_per_owner_out) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
     if (!m || !descs_per_owner_out || nranks < 1 || nranks > MZ_MAX_RANKS) return TSX_HIP_EINVAL;
     *descs_per_owner_out = mini_part_cap(m, text_bytes, 1);
     return TSX_HIP_OK;
@@ -1569,6 +1668,8 @@ static int mini_describe(tsx_hip_map *m, const void *dev_text, size_t n_total, s
 
 extern "C" int tsx_hip_mini_describe_device(tsx_hip_map *m, const void *dev_text, size_t n_total, size_t off, size_t len,
                                             void *dev_kmer_sum, void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (off & 15) || off > n_total || len > n_total - off)
         return TSX_HIP_EINVAL;
     if (!tsx_hip_mini_supported(m)) return TSX_HIP_EINVAL;
@@ -1579,6 +1680,8 @@ extern "C" int tsx_hip_mini_describe_device(tsx_hip_map *m, const void *dev_text
 
 extern "C" int tsx_hip_mini_split_device(tsx_hip_map *m, uint32_t part, uint32_t nparts, int nranks, void *dev_desc,
                                          size_t cap_per_owner, void *dev_counts, void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     if (!m || nparts == 0 || part >= nparts || !dev_desc || ((uintptr_t)dev_desc & 15) || !dev_counts || nranks < 1 ||
         nranks > MZ_MAX_RANKS)
         return TSX_HIP_EINVAL;
@@ -1591,6 +1694,8 @@ extern "C" int tsx_hip_mini_split_device(tsx_hip_map *m, uint32_t part, uint32_t
 extern "C" int tsx_hip_mini_window_device(tsx_hip_map *m, const void *dev_text, size_t n_total, size_t win_off, size_t win_len,
                                           int nranks, void *dev_desc, size_t cap_per_owner, void *dev_counts,
                                           void *dev_kmer_sum, void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_desc || ((uintptr_t)dev_desc & 15) ||
         !dev_counts || win_off > n_total || win_len > n_total - win_off || nranks < 1 || nranks > MZ_MAX_RANKS)
         return TSX_HIP_EINVAL;
@@ -1615,10 +1720,12 @@ extern "C" int tsx_hip_mini_owner_host(int k, int nranks, const uint64_t *kmers,
 // Walks n_desc packed descriptions (any GPU's), keeps the keys this shard owns and partitions them by radix level 1
 // into list set `slot` of `nslots` (slot 0 plans for est_total_keys owned keys in all).  dev_emit_sum += k-mer
 // occurrences kept.  Then tsx_hip_shard_build_l1_device.
-extern "C" int tsx_hip_shard_walk_device(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int long_desc, uint32_t slot,
-                                         uint32_t nslots, size_t est_total_keys, void *dev_emit_sum, void *stream) {
+static int l1_supported(tsx_hip_map *m);
+// tsx_hip_shard_walk_device, and the walks of a table built slab by slab (count_slabs), canonical ones included
+static int shard_walk(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int long_desc, uint32_t slot, uint32_t nslots,
+                      size_t est_total_keys, void *dev_emit_sum, void *stream) {
     if (!m || (!dev_desc && n_desc) || ((uintptr_t)dev_desc & 15) || nslots == 0 || slot >= nslots) return TSX_HIP_EINVAL;
-    if (!tsx_hip_shard_l1_supported(m)) return TSX_HIP_EINVAL;
+    if (!l1_supported(m)) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
     if (!m->sh_pl) m->sh_pl = new PartPlan();
@@ -1672,20 +1779,29 @@ extern "C" int tsx_hip_shard_walk_device(tsx_hip_map *m, const void *dev_desc, s
     TableParams pp = m->p;
     pp.defer = DeferList{m->d_def_rec, m->d_def_cnt, m->d_def_n, (uint64_t)m->def_cap};
     const size_t lds = (size_t)pl.nb1 * (((size_t)8 << SP_CAPBITS) + 8 + 8 + 4 + 4);
-    if (lds > ((size_t)80 << 10))   // 512 lists: one workgroup per CU, 1024 threads
-        hipLaunchKernelGGL(walk_part_kernel<1024>, dim3(gw), dim3(1024), lds, st, pp, (const uint4 *)dev_desc, chunk,
+    // (a canonical map gets here only from count_slabs: the exchanges refuse it)
+    if (lds > ((size_t)80 << 10)) {   // 512 lists: one workgroup per CU, 1024 threads
+        DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<1024, CANV>), dim3(gw), dim3(1024), lds, st, pp, (const uint4 *)dev_desc, chunk,
                            (const unsigned long long *)nullptr, gw, m->dbg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
                            (uint32_t)(m->p.l - pl.b1), m->d_ovq + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
                            m->d_ovq_cnt + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
-                           (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q);
-    else
-        hipLaunchKernelGGL(walk_part_kernel<SP_NT>, dim3(gw), dim3(SP_NT), lds, st, pp, (const uint4 *)dev_desc, chunk,
+                           (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q));
+    } else {
+        DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<SP_NT, CANV>), dim3(gw), dim3(SP_NT), lds, st, pp, (const uint4 *)dev_desc, chunk,
                            (const unsigned long long *)nullptr, gw, m->dbg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
                            (uint32_t)(m->p.l - pl.b1), m->d_ovq + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
                            m->d_ovq_cnt + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
-                           (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q);
+                           (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q));
+    }
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_shard_walk_device(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int long_desc, uint32_t slot,
+                                         uint32_t nslots, size_t est_total_keys, void *dev_emit_sum, void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // the exchanges have no canonical form (owners are strand-dependent)
+    if (m && n_desc) m->used = true;
+    return shard_walk(m, dev_desc, n_desc, long_desc, slot, nslots, est_total_keys, dev_emit_sum, stream);
 }
 
 // The same in two kernels, for larger world sizes: this GPU keeps one key in N, so the fused walk is mostly waiting
@@ -1694,8 +1810,10 @@ extern "C" int tsx_hip_shard_walk_device(tsx_hip_map *m, const void *dev_desc, s
 // reads the wave logs as pieces (512 workgroups, each streaming ten of them) into list set `slot` of `nslots`.
 extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int long_desc, uint32_t slot,
                                            uint32_t nslots, size_t est_total_keys, void *dev_emit_sum, void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     if (!m || (!dev_desc && n_desc) || ((uintptr_t)dev_desc & 15) || nslots == 0 || slot >= nslots) return TSX_HIP_EINVAL;
-    if (!tsx_hip_shard_l1_supported(m)) return TSX_HIP_EINVAL;
+    if (!l1_supported(m)) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
     if (!m->sh_pl) m->sh_pl = new PartPlan();
@@ -1738,7 +1856,7 @@ extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc,
     TableParams pp = m->p;
     pp.defer = DeferList{m->d_def_rec, m->d_def_cnt, m->d_def_n, (uint64_t)m->def_cap};
     const uint64_t chunk = (n_desc + greg - 1) / greg;   // descriptions per wave
-    hipLaunchKernelGGL(walk_log_kernel, dim3(gs), dim3(NT), m->lut.size() * 8, st, pp, (const uint4 *)dev_desc, chunk,
+    hipLaunchKernelGGL(walk_log_kernel<false>, dim3(gs), dim3(NT), m->lut.size() * 8, st, pp, (const uint4 *)dev_desc, chunk,
                        (const unsigned long long *)nullptr, (uint32_t)greg, m->dbg, m->d_buf[0], lp.log_cap, lp.c_log, lp.d_hist,
                        lp.nb1, (uint32_t)(m->p.l - lp.b1), (uint64_t)n_desc, long_desc ? 1 : 0, 1,
                        (unsigned long long *)dev_emit_sum);
@@ -1757,6 +1875,8 @@ extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc,
 
 // level 2 + build over the sub-lists the windows' level-1 launches have filled
 extern "C" int tsx_hip_shard_build_l1_device(tsx_hip_map *m, void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     if (!m || !m->sh_pl || !m->sh_pl->fused) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
@@ -1774,6 +1894,8 @@ extern "C" int tsx_hip_shard_build_l1_device(tsx_hip_map *m, void *stream) {
 
 extern "C" int tsx_hip_add_hashed_device(tsx_hip_map *m, const void *dev_keys, const void *dev_counts, size_t n,
                                          void *stream) {
+    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (m) m->used = true;
     if (!m || (!dev_keys && n)) return TSX_HIP_EINVAL;
     if (m->p.wk != 1 || m->p.W != 1) return TSX_HIP_EINVAL;
     if (n == 0) return TSX_HIP_OK;
@@ -1917,7 +2039,7 @@ static int count_slabs(tsx_hip_map *m, const uint8_t *base, size_t n, hipStream_
             for (int i = 0; i < 4; ++i) if (hipEventRecord(ev[i], st) != hipSuccess) rc = TSX_HIP_EHIP;
         }
         for (uint32_t w = 0; w < nwin && rc == TSX_HIP_OK; ++w)
-            rc = tsx_hip_shard_walk_device(m, d_desc + doff[w] * 2, (size_t)cnt[w], 1, w, nwin, est, nullptr, st);
+            rc = shard_walk(m, d_desc + doff[w] * 2, (size_t)cnt[w], 1, w, nwin, est, nullptr, st);
         if (rc == TSX_HIP_OK) {
             if (!m->sh_pl || !m->sh_pl->fused) rc = TSX_HIP_EINVAL;
             else rc = run_partition_build(m, *m->sh_pl, nullptr, nullptr, 0, st, ev);
@@ -1935,6 +2057,7 @@ static int count_slabs(tsx_hip_map *m, const uint8_t *base, size_t n, hipStream_
 extern "C" int tsx_hip_count_fastq_device(tsx_hip_map *m, const void *dev_text, size_t n, void *stream) {
     if (!m || (!dev_text && n) || ((uintptr_t)dev_text & 15)) return TSX_HIP_EINVAL;
     if (m->p.lg != m->p.l) return TSX_HIP_EINVAL;   // a shard: keys of other owners must travel (shard_scan / shard_build)
+    if (n) m->used = true;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
     HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));
@@ -2130,6 +2253,7 @@ static const size_t BGZF_PRE = 256;   // >= k - 1, a multiple of 16
 extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, size_t n) {
     if (!m || (!gz && n)) return TSX_HIP_EINVAL;
     if (m->p.lg != m->p.l) return TSX_HIP_EINVAL;   // see tsx_hip_count_fastq_device
+    if (n) m->used = true;
     BgzfIndex ix;
     if (!bgzf_index((const uint8_t *)gz, n, ix)) { g_last_error = "not a BGZF file (no BC extra field in every gzip member)"; return TSX_HIP_EINVAL; }
     HIP_TRY(hipSetDevice(m->device));
@@ -2238,6 +2362,7 @@ static void parallel_memcpy(uint8_t *dst, const char *src, size_t len) {
 extern "C" int tsx_hip_count_fastq_host(tsx_hip_map *m, const char *text, size_t n) {
     if (!m || (!text && n)) return TSX_HIP_EINVAL;
     if (m->p.lg != m->p.l) return TSX_HIP_EINVAL;   // see tsx_hip_count_fastq_device
+    if (n) m->used = true;
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipStreamSynchronize(m->stream));
     if (slab_bits(m) && (m->path == 2 || (m->path == 0 && n * 32 >= m->lay.table_bytes))) {
@@ -2289,8 +2414,9 @@ extern "C" int tsx_hip_add_kmers_device(tsx_hip_map *m, const void *dev_kmers, c
     int rcz = ensure_zeroed(m, st);
     if (rcz != TSX_HIP_OK) return rcz;
     const int grid = grid_for(m, n, 8);
-    DISPATCH_WK(m, hipLaunchKernelGGL((add_kmers_kernel<WKV>), dim3(grid), dim3(NT), 0, st, m->p,
-                                      (const uint64_t *)dev_kmers, (const uint64_t *)dev_counts, (uint64_t)n));
+    m->used = true;
+    DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((add_kmers_kernel<WKV, CANV>), dim3(grid), dim3(NT), 0, st, m->p,
+                                                        (const uint64_t *)dev_kmers, (const uint64_t *)dev_counts, (uint64_t)n)));
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
@@ -2326,9 +2452,9 @@ extern "C" int tsx_hip_get_counts_device(tsx_hip_map *m, const void *dev_kmers, 
     int rcz = ensure_zeroed(m, st);
     if (rcz != TSX_HIP_OK) return rcz;
     const int grid = grid_for(m, n, 8);
-    DISPATCH_WK(m, hipLaunchKernelGGL((get_counts_kernel<WKV>), dim3(grid), dim3(NT), 0, st, m->p,
-                                      (const uint64_t *)dev_kmers, (uint64_t)n, (uint64_t *)dev_counts_out,
-                                      (uint64_t *)nullptr));
+    DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((get_counts_kernel<WKV, CANV>), dim3(grid), dim3(NT), 0, st, m->p,
+                                                        (const uint64_t *)dev_kmers, (uint64_t)n, (uint64_t *)dev_counts_out,
+                                                        (uint64_t *)nullptr)));
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
@@ -2358,8 +2484,9 @@ static int lookup_host(tsx_hip_map *m, const uint64_t *kmers, size_t n, uint64_t
     do {
         if (hipMemcpyAsync(dk, kmers, kb, hipMemcpyHostToDevice, m->stream) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         const int grid = grid_for(m, n, 8);
-        DISPATCH_WK(m, hipLaunchKernelGGL((get_counts_kernel<WKV>), dim3(grid), dim3(NT), 0, m->stream, m->p,
-                                          (const uint64_t *)dk, (uint64_t)n, dc, slots_out ? dp : (uint64_t *)nullptr));
+        DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((get_counts_kernel<WKV, CANV>), dim3(grid), dim3(NT), 0, m->stream,
+                                                            m->p, (const uint64_t *)dk, (uint64_t)n, dc,
+                                                            slots_out ? dp : (uint64_t *)nullptr)));
         if (hipGetLastError() != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         if (hipMemcpyAsync(counts_out, dc, n * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         if (slots_out && hipMemcpyAsync(slots_out, dp, n * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
@@ -2452,8 +2579,9 @@ static int dump_slots(tsx_hip_map *m, int nranks, uint64_t slot_lo, uint64_t slo
     const int grid = grid_for(m, std::max<uint64_t>(1, slot_hi - slot_lo), 8);
     unsigned long long *seg = m->d_seg;
     HIP_TRY(hipMemsetAsync(seg, 0, 64 * sizeof(unsigned long long), st));
-    DISPATCH_WK(m, hipLaunchKernelGGL((dump_kernel<WKV>), dim3(grid), dim3(NT), 0, st, m->p, nranks, 0,
-                                      (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, seg, slot_lo, slot_hi));
+    DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((dump_kernel<WKV, CANV>), dim3(grid), dim3(NT), 0, st, m->p, nranks, 0,
+                                                        (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, seg, slot_lo,
+                                                        slot_hi)));
     // segment sizes -> caller; exclusive prefix -> cursors (tiny: done on the host)
     unsigned long long h_seg[64];
     HIP_TRY(hipMemcpyAsync(h_seg, seg, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -2463,9 +2591,9 @@ static int dump_slots(tsx_hip_map *m, int nranks, uint64_t slot_lo, uint64_t slo
     if (total > cap) return TSX_HIP_ERANGE;
     HIP_TRY(hipMemcpyAsync(dev_seg_counts, h_seg, (size_t)nranks * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(seg, cur, 64 * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
-    DISPATCH_WK(m, hipLaunchKernelGGL((dump_kernel<WKV>), dim3(grid), dim3(NT), 0, st, m->p, nranks, 1,
-                                      (uint64_t *)dev_kmers_out, (uint64_t *)dev_counts_out, (uint64_t)cap, seg, slot_lo,
-                                      slot_hi));
+    DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((dump_kernel<WKV, CANV>), dim3(grid), dim3(NT), 0, st, m->p, nranks, 1,
+                                                        (uint64_t *)dev_kmers_out, (uint64_t *)dev_counts_out, (uint64_t)cap,
+                                                        seg, slot_lo, slot_hi)));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));  // cur[] lives on this stack frame
     return TSX_HIP_OK;
@@ -2515,6 +2643,11 @@ extern "C" int tsx_hip_dump_host(tsx_hip_map *m, uint64_t *kmers_out, uint64_t *
 
 extern "C" int tsx_hip_owner_host(const tsx_hip_map *m, const uint64_t *kmer, int nranks) {
     if (!m || !kmer || nranks < 1) return TSX_HIP_EINVAL;
+    uint64_t cx[4];
+    if (m->canon) {   // the owner of a strand pair is that of the k-mer its dump reports (dump_kernel)
+        tsx_hip_canonical_host(m->p.k, kmer, 1, cx);
+        kmer = cx;
+    }
     uint64_t z = 0x243F6A8885A308D3ULL;
     for (int t = 0; t < m->p.wk; ++t) {
         uint64_t x = (t == m->p.wk - 1) ? (kmer[t] & m->p.top_mask) : kmer[t];

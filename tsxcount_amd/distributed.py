@@ -278,6 +278,9 @@ class ShardedCounter:
     MIN_WINDOW = 32 << 20      # bytes of text below which a step is not split further
 
     def __init__(self, hmap, max_text_bytes, group=None, windows=None):
+        if getattr(hmap, "canonical", False):
+            raise ValueError("%s: no canonical counting (the exchange's owners are strand-dependent); "
+                             "count per GPU and merge_tables instead" % type(self).__name__)
         self.m = hmap
         self.comm = _comm(group)
         self.world, self.rank = self.comm.world, self.comm.rank
@@ -610,6 +613,9 @@ class MinimizerCounter:
     PIECE = 2 << 30          # bytes of text described at once (the entry point takes less than 4 GiB)
 
     def __init__(self, hmap, max_text_bytes, group=None, windows=None):
+        if getattr(hmap, "canonical", False):
+            raise ValueError("%s: no canonical counting (the exchange's owners are strand-dependent); "
+                             "count per GPU and merge_tables instead" % type(self).__name__)
         from . import _check
         self.m = hmap
         self.comm = _comm(group)

@@ -106,6 +106,8 @@ public:
 
     // FASTXreader<FASTAEntry> (FastXReader.h:97-116) reads two lines per record, FASTQEntry (:62-95) four
     void setRecordLines(int iLines) { check(tsx_hip_set_record_lines(m_pMap, iLines)); }
+    // canonical counting: a k-mer and its reverse complement share one counter (empty table only)
+    void setCanonical(bool bOn) { check(tsx_hip_set_canonical(m_pMap, bOn ? 1 : 0)); }
 
     // countKMers body (main.cpp:104-218): whole FASTQ text -> table
     void countFastq(const char *pText, size_t iBytes) { check(tsx_hip_count_fastq_host(m_pMap, pText, iBytes)); }
@@ -175,6 +177,8 @@ public:
     const tsx_hip_layout &getLayout() const { return m_oLayout; }
     int size() const { return tsx_hip_group_size(m_pGroup); }
     void setRecordLines(int iLines) { check(tsx_hip_group_set_record_lines(m_pGroup, iLines)); }
+    // canonical counting on every GPU's table (the merge only: not with the minimizer exchange)
+    void setCanonical(bool bOn) { check(tsx_hip_group_set_canonical(m_pGroup, bOn ? 1 : 0)); }
     // 0: per-GPU tables merged after the count (any k); 1: the minimizer exchange (20 <= k <= 32, at most 16 GPUs)
     void setExchange(int iMode) { check(tsx_hip_group_set_exchange(m_pGroup, iMode)); }
     int exchange() const { return tsx_hip_group_exchange(m_pGroup); }

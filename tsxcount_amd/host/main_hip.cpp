@@ -15,6 +15,7 @@
 #include <fstream>
 #include <iostream>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "TSXHashMapHIP.h"
@@ -31,6 +32,7 @@ struct arguments {
     std::string exchange = "auto"; // --exchange=merge|mini|auto: tables merged after the count / minimizer exchange (20 <= k <= 32;
                                   // auto: from 4 GPUs on where it applies)
     std::vector<int> devices;     // --devices=a,b,...: HIP ordinal per rank (default 0 .. N-1)
+    bool canonical = false;       // --canonical: a k-mer and its reverse complement share one counter
 };
 
 static bool opt(const char *arg, const char *name, std::string &val) {
@@ -42,9 +44,10 @@ static bool opt(const char *arg, const char *name, std::string &val) {
 
 static int usage() {
     std::cerr << "Usage: tsxCount --input=FASTQ|FASTA[.gz] [--k=K] [--l=L] [--s=STORAGE] [--mode=HIP] [--threads=T]\n"
-                 "                [--check] [--checkabort] [--seed=S] [--device=D] [--format=fastq|fasta]\n"
+                 "                [--check] [--checkabort] [--seed=S] [--device=D] [--format=fastq|fasta] [--canonical]\n"
                  "                [--gpus=N [--comm=rccl|copy] [--devices=a,b,...] [--exchange=merge|mini|auto]]\n"
-                 "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line)."
+                 "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
+                 "--canonical counts a k-mer and its reverse complement as one (the check then expects f(x) + f(rc x))."
               << std::endl;
     return 1;
 }
@@ -109,6 +112,13 @@ static bool is_fasta(const arguments &a) {   // FASTA (two lines per record, FAS
     return a.format == "fasta" || (a.format.empty() && (ends(".fa") || ends(".fasta") || ends(".fna")));
 }
 
+// reverse complement of an ACGT string (what --canonical --check pairs up)
+static std::string revcomp(const std::string &s) {
+    std::string r(s.rbegin(), s.rend());
+    for (char &c : r) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c;
+    return r;
+}
+
 // "Added a total of ..." and the --check of main.cpp:224-396, for one table or a group of them
 template <typename Map>
 static int report_and_check(Map &oMap, const arguments &a, double dt) {
@@ -131,6 +141,19 @@ static int report_and_check(Map &oMap, const arguments &a, double dt) {
         std::vector<std::string> names;
         std::string line;
         uint64_t iRefCount = 0, totalerrors = 0;
+        // --canonical: the file holds forward counts f; a listed k-mer x must count f(x) + f(rc x) (f(x) for a
+        // palindrome), and the table holds one entry per strand pair
+        std::unordered_map<std::string, uint64_t> fwd;
+        uint64_t iPairs = 0;
+        if (a.canonical) {
+            while (std::getline(file, line)) {
+                const size_t tab = line.find('\t');
+                if (tab == std::string::npos || (int)tab != a.k) continue;
+                fwd[line.substr(0, tab)] = strtoull(line.c_str() + tab + 1, nullptr, 10);
+            }
+            file.clear();
+            file.seekg(0);
+        }
         auto flush = [&]() {
             if (expect.empty()) return;
             oMap.getKmerCounts(limbs, expect.size(), got);
@@ -152,14 +175,22 @@ static int report_and_check(Map &oMap, const arguments &a, double dt) {
             if ((int)kmer.size() != a.k) continue;
             tsx_kmer_t enc = oMap.fromSequence(kmer);
             limbs.insert(limbs.end(), enc.begin(), enc.end());
-            expect.push_back(strtoull(line.c_str() + tab + 1, nullptr, 10));
+            uint64_t want = strtoull(line.c_str() + tab + 1, nullptr, 10);
+            if (a.canonical) {
+                const std::string rc = revcomp(kmer);
+                const auto it = fwd.find(rc);
+                if (rc != kmer && it != fwd.end()) want += it->second;
+                if (rc >= kmer || it == fwd.end()) ++iPairs;   // the pair is counted once: at its smaller listed strand
+            }
+            expect.push_back(want);
             names.push_back(kmer);
             if (expect.size() >= 100000) flush();  // main.cpp:263
         }
         flush();
         std::cout << "total errors" << totalerrors << std::endl;
         std::cout << "Kmer count check completed." << std::endl;
-        std::cout << "Reference kmer count: " << iRefCount << std::endl;
+        if (a.canonical) iRefCount = iPairs;
+        std::cout << "Reference kmer count: " << iRefCount << (a.canonical ? " (strand pairs)" : "") << std::endl;
         std::cout << "tsxCount kmer count: " << st.distinct << std::endl;
         if (totalerrors || iRefCount != st.distinct) rc = 5;
     }
@@ -174,8 +205,10 @@ static int run_group(const arguments &a) {
     TSXHashMapHIPGroup oGroup(a.gpus, a.devices.empty() ? nullptr : a.devices.data(), (uint8_t)a.l, (uint32_t)a.storagebits,
                               (uint16_t)a.k, a.seed, a.comm == "copy" ? 1 : 0);
     if (is_fasta(a)) { oGroup.setRecordLines(2); std::cerr << "Format=FASTA (2 lines per record)" << std::endl; }
-    // the minimizer exchange where it applies (auto: from 4 GPUs on, as bench.py); --exchange=mini insists on it
-    if (a.exchange == "mini" || (a.exchange == "auto" && a.gpus >= 4 && a.gpus <= 16 && a.k >= 20 && a.k <= 32)) {
+    if (a.canonical) oGroup.setCanonical(true);
+    // the minimizer exchange where it applies (auto: from 4 GPUs on, as bench.py, and not with --canonical); --exchange=mini
+    // insists on it
+    if (a.exchange == "mini" || (a.exchange == "auto" && !a.canonical && a.gpus >= 4 && a.gpus <= 16 && a.k >= 20 && a.k <= 32)) {
         try { oGroup.setExchange(1); }
         catch (const TSXException &e) { if (a.exchange == "mini") throw; }
     }
@@ -216,6 +249,7 @@ int main(int argc, char *argv[]) {
         else if (opt(argv[i], "gpus", v)) { a.gpus = atoi(v.c_str()); a.group = true; }
         else if (opt(argv[i], "comm", v)) a.comm = v;
         else if (opt(argv[i], "exchange", v)) a.exchange = v;
+        else if (opt(argv[i], "canonical", v)) a.canonical = true;
         else if (opt(argv[i], "devices", v)) {
             for (size_t at = 0; at < v.size();) {
                 const size_t c = v.find(',', at);
@@ -235,6 +269,7 @@ int main(int argc, char *argv[]) {
     std::cerr << "L=" << a.l << std::endl;
     std::cerr << "StorageBits=" << a.storagebits << std::endl;
     std::cerr << "Check=" << (a.check ? "Yes" : "No") << std::endl;
+    if (a.canonical) std::cerr << "Canonical=Yes" << std::endl;
     std::cerr << "Input=" << a.input_path << std::endl;
     std::cerr << "Threads=" << a.threads << std::endl;
     std::cerr << "Mode=" << a.mode << std::endl;
@@ -245,12 +280,17 @@ int main(int argc, char *argv[]) {
     }
 
     if (a.exchange != "merge" && a.exchange != "mini" && a.exchange != "auto") return usage();
+    if (a.canonical && a.group && a.exchange == "mini") {
+        std::cerr << "--exchange=mini cannot count canonically (its owners are strand-dependent); use --exchange=merge" << std::endl;
+        return usage();
+    }
     if (a.gpus < 1 || (a.comm != "rccl" && a.comm != "copy") || (!a.devices.empty() && (int)a.devices.size() != a.gpus)) return usage();
     try {
         if (a.group) return run_group(a);
         std::cerr << "Creating TSXHashMap HIP" << std::endl;
         TSXHashMapHIP oMap((uint8_t)a.l, (uint32_t)a.storagebits, (uint16_t)a.k, (uint8_t)a.threads, a.seed, a.device);
         if (is_fasta(a)) { oMap.setRecordLines(2); std::cerr << "Format=FASTA (2 lines per record)" << std::endl; }
+        if (a.canonical) oMap.setCanonical(true);
         std::vector<char> owned;
         const char *text = nullptr;
         size_t n = 0;
