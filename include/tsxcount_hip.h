@@ -34,7 +34,8 @@ enum {
     TSX_HIP_EFULL = -5,     /* a k-mer could not be placed: reference exit(42), TSXHashMap.h:340-343 */
     TSX_HIP_EOVERFLOW = -6, /* the secondary (count overflow) array is full */
     TSX_HIP_ERANGE = -7,    /* output buffer too small */
-    TSX_HIP_ELOCK = -8      /* a multi-limb slot stayed locked past the spin bound: counts may be wrong */
+    TSX_HIP_ELOCK = -8,     /* a multi-limb slot stayed locked past the spin bound: counts may be wrong */
+    TSX_HIP_EIO = -9        /* writing an output file failed (see tsx_hip_last_error) */
 };
 
 /* Layout the library derived from (k, l, storagebits); see DESIGN.md. */
@@ -252,6 +253,35 @@ int tsx_hip_dump_range_device(tsx_hip_map *m, uint64_t slot_lo, uint64_t slot_hi
                               void *dev_counts_out, size_t cap, void *dev_n, void *stream);
 int tsx_hip_owner_host(const tsx_hip_map *m, const uint64_t *kmer, int nranks);
 
+/*
+ * Counts out of the table, reduced on the device (csrc/tsx_output.h); both walk the slots like getAllKmers
+ * (TSXHashMap.h:660-722) and leave the table as it is.
+ *   histogram_device  abundance histogram of the slots [slot_lo, slot_hi) (jellyfish `histo`; no reference
+ *                     counterpart): dev_hist (nbins uint64, zeroed by the call) gets hist[c] = k-mers counted exactly c
+ *                     times for c < nbins - 1, hist[nbins - 1] = those counted nbins - 1 times or more; an occupied slot
+ *                     whose count reads 0 lands in hist[0], so the sum is always the number of k-mers in the range.
+ *                     nbins >= 2.  Queued on `stream` (NULL = the map's own), returns without waiting.
+ *   histogram_host    the same over the whole table into host memory.
+ */
+int tsx_hip_histogram_device(tsx_hip_map *m, uint64_t slot_lo, uint64_t slot_hi, size_t nbins, void *dev_hist, void *stream);
+int tsx_hip_histogram_host(tsx_hip_map *m, uint64_t *hist_out, size_t nbins);
+/*
+ * The `.count` file of count_kmers.py that main.cpp:224-396 reads back for --check: one line "kmer<TAB>count\n" per
+ * k-mer whose count lies in [lower, upper] (bases as tsx_hip_decode writes them, the count in decimal; a canonical
+ * table writes the lexicographically smaller strand, as the dumps do).  Order unspecified.
+ *   format_counts_device  the text of the slots [slot_lo, slot_hi) into dev_text (cap bytes); *dev_nbytes and
+ *                         *dev_nlines (uint64, device) receive its size.  Waits for the result; TSX_HIP_ERANGE when the
+ *                         text does not fit (the buffer then holds part of it).  A line is at most k + 22 bytes.
+ *   write_counts_host     the whole table to the file descriptor fd, chunk_bytes of device text at a time (0 = 256 MiB;
+ *                         less than one line of k + 22 bytes: TSX_HIP_EINVAL); the device formats the next chunk while
+ *                         the host writes one.  Lines and bytes written (optional).  A failed write: TSX_HIP_EIO.
+ * Both: TSX_HIP_EINVAL for lower > upper.
+ */
+int tsx_hip_format_counts_device(tsx_hip_map *m, uint64_t slot_lo, uint64_t slot_hi, uint64_t lower, uint64_t upper,
+                                 void *dev_text, size_t cap, void *dev_nbytes, void *dev_nlines, void *stream);
+int tsx_hip_write_counts_host(tsx_hip_map *m, int fd, uint64_t lower, uint64_t upper, size_t chunk_bytes,
+                              uint64_t *lines_out, uint64_t *bytes_out);
+
 /* IBijectiveFunction::apply / inv_apply (IBijectiveFunction.h:26-27) on the host,
  * and the matrix rows (row i <-> output bit 2k-1-i, BijectiveKMapping.h:202-256). */
 int tsx_hip_hash_apply(const tsx_hip_map *m, const uint64_t *kmer, uint64_t *key_out);
@@ -401,6 +431,12 @@ int tsx_hip_group_merge(tsx_hip_group *g);
 int tsx_hip_group_get_counts_host(tsx_hip_group *g, const uint64_t *kmers, size_t n, uint64_t *counts_out);
 int tsx_hip_group_get_stats(tsx_hip_group *g, tsx_hip_stats *out);
 uint64_t tsx_hip_group_exchanged_entries(const tsx_hip_group *g);   /* entries that changed GPU in the last merge */
+/* tsx_hip_histogram_host / tsx_hip_write_counts_host over the group, rank by rank: after group_count_fastq_host every
+ * k-mer lives on one GPU (the merge leaves it on its owner; the minimizer exchange is disjoint by construction), so the
+ * histogram is the sum of the ranks' and the file (the `.count` format of main.cpp:224-396) lists every k-mer once. */
+int tsx_hip_group_histogram_host(tsx_hip_group *g, uint64_t *hist_out, size_t nbins);
+int tsx_hip_group_write_counts_host(tsx_hip_group *g, int fd, uint64_t lower, uint64_t upper, size_t chunk_bytes,
+                                    uint64_t *lines_out, uint64_t *bytes_out);
 /* Where group_count_fastq_host cuts a text: cuts_out[0 .. parts], shard i = [cuts_out[i], cuts_out[i + 1]); every cut is
  * a record boundary of the reference's reader.  Host logic only (no GPU). */
 int tsx_hip_cut_records_host(const char *text, size_t n, int parts, int lines_per_record, size_t *cuts_out);

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libtsxcount_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tsxcount_hip.h")
 
-OK, EINVAL, ENODEVICE, ENOMEM, EHIP, EFULL, EOVERFLOW, ERANGE, ELOCK = 0, -1, -2, -3, -4, -5, -6, -7, -8
+OK, EINVAL, ENODEVICE, ENOMEM, EHIP, EFULL, EOVERFLOW, ERANGE, ELOCK, EIO = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9
 
 
 class TSXException(RuntimeError):
@@ -120,6 +120,12 @@ def lib():
     L.tsx_hip_partition_device.argtypes = [vp, ci, vp, vp, sz, vp, vp]
     L.tsx_hip_dump_range_device.argtypes = [vp, u64, u64, vp, vp, sz, vp, vp]
     L.tsx_hip_owner_host.argtypes = [vp, u64p, ci]
+    L.tsx_hip_histogram_device.argtypes = [vp, u64, u64, sz, vp, vp]
+    L.tsx_hip_histogram_host.argtypes = [vp, u64p, sz]
+    L.tsx_hip_format_counts_device.argtypes = [vp, u64, u64, u64, u64, vp, sz, vp, vp, vp]
+    L.tsx_hip_write_counts_host.argtypes = [vp, ci, u64, u64, sz, u64p, u64p]
+    L.tsx_hip_group_histogram_host.argtypes = [vp, u64p, sz]
+    L.tsx_hip_group_write_counts_host.argtypes = [vp, ci, u64, u64, sz, u64p, u64p]
     L.tsx_hip_hash_apply.argtypes = [vp, u64p, u64p]
     L.tsx_hip_hash_invert.argtypes = [vp, u64p, u64p]
     L.tsx_hip_hash_rows.argtypes = [vp, u64p]
@@ -159,7 +165,7 @@ def _check(code):
     if code != OK:
         L = lib()
         msg = L.tsx_hip_strerror(code).decode()
-        if code in (EHIP, ENODEVICE, ENOMEM):
+        if code in (EHIP, ENODEVICE, ENOMEM, EIO):
             extra = L.tsx_hip_last_error().decode()
             if extra:
                 msg += " (" + extra + ")"
@@ -327,6 +333,28 @@ class TSXHashMapHIP:
         _check(self._lib.tsx_hip_dump_range_device(self._h, slot_lo, slot_hi, vp(kmers_ptr), vp(counts_ptr), cap,
                                                    vp(n_ptr), vp(stream) if stream else None))
 
+    def getCountHistogram(self, nbins=10002, slot_lo=0, slot_hi=None):
+        """Abundance histogram (numpy uint64, nbins): [c] = k-mers counted c times, the last bin pools every count
+        >= nbins - 1.  The whole table, or the slots [slot_lo, slot_hi) (tsx_hip_histogram_device on a torch buffer)."""
+        out = np.zeros(nbins, dtype=np.uint64)
+        if slot_lo == 0 and slot_hi is None:
+            _check(self._lib.tsx_hip_histogram_host(self._h, _p(out), nbins))
+            return out
+        import torch
+        hi = int(self.layout.slots) if slot_hi is None else int(slot_hi)
+        buf = torch.empty(max(nbins, 1), dtype=torch.int64, device=torch.device("cuda", self.device))
+        st = torch.cuda.Stream(buf.device)   # a stream of its own: torch's default one does not wait for the map's
+        _check(self._lib.tsx_hip_histogram_device(self._h, int(slot_lo), hi, nbins, ctypes.c_void_p(buf.data_ptr()),
+                                                  ctypes.c_void_p(st.cuda_stream)))
+        st.synchronize()
+        out[:] = buf.cpu().numpy().view(np.uint64)
+        return out
+
+    def writeCounts(self, path, lower=1, upper=None, chunk_bytes=0):
+        """Every k-mer whose count lies in [lower, upper] as "kmer<TAB>count" lines (the .count format of
+        count_kmers.py / main.cpp:224-396), in no particular order.  Returns (lines, bytes)."""
+        return _write_counts(self._lib.tsx_hip_write_counts_host, self.handle, _check, path, lower, upper, chunk_bytes)
+
     def getKmerCountsDevice(self, kmers_ptr, n, out_ptr, stream=None):
         vp = ctypes.c_void_p
         _check(self._lib.tsx_hip_get_counts_device(self._h, vp(kmers_ptr), n, vp(out_ptr),
@@ -422,6 +450,19 @@ class TSXHashMapHIP:
         return out
 
 
+def _write_counts(fn, handle, check, path, lower, upper, chunk_bytes):
+    """tsx_hip_write_counts_host / tsx_hip_group_write_counts_host into the file `path` (created or truncated)."""
+    upper = (1 << 64) - 1 if upper is None else int(upper)
+    lines, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+    try:
+        rc = fn(handle, fd, int(lower), upper, int(chunk_bytes), ctypes.byref(lines), ctypes.byref(nbytes))
+    finally:
+        os.close(fd)
+    check(rc)
+    return int(lines.value), int(nbytes.value)
+
+
 def cut_records(text, parts, lines_per_record=4):
     """Where the multi-GPU host cuts a text: parts + 1 offsets, every one a record boundary of the reference's reader."""
     b = bytes(text)
@@ -483,6 +524,16 @@ class TSXHashMapHIPGroup:
         s = Stats()
         self._check(self._lib.tsx_hip_group_get_stats(self._h, ctypes.byref(s)))
         return s.as_dict()
+
+    def getCountHistogram(self, nbins=10002):
+        """The abundance histogram of the whole group (the sum of the ranks'; see TSXHashMapHIP.getCountHistogram)."""
+        out = np.zeros(nbins, dtype=np.uint64)
+        self._check(self._lib.tsx_hip_group_histogram_host(self._h, _p(out), nbins))
+        return out
+
+    def writeCounts(self, path, lower=1, upper=None, chunk_bytes=0):
+        """Every k-mer of the group in [lower, upper] as "kmer<TAB>count" lines, rank after rank.  Returns (lines, bytes)."""
+        return _write_counts(self._lib.tsx_hip_group_write_counts_host, self._h, self._check, path, lower, upper, chunk_bytes)
 
     def rank_stats(self, rank):
         s = Stats()

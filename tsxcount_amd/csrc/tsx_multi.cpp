@@ -616,6 +616,36 @@ extern "C" int tsx_hip_group_get_stats(tsx_hip_group *g, tsx_hip_stats *out) {
 
 extern "C" uint64_t tsx_hip_group_exchanged_entries(const tsx_hip_group *g) { return g ? g->exchanged_entries : 0; }
 
+// Output over the group, rank by rank: the tables are disjoint once the count has returned (the merge leaves each k-mer
+// on its owner; the minimizer exchange sends every k-mer to one owner), so sums and concatenation are exact.
+extern "C" int tsx_hip_group_histogram_host(tsx_hip_group *g, uint64_t *hist_out, size_t nbins) {
+    if (!g || !hist_out || nbins < 2) return TSX_HIP_EINVAL;
+    std::vector<uint64_t> part(nbins);
+    memset(hist_out, 0, nbins * sizeof(uint64_t));
+    for (tsx_hip_map *m : g->maps) {
+        const int rc = tsx_hip_histogram_host(m, part.data(), nbins);
+        if (rc != TSX_HIP_OK) return rc;
+        for (size_t i = 0; i < nbins; ++i) hist_out[i] += part[i];
+    }
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_group_write_counts_host(tsx_hip_group *g, int fd, uint64_t lower, uint64_t upper, size_t chunk_bytes,
+                                               uint64_t *lines_out, uint64_t *bytes_out) {
+    if (lines_out) *lines_out = 0;
+    if (bytes_out) *bytes_out = 0;
+    if (!g) return TSX_HIP_EINVAL;
+    int rc = TSX_HIP_OK;
+    for (tsx_hip_map *m : g->maps) {
+        uint64_t l = 0, b = 0;
+        rc = tsx_hip_write_counts_host(m, fd, lower, upper, chunk_bytes, &l, &b);
+        if (lines_out) *lines_out += l;
+        if (bytes_out) *bytes_out += b;
+        if (rc != TSX_HIP_OK) break;
+    }
+    return rc;
+}
+
 // The record cuts of a text (host logic, no GPU): cuts_out[0 .. parts] with cuts_out[0] = 0, cuts_out[parts] = n.
 extern "C" int tsx_hip_cut_records_host(const char *text, size_t n, int parts, int lines_per_record, size_t *cuts_out) {
     if ((!text && n) || parts < 1 || parts > 4096 || (lines_per_record != 2 && lines_per_record != 4) || !cuts_out) return TSX_HIP_EINVAL;

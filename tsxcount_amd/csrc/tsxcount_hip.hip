@@ -6,6 +6,7 @@
 #include "tsx_partition.h"
 #include "tsx_minimizer.h"
 #include "tsx_inflate.h"
+#include "tsx_output.h"
 
 #include <mutex>
 #include <hip/hip_runtime.h>
@@ -13,12 +14,15 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cerrno>
 #include <cmath>
 #include <cstring>
 #include <deque>
 #include <string>
 #include <thread>
 #include <vector>
+
+#include <unistd.h>
 
 using namespace tsx;
 
@@ -142,6 +146,7 @@ extern "C" const char *tsx_hip_strerror(int code) {
         case TSX_HIP_EOVERFLOW: return "count overflow array full";
         case TSX_HIP_ERANGE: return "output buffer too small";
         case TSX_HIP_ELOCK: return "a multi-limb slot stayed locked past the spin bound";
+        case TSX_HIP_EIO: return "writing the output failed";
     }
     return "unknown";
 }
@@ -2638,6 +2643,163 @@ extern "C" int tsx_hip_dump_host(tsx_hip_map *m, uint64_t *kmers_out, uint64_t *
             rc = TSX_HIP_EHIP;
     }
     (void)hipFree(dk); (void)hipFree(dc); (void)hipFree(dn);
+    return rc;
+}
+
+// ---- output: abundance histogram and the .count text (tsx_output.h) -------------
+static const size_t WRITE_CHUNK_DEFAULT = (size_t)256 << 20;   // text bytes per chunk of tsx_hip_write_counts_host
+static inline size_t line_max(const tsx_hip_map *m) { return (size_t)m->p.k + 22; }   // bases, TAB, 20 digits, newline
+
+static int histogram_launch(tsx_hip_map *m, uint64_t slot_lo, uint64_t slot_hi, size_t nbins, void *dev_hist, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(dev_hist, 0, nbins * sizeof(unsigned long long), st));
+    const uint64_t n = slot_hi - slot_lo, sslots = m->p.sec_mask + 1;
+    uint64_t grid = (uint64_t)grid_for(m, std::max<uint64_t>(n / HIST_UNROLL, sslots), 8);
+    // A workgroup's LDS bins are flushed as int32: bound what one workgroup visits (pass A + pass B) below 2^31.
+    auto per_wg = [&](uint64_t g) {
+        const uint64_t a = 64 * HIST_UNROLL * (NT / 64), b = NT;
+        return (n + g * a - 1) / (g * a) * a + (sslots + g * b - 1) / (g * b) * b;
+    };
+    while (per_wg(grid) >= (1ULL << 31) && grid < (1ULL << 30)) grid *= 2;
+    if (per_wg(grid) >= (1ULL << 31)) return TSX_HIP_EINVAL;
+    hipLaunchKernelGGL(count_histogram_kernel, dim3((unsigned)grid), dim3(NT), 0, st, m->p, slot_lo, slot_hi, (uint64_t)nbins,
+                       (unsigned long long *)dev_hist);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_histogram_device(tsx_hip_map *m, uint64_t slot_lo, uint64_t slot_hi, size_t nbins, void *dev_hist,
+                                        void *stream) {
+    if (!m || !dev_hist || nbins < 2 || slot_lo > slot_hi || slot_hi > m->lay.slots) return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    int rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    return histogram_launch(m, slot_lo, slot_hi, nbins, dev_hist, st);
+}
+
+extern "C" int tsx_hip_histogram_host(tsx_hip_map *m, uint64_t *hist_out, size_t nbins) {
+    if (!m || !hist_out || nbins < 2) return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    join_foreign(m, false);
+    void *d = nullptr;
+    HIP_TRY(hipMalloc(&d, nbins * sizeof(uint64_t)));
+    int rc = tsx_hip_histogram_device(m, 0, m->lay.slots, nbins, d, nullptr);
+    if (rc == TSX_HIP_OK && (hipMemcpyAsync(hist_out, d, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
+                             hipStreamSynchronize(m->stream) != hipSuccess))
+        rc = TSX_HIP_EHIP;
+    (void)hipFree(d);
+    return rc;
+}
+
+// Zero the two counters and queue format_counts_kernel over [slot_lo, slot_hi) (nothing to format: counters only).
+static int format_launch(tsx_hip_map *m, uint64_t slot_lo, uint64_t slot_hi, uint64_t lower, uint64_t upper, void *dev_text,
+                         size_t cap, unsigned long long *d_nbytes, unsigned long long *d_nlines, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(d_nbytes, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(d_nlines, 0, sizeof(unsigned long long), st));
+    if (slot_hi == slot_lo) return TSX_HIP_OK;
+    const int grid = grid_for(m, slot_hi - slot_lo, 8);
+    DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((format_counts_kernel<WKV, CANV>), dim3(grid), dim3(NT), 0, st, m->p,
+                                                        slot_lo, slot_hi, lower, upper, (uint8_t *)dev_text, (uint64_t)cap,
+                                                        d_nbytes, d_nlines)));
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_format_counts_device(tsx_hip_map *m, uint64_t slot_lo, uint64_t slot_hi, uint64_t lower, uint64_t upper,
+                                            void *dev_text, size_t cap, void *dev_nbytes, void *dev_nlines, void *stream) {
+    if (!m || !dev_nbytes || !dev_nlines || (!dev_text && cap) || lower > upper) return TSX_HIP_EINVAL;
+    if (slot_lo > slot_hi || slot_hi > m->lay.slots) return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    int rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    rc = format_launch(m, slot_lo, slot_hi, lower, upper, dev_text, cap, (unsigned long long *)dev_nbytes,
+                       (unsigned long long *)dev_nlines, st);
+    if (rc != TSX_HIP_OK) return rc;
+    unsigned long long nb = 0;
+    HIP_TRY(hipMemcpyAsync(&nb, dev_nbytes, sizeof nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return nb > cap ? TSX_HIP_ERANGE : TSX_HIP_OK;
+}
+
+// write(2) until every byte is out: short writes continue, EINTR retries, anything else is TSX_HIP_EIO.
+static int write_all(int fd, const uint8_t *p, size_t n) {
+    while (n) {
+        const ssize_t w = write(fd, p, n);
+        if (w < 0 && errno == EINTR) continue;
+        if (w <= 0) {
+            g_last_error = std::string("write: ") + (w < 0 ? strerror(errno) : "no progress");
+            return TSX_HIP_EIO;
+        }
+        p += w;
+        n -= (size_t)w;
+    }
+    return TSX_HIP_OK;
+}
+
+// The table as text, chunk by chunk: a chunk is floor(chunk_bytes / line_max) slots, so its text always fits.  Two device
+// and two pinned host buffers: the device formats chunk i + 1 while chunk i is written to fd.
+extern "C" int tsx_hip_write_counts_host(tsx_hip_map *m, int fd, uint64_t lower, uint64_t upper, size_t chunk_bytes,
+                                         uint64_t *lines_out, uint64_t *bytes_out) {
+    if (lines_out) *lines_out = 0;
+    if (bytes_out) *bytes_out = 0;
+    if (!m || fd < 0 || lower > upper || (chunk_bytes && chunk_bytes < line_max(m))) return TSX_HIP_EINVAL;
+    if (!chunk_bytes) chunk_bytes = WRITE_CHUNK_DEFAULT;
+    const uint64_t slots = m->lay.slots, per = chunk_bytes / line_max(m);
+    const uint64_t nchunks = (slots + per - 1) / per;
+    const size_t buf = (size_t)std::min<uint64_t>(per, slots) * line_max(m);
+    const int nbuf = nchunks > 1 ? 2 : 1;
+    HIP_TRY(hipSetDevice(m->device));
+    join_foreign(m, false);
+    hipStream_t st = m->stream;
+    int rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    uint8_t *d_text[2] = {nullptr, nullptr}, *h_text[2] = {nullptr, nullptr};
+    unsigned long long *d_cnt = nullptr, *h_cnt = nullptr;
+    hipEvent_t ev_cnt = nullptr, ev_txt = nullptr;
+    if (hipMalloc((void **)&d_cnt, 2 * sizeof(unsigned long long)) != hipSuccess ||
+        hipHostMalloc((void **)&h_cnt, 2 * sizeof(unsigned long long)) != hipSuccess)
+        rc = TSX_HIP_ENOMEM;
+    for (int b = 0; b < nbuf && rc == TSX_HIP_OK; ++b)
+        if (hipMalloc((void **)&d_text[b], buf) != hipSuccess || hipHostMalloc((void **)&h_text[b], buf) != hipSuccess)
+            rc = TSX_HIP_ENOMEM;
+    if (rc == TSX_HIP_OK && (hipEventCreateWithFlags(&ev_cnt, hipEventDisableTiming) != hipSuccess ||
+                             hipEventCreateWithFlags(&ev_txt, hipEventDisableTiming) != hipSuccess))
+        rc = TSX_HIP_EHIP;
+    // stream order: fmt(0) cnt(0) | txt(0) fmt(1) cnt(1) | txt(1) fmt(2) cnt(2) | ...
+    auto queue_chunk = [&](uint64_t i) {
+        const uint64_t lo = i * per, hi = std::min(slots, lo + per);
+        int r = format_launch(m, lo, hi, lower, upper, d_text[i & 1], buf, d_cnt, d_cnt + 1, st);
+        if (r == TSX_HIP_OK && (hipMemcpyAsync(h_cnt, d_cnt, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                                hipEventRecord(ev_cnt, st) != hipSuccess))
+            r = TSX_HIP_EHIP;
+        return r;
+    };
+    uint64_t lines = 0, bytes = 0;
+    if (rc == TSX_HIP_OK) rc = queue_chunk(0);
+    for (uint64_t i = 0; i < nchunks && rc == TSX_HIP_OK; ++i) {
+        const int b = (int)(i & 1);
+        if (hipEventSynchronize(ev_cnt) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        const uint64_t nb = h_cnt[0], nl = h_cnt[1];
+        if (nb > buf) { rc = TSX_HIP_ERANGE; break; }   // cannot happen: a chunk's text fits by construction
+        if ((nb && hipMemcpyAsync(h_text[b], d_text[b], nb, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+            hipEventRecord(ev_txt, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        if (i + 1 < nchunks && (rc = queue_chunk(i + 1)) != TSX_HIP_OK) break;
+        if (hipEventSynchronize(ev_txt) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        rc = write_all(fd, h_text[b], nb);
+        if (rc == TSX_HIP_OK) { lines += nl; bytes += nb; }
+    }
+    (void)hipStreamSynchronize(st);   // nothing queued may outlive the buffers
+    for (int b = 0; b < 2; ++b) {
+        if (d_text[b]) (void)hipFree(d_text[b]);
+        if (h_text[b]) (void)hipHostFree(h_text[b]);
+    }
+    if (d_cnt) (void)hipFree(d_cnt);
+    if (h_cnt) (void)hipHostFree(h_cnt);
+    if (ev_cnt) (void)hipEventDestroy(ev_cnt);
+    if (ev_txt) (void)hipEventDestroy(ev_txt);
+    if (lines_out) *lines_out = lines;
+    if (bytes_out) *bytes_out = bytes;
     return rc;
 }
 

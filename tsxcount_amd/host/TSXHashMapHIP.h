@@ -10,6 +10,9 @@
 #ifndef TSXCOUNT_TSXHASHMAPHIP_H
 #define TSXCOUNT_TSXHASHMAPHIP_H
 
+#include <fcntl.h>
+#include <unistd.h>
+
 #include <cstdint>
 #include <exception>
 #include <iostream>
@@ -32,6 +35,19 @@ protected:
 };
 
 typedef std::vector<uint64_t> tsx_kmer_t;  // TSX::tsx_kmer_t (TSXTypes.h:23)
+
+// Open (create / truncate) sPath, hand the descriptor to fnWrite (a tsx_hip_*write_counts_host call), close it; fnCheck
+// throws on an error code.  Returns the lines written.
+template <typename W, typename C>
+static uint64_t tsx_write_counts_file(const std::string &sPath, W fnWrite, C fnCheck) {
+    const int fd = open(sPath.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) throw TSXException("could not open " + sPath + " for writing", TSX_HIP_EIO);
+    uint64_t iLines = 0, iBytes = 0;
+    int rc = fnWrite(fd, &iLines, &iBytes);
+    if (close(fd) != 0 && rc == TSX_HIP_OK) rc = TSX_HIP_EIO;
+    fnCheck(rc);
+    return iLines;
+}
 
 class TSXHashMapHIP {
 public:
@@ -104,6 +120,19 @@ public:
         return out;
     }
 
+    // abundance histogram: [c] = k-mers counted c times, [iBins - 1] = counted iBins - 1 times or more
+    std::vector<uint64_t> histogram(size_t iBins) {
+        std::vector<uint64_t> h(iBins);
+        check(tsx_hip_histogram_host(m_pMap, h.data(), iBins));
+        return h;
+    }
+    // the FASTQ.<k>.count file main.cpp:224-396 reads: "kmer<TAB>count" for every count in [iLower, iUpper]; returns lines
+    uint64_t write_counts(const std::string &sPath, uint64_t iLower = 1, uint64_t iUpper = UINT64_MAX) {
+        return tsx_write_counts_file(sPath, [&](int fd, uint64_t *l, uint64_t *b) {
+            return tsx_hip_write_counts_host(m_pMap, fd, iLower, iUpper, 0, l, b);
+        }, check);
+    }
+
     // FASTXreader<FASTAEntry> (FastXReader.h:97-116) reads two lines per record, FASTQEntry (:62-95) four
     void setRecordLines(int iLines) { check(tsx_hip_set_record_lines(m_pMap, iLines)); }
     // canonical counting: a k-mer and its reverse complement share one counter (empty table only)
@@ -142,7 +171,7 @@ private:
     static void check(int rc) {
         if (rc == TSX_HIP_OK) return;
         std::string msg = tsx_hip_strerror(rc);
-        if (rc == TSX_HIP_EHIP || rc == TSX_HIP_ENODEVICE || rc == TSX_HIP_ENOMEM) {
+        if (rc == TSX_HIP_EHIP || rc == TSX_HIP_ENODEVICE || rc == TSX_HIP_ENOMEM || rc == TSX_HIP_EIO) {
             msg += " (";
             msg += tsx_hip_last_error();
             msg += ")";
@@ -200,6 +229,17 @@ public:
         return s;
     }
     uint64_t exchangedEntries() const { return tsx_hip_group_exchanged_entries(m_pGroup); }
+    // the histogram / .count file of the whole group (the ranks' tables are disjoint after countFastq)
+    std::vector<uint64_t> histogram(size_t iBins) {
+        std::vector<uint64_t> h(iBins);
+        check(tsx_hip_group_histogram_host(m_pGroup, h.data(), iBins));
+        return h;
+    }
+    uint64_t write_counts(const std::string &sPath, uint64_t iLower = 1, uint64_t iUpper = UINT64_MAX) {
+        return tsx_write_counts_file(sPath, [&](int fd, uint64_t *l, uint64_t *b) {
+            return tsx_hip_group_write_counts_host(m_pGroup, fd, iLower, iUpper, 0, l, b);
+        }, check);
+    }
     void print_stats() {
         tsx_hip_stats s = stats();
         std::cerr << "Used fields: " << s.distinct << std::endl;

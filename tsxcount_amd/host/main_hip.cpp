@@ -33,6 +33,9 @@ struct arguments {
                                   // auto: from 4 GPUs on where it applies)
     std::vector<int> devices;     // --devices=a,b,...: HIP ordinal per rank (default 0 .. N-1)
     bool canonical = false;       // --canonical: a k-mer and its reverse complement share one counter
+    std::string output, histo;    // --output=FILE: "kmer<TAB>count" lines; --histo=FILE: "count<TAB>k-mers" lines
+    uint64_t lower = 1, upper = UINT64_MAX;   // --lower / --upper: the counts --output writes
+    uint64_t histo_max = 10000;   // --histo-max=H: counts 1..H, then one line H+1 for everything above
 };
 
 static bool opt(const char *arg, const char *name, std::string &val) {
@@ -46,8 +49,12 @@ static int usage() {
     std::cerr << "Usage: tsxCount --input=FASTQ|FASTA[.gz] [--k=K] [--l=L] [--s=STORAGE] [--mode=HIP] [--threads=T]\n"
                  "                [--check] [--checkabort] [--seed=S] [--device=D] [--format=fastq|fasta] [--canonical]\n"
                  "                [--gpus=N [--comm=rccl|copy] [--devices=a,b,...] [--exchange=merge|mini|auto]]\n"
+                 "                [--output=FILE [--lower=N] [--upper=N]] [--histo=FILE [--histo-max=H]]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
-                 "--canonical counts a k-mer and its reverse complement as one (the check then expects f(x) + f(rc x))."
+                 "--canonical counts a k-mer and its reverse complement as one (the check then expects f(x) + f(rc x)).\n"
+                 "--output writes every k-mer counted lower..upper times (default 1..unbounded) as kmer<TAB>count, in no\n"
+                 "particular order. --histo writes count<TAB>number of k-mers for every count 1..H (default 10000) that\n"
+                 "occurs, then H+1<TAB>number of k-mers counted more than H times."
               << std::endl;
     return 1;
 }
@@ -117,6 +124,25 @@ static std::string revcomp(const std::string &s) {
     std::string r(s.rbegin(), s.rend());
     for (char &c : r) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c;
     return r;
+}
+
+// --output and --histo, for one table or a group of them (after the count and the check)
+template <typename Map>
+static void write_outputs(Map &oMap, const arguments &a) {
+    if (!a.output.empty()) {
+        const uint64_t iLines = oMap.write_counts(a.output, a.lower, a.upper);
+        std::cerr << "Wrote " << iLines << " kmers to " << a.output << std::endl;
+    }
+    if (!a.histo.empty()) {
+        const std::vector<uint64_t> h = oMap.histogram((size_t)a.histo_max + 2);
+        std::ofstream f(a.histo);
+        for (uint64_t c = 1; c <= a.histo_max; ++c)
+            if (h[c]) f << c << '\t' << h[c] << '\n';
+        f << a.histo_max + 1 << '\t' << h[a.histo_max + 1] << '\n';
+        f.close();
+        if (!f) throw TSXException("could not write " + a.histo, TSX_HIP_EIO);
+        std::cerr << "Wrote the count histogram to " << a.histo << std::endl;
+    }
 }
 
 // "Added a total of ..." and the --check of main.cpp:224-396, for one table or a group of them
@@ -194,6 +220,7 @@ static int report_and_check(Map &oMap, const arguments &a, double dt) {
         std::cout << "tsxCount kmer count: " << st.distinct << std::endl;
         if (totalerrors || iRefCount != st.distinct) rc = 5;
     }
+    write_outputs(oMap, a);
     oMap.print_stats();
     return rc;
 }
@@ -250,6 +277,11 @@ int main(int argc, char *argv[]) {
         else if (opt(argv[i], "comm", v)) a.comm = v;
         else if (opt(argv[i], "exchange", v)) a.exchange = v;
         else if (opt(argv[i], "canonical", v)) a.canonical = true;
+        else if (opt(argv[i], "output", v)) a.output = v;
+        else if (opt(argv[i], "lower", v)) a.lower = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "upper", v)) a.upper = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "histo", v)) a.histo = v;
+        else if (opt(argv[i], "histo-max", v)) a.histo_max = strtoull(v.c_str(), nullptr, 10);
         else if (opt(argv[i], "devices", v)) {
             for (size_t at = 0; at < v.size();) {
                 const size_t c = v.find(',', at);
@@ -280,6 +312,7 @@ int main(int argc, char *argv[]) {
     }
 
     if (a.exchange != "merge" && a.exchange != "mini" && a.exchange != "auto") return usage();
+    if (a.lower > a.upper || a.histo_max < 1 || a.histo_max > ((uint64_t)1 << 32)) return usage();
     if (a.canonical && a.group && a.exchange == "mini") {
         std::cerr << "--exchange=mini cannot count canonically (its owners are strand-dependent); use --exchange=merge" << std::endl;
         return usage();
