@@ -282,6 +282,57 @@ int tsx_hip_format_counts_device(tsx_hip_map *m, uint64_t slot_lo, uint64_t slot
 int tsx_hip_write_counts_host(tsx_hip_map *m, int fd, uint64_t lower, uint64_t upper, size_t chunk_bytes,
                               uint64_t *lines_out, uint64_t *bytes_out);
 
+/*
+ * Read queries (csrc/tsx_query.h; no reference counterpart): run the records of a text against the table.  Records and
+ * k-mers are exactly what counting the same text would count (FastXReader.h:62-116): empty lines are dropped, a record
+ * is tsx_hip_set_record_lines consecutive non-empty lines (a trailing incomplete record is still one), its second line
+ * is the sequence, every window of k bytes of it is one k-mer occurrence with the stand-in code of tsx_hip_encode for
+ * non-ACGT bytes.  c(x) is getKmerCount(x) (TSXHashMap.h:548-638), 0 when x is absent; on a canonical table either
+ * strand finds the pair's count.  Records are numbered from 0 in text order; per record:
+ *   kmers      max(0, len - k + 1) of its sequence line
+ *   in_range   windows with lower <= c <= upper, with multiplicity
+ *   min_count  the smallest c, 0 when kmers = 0
+ *   sum_count  the sum of c mod 2^64
+ * Every query refuses a map created with shard_bits > 0 (a shard answers 0 for k-mers it does not own) and lower > upper
+ * with TSX_HIP_EINVAL.
+ *   query_reads_device  dev_text as tsx_hip_count_fastq_device takes it (16-byte aligned, starts at a record boundary);
+ *                       queued on `stream` (NULL = the map's own) after what is queued there, the stats of records
+ *                       [0, stats_cap) to dev_stats (zeroed by the call).  WAITS for the stream and reports the record
+ *                       count to the host (*n_records, optional); more records than stats_cap: TSX_HIP_ERANGE (the first
+ *                       stats_cap are written).
+ *   query_reads_host    the same for text in host memory, taken in pieces cut at record boundaries, chunk_bytes at a
+ *                       time (0 = 256 MiB; a record longer than a piece is taken whole); stats_out in host memory.
+ */
+typedef struct tsx_hip_read_stats {
+    uint64_t kmers, in_range, min_count, sum_count;
+} tsx_hip_read_stats;
+int tsx_hip_query_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, uint64_t lower, uint64_t upper,
+                               void *dev_stats, size_t stats_cap, size_t *n_records, void *stream);
+int tsx_hip_query_reads_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, uint64_t upper,
+                             tsx_hip_read_stats *stats_out, size_t stats_cap, size_t *n_records, size_t chunk_bytes);
+/*
+ * Read filter: a record passes iff in_range >= min_in_range and in_range * 10^6 >= fraction_ppm * kmers (so a record
+ * shorter than k passes when min_in_range = 0); invert != 0 writes the records that fail instead.  A written record is
+ * its bytes from the first byte of its first line through the '\n' that ends its last line ('\n' added when the text
+ * ends without one); empty lines between records are not written; output is in input order.  TSX_HIP_EINVAL also for
+ * fraction_ppm > 10^6.
+ *   filter_reads_host    text in host memory, in pieces as query_reads_host; the device compacts each piece while the
+ *                        host writes the previous one to fd.  Records kept and bytes written (optional).  A failed write:
+ *                        TSX_HIP_EIO.
+ *   filter_reads_device  the whole of dev_text (as query_reads_device; n < 3.75 GiB) into dev_out (16-byte aligned,
+ *                        out_cap >= n + 64, else TSX_HIP_ERANGE); *out_bytes = the output's size.  Waits for the stream.
+ */
+typedef struct tsx_hip_filter_rule {
+    uint64_t lower, upper;      /* the count range of an in_range window */
+    uint64_t min_in_range;      /* windows in range a record needs */
+    uint32_t fraction_ppm;      /* share of its windows that must be in range, in millionths (10^6 = all) */
+    int32_t invert;             /* write the records that fail */
+} tsx_hip_filter_rule;
+int tsx_hip_filter_reads_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_filter_rule *rule, int fd,
+                              size_t chunk_bytes, uint64_t *kept_out, uint64_t *bytes_out);
+int tsx_hip_filter_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_filter_rule *rule,
+                                void *dev_out, size_t out_cap, size_t *out_bytes, uint64_t *kept_out, void *stream);
+
 /* IBijectiveFunction::apply / inv_apply (IBijectiveFunction.h:26-27) on the host,
  * and the matrix rows (row i <-> output bit 2k-1-i, BijectiveKMapping.h:202-256). */
 int tsx_hip_hash_apply(const tsx_hip_map *m, const uint64_t *kmer, uint64_t *key_out);

@@ -46,6 +46,21 @@ class Stats(ctypes.Structure):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
+class FilterRule(ctypes.Structure):
+    """tsx_hip_filter_rule: a record passes iff in_range >= min_in_range and in_range * 10^6 >= fraction_ppm * kmers."""
+    _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("min_in_range", ctypes.c_uint64),
+                ("fraction_ppm", ctypes.c_uint32), ("invert", ctypes.c_int32)]
+
+
+READ_STATS_DTYPE = np.dtype([("kmers", np.uint64), ("in_range", np.uint64), ("min_count", np.uint64), ("sum_count", np.uint64)])
+
+
+def filter_rule(lower=2, upper=None, min_in_range=0, fraction=1.0, invert=False):
+    """A FilterRule from the Python arguments (fraction: share of a record's k-mers that must be in range, 0..1)."""
+    return FilterRule(int(lower), (1 << 64) - 1 if upper is None else int(upper), int(min_in_range),
+                      int(round(float(fraction) * 1e6)), 1 if invert else 0)
+
+
 def build():
     """Compile the library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     import subprocess
@@ -126,6 +141,10 @@ def lib():
     L.tsx_hip_write_counts_host.argtypes = [vp, ci, u64, u64, sz, u64p, u64p]
     L.tsx_hip_group_histogram_host.argtypes = [vp, u64p, sz]
     L.tsx_hip_group_write_counts_host.argtypes = [vp, ci, u64, u64, sz, u64p, u64p]
+    L.tsx_hip_query_reads_device.argtypes = [vp, vp, sz, u64, u64, vp, sz, ctypes.POINTER(sz), vp]
+    L.tsx_hip_query_reads_host.argtypes = [vp, ctypes.c_char_p, sz, u64, u64, vp, sz, ctypes.POINTER(sz), sz]
+    L.tsx_hip_filter_reads_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(FilterRule), ci, sz, u64p, u64p]
+    L.tsx_hip_filter_reads_device.argtypes = [vp, vp, sz, ctypes.POINTER(FilterRule), vp, sz, ctypes.POINTER(sz), u64p, vp]
     L.tsx_hip_hash_apply.argtypes = [vp, u64p, u64p]
     L.tsx_hip_hash_invert.argtypes = [vp, u64p, u64p]
     L.tsx_hip_hash_rows.argtypes = [vp, u64p]
@@ -354,6 +373,60 @@ class TSXHashMapHIP:
         """Every k-mer whose count lies in [lower, upper] as "kmer<TAB>count" lines (the .count format of
         count_kmers.py / main.cpp:224-396), in no particular order.  Returns (lines, bytes)."""
         return _write_counts(self._lib.tsx_hip_write_counts_host, self.handle, _check, path, lower, upper, chunk_bytes)
+
+    def queryReads(self, text, lower=1, upper=None, chunk_bytes=0):
+        """Per-record k-mer stats of a FASTQ / FASTA text against the table (tsx_hip_query_reads_host): a numpy
+        structured array (READ_STATS_DTYPE: kmers, in_range, min_count, sum_count), one entry per record in text
+        order; in_range counts the k-mers whose count lies in [lower, upper]."""
+        b = bytes(text)
+        upper = (1 << 64) - 1 if upper is None else int(upper)
+        cap = len(b) // 256 + 16
+        for _ in range(2):
+            out = np.zeros(cap, dtype=READ_STATS_DTYPE)
+            n = ctypes.c_size_t(0)
+            rc = self._lib.tsx_hip_query_reads_host(self.handle, b, len(b), int(lower), upper, out.ctypes.data_as(ctypes.c_void_p),
+                                                    cap, ctypes.byref(n), int(chunk_bytes))
+            if rc != ERANGE:
+                break
+            cap = n.value
+        _check(rc)
+        return out[:n.value]
+
+    def filterReads(self, text, path_or_fd, lower=2, upper=None, min_in_range=0, fraction=1.0, invert=False, chunk_bytes=0):
+        """Write the records of `text` whose k-mers pass the rule (tsx_hip_filter_reads_host) to a path (created or
+        truncated) or an open file descriptor.  Returns (records kept, bytes written)."""
+        b = bytes(text)
+        rule = filter_rule(lower, upper, min_in_range, fraction, invert)
+        kept, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        own = not isinstance(path_or_fd, int)
+        fd = os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd
+        try:
+            rc = self._lib.tsx_hip_filter_reads_host(self.handle, b, len(b), ctypes.byref(rule), fd, int(chunk_bytes),
+                                                     ctypes.byref(kept), ctypes.byref(nbytes))
+        finally:
+            if own:
+                os.close(fd)
+        _check(rc)
+        return int(kept.value), int(nbytes.value)
+
+    def queryReadsDevice(self, text_ptr, nbytes, stats_ptr, cap, lower=1, upper=None, stream=None):
+        """tsx_hip_query_reads_device: stats of the records of a device text into a device buffer of cap records.
+        Returns the record count (more than cap: TSXException ERANGE)."""
+        vp = ctypes.c_void_p
+        n = ctypes.c_size_t(0)
+        _check(self._lib.tsx_hip_query_reads_device(self.handle, vp(text_ptr), nbytes, int(lower),
+                                                    (1 << 64) - 1 if upper is None else int(upper), vp(stats_ptr), cap,
+                                                    ctypes.byref(n), vp(stream) if stream else None))
+        return int(n.value)
+
+    def filterReadsDevice(self, text_ptr, nbytes, out_ptr, out_cap, rule, stream=None):
+        """tsx_hip_filter_reads_device: the passing records of a device text into a device buffer.  Returns (records
+        kept, bytes)."""
+        vp = ctypes.c_void_p
+        nb, kept = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        _check(self._lib.tsx_hip_filter_reads_device(self.handle, vp(text_ptr), nbytes, ctypes.byref(rule), vp(out_ptr), out_cap,
+                                                     ctypes.byref(nb), ctypes.byref(kept), vp(stream) if stream else None))
+        return int(kept.value), int(nb.value)
 
     def getKmerCountsDevice(self, kmers_ptr, n, out_ptr, stream=None):
         vp = ctypes.c_void_p

@@ -7,6 +7,7 @@
 #include "tsx_minimizer.h"
 #include "tsx_inflate.h"
 #include "tsx_output.h"
+#include "tsx_query.h"
 
 #include <mutex>
 #include <hip/hip_runtime.h>
@@ -2931,5 +2932,310 @@ extern "C" int tsx_hip_synth_zipf_device(uint64_t seed, uint64_t n_reads, uint32
     }
     if (hipStreamSynchronize(st) != hipSuccess) rc = TSX_HIP_EHIP;
     (void)hipFree(d_off); (void)hipFree(d_thr);
+    return rc;
+}
+
+// ---- read queries: per-record k-mer stats and the read filter (tsx_query.h) --------------------------------------
+static const size_t QUERY_CHUNK_DEFAULT = (size_t)256 << 20;   // text bytes per piece of the host entry points
+static const size_t QUERY_PIECE_MAX = (size_t)0xF0000000;      // a piece's line index is 32 bits wide
+
+static bool query_args_ok(const tsx_hip_map *m, uint64_t lower, uint64_t upper) {
+    // a shard answers 0 for the k-mers it does not own: its stats would be wrong, not partial
+    return m && lower <= upper && m->p.lg == m->p.l;
+}
+
+// The line passes of run_fastq_piece (tile line ends, then their exclusive scan from *d_carry) over [0, own_end).
+static int query_line_pass(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open, hipStream_t st) {
+    const uint64_t ntiles = (own_end + TILE - 1) / TILE;
+    if (ntiles > m->tile_cap) {
+        if (m->d_tile) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(m->d_tile)); m->d_tile = nullptr; }
+        m->tile_cap = ntiles + ntiles / 4 + 1024;
+        HIP_TRY(hipMalloc((void **)&m->d_tile, (m->tile_cap + m->tile_cap / SCAN_CHUNK + 16) * sizeof(uint32_t)));
+    }
+    const int g1 = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8);
+    hipLaunchKernelGGL(line_count_kernel, dim3(g1), dim3(NT), 0, st, d_text, n, own_end, head_open, m->d_tile, ntiles);
+    const uint64_t nchunks = (ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    uint32_t *chunk = m->d_tile + m->tile_cap;
+    hipLaunchKernelGGL(line_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const uint32_t *)m->d_tile,
+                       ntiles, chunk);
+    hipLaunchKernelGGL(line_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, m->d_carry);
+    hipLaunchKernelGGL(line_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, m->d_tile, ntiles,
+                       (const uint32_t *)chunk);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// query_reads_kernel over the start positions [0, own_end) of d_text (n readable bytes), after query_line_pass.
+static int query_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
+                        const unsigned long long *d_line_base, uint64_t lower, uint64_t upper, unsigned long long *d_stats,
+                        uint64_t cap, hipStream_t st) {
+    if (own_end == 0) return TSX_HIP_OK;
+    const uint64_t ntiles = (own_end + TILE - 1) / TILE;
+    const size_t lut_bytes = m->lut.size() * 8;
+    const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 4);
+    const uint32_t lshift = m->p.line_mask == 3 ? 2u : 1u;
+    DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((query_reads_kernel<WKV, CANV>), dim3(grid), dim3(NT), lut_bytes, st,
+                                                        m->p, d_text, n, own_end, head_open, (const uint32_t *)m->d_tile,
+                                                        ntiles, d_line_base, lshift, lower, upper, d_stats, (uint64_t)cap)));
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// Device texts in windows like tsx_hip_count_fastq_device; the line index of each window continues from a 64-bit
+// base on the device (the map's FASTQ scratch: word 0 of d_carry is the scan carry, words 2 and 3 the line base and
+// the record count).
+extern "C" int tsx_hip_query_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, uint64_t lower, uint64_t upper,
+                                          void *dev_stats, size_t stats_cap, size_t *n_records, void *stream) {
+    if (n_records) *n_records = 0;
+    if (!query_args_ok(m, lower, upper) || (!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_stats && stats_cap))
+        return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    int rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    unsigned long long *stats = (unsigned long long *)dev_stats;
+    unsigned long long *d_base = (unsigned long long *)m->d_carry + 2, *d_nrec = d_base + 1;
+    if (stats_cap) HIP_TRY(hipMemsetAsync(stats, 0, stats_cap * sizeof(tsx_hip_read_stats), st));
+    HIP_TRY(hipMemsetAsync(d_base, 0, 2 * sizeof(unsigned long long), st));
+    const uint8_t *base = (const uint8_t *)dev_text;
+    const size_t halo = (size_t)m->p.k - 1, WIN = dev_window_bytes();
+    const uint32_t lpr = m->p.line_mask + 1;
+    for (size_t off = 0; off < n; off += WIN) {
+        const size_t own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
+        const int head_open = off > 0 ? -1 : 0;
+        HIP_TRY(hipMemsetAsync(m->d_carry, 0, sizeof(uint32_t), st));
+        if ((rc = query_line_pass(m, base + off, len, own, head_open, st)) != TSX_HIP_OK) return rc;
+        if ((rc = query_launch(m, base + off, len, own, head_open, d_base, lower, upper, stats, stats_cap, st)) != TSX_HIP_OK)
+            return rc;
+        const bool last = off + own >= n;
+        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry, last ? 1 : 0,
+                           base + n - 1, lpr, d_nrec);
+    }
+    if (n == 0)
+        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry, 1,
+                           (const uint8_t *)nullptr, lpr, d_nrec);
+    if (stats_cap)
+        hipLaunchKernelGGL(query_finalize_kernel, dim3(grid_for(m, stats_cap, 8)), dim3(NT), 0, st, stats, (uint64_t)stats_cap,
+                           (const unsigned long long *)d_nrec, (uint64_t)0);
+    HIP_TRY(hipGetLastError());
+    unsigned long long nrec = 0;
+    HIP_TRY(hipMemcpyAsync(&nrec, d_nrec, sizeof nrec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n_records) *n_records = (size_t)nrec;
+    return nrec > stats_cap ? TSX_HIP_ERANGE : TSX_HIP_OK;
+}
+
+// Scratch of one host query / filter call.
+struct QueryBufs {
+    uint8_t *text = nullptr; size_t text_have = 0;
+    unsigned long long *stats = nullptr; size_t stats_have = 0;
+    unsigned long long *span = nullptr; size_t span_have = 0;
+    unsigned long long *koff = nullptr; size_t koff_have = 0;
+    uint8_t *out = nullptr; size_t out_have = 0;
+    unsigned long long *info = nullptr, *h_info = nullptr;   // cut, records, open, total, line base (0), kept
+    uint8_t *h_out = nullptr; size_t h_out_have = 0;
+    hipEvent_t ev = nullptr;
+    int init(hipStream_t st) {
+        HIP_TRY(hipMalloc((void **)&info, 8 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(info, 0, 8 * sizeof(unsigned long long), st));
+        HIP_TRY(hipHostMalloc((void **)&h_info, 8 * sizeof(unsigned long long), hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        return TSX_HIP_OK;
+    }
+    void release(hipStream_t st) {   // nothing queued may outlive the buffers
+        (void)hipStreamSynchronize(st);
+        for (void *p : {(void *)text, (void *)stats, (void *)span, (void *)koff, (void *)out, (void *)info}) if (p) (void)hipFree(p);
+        if (h_info) (void)hipHostFree(h_info);
+        if (h_out) (void)hipHostFree(h_out);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
+// One piece [0, len) of text in device memory that starts at a record boundary: the line pass, the record scan (where
+// the last whole record ends, and the spans when `spans`), then -- when it holds a whole record -- the stats of its
+// records [0, nrec) in b.stats.  Waits once, for the cut.  Not last and no whole record: nrec = 0, nothing queried.
+static int query_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint64_t len, bool last, uint64_t lower,
+                       uint64_t upper, bool spans, hipStream_t st, uint64_t &cut, uint64_t &nrec, bool &open) {
+    cut = nrec = 0; open = false;
+    if (len == 0) return TSX_HIP_OK;
+    const uint32_t lpr = m->p.line_mask + 1;
+    const uint64_t ntiles = (len + TILE - 1) / TILE, span_cap = len / (2 * lpr) + 2;
+    int rc;
+    HIP_TRY(hipMemsetAsync(m->d_carry, 0, sizeof(uint32_t), st));
+    if ((rc = query_line_pass(m, d_text, len, len, 0, st)) != TSX_HIP_OK) return rc;
+    if (spans && (rc = grow(st, b.span, b.span_have, span_cap * 16)) != TSX_HIP_OK) return rc;
+    hipLaunchKernelGGL(record_scan_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
+                       d_text, len, (const uint32_t *)m->d_tile, ntiles, (const uint32_t *)m->d_carry, lpr, last ? 1 : 0,
+                       b.info, spans ? b.span : nullptr, span_cap);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b.h_info, b.info, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    cut = b.h_info[0]; nrec = b.h_info[1]; open = b.h_info[2] != 0;
+    if (nrec == 0) return TSX_HIP_OK;
+    if ((rc = grow(st, b.stats, b.stats_have, nrec * sizeof(tsx_hip_read_stats))) != TSX_HIP_OK) return rc;
+    HIP_TRY(hipMemsetAsync(b.stats, 0, nrec * sizeof(tsx_hip_read_stats), st));
+    if ((rc = query_launch(m, d_text, cut, cut, 0, b.info + 4, lower, upper, b.stats, nrec, st)) != TSX_HIP_OK) return rc;
+    hipLaunchKernelGGL(query_finalize_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.stats, nrec,
+                       (const unsigned long long *)nullptr, nrec);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// The filter behind query_piece: kept lengths, their scan (total -> b.info[3], kept records -> b.info[5]), the
+// compaction into b.out (grown to the piece's worst case: cut + 1 bytes, rounded up).  Queued, not waited for.
+static int filter_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint64_t cut, uint64_t nrec, bool open,
+                        const tsx_hip_filter_rule &rule, hipStream_t st) {
+    const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    int rc = grow(st, b.koff, b.koff_have, (nk + nchunks + 16) * sizeof(unsigned long long));
+    if (rc == TSX_HIP_OK) rc = grow(st, b.out, b.out_have, cut + 64);
+    if (rc != TSX_HIP_OK) return rc;
+    HIP_TRY(hipMemsetAsync(b.koff + nrec, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(filter_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, (const unsigned long long *)b.stats,
+                       (const unsigned long long *)b.span, nrec, rule.min_in_range, (uint64_t)rule.fraction_ppm, rule.invert,
+                       open ? 1 : 0, b.koff, b.info + 5);
+    unsigned long long *chunk = b.koff + nk;
+    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)b.koff,
+                       nk, chunk);
+    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, b.info + 3);
+    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, b.koff, nk,
+                       (const unsigned long long *)chunk);
+    // (the copy grid covers the worst case; lanes past the total fall through)
+    hipLaunchKernelGGL(filter_copy_kernel, dim3(grid_for(m, (cut + 16) / 16 + 64, 8)), dim3(NT), 0, st, d_text, cut,
+                       (const unsigned long long *)b.span, (const unsigned long long *)b.koff, nrec, b.out, (uint64_t)b.out_have);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+static bool rule_ok(const tsx_hip_filter_rule *r) {
+    return r && r->lower <= r->upper && r->fraction_ppm <= 1000000u;
+}
+
+// The host entry points: the text in pieces cut at record boundaries, chunk_bytes at a time.  A piece that holds no
+// whole record (a record longer than the piece) grows until it does.  stats mode (fd < 0): each piece's stats go to
+// stats_out[rec_base ..] while they fit.  filter mode: the output of piece i is written to fd while the device works on
+// piece i + 1.
+static int query_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, uint64_t upper, size_t chunk_bytes,
+                      tsx_hip_read_stats *stats_out, size_t stats_cap, size_t *n_records, const tsx_hip_filter_rule *rule,
+                      int fd, uint64_t *kept_out, uint64_t *bytes_out) {
+    if (!chunk_bytes) chunk_bytes = QUERY_CHUNK_DEFAULT;
+    chunk_bytes = std::min(chunk_bytes, QUERY_PIECE_MAX);
+    HIP_TRY(hipSetDevice(m->device));
+    join_foreign(m, false);
+    hipStream_t st = m->stream;
+    int rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    QueryBufs b;
+    rc = b.init(st);
+    uint64_t rec_base = 0, kept = 0, bytes = 0, pending = 0;
+    bool have_pending = false;
+    for (size_t off = 0; off < n && rc == TSX_HIP_OK;) {
+        size_t len = std::min(chunk_bytes, n - off);
+        uint64_t cut = 0, nrec = 0;
+        bool open = false;
+        for (;;) {
+            const bool last = off + len == n;
+            if ((rc = grow(st, b.text, b.text_have, len + 256)) != TSX_HIP_OK) break;
+            if (hipMemcpyAsync(b.text, text + off, len, hipMemcpyHostToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            if ((rc = query_piece(m, b, b.text, len, last, lower, upper, rule != nullptr, st, cut, nrec, open)) != TSX_HIP_OK) break;
+            if (nrec || last) break;
+            if (len >= QUERY_PIECE_MAX) { g_last_error = "a record longer than 3.75 GiB"; rc = TSX_HIP_EINVAL; break; }
+            len = std::min(std::min(2 * len, n - off), QUERY_PIECE_MAX);
+        }
+        if (rc != TSX_HIP_OK) break;
+        if (!rule) {
+            if (rec_base < stats_cap && nrec &&
+                (hipMemcpyAsync(stats_out + rec_base, b.stats, std::min<uint64_t>(nrec, stats_cap - rec_base) * sizeof(tsx_hip_read_stats),
+                                hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+                rc = TSX_HIP_EHIP;
+        } else if (nrec) {
+            rc = filter_piece(m, b, b.text, cut, nrec, open, *rule, st);
+            if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.h_info + 3, b.info + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                                     hipEventRecord(b.ev, st) != hipSuccess))
+                rc = TSX_HIP_EHIP;
+            if (rc == TSX_HIP_OK && have_pending) {   // the previous piece's output, while the device works on this one
+                rc = write_all(fd, b.h_out, pending);
+                if (rc == TSX_HIP_OK) bytes += pending;
+                have_pending = false;
+            }
+            if (rc == TSX_HIP_OK && hipEventSynchronize(b.ev) != hipSuccess) rc = TSX_HIP_EHIP;
+            if (rc == TSX_HIP_OK && b.h_info[3] > cut + 1) { g_last_error = "filter output larger than its piece"; rc = TSX_HIP_EHIP; }
+            if (rc == TSX_HIP_OK) {
+                const uint64_t total = b.h_info[3];
+                kept += b.h_info[5];
+                if (total > b.h_out_have) {
+                    if (b.h_out) (void)hipHostFree(b.h_out);
+                    b.h_out = nullptr; b.h_out_have = 0;
+                    if (hipHostMalloc((void **)&b.h_out, total + total / 8 + 4096, hipHostMallocDefault) != hipSuccess) rc = TSX_HIP_ENOMEM;
+                    else b.h_out_have = total + total / 8 + 4096;
+                }
+                if (rc == TSX_HIP_OK && total && (hipMemcpyAsync(b.h_out, b.out, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                                                  hipStreamSynchronize(st) != hipSuccess))
+                    rc = TSX_HIP_EHIP;
+                pending = total;
+                have_pending = rc == TSX_HIP_OK;
+                // (the kept counter is per piece)
+                if (rc == TSX_HIP_OK && hipMemsetAsync(b.info + 5, 0, sizeof(unsigned long long), st) != hipSuccess) rc = TSX_HIP_EHIP;
+            }
+        }
+        rec_base += nrec;
+        off += cut;
+    }
+    if (rc == TSX_HIP_OK && have_pending) {
+        rc = write_all(fd, b.h_out, pending);
+        if (rc == TSX_HIP_OK) bytes += pending;
+    }
+    b.release(st);
+    if (n_records) *n_records = (size_t)rec_base;
+    if (kept_out) *kept_out = kept;
+    if (bytes_out) *bytes_out = bytes;
+    if (rc == TSX_HIP_OK && !rule && rec_base > stats_cap) rc = TSX_HIP_ERANGE;
+    return rc;
+}
+
+extern "C" int tsx_hip_query_reads_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, uint64_t upper,
+                                        tsx_hip_read_stats *stats_out, size_t stats_cap, size_t *n_records, size_t chunk_bytes) {
+    if (n_records) *n_records = 0;
+    if (!query_args_ok(m, lower, upper) || (!text && n) || (!stats_out && stats_cap)) return TSX_HIP_EINVAL;
+    return query_host(m, text, n, lower, upper, chunk_bytes, stats_out, stats_cap, n_records, nullptr, -1, nullptr, nullptr);
+}
+
+extern "C" int tsx_hip_filter_reads_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_filter_rule *rule, int fd,
+                                         size_t chunk_bytes, uint64_t *kept_out, uint64_t *bytes_out) {
+    if (kept_out) *kept_out = 0;
+    if (bytes_out) *bytes_out = 0;
+    if (!rule_ok(rule) || !query_args_ok(m, rule->lower, rule->upper) || (!text && n) || fd < 0) return TSX_HIP_EINVAL;
+    return query_host(m, text, n, rule->lower, rule->upper, chunk_bytes, nullptr, 0, nullptr, rule, fd, kept_out, bytes_out);
+}
+
+extern "C" int tsx_hip_filter_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_filter_rule *rule,
+                                           void *dev_out, size_t out_cap, size_t *out_bytes, uint64_t *kept_out, void *stream) {
+    if (out_bytes) *out_bytes = 0;
+    if (kept_out) *kept_out = 0;
+    if (!rule_ok(rule) || !query_args_ok(m, rule->lower, rule->upper) || (!dev_text && n) || ((uintptr_t)dev_text & 15) ||
+        !dev_out || ((uintptr_t)dev_out & 15) || n >= QUERY_PIECE_MAX)
+        return TSX_HIP_EINVAL;
+    if (out_cap < n + 64) return TSX_HIP_ERANGE;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    int rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    QueryBufs b;
+    rc = b.init(st);
+    b.out = (uint8_t *)dev_out; b.out_have = out_cap;   // the compaction writes the caller's buffer (never grown)
+    uint64_t cut = 0, nrec = 0, total = 0, kept = 0;
+    bool open = false;
+    if (rc == TSX_HIP_OK) rc = query_piece(m, b, (const uint8_t *)dev_text, n, true, rule->lower, rule->upper, true, st, cut, nrec, open);
+    if (rc == TSX_HIP_OK && nrec) {
+        rc = filter_piece(m, b, (const uint8_t *)dev_text, cut, nrec, open, *rule, st);
+        if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.h_info + 3, b.info + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                                 hipStreamSynchronize(st) != hipSuccess))
+            rc = TSX_HIP_EHIP;
+        if (rc == TSX_HIP_OK) { total = b.h_info[3]; kept = b.h_info[5]; }
+        if (rc == TSX_HIP_OK && total > cut + 1) { g_last_error = "filter output larger than its text"; rc = TSX_HIP_EHIP; }
+    }
+    b.out = nullptr;
+    b.release(st);
+    if (out_bytes) *out_bytes = (size_t)total;
+    if (kept_out) *kept_out = kept;
     return rc;
 }

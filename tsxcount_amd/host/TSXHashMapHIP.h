@@ -49,6 +49,35 @@ static uint64_t tsx_write_counts_file(const std::string &sPath, W fnWrite, C fnC
     return iLines;
 }
 
+// Read queries over one table (tsx_hip_query_reads_host / tsx_hip_filter_reads_host); fnCheck throws on an error code.
+template <typename C>
+static std::vector<tsx_hip_read_stats> tsx_query_reads(tsx_hip_map *pMap, const char *pText, size_t iBytes, uint64_t iLower,
+                                                       uint64_t iUpper, size_t iChunkBytes, C fnCheck) {
+    // a first guess of 256 bytes per record; a text with shorter records is queried again with the exact count
+    std::vector<tsx_hip_read_stats> out(iBytes / 256 + 16);
+    size_t n = 0;
+    int rc = tsx_hip_query_reads_host(pMap, pText, iBytes, iLower, iUpper, out.data(), out.size(), &n, iChunkBytes);
+    if (rc == TSX_HIP_ERANGE) {
+        out.resize(n);
+        rc = tsx_hip_query_reads_host(pMap, pText, iBytes, iLower, iUpper, out.data(), n, &n, iChunkBytes);
+    }
+    fnCheck(rc);
+    out.resize(n);
+    return out;
+}
+template <typename C>
+static std::pair<uint64_t, uint64_t> tsx_filter_reads(tsx_hip_map *pMap, const char *pText, size_t iBytes,
+                                                      const tsx_hip_filter_rule &oRule, const std::string &sPath,
+                                                      size_t iChunkBytes, C fnCheck) {
+    const int fd = open(sPath.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) throw TSXException("could not open " + sPath + " for writing", TSX_HIP_EIO);
+    uint64_t iKept = 0, iWritten = 0;
+    int rc = tsx_hip_filter_reads_host(pMap, pText, iBytes, &oRule, fd, iChunkBytes, &iKept, &iWritten);
+    if (close(fd) != 0 && rc == TSX_HIP_OK) rc = TSX_HIP_EIO;
+    fnCheck(rc);
+    return std::make_pair(iKept, iWritten);
+}
+
 class TSXHashMapHIP {
 public:
     // TSXHashMapCAS(iL, iStorageBits, iK, iThreads) (TSXHashMapCAS.h:239-245);
@@ -133,6 +162,17 @@ public:
         }, check);
     }
 
+    // per-record k-mer stats of a text against the table, records in text order (tsx_hip_query_reads_host)
+    std::vector<tsx_hip_read_stats> queryReads(const char *pText, size_t iBytes, uint64_t iLower = 1,
+                                               uint64_t iUpper = UINT64_MAX, size_t iChunkBytes = 0) {
+        return tsx_query_reads(m_pMap, pText, iBytes, iLower, iUpper, iChunkBytes, check);
+    }
+    // the records of a text that pass oRule into sPath (created / truncated); returns {records kept, bytes written}
+    std::pair<uint64_t, uint64_t> filterReads(const char *pText, size_t iBytes, const tsx_hip_filter_rule &oRule,
+                                              const std::string &sPath, size_t iChunkBytes = 0) {
+        return tsx_filter_reads(m_pMap, pText, iBytes, oRule, sPath, iChunkBytes, check);
+    }
+
     // FASTXreader<FASTAEntry> (FastXReader.h:97-116) reads two lines per record, FASTQEntry (:62-95) four
     void setRecordLines(int iLines) { check(tsx_hip_set_record_lines(m_pMap, iLines)); }
     // canonical counting: a k-mer and its reverse complement share one counter (empty table only)
@@ -205,6 +245,7 @@ public:
 
     const tsx_hip_layout &getLayout() const { return m_oLayout; }
     int size() const { return tsx_hip_group_size(m_pGroup); }
+    tsx_hip_map *rankMap(int iRank) { return tsx_hip_group_map(m_pGroup, iRank); }
     void setRecordLines(int iLines) { check(tsx_hip_group_set_record_lines(m_pGroup, iLines)); }
     // canonical counting on every GPU's table (the merge only: not with the minimizer exchange)
     void setCanonical(bool bOn) { check(tsx_hip_group_set_canonical(m_pGroup, bOn ? 1 : 0)); }

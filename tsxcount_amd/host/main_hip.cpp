@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -36,6 +37,12 @@ struct arguments {
     std::string output, histo;    // --output=FILE: "kmer<TAB>count" lines; --histo=FILE: "count<TAB>k-mers" lines
     uint64_t lower = 1, upper = UINT64_MAX;   // --lower / --upper: the counts --output writes
     uint64_t histo_max = 10000;   // --histo-max=H: counts 1..H, then one line H+1 for everything above
+    // read queries after the count: --filter=OUT writes the records of --filter-input (default --input) that pass the
+    // rule, --read-stats=FILE one line of k-mer stats per record
+    std::string filter, filter_input, read_stats;
+    uint64_t filter_lower = 2, filter_upper = UINT64_MAX, filter_min = 0;
+    double filter_fraction = 1.0;
+    bool filter_invert = false;
 };
 
 static bool opt(const char *arg, const char *name, std::string &val) {
@@ -50,11 +57,18 @@ static int usage() {
                  "                [--check] [--checkabort] [--seed=S] [--device=D] [--format=fastq|fasta] [--canonical]\n"
                  "                [--gpus=N [--comm=rccl|copy] [--devices=a,b,...] [--exchange=merge|mini|auto]]\n"
                  "                [--output=FILE [--lower=N] [--upper=N]] [--histo=FILE [--histo-max=H]]\n"
+                 "                [--filter=OUT] [--read-stats=FILE] [--filter-input=FILE] [--filter-lower=N] [--filter-upper=N]\n"
+                 "                [--filter-min=M] [--filter-fraction=F] [--filter-invert]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
                  "--canonical counts a k-mer and its reverse complement as one (the check then expects f(x) + f(rc x)).\n"
                  "--output writes every k-mer counted lower..upper times (default 1..unbounded) as kmer<TAB>count, in no\n"
                  "particular order. --histo writes count<TAB>number of k-mers for every count 1..H (default 10000) that\n"
-                 "occurs, then H+1<TAB>number of k-mers counted more than H times."
+                 "occurs, then H+1<TAB>number of k-mers counted more than H times.\n"
+                 "After the count, --filter writes the records of --filter-input (default: --input) whose k-mers pass: a\n"
+                 "k-mer is in range when its count lies in filter-lower..filter-upper (default 2..unbounded); a record passes\n"
+                 "with at least M (default 0) k-mers in range that make at least the share F (default 1.0) of its k-mers.\n"
+                 "--filter-invert writes the records that fail. --read-stats writes index<TAB>kmers<TAB>in_range<TAB>min<TAB>sum\n"
+                 "per record of the same input. One GPU only."
               << std::endl;
     return 1;
 }
@@ -143,6 +157,70 @@ static void write_outputs(Map &oMap, const arguments &a) {
         if (!f) throw TSXException("could not write " + a.histo, TSX_HIP_EIO);
         std::cerr << "Wrote the count histogram to " << a.histo << std::endl;
     }
+}
+
+static bool is_fasta_path(const std::string &path, const std::string &format) {
+    arguments b;
+    b.input_path = path;
+    b.format = format;
+    return is_fasta(b);
+}
+
+static bool wants_queries(const arguments &a) { return !a.filter.empty() || !a.read_stats.empty(); }
+
+// --filter and --read-stats on one table, after the count, the check and --output / --histo.  The input loads as the
+// counted one does; a BGZF file is inflated on the device.
+static int run_read_queries(tsx_hip_map *pMap, const arguments &a) {
+    auto check = [](int rc) {
+        if (rc == TSX_HIP_OK) return;
+        std::string msg = tsx_hip_strerror(rc);
+        if (rc == TSX_HIP_EHIP || rc == TSX_HIP_EIO || rc == TSX_HIP_ENOMEM) msg += std::string(" (") + tsx_hip_last_error() + ")";
+        throw TSXException(msg, rc);
+    };
+    const std::string path = a.filter_input.empty() ? a.input_path : a.filter_input;
+    std::vector<char> owned;
+    const char *text = nullptr;
+    size_t n = 0;
+    void *map = nullptr;
+    bool bgzf = false;
+    if (!load_input(path, owned, text, n, map, bgzf, true)) {
+        std::cerr << "Could not read " << path << std::endl;
+        return 3;
+    }
+    if (bgzf) {
+        size_t members = 0, tb = 0, got = 0;
+        check(tsx_hip_bgzf_index_host(text, n, &members, &tb));
+        std::vector<char> inflated(tb ? tb : 1);
+        check(tsx_hip_inflate_bgzf_host(a.device, text, n, inflated.data(), tb, &got));
+        munmap(map, n);
+        map = nullptr;
+        owned.swap(inflated);
+        owned.resize(got);
+        text = owned.data();
+        n = got;
+    }
+    check(tsx_hip_set_record_lines(pMap, is_fasta_path(path, a.format) ? 2 : 4));
+    if (!a.read_stats.empty()) {
+        const std::vector<tsx_hip_read_stats> st = tsx_query_reads(pMap, text, n, a.filter_lower, a.filter_upper, 0, check);
+        std::ofstream f(a.read_stats);
+        for (size_t i = 0; i < st.size(); ++i)
+            f << i << '\t' << st[i].kmers << '\t' << st[i].in_range << '\t' << st[i].min_count << '\t' << st[i].sum_count << '\n';
+        f.close();
+        if (!f) throw TSXException("could not write " + a.read_stats, TSX_HIP_EIO);
+        std::cerr << "Wrote the k-mer stats of " << st.size() << " records to " << a.read_stats << std::endl;
+    }
+    if (!a.filter.empty()) {
+        tsx_hip_filter_rule rule;
+        rule.lower = a.filter_lower;
+        rule.upper = a.filter_upper;
+        rule.min_in_range = a.filter_min;
+        rule.fraction_ppm = (uint32_t)std::llround(a.filter_fraction * 1e6);
+        rule.invert = a.filter_invert ? 1 : 0;
+        const std::pair<uint64_t, uint64_t> r = tsx_filter_reads(pMap, text, n, rule, a.filter, 0, check);
+        std::cerr << "Wrote " << r.first << " records (" << r.second << " bytes) to " << a.filter << std::endl;
+    }
+    if (map) munmap(map, n);
+    return 0;
 }
 
 // "Added a total of ..." and the --check of main.cpp:224-396, for one table or a group of them
@@ -255,7 +333,10 @@ static int run_group(const arguments &a) {
     double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (map) munmap(map, n);
     std::cerr << (oGroup.exchange() == 1 ? "descriptions moved between GPUs by the last share: " : "entries moved between GPUs by the merge: ") << oGroup.exchangedEntries() << std::endl;
-    return report_and_check(oGroup, a, dt);
+    const int rc = report_and_check(oGroup, a, dt);
+    if (!wants_queries(a)) return rc;
+    const int rq = run_read_queries(oGroup.rankMap(0), a);   // one GPU: its table holds every k-mer
+    return rc ? rc : rq;
 }
 
 int main(int argc, char *argv[]) {
@@ -282,6 +363,14 @@ int main(int argc, char *argv[]) {
         else if (opt(argv[i], "upper", v)) a.upper = strtoull(v.c_str(), nullptr, 10);
         else if (opt(argv[i], "histo", v)) a.histo = v;
         else if (opt(argv[i], "histo-max", v)) a.histo_max = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "filter", v)) { a.filter = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "filter-input", v)) a.filter_input = v;
+        else if (opt(argv[i], "filter-lower", v)) a.filter_lower = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "filter-upper", v)) a.filter_upper = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "filter-min", v)) a.filter_min = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "filter-fraction", v)) a.filter_fraction = atof(v.c_str());
+        else if (opt(argv[i], "filter-invert", v)) a.filter_invert = true;
+        else if (opt(argv[i], "read-stats", v)) { a.read_stats = v; if (v.empty()) return usage(); }
         else if (opt(argv[i], "devices", v)) {
             for (size_t at = 0; at < v.size();) {
                 const size_t c = v.find(',', at);
@@ -318,6 +407,13 @@ int main(int argc, char *argv[]) {
         return usage();
     }
     if (a.gpus < 1 || (a.comm != "rccl" && a.comm != "copy") || (!a.devices.empty() && (int)a.devices.size() != a.gpus)) return usage();
+    if (a.filter_lower > a.filter_upper || !(a.filter_fraction >= 0.0 && a.filter_fraction <= 1.0)) return usage();
+    if (wants_queries(a) && a.gpus > 1) {
+        std::cerr << "--filter and --read-stats run on one GPU only: every k-mer lives on one rank of a --gpus " << a.gpus
+                  << " run, and per-rank queries are not combined yet. Count with --gpus=1 (or without --gpus) to filter."
+                  << std::endl;
+        return usage();
+    }
     try {
         if (a.group) return run_group(a);
         std::cerr << "Creating TSXHashMap HIP" << std::endl;
@@ -351,7 +447,10 @@ int main(int argc, char *argv[]) {
         }
         double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (map) munmap(map, n);
-        return report_and_check(oMap, a, dt);
+        const int rc = report_and_check(oMap, a, dt);
+        if (!wants_queries(a)) return rc;
+        const int rq = run_read_queries(oMap.handle(), a);
+        return rc ? rc : rq;
     } catch (const TSXException &e) {
         std::cerr << "TSXException: " << e.what() << std::endl;
         return e.code() == TSX_HIP_EFULL ? 42 : 10;  // exit(42): TSXHashMap.h:340-343
