@@ -31,11 +31,7 @@ enum StatIdx {
     ST_SCRATCH2 = 6,
     ST_FALLBACK = 7,   // keys the partitioned path handed to insert_key (a list or log region was full)
     ST_SCRATCH3 = 8,   // reduction: sum of all counts
-    ST_DBG0 = 9,       // diagnostic builds (TSX_HIP_DEBUG bit 4): wave-rounds of the segment build ...
-    ST_DBG1 = 10,      // ... shader cycles inside its insert loop, summed over waves
-    ST_DBG2 = 11,      // ... lanes that probed, summed over rounds
-    ST_DBG3 = 12,      // ... rounds with fewer than 16 probing lanes
-    ST_DBG4 = 13,      // ... cycles of those rounds
+    // 9 .. 15: spare
     ST_N = 16
 };
 

@@ -207,7 +207,7 @@ __device__ __forceinline__ bool kmer_eq(const uint64_t (&a)[WK], const uint64_t 
 template <int WK, bool CANON = false>
 __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableParams p, const uint8_t *buf, uint64_t n,
                                                          uint64_t own_end, int head_open,
-                                                         const uint32_t *tile_line, uint64_t ntiles, int dbg) {
+                                                         const uint32_t *tile_line, uint64_t ntiles) {
     __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
     __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
     __shared__ uint64_t s_le[TILE / 64];
@@ -322,8 +322,7 @@ __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableP
                     s_dcnt[slot_of[j]] = 0;
                     s_dpos[slot_of[j]] = 0;
                 }
-                if (!(dbg & 1)) insert_key<WK>(p, hk[j], d);
-                else if (d == 0xFFFFFFFFFFULL) p.stats[ST_SCRATCH] = hk[j][0];  // keep the hash alive in ablation runs
+                insert_key<WK>(p, hk[j], d);
             }
             lds_barrier();
         }
@@ -501,7 +500,7 @@ __global__ __launch_bounds__(NT, 5) void strip_desc_kernel(TableParams p, const 
 // position is the smaller of the two.
 template <bool CANON = false>
 __global__ __launch_bounds__(NT, 4) void walk_log_kernel(TableParams p, const uint4 *desc, uint64_t desc_cap,
-                                                         const unsigned long long *desc_cnt, uint32_t nregions, int dbg,
+                                                         const unsigned long long *desc_cnt, uint32_t nregions,
                                                          uint64_t *log, uint64_t log_cap, unsigned long long *log_cnt,
                                                          uint32_t *hist, uint32_t hist_nb, uint32_t hist_shift,
                                                          uint64_t n_packed, int long_desc, int own_only,
@@ -544,10 +543,6 @@ __global__ __launch_bounds__(NT, 4) void walk_log_kernel(TableParams p, const ui
     uint32_t fill = 0;  // wave-uniform
     const uint32_t cap32 = (uint32_t)min(log_cap, (uint64_t)0xFFFFFFFFu);
     const TableParams *pk = (const TableParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    auto side_insert = [&](uint64_t hkey, uint64_t d) {
-        if (dbg & 1) return;
-        defer_append1(pk, hkey, d);
-    };
     auto is_mine = [&](uint64_t hk) -> bool {
         if (!own_only) return true;
         const uint64_t h1[1] = {hk};
@@ -649,7 +644,7 @@ __global__ __launch_bounds__(NT, 4) void walk_log_kernel(TableParams p, const ui
                             for (int q = 0; q < HOT_N; ++q)
                                 if (!hcnt[q]) { at = q; hkey[q] = key; break; }
                         if (at >= 0 && (uint64_t)hcnt[at] + tot < 0xFFFFFFF0ULL) hcnt[at] += tot;
-                        else side_insert(key, tot);
+                        else defer_append1(pk, key, tot);
                     }
                 }
             }
@@ -714,7 +709,7 @@ __global__ __launch_bounds__(NT, 4) void walk_log_kernel(TableParams p, const ui
                                     my_log[at] = key;
                                     atomicAdd(&my_hist[(uint32_t)(key >> hist_shift) & (hist_nb - 1)], 1u);
                                 } else {
-                                    side_insert(key, 1);  // region full: deferred list (or the exchanged hot list)
+                                    defer_append1(pk, key, 1);  // region full: deferred list (or the exchanged hot list)
                                 }
                             }
                             fill += (uint32_t)__builtin_popcountll(mk);
@@ -725,7 +720,7 @@ __global__ __launch_bounds__(NT, 4) void walk_log_kernel(TableParams p, const ui
         }
     }
     lds_barrier();
-    if (tid < (NT / 64) * HOT_N && s_hot_cnt[tid]) side_insert(s_hot_key[tid], s_hot_cnt[tid]);
+    if (tid < (NT / 64) * HOT_N && s_hot_cnt[tid]) defer_append1(pk, s_hot_key[tid], s_hot_cnt[tid]);
     if (emit_sum) {
         for (int d = 32; d > 0; d >>= 1) emitted += __shfl_down(emitted, d, 64);
         if (lane == 0 && emitted) atomicAdd(emit_sum, emitted);
@@ -882,7 +877,7 @@ __global__ __launch_bounds__(NT, 4) void strip_desc_wide_kernel(TableParams p, c
 // CANON: as walk_log_kernel, with the WK-limb mirror roll.
 template <int WK, bool CANON = false>
 __global__ __launch_bounds__(NT, 2) void walk_log_wide_kernel(TableParams p, const uint4 *desc, uint64_t desc_cap,
-                                                              const unsigned long long *desc_cnt, uint32_t nregions, int dbg,
+                                                              const unsigned long long *desc_cnt, uint32_t nregions,
                                                               uint64_t *log, uint64_t log_cap, unsigned long long *log_cnt,
                                                               uint32_t *hist, uint32_t hist_nb, uint32_t hist_shift) {
     constexpr int RW = RecWords<WK>::value;
@@ -974,7 +969,7 @@ __global__ __launch_bounds__(NT, 2) void walk_log_wide_kernel(TableParams p, con
     #pragma unroll
                             for (int t = 0; t < RW; ++t) o[t] = (t < WK) ? kc[t < WK ? t : 0] : 0ULL;
                             atomicAdd(&my_hist[(uint32_t)(kc[0] >> hist_shift) & (hist_nb - 1)], 1u);
-                        } else if (!(dbg & 1)) {
+                        } else {
                             uint64_t rec[RW];
     #pragma unroll
                             for (int t = 0; t < RW; ++t) rec[t] = (t < WK) ? kc[t < WK ? t : 0] : 0ULL;
@@ -1025,11 +1020,13 @@ __global__ __launch_bounds__(NT, 2) void walk_log_wide_kernel(TableParams p, con
                                     for (int t = 0; t < WK; ++t) hkey[q * WK + t] = s_homh[b * WK + t];
                                     break;
                                 }
-                        if (at >= 0 && (uint64_t)hcnt[at] + tot < 0xFFFFFFF0ULL) hcnt[at] += tot;
-                        else if (!(dbg & 1)) {
+                        // no room: the deferred list (tested first: in the other order the compiler keeps 12 more VGPRs)
+                        if (at < 0 || (uint64_t)hcnt[at] + tot >= 0xFFFFFFF0ULL) {
                             uint64_t rec[RW];
                             for (int t = 0; t < RW; ++t) rec[t] = (t < WK) ? s_homh[b * WK + (t < WK ? t : 0)] : 0ULL;
                             defer_append<RW>(pk, rec, tot);
+                        } else {
+                            hcnt[at] += tot;
                         }
                     }
                 }
@@ -1037,7 +1034,7 @@ __global__ __launch_bounds__(NT, 2) void walk_log_wide_kernel(TableParams p, con
         }
     }
     lds_barrier();
-    if (tid < (NT / 64) * HOT_N && s_hot_cnt[tid] && !(dbg & 1)) {
+    if (tid < (NT / 64) * HOT_N && s_hot_cnt[tid]) {
         uint64_t rec[RW];
         for (int t = 0; t < RW; ++t) rec[t] = (t < WK) ? s_hot_key[(size_t)tid * WK + (t < WK ? t : 0)] : 0ULL;
         defer_append<RW>(pk, rec, s_hot_cnt[tid]);

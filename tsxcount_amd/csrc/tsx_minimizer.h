@@ -65,7 +65,7 @@ __device__ __forceinline__ uint32_t mul24(uint32_t a, uint32_t b) {
 __global__ __launch_bounds__(MZ_NT) void desc_owner_split_kernel(TableParams p, const uint4 *desc, uint64_t desc_cap,
                                                                     const unsigned long long *desc_cnt, uint32_t nregions,
                                                                     uint32_t nranks, uint4 *out, uint64_t out_cap,
-                                                                    uint32_t *used, unsigned long long *hom_cnt, int merge,
+                                                                    uint32_t *used, unsigned long long *hom_cnt,
                                                                     uint32_t part, uint32_t nparts,
                                                                     const unsigned long long *hom_pre) {
     __shared__ uint32_t s_cnt[MZ_MAX_RANKS];    // descriptions of this round per owner
@@ -163,28 +163,26 @@ __global__ __launch_bounds__(MZ_NT) void desc_owner_split_kernel(TableParams p, 
             //      as this strip's neighbour) travels as ONE description from its first start, if it is at most 16 starts long:
             //      T = length of the run that ends at start 15, Ld = length of the run that begins at start 0
             uint32_t xm = 0, xo = 0, x0 = 0, x1 = 0, x2 = 0;     // the description of such a run
-            if (merge) {
-                const uint32_t eqn = ~((P0 ^ (P0 >> 1)) | (P1 ^ (P1 >> 1)) | (P2 ^ (P2 >> 1)) | (P3 ^ (P3 >> 1)));
-                const uint32_t cont = eqn & vm & (vm >> 1) & 0x7FFFu;    // bit i: starts i and i + 1 valid, one owner
-                uint32_t T = 0, Ld = 0;
-                if (vm >> 15) { const uint32_t y = ~cont << 17; T = 1u + (y ? (uint32_t)__clz((int)y) : 15u); }
-                if (vm & 1u) { const uint32_t nz = ~cont & 0x7FFFu; Ld = 1u + (nz ? (uint32_t)__ffs((int)nz) - 1u : 15u); }
-                const uint32_t ot = ((P0 >> 15) & 1u) | (((P1 >> 15) & 1u) << 1) | (((P2 >> 15) & 1u) << 2) | (((P3 >> 15) & 1u) << 3);
-                const uint32_t ol = (P0 & 1u) | ((P1 & 1u) << 1) | ((P2 & 1u) << 2) | ((P3 & 1u) << 3);
-                const uint32_t adj = (d.w >> 16) & 1u;
-                const uint32_t lead = Ld | (ol << 8) | (adj << 16), tail = T | (ot << 8);
-                const uint32_t lead_n = __shfl_down(lead, 1, 64), c2_n = __shfl_down(c2, 1, 64), tail_p = __shfl_up(tail, 1, 64);
-                const uint32_t L_n = lead_n & 0xFFu, T_p = tail_p & 0xFFu;
-                const bool fwd = lane < 63u && (lead_n >> 16) && T > 0u && L_n > 0u && ot == ((lead_n >> 8) & 0xFFu) && T + L_n <= 16u;
-                const bool bwd = lane > 0u && adj && T_p > 0u && Ld > 0u && (tail_p >> 8) == ol && T_p + Ld <= 16u;
-                if (bwd) vm &= ~((1u << Ld) - 1u);            // the strip before this one took them
-                if (fwd) {
-                    vm &= ~((0xFFFFu << (16u - T)) & 0xFFFFu);
-                    const uint32_t sft = 2u * (16u - T);      // 2 .. 30
-                    x0 = __funnelshift_r(c0, c1, sft); x1 = __funnelshift_r(c1, c2, sft); x2 = __funnelshift_r(c2, c2_n, sft);
-                    xm = (1u << (T + L_n)) - 1u;
-                    xo = ot;
-                }
+            const uint32_t eqn = ~((P0 ^ (P0 >> 1)) | (P1 ^ (P1 >> 1)) | (P2 ^ (P2 >> 1)) | (P3 ^ (P3 >> 1)));
+            const uint32_t cont = eqn & vm & (vm >> 1) & 0x7FFFu;    // bit i: starts i and i + 1 valid, one owner
+            uint32_t T = 0, Ld = 0;
+            if (vm >> 15) { const uint32_t y = ~cont << 17; T = 1u + (y ? (uint32_t)__clz((int)y) : 15u); }
+            if (vm & 1u) { const uint32_t nz = ~cont & 0x7FFFu; Ld = 1u + (nz ? (uint32_t)__ffs((int)nz) - 1u : 15u); }
+            const uint32_t ot = ((P0 >> 15) & 1u) | (((P1 >> 15) & 1u) << 1) | (((P2 >> 15) & 1u) << 2) | (((P3 >> 15) & 1u) << 3);
+            const uint32_t ol = (P0 & 1u) | ((P1 & 1u) << 1) | ((P2 & 1u) << 2) | ((P3 & 1u) << 3);
+            const uint32_t adj = (d.w >> 16) & 1u;
+            const uint32_t lead = Ld | (ol << 8) | (adj << 16), tail = T | (ot << 8);
+            const uint32_t lead_n = __shfl_down(lead, 1, 64), c2_n = __shfl_down(c2, 1, 64), tail_p = __shfl_up(tail, 1, 64);
+            const uint32_t L_n = lead_n & 0xFFu, T_p = tail_p & 0xFFu;
+            const bool fwd = lane < 63u && (lead_n >> 16) && T > 0u && L_n > 0u && ot == ((lead_n >> 8) & 0xFFu) && T + L_n <= 16u;
+            const bool bwd = lane > 0u && adj && T_p > 0u && Ld > 0u && (tail_p >> 8) == ol && T_p + Ld <= 16u;
+            if (bwd) vm &= ~((1u << Ld) - 1u);            // the strip before this one took them
+            if (fwd) {
+                vm &= ~((0xFFFFu << (16u - T)) & 0xFFFFu);
+                const uint32_t sft = 2u * (16u - T);      // 2 .. 30
+                x0 = __funnelshift_r(c0, c1, sft); x1 = __funnelshift_r(c1, c2, sft); x2 = __funnelshift_r(c2, c2_n, sft);
+                xm = (1u << (T + L_n)) - 1u;
+                xo = ot;
             }
             // ---- one description per owner present in the strip: places by LDS counters, MZ_ROUND owners per round
             uint32_t left = vm;

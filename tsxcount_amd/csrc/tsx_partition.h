@@ -241,7 +241,7 @@ __global__ __launch_bounds__(NT) void partition_ring_kernel(
     TableParams p, const uint64_t *src, const unsigned long long *src_start, const unsigned long long *src_cnt,
     uint64_t src_cap, uint32_t nregions, uint32_t cpr, uint64_t *dst, const unsigned long long *offs,
     const unsigned long long *offs_base, unsigned long long *dst_cnt, uint64_t dst_cap, uint32_t nb, uint32_t shift,
-    uint32_t capbits, int dbg, uint64_t *ovq_all, uint32_t *ovq_cnt, uint32_t ovq_cap,
+    uint32_t capbits, uint64_t *ovq_all, uint32_t *ovq_cnt, uint32_t ovq_cap,
     const unsigned long long *src_pcnt, uint32_t src_np, uint64_t src_pcap, int dst_bm, unsigned long long *key_sum,
     uint32_t dst_r0, uint32_t dst_nr, int fmt, uint32_t dch, const uint32_t *skew_flag) {
     constexpr int RPT = (PART_WPT >= RW) ? PART_WPT / RW : 1;   // records per thread per batch
@@ -337,7 +337,6 @@ __global__ __launch_bounds__(NT) void partition_ring_kernel(
     // one word of a burst: word q of the burst that starts at ring index hd of `ring` and at destination `at`
     auto put_word = [&](uint64_t w, const uint64_t *ring, uint32_t hd, uint32_t q, unsigned long long at,
                         unsigned long long lim) {
-        if (dbg & 256) return;  // ablation: no stores
         if (at + q < lim) { dst[at + q] = (RW == 1 && fmt) ? format_record(p, w) : w; return; }   // (fmt: see format_record)
         if ((q & (RW - 1)) == 0) {   // sub-list full: the lane that holds the record's first word spills all of it
             uint64_t rec[RW];
@@ -373,7 +372,6 @@ __global__ __launch_bounds__(NT) void partition_ring_kernel(
         lds_barrier();
         between();
         const uint32_t oct = tid >> 3, ol = tid & 7;  // (B): an octet of lanes per job
-        if (dbg & 512) return;  // ablation: bookkeeping only
         const uint32_t njobs = s_njobs[par];
         for (uint32_t j0 = 0; j0 < njobs; j0 += PART_ITER * (NT / 8)) {
             unsigned long long meta[PART_ITER], lim[PART_ITER];
@@ -506,7 +504,7 @@ __global__ __launch_bounds__(NT) void partition_ring_kernel(
                         uint64_t *ring = s_stage + ((size_t)b << capbits) + (slot[q] & cmask);
 #pragma unroll
                         for (int t = 0; t < RW; ++t) ring[t] = cur[q][t];
-                    } else if (!(dbg & 256)) {  // ring full: take the next place of the list directly
+                    } else {  // ring full: take the next place of the list directly
                         const unsigned long long at = atomicAdd(&s_cur[b], (unsigned long long)RW);
                         if (at < s_lim[b]) {
                             if (RW == 1 && fmt) dst[at] = format_record(p, cur[q][0]);
@@ -568,7 +566,7 @@ __global__ __launch_bounds__(NT) void partition_ring_kernel(
             const uint64_t li = dst_bm ? ((uint64_t)b * dst_nr + dst_r0 + r) * cpr + c : ((uint64_t)r * nb + b) * cpr + c;
             dst_cnt[li] = (min(s_cur[b], s_lim[b]) - li * dst_cap * RW) / RW;
         }
-    if (tid < OVF_N && s_sp.ovc[tid] && !(dbg & 1)) {   // hot keys: one deferred entry each, with the total
+    if (tid < OVF_N && s_sp.ovc[tid]) {   // hot keys: one deferred entry each, with the total
         uint64_t rec[RW];
 #pragma unroll
         for (int t = 0; t < RW; ++t) rec[t] = s_sp.ovk[tid * RW + t];
@@ -646,7 +644,7 @@ __global__ __launch_bounds__(256) void desc_pack_kernel(const uint4 *desc, uint6
 // key of a position is the smaller of the two; the homopolymer keys are those of the pairs A/T and C/G.
 template <int NT, bool CANON = false>   // 512 threads, two workgroups per CU (up to 256 level-1 lists); 1024 threads where 512 lists leave room for one
 __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const uint4 *desc, uint64_t desc_cap,
-                                                            const unsigned long long *desc_cnt, uint32_t nregions, int dbg,
+                                                            const unsigned long long *desc_cnt, uint32_t nregions,
                                                             uint64_t *dst, uint64_t dst_cap, unsigned long long *dst_cnt,
                                                             uint32_t nb, uint32_t shift, uint64_t *ovq_all,
                                                             uint32_t *ovq_cnt, uint32_t ovq_cap, uint64_t n_packed,
@@ -717,10 +715,6 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
     const uint32_t ngrp = (2u * k + 3u) / 4u;
 
     const TableParams *pk = (const TableParams *)__builtin_amdgcn_kernarg_segment_ptr();
-    auto side_insert = [&](uint64_t hkey, uint64_t d) {
-        if (dbg & 1) return;
-        defer_append1(pk, hkey, d);
-    };
     // a key that found its sub-list full: spill cache (a hot key hits it), overflow queue, deferred list
     auto spill = [&](uint64_t key) {
         ++spilled;
@@ -735,7 +729,7 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
             const uint32_t at = atomicAdd(&s_ovn, 1u);
             if (at < ovq_cap) { ovq[at] = key; return; }
         }
-        side_insert(key, 1);
+        defer_append1(pk, key, 1);
     };
     uint32_t round = 0;
     // partition_ring_kernel's flush for one-word records and fixed-capacity lists: (A) one thread per list decides
@@ -901,7 +895,7 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
                             for (int q = 0; q < HOT_N; ++q)
                                 if (!hcnt[q]) { at = q; hkey[q] = key; break; }
                         if (at >= 0 && (uint64_t)hcnt[at] + tot < 0xFFFFFFF0ULL) hcnt[at] += tot;
-                        else side_insert(key, tot);
+                        else defer_append1(pk, key, tot);
                     }
                 }
             }
@@ -971,9 +965,9 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
     flush(true, false);
     lds_barrier();
     for (uint32_t b = tid; b < nb; b += NT) dst_cnt[(uint64_t)b * dst_gtot + gl] = min(s_cur[b], cap32);
-    if (tid < OVF_N && s_ovc[tid] && !(dbg & 1)) side_insert(s_ovk[tid] ^ OVF_SALT, s_ovc[tid]);
+    if (tid < OVF_N && s_ovc[tid]) defer_append1(pk, s_ovk[tid] ^ OVF_SALT, s_ovc[tid]);
     if (tid == 0 && ovq_cnt) ovq_cnt[blockIdx.x] = min(s_ovn, ovq_cap);
-    if (tid < (NT / 64) * HOT_N && s_hot_cnt[tid]) side_insert(s_hot_key[tid], s_hot_cnt[tid]);
+    if (tid < (NT / 64) * HOT_N && s_hot_cnt[tid]) defer_append1(pk, s_hot_key[tid], s_hot_cnt[tid]);
     if (emit_sum) {
         for (int d = 32; d > 0; d >>= 1) emitted += __shfl_down(emitted, d, 64);
         if (lane == 0 && emitted) atomicAdd(emit_sum, emitted);
@@ -1289,13 +1283,12 @@ __device__ __forceinline__ uint32_t pass_total(uint32_t mine, uint32_t wi, uint3
 
 // PRE: the lists hold PRE-FORMATTED records (format_record below: level 2 wrote them that way) -- the slot image of the
 // key without reprobe count and counter, with the first probe position above it: the hand-out is a mask and a shift.
-template <bool DIAG, bool PRE>   // DIAG: the ablation / diagnostic switches of TSX_HIP_DEBUG are compiled in
+template <bool PRE>
 __global__ __launch_bounds__(1024) void build_segments_stream_kernel(TableParams p, const uint64_t *lists,
                                                                      const unsigned long long *list_start,
                                                                      const unsigned long long *list_cnt,
                                                                      uint64_t list_cap, uint32_t pieces, uint32_t nseg,
-                                                                     int dbg_arg, int fresh, int look_ahead) {
-    const int dbg = DIAG ? dbg_arg : 0;
+                                                                     int fresh) {
     extern __shared__ uint64_t s_seg[];  // 2^S slots, then four batches of 64 keys per wave
     const uint32_t nslots = 1u << p.S;
     const uint32_t tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
@@ -1388,7 +1381,7 @@ __global__ __launch_bounds__(1024) void build_segments_stream_kernel(TableParams
         }
         lds_barrier();
         const uint32_t npass = ((mine + 63u) / 64u + nw * BK - 1u) / (nw * BK);   // wave-group uniform
-        for (uint32_t pass = 0; pass < npass && !(dbg & 2); ++pass) {
+        for (uint32_t pass = 0; pass < npass; ++pass) {
             if (pass > 0) load_batches(base, mine, wi, nw, pass, lane, B);   // long lists only: not prefetched
             const uint32_t total = __builtin_amdgcn_readfirstlane(pass_total(mine, wi, nw, pass));   // (a scalar, said so)
             uint32_t cb = 0, off = 0, taken = 0;    // wave-uniform: current batch, keys consumed of it, keys consumed in all
@@ -1404,11 +1397,9 @@ __global__ __launch_bounds__(1024) void build_segments_stream_kernel(TableParams
             // The loop is bound by instruction issue (16 waves share 4 SIMDs: every instruction of the round costs
             // the round ~8 cycles; the LDS pipe would allow ~430 cycles per round, scripts/lds_cas_chain.hip), so it
             // is kept lean: a lane's state is (e0, q, i) with i == 0 meaning "holds no key"; nothing else lives
-            // across rounds, the diagnostic switches are compiled out of the production instance.
+            // across rounds.
             uint32_t e0_lo = 0, e0_hi = 0;
             uint32_t i = 0, q = 0;
-            unsigned long long d_rounds = 0, d_t0 = 0;
-            if (DIAG && (dbg & 16)) d_t0 = __builtin_amdgcn_s_memtime();
             // one probe for every lane that holds a key
             auto probe = [&]() {
                 if (i != 0u) {
@@ -1431,7 +1422,6 @@ __global__ __launch_bounds__(1024) void build_segments_stream_kernel(TableParams
                         atomicAdd(&p.stats[ST_FAIL], 1ULL);
                         placed = true;
                     }
-                    if (DIAG && (dbg & 8)) placed = true;   // ablation: every key 'placed' by its first probe
                     ++i;
                     q = (q + i) & smask;
                     if (placed) i = 0u;
@@ -1470,11 +1460,10 @@ __global__ __launch_bounds__(1024) void build_segments_stream_kernel(TableParams
                         ring[(((cb + 3u) & 3u) << 6) + lane] = pick_batch(B, cb + 3u);
                     }
                 }
-                if (DIAG) ++d_rounds;
                 probe();
             }
             // ---- the stream is dry: the batch registers take the next segment's first batches
-            if (pass + 1u == npass && look_ahead < 4) {
+            if (pass + 1u == npass) {
                 nx_seg = 0xFFFFFFFFu;
                 if (seg2 < nseg) {
                     nx_n = seg_total(sizes2);
@@ -1493,9 +1482,8 @@ __global__ __launch_bounds__(1024) void build_segments_stream_kernel(TableParams
             // next round's CAS goes.  (Seven positions instead of three: no better, 6.04 vs 5.97 ms; looking ahead in
             // every round, not only in the tail: worse, 6.73 ms -- the main phase is bound by instruction issue.)
             while (__ballot(i != 0u) != 0ULL) {
-                if (DIAG) ++d_rounds;
                 probe();
-                if (look_ahead && i != 0u && i + 3u < maxr) {
+                if (i != 0u && i + 3u < maxr) {
                     const uint32_t q1 = (q + i + 1u) & smask, q2 = (q1 + i + 2u) & smask, q3 = (q2 + i + 3u) & smask;
                     const uint64_t v0 = s_seg[q], v1 = s_seg[q1], v2 = s_seg[q2];
                     const uint64_t e0 = ((uint64_t)e0_hi << 32) | e0_lo;
@@ -1507,15 +1495,10 @@ __global__ __launch_bounds__(1024) void build_segments_stream_kernel(TableParams
                     else if (t0) { i += 1u; q = q1; }
                 }
             }
-            if (DIAG && (dbg & 16) && lane == 0) {
-                atomicAdd(&p.stats[ST_DBG0], d_rounds);
-                atomicAdd(&p.stats[ST_DBG1], (unsigned long long)(__builtin_amdgcn_s_memtime() - d_t0));
-            }
         }
         lds_barrier();
-        if (!(dbg & 4))
-            for (uint32_t i = tid * 2; i < nslots; i += nt * 2)
-                *reinterpret_cast<uint4 *>(&slots[i]) = *reinterpret_cast<const uint4 *>(&s_seg[i]);
+        for (uint32_t i = tid * 2; i < nslots; i += nt * 2)
+            *reinterpret_cast<uint4 *>(&slots[i]) = *reinterpret_cast<const uint4 *>(&s_seg[i]);
         if (tid == 0) p.seg_dirty[seg] = 1;
     }
 }

@@ -38,12 +38,7 @@ static thread_local std::string g_last_error;
         }                                                                                \
     } while (0)
 
-static int scan_wg_per_cu() {  // walk_log_kernel workgroups per CU
-    static int v = 0;
-    if (!v) { v = 5; if (const char *e = getenv("TSX_HIP_SCAN_WGS")) v = std::min(16, std::max(1, atoi(e))); }
-    return v;
-}
-#define SCAN_WG_PER_CU scan_wg_per_cu()
+static const int SCAN_WG_PER_CU = 5;  // walk_log_kernel workgroups per CU
 static const uint32_t OVQ_CAP = 2048;  // keys per overflow queue (one queue per level-2 workgroup: 32 MiB at 2048 workgroups)
 static const size_t STAGE_PIECE_DEFAULT = (size_t)64 << 20;  // bytes of FASTQ per host piece
 
@@ -98,7 +93,6 @@ struct tsx_hip_map {
     uint64_t *d_small = nullptr;     // scratch of tsx_hip_get_counts_host / tsx_hip_lookup_host for a few k-mers
     bool attr_done = false;          // dynamic-LDS limits of the partition / build kernels set on this map's device
     int timing = 0;
-    int dbg = 0;                     // TSX_HIP_DEBUG: bit0 = skip the global insert (ablation builds only)
     std::vector<hipEvent_t> ev;      // seven per piece: before pass 1, before pass 3, after pass 3, start of the
                                      // partition phase (later than the scan's end only in a sharded run: the
                                      // exchange lies between), after level 1, level 2, build
@@ -500,7 +494,6 @@ extern "C" int tsx_hip_create_shard(tsx_hip_map **out, int k, int l, int storage
         return TSX_HIP_ENODEVICE;
     }
     m->device = device; m->seed = hash_seed;
-    if (const char *e = getenv("TSX_HIP_DEBUG")) m->dbg = atoi(e);
     if (const char *e = getenv("TSX_HIP_PATH")) m->path = atoi(e);
     if (const char *e = getenv("TSX_HIP_PIECE_BYTES")) {
         const long long v = atoll(e);
@@ -839,10 +832,6 @@ static int plan_partition(tsx_hip_map *m, uint64_t maxrec, int g, bool own_log, 
     pl.nseg = 1u << nsegbits;
     // fan-out per level is capped at 512 (histogram of the scan kernel and ring staging live in LDS)
     pl.b1 = std::min(9, (nsegbits <= 8) ? nsegbits : (nsegbits + 1) / 2);
-    if (const char *e = getenv("TSX_HIP_B1")) {   // experiments: the split between the two levels
-        const int b = atoi(e);
-        if (b >= 1 && b <= 9 && nsegbits - b >= 1 && nsegbits - b <= 9) pl.b1 = b;
-    }
     pl.b2 = nsegbits - pl.b1;
     pl.nb1 = 1u << pl.b1; pl.nb2 = 1u << pl.b2;
     pl.hist_nb = hist_nb_override ? hist_nb_override : pl.nb1;
@@ -906,9 +895,8 @@ static int plan_partition(tsx_hip_map *m, uint64_t maxrec, int g, bool own_log, 
         HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<4, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
         HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<2, 1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
         HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<4, 1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)build_segments_stream_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
-        HIP_TRY(hipFuncSetAttribute((const void *)build_segments_stream_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
-        HIP_TRY(hipFuncSetAttribute((const void *)build_segments_stream_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
+        HIP_TRY(hipFuncSetAttribute((const void *)build_segments_stream_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
+        HIP_TRY(hipFuncSetAttribute((const void *)build_segments_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
         HIP_TRY(hipFuncSetAttribute((const void *)build_segments_wide_stream_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
         HIP_TRY(hipFuncSetAttribute((const void *)build_segments_wide_stream_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
         HIP_TRY(hipFuncSetAttribute((const void *)build_segments_wide_stream_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
@@ -964,7 +952,6 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
         const uint32_t mean = std::max<uint32_t>(1, RING_NT * PART_WPT / nb);
         uint32_t bits = 4;
         while ((1u << bits) < PART_FLUSH + 2 * mean && bits < 6) ++bits;
-        if (const char *e = getenv("TSX_HIP_RING_BITS")) bits = (uint32_t)std::min(6, std::max(4, atoi(e)));   // experiments
         return bits;
     };
     auto part_lds = [](uint32_t nb, uint32_t bits) { return (size_t)nb * (((size_t)8 << bits) + 36); };
@@ -978,7 +965,7 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
         hipLaunchKernelGGL((partition_ring_kernel<RWV, NTV>), dim3(pl.g), dim3(NTV), part_lds(pl.nb1, bits), st,                 \
                            pp, src, region_start, (const unsigned long long *)pl.c_log, src_cap, (uint32_t)pl.g, 1u,             \
                            pl.buf1, (const unsigned long long *)pl.d_offs, (const unsigned long long *)pl.c_bstart,              \
-                           (unsigned long long *)nullptr, (uint64_t)0, pl.nb1, (uint32_t)(p.l - pl.b1), bits, m->dbg,            \
+                           (unsigned long long *)nullptr, (uint64_t)0, pl.nb1, (uint32_t)(p.l - pl.b1), bits,                    \
                            (uint64_t *)nullptr, (uint32_t *)nullptr, 0u, (const unsigned long long *)nullptr, 0u, (uint64_t)0,   \
                            0, (unsigned long long *)nullptr, 0u, 0u, 0, 0u, (const uint32_t *)nullptr)
         // (512 lists: the rings leave room for one workgroup per CU -- 1024 threads then, 16 waves either way)
@@ -995,10 +982,8 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
     uint32_t pieces = 1;
     uint32_t nq2 = 0;
     // level 2 leaves PRE-FORMATTED records (format_record, tsx_partition.h) where the stream build of one-limb keys and
-    // slots reads them and the fields fit: slot image in bits [0, R + F), first probe position above (TSX_HIP_BUILD_PRE=0: raw keys)
-    static int pre_ok = -1;
-    if (pre_ok < 0) { const char *e = getenv("TSX_HIP_BUILD_PRE"); pre_ok = e ? atoi(e) : 1; }
-    const int pre = (pre_ok && pl.b2 && p.wk == 1 && p.W == 1 && !m->dbg && p.R + p.F >= 32 && p.R + p.F + p.S <= 64) ? 1 : 0;
+    // slots reads them and the fields fit: slot image in bits [0, R + F), first probe position above
+    const int pre = (pl.b2 && p.wk == 1 && p.W == 1 && p.R + p.F >= 32 && p.R + p.F + p.S <= 64) ? 1 : 0;
     if (pl.b2) {  // level 2: cpr2 workgroups per level-1 bucket, each with its own sub-list per segment
         const uint32_t bits = ring_bits(pl.nb2);
         nq2 = pl.nb1 * pl.cpr2;   // one overflow queue per workgroup (the fused scan's queues follow them)
@@ -1013,24 +998,18 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
         }
         // Which form of the level-2 kernel works (partition_ring_kernel: SKEW) is decided on the device: skew_probe_kernel
         // samples every bucket and raises the flag -- the last word of the overflow-queue counters -- when it finds a hot
-        // key; both forms are launched, per bucket one of them returns at once.  TSX_HIP_SKEW=0|1 forces the plain / the skew form.
-        static int skew_force = -2;
-        if (skew_force == -2) { const char *e = getenv("TSX_HIP_SKEW"); skew_force = e ? atoi(e) : -1; }
+        // key; both forms are launched, per bucket one of them returns at once.
         uint32_t *d_skew = m->d_ovq_cnt + m->ovq_queues / rw;   // (ensure_ovq keeps one spare counter behind the queues')
-        if (skew_force >= 0) {
-            HIP_TRY(hipMemsetAsync(d_skew, skew_force ? 1 : 0, (size_t)pl.nb1 * 4, st));   // (any non-zero word means "skewed")
-        } else {
-            DISPATCH_RW(rw, hipLaunchKernelGGL((skew_probe_kernel<RWV>), dim3(pl.nb1), dim3(256), 0, st, (const uint64_t *)pl.buf1,
-                                               (const unsigned long long *)pl.c_bstart, (const unsigned long long *)pl.c_bcnt,
-                                               (const unsigned long long *)(pl.fused ? pl.c_l1 : nullptr), pl.G1, pl.cap1, d_skew));
-        }
+        DISPATCH_RW(rw, hipLaunchKernelGGL((skew_probe_kernel<RWV>), dim3(pl.nb1), dim3(256), 0, st, (const uint64_t *)pl.buf1,
+                                           (const unsigned long long *)pl.c_bstart, (const unsigned long long *)pl.c_bcnt,
+                                           (const unsigned long long *)(pl.fused ? pl.c_l1 : nullptr), pl.G1, pl.cap1, d_skew));
         // (512 lists of one-word records: the rings leave room for one workgroup per CU -- 1024 threads then)
 #define TSX_LEVEL2(RWV, NTV, SK, BITS)                                                                                          \
         hipLaunchKernelGGL((partition_ring_kernel<RWV, NTV, SK>), dim3(pl.nb1 * pl.cpr2), dim3(NTV), part_lds(pl.nb2, BITS), st,  \
                            pp, (const uint64_t *)pl.buf1, (const unsigned long long *)pl.c_bstart,                              \
                            (const unsigned long long *)pl.c_bcnt, (uint64_t)0, pl.nb1, pl.cpr2, m->d_buf[0],                    \
                            (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, pl.c_seg, pl.cap_sub,      \
-                           pl.nb2, (uint32_t)p.S, BITS, m->dbg, m->d_ovq, m->d_ovq_cnt, OVQ_CAP,                                 \
+                           pl.nb2, (uint32_t)p.S, BITS, m->d_ovq, m->d_ovq_cnt, OVQ_CAP,                                         \
                            (const unsigned long long *)(pl.fused ? pl.c_l1 : nullptr), pl.G1, pl.cap1, 0,                       \
                            (unsigned long long *)nullptr, 0u, 0u, pre, dch, (const uint32_t *)d_skew)
         if (part_lds(pl.nb2, bits) > ((size_t)80 << 10)) {
@@ -1044,55 +1023,40 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
     }
     if (ev) HIP_TRY(hipEventRecord(ev[5], st));
     const int fresh = m->fresh ? 1 : 0;
-    if (!(m->dbg & 64)) {  // ablation: bit 6 skips the build (partition timing experiments)
-        const int gb = (int)std::min<uint32_t>(pl.nseg, (uint32_t)m->cus * 16);
-        const size_t seg_bytes = ((size_t)8 << p.S) * p.W;
-        static int build_la = -1;   // TSX_HIP_BUILD_LOOKAHEAD=0|1: the tail's look-ahead over the next probe positions
-        if (build_la < 0) { const char *e = getenv("TSX_HIP_BUILD_LOOKAHEAD"); build_la = e ? atoi(e) : 1; }
-        if (p.wk == 1 && p.W == 1) {
-            if (m->dbg)   // the instance with the ablation / diagnostic switches compiled in
-                hipLaunchKernelGGL((build_segments_stream_kernel<true, false>), dim3(gb), dim3(1024), seg_bytes + (32 << 10), st, pp,
-                                   lists, lists_start, lists_cnt, lists_cap, pieces, pl.nseg, m->dbg, fresh, build_la);
-            else {
-                // TSX_HIP_BUILD_SNT: threads per workgroup of the stream build (1024; 512 with TSX_HIP_SEG_BITS=13 puts two
-                // workgroups on a CU: 64 KiB segment + 16 KiB of rings each)
-                int snt = 1024;
-                if (const char *e = getenv("TSX_HIP_BUILD_SNT")) snt = std::min(1024, std::max(64 * (int)pieces, atoi(e) & ~63));
-                if (pre)
-                    hipLaunchKernelGGL((build_segments_stream_kernel<false, true>), dim3(gb), dim3(snt), seg_bytes + (size_t)(snt / 64) * 2048, st, pp,
-                                       lists, lists_start, lists_cnt, lists_cap, pieces, pl.nseg, 0, fresh, build_la);
-                else
-                    hipLaunchKernelGGL((build_segments_stream_kernel<false, false>), dim3(gb), dim3(snt), seg_bytes + (size_t)(snt / 64) * 2048, st, pp,
-                                       lists, lists_start, lists_cnt, lists_cap, pieces, pl.nseg, 0, fresh, build_la);
-            }
-        } else {   // multi-limb keys and / or slots: wave streams too (64 records of LDS per wave behind the segment)
-            // a segment of <= 64 KiB (TSX_HIP_SEG_BITS): 512 threads, two workgroups per CU -- one sweeps while the other inserts
-            int wnt = (seg_bytes <= ((size_t)64 << 10)) ? 512 : 1024;
-            if (const char *e = getenv("TSX_HIP_BUILD_WNT")) wnt = std::min(1024, std::max(64 * (int)pieces, atoi(e) & ~63));
-            const size_t ring_bytes = (size_t)(wnt / 64) * 64 * 8 * rw;
-            DISPATCH_WK(m, hipLaunchKernelGGL((build_segments_wide_stream_kernel<WKV>), dim3(gb), dim3(wnt),
-                                              seg_bytes + ring_bytes, st, pp, lists, lists_start, lists_cnt, lists_cap, pieces,
-                                              pl.nseg, fresh));
-        }
-        HIP_TRY(hipGetLastError());
-        m->fresh = false;   // every segment has been written: built, or zeroed
+    const int gb = (int)std::min<uint32_t>(pl.nseg, (uint32_t)m->cus * 16);
+    const size_t seg_bytes = ((size_t)8 << p.S) * p.W;
+    if (p.wk == 1 && p.W == 1) {   // 1024 threads: the segment + 16 waves' rings of 2 KiB
+        const size_t lds = seg_bytes + (size_t)(1024 / 64) * 2048;
+        if (pre)
+            hipLaunchKernelGGL((build_segments_stream_kernel<true>), dim3(gb), dim3(1024), lds, st, pp,
+                               lists, lists_start, lists_cnt, lists_cap, pieces, pl.nseg, fresh);
+        else
+            hipLaunchKernelGGL((build_segments_stream_kernel<false>), dim3(gb), dim3(1024), lds, st, pp,
+                               lists, lists_start, lists_cnt, lists_cap, pieces, pl.nseg, fresh);
+    } else {   // multi-limb keys and / or slots: wave streams too (64 records of LDS per wave behind the segment)
+        // a segment of <= 64 KiB (TSX_HIP_SEG_BITS): 512 threads, two workgroups per CU -- one sweeps while the other inserts
+        const int wnt = (seg_bytes <= ((size_t)64 << 10)) ? 512 : 1024;
+        const size_t ring_bytes = (size_t)(wnt / 64) * 64 * 8 * rw;
+        DISPATCH_WK(m, hipLaunchKernelGGL((build_segments_wide_stream_kernel<WKV>), dim3(gb), dim3(wnt),
+                                          seg_bytes + ring_bytes, st, pp, lists, lists_start, lists_cnt, lists_cap, pieces,
+                                          pl.nseg, fresh));
     }
+    HIP_TRY(hipGetLastError());
+    m->fresh = false;   // every segment has been written: built, or zeroed
     if (ev) HIP_TRY(hipEventRecord(ev[6], st));
     // Records that found their sub-list filled up by a hot key, and the deferred list: inserted now, by the
     // whole chip, into a table whose segments are all in place.
-    if (nq2 && !(m->dbg & 1)) {
+    if (nq2) {
         const uint32_t nq = nq2 + pl.G1;
         DISPATCH_WK(m, hipLaunchKernelGGL((overflow_insert_kernel<WKV>), dim3(std::min<uint32_t>(nq, (uint32_t)m->cus * 8)),
                                           dim3(PART_NT), 0, st, pp, (const uint64_t *)m->d_ovq,
                                           (const uint32_t *)m->d_ovq_cnt, OVQ_CAP, nq));
         HIP_TRY(hipGetLastError());
     }
-    if (!(m->dbg & 1)) {
-        DISPATCH_WK(m, hipLaunchKernelGGL((deferred_insert_kernel<WKV>), dim3(m->cus * 2), dim3(PART_NT), 0, st, pp,
-                                          (const uint64_t *)m->d_def_rec, (const uint64_t *)m->d_def_cnt,
-                                          (const unsigned long long *)m->d_def_n, (uint64_t)0, (uint64_t)m->def_cap));
-        HIP_TRY(hipGetLastError());
-    }
+    DISPATCH_WK(m, hipLaunchKernelGGL((deferred_insert_kernel<WKV>), dim3(m->cus * 2), dim3(PART_NT), 0, st, pp,
+                                      (const uint64_t *)m->d_def_rec, (const uint64_t *)m->d_def_cnt,
+                                      (const unsigned long long *)m->d_def_n, (uint64_t)0, (uint64_t)m->def_cap));
+    HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
 
@@ -1207,7 +1171,7 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
         if (rcz != TSX_HIP_OK) return rcz;
         DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV>), dim3(g3), dim3(NT), lut_bytes, st,
                                                             m->p, d_text, n, own_end, head_open, (const uint32_t *)m->d_tile,
-                                                            ntiles, m->dbg)));
+                                                            ntiles)));
         HIP_TRY(hipGetLastError());
         if (ev) for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i], st));
         return TSX_HIP_OK;
@@ -1229,7 +1193,7 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
     const int fuse = (fuse_env && atoi(fuse_env) == 0) ? 0 : 2;
     const int g_sp = (int)std::min<uint64_t>((own_end + 8191) / 8192, (uint64_t)m->cus * 2);   // walk workgroups
     // strip_desc_kernel: 52 VGPRs, 2.4 KiB of LDS -- eight workgroups per CU (five: 3.9 ms for both kernels, eight: 3.7)
-    static const int desc_wgs = getenv("TSX_HIP_DESC_WGS") ? std::min(16, std::max(1, atoi(getenv("TSX_HIP_DESC_WGS")))) : 8;
+    const int desc_wgs = 8;
     const int gd = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * desc_wgs), gdreg = gd * (NT / 64);
     const bool want_fuse = fuse && !shard_send && p.wk == 1;
 
@@ -1258,9 +1222,7 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
         {
             // two kernels: strip descriptions (16 B per strip with a k-mer start, one region per wave, in buffer 0 --
             // level 2 overwrites it later), then the walk with every lane busy
-            // all keys stay on this GPU: a ring flush per quarter strip (TSX_HIP_WALK_FLUSHQ=2|4: experiments)
-            uint32_t local_fq = 1u;
-            if (const char *e = getenv("TSX_HIP_WALK_FLUSHQ")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) local_fq = (uint32_t)v; }
+            // all keys stay on this GPU: a ring flush per quarter strip (flush_q = 1)
             // (TSX_HIP_LOCAL_LONG=1: four strips per 32-byte description, as in the exchange of a sharded run)
             const char *ll_env = getenv("TSX_HIP_LOCAL_LONG");
             const int lng = ll_env ? (atoi(ll_env) != 0) : 0;
@@ -1273,15 +1235,15 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
             if (lds > ((size_t)80 << 10)) {   // 512 lists: one workgroup per CU, 1024 threads
                 DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<1024, CANV>), dim3(pl.G1), dim3(1024), lds, st, pp,
                                    (const uint4 *)m->d_buf[0], desc_cap,
-                                   (const unsigned long long *)pl.c_log, (uint32_t)gdreg, m->dbg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
+                                   (const unsigned long long *)pl.c_log, (uint32_t)gdreg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
                                    (uint32_t)(p.l - pl.b1), m->d_ovq + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt + nq2, OVQ_CAP,
-                                   (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, local_fq));
+                                   (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, 1u));
             } else {
                 DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<SP_NT, CANV>), dim3(pl.G1), dim3(SP_NT), lds, st, pp,
                                    (const uint4 *)m->d_buf[0], desc_cap,
-                                   (const unsigned long long *)pl.c_log, (uint32_t)gdreg, m->dbg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
+                                   (const unsigned long long *)pl.c_log, (uint32_t)gdreg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
                                    (uint32_t)(p.l - pl.b1), m->d_ovq + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt + nq2, OVQ_CAP,
-                                   (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, local_fq));
+                                   (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, 1u));
             }
         }
     } else if (p.wk == 1) {
@@ -1303,7 +1265,7 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
         HIP_TRY(hipGetLastError());
         DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_kernel<CANV>), dim3(gs), dim3(NT), lut_bytes, st, pp,
                            (const uint4 *)m->d_buf[1], desc_cap,
-                           (const unsigned long long *)m->d_desc_cnt, (uint32_t)gdreg, m->dbg, m->d_buf[0], pl.log_cap,
+                           (const unsigned long long *)m->d_desc_cnt, (uint32_t)gdreg, m->d_buf[0], pl.log_cap,
                            pl.c_log, pl.d_hist, hist_nb, hist_shift, (uint64_t)0, 0, 0, (unsigned long long *)nullptr));
     } else {
         // multi-limb keys, two kernels as well: descriptions (first k-mer + entering bases + validity) into buffer 1,
@@ -1324,7 +1286,7 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
                            (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], desc_cap, m->d_desc_cnt);              \
         DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_wide_kernel<WKV, CANV>), dim3(gs), dim3(NT), lut_bytes, st, pp,     \
                            (const uint4 *)m->d_buf[1],                                                                       \
-                           desc_cap, (const unsigned long long *)m->d_desc_cnt, (uint32_t)gdreg, m->dbg, m->d_buf[0],        \
+                           desc_cap, (const unsigned long long *)m->d_desc_cnt, (uint32_t)gdreg, m->d_buf[0],                \
                            pl.log_cap, pl.c_log, pl.d_hist, hist_nb, hist_shift))
         switch (p.wk) {
             case 2: TSX_WIDE2(2); break;
@@ -1479,7 +1441,7 @@ extern "C" int tsx_hip_shard_build_pieces_device(tsx_hip_map *m, const void *dev
                            pp, keys, (const unsigned long long *)pl.c_rstart, (const unsigned long long *)pl.c_log, (uint64_t)0,
                            (uint32_t)g, 1u, pl.buf1, (const unsigned long long *)nullptr,
                            (const unsigned long long *)nullptr, pl.c_l1, pl.cap1, pl.nb1, (uint32_t)(m->p.l - pl.b1), bits,
-                           m->dbg, m->d_ovq + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt + nq2, OVQ_CAP,
+                           m->d_ovq + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt + nq2, OVQ_CAP,
                            (const unsigned long long *)nullptr, 0u, (uint64_t)0, 1, key_sum, 0u, (uint32_t)g, 0, 0u, (const uint32_t *)nullptr);
     } else {
         hipLaunchKernelGGL(hist_kernel, dim3(g), dim3(PART_NT), 0, st, keys, (uint32_t)g, pl.nb1, (uint32_t)(m->p.l - pl.b1),
@@ -1566,7 +1528,7 @@ extern "C" int tsx_hip_shard_l1_window_device(tsx_hip_map *m, const void *dev_ke
     hipLaunchKernelGGL((partition_ring_kernel<1>), dim3(rw), dim3(RING_NT), (size_t)pl.nb1 * (((size_t)8 << bits) + 36), st, pp,
                        (const uint64_t *)dev_keys, (const unsigned long long *)ds, (const unsigned long long *)dc, (uint64_t)0, rw,
                        1u, pl.buf1, (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, pl.c_l1,
-                       pl.cap1, pl.nb1, (uint32_t)(m->p.l - pl.b1), bits, m->dbg,
+                       pl.cap1, pl.nb1, (uint32_t)(m->p.l - pl.b1), bits,
                        m->d_ovq + ((size_t)nq2 + (size_t)window * rw) * OVQ_CAP, m->d_ovq_cnt + nq2 + (size_t)window * rw, OVQ_CAP,
                        (const unsigned long long *)nullptr, 0u, (uint64_t)0, 1, (unsigned long long *)dev_key_sum,
                        window * rw, g1, 0, 0u, (const uint32_t *)nullptr);
@@ -1644,14 +1606,12 @@ static int mini_split(tsx_hip_map *m, uint32_t part, uint32_t nparts, int nranks
                       void *dev_counts, hipStream_t st) {
     HIP_TRY(hipMemsetAsync(dev_counts, 0, ((size_t)nranks + 4) * 8, st));
     if (m->mz_regions == 0) return TSX_HIP_OK;   // an empty text
-    static const int mz_wgs = getenv("TSX_HIP_MZ_WGS") ? std::min(MZ_WG_PER_CU, std::max(1, atoi(getenv("TSX_HIP_MZ_WGS")))) : MZ_WG_PER_CU;
-    static const int mz_merge = getenv("TSX_HIP_MZ_MERGE") ? atoi(getenv("TSX_HIP_MZ_MERGE")) : 1;
-    const int gdr = (int)m->mz_regions, gsp = std::min(gdr, m->cus * mz_wgs);
+    const int gdr = (int)m->mz_regions, gsp = std::min(gdr, m->cus * MZ_WG_PER_CU);
     unsigned long long *d_cnt = m->d_desc_cnt, *count = (unsigned long long *)dev_counts;
     uint32_t *d_used = (uint32_t *)(d_cnt + 2 * (size_t)gdr + 8);   // chunks taken per (owner, workgroup)
     hipLaunchKernelGGL(desc_owner_split_kernel, dim3(gsp), dim3(MZ_NT), 0, st, m->p, (const uint4 *)m->d_buf[1], m->mz_dcap,
                        (const unsigned long long *)d_cnt, (uint32_t)gdr, (uint32_t)nranks, (uint4 *)dev_desc, (uint64_t)cap_per_owner,
-                       d_used, count + nranks, mz_merge, part, nparts,
+                       d_used, count + nranks, part, nparts,
                        (const unsigned long long *)(d_cnt + 2 * (size_t)gdr + 8 + ((size_t)MZ_MAX_RANKS * m->cus * MZ_WG_PER_CU + 1) / 2));
     hipLaunchKernelGGL(desc_owner_finish_kernel, dim3(nranks), dim3(MZ_NT), 0, st, (const uint32_t *)d_used, (uint32_t)gsp,
                        (uint32_t)nranks, (uint4 *)dev_desc, (uint64_t)cap_per_owner, count, m->p.stats);
@@ -1776,25 +1736,24 @@ static int shard_walk(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int l
     if (n_desc == 0) return TSX_HIP_OK;
     const uint32_t gw = m->sh_rw, nq2 = pl.nb1 * pl.cpr2;
     const uint64_t chunk = (n_desc + gw - 1) / gw;   // descriptions per workgroup
-    // this GPU keeps one key in 2^shard_bits: a ring flush every 1, 2 or 4 quarter strips (walk_part_kernel)
+    // this GPU keeps one key in 2^shard_bits: a ring flush every 1, 2 or 4 quarter strips (walk_part_kernel); every 2
+    // in the minimizer exchange
     const uint32_t nown = 1u << (m->p.lg - m->p.l);
-    uint32_t flush_q = nown >= 4 ? 4u : (nown == 2 ? 2u : 1u);
+    const uint32_t flush_q = mini ? 2u : (nown >= 4 ? 4u : (nown == 2 ? 2u : 1u));
     const int own_mode = mini ? (2 | (caller_slot > 0 ? 4 : 0)) : 1;
-    if (mini) flush_q = 2u;
-    if (const char *e = getenv("TSX_HIP_WALK_FLUSHQ")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) flush_q = (uint32_t)v; }
     TableParams pp = m->p;
     pp.defer = DeferList{m->d_def_rec, m->d_def_cnt, m->d_def_n, (uint64_t)m->def_cap};
     const size_t lds = (size_t)pl.nb1 * (((size_t)8 << SP_CAPBITS) + 8 + 8 + 4 + 4);
     // (a canonical map gets here only from count_slabs: the exchanges refuse it)
     if (lds > ((size_t)80 << 10)) {   // 512 lists: one workgroup per CU, 1024 threads
         DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<1024, CANV>), dim3(gw), dim3(1024), lds, st, pp, (const uint4 *)dev_desc, chunk,
-                           (const unsigned long long *)nullptr, gw, m->dbg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
+                           (const unsigned long long *)nullptr, gw, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
                            (uint32_t)(m->p.l - pl.b1), m->d_ovq + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
                            m->d_ovq_cnt + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
                            (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q));
     } else {
         DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<SP_NT, CANV>), dim3(gw), dim3(SP_NT), lds, st, pp, (const uint4 *)dev_desc, chunk,
-                           (const unsigned long long *)nullptr, gw, m->dbg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
+                           (const unsigned long long *)nullptr, gw, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
                            (uint32_t)(m->p.l - pl.b1), m->d_ovq + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
                            m->d_ovq_cnt + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
                            (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q));
@@ -1863,7 +1822,7 @@ extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc,
     pp.defer = DeferList{m->d_def_rec, m->d_def_cnt, m->d_def_n, (uint64_t)m->def_cap};
     const uint64_t chunk = (n_desc + greg - 1) / greg;   // descriptions per wave
     hipLaunchKernelGGL(walk_log_kernel<false>, dim3(gs), dim3(NT), m->lut.size() * 8, st, pp, (const uint4 *)dev_desc, chunk,
-                       (const unsigned long long *)nullptr, (uint32_t)greg, m->dbg, m->d_buf[0], lp.log_cap, lp.c_log, lp.d_hist,
+                       (const unsigned long long *)nullptr, (uint32_t)greg, m->d_buf[0], lp.log_cap, lp.c_log, lp.d_hist,
                        lp.nb1, (uint32_t)(m->p.l - lp.b1), (uint64_t)n_desc, long_desc ? 1 : 0, 1,
                        (unsigned long long *)dev_emit_sum);
     HIP_TRY(hipGetLastError());
@@ -1871,7 +1830,7 @@ extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc,
     hipLaunchKernelGGL((partition_ring_kernel<1>), dim3(gw), dim3(RING_NT), (size_t)pl.nb1 * (((size_t)8 << bits) + 36), st, pp,
                        (const uint64_t *)m->d_buf[0], (const unsigned long long *)nullptr, (const unsigned long long *)nullptr,
                        (uint64_t)0, 1u, gw, pl.buf1, (const unsigned long long *)nullptr, (const unsigned long long *)nullptr,
-                       pl.c_l1, pl.cap1, pl.nb1, (uint32_t)(m->p.l - pl.b1), bits, m->dbg,
+                       pl.c_l1, pl.cap1, pl.nb1, (uint32_t)(m->p.l - pl.b1), bits,
                        m->d_ovq + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP, m->d_ovq_cnt + nq2 + (size_t)slot * gw, OVQ_CAP,
                        (const unsigned long long *)lp.c_log, (uint32_t)greg, lp.log_cap, 1, (unsigned long long *)nullptr, slot,
                        nslots, 0, 0u, (const uint32_t *)nullptr);
@@ -2344,15 +2303,12 @@ static int ensure_staging(tsx_hip_map *m, size_t n) {
 }
 
 // Pageable -> pinned staging copy on several host threads: one thread moves ~10 GB/s,
-// the PCIe link ~55 GB/s.  TSX_HIP_COPY_THREADS overrides the default (hardware threads - 2,
-// at most 12).
+// the PCIe link ~55 GB/s.  Hardware threads - 2, at least 2 and at most 12.
 static void parallel_memcpy(uint8_t *dst, const char *src, size_t len) {
-    static unsigned maxt = 0;
-    if (!maxt) {
+    static const unsigned maxt = [] {   // (initialised once, also when rank threads copy at the same time)
         const unsigned hw = std::thread::hardware_concurrency();
-        maxt = std::min(12u, std::max(2u, hw > 2 ? hw - 2 : 2u));
-        if (const char *e = getenv("TSX_HIP_COPY_THREADS")) maxt = (unsigned)std::min(64, std::max(1, atoi(e)));
-    }
+        return std::min(12u, std::max(2u, hw > 2 ? hw - 2 : 2u));
+    }();
     const size_t MIN_PER_THREAD = (size_t)8 << 20;
     unsigned nthreads = (unsigned)std::min<size_t>(maxt, len / MIN_PER_THREAD);
     if (nthreads <= 1) { memcpy(dst, src, len); return; }
@@ -2530,16 +2486,14 @@ extern "C" int tsx_hip_get_counts_host(tsx_hip_map *m, const uint64_t *kmers, si
     return lookup_host(m, kmers, n, counts_out, nullptr);
 }
 
-// Diagnostic builds only (TSX_HIP_DEBUG bit 4): the ST_DBG* counters.  Not part of include/tsxcount_hip.h.
+// Word 7: entries of the deferred list of the last partitioned pass; words 0-6 are spare and read 0.  Not part of
+// include/tsxcount_hip.h.
 extern "C" int tsx_hip_debug_counters(tsx_hip_map *m, uint64_t *out8) {
     if (!m || !out8) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
-    unsigned long long st[ST_N];
-    int rc = read_stats(m, st);
-    if (rc != TSX_HIP_OK) return rc;
-    for (int i = 0; i < 7; ++i) out8[i] = st[ST_DBG0 + i];
-    out8[7] = 0;
-    if (m->d_def_n) {   // entries of the deferred list of the last partitioned pass
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    for (int i = 0; i < 8; ++i) out8[i] = 0;
+    if (m->d_def_n) {
         unsigned long long dn = 0;
         HIP_TRY(hipMemcpy(&dn, m->d_def_n, 8, hipMemcpyDeviceToHost));
         out8[7] = dn;

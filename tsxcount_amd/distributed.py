@@ -121,9 +121,9 @@ def agreed_max(value, comm, device):
 
 def window_geometry(max_text_bytes, windows=None, min_window=32 << 20):
     """(windows, win_bytes) of a step over texts of at most max_text_bytes: at most 4 windows of at least min_window
-    bytes (TSX_HIP_SHARD_WINDOWS overrides the count), window length a multiple of 4 KiB."""
+    bytes, window length a multiple of 4 KiB."""
     if windows is None:
-        windows = int(os.environ.get("TSX_HIP_SHARD_WINDOWS", "0")) or max(1, min(4, max_text_bytes // min_window))
+        windows = max(1, min(4, max_text_bytes // min_window))
     windows = max(1, int(windows))
     return windows, max(4096, ((max_text_bytes + windows - 1) // windows + 4095) & ~4095)
 
@@ -480,7 +480,7 @@ class ShardedCounter:
         failure = None     # seen by every rank in the same window (statuses travel with the sizes): all leave together
         late = None        # seen by this rank only: it stays in the collectives, everyone raises after the last all-reduce
         piece_off, piece_cnt, hot_g = [], [], []
-        l1_windows = bool(L.tsx_hip_shard_l1_supported(m.handle)) and os.environ.get("TSX_HIP_SHARD_L1_WINDOWS", "1") != "0"
+        l1_windows = bool(L.tsx_hip_shard_l1_supported(m.handle))
         est_total = 0
         rc_scan = self._scan(0, text_ptr, nbytes)
         for i in range(nwin):
