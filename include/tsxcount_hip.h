@@ -130,6 +130,27 @@ int tsx_hip_clear(tsx_hip_map *m);
 int tsx_hip_set_canonical(tsx_hip_map *m, int on);
 int tsx_hip_canonical(const tsx_hip_map *m);
 int tsx_hip_canonical_host(int k, const uint64_t *kmers, size_t n, uint64_t *out);
+
+/*
+ * Base rule (jellyfish -Q and its non-ACGT rule; no reference counterpart): which windows of a sequence line are
+ * k-mers.  Off by default: every window of k bytes counts, a non-ACGT byte as its stand-in code.
+ *   acgt_only        1: a window is a k-mer only if all k of its bytes are in ACGTacgt.
+ *   min_qual_char    c > 0: a window is a k-mer only if every base in it has a quality byte >= c (unsigned compare).
+ *                    The quality of base j of a record's sequence line is byte j of the record's 4th non-empty line;
+ *                    a base without one (a shorter quality line) counts as low quality.  FASTQ only: with 2-line
+ *                    records the count and query entry points return TSX_HIP_EINVAL (tsx_hip_last_error says why).
+ * The rule does not change keys: it may change between calls, and each call counts (or queries) under the rule in
+ * effect then.  It holds for tsx_hip_count_fastq_host/_device/_bgzf_host (kmers_added counts only what it keeps) and
+ * for tsx_hip_query_reads_* / tsx_hip_filter_reads_* (a dropped window is not a k-mer of the read).  Host pieces and
+ * BGZF batches are cut at record boundaries under min_qual_char: a record longer than a piece (or than 8 MiB in a
+ * BGZF file) gives TSX_HIP_ERANGE.  Like canonical tables, the sharded and minimizer exchanges refuse a table with a
+ * rule (TSX_HIP_EINVAL; the *_supported queries answer 0); the group merge works.
+ *   set_base_rule    acgt_only 0 or 1, min_qual_char 0 .. 255 (0 = off); a rule on a map created with
+ *                    shard_bits > 0: TSX_HIP_EINVAL.
+ *   get_base_rule    the rule in effect (either pointer may be NULL).
+ */
+int tsx_hip_set_base_rule(tsx_hip_map *m, int acgt_only, int min_qual_char);
+int tsx_hip_get_base_rule(const tsx_hip_map *m, int *acgt_only, int *min_qual_char);
 /* Wait for everything queued on the map's stream and report sticky errors
  * (TSX_HIP_EFULL / TSX_HIP_EOVERFLOW / TSX_HIP_ELOCK) raised by earlier inserts. */
 int tsx_hip_sync(tsx_hip_map *m);
@@ -470,6 +491,9 @@ int tsx_hip_group_set_record_lines(tsx_hip_group *g, int lines);
 /* tsx_hip_set_canonical on every rank's table (an empty group only); lookups then route the canonical form of a
  * k-mer to its owner.  Refused together with the minimizer exchange (either order): TSX_HIP_EINVAL. */
 int tsx_hip_group_set_canonical(tsx_hip_group *g, int on);
+/* tsx_hip_set_base_rule on every rank's table (at any time).  Refused together with the minimizer exchange (either
+ * order): TSX_HIP_EINVAL. */
+int tsx_hip_group_set_base_rule(tsx_hip_group *g, int acgt_only, int min_qual_char);
 /* exchange 0 (default): every GPU counts its shard into its own table, the tables are merged afterwards (any k);
  * exchange 1: the minimizer exchange (20 <= k <= 32, at most 16 GPUs) -- strip descriptions travel to the GPU that owns
  * their k-mers' minimizer BEFORE anything is built, nothing is merged (tsx_hip_group_merge is then a no-op), lookups go to

@@ -120,6 +120,9 @@ def lib():
     L.tsx_hip_canonical.argtypes = [vp]
     L.tsx_hip_canonical_host.argtypes = [ci, u64p, sz, u64p]
     L.tsx_hip_group_set_canonical.argtypes = [vp, ci]
+    L.tsx_hip_set_base_rule.argtypes = [vp, ci, ci]
+    L.tsx_hip_get_base_rule.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.tsx_hip_group_set_base_rule.argtypes = [vp, ci, ci]
     L.tsx_hip_sync.argtypes = [vp]
     L.tsx_hip_count_fastq_host.argtypes = [vp, ctypes.c_char_p, sz]
     L.tsx_hip_count_fastq_device.argtypes = [vp, vp, sz, vp]
@@ -237,6 +240,22 @@ def canonical(kmers, k):
     return out
 
 
+def min_qual_code(min_qual_char):
+    """The byte of a min_qual_char argument: None or 0 = off, a one-character str (e.g. '5') or an int 1 .. 255."""
+    if min_qual_char is None:
+        return 0
+    if isinstance(min_qual_char, (bytes, str)):
+        b = min_qual_char.encode("latin-1") if isinstance(min_qual_char, str) else min_qual_char
+        if len(b) != 1:
+            raise ValueError("min_qual_char: one character, got %r" % (min_qual_char,))
+        return b[0]
+    if isinstance(min_qual_char, bool) or not isinstance(min_qual_char, (int, np.integer)):
+        raise TypeError("min_qual_char: a one-character str or an int, got %r" % (min_qual_char,))
+    if not 0 <= int(min_qual_char) <= 255:
+        raise ValueError("min_qual_char: 0 .. 255, got %d" % min_qual_char)
+    return int(min_qual_char)
+
+
 def encode_many(seqs, k):
     out = np.zeros((len(seqs), key_limbs(k)), dtype=np.uint64)
     for i, s in enumerate(seqs):
@@ -252,7 +271,8 @@ class TSXHashMapHIP:
     """
 
     def __init__(self, iL, iStorageBits, iK, iThreads=0, hash_seed=1, overflow_l=0, device=0, shard_bits=0,
-                 shard_index=0, canonical=False):
+                 shard_index=0, canonical=False, acgt_only=False, min_qual_char=None):
+        min_qual_code(min_qual_char)   # (argument errors before anything is allocated)
         self._h = ctypes.c_void_p()
         self._lib = lib()
         _check(self._lib.tsx_hip_create_shard(ctypes.byref(self._h), iK, iL, iStorageBits, overflow_l,
@@ -260,8 +280,27 @@ class TSXHashMapHIP:
         self.layout = Layout()
         _check(self._lib.tsx_hip_get_layout(self._h, ctypes.byref(self.layout)))
         self.k, self.l, self.wk, self.device = iK, iL, self.layout.key_limbs, device
+        self._lines = 4
         if canonical:
             self.set_canonical(True)
+        if acgt_only or min_qual_char:
+            self.set_base_rule(acgt_only, min_qual_char)
+
+    @property
+    def base_rule(self):
+        """(acgt_only, min_qual_char) in effect: min_qual_char as a one-character str, None when off."""
+        a, q = ctypes.c_int(), ctypes.c_int()
+        _check(self._lib.tsx_hip_get_base_rule(self.handle, ctypes.byref(a), ctypes.byref(q)))
+        return bool(a.value), (chr(q.value) if q.value else None)
+
+    def set_base_rule(self, acgt_only=False, min_qual_char=None):
+        """Which windows count as k-mers (tsx_hip_set_base_rule): acgt_only drops windows with a byte outside ACGTacgt,
+        min_qual_char (a one-character str or an int) those with a base whose quality byte is below it or missing.
+        Keys do not change, so the rule may change between calls; FASTQ only for min_qual_char."""
+        q = min_qual_code(min_qual_char)
+        if q and self._lines != 4:
+            raise ValueError("min_qual_char needs FASTQ records: a FASTA text has no quality line")
+        _check(self._lib.tsx_hip_set_base_rule(self.handle, 1 if acgt_only else 0, q))
 
     @property
     def canonical(self):
@@ -488,7 +527,10 @@ class TSXHashMapHIP:
 
     def set_record_lines(self, lines):
         """4 = FASTQ records (default), 2 = FASTA as FASTXreader<FASTAEntry> reads it (tsx_hip_set_record_lines)."""
+        if lines != 4 and self.base_rule[1] is not None:
+            raise ValueError("min_qual_char needs FASTQ records: a FASTA text has no quality line")
         _check(self._lib.tsx_hip_set_record_lines(self._h, lines))
+        self._lines = lines
 
     def set_path(self, path):
         """0 auto, 1 atomic, 2 partitioned (tsx_hip_set_path)."""
@@ -550,7 +592,8 @@ class TSXHashMapHIPGroup:
     device copies, ranks may share a GPU), lookups go to the owner of each k-mer."""
 
     def __init__(self, gpus, iL, iStorageBits, iK, hash_seed=1, devices=None, comm="rccl", exchange="merge",
-                 canonical=False):
+                 canonical=False, acgt_only=False, min_qual_char=None):
+        min_qual_code(min_qual_char)
         self._lib = lib()
         self._h = ctypes.c_void_p()
         dv = (ctypes.c_int * gpus)(*devices) if devices is not None else None
@@ -561,9 +604,25 @@ class TSXHashMapHIPGroup:
         if canonical:   # (the minimizer exchange refuses it)
             self._check(self._lib.tsx_hip_group_set_canonical(self._h, 1))
         self.canonical = bool(canonical)
+        self._lines = 4
+        self._rule = (False, None)
+        if acgt_only or min_qual_char:   # (the minimizer exchange refuses it)
+            self.set_base_rule(acgt_only, min_qual_char)
         if exchange != "merge":      # "mini": the minimizer exchange (20 <= k <= 32), nothing is merged afterwards
             self._check(self._lib.tsx_hip_group_set_exchange(self._h, {"merge": 0, "mini": 1}[exchange]))
         self.exchange = exchange
+
+    @property
+    def base_rule(self):
+        """(acgt_only, min_qual_char) on every rank's table (see TSXHashMapHIP.set_base_rule)."""
+        return self._rule
+
+    def set_base_rule(self, acgt_only=False, min_qual_char=None):
+        q = min_qual_code(min_qual_char)
+        if q and self._lines != 4:
+            raise ValueError("min_qual_char needs FASTQ records: a FASTA text has no quality line")
+        self._check(self._lib.tsx_hip_group_set_base_rule(self._h, 1 if acgt_only else 0, q))
+        self._rule = (bool(acgt_only), chr(q) if q else None)
 
     def _check(self, rc):
         if rc != OK:
@@ -578,7 +637,10 @@ class TSXHashMapHIPGroup:
         return self._lib.tsx_hip_group_comm_name(self._h).decode()
 
     def set_record_lines(self, lines):
+        if lines != 4 and self._rule[1] is not None:
+            raise ValueError("min_qual_char needs FASTQ records: a FASTA text has no quality line")
         self._check(self._lib.tsx_hip_group_set_record_lines(self._h, lines))
+        self._lines = lines
 
     def clear(self):
         self._check(self._lib.tsx_hip_group_clear(self._h))

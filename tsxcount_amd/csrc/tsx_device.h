@@ -74,6 +74,8 @@ struct TableParams {
     uint32_t line_mask;         // lines per record - 1: 3 = FASTQ (FASTQEntry, FastXReader.h:62-95), 1 = FASTA as
                                 // FASTXreader<FASTAEntry> reads it (two lines per record, :97-116); the sequence
                                 // is the line with (index & line_mask) == 1
+    uint32_t acgt_only;         // base rule (tsx_hip_set_base_rule; read by the BR scan front ends only): 1 = a byte
+                                // outside ACGTacgt breaks every window that holds it.  (In the padding before defer.)
     DeferList defer;            // see DeferList; set per launch by the host
     uint64_t pos_base;          // slot number of table[0] in the table the lookups see: 0, except in the per-slab views of
                                 // a table that is built slab by slab (l - S > 18, tsxcount_hip.hip: count_slabs) -- the

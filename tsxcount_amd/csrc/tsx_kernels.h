@@ -52,6 +52,34 @@ __device__ __forceinline__ void classify16(const uint4 v, bool prev_nl, uint32_t
     le16 = nl16 & ~prev & 0xFFFFu;
 }
 
+// Base rule (tsx_hip_set_base_rule, tsx_baserule.h): extra break bits of the 16 bytes v at offset off of a text of n
+// bytes, ORed into the newline mask of the front ends (never into the line-end mask).  acgt_only: bit i = byte i is
+// not in ACGTacgt -- the byte its 2-bit code stands for (v_perm of "acgt" by the code) differs from the byte with bit 5
+// set, four bytes at a time.  qmap: the low-quality bitmap, one 16-bit word per 16 bytes (the kernels' last argument,
+// null when the rule has no quality part: it leaves the other arguments where the default instantiations have them).  Bytes at or past n are
+// newlines already.
+__device__ __forceinline__ uint32_t nonacgt16(const uint4 v) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t bad = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t t = ((w[i] >> 1) ^ (w[i] >> 2)) & 0x03030303u;
+        const uint32_t d = (w[i] | 0x20202020u) ^ __builtin_amdgcn_perm(0u, 0x74676361u, t);
+        uint32_t u = ((((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u) >> 7;   // bit 8j: byte j differs
+        u |= u >> 7;
+        bad |= ((u | (u >> 14)) & 0xFu) << (4 * i);
+    }
+    return bad;
+}
+template <bool BR>
+__device__ __forceinline__ uint32_t rule_bits16(const TableParams &p, const uint16_t *qmap, const uint4 v, uint64_t off,
+                                                uint64_t n) {
+    if constexpr (!BR) return 0u;
+    uint32_t b = p.acgt_only ? nonacgt16(v) : 0u;
+    if (qmap && off < n) b |= qmap[off >> 4];
+    return b;
+}
+
 // Loads 16 bytes at byte offset off (multiple of 16) of a text of n bytes;
 // bytes at or past n read as '\n' (the last line may lack its terminator).
 __device__ __forceinline__ uint4 load16(const uint8_t *buf, uint64_t off, uint64_t n) {
@@ -204,10 +232,12 @@ __device__ __forceinline__ bool kmer_eq(const uint64_t (&a)[WK], const uint64_t 
 //   4. after a barrier the claimant of each dedup slot issues ONE global
 //      insert carrying the slot's total.
 // CANON (canonical counting): the key of a k-mer is min(h(x), h(rc x)); the LDS dedup still merges equal k-mers only.
-template <int WK, bool CANON = false>
+// BR (base rule): rule_bits16 breaks windows as newlines do.
+template <int WK, bool CANON = false, bool BR = false>
 __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableParams p, const uint8_t *buf, uint64_t n,
                                                          uint64_t own_end, int head_open,
-                                                         const uint32_t *tile_line, uint64_t ntiles) {
+                                                         const uint32_t *tile_line, uint64_t ntiles,
+                                                         const uint16_t *qmap = nullptr) {
     __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
     __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
     __shared__ uint64_t s_le[TILE / 64];
@@ -231,14 +261,18 @@ __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableP
         {
             const uint64_t off = base + (uint64_t)tid * 16;
             uint32_t nl, le, code;
-            classify16(load16(buf, off, n), prev_is_nl(buf, off, n, head_open), nl, le, code);
+            const uint4 v = load16(buf, off, n);
+            classify16(v, prev_is_nl(buf, off, n, head_open), nl, le, code);
+            if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, v, off, n);
             reinterpret_cast<uint32_t *>(s_codes)[tid] = code;
             reinterpret_cast<uint16_t *>(s_nl)[tid] = (uint16_t)nl;
             reinterpret_cast<uint16_t *>(s_le)[tid] = (uint16_t)le;
             if (tid < HALO / 16) {
                 const uint64_t hoff = base + TILE + (uint64_t)tid * 16;
                 uint32_t hnl, hle, hcode;
-                classify16(load16(buf, hoff, n), false, hnl, hle, hcode);
+                const uint4 hv = load16(buf, hoff, n);
+                classify16(hv, false, hnl, hle, hcode);
+                if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, hv, hoff, n);
                 reinterpret_cast<uint32_t *>(s_codes)[TILE / 16 + tid] = hcode;
                 reinterpret_cast<uint16_t *>(s_nl)[TILE / 16 + tid] = (uint16_t)hnl;
             }
@@ -341,12 +375,14 @@ __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableP
 // descriptions, one per lane, every lane busy, and does first window + rolls + level-1 rings.  k <= 32.
 // HOMOUT (the minimizer exchange, 20 <= k <= 32, short descriptions): homopolymer k-mers leave the validity bits here and
 // are counted per base in hom_out[0..3] -- a strip that lies wholly in a poly-A tail is then not described at all.
-template <bool HOMOUT = false>
+// BR (base rule): rule_bits16 breaks windows as newlines do (not with HOMOUT: the minimizer exchange refuses a rule).
+template <bool HOMOUT = false, bool BR = false>
 __global__ __launch_bounds__(NT, 5) void strip_desc_kernel(TableParams p, const uint8_t *buf, uint64_t n, uint64_t own_end,
                                                            int head_open, const uint32_t *tile_line, uint64_t ntiles,
                                                            uint4 *desc, uint64_t desc_cap, unsigned long long *desc_cnt,
                                                            unsigned long long *kmer_sum, int long_desc,
-                                                           unsigned long long *hom_out = nullptr) {
+                                                           unsigned long long *hom_out = nullptr,
+                                                           const uint16_t *qmap = nullptr) {
     // long_desc (the exchange of a sharded run): FOUR neighbouring strips in one description of 32 bytes -- 96 bases
     // + 64 validity bits, half the bytes per start position (the 32 bases behind a strip's own 16 are shared).
     __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
@@ -382,12 +418,14 @@ __global__ __launch_bounds__(NT, 5) void strip_desc_kernel(TableParams p, const 
         {
             uint32_t nl, le, code;
             classify16(cur, cur_pnl, nl, le, code);
+            if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, cur, base + (uint64_t)tid * 16, n);
             reinterpret_cast<uint32_t *>(s_codes)[tid] = code;
             reinterpret_cast<uint16_t *>(s_nl)[tid] = (uint16_t)nl;
             reinterpret_cast<uint16_t *>(s_le)[tid] = (uint16_t)le;
             if (tid < HALO / 16) {
                 uint32_t hnl, hle, hcode;
                 classify16(hcur, false, hnl, hle, hcode);
+                if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, hcur, base + TILE + (uint64_t)tid * 16, n);
                 reinterpret_cast<uint32_t *>(s_codes)[TILE / 16 + tid] = hcode;
                 reinterpret_cast<uint16_t *>(s_nl)[TILE / 16 + tid] = (uint16_t)hnl;
             }
@@ -747,10 +785,11 @@ __device__ __forceinline__ void shr_or3(uint64_t (&r)[3], uint32_t s) {
 // description is 2 WK + 2 words, padded to whole 16-byte units.
 template <int WK> struct WideDescU4 { static constexpr int value = (2 * WK + 2 + 3) / 4; };   // uint4 per description
 
-template <int WK>
+template <int WK, bool BR = false>   // BR: as strip_desc_kernel
 __global__ __launch_bounds__(NT, 4) void strip_desc_wide_kernel(TableParams p, const uint8_t *buf, uint64_t n, uint64_t own_end,
                                                                 int head_open, const uint32_t *tile_line, uint64_t ntiles,
-                                                                uint4 *desc, uint64_t desc_cap, unsigned long long *desc_cnt) {
+                                                                uint4 *desc, uint64_t desc_cap, unsigned long long *desc_cnt,
+                                                                const uint16_t *qmap = nullptr) {
     constexpr int DU = WideDescU4<WK>::value;
     __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
     __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
@@ -785,12 +824,14 @@ __global__ __launch_bounds__(NT, 4) void strip_desc_wide_kernel(TableParams p, c
         {
             uint32_t nl, le, code;
             classify16(cur, cur_pnl, nl, le, code);
+            if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, cur, base + (uint64_t)tid * 16, n);
             reinterpret_cast<uint32_t *>(s_codes)[tid] = code;
             reinterpret_cast<uint16_t *>(s_nl)[tid] = (uint16_t)nl;
             reinterpret_cast<uint16_t *>(s_le)[tid] = (uint16_t)le;
             if (tid < HALO / 16) {
                 uint32_t hnl, hle, hcode;
                 classify16(hcur, false, hnl, hle, hcode);
+                if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, hcur, base + TILE + (uint64_t)tid * 16, n);
                 reinterpret_cast<uint32_t *>(s_codes)[TILE / 16 + tid] = hcode;
                 reinterpret_cast<uint16_t *>(s_nl)[TILE / 16 + tid] = (uint16_t)hnl;
             }

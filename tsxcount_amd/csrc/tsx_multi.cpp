@@ -389,6 +389,8 @@ extern "C" int tsx_hip_group_set_exchange(tsx_hip_group *g, int mode) {
     if (mode == 1) {
         if (g->n > 16) { g_multi_error = "minimizer exchange: at most 16 GPUs"; return TSX_HIP_EINVAL; }
         if (tsx_hip_canonical(g->maps[0]) == 1) { g_multi_error = "minimizer exchange: no canonical counting (owners are strand-dependent)"; return TSX_HIP_EINVAL; }
+        int acgt = 0, minq = 0;
+        if (tsx_hip_get_base_rule(g->maps[0], &acgt, &minq) == TSX_HIP_OK && (acgt || minq)) { g_multi_error = "minimizer exchange: no base rule (use the merge)"; return TSX_HIP_EINVAL; }
         for (tsx_hip_map *m : g->maps)
             if (!tsx_hip_mini_supported(m)) { g_multi_error = "minimizer exchange: 20 <= k <= 32 and a table split by two radix levels"; return TSX_HIP_EINVAL; }
     }
@@ -404,6 +406,16 @@ extern "C" int tsx_hip_group_set_canonical(tsx_hip_group *g, int on) {
     if (on && g->exchange == 1) { g_multi_error = "canonical counting: not with the minimizer exchange"; return TSX_HIP_EINVAL; }
     for (tsx_hip_map *m : g->maps)
         if (tsx_hip_set_canonical(m, on) != TSX_HIP_OK) { g_multi_error = "canonical counting: the tables must be empty"; return TSX_HIP_EINVAL; }
+    return TSX_HIP_OK;
+}
+
+// The base rule on every rank's table.  Each rank counts a shard of whole records (cut_records), so a quality rule sees
+// every record's quality line; the merge moves counted k-mers and needs nothing else.  The rule may change between calls.
+extern "C" int tsx_hip_group_set_base_rule(tsx_hip_group *g, int acgt_only, int min_qual_char) {
+    if (!g) return TSX_HIP_EINVAL;
+    if ((acgt_only || min_qual_char) && g->exchange == 1) { g_multi_error = "base rule: not with the minimizer exchange"; return TSX_HIP_EINVAL; }
+    for (tsx_hip_map *m : g->maps)
+        if (tsx_hip_set_base_rule(m, acgt_only, min_qual_char) != TSX_HIP_OK) { g_multi_error = "base rule: acgt_only 0 or 1, min_qual_char 0 .. 255"; return TSX_HIP_EINVAL; }
     return TSX_HIP_OK;
 }
 
@@ -424,6 +436,11 @@ constexpr size_t MINI_MIN_SHARE = (size_t)32 << 20;
 static int mini_rank(tsx_hip_group *g, int r, const char *text, size_t len, size_t max_len, MiniShared &sh) {
     const int n = g->n;
     tsx_hip_map *m = g->maps[r];
+    int acgt = 0, minq = 0;
+    if (tsx_hip_get_base_rule(m, &acgt, &minq) != TSX_HIP_OK || acgt || minq) {   // (every rank refuses: no barrier is entered)
+        g_multi_error = "minimizer exchange: no base rule (use the merge)";
+        return TSX_HIP_EINVAL;
+    }
     (void)hipSetDevice(g->devices[r]);
     hipStream_t st = g->streams[r];
     int rc = TSX_HIP_OK;

@@ -56,12 +56,13 @@ __device__ inline uint64_t lookup_rest(const TableParams &p, const uint64_t (&h)
 //      records are separated by invalid positions); a segmented suffix reduction leaves the run's kmers, in_range,
 //      sum and min at its first lane, which adds them to the record with four global atomics.
 // stats[r] is written for r < cap only.
-template <int WK, bool CANON = false>
+// BR (base rule): windows the rule drops are not k-mers of the read (rule_bits16, as the count kernels).
+template <int WK, bool CANON = false, bool BR = false>
 __global__ __launch_bounds__(NT, 2) void query_reads_kernel(TableParams p, const uint8_t *buf, uint64_t n, uint64_t own_end,
                                                             int head_open, const uint32_t *tile_line, uint64_t ntiles,
                                                             const unsigned long long *line_base, uint32_t lshift,
                                                             uint64_t lower, uint64_t upper, unsigned long long *stats,
-                                                            uint64_t cap) {
+                                                            uint64_t cap, const uint16_t *qmap = nullptr) {
     __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
     __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
     __shared__ uint64_t s_le[TILE / 64];
@@ -85,14 +86,18 @@ __global__ __launch_bounds__(NT, 2) void query_reads_kernel(TableParams p, const
         {
             const uint64_t off = base + (uint64_t)tid * 16;
             uint32_t nl, le, code;
-            classify16(load16(buf, off, n), prev_is_nl(buf, off, n, head_open), nl, le, code);
+            const uint4 v = load16(buf, off, n);
+            classify16(v, prev_is_nl(buf, off, n, head_open), nl, le, code);
+            if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, v, off, n);
             reinterpret_cast<uint32_t *>(s_codes)[tid] = code;
             reinterpret_cast<uint16_t *>(s_nl)[tid] = (uint16_t)nl;
             reinterpret_cast<uint16_t *>(s_le)[tid] = (uint16_t)le;
             if (tid < HALO / 16) {
                 const uint64_t hoff = base + TILE + (uint64_t)tid * 16;
                 uint32_t hnl, hle, hcode;
-                classify16(load16(buf, hoff, n), false, hnl, hle, hcode);
+                const uint4 hv = load16(buf, hoff, n);
+                classify16(hv, false, hnl, hle, hcode);
+                if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, hv, hoff, n);
                 reinterpret_cast<uint32_t *>(s_codes)[TILE / 16 + tid] = hcode;
                 reinterpret_cast<uint16_t *>(s_nl)[TILE / 16 + tid] = (uint16_t)hnl;
             }

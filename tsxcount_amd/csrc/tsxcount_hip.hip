@@ -8,6 +8,7 @@
 #include "tsx_inflate.h"
 #include "tsx_output.h"
 #include "tsx_query.h"
+#include "tsx_baserule.h"
 
 #include <mutex>
 #include <hip/hip_runtime.h>
@@ -68,6 +69,10 @@ struct tsx_hip_map {
     uint64_t mroll[64] = {0};            // the mirror roll of the reverse complement's hash (canonical walks)
     std::vector<uint64_t> mroll_wide;
     bool canon = false;                  // canonical counting (tsx_hip_set_canonical)
+    uint32_t minq = 0;                   // base rule (tsx_hip_set_base_rule): min_qual_char, 0 = off; acgt_only is p.acgt_only
+    uint16_t *d_qmap = nullptr; size_t qmap_bytes = 0;             // its low-quality bitmap (tsx_baserule.h)
+    const uint16_t *qmap_cur = nullptr;  // the bitmap at the text the next scan launches read (set per call, else null)
+    unsigned long long *d_qrec = nullptr; size_t qrec_bytes = 0;   // line spans per record behind it, and record cuts
     bool used = false;                   // something was inserted since the map was created or cleared
     // FASTQ scratch
     uint32_t *d_tile = nullptr; uint64_t tile_cap = 0;
@@ -580,6 +585,7 @@ extern "C" void tsx_hip_destroy(tsx_hip_map *m) {
     (void)hipFree(m->d_ovq); (void)hipFree(m->d_ovq_cnt); (void)hipFree(m->d_small);
     (void)hipFree(m->d_def_rec); (void)hipFree(m->d_def_cnt); (void)hipFree(m->d_def_n);
     (void)hipFree(m->d_tile); (void)hipFree(m->d_carry); (void)hipFree(m->d_seg);
+    (void)hipFree(m->d_qmap); (void)hipFree(m->d_qrec);
     (void)hipFree(m->p.seg_dirty); (void)hipFree(m->d_buf[0]); (void)hipFree(m->d_buf[1]); (void)hipFree(m->d_cnt);
     for (int i = 0; i < 2; ++i) {
         if (m->h_stage[i]) (void)hipHostFree(m->h_stage[i]);
@@ -659,6 +665,29 @@ extern "C" int tsx_hip_canonical(const tsx_hip_map *m) {
     return m->canon ? 1 : 0;
 }
 
+// The base rule does not change keys: it may change between calls, each call counts under the rule it finds.  A
+// table sharded by slot range is filled by the exchanges, which have no base rule.
+extern "C" int tsx_hip_set_base_rule(tsx_hip_map *m, int acgt_only, int min_qual_char) {
+    if (!m || acgt_only < 0 || acgt_only > 1 || min_qual_char < 0 || min_qual_char > 255) return TSX_HIP_EINVAL;
+    if ((acgt_only || min_qual_char) && m->p.lg != m->p.l) return TSX_HIP_EINVAL;
+    m->p.acgt_only = (uint32_t)acgt_only;
+    m->minq = (uint32_t)min_qual_char;
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_get_base_rule(const tsx_hip_map *m, int *acgt_only, int *min_qual_char) {
+    if (!m) return TSX_HIP_EINVAL;
+    if (acgt_only) *acgt_only = m->p.acgt_only ? 1 : 0;
+    if (min_qual_char) *min_qual_char = (int)m->minq;
+    return TSX_HIP_OK;
+}
+
+// canonical tables and tables with a base rule: single-table and merge paths only (the exchanges refuse them)
+static inline bool exch_refused(const tsx_hip_map *m) {
+    if (m && (m->p.acgt_only || m->minq)) { g_last_error = "a table with a base rule: single-table and merge paths only"; return true; }
+    return m && m->canon;
+}
+
 extern "C" int tsx_hip_canonical_host(int k, const uint64_t *kmers, size_t n, uint64_t *out) {
     if (k < 1 || k > 127 || ((!kmers || !out) && n)) return TSX_HIP_EINVAL;
     const int wk = (2 * k + 63) / 64;
@@ -731,6 +760,9 @@ static inline int grid_for(const tsx_hip_map *m, uint64_t work_items, int per_cu
 // The kernels that make hashed keys in two forms: CANV = canonical counting (tsx_hip_set_canonical) or not.
 #define DISPATCH_CANON(m, CALL)                                                    \
     if ((m)->canon) { constexpr bool CANV = true; CALL; } else { constexpr bool CANV = false; CALL; }
+// The scan front ends in two forms: BRV = a base rule is in effect for this launch (tsx_hip_set_base_rule) or not.
+#define DISPATCH_BR(m, CALL)                                                                                           \
+    if ((m)->p.acgt_only || (m)->qmap_cur) { constexpr bool BRV = true; CALL; } else { constexpr bool BRV = false; CALL; }
 
 // ---- partitioned path: plan, scratch, launches ------------------------------------
 struct PartPlan {
@@ -1133,8 +1165,9 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
             hipLaunchKernelGGL(strip_desc_kernel<true>, dim3(gdd), dim3(NT), 0, st, m->p, d_text, n, own_end, head_open,
                                (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], dcap, d_cnt, dsc.sum, 0, d_hom);
         } else
-        hipLaunchKernelGGL(strip_desc_kernel<false>, dim3(gdd), dim3(NT), 0, st, m->p, d_text, n, own_end, head_open,
-                           (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], dcap, d_cnt, dsc.sum, dsc.long_desc);
+        DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_kernel<false, BRV>), dim3(gdd), dim3(NT), 0, st, m->p, d_text, n, own_end,
+                           head_open, (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], dcap, d_cnt, dsc.sum,
+                           dsc.long_desc, (unsigned long long *)nullptr, m->qmap_cur));
         if (dsc.owners) {   // owner = f(minimizer): the regions stay where they are, mini_split hands them out by owner
             HIP_TRY(hipGetLastError());
             m->mz_regions = (uint32_t)gdr; m->mz_dcap = dcap;
@@ -1169,9 +1202,9 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
     if (!use_part) {
         int rcz = ensure_zeroed(m, st);
         if (rcz != TSX_HIP_OK) return rcz;
-        DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV>), dim3(g3), dim3(NT), lut_bytes, st,
-                                                            m->p, d_text, n, own_end, head_open, (const uint32_t *)m->d_tile,
-                                                            ntiles)));
+        DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV, BRV>), dim3(g3), dim3(NT),
+                                                            lut_bytes, st, m->p, d_text, n, own_end, head_open,
+                                                            (const uint32_t *)m->d_tile, ntiles, m->qmap_cur))));
         HIP_TRY(hipGetLastError());
         if (ev) for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i], st));
         return TSX_HIP_OK;
@@ -1229,8 +1262,9 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
             const uint64_t desc_cap = ((ntiles + gd - 1) / gd) * (lng ? 16 : 64);
             rc = grow(st, m->d_buf[0], m->buf_bytes[0], (size_t)gdreg * desc_cap * (lng ? 32 : 16));
             if (rc != TSX_HIP_OK) return rc;
-            hipLaunchKernelGGL(strip_desc_kernel<false>, dim3(gd), dim3(NT), 0, st, pp, d_text, n, own_end, head_open,
-                               (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[0], desc_cap, pl.c_log, (unsigned long long *)nullptr, lng);
+            DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_kernel<false, BRV>), dim3(gd), dim3(NT), 0, st, pp, d_text, n, own_end,
+                               head_open, (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[0], desc_cap, pl.c_log,
+                               (unsigned long long *)nullptr, lng, (unsigned long long *)nullptr, m->qmap_cur));
             HIP_TRY(hipGetLastError());
             if (lds > ((size_t)80 << 10)) {   // 512 lists: one workgroup per CU, 1024 threads
                 DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<1024, CANV>), dim3(pl.G1), dim3(1024), lds, st, pp,
@@ -1259,9 +1293,9 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
             m->desc_cnt_entries = have;
             if (rc != TSX_HIP_OK) return rc;
         }
-        hipLaunchKernelGGL(strip_desc_kernel<false>, dim3(gd), dim3(NT), 0, st, pp, d_text, n, own_end, head_open,
-                           (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], desc_cap, m->d_desc_cnt,
-                           (unsigned long long *)nullptr, 0);
+        DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_kernel<false, BRV>), dim3(gd), dim3(NT), 0, st, pp, d_text, n, own_end,
+                           head_open, (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], desc_cap, m->d_desc_cnt,
+                           (unsigned long long *)nullptr, 0, (unsigned long long *)nullptr, m->qmap_cur));
         HIP_TRY(hipGetLastError());
         DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_kernel<CANV>), dim3(gs), dim3(NT), lut_bytes, st, pp,
                            (const uint4 *)m->d_buf[1], desc_cap,
@@ -1282,8 +1316,9 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
             if (rc != TSX_HIP_OK) return rc;
         }
 #define TSX_WIDE2(WKV)                                                                                                      \
-        hipLaunchKernelGGL((strip_desc_wide_kernel<WKV>), dim3(gd), dim3(NT), 0, st, pp, d_text, n, own_end, head_open,      \
-                           (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], desc_cap, m->d_desc_cnt);              \
+        DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_wide_kernel<WKV, BRV>), dim3(gd), dim3(NT), 0, st, pp, d_text, n,      \
+                           own_end, head_open, (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], desc_cap,         \
+                           m->d_desc_cnt, m->qmap_cur));                                                                     \
         DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_wide_kernel<WKV, CANV>), dim3(gs), dim3(NT), lut_bytes, st, pp,     \
                            (const uint4 *)m->d_buf[1],                                                                       \
                            desc_cap, (const unsigned long long *)m->d_desc_cnt, (uint32_t)gdreg, m->d_buf[0],                \
@@ -1328,7 +1363,7 @@ extern "C" int tsx_hip_shard_scan_window_device(tsx_hip_map *m, const void *dev_
                                                 size_t own_cap_keys, void *dev_send_counts, void *dev_hot_keys,
                                                 void *dev_hot_counts, size_t hot_cap, void *dev_hot_n,
                                                 void *dev_key_sum, void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_send || !dev_send_counts ||
         !dev_hot_keys || !dev_hot_counts || !dev_hot_n || win_off > n_total || win_len > n_total - win_off)
@@ -1358,14 +1393,14 @@ extern "C" int tsx_hip_shard_scan_window_device(tsx_hip_map *m, const void *dev_
 extern "C" int tsx_hip_shard_scan_device(tsx_hip_map *m, const void *dev_text, size_t n, void *dev_send,
                                          size_t send_cap_keys, void *dev_send_counts, void *dev_hot_keys,
                                          void *dev_hot_counts, size_t hot_cap, void *dev_hot_n, void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     return tsx_hip_shard_scan_window_device(m, dev_text, n, 0, n, dev_send, send_cap_keys, nullptr, 0, dev_send_counts,
                                             dev_hot_keys, dev_hot_counts, hot_cap, dev_hot_n, nullptr, stream);
 }
 
 extern "C" int tsx_hip_shard_send_capacity(tsx_hip_map *m, size_t text_bytes, size_t *keys_out) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (!m || !keys_out) return TSX_HIP_EINVAL;
     const uint64_t ntiles = (text_bytes + TILE - 1) / TILE;
     const int g = (int)std::max<uint64_t>(1, std::min<uint64_t>(ntiles, (uint64_t)m->cus * SCAN_WG_PER_CU)) * (NT / 64);
@@ -1378,7 +1413,7 @@ extern "C" int tsx_hip_shard_send_capacity(tsx_hip_map *m, size_t text_bytes, si
 extern "C" int tsx_hip_shard_build_pieces_device(tsx_hip_map *m, const void *dev_keys, const uint64_t *piece_off,
                                                  const uint64_t *piece_cnt, size_t npieces, void *dev_key_sum,
                                                  void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     if (!m || !dev_keys || ((uintptr_t)dev_keys & 7) || (npieces && (!piece_off || !piece_cnt))) return TSX_HIP_EINVAL;
     unsigned long long *key_sum = (unsigned long long *)dev_key_sum;
@@ -1455,7 +1490,7 @@ extern "C" int tsx_hip_shard_build_pieces_device(tsx_hip_map *m, const void *dev
 
 extern "C" int tsx_hip_shard_build_device(tsx_hip_map *m, const void *dev_keys, size_t n_keys, void *dev_key_sum,
                                           void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     if (!m || (!dev_keys && n_keys)) return TSX_HIP_EINVAL;
     if (n_keys == 0) return TSX_HIP_OK;
@@ -1473,11 +1508,11 @@ static int l1_supported(tsx_hip_map *m) {
     return nsegbits - b1 > 0 ? 1 : 0;
 }
 
-extern "C" int tsx_hip_shard_l1_supported(tsx_hip_map *m) { return (m && m->canon) ? 0 : l1_supported(m); }
+extern "C" int tsx_hip_shard_l1_supported(tsx_hip_map *m) { return exch_refused(m) ? 0 : l1_supported(m); }
 
 extern "C" int tsx_hip_shard_l1_window_device(tsx_hip_map *m, const void *dev_keys, size_t n_keys, uint32_t window,
                                               uint32_t nwindows, size_t est_total_keys, void *dev_key_sum, void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     if (!m || (!dev_keys && n_keys) || ((uintptr_t)dev_keys & 7) || nwindows == 0 || window >= nwindows) return TSX_HIP_EINVAL;
     if (!l1_supported(m)) return TSX_HIP_EINVAL;
@@ -1542,7 +1577,7 @@ extern "C" int tsx_hip_shard_l1_window_device(tsx_hip_map *m, const void *dev_ke
 // descriptions are ALL-GATHERED, and every GPU walks all of them, keeping the keys it owns
 // (tsx_hip_shard_walk_device): N x the rolling work, N/8 of the traffic of the key exchange -- a quarter at N = 2.
 extern "C" int tsx_hip_shard_desc_capacity(tsx_hip_map *m, size_t text_bytes, int long_desc, size_t *descs_out) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (!m || !descs_out) return TSX_HIP_EINVAL;
     // one description per 16 (long: 64) start positions at most; a long one is 32 bytes, a short one 16
     *descs_out = text_bytes / (long_desc ? 64 : 16) + 4096;
@@ -1552,7 +1587,7 @@ extern "C" int tsx_hip_shard_desc_capacity(tsx_hip_map *m, size_t text_bytes, in
 extern "C" int tsx_hip_shard_desc_window_device(tsx_hip_map *m, const void *dev_text, size_t n_total, size_t win_off,
                                                 size_t win_len, int long_desc, void *dev_desc, size_t desc_cap,
                                                 void *dev_count, void *dev_kmer_sum, void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_desc || ((uintptr_t)dev_desc & 15) ||
         !dev_count || win_off > n_total || win_len > n_total - win_off)
@@ -1589,13 +1624,13 @@ static size_t mini_part_cap(const tsx_hip_map *m, size_t text_bytes, uint32_t np
     return text_bytes / 8 / nparts + 65536 + 4096 + (size_t)2 * MZ_CHUNK * (size_t)m->cus * MZ_WG_PER_CU;
 }
 extern "C" int tsx_hip_mini_part_capacity(tsx_hip_map *m, size_t text_bytes, uint32_t nparts, size_t *descs_per_owner_out) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (!m || !descs_per_owner_out || nparts == 0) return TSX_HIP_EINVAL;
     *descs_per_owner_out = mini_part_cap(m, text_bytes, nparts);
     return TSX_HIP_OK;
 }
 extern "C" int tsx_hip_mini_capacity(tsx_hip_map *m, size_t text_bytes, int nranks, size_t *descs_per_owner_out) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (!m || !descs_per_owner_out || nranks < 1 || nranks > MZ_MAX_RANKS) return TSX_HIP_EINVAL;
     *descs_per_owner_out = mini_part_cap(m, text_bytes, 1);
     return TSX_HIP_OK;
@@ -1634,7 +1669,7 @@ static int mini_describe(tsx_hip_map *m, const void *dev_text, size_t n_total, s
 
 extern "C" int tsx_hip_mini_describe_device(tsx_hip_map *m, const void *dev_text, size_t n_total, size_t off, size_t len,
                                             void *dev_kmer_sum, void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (off & 15) || off > n_total || len > n_total - off)
         return TSX_HIP_EINVAL;
@@ -1646,7 +1681,7 @@ extern "C" int tsx_hip_mini_describe_device(tsx_hip_map *m, const void *dev_text
 
 extern "C" int tsx_hip_mini_split_device(tsx_hip_map *m, uint32_t part, uint32_t nparts, int nranks, void *dev_desc,
                                          size_t cap_per_owner, void *dev_counts, void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     if (!m || nparts == 0 || part >= nparts || !dev_desc || ((uintptr_t)dev_desc & 15) || !dev_counts || nranks < 1 ||
         nranks > MZ_MAX_RANKS)
@@ -1660,7 +1695,7 @@ extern "C" int tsx_hip_mini_split_device(tsx_hip_map *m, uint32_t part, uint32_t
 extern "C" int tsx_hip_mini_window_device(tsx_hip_map *m, const void *dev_text, size_t n_total, size_t win_off, size_t win_len,
                                           int nranks, void *dev_desc, size_t cap_per_owner, void *dev_counts,
                                           void *dev_kmer_sum, void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_desc || ((uintptr_t)dev_desc & 15) ||
         !dev_counts || win_off > n_total || win_len > n_total - win_off || nranks < 1 || nranks > MZ_MAX_RANKS)
@@ -1764,7 +1799,7 @@ static int shard_walk(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int l
 
 extern "C" int tsx_hip_shard_walk_device(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int long_desc, uint32_t slot,
                                          uint32_t nslots, size_t est_total_keys, void *dev_emit_sum, void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // the exchanges have no canonical form (owners are strand-dependent)
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // the exchanges have no canonical form (owners are strand-dependent) nor base rule
     if (m && n_desc) m->used = true;
     return shard_walk(m, dev_desc, n_desc, long_desc, slot, nslots, est_total_keys, dev_emit_sum, stream);
 }
@@ -1775,7 +1810,7 @@ extern "C" int tsx_hip_shard_walk_device(tsx_hip_map *m, const void *dev_desc, s
 // reads the wave logs as pieces (512 workgroups, each streaming ten of them) into list set `slot` of `nslots`.
 extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int long_desc, uint32_t slot,
                                            uint32_t nslots, size_t est_total_keys, void *dev_emit_sum, void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     if (!m || (!dev_desc && n_desc) || ((uintptr_t)dev_desc & 15) || nslots == 0 || slot >= nslots) return TSX_HIP_EINVAL;
     if (!l1_supported(m)) return TSX_HIP_EINVAL;
@@ -1840,7 +1875,7 @@ extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc,
 
 // level 2 + build over the sub-lists the windows' level-1 launches have filled
 extern "C" int tsx_hip_shard_build_l1_device(tsx_hip_map *m, void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     if (!m || !m->sh_pl || !m->sh_pl->fused) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
@@ -1859,7 +1894,7 @@ extern "C" int tsx_hip_shard_build_l1_device(tsx_hip_map *m, void *stream) {
 
 extern "C" int tsx_hip_add_hashed_device(tsx_hip_map *m, const void *dev_keys, const void *dev_counts, size_t n,
                                          void *stream) {
-    if (m && m->canon) return TSX_HIP_EINVAL;   // canonical counting: single-table and merge paths only
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
     if (m) m->used = true;
     if (!m || (!dev_keys && n)) return TSX_HIP_EINVAL;
     if (m->p.wk != 1 || m->p.W != 1) return TSX_HIP_EINVAL;
@@ -1954,7 +1989,106 @@ static size_t dev_window_bytes() {
     return w;
 }
 
-static int count_slabs(tsx_hip_map *m, const uint8_t *base, size_t n, hipStream_t st) {
+// ---- base rule: the low-quality bitmap and texts cut at record boundaries (tsx_baserule.h) ------------------------
+static int query_line_pass(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open, hipStream_t st);
+static int ensure_staging(tsx_hip_map *m, size_t n);
+static void parallel_memcpy(uint8_t *dst, const char *src, size_t len);
+
+// min_qual_char reads the 4th line of a FASTQ record: FASTA tables refuse it.
+static int base_rule_ok(const tsx_hip_map *m) {
+    if (m->minq && m->p.line_mask != 3) {
+        g_last_error = "min_qual_char needs FASTQ records (4 lines): a FASTA text has no quality line";
+        return TSX_HIP_EINVAL;
+    }
+    return TSX_HIP_OK;
+}
+
+// m->d_qmap = the low-quality bitmap of d_text[0, n), a text that starts at a record boundary.  Uses the map's line
+// scratch (d_tile, word 0 of d_carry) and waits once, for the line count.  The scan launches get it as qmap_cur.
+static int build_qmap(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, hipStream_t st) {
+    if (n >= ((uint64_t)1 << 33)) { g_last_error = "min_qual_char: a text of 8 GiB or more"; return TSX_HIP_ERANGE; }
+    const size_t words = (size_t)(n + 15) / 16 + 16;
+    int rc = grow(st, m->d_qmap, m->qmap_bytes, words * 2);
+    if (rc != TSX_HIP_OK) return rc;
+    HIP_TRY(hipMemsetAsync(m->d_qmap, 0, words * 2, st));
+    if (n == 0) return TSX_HIP_OK;
+    HIP_TRY(hipMemsetAsync(m->d_carry, 0, sizeof(uint32_t), st));
+    if ((rc = query_line_pass(m, d_text, n, n, 0, st)) != TSX_HIP_OK) return rc;
+    uint32_t lines = 0;
+    HIP_TRY(hipMemcpyAsync(&lines, m->d_carry, sizeof lines, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t nrec = (uint64_t)lines / 4 + 1, ntiles = (n + TILE - 1) / TILE;
+    if ((rc = grow(st, m->d_qrec, m->qrec_bytes, (size_t)nrec * QR_N * 8)) != TSX_HIP_OK) return rc;
+    HIP_TRY(hipMemsetAsync(m->d_qrec, 0, (size_t)nrec * QR_N * 8, st));
+    hipLaunchKernelGGL(qual_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
+                       d_text, n, (const uint32_t *)m->d_tile, ntiles, (const uint32_t *)m->d_carry, m->d_qrec, nrec);
+    hipLaunchKernelGGL(qual_bits_kernel, dim3(grid_for(m, nrec * 16, 8)), dim3(NT), 0, st, d_text,
+                       (const unsigned long long *)m->d_qrec, nrec, m->minq, m->d_qmap);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// qmap_cur is set only for the launches of one call: the rule may change between calls.
+struct QmapScope {
+    tsx_hip_map *m;
+    explicit QmapScope(tsx_hip_map *mm) : m(mm) {}
+    ~QmapScope() { m->qmap_cur = nullptr; }
+};
+
+// One piece d[0, len) of a text cut at record boundaries (a quality rule): where its last whole record ends (cut; the
+// whole piece when last; 0 when it holds no whole record), then the bitmap and the count of [0, cut).  Waits for the cut.
+static int count_record_piece(tsx_hip_map *m, const uint8_t *d, uint64_t len, bool last, hipStream_t st, uint64_t &cut) {
+    cut = last ? len : 0;
+    if (len == 0) return TSX_HIP_OK;
+    int rc;
+    if (!last) {
+        if ((rc = grow(st, m->d_qrec, m->qrec_bytes, 64)) != TSX_HIP_OK) return rc;
+        unsigned long long *info = m->d_qrec;   // (read back before build_qmap reuses it)
+        const uint64_t ntiles = (len + TILE - 1) / TILE;
+        HIP_TRY(hipMemsetAsync(m->d_carry, 0, sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(info, 0, 4 * sizeof(unsigned long long), st));
+        if ((rc = query_line_pass(m, d, len, len, 0, st)) != TSX_HIP_OK) return rc;
+        hipLaunchKernelGGL(record_scan_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
+                           d, len, (const uint32_t *)m->d_tile, ntiles, (const uint32_t *)m->d_carry, m->p.line_mask + 1, 0,
+                           info, (unsigned long long *)nullptr, (uint64_t)0);
+        HIP_TRY(hipGetLastError());
+        unsigned long long h[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(h, info, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        cut = h[1] ? h[0] : 0;
+        if (cut == 0) return TSX_HIP_OK;
+    }
+    if ((rc = build_qmap(m, d, cut, st)) != TSX_HIP_OK) return rc;
+    QmapScope qs(m);
+    m->qmap_cur = m->d_qmap;
+    HIP_TRY(hipMemsetAsync(m->d_carry, 0, sizeof(uint32_t), st));
+    return run_fastq_piece(m, d, cut, cut, 0, st);
+}
+
+// tsx_hip_count_fastq_host under a quality rule: pieces of m->piece bytes cut at record boundaries, one at a time; the
+// next piece starts where the last whole record of this one ends.  A record longer than a piece: ERANGE.
+static int count_host_records(tsx_hip_map *m, const char *text, size_t n) {
+    int rc = ensure_staging(m, n);
+    if (rc != TSX_HIP_OK) return rc;
+    hipStream_t st = m->stream;
+    for (size_t off = 0; off < n;) {
+        const size_t len = std::min(m->piece, n - off);
+        const bool last = off + len == n;
+        parallel_memcpy(m->h_stage[0], text + off, len);
+        HIP_TRY(hipMemcpyAsync(m->d_stage[0], m->h_stage[0], len, hipMemcpyHostToDevice, st));
+        uint64_t cut = 0;
+        if ((rc = count_record_piece(m, m->d_stage[0], len, last, st, cut)) != TSX_HIP_OK) return rc;
+        if (cut == 0) {
+            g_last_error = "min_qual_char: a record longer than a host piece (" + std::to_string(m->piece) + " bytes)";
+            return TSX_HIP_ERANGE;
+        }
+        HIP_TRY(hipStreamSynchronize(st));   // (the staging buffers are reused by the next piece)
+        off += cut;
+    }
+    return tsx_hip_sync(m);
+}
+
+static int count_slabs(tsx_hip_map *m, const uint8_t *base, size_t n, hipStream_t st, const uint16_t *qmap) {
     const int sb = slab_bits(m);
     const uint32_t nslab = 1u << sb;
     const size_t halo = (size_t)m->p.k - 1, WIN = dev_window_bytes();
@@ -1973,8 +2107,10 @@ static int count_slabs(tsx_hip_map *m, const uint8_t *base, size_t n, hipStream_
         const size_t off = (size_t)w * WIN, own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
         DescOut dsc;
         dsc.out = d_desc + doff[w] * 2; dsc.cap = doff[w + 1] - doff[w]; dsc.count = d_cnt + w; dsc.sum = d_cnt + nwin; dsc.long_desc = 1;
+        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;   // (windows start at multiples of 16)
         rc = run_fastq_piece(m, base + off, len, own, off > 0 ? -1 : 0, st, ShardOut(), HotOut(), dsc);
     }
+    m->qmap_cur = nullptr;
     if (rc != TSX_HIP_OK) return done(rc);
     std::vector<unsigned long long> cnt(nwin + 1);
     if (hipMemcpyAsync(cnt.data(), d_cnt, (size_t)(nwin + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -2025,14 +2161,21 @@ extern "C" int tsx_hip_count_fastq_device(tsx_hip_map *m, const void *dev_text, 
     if (n) m->used = true;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
-    HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));
     const uint8_t *base = (const uint8_t *)dev_text;
+    // a quality rule: the bitmap of the whole (resident) text, read by each window at its offset
+    int rcq = base_rule_ok(m);
+    if (rcq == TSX_HIP_OK && m->minq) rcq = build_qmap(m, base, n, st);
+    if (rcq != TSX_HIP_OK) return rcq;
+    const uint16_t *qmap = m->minq ? m->d_qmap : nullptr;
+    QmapScope qs(m);
+    HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));
     const size_t halo = (size_t)m->p.k - 1;
     const size_t DEV_WINDOW = dev_window_bytes();
-    if (slab_bits(m) && (m->path == 2 || (m->path == 0 && n * 32 >= m->lay.table_bytes))) return count_slabs(m, base, n, st);
+    if (slab_bits(m) && (m->path == 2 || (m->path == 0 && n * 32 >= m->lay.table_bytes))) return count_slabs(m, base, n, st, qmap);
     for (size_t off = 0; off < n || off == 0; off += DEV_WINDOW) {
         const size_t own = std::min(DEV_WINDOW, n - off);
         const size_t len = std::min(own + halo, n - off);
+        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;   // (windows start at multiples of 16)
         // whether the previous window ends inside a line is read on the device (the byte in front of this one)
         int rc = run_fastq_piece(m, base + off, len, own, off > 0 ? -1 : 0, st);
         if (rc != TSX_HIP_OK) return rc;
@@ -2215,6 +2358,54 @@ extern "C" int tsx_hip_inflate_bgzf_host(int device, const void *gz, size_t n, v
 // piece (is its first line open?) as well.  On an inflate error the table holds the batches before it.
 static const size_t BGZF_PRE = 256;   // >= k - 1, a multiple of 16
 
+// tsx_hip_count_fastq_bgzf_host under a quality rule: batch by batch on the map's stream.  The unfinished last record of
+// a batch is carried into the next one instead of a k-1 byte halo: it goes in front of the next batch's text, behind
+// newlines that align the piece to 16 bytes (empty lines are dropped).  A record longer than BGZF_CARRY: ERANGE.
+static const size_t BGZF_CARRY = (size_t)8 << 20;
+
+static int count_bgzf_records(tsx_hip_map *m, const uint8_t *gz, size_t n, const BgzfIndex &ix, hipStream_t st) {
+    const size_t batch = bgzf_batch_bytes(), nm = ix.in_off.size(), head = BGZF_CARRY + 16;
+    size_t biggest = 0;
+    for (size_t m0 = 0; m0 < nm;) { const size_t m1 = bgzf_next_batch(ix, m0, batch); biggest = std::max(biggest, bgzf_batch_text(ix, m0, m1)); m0 = m1; }
+    BgzfDev dv;
+    uint8_t *d_txt = nullptr, *d_tail = nullptr;
+    int rc = TSX_HIP_OK;
+    if (hipMalloc((void **)&d_txt, head + biggest + 256) != hipSuccess || hipMalloc((void **)&d_tail, head) != hipSuccess) {
+        g_last_error = "hipMalloc of a BGZF text buffer failed";
+        rc = TSX_HIP_ENOMEM;
+    }
+    size_t r = 0;   // bytes of the carried record in d_tail
+    for (size_t m0 = 0; m0 < nm && rc == TSX_HIP_OK;) {
+        const size_t m1 = bgzf_next_batch(ix, m0, batch), nb = bgzf_batch_text(ix, m0, m1);
+        const bool last = m1 == nm;
+        if ((rc = inflate_batch(gz, n, ix, m0, m1, dv, d_txt + head, st)) != TSX_HIP_OK) break;
+        const size_t ra = (r + 15) & ~(size_t)15;
+        uint8_t *piece = d_txt + head - ra;
+        if ((ra > r && hipMemsetAsync(piece, '\n', ra - r, st) != hipSuccess) ||
+            (r && hipMemcpyAsync(piece + ra - r, d_tail, r, hipMemcpyDeviceToDevice, st) != hipSuccess) ||
+            hipMemsetAsync(d_txt + head + nb, '\n', 256, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        const size_t len = ra + nb;
+        uint64_t cut = 0;
+        if ((rc = count_record_piece(m, piece, len, last, st, cut)) != TSX_HIP_OK) break;
+        if (!last) {
+            const size_t rest = len - cut;
+            if (rest > BGZF_CARRY) {
+                g_last_error = "min_qual_char: a record longer than " + std::to_string(BGZF_CARRY) + " bytes in a BGZF file";
+                rc = TSX_HIP_ERANGE;
+                break;
+            }
+            if (rest && hipMemcpyAsync(d_tail, piece + cut, rest, hipMemcpyDeviceToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            r = rest;
+        }
+        if (hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }   // (d_txt is refilled next)
+        m0 = m1;
+    }
+    hipError_t e = hipStreamSynchronize(st);
+    (void)hipFree(d_txt); (void)hipFree(d_tail);
+    if (rc == TSX_HIP_OK && e != hipSuccess) { g_last_error = hipGetErrorString(e); rc = TSX_HIP_EHIP; }
+    return rc;
+}
+
 extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, size_t n) {
     if (!m || (!gz && n)) return TSX_HIP_EINVAL;
     if (m->p.lg != m->p.l) return TSX_HIP_EINVAL;   // see tsx_hip_count_fastq_device
@@ -2224,6 +2415,8 @@ extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, siz
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = m->stream;
     join_foreign(m, false);
+    if (int rcq = base_rule_ok(m)) return rcq;
+    if (m->minq) return count_bgzf_records(m, (const uint8_t *)gz, n, ix, st);
     HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));
     const size_t batch = bgzf_batch_bytes(), nm = ix.in_off.size(), head = BGZF_PRE + 16;
     size_t biggest = 0;
@@ -2339,7 +2532,10 @@ extern "C" int tsx_hip_count_fastq_host(tsx_hip_map *m, const char *text, size_t
         (void)hipFree(d_text);
         return rcb;
     }
-    int rc = ensure_staging(m, n);
+    int rc = base_rule_ok(m);
+    if (rc != TSX_HIP_OK) return rc;
+    if (m->minq) return count_host_records(m, text, n);
+    rc = ensure_staging(m, n);
     if (rc != TSX_HIP_OK) return rc;
     hipStream_t st = m->stream;
     HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));
@@ -2928,9 +3124,10 @@ static int query_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint6
     const size_t lut_bytes = m->lut.size() * 8;
     const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 4);
     const uint32_t lshift = m->p.line_mask == 3 ? 2u : 1u;
-    DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((query_reads_kernel<WKV, CANV>), dim3(grid), dim3(NT), lut_bytes, st,
-                                                        m->p, d_text, n, own_end, head_open, (const uint32_t *)m->d_tile,
-                                                        ntiles, d_line_base, lshift, lower, upper, d_stats, (uint64_t)cap)));
+    DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((query_reads_kernel<WKV, CANV, BRV>), dim3(grid), dim3(NT),
+                                                        lut_bytes, st, m->p, d_text, n, own_end, head_open,
+                                                        (const uint32_t *)m->d_tile, ntiles, d_line_base, lshift, lower, upper,
+                                                        d_stats, (uint64_t)cap, m->qmap_cur))));
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
@@ -2947,6 +3144,10 @@ extern "C" int tsx_hip_query_reads_device(tsx_hip_map *m, const void *dev_text, 
     hipStream_t st = pick_stream(m, stream);
     int rc = ensure_zeroed(m, st);
     if (rc != TSX_HIP_OK) return rc;
+    if ((rc = base_rule_ok(m)) != TSX_HIP_OK) return rc;
+    if (m->minq && (rc = build_qmap(m, (const uint8_t *)dev_text, n, st)) != TSX_HIP_OK) return rc;
+    const uint16_t *qmap = m->minq ? m->d_qmap : nullptr;
+    QmapScope qs(m);
     unsigned long long *stats = (unsigned long long *)dev_stats;
     unsigned long long *d_base = (unsigned long long *)m->d_carry + 2, *d_nrec = d_base + 1;
     if (stats_cap) HIP_TRY(hipMemsetAsync(stats, 0, stats_cap * sizeof(tsx_hip_read_stats), st));
@@ -2957,6 +3158,7 @@ extern "C" int tsx_hip_query_reads_device(tsx_hip_map *m, const void *dev_text, 
     for (size_t off = 0; off < n; off += WIN) {
         const size_t own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
         const int head_open = off > 0 ? -1 : 0;
+        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;   // (windows start at multiples of 16)
         HIP_TRY(hipMemsetAsync(m->d_carry, 0, sizeof(uint32_t), st));
         if ((rc = query_line_pass(m, base + off, len, own, head_open, st)) != TSX_HIP_OK) return rc;
         if ((rc = query_launch(m, base + off, len, own, head_open, d_base, lower, upper, stats, stats_cap, st)) != TSX_HIP_OK)
@@ -3028,6 +3230,11 @@ static int query_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint
     if (nrec == 0) return TSX_HIP_OK;
     if ((rc = grow(st, b.stats, b.stats_have, nrec * sizeof(tsx_hip_read_stats))) != TSX_HIP_OK) return rc;
     HIP_TRY(hipMemsetAsync(b.stats, 0, nrec * sizeof(tsx_hip_read_stats), st));
+    QmapScope qs(m);
+    if (m->minq) {   // a quality rule: the bitmap of the whole records (its line pass over [0, cut) rewrites d_tile with the same values)
+        if ((rc = build_qmap(m, d_text, cut, st)) != TSX_HIP_OK) return rc;
+        m->qmap_cur = m->d_qmap;
+    }
     if ((rc = query_launch(m, d_text, cut, cut, 0, b.info + 4, lower, upper, b.stats, nrec, st)) != TSX_HIP_OK) return rc;
     hipLaunchKernelGGL(query_finalize_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.stats, nrec,
                        (const unsigned long long *)nullptr, nrec);
@@ -3076,7 +3283,8 @@ static int query_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower
     HIP_TRY(hipSetDevice(m->device));
     join_foreign(m, false);
     hipStream_t st = m->stream;
-    int rc = ensure_zeroed(m, st);
+    int rc = base_rule_ok(m);
+    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
     if (rc != TSX_HIP_OK) return rc;
     QueryBufs b;
     rc = b.init(st);
@@ -3171,7 +3379,8 @@ extern "C" int tsx_hip_filter_reads_device(tsx_hip_map *m, const void *dev_text,
     if (out_cap < n + 64) return TSX_HIP_ERANGE;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
-    int rc = ensure_zeroed(m, st);
+    int rc = base_rule_ok(m);
+    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
     if (rc != TSX_HIP_OK) return rc;
     QueryBufs b;
     rc = b.init(st);

@@ -281,6 +281,9 @@ class ShardedCounter:
         if getattr(hmap, "canonical", False):
             raise ValueError("%s: no canonical counting (the exchange's owners are strand-dependent); "
                              "count per GPU and merge_tables instead" % type(self).__name__)
+        if getattr(hmap, "base_rule", (False, None)) != (False, None):
+            raise ValueError("%s: no base rule (acgt_only / min_qual_char); count per GPU and merge_tables instead"
+                             % type(self).__name__)
         self.m = hmap
         self.comm = _comm(group)
         self.world, self.rank = self.comm.world, self.comm.rank
@@ -616,6 +619,9 @@ class MinimizerCounter:
         if getattr(hmap, "canonical", False):
             raise ValueError("%s: no canonical counting (the exchange's owners are strand-dependent); "
                              "count per GPU and merge_tables instead" % type(self).__name__)
+        if getattr(hmap, "base_rule", (False, None)) != (False, None):
+            raise ValueError("%s: no base rule (acgt_only / min_qual_char); count per GPU and merge_tables instead"
+                             % type(self).__name__)
         from . import _check
         self.m = hmap
         self.comm = _comm(group)

@@ -177,6 +177,8 @@ public:
     void setRecordLines(int iLines) { check(tsx_hip_set_record_lines(m_pMap, iLines)); }
     // canonical counting: a k-mer and its reverse complement share one counter (empty table only)
     void setCanonical(bool bOn) { check(tsx_hip_set_canonical(m_pMap, bOn ? 1 : 0)); }
+    // base rule: which windows are k-mers -- only ACGTacgt bytes, every quality byte >= iMinQualChar (0 = off; FASTQ)
+    void setBaseRule(bool bAcgtOnly, int iMinQualChar) { check(tsx_hip_set_base_rule(m_pMap, bAcgtOnly ? 1 : 0, iMinQualChar)); }
 
     // countKMers body (main.cpp:104-218): whole FASTQ text -> table
     void countFastq(const char *pText, size_t iBytes) { check(tsx_hip_count_fastq_host(m_pMap, pText, iBytes)); }
@@ -249,6 +251,8 @@ public:
     void setRecordLines(int iLines) { check(tsx_hip_group_set_record_lines(m_pGroup, iLines)); }
     // canonical counting on every GPU's table (the merge only: not with the minimizer exchange)
     void setCanonical(bool bOn) { check(tsx_hip_group_set_canonical(m_pGroup, bOn ? 1 : 0)); }
+    // the base rule on every GPU's table (the merge only: not with the minimizer exchange)
+    void setBaseRule(bool bAcgtOnly, int iMinQualChar) { check(tsx_hip_group_set_base_rule(m_pGroup, bAcgtOnly ? 1 : 0, iMinQualChar)); }
     // 0: per-GPU tables merged after the count (any k); 1: the minimizer exchange (20 <= k <= 32, at most 16 GPUs)
     void setExchange(int iMode) { check(tsx_hip_group_set_exchange(m_pGroup, iMode)); }
     int exchange() const { return tsx_hip_group_exchange(m_pGroup); }

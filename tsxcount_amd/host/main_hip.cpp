@@ -34,6 +34,8 @@ struct arguments {
                                   // auto: from 4 GPUs on where it applies)
     std::vector<int> devices;     // --devices=a,b,...: HIP ordinal per rank (default 0 .. N-1)
     bool canonical = false;       // --canonical: a k-mer and its reverse complement share one counter
+    bool acgt_only = false;       // --acgt-only: windows with a byte outside ACGTacgt are not k-mers
+    int min_qual_char = 0;        // --min-qual-char=C: windows with a base whose quality byte is below C are not k-mers
     std::string output, histo;    // --output=FILE: "kmer<TAB>count" lines; --histo=FILE: "count<TAB>k-mers" lines
     uint64_t lower = 1, upper = UINT64_MAX;   // --lower / --upper: the counts --output writes
     uint64_t histo_max = 10000;   // --histo-max=H: counts 1..H, then one line H+1 for everything above
@@ -55,12 +57,16 @@ static bool opt(const char *arg, const char *name, std::string &val) {
 static int usage() {
     std::cerr << "Usage: tsxCount --input=FASTQ|FASTA[.gz] [--k=K] [--l=L] [--s=STORAGE] [--mode=HIP] [--threads=T]\n"
                  "                [--check] [--checkabort] [--seed=S] [--device=D] [--format=fastq|fasta] [--canonical]\n"
+                 "                [--acgt-only] [--min-qual-char=C]\n"
                  "                [--gpus=N [--comm=rccl|copy] [--devices=a,b,...] [--exchange=merge|mini|auto]]\n"
                  "                [--output=FILE [--lower=N] [--upper=N]] [--histo=FILE [--histo-max=H]]\n"
                  "                [--filter=OUT] [--read-stats=FILE] [--filter-input=FILE] [--filter-lower=N] [--filter-upper=N]\n"
                  "                [--filter-min=M] [--filter-fraction=F] [--filter-invert]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
                  "--canonical counts a k-mer and its reverse complement as one (the check then expects f(x) + f(rc x)).\n"
+                 "--acgt-only skips every k-mer with a byte outside ACGTacgt (an N, say); --min-qual-char=C every k-mer with a\n"
+                 "base whose quality byte is below the character C, or that has none (FASTQ only). Both hold for the read\n"
+                 "queries too.\n"
                  "--output writes every k-mer counted lower..upper times (default 1..unbounded) as kmer<TAB>count, in no\n"
                  "particular order. --histo writes count<TAB>number of k-mers for every count 1..H (default 10000) that\n"
                  "occurs, then H+1<TAB>number of k-mers counted more than H times.\n"
@@ -311,9 +317,11 @@ static int run_group(const arguments &a) {
                               (uint16_t)a.k, a.seed, a.comm == "copy" ? 1 : 0);
     if (is_fasta(a)) { oGroup.setRecordLines(2); std::cerr << "Format=FASTA (2 lines per record)" << std::endl; }
     if (a.canonical) oGroup.setCanonical(true);
+    if (a.acgt_only || a.min_qual_char) oGroup.setBaseRule(a.acgt_only, a.min_qual_char);
     // the minimizer exchange where it applies (auto: from 4 GPUs on, as bench.py, and not with --canonical); --exchange=mini
     // insists on it
-    if (a.exchange == "mini" || (a.exchange == "auto" && !a.canonical && a.gpus >= 4 && a.gpus <= 16 && a.k >= 20 && a.k <= 32)) {
+    const bool rule = a.acgt_only || a.min_qual_char;
+    if (a.exchange == "mini" || (a.exchange == "auto" && !a.canonical && !rule && a.gpus >= 4 && a.gpus <= 16 && a.k >= 20 && a.k <= 32)) {
         try { oGroup.setExchange(1); }
         catch (const TSXException &e) { if (a.exchange == "mini") throw; }
     }
@@ -358,6 +366,11 @@ int main(int argc, char *argv[]) {
         else if (opt(argv[i], "comm", v)) a.comm = v;
         else if (opt(argv[i], "exchange", v)) a.exchange = v;
         else if (opt(argv[i], "canonical", v)) a.canonical = true;
+        else if (opt(argv[i], "acgt-only", v)) a.acgt_only = true;
+        else if (opt(argv[i], "min-qual-char", v)) {
+            if (v.size() != 1) { std::cerr << "--min-qual-char takes one character (e.g. --min-qual-char=5)" << std::endl; return usage(); }
+            a.min_qual_char = (unsigned char)v[0];
+        }
         else if (opt(argv[i], "output", v)) a.output = v;
         else if (opt(argv[i], "lower", v)) a.lower = strtoull(v.c_str(), nullptr, 10);
         else if (opt(argv[i], "upper", v)) a.upper = strtoull(v.c_str(), nullptr, 10);
@@ -391,6 +404,8 @@ int main(int argc, char *argv[]) {
     std::cerr << "StorageBits=" << a.storagebits << std::endl;
     std::cerr << "Check=" << (a.check ? "Yes" : "No") << std::endl;
     if (a.canonical) std::cerr << "Canonical=Yes" << std::endl;
+    if (a.acgt_only) std::cerr << "AcgtOnly=Yes" << std::endl;
+    if (a.min_qual_char) std::cerr << "MinQualChar=" << (char)a.min_qual_char << std::endl;
     std::cerr << "Input=" << a.input_path << std::endl;
     std::cerr << "Threads=" << a.threads << std::endl;
     std::cerr << "Mode=" << a.mode << std::endl;
@@ -404,6 +419,14 @@ int main(int argc, char *argv[]) {
     if (a.lower > a.upper || a.histo_max < 1 || a.histo_max > ((uint64_t)1 << 32)) return usage();
     if (a.canonical && a.group && a.exchange == "mini") {
         std::cerr << "--exchange=mini cannot count canonically (its owners are strand-dependent); use --exchange=merge" << std::endl;
+        return usage();
+    }
+    if ((a.acgt_only || a.min_qual_char) && a.group && a.exchange == "mini") {
+        std::cerr << "--exchange=mini has no base rule (--acgt-only, --min-qual-char); use --exchange=merge" << std::endl;
+        return usage();
+    }
+    if (a.min_qual_char && is_fasta(a)) {
+        std::cerr << "--min-qual-char needs FASTQ input: a FASTA record has no quality line" << std::endl;
         return usage();
     }
     if (a.gpus < 1 || (a.comm != "rccl" && a.comm != "copy") || (!a.devices.empty() && (int)a.devices.size() != a.gpus)) return usage();
@@ -420,6 +443,7 @@ int main(int argc, char *argv[]) {
         TSXHashMapHIP oMap((uint8_t)a.l, (uint32_t)a.storagebits, (uint16_t)a.k, (uint8_t)a.threads, a.seed, a.device);
         if (is_fasta(a)) { oMap.setRecordLines(2); std::cerr << "Format=FASTA (2 lines per record)" << std::endl; }
         if (a.canonical) oMap.setCanonical(true);
+        if (a.acgt_only || a.min_qual_char) oMap.setBaseRule(a.acgt_only, a.min_qual_char);
         std::vector<char> owned;
         const char *text = nullptr;
         size_t n = 0;
