@@ -35,7 +35,8 @@ enum {
     TSX_HIP_EOVERFLOW = -6, /* the secondary (count overflow) array is full */
     TSX_HIP_ERANGE = -7,    /* output buffer too small */
     TSX_HIP_ELOCK = -8,     /* a multi-limb slot stayed locked past the spin bound: counts may be wrong */
-    TSX_HIP_EIO = -9        /* writing an output file failed (see tsx_hip_last_error) */
+    TSX_HIP_EIO = -9,       /* writing an output file failed (see tsx_hip_last_error) */
+    TSX_HIP_EFORMAT = -10   /* not a k-mer database, or a damaged one (see tsx_hip_last_error) */
 };
 
 /* Layout the library derived from (k, l, storagebits); see DESIGN.md. */
@@ -302,6 +303,42 @@ int tsx_hip_format_counts_device(tsx_hip_map *m, uint64_t slot_lo, uint64_t slot
                                  void *dev_text, size_t cap, void *dev_nbytes, void *dev_nlines, void *stream);
 int tsx_hip_write_counts_host(tsx_hip_map *m, int fd, uint64_t lower, uint64_t upper, size_t chunk_bytes,
                               uint64_t *lines_out, uint64_t *bytes_out);
+
+/*
+ * K-mer database (csrc/tsx_db.h; no reference counterpart -- jellyfish `count -o` / `merge`): a lossless image of the
+ * occupied slots of one table in a file, loaded back into a table or added to one.  Format version 1, little-endian
+ * (DESIGN.md §3 "K-mer database"): a 128-byte header, one carry record per occupied entry of the secondary array
+ * (pos, carry, the W words of slot pos), then chunks in slot order -- slot_lo, slot_hi, n_entries, checksum, one
+ * occupancy bitmap word per 64 slots, the n_entries x W slot words as the table holds them -- and an end chunk with
+ * slot_lo == slot_hi == 2^l, n_entries == 0.
+ *   db_read_info  host only (no GPU): the header at offset 0 of fd (pread), magic, version and header checksum checked.
+ *   save_host     the table to fd from its current position, chunk_bytes at most per chunk (0 = 256 MiB; too small for
+ *                 64 slots: TSX_HIP_EINVAL); the device packs chunk i + 1 while the host writes chunk i.  Entries
+ *                 (= distinct) and bytes written (optional).  A failed write: TSX_HIP_EIO.
+ *   load_host     the database at the current position of fd into the table.  An empty table (just created or after
+ *                 tsx_hip_clear) with the database's l, slot layout, segment bits and seed takes the slots as they are
+ *                 (direct placement; the carries go through the secondary insert, so overflow_l may differ); any other
+ *                 table gets every k-mer added with its count (re-insert: a different l or storage bits or seed, or a
+ *                 table that already holds k-mers -- the load then merges by summing).  kmers_added grows by the
+ *                 database's.  chunk_bytes: initial staging size (0 = 256 MiB; a larger chunk is staged whole); the
+ *                 host reads chunk i + 1 while the device places chunk i.  Entries read (optional).
+ * TSX_HIP_EFORMAT: bad magic or version, a checksum mismatch, a missing end marker (truncated file), chunks that do not
+ * tile [0, 2^l), an occupied word with reprobe count 0 or LOCK set.  TSX_HIP_EINVAL: a different k, canonical mode or
+ * base rule than the table's, a map created with shard_bits > 0.  After any error of load_host the table's content is
+ * unspecified: tsx_hip_clear recovers it.  A tsx_hip_group is not saved or loaded (save each rank's map instead).
+ */
+typedef struct tsx_hip_db_info {
+    uint32_t version;
+    int32_t k, l;
+    int32_t entry_limbs, func_bits, reprobe_bits, count_bits, seg_bits, overflow_l;   /* the slot layout (tsx_hip_layout) */
+    int32_t canonical, acgt_only, min_qual_char;                                      /* counting mode and base rule */
+    uint64_t hash_seed;
+    uint64_t kmers_added, distinct, count_sum;                                        /* tsx_hip_stats at the save */
+    uint64_t carry_records;
+} tsx_hip_db_info;
+int tsx_hip_db_read_info(int fd, tsx_hip_db_info *out);
+int tsx_hip_save_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uint64_t *entries_out, uint64_t *bytes_out);
+int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uint64_t *entries_out);
 
 /*
  * Read queries (csrc/tsx_query.h; no reference counterpart): run the records of a text against the table.  Records and

@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libtsxcount_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tsxcount_hip.h")
 
 OK, EINVAL, ENODEVICE, ENOMEM, EHIP, EFULL, EOVERFLOW, ERANGE, ELOCK, EIO = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9
+EFORMAT = -10
 
 
 class TSXException(RuntimeError):
@@ -50,6 +51,19 @@ class FilterRule(ctypes.Structure):
     """tsx_hip_filter_rule: a record passes iff in_range >= min_in_range and in_range * 10^6 >= fraction_ppm * kmers."""
     _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("min_in_range", ctypes.c_uint64),
                 ("fraction_ppm", ctypes.c_uint32), ("invert", ctypes.c_int32)]
+
+
+class DbInfo(ctypes.Structure):
+    """tsx_hip_db_info: the header of a k-mer database file."""
+    _fields_ = [("version", ctypes.c_uint32), ("k", ctypes.c_int32), ("l", ctypes.c_int32),
+                ("entry_limbs", ctypes.c_int32), ("func_bits", ctypes.c_int32), ("reprobe_bits", ctypes.c_int32),
+                ("count_bits", ctypes.c_int32), ("seg_bits", ctypes.c_int32), ("overflow_l", ctypes.c_int32),
+                ("canonical", ctypes.c_int32), ("acgt_only", ctypes.c_int32), ("min_qual_char", ctypes.c_int32),
+                ("hash_seed", ctypes.c_uint64), ("kmers_added", ctypes.c_uint64), ("distinct", ctypes.c_uint64),
+                ("count_sum", ctypes.c_uint64), ("carry_records", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
 READ_STATS_DTYPE = np.dtype([("kmers", np.uint64), ("in_range", np.uint64), ("min_count", np.uint64), ("sum_count", np.uint64)])
@@ -142,6 +156,9 @@ def lib():
     L.tsx_hip_histogram_host.argtypes = [vp, u64p, sz]
     L.tsx_hip_format_counts_device.argtypes = [vp, u64, u64, u64, u64, vp, sz, vp, vp, vp]
     L.tsx_hip_write_counts_host.argtypes = [vp, ci, u64, u64, sz, u64p, u64p]
+    L.tsx_hip_db_read_info.argtypes = [ci, ctypes.POINTER(DbInfo)]
+    L.tsx_hip_save_host.argtypes = [vp, ci, sz, u64p, u64p]
+    L.tsx_hip_load_host.argtypes = [vp, ci, sz, u64p]
     L.tsx_hip_group_histogram_host.argtypes = [vp, u64p, sz]
     L.tsx_hip_group_write_counts_host.argtypes = [vp, ci, u64, u64, sz, u64p, u64p]
     L.tsx_hip_query_reads_device.argtypes = [vp, vp, sz, u64, u64, vp, sz, ctypes.POINTER(sz), vp]
@@ -187,7 +204,7 @@ def _check(code):
     if code != OK:
         L = lib()
         msg = L.tsx_hip_strerror(code).decode()
-        if code in (EHIP, ENODEVICE, ENOMEM, EIO):
+        if code in (EHIP, ENODEVICE, ENOMEM, EIO, EFORMAT):
             extra = L.tsx_hip_last_error().decode()
             if extra:
                 msg += " (" + extra + ")"
@@ -413,6 +430,51 @@ class TSXHashMapHIP:
         count_kmers.py / main.cpp:224-396), in no particular order.  Returns (lines, bytes)."""
         return _write_counts(self._lib.tsx_hip_write_counts_host, self.handle, _check, path, lower, upper, chunk_bytes)
 
+    def saveDatabase(self, path_or_fd, chunk_bytes=0):
+        """The table as a k-mer database (tsx_hip_save_host) to a path (created or truncated) or an open file descriptor
+        (written from its current position).  Returns (entries, bytes written)."""
+        entries, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        own = not isinstance(path_or_fd, int)
+        fd = os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd
+        try:
+            rc = self._lib.tsx_hip_save_host(self.handle, fd, int(chunk_bytes), ctypes.byref(entries), ctypes.byref(nbytes))
+        finally:
+            if own:
+                os.close(fd)
+        _check(rc)
+        return int(entries.value), int(nbytes.value)
+
+    def addDatabase(self, path_or_fd, chunk_bytes=0):
+        """Load a k-mer database into this table (tsx_hip_load_host): placed as it is into an empty table of the same
+        geometry and seed, otherwise every k-mer is added with its count (a merge).  Returns the entries read.  After an
+        error the table's content is unspecified: clear() recovers it."""
+        entries = ctypes.c_uint64(0)
+        own = not isinstance(path_or_fd, int)
+        fd = os.open(path_or_fd, os.O_RDONLY) if own else path_or_fd
+        try:
+            rc = self._lib.tsx_hip_load_host(self.handle, fd, int(chunk_bytes), ctypes.byref(entries))
+        finally:
+            if own:
+                os.close(fd)
+        _check(rc)
+        return int(entries.value)
+
+    @classmethod
+    def fromDatabase(cls, path, iL=None, iStorageBits=None, device=0, chunk_bytes=0):
+        """A new table holding a k-mer database: k, seed, counting mode and base rule come from the file; l and the
+        storage bits too unless given (a different geometry loads through the re-insert path)."""
+        info = database_info(path)
+        same = iL in (None, info["l"]) and iStorageBits in (None, info["count_bits"])
+        m = cls(info["l"] if iL is None else iL, info["count_bits"] if iStorageBits is None else iStorageBits, info["k"],
+                hash_seed=info["hash_seed"], overflow_l=info["overflow_l"] if same else 0, device=device,
+                canonical=bool(info["canonical"]), acgt_only=bool(info["acgt_only"]), min_qual_char=info["min_qual_char"] or None)
+        try:
+            m.addDatabase(path, chunk_bytes)
+        except Exception:
+            m.close()
+            raise
+        return m
+
     def queryReads(self, text, lower=1, upper=None, chunk_bytes=0):
         """Per-record k-mer stats of a FASTQ / FASTA text against the table (tsx_hip_query_reads_host): a numpy
         structured array (READ_STATS_DTYPE: kmers, in_range, min_count, sum_count), one entry per record in text
@@ -576,6 +638,20 @@ def _write_counts(fn, handle, check, path, lower, upper, chunk_bytes):
         os.close(fd)
     check(rc)
     return int(lines.value), int(nbytes.value)
+
+
+def database_info(path_or_fd):
+    """The header of a k-mer database file as a dict (tsx_hip_db_read_info; no GPU needed)."""
+    info = DbInfo()
+    own = not isinstance(path_or_fd, int)
+    fd = os.open(path_or_fd, os.O_RDONLY) if own else path_or_fd
+    try:
+        rc = lib().tsx_hip_db_read_info(fd, ctypes.byref(info))
+    finally:
+        if own:
+            os.close(fd)
+    _check(rc)
+    return info.as_dict()
 
 
 def cut_records(text, parts, lines_per_record=4):

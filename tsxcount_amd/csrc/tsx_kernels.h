@@ -1158,13 +1158,11 @@ __global__ __launch_bounds__(NT) void occupied_kernel(TableParams p) {
     }
 }
 
-// Rebuild the k-mer stored in slot `pos` (TSXHashMap::getAllKmers,
+// Rebuild the k-mer whose slot words e[0..W) sit in slot `pos` (TSXHashMap::getAllKmers,
 // TSXHashMap.h:660-722): hashed key = func bits | (pos - i(i+1)/2 mod 2^l),
-// then the inverse mapping.
+// then the inverse mapping.  e need not be in the table (the database loader, tsx_db.h).
 template <int WK>
-__device__ __forceinline__ void slot_to_kmer(const TableParams &p, uint64_t pos, uint64_t (&x)[WK],
-                                             uint64_t &count) {
-    const uint64_t *e = p.table + pos * (uint64_t)p.W;
+__device__ __forceinline__ void words_to_kmer(const TableParams &p, uint64_t pos, const uint64_t *e, uint64_t (&x)[WK]) {
     const uint64_t v = e[0];
     const uint32_t i = (uint32_t)(v & ((1ULL << p.R) - 1ULL));
     const uint64_t pos0 = (pos & ~p.seg_mask) | ((pos - (((uint64_t)i * (i + 1)) >> 1)) & p.seg_mask);
@@ -1191,7 +1189,15 @@ __device__ __forceinline__ void slot_to_kmer(const TableParams &p, uint64_t pos,
     h[0] |= pos0 | ((uint64_t)p.shard << p.l);
     h[WK - 1] &= p.top_mask;
     hash_apply<WK>(p, p.ilut, h, x);
-    count = (v >> p.cshift) + (sec_get(p, pos) << p.C);
+}
+
+// The k-mer in slot `pos` of the table and its count (in-slot field plus carries from the secondary array).
+template <int WK>
+__device__ __forceinline__ void slot_to_kmer(const TableParams &p, uint64_t pos, uint64_t (&x)[WK],
+                                             uint64_t &count) {
+    const uint64_t *e = p.table + pos * (uint64_t)p.W;
+    words_to_kmer<WK>(p, pos, e, x);
+    count = (e[0] >> p.cshift) + (sec_get(p, pos) << p.C);
 }
 
 __device__ __forceinline__ int owner_of(const uint64_t *x, int wk, int nranks) {

@@ -9,6 +9,7 @@
 #include "tsx_output.h"
 #include "tsx_query.h"
 #include "tsx_baserule.h"
+#include "tsx_db.h"
 
 #include <mutex>
 #include <hip/hip_runtime.h>
@@ -147,6 +148,7 @@ extern "C" const char *tsx_hip_strerror(int code) {
         case TSX_HIP_ERANGE: return "output buffer too small";
         case TSX_HIP_ELOCK: return "a multi-limb slot stayed locked past the spin bound";
         case TSX_HIP_EIO: return "writing the output failed";
+        case TSX_HIP_EFORMAT: return "not a k-mer database, or a damaged one";
     }
     return "unknown";
 }
@@ -2951,6 +2953,429 @@ extern "C" int tsx_hip_write_counts_host(tsx_hip_map *m, int fd, uint64_t lower,
     if (ev_txt) (void)hipEventDestroy(ev_txt);
     if (lines_out) *lines_out = lines;
     if (bytes_out) *bytes_out = bytes;
+    return rc;
+}
+
+// ---- k-mer database: save, load, merge (tsx_db.h; DESIGN.md §3 "K-mer database") -------------------------------
+static const uint8_t DB_MAGIC[8] = {'T', 'S', 'X', 'K', 'M', 'E', 'R', 'S'};
+static const uint32_t DB_VERSION = 1;
+static const size_t DB_HEADER = 128, DB_CHUNK_HEAD = 32;
+static const size_t DB_CHUNK_DEFAULT = (size_t)256 << 20;
+static_assert(__BYTE_ORDER__ == __ORDER_LITTLE_ENDIAN__, "the database format is little-endian, as the host");
+
+// FNV-1a, 64 bit: the checksum of the header (bytes 0 .. 119) and of the carry section.
+static uint64_t db_fnv(const void *p, size_t n, uint64_t h = 0xCBF29CE484222325ULL) {
+    const uint8_t *b = (const uint8_t *)p;
+    for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 0x100000001B3ULL; }
+    return h;
+}
+template <typename T> static inline void db_put(uint8_t *b, size_t at, T v) { memcpy(b + at, &v, sizeof v); }
+template <typename T> static inline T db_get(const uint8_t *b, size_t at) { T v; memcpy(&v, b + at, sizeof v); return v; }
+
+static int db_fail(const std::string &why) { g_last_error = why; return TSX_HIP_EFORMAT; }
+
+static void db_header_bytes(const tsx_hip_db_info &in, uint64_t carry_sum, uint8_t *b) {
+    memset(b, 0, DB_HEADER);
+    memcpy(b, DB_MAGIC, 8);
+    db_put<uint32_t>(b, 8, in.version); db_put<uint32_t>(b, 12, (uint32_t)DB_HEADER);
+    db_put<int32_t>(b, 16, in.k); db_put<int32_t>(b, 20, in.l); db_put<int32_t>(b, 24, in.entry_limbs);
+    db_put<int32_t>(b, 28, in.func_bits); db_put<int32_t>(b, 32, in.reprobe_bits); db_put<int32_t>(b, 36, in.count_bits);
+    db_put<int32_t>(b, 40, in.seg_bits); db_put<int32_t>(b, 44, in.overflow_l); db_put<uint64_t>(b, 48, in.hash_seed);
+    db_put<int32_t>(b, 56, in.canonical); db_put<int32_t>(b, 60, in.acgt_only); db_put<int32_t>(b, 64, in.min_qual_char);
+    db_put<uint64_t>(b, 72, in.kmers_added); db_put<uint64_t>(b, 80, in.distinct); db_put<uint64_t>(b, 88, in.count_sum);
+    db_put<uint64_t>(b, 96, in.carry_records); db_put<uint64_t>(b, 104, carry_sum);
+    db_put<uint64_t>(b, 120, db_fnv(b, 120));
+}
+
+static int db_parse_header(const uint8_t *b, tsx_hip_db_info *out, uint64_t *carry_sum) {
+    if (memcmp(b, DB_MAGIC, 8) != 0) return db_fail("not a k-mer database (bad magic)");
+    tsx_hip_db_info d;
+    d.version = db_get<uint32_t>(b, 8);
+    if (d.version != DB_VERSION || db_get<uint32_t>(b, 12) != DB_HEADER)
+        return db_fail("k-mer database format version " + std::to_string(d.version) + " (this library reads version 1)");
+    if (db_get<uint64_t>(b, 120) != db_fnv(b, 120)) return db_fail("k-mer database header checksum mismatch");
+    d.k = db_get<int32_t>(b, 16); d.l = db_get<int32_t>(b, 20); d.entry_limbs = db_get<int32_t>(b, 24);
+    d.func_bits = db_get<int32_t>(b, 28); d.reprobe_bits = db_get<int32_t>(b, 32); d.count_bits = db_get<int32_t>(b, 36);
+    d.seg_bits = db_get<int32_t>(b, 40); d.overflow_l = db_get<int32_t>(b, 44); d.hash_seed = db_get<uint64_t>(b, 48);
+    d.canonical = db_get<int32_t>(b, 56); d.acgt_only = db_get<int32_t>(b, 60); d.min_qual_char = db_get<int32_t>(b, 64);
+    d.kmers_added = db_get<uint64_t>(b, 72); d.distinct = db_get<uint64_t>(b, 80); d.count_sum = db_get<uint64_t>(b, 88);
+    d.carry_records = db_get<uint64_t>(b, 96);
+    if (d.k < 1 || d.k > 127 || d.l < 4 || d.l > 36 || d.entry_limbs < 1 || d.entry_limbs > 4 || d.seg_bits < 1 ||
+        d.seg_bits > d.l || (d.canonical & ~1) || (d.acgt_only & ~1) || d.min_qual_char < 0 || d.min_qual_char > 255 ||
+        d.carry_records > ((uint64_t)1 << d.l))
+        return db_fail("k-mer database header out of range");
+    if (out) *out = d;
+    if (carry_sum) *carry_sum = db_get<uint64_t>(b, 104);
+    return TSX_HIP_OK;
+}
+
+// read(2) until n bytes are in or the file ends: the bytes read; -1 on an error (g_last_error says which).
+static ssize_t db_read(int fd, void *p, size_t n) {
+    size_t got = 0;
+    while (got < n) {
+        const ssize_t r = read(fd, (uint8_t *)p + got, n - got);
+        if (r < 0 && errno == EINTR) continue;
+        if (r < 0) { g_last_error = std::string("read: ") + strerror(errno); return -1; }
+        if (r == 0) break;
+        got += (size_t)r;
+    }
+    return (ssize_t)got;
+}
+static int db_read_exact(int fd, void *p, size_t n, const char *what) {
+    const ssize_t r = db_read(fd, p, n);
+    if (r < 0) return TSX_HIP_EIO;
+    if ((size_t)r != n) return db_fail(std::string("k-mer database truncated (") + what + ")");
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_db_read_info(int fd, tsx_hip_db_info *out) {
+    if (fd < 0 || !out) return TSX_HIP_EINVAL;
+    uint8_t b[DB_HEADER];
+    size_t got = 0;
+    while (got < DB_HEADER) {
+        const ssize_t r = pread(fd, b + got, DB_HEADER - got, (off_t)got);
+        if (r < 0 && errno == EINTR) continue;
+        if (r < 0) { g_last_error = std::string("pread: ") + strerror(errno); return TSX_HIP_EIO; }
+        if (r == 0) return db_fail("k-mer database truncated (header)");
+        got += (size_t)r;
+    }
+    return db_parse_header(b, out, nullptr);
+}
+
+// Slots per chunk such that a chunk's worst case (every slot occupied) fits chunk_bytes; 0 when not even 64 do.
+static uint64_t db_span(size_t chunk_bytes, int W) {
+    if (chunk_bytes < DB_CHUNK_HEAD) return 0;
+    return (uint64_t)((chunk_bytes - DB_CHUNK_HEAD) / (8 + 64 * 8 * (size_t)W)) * 64;
+}
+static inline uint64_t db_tiles(uint64_t lo, uint64_t hi) { return (hi - lo + DB_TILE - 1) / DB_TILE; }
+
+extern "C" int tsx_hip_save_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uint64_t *entries_out, uint64_t *bytes_out) {
+    if (entries_out) *entries_out = 0;
+    if (bytes_out) *bytes_out = 0;
+    if (!m || fd < 0) return TSX_HIP_EINVAL;
+    if (m->p.lg != m->p.l) { g_last_error = "a shard of a multi-GPU table is not saved"; return TSX_HIP_EINVAL; }
+    if (!chunk_bytes) chunk_bytes = DB_CHUNK_DEFAULT;
+    const int W = m->p.W;
+    const uint64_t slots = m->lay.slots;
+    const uint64_t span = std::min<uint64_t>(db_span(chunk_bytes, W), (slots + 63) & ~63ULL);
+    if (span == 0) return TSX_HIP_EINVAL;
+    tsx_hip_stats s;
+    int rc = tsx_hip_get_stats(m, &s);   // (zeroes a lazily cleared table; waits for everything queued)
+    if (rc != TSX_HIP_OK) return rc;
+    hipStream_t st = m->stream;
+    // carry records, sorted by slot (the file does not depend on the secondary array's probe order)
+    const int RW = 2 + W;
+    std::vector<uint64_t> carry((size_t)s.overflow_used * RW);
+    if (s.overflow_used) {
+        uint64_t *d_rec = nullptr;
+        unsigned long long *d_n = nullptr, h_n = 0;
+        HIP_TRY(hipMalloc((void **)&d_rec, carry.size() * 8 + 8));
+        d_n = (unsigned long long *)(d_rec + carry.size());
+        rc = TSX_HIP_OK;
+        if (hipMemsetAsync(d_n, 0, 8, st) != hipSuccess) rc = TSX_HIP_EHIP;
+        if (rc == TSX_HIP_OK) {
+            hipLaunchKernelGGL(db_carry_gather_kernel, dim3(grid_for(m, m->p.sec_mask + 1, 8)), dim3(NT), 0, st, m->p, d_rec,
+                               (uint64_t)s.overflow_used, d_n);
+            if (hipGetLastError() != hipSuccess ||
+                hipMemcpyAsync(carry.data(), d_rec, carry.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+                rc = TSX_HIP_EHIP;
+        }
+        (void)hipFree(d_rec);
+        if (rc != TSX_HIP_OK) return rc;
+        if (h_n != s.overflow_used) { g_last_error = "secondary array changed during the save"; return TSX_HIP_EHIP; }
+        std::vector<uint64_t> order(s.overflow_used), sorted(carry.size());
+        for (uint64_t i = 0; i < s.overflow_used; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return carry[a * RW] < carry[b * RW]; });
+        for (uint64_t i = 0; i < s.overflow_used; ++i) memcpy(&sorted[i * RW], &carry[order[i] * RW], (size_t)RW * 8);
+        carry.swap(sorted);
+    }
+    tsx_hip_db_info info;
+    memset(&info, 0, sizeof info);
+    info.version = DB_VERSION; info.k = m->p.k; info.l = m->p.l; info.entry_limbs = W; info.func_bits = m->p.F;
+    info.reprobe_bits = m->p.R; info.count_bits = m->p.C; info.seg_bits = m->p.S; info.overflow_l = m->lay.overflow_l;
+    info.canonical = m->canon ? 1 : 0; info.acgt_only = m->p.acgt_only ? 1 : 0; info.min_qual_char = (int32_t)m->minq;
+    info.hash_seed = m->seed; info.kmers_added = s.kmers_added; info.distinct = s.distinct; info.count_sum = s.count_sum;
+    info.carry_records = s.overflow_used;
+    uint8_t head[DB_HEADER];
+    db_header_bytes(info, db_fnv(carry.data(), carry.size() * 8), head);
+    uint64_t bytes = 0, entries = 0;
+    rc = write_all(fd, head, DB_HEADER);
+    if (rc == TSX_HIP_OK && !carry.empty()) rc = write_all(fd, (const uint8_t *)carry.data(), carry.size() * 8);
+    if (rc != TSX_HIP_OK) return rc;
+    bytes += DB_HEADER + carry.size() * 8;
+
+    // chunks: stream order  pack(0) res(0) | payload(0) pack(1) res(1) | payload(1) pack(2) ...  -- the device packs
+    // chunk i + 1 while the host writes chunk i (tsx_hip_write_counts_host does the same with text)
+    const uint64_t nchunks = (slots + span - 1) / span, ntmax = db_tiles(0, span);
+    const size_t buf = (size_t)(span / 64 + span * W) * 8;
+    const int nbuf = nchunks > 1 ? 2 : 1;
+    uint64_t *d_buf[2] = {nullptr, nullptr}, *h_buf[2] = {nullptr, nullptr};
+    unsigned long long *d_tile = nullptr, *d_sum = nullptr, *h_res = nullptr;
+    hipEvent_t ev_res = nullptr, ev_buf = nullptr;
+    if (hipMalloc((void **)&d_tile, (ntmax + 2) * 8) != hipSuccess || hipHostMalloc((void **)&h_res, 2 * 8) != hipSuccess)
+        rc = TSX_HIP_ENOMEM;
+    d_sum = d_tile ? d_tile + ntmax + 1 : nullptr;
+    for (int b = 0; b < nbuf && rc == TSX_HIP_OK; ++b)
+        if (hipMalloc((void **)&d_buf[b], buf) != hipSuccess || hipHostMalloc((void **)&h_buf[b], buf) != hipSuccess)
+            rc = TSX_HIP_ENOMEM;
+    if (rc == TSX_HIP_OK && (hipEventCreateWithFlags(&ev_res, hipEventDisableTiming) != hipSuccess ||
+                             hipEventCreateWithFlags(&ev_buf, hipEventDisableTiming) != hipSuccess))
+        rc = TSX_HIP_EHIP;
+    auto queue_chunk = [&](uint64_t i) {
+        const uint64_t lo = i * span, hi = std::min(slots, lo + span), nt = db_tiles(lo, hi);
+        uint64_t *bm = d_buf[i & 1], *ent = bm + span / 64;
+        if (hipMemsetAsync(d_sum, 0, 8, st) != hipSuccess) return TSX_HIP_EHIP;
+        hipLaunchKernelGGL(db_count_table_kernel, dim3((unsigned)nt), dim3(NT), 0, st, m->p, lo, hi, d_tile);
+        hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(NT), 0, st, d_tile, nt);
+        hipLaunchKernelGGL(db_pack_kernel, dim3((unsigned)nt), dim3(NT), 0, st, m->p, lo, hi, (const unsigned long long *)d_tile,
+                           bm, ent, span, d_sum);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(h_res, d_tile + nt, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(h_res + 1, d_sum, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(ev_res, st) != hipSuccess)
+            return TSX_HIP_EHIP;
+        return TSX_HIP_OK;
+    };
+    if (rc == TSX_HIP_OK) rc = queue_chunk(0);
+    for (uint64_t i = 0; i < nchunks && rc == TSX_HIP_OK; ++i) {
+        const int b = (int)(i & 1);
+        const uint64_t lo = i * span, hi = std::min(slots, lo + span), nbm = (hi - lo + 63) / 64;
+        if (hipEventSynchronize(ev_res) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        const uint64_t n = h_res[0], sum = h_res[1];
+        if (n > hi - lo) { rc = TSX_HIP_ERANGE; break; }   // cannot happen: a tile counts at most its slots
+        const size_t bmb = (size_t)nbm * 8, entb = (size_t)n * W * 8;
+        if (hipMemcpyAsync(h_buf[b], d_buf[b], bmb, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            (entb && hipMemcpyAsync(h_buf[b] + span / 64, d_buf[b] + span / 64, entb, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+            hipEventRecord(ev_buf, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        if (i + 1 < nchunks && (rc = queue_chunk(i + 1)) != TSX_HIP_OK) break;
+        uint64_t ch[4] = {lo, hi, n, sum};
+        rc = write_all(fd, (const uint8_t *)ch, DB_CHUNK_HEAD);
+        if (hipEventSynchronize(ev_buf) != hipSuccess && rc == TSX_HIP_OK) rc = TSX_HIP_EHIP;
+        if (rc == TSX_HIP_OK) rc = write_all(fd, (const uint8_t *)h_buf[b], bmb);
+        if (rc == TSX_HIP_OK && entb) rc = write_all(fd, (const uint8_t *)(h_buf[b] + span / 64), entb);
+        if (rc == TSX_HIP_OK) { bytes += DB_CHUNK_HEAD + bmb + entb; entries += n; }
+    }
+    (void)hipStreamSynchronize(st);   // nothing queued may outlive the buffers
+    for (int b = 0; b < 2; ++b) {
+        if (d_buf[b]) (void)hipFree(d_buf[b]);
+        if (h_buf[b]) (void)hipHostFree(h_buf[b]);
+    }
+    if (d_tile) (void)hipFree(d_tile);
+    if (h_res) (void)hipHostFree(h_res);
+    if (ev_res) (void)hipEventDestroy(ev_res);
+    if (ev_buf) (void)hipEventDestroy(ev_buf);
+    if (rc == TSX_HIP_OK) {
+        const uint64_t end[4] = {slots, slots, 0, 0};
+        rc = write_all(fd, (const uint8_t *)end, DB_CHUNK_HEAD);
+        if (rc == TSX_HIP_OK) bytes += DB_CHUNK_HEAD;
+    }
+    if (rc == TSX_HIP_OK && entries != s.distinct) { g_last_error = "the table changed during the save"; rc = TSX_HIP_EHIP; }
+    if (entries_out) *entries_out = entries;
+    if (bytes_out) *bytes_out = bytes;
+    return rc;
+}
+
+// Staging of one chunk of the load (two of them alternate): the file bytes in pinned memory and on the device, the tile
+// offsets, the k-mers and counts of the re-insert path, and the result words of the load kernels.
+struct DbStage {
+    uint8_t *h = nullptr, *d = nullptr;
+    size_t cap = 0;
+    unsigned long long *d_tile = nullptr; uint64_t tile_cap = 0;
+    uint64_t *d_kx = nullptr; uint64_t kx_cap = 0;   // kmers (WK words) then counts, per entry
+    unsigned long long *d_res = nullptr, *h_res = nullptr;
+    hipEvent_t done = nullptr;
+    bool busy = false;
+    uint64_t n = 0, sum = 0;                          // what the chunk's head promised
+    void release() {
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+        if (d_tile) (void)hipFree(d_tile);
+        if (d_kx) (void)hipFree(d_kx);
+        if (d_res) (void)hipFree(d_res);
+        if (h_res) (void)hipHostFree(h_res);
+        if (done) (void)hipEventDestroy(done);
+    }
+};
+
+// The database layout as TableParams (what words_to_kmer needs), with its inverse mapping uploaded to *d_ilut.
+static int db_source_params(const tsx_hip_db_info &d, TableParams &sp, uint64_t **d_ilut) {
+    tsx_hip_map src;   // host fields only: no device allocations
+    if (derive_layout(&src, d.k, d.l, d.count_bits, d.overflow_l, 0, 0) != TSX_HIP_OK || src.p.W != d.entry_limbs ||
+        src.p.F != d.func_bits || src.p.R != d.reprobe_bits || src.p.C != d.count_bits)
+        return db_fail("k-mer database header: inconsistent slot layout");
+    src.p.S = d.seg_bits;
+    src.p.seg_mask = (1ULL << d.seg_bits) - 1ULL;
+    src.seed = d.hash_seed;
+    if (d_ilut) {
+        int rc = make_mapping(&src);
+        if (rc != TSX_HIP_OK) return rc;
+        make_lut(&src, src.irows, src.ilut);
+        HIP_TRY(hipMalloc((void **)d_ilut, src.ilut.size() * 8));
+        HIP_TRY(hipMemcpy(*d_ilut, src.ilut.data(), src.ilut.size() * 8, hipMemcpyHostToDevice));
+        src.p.ilut = *d_ilut;
+    }
+    src.p.table = nullptr; src.p.sec_keys = src.p.sec_cnt = nullptr; src.p.stats = nullptr; src.p.lut = nullptr;
+    src.p.roll = nullptr; src.p.seg_dirty = nullptr;
+    sp = src.p;
+    return TSX_HIP_OK;
+}
+
+template <typename T> static int db_grow_dev(T *&p, uint64_t &have, uint64_t need) {
+    if (need <= have) return TSX_HIP_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr; have = 0;
+    HIP_TRY(hipMalloc((void **)&p, need * sizeof(T)));
+    have = need;
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uint64_t *entries_out) {
+    if (entries_out) *entries_out = 0;
+    if (!m || fd < 0) return TSX_HIP_EINVAL;
+    if (m->p.lg != m->p.l) { g_last_error = "a shard of a multi-GPU table does not load a database"; return TSX_HIP_EINVAL; }
+    if (!chunk_bytes) chunk_bytes = DB_CHUNK_DEFAULT;
+    uint8_t head[DB_HEADER];
+    int rc = db_read_exact(fd, head, DB_HEADER, "header");
+    tsx_hip_db_info d;
+    uint64_t carry_sum = 0;
+    if (rc == TSX_HIP_OK) rc = db_parse_header(head, &d, &carry_sum);
+    if (rc != TSX_HIP_OK) return rc;
+    if (d.k != m->p.k || d.canonical != (m->canon ? 1 : 0) || d.acgt_only != (m->p.acgt_only ? 1 : 0) ||
+        d.min_qual_char != (int)m->minq) {
+        g_last_error = "the database was counted with a different k, canonical mode or base rule than this table";
+        return TSX_HIP_EINVAL;
+    }
+    HIP_TRY(hipSetDevice(m->device));
+    join_foreign(m, false);
+    hipStream_t st = m->stream;
+    TableParams sp;
+    uint64_t *d_ilut = nullptr;
+    const bool direct = !m->used && d.l == m->p.l && d.entry_limbs == m->p.W && d.func_bits == m->p.F &&
+                        d.reprobe_bits == m->p.R && d.count_bits == m->p.C && d.seg_bits == m->p.S && d.hash_seed == m->seed;
+    rc = db_source_params(d, sp, direct ? nullptr : &d_ilut);
+    if (rc != TSX_HIP_OK) { (void)hipFree(d_ilut); return rc; }
+    if (direct) sp = m->p;
+    const int W = d.entry_limbs, RW = 2 + W, WK = m->p.wk;
+    const uint64_t slots = 1ULL << d.l;
+    unsigned long long kmers_before = 0;
+    DbStage sg[2];
+    uint64_t *d_carry = nullptr;
+    uint64_t entries = 0;
+    do {
+        // the table: a direct load writes every slot, so a lazily cleared table needs no memset
+        if (direct) m->fresh = false;
+        else if ((rc = ensure_zeroed(m, st)) != TSX_HIP_OK) break;
+        m->used = true;
+        if (hipMemcpyAsync(&kmers_before, m->p.stats + ST_KMERS, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        // carry section
+        if (d.carry_records) {
+            std::vector<uint64_t> rec((size_t)d.carry_records * RW);
+            if ((rc = db_read_exact(fd, rec.data(), rec.size() * 8, "carry records")) != TSX_HIP_OK) break;
+            if (db_fnv(rec.data(), rec.size() * 8) != carry_sum) { rc = db_fail("k-mer database carry records checksum mismatch"); break; }
+            for (uint64_t i = 0; i < d.carry_records && rc == TSX_HIP_OK; ++i) {
+                const uint64_t *r = &rec[i * RW];
+                const uint64_t rp = r[2] & ((1ULL << sp.R) - 1ULL);
+                if (r[0] >= slots || r[1] == 0 || r[2] == 0 || rp == 0 || rp > sp.max_reprobes || (r[2] & sp.lock_bit))
+                    rc = db_fail("k-mer database: malformed carry record");
+            }
+            if (rc != TSX_HIP_OK) break;
+            const size_t kx = direct ? 0 : (size_t)d.carry_records * (WK + 1);
+            if (hipMalloc((void **)&d_carry, (rec.size() + kx) * 8) != hipSuccess) { rc = TSX_HIP_ENOMEM; break; }
+            if (hipMemcpyAsync(d_carry, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            const int grid = grid_for(m, d.carry_records, 8);
+            uint64_t *kx_k = d_carry + rec.size(), *kx_c = kx_k + (size_t)d.carry_records * WK;
+            if (direct) {
+                hipLaunchKernelGGL((db_carry_kernel<true, 1>), dim3(grid), dim3(NT), 0, st, m->p, sp, (const uint64_t *)d_carry,
+                                   (uint64_t)d.carry_records, (uint64_t *)nullptr, (uint64_t *)nullptr);
+            } else {
+                DISPATCH_WK(m, hipLaunchKernelGGL((db_carry_kernel<false, WKV>), dim3(grid), dim3(NT), 0, st, m->p, sp,
+                                                  (const uint64_t *)d_carry, (uint64_t)d.carry_records, kx_k, kx_c));
+            }
+            if (hipGetLastError() != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            if (!direct && (rc = tsx_hip_add_kmers_device(m, kx_k, kx_c, (size_t)d.carry_records, nullptr)) != TSX_HIP_OK) break;
+            if (hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }   // rec goes out of scope
+        }
+        // chunks: the host reads chunk i + 1 while the device places chunk i
+        for (int b = 0; b < 2 && rc == TSX_HIP_OK; ++b) {
+            if (hipEventCreateWithFlags(&sg[b].done, hipEventDisableTiming) != hipSuccess ||
+                hipMalloc((void **)&sg[b].d_res, DB_RES_N * 8) != hipSuccess ||
+                hipHostMalloc((void **)&sg[b].h_res, DB_RES_N * 8) != hipSuccess) rc = TSX_HIP_ENOMEM;
+        }
+        auto finish = [&](DbStage &s) -> int {   // the result of a chunk whose work has finished
+            s.busy = false;
+            if (s.h_res[DB_RES_TOTAL] != s.n) return db_fail("k-mer database chunk: bitmap and entry count disagree");
+            if (s.h_res[DB_RES_BAD]) return db_fail("k-mer database chunk: malformed entries");
+            if (s.h_res[DB_RES_SUM] != s.sum) return db_fail("k-mer database chunk checksum mismatch");
+            entries += s.n;
+            return TSX_HIP_OK;
+        };
+        uint64_t expect_lo = 0;
+        bool ended = false;
+        for (uint64_t i = 0; rc == TSX_HIP_OK && !ended; ++i) {
+            DbStage &s = sg[i & 1];
+            if (s.busy) {
+                if (hipEventSynchronize(s.done) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+                if ((rc = finish(s)) != TSX_HIP_OK) break;
+            }
+            uint64_t ch[4];
+            if ((rc = db_read_exact(fd, ch, DB_CHUNK_HEAD, "no end marker")) != TSX_HIP_OK) break;
+            const uint64_t lo = ch[0], hi = ch[1], n = ch[2];
+            if (lo != expect_lo || hi > slots || (lo == hi && (lo != slots || n != 0)) || n > hi - lo ||
+                ((hi - lo) & 63 && hi != slots)) { rc = db_fail("k-mer database: chunks do not tile the table"); break; }
+            if (lo == slots) { ended = true; break; }
+            expect_lo = hi;
+            const uint64_t nbm = (hi - lo + 63) / 64, nt = db_tiles(lo, hi);
+            const size_t bytes = (size_t)(nbm + n * W) * 8;
+            if (bytes > s.cap) {   // grow-only; chunk_bytes is the first size
+                if (s.h) (void)hipHostFree(s.h);
+                if (s.d) (void)hipFree(s.d);
+                s.h = s.d = nullptr; s.cap = 0;
+                const size_t want = std::max(bytes, std::min(chunk_bytes, (size_t)(slots / 64 + slots * W) * 8));
+                if (hipHostMalloc((void **)&s.h, want) != hipSuccess || hipMalloc((void **)&s.d, want) != hipSuccess) { rc = TSX_HIP_ENOMEM; break; }
+                s.cap = want;
+            }
+            if ((rc = db_grow_dev(s.d_tile, s.tile_cap, nt + 1)) != TSX_HIP_OK) break;
+            if (!direct && (rc = db_grow_dev(s.d_kx, s.kx_cap, std::max<uint64_t>(1, n) * (WK + 1))) != TSX_HIP_OK) break;
+            if ((rc = db_read_exact(fd, s.h, bytes, "chunk")) != TSX_HIP_OK) break;
+            s.n = n; s.sum = ch[3];
+            const uint64_t *bm = (const uint64_t *)s.d, *ent = bm + nbm;
+            uint64_t *kx_k = s.d_kx, *kx_c = s.d_kx ? s.d_kx + n * WK : nullptr;
+            const unsigned nb = (unsigned)((nt + NT / 64 - 1) / (NT / 64));
+            if (hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+                hipMemsetAsync(s.d_res, 0, DB_RES_N * 8, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            hipLaunchKernelGGL(db_count_bitmap_kernel, dim3(nb), dim3(NT), 0, st, bm, nbm, nt, s.d_tile);
+            hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(NT), 0, st, s.d_tile, nt);
+            if (direct) {
+                hipLaunchKernelGGL((db_load_kernel<true, 1>), dim3((unsigned)nt), dim3(NT), 0, st, m->p, sp, lo, hi, bm, ent, n,
+                                   (const unsigned long long *)s.d_tile, (uint64_t *)nullptr, (uint64_t *)nullptr, s.d_res);
+            } else {
+                DISPATCH_WK(m, hipLaunchKernelGGL((db_load_kernel<false, WKV>), dim3((unsigned)nt), dim3(NT), 0, st, m->p, sp, lo, hi,
+                                                  bm, ent, n, (const unsigned long long *)s.d_tile, kx_k, kx_c, s.d_res));
+            }
+            if (hipGetLastError() != hipSuccess ||
+                hipMemcpyAsync(s.d_res + DB_RES_TOTAL, s.d_tile + nt, 8, hipMemcpyDeviceToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            if (!direct && n && (rc = tsx_hip_add_kmers_device(m, kx_k, kx_c, (size_t)n, nullptr)) != TSX_HIP_OK) break;
+            if (hipMemcpyAsync(s.h_res, s.d_res, DB_RES_N * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipEventRecord(s.done, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            s.busy = true;
+        }
+        (void)hipStreamSynchronize(st);
+        for (int b = 0; b < 2; ++b)
+            if (sg[b].busy) { const int r = finish(sg[b]); if (rc == TSX_HIP_OK) rc = r; }
+        if (rc != TSX_HIP_OK) break;
+        if (entries != d.distinct) { rc = db_fail("k-mer database: entry count differs from the header"); break; }
+        // kmers_added grows by the database's (the re-insert has added the sum of the counts instead)
+        const unsigned long long ka = kmers_before + d.kmers_added;
+        if (hipMemcpyAsync(m->p.stats + ST_KMERS, &ka, 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        rc = tsx_hip_sync(m);
+    } while (0);
+    (void)hipStreamSynchronize(st);
+    for (int b = 0; b < 2; ++b) sg[b].release();
+    if (d_carry) (void)hipFree(d_carry);
+    if (d_ilut) (void)hipFree(d_ilut);
+    if (entries_out) *entries_out = entries;
     return rc;
 }
 

@@ -83,9 +83,9 @@ public:
     // TSXHashMapCAS(iL, iStorageBits, iK, iThreads) (TSXHashMapCAS.h:239-245);
     // iThreads is accepted for CLI compatibility, the GPU picks its own launch width.
     TSXHashMapHIP(uint8_t iL, uint32_t iStorageBits, uint16_t iK, uint8_t iThreads = 0, uint64_t iHashSeed = 1,
-                  int iDevice = 0)
+                  int iDevice = 0, int iOverflowL = 0)
         : m_iL(iL), m_iK(iK), m_iThreads(iThreads) {
-        int rc = tsx_hip_create(&m_pMap, iK, iL, (int)iStorageBits, 0, iHashSeed, iDevice);
+        int rc = tsx_hip_create(&m_pMap, iK, iL, (int)iStorageBits, iOverflowL, iHashSeed, iDevice);
         check(rc);
         check(tsx_hip_get_layout(m_pMap, &m_oLayout));
         std::cerr << "Creating array with " << m_oLayout.table_bytes << " bytes for " << m_oLayout.slots
@@ -162,6 +162,34 @@ public:
         }, check);
     }
 
+    // the table as a k-mer database file (tsx_hip_save_host), created / truncated; returns the entries written
+    uint64_t saveDatabase(const std::string &sPath, size_t iChunkBytes = 0) {
+        return tsx_write_counts_file(sPath, [&](int fd, uint64_t *e, uint64_t *b) {
+            return tsx_hip_save_host(m_pMap, fd, iChunkBytes, e, b);
+        }, check);
+    }
+    // a k-mer database into this table (tsx_hip_load_host): placed as it is, or added to what the table holds; returns the
+    // entries read
+    uint64_t loadDatabase(const std::string &sPath, size_t iChunkBytes = 0) {
+        const int fd = open(sPath.c_str(), O_RDONLY);
+        if (fd < 0) throw TSXException("could not open " + sPath, TSX_HIP_EIO);
+        uint64_t iEntries = 0;
+        const int rc = tsx_hip_load_host(m_pMap, fd, iChunkBytes, &iEntries);
+        close(fd);
+        check(rc);
+        return iEntries;
+    }
+    // the header of a k-mer database file (tsx_hip_db_read_info; no GPU)
+    static tsx_hip_db_info databaseInfo(const std::string &sPath) {
+        const int fd = open(sPath.c_str(), O_RDONLY);
+        if (fd < 0) throw TSXException("could not open " + sPath, TSX_HIP_EIO);
+        tsx_hip_db_info oInfo;
+        const int rc = tsx_hip_db_read_info(fd, &oInfo);
+        close(fd);
+        check(rc);
+        return oInfo;
+    }
+
     // per-record k-mer stats of a text against the table, records in text order (tsx_hip_query_reads_host)
     std::vector<tsx_hip_read_stats> queryReads(const char *pText, size_t iBytes, uint64_t iLower = 1,
                                                uint64_t iUpper = UINT64_MAX, size_t iChunkBytes = 0) {
@@ -213,7 +241,8 @@ private:
     static void check(int rc) {
         if (rc == TSX_HIP_OK) return;
         std::string msg = tsx_hip_strerror(rc);
-        if (rc == TSX_HIP_EHIP || rc == TSX_HIP_ENODEVICE || rc == TSX_HIP_ENOMEM || rc == TSX_HIP_EIO) {
+        if (rc == TSX_HIP_EHIP || rc == TSX_HIP_ENODEVICE || rc == TSX_HIP_ENOMEM || rc == TSX_HIP_EIO ||
+            rc == TSX_HIP_EFORMAT) {
             msg += " (";
             msg += tsx_hip_last_error();
             msg += ")";

@@ -45,6 +45,10 @@ struct arguments {
     uint64_t filter_lower = 2, filter_upper = UINT64_MAX, filter_min = 0;
     double filter_fraction = 1.0;
     bool filter_invert = false;
+    // k-mer databases: --save=DB after the count and the check, --load=DB[,DB2,...] before the count (summed)
+    std::string save;
+    std::vector<std::string> load;
+    bool given_k = false, given_l = false, given_s = false, given_seed = false;
 };
 
 static bool opt(const char *arg, const char *name, std::string &val) {
@@ -55,13 +59,13 @@ static bool opt(const char *arg, const char *name, std::string &val) {
 }
 
 static int usage() {
-    std::cerr << "Usage: tsxCount --input=FASTQ|FASTA[.gz] [--k=K] [--l=L] [--s=STORAGE] [--mode=HIP] [--threads=T]\n"
+    std::cerr << "Usage: tsxCount [--input=FASTQ|FASTA[.gz]] [--k=K] [--l=L] [--s=STORAGE] [--mode=HIP] [--threads=T]\n"
                  "                [--check] [--checkabort] [--seed=S] [--device=D] [--format=fastq|fasta] [--canonical]\n"
                  "                [--acgt-only] [--min-qual-char=C]\n"
                  "                [--gpus=N [--comm=rccl|copy] [--devices=a,b,...] [--exchange=merge|mini|auto]]\n"
                  "                [--output=FILE [--lower=N] [--upper=N]] [--histo=FILE [--histo-max=H]]\n"
                  "                [--filter=OUT] [--read-stats=FILE] [--filter-input=FILE] [--filter-lower=N] [--filter-upper=N]\n"
-                 "                [--filter-min=M] [--filter-fraction=F] [--filter-invert]\n"
+                 "                [--filter-min=M] [--filter-fraction=F] [--filter-invert] [--save=DB] [--load=DB[,DB2,...]]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
                  "--canonical counts a k-mer and its reverse complement as one (the check then expects f(x) + f(rc x)).\n"
                  "--acgt-only skips every k-mer with a byte outside ACGTacgt (an N, say); --min-qual-char=C every k-mer with a\n"
@@ -74,7 +78,12 @@ static int usage() {
                  "k-mer is in range when its count lies in filter-lower..filter-upper (default 2..unbounded); a record passes\n"
                  "with at least M (default 0) k-mers in range that make at least the share F (default 1.0) of its k-mers.\n"
                  "--filter-invert writes the records that fail. --read-stats writes index<TAB>kmers<TAB>in_range<TAB>min<TAB>sum\n"
-                 "per record of the same input. One GPU only."
+                 "per record of the same input. One GPU only.\n"
+                 "--save writes the table as a k-mer database after the count and the check. --load fills the table from\n"
+                 "k-mer databases first (several are summed); the first sets k, l, s and the seed unless they are given, a\n"
+                 "different l or s re-inserts every k-mer. --input is then optional: its reads are counted on top of the\n"
+                 "loaded counts. --load refuses --check; --filter and --read-stats without --input need --filter-input.\n"
+                 "--canonical, --acgt-only and --min-qual-char must match the databases. One GPU only."
               << std::endl;
     return 1;
 }
@@ -229,6 +238,14 @@ static int run_read_queries(tsx_hip_map *pMap, const arguments &a) {
     return 0;
 }
 
+// --save, after the count and the check (one table only: a group refuses it earlier)
+static void save_database(TSXHashMapHIP &oMap, const arguments &a) {
+    if (a.save.empty()) return;
+    const uint64_t iEntries = oMap.saveDatabase(a.save);
+    std::cerr << "Wrote a k-mer database of " << iEntries << " kmers to " << a.save << std::endl;
+}
+static void save_database(TSXHashMapHIPGroup &, const arguments &) {}
+
 // "Added a total of ..." and the --check of main.cpp:224-396, for one table or a group of them
 template <typename Map>
 static int report_and_check(Map &oMap, const arguments &a, double dt) {
@@ -304,6 +321,7 @@ static int report_and_check(Map &oMap, const arguments &a, double dt) {
         std::cout << "tsxCount kmer count: " << st.distinct << std::endl;
         if (totalerrors || iRefCount != st.distinct) rc = 5;
     }
+    save_database(oMap, a);
     write_outputs(oMap, a);
     oMap.print_stats();
     return rc;
@@ -351,15 +369,26 @@ int main(int argc, char *argv[]) {
     arguments a;
     for (int i = 1; i < argc; ++i) {
         std::string v;
-        if (opt(argv[i], "k", v)) a.k = atoi(v.c_str());
-        else if (opt(argv[i], "l", v)) a.l = atoi(v.c_str());
-        else if (opt(argv[i], "s", v)) a.storagebits = atoi(v.c_str());
+        if (opt(argv[i], "k", v)) { a.k = atoi(v.c_str()); a.given_k = true; }
+        else if (opt(argv[i], "l", v)) { a.l = atoi(v.c_str()); a.given_l = true; }
+        else if (opt(argv[i], "s", v)) { a.storagebits = atoi(v.c_str()); a.given_s = true; }
         else if (opt(argv[i], "threads", v)) a.threads = atoi(v.c_str());
         else if (opt(argv[i], "input", v)) a.input_path = v;
         else if (opt(argv[i], "mode", v)) a.mode = v;
         else if (opt(argv[i], "check", v)) a.check = true;
         else if (opt(argv[i], "checkabort", v)) a.checkabort = true;
-        else if (opt(argv[i], "seed", v)) a.seed = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "seed", v)) { a.seed = strtoull(v.c_str(), nullptr, 10); a.given_seed = true; }
+        else if (opt(argv[i], "save", v)) { a.save = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "load", v)) {
+            for (size_t at = 0; at <= v.size();) {
+                const size_t c = v.find(',', at);
+                const std::string one = v.substr(at, c == std::string::npos ? std::string::npos : c - at);
+                if (one.empty()) return usage();
+                a.load.push_back(one);
+                if (c == std::string::npos) break;
+                at = c + 1;
+            }
+        }
         else if (opt(argv[i], "format", v)) a.format = v;
         else if (opt(argv[i], "device", v)) a.device = atoi(v.c_str());
         else if (opt(argv[i], "gpus", v)) { a.gpus = atoi(v.c_str()); a.group = true; }
@@ -396,7 +425,32 @@ int main(int argc, char *argv[]) {
         else if (argv[i][0] == '-') { std::cerr << "unknown option " << argv[i] << std::endl; return usage(); }
     }
     std::transform(a.mode.begin(), a.mode.end(), a.mode.begin(), ::toupper);
-    if (a.input_path.empty()) return usage();
+    if (a.input_path.empty() && a.load.empty()) return usage();
+    // --load: the first database sets k, l, s and the seed unless they are given; every one must match the counting mode
+    int overflow_l = 0;
+    for (size_t i = 0; i < a.load.size(); ++i) {
+        tsx_hip_db_info d;
+        try {
+            d = TSXHashMapHIP::databaseInfo(a.load[i]);
+        } catch (const TSXException &e) {
+            std::cerr << "--load=" << a.load[i] << ": " << e.what() << std::endl;
+            return 3;
+        }
+        if (i == 0) {
+            if (!a.given_k) a.k = d.k;
+            if (!a.given_l) a.l = d.l;
+            if (!a.given_s) a.storagebits = d.count_bits;
+            if (!a.given_seed) a.seed = d.hash_seed;
+            if (a.l == d.l && a.storagebits == d.count_bits) overflow_l = d.overflow_l;
+        }
+        if (d.k != a.k || (d.canonical != 0) != a.canonical || (d.acgt_only != 0) != a.acgt_only || d.min_qual_char != a.min_qual_char) {
+            std::cerr << "--load=" << a.load[i] << " was counted with k=" << d.k << (d.canonical ? " --canonical" : "")
+                      << (d.acgt_only ? " --acgt-only" : "");
+            if (d.min_qual_char) std::cerr << " --min-qual-char=" << (char)d.min_qual_char;
+            std::cerr << "; give the same k, --canonical, --acgt-only and --min-qual-char to load it" << std::endl;
+            return 2;
+        }
+    }
 
     std::cout << "Running with parameters " << std::endl;
     std::cerr << "K=" << a.k << std::endl;
@@ -407,6 +461,8 @@ int main(int argc, char *argv[]) {
     if (a.acgt_only) std::cerr << "AcgtOnly=Yes" << std::endl;
     if (a.min_qual_char) std::cerr << "MinQualChar=" << (char)a.min_qual_char << std::endl;
     std::cerr << "Input=" << a.input_path << std::endl;
+    for (const std::string &db : a.load) std::cerr << "Load=" << db << std::endl;
+    if (!a.save.empty()) std::cerr << "Save=" << a.save << std::endl;
     std::cerr << "Threads=" << a.threads << std::endl;
     std::cerr << "Mode=" << a.mode << std::endl;
     if (a.mode != "HIP") {
@@ -437,10 +493,24 @@ int main(int argc, char *argv[]) {
                   << std::endl;
         return usage();
     }
+    if ((!a.save.empty() || !a.load.empty()) && a.gpus > 1) {
+        std::cerr << "--save and --load work on one GPU only: a --gpus " << a.gpus << " run keeps one table per GPU. Count with"
+                  << " --gpus=1 (or without --gpus) to save or load a k-mer database." << std::endl;
+        return usage();
+    }
+    if (!a.load.empty() && a.check) {
+        std::cerr << "--check compares the counts with those of --input alone: it cannot follow --load" << std::endl;
+        return usage();
+    }
+    if (wants_queries(a) && a.input_path.empty() && a.filter_input.empty()) {
+        std::cerr << "--filter and --read-stats without --input need --filter-input=FILE" << std::endl;
+        return usage();
+    }
+    if (!a.save.empty() || !a.load.empty()) a.group = false;   // --gpus=1: the one table of this process
     try {
         if (a.group) return run_group(a);
         std::cerr << "Creating TSXHashMap HIP" << std::endl;
-        TSXHashMapHIP oMap((uint8_t)a.l, (uint32_t)a.storagebits, (uint16_t)a.k, (uint8_t)a.threads, a.seed, a.device);
+        TSXHashMapHIP oMap((uint8_t)a.l, (uint32_t)a.storagebits, (uint16_t)a.k, (uint8_t)a.threads, a.seed, a.device, overflow_l);
         if (is_fasta(a)) { oMap.setRecordLines(2); std::cerr << "Format=FASTA (2 lines per record)" << std::endl; }
         if (a.canonical) oMap.setCanonical(true);
         if (a.acgt_only || a.min_qual_char) oMap.setBaseRule(a.acgt_only, a.min_qual_char);
@@ -449,12 +519,18 @@ int main(int argc, char *argv[]) {
         size_t n = 0;
         void *map = nullptr;
         bool bgzf = false;
-        if (!load_input(a.input_path, owned, text, n, map, bgzf, true)) {
+        if (!a.input_path.empty() && !load_input(a.input_path, owned, text, n, map, bgzf, true)) {
             std::cerr << "Could not read " << a.input_path << std::endl;
             return 3;
         }
         auto t0 = std::chrono::steady_clock::now();
-        if (bgzf) {
+        for (const std::string &db : a.load) {
+            const uint64_t iEntries = oMap.loadDatabase(db);
+            std::cerr << "Loaded " << iEntries << " kmers from " << db << std::endl;
+        }
+        if (a.input_path.empty()) {
+            // nothing to count: the loaded tables are the result
+        } else if (bgzf) {
             try {
                 oMap.countFastqBgzf(text, n);
             } catch (const TSXException &e) {
@@ -463,6 +539,7 @@ int main(int argc, char *argv[]) {
                 if (e.code() != TSX_HIP_ENOMEM) throw;
                 std::cerr << "BGZF on the device: " << e.what() << " -- reading through zlib instead" << std::endl;
                 oMap.clear();
+                for (const std::string &db : a.load) oMap.loadDatabase(db);
                 if (!read_gz(a.input_path, owned)) { std::cerr << "Could not read " << a.input_path << std::endl; return 3; }
                 oMap.countFastq(owned.data(), owned.size());
             }
