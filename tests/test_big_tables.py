@@ -18,6 +18,7 @@ into k-mers with the inverse mapping.
 The large cases (64-72 GiB tables) each run in a fresh process, one after another."""
 import ctypes
 import os
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -536,3 +537,70 @@ def test_wide_table_word_offsets_above_2_32(T, k, l, W):
     S = default_seg_bits(W, l)
     cut = (1 << 32) // W
     run_case("case_big", [k, l, 2, "atomic", False, [cut - 3, (1 << l) - 1], [cut]], {"TSX_HIP_SEG_BITS": str(S)}, 1200)
+
+
+# ---- 5. a database of a table above 2^32 slots ---------------------------------------------------------------------
+
+def case_big_database(k, l, s, homes):
+    """The partitioned k = 31, l = 33, s = 2 table of case_big saved as a k-mer database: the file read with kmerdb
+    (non-zero bitmap words only), placed directly into a fresh l = 33 table, counted on again slab by slab (the build
+    merges with the segments the load marked dirty) and re-inserted into a small table."""
+    import kmerdb as K
+    import tsxcount_amd as T
+    S = int(os.environ["TSX_HIP_SEG_BITS"])
+    rng = np.random.default_rng(l * 1000 + k + 1)
+    tmpdir = tempfile.mkdtemp(prefix="tsx_bigdb_")
+    db = os.path.join(tmpdir, "big.db")
+    m = T.TSXHashMapHIP(l, s, k)
+    try:
+        assert m.layout.count_bits == s and S == default_seg_bits(1, l)
+        m.set_path("partitioned")
+        rows = m.hash_rows()
+        bg_text, bk, bc, bn = background(k, 3000, 5)
+        bg_homes = np.sort(hash_keys(rows, bk, k)[:, 0] & np.uint64((1 << l) - 1))
+        mults = [1, 3, 4, 5, 1000, 65537]
+        planted = [(h, plant_cluster(m, rng, h, len(mults))) for h in homes]
+        for h, keys in planted:
+            assert window_is_free(predicted_slots(h, len(keys), S), bg_homes, S), h
+        pk = np.concatenate([keys for _, keys in planted])
+        reps = mults * len(homes)
+        text = bg_text + records(pk, reps, k, rng)
+        added = bn + sum(reps)
+        ek, ec = combine(np.concatenate([bk, pk]), np.concatenate([bc, np.array(reps, dtype=np.uint64)]))
+        m.countFastq(text)
+        check_counts(m, ek, ec, added)
+        assert max(check_clusters(m, planted, S)) >= 1 << 32
+        m.saveDatabase(db)
+    finally:
+        m.close()
+    f = K.read_db(db, rows)
+    assert f.kmers == dict(zip(kmer_strings(ek, k), ec.tolist()))
+    assert len(f.carries) >= len(planted) and max(f.entries) >= 1 << 32
+    d = T.TSXHashMapHIP(l, s, k)   # direct placement
+    try:
+        d.addDatabase(db)
+        check_counts(d, ek, ec, added)
+        check_clusters(d, planted, S)
+        d.set_path("partitioned")
+        d.countFastq(text)
+        check_counts(d, ek, 2 * ec, 2 * added)
+        check_clusters(d, planted, S)
+    finally:
+        d.close()
+    r = T.TSXHashMapHIP(24, s, k)   # re-insert
+    try:
+        r.addDatabase(db)
+        check_counts(r, ek, ec, added)
+    finally:
+        r.close()
+    os.unlink(db)
+    os.rmdir(tmpdir)
+
+
+def test_database_of_a_table_above_2_32_slots(T):
+    """Save and load a 2^33-slot table: its bitmap alone is 1 GiB."""
+    need_memory(BIG_NEED)
+    free = shutil.disk_usage(tempfile.gettempdir()).free
+    if free < 4 * GIB:
+        pytest.skip("needs 4 GiB free in %s for the database, has %.1f GiB" % (tempfile.gettempdir(), free / GIB))
+    run_case("case_big_database", [31, 33, 2, L33_HOMES], {"TSX_HIP_SEG_BITS": str(default_seg_bits(1, 33))}, 1500)

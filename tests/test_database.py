@@ -11,26 +11,10 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, python_counts
+from kmerdb import fnv1a64 as fnv, pack_header as header   # the header built from the format description
 
 EXE = os.path.join(ROOT, "tsxcount_amd", "bin", "tsxCount")
 GOLDEN_FASTQ = os.path.join(GOLDEN, "small_t7.1000.fastq")
-MAGIC = b"TSXKMERS"
-
-
-def fnv(b):
-    h = 0xCBF29CE484222325
-    for x in b:
-        h = ((h ^ x) * 0x100000001B3) & 0xFFFFFFFFFFFFFFFF
-    return h
-
-
-def header(version=1, k=31, l=20, W=1, F=42, R=8, C=14, S=14, ol=16, seed=7, canonical=0, acgt=0, minq=0,
-           added=1000, distinct=600, count_sum=1000, carries=0, carry_sum=fnv(b"")):
-    """A version-1 header built from the format description."""
-    b = MAGIC + struct.pack("<II8iQ3iI6Q", version, 128, k, l, W, F, R, C, S, ol, seed, canonical, acgt, minq, 0,
-                            added, distinct, count_sum, carries, carry_sum, 0)
-    assert len(b) == 120, len(b)
-    return bytes(b) + struct.pack("<Q", fnv(b))
 
 
 def run_cli(*args, timeout=300):

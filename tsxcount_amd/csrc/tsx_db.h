@@ -28,8 +28,9 @@ namespace tsx {
 
 constexpr uint32_t DB_TILE = 4096;   // slots per workgroup (64 bitmap words; 16 rounds of NT slots)
 constexpr uint64_t DB_SALT_BM = 0x6A09E667F3BCC909ULL, DB_SALT_E = 0xBB67AE8584CAA73BULL;
-enum DbRes { DB_RES_SUM = 0, DB_RES_BAD = 1, DB_RES_TOTAL = 2, DB_RES_N = 4 };   // per-chunk result words of a load (TOTAL: the
-                                                                               // bitmap's set bits, copied behind the scan)
+// Per-chunk result words of a load.  TOTAL: the bitmap's set bits, copied behind the scan; ZERO: entries whose in-slot
+// count is 0, each of which needs a carry record.
+enum DbRes { DB_RES_SUM = 0, DB_RES_BAD = 1, DB_RES_TOTAL = 2, DB_RES_ZERO = 3, DB_RES_N = 4 };
 
 __device__ __forceinline__ uint64_t db_bm_term(uint64_t gword, uint64_t bm) { return mix64(mix64(gword ^ DB_SALT_BM) ^ bm); }
 __device__ __forceinline__ uint64_t db_entry_term(uint64_t pos, const uint64_t (&e)[4], int W) {
@@ -37,10 +38,21 @@ __device__ __forceinline__ uint64_t db_entry_term(uint64_t pos, const uint64_t (
     for (int t = 0; t < W; ++t) h = mix64(h ^ e[t]);
     return h;
 }
-// What an occupied word 0 of a well-formed table looks like: reprobe count 1 .. max_reprobes, LOCK clear.
-__device__ __forceinline__ bool db_word_ok(const TableParams &p, uint64_t e0) {
-    const uint64_t i = e0 & ((1ULL << p.R) - 1ULL);
-    return e0 != 0 && i != 0 && i <= p.max_reprobes && (e0 & p.lock_bit) == 0;
+// What the W words of an occupied slot of a well-formed table look like: reprobe count 1 .. max_reprobes and no bit
+// outside the fields -- limb 0 holds the reprobe count, min(F, K0 - R) func bits and the counter (LOCK clear), limbs
+// 1..W-1 the func bits that spill, low bits first.  A stray bit would make direct placement keep a word that no lookup
+// matches while the re-insert path (words_to_kmer masks it away) counts a k-mer.
+__device__ __forceinline__ bool db_word_ok(const TableParams &p, const uint64_t (&e)[4]) {
+    const uint64_t i = e[0] & ((1ULL << p.R) - 1ULL);
+    const int f0 = min(p.F, p.K0 - p.R);
+    const uint64_t keep0 = ((1ULL << (p.R + f0)) - 1ULL) | (~0ULL << p.cshift);
+    bool ok = i != 0 && i <= p.max_reprobes && (e[0] & ~keep0) == 0;
+    int spill = p.F - f0;
+    for (int t = 1; t < p.W; ++t, spill -= 64) {
+        const uint64_t keep = spill >= 64 ? ~0ULL : spill <= 0 ? 0ULL : (1ULL << spill) - 1ULL;
+        ok = ok && (e[t] & ~keep) == 0;
+    }
+    return ok;
 }
 // Sum over the lanes of the workgroup, one atomic per wave.
 __device__ __forceinline__ void db_add(unsigned long long *dst, unsigned long long v) {
@@ -156,7 +168,8 @@ __global__ __launch_bounds__(NT) void db_pack_kernel(TableParams p, uint64_t slo
 
 // Load, pass 2, over the tiles of one chunk [slot_lo, slot_hi) held in device memory (bm: its bitmap, ent: its n_ent
 // entries).  src: the layout of the database (the table's own for PLACE).  res[DB_RES_SUM] += checksum of what was read,
-// res[DB_RES_BAD] += malformed entries (a set bit past slot_hi or past n_ent entries, a word that no table holds).
+// res[DB_RES_BAD] += malformed entries (a set bit past slot_hi or past n_ent entries, a word that no table holds),
+// res[DB_RES_ZERO] += entries whose in-slot count is 0 (the host matches them with carry records).
 //   PLACE   every slot of the range is written (zeros where the bitmap has none), seg_dirty set where entries land
 //   !PLACE  entry i -> kmers_out[i] (the k-mer, WK words) and counts_out[i] (its in-slot count)
 template <bool PLACE, int WK>
@@ -169,7 +182,7 @@ __global__ __launch_bounds__(NT) void db_load_kernel(TableParams p, TableParams 
     const uint64_t lt = (1ULL << lane) - 1ULL;
     const uint64_t t0 = slot_lo + (uint64_t)blockIdx.x * DB_TILE;
     uint64_t at = tile_off[blockIdx.x];
-    unsigned long long cs = 0, bad = 0;
+    unsigned long long cs = 0, bad = 0, zero = 0;
     for (uint32_t r = 0; r < DB_TILE; r += NT) {
         const uint64_t pos = t0 + r + threadIdx.x;
         const uint64_t wpos = pos - lane;
@@ -187,7 +200,8 @@ __global__ __launch_bounds__(NT) void db_load_kernel(TableParams p, TableParams 
             if (idx < n_ent) {
                 for (int t = 0; t < W; ++t) e[t] = ent[idx * W + t];
                 cs += db_entry_term(pos, e, W);
-                ok = db_word_ok(src, e[0]);
+                ok = db_word_ok(src, e);
+                zero += (e[0] >> src.cshift) == 0 ? 1 : 0;
                 if (ok && !PLACE) {
                     uint64_t x[WK];
                     words_to_kmer<WK>(src, pos, e, x);
@@ -206,6 +220,7 @@ __global__ __launch_bounds__(NT) void db_load_kernel(TableParams p, TableParams 
     }
     db_add(&res[DB_RES_SUM], cs);
     db_add(&res[DB_RES_BAD], bad);
+    db_add(&res[DB_RES_ZERO], zero);
 }
 
 // Save: every occupied entry of the secondary array as a record (pos, carry, the W words of slot pos), at most cap of

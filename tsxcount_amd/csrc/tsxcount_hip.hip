@@ -3186,6 +3186,7 @@ struct DbStage {
     hipEvent_t done = nullptr;
     bool busy = false;
     uint64_t n = 0, sum = 0;                          // what the chunk's head promised
+    uint64_t zero_carried = 0;                        // its entries with in-slot count 0 that a carry record names
     void release() {
         if (h) (void)hipHostFree(h);
         if (d) (void)hipFree(d);
@@ -3260,6 +3261,7 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
     unsigned long long kmers_before = 0;
     DbStage sg[2];
     uint64_t *d_carry = nullptr;
+    std::vector<uint64_t> rec;   // the carry records: each is checked against the chunk that holds its pos
     uint64_t entries = 0;
     do {
         // the table: a direct load writes every slot, so a lazily cleared table needs no memset
@@ -3270,7 +3272,7 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
             hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         // carry section
         if (d.carry_records) {
-            std::vector<uint64_t> rec((size_t)d.carry_records * RW);
+            rec.resize((size_t)d.carry_records * RW);
             if ((rc = db_read_exact(fd, rec.data(), rec.size() * 8, "carry records")) != TSX_HIP_OK) break;
             if (db_fnv(rec.data(), rec.size() * 8) != carry_sum) { rc = db_fail("k-mer database carry records checksum mismatch"); break; }
             for (uint64_t i = 0; i < d.carry_records && rc == TSX_HIP_OK; ++i) {
@@ -3278,6 +3280,8 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
                 const uint64_t rp = r[2] & ((1ULL << sp.R) - 1ULL);
                 if (r[0] >= slots || r[1] == 0 || r[2] == 0 || rp == 0 || rp > sp.max_reprobes || (r[2] & sp.lock_bit))
                     rc = db_fail("k-mer database: malformed carry record");
+                else if (i > 0 && r[0] <= r[-RW])
+                    rc = db_fail("k-mer database: carry records not sorted by slot or not unique");
             }
             if (rc != TSX_HIP_OK) break;
             const size_t kx = direct ? 0 : (size_t)d.carry_records * (WK + 1);
@@ -3294,7 +3298,7 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
             }
             if (hipGetLastError() != hipSuccess) { rc = TSX_HIP_EHIP; break; }
             if (!direct && (rc = tsx_hip_add_kmers_device(m, kx_k, kx_c, (size_t)d.carry_records, nullptr)) != TSX_HIP_OK) break;
-            if (hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }   // rec goes out of scope
+            if (hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         }
         // chunks: the host reads chunk i + 1 while the device places chunk i
         for (int b = 0; b < 2 && rc == TSX_HIP_OK; ++b) {
@@ -3307,10 +3311,11 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
             if (s.h_res[DB_RES_TOTAL] != s.n) return db_fail("k-mer database chunk: bitmap and entry count disagree");
             if (s.h_res[DB_RES_BAD]) return db_fail("k-mer database chunk: malformed entries");
             if (s.h_res[DB_RES_SUM] != s.sum) return db_fail("k-mer database chunk checksum mismatch");
+            if (s.h_res[DB_RES_ZERO] != s.zero_carried) return db_fail("k-mer database chunk: an entry with count 0");
             entries += s.n;
             return TSX_HIP_OK;
         };
-        uint64_t expect_lo = 0;
+        uint64_t expect_lo = 0, next_carry = 0;
         bool ended = false;
         for (uint64_t i = 0; rc == TSX_HIP_OK && !ended; ++i) {
             DbStage &s = sg[i & 1];
@@ -3339,6 +3344,27 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
             if (!direct && (rc = db_grow_dev(s.d_kx, s.kx_cap, std::max<uint64_t>(1, n) * (WK + 1))) != TSX_HIP_OK) break;
             if ((rc = db_read_exact(fd, s.h, bytes, "chunk")) != TSX_HIP_OK) break;
             s.n = n; s.sum = ch[3];
+            // the carry records of this chunk (sorted, so they come in order): slot pos must be occupied and hold the
+            // record's words; a popcount of the bitmap up to pos gives the entry's index.  In-slot counts of 0 are
+            // counted here and compared with the device's count of them, so that no entry's total count is 0.
+            {
+                const uint64_t *hbm = (const uint64_t *)s.h, *hent = hbm + nbm;
+                uint64_t w = 0, before = 0;   // set bits of the words before w
+                s.zero_carried = 0;
+                for (; next_carry < d.carry_records && rec[next_carry * RW] < hi; ++next_carry) {
+                    const uint64_t *r = &rec[next_carry * RW];
+                    const uint64_t off = r[0] - lo, wc = off >> 6;
+                    for (; w < wc; ++w) before += (uint64_t)__builtin_popcountll(hbm[w]);
+                    const uint64_t bit = 1ULL << (off & 63);
+                    const uint64_t idx = before + (uint64_t)__builtin_popcountll(hbm[wc] & (bit - 1ULL));
+                    if (!(hbm[wc] & bit) || idx >= n || memcmp(&hent[idx * W], r + 2, (size_t)W * 8) != 0) {
+                        rc = db_fail("k-mer database: a carry record does not match the entry at its slot");
+                        break;
+                    }
+                    s.zero_carried += (hent[idx * W] >> sp.cshift) == 0 ? 1 : 0;
+                }
+                if (rc != TSX_HIP_OK) break;
+            }
             const uint64_t *bm = (const uint64_t *)s.d, *ent = bm + nbm;
             uint64_t *kx_k = s.d_kx, *kx_c = s.d_kx ? s.d_kx + n * WK : nullptr;
             const unsigned nb = (unsigned)((nt + NT / 64 - 1) / (NT / 64));
