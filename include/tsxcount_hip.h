@@ -391,6 +391,48 @@ int tsx_hip_filter_reads_host(tsx_hip_map *m, const char *text, size_t n, const 
 int tsx_hip_filter_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_filter_rule *rule,
                                 void *dev_out, size_t out_cap, size_t *out_bytes, uint64_t *kept_out, void *stream);
 
+/*
+ * Table set operations (csrc/tsx_combine.h; no reference counterpart -- `kmc_tools simple`, `jellyfish merge --min/--max`):
+ * the k-mers of two tables A and B joined on the device into an EMPTY third table OUT, or only compared.  a(x), b(x) are
+ * getKmerCount(x) in A and B (in-slot field plus carries, 0 when absent; on canonical tables x is the pair).  First the
+ * ranges: a'(x) = a(x) if a_lower <= a(x) <= a_upper, else 0; the same for b'.  Then
+ *   op         x is in OUT iff        its count
+ *   INTERSECT  a' > 0 and b' > 0      MIN: min(a', b'); MAX: max; SUM: a' + b' (mod 2^64); LEFT: a'; RIGHT: b'
+ *   UNION      a' > 0 or b' > 0       both present: as INTERSECT; one present: that one's count (every count mode)
+ *   SUBTRACT   a' > 0 and b' = 0      a' (count_mode ignored)
+ *   DIFF       a' > b'                a' - b' (count_mode ignored)
+ * A lower bound of 0 is taken as 1 (an absent k-mer is never in range).  UNION / SUM with full ranges gives the table
+ * that tsx_hip_load_host gives when it merges B's database into A.
+ *   out == NULL   nothing is written, only stats_out is filled (Jaccard index = both / (a_in_range + b_in_range - both));
+ *                 out_entries / out_count_sum are then what the rule WOULD write.
+ *   out           empty (just created or after tsx_hip_clear), not a and not b, on the same device.  a == b is allowed.
+ * All three agree in k, canonical mode and base rule, and none was created with shard_bits > 0; l, storage bits,
+ * overflow_l and hash seed may differ between all three.  A and B are left as they are, bit for bit.  OUT's kmers_added
+ * grows by out_count_sum (count_sum == kmers_added keeps holding), its distinct is out_entries.  The call waits for what
+ * is queued on the three maps' streams, and for its own result.
+ * Two paths with identical results: when A and B share l, slot layout, segment bits and seed (the condition of
+ * tsx_hip_load_host's direct placement) the join works on hashed keys and stays inside one table segment per key
+ * ("aligned"; with OUT of that geometry too, nothing is staged); any other pair goes through k-mers ("general").
+ * TSX_HIP_EINVAL (tsx_hip_last_error says which): lower > upper, an unknown op or count mode, out not empty or equal to
+ * a or b, maps on different devices, a different k, canonical mode or base rule, a map created with shard_bits > 0.
+ * TSX_HIP_EFULL: a k-mer did not fit into OUT (sticky as for inserts; OUT's content is then unspecified, tsx_hip_clear
+ * recovers it).  TSX_HIP_EOVERFLOW: OUT's secondary array is full.
+ */
+enum { TSX_HIP_OP_INTERSECT = 0, TSX_HIP_OP_UNION = 1, TSX_HIP_OP_SUBTRACT = 2, TSX_HIP_OP_DIFF = 3 };
+enum { TSX_HIP_CNT_MIN = 0, TSX_HIP_CNT_MAX = 1, TSX_HIP_CNT_SUM = 2, TSX_HIP_CNT_LEFT = 3, TSX_HIP_CNT_RIGHT = 4 };
+typedef struct tsx_hip_combine_rule {
+    int32_t op, count_mode;
+    uint64_t a_lower, a_upper, b_lower, b_upper;   /* the count range of each input (kmc_tools -ci / -cx) */
+} tsx_hip_combine_rule;
+typedef struct tsx_hip_combine_stats {
+    uint64_t a_in_range, b_in_range;   /* distinct k-mers of A / B whose count is in its range */
+    uint64_t both;                     /* distinct k-mers in range in both */
+    uint64_t a_sum_both, b_sum_both;   /* sum of a' / b' over those */
+    uint64_t out_entries, out_count_sum;
+} tsx_hip_combine_stats;
+int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b, const tsx_hip_combine_rule *rule,
+                    tsx_hip_combine_stats *stats_out /* optional */);
+
 /* IBijectiveFunction::apply / inv_apply (IBijectiveFunction.h:26-27) on the host,
  * and the matrix rows (row i <-> output bit 2k-1-i, BijectiveKMapping.h:202-256). */
 int tsx_hip_hash_apply(const tsx_hip_map *m, const uint64_t *kmer, uint64_t *key_out);

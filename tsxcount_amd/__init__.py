@@ -66,6 +66,25 @@ class DbInfo(ctypes.Structure):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
+class CombineRule(ctypes.Structure):
+    """tsx_hip_combine_rule: the op, the count mode and the count range of each input."""
+    _fields_ = [("op", ctypes.c_int32), ("count_mode", ctypes.c_int32), ("a_lower", ctypes.c_uint64),
+                ("a_upper", ctypes.c_uint64), ("b_lower", ctypes.c_uint64), ("b_upper", ctypes.c_uint64)]
+
+
+class CombineStats(ctypes.Structure):
+    """tsx_hip_combine_stats."""
+    _fields_ = [("a_in_range", ctypes.c_uint64), ("b_in_range", ctypes.c_uint64), ("both", ctypes.c_uint64),
+                ("a_sum_both", ctypes.c_uint64), ("b_sum_both", ctypes.c_uint64), ("out_entries", ctypes.c_uint64),
+                ("out_count_sum", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+COMBINE_OPS = {"intersect": 0, "union": 1, "subtract": 2, "diff": 3}
+COMBINE_COUNTS = {"min": 0, "max": 1, "sum": 2, "left": 3, "right": 4}
+
 READ_STATS_DTYPE = np.dtype([("kmers", np.uint64), ("in_range", np.uint64), ("min_count", np.uint64), ("sum_count", np.uint64)])
 
 
@@ -73,6 +92,15 @@ def filter_rule(lower=2, upper=None, min_in_range=0, fraction=1.0, invert=False)
     """A FilterRule from the Python arguments (fraction: share of a record's k-mers that must be in range, 0..1)."""
     return FilterRule(int(lower), (1 << 64) - 1 if upper is None else int(upper), int(min_in_range),
                       int(round(float(fraction) * 1e6)), 1 if invert else 0)
+
+
+def combine_rule(op="intersect", counts="min", a_range=(1, None), b_range=(1, None)):
+    """A CombineRule from the Python arguments: op and counts by name (COMBINE_OPS, COMBINE_COUNTS) or number, each
+    range as (lower, upper) with None = no upper bound."""
+    top = (1 << 64) - 1
+    return CombineRule(int(COMBINE_OPS.get(op, op)), int(COMBINE_COUNTS.get(counts, counts)),
+                       int(a_range[0]), top if a_range[1] is None else int(a_range[1]),
+                       int(b_range[0]), top if b_range[1] is None else int(b_range[1]))
 
 
 def build():
@@ -159,6 +187,7 @@ def lib():
     L.tsx_hip_db_read_info.argtypes = [ci, ctypes.POINTER(DbInfo)]
     L.tsx_hip_save_host.argtypes = [vp, ci, sz, u64p, u64p]
     L.tsx_hip_load_host.argtypes = [vp, ci, sz, u64p]
+    L.tsx_hip_combine.argtypes = [vp, vp, vp, ctypes.POINTER(CombineRule), ctypes.POINTER(CombineStats)]
     L.tsx_hip_group_histogram_host.argtypes = [vp, u64p, sz]
     L.tsx_hip_group_write_counts_host.argtypes = [vp, ci, u64, u64, sz, u64p, u64p]
     L.tsx_hip_query_reads_device.argtypes = [vp, vp, sz, u64, u64, vp, sz, ctypes.POINTER(sz), vp]
@@ -297,6 +326,8 @@ class TSXHashMapHIP:
         self.layout = Layout()
         _check(self._lib.tsx_hip_get_layout(self._h, ctypes.byref(self.layout)))
         self.k, self.l, self.wk, self.device = iK, iL, self.layout.key_limbs, device
+        self.hash_seed = hash_seed
+        self.combine_stats = None
         self._lines = 4
         if canonical:
             self.set_canonical(True)
@@ -474,6 +505,48 @@ class TSXHashMapHIP:
             m.close()
             raise
         return m
+
+    def _combine(self, other, rule, out):
+        st = CombineStats()
+        rc = self._lib.tsx_hip_combine(out.handle if out is not None else None, self.handle, other.handle,
+                                       ctypes.byref(rule), ctypes.byref(st))
+        if rc == EINVAL:
+            raise TSXException(rc, self._lib.tsx_hip_last_error().decode() or self._lib.tsx_hip_strerror(rc).decode())
+        _check(rc)
+        return st.as_dict()
+
+    def combine(self, other, op="intersect", counts="min", a_range=(1, None), b_range=(1, None), out=None, iL=None,
+                iStorageBits=None, hash_seed=None):
+        """Set operation on two tables (tsx_hip_combine): self is A, `other` is B.  op: "intersect", "union",
+        "subtract" (A's k-mers that B lacks) or "diff" (count differences a - b > 0); counts: "min", "max", "sum",
+        "left", "right" where a k-mer is in both; a_range / b_range: (lower, upper) of the counts that take part.
+        Returns the result table with .combine_stats set: `out` (an empty map) when given, else a new map created like
+        self -- same l, storage bits and seed unless iL / iStorageBits / hash_seed say otherwise."""
+        rule = combine_rule(op, counts, a_range, b_range)
+        made = out is None
+        if made:
+            same = iL in (None, self.l) and iStorageBits in (None, self.layout.count_bits)
+            acgt, minq = self.base_rule
+            out = TSXHashMapHIP(self.l if iL is None else iL,
+                                self.layout.count_bits if iStorageBits is None else iStorageBits, self.k,
+                                hash_seed=self.hash_seed if hash_seed is None else hash_seed,
+                                overflow_l=self.layout.overflow_l if same else 0, device=self.device,
+                                canonical=self.canonical, acgt_only=acgt, min_qual_char=minq)
+        try:
+            out.combine_stats = self._combine(other, rule, out)
+        except Exception:
+            if made:
+                out.close()
+            raise
+        return out
+
+    def compare(self, other, a_range=(1, None), b_range=(1, None)):
+        """How two tables overlap (tsx_hip_combine without an output table): the combine stats of an intersection
+        -- a_in_range, b_in_range, both, a_sum_both, b_sum_both, ... -- plus `jaccard` = both / (a + b - both)."""
+        st = self._combine(other, combine_rule("intersect", "min", a_range, b_range), None)
+        union = st["a_in_range"] + st["b_in_range"] - st["both"]
+        st["jaccard"] = st["both"] / union if union else 0.0
+        return st
 
     def queryReads(self, text, lower=1, upper=None, chunk_bytes=0):
         """Per-record k-mer stats of a FASTQ / FASTA text against the table (tsx_hip_query_reads_host): a numpy

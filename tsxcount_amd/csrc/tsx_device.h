@@ -365,8 +365,11 @@ __device__ inline bool insert_key(const TableParams &p, const uint64_t (&h)[WK],
 // launch after every insert kernel has finished.
 // pos_out (optional): the slot the k-mer was found in, ~0 when it is not in the table
 // (KmerCountDebug::iFirstPos of getKmerCountDebug, TSXHashMap.h:477-545).
+// sec = false: the caller knows that nothing ever carried in this table (stats[ST_CARRY] == 0) and spares the probe
+// of the secondary array.
 template <int WK>
-__device__ inline uint64_t lookup_key(const TableParams &p, const uint64_t (&h)[WK], uint64_t *pos_out = nullptr) {
+__device__ inline uint64_t lookup_key(const TableParams &p, const uint64_t (&h)[WK], uint64_t *pos_out = nullptr,
+                                      bool sec = true) {
     if (pos_out) *pos_out = ~0ULL;
     if (p.lg != p.l && owner_shard<WK>(p, h) != p.shard) return 0;  // lives on another GPU
     uint64_t pos0, e0, hi[4];
@@ -382,7 +385,7 @@ __device__ inline uint64_t lookup_key(const TableParams &p, const uint64_t (&h)[
         for (int t = 1; t < W; ++t) same &= (e[t] == hi[t - 1]);
         if (!same) continue;
         if (pos_out) *pos_out = pos;
-        return (v >> p.cshift) + (sec_get(p, pos) << p.C);
+        return (v >> p.cshift) + (sec ? sec_get(p, pos) << p.C : 0ULL);
     }
     return 0;
 }

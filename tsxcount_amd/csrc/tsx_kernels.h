@@ -1158,11 +1158,10 @@ __global__ __launch_bounds__(NT) void occupied_kernel(TableParams p) {
     }
 }
 
-// Rebuild the k-mer whose slot words e[0..W) sit in slot `pos` (TSXHashMap::getAllKmers,
-// TSXHashMap.h:660-722): hashed key = func bits | (pos - i(i+1)/2 mod 2^l),
-// then the inverse mapping.  e need not be in the table (the database loader, tsx_db.h).
+// The hashed key whose slot words e[0..W) sit in slot `pos`: func bits | (pos - i(i+1)/2 mod 2^l).  Shifts only -- what
+// the aligned table join (tsx_combine.h) works on.  e need not be in the table (the database loader, tsx_db.h).
 template <int WK>
-__device__ __forceinline__ void words_to_kmer(const TableParams &p, uint64_t pos, const uint64_t *e, uint64_t (&x)[WK]) {
+__device__ __forceinline__ void words_to_key(const TableParams &p, uint64_t pos, const uint64_t *e, uint64_t (&h)[WK]) {
     const uint64_t v = e[0];
     const uint32_t i = (uint32_t)(v & ((1ULL << p.R) - 1ULL));
     const uint64_t pos0 = (pos & ~p.seg_mask) | ((pos - (((uint64_t)i * (i + 1)) >> 1)) & p.seg_mask);
@@ -1175,7 +1174,6 @@ __device__ __forceinline__ void words_to_kmer(const TableParams &p, uint64_t pos
         fr[t] |= hv >> (64 - p.K0);
     }
     // func = fr >> R ; h = (func << l) | pos0
-    uint64_t h[WK];
     uint64_t func[6];
 #pragma unroll
     for (int t = 0; t < 5; ++t) func[t] = (fr[t] >> p.R) | (fr[t + 1] << (64 - p.R));
@@ -1188,6 +1186,14 @@ __device__ __forceinline__ void words_to_kmer(const TableParams &p, uint64_t pos
     }
     h[0] |= pos0 | ((uint64_t)p.shard << p.l);
     h[WK - 1] &= p.top_mask;
+}
+
+// Rebuild the k-mer of those slot words (TSXHashMap::getAllKmers, TSXHashMap.h:660-722): the hashed key, then the
+// inverse mapping.
+template <int WK>
+__device__ __forceinline__ void words_to_kmer(const TableParams &p, uint64_t pos, const uint64_t *e, uint64_t (&x)[WK]) {
+    uint64_t h[WK];
+    words_to_key<WK>(p, pos, e, h);
     hash_apply<WK>(p, p.ilut, h, x);
 }
 

@@ -10,6 +10,7 @@
 #include "tsx_query.h"
 #include "tsx_baserule.h"
 #include "tsx_db.h"
+#include "tsx_combine.h"
 
 #include <mutex>
 #include <hip/hip_runtime.h>
@@ -3402,6 +3403,179 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
     if (d_carry) (void)hipFree(d_carry);
     if (d_ilut) (void)hipFree(d_ilut);
     if (entries_out) *entries_out = entries;
+    return rc;
+}
+
+// ---- table set operations (tsx_combine.h) ------------------------------------------------------------------------
+static const size_t COMBINE_CHUNK_DEFAULT = (size_t)256 << 20;   // bytes of one staging chunk of (k-mer, count)
+
+static int combine_fail(const char *why) { g_last_error = why; return TSX_HIP_EINVAL; }
+
+// l, slot layout, segment bits and seed agree: a hashed key has the same home slot and the same slot words in both.
+static bool combine_aligned(const tsx_hip_map *x, const tsx_hip_map *y) {
+    return x->p.l == y->p.l && x->p.W == y->p.W && x->p.F == y->p.F && x->p.R == y->p.R && x->p.C == y->p.C &&
+           x->p.S == y->p.S && x->seed == y->seed;
+}
+
+// Staging of the paths that go through k-mers: two chunks, so that add_kmers_kernel inserts one (on OUT's stream)
+// while the sweep fills the other (on A's).
+struct CombineStage {
+    uint64_t *d_kmers[2] = {nullptr, nullptr}, *d_counts[2] = {nullptr, nullptr};
+    unsigned long long *d_n = nullptr, *h_n = nullptr;   // entries staged per chunk
+    hipEvent_t swept[2] = {nullptr, nullptr}, inserted[2] = {nullptr, nullptr};
+    bool waiting[2] = {false, false}, reuse[2] = {false, false};
+    void release() {
+        for (int b = 0; b < 2; ++b) {
+            if (d_kmers[b]) (void)hipFree(d_kmers[b]);
+            if (d_counts[b]) (void)hipFree(d_counts[b]);
+            if (swept[b]) (void)hipEventDestroy(swept[b]);
+            if (inserted[b]) (void)hipEventDestroy(inserted[b]);
+        }
+        if (d_n) (void)hipFree(d_n);
+        if (h_n) (void)hipHostFree(h_n);
+    }
+};
+
+extern "C" int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b, const tsx_hip_combine_rule *rule,
+                               tsx_hip_combine_stats *stats_out) {
+    if (stats_out) memset(stats_out, 0, sizeof *stats_out);
+    if (!a || !b || !rule) return combine_fail("combine: a, b and the rule are needed");
+    if (rule->op < TSX_HIP_OP_INTERSECT || rule->op > TSX_HIP_OP_DIFF) return combine_fail("combine: unknown op");
+    if (rule->count_mode < TSX_HIP_CNT_MIN || rule->count_mode > TSX_HIP_CNT_RIGHT) return combine_fail("combine: unknown count mode");
+    const uint64_t a_lo = std::max<uint64_t>(1, rule->a_lower), b_lo = std::max<uint64_t>(1, rule->b_lower);
+    if (a_lo > rule->a_upper || b_lo > rule->b_upper) return combine_fail("combine: lower > upper");
+    if (out && (out == a || out == b)) return combine_fail("combine: out is one of the inputs");
+    tsx_hip_map *maps[3] = {a, b, out};
+    for (tsx_hip_map *m : maps) {
+        if (!m) continue;
+        if (m->p.lg != m->p.l) return combine_fail("combine: a shard of a multi-GPU table");
+        if (m->device != a->device) return combine_fail("combine: the tables are on different devices");
+        if (m->p.k != a->p.k) return combine_fail("combine: the tables differ in k");
+        if (m->canon != a->canon) return combine_fail("combine: the tables differ in canonical mode");
+        if (m->p.acgt_only != a->p.acgt_only || m->minq != a->minq) return combine_fail("combine: the tables differ in base rule");
+    }
+    if (out && out->used) return combine_fail("combine: out is not empty");
+    int path = 0;
+    if (const char *e = getenv("TSX_HIP_COMBINE_PATH")) path = atoi(e);
+    const bool ab_aligned = combine_aligned(a, b);
+    if (path < 0 || path > 2) return combine_fail("combine: TSX_HIP_COMBINE_PATH is 0, 1 or 2");
+    if (path == 2 && !ab_aligned) return combine_fail("combine: the aligned path needs A and B of one l, slot layout, segment bits and seed");
+    const bool aligned = path == 2 || (path == 0 && ab_aligned);
+    const bool fused = aligned && out && combine_aligned(a, out);   // survivors go in by hashed key: no staging
+    size_t chunk_bytes = COMBINE_CHUNK_DEFAULT;
+    if (const char *e = getenv("TSX_HIP_COMBINE_CHUNK_BYTES")) { const long long v = atoll(e); if (v > 0) chunk_bytes = (size_t)v; }
+    const int WK = a->p.wk;
+    const uint64_t max_slots = std::max(a->lay.slots, b->lay.slots);
+    const uint64_t chunk_slots = std::min<uint64_t>(max_slots, std::max<uint64_t>(64, (chunk_bytes / ((size_t)(WK + 1) * 8)) & ~(uint64_t)63));
+
+    HIP_TRY(hipSetDevice(a->device));
+    // behind everything queued on the three maps; lazily cleared tables are zeroed before anyone reads them
+    for (tsx_hip_map *m : maps) {
+        if (!m) continue;
+        join_foreign(m, true);
+        int rcz = ensure_zeroed(m, m->stream);
+        if (rcz != TSX_HIP_OK) return rcz;
+        HIP_TRY(hipStreamSynchronize(m->stream));
+    }
+    unsigned long long a_carry = 0, b_carry = 0;
+    HIP_TRY(hipMemcpy(&a_carry, a->p.stats + ST_CARRY, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&b_carry, b->p.stats + ST_CARRY, 8, hipMemcpyDeviceToHost));
+
+    hipStream_t sw = a->stream;                  // the sweeps
+    hipStream_t ins = out ? out->stream : sw;    // the inserts of staged chunks
+    CombineStage sg;
+    unsigned long long *d_res = nullptr;
+    unsigned long long h_res[CB_N] = {0};
+    int rc = TSX_HIP_OK;
+    const bool staging = out && !fused;
+    do {
+        if (hipMalloc((void **)&d_res, CB_N * 8) != hipSuccess) { rc = TSX_HIP_ENOMEM; break; }
+        if (hipMemsetAsync(d_res, 0, CB_N * 8, sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        if (staging) {
+            if (hipMalloc((void **)&sg.d_n, 2 * 8) != hipSuccess || hipHostMalloc((void **)&sg.h_n, 2 * 8) != hipSuccess) { rc = TSX_HIP_ENOMEM; break; }
+            for (int i = 0; i < 2 && rc == TSX_HIP_OK; ++i) {
+                if (hipMalloc((void **)&sg.d_kmers[i], (size_t)chunk_slots * WK * 8) != hipSuccess ||
+                    hipMalloc((void **)&sg.d_counts[i], (size_t)chunk_slots * 8) != hipSuccess) { g_last_error = "combine: staging"; rc = TSX_HIP_ENOMEM; }
+                else if (hipEventCreateWithFlags(&sg.swept[i], hipEventDisableTiming) != hipSuccess ||
+                         hipEventCreateWithFlags(&sg.inserted[i], hipEventDisableTiming) != hipSuccess) rc = TSX_HIP_EHIP;
+            }
+            if (rc != TSX_HIP_OK) break;
+        }
+        // the chunk in buffer i has been swept: insert it into OUT
+        auto insert_chunk = [&](int i) -> int {
+            sg.waiting[i] = false;
+            if (hipEventSynchronize(sg.swept[i]) != hipSuccess) return TSX_HIP_EHIP;
+            const unsigned long long n = sg.h_n[i];
+            if (n == 0) return TSX_HIP_OK;
+            const int r = tsx_hip_add_kmers_device(out, sg.d_kmers[i], sg.d_counts[i], (size_t)n, nullptr);
+            if (r != TSX_HIP_OK) return r;
+            if (hipEventRecord(sg.inserted[i], ins) != hipSuccess) return TSX_HIP_EHIP;
+            sg.reuse[i] = true;
+            return TSX_HIP_OK;
+        };
+        uint64_t chunk = 0;
+        for (int side = 0; side < 2 && rc == TSX_HIP_OK; ++side) {
+            tsx_hip_map *src = side == 0 ? a : b, *oth = side == 0 ? b : a;
+            CombineArgs ca;
+            ca.op = rule->op; ca.mode = rule->count_mode; ca.side = side;
+            ca.src_sec = (side == 0 ? a_carry : b_carry) != 0; ca.oth_sec = (side == 0 ? b_carry : a_carry) != 0;
+            ca.s_lo = side == 0 ? a_lo : b_lo; ca.s_hi = side == 0 ? rule->a_upper : rule->b_upper;
+            ca.o_lo = side == 0 ? b_lo : a_lo; ca.o_hi = side == 0 ? rule->b_upper : rule->a_upper;
+            // B's sweep writes only for UNION; for the other ops it counts b_in_range
+            const bool writes = out && (side == 0 || rule->op == TSX_HIP_OP_UNION);
+            ca.emit = !writes ? 0 : fused ? 2 : 1;
+            if (side == 1 && !writes && !stats_out) break;
+            const uint64_t slots = src->lay.slots;
+            const uint64_t span = ca.emit == 1 ? chunk_slots : slots;
+            if (ca.emit == 2) out->used = true;   // (the sweep itself inserts; OUT's stream is idle, see above)
+            for (uint64_t lo = 0; lo < slots && rc == TSX_HIP_OK; lo += span) {
+                const uint64_t hi = std::min(slots, lo + span);
+                const int i = (int)(chunk & 1);
+                uint64_t *dk = nullptr, *dc = nullptr;
+                unsigned long long *dn = nullptr;
+                if (ca.emit == 1) {
+                    if (sg.waiting[i] && (rc = insert_chunk(i)) != TSX_HIP_OK) break;
+                    if (sg.reuse[i] && hipStreamWaitEvent(sw, sg.inserted[i], 0) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+                    dk = sg.d_kmers[i]; dc = sg.d_counts[i]; dn = sg.d_n + i;
+                    if (hipMemsetAsync(dn, 0, 8, sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+                }
+                const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((hi - lo + CB_TILE - 1) / CB_TILE, (uint64_t)a->cus * 8));
+                const TableParams &po = out ? out->p : src->p;
+                if (aligned) {
+                    DISPATCH_WK(a, hipLaunchKernelGGL((combine_sweep_kernel<WKV, false, true>), dim3(grid), dim3(NT), 0, sw, src->p,
+                                                      oth->p, po, ca, lo, hi, dk, dc, (uint64_t)(hi - lo), dn, d_res));
+                } else {
+                    DISPATCH_CANON(a, DISPATCH_WK(a, hipLaunchKernelGGL((combine_sweep_kernel<WKV, CANV, false>), dim3(grid), dim3(NT),
+                                                                        0, sw, src->p, oth->p, po, ca, lo, hi, dk, dc,
+                                                                        (uint64_t)(hi - lo), dn, d_res)));
+                }
+                if (hipGetLastError() != hipSuccess) { g_last_error = "combine_sweep_kernel launch"; rc = TSX_HIP_EHIP; break; }
+                if (ca.emit == 1) {
+                    if (hipMemcpyAsync(sg.h_n + i, dn, 8, hipMemcpyDeviceToHost, sw) != hipSuccess ||
+                        hipEventRecord(sg.swept[i], sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+                    sg.waiting[i] = true;
+                    ++chunk;
+                    const int prev = (int)(chunk & 1);   // the chunk before this one: insert it while this one is swept
+                    if (sg.waiting[prev]) rc = insert_chunk(prev);
+                }
+            }
+        }
+        for (int i = 0; i < 2 && rc == TSX_HIP_OK; ++i)
+            if (sg.waiting[(chunk + i) & 1]) rc = insert_chunk((int)((chunk + i) & 1));
+        if (rc != TSX_HIP_OK) break;
+        if (hipMemcpyAsync(h_res, d_res, CB_N * 8, hipMemcpyDeviceToHost, sw) != hipSuccess ||
+            hipStreamSynchronize(sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        if (out) rc = tsx_hip_sync(out);
+    } while (0);
+    (void)hipStreamSynchronize(sw);
+    if (out) (void)hipStreamSynchronize(ins);
+    sg.release();
+    if (d_res) (void)hipFree(d_res);
+    if (stats_out) {
+        stats_out->a_in_range = h_res[CB_A_IN]; stats_out->b_in_range = h_res[CB_B_IN]; stats_out->both = h_res[CB_BOTH];
+        stats_out->a_sum_both = h_res[CB_A_SUM]; stats_out->b_sum_both = h_res[CB_B_SUM];
+        stats_out->out_entries = h_res[CB_OUT_N]; stats_out->out_count_sum = h_res[CB_OUT_SUM];
+    }
     return rc;
 }
 

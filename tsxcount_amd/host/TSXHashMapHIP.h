@@ -201,6 +201,21 @@ public:
         return tsx_filter_reads(m_pMap, pText, iBytes, oRule, sPath, iChunkBytes, check);
     }
 
+    // set operation on two tables (tsx_hip_combine): this is A, oOther is B, the result goes into the empty table oOut
+    tsx_hip_combine_stats combine(TSXHashMapHIP &oOther, TSXHashMapHIP &oOut, const tsx_hip_combine_rule &oRule) {
+        return combineInto(oOut.m_pMap, oOther, oRule);
+    }
+    // how two tables overlap: the stats of an intersection, nothing is written (jaccard() turns them into the index)
+    tsx_hip_combine_stats compare(TSXHashMapHIP &oOther, uint64_t iALower = 1, uint64_t iAUpper = UINT64_MAX,
+                                  uint64_t iBLower = 1, uint64_t iBUpper = UINT64_MAX) {
+        const tsx_hip_combine_rule oRule = {TSX_HIP_OP_INTERSECT, TSX_HIP_CNT_MIN, iALower, iAUpper, iBLower, iBUpper};
+        return combineInto(nullptr, oOther, oRule);
+    }
+    static double jaccard(const tsx_hip_combine_stats &s) {
+        const uint64_t iUnion = s.a_in_range + s.b_in_range - s.both;
+        return iUnion ? (double)s.both / (double)iUnion : 0.0;
+    }
+
     // FASTXreader<FASTAEntry> (FastXReader.h:97-116) reads two lines per record, FASTQEntry (:62-95) four
     void setRecordLines(int iLines) { check(tsx_hip_set_record_lines(m_pMap, iLines)); }
     // canonical counting: a k-mer and its reverse complement share one counter (empty table only)
@@ -238,6 +253,13 @@ public:
     tsx_hip_map *handle() { return m_pMap; }
 
 private:
+    tsx_hip_combine_stats combineInto(tsx_hip_map *pOut, TSXHashMapHIP &oOther, const tsx_hip_combine_rule &oRule) {
+        tsx_hip_combine_stats s;
+        const int rc = tsx_hip_combine(pOut, m_pMap, oOther.m_pMap, &oRule, &s);
+        if (rc == TSX_HIP_EINVAL) throw TSXException(tsx_hip_last_error(), rc);   // (the refusal says which argument)
+        check(rc);
+        return s;
+    }
     static void check(int rc) {
         if (rc == TSX_HIP_OK) return;
         std::string msg = tsx_hip_strerror(rc);

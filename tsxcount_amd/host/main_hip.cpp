@@ -48,6 +48,12 @@ struct arguments {
     // k-mer databases: --save=DB after the count and the check, --load=DB[,DB2,...] before the count (summed)
     std::string save;
     std::vector<std::string> load;
+    // table set operations: --with=DB[,DB2,...] is the second table (summed as --load sums), --op joins the counted /
+    // loaded table with it and the result takes its place for everything after the check; --compare prints the overlap
+    std::vector<std::string> with;
+    std::string op, op_count = "min";
+    uint64_t a_lower = 1, a_upper = UINT64_MAX, b_lower = 1, b_upper = UINT64_MAX;
+    bool compare = false;
     bool given_k = false, given_l = false, given_s = false, given_seed = false;
 };
 
@@ -66,6 +72,8 @@ static int usage() {
                  "                [--output=FILE [--lower=N] [--upper=N]] [--histo=FILE [--histo-max=H]]\n"
                  "                [--filter=OUT] [--read-stats=FILE] [--filter-input=FILE] [--filter-lower=N] [--filter-upper=N]\n"
                  "                [--filter-min=M] [--filter-fraction=F] [--filter-invert] [--save=DB] [--load=DB[,DB2,...]]\n"
+                 "                [--with=DB[,DB2,...] [--op=intersect|union|subtract|diff] [--op-count=min|max|sum|left|right]\n"
+                 "                 [--a-lower=N] [--a-upper=N] [--b-lower=N] [--b-upper=N] [--compare]]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
                  "--canonical counts a k-mer and its reverse complement as one (the check then expects f(x) + f(rc x)).\n"
                  "--acgt-only skips every k-mer with a byte outside ACGTacgt (an N, say); --min-qual-char=C every k-mer with a\n"
@@ -83,7 +91,15 @@ static int usage() {
                  "k-mer databases first (several are summed); the first sets k, l, s and the seed unless they are given, a\n"
                  "different l or s re-inserts every k-mer. --input is then optional: its reads are counted on top of the\n"
                  "loaded counts. --load refuses --check; --filter and --read-stats without --input need --filter-input.\n"
-                 "--canonical, --acgt-only and --min-qual-char must match the databases. One GPU only."
+                 "--canonical, --acgt-only and --min-qual-char must match the databases. One GPU only.\n"
+                 "--with names a second table B (databases, summed); A is the table as --load and --input leave it. --op joins\n"
+                 "them after the count and the check: intersect (k-mers of both), union (of either), subtract (A's k-mers that\n"
+                 "B lacks, with A's count), diff (count differences a - b > 0). --op-count picks the count of a k-mer that is\n"
+                 "in both: min (default), max, sum, left (A's), right (B's). --a-lower/--a-upper and --b-lower/--b-upper keep\n"
+                 "only the k-mers of A / B counted that often. The result takes the table's place for --output, --histo,\n"
+                 "--save, --filter and --read-stats. --compare prints compare<TAB>a<TAB>b<TAB>both<TAB>jaccard (distinct k-mers\n"
+                 "of A, of B, of both, Jaccard index) and the summed counts of the shared k-mers. B must match A's k,\n"
+                 "--canonical, --acgt-only and --min-qual-char. One GPU only."
               << std::endl;
     return 1;
 }
@@ -246,9 +262,19 @@ static void save_database(TSXHashMapHIP &oMap, const arguments &a) {
 }
 static void save_database(TSXHashMapHIPGroup &, const arguments &) {}
 
+// --op / --op-count by name: the TSX_HIP_OP_* / TSX_HIP_CNT_* value, -1 for none given, -2 / -1 for an unknown one
+static int op_index(const std::string &s) {
+    return s.empty() ? -1 : s == "intersect" ? TSX_HIP_OP_INTERSECT : s == "union" ? TSX_HIP_OP_UNION
+         : s == "subtract" ? TSX_HIP_OP_SUBTRACT : s == "diff" ? TSX_HIP_OP_DIFF : -2;
+}
+static int count_index(const std::string &s) {
+    return s == "min" ? TSX_HIP_CNT_MIN : s == "max" ? TSX_HIP_CNT_MAX : s == "sum" ? TSX_HIP_CNT_SUM
+         : s == "left" ? TSX_HIP_CNT_LEFT : s == "right" ? TSX_HIP_CNT_RIGHT : -1;
+}
+
 // "Added a total of ..." and the --check of main.cpp:224-396, for one table or a group of them
 template <typename Map>
-static int report_and_check(Map &oMap, const arguments &a, double dt) {
+static int report_and_check(Map &oMap, const arguments &a, double dt, bool outputs = true) {
     tsx_hip_stats st = oMap.stats();
     std::cout << "Added a total of " << st.distinct << " different kmers" << std::endl;
     std::cerr << "add calls: " << st.kmers_added << std::endl;
@@ -321,8 +347,10 @@ static int report_and_check(Map &oMap, const arguments &a, double dt) {
         std::cout << "tsxCount kmer count: " << st.distinct << std::endl;
         if (totalerrors || iRefCount != st.distinct) rc = 5;
     }
-    save_database(oMap, a);
-    write_outputs(oMap, a);
+    if (outputs) {   // (after a set operation its result is saved and written instead)
+        save_database(oMap, a);
+        write_outputs(oMap, a);
+    }
     oMap.print_stats();
     return rc;
 }
@@ -379,16 +407,24 @@ int main(int argc, char *argv[]) {
         else if (opt(argv[i], "checkabort", v)) a.checkabort = true;
         else if (opt(argv[i], "seed", v)) { a.seed = strtoull(v.c_str(), nullptr, 10); a.given_seed = true; }
         else if (opt(argv[i], "save", v)) { a.save = v; if (v.empty()) return usage(); }
-        else if (opt(argv[i], "load", v)) {
+        else if (opt(argv[i], "load", v) || opt(argv[i], "with", v)) {
+            std::vector<std::string> &list = std::string(argv[i]).compare(0, 6, "--load") == 0 ? a.load : a.with;
             for (size_t at = 0; at <= v.size();) {
                 const size_t c = v.find(',', at);
                 const std::string one = v.substr(at, c == std::string::npos ? std::string::npos : c - at);
                 if (one.empty()) return usage();
-                a.load.push_back(one);
+                list.push_back(one);
                 if (c == std::string::npos) break;
                 at = c + 1;
             }
         }
+        else if (opt(argv[i], "op", v)) { a.op = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "op-count", v)) a.op_count = v;
+        else if (opt(argv[i], "a-lower", v)) a.a_lower = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "a-upper", v)) a.a_upper = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "b-lower", v)) a.b_lower = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "b-upper", v)) a.b_upper = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "compare", v)) a.compare = true;
         else if (opt(argv[i], "format", v)) a.format = v;
         else if (opt(argv[i], "device", v)) a.device = atoi(v.c_str());
         else if (opt(argv[i], "gpus", v)) { a.gpus = atoi(v.c_str()); a.group = true; }
@@ -451,6 +487,45 @@ int main(int argc, char *argv[]) {
             return 2;
         }
     }
+    // table set operations: what the options and the headers of --with already tell, before the GPU is touched
+    if (op_index(a.op) == -2 || count_index(a.op_count) < 0) {
+        std::cerr << "--op is intersect, union, subtract or diff; --op-count is min, max, sum, left or right" << std::endl;
+        return usage();
+    }
+    if ((!a.op.empty() || a.compare) && a.with.empty()) {
+        std::cerr << "--op and --compare need a second table: --with=DB[,DB2,...]" << std::endl;
+        return usage();
+    }
+    if (!a.with.empty() && a.op.empty() && !a.compare) {
+        std::cerr << "--with needs --op or --compare" << std::endl;
+        return usage();
+    }
+    if (!a.with.empty() && a.gpus > 1) {
+        std::cerr << "--with works on one GPU only: a --gpus " << a.gpus << " run keeps one table per GPU" << std::endl;
+        return usage();
+    }
+    if (std::max<uint64_t>(1, a.a_lower) > a.a_upper || std::max<uint64_t>(1, a.b_lower) > a.b_upper) return usage();
+    tsx_hip_db_info with_first;
+    memset(&with_first, 0, sizeof with_first);
+    for (size_t i = 0; i < a.with.size(); ++i) {
+        tsx_hip_db_info d;
+        try {
+            d = TSXHashMapHIP::databaseInfo(a.with[i]);
+        } catch (const TSXException &e) {
+            std::cerr << "--with=" << a.with[i] << ": " << e.what() << std::endl;
+            return 3;
+        }
+        if (i == 0) with_first = d;
+        if (d.k != a.k || (d.canonical != 0) != a.canonical || (d.acgt_only != 0) != a.acgt_only || d.min_qual_char != a.min_qual_char) {
+            std::cerr << "--with=" << a.with[i] << " was counted with k=" << d.k << (d.canonical ? " --canonical" : "")
+                      << (d.acgt_only ? " --acgt-only" : "");
+            if (d.min_qual_char) std::cerr << " --min-qual-char=" << (char)d.min_qual_char;
+            std::cerr << "; the first table has k=" << a.k << (a.canonical ? " --canonical" : "") << (a.acgt_only ? " --acgt-only" : "");
+            if (a.min_qual_char) std::cerr << " --min-qual-char=" << (char)a.min_qual_char;
+            std::cerr << ": both tables of a set operation need the same" << std::endl;
+            return 2;
+        }
+    }
 
     std::cout << "Running with parameters " << std::endl;
     std::cerr << "K=" << a.k << std::endl;
@@ -462,6 +537,8 @@ int main(int argc, char *argv[]) {
     if (a.min_qual_char) std::cerr << "MinQualChar=" << (char)a.min_qual_char << std::endl;
     std::cerr << "Input=" << a.input_path << std::endl;
     for (const std::string &db : a.load) std::cerr << "Load=" << db << std::endl;
+    for (const std::string &db : a.with) std::cerr << "With=" << db << std::endl;
+    if (!a.op.empty()) std::cerr << "Op=" << a.op << " OpCount=" << a.op_count << std::endl;
     if (!a.save.empty()) std::cerr << "Save=" << a.save << std::endl;
     std::cerr << "Threads=" << a.threads << std::endl;
     std::cerr << "Mode=" << a.mode << std::endl;
@@ -506,7 +583,7 @@ int main(int argc, char *argv[]) {
         std::cerr << "--filter and --read-stats without --input need --filter-input=FILE" << std::endl;
         return usage();
     }
-    if (!a.save.empty() || !a.load.empty()) a.group = false;   // --gpus=1: the one table of this process
+    if (!a.save.empty() || !a.load.empty() || !a.with.empty()) a.group = false;   // --gpus=1: the one table of this process
     try {
         if (a.group) return run_group(a);
         std::cerr << "Creating TSXHashMap HIP" << std::endl;
@@ -548,9 +625,46 @@ int main(int argc, char *argv[]) {
         }
         double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (map) munmap(map, n);
-        const int rc = report_and_check(oMap, a, dt);
+        if (a.with.empty()) {
+            const int rc = report_and_check(oMap, a, dt);
+            if (!wants_queries(a)) return rc;
+            const int rq = run_read_queries(oMap.handle(), a);
+            return rc ? rc : rq;
+        }
+        // --with: B is built like its first database, OUT like A; the result takes A's place from here on
+        const int rc = report_and_check(oMap, a, dt, a.op.empty());
+        std::cerr << "Creating the second table" << std::endl;
+        TSXHashMapHIP oWith((uint8_t)with_first.l, (uint32_t)with_first.count_bits, (uint16_t)a.k, (uint8_t)a.threads,
+                            with_first.hash_seed, a.device, with_first.overflow_l);
+        if (a.canonical) oWith.setCanonical(true);
+        if (a.acgt_only || a.min_qual_char) oWith.setBaseRule(a.acgt_only, a.min_qual_char);
+        for (const std::string &db : a.with) {
+            const uint64_t iEntries = oWith.loadDatabase(db);
+            std::cerr << "Loaded " << iEntries << " kmers from " << db << std::endl;
+        }
+        if (a.compare) {
+            const tsx_hip_combine_stats s = oMap.compare(oWith, a.a_lower, a.a_upper, a.b_lower, a.b_upper);
+            std::cout << "compare\t" << s.a_in_range << '\t' << s.b_in_range << '\t' << s.both << '\t'
+                      << TSXHashMapHIP::jaccard(s) << std::endl;
+            std::cout << "compare-sums\t" << s.a_sum_both << '\t' << s.b_sum_both << std::endl;
+        }
+        if (a.op.empty()) {
+            if (!wants_queries(a)) return rc;
+            const int rq = run_read_queries(oMap.handle(), a);
+            return rc ? rc : rq;
+        }
+        std::cerr << "Creating the result table" << std::endl;
+        TSXHashMapHIP oOut((uint8_t)a.l, (uint32_t)a.storagebits, (uint16_t)a.k, (uint8_t)a.threads, a.seed, a.device, overflow_l);
+        if (a.canonical) oOut.setCanonical(true);
+        if (a.acgt_only || a.min_qual_char) oOut.setBaseRule(a.acgt_only, a.min_qual_char);
+        const tsx_hip_combine_rule oRule = {op_index(a.op), count_index(a.op_count), a.a_lower, a.a_upper, a.b_lower, a.b_upper};
+        const tsx_hip_combine_stats s = oMap.combine(oWith, oOut, oRule);
+        std::cout << a.op << ": " << s.out_entries << " different kmers, count sum " << s.out_count_sum << " (first table "
+                  << s.a_in_range << ", second " << s.b_in_range << ", both " << s.both << " in range)" << std::endl;
+        save_database(oOut, a);
+        write_outputs(oOut, a);
         if (!wants_queries(a)) return rc;
-        const int rq = run_read_queries(oMap.handle(), a);
+        const int rq = run_read_queries(oOut.handle(), a);
         return rc ? rc : rq;
     } catch (const TSXException &e) {
         std::cerr << "TSXException: " << e.what() << std::endl;
