@@ -189,9 +189,37 @@ int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, size_t n);
  * Lines per record of the texts handed to the count_fastq / shard_scan entry points: 4 = FASTQ
  * (FASTQEntry, FastXReader.h:62-95; the default), 2 = FASTA exactly as FASTXreader<FASTAEntry> reads it
  * (FastXReader.h:97-116: header line, ONE sequence line; sequences wrapped over several lines are not
- * joined there either).  Empty lines are dropped in both.
+ * joined there either).  Empty lines are dropped in both.  Wrapped FASTA has entry points of its own, which join the
+ * lines and do not look at this setting: tsx_hip_count_fasta_host / _device / _bgzf_host below.
  */
 int tsx_hip_set_record_lines(tsx_hip_map *m, int lines);
+
+/*
+ * Wrapped (multi-line) FASTA (csrc/tsx_fasta.h; no reference counterpart -- jellyfish and KMC join the lines too).  The
+ * text is split at '\n' and empty lines are dropped; a line whose first byte is '>' is a header; the sequence of a record
+ * is every other line up to the next header (or the end of the text), joined in order; lines in front of the first
+ * header are a record of their own; a record without a sequence byte vanishes; a '>' elsewhere in a line and '\r' are
+ * ordinary bytes.  Every window of k bytes of a record's sequence is a k-mer (stand-in codes, canonical mode and
+ * acgt_only as everywhere): kmers_added grows by the sum of max(0, len - k + 1) over the records.  The lines are joined
+ * on the device, piece by piece, into the text's two-line form -- ">\n" + sequence + "\n" per record, header text
+ * dropped -- which the scan kernels then count; what a k-mer across two pieces needs travels in a device-resident carry.
+ *   count_fasta_host       text in host memory, staged in pieces of TSX_HIP_PIECE_BYTES cut anywhere.
+ *   count_fasta_device     a resident text (16-byte aligned) in windows of TSX_HIP_DEV_WINDOW (2 GiB at most); queued on
+ *                          `stream` (NULL = the map's own), returns without waiting.
+ *   count_fasta_bgzf_host  a BGZF image, batch after batch (TSX_HIP_BGZF_BATCH): inflated on the device, joined, counted.
+ *                          TSX_HIP_EINVAL when the buffer is not BGZF.
+ * All three count two-line records for the duration of the call whatever tsx_hip_set_record_lines says, and leave that
+ * setting as they found it; a table built slab by slab keeps the whole two-line text resident, as
+ * tsx_hip_count_fastq_host does.  TSX_HIP_EINVAL (tsx_hip_last_error says why): a map created with shard_bits > 0, a
+ * base rule with min_qual_char (no quality line).
+ *   unwrap_fasta_host      the two-line form of a whole text (one piece, whatever the window) into host memory: tests and
+ *                          tools.  *out_bytes = its size, at most n + 2.  TSX_HIP_ERANGE for n >= 2^32 - 64 (*out_bytes
+ *                          = n + 2 then) and when out_cap is too small (*out_bytes = the size needed).
+ */
+int tsx_hip_count_fasta_host(tsx_hip_map *m, const char *text, size_t n);
+int tsx_hip_count_fasta_device(tsx_hip_map *m, const void *dev_text, size_t n, void *stream);
+int tsx_hip_count_fasta_bgzf_host(tsx_hip_map *m, const void *gz, size_t n);
+int tsx_hip_unwrap_fasta_host(int device, const char *text, size_t n, void *out_host, size_t out_cap, size_t *out_bytes);
 
 /*
  * Measurement hooks (no reference counterpart): with timing enabled every

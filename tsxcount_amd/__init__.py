@@ -168,6 +168,10 @@ def lib():
     L.tsx_hip_sync.argtypes = [vp]
     L.tsx_hip_count_fastq_host.argtypes = [vp, ctypes.c_char_p, sz]
     L.tsx_hip_count_fastq_device.argtypes = [vp, vp, sz, vp]
+    L.tsx_hip_count_fasta_host.argtypes = [vp, ctypes.c_char_p, sz]
+    L.tsx_hip_count_fasta_device.argtypes = [vp, vp, sz, vp]
+    L.tsx_hip_count_fasta_bgzf_host.argtypes = [vp, vp, sz]
+    L.tsx_hip_unwrap_fasta_host.argtypes = [ci, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz)]
     L.tsx_hip_add_kmers_host.argtypes = [vp, u64p, u64p, sz]
     L.tsx_hip_add_kmers_device.argtypes = [vp, vp, vp, sz, vp]
     L.tsx_hip_get_counts_host.argtypes = [vp, u64p, sz, u64p]
@@ -631,6 +635,28 @@ class TSXHashMapHIP:
         _check(self._lib.tsx_hip_count_fastq_device(self._h, ctypes.c_void_p(dev_ptr), nbytes,
                                                     ctypes.c_void_p(stream) if stream else None))
 
+    def _check_fasta(self, rc):
+        if rc == EINVAL:   # a refusal: the library says which
+            raise TSXException(rc, self._lib.tsx_hip_last_error().decode() or self._lib.tsx_hip_strerror(rc).decode())
+        _check(rc)
+
+    def countFasta(self, data):
+        """Count a wrapped (multi-line) FASTA text held in host memory: the sequence lines of a record are joined on the
+        device (csrc/tsx_fasta.h), the k-mers are those of join_fasta(data) read as two-line records.  Works whatever
+        set_record_lines says and leaves it alone."""
+        b = bytes(data)
+        self._check_fasta(self._lib.tsx_hip_count_fasta_host(self.handle, b, len(b)))
+
+    def countFastaBgzf(self, gz):
+        """The same for the image of a blocked gzip (BGZF) file."""
+        b = bytes(gz)
+        self._check_fasta(self._lib.tsx_hip_count_fasta_bgzf_host(self.handle, b, len(b)))
+
+    def countFastaDevice(self, dev_ptr, nbytes, stream=None):
+        """The same for a text resident on the device (16-byte aligned); queued, call sync() before reading."""
+        self._check_fasta(self._lib.tsx_hip_count_fasta_device(self.handle, ctypes.c_void_p(dev_ptr), nbytes,
+                                                               ctypes.c_void_p(stream) if stream else None))
+
     def clear(self):
         _check(self._lib.tsx_hip_clear(self._h))
 
@@ -826,6 +852,38 @@ class TSXHashMapHIPGroup:
 
     def exchanged_entries(self):
         return int(self._lib.tsx_hip_group_exchanged_entries(self._h))
+
+
+def join_fasta(text):
+    """The canonical two-line form of a wrapped (multi-line) FASTA text, on the CPU: the statement of the record rules
+    that countFasta / unwrap_fasta follow.  The text is split at b"\\n" and empty lines are dropped; a line whose first
+    byte is b">" is a header; the sequence of a record is every other line up to the next header (or the end) joined in
+    order; lines in front of the first header are a record of their own; a record without a sequence byte vanishes; a
+    b">" elsewhere in a line and b"\\r" are ordinary bytes.  The result is b">\\n" + sequence + b"\\n" per record:
+    header text is dropped (nothing downstream of counting reads it)."""
+    out, seq = [], []
+    for line in bytes(text).split(b"\n"):
+        if not line:
+            continue
+        if line[:1] == b">":
+            if seq:
+                out.append(b">\n" + b"".join(seq) + b"\n")
+            seq = []
+        else:
+            seq.append(line)
+    if seq:
+        out.append(b">\n" + b"".join(seq) + b"\n")
+    return b"".join(out)
+
+
+def unwrap_fasta(text, device=0):
+    """join_fasta(text) computed on the GPU (tsx_hip_unwrap_fasta_host: the whole text as one piece)."""
+    b = bytes(text)
+    cap = len(b) + 2
+    out = ctypes.create_string_buffer(max(cap, 1))
+    got = ctypes.c_size_t(0)
+    _check(lib().tsx_hip_unwrap_fasta_host(device, b, len(b), out, cap, ctypes.byref(got)))
+    return out.raw[:got.value]
 
 
 def bgzf_index(gz):

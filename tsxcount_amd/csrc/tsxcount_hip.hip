@@ -11,6 +11,7 @@
 #include "tsx_baserule.h"
 #include "tsx_db.h"
 #include "tsx_combine.h"
+#include "tsx_fasta.h"
 
 #include <mutex>
 #include <hip/hip_runtime.h>
@@ -122,6 +123,10 @@ struct tsx_hip_map {
     // is remembered (`foreign`) and tsx_hip_clear / tsx_hip_sync order themselves behind what was queued there.
     uint8_t *d_slabdesc = nullptr;      // count_slabs: the descriptions of every text window, then one counter per window
     size_t slabdesc_bytes = 0;
+    // wrapped FASTA (tsx_fasta.h): the two-line text of one piece, the scan scratch, the carry between pieces
+    uint8_t *d_fa_out = nullptr; size_t fa_out_bytes = 0;
+    uint32_t *d_fa_ws = nullptr; size_t fa_ws_bytes = 0;
+    uint32_t *d_fa_carry = nullptr;
     hipEvent_t clear_ev = nullptr, join_ev = nullptr;
     bool clear_ev_set = false;
     hipStream_t foreign = nullptr;
@@ -589,6 +594,7 @@ extern "C" void tsx_hip_destroy(tsx_hip_map *m) {
     (void)hipFree(m->d_def_rec); (void)hipFree(m->d_def_cnt); (void)hipFree(m->d_def_n);
     (void)hipFree(m->d_tile); (void)hipFree(m->d_carry); (void)hipFree(m->d_seg);
     (void)hipFree(m->d_qmap); (void)hipFree(m->d_qrec);
+    (void)hipFree(m->d_fa_out); (void)hipFree(m->d_fa_ws); (void)hipFree(m->d_fa_carry);
     (void)hipFree(m->p.seg_dirty); (void)hipFree(m->d_buf[0]); (void)hipFree(m->d_buf[1]); (void)hipFree(m->d_cnt);
     for (int i = 0; i < 2; ++i) {
         if (m->h_stage[i]) (void)hipHostFree(m->h_stage[i]);
@@ -2564,6 +2570,208 @@ extern "C" int tsx_hip_count_fastq_host(tsx_hip_map *m, const char *text, size_t
         used[buf] = true;
     }
     return tsx_hip_sync(m);
+}
+
+// ---- wrapped FASTA: sequence lines joined on the device (tsx_fasta.h), then counted as two-line text ----------------
+static const size_t FA_PIECE_MAX = (size_t)1 << 31;   // output positions of a piece are 32 bits wide
+static const size_t FA_TAIL = 256;                    // newlines behind a piece's bound
+// Bytes the two-line text of a piece of n bytes can take: the text (+ 2), ">\n" + k - 1 carried bases; a multiple of 16.
+static inline size_t fa_bound(size_t n, int k) { return (n + (size_t)k + 16 + 15) & ~(size_t)15; }
+
+// Unwraps d_text[0, n) (16-byte aligned, 0 < n <= FA_PIECE_MAX) behind the carry in d_carry (FA_CARRY_BYTES, then
+// FA_INFO_WORDS info words) into d_out[0, out_end): the two-line text, then '\n' up to out_end.  Leaves the carry of the
+// next piece and the output's size (info word 0) on the device; does not wait.
+static int fasta_unwrap(const uint8_t *d_text, uint64_t n, uint32_t *d_carry, uint32_t kminus1, uint32_t *&d_ws, size_t &ws_bytes,
+                        uint8_t *d_out, uint64_t out_end, int cus, hipStream_t st) {
+    const uint64_t ntiles = (n + TILE - 1) / TILE, nchunks = (ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    int rc = grow(st, d_ws, ws_bytes, (size_t)ntiles * 24 + (size_t)nchunks * (FA_CHUNK_WORDS + 2) * 4 + 64);
+    if (rc != TSX_HIP_OK) return rc;
+    uint4 *summ = reinterpret_cast<uint4 *>(d_ws);
+    uint32_t *tile_state = d_ws + ntiles * 4, *tile_pos = tile_state + ntiles, *chunk_fn = tile_pos + ntiles;
+    uint32_t *chunk_in = chunk_fn + nchunks * FA_CHUNK_WORDS, *info = d_carry + FA_CARRY_BYTES / 4;
+    const uint32_t cap = (uint32_t)std::min<uint64_t>(out_end, 0xFFFFFFF0u);
+    const int g = (int)std::min<uint64_t>(ntiles, (uint64_t)cus * 8);
+    hipLaunchKernelGGL(fasta_summary_kernel, dim3(g), dim3(NT), 0, st, d_text, n, (const uint32_t *)d_carry, summ, ntiles);
+    hipLaunchKernelGGL(fasta_chunk_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const uint4 *)summ, ntiles, chunk_fn);
+    hipLaunchKernelGGL(fasta_chunk_scan_kernel, dim3(1), dim3(NT), 0, st, (const uint32_t *)chunk_fn, (uint32_t)nchunks,
+                       (const uint32_t *)d_carry, kminus1, chunk_in, info, d_out, cap);
+    hipLaunchKernelGGL(fasta_tile_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const uint4 *)summ, ntiles,
+                       (const uint32_t *)chunk_in, tile_state, tile_pos);
+    hipLaunchKernelGGL(fasta_emit_kernel, dim3(g), dim3(NT), 0, st, d_text, n, (const uint32_t *)d_carry, (const uint32_t *)tile_state,
+                       (const uint32_t *)tile_pos, ntiles, d_out, cap);
+    hipLaunchKernelGGL(fasta_finish_kernel, dim3(1), dim3(128), 0, st, d_text, n, (const uint32_t *)info, (const uint8_t *)d_out, kminus1,
+                       d_carry);
+    hipLaunchKernelGGL(fasta_fill_kernel, dim3((uint32_t)std::min<uint64_t>(out_end / (16 * NT) + 1, (uint64_t)cus * 8)), dim3(NT), 0, st,
+                       (const uint32_t *)info, d_out, out_end);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// The wrapped-FASTA entry points count two-line records whatever tsx_hip_set_record_lines says, and put it back.
+struct FastaScope {
+    tsx_hip_map *m;
+    uint32_t mask;
+    explicit FastaScope(tsx_hip_map *mm) : m(mm), mask(mm->p.line_mask) { m->p.line_mask = 1u; }
+    ~FastaScope() { m->p.line_mask = mask; }
+};
+
+static int fasta_args_ok(const tsx_hip_map *m) {
+    if (m->p.lg != m->p.l) { g_last_error = "wrapped FASTA: a map created with shard_bits > 0"; return TSX_HIP_EINVAL; }
+    if (m->minq) { g_last_error = "wrapped FASTA: min_qual_char needs FASTQ records (a FASTA text has no quality line)"; return TSX_HIP_EINVAL; }
+    return TSX_HIP_OK;
+}
+static int fasta_begin(tsx_hip_map *m, hipStream_t st) {   // the carry of a new text: at a line start, no open record
+    if (!m->d_fa_carry) HIP_TRY(hipMalloc((void **)&m->d_fa_carry, FA_CARRY_BYTES + FA_INFO_WORDS * 4));
+    HIP_TRY(hipMemsetAsync(m->d_fa_carry, 0, FA_CARRY_BYTES + FA_INFO_WORDS * 4, st));
+    return TSX_HIP_OK;
+}
+static inline bool slab_build_wanted(const tsx_hip_map *m, size_t n) {
+    return slab_bits(m) && (m->path == 2 || (m->path == 0 && n * 32 >= m->lay.table_bytes));
+}
+
+// One piece of a wrapped text, behind the carry: unwrapped into the map's scratch and counted at its upper-bound length
+// (what the unwrap did not write there is newlines: empty lines), so that nothing is read back.
+static int fasta_count_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, hipStream_t st) {
+    if (n == 0) return TSX_HIP_OK;
+    const size_t ub = fa_bound(n, m->p.k);
+    int rc = grow(st, m->d_fa_out, m->fa_out_bytes, ub + FA_TAIL);
+    if (rc == TSX_HIP_OK)
+        rc = fasta_unwrap(d_text, n, m->d_fa_carry, (uint32_t)m->p.k - 1u, m->d_fa_ws, m->fa_ws_bytes, m->d_fa_out, ub + FA_TAIL, m->cus, st);
+    if (rc != TSX_HIP_OK) return rc;
+    HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));   // (every unwrapped piece starts at a record boundary)
+    return run_fastq_piece(m, m->d_fa_out, ub, ub, 0, st);
+}
+
+extern "C" int tsx_hip_count_fasta_device(tsx_hip_map *m, const void *dev_text, size_t n, void *stream) {
+    if (!m || (!dev_text && n) || ((uintptr_t)dev_text & 15)) return TSX_HIP_EINVAL;
+    if (int rca = fasta_args_ok(m)) return rca;
+    if (n) m->used = true;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    int rc = fasta_begin(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    FastaScope fs(m);
+    const uint8_t *base = (const uint8_t *)dev_text;
+    const size_t WIN = std::min(dev_window_bytes(), FA_PIECE_MAX);
+    if (!slab_build_wanted(m, n)) {
+        for (size_t off = 0; off < n && rc == TSX_HIP_OK; off += WIN) rc = fasta_count_piece(m, base + off, std::min(WIN, n - off), st);
+        return rc;
+    }
+    // a table built slab by slab walks the whole text once per slab: every window's two-line text stays, back to back
+    size_t total = 0;
+    for (size_t off = 0; off < n; off += WIN) total += fa_bound(std::min(WIN, n - off), m->p.k);
+    if ((rc = grow(st, m->d_fa_out, m->fa_out_bytes, total + FA_TAIL)) != TSX_HIP_OK) return rc;
+    size_t at = 0;
+    for (size_t off = 0; off < n && rc == TSX_HIP_OK; off += WIN) {
+        const size_t len = std::min(WIN, n - off), ub = fa_bound(len, m->p.k);
+        rc = fasta_unwrap(base + off, len, m->d_fa_carry, (uint32_t)m->p.k - 1u, m->d_fa_ws, m->fa_ws_bytes, m->d_fa_out + at,
+                          ub + (off + len == n ? FA_TAIL : 0), m->cus, st);
+        at += ub;
+    }
+    if (rc != TSX_HIP_OK) return rc;
+    return tsx_hip_count_fastq_device(m, m->d_fa_out, total, stream);
+}
+
+extern "C" int tsx_hip_count_fasta_host(tsx_hip_map *m, const char *text, size_t n) {
+    if (!m || (!text && n)) return TSX_HIP_EINVAL;
+    if (int rca = fasta_args_ok(m)) return rca;
+    if (n) m->used = true;
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    if (slab_build_wanted(m, n)) {   // the whole text resident, as tsx_hip_count_fastq_host does for such a table
+        uint8_t *d_text = nullptr;
+        HIP_TRY(hipMalloc((void **)&d_text, n + 256));
+        int rcb = hipMemcpy(d_text, text, n, hipMemcpyHostToDevice) == hipSuccess ? TSX_HIP_OK : TSX_HIP_EHIP;
+        if (rcb == TSX_HIP_OK) rcb = tsx_hip_count_fasta_device(m, d_text, n, nullptr);
+        if (rcb == TSX_HIP_OK) rcb = tsx_hip_sync(m);
+        (void)hipStreamSynchronize(m->stream);
+        (void)hipFree(d_text);
+        return rcb;
+    }
+    int rc = ensure_staging(m, n);
+    if (rc != TSX_HIP_OK) return rc;
+    hipStream_t st = m->stream;
+    if ((rc = fasta_begin(m, st)) != TSX_HIP_OK) return rc;
+    FastaScope fs(m);
+    // pieces are cut anywhere and overlap nowhere: what a k-mer across the cut needs travels in the carry
+    const size_t piece = std::min(m->piece, FA_PIECE_MAX);
+    int buf = 0;
+    bool used[2] = {false, false};
+    for (size_t off = 0; off < n; off += piece, buf ^= 1) {
+        const size_t len = std::min(piece, n - off);
+        if (used[buf]) HIP_TRY(hipEventSynchronize(m->stage_done[buf]));
+        parallel_memcpy(m->h_stage[buf], text + off, len);
+        HIP_TRY(hipMemcpyAsync(m->d_stage[buf], m->h_stage[buf], len, hipMemcpyHostToDevice, m->copy_stream));
+        HIP_TRY(hipEventRecord(m->stage_in[buf], m->copy_stream));
+        HIP_TRY(hipStreamWaitEvent(st, m->stage_in[buf], 0));
+        if ((rc = fasta_count_piece(m, m->d_stage[buf], len, st)) != TSX_HIP_OK) return rc;
+        HIP_TRY(hipEventRecord(m->stage_done[buf], st));
+        used[buf] = true;
+    }
+    return tsx_hip_sync(m);
+}
+
+// Batch after batch on the map's stream: inflated, unwrapped behind the carry, counted.
+extern "C" int tsx_hip_count_fasta_bgzf_host(tsx_hip_map *m, const void *gz, size_t n) {
+    if (!m || (!gz && n)) return TSX_HIP_EINVAL;
+    if (int rca = fasta_args_ok(m)) return rca;
+    if (n) m->used = true;
+    BgzfIndex ix;
+    if (!bgzf_index((const uint8_t *)gz, n, ix)) { g_last_error = "not a BGZF file (no BC extra field in every gzip member)"; return TSX_HIP_EINVAL; }
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = m->stream;
+    join_foreign(m, false);
+    int rc = fasta_begin(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    FastaScope fs(m);
+    const size_t batch = std::min(bgzf_batch_bytes(), FA_PIECE_MAX), nm = ix.in_off.size();
+    size_t biggest = 0;
+    for (size_t m0 = 0; m0 < nm;) { const size_t m1 = bgzf_next_batch(ix, m0, batch); biggest = std::max(biggest, bgzf_batch_text(ix, m0, m1)); m0 = m1; }
+    BgzfDev dv;
+    uint8_t *d_txt = nullptr;
+    if (hipMalloc((void **)&d_txt, biggest + 256) != hipSuccess) { g_last_error = "hipMalloc of a BGZF text buffer failed"; return TSX_HIP_ENOMEM; }
+    for (size_t m0 = 0; m0 < nm && rc == TSX_HIP_OK;) {
+        const size_t m1 = bgzf_next_batch(ix, m0, batch);
+        rc = inflate_batch((const uint8_t *)gz, n, ix, m0, m1, dv, d_txt, st);   // (behind the count of the batch before)
+        if (rc == TSX_HIP_OK) rc = fasta_count_piece(m, d_txt, bgzf_batch_text(ix, m0, m1), st);
+        m0 = m1;
+    }
+    hipError_t e = hipStreamSynchronize(st);
+    (void)hipFree(d_txt);
+    if (rc == TSX_HIP_OK && e != hipSuccess) { g_last_error = hipGetErrorString(e); rc = TSX_HIP_EHIP; }
+    return rc == TSX_HIP_OK ? tsx_hip_sync(m) : rc;
+}
+
+extern "C" int tsx_hip_unwrap_fasta_host(int device, const char *text, size_t n, void *out_host, size_t out_cap, size_t *out_bytes) {
+    if ((!text && n) || !out_bytes) return TSX_HIP_EINVAL;
+    *out_bytes = n ? n + 2 : 0;   // (the bound, until the size is known)
+    if (n >= ((size_t)1 << 32) - 64) { g_last_error = "unwrap_fasta: a text of 2^32 - 64 bytes or more"; return TSX_HIP_ERANGE; }
+    if (n == 0) return TSX_HIP_OK;
+    HIP_TRY(hipSetDevice(device));
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    uint8_t *d_text = nullptr, *d_out = nullptr;
+    uint32_t *d_carry = nullptr, *d_ws = nullptr;
+    size_t ws_bytes = 0;
+    const size_t end = ((n + 2 + 15) & ~(size_t)15) + 16;
+    auto run = [&]() -> int {
+        HIP_TRY(hipMalloc((void **)&d_text, n + 256));
+        HIP_TRY(hipMalloc((void **)&d_out, end));
+        HIP_TRY(hipMalloc((void **)&d_carry, FA_CARRY_BYTES + FA_INFO_WORDS * 4));
+        HIP_TRY(hipMemcpy(d_text, text, n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(d_carry, 0, FA_CARRY_BYTES + FA_INFO_WORDS * 4));
+        int rc = fasta_unwrap(d_text, n, d_carry, 0u, d_ws, ws_bytes, d_out, end, cus, nullptr);
+        if (rc != TSX_HIP_OK) return rc;
+        uint32_t total = 0;
+        HIP_TRY(hipMemcpy(&total, d_carry + FA_CARRY_BYTES / 4, 4, hipMemcpyDeviceToHost));
+        *out_bytes = total ? (size_t)total + 1 : 0;   // the newline that ends the last record comes from the fill
+        if (*out_bytes > out_cap || (*out_bytes && !out_host)) return TSX_HIP_ERANGE;
+        if (*out_bytes) HIP_TRY(hipMemcpy(out_host, d_out, *out_bytes, hipMemcpyDeviceToHost));
+        return TSX_HIP_OK;
+    };
+    const int rc = run();
+    (void)hipFree(d_text); (void)hipFree(d_out); (void)hipFree(d_carry); (void)hipFree(d_ws);
+    return rc;
 }
 
 extern "C" int tsx_hip_add_kmers_device(tsx_hip_map *m, const void *dev_kmers, const void *dev_counts, size_t n,

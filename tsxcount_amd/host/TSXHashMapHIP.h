@@ -231,6 +231,18 @@ public:
         if (rc == TSX_HIP_EINVAL) throw TSXException(std::string("BGZF input: ") + tsx_hip_last_error(), rc);
         check(rc);
     }
+    // wrapped (multi-line) FASTA: the sequence lines of a record joined on the device (csrc/tsx_fasta.h), then counted
+    // as two-line records -- whatever setRecordLines says, which stays as it is
+    void countFasta(const char *pText, size_t iBytes) {
+        int rc = tsx_hip_count_fasta_host(m_pMap, pText, iBytes);
+        if (rc == TSX_HIP_EINVAL) throw TSXException(std::string("wrapped FASTA input: ") + tsx_hip_last_error(), rc);
+        check(rc);
+    }
+    void countFastaBgzf(const void *pGz, size_t iBytes) {
+        int rc = tsx_hip_count_fasta_bgzf_host(m_pMap, pGz, iBytes);
+        if (rc == TSX_HIP_EINVAL) throw TSXException(std::string("wrapped FASTA input: ") + tsx_hip_last_error(), rc);
+        check(rc);
+    }
 
     // empties the table (the reference has no counterpart: its maps are filled once)
     void clear() { check(tsx_hip_clear(m_pMap)); }

@@ -23,7 +23,7 @@
 
 struct arguments {
     int k = 14, l = 26, storagebits = 4, threads = 0;  // main.cpp:410-413
-    std::string input_path, mode = "HIP", format;   // format: "", "fastq" or "fasta" ("" = by file name)
+    std::string input_path, mode = "HIP", format;   // format: "", "fastq", "fasta" or "fasta-wrapped" ("" = by file name)
     bool check = false, checkabort = false;
     unsigned long long seed = 1;
     int device = 0;
@@ -66,7 +66,7 @@ static bool opt(const char *arg, const char *name, std::string &val) {
 
 static int usage() {
     std::cerr << "Usage: tsxCount [--input=FASTQ|FASTA[.gz]] [--k=K] [--l=L] [--s=STORAGE] [--mode=HIP] [--threads=T]\n"
-                 "                [--check] [--checkabort] [--seed=S] [--device=D] [--format=fastq|fasta] [--canonical]\n"
+                 "                [--check] [--checkabort] [--seed=S] [--device=D] [--format=fastq|fasta|fasta-wrapped] [--canonical]\n"
                  "                [--acgt-only] [--min-qual-char=C]\n"
                  "                [--gpus=N [--comm=rccl|copy] [--devices=a,b,...] [--exchange=merge|mini|auto]]\n"
                  "                [--output=FILE [--lower=N] [--upper=N]] [--histo=FILE [--histo-max=H]]\n"
@@ -75,6 +75,11 @@ static int usage() {
                  "                [--with=DB[,DB2,...] [--op=intersect|union|subtract|diff] [--op-count=min|max|sum|left|right]\n"
                  "                 [--a-lower=N] [--a-upper=N] [--b-lower=N] [--b-upper=N] [--compare]]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
+                 "--format=fasta reads two lines per record (a header, ONE sequence line), as file names ending in .fa, .fasta\n"
+                 "or .fna do. --format=fasta-wrapped reads FASTA whose sequences are wrapped over several lines (what genome and\n"
+                 "assembly downloads look like): the lines of a record are joined on the GPU, k-mers across line breaks count.\n"
+                 "It names the format of --input only (a --filter-input goes by its own file name), runs on one GPU, and has no\n"
+                 "--min-qual-char and no --filter / --read-stats of the wrapped input itself.\n"
                  "--canonical counts a k-mer and its reverse complement as one (the check then expects f(x) + f(rc x)).\n"
                  "--acgt-only skips every k-mer with a byte outside ACGTacgt (an N, say); --min-qual-char=C every k-mer with a\n"
                  "base whose quality byte is below the character C, or that has none (FASTQ only). Both hold for the read\n"
@@ -157,6 +162,8 @@ static bool load_input(const std::string &path, std::vector<char> &owned, const 
     return true;
 }
 
+static bool is_wrapped(const arguments &a) { return a.format == "fasta-wrapped"; }   // multi-line FASTA, lines joined on the GPU
+
 static bool is_fasta(const arguments &a) {   // FASTA (two lines per record, FASTXreader<FASTAEntry>) by option or by file name
     std::string stem = a.input_path;
     if (stem.size() > 3 && stem.rfind(".gz") == stem.size() - 3) stem.resize(stem.size() - 3);
@@ -230,7 +237,8 @@ static int run_read_queries(tsx_hip_map *pMap, const arguments &a) {
         text = owned.data();
         n = got;
     }
-    check(tsx_hip_set_record_lines(pMap, is_fasta_path(path, a.format) ? 2 : 4));
+    // (--format=fasta-wrapped names the format of --input only: the queried file goes by its name)
+    check(tsx_hip_set_record_lines(pMap, is_fasta_path(path, is_wrapped(a) ? std::string() : a.format) ? 2 : 4));
     if (!a.read_stats.empty()) {
         const std::vector<tsx_hip_read_stats> st = tsx_query_reads(pMap, text, n, a.filter_lower, a.filter_upper, 0, check);
         std::ofstream f(a.read_stats);
@@ -562,6 +570,23 @@ int main(int argc, char *argv[]) {
         std::cerr << "--min-qual-char needs FASTQ input: a FASTA record has no quality line" << std::endl;
         return usage();
     }
+    if (is_wrapped(a)) {
+        if (a.gpus > 1) {
+            std::cerr << "--format=fasta-wrapped runs on one GPU only: a --gpus " << a.gpus << " run cuts the text at two-line or"
+                      << " four-line records" << std::endl;
+            return usage();
+        }
+        if (a.min_qual_char) {
+            std::cerr << "--min-qual-char needs FASTQ input: a FASTA record has no quality line" << std::endl;
+            return usage();
+        }
+        if (wants_queries(a) && (a.filter_input.empty() || a.filter_input == a.input_path)) {
+            std::cerr << "--filter and --read-stats do not read wrapped FASTA: give the reads to query as --filter-input=FILE"
+                      << " (FASTQ, or FASTA with one sequence line per record)" << std::endl;
+            return usage();
+        }
+        a.group = false;   // --gpus=1: the one table of this process
+    }
     if (a.gpus < 1 || (a.comm != "rccl" && a.comm != "copy") || (!a.devices.empty() && (int)a.devices.size() != a.gpus)) return usage();
     if (a.filter_lower > a.filter_upper || !(a.filter_fraction >= 0.0 && a.filter_fraction <= 1.0)) return usage();
     if (wants_queries(a) && a.gpus > 1) {
@@ -588,9 +613,11 @@ int main(int argc, char *argv[]) {
         if (a.group) return run_group(a);
         std::cerr << "Creating TSXHashMap HIP" << std::endl;
         TSXHashMapHIP oMap((uint8_t)a.l, (uint32_t)a.storagebits, (uint16_t)a.k, (uint8_t)a.threads, a.seed, a.device, overflow_l);
-        if (is_fasta(a)) { oMap.setRecordLines(2); std::cerr << "Format=FASTA (2 lines per record)" << std::endl; }
+        if (is_wrapped(a)) std::cerr << "Format=FASTA (wrapped, lines joined)" << std::endl;
+        else if (is_fasta(a)) { oMap.setRecordLines(2); std::cerr << "Format=FASTA (2 lines per record)" << std::endl; }
         if (a.canonical) oMap.setCanonical(true);
         if (a.acgt_only || a.min_qual_char) oMap.setBaseRule(a.acgt_only, a.min_qual_char);
+        const bool wrapped = is_wrapped(a);
         std::vector<char> owned;
         const char *text = nullptr;
         size_t n = 0;
@@ -609,7 +636,8 @@ int main(int argc, char *argv[]) {
             // nothing to count: the loaded tables are the result
         } else if (bgzf) {
             try {
-                oMap.countFastqBgzf(text, n);
+                if (wrapped) oMap.countFastaBgzf(text, n);
+                else oMap.countFastqBgzf(text, n);
             } catch (const TSXException &e) {
                 // the device path needs two batch-sized text buffers next to the table: without them the input is
                 // read the way the reference reads it (zlib on the host) and counted through the staged host path
@@ -618,8 +646,11 @@ int main(int argc, char *argv[]) {
                 oMap.clear();
                 for (const std::string &db : a.load) oMap.loadDatabase(db);
                 if (!read_gz(a.input_path, owned)) { std::cerr << "Could not read " << a.input_path << std::endl; return 3; }
-                oMap.countFastq(owned.data(), owned.size());
+                if (wrapped) oMap.countFasta(owned.data(), owned.size());
+                else oMap.countFastq(owned.data(), owned.size());
             }
+        } else if (wrapped) {
+            oMap.countFasta(text, n);
         } else {
             oMap.countFastq(text, n);
         }
