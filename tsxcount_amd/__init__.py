@@ -244,6 +244,14 @@ def _check(code):
         raise TSXException(code, msg)
 
 
+def _check_bgzf(code):
+    """A refused BGZF image: the library says which member and why (tsx_hip_last_error)."""
+    if code == EINVAL:
+        L = lib()
+        raise TSXException(code, L.tsx_hip_last_error().decode() or L.tsx_hip_strerror(code).decode())
+    _check(code)
+
+
 def _p(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
 
@@ -629,7 +637,7 @@ class TSXHashMapHIP:
     def countFastqBgzf(self, gz):
         """The same for the image of a blocked gzip (BGZF) file: members inflated on the device (tsx_inflate.h)."""
         b = bytes(gz)
-        _check(self._lib.tsx_hip_count_fastq_bgzf_host(self._h, b, len(b)))
+        _check_bgzf(self._lib.tsx_hip_count_fastq_bgzf_host(self._h, b, len(b)))
 
     def countFastqDevice(self, dev_ptr, nbytes, stream=None):
         _check(self._lib.tsx_hip_count_fastq_device(self._h, ctypes.c_void_p(dev_ptr), nbytes,
@@ -902,7 +910,7 @@ def bgzf_inflate(gz, device=0):
         raise TSXException(EINVAL, "not a BGZF image")
     out = ctypes.create_string_buffer(max(ix[1], 1))
     got = ctypes.c_size_t(0)
-    _check(lib().tsx_hip_inflate_bgzf_host(device, b, len(b), out, ix[1], ctypes.byref(got)))
+    _check_bgzf(lib().tsx_hip_inflate_bgzf_host(device, b, len(b), out, ix[1], ctypes.byref(got)))
     return out.raw[:got.value]
 
 

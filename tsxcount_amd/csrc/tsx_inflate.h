@@ -329,6 +329,8 @@ __global__ __launch_bounds__(INF_NT) void inflate_members_kernel(const uint8_t *
                 ++lcnt; ++pos;
                 if (lcnt == 8u) { __builtin_memcpy(o + pos - 8u, &lbuf, 8); lbuf = 0; lcnt = 0; }
             } else if (clen != 0) {
+                // (64, not less: the eighth store ends at pos + 64, and with clen in 57..63 at the end of the member it
+                // would run into the next member's text -- tests/test_inflate_streams.py fails with 56)
                 if (small && have_pat && pos + 64u <= olen) {   // up to eight stores, no load: long runs in few iterations
                     const uint32_t step = (8u / cdist) * cdist;   // whole periods per store
                     const uint32_t n = min(clen, 8u * step);
