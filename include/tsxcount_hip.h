@@ -613,6 +613,11 @@ int tsx_hip_group_merge(tsx_hip_group *g);
 int tsx_hip_group_get_counts_host(tsx_hip_group *g, const uint64_t *kmers, size_t n, uint64_t *counts_out);
 int tsx_hip_group_get_stats(tsx_hip_group *g, tsx_hip_stats *out);
 uint64_t tsx_hip_group_exchanged_entries(const tsx_hip_group *g);   /* entries that changed GPU in the last merge */
+/* Rounds of the last group_count_fastq_host (countKMers for N GPUs, main.cpp:104-218 + the exchange): pieces of the longest
+ * shard x shares of a piece for the minimizer exchange, 0 for the merge.  A piece is 2 GiB of text and a share at least
+ * 32 MiB; TSX_HIP_MZ_PIECE (bytes, rounded up to a multiple of 4096, 4096 .. 2 GiB) and TSX_HIP_MZ_SHARE (bytes, >= 1;
+ * shares = piece / share, 1 .. 4) are read once per count and let tests put many rounds into a small text. */
+uint32_t tsx_hip_group_exchange_rounds(const tsx_hip_group *g);
 /* tsx_hip_histogram_host / tsx_hip_write_counts_host over the group, rank by rank: after group_count_fastq_host every
  * k-mer lives on one GPU (the merge leaves it on its owner; the minimizer exchange is disjoint by construction), so the
  * histogram is the sum of the ranks' and the file (the `.count` format of main.cpp:224-396) lists every k-mer once. */

@@ -228,6 +228,8 @@ def lib():
     L.tsx_hip_group_set_exchange.argtypes = [vp, ci]
     L.tsx_hip_group_exchange.argtypes = [vp]
     L.tsx_hip_group_exchanged_entries.restype = u64
+    L.tsx_hip_group_exchange_rounds.argtypes = [vp]
+    L.tsx_hip_group_exchange_rounds.restype = ctypes.c_uint32
     L.tsx_hip_cut_records_host.argtypes = [ctypes.c_char_p, sz, ci, ci, ctypes.POINTER(sz)]
     _lib = L
     return L
@@ -860,6 +862,11 @@ class TSXHashMapHIPGroup:
 
     def exchanged_entries(self):
         return int(self._lib.tsx_hip_group_exchanged_entries(self._h))
+
+    def exchange_rounds(self):
+        """Rounds of the last countFastq: pieces x shares of the minimizer exchange (TSX_HIP_MZ_PIECE / TSX_HIP_MZ_SHARE
+        shrink both), 0 for the merge."""
+        return int(self._lib.tsx_hip_group_exchange_rounds(self._h))
 
 
 def join_fasta(text):

@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <condition_variable>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -205,6 +206,7 @@ struct tsx_hip_group {
     int k = 0;
     int exchange = 0;                 // 0: per-GPU tables merged after the count; 1: minimizer exchange (tsx_minimizer.h)
     uint64_t exchanged_entries = 0;   // entries that changed GPU in the last merge
+    uint32_t exchange_rounds = 0;     // rounds of the last count's minimizer exchange (pieces x shares), 0 after a merge
     double last_merge_ms = 0;
 };
 
@@ -431,9 +433,28 @@ struct MiniShared {
 };
 constexpr size_t MINI_PIECE = (size_t)2 << 30;     // bytes of text described at once
 constexpr size_t MINI_MIN_SHARE = (size_t)32 << 20;
+// The rounds of one count: pieces of the longest shard, shares of a piece.  Worked out ONCE per count, on the calling
+// thread, and handed to every rank.  TSX_HIP_MZ_PIECE / TSX_HIP_MZ_SHARE: tests exercise the seams between rounds.
+struct MiniGeometry { size_t piece_bytes; uint32_t pieces, parts; };
+MiniGeometry mini_geometry(size_t max_len) {
+    size_t piece = MINI_PIECE, share = MINI_MIN_SHARE;
+    if (const char *e = getenv("TSX_HIP_MZ_PIECE")) {   // a multiple of 4096: the offset of a piece stays 16-byte aligned
+        const long long v = atoll(e);
+        if (v > 0) piece = (std::min((size_t)v, MINI_PIECE) + 4095) & ~(size_t)4095;
+    }
+    if (const char *e = getenv("TSX_HIP_MZ_SHARE")) {
+        const long long v = atoll(e);
+        if (v > 0) share = (size_t)v;
+    }
+    MiniGeometry geo;
+    geo.piece_bytes = std::min(piece, std::max<size_t>(4096, (max_len + 4095) & ~(size_t)4095));
+    geo.pieces = (uint32_t)std::max<size_t>(1, (max_len + geo.piece_bytes - 1) / geo.piece_bytes);
+    geo.parts = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, geo.piece_bytes / share));
+    return geo;
+}
 }  // namespace
 
-static int mini_rank(tsx_hip_group *g, int r, const char *text, size_t len, size_t max_len, MiniShared &sh) {
+static int mini_rank(tsx_hip_group *g, int r, const char *text, size_t len, const MiniGeometry &geo, MiniShared &sh) {
     const int n = g->n;
     tsx_hip_map *m = g->maps[r];
     int acgt = 0, minq = 0;
@@ -444,11 +465,9 @@ static int mini_rank(tsx_hip_group *g, int r, const char *text, size_t len, size
     (void)hipSetDevice(g->devices[r]);
     hipStream_t st = g->streams[r];
     int rc = TSX_HIP_OK;
-    // the same rounds on every rank, whatever its own shard: pieces of the longest shard, shares of a piece
-    const size_t piece_bytes = std::min(MINI_PIECE, std::max<size_t>(4096, (max_len + 4095) & ~(size_t)4095));
-    const uint32_t pieces = (uint32_t)std::max<size_t>(1, (max_len + piece_bytes - 1) / piece_bytes);
-    const uint32_t parts = (uint32_t)std::max<size_t>(1, std::min<size_t>(4, piece_bytes / MINI_MIN_SHARE));
-    const uint32_t rounds = pieces * parts;
+    // the same rounds on every rank, whatever its own shard
+    const size_t piece_bytes = geo.piece_bytes;
+    const uint32_t parts = geo.parts, rounds = geo.pieces * geo.parts;
     size_t cap = 0;
     (void)tsx_hip_mini_part_capacity(m, piece_bytes + 256, parts, &cap);
     uint8_t *d_text = nullptr;
@@ -573,8 +592,11 @@ extern "C" int tsx_hip_group_count_fastq_host(tsx_hip_group *g, const char *text
         size_t max_len = 0;
         for (int r = 0; r < g->n; ++r) max_len = std::max(max_len, cuts[r + 1] - cuts[r]);
         MiniShared sh(g->n);
-        return run_ranks(g, [&](int r) { return mini_rank(g, r, text + cuts[r], cuts[r + 1] - cuts[r], max_len, sh); });
+        const MiniGeometry geo = mini_geometry(max_len);
+        g->exchange_rounds = geo.pieces * geo.parts;
+        return run_ranks(g, [&](int r) { return mini_rank(g, r, text + cuts[r], cuts[r + 1] - cuts[r], geo, sh); });
     }
+    g->exchange_rounds = 0;
     std::vector<Slot> slots(g->n), cslots(g->n);
     std::vector<std::vector<unsigned long long>> seg(g->n);
     std::vector<int> ok(g->n, 0);
@@ -632,6 +654,7 @@ extern "C" int tsx_hip_group_get_stats(tsx_hip_group *g, tsx_hip_stats *out) {
 }
 
 extern "C" uint64_t tsx_hip_group_exchanged_entries(const tsx_hip_group *g) { return g ? g->exchanged_entries : 0; }
+extern "C" uint32_t tsx_hip_group_exchange_rounds(const tsx_hip_group *g) { return g ? g->exchange_rounds : 0; }
 
 // Output over the group, rank by rank: the tables are disjoint once the count has returned (the merge leaves each k-mer
 // on its owner; the minimizer exchange sends every k-mer to one owner), so sums and concatenation are exact.

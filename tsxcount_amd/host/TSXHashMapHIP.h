@@ -337,6 +337,7 @@ public:
         return s;
     }
     uint64_t exchangedEntries() const { return tsx_hip_group_exchanged_entries(m_pGroup); }
+    uint32_t exchangeRounds() const { return tsx_hip_group_exchange_rounds(m_pGroup); }
     // the histogram / .count file of the whole group (the ranks' tables are disjoint after countFastq)
     std::vector<uint64_t> histogram(size_t iBins) {
         std::vector<uint64_t> h(iBins);

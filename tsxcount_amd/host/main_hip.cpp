@@ -394,7 +394,9 @@ static int run_group(const arguments &a) {
     oGroup.countFastq(text, n);
     double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (map) munmap(map, n);
-    std::cerr << (oGroup.exchange() == 1 ? "descriptions moved between GPUs by the last share: " : "entries moved between GPUs by the merge: ") << oGroup.exchangedEntries() << std::endl;
+    std::cerr << (oGroup.exchange() == 1 ? "descriptions moved between GPUs by the last share: " : "entries moved between GPUs by the merge: ") << oGroup.exchangedEntries();
+    if (oGroup.exchange() == 1) std::cerr << " (exchange rounds: " << oGroup.exchangeRounds() << ")";
+    std::cerr << std::endl;
     const int rc = report_and_check(oGroup, a, dt);
     if (!wants_queries(a)) return rc;
     const int rq = run_read_queries(oGroup.rankMap(0), a);   // one GPU: its table holds every k-mer
