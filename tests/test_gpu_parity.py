@@ -320,8 +320,9 @@ def test_rolling_hash_every_one_limb_k(T, k):
 
 
 def test_log_region_overflow_takes_the_side_path(T, monkeypatch):
-    """A wave's key-log region that fills up hands the rest of its keys to the atomic path
-    (scan_side_insert): forced here by shrinking the regions to 64 keys."""
+    """A wave's key-log region that fills up hands the rest of its keys to the deferred list
+    (defer_append1; deferred_insert_kernel inserts them after the segment build): forced here by
+    shrinking the regions to 64 keys."""
     from tsxcount_amd import synth
     text = synth.fastq(9, 0, 600)
     monkeypatch.setenv("TSX_HIP_LOG_CAP", "64")
