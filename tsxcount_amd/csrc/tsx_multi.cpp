@@ -17,6 +17,7 @@
 //                 double for world sizes a one-GPU box cannot give RCCL
 // The sizes of the groups travel through host memory (the ranks are threads of this process).
 #include "../../include/tsxcount_hip.h"
+#include "tsx_own.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
@@ -198,7 +199,7 @@ struct tsx_hip_group {
     int n = 0;
     std::vector<tsx_hip_map *> maps;
     std::vector<int> devices;
-    std::vector<hipStream_t> streams;
+    std::vector<tsx::Stream> streams;   // one per rank, on its device
     Exchange *xch = nullptr;
     Barrier *bar = nullptr;
     int lines_per_record = 4;
@@ -215,7 +216,7 @@ extern "C" const char *tsx_hip_group_last_error(void) { return g_multi_error.c_s
 extern "C" void tsx_hip_group_destroy(tsx_hip_group *g) {
     if (!g) return;
     for (int r = 0; r < g->n; ++r) {
-        if (r < (int)g->streams.size() && g->streams[r]) { (void)hipSetDevice(g->devices[r]); (void)hipStreamDestroy(g->streams[r]); }
+        if (r < (int)g->streams.size() && g->streams[r].get()) { (void)hipSetDevice(g->devices[r]); g->streams[r].reset(); }
         if (r < (int)g->maps.size()) tsx_hip_destroy(g->maps[r]);
     }
     delete g->xch;
@@ -266,13 +267,13 @@ extern "C" int tsx_hip_group_create(tsx_hip_group **out, int ngpus, const int *d
         const int rc = tsx_hip_create(&m, k, l, storagebits, overflow_l, hash_seed, g->devices[r]);
         if (rc != TSX_HIP_OK) { g_multi_error = tsx_hip_last_error(); tsx_hip_group_destroy(g); return rc; }
         g->maps.push_back(m);
-        hipStream_t st = nullptr;
-        if (hipSetDevice(g->devices[r]) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+        tsx::Stream st;
+        if (hipSetDevice(g->devices[r]) != hipSuccess || st.create() != TSX_HIP_OK) {
             g_multi_error = "hipStreamCreate failed";
             tsx_hip_group_destroy(g);
             return TSX_HIP_EHIP;
         }
-        g->streams.push_back(st);
+        g->streams.push_back(std::move(st));
     }
     *out = g;
     return TSX_HIP_OK;
@@ -320,20 +321,19 @@ static int merge_rank(tsx_hip_group *g, int r, std::vector<Slot> &slots, std::ve
     tsx_hip_map *m = g->maps[r];
     int rc = rc_in;
     (void)hipSetDevice(g->devices[r]);
-    hipStream_t st = g->streams[r];
+    hipStream_t st = g->streams[r].get();
     tsx_hip_stats s;
     memset(&s, 0, sizeof s);
     if (rc == TSX_HIP_OK) rc = tsx_hip_get_stats(m, &s);
     const size_t mine = (rc == TSX_HIP_OK) ? (size_t)s.distinct : 0;
-    uint64_t *d_k = nullptr, *d_c = nullptr, *d_rk = nullptr, *d_rc = nullptr;
-    unsigned long long *d_seg = nullptr;
-    auto dmalloc = [&](void **p, size_t bytes) {
-        if (rc != TSX_HIP_OK) return;
-        if (hipMalloc(p, std::max<size_t>(bytes, 64)) != hipSuccess) { g_multi_error = "hipMalloc of a merge buffer failed"; rc = TSX_HIP_ENOMEM; }
+    tsx::DevBuf<uint64_t> buf_k, buf_c, buf_rk, buf_rc;
+    tsx::DevBuf<unsigned long long> buf_seg;
+    auto dmalloc = [&](auto &buf, size_t bytes) {   // (skipped after a failure; at least 64 bytes)
+        if (rc == TSX_HIP_OK && buf.alloc(std::max<size_t>(bytes, 64)) != TSX_HIP_OK) { g_multi_error = "hipMalloc of a merge buffer failed"; rc = TSX_HIP_ENOMEM; }
+        return buf.get();
     };
-    dmalloc((void **)&d_k, mine * wk * 8);
-    dmalloc((void **)&d_c, mine * 8);
-    dmalloc((void **)&d_seg, (size_t)n * 8);
+    uint64_t *const d_k = dmalloc(buf_k, mine * wk * 8), *const d_c = dmalloc(buf_c, mine * 8);
+    unsigned long long *const d_seg = dmalloc(buf_seg, (size_t)n * 8);
     seg[r].assign(n, 0);
     if (rc == TSX_HIP_OK && mine) {
         rc = tsx_hip_partition_device(m, n, d_k, d_c, mine, d_seg, st);   // waits for its own stream
@@ -353,8 +353,7 @@ static int merge_rank(tsx_hip_group *g, int r, std::vector<Slot> &slots, std::ve
         ks.recv_off[p + 1] = cs.recv_off[p + 1] * wk;
     }
     const size_t got = cs.recv_off[n];
-    dmalloc((void **)&d_rk, got * wk * 8);
-    dmalloc((void **)&d_rc, got * 8);
+    uint64_t *const d_rk = dmalloc(buf_rk, got * wk * 8), *const d_rc = dmalloc(buf_rc, got * 8);
     ks.send = d_k; ks.recv = d_rk; cs.send = d_c; cs.recv = d_rc;
     // a rank that cannot send or receive must not leave its peers inside the collective: agree first
     ok[r] = (rc == TSX_HIP_OK) ? 1 : 0;
@@ -373,7 +372,6 @@ static int merge_rank(tsx_hip_group *g, int r, std::vector<Slot> &slots, std::ve
     if (rc == TSX_HIP_OK && got) rc = tsx_hip_add_kmers_device(m, d_rk, d_rc, got, st);
     if (rc == TSX_HIP_OK && hipStreamSynchronize(st) != hipSuccess) rc = TSX_HIP_EHIP;
     if (rc == TSX_HIP_OK) rc = tsx_hip_sync(m);
-    (void)hipFree(d_k); (void)hipFree(d_c); (void)hipFree(d_seg); (void)hipFree(d_rk); (void)hipFree(d_rc);
     if (r == 0) {
         uint64_t moved = 0;
         for (int a = 0; a < n; ++a) for (int b = 0; b < n; ++b) if (a != b) moved += seg[a][b];
@@ -463,25 +461,24 @@ static int mini_rank(tsx_hip_group *g, int r, const char *text, size_t len, cons
         return TSX_HIP_EINVAL;
     }
     (void)hipSetDevice(g->devices[r]);
-    hipStream_t st = g->streams[r];
+    hipStream_t st = g->streams[r].get();
     int rc = TSX_HIP_OK;
     // the same rounds on every rank, whatever its own shard
     const size_t piece_bytes = geo.piece_bytes;
     const uint32_t parts = geo.parts, rounds = geo.pieces * geo.parts;
     size_t cap = 0;
     (void)tsx_hip_mini_part_capacity(m, piece_bytes + 256, parts, &cap);
-    uint8_t *d_text = nullptr;
-    uint64_t *d_lists = nullptr, *d_recv = nullptr;
-    unsigned long long *d_cnt = nullptr, *d_emit = nullptr;
-    size_t recv_words = 0;
-    auto dmalloc = [&](void **p, size_t bytes) {
-        if (rc != TSX_HIP_OK) return;
-        if (hipMalloc(p, std::max<size_t>(bytes, 64)) != hipSuccess) { g_multi_error = "hipMalloc of an exchange buffer failed"; rc = TSX_HIP_ENOMEM; }
+    tsx::DevBuf<uint8_t> buf_text;
+    tsx::DevBuf<uint64_t> buf_lists, buf_recv;
+    tsx::DevBuf<unsigned long long> buf_cnt, buf_emit;
+    tsx::SyncAtExit wait(st);   // nothing queued may outlive the buffers
+    auto dmalloc = [&](auto &buf, size_t bytes) {   // (skipped after a failure; at least 64 bytes)
+        if (rc == TSX_HIP_OK && buf.alloc(std::max<size_t>(bytes, 64)) != TSX_HIP_OK) { g_multi_error = "hipMalloc of an exchange buffer failed"; rc = TSX_HIP_ENOMEM; }
+        return buf.get();
     };
-    dmalloc((void **)&d_text, len + 256);
-    dmalloc((void **)&d_lists, (size_t)n * cap * 16);
-    dmalloc((void **)&d_cnt, ((size_t)n + 4) * 8);
-    dmalloc((void **)&d_emit, 16);
+    uint8_t *const d_text = dmalloc(buf_text, len + 256);
+    uint64_t *const d_lists = dmalloc(buf_lists, (size_t)n * cap * 16), *d_recv = nullptr;
+    unsigned long long *const d_cnt = dmalloc(buf_cnt, ((size_t)n + 4) * 8), *const d_emit = dmalloc(buf_emit, 16);
     if (rc == TSX_HIP_OK && (hipMemcpyAsync(d_text, text, len, hipMemcpyHostToDevice, st) != hipSuccess ||
                              hipMemsetAsync(d_text + len, '\n', 256, st) != hipSuccess || hipMemsetAsync(d_emit, 0, 16, st) != hipSuccess))
         rc = TSX_HIP_EHIP;
@@ -512,10 +509,9 @@ static int mini_rank(tsx_hip_group *g, int r, const char *text, size_t len, cons
             sl.recv_off[p + 1] = sl.recv_off[p] + (size_t)sh.cnt[p][r] * 2;
         }
         const size_t got = sl.recv_off[n];            // words: two per description
-        if (rc == TSX_HIP_OK && got > recv_words) {
-            if (d_recv) { (void)hipStreamSynchronize(st); (void)hipFree(d_recv); d_recv = nullptr; }
-            recv_words = got + got / 4 + 4096;
-            dmalloc((void **)&d_recv, recv_words * 8);
+        if (rc == TSX_HIP_OK && got * 8 > buf_recv.cap()) {
+            if (buf_recv.get()) (void)hipStreamSynchronize(st);   // (the walk of the round before reads it)
+            d_recv = dmalloc(buf_recv, (got + got / 4 + 4096) * 8);
         }
         sl.send = d_lists; sl.recv = d_recv;
         sh.ok[r] = (rc == TSX_HIP_OK) ? 1 : 0;
@@ -563,8 +559,6 @@ static int mini_rank(tsx_hip_group *g, int r, const char *text, size_t len, cons
         rc = TSX_HIP_EHIP;
     }
     if (rc == TSX_HIP_OK) rc = tsx_hip_sync(m);
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(d_text); (void)hipFree(d_lists); (void)hipFree(d_recv); (void)hipFree(d_cnt); (void)hipFree(d_emit);
     if (r == 0) {
         uint64_t moved = 0;   // (of the last share only: the sizes of earlier shares are gone)
         for (int a = 0; a < n; ++a) for (int b = 0; b < n; ++b) if (a != b) moved += sh.cnt[a][b];

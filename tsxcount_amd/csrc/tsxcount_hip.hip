@@ -12,6 +12,7 @@
 #include "tsx_db.h"
 #include "tsx_combine.h"
 #include "tsx_fasta.h"
+#include "tsx_own.h"
 
 #include <mutex>
 #include <hip/hip_runtime.h>
@@ -23,6 +24,7 @@
 #include <cmath>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -41,95 +43,130 @@ static thread_local std::string g_last_error;
             return (_e == hipErrorOutOfMemory) ? TSX_HIP_ENOMEM : TSX_HIP_EHIP;          \
         }                                                                                \
     } while (0)
+// the same for a step that returns a TSX_HIP_* code (the owners' alloc / reserve / create among them)
+#define TSX_TRY(expr)                                                                    \
+    do {                                                                                 \
+        const int _rc = (expr);                                                          \
+        if (_rc != TSX_HIP_OK) return _rc;                                               \
+    } while (0)
+
+int tsx::own_fail(const char *what, hipError_t e) {
+    g_last_error = std::string(what) + ": " + hipGetErrorString(e);
+    return (e == hipErrorOutOfMemory) ? TSX_HIP_ENOMEM : TSX_HIP_EHIP;
+}
 
 static const int SCAN_WG_PER_CU = 5;  // walk_log_kernel workgroups per CU
 static const uint32_t OVQ_CAP = 2048;  // keys per overflow queue (one queue per level-2 workgroup: 32 MiB at 2048 workgroups)
 static const size_t STAGE_PIECE_DEFAULT = (size_t)64 << 20;  // bytes of FASTQ per host piece
 
-struct PartPlan;
-struct tsx_hip_map;
-static void drop_sh_plan(tsx_hip_map *m);
+struct PartPlan {
+    int g;                       // regions of the key log (= scan waves, or cuts of a received array)
+    int rw;                      // 64-bit words per record
+    uint64_t log_cap;            // records per log region
+    int b1, b2;                  // radix bits of level 1 / level 2 (b2 == 0: one level)
+    uint32_t nb1, nb2, nseg, cpr2;
+    uint64_t cap_sub;            // records per level-2 sub-list
+    uint32_t hist_nb;            // bins of the scan-side histogram (nb1, or #owners for a sharded scan)
+    unsigned long long *c_log, *c_rstart, *c_bstart, *c_bcnt, *c_seg, *d_offs;
+    uint32_t *d_hist;
+    size_t cnt_need;
+    // walk fused with level 1 (walk_part_kernel): G1 workgroups, each with a sub-list of cap1 records per level-1
+    // bucket in buffer 1 (list (b, g) at (b * G1 + g) * cap1), sizes in c_l1[b * G1 + g]
+    bool fused;
+    uint32_t G1;
+    uint64_t cap1;
+    unsigned long long *c_l1;
+    uint64_t *buf1;              // buffer 1 of this plan (the map's, or the window-wise sharded level 1's own)
+};
+
+// Ownership (tsx_own.h): every device buffer, pinned buffer, event and stream of a map is a member that releases
+// itself -- adding one is adding a member, nothing else.  The capacities are the owners' (bytes).  TableParams only
+// borrows: it goes to the kernels by value, so `p` holds copies of get().
 struct tsx_hip_map {
     TableParams p{};
     tsx_hip_layout lay{};
     int device = 0;
     uint64_t seed = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;                       // declared in front of every buffer: it outlives them
+    Stream copy_stream;                  // H2D copies of the host entry point
     // bijective mapping, host copy: rows[i] yields output bit n-1-i
     std::vector<uint64_t> rows, irows;   // n x wk
     std::vector<uint64_t> lut, ilut;     // [groups][1<<g][wk]
-    uint64_t *d_lut = nullptr, *d_ilut = nullptr, *d_roll = nullptr;
-    uint64_t *d_ovq = nullptr;           // overflow queues of the level-2 partition (OVQ_CAP records per workgroup)
-    uint64_t *d_def_rec = nullptr, *d_def_cnt = nullptr;   // deferred list (DeferList, tsx_device.h)
-    unsigned long long *d_def_n = nullptr;
-    size_t def_cap = 0;
+    DevBuf<uint64_t> table, sec_keys, sec_cnt;   // what p.table, p.sec_keys, p.sec_cnt, p.stats, p.seg_dirty, p.lut,
+    DevBuf<unsigned long long> stats;            // p.ilut and p.roll point to
+    DevBuf<uint8_t> seg_dirty;
+    DevBuf<uint64_t> d_lut, d_ilut, d_roll;
+    DevBuf<uint64_t> d_ovq;              // overflow queues of the level-2 partition (OVQ_CAP records per workgroup)
+    DevBuf<uint64_t> d_def_rec, d_def_cnt;   // deferred list (DeferList, tsx_device.h)
+    DevBuf<unsigned long long> d_def_n;
+    uint64_t def_cap() const { return d_def_cnt.cap() / 8; }   // its records
+    DeferList defer() const { return DeferList{d_def_rec.get(), d_def_cnt.get(), d_def_n.get(), def_cap()}; }
     bool fresh = false;                  // tsx_hip_clear() was called and the table itself has not been zeroed yet:
                                          // the next partitioned build writes every segment, anything else zeroes first
-    uint32_t *d_ovq_cnt = nullptr;
-    size_t ovq_queues = 0;
+    DevBuf<uint32_t> d_ovq_cnt;
     uint64_t roll[64] = {0};             // one-limb keys: sliding-window hash update table
     std::vector<uint64_t> roll_wide;     // multi-limb keys: the same, key_limbs words per entry
     uint64_t mroll[64] = {0};            // the mirror roll of the reverse complement's hash (canonical walks)
     std::vector<uint64_t> mroll_wide;
     bool canon = false;                  // canonical counting (tsx_hip_set_canonical)
     uint32_t minq = 0;                   // base rule (tsx_hip_set_base_rule): min_qual_char, 0 = off; acgt_only is p.acgt_only
-    uint16_t *d_qmap = nullptr; size_t qmap_bytes = 0;             // its low-quality bitmap (tsx_baserule.h)
+    DevBuf<uint16_t> d_qmap;             // its low-quality bitmap (tsx_baserule.h)
     const uint16_t *qmap_cur = nullptr;  // the bitmap at the text the next scan launches read (set per call, else null)
-    unsigned long long *d_qrec = nullptr; size_t qrec_bytes = 0;   // line spans per record behind it, and record cuts
+    DevBuf<unsigned long long> d_qrec;   // line spans per record behind it, and record cuts
     bool used = false;                   // something was inserted since the map was created or cleared
     // FASTQ scratch
-    uint32_t *d_tile = nullptr; uint64_t tile_cap = 0;
-    uint32_t *d_carry = nullptr;
-    unsigned long long *d_seg = nullptr;  // 64 owner counters / cursors
+    DevBuf<uint32_t> d_tile;             // tile counts, then one partial sum per SCAN_CHUNK tiles
+    uint64_t tile_cap = 0;               // tiles it has room for: where the partial sums start (ensure_tiles)
+    DevBuf<uint32_t> d_carry;
+    DevBuf<unsigned long long> d_seg;    // 64 owner counters / cursors
     // host staging
-    uint8_t *h_stage[2] = {nullptr, nullptr};
-    uint8_t *d_stage[2] = {nullptr, nullptr};
-    hipEvent_t stage_done[2] = {nullptr, nullptr};   // kernels that read d_stage[i] have finished
-    hipEvent_t stage_in[2] = {nullptr, nullptr};     // the H2D copy into d_stage[i] has finished
-    hipStream_t copy_stream = nullptr;               // H2D copies of the host entry point
-    size_t stage_bytes = 0;
+    PinBuf<uint8_t> h_stage[2];
+    DevBuf<uint8_t> d_stage[2];
+    Event stage_done[2];                 // kernels that read d_stage[i] have finished
+    Event stage_in[2];                   // the H2D copy into d_stage[i] has finished
     size_t piece = STAGE_PIECE_DEFAULT;  // TSX_HIP_PIECE_BYTES overrides (tests exercise piece seams)
     bool piece_fixed = false;
     int cus = 256;
     // partitioned insert path (tsx_partition.h): grow-only scratch
     int path = 0;                    // 0 auto, 1 atomic, 2 partitioned (tsx_hip_set_path / TSX_HIP_PATH)
-    uint64_t *d_buf[2] = {nullptr, nullptr};
-    size_t buf_bytes[2] = {0, 0};
-    unsigned long long *d_cnt = nullptr;   // [log regions | level-1 lists | segment lists]
-    size_t cnt_entries = 0;
+    DevBuf<uint64_t> d_buf[2];
+    DevBuf<unsigned long long> d_cnt;      // [log regions | level-1 lists | segment lists]
     // optional per-pass timing (HIP events on the launch stream)
-    uint64_t *d_small = nullptr;     // scratch of tsx_hip_get_counts_host / tsx_hip_lookup_host for a few k-mers
+    DevBuf<uint64_t> d_small;        // scratch of tsx_hip_get_counts_host / tsx_hip_lookup_host for a few k-mers
     bool attr_done = false;          // dynamic-LDS limits of the partition / build kernels set on this map's device
     int timing = 0;
-    std::vector<hipEvent_t> ev;      // seven per piece: before pass 1, before pass 3, after pass 3, start of the
+    std::vector<Event> ev;           // eight per piece: before pass 1, before pass 3, after pass 3, start of the
                                      // partition phase (later than the scan's end only in a sharded run: the
-                                     // exchange lies between), after level 1, level 2, build
+                                     // exchange lies between), after level 1, level 2, build, the inserts behind it
     std::vector<unsigned long long> h_regions;   // host copy of the region table of a sharded build (starts, then sizes)
-    PartPlan *sh_pl = nullptr;                   // sharded run, level 1 per exchange window: the plan made at window 0,
+    std::unique_ptr<PartPlan> sh_pl;             // sharded run, level 1 per exchange window: the plan made at window 0,
     uint32_t sh_rw = 0, sh_windows = 0;          // regions per window, windows of the step,
     uint32_t mz_regions = 0; uint64_t mz_dcap = 0; size_t mz_len = 0;   // minimizer exchange: the described text waiting in buffer 1 (regions x capacity; its bytes)
     bool sh_ev3 = false;                         // stage timing: the walks of a description exchange have recorded event 3
-    unsigned long long *d_desc_cnt = nullptr;    // strips described per wave of strip_desc_kernel (key log form)
-    size_t desc_cnt_entries = 0;
-    uint64_t *sh_buf1 = nullptr;                 // and its own sub-list buffer and counters (the scans of the later
-    size_t sh_buf1_bytes = 0;                    // windows plan with -- and clear -- the map's while level 1 of the
-    unsigned long long *sh_cnt = nullptr;        // earlier ones has already left its sizes there)
-    size_t sh_cnt_entries = 0;
+    DevBuf<unsigned long long> d_desc_cnt;       // strips described per wave of strip_desc_kernel (key log form)
+    DevBuf<uint64_t> sh_buf1;                    // and its own sub-list buffer and counters (the scans of the later
+    DevBuf<unsigned long long> sh_cnt;           // windows plan with -- and clear -- the map's while level 1 of the
+                                                 // earlier ones has already left its sizes there)
     std::deque<long> ev_open;        // tuples of shard scans whose partition phase has not run yet (oldest first)
     size_t ev_used = 0;
     // Ordering between the map's own stream and a caller's stream (the `stream` argument of the *_device entry
     // points): tsx_hip_clear works on the map's stream and records clear_ev behind it; every entry point that
     // launches on a caller's stream waits for that event first.  The other way round, the last caller's stream
     // is remembered (`foreign`) and tsx_hip_clear / tsx_hip_sync order themselves behind what was queued there.
-    uint8_t *d_slabdesc = nullptr;      // count_slabs: the descriptions of every text window, then one counter per window
-    size_t slabdesc_bytes = 0;
+    DevBuf<uint8_t> d_slabdesc;         // count_slabs: the descriptions of every text window, then one counter per window
     // wrapped FASTA (tsx_fasta.h): the two-line text of one piece, the scan scratch, the carry between pieces
-    uint8_t *d_fa_out = nullptr; size_t fa_out_bytes = 0;
-    uint32_t *d_fa_ws = nullptr; size_t fa_ws_bytes = 0;
-    uint32_t *d_fa_carry = nullptr;
-    hipEvent_t clear_ev = nullptr, join_ev = nullptr;
+    DevBuf<uint8_t> d_fa_out;
+    DevBuf<uint32_t> d_fa_ws;
+    DevBuf<uint32_t> d_fa_carry;
+    Event clear_ev, join_ev;
     bool clear_ev_set = false;
-    hipStream_t foreign = nullptr;
+    hipStream_t foreign = nullptr;       // (a caller's: not owned)
+    // A map without a stream never touched the device (db_source_params builds one for its host fields).
+    ~tsx_hip_map() {
+        if (!stream.get()) return;
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream.get());
+    }
 };
 
 static const size_t STAGE_PAD = 256;
@@ -497,12 +534,12 @@ extern "C" int tsx_hip_create_shard(tsx_hip_map **out, int k, int l, int storage
                                     uint64_t hash_seed, int device, int shard_bits, int shard_index) {
     if (!out) return TSX_HIP_EINVAL;
     *out = nullptr;
-    tsx_hip_map *m = new tsx_hip_map();
+    std::unique_ptr<tsx_hip_map> owner(new tsx_hip_map());   // released into *out on success
+    tsx_hip_map *m = owner.get();
     int rc = derive_layout(m, k, l, storagebits, overflow_l, shard_bits, shard_index);
-    if (rc != TSX_HIP_OK) { delete m; return rc; }
+    if (rc != TSX_HIP_OK) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        delete m;
         g_last_error = "no HIP device (the HIP path has no CPU fallback)";
         return TSX_HIP_ENODEVICE;
     }
@@ -512,45 +549,38 @@ extern "C" int tsx_hip_create_shard(tsx_hip_map **out, int k, int l, int storage
         const long long v = atoll(e);
         if (v >= 256) { m->piece = ((size_t)v + 15) & ~(size_t)15; m->piece_fixed = true; }
     }
-    auto fail = [&](int code) { tsx_hip_destroy(m); return code; };
-#define HIP_TRY_C(expr)                                                         \
-    do {                                                                        \
-        hipError_t _e = (expr);                                                 \
-        if (_e != hipSuccess) {                                                 \
-            g_last_error = std::string(#expr) + ": " + hipGetErrorString(_e);   \
-            return fail(_e == hipErrorOutOfMemory ? TSX_HIP_ENOMEM : TSX_HIP_EHIP); \
-        }                                                                       \
-    } while (0)
     // Host pieces large enough for the partitioned path to pay off (text >= table / 32),
     // between 64 MiB and 1 GiB of pinned staging per buffer.
     if (!m->piece_fixed) {
         const size_t want = (size_t)(m->lay.table_bytes / 16);
         m->piece = std::min<size_t>((size_t)1 << 30, std::max<size_t>(STAGE_PIECE_DEFAULT, want)) & ~(size_t)4095;
     }
-    HIP_TRY_C(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     hipDeviceProp_t prop;
-    HIP_TRY_C(hipGetDeviceProperties(&prop, device));
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
     m->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    HIP_TRY_C(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-    HIP_TRY_C(hipEventCreateWithFlags(&m->clear_ev, hipEventDisableTiming));
-    HIP_TRY_C(hipEventCreateWithFlags(&m->join_ev, hipEventDisableTiming));
+    TSX_TRY(m->stream.create());
+    TSX_TRY(m->clear_ev.create());
+    TSX_TRY(m->join_ev.create());
     TableParams &p = m->p;
-    HIP_TRY_C(hipMalloc((void **)&p.table, m->lay.table_bytes));
-    HIP_TRY_C(hipMalloc((void **)&p.sec_keys, (p.sec_mask + 1) * 8));
-    HIP_TRY_C(hipMalloc((void **)&p.sec_cnt, (p.sec_mask + 1) * 8));
-    HIP_TRY_C(hipMalloc((void **)&p.stats, ST_N * sizeof(unsigned long long)));
-    HIP_TRY_C(hipMalloc((void **)&p.seg_dirty, (size_t)(m->lay.slots >> p.S)));
-    HIP_TRY_C(hipMalloc((void **)&m->d_carry, 64));
-    HIP_TRY_C(hipMalloc((void **)&m->d_seg, 64 * sizeof(unsigned long long)));
+    TSX_TRY(m->table.alloc(m->lay.table_bytes));
+    TSX_TRY(m->sec_keys.alloc((p.sec_mask + 1) * 8));
+    TSX_TRY(m->sec_cnt.alloc((p.sec_mask + 1) * 8));
+    TSX_TRY(m->stats.alloc(ST_N * sizeof(unsigned long long)));
+    TSX_TRY(m->seg_dirty.alloc((size_t)(m->lay.slots >> p.S)));
+    p.table = m->table.get(); p.sec_keys = m->sec_keys.get(); p.sec_cnt = m->sec_cnt.get();
+    p.stats = m->stats.get(); p.seg_dirty = m->seg_dirty.get();
+    TSX_TRY(m->d_carry.alloc(64));
+    TSX_TRY(m->d_seg.alloc(64 * sizeof(unsigned long long)));
     rc = make_mapping(m);
-    if (rc != TSX_HIP_OK) return fail(rc);
+    if (rc != TSX_HIP_OK) return rc;
     make_lut(m, m->rows, m->lut);
     make_lut(m, m->irows, m->ilut);
-    HIP_TRY_C(hipMalloc((void **)&m->d_lut, m->lut.size() * 8));
-    HIP_TRY_C(hipMalloc((void **)&m->d_ilut, m->ilut.size() * 8));
-    HIP_TRY_C(hipMemcpy(m->d_lut, m->lut.data(), m->lut.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY_C(hipMemcpy(m->d_ilut, m->ilut.data(), m->ilut.size() * 8, hipMemcpyHostToDevice));
-    p.lut = m->d_lut; p.ilut = m->d_ilut; p.roll = nullptr;
+    TSX_TRY(m->d_lut.alloc(m->lut.size() * 8));
+    TSX_TRY(m->d_ilut.alloc(m->ilut.size() * 8));
+    HIP_TRY(hipMemcpy(m->d_lut.get(), m->lut.data(), m->lut.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(m->d_ilut.get(), m->ilut.data(), m->ilut.size() * 8, hipMemcpyHostToDevice));
+    p.lut = m->d_lut.get(); p.ilut = m->d_ilut.get(); p.roll = nullptr;
     {
         const void *src = (p.wk == 1) ? (const void *)m->roll : (const void *)m->roll_wide.data();
         const size_t bytes = (size_t)64 * p.wk * 8;
@@ -568,47 +598,20 @@ extern "C" int tsx_hip_create_shard(tsx_hip_map **out, int k, int l, int storage
         }
         // the mirror roll of the canonical walks behind both (MROLL1_AT / 64 * key_limbs words in, tsx_device.h)
         const void *msrc = (p.wk == 1) ? (const void *)m->mroll : (const void *)m->mroll_wide.data();
-        HIP_TRY_C(hipMalloc((void **)&m->d_roll, 2 * bytes + lut4.size() * 8));
-        HIP_TRY_C(hipMemcpy(m->d_roll, src, bytes, hipMemcpyHostToDevice));
+        TSX_TRY(m->d_roll.alloc(2 * bytes + lut4.size() * 8));
+        HIP_TRY(hipMemcpy(m->d_roll.get(), src, bytes, hipMemcpyHostToDevice));
         if (!lut4.empty())
-            HIP_TRY_C(hipMemcpy(m->d_roll + 64, lut4.data(), lut4.size() * 8, hipMemcpyHostToDevice));
-        HIP_TRY_C(hipMemcpy(m->d_roll + 64 * p.wk + lut4.size(), msrc, bytes, hipMemcpyHostToDevice));
-        p.roll = m->d_roll;
+            HIP_TRY(hipMemcpy(m->d_roll.get() + 64, lut4.data(), lut4.size() * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(m->d_roll.get() + 64 * p.wk + lut4.size(), msrc, bytes, hipMemcpyHostToDevice));
+        p.roll = m->d_roll.get();
     }
     rc = clear_impl(m, true);
-    if (rc != TSX_HIP_OK) return fail(rc);
-    *out = m;
+    if (rc != TSX_HIP_OK) return rc;
+    *out = owner.release();
     return TSX_HIP_OK;
-#undef HIP_TRY_C
 }
 
-extern "C" void tsx_hip_destroy(tsx_hip_map *m) {
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    (void)hipFree(m->p.table); (void)hipFree(m->p.sec_keys); (void)hipFree(m->p.sec_cnt);
-    drop_sh_plan(m);
-    (void)hipFree(m->sh_buf1); (void)hipFree(m->sh_cnt); (void)hipFree(m->d_desc_cnt); (void)hipFree(m->d_slabdesc);
-    (void)hipFree(m->p.stats); (void)hipFree(m->d_lut); (void)hipFree(m->d_ilut); (void)hipFree(m->d_roll);
-    (void)hipFree(m->d_ovq); (void)hipFree(m->d_ovq_cnt); (void)hipFree(m->d_small);
-    (void)hipFree(m->d_def_rec); (void)hipFree(m->d_def_cnt); (void)hipFree(m->d_def_n);
-    (void)hipFree(m->d_tile); (void)hipFree(m->d_carry); (void)hipFree(m->d_seg);
-    (void)hipFree(m->d_qmap); (void)hipFree(m->d_qrec);
-    (void)hipFree(m->d_fa_out); (void)hipFree(m->d_fa_ws); (void)hipFree(m->d_fa_carry);
-    (void)hipFree(m->p.seg_dirty); (void)hipFree(m->d_buf[0]); (void)hipFree(m->d_buf[1]); (void)hipFree(m->d_cnt);
-    for (int i = 0; i < 2; ++i) {
-        if (m->h_stage[i]) (void)hipHostFree(m->h_stage[i]);
-        if (m->d_stage[i]) (void)hipFree(m->d_stage[i]);
-        if (m->stage_done[i]) (void)hipEventDestroy(m->stage_done[i]);
-        if (m->stage_in[i]) (void)hipEventDestroy(m->stage_in[i]);
-    }
-    if (m->copy_stream) (void)hipStreamDestroy(m->copy_stream);
-    for (hipEvent_t e : m->ev) (void)hipEventDestroy(e);
-    if (m->clear_ev) (void)hipEventDestroy(m->clear_ev);
-    if (m->join_ev) (void)hipEventDestroy(m->join_ev);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
-    delete m;
-}
+extern "C" void tsx_hip_destroy(tsx_hip_map *m) { delete m; }
 
 extern "C" int tsx_hip_get_layout(const tsx_hip_map *m, tsx_hip_layout *out) {
     if (!m || !out) return TSX_HIP_EINVAL;
@@ -633,16 +636,16 @@ static int clear_impl(tsx_hip_map *m, bool full) {
     HIP_TRY(hipSetDevice(m->device));
     join_foreign(m, false);
     if (full || !can_partition(m)) {
-        HIP_TRY(hipMemsetAsync(m->p.table, 0, m->lay.table_bytes, m->stream));
+        HIP_TRY(hipMemsetAsync(m->p.table, 0, m->lay.table_bytes, m->stream.get()));
         m->fresh = false;
     } else {
         m->fresh = true;
     }
-    hipLaunchKernelGGL(sec_clear_kernel, dim3(m->cus * 4), dim3(NT), 0, m->stream, m->p, full ? 1 : 0);
+    hipLaunchKernelGGL(sec_clear_kernel, dim3(m->cus * 4), dim3(NT), 0, m->stream.get(), m->p, full ? 1 : 0);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(m->p.stats, 0, ST_N * sizeof(unsigned long long), m->stream));
-    HIP_TRY(hipMemsetAsync(m->p.seg_dirty, 0, (size_t)(m->lay.slots >> m->p.S), m->stream));
-    HIP_TRY(hipEventRecord(m->clear_ev, m->stream));
+    HIP_TRY(hipMemsetAsync(m->p.stats, 0, ST_N * sizeof(unsigned long long), m->stream.get()));
+    HIP_TRY(hipMemsetAsync(m->p.seg_dirty, 0, (size_t)(m->lay.slots >> m->p.S), m->stream.get()));
+    HIP_TRY(hipEventRecord(m->clear_ev.get(), m->stream.get()));
     m->clear_ev_set = true;
     m->used = false;   // (the counting mode stays)
     return TSX_HIP_OK;
@@ -717,8 +720,8 @@ extern "C" int tsx_hip_canonical_host(int k, const uint64_t *kmers, size_t n, ui
 }
 
 static int read_stats(tsx_hip_map *m, unsigned long long *st) {
-    HIP_TRY(hipMemcpyAsync(st, m->p.stats, ST_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream));
-    HIP_TRY(hipStreamSynchronize(m->stream));
+    HIP_TRY(hipMemcpyAsync(st, m->p.stats, ST_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, m->stream.get()));
+    HIP_TRY(hipStreamSynchronize(m->stream.get()));
     return TSX_HIP_OK;
 }
 
@@ -736,9 +739,9 @@ extern "C" int tsx_hip_sync(tsx_hip_map *m) {
 }
 
 static inline hipStream_t pick_stream(tsx_hip_map *m, void *stream) {
-    hipStream_t st = stream ? (hipStream_t)stream : m->stream;
-    if (st != m->stream) {
-        if (m->clear_ev_set) (void)hipStreamWaitEvent(st, m->clear_ev, 0);   // behind the last tsx_hip_clear
+    hipStream_t st = stream ? (hipStream_t)stream : m->stream.get();
+    if (st != m->stream.get()) {
+        if (m->clear_ev_set) (void)hipStreamWaitEvent(st, m->clear_ev.get(), 0);   // behind the last tsx_hip_clear
         m->foreign = st;
     }
     return st;
@@ -749,8 +752,8 @@ static inline void join_foreign(tsx_hip_map *m, bool host_wait) {
     if (host_wait) {
         (void)hipStreamSynchronize(m->foreign);
         m->foreign = nullptr;
-    } else if (m->join_ev && hipEventRecord(m->join_ev, m->foreign) == hipSuccess) {
-        (void)hipStreamWaitEvent(m->stream, m->join_ev, 0);
+    } else if (m->join_ev.get() && hipEventRecord(m->join_ev.get(), m->foreign) == hipSuccess) {
+        (void)hipStreamWaitEvent(m->stream.get(), m->join_ev.get(), 0);
     }
 }
 static inline int grid_for(const tsx_hip_map *m, uint64_t work_items, int per_cu) {
@@ -774,28 +777,6 @@ static inline int grid_for(const tsx_hip_map *m, uint64_t work_items, int per_cu
     if ((m)->p.acgt_only || (m)->qmap_cur) { constexpr bool BRV = true; CALL; } else { constexpr bool BRV = false; CALL; }
 
 // ---- partitioned path: plan, scratch, launches ------------------------------------
-struct PartPlan {
-    int g;                       // regions of the key log (= scan waves, or cuts of a received array)
-    int rw;                      // 64-bit words per record
-    uint64_t log_cap;            // records per log region
-    int b1, b2;                  // radix bits of level 1 / level 2 (b2 == 0: one level)
-    uint32_t nb1, nb2, nseg, cpr2;
-    uint64_t cap_sub;            // records per level-2 sub-list
-    uint32_t hist_nb;            // bins of the scan-side histogram (nb1, or #owners for a sharded scan)
-    unsigned long long *c_log, *c_rstart, *c_bstart, *c_bcnt, *c_seg, *d_offs;
-    uint32_t *d_hist;
-    size_t cnt_need;
-    // walk fused with level 1 (walk_part_kernel): G1 workgroups, each with a sub-list of cap1 records per level-1
-    // bucket in buffer 1 (list (b, g) at (b * G1 + g) * cap1), sizes in c_l1[b * G1 + g]
-    bool fused;
-    uint32_t G1;
-    uint64_t cap1;
-    unsigned long long *c_l1;
-    uint64_t *buf1;              // buffer 1 of this plan (the map's, or the window-wise sharded level 1's own)
-};
-
-static void drop_sh_plan(tsx_hip_map *m) { delete m->sh_pl; m->sh_pl = nullptr; }
-
 static inline int rec_words(int wk) { return wk == 3 ? 4 : wk; }
 
 // Two radix levels of at most 512 lists reach 2^18 segments (2^32 one-limb slots).  A larger table of one-limb keys and
@@ -830,36 +811,24 @@ static uint32_t level2_cpr(const tsx_hip_map *m) {
     return c;
 }
 
-template <typename T>
-static int grow(hipStream_t st, T *&ptr, size_t &have, size_t need) {
-    if (need <= have) return TSX_HIP_OK;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (ptr) HIP_TRY(hipFree(ptr));
-    ptr = nullptr; have = 0;
-    HIP_TRY(hipMalloc((void **)&ptr, need + need / 8 + 4096));
-    have = need + need / 8 + 4096;
-    return TSX_HIP_OK;
-}
+// Grow-only scratch: room for `need` bytes, an eighth + 4 KiB more when it has to be allocated anew.
+template <typename B>
+static int grow(hipStream_t st, B &buf, size_t need) { return buf.reserve(&st, need, need + need / 8 + 4096); }
 
 // The deferred list of the map (local runs): room for every record of the pass in the worst case (skewed
 // input whose keys all spill); only what is appended is ever touched.
 static int ensure_deferred(tsx_hip_map *m, uint64_t maxrec, hipStream_t st) {
     const int rw = rec_words(m->p.wk);
-    if (!m->d_def_n) HIP_TRY(hipMalloc((void **)&m->d_def_n, 64));
+    if (!m->d_def_n.get()) TSX_TRY(m->d_def_n.alloc(64));
     // (passes of billions of records: room for 2^28 of them -- what lands here is hot keys with their totals and the
     // spill of skewed lists; beyond the capacity records count as insert failures, reported by tsx_hip_sync)
     if (maxrec > ((uint64_t)1 << 30)) maxrec = std::max<uint64_t>((uint64_t)1 << 28, maxrec / 16);
-    if (maxrec > m->def_cap) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (m->d_def_rec) HIP_TRY(hipFree(m->d_def_rec));
-        if (m->d_def_cnt) HIP_TRY(hipFree(m->d_def_cnt));
-        m->d_def_rec = m->d_def_cnt = nullptr; m->def_cap = 0;
-        const size_t cap = maxrec + maxrec / 8 + 4096;
-        HIP_TRY(hipMalloc((void **)&m->d_def_rec, cap * rw * 8));
-        HIP_TRY(hipMalloc((void **)&m->d_def_cnt, cap * 8));
-        m->def_cap = cap;
-    }
-    return TSX_HIP_OK;
+    if (maxrec <= m->def_cap()) return TSX_HIP_OK;
+    const size_t cap = maxrec + maxrec / 8 + 4096;
+    int rc = m->d_def_rec.reserve(&st, (size_t)maxrec * rw * 8, cap * rw * 8);   // (waits before it frees)
+    if (rc == TSX_HIP_OK) rc = m->d_def_cnt.alloc(cap * 8);
+    if (rc != TSX_HIP_OK) { m->d_def_rec.reset(); m->d_def_cnt.reset(); }   // both or none
+    return rc;
 }
 
 // maxrec: upper bound of records; g: number of source regions; own_log: the records come from
@@ -900,28 +869,22 @@ static int plan_partition(tsx_hip_map *m, uint64_t maxrec, int g, bool own_log, 
     const uint64_t rec_cap = pl.fused ? 0 : (own_log ? (uint64_t)g * pl.log_cap : maxrec);
     const size_t need0 = std::max<uint64_t>(own_log ? rec_cap : 0, pl.b2 ? (uint64_t)pl.nseg * pl.cpr2 * pl.cap_sub : 0) * 8 * pl.rw;
     const size_t need1 = (pl.fused ? (uint64_t)pl.nb1 * pl.G1 * pl.cap1 : rec_cap) * 8 * pl.rw;
-    int rc = grow(st, m->d_buf[0], m->buf_bytes[0], need0);
-    if (rc != TSX_HIP_OK) return rc;
-    rc = grow(st, m->d_buf[1], m->buf_bytes[1], need1);
-    if (rc != TSX_HIP_OK) return rc;
-    pl.buf1 = m->d_buf[1];
+    TSX_TRY(grow(st, m->d_buf[0], need0));
+    TSX_TRY(grow(st, m->d_buf[1], need1));
+    pl.buf1 = m->d_buf[1].get();
     // counters: [region fill | region start | bucket start | bucket size | sub-list size], then the
     // histogram matrix (u32) and its exclusive scan (u64), both max(nb1, hist_nb) x g
     const uint32_t hb = std::max(pl.nb1, pl.hist_nb);
     pl.cnt_need = 2 * (size_t)g + 2 * (size_t)hb + (size_t)pl.nseg * pl.cpr2 + (size_t)pl.nb1 * pl.G1;
     const size_t mat = (size_t)hb * g;
-    size_t have = m->cnt_entries;
-    unsigned long long *ptr = m->d_cnt;
-    rc = grow(st, ptr, have, pl.cnt_need * 8 + mat * 12 + 64);
-    m->d_cnt = ptr; m->cnt_entries = have;
-    if (rc != TSX_HIP_OK) return rc;
-    pl.c_log = m->d_cnt;                    // fill of each log region, or size of each cut of a received array
+    TSX_TRY(grow(st, m->d_cnt, pl.cnt_need * 8 + mat * 12 + 64));
+    pl.c_log = m->d_cnt.get();                    // fill of each log region, or size of each cut of a received array
     pl.c_rstart = pl.c_log + g;
     pl.c_bstart = pl.c_rstart + g; pl.c_bcnt = pl.c_bstart + hb; pl.c_seg = pl.c_bcnt + hb;
     pl.c_l1 = pl.c_seg + (size_t)pl.nseg * pl.cpr2;
     pl.d_offs = pl.c_l1 + (size_t)pl.nb1 * pl.G1;
     pl.d_hist = reinterpret_cast<uint32_t *>(pl.d_offs + mat);
-    HIP_TRY(hipMemsetAsync(m->d_cnt, 0, pl.cnt_need * 8, st));
+    HIP_TRY(hipMemsetAsync(m->d_cnt.get(), 0, pl.cnt_need * 8, st));
     if (!m->attr_done) {   // per map, hence per device: the attribute belongs to the device's copy of the kernel
         const int big = 150 << 10, seg = 128 << 10;
         HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
@@ -955,18 +918,25 @@ static int plan_partition(tsx_hip_map *m, uint64_t maxrec, int g, bool own_log, 
     return TSX_HIP_OK;
 }
 
+// The window-wise level 1 of a sharded run plans with its own sub-list buffer and counters in the map's place.
+static int plan_sharded_l1(tsx_hip_map *m, uint64_t maxrec, int g1, hipStream_t st, PartPlan &pl) {
+    std::swap(m->d_buf[1], m->sh_buf1); std::swap(m->d_cnt, m->sh_cnt);
+    const int rc = plan_partition(m, maxrec, g1, false, 0, st, pl, g1);
+    std::swap(m->d_buf[1], m->sh_buf1); std::swap(m->d_cnt, m->sh_cnt);
+    return rc;
+}
+
 // Overflow queues (OVQ_CAP records each): one per level-2 workgroup, plus one per workgroup of the fused scan.
 static int ensure_ovq(tsx_hip_map *m, size_t nq, int rw, hipStream_t st) {
-    if (nq * rw <= m->ovq_queues) return TSX_HIP_OK;
-    HIP_TRY(hipStreamSynchronize(st));
-    if (m->d_ovq) HIP_TRY(hipFree(m->d_ovq));
-    if (m->d_ovq_cnt) HIP_TRY(hipFree(m->d_ovq_cnt));
-    m->d_ovq = nullptr; m->d_ovq_cnt = nullptr; m->ovq_queues = 0;
-    HIP_TRY(hipMalloc((void **)&m->d_ovq, nq * OVQ_CAP * 8 * rw));
-    HIP_TRY(hipMalloc((void **)&m->d_ovq_cnt, nq * 4 + 512 * 4 + 64));   // (+ the skew flags of level 2, one per bucket, behind the counters)
-    m->ovq_queues = nq * rw;
-    return TSX_HIP_OK;
+    const size_t bytes = nq * OVQ_CAP * 8 * rw;
+    if (bytes <= m->d_ovq.cap()) return TSX_HIP_OK;
+    int rc = m->d_ovq.reserve(&st, bytes, bytes);   // (waits before it frees)
+    if (rc == TSX_HIP_OK) rc = m->d_ovq_cnt.alloc(nq * 4 + 512 * 4 + 64);   // (+ the skew flags of level 2, one per bucket, behind the counters)
+    if (rc != TSX_HIP_OK) { m->d_ovq.reset(); m->d_ovq_cnt.reset(); }   // both or none
+    return rc;
 }
+// queues of a map whose records are rw words wide (the skew flags lie behind their counters)
+static inline size_t ovq_queues(const tsx_hip_map *m, int rw) { return m->d_ovq.cap() / ((size_t)OVQ_CAP * 8 * rw); }
 
 // Launch with the record width as a compile-time constant.
 #define DISPATCH_RW(rw, CALL)                        \
@@ -983,10 +953,10 @@ static int ensure_ovq(tsx_hip_map *m, size_t nq, int rw, hipStream_t st) {
 // counter before the first kernel that may append to it.
 static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_t *src,
                                const unsigned long long *region_start, uint64_t src_cap, hipStream_t st,
-                               hipEvent_t *ev = nullptr) {
+                               Event *ev = nullptr) {
     TableParams pp = m->p;
     const TableParams &p = m->p;
-    pp.defer = DeferList{m->d_def_rec, m->d_def_cnt, m->d_def_n, (uint64_t)m->def_cap};
+    pp.defer = m->defer();
     const int rw = pl.rw;
     // ring depth in words: PART_FLUSH-1 words may stay behind a flush, plus one batch of arrivals (mean = batch / nb)
     auto ring_bits = [](uint32_t nb) {
@@ -1016,7 +986,7 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
         HIP_TRY(hipGetLastError());
     }
     }   // (fused: walk_part_kernel has left the level-1 sub-lists in buffer 1)
-    if (ev) HIP_TRY(hipEventRecord(ev[4], st));
+    if (ev) HIP_TRY(hipEventRecord(ev[4].get(), st));
     const uint64_t *lists = pl.buf1;
     const unsigned long long *lists_start = pl.c_bstart, *lists_cnt = pl.c_bcnt;
     uint64_t lists_cap = 0;
@@ -1032,7 +1002,7 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
         // quarter of the list shared out over the workgroups, a power of two in 64 .. 4096; 0: the list is too small
         uint32_t dch = 0;
         for (uint32_t c = 4096; c >= 64 && !dch; c >>= 1)
-            if ((uint64_t)c * nq2 * 4 <= (uint64_t)m->def_cap) dch = c;
+            if ((uint64_t)c * nq2 * 4 <= m->def_cap()) dch = c;
         {
             const int rco = ensure_ovq(m, (size_t)nq2 + pl.G1, rw, st);
             if (rco != TSX_HIP_OK) return rco;
@@ -1040,7 +1010,7 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
         // Which form of the level-2 kernel works (partition_ring_kernel: SKEW) is decided on the device: skew_probe_kernel
         // samples every bucket and raises the flag -- the last word of the overflow-queue counters -- when it finds a hot
         // key; both forms are launched, per bucket one of them returns at once.
-        uint32_t *d_skew = m->d_ovq_cnt + m->ovq_queues / rw;   // (ensure_ovq keeps one spare counter behind the queues')
+        uint32_t *d_skew = m->d_ovq_cnt.get() + ovq_queues(m, rw);   // (ensure_ovq keeps one spare counter behind the queues')
         DISPATCH_RW(rw, hipLaunchKernelGGL((skew_probe_kernel<RWV>), dim3(pl.nb1), dim3(256), 0, st, (const uint64_t *)pl.buf1,
                                            (const unsigned long long *)pl.c_bstart, (const unsigned long long *)pl.c_bcnt,
                                            (const unsigned long long *)(pl.fused ? pl.c_l1 : nullptr), pl.G1, pl.cap1, d_skew));
@@ -1048,9 +1018,9 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
 #define TSX_LEVEL2(RWV, NTV, SK, BITS)                                                                                          \
         hipLaunchKernelGGL((partition_ring_kernel<RWV, NTV, SK>), dim3(pl.nb1 * pl.cpr2), dim3(NTV), part_lds(pl.nb2, BITS), st,  \
                            pp, (const uint64_t *)pl.buf1, (const unsigned long long *)pl.c_bstart,                              \
-                           (const unsigned long long *)pl.c_bcnt, (uint64_t)0, pl.nb1, pl.cpr2, m->d_buf[0],                    \
+                           (const unsigned long long *)pl.c_bcnt, (uint64_t)0, pl.nb1, pl.cpr2, m->d_buf[0].get(),                    \
                            (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, pl.c_seg, pl.cap_sub,      \
-                           pl.nb2, (uint32_t)p.S, BITS, m->d_ovq, m->d_ovq_cnt, OVQ_CAP,                                         \
+                           pl.nb2, (uint32_t)p.S, BITS, m->d_ovq.get(), m->d_ovq_cnt.get(), OVQ_CAP,                                         \
                            (const unsigned long long *)(pl.fused ? pl.c_l1 : nullptr), pl.G1, pl.cap1, 0,                       \
                            (unsigned long long *)nullptr, 0u, 0u, pre, dch, (const uint32_t *)d_skew)
         if (part_lds(pl.nb2, bits) > ((size_t)80 << 10)) {
@@ -1060,9 +1030,9 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
         }
 #undef TSX_LEVEL2
         HIP_TRY(hipGetLastError());
-        lists = m->d_buf[0]; lists_start = nullptr; lists_cnt = pl.c_seg; lists_cap = pl.cap_sub; pieces = pl.cpr2;
+        lists = m->d_buf[0].get(); lists_start = nullptr; lists_cnt = pl.c_seg; lists_cap = pl.cap_sub; pieces = pl.cpr2;
     }
-    if (ev) HIP_TRY(hipEventRecord(ev[5], st));
+    if (ev) HIP_TRY(hipEventRecord(ev[5].get(), st));
     const int fresh = m->fresh ? 1 : 0;
     const int gb = (int)std::min<uint32_t>(pl.nseg, (uint32_t)m->cus * 16);
     const size_t seg_bytes = ((size_t)8 << p.S) * p.W;
@@ -1084,19 +1054,19 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
     }
     HIP_TRY(hipGetLastError());
     m->fresh = false;   // every segment has been written: built, or zeroed
-    if (ev) HIP_TRY(hipEventRecord(ev[6], st));
+    if (ev) HIP_TRY(hipEventRecord(ev[6].get(), st));
     // Records that found their sub-list filled up by a hot key, and the deferred list: inserted now, by the
     // whole chip, into a table whose segments are all in place.
     if (nq2) {
         const uint32_t nq = nq2 + pl.G1;
         DISPATCH_WK(m, hipLaunchKernelGGL((overflow_insert_kernel<WKV>), dim3(std::min<uint32_t>(nq, (uint32_t)m->cus * 8)),
-                                          dim3(PART_NT), 0, st, pp, (const uint64_t *)m->d_ovq,
-                                          (const uint32_t *)m->d_ovq_cnt, OVQ_CAP, nq));
+                                          dim3(PART_NT), 0, st, pp, (const uint64_t *)m->d_ovq.get(),
+                                          (const uint32_t *)m->d_ovq_cnt.get(), OVQ_CAP, nq));
         HIP_TRY(hipGetLastError());
     }
     DISPATCH_WK(m, hipLaunchKernelGGL((deferred_insert_kernel<WKV>), dim3(m->cus * 2), dim3(PART_NT), 0, st, pp,
-                                      (const uint64_t *)m->d_def_rec, (const uint64_t *)m->d_def_cnt,
-                                      (const unsigned long long *)m->d_def_n, (uint64_t)0, (uint64_t)m->def_cap));
+                                      (const uint64_t *)m->d_def_rec.get(), (const uint64_t *)m->d_def_cnt.get(),
+                                      (const unsigned long long *)m->d_def_n.get(), (uint64_t)0, m->def_cap()));
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
@@ -1122,6 +1092,28 @@ struct ShardOut {
 struct DescOut { uint4 *out = nullptr; uint64_t cap = 0; unsigned long long *count = nullptr, *sum = nullptr; int long_desc = 0; int owners = 0; };
 // (owners != 0: describe only -- the wave regions stay in buffer 1 for mini_split)
 
+// Room for the line counts of ntiles tiles and one partial sum per SCAN_CHUNK of them behind m->tile_cap counts.
+static int ensure_tiles(tsx_hip_map *m, uint64_t ntiles, hipStream_t st) {
+    if (ntiles <= m->tile_cap) return TSX_HIP_OK;
+    const uint64_t cap = ntiles + ntiles / 4 + 1024;
+    const size_t bytes = (size_t)(cap + cap / SCAN_CHUNK + 16) * sizeof(uint32_t);
+    m->tile_cap = 0;
+    TSX_TRY(m->d_tile.reserve(&st, bytes, bytes));
+    m->tile_cap = cap;
+    return TSX_HIP_OK;
+}
+
+// The next EV_N timing events of the map (created with timing on first use).
+static int next_timing_events(tsx_hip_map *m, Event *&ev) {
+    while (m->ev_used + EV_N > m->ev.size()) {
+        m->ev.emplace_back();
+        const int rc = m->ev.back().create(hipEventDefault);
+        if (rc != TSX_HIP_OK) { m->ev.pop_back(); return rc; }
+    }
+    ev = &m->ev[m->ev_used]; m->ev_used += EV_N;
+    return TSX_HIP_OK;
+}
+
 static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
                            hipStream_t st, ShardOut sh = ShardOut(), HotOut hot = HotOut(), DescOut dsc = DescOut()) {
     uint64_t *shard_send = sh.send;
@@ -1129,72 +1121,59 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
     unsigned long long *shard_counts = sh.counts;
     if (own_end == 0) return TSX_HIP_OK;
     const uint64_t ntiles = (own_end + TILE - 1) / TILE;
-    if (ntiles > m->tile_cap) {
-        if (m->d_tile) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(m->d_tile)); m->d_tile = nullptr; }
-        m->tile_cap = ntiles + ntiles / 4 + 1024;
-        // tile counts, then one partial sum per SCAN_CHUNK tiles
-        HIP_TRY(hipMalloc((void **)&m->d_tile, (m->tile_cap + m->tile_cap / SCAN_CHUNK + 16) * sizeof(uint32_t)));
-    }
-    hipEvent_t *ev = nullptr;
+    TSX_TRY(ensure_tiles(m, ntiles, st));
+    Event *ev = nullptr;
     if (m->timing) {
-        if (m->ev_used + EV_N > m->ev.size()) {
-            for (int i = 0; i < EV_N; ++i) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); m->ev.push_back(e); }
-        }
-        ev = &m->ev[m->ev_used]; m->ev_used += EV_N;
-        HIP_TRY(hipEventRecord(ev[0], st));
+        TSX_TRY(next_timing_events(m, ev));
+        HIP_TRY(hipEventRecord(ev[0].get(), st));
     }
     const int g1 = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8);
-    hipLaunchKernelGGL(line_count_kernel, dim3(g1), dim3(NT), 0, st, d_text, n, own_end, head_open, m->d_tile, ntiles);
+    hipLaunchKernelGGL(line_count_kernel, dim3(g1), dim3(NT), 0, st, d_text, n, own_end, head_open, m->d_tile.get(), ntiles);
     {
         const uint64_t nchunks = (ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
-        uint32_t *chunk = m->d_tile + m->tile_cap;
+        uint32_t *chunk = m->d_tile.get() + m->tile_cap;
         hipLaunchKernelGGL(line_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st,
-                           (const uint32_t *)m->d_tile, ntiles, chunk);
-        hipLaunchKernelGGL(line_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, m->d_carry);
-        hipLaunchKernelGGL(line_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, m->d_tile, ntiles,
+                           (const uint32_t *)m->d_tile.get(), ntiles, chunk);
+        hipLaunchKernelGGL(line_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, m->d_carry.get());
+        hipLaunchKernelGGL(line_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, m->d_tile.get(), ntiles,
                            (const uint32_t *)chunk);
     }
-    if (ev) HIP_TRY(hipEventRecord(ev[1], st));
+    if (ev) HIP_TRY(hipEventRecord(ev[1].get(), st));
     if (dsc.out || dsc.owners) {
         const int gdd = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8), gdr = gdd * (NT / 64);
         const uint32_t du = dsc.long_desc ? 2u : 1u;   // 16-byte units per description (long: four strips in 32 bytes)
         const uint64_t dcap = ((ntiles + gdd - 1) / gdd) * (dsc.long_desc ? 16 : 64);
-        int rcd = grow(st, m->d_buf[1], m->buf_bytes[1], (size_t)gdr * dcap * du * 16);
-        if (rcd != TSX_HIP_OK) return rcd;
-        {   // region sizes | region offsets | total
-            size_t have = m->desc_cnt_entries;
-            rcd = grow(st, m->d_desc_cnt, have, ((size_t)2 * gdr + 16) * 8 + (size_t)MZ_MAX_RANKS * m->cus * MZ_WG_PER_CU * 4 + 64);
-            m->desc_cnt_entries = have;
-            if (rcd != TSX_HIP_OK) return rcd;
-        }
-        unsigned long long *d_cnt = m->d_desc_cnt, *d_offs = d_cnt + gdr, *d_tot = d_offs + gdr;
+        TSX_TRY(grow(st, m->d_buf[1], (size_t)gdr * dcap * du * 16));
+        // region sizes | region offsets | total
+        TSX_TRY(grow(st, m->d_desc_cnt, ((size_t)2 * gdr + 16) * 8 + (size_t)MZ_MAX_RANKS * m->cus * MZ_WG_PER_CU * 4 + 64));
+        unsigned long long *d_cnt = m->d_desc_cnt.get(), *d_offs = d_cnt + gdr, *d_tot = d_offs + gdr;
         if (dsc.owners) {   // homopolymers leave here already: counted in the four words behind the chunk counters
             unsigned long long *d_hom = d_cnt + 2 * (size_t)gdr + 8 + ((size_t)MZ_MAX_RANKS * m->cus * MZ_WG_PER_CU + 1) / 2;
             HIP_TRY(hipMemsetAsync(d_hom, 0, 32, st));
             hipLaunchKernelGGL(strip_desc_kernel<true>, dim3(gdd), dim3(NT), 0, st, m->p, d_text, n, own_end, head_open,
-                               (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], dcap, d_cnt, dsc.sum, 0, d_hom);
+                               (const uint32_t *)m->d_tile.get(), ntiles, (uint4 *)m->d_buf[1].get(), dcap, d_cnt, dsc.sum, 0, d_hom);
         } else
         DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_kernel<false, BRV>), dim3(gdd), dim3(NT), 0, st, m->p, d_text, n, own_end,
-                           head_open, (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], dcap, d_cnt, dsc.sum,
+                           head_open, (const uint32_t *)m->d_tile.get(), ntiles, (uint4 *)m->d_buf[1].get(), dcap, d_cnt, dsc.sum,
                            dsc.long_desc, (unsigned long long *)nullptr, m->qmap_cur));
         if (dsc.owners) {   // owner = f(minimizer): the regions stay where they are, mini_split hands them out by owner
             HIP_TRY(hipGetLastError());
             m->mz_regions = (uint32_t)gdr; m->mz_dcap = dcap;
             if (ev) {
-                for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i], st));
+                for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i].get(), st));
                 m->ev_open.push_back((long)(ev - m->ev.data()));
             }
             return TSX_HIP_OK;
         }
         hipLaunchKernelGGL(desc_prefix_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long *)d_cnt, (uint32_t)gdr,
                            d_offs, d_tot, dcap, (uint64_t)dsc.cap, m->p.stats);
-        hipLaunchKernelGGL(desc_pack_kernel, dim3(std::min(gdr, m->cus * 8)), dim3(256), 0, st, (const uint4 *)m->d_buf[1], dcap,
+        hipLaunchKernelGGL(desc_pack_kernel, dim3(std::min(gdr, m->cus * 8)), dim3(256), 0, st, (const uint4 *)m->d_buf[1].get(), dcap,
                            (const unsigned long long *)d_cnt, (const unsigned long long *)d_offs, (uint32_t)gdr, dsc.out,
                            dsc.cap * du, du);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(dsc.count, d_tot, 8, hipMemcpyDeviceToDevice, st));
         if (ev) {   // the walks, level 2 and the build follow in other calls, which record 3..7 of the first window's tuple again
-            for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i], st));
+            for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i].get(), st));
             m->ev_open.push_back((long)(ev - m->ev.data()));
         }
         return TSX_HIP_OK;
@@ -1213,9 +1192,9 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
         if (rcz != TSX_HIP_OK) return rcz;
         DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV, BRV>), dim3(g3), dim3(NT),
                                                             lut_bytes, st, m->p, d_text, n, own_end, head_open,
-                                                            (const uint32_t *)m->d_tile, ntiles, m->qmap_cur))));
+                                                            (const uint32_t *)m->d_tile.get(), ntiles, m->qmap_cur))));
         HIP_TRY(hipGetLastError());
-        if (ev) for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i], st));
+        if (ev) for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i].get(), st));
         return TSX_HIP_OK;
     }
 
@@ -1251,8 +1230,8 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
     } else {
         rc = ensure_deferred(m, maxrec, st);
         if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_def_n, 0, 8, st));
-        pp.defer = DeferList{m->d_def_rec, m->d_def_cnt, m->d_def_n, (uint64_t)m->def_cap};
+        HIP_TRY(hipMemsetAsync(m->d_def_n.get(), 0, 8, st));
+        pp.defer = m->defer();
     }
     // scan -> key log + histogram by level-1 bucket, or by owner GPU for a sharded scan
     const uint32_t hist_nb = shard_send ? nown : pl.nb1, hist_shift = (uint32_t)(shard_send ? p.l : p.l - pl.b1);
@@ -1269,23 +1248,22 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
             const char *ll_env = getenv("TSX_HIP_LOCAL_LONG");
             const int lng = ll_env ? (atoi(ll_env) != 0) : 0;
             const uint64_t desc_cap = ((ntiles + gd - 1) / gd) * (lng ? 16 : 64);
-            rc = grow(st, m->d_buf[0], m->buf_bytes[0], (size_t)gdreg * desc_cap * (lng ? 32 : 16));
-            if (rc != TSX_HIP_OK) return rc;
+            TSX_TRY(grow(st, m->d_buf[0], (size_t)gdreg * desc_cap * (lng ? 32 : 16)));
             DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_kernel<false, BRV>), dim3(gd), dim3(NT), 0, st, pp, d_text, n, own_end,
-                               head_open, (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[0], desc_cap, pl.c_log,
+                               head_open, (const uint32_t *)m->d_tile.get(), ntiles, (uint4 *)m->d_buf[0].get(), desc_cap, pl.c_log,
                                (unsigned long long *)nullptr, lng, (unsigned long long *)nullptr, m->qmap_cur));
             HIP_TRY(hipGetLastError());
             if (lds > ((size_t)80 << 10)) {   // 512 lists: one workgroup per CU, 1024 threads
                 DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<1024, CANV>), dim3(pl.G1), dim3(1024), lds, st, pp,
-                                   (const uint4 *)m->d_buf[0], desc_cap,
+                                   (const uint4 *)m->d_buf[0].get(), desc_cap,
                                    (const unsigned long long *)pl.c_log, (uint32_t)gdreg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
-                                   (uint32_t)(p.l - pl.b1), m->d_ovq + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt + nq2, OVQ_CAP,
+                                   (uint32_t)(p.l - pl.b1), m->d_ovq.get() + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt.get() + nq2, OVQ_CAP,
                                    (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, 1u));
             } else {
                 DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<SP_NT, CANV>), dim3(pl.G1), dim3(SP_NT), lds, st, pp,
-                                   (const uint4 *)m->d_buf[0], desc_cap,
+                                   (const uint4 *)m->d_buf[0].get(), desc_cap,
                                    (const unsigned long long *)pl.c_log, (uint32_t)gdreg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
-                                   (uint32_t)(p.l - pl.b1), m->d_ovq + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt + nq2, OVQ_CAP,
+                                   (uint32_t)(p.l - pl.b1), m->d_ovq.get() + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt.get() + nq2, OVQ_CAP,
                                    (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, 1u));
             }
         }
@@ -1293,44 +1271,32 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
         // key log form (sharded scans, one-level tables), the scan in two kernels as well: descriptions into buffer 1
         // (level 1 fills it only afterwards), then the walk with every lane busy into the wave's log region
         const uint64_t desc_cap = ((ntiles + gd - 1) / gd) * 64;
-        rc = grow(st, m->d_buf[1], m->buf_bytes[1], (size_t)gdreg * desc_cap * 16);
-        if (rc != TSX_HIP_OK) return rc;
-        pl.buf1 = m->d_buf[1];
-        {
-            size_t have = m->desc_cnt_entries;
-            rc = grow(st, m->d_desc_cnt, have, (size_t)gdreg * 8);
-            m->desc_cnt_entries = have;
-            if (rc != TSX_HIP_OK) return rc;
-        }
+        TSX_TRY(grow(st, m->d_buf[1], (size_t)gdreg * desc_cap * 16));
+        pl.buf1 = m->d_buf[1].get();
+        TSX_TRY(grow(st, m->d_desc_cnt, (size_t)gdreg * 8));
         DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_kernel<false, BRV>), dim3(gd), dim3(NT), 0, st, pp, d_text, n, own_end,
-                           head_open, (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], desc_cap, m->d_desc_cnt,
+                           head_open, (const uint32_t *)m->d_tile.get(), ntiles, (uint4 *)m->d_buf[1].get(), desc_cap, m->d_desc_cnt.get(),
                            (unsigned long long *)nullptr, 0, (unsigned long long *)nullptr, m->qmap_cur));
         HIP_TRY(hipGetLastError());
         DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_kernel<CANV>), dim3(gs), dim3(NT), lut_bytes, st, pp,
-                           (const uint4 *)m->d_buf[1], desc_cap,
-                           (const unsigned long long *)m->d_desc_cnt, (uint32_t)gdreg, m->d_buf[0], pl.log_cap,
+                           (const uint4 *)m->d_buf[1].get(), desc_cap,
+                           (const unsigned long long *)m->d_desc_cnt.get(), (uint32_t)gdreg, m->d_buf[0].get(), pl.log_cap,
                            pl.c_log, pl.d_hist, hist_nb, hist_shift, (uint64_t)0, 0, 0, (unsigned long long *)nullptr));
     } else {
         // multi-limb keys, two kernels as well: descriptions (first k-mer + entering bases + validity) into buffer 1,
         // then the walk with every lane busy
         const int du = (2 * p.wk + 2 + 3) / 4;
         const uint64_t desc_cap = ((ntiles + gd - 1) / gd) * 64;
-        rc = grow(st, m->d_buf[1], m->buf_bytes[1], (size_t)gdreg * desc_cap * du * 16);
-        if (rc != TSX_HIP_OK) return rc;
-        pl.buf1 = m->d_buf[1];
-        {
-            size_t have = m->desc_cnt_entries;
-            rc = grow(st, m->d_desc_cnt, have, (size_t)gdreg * 8);
-            m->desc_cnt_entries = have;
-            if (rc != TSX_HIP_OK) return rc;
-        }
+        TSX_TRY(grow(st, m->d_buf[1], (size_t)gdreg * desc_cap * du * 16));
+        pl.buf1 = m->d_buf[1].get();
+        TSX_TRY(grow(st, m->d_desc_cnt, (size_t)gdreg * 8));
 #define TSX_WIDE2(WKV)                                                                                                      \
         DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_wide_kernel<WKV, BRV>), dim3(gd), dim3(NT), 0, st, pp, d_text, n,      \
-                           own_end, head_open, (const uint32_t *)m->d_tile, ntiles, (uint4 *)m->d_buf[1], desc_cap,         \
-                           m->d_desc_cnt, m->qmap_cur));                                                                     \
+                           own_end, head_open, (const uint32_t *)m->d_tile.get(), ntiles, (uint4 *)m->d_buf[1].get(), desc_cap,         \
+                           m->d_desc_cnt.get(), m->qmap_cur));                                                                     \
         DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_wide_kernel<WKV, CANV>), dim3(gs), dim3(NT), lut_bytes, st, pp,     \
-                           (const uint4 *)m->d_buf[1],                                                                       \
-                           desc_cap, (const unsigned long long *)m->d_desc_cnt, (uint32_t)gdreg, m->d_buf[0],                \
+                           (const uint4 *)m->d_buf[1].get(),                                                                       \
+                           desc_cap, (const unsigned long long *)m->d_desc_cnt.get(), (uint32_t)gdreg, m->d_buf[0].get(),                \
                            pl.log_cap, pl.c_log, pl.d_hist, hist_nb, hist_shift))
         switch (p.wk) {
             case 2: TSX_WIDE2(2); break;
@@ -1340,7 +1306,7 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
 #undef TSX_WIDE2
     }
     HIP_TRY(hipGetLastError());
-    if (ev) { HIP_TRY(hipEventRecord(ev[2], st)); HIP_TRY(hipEventRecord(ev[3], st)); }
+    if (ev) { HIP_TRY(hipEventRecord(ev[2].get(), st)); HIP_TRY(hipEventRecord(ev[3].get(), st)); }
     if (shard_send) {
         // level 0: split every log region by owner into the caller's send buffer (exact offsets)
         if ((uint64_t)greg * pl.log_cap > shard_cap || (sh.own && (uint64_t)greg * pl.log_cap > sh.own_cap))
@@ -1349,21 +1315,21 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
                            (uint32_t)greg, pl.c_bcnt);
         hipLaunchKernelGGL(offsets_finish_kernel, dim3(1), dim3(1024), 0, st, nown, pl.c_bstart, pl.c_bcnt);
         hipLaunchKernelGGL(split_owner_kernel, dim3(std::min(greg, m->cus * 8)), dim3(PART_NT), 0, st,
-                           (const uint64_t *)m->d_buf[0], (const unsigned long long *)pl.c_log, pl.log_cap,
+                           (const uint64_t *)m->d_buf[0].get(), (const unsigned long long *)pl.c_log, pl.log_cap,
                            (uint32_t)greg, shard_send, (const unsigned long long *)pl.d_offs,
                            (const unsigned long long *)pl.c_bstart, (const unsigned long long *)pl.c_bcnt, nown,
                            (uint32_t)p.l, sh.own, p.shard, sh.key_sum);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(shard_counts, pl.c_bcnt, nown * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
     } else {
-        rc = run_partition_build(m, pl, m->d_buf[0], nullptr, pl.log_cap, st, ev);
+        rc = run_partition_build(m, pl, m->d_buf[0].get(), nullptr, pl.log_cap, st, ev);
         if (rc != TSX_HIP_OK) return rc;
     }
     if (ev && shard_send) {   // the partition phase follows in tsx_hip_shard_build_device, which records 3..6 again
-        for (int i = 3; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i], st));
+        for (int i = 3; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i].get(), st));
         m->ev_open.push_back((long)(ev - m->ev.data()));
     }
-    if (ev && !shard_send) HIP_TRY(hipEventRecord(ev[7], st));
+    if (ev && !shard_send) HIP_TRY(hipEventRecord(ev[7].get(), st));
     return TSX_HIP_OK;
 }
 
@@ -1381,7 +1347,7 @@ extern "C" int tsx_hip_shard_scan_window_device(tsx_hip_map *m, const void *dev_
     if (win_len >= ((size_t)4 << 30)) return TSX_HIP_ERANGE;  // one window per call
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
-    if (win_off == 0) HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));   // line index restarts with the text
+    if (win_off == 0) HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));   // line index restarts with the text
     HIP_TRY(hipMemsetAsync(dev_hot_n, 0, 8, st));
     HIP_TRY(hipMemsetAsync(dev_send_counts, 0, sizeof(unsigned long long) << (m->p.lg - m->p.l), st));
     if (win_len == 0) return TSX_HIP_OK;
@@ -1464,14 +1430,14 @@ extern "C" int tsx_hip_shard_build_pieces_device(tsx_hip_map *m, const void *dev
     if (rc != TSX_HIP_OK) return rc;
     rc = ensure_deferred(m, n_keys + 65536, st);
     if (rc != TSX_HIP_OK) return rc;
-    HIP_TRY(hipMemsetAsync(m->d_def_n, 0, 8, st));
+    HIP_TRY(hipMemsetAsync(m->d_def_n.get(), 0, 8, st));
     // region table: starts into c_rstart, sizes into c_log (plan_partition laid them out back to back: [c_log | c_rstart])
     HIP_TRY(hipMemcpyAsync(pl.c_rstart, m->h_regions.data(), (size_t)g * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(pl.c_log, m->h_regions.data() + g, (size_t)g * 8, hipMemcpyHostToDevice, st));
-    hipEvent_t *ev = nullptr;
+    Event *ev = nullptr;
     if (m->timing && !m->ev_open.empty() && (size_t)m->ev_open.front() + EV_N <= m->ev_used) {
         ev = &m->ev[(size_t)m->ev_open.front()];
-        HIP_TRY(hipEventRecord(ev[3], st));   // the histogram of the received keys counts as level 1
+        HIP_TRY(hipEventRecord(ev[3].get(), st));   // the histogram of the received keys counts as level 1
     }
     if (!m->ev_open.empty()) m->ev_open.pop_front();
     if (pl.fused) {
@@ -1479,13 +1445,13 @@ extern "C" int tsx_hip_shard_build_pieces_device(tsx_hip_map *m, const void *dev
         rc = ensure_ovq(m, (size_t)nq2 + pl.G1, pl.rw, st);
         if (rc != TSX_HIP_OK) return rc;
         TableParams pp = m->p;
-        pp.defer = DeferList{m->d_def_rec, m->d_def_cnt, m->d_def_n, (uint64_t)m->def_cap};
+        pp.defer = m->defer();
         const uint32_t bits = 5;   // 32-word rings: 16 words may stay behind a flush, 8 arrive per batch on average
         hipLaunchKernelGGL((partition_ring_kernel<1>), dim3(g), dim3(RING_NT), (size_t)pl.nb1 * (((size_t)8 << bits) + 36), st,
                            pp, keys, (const unsigned long long *)pl.c_rstart, (const unsigned long long *)pl.c_log, (uint64_t)0,
                            (uint32_t)g, 1u, pl.buf1, (const unsigned long long *)nullptr,
                            (const unsigned long long *)nullptr, pl.c_l1, pl.cap1, pl.nb1, (uint32_t)(m->p.l - pl.b1), bits,
-                           m->d_ovq + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt + nq2, OVQ_CAP,
+                           m->d_ovq.get() + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt.get() + nq2, OVQ_CAP,
                            (const unsigned long long *)nullptr, 0u, (uint64_t)0, 1, key_sum, 0u, (uint32_t)g, 0, 0u, (const uint32_t *)nullptr);
     } else {
         hipLaunchKernelGGL(hist_kernel, dim3(g), dim3(PART_NT), 0, st, keys, (uint32_t)g, pl.nb1, (uint32_t)(m->p.l - pl.b1),
@@ -1493,7 +1459,7 @@ extern "C" int tsx_hip_shard_build_pieces_device(tsx_hip_map *m, const void *dev
     }
     HIP_TRY(hipGetLastError());
     rc = run_partition_build(m, pl, keys, pl.c_rstart, 0, st, ev);
-    if (rc == TSX_HIP_OK && ev) HIP_TRY(hipEventRecord(ev[7], st));
+    if (rc == TSX_HIP_OK && ev) HIP_TRY(hipEventRecord(ev[7].get(), st));
     return rc;
 }
 
@@ -1527,7 +1493,7 @@ extern "C" int tsx_hip_shard_l1_window_device(tsx_hip_map *m, const void *dev_ke
     if (!l1_supported(m)) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
-    if (!m->sh_pl) m->sh_pl = new PartPlan();
+    if (!m->sh_pl) m->sh_pl.reset(new PartPlan());
     PartPlan &pl = *m->sh_pl;
     if (window == 0) {
         // one workgroup per region, two workgroups per CU: every window's launch fills the chip once
@@ -1535,20 +1501,16 @@ extern "C" int tsx_hip_shard_l1_window_device(tsx_hip_map *m, const void *dev_ke
         m->sh_windows = nwindows;
         const int g1 = (int)(m->sh_rw * nwindows);
         const uint64_t maxrec = std::max<uint64_t>(est_total_keys, n_keys) + 65536;
-        std::swap(m->d_buf[1], m->sh_buf1); std::swap(m->buf_bytes[1], m->sh_buf1_bytes);
-        std::swap(m->d_cnt, m->sh_cnt); std::swap(m->cnt_entries, m->sh_cnt_entries);
-        int rc = plan_partition(m, maxrec, g1, false, 0, st, pl, g1);
-        std::swap(m->d_buf[1], m->sh_buf1); std::swap(m->buf_bytes[1], m->sh_buf1_bytes);
-        std::swap(m->d_cnt, m->sh_cnt); std::swap(m->cnt_entries, m->sh_cnt_entries);
+        int rc = plan_sharded_l1(m, maxrec, g1, st, pl);
         if (rc != TSX_HIP_OK) return rc;
         if (!pl.fused) return TSX_HIP_EINVAL;
         rc = ensure_deferred(m, maxrec, st);
         if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_def_n, 0, 8, st));
+        HIP_TRY(hipMemsetAsync(m->d_def_n.get(), 0, 8, st));
         const uint32_t nq2 = pl.nb1 * pl.cpr2;
         rc = ensure_ovq(m, (size_t)nq2 + pl.G1, pl.rw, st);
         if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_ovq_cnt, 0, ((size_t)nq2 + pl.G1) * 4, st));   // queues of windows that never run
+        HIP_TRY(hipMemsetAsync(m->d_ovq_cnt.get(), 0, ((size_t)nq2 + pl.G1) * 4, st));   // queues of windows that never run
         m->h_regions.assign((size_t)2 * g1, 0);
     } else if (m->sh_windows != nwindows || !pl.fused) {
         return TSX_HIP_EINVAL;
@@ -1567,13 +1529,13 @@ extern "C" int tsx_hip_shard_l1_window_device(tsx_hip_map *m, const void *dev_ke
     HIP_TRY(hipMemcpyAsync(ds, hs, (size_t)rw * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dc, hc, (size_t)rw * 8, hipMemcpyHostToDevice, st));
     TableParams pp = m->p;
-    pp.defer = DeferList{m->d_def_rec, m->d_def_cnt, m->d_def_n, (uint64_t)m->def_cap};
+    pp.defer = m->defer();
     const uint32_t nq2 = pl.nb1 * pl.cpr2, bits = 5;
     hipLaunchKernelGGL((partition_ring_kernel<1>), dim3(rw), dim3(RING_NT), (size_t)pl.nb1 * (((size_t)8 << bits) + 36), st, pp,
                        (const uint64_t *)dev_keys, (const unsigned long long *)ds, (const unsigned long long *)dc, (uint64_t)0, rw,
                        1u, pl.buf1, (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, pl.c_l1,
                        pl.cap1, pl.nb1, (uint32_t)(m->p.l - pl.b1), bits,
-                       m->d_ovq + ((size_t)nq2 + (size_t)window * rw) * OVQ_CAP, m->d_ovq_cnt + nq2 + (size_t)window * rw, OVQ_CAP,
+                       m->d_ovq.get() + ((size_t)nq2 + (size_t)window * rw) * OVQ_CAP, m->d_ovq_cnt.get() + nq2 + (size_t)window * rw, OVQ_CAP,
                        (const unsigned long long *)nullptr, 0u, (uint64_t)0, 1, (unsigned long long *)dev_key_sum,
                        window * rw, g1, 0, 0u, (const uint32_t *)nullptr);
     HIP_TRY(hipGetLastError());
@@ -1606,7 +1568,7 @@ extern "C" int tsx_hip_shard_desc_window_device(tsx_hip_map *m, const void *dev_
     if (desc_cap < win_len / (long_desc ? 64 : 16) + 1) return TSX_HIP_ERANGE;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
-    if (win_off == 0) HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));
+    if (win_off == 0) HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));
     HIP_TRY(hipMemsetAsync(dev_count, 0, 8, st));
     if (win_len == 0) return TSX_HIP_OK;
     DescOut dsc;
@@ -1651,9 +1613,9 @@ static int mini_split(tsx_hip_map *m, uint32_t part, uint32_t nparts, int nranks
     HIP_TRY(hipMemsetAsync(dev_counts, 0, ((size_t)nranks + 4) * 8, st));
     if (m->mz_regions == 0) return TSX_HIP_OK;   // an empty text
     const int gdr = (int)m->mz_regions, gsp = std::min(gdr, m->cus * MZ_WG_PER_CU);
-    unsigned long long *d_cnt = m->d_desc_cnt, *count = (unsigned long long *)dev_counts;
+    unsigned long long *d_cnt = m->d_desc_cnt.get(), *count = (unsigned long long *)dev_counts;
     uint32_t *d_used = (uint32_t *)(d_cnt + 2 * (size_t)gdr + 8);   // chunks taken per (owner, workgroup)
-    hipLaunchKernelGGL(desc_owner_split_kernel, dim3(gsp), dim3(MZ_NT), 0, st, m->p, (const uint4 *)m->d_buf[1], m->mz_dcap,
+    hipLaunchKernelGGL(desc_owner_split_kernel, dim3(gsp), dim3(MZ_NT), 0, st, m->p, (const uint4 *)m->d_buf[1].get(), m->mz_dcap,
                        (const unsigned long long *)d_cnt, (uint32_t)gdr, (uint32_t)nranks, (uint4 *)dev_desc, (uint64_t)cap_per_owner,
                        d_used, count + nranks, part, nparts,
                        (const unsigned long long *)(d_cnt + 2 * (size_t)gdr + 8 + ((size_t)MZ_MAX_RANKS * m->cus * MZ_WG_PER_CU + 1) / 2));
@@ -1665,7 +1627,7 @@ static int mini_split(tsx_hip_map *m, uint32_t part, uint32_t nparts, int nranks
 
 static int mini_describe(tsx_hip_map *m, const void *dev_text, size_t n_total, size_t off, size_t len, void *dev_kmer_sum,
                          hipStream_t st) {
-    if (off == 0) HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));
+    if (off == 0) HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));
     m->mz_regions = 0; m->mz_len = len;
     if (len == 0) return TSX_HIP_OK;
     DescOut dsc;
@@ -1738,7 +1700,7 @@ static int shard_walk(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int l
     if (!l1_supported(m)) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
-    if (!m->sh_pl) m->sh_pl = new PartPlan();
+    if (!m->sh_pl) m->sh_pl.reset(new PartPlan());
     PartPlan &pl = *m->sh_pl;
     // long_desc & 2: what the minimizer exchange sent to a map with shard_bits = 0 -- every key stays, homopolymers were
     // taken out by the sender, about half of a description's 16 positions are valid (a flush every second quarter), and
@@ -1756,25 +1718,21 @@ static int shard_walk(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int l
         m->sh_windows = caller_slots;
         const int g1 = (int)(gw * nslots);
         const uint64_t maxrec = est_total_keys + 65536;
-        std::swap(m->d_buf[1], m->sh_buf1); std::swap(m->buf_bytes[1], m->sh_buf1_bytes);
-        std::swap(m->d_cnt, m->sh_cnt); std::swap(m->cnt_entries, m->sh_cnt_entries);
-        int rc = plan_partition(m, maxrec, g1, false, 0, st, pl, g1);
-        std::swap(m->d_buf[1], m->sh_buf1); std::swap(m->buf_bytes[1], m->sh_buf1_bytes);
-        std::swap(m->d_cnt, m->sh_cnt); std::swap(m->cnt_entries, m->sh_cnt_entries);
+        int rc = plan_sharded_l1(m, maxrec, g1, st, pl);
         if (rc != TSX_HIP_OK) return rc;
         if (!pl.fused) return TSX_HIP_EINVAL;
         rc = ensure_deferred(m, maxrec, st);
         if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_def_n, 0, 8, st));
+        HIP_TRY(hipMemsetAsync(m->d_def_n.get(), 0, 8, st));
         const uint32_t nq2 = pl.nb1 * pl.cpr2;
         rc = ensure_ovq(m, (size_t)nq2 + pl.G1, pl.rw, st);
         if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_ovq_cnt, 0, ((size_t)nq2 + pl.G1) * 4, st));
+        HIP_TRY(hipMemsetAsync(m->d_ovq_cnt.get(), 0, ((size_t)nq2 + pl.G1) * 4, st));
     } else if (m->sh_windows != caller_slots || !pl.fused) {
         return TSX_HIP_EINVAL;
     }
     if (caller_slot == 0 && m->timing && !m->ev_open.empty() && (size_t)m->ev_open.front() + EV_N <= m->ev_used) {
-        HIP_TRY(hipEventRecord(m->ev[(size_t)m->ev_open.front() + 3], st));   // "level 1" = the walks, up to the start of level 2
+        HIP_TRY(hipEventRecord(m->ev[(size_t)m->ev_open.front() + 3].get(), st));   // "level 1" = the walks, up to the start of level 2
         m->sh_ev3 = true;
     }
     if (n_desc == 0) return TSX_HIP_OK;
@@ -1786,20 +1744,20 @@ static int shard_walk(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int l
     const uint32_t flush_q = mini ? 2u : (nown >= 4 ? 4u : (nown == 2 ? 2u : 1u));
     const int own_mode = mini ? (2 | (caller_slot > 0 ? 4 : 0)) : 1;
     TableParams pp = m->p;
-    pp.defer = DeferList{m->d_def_rec, m->d_def_cnt, m->d_def_n, (uint64_t)m->def_cap};
+    pp.defer = m->defer();
     const size_t lds = (size_t)pl.nb1 * (((size_t)8 << SP_CAPBITS) + 8 + 8 + 4 + 4);
     // (a canonical map gets here only from count_slabs: the exchanges refuse it)
     if (lds > ((size_t)80 << 10)) {   // 512 lists: one workgroup per CU, 1024 threads
         DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<1024, CANV>), dim3(gw), dim3(1024), lds, st, pp, (const uint4 *)dev_desc, chunk,
                            (const unsigned long long *)nullptr, gw, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
-                           (uint32_t)(m->p.l - pl.b1), m->d_ovq + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
-                           m->d_ovq_cnt + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
+                           (uint32_t)(m->p.l - pl.b1), m->d_ovq.get() + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
+                           m->d_ovq_cnt.get() + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
                            (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q));
     } else {
         DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<SP_NT, CANV>), dim3(gw), dim3(SP_NT), lds, st, pp, (const uint4 *)dev_desc, chunk,
                            (const unsigned long long *)nullptr, gw, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
-                           (uint32_t)(m->p.l - pl.b1), m->d_ovq + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
-                           m->d_ovq_cnt + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
+                           (uint32_t)(m->p.l - pl.b1), m->d_ovq.get() + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
+                           m->d_ovq_cnt.get() + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
                            (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q));
     }
     HIP_TRY(hipGetLastError());
@@ -1825,7 +1783,7 @@ extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc,
     if (!l1_supported(m)) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
-    if (!m->sh_pl) m->sh_pl = new PartPlan();
+    if (!m->sh_pl) m->sh_pl.reset(new PartPlan());
     PartPlan &pl = *m->sh_pl;
     if (slot == 0) {
         uint32_t gw = (uint32_t)m->cus * 2;
@@ -1834,25 +1792,21 @@ extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc,
         m->sh_windows = nslots;
         const int g1 = (int)(gw * nslots);
         const uint64_t maxrec = est_total_keys + 65536;
-        std::swap(m->d_buf[1], m->sh_buf1); std::swap(m->buf_bytes[1], m->sh_buf1_bytes);
-        std::swap(m->d_cnt, m->sh_cnt); std::swap(m->cnt_entries, m->sh_cnt_entries);
-        int rc = plan_partition(m, maxrec, g1, false, 0, st, pl, g1);
-        std::swap(m->d_buf[1], m->sh_buf1); std::swap(m->buf_bytes[1], m->sh_buf1_bytes);
-        std::swap(m->d_cnt, m->sh_cnt); std::swap(m->cnt_entries, m->sh_cnt_entries);
+        int rc = plan_sharded_l1(m, maxrec, g1, st, pl);
         if (rc != TSX_HIP_OK) return rc;
         if (!pl.fused) return TSX_HIP_EINVAL;
         rc = ensure_deferred(m, maxrec, st);
         if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_def_n, 0, 8, st));
+        HIP_TRY(hipMemsetAsync(m->d_def_n.get(), 0, 8, st));
         const uint32_t nq2 = pl.nb1 * pl.cpr2;
         rc = ensure_ovq(m, (size_t)nq2 + pl.G1, pl.rw, st);
         if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_ovq_cnt, 0, ((size_t)nq2 + pl.G1) * 4, st));
+        HIP_TRY(hipMemsetAsync(m->d_ovq_cnt.get(), 0, ((size_t)nq2 + pl.G1) * 4, st));
     } else if (m->sh_windows != nslots || !pl.fused) {
         return TSX_HIP_EINVAL;
     }
     if (slot == 0 && m->timing && !m->ev_open.empty() && (size_t)m->ev_open.front() + EV_N <= m->ev_used) {
-        HIP_TRY(hipEventRecord(m->ev[(size_t)m->ev_open.front() + 3], st));
+        HIP_TRY(hipEventRecord(m->ev[(size_t)m->ev_open.front() + 3].get(), st));
         m->sh_ev3 = true;
     }
     if (n_desc == 0) return TSX_HIP_OK;
@@ -1863,19 +1817,19 @@ extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc,
     int rc = plan_partition(m, keep, greg, true, 0, st, lp, 0);
     if (rc != TSX_HIP_OK) return rc;
     TableParams pp = m->p;
-    pp.defer = DeferList{m->d_def_rec, m->d_def_cnt, m->d_def_n, (uint64_t)m->def_cap};
+    pp.defer = m->defer();
     const uint64_t chunk = (n_desc + greg - 1) / greg;   // descriptions per wave
     hipLaunchKernelGGL(walk_log_kernel<false>, dim3(gs), dim3(NT), m->lut.size() * 8, st, pp, (const uint4 *)dev_desc, chunk,
-                       (const unsigned long long *)nullptr, (uint32_t)greg, m->d_buf[0], lp.log_cap, lp.c_log, lp.d_hist,
+                       (const unsigned long long *)nullptr, (uint32_t)greg, m->d_buf[0].get(), lp.log_cap, lp.c_log, lp.d_hist,
                        lp.nb1, (uint32_t)(m->p.l - lp.b1), (uint64_t)n_desc, long_desc ? 1 : 0, 1,
                        (unsigned long long *)dev_emit_sum);
     HIP_TRY(hipGetLastError());
     const uint32_t gw = m->sh_rw, nq2 = pl.nb1 * pl.cpr2, bits = 5;
     hipLaunchKernelGGL((partition_ring_kernel<1>), dim3(gw), dim3(RING_NT), (size_t)pl.nb1 * (((size_t)8 << bits) + 36), st, pp,
-                       (const uint64_t *)m->d_buf[0], (const unsigned long long *)nullptr, (const unsigned long long *)nullptr,
+                       (const uint64_t *)m->d_buf[0].get(), (const unsigned long long *)nullptr, (const unsigned long long *)nullptr,
                        (uint64_t)0, 1u, gw, pl.buf1, (const unsigned long long *)nullptr, (const unsigned long long *)nullptr,
                        pl.c_l1, pl.cap1, pl.nb1, (uint32_t)(m->p.l - pl.b1), bits,
-                       m->d_ovq + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP, m->d_ovq_cnt + nq2 + (size_t)slot * gw, OVQ_CAP,
+                       m->d_ovq.get() + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP, m->d_ovq_cnt.get() + nq2 + (size_t)slot * gw, OVQ_CAP,
                        (const unsigned long long *)lp.c_log, (uint32_t)greg, lp.log_cap, 1, (unsigned long long *)nullptr, slot,
                        nslots, 0, 0u, (const uint32_t *)nullptr);
     HIP_TRY(hipGetLastError());
@@ -1889,15 +1843,15 @@ extern "C" int tsx_hip_shard_build_l1_device(tsx_hip_map *m, void *stream) {
     if (!m || !m->sh_pl || !m->sh_pl->fused) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
-    hipEvent_t *ev = nullptr;
+    Event *ev = nullptr;
     if (m->timing && !m->ev_open.empty() && (size_t)m->ev_open.front() + EV_N <= m->ev_used) {
         ev = &m->ev[(size_t)m->ev_open.front()];
-        if (!m->sh_ev3) HIP_TRY(hipEventRecord(ev[3], st));
+        if (!m->sh_ev3) HIP_TRY(hipEventRecord(ev[3].get(), st));
     }
     m->sh_ev3 = false;
     if (!m->ev_open.empty()) m->ev_open.pop_front();
     int rc = run_partition_build(m, *m->sh_pl, nullptr, nullptr, 0, st, ev);
-    if (rc == TSX_HIP_OK && ev) HIP_TRY(hipEventRecord(ev[7], st));
+    if (rc == TSX_HIP_OK && ev) HIP_TRY(hipEventRecord(ev[7].get(), st));
     return rc;
 }
 
@@ -1955,10 +1909,10 @@ extern "C" int tsx_hip_get_stage_timing(tsx_hip_map *m, double *stage_ms, uint64
     // line, scan, level 1, level 2, build kernel, gap, inserts after the build (overflow queues + deferred list)
     static const int from[7] = {0, 1, 3, 4, 5, 2, 6}, to[7] = {1, 2, 4, 5, 6, 3, 7};
     for (size_t i = 0; i + EV_N <= m->ev_used; i += EV_N) {
-        HIP_TRY(hipEventSynchronize(m->ev[i + 7]));
+        HIP_TRY(hipEventSynchronize(m->ev[i + 7].get()));
         for (int sgm = 0; sgm < 7; ++sgm) {
             float t = 0;
-            HIP_TRY(hipEventElapsedTime(&t, m->ev[i + from[sgm]], m->ev[i + to[sgm]]));
+            HIP_TRY(hipEventElapsedTime(&t, m->ev[i + from[sgm]].get(), m->ev[i + to[sgm]].get()));
             acc[sgm] += t;
         }
     }
@@ -2012,27 +1966,27 @@ static int base_rule_ok(const tsx_hip_map *m) {
     return TSX_HIP_OK;
 }
 
-// m->d_qmap = the low-quality bitmap of d_text[0, n), a text that starts at a record boundary.  Uses the map's line
+// m->d_qmap.get() = the low-quality bitmap of d_text[0, n), a text that starts at a record boundary.  Uses the map's line
 // scratch (d_tile, word 0 of d_carry) and waits once, for the line count.  The scan launches get it as qmap_cur.
 static int build_qmap(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, hipStream_t st) {
     if (n >= ((uint64_t)1 << 33)) { g_last_error = "min_qual_char: a text of 8 GiB or more"; return TSX_HIP_ERANGE; }
     const size_t words = (size_t)(n + 15) / 16 + 16;
-    int rc = grow(st, m->d_qmap, m->qmap_bytes, words * 2);
+    int rc = grow(st, m->d_qmap, words * 2);
     if (rc != TSX_HIP_OK) return rc;
-    HIP_TRY(hipMemsetAsync(m->d_qmap, 0, words * 2, st));
+    HIP_TRY(hipMemsetAsync(m->d_qmap.get(), 0, words * 2, st));
     if (n == 0) return TSX_HIP_OK;
-    HIP_TRY(hipMemsetAsync(m->d_carry, 0, sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
     if ((rc = query_line_pass(m, d_text, n, n, 0, st)) != TSX_HIP_OK) return rc;
     uint32_t lines = 0;
-    HIP_TRY(hipMemcpyAsync(&lines, m->d_carry, sizeof lines, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&lines, m->d_carry.get(), sizeof lines, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const uint64_t nrec = (uint64_t)lines / 4 + 1, ntiles = (n + TILE - 1) / TILE;
-    if ((rc = grow(st, m->d_qrec, m->qrec_bytes, (size_t)nrec * QR_N * 8)) != TSX_HIP_OK) return rc;
-    HIP_TRY(hipMemsetAsync(m->d_qrec, 0, (size_t)nrec * QR_N * 8, st));
+    if ((rc = grow(st, m->d_qrec, (size_t)nrec * QR_N * 8)) != TSX_HIP_OK) return rc;
+    HIP_TRY(hipMemsetAsync(m->d_qrec.get(), 0, (size_t)nrec * QR_N * 8, st));
     hipLaunchKernelGGL(qual_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
-                       d_text, n, (const uint32_t *)m->d_tile, ntiles, (const uint32_t *)m->d_carry, m->d_qrec, nrec);
+                       d_text, n, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), m->d_qrec.get(), nrec);
     hipLaunchKernelGGL(qual_bits_kernel, dim3(grid_for(m, nrec * 16, 8)), dim3(NT), 0, st, d_text,
-                       (const unsigned long long *)m->d_qrec, nrec, m->minq, m->d_qmap);
+                       (const unsigned long long *)m->d_qrec.get(), nrec, m->minq, m->d_qmap.get());
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
@@ -2051,14 +2005,14 @@ static int count_record_piece(tsx_hip_map *m, const uint8_t *d, uint64_t len, bo
     if (len == 0) return TSX_HIP_OK;
     int rc;
     if (!last) {
-        if ((rc = grow(st, m->d_qrec, m->qrec_bytes, 64)) != TSX_HIP_OK) return rc;
-        unsigned long long *info = m->d_qrec;   // (read back before build_qmap reuses it)
+        if ((rc = grow(st, m->d_qrec, 64)) != TSX_HIP_OK) return rc;
+        unsigned long long *info = m->d_qrec.get();   // (read back before build_qmap reuses it)
         const uint64_t ntiles = (len + TILE - 1) / TILE;
-        HIP_TRY(hipMemsetAsync(m->d_carry, 0, sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
         HIP_TRY(hipMemsetAsync(info, 0, 4 * sizeof(unsigned long long), st));
         if ((rc = query_line_pass(m, d, len, len, 0, st)) != TSX_HIP_OK) return rc;
         hipLaunchKernelGGL(record_scan_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
-                           d, len, (const uint32_t *)m->d_tile, ntiles, (const uint32_t *)m->d_carry, m->p.line_mask + 1, 0,
+                           d, len, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), m->p.line_mask + 1, 0,
                            info, (unsigned long long *)nullptr, (uint64_t)0);
         HIP_TRY(hipGetLastError());
         unsigned long long h[2] = {0, 0};
@@ -2069,8 +2023,8 @@ static int count_record_piece(tsx_hip_map *m, const uint8_t *d, uint64_t len, bo
     }
     if ((rc = build_qmap(m, d, cut, st)) != TSX_HIP_OK) return rc;
     QmapScope qs(m);
-    m->qmap_cur = m->d_qmap;
-    HIP_TRY(hipMemsetAsync(m->d_carry, 0, sizeof(uint32_t), st));
+    m->qmap_cur = m->d_qmap.get();
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
     return run_fastq_piece(m, d, cut, cut, 0, st);
 }
 
@@ -2079,14 +2033,14 @@ static int count_record_piece(tsx_hip_map *m, const uint8_t *d, uint64_t len, bo
 static int count_host_records(tsx_hip_map *m, const char *text, size_t n) {
     int rc = ensure_staging(m, n);
     if (rc != TSX_HIP_OK) return rc;
-    hipStream_t st = m->stream;
+    hipStream_t st = m->stream.get();
     for (size_t off = 0; off < n;) {
         const size_t len = std::min(m->piece, n - off);
         const bool last = off + len == n;
-        parallel_memcpy(m->h_stage[0], text + off, len);
-        HIP_TRY(hipMemcpyAsync(m->d_stage[0], m->h_stage[0], len, hipMemcpyHostToDevice, st));
+        parallel_memcpy(m->h_stage[0].get(), text + off, len);
+        HIP_TRY(hipMemcpyAsync(m->d_stage[0].get(), m->h_stage[0].get(), len, hipMemcpyHostToDevice, st));
         uint64_t cut = 0;
-        if ((rc = count_record_piece(m, m->d_stage[0], len, last, st, cut)) != TSX_HIP_OK) return rc;
+        if ((rc = count_record_piece(m, m->d_stage[0].get(), len, last, st, cut)) != TSX_HIP_OK) return rc;
         if (cut == 0) {
             g_last_error = "min_qual_char: a record longer than a host piece (" + std::to_string(m->piece) + " bytes)";
             return TSX_HIP_ERANGE;
@@ -2106,10 +2060,10 @@ static int count_slabs(tsx_hip_map *m, const uint8_t *base, size_t n, hipStream_
     std::vector<size_t> doff(nwin + 1, 0);
     for (uint32_t w = 0; w < nwin; ++w) doff[w + 1] = doff[w] + std::min(WIN, n - (size_t)w * WIN) / 64 + 4096;
     // (scratch of the map, grown on demand: allocating and freeing gigabytes per call costs more than the kernels)
-    int rc = grow(st, m->d_slabdesc, m->slabdesc_bytes, doff[nwin] * 32 + (size_t)(nwin + 1) * 8);
+    int rc = grow(st, m->d_slabdesc, doff[nwin] * 32 + (size_t)(nwin + 1) * 8);
     if (rc != TSX_HIP_OK) return rc;
-    uint4 *d_desc = reinterpret_cast<uint4 *>(m->d_slabdesc);
-    unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(m->d_slabdesc + doff[nwin] * 32);
+    uint4 *d_desc = reinterpret_cast<uint4 *>(m->d_slabdesc.get());
+    unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(m->d_slabdesc.get() + doff[nwin] * 32);
     auto done = [&](int code) { m->ev_open.clear(); return code; };
     if (hipMemsetAsync(d_cnt, 0, (size_t)(nwin + 1) * 8, st) != hipSuccess) return done(TSX_HIP_EHIP);
     for (uint32_t w = 0; w < nwin && rc == TSX_HIP_OK; ++w) {
@@ -2140,13 +2094,10 @@ static int count_slabs(tsx_hip_map *m, const uint8_t *base, size_t n, hipStream_
         v.table = whole.table + ((uint64_t)s << v.l);
         v.seg_dirty = whole.seg_dirty + ((uint64_t)s << (v.l - v.S));
         m->fresh = fresh;
-        hipEvent_t *ev = nullptr;
+        Event *ev = nullptr;
         if (m->timing) {
-            if (m->ev_used + EV_N > m->ev.size())
-                for (int i = 0; i < EV_N; ++i) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) { rc = TSX_HIP_EHIP; break; } m->ev.push_back(e); }
-            if (rc != TSX_HIP_OK) break;
-            ev = &m->ev[m->ev_used]; m->ev_used += EV_N;
-            for (int i = 0; i < 4; ++i) if (hipEventRecord(ev[i], st) != hipSuccess) rc = TSX_HIP_EHIP;
+            if ((rc = next_timing_events(m, ev)) != TSX_HIP_OK) break;
+            for (int i = 0; i < 4; ++i) if (hipEventRecord(ev[i].get(), st) != hipSuccess) rc = TSX_HIP_EHIP;
         }
         for (uint32_t w = 0; w < nwin && rc == TSX_HIP_OK; ++w)
             rc = shard_walk(m, d_desc + doff[w] * 2, (size_t)cnt[w], 1, w, nwin, est, nullptr, st);
@@ -2154,7 +2105,7 @@ static int count_slabs(tsx_hip_map *m, const uint8_t *base, size_t n, hipStream_
             if (!m->sh_pl || !m->sh_pl->fused) rc = TSX_HIP_EINVAL;
             else rc = run_partition_build(m, *m->sh_pl, nullptr, nullptr, 0, st, ev);
         }
-        if (rc == TSX_HIP_OK && ev && hipEventRecord(ev[7], st) != hipSuccess) rc = TSX_HIP_EHIP;
+        if (rc == TSX_HIP_OK && ev && hipEventRecord(ev[7].get(), st) != hipSuccess) rc = TSX_HIP_EHIP;
     }
     m->p = whole;
     if (rc == TSX_HIP_OK) m->fresh = false;
@@ -2175,9 +2126,9 @@ extern "C" int tsx_hip_count_fastq_device(tsx_hip_map *m, const void *dev_text, 
     int rcq = base_rule_ok(m);
     if (rcq == TSX_HIP_OK && m->minq) rcq = build_qmap(m, base, n, st);
     if (rcq != TSX_HIP_OK) return rcq;
-    const uint16_t *qmap = m->minq ? m->d_qmap : nullptr;
+    const uint16_t *qmap = m->minq ? m->d_qmap.get() : nullptr;
     QmapScope qs(m);
-    HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));
     const size_t halo = (size_t)m->p.k - 1;
     const size_t DEV_WINDOW = dev_window_bytes();
     if (slab_bits(m) && (m->path == 2 || (m->path == 0 && n * 32 >= m->lay.table_bytes))) return count_slabs(m, base, n, st, qmap);
@@ -2247,10 +2198,8 @@ extern "C" int tsx_hip_bgzf_index_host(const void *gz, size_t n, size_t *members
 
 // Device scratch of the BGZF path: the compressed bytes and the member index of ONE batch of members.
 struct BgzfDev {
-    uint8_t *d_gz = nullptr, *d_ix = nullptr;
-    size_t gz_cap = 0, ix_cap = 0;
-    uint32_t *d_tab = nullptr;      // CRC-32 tables
-    ~BgzfDev() { (void)hipFree(d_gz); (void)hipFree(d_ix); (void)hipFree(d_tab); }
+    DevBuf<uint8_t> d_gz, d_ix;
+    DevBuf<uint32_t> d_tab;      // CRC-32 tables
 };
 
 // Members are inflated in BATCHES of at most this many bytes of text (whole members, at least one), so that a large
@@ -2287,24 +2236,22 @@ static int inflate_batch(const uint8_t *gz, size_t n, const BgzfIndex &ix, size_
             for (uint32_t i = 0; i < 256; ++i)
                 crc_tab[j * 256 + i] = (crc_tab[(j - 1) * 256 + i] >> 8) ^ crc_tab[crc_tab[(j - 1) * 256 + i] & 0xFFu];
     });
-    if (!dv.d_tab) {
-        HIP_TRY(hipMalloc((void **)&dv.d_tab, sizeof(crc_tab)));
-        HIP_TRY(hipMemcpyAsync(dv.d_tab, crc_tab, sizeof(crc_tab), hipMemcpyHostToDevice, st));
+    if (!dv.d_tab.get()) {
+        TSX_TRY(dv.d_tab.alloc(sizeof(crc_tab)));
+        HIP_TRY(hipMemcpyAsync(dv.d_tab.get(), crc_tab, sizeof(crc_tab), hipMemcpyHostToDevice, st));
         HIP_TRY(hipFuncSetAttribute((const void *)inflate_members_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)INF_LDS_BYTES));
     }
     const size_t lo = (size_t)ix.in_off[m0], hi = (size_t)ix.in_off[m1 - 1] + ix.in_len[m1 - 1];
     const size_t gz_bytes = std::min(n, hi + 16) - lo;       // the bit reader looks up to 16 bytes past a member
-    int rc = grow(st, dv.d_gz, dv.gz_cap, (hi - lo) + 64);
-    if (rc != TSX_HIP_OK) return rc;
+    TSX_TRY(grow(st, dv.d_gz, (hi - lo) + 64));
     // one allocation for the index: in_off | out_off | in_len | out_len | crc | status
-    rc = grow(st, dv.d_ix, dv.ix_cap, nm * (8 + 8 + 4 + 4 + 4 + 4));
-    if (rc != TSX_HIP_OK) return rc;
+    TSX_TRY(grow(st, dv.d_ix, nm * (8 + 8 + 4 + 4 + 4 + 4)));
     std::vector<uint64_t> in_off(nm), out_off(nm);
     for (size_t i = 0; i < nm; ++i) { in_off[i] = ix.in_off[m0 + i] - lo; out_off[i] = ix.out_off[m0 + i] - ix.out_off[m0]; }
-    uint64_t *d_in_off = (uint64_t *)dv.d_ix, *d_out_off = d_in_off + nm;
+    uint64_t *d_in_off = (uint64_t *)dv.d_ix.get(), *d_out_off = d_in_off + nm;
     uint32_t *d_in_len = (uint32_t *)(d_out_off + nm), *d_out_len = d_in_len + nm, *d_crc = d_out_len + nm, *d_status = d_crc + nm;
-    HIP_TRY(hipMemcpyAsync(dv.d_gz, gz + lo, gz_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dv.d_gz.get(), gz + lo, gz_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_in_off, in_off.data(), nm * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_out_off, out_off.data(), nm * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_in_len, ix.in_len.data() + m0, nm * 4, hipMemcpyHostToDevice, st));
@@ -2312,9 +2259,9 @@ static int inflate_batch(const uint8_t *gz, size_t n, const BgzfIndex &ix, size_
     HIP_TRY(hipMemcpyAsync(d_crc, ix.crc.data() + m0, nm * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(d_status, 0xFF, nm * 4, st));
     hipLaunchKernelGGL(inflate_members_kernel, dim3((uint32_t)((nm + INF_NT - 1) / INF_NT)), dim3(INF_NT), INF_LDS_BYTES, st,
-                       (const uint8_t *)dv.d_gz, (const uint64_t *)d_in_off, (const uint32_t *)d_in_len,
+                       (const uint8_t *)dv.d_gz.get(), (const uint64_t *)d_in_off, (const uint32_t *)d_in_len,
                        (const uint64_t *)d_out_off, (const uint32_t *)d_out_len, (const uint32_t *)d_crc, (uint32_t)nm, d_out,
-                       d_status, (const uint32_t *)dv.d_tab);
+                       d_status, (const uint32_t *)dv.d_tab.get());
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> status(nm);
     HIP_TRY(hipMemcpyAsync(status.data(), d_status, nm * 4, hipMemcpyDeviceToHost, st));
@@ -2343,22 +2290,19 @@ extern "C" int tsx_hip_inflate_bgzf_host(int device, const void *gz, size_t n, v
     if (ix.text_bytes > out_cap || (ix.text_bytes && !out_host)) return TSX_HIP_ERANGE;
     HIP_TRY(hipSetDevice(device));
     BgzfDev dv;
-    uint8_t *d_out = nullptr;
-    size_t out_have = 0;
+    DevBuf<uint8_t> d_out;
     const size_t batch = bgzf_batch_bytes();
-    int rc = TSX_HIP_OK;
-    for (size_t m0 = 0; m0 < ix.in_off.size() && rc == TSX_HIP_OK;) {
+    for (size_t m0 = 0; m0 < ix.in_off.size();) {
         const size_t m1 = bgzf_next_batch(ix, m0, batch), nb = bgzf_batch_text(ix, m0, m1);
-        rc = grow((hipStream_t) nullptr, d_out, out_have, nb + 256);
-        if (rc == TSX_HIP_OK) rc = inflate_batch((const uint8_t *)gz, n, ix, m0, m1, dv, d_out, nullptr);
-        if (rc == TSX_HIP_OK && nb && hipMemcpy((uint8_t *)out_host + ix.out_off[m0], d_out, nb, hipMemcpyDeviceToHost) != hipSuccess) {
+        TSX_TRY(grow((hipStream_t) nullptr, d_out, nb + 256));
+        TSX_TRY(inflate_batch((const uint8_t *)gz, n, ix, m0, m1, dv, d_out.get(), nullptr));
+        if (nb && hipMemcpy((uint8_t *)out_host + ix.out_off[m0], d_out.get(), nb, hipMemcpyDeviceToHost) != hipSuccess) {
             g_last_error = "hipMemcpy of the inflated text failed";
-            rc = TSX_HIP_EHIP;
+            return TSX_HIP_EHIP;
         }
         m0 = m1;
     }
-    (void)hipFree(d_out);
-    return rc;
+    return TSX_HIP_OK;
 }
 
 // The text never exists as a whole: batch b is inflated into one of two buffers BEHIND the last BGZF_PRE + 16 bytes
@@ -2377,12 +2321,13 @@ static int count_bgzf_records(tsx_hip_map *m, const uint8_t *gz, size_t n, const
     size_t biggest = 0;
     for (size_t m0 = 0; m0 < nm;) { const size_t m1 = bgzf_next_batch(ix, m0, batch); biggest = std::max(biggest, bgzf_batch_text(ix, m0, m1)); m0 = m1; }
     BgzfDev dv;
-    uint8_t *d_txt = nullptr, *d_tail = nullptr;
+    DevBuf<uint8_t> txt, tail;
     int rc = TSX_HIP_OK;
-    if (hipMalloc((void **)&d_txt, head + biggest + 256) != hipSuccess || hipMalloc((void **)&d_tail, head) != hipSuccess) {
+    if (txt.alloc(head + biggest + 256) != TSX_HIP_OK || tail.alloc(head) != TSX_HIP_OK) {
         g_last_error = "hipMalloc of a BGZF text buffer failed";
         rc = TSX_HIP_ENOMEM;
     }
+    uint8_t *const d_txt = txt.get(), *const d_tail = tail.get();
     size_t r = 0;   // bytes of the carried record in d_tail
     for (size_t m0 = 0; m0 < nm && rc == TSX_HIP_OK;) {
         const size_t m1 = bgzf_next_batch(ix, m0, batch), nb = bgzf_batch_text(ix, m0, m1);
@@ -2409,8 +2354,7 @@ static int count_bgzf_records(tsx_hip_map *m, const uint8_t *gz, size_t n, const
         if (hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }   // (d_txt is refilled next)
         m0 = m1;
     }
-    hipError_t e = hipStreamSynchronize(st);
-    (void)hipFree(d_txt); (void)hipFree(d_tail);
+    hipError_t e = hipStreamSynchronize(st);   // nothing queued may outlive the buffers
     if (rc == TSX_HIP_OK && e != hipSuccess) { g_last_error = hipGetErrorString(e); rc = TSX_HIP_EHIP; }
     return rc;
 }
@@ -2422,33 +2366,35 @@ extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, siz
     BgzfIndex ix;
     if (!bgzf_index((const uint8_t *)gz, n, ix)) { g_last_error = "not a BGZF file (no BC extra field in every gzip member)"; return TSX_HIP_EINVAL; }
     HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = m->stream;
+    hipStream_t st = m->stream.get();
     join_foreign(m, false);
     if (int rcq = base_rule_ok(m)) return rcq;
     if (m->minq) return count_bgzf_records(m, (const uint8_t *)gz, n, ix, st);
-    HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));
     const size_t batch = bgzf_batch_bytes(), nm = ix.in_off.size(), head = BGZF_PRE + 16;
     size_t biggest = 0;
     for (size_t m0 = 0; m0 < nm;) { const size_t m1 = bgzf_next_batch(ix, m0, batch); biggest = std::max(biggest, bgzf_batch_text(ix, m0, m1)); m0 = m1; }
+    // (the inflate stream is declared first: it outlives the buffers it fills)
+    Stream inflate_stream;
+    Event counted[2];
     BgzfDev dv;
-    uint8_t *d_txt[2] = {nullptr, nullptr};
+    DevBuf<uint8_t> txt[2];
     const size_t buf_bytes = head + biggest + 256;
     int rc = TSX_HIP_OK;
-    for (int i = 0; i < 2 && rc == TSX_HIP_OK; ++i)
-        if ((i == 0 || bgzf_next_batch(ix, 0, batch) < nm) && hipMalloc((void **)&d_txt[i], buf_bytes) != hipSuccess) {
+    for (int i = 0; i < 2 && rc == TSX_HIP_OK; ++i)   // (the second buffer only when a second batch exists)
+        if ((i == 0 || bgzf_next_batch(ix, 0, batch) < nm) && txt[i].alloc(buf_bytes) != TSX_HIP_OK) {
             g_last_error = "hipMalloc of a BGZF text buffer failed";
             rc = TSX_HIP_ENOMEM;
         }
+    uint8_t *const d_txt[2] = {txt[0].get(), txt[1].get()};
     // Batch i + 1 is copied to the device and inflated on a stream of its own while batch i is counted on the map's: the
     // inflate stream only waits for the count that last read the buffer it is about to fill (two batches back).
-    hipStream_t st_inf = nullptr;
-    hipEvent_t counted[2] = {nullptr, nullptr};
     if (rc == TSX_HIP_OK && d_txt[1] &&
-        (hipStreamCreateWithFlags(&st_inf, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&counted[0], hipEventDisableTiming) != hipSuccess ||
-         hipEventCreateWithFlags(&counted[1], hipEventDisableTiming) != hipSuccess)) {
+        (inflate_stream.create() != TSX_HIP_OK || counted[0].create() != TSX_HIP_OK || counted[1].create() != TSX_HIP_OK)) {
         g_last_error = "hipStreamCreate for the BGZF inflate stream failed";
         rc = TSX_HIP_EHIP;
     }
+    const hipStream_t st_inf = inflate_stream.get();
     size_t prev_len = 0;   // bytes of text in the previous batch's buffer, behind its head
     int b = 0;
     size_t nbatch = 0;
@@ -2457,13 +2403,13 @@ extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, siz
         const bool first = (m0 == 0), last = (m1 == nm);
         uint8_t *buf = d_txt[b];
         hipStream_t sti = st_inf ? st_inf : st;   // (one batch in all: everything on the map's stream)
-        if (st_inf && nbatch >= 2 && hipStreamWaitEvent(st_inf, counted[b], 0) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        if (st_inf && nbatch >= 2 && hipStreamWaitEvent(st_inf, counted[b].get(), 0) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         rc = inflate_batch((const uint8_t *)gz, n, ix, m0, m1, dv, buf + head, sti);   // (returns when the text is there)
         if (rc != TSX_HIP_OK) break;
         if (!first) {   // the end of the text so far (it may reach back into the previous buffer's own head)
             if (hipMemcpyAsync(buf, d_txt[b ^ 1] + prev_len, head, hipMemcpyDeviceToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
             // (the other buffer is free for the next batch's text only behind this copy as well)
-            if (st_inf && hipEventRecord(counted[b ^ 1], st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            if (st_inf && hipEventRecord(counted[b ^ 1].get(), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         }
         if (hipMemsetAsync(buf + head + nb, '\n', 256, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         // piece: from `from` (16-byte aligned) to the end of this batch's text; it owns all start positions but the
@@ -2471,37 +2417,29 @@ extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, siz
         const size_t from = first ? head : 16, len = head + nb - from;
         const size_t own = last ? len : (len > BGZF_PRE ? len - BGZF_PRE : 0);
         rc = run_fastq_piece(m, buf + from, len, own, first ? 0 : -1, st);
-        if (rc == TSX_HIP_OK && st_inf && hipEventRecord(counted[b], st) != hipSuccess) rc = TSX_HIP_EHIP;
+        if (rc == TSX_HIP_OK && st_inf && hipEventRecord(counted[b].get(), st) != hipSuccess) rc = TSX_HIP_EHIP;
         prev_len = nb;
         m0 = m1;
     }
-    hipError_t e = hipStreamSynchronize(st);
-    if (st_inf) { (void)hipStreamSynchronize(st_inf); (void)hipStreamDestroy(st_inf); }
-    for (hipEvent_t ev : counted) if (ev) (void)hipEventDestroy(ev);
-    (void)hipFree(d_txt[0]); (void)hipFree(d_txt[1]);
+    hipError_t e = hipStreamSynchronize(st);   // nothing queued may outlive the buffers
+    if (st_inf) (void)hipStreamSynchronize(st_inf);
     if (rc == TSX_HIP_OK && e != hipSuccess) { g_last_error = hipGetErrorString(e); rc = TSX_HIP_EHIP; }
     return rc;
 }
 
 static int ensure_staging(tsx_hip_map *m, size_t n) {
     const size_t bytes = std::min(m->piece, n) + STAGE_PAD + 128;
-    if (m->stage_bytes >= bytes) return TSX_HIP_OK;
-    for (int i = 0; i < 2; ++i) {  // grow: drop the smaller buffers first
-        if (m->h_stage[i]) { HIP_TRY(hipHostFree(m->h_stage[i])); m->h_stage[i] = nullptr; }
-        if (m->d_stage[i]) { HIP_TRY(hipFree(m->d_stage[i])); m->d_stage[i] = nullptr; }
-        if (m->stage_done[i]) { HIP_TRY(hipEventDestroy(m->stage_done[i])); m->stage_done[i] = nullptr; }
-        if (m->stage_in[i]) { HIP_TRY(hipEventDestroy(m->stage_in[i])); m->stage_in[i] = nullptr; }
+    if (m->d_stage[1].cap() >= bytes) return TSX_HIP_OK;   // (allocated last: there when all of them are)
+    auto drop = [&] { for (int i = 0; i < 2; ++i) { m->h_stage[i].reset(); m->d_stage[i].reset(); } };
+    drop();   // grow: drop the smaller buffers first
+    int rc = m->copy_stream.get() ? TSX_HIP_OK : m->copy_stream.create();
+    for (int i = 0; i < 2 && rc == TSX_HIP_OK; ++i) {
+        if ((rc = m->h_stage[i].alloc(bytes)) == TSX_HIP_OK) rc = m->d_stage[i].alloc(bytes);
+        if (rc == TSX_HIP_OK) rc = m->stage_done[i].create();
+        if (rc == TSX_HIP_OK) rc = m->stage_in[i].create();
     }
-    if (!m->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
-    m->stage_bytes = 0;
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(hipHostMalloc((void **)&m->h_stage[i], bytes, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&m->d_stage[i], bytes));
-        HIP_TRY(hipEventCreateWithFlags(&m->stage_done[i], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&m->stage_in[i], hipEventDisableTiming));
-    }
-    m->stage_bytes = bytes;
-    return TSX_HIP_OK;
+    if (rc != TSX_HIP_OK) drop();   // all four buffers or none
+    return rc;
 }
 
 // Pageable -> pinned staging copy on several host threads: one thread moves ~10 GB/s,
@@ -2528,26 +2466,23 @@ extern "C" int tsx_hip_count_fastq_host(tsx_hip_map *m, const char *text, size_t
     if (m->p.lg != m->p.l) return TSX_HIP_EINVAL;   // see tsx_hip_count_fastq_device
     if (n) m->used = true;
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipStreamSynchronize(m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream.get()));
     if (slab_bits(m) && (m->path == 2 || (m->path == 0 && n * 32 >= m->lay.table_bytes))) {
         // a table built slab by slab walks the whole text once per slab: the text goes to the device in one piece
-        uint8_t *d_text = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_text, n + 256));
-        int rcb = TSX_HIP_OK;
-        if (hipMemcpy(d_text, text, n, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_text + n, '\n', 256) != hipSuccess) rcb = TSX_HIP_EHIP;
-        if (rcb == TSX_HIP_OK) rcb = tsx_hip_count_fastq_device(m, d_text, n, nullptr);
-        if (rcb == TSX_HIP_OK) rcb = tsx_hip_sync(m);
-        (void)hipStreamSynchronize(m->stream);
-        (void)hipFree(d_text);
-        return rcb;
+        DevBuf<uint8_t> d_text;
+        TSX_TRY(d_text.alloc(n + 256));
+        SyncAtExit wait(m->stream.get());   // nothing queued may outlive the text
+        if (hipMemcpy(d_text.get(), text, n, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_text.get() + n, '\n', 256) != hipSuccess) return TSX_HIP_EHIP;
+        TSX_TRY(tsx_hip_count_fastq_device(m, d_text.get(), n, nullptr));
+        return tsx_hip_sync(m);
     }
     int rc = base_rule_ok(m);
     if (rc != TSX_HIP_OK) return rc;
     if (m->minq) return count_host_records(m, text, n);
     rc = ensure_staging(m, n);
     if (rc != TSX_HIP_OK) return rc;
-    hipStream_t st = m->stream;
-    HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));
+    hipStream_t st = m->stream.get();
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));
     // Pieces own m->piece start positions and carry a k-1 byte halo so that
     // windows beginning near the end of a piece see their last bytes.
     const size_t halo = (size_t)m->p.k - 1;
@@ -2558,15 +2493,15 @@ extern "C" int tsx_hip_count_fastq_host(tsx_hip_map *m, const char *text, size_t
         const size_t len = std::min(own + halo, n - off);
         // three legs overlap: this piece's host copy, the previous piece's H2D copy (its own stream)
         // and the kernels of the piece before that
-        if (used[buf]) HIP_TRY(hipEventSynchronize(m->stage_done[buf]));
-        parallel_memcpy(m->h_stage[buf], text + off, len);
-        HIP_TRY(hipMemcpyAsync(m->d_stage[buf], m->h_stage[buf], len, hipMemcpyHostToDevice, m->copy_stream));
-        HIP_TRY(hipEventRecord(m->stage_in[buf], m->copy_stream));
-        HIP_TRY(hipStreamWaitEvent(st, m->stage_in[buf], 0));
+        if (used[buf]) HIP_TRY(hipEventSynchronize(m->stage_done[buf].get()));
+        parallel_memcpy(m->h_stage[buf].get(), text + off, len);
+        HIP_TRY(hipMemcpyAsync(m->d_stage[buf].get(), m->h_stage[buf].get(), len, hipMemcpyHostToDevice, m->copy_stream.get()));
+        HIP_TRY(hipEventRecord(m->stage_in[buf].get(), m->copy_stream.get()));
+        HIP_TRY(hipStreamWaitEvent(st, m->stage_in[buf].get(), 0));
         const int head_open = (off > 0 && text[off - 1] != '\n') ? 1 : 0;
-        rc = run_fastq_piece(m, m->d_stage[buf], len, own, head_open, st);
+        rc = run_fastq_piece(m, m->d_stage[buf].get(), len, own, head_open, st);
         if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipEventRecord(m->stage_done[buf], st));
+        HIP_TRY(hipEventRecord(m->stage_done[buf].get(), st));
         used[buf] = true;
     }
     return tsx_hip_sync(m);
@@ -2581,11 +2516,11 @@ static inline size_t fa_bound(size_t n, int k) { return (n + (size_t)k + 16 + 15
 // Unwraps d_text[0, n) (16-byte aligned, 0 < n <= FA_PIECE_MAX) behind the carry in d_carry (FA_CARRY_BYTES, then
 // FA_INFO_WORDS info words) into d_out[0, out_end): the two-line text, then '\n' up to out_end.  Leaves the carry of the
 // next piece and the output's size (info word 0) on the device; does not wait.
-static int fasta_unwrap(const uint8_t *d_text, uint64_t n, uint32_t *d_carry, uint32_t kminus1, uint32_t *&d_ws, size_t &ws_bytes,
+static int fasta_unwrap(const uint8_t *d_text, uint64_t n, uint32_t *d_carry, uint32_t kminus1, DevBuf<uint32_t> &ws,
                         uint8_t *d_out, uint64_t out_end, int cus, hipStream_t st) {
     const uint64_t ntiles = (n + TILE - 1) / TILE, nchunks = (ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    int rc = grow(st, d_ws, ws_bytes, (size_t)ntiles * 24 + (size_t)nchunks * (FA_CHUNK_WORDS + 2) * 4 + 64);
-    if (rc != TSX_HIP_OK) return rc;
+    TSX_TRY(grow(st, ws, (size_t)ntiles * 24 + (size_t)nchunks * (FA_CHUNK_WORDS + 2) * 4 + 64));
+    uint32_t *const d_ws = ws.get();
     uint4 *summ = reinterpret_cast<uint4 *>(d_ws);
     uint32_t *tile_state = d_ws + ntiles * 4, *tile_pos = tile_state + ntiles, *chunk_fn = tile_pos + ntiles;
     uint32_t *chunk_in = chunk_fn + nchunks * FA_CHUNK_WORDS, *info = d_carry + FA_CARRY_BYTES / 4;
@@ -2621,8 +2556,8 @@ static int fasta_args_ok(const tsx_hip_map *m) {
     return TSX_HIP_OK;
 }
 static int fasta_begin(tsx_hip_map *m, hipStream_t st) {   // the carry of a new text: at a line start, no open record
-    if (!m->d_fa_carry) HIP_TRY(hipMalloc((void **)&m->d_fa_carry, FA_CARRY_BYTES + FA_INFO_WORDS * 4));
-    HIP_TRY(hipMemsetAsync(m->d_fa_carry, 0, FA_CARRY_BYTES + FA_INFO_WORDS * 4, st));
+    if (!m->d_fa_carry.get()) TSX_TRY(m->d_fa_carry.alloc(FA_CARRY_BYTES + FA_INFO_WORDS * 4));
+    HIP_TRY(hipMemsetAsync(m->d_fa_carry.get(), 0, FA_CARRY_BYTES + FA_INFO_WORDS * 4, st));
     return TSX_HIP_OK;
 }
 static inline bool slab_build_wanted(const tsx_hip_map *m, size_t n) {
@@ -2634,12 +2569,12 @@ static inline bool slab_build_wanted(const tsx_hip_map *m, size_t n) {
 static int fasta_count_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, hipStream_t st) {
     if (n == 0) return TSX_HIP_OK;
     const size_t ub = fa_bound(n, m->p.k);
-    int rc = grow(st, m->d_fa_out, m->fa_out_bytes, ub + FA_TAIL);
+    int rc = grow(st, m->d_fa_out, ub + FA_TAIL);
     if (rc == TSX_HIP_OK)
-        rc = fasta_unwrap(d_text, n, m->d_fa_carry, (uint32_t)m->p.k - 1u, m->d_fa_ws, m->fa_ws_bytes, m->d_fa_out, ub + FA_TAIL, m->cus, st);
+        rc = fasta_unwrap(d_text, n, m->d_fa_carry.get(), (uint32_t)m->p.k - 1u, m->d_fa_ws, m->d_fa_out.get(), ub + FA_TAIL, m->cus, st);
     if (rc != TSX_HIP_OK) return rc;
-    HIP_TRY(hipMemsetAsync(m->d_carry, 0, 64, st));   // (every unwrapped piece starts at a record boundary)
-    return run_fastq_piece(m, m->d_fa_out, ub, ub, 0, st);
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));   // (every unwrapped piece starts at a record boundary)
+    return run_fastq_piece(m, m->d_fa_out.get(), ub, ub, 0, st);
 }
 
 extern "C" int tsx_hip_count_fasta_device(tsx_hip_map *m, const void *dev_text, size_t n, void *stream) {
@@ -2660,16 +2595,16 @@ extern "C" int tsx_hip_count_fasta_device(tsx_hip_map *m, const void *dev_text, 
     // a table built slab by slab walks the whole text once per slab: every window's two-line text stays, back to back
     size_t total = 0;
     for (size_t off = 0; off < n; off += WIN) total += fa_bound(std::min(WIN, n - off), m->p.k);
-    if ((rc = grow(st, m->d_fa_out, m->fa_out_bytes, total + FA_TAIL)) != TSX_HIP_OK) return rc;
+    if ((rc = grow(st, m->d_fa_out, total + FA_TAIL)) != TSX_HIP_OK) return rc;
     size_t at = 0;
     for (size_t off = 0; off < n && rc == TSX_HIP_OK; off += WIN) {
         const size_t len = std::min(WIN, n - off), ub = fa_bound(len, m->p.k);
-        rc = fasta_unwrap(base + off, len, m->d_fa_carry, (uint32_t)m->p.k - 1u, m->d_fa_ws, m->fa_ws_bytes, m->d_fa_out + at,
+        rc = fasta_unwrap(base + off, len, m->d_fa_carry.get(), (uint32_t)m->p.k - 1u, m->d_fa_ws, m->d_fa_out.get() + at,
                           ub + (off + len == n ? FA_TAIL : 0), m->cus, st);
         at += ub;
     }
     if (rc != TSX_HIP_OK) return rc;
-    return tsx_hip_count_fastq_device(m, m->d_fa_out, total, stream);
+    return tsx_hip_count_fastq_device(m, m->d_fa_out.get(), total, stream);
 }
 
 extern "C" int tsx_hip_count_fasta_host(tsx_hip_map *m, const char *text, size_t n) {
@@ -2677,20 +2612,18 @@ extern "C" int tsx_hip_count_fasta_host(tsx_hip_map *m, const char *text, size_t
     if (int rca = fasta_args_ok(m)) return rca;
     if (n) m->used = true;
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipStreamSynchronize(m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream.get()));
     if (slab_build_wanted(m, n)) {   // the whole text resident, as tsx_hip_count_fastq_host does for such a table
-        uint8_t *d_text = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_text, n + 256));
-        int rcb = hipMemcpy(d_text, text, n, hipMemcpyHostToDevice) == hipSuccess ? TSX_HIP_OK : TSX_HIP_EHIP;
-        if (rcb == TSX_HIP_OK) rcb = tsx_hip_count_fasta_device(m, d_text, n, nullptr);
-        if (rcb == TSX_HIP_OK) rcb = tsx_hip_sync(m);
-        (void)hipStreamSynchronize(m->stream);
-        (void)hipFree(d_text);
-        return rcb;
+        DevBuf<uint8_t> d_text;
+        TSX_TRY(d_text.alloc(n + 256));
+        SyncAtExit wait(m->stream.get());   // nothing queued may outlive the text
+        if (hipMemcpy(d_text.get(), text, n, hipMemcpyHostToDevice) != hipSuccess) return TSX_HIP_EHIP;
+        TSX_TRY(tsx_hip_count_fasta_device(m, d_text.get(), n, nullptr));
+        return tsx_hip_sync(m);
     }
     int rc = ensure_staging(m, n);
     if (rc != TSX_HIP_OK) return rc;
-    hipStream_t st = m->stream;
+    hipStream_t st = m->stream.get();
     if ((rc = fasta_begin(m, st)) != TSX_HIP_OK) return rc;
     FastaScope fs(m);
     // pieces are cut anywhere and overlap nowhere: what a k-mer across the cut needs travels in the carry
@@ -2699,13 +2632,13 @@ extern "C" int tsx_hip_count_fasta_host(tsx_hip_map *m, const char *text, size_t
     bool used[2] = {false, false};
     for (size_t off = 0; off < n; off += piece, buf ^= 1) {
         const size_t len = std::min(piece, n - off);
-        if (used[buf]) HIP_TRY(hipEventSynchronize(m->stage_done[buf]));
-        parallel_memcpy(m->h_stage[buf], text + off, len);
-        HIP_TRY(hipMemcpyAsync(m->d_stage[buf], m->h_stage[buf], len, hipMemcpyHostToDevice, m->copy_stream));
-        HIP_TRY(hipEventRecord(m->stage_in[buf], m->copy_stream));
-        HIP_TRY(hipStreamWaitEvent(st, m->stage_in[buf], 0));
-        if ((rc = fasta_count_piece(m, m->d_stage[buf], len, st)) != TSX_HIP_OK) return rc;
-        HIP_TRY(hipEventRecord(m->stage_done[buf], st));
+        if (used[buf]) HIP_TRY(hipEventSynchronize(m->stage_done[buf].get()));
+        parallel_memcpy(m->h_stage[buf].get(), text + off, len);
+        HIP_TRY(hipMemcpyAsync(m->d_stage[buf].get(), m->h_stage[buf].get(), len, hipMemcpyHostToDevice, m->copy_stream.get()));
+        HIP_TRY(hipEventRecord(m->stage_in[buf].get(), m->copy_stream.get()));
+        HIP_TRY(hipStreamWaitEvent(st, m->stage_in[buf].get(), 0));
+        if ((rc = fasta_count_piece(m, m->d_stage[buf].get(), len, st)) != TSX_HIP_OK) return rc;
+        HIP_TRY(hipEventRecord(m->stage_done[buf].get(), st));
         used[buf] = true;
     }
     return tsx_hip_sync(m);
@@ -2719,7 +2652,7 @@ extern "C" int tsx_hip_count_fasta_bgzf_host(tsx_hip_map *m, const void *gz, siz
     BgzfIndex ix;
     if (!bgzf_index((const uint8_t *)gz, n, ix)) { g_last_error = "not a BGZF file (no BC extra field in every gzip member)"; return TSX_HIP_EINVAL; }
     HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = m->stream;
+    hipStream_t st = m->stream.get();
     join_foreign(m, false);
     int rc = fasta_begin(m, st);
     if (rc != TSX_HIP_OK) return rc;
@@ -2728,16 +2661,16 @@ extern "C" int tsx_hip_count_fasta_bgzf_host(tsx_hip_map *m, const void *gz, siz
     size_t biggest = 0;
     for (size_t m0 = 0; m0 < nm;) { const size_t m1 = bgzf_next_batch(ix, m0, batch); biggest = std::max(biggest, bgzf_batch_text(ix, m0, m1)); m0 = m1; }
     BgzfDev dv;
-    uint8_t *d_txt = nullptr;
-    if (hipMalloc((void **)&d_txt, biggest + 256) != hipSuccess) { g_last_error = "hipMalloc of a BGZF text buffer failed"; return TSX_HIP_ENOMEM; }
+    DevBuf<uint8_t> txt;
+    if (txt.alloc(biggest + 256) != TSX_HIP_OK) { g_last_error = "hipMalloc of a BGZF text buffer failed"; return TSX_HIP_ENOMEM; }
+    uint8_t *const d_txt = txt.get();
     for (size_t m0 = 0; m0 < nm && rc == TSX_HIP_OK;) {
         const size_t m1 = bgzf_next_batch(ix, m0, batch);
         rc = inflate_batch((const uint8_t *)gz, n, ix, m0, m1, dv, d_txt, st);   // (behind the count of the batch before)
         if (rc == TSX_HIP_OK) rc = fasta_count_piece(m, d_txt, bgzf_batch_text(ix, m0, m1), st);
         m0 = m1;
     }
-    hipError_t e = hipStreamSynchronize(st);
-    (void)hipFree(d_txt);
+    hipError_t e = hipStreamSynchronize(st);   // nothing queued may outlive the buffers
     if (rc == TSX_HIP_OK && e != hipSuccess) { g_last_error = hipGetErrorString(e); rc = TSX_HIP_EHIP; }
     return rc == TSX_HIP_OK ? tsx_hip_sync(m) : rc;
 }
@@ -2750,28 +2683,21 @@ extern "C" int tsx_hip_unwrap_fasta_host(int device, const char *text, size_t n,
     HIP_TRY(hipSetDevice(device));
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    uint8_t *d_text = nullptr, *d_out = nullptr;
-    uint32_t *d_carry = nullptr, *d_ws = nullptr;
-    size_t ws_bytes = 0;
+    DevBuf<uint8_t> d_text, d_out;
+    DevBuf<uint32_t> d_carry, d_ws;
     const size_t end = ((n + 2 + 15) & ~(size_t)15) + 16;
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc((void **)&d_text, n + 256));
-        HIP_TRY(hipMalloc((void **)&d_out, end));
-        HIP_TRY(hipMalloc((void **)&d_carry, FA_CARRY_BYTES + FA_INFO_WORDS * 4));
-        HIP_TRY(hipMemcpy(d_text, text, n, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(d_carry, 0, FA_CARRY_BYTES + FA_INFO_WORDS * 4));
-        int rc = fasta_unwrap(d_text, n, d_carry, 0u, d_ws, ws_bytes, d_out, end, cus, nullptr);
-        if (rc != TSX_HIP_OK) return rc;
-        uint32_t total = 0;
-        HIP_TRY(hipMemcpy(&total, d_carry + FA_CARRY_BYTES / 4, 4, hipMemcpyDeviceToHost));
-        *out_bytes = total ? (size_t)total + 1 : 0;   // the newline that ends the last record comes from the fill
-        if (*out_bytes > out_cap || (*out_bytes && !out_host)) return TSX_HIP_ERANGE;
-        if (*out_bytes) HIP_TRY(hipMemcpy(out_host, d_out, *out_bytes, hipMemcpyDeviceToHost));
-        return TSX_HIP_OK;
-    };
-    const int rc = run();
-    (void)hipFree(d_text); (void)hipFree(d_out); (void)hipFree(d_carry); (void)hipFree(d_ws);
-    return rc;
+    TSX_TRY(d_text.alloc(n + 256));
+    TSX_TRY(d_out.alloc(end));
+    TSX_TRY(d_carry.alloc(FA_CARRY_BYTES + FA_INFO_WORDS * 4));
+    HIP_TRY(hipMemcpy(d_text.get(), text, n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_carry.get(), 0, FA_CARRY_BYTES + FA_INFO_WORDS * 4));
+    TSX_TRY(fasta_unwrap(d_text.get(), n, d_carry.get(), 0u, d_ws, d_out.get(), end, cus, nullptr));
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpy(&total, d_carry.get() + FA_CARRY_BYTES / 4, 4, hipMemcpyDeviceToHost));
+    *out_bytes = total ? (size_t)total + 1 : 0;   // the newline that ends the last record comes from the fill
+    if (*out_bytes > out_cap || (*out_bytes && !out_host)) return TSX_HIP_ERANGE;
+    if (*out_bytes) HIP_TRY(hipMemcpy(out_host, d_out.get(), *out_bytes, hipMemcpyDeviceToHost));
+    return TSX_HIP_OK;
 }
 
 extern "C" int tsx_hip_add_kmers_device(tsx_hip_map *m, const void *dev_kmers, const void *dev_counts, size_t n,
@@ -2794,22 +2720,17 @@ extern "C" int tsx_hip_add_kmers_host(tsx_hip_map *m, const uint64_t *kmers, con
     if (!m || (!kmers && n)) return TSX_HIP_EINVAL;
     if (n == 0) return TSX_HIP_OK;
     HIP_TRY(hipSetDevice(m->device));
-    uint64_t *dk = nullptr, *dc = nullptr;
+    DevBuf<uint64_t> dk, dc;
     const size_t kb = n * (size_t)m->p.wk * 8;
-    HIP_TRY(hipMalloc((void **)&dk, kb));
-    int rc = TSX_HIP_OK;
-    do {
-        if (hipMemcpyAsync(dk, kmers, kb, hipMemcpyHostToDevice, m->stream) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        if (counts) {
-            if (hipMalloc((void **)&dc, n * 8) != hipSuccess) { rc = TSX_HIP_ENOMEM; break; }
-            if (hipMemcpyAsync(dc, counts, n * 8, hipMemcpyHostToDevice, m->stream) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        }
-        rc = tsx_hip_add_kmers_device(m, dk, dc, n, nullptr);
-        if (rc == TSX_HIP_OK) rc = tsx_hip_sync(m);
-    } while (0);
-    (void)hipStreamSynchronize(m->stream);
-    (void)hipFree(dk); (void)hipFree(dc);
-    return rc;
+    TSX_TRY(dk.alloc(kb));
+    SyncAtExit wait(m->stream.get());   // nothing queued may outlive the buffers
+    if (hipMemcpyAsync(dk.get(), kmers, kb, hipMemcpyHostToDevice, m->stream.get()) != hipSuccess) return TSX_HIP_EHIP;
+    if (counts) {
+        if (dc.alloc(n * 8) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+        if (hipMemcpyAsync(dc.get(), counts, n * 8, hipMemcpyHostToDevice, m->stream.get()) != hipSuccess) return TSX_HIP_EHIP;
+    }
+    TSX_TRY(tsx_hip_add_kmers_device(m, dk.get(), dc.get(), n, nullptr));
+    return tsx_hip_sync(m);
 }
 
 extern "C" int tsx_hip_get_counts_device(tsx_hip_map *m, const void *dev_kmers, size_t n, void *dev_counts_out,
@@ -2829,39 +2750,41 @@ extern "C" int tsx_hip_get_counts_device(tsx_hip_map *m, const void *dev_kmers, 
 }
 
 // Host-side lookups of a handful of k-mers (the reference calls getKmerCount one k-mer at a time,
-// main.cpp:285-330) go through a small device scratch kept with the map instead of hipMalloc/hipFree.
+// main.cpp:285-330) go through a small device scratch kept with the map instead of buffers of the call.
 static const size_t SMALL_LOOKUP = 256;
 static int lookup_host(tsx_hip_map *m, const uint64_t *kmers, size_t n, uint64_t *counts_out, uint64_t *slots_out) {
     if (!m || ((!kmers || !counts_out) && n)) return TSX_HIP_EINVAL;
     if (n == 0) return TSX_HIP_OK;
     HIP_TRY(hipSetDevice(m->device));
     join_foreign(m, false);
-    int rcz = ensure_zeroed(m, m->stream);
+    int rcz = ensure_zeroed(m, m->stream.get());
     if (rcz != TSX_HIP_OK) return rcz;
     const size_t wk = (size_t)m->p.wk, kb = n * wk * 8;
+    DevBuf<uint64_t> big_k, big_c;   // more than SMALL_LOOKUP k-mers: buffers of this call
     uint64_t *dk = nullptr, *dc = nullptr, *dp = nullptr;
     const bool small = n <= SMALL_LOOKUP;
     if (small) {
-        if (!m->d_small) HIP_TRY(hipMalloc((void **)&m->d_small, SMALL_LOOKUP * (4 + 2) * 8));
-        dk = m->d_small; dc = dk + SMALL_LOOKUP * 4; dp = dc + SMALL_LOOKUP;
+        if (!m->d_small.get()) TSX_TRY(m->d_small.alloc(SMALL_LOOKUP * (4 + 2) * 8));
+        dk = m->d_small.get(); dc = dk + SMALL_LOOKUP * 4; dp = dc + SMALL_LOOKUP;
     } else {
-        HIP_TRY(hipMalloc((void **)&dk, kb));
-        if (hipMalloc((void **)&dc, n * 16) != hipSuccess) { (void)hipFree(dk); return TSX_HIP_ENOMEM; }
-        dp = dc + n;
+        TSX_TRY(big_k.alloc(kb));
+        if (big_c.alloc(n * 16) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+        dk = big_k.get(); dc = big_c.get(); dp = dc + n;
     }
-    int rc = TSX_HIP_OK;
-    do {
-        if (hipMemcpyAsync(dk, kmers, kb, hipMemcpyHostToDevice, m->stream) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+    const hipStream_t st = m->stream.get();
+    auto run = [&]() -> int {
+        if (hipMemcpyAsync(dk, kmers, kb, hipMemcpyHostToDevice, st) != hipSuccess) return TSX_HIP_EHIP;
         const int grid = grid_for(m, n, 8);
-        DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((get_counts_kernel<WKV, CANV>), dim3(grid), dim3(NT), 0, m->stream,
+        DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((get_counts_kernel<WKV, CANV>), dim3(grid), dim3(NT), 0, st,
                                                             m->p, (const uint64_t *)dk, (uint64_t)n, dc,
                                                             slots_out ? dp : (uint64_t *)nullptr)));
-        if (hipGetLastError() != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        if (hipMemcpyAsync(counts_out, dc, n * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        if (slots_out && hipMemcpyAsync(slots_out, dp, n * 8, hipMemcpyDeviceToHost, m->stream) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        if (hipStreamSynchronize(m->stream) != hipSuccess) rc = TSX_HIP_EHIP;
-    } while (0);
-    if (!small) { (void)hipStreamSynchronize(m->stream); (void)hipFree(dk); (void)hipFree(dc); }
+        if (hipGetLastError() != hipSuccess) return TSX_HIP_EHIP;
+        if (hipMemcpyAsync(counts_out, dc, n * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return TSX_HIP_EHIP;
+        if (slots_out && hipMemcpyAsync(slots_out, dp, n * 8, hipMemcpyDeviceToHost, st) != hipSuccess) return TSX_HIP_EHIP;
+        return hipStreamSynchronize(st) == hipSuccess ? TSX_HIP_OK : TSX_HIP_EHIP;
+    };
+    const int rc = run();
+    if (!small) (void)hipStreamSynchronize(st);   // nothing queued may outlive the buffers of this call
     return rc;
 }
 
@@ -2876,15 +2799,14 @@ extern "C" int tsx_hip_kmer_starts_host(tsx_hip_map *m, uint8_t *bits_out, size_
     HIP_TRY(hipSetDevice(m->device));
     const uint64_t nb = (m->lay.slots + 7) / 8;
     join_foreign(m, false);
-    int rcz = ensure_zeroed(m, m->stream);
+    int rcz = ensure_zeroed(m, m->stream.get());
     if (rcz != TSX_HIP_OK) return rcz;
-    uint8_t *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, nb));
-    hipLaunchKernelGGL(kmer_starts_kernel, dim3(grid_for(m, nb, 8)), dim3(NT), 0, m->stream, m->p, d, nb);
+    DevBuf<uint8_t> d;
+    TSX_TRY(d.alloc(nb));
+    hipLaunchKernelGGL(kmer_starts_kernel, dim3(grid_for(m, nb, 8)), dim3(NT), 0, m->stream.get(), m->p, d.get(), nb);
     int rc = (hipGetLastError() == hipSuccess &&
-              hipMemcpyAsync(bits_out, d, nb, hipMemcpyDeviceToHost, m->stream) == hipSuccess &&
-              hipStreamSynchronize(m->stream) == hipSuccess) ? TSX_HIP_OK : TSX_HIP_EHIP;
-    (void)hipFree(d);
+              hipMemcpyAsync(bits_out, d.get(), nb, hipMemcpyDeviceToHost, m->stream.get()) == hipSuccess &&
+              hipStreamSynchronize(m->stream.get()) == hipSuccess) ? TSX_HIP_OK : TSX_HIP_EHIP;
     if (rc == TSX_HIP_OK && nbytes > nb) memset(bits_out + nb, 0, nbytes - nb);
     return rc;
 }
@@ -2893,16 +2815,18 @@ extern "C" int tsx_hip_get_counts_host(tsx_hip_map *m, const uint64_t *kmers, si
     return lookup_host(m, kmers, n, counts_out, nullptr);
 }
 
-// Word 7: entries of the deferred list of the last partitioned pass; words 0-6 are spare and read 0.  Not part of
-// include/tsxcount_hip.h.
+// Words 0-2: the owners alive in this process (tsx_own.h) -- device buffers, pinned buffers, events + streams; tests
+// take differences.  Word 7: entries of the deferred list of the last partitioned pass.  Words 3-6 are spare and
+// read 0.  Not part of include/tsxcount_hip.h.
 extern "C" int tsx_hip_debug_counters(tsx_hip_map *m, uint64_t *out8) {
     if (!m || !out8) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipStreamSynchronize(m->stream));
+    HIP_TRY(hipStreamSynchronize(m->stream.get()));
     for (int i = 0; i < 8; ++i) out8[i] = 0;
-    if (m->d_def_n) {
+    out8[0] = (uint64_t)g_live_dev.load(); out8[1] = (uint64_t)g_live_pin.load(); out8[2] = (uint64_t)g_live_sync.load();
+    if (m->d_def_n.get()) {
         unsigned long long dn = 0;
-        HIP_TRY(hipMemcpy(&dn, m->d_def_n, 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&dn, m->d_def_n.get(), 8, hipMemcpyDeviceToHost));
         out8[7] = dn;
     }
     return TSX_HIP_OK;
@@ -2912,12 +2836,12 @@ extern "C" int tsx_hip_get_stats(tsx_hip_map *m, tsx_hip_stats *out) {
     if (!m || !out) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     join_foreign(m, false);
-    int rcz = ensure_zeroed(m, m->stream);
+    int rcz = ensure_zeroed(m, m->stream.get());
     if (rcz != TSX_HIP_OK) return rcz;
-    HIP_TRY(hipMemsetAsync(m->p.stats + ST_SCRATCH, 0, 2 * sizeof(unsigned long long), m->stream));
-    HIP_TRY(hipMemsetAsync(m->p.stats + ST_SCRATCH3, 0, sizeof(unsigned long long), m->stream));
+    HIP_TRY(hipMemsetAsync(m->p.stats + ST_SCRATCH, 0, 2 * sizeof(unsigned long long), m->stream.get()));
+    HIP_TRY(hipMemsetAsync(m->p.stats + ST_SCRATCH3, 0, sizeof(unsigned long long), m->stream.get()));
     const int grid = grid_for(m, m->lay.slots, 8);
-    hipLaunchKernelGGL(occupied_kernel, dim3(grid), dim3(NT), 0, m->stream, m->p);
+    hipLaunchKernelGGL(occupied_kernel, dim3(grid), dim3(NT), 0, m->stream.get(), m->p);
     HIP_TRY(hipGetLastError());
     unsigned long long st[ST_N];
     int rc = read_stats(m, st);
@@ -2944,7 +2868,7 @@ static int dump_slots(tsx_hip_map *m, int nranks, uint64_t slot_lo, uint64_t slo
     int rcz = ensure_zeroed(m, st);
     if (rcz != TSX_HIP_OK) return rcz;
     const int grid = grid_for(m, std::max<uint64_t>(1, slot_hi - slot_lo), 8);
-    unsigned long long *seg = m->d_seg;
+    unsigned long long *seg = m->d_seg.get();
     HIP_TRY(hipMemsetAsync(seg, 0, 64 * sizeof(unsigned long long), st));
     DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((dump_kernel<WKV, CANV>), dim3(grid), dim3(NT), 0, st, m->p, nranks, 0,
                                                         (uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0, seg, slot_lo,
@@ -2993,19 +2917,15 @@ extern "C" int tsx_hip_dump_host(tsx_hip_map *m, uint64_t *kmers_out, uint64_t *
     if (s.distinct > cap) return TSX_HIP_ERANGE;
     *n_out = (size_t)s.distinct;
     if (s.distinct == 0) return TSX_HIP_OK;
-    uint64_t *dk = nullptr, *dc = nullptr, *dn = nullptr;
+    DevBuf<uint64_t> dk, dc, dn;
     const size_t kb = (size_t)s.distinct * m->p.wk * 8;
-    HIP_TRY(hipMalloc((void **)&dk, kb));
-    if (hipMalloc((void **)&dc, s.distinct * 8) != hipSuccess) { (void)hipFree(dk); return TSX_HIP_ENOMEM; }
-    if (hipMalloc((void **)&dn, 64) != hipSuccess) { (void)hipFree(dk); (void)hipFree(dc); return TSX_HIP_ENOMEM; }
-    rc = tsx_hip_dump_device(m, dk, dc, (size_t)s.distinct, dn, nullptr);
-    if (rc == TSX_HIP_OK) {
-        if (hipMemcpy(kmers_out, dk, kb, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(counts_out, dc, s.distinct * 8, hipMemcpyDeviceToHost) != hipSuccess)
-            rc = TSX_HIP_EHIP;
-    }
-    (void)hipFree(dk); (void)hipFree(dc); (void)hipFree(dn);
-    return rc;
+    TSX_TRY(dk.alloc(kb));
+    if (dc.alloc(s.distinct * 8) != TSX_HIP_OK || dn.alloc(64) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+    TSX_TRY(tsx_hip_dump_device(m, dk.get(), dc.get(), (size_t)s.distinct, dn.get(), nullptr));
+    if (hipMemcpy(kmers_out, dk.get(), kb, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(counts_out, dc.get(), s.distinct * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return TSX_HIP_EHIP;
+    return TSX_HIP_OK;
 }
 
 // ---- output: abundance histogram and the .count text (tsx_output.h) -------------
@@ -3043,14 +2963,13 @@ extern "C" int tsx_hip_histogram_host(tsx_hip_map *m, uint64_t *hist_out, size_t
     if (!m || !hist_out || nbins < 2) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     join_foreign(m, false);
-    void *d = nullptr;
-    HIP_TRY(hipMalloc(&d, nbins * sizeof(uint64_t)));
-    int rc = tsx_hip_histogram_device(m, 0, m->lay.slots, nbins, d, nullptr);
-    if (rc == TSX_HIP_OK && (hipMemcpyAsync(hist_out, d, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream) != hipSuccess ||
-                             hipStreamSynchronize(m->stream) != hipSuccess))
-        rc = TSX_HIP_EHIP;
-    (void)hipFree(d);
-    return rc;
+    DevBuf<uint64_t> d;
+    TSX_TRY(d.alloc(nbins * sizeof(uint64_t)));
+    TSX_TRY(tsx_hip_histogram_device(m, 0, m->lay.slots, nbins, d.get(), nullptr));
+    if (hipMemcpyAsync(hist_out, d.get(), nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream.get()) != hipSuccess ||
+        hipStreamSynchronize(m->stream.get()) != hipSuccess)
+        return TSX_HIP_EHIP;
+    return TSX_HIP_OK;
 }
 
 // Zero the two counters and queue format_counts_kernel over [slot_lo, slot_hi) (nothing to format: counters only).
@@ -3113,21 +3032,23 @@ extern "C" int tsx_hip_write_counts_host(tsx_hip_map *m, int fd, uint64_t lower,
     const int nbuf = nchunks > 1 ? 2 : 1;
     HIP_TRY(hipSetDevice(m->device));
     join_foreign(m, false);
-    hipStream_t st = m->stream;
+    hipStream_t st = m->stream.get();
     int rc = ensure_zeroed(m, st);
     if (rc != TSX_HIP_OK) return rc;
-    uint8_t *d_text[2] = {nullptr, nullptr}, *h_text[2] = {nullptr, nullptr};
-    unsigned long long *d_cnt = nullptr, *h_cnt = nullptr;
-    hipEvent_t ev_cnt = nullptr, ev_txt = nullptr;
-    if (hipMalloc((void **)&d_cnt, 2 * sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc((void **)&h_cnt, 2 * sizeof(unsigned long long)) != hipSuccess)
-        rc = TSX_HIP_ENOMEM;
-    for (int b = 0; b < nbuf && rc == TSX_HIP_OK; ++b)
-        if (hipMalloc((void **)&d_text[b], buf) != hipSuccess || hipHostMalloc((void **)&h_text[b], buf) != hipSuccess)
-            rc = TSX_HIP_ENOMEM;
-    if (rc == TSX_HIP_OK && (hipEventCreateWithFlags(&ev_cnt, hipEventDisableTiming) != hipSuccess ||
-                             hipEventCreateWithFlags(&ev_txt, hipEventDisableTiming) != hipSuccess))
-        rc = TSX_HIP_EHIP;
+    DevBuf<uint8_t> dev_text[2];
+    PinBuf<uint8_t> host_text[2];
+    DevBuf<unsigned long long> dev_cnt;
+    PinBuf<unsigned long long> host_cnt;
+    Event cnt_ready, txt_ready;
+    SyncAtExit wait(st);   // nothing queued may outlive the buffers
+    if (dev_cnt.alloc(2 * sizeof(unsigned long long)) != TSX_HIP_OK || host_cnt.alloc(2 * sizeof(unsigned long long)) != TSX_HIP_OK)
+        return TSX_HIP_ENOMEM;
+    for (int b = 0; b < nbuf; ++b)   // (the second pair only when a second chunk exists)
+        if (dev_text[b].alloc(buf) != TSX_HIP_OK || host_text[b].alloc(buf) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+    if (cnt_ready.create() != TSX_HIP_OK || txt_ready.create() != TSX_HIP_OK) return TSX_HIP_EHIP;
+    uint8_t *const d_text[2] = {dev_text[0].get(), dev_text[1].get()}, *const h_text[2] = {host_text[0].get(), host_text[1].get()};
+    unsigned long long *const d_cnt = dev_cnt.get(), *const h_cnt = host_cnt.get();
+    const hipEvent_t ev_cnt = cnt_ready.get(), ev_txt = txt_ready.get();
     // stream order: fmt(0) cnt(0) | txt(0) fmt(1) cnt(1) | txt(1) fmt(2) cnt(2) | ...
     auto queue_chunk = [&](uint64_t i) {
         const uint64_t lo = i * per, hi = std::min(slots, lo + per);
@@ -3151,15 +3072,6 @@ extern "C" int tsx_hip_write_counts_host(tsx_hip_map *m, int fd, uint64_t lower,
         rc = write_all(fd, h_text[b], nb);
         if (rc == TSX_HIP_OK) { lines += nl; bytes += nb; }
     }
-    (void)hipStreamSynchronize(st);   // nothing queued may outlive the buffers
-    for (int b = 0; b < 2; ++b) {
-        if (d_text[b]) (void)hipFree(d_text[b]);
-        if (h_text[b]) (void)hipHostFree(h_text[b]);
-    }
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (h_cnt) (void)hipHostFree(h_cnt);
-    if (ev_cnt) (void)hipEventDestroy(ev_cnt);
-    if (ev_txt) (void)hipEventDestroy(ev_txt);
     if (lines_out) *lines_out = lines;
     if (bytes_out) *bytes_out = bytes;
     return rc;
@@ -3271,15 +3183,16 @@ extern "C" int tsx_hip_save_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
     tsx_hip_stats s;
     int rc = tsx_hip_get_stats(m, &s);   // (zeroes a lazily cleared table; waits for everything queued)
     if (rc != TSX_HIP_OK) return rc;
-    hipStream_t st = m->stream;
+    hipStream_t st = m->stream.get();
     // carry records, sorted by slot (the file does not depend on the secondary array's probe order)
     const int RW = 2 + W;
     std::vector<uint64_t> carry((size_t)s.overflow_used * RW);
     if (s.overflow_used) {
-        uint64_t *d_rec = nullptr;
-        unsigned long long *d_n = nullptr, h_n = 0;
-        HIP_TRY(hipMalloc((void **)&d_rec, carry.size() * 8 + 8));
-        d_n = (unsigned long long *)(d_rec + carry.size());
+        DevBuf<uint64_t> rec;
+        TSX_TRY(rec.alloc(carry.size() * 8 + 8));
+        uint64_t *const d_rec = rec.get();
+        unsigned long long *const d_n = (unsigned long long *)(d_rec + carry.size());
+        unsigned long long h_n = 0;
         rc = TSX_HIP_OK;
         if (hipMemsetAsync(d_n, 0, 8, st) != hipSuccess) rc = TSX_HIP_EHIP;
         if (rc == TSX_HIP_OK) {
@@ -3290,7 +3203,6 @@ extern "C" int tsx_hip_save_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
                 hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
                 rc = TSX_HIP_EHIP;
         }
-        (void)hipFree(d_rec);
         if (rc != TSX_HIP_OK) return rc;
         if (h_n != s.overflow_used) { g_last_error = "secondary array changed during the save"; return TSX_HIP_EHIP; }
         std::vector<uint64_t> order(s.overflow_used), sorted(carry.size());
@@ -3319,18 +3231,18 @@ extern "C" int tsx_hip_save_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
     const uint64_t nchunks = (slots + span - 1) / span, ntmax = db_tiles(0, span);
     const size_t buf = (size_t)(span / 64 + span * W) * 8;
     const int nbuf = nchunks > 1 ? 2 : 1;
-    uint64_t *d_buf[2] = {nullptr, nullptr}, *h_buf[2] = {nullptr, nullptr};
-    unsigned long long *d_tile = nullptr, *d_sum = nullptr, *h_res = nullptr;
-    hipEvent_t ev_res = nullptr, ev_buf = nullptr;
-    if (hipMalloc((void **)&d_tile, (ntmax + 2) * 8) != hipSuccess || hipHostMalloc((void **)&h_res, 2 * 8) != hipSuccess)
-        rc = TSX_HIP_ENOMEM;
-    d_sum = d_tile ? d_tile + ntmax + 1 : nullptr;
-    for (int b = 0; b < nbuf && rc == TSX_HIP_OK; ++b)
-        if (hipMalloc((void **)&d_buf[b], buf) != hipSuccess || hipHostMalloc((void **)&h_buf[b], buf) != hipSuccess)
-            rc = TSX_HIP_ENOMEM;
-    if (rc == TSX_HIP_OK && (hipEventCreateWithFlags(&ev_res, hipEventDisableTiming) != hipSuccess ||
-                             hipEventCreateWithFlags(&ev_buf, hipEventDisableTiming) != hipSuccess))
-        rc = TSX_HIP_EHIP;
+    DevBuf<uint64_t> dev_buf[2];
+    PinBuf<uint64_t> host_buf[2];
+    DevBuf<unsigned long long> dev_tile;
+    PinBuf<unsigned long long> host_res;
+    Event res_ready, buf_ready;
+    if (dev_tile.alloc((ntmax + 2) * 8) != TSX_HIP_OK || host_res.alloc(2 * 8) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
+    for (int b = 0; b < nbuf && rc == TSX_HIP_OK; ++b)   // (the second pair only when a second chunk exists)
+        if (dev_buf[b].alloc(buf) != TSX_HIP_OK || host_buf[b].alloc(buf) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
+    if (rc == TSX_HIP_OK && (res_ready.create() != TSX_HIP_OK || buf_ready.create() != TSX_HIP_OK)) rc = TSX_HIP_EHIP;
+    uint64_t *const d_buf[2] = {dev_buf[0].get(), dev_buf[1].get()}, *const h_buf[2] = {host_buf[0].get(), host_buf[1].get()};
+    unsigned long long *const d_tile = dev_tile.get(), *const d_sum = d_tile ? d_tile + ntmax + 1 : nullptr, *const h_res = host_res.get();
+    const hipEvent_t ev_res = res_ready.get(), ev_buf = buf_ready.get();
     auto queue_chunk = [&](uint64_t i) {
         const uint64_t lo = i * span, hi = std::min(slots, lo + span), nt = db_tiles(lo, hi);
         uint64_t *bm = d_buf[i & 1], *ent = bm + span / 64;
@@ -3365,14 +3277,6 @@ extern "C" int tsx_hip_save_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
         if (rc == TSX_HIP_OK) { bytes += DB_CHUNK_HEAD + bmb + entb; entries += n; }
     }
     (void)hipStreamSynchronize(st);   // nothing queued may outlive the buffers
-    for (int b = 0; b < 2; ++b) {
-        if (d_buf[b]) (void)hipFree(d_buf[b]);
-        if (h_buf[b]) (void)hipHostFree(h_buf[b]);
-    }
-    if (d_tile) (void)hipFree(d_tile);
-    if (h_res) (void)hipHostFree(h_res);
-    if (ev_res) (void)hipEventDestroy(ev_res);
-    if (ev_buf) (void)hipEventDestroy(ev_buf);
     if (rc == TSX_HIP_OK) {
         const uint64_t end[4] = {slots, slots, 0, 0};
         rc = write_all(fd, (const uint8_t *)end, DB_CHUNK_HEAD);
@@ -3387,28 +3291,20 @@ extern "C" int tsx_hip_save_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
 // Staging of one chunk of the load (two of them alternate): the file bytes in pinned memory and on the device, the tile
 // offsets, the k-mers and counts of the re-insert path, and the result words of the load kernels.
 struct DbStage {
-    uint8_t *h = nullptr, *d = nullptr;
-    size_t cap = 0;
-    unsigned long long *d_tile = nullptr; uint64_t tile_cap = 0;
-    uint64_t *d_kx = nullptr; uint64_t kx_cap = 0;   // kmers (WK words) then counts, per entry
-    unsigned long long *d_res = nullptr, *h_res = nullptr;
-    hipEvent_t done = nullptr;
+    PinBuf<uint8_t> h;
+    DevBuf<uint8_t> d;
+    DevBuf<unsigned long long> d_tile;
+    DevBuf<uint64_t> d_kx;                            // kmers (WK words) then counts, per entry
+    DevBuf<unsigned long long> d_res;
+    PinBuf<unsigned long long> h_res;
+    Event done;
     bool busy = false;
     uint64_t n = 0, sum = 0;                          // what the chunk's head promised
     uint64_t zero_carried = 0;                        // its entries with in-slot count 0 that a carry record names
-    void release() {
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        if (d_tile) (void)hipFree(d_tile);
-        if (d_kx) (void)hipFree(d_kx);
-        if (d_res) (void)hipFree(d_res);
-        if (h_res) (void)hipHostFree(h_res);
-        if (done) (void)hipEventDestroy(done);
-    }
 };
 
 // The database layout as TableParams (what words_to_kmer needs), with its inverse mapping uploaded to *d_ilut.
-static int db_source_params(const tsx_hip_db_info &d, TableParams &sp, uint64_t **d_ilut) {
+static int db_source_params(const tsx_hip_db_info &d, TableParams &sp, DevBuf<uint64_t> *d_ilut) {
     tsx_hip_map src;   // host fields only: no device allocations
     if (derive_layout(&src, d.k, d.l, d.count_bits, d.overflow_l, 0, 0) != TSX_HIP_OK || src.p.W != d.entry_limbs ||
         src.p.F != d.func_bits || src.p.R != d.reprobe_bits || src.p.C != d.count_bits)
@@ -3420,22 +3316,13 @@ static int db_source_params(const tsx_hip_db_info &d, TableParams &sp, uint64_t 
         int rc = make_mapping(&src);
         if (rc != TSX_HIP_OK) return rc;
         make_lut(&src, src.irows, src.ilut);
-        HIP_TRY(hipMalloc((void **)d_ilut, src.ilut.size() * 8));
-        HIP_TRY(hipMemcpy(*d_ilut, src.ilut.data(), src.ilut.size() * 8, hipMemcpyHostToDevice));
-        src.p.ilut = *d_ilut;
+        TSX_TRY(d_ilut->alloc(src.ilut.size() * 8));
+        HIP_TRY(hipMemcpy(d_ilut->get(), src.ilut.data(), src.ilut.size() * 8, hipMemcpyHostToDevice));
+        src.p.ilut = d_ilut->get();
     }
     src.p.table = nullptr; src.p.sec_keys = src.p.sec_cnt = nullptr; src.p.stats = nullptr; src.p.lut = nullptr;
     src.p.roll = nullptr; src.p.seg_dirty = nullptr;
     sp = src.p;
-    return TSX_HIP_OK;
-}
-
-template <typename T> static int db_grow_dev(T *&p, uint64_t &have, uint64_t need) {
-    if (need <= have) return TSX_HIP_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr; have = 0;
-    HIP_TRY(hipMalloc((void **)&p, need * sizeof(T)));
-    have = need;
     return TSX_HIP_OK;
 }
 
@@ -3457,18 +3344,19 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
     }
     HIP_TRY(hipSetDevice(m->device));
     join_foreign(m, false);
-    hipStream_t st = m->stream;
+    hipStream_t st = m->stream.get();
     TableParams sp;
-    uint64_t *d_ilut = nullptr;
+    DevBuf<uint64_t> d_ilut;
     const bool direct = !m->used && d.l == m->p.l && d.entry_limbs == m->p.W && d.func_bits == m->p.F &&
                         d.reprobe_bits == m->p.R && d.count_bits == m->p.C && d.seg_bits == m->p.S && d.hash_seed == m->seed;
     rc = db_source_params(d, sp, direct ? nullptr : &d_ilut);
-    if (rc != TSX_HIP_OK) { (void)hipFree(d_ilut); return rc; }
+    if (rc != TSX_HIP_OK) return rc;
     if (direct) sp = m->p;
     const int W = d.entry_limbs, RW = 2 + W, WK = m->p.wk;
     const uint64_t slots = 1ULL << d.l;
     unsigned long long kmers_before = 0;
     DbStage sg[2];
+    DevBuf<uint64_t> carry;
     uint64_t *d_carry = nullptr;
     std::vector<uint64_t> rec;   // the carry records: each is checked against the chunk that holds its pos
     uint64_t entries = 0;
@@ -3494,7 +3382,8 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
             }
             if (rc != TSX_HIP_OK) break;
             const size_t kx = direct ? 0 : (size_t)d.carry_records * (WK + 1);
-            if (hipMalloc((void **)&d_carry, (rec.size() + kx) * 8) != hipSuccess) { rc = TSX_HIP_ENOMEM; break; }
+            if (carry.alloc((rec.size() + kx) * 8) != TSX_HIP_OK) { rc = TSX_HIP_ENOMEM; break; }
+            d_carry = carry.get();
             if (hipMemcpyAsync(d_carry, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
             const int grid = grid_for(m, d.carry_records, 8);
             uint64_t *kx_k = d_carry + rec.size(), *kx_c = kx_k + (size_t)d.carry_records * WK;
@@ -3511,16 +3400,16 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
         }
         // chunks: the host reads chunk i + 1 while the device places chunk i
         for (int b = 0; b < 2 && rc == TSX_HIP_OK; ++b) {
-            if (hipEventCreateWithFlags(&sg[b].done, hipEventDisableTiming) != hipSuccess ||
-                hipMalloc((void **)&sg[b].d_res, DB_RES_N * 8) != hipSuccess ||
-                hipHostMalloc((void **)&sg[b].h_res, DB_RES_N * 8) != hipSuccess) rc = TSX_HIP_ENOMEM;
+            if (sg[b].done.create() != TSX_HIP_OK || sg[b].d_res.alloc(DB_RES_N * 8) != TSX_HIP_OK ||
+                sg[b].h_res.alloc(DB_RES_N * 8) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
         }
         auto finish = [&](DbStage &s) -> int {   // the result of a chunk whose work has finished
             s.busy = false;
-            if (s.h_res[DB_RES_TOTAL] != s.n) return db_fail("k-mer database chunk: bitmap and entry count disagree");
-            if (s.h_res[DB_RES_BAD]) return db_fail("k-mer database chunk: malformed entries");
-            if (s.h_res[DB_RES_SUM] != s.sum) return db_fail("k-mer database chunk checksum mismatch");
-            if (s.h_res[DB_RES_ZERO] != s.zero_carried) return db_fail("k-mer database chunk: an entry with count 0");
+            const unsigned long long *res = s.h_res.get();
+            if (res[DB_RES_TOTAL] != s.n) return db_fail("k-mer database chunk: bitmap and entry count disagree");
+            if (res[DB_RES_BAD]) return db_fail("k-mer database chunk: malformed entries");
+            if (res[DB_RES_SUM] != s.sum) return db_fail("k-mer database chunk checksum mismatch");
+            if (res[DB_RES_ZERO] != s.zero_carried) return db_fail("k-mer database chunk: an entry with count 0");
             entries += s.n;
             return TSX_HIP_OK;
         };
@@ -3529,7 +3418,7 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
         for (uint64_t i = 0; rc == TSX_HIP_OK && !ended; ++i) {
             DbStage &s = sg[i & 1];
             if (s.busy) {
-                if (hipEventSynchronize(s.done) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+                if (hipEventSynchronize(s.done.get()) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
                 if ((rc = finish(s)) != TSX_HIP_OK) break;
             }
             uint64_t ch[4];
@@ -3541,23 +3430,20 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
             expect_lo = hi;
             const uint64_t nbm = (hi - lo + 63) / 64, nt = db_tiles(lo, hi);
             const size_t bytes = (size_t)(nbm + n * W) * 8;
-            if (bytes > s.cap) {   // grow-only; chunk_bytes is the first size
-                if (s.h) (void)hipHostFree(s.h);
-                if (s.d) (void)hipFree(s.d);
-                s.h = s.d = nullptr; s.cap = 0;
-                const size_t want = std::max(bytes, std::min(chunk_bytes, (size_t)(slots / 64 + slots * W) * 8));
-                if (hipHostMalloc((void **)&s.h, want) != hipSuccess || hipMalloc((void **)&s.d, want) != hipSuccess) { rc = TSX_HIP_ENOMEM; break; }
-                s.cap = want;
-            }
-            if ((rc = db_grow_dev(s.d_tile, s.tile_cap, nt + 1)) != TSX_HIP_OK) break;
-            if (!direct && (rc = db_grow_dev(s.d_kx, s.kx_cap, std::max<uint64_t>(1, n) * (WK + 1))) != TSX_HIP_OK) break;
-            if ((rc = db_read_exact(fd, s.h, bytes, "chunk")) != TSX_HIP_OK) break;
+            // grow-only; chunk_bytes is the first size.  (No wait: s.done has been waited for, nothing reads the stage.)
+            const size_t want = std::max(bytes, std::min(chunk_bytes, (size_t)(slots / 64 + slots * W) * 8));
+            if (bytes > s.d.cap()) s.h.reset();   // (both or none: d is allocated last)
+            if (s.h.reserve(nullptr, bytes, want) != TSX_HIP_OK || s.d.reserve(nullptr, bytes, want) != TSX_HIP_OK) { rc = TSX_HIP_ENOMEM; break; }
+            if ((rc = s.d_tile.reserve(nullptr, (nt + 1) * 8, (nt + 1) * 8)) != TSX_HIP_OK) break;
+            const size_t kxb = (size_t)std::max<uint64_t>(1, n) * (WK + 1) * 8;
+            if (!direct && (rc = s.d_kx.reserve(nullptr, kxb, kxb)) != TSX_HIP_OK) break;
+            if ((rc = db_read_exact(fd, s.h.get(), bytes, "chunk")) != TSX_HIP_OK) break;
             s.n = n; s.sum = ch[3];
             // the carry records of this chunk (sorted, so they come in order): slot pos must be occupied and hold the
             // record's words; a popcount of the bitmap up to pos gives the entry's index.  In-slot counts of 0 are
             // counted here and compared with the device's count of them, so that no entry's total count is 0.
             {
-                const uint64_t *hbm = (const uint64_t *)s.h, *hent = hbm + nbm;
+                const uint64_t *hbm = (const uint64_t *)s.h.get(), *hent = hbm + nbm;
                 uint64_t w = 0, before = 0;   // set bits of the words before w
                 s.zero_carried = 0;
                 for (; next_carry < d.carry_records && rec[next_carry * RW] < hi; ++next_carry) {
@@ -3574,25 +3460,26 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
                 }
                 if (rc != TSX_HIP_OK) break;
             }
-            const uint64_t *bm = (const uint64_t *)s.d, *ent = bm + nbm;
-            uint64_t *kx_k = s.d_kx, *kx_c = s.d_kx ? s.d_kx + n * WK : nullptr;
+            const uint64_t *bm = (const uint64_t *)s.d.get(), *ent = bm + nbm;
+            uint64_t *kx_k = s.d_kx.get(), *kx_c = kx_k ? kx_k + n * WK : nullptr;
+            unsigned long long *const s_tile = s.d_tile.get(), *const s_res = s.d_res.get();
             const unsigned nb = (unsigned)((nt + NT / 64 - 1) / (NT / 64));
-            if (hipMemcpyAsync(s.d, s.h, bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
-                hipMemsetAsync(s.d_res, 0, DB_RES_N * 8, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            hipLaunchKernelGGL(db_count_bitmap_kernel, dim3(nb), dim3(NT), 0, st, bm, nbm, nt, s.d_tile);
-            hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(NT), 0, st, s.d_tile, nt);
+            if (hipMemcpyAsync(s.d.get(), s.h.get(), bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
+                hipMemsetAsync(s_res, 0, DB_RES_N * 8, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            hipLaunchKernelGGL(db_count_bitmap_kernel, dim3(nb), dim3(NT), 0, st, bm, nbm, nt, s_tile);
+            hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(NT), 0, st, s_tile, nt);
             if (direct) {
                 hipLaunchKernelGGL((db_load_kernel<true, 1>), dim3((unsigned)nt), dim3(NT), 0, st, m->p, sp, lo, hi, bm, ent, n,
-                                   (const unsigned long long *)s.d_tile, (uint64_t *)nullptr, (uint64_t *)nullptr, s.d_res);
+                                   (const unsigned long long *)s_tile, (uint64_t *)nullptr, (uint64_t *)nullptr, s_res);
             } else {
                 DISPATCH_WK(m, hipLaunchKernelGGL((db_load_kernel<false, WKV>), dim3((unsigned)nt), dim3(NT), 0, st, m->p, sp, lo, hi,
-                                                  bm, ent, n, (const unsigned long long *)s.d_tile, kx_k, kx_c, s.d_res));
+                                                  bm, ent, n, (const unsigned long long *)s_tile, kx_k, kx_c, s_res));
             }
             if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(s.d_res + DB_RES_TOTAL, s.d_tile + nt, 8, hipMemcpyDeviceToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+                hipMemcpyAsync(s_res + DB_RES_TOTAL, s_tile + nt, 8, hipMemcpyDeviceToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
             if (!direct && n && (rc = tsx_hip_add_kmers_device(m, kx_k, kx_c, (size_t)n, nullptr)) != TSX_HIP_OK) break;
-            if (hipMemcpyAsync(s.h_res, s.d_res, DB_RES_N * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipEventRecord(s.done, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            if (hipMemcpyAsync(s.h_res.get(), s_res, DB_RES_N * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipEventRecord(s.done.get(), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
             s.busy = true;
         }
         (void)hipStreamSynchronize(st);
@@ -3606,10 +3493,7 @@ extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uin
             hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         rc = tsx_hip_sync(m);
     } while (0);
-    (void)hipStreamSynchronize(st);
-    for (int b = 0; b < 2; ++b) sg[b].release();
-    if (d_carry) (void)hipFree(d_carry);
-    if (d_ilut) (void)hipFree(d_ilut);
+    (void)hipStreamSynchronize(st);   // nothing queued may outlive the stages
     if (entries_out) *entries_out = entries;
     return rc;
 }
@@ -3628,20 +3512,11 @@ static bool combine_aligned(const tsx_hip_map *x, const tsx_hip_map *y) {
 // Staging of the paths that go through k-mers: two chunks, so that add_kmers_kernel inserts one (on OUT's stream)
 // while the sweep fills the other (on A's).
 struct CombineStage {
-    uint64_t *d_kmers[2] = {nullptr, nullptr}, *d_counts[2] = {nullptr, nullptr};
-    unsigned long long *d_n = nullptr, *h_n = nullptr;   // entries staged per chunk
-    hipEvent_t swept[2] = {nullptr, nullptr}, inserted[2] = {nullptr, nullptr};
+    DevBuf<uint64_t> d_kmers[2], d_counts[2];
+    DevBuf<unsigned long long> d_n;   // entries staged per chunk
+    PinBuf<unsigned long long> h_n;
+    Event swept[2], inserted[2];
     bool waiting[2] = {false, false}, reuse[2] = {false, false};
-    void release() {
-        for (int b = 0; b < 2; ++b) {
-            if (d_kmers[b]) (void)hipFree(d_kmers[b]);
-            if (d_counts[b]) (void)hipFree(d_counts[b]);
-            if (swept[b]) (void)hipEventDestroy(swept[b]);
-            if (inserted[b]) (void)hipEventDestroy(inserted[b]);
-        }
-        if (d_n) (void)hipFree(d_n);
-        if (h_n) (void)hipHostFree(h_n);
-    }
 };
 
 extern "C" int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b, const tsx_hip_combine_rule *rule,
@@ -3681,43 +3556,44 @@ extern "C" int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b,
     for (tsx_hip_map *m : maps) {
         if (!m) continue;
         join_foreign(m, true);
-        int rcz = ensure_zeroed(m, m->stream);
+        int rcz = ensure_zeroed(m, m->stream.get());
         if (rcz != TSX_HIP_OK) return rcz;
-        HIP_TRY(hipStreamSynchronize(m->stream));
+        HIP_TRY(hipStreamSynchronize(m->stream.get()));
     }
     unsigned long long a_carry = 0, b_carry = 0;
     HIP_TRY(hipMemcpy(&a_carry, a->p.stats + ST_CARRY, 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&b_carry, b->p.stats + ST_CARRY, 8, hipMemcpyDeviceToHost));
 
-    hipStream_t sw = a->stream;                  // the sweeps
-    hipStream_t ins = out ? out->stream : sw;    // the inserts of staged chunks
+    hipStream_t sw = a->stream.get();                  // the sweeps
+    hipStream_t ins = out ? out->stream.get() : sw;    // the inserts of staged chunks
     CombineStage sg;
+    DevBuf<unsigned long long> res;
     unsigned long long *d_res = nullptr;
     unsigned long long h_res[CB_N] = {0};
     int rc = TSX_HIP_OK;
     const bool staging = out && !fused;
     do {
-        if (hipMalloc((void **)&d_res, CB_N * 8) != hipSuccess) { rc = TSX_HIP_ENOMEM; break; }
+        if (res.alloc(CB_N * 8) != TSX_HIP_OK) { rc = TSX_HIP_ENOMEM; break; }
+        d_res = res.get();
         if (hipMemsetAsync(d_res, 0, CB_N * 8, sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         if (staging) {
-            if (hipMalloc((void **)&sg.d_n, 2 * 8) != hipSuccess || hipHostMalloc((void **)&sg.h_n, 2 * 8) != hipSuccess) { rc = TSX_HIP_ENOMEM; break; }
+            if (sg.d_n.alloc(2 * 8) != TSX_HIP_OK || sg.h_n.alloc(2 * 8) != TSX_HIP_OK) { rc = TSX_HIP_ENOMEM; break; }
             for (int i = 0; i < 2 && rc == TSX_HIP_OK; ++i) {
-                if (hipMalloc((void **)&sg.d_kmers[i], (size_t)chunk_slots * WK * 8) != hipSuccess ||
-                    hipMalloc((void **)&sg.d_counts[i], (size_t)chunk_slots * 8) != hipSuccess) { g_last_error = "combine: staging"; rc = TSX_HIP_ENOMEM; }
-                else if (hipEventCreateWithFlags(&sg.swept[i], hipEventDisableTiming) != hipSuccess ||
-                         hipEventCreateWithFlags(&sg.inserted[i], hipEventDisableTiming) != hipSuccess) rc = TSX_HIP_EHIP;
+                if (sg.d_kmers[i].alloc((size_t)chunk_slots * WK * 8) != TSX_HIP_OK ||
+                    sg.d_counts[i].alloc((size_t)chunk_slots * 8) != TSX_HIP_OK) { g_last_error = "combine: staging"; rc = TSX_HIP_ENOMEM; }
+                else if (sg.swept[i].create() != TSX_HIP_OK || sg.inserted[i].create() != TSX_HIP_OK) rc = TSX_HIP_EHIP;
             }
             if (rc != TSX_HIP_OK) break;
         }
         // the chunk in buffer i has been swept: insert it into OUT
         auto insert_chunk = [&](int i) -> int {
             sg.waiting[i] = false;
-            if (hipEventSynchronize(sg.swept[i]) != hipSuccess) return TSX_HIP_EHIP;
-            const unsigned long long n = sg.h_n[i];
+            if (hipEventSynchronize(sg.swept[i].get()) != hipSuccess) return TSX_HIP_EHIP;
+            const unsigned long long n = sg.h_n.get()[i];
             if (n == 0) return TSX_HIP_OK;
-            const int r = tsx_hip_add_kmers_device(out, sg.d_kmers[i], sg.d_counts[i], (size_t)n, nullptr);
+            const int r = tsx_hip_add_kmers_device(out, sg.d_kmers[i].get(), sg.d_counts[i].get(), (size_t)n, nullptr);
             if (r != TSX_HIP_OK) return r;
-            if (hipEventRecord(sg.inserted[i], ins) != hipSuccess) return TSX_HIP_EHIP;
+            if (hipEventRecord(sg.inserted[i].get(), ins) != hipSuccess) return TSX_HIP_EHIP;
             sg.reuse[i] = true;
             return TSX_HIP_OK;
         };
@@ -3743,8 +3619,8 @@ extern "C" int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b,
                 unsigned long long *dn = nullptr;
                 if (ca.emit == 1) {
                     if (sg.waiting[i] && (rc = insert_chunk(i)) != TSX_HIP_OK) break;
-                    if (sg.reuse[i] && hipStreamWaitEvent(sw, sg.inserted[i], 0) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-                    dk = sg.d_kmers[i]; dc = sg.d_counts[i]; dn = sg.d_n + i;
+                    if (sg.reuse[i] && hipStreamWaitEvent(sw, sg.inserted[i].get(), 0) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+                    dk = sg.d_kmers[i].get(); dc = sg.d_counts[i].get(); dn = sg.d_n.get() + i;
                     if (hipMemsetAsync(dn, 0, 8, sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
                 }
                 const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((hi - lo + CB_TILE - 1) / CB_TILE, (uint64_t)a->cus * 8));
@@ -3759,8 +3635,8 @@ extern "C" int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b,
                 }
                 if (hipGetLastError() != hipSuccess) { g_last_error = "combine_sweep_kernel launch"; rc = TSX_HIP_EHIP; break; }
                 if (ca.emit == 1) {
-                    if (hipMemcpyAsync(sg.h_n + i, dn, 8, hipMemcpyDeviceToHost, sw) != hipSuccess ||
-                        hipEventRecord(sg.swept[i], sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+                    if (hipMemcpyAsync(sg.h_n.get() + i, dn, 8, hipMemcpyDeviceToHost, sw) != hipSuccess ||
+                        hipEventRecord(sg.swept[i].get(), sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
                     sg.waiting[i] = true;
                     ++chunk;
                     const int prev = (int)(chunk & 1);   // the chunk before this one: insert it while this one is swept
@@ -3775,10 +3651,8 @@ extern "C" int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b,
             hipStreamSynchronize(sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         if (out) rc = tsx_hip_sync(out);
     } while (0);
-    (void)hipStreamSynchronize(sw);
+    (void)hipStreamSynchronize(sw);   // nothing queued may outlive the staging
     if (out) (void)hipStreamSynchronize(ins);
-    sg.release();
-    if (d_res) (void)hipFree(d_res);
     if (stats_out) {
         stats_out->a_in_range = h_res[CB_A_IN]; stats_out->b_in_range = h_res[CB_B_IN]; stats_out->both = h_res[CB_BOTH];
         stats_out->a_sum_both = h_res[CB_A_SUM]; stats_out->b_sum_both = h_res[CB_B_SUM];
@@ -3865,8 +3739,9 @@ extern "C" int tsx_hip_synth_fastq_device(uint64_t seed, uint64_t first_read, ui
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return TSX_HIP_ENODEVICE;
     HIP_TRY(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
-    uint64_t *d_off = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_off, (n_reads + 1) * 8));
+    DevBuf<uint64_t> off;
+    TSX_TRY(off.alloc((n_reads + 1) * 8));
+    uint64_t *const d_off = off.get();
     int rc = TSX_HIP_OK;
     if (hipMemcpyAsync(d_off, offs.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess) rc = TSX_HIP_EHIP;
     if (rc == TSX_HIP_OK) {
@@ -3875,8 +3750,7 @@ extern "C" int tsx_hip_synth_fastq_device(uint64_t seed, uint64_t first_read, ui
                            (const uint64_t *)d_off, (uint8_t *)dev_out);
         if (hipGetLastError() != hipSuccess) rc = TSX_HIP_EHIP;
     }
-    if (hipStreamSynchronize(st) != hipSuccess) rc = TSX_HIP_EHIP;
-    (void)hipFree(d_off);
+    if (hipStreamSynchronize(st) != hipSuccess) rc = TSX_HIP_EHIP;   // (d_off is read until here)
     return rc;
 }
 
@@ -3901,9 +3775,10 @@ extern "C" int tsx_hip_synth_zipf_device(uint64_t seed, uint64_t n_reads, uint32
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return TSX_HIP_ENODEVICE;
     HIP_TRY(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
-    uint64_t *d_off = nullptr, *d_thr = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_off, (n_reads + 1) * 8));
-    if (hipMalloc((void **)&d_thr, (size_t)n_templates * 8) != hipSuccess) { (void)hipFree(d_off); return TSX_HIP_ENOMEM; }
+    DevBuf<uint64_t> off, thr_buf;
+    TSX_TRY(off.alloc((n_reads + 1) * 8));
+    if (thr_buf.alloc((size_t)n_templates * 8) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+    uint64_t *const d_off = off.get(), *const d_thr = thr_buf.get();
     int rc = TSX_HIP_OK;
     if (hipMemcpyAsync(d_off, offs.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(d_thr, thr, (size_t)n_templates * 8, hipMemcpyHostToDevice, st) != hipSuccess) rc = TSX_HIP_EHIP;
@@ -3913,8 +3788,7 @@ extern "C" int tsx_hip_synth_zipf_device(uint64_t seed, uint64_t n_reads, uint32
                            (const uint64_t *)d_thr, (const uint64_t *)d_off, (uint8_t *)dev_out);
         if (hipGetLastError() != hipSuccess) rc = TSX_HIP_EHIP;
     }
-    if (hipStreamSynchronize(st) != hipSuccess) rc = TSX_HIP_EHIP;
-    (void)hipFree(d_off); (void)hipFree(d_thr);
+    if (hipStreamSynchronize(st) != hipSuccess) rc = TSX_HIP_EHIP;   // (both are read until here)
     return rc;
 }
 
@@ -3930,19 +3804,15 @@ static bool query_args_ok(const tsx_hip_map *m, uint64_t lower, uint64_t upper) 
 // The line passes of run_fastq_piece (tile line ends, then their exclusive scan from *d_carry) over [0, own_end).
 static int query_line_pass(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open, hipStream_t st) {
     const uint64_t ntiles = (own_end + TILE - 1) / TILE;
-    if (ntiles > m->tile_cap) {
-        if (m->d_tile) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(m->d_tile)); m->d_tile = nullptr; }
-        m->tile_cap = ntiles + ntiles / 4 + 1024;
-        HIP_TRY(hipMalloc((void **)&m->d_tile, (m->tile_cap + m->tile_cap / SCAN_CHUNK + 16) * sizeof(uint32_t)));
-    }
+    TSX_TRY(ensure_tiles(m, ntiles, st));
     const int g1 = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8);
-    hipLaunchKernelGGL(line_count_kernel, dim3(g1), dim3(NT), 0, st, d_text, n, own_end, head_open, m->d_tile, ntiles);
+    hipLaunchKernelGGL(line_count_kernel, dim3(g1), dim3(NT), 0, st, d_text, n, own_end, head_open, m->d_tile.get(), ntiles);
     const uint64_t nchunks = (ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    uint32_t *chunk = m->d_tile + m->tile_cap;
-    hipLaunchKernelGGL(line_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const uint32_t *)m->d_tile,
+    uint32_t *chunk = m->d_tile.get() + m->tile_cap;
+    hipLaunchKernelGGL(line_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const uint32_t *)m->d_tile.get(),
                        ntiles, chunk);
-    hipLaunchKernelGGL(line_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, m->d_carry);
-    hipLaunchKernelGGL(line_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, m->d_tile, ntiles,
+    hipLaunchKernelGGL(line_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, m->d_carry.get());
+    hipLaunchKernelGGL(line_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, m->d_tile.get(), ntiles,
                        (const uint32_t *)chunk);
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
@@ -3959,7 +3829,7 @@ static int query_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint6
     const uint32_t lshift = m->p.line_mask == 3 ? 2u : 1u;
     DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((query_reads_kernel<WKV, CANV, BRV>), dim3(grid), dim3(NT),
                                                         lut_bytes, st, m->p, d_text, n, own_end, head_open,
-                                                        (const uint32_t *)m->d_tile, ntiles, d_line_base, lshift, lower, upper,
+                                                        (const uint32_t *)m->d_tile.get(), ntiles, d_line_base, lshift, lower, upper,
                                                         d_stats, (uint64_t)cap, m->qmap_cur))));
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
@@ -3979,10 +3849,10 @@ extern "C" int tsx_hip_query_reads_device(tsx_hip_map *m, const void *dev_text, 
     if (rc != TSX_HIP_OK) return rc;
     if ((rc = base_rule_ok(m)) != TSX_HIP_OK) return rc;
     if (m->minq && (rc = build_qmap(m, (const uint8_t *)dev_text, n, st)) != TSX_HIP_OK) return rc;
-    const uint16_t *qmap = m->minq ? m->d_qmap : nullptr;
+    const uint16_t *qmap = m->minq ? m->d_qmap.get() : nullptr;
     QmapScope qs(m);
     unsigned long long *stats = (unsigned long long *)dev_stats;
-    unsigned long long *d_base = (unsigned long long *)m->d_carry + 2, *d_nrec = d_base + 1;
+    unsigned long long *d_base = (unsigned long long *)m->d_carry.get() + 2, *d_nrec = d_base + 1;
     if (stats_cap) HIP_TRY(hipMemsetAsync(stats, 0, stats_cap * sizeof(tsx_hip_read_stats), st));
     HIP_TRY(hipMemsetAsync(d_base, 0, 2 * sizeof(unsigned long long), st));
     const uint8_t *base = (const uint8_t *)dev_text;
@@ -3992,16 +3862,16 @@ extern "C" int tsx_hip_query_reads_device(tsx_hip_map *m, const void *dev_text, 
         const size_t own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
         const int head_open = off > 0 ? -1 : 0;
         m->qmap_cur = qmap ? qmap + off / 16 : nullptr;   // (windows start at multiples of 16)
-        HIP_TRY(hipMemsetAsync(m->d_carry, 0, sizeof(uint32_t), st));
+        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
         if ((rc = query_line_pass(m, base + off, len, own, head_open, st)) != TSX_HIP_OK) return rc;
         if ((rc = query_launch(m, base + off, len, own, head_open, d_base, lower, upper, stats, stats_cap, st)) != TSX_HIP_OK)
             return rc;
         const bool last = off + own >= n;
-        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry, last ? 1 : 0,
+        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), last ? 1 : 0,
                            base + n - 1, lpr, d_nrec);
     }
     if (n == 0)
-        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry, 1,
+        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), 1,
                            (const uint8_t *)nullptr, lpr, d_nrec);
     if (stats_cap)
         hipLaunchKernelGGL(query_finalize_kernel, dim3(grid_for(m, stats_cap, 8)), dim3(NT), 0, st, stats, (uint64_t)stats_cap,
@@ -4016,27 +3886,22 @@ extern "C" int tsx_hip_query_reads_device(tsx_hip_map *m, const void *dev_text, 
 
 // Scratch of one host query / filter call.
 struct QueryBufs {
-    uint8_t *text = nullptr; size_t text_have = 0;
-    unsigned long long *stats = nullptr; size_t stats_have = 0;
-    unsigned long long *span = nullptr; size_t span_have = 0;
-    unsigned long long *koff = nullptr; size_t koff_have = 0;
-    uint8_t *out = nullptr; size_t out_have = 0;
-    unsigned long long *info = nullptr, *h_info = nullptr;   // cut, records, open, total, line base (0), kept
-    uint8_t *h_out = nullptr; size_t h_out_have = 0;
-    hipEvent_t ev = nullptr;
-    int init(hipStream_t st) {
-        HIP_TRY(hipMalloc((void **)&info, 8 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(info, 0, 8 * sizeof(unsigned long long), st));
-        HIP_TRY(hipHostMalloc((void **)&h_info, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        return TSX_HIP_OK;
-    }
-    void release(hipStream_t st) {   // nothing queued may outlive the buffers
-        (void)hipStreamSynchronize(st);
-        for (void *p : {(void *)text, (void *)stats, (void *)span, (void *)koff, (void *)out, (void *)info}) if (p) (void)hipFree(p);
-        if (h_info) (void)hipHostFree(h_info);
-        if (h_out) (void)hipHostFree(h_out);
-        if (ev) (void)hipEventDestroy(ev);
+    DevBuf<uint8_t> text;
+    DevBuf<unsigned long long> stats, span, koff;
+    DevBuf<uint8_t> own_out;                       // the filter's output, unless the caller gave a buffer:
+    uint8_t *out = nullptr; size_t out_have = 0;   // where it goes, and the room there
+    DevBuf<unsigned long long> info;               // cut, records, open, total, line base (0), kept
+    PinBuf<unsigned long long> h_info;
+    PinBuf<uint8_t> h_out;
+    Event ev;
+    hipStream_t st;
+    explicit QueryBufs(hipStream_t s) : st(s) {}
+    ~QueryBufs() { (void)hipStreamSynchronize(st); }   // nothing queued may outlive the buffers
+    int init() {
+        TSX_TRY(info.alloc(8 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(info.get(), 0, 8 * sizeof(unsigned long long), st));
+        TSX_TRY(h_info.alloc(8 * sizeof(unsigned long long)));
+        return ev.create();
     }
 };
 
@@ -4050,52 +3915,58 @@ static int query_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint
     const uint32_t lpr = m->p.line_mask + 1;
     const uint64_t ntiles = (len + TILE - 1) / TILE, span_cap = len / (2 * lpr) + 2;
     int rc;
-    HIP_TRY(hipMemsetAsync(m->d_carry, 0, sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
     if ((rc = query_line_pass(m, d_text, len, len, 0, st)) != TSX_HIP_OK) return rc;
-    if (spans && (rc = grow(st, b.span, b.span_have, span_cap * 16)) != TSX_HIP_OK) return rc;
+    if (spans && (rc = grow(st, b.span, span_cap * 16)) != TSX_HIP_OK) return rc;
     hipLaunchKernelGGL(record_scan_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
-                       d_text, len, (const uint32_t *)m->d_tile, ntiles, (const uint32_t *)m->d_carry, lpr, last ? 1 : 0,
-                       b.info, spans ? b.span : nullptr, span_cap);
+                       d_text, len, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), lpr, last ? 1 : 0,
+                       b.info.get(), spans ? b.span.get() : nullptr, span_cap);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b.h_info, b.info, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    const unsigned long long *h_info = b.h_info.get();
+    HIP_TRY(hipMemcpyAsync(b.h_info.get(), b.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    cut = b.h_info[0]; nrec = b.h_info[1]; open = b.h_info[2] != 0;
+    cut = h_info[0]; nrec = h_info[1]; open = h_info[2] != 0;
     if (nrec == 0) return TSX_HIP_OK;
-    if ((rc = grow(st, b.stats, b.stats_have, nrec * sizeof(tsx_hip_read_stats))) != TSX_HIP_OK) return rc;
-    HIP_TRY(hipMemsetAsync(b.stats, 0, nrec * sizeof(tsx_hip_read_stats), st));
+    if ((rc = grow(st, b.stats, nrec * sizeof(tsx_hip_read_stats))) != TSX_HIP_OK) return rc;
+    HIP_TRY(hipMemsetAsync(b.stats.get(), 0, nrec * sizeof(tsx_hip_read_stats), st));
     QmapScope qs(m);
     if (m->minq) {   // a quality rule: the bitmap of the whole records (its line pass over [0, cut) rewrites d_tile with the same values)
         if ((rc = build_qmap(m, d_text, cut, st)) != TSX_HIP_OK) return rc;
-        m->qmap_cur = m->d_qmap;
+        m->qmap_cur = m->d_qmap.get();
     }
-    if ((rc = query_launch(m, d_text, cut, cut, 0, b.info + 4, lower, upper, b.stats, nrec, st)) != TSX_HIP_OK) return rc;
-    hipLaunchKernelGGL(query_finalize_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.stats, nrec,
+    if ((rc = query_launch(m, d_text, cut, cut, 0, b.info.get() + 4, lower, upper, b.stats.get(), nrec, st)) != TSX_HIP_OK) return rc;
+    hipLaunchKernelGGL(query_finalize_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.stats.get(), nrec,
                        (const unsigned long long *)nullptr, nrec);
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
 
 // The filter behind query_piece: kept lengths, their scan (total -> b.info[3], kept records -> b.info[5]), the
-// compaction into b.out (grown to the piece's worst case: cut + 1 bytes, rounded up).  Queued, not waited for.
+// compaction into b.out (own_out grown to the piece's worst case: cut + 1 bytes, rounded up -- or the caller's
+// buffer, never grown).  Queued, not waited for.
 static int filter_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint64_t cut, uint64_t nrec, bool open,
                         const tsx_hip_filter_rule &rule, hipStream_t st) {
     const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    int rc = grow(st, b.koff, b.koff_have, (nk + nchunks + 16) * sizeof(unsigned long long));
-    if (rc == TSX_HIP_OK) rc = grow(st, b.out, b.out_have, cut + 64);
-    if (rc != TSX_HIP_OK) return rc;
-    HIP_TRY(hipMemsetAsync(b.koff + nrec, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(filter_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, (const unsigned long long *)b.stats,
-                       (const unsigned long long *)b.span, nrec, rule.min_in_range, (uint64_t)rule.fraction_ppm, rule.invert,
-                       open ? 1 : 0, b.koff, b.info + 5);
-    unsigned long long *chunk = b.koff + nk;
-    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)b.koff,
+    TSX_TRY(grow(st, b.koff, (nk + nchunks + 16) * sizeof(unsigned long long)));
+    if (cut + 64 > b.out_have) {   // (as grow() finds it: a caller's buffer has the room, tsx_hip_filter_reads_device checks)
+        TSX_TRY(grow(st, b.own_out, cut + 64));
+        b.out = b.own_out.get(); b.out_have = b.own_out.cap();
+    }
+    unsigned long long *const koff = b.koff.get(), *const info = b.info.get();
+    const unsigned long long *span = b.span.get();
+    HIP_TRY(hipMemsetAsync(koff + nrec, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(filter_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, (const unsigned long long *)b.stats.get(),
+                       span, nrec, rule.min_in_range, (uint64_t)rule.fraction_ppm, rule.invert,
+                       open ? 1 : 0, koff, info + 5);
+    unsigned long long *chunk = koff + nk;
+    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)koff,
                        nk, chunk);
-    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, b.info + 3);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, b.koff, nk,
+    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, info + 3);
+    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, koff, nk,
                        (const unsigned long long *)chunk);
     // (the copy grid covers the worst case; lanes past the total fall through)
     hipLaunchKernelGGL(filter_copy_kernel, dim3(grid_for(m, (cut + 16) / 16 + 64, 8)), dim3(NT), 0, st, d_text, cut,
-                       (const unsigned long long *)b.span, (const unsigned long long *)b.koff, nrec, b.out, (uint64_t)b.out_have);
+                       span, (const unsigned long long *)koff, nrec, b.out, (uint64_t)b.out_have);
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
@@ -4115,12 +3986,13 @@ static int query_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower
     chunk_bytes = std::min(chunk_bytes, QUERY_PIECE_MAX);
     HIP_TRY(hipSetDevice(m->device));
     join_foreign(m, false);
-    hipStream_t st = m->stream;
+    hipStream_t st = m->stream.get();
     int rc = base_rule_ok(m);
     if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
     if (rc != TSX_HIP_OK) return rc;
-    QueryBufs b;
-    rc = b.init(st);
+    QueryBufs b(st);
+    rc = b.init();
+    const unsigned long long *h_info = b.h_info.get();
     uint64_t rec_base = 0, kept = 0, bytes = 0, pending = 0;
     bool have_pending = false;
     for (size_t off = 0; off < n && rc == TSX_HIP_OK;) {
@@ -4129,9 +4001,9 @@ static int query_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower
         bool open = false;
         for (;;) {
             const bool last = off + len == n;
-            if ((rc = grow(st, b.text, b.text_have, len + 256)) != TSX_HIP_OK) break;
-            if (hipMemcpyAsync(b.text, text + off, len, hipMemcpyHostToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            if ((rc = query_piece(m, b, b.text, len, last, lower, upper, rule != nullptr, st, cut, nrec, open)) != TSX_HIP_OK) break;
+            if ((rc = grow(st, b.text, len + 256)) != TSX_HIP_OK) break;
+            if (hipMemcpyAsync(b.text.get(), text + off, len, hipMemcpyHostToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            if ((rc = query_piece(m, b, b.text.get(), len, last, lower, upper, rule != nullptr, st, cut, nrec, open)) != TSX_HIP_OK) break;
             if (nrec || last) break;
             if (len >= QUERY_PIECE_MAX) { g_last_error = "a record longer than 3.75 GiB"; rc = TSX_HIP_EINVAL; break; }
             len = std::min(std::min(2 * len, n - off), QUERY_PIECE_MAX);
@@ -4139,47 +4011,42 @@ static int query_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower
         if (rc != TSX_HIP_OK) break;
         if (!rule) {
             if (rec_base < stats_cap && nrec &&
-                (hipMemcpyAsync(stats_out + rec_base, b.stats, std::min<uint64_t>(nrec, stats_cap - rec_base) * sizeof(tsx_hip_read_stats),
+                (hipMemcpyAsync(stats_out + rec_base, b.stats.get(), std::min<uint64_t>(nrec, stats_cap - rec_base) * sizeof(tsx_hip_read_stats),
                                 hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
                 rc = TSX_HIP_EHIP;
         } else if (nrec) {
-            rc = filter_piece(m, b, b.text, cut, nrec, open, *rule, st);
-            if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.h_info + 3, b.info + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                                     hipEventRecord(b.ev, st) != hipSuccess))
+            rc = filter_piece(m, b, b.text.get(), cut, nrec, open, *rule, st);
+            if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.h_info.get() + 3, b.info.get() + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                                     hipEventRecord(b.ev.get(), st) != hipSuccess))
                 rc = TSX_HIP_EHIP;
             if (rc == TSX_HIP_OK && have_pending) {   // the previous piece's output, while the device works on this one
-                rc = write_all(fd, b.h_out, pending);
+                rc = write_all(fd, b.h_out.get(), pending);
                 if (rc == TSX_HIP_OK) bytes += pending;
                 have_pending = false;
             }
-            if (rc == TSX_HIP_OK && hipEventSynchronize(b.ev) != hipSuccess) rc = TSX_HIP_EHIP;
-            if (rc == TSX_HIP_OK && b.h_info[3] > cut + 1) { g_last_error = "filter output larger than its piece"; rc = TSX_HIP_EHIP; }
+            if (rc == TSX_HIP_OK && hipEventSynchronize(b.ev.get()) != hipSuccess) rc = TSX_HIP_EHIP;
+            if (rc == TSX_HIP_OK && h_info[3] > cut + 1) { g_last_error = "filter output larger than its piece"; rc = TSX_HIP_EHIP; }
             if (rc == TSX_HIP_OK) {
-                const uint64_t total = b.h_info[3];
-                kept += b.h_info[5];
-                if (total > b.h_out_have) {
-                    if (b.h_out) (void)hipHostFree(b.h_out);
-                    b.h_out = nullptr; b.h_out_have = 0;
-                    if (hipHostMalloc((void **)&b.h_out, total + total / 8 + 4096, hipHostMallocDefault) != hipSuccess) rc = TSX_HIP_ENOMEM;
-                    else b.h_out_have = total + total / 8 + 4096;
-                }
-                if (rc == TSX_HIP_OK && total && (hipMemcpyAsync(b.h_out, b.out, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                const uint64_t total = h_info[3];
+                kept += h_info[5];
+                // (no wait: the copy that last filled it has been waited for, and written out above)
+                if (b.h_out.reserve(nullptr, total, total + total / 8 + 4096) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
+                if (rc == TSX_HIP_OK && total && (hipMemcpyAsync(b.h_out.get(), b.out, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
                                                   hipStreamSynchronize(st) != hipSuccess))
                     rc = TSX_HIP_EHIP;
                 pending = total;
                 have_pending = rc == TSX_HIP_OK;
                 // (the kept counter is per piece)
-                if (rc == TSX_HIP_OK && hipMemsetAsync(b.info + 5, 0, sizeof(unsigned long long), st) != hipSuccess) rc = TSX_HIP_EHIP;
+                if (rc == TSX_HIP_OK && hipMemsetAsync(b.info.get() + 5, 0, sizeof(unsigned long long), st) != hipSuccess) rc = TSX_HIP_EHIP;
             }
         }
         rec_base += nrec;
         off += cut;
     }
     if (rc == TSX_HIP_OK && have_pending) {
-        rc = write_all(fd, b.h_out, pending);
+        rc = write_all(fd, b.h_out.get(), pending);
         if (rc == TSX_HIP_OK) bytes += pending;
     }
-    b.release(st);
     if (n_records) *n_records = (size_t)rec_base;
     if (kept_out) *kept_out = kept;
     if (bytes_out) *bytes_out = bytes;
@@ -4215,22 +4082,20 @@ extern "C" int tsx_hip_filter_reads_device(tsx_hip_map *m, const void *dev_text,
     int rc = base_rule_ok(m);
     if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
     if (rc != TSX_HIP_OK) return rc;
-    QueryBufs b;
-    rc = b.init(st);
+    QueryBufs b(st);
+    rc = b.init();
     b.out = (uint8_t *)dev_out; b.out_have = out_cap;   // the compaction writes the caller's buffer (never grown)
     uint64_t cut = 0, nrec = 0, total = 0, kept = 0;
     bool open = false;
     if (rc == TSX_HIP_OK) rc = query_piece(m, b, (const uint8_t *)dev_text, n, true, rule->lower, rule->upper, true, st, cut, nrec, open);
     if (rc == TSX_HIP_OK && nrec) {
         rc = filter_piece(m, b, (const uint8_t *)dev_text, cut, nrec, open, *rule, st);
-        if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.h_info + 3, b.info + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.h_info.get() + 3, b.info.get() + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
                                  hipStreamSynchronize(st) != hipSuccess))
             rc = TSX_HIP_EHIP;
-        if (rc == TSX_HIP_OK) { total = b.h_info[3]; kept = b.h_info[5]; }
+        if (rc == TSX_HIP_OK) { total = b.h_info.get()[3]; kept = b.h_info.get()[5]; }
         if (rc == TSX_HIP_OK && total > cut + 1) { g_last_error = "filter output larger than its text"; rc = TSX_HIP_EHIP; }
     }
-    b.out = nullptr;
-    b.release(st);
     if (out_bytes) *out_bytes = (size_t)total;
     if (kept_out) *kept_out = kept;
     return rc;
