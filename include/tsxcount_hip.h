@@ -418,6 +418,55 @@ int tsx_hip_filter_reads_host(tsx_hip_map *m, const char *text, size_t n, const 
                               size_t chunk_bytes, uint64_t *kept_out, uint64_t *bytes_out);
 int tsx_hip_filter_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_filter_rule *rule,
                                 void *dev_out, size_t out_cap, size_t *out_bytes, uint64_t *kept_out, void *stream);
+/*
+ * Read trimming (csrc/tsx_trim.h; no reference counterpart -- khmer `filter-abund` / `trim-low-abund`, Quake, Lighter):
+ * keep of every record the stretch of its sequence whose k-mers are trusted.  Records, lines, k-mers and c(x) are those
+ * of tsx_hip_query_reads_*, and the table's base rule (tsx_hip_set_base_rule) decides which windows are k-mers at all.
+ * Window i of a sequence line of length L (0 <= i <= L - k) is SOLID when it is a k-mer under the base rule and
+ * lower <= c(x) <= upper.  A RUN is a maximal stretch of consecutive solid windows [i, j]; it covers bases [i, j + k).
+ * `mode` picks the run that decides the record's kept span:
+ *   TSX_HIP_TRIM_LONGEST  the longest run, the leftmost among equals
+ *   TSX_HIP_TRIM_PREFIX   the run that contains window 0 (none when window 0 is not solid): cut at the first untrusted k-mer
+ * The span is (start, length) in bases of the sequence line, (0, 0) without a run; a non-empty span is >= k long (and,
+ * like a sequence line, shorter than 4 GiB).
+ * A record is WRITTEN when length >= min_len (0 = k; a record of length 0 is never written).  A written record is, in
+ * order: its first line, whole; bytes [start, start + length) of the sequence line; for 4-line records the third line,
+ * whole, and bytes [min(start, Lq), min(start + length, Lq)) of the quality line of length Lq -- each followed by '\n'
+ * (also where the text's last line lacks one).  A trailing incomplete record writes the lines it has, by the same
+ * rules.  Output is in input order; empty lines of the input are not written.
+ * TSX_HIP_EINVAL for a map created with shard_bits > 0, lower > upper, an unknown mode and reserved != 0.
+ *   trim_spans_device  dev_text as tsx_hip_query_reads_device takes it; the spans of records [0, spans_cap) to dev_spans
+ *                      (tsx_hip_trim_span each, zeroed by the call; min_len plays no part).  WAITS for the stream; more
+ *                      records than spans_cap: TSX_HIP_ERANGE (the first spans_cap are written).
+ *   trim_spans_host    the same for text in host memory, in pieces as tsx_hip_query_reads_host (chunk_bytes 0 = 256 MiB).
+ *   trim_reads_device  the written records of the whole of dev_text (n < 3.75 GiB) into dev_out (16-byte aligned,
+ *                      out_cap >= n + 64, else TSX_HIP_ERANGE); totals->bytes = the output's size.  Waits for the stream.
+ *   trim_reads_host    text in host memory in pieces; the device trims piece i + 1 while the host writes piece i to fd.
+ *                      A failed write: TSX_HIP_EIO.
+ * totals (optional): records seen, records written, bases of all sequence lines, bases written, bytes written.
+ */
+#define TSX_HIP_TRIM_LONGEST 0
+#define TSX_HIP_TRIM_PREFIX 1
+typedef struct tsx_hip_trim_rule {
+    uint64_t lower, upper;      /* the count range of a solid window */
+    uint64_t min_len;           /* bases a record must keep to be written (0 = k) */
+    int32_t mode;               /* TSX_HIP_TRIM_* */
+    int32_t reserved;           /* 0 */
+} tsx_hip_trim_rule;
+typedef struct tsx_hip_trim_span {
+    uint64_t start, length;
+} tsx_hip_trim_span;
+typedef struct tsx_hip_trim_totals {
+    uint64_t records, kept, bases_in, bases_kept, bytes;
+} tsx_hip_trim_totals;
+int tsx_hip_trim_spans_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_trim_rule *rule,
+                              void *dev_spans, size_t spans_cap, size_t *n_records, void *stream);
+int tsx_hip_trim_spans_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_trim_rule *rule,
+                            tsx_hip_trim_span *spans_out, size_t spans_cap, size_t *n_records, size_t chunk_bytes);
+int tsx_hip_trim_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_trim_rule *rule,
+                              void *dev_out, size_t out_cap, tsx_hip_trim_totals *totals, void *stream);
+int tsx_hip_trim_reads_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_trim_rule *rule, int fd,
+                            size_t chunk_bytes, tsx_hip_trim_totals *totals);
 
 /*
  * Table set operations (csrc/tsx_combine.h; no reference counterpart -- `kmc_tools simple`, `jellyfish merge --min/--max`):

@@ -53,6 +53,21 @@ class FilterRule(ctypes.Structure):
                 ("fraction_ppm", ctypes.c_uint32), ("invert", ctypes.c_int32)]
 
 
+class TrimRule(ctypes.Structure):
+    """tsx_hip_trim_rule: a window is solid when lower <= count <= upper; mode picks the run that is kept."""
+    _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("min_len", ctypes.c_uint64),
+                ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class TrimTotals(ctypes.Structure):
+    """tsx_hip_trim_totals."""
+    _fields_ = [("records", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("bases_in", ctypes.c_uint64),
+                ("bases_kept", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
 class DbInfo(ctypes.Structure):
     """tsx_hip_db_info: the header of a k-mer database file."""
     _fields_ = [("version", ctypes.c_uint32), ("k", ctypes.c_int32), ("l", ctypes.c_int32),
@@ -92,6 +107,21 @@ def filter_rule(lower=2, upper=None, min_in_range=0, fraction=1.0, invert=False)
     """A FilterRule from the Python arguments (fraction: share of a record's k-mers that must be in range, 0..1)."""
     return FilterRule(int(lower), (1 << 64) - 1 if upper is None else int(upper), int(min_in_range),
                       int(round(float(fraction) * 1e6)), 1 if invert else 0)
+
+
+TRIM_MODES = {"longest": 0, "prefix": 1}
+TRIM_SPAN_DTYPE = np.dtype([("start", np.uint64), ("length", np.uint64)])
+
+
+def trim_rule(lower=2, upper=None, mode="longest", min_len=0):
+    """A TrimRule from the Python arguments (mode by name, TRIM_MODES).  Raises ValueError for an unknown mode and for
+    lower > upper, before any GPU call."""
+    if mode not in TRIM_MODES:
+        raise ValueError("trim mode must be one of %s, not %r" % (sorted(TRIM_MODES), mode))
+    upper = (1 << 64) - 1 if upper is None else int(upper)
+    if int(lower) > upper:
+        raise ValueError("trim range: lower %d > upper %d" % (int(lower), upper))
+    return TrimRule(int(lower), upper, int(min_len), TRIM_MODES[mode], 0)
 
 
 def combine_rule(op="intersect", counts="min", a_range=(1, None), b_range=(1, None)):
@@ -198,6 +228,10 @@ def lib():
     L.tsx_hip_query_reads_host.argtypes = [vp, ctypes.c_char_p, sz, u64, u64, vp, sz, ctypes.POINTER(sz), sz]
     L.tsx_hip_filter_reads_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(FilterRule), ci, sz, u64p, u64p]
     L.tsx_hip_filter_reads_device.argtypes = [vp, vp, sz, ctypes.POINTER(FilterRule), vp, sz, ctypes.POINTER(sz), u64p, vp]
+    L.tsx_hip_trim_spans_device.argtypes = [vp, vp, sz, ctypes.POINTER(TrimRule), vp, sz, ctypes.POINTER(sz), vp]
+    L.tsx_hip_trim_spans_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), vp, sz, ctypes.POINTER(sz), sz]
+    L.tsx_hip_trim_reads_device.argtypes = [vp, vp, sz, ctypes.POINTER(TrimRule), vp, sz, ctypes.POINTER(TrimTotals), vp]
+    L.tsx_hip_trim_reads_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), ci, sz, ctypes.POINTER(TrimTotals)]
     L.tsx_hip_hash_apply.argtypes = [vp, u64p, u64p]
     L.tsx_hip_hash_invert.argtypes = [vp, u64p, u64p]
     L.tsx_hip_hash_rows.argtypes = [vp, u64p]
@@ -596,6 +630,60 @@ class TSXHashMapHIP:
                 os.close(fd)
         _check(rc)
         return int(kept.value), int(nbytes.value)
+
+    def trimSpans(self, text, lower=2, upper=None, mode="longest", chunk_bytes=0):
+        """The kept span of every record of a FASTQ / FASTA text (tsx_hip_trim_spans_host): a numpy structured array
+        (TRIM_SPAN_DTYPE: start, length in bases of the sequence line), one entry per record in text order.  A window
+        is solid when its count lies in [lower, upper]; mode "longest" keeps the longest run of solid windows (the
+        leftmost among equals), "prefix" the run that starts the read."""
+        rule = trim_rule(lower, upper, mode)
+        b = bytes(text)
+        cap = len(b) // 256 + 16
+        for _ in range(2):
+            out = np.zeros(cap, dtype=TRIM_SPAN_DTYPE)
+            n = ctypes.c_size_t(0)
+            rc = self._lib.tsx_hip_trim_spans_host(self.handle, b, len(b), ctypes.byref(rule), out.ctypes.data_as(ctypes.c_void_p),
+                                                   cap, ctypes.byref(n), int(chunk_bytes))
+            if rc != ERANGE:
+                break
+            cap = n.value
+        _check(rc)
+        return out[:n.value]
+
+    def trimReads(self, text, path_or_fd, lower=2, upper=None, mode="longest", min_len=0, chunk_bytes=0):
+        """Write the records of `text` cut to their kept spans (tsx_hip_trim_reads_host) to a path (created or
+        truncated) or an open file descriptor; records that keep fewer than min_len bases (0 = k) are dropped.  Returns
+        the totals as a dict: records, kept, bases_in, bases_kept, bytes."""
+        rule = trim_rule(lower, upper, mode, min_len)
+        b = bytes(text)
+        tot = TrimTotals()
+        own = not isinstance(path_or_fd, int)
+        fd = os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd
+        try:
+            rc = self._lib.tsx_hip_trim_reads_host(self.handle, b, len(b), ctypes.byref(rule), fd, int(chunk_bytes),
+                                                   ctypes.byref(tot))
+        finally:
+            if own:
+                os.close(fd)
+        _check(rc)
+        return tot.as_dict()
+
+    def trimSpansDevice(self, text_ptr, nbytes, spans_ptr, cap, rule, stream=None):
+        """tsx_hip_trim_spans_device: the kept spans of the records of a device text into a device buffer of cap spans.
+        Returns the record count (more than cap: TSXException ERANGE)."""
+        vp = ctypes.c_void_p
+        n = ctypes.c_size_t(0)
+        _check(self._lib.tsx_hip_trim_spans_device(self.handle, vp(text_ptr), nbytes, ctypes.byref(rule), vp(spans_ptr), cap,
+                                                   ctypes.byref(n), vp(stream) if stream else None))
+        return int(n.value)
+
+    def trimReadsDevice(self, text_ptr, nbytes, out_ptr, out_cap, rule, stream=None):
+        """tsx_hip_trim_reads_device: the trimmed records of a device text into a device buffer.  Returns the totals."""
+        vp = ctypes.c_void_p
+        tot = TrimTotals()
+        _check(self._lib.tsx_hip_trim_reads_device(self.handle, vp(text_ptr), nbytes, ctypes.byref(rule), vp(out_ptr), out_cap,
+                                                   ctypes.byref(tot), vp(stream) if stream else None))
+        return tot.as_dict()
 
     def queryReadsDevice(self, text_ptr, nbytes, stats_ptr, cap, lower=1, upper=None, stream=None):
         """tsx_hip_query_reads_device: stats of the records of a device text into a device buffer of cap records.

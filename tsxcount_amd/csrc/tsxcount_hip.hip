@@ -12,6 +12,7 @@
 #include "tsx_db.h"
 #include "tsx_combine.h"
 #include "tsx_fasta.h"
+#include "tsx_trim.h"
 #include "tsx_own.h"
 
 #include <mutex>
@@ -4098,5 +4099,302 @@ extern "C" int tsx_hip_filter_reads_device(tsx_hip_map *m, const void *dev_text,
     }
     if (out_bytes) *out_bytes = (size_t)total;
     if (kept_out) *kept_out = kept;
+    return rc;
+}
+
+// ---- read trimming: the solid stretch of every record (tsx_trim.h) ------------------------------------------------
+static bool trim_rule_ok(const tsx_hip_map *m, const tsx_hip_trim_rule *r) {
+    return r && query_args_ok(m, r->lower, r->upper) && (r->mode == TSX_HIP_TRIM_LONGEST || r->mode == TSX_HIP_TRIM_PREFIX) &&
+           r->reserved == 0;
+}
+
+// solid_bits_kernel over the start positions [0, own_end) of d_text (n readable bytes), after query_line_pass.
+static int solid_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
+                        const unsigned long long *d_line_base, const tsx_hip_trim_rule &rule, unsigned long long *d_bits,
+                        hipStream_t st) {
+    if (own_end == 0) return TSX_HIP_OK;
+    const uint64_t ntiles = (own_end + TILE - 1) / TILE;
+    const size_t lut_bytes = m->lut.size() * 8;
+    const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 4);
+    DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((solid_bits_kernel<WKV, CANV, BRV>), dim3(grid), dim3(NT),
+                                                        lut_bytes, st, m->p, d_text, n, own_end, head_open,
+                                                        (const uint32_t *)m->d_tile.get(), ntiles, d_line_base, rule.lower,
+                                                        rule.upper, d_bits, m->qmap_cur))));
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// Spans of a device text in windows, as tsx_hip_query_reads_device: every window adds its words to one bitmap of the
+// whole text and its line offsets to one array; the runs are walked once, after the last window.
+extern "C" int tsx_hip_trim_spans_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_trim_rule *rule,
+                                         void *dev_spans, size_t spans_cap, size_t *n_records, void *stream) {
+    if (n_records) *n_records = 0;
+    if (!trim_rule_ok(m, rule) || (!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_spans && spans_cap)) return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    int rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    if ((rc = base_rule_ok(m)) != TSX_HIP_OK) return rc;
+    if (m->minq && (rc = build_qmap(m, (const uint8_t *)dev_text, n, st)) != TSX_HIP_OK) return rc;
+    const uint16_t *qmap = m->minq ? m->d_qmap.get() : nullptr;
+    QmapScope qs(m);
+    const uint32_t lpr = m->p.line_mask + 1, lshift = lpr == 4 ? 2u : 1u;
+    // (a non-empty line and its '\n' are two bytes: no text holds more records than this)
+    const uint64_t cap = std::min<uint64_t>(spans_cap, n / (2 * lpr) + 2), nwords = ((uint64_t)n + 63) / 64;
+    DevBuf<unsigned long long> bits, lo;
+    SyncAtExit wait(st);
+    TSX_TRY(bits.alloc((nwords + 1) * 8));
+    TSX_TRY(lo.alloc((cap + 1) * TL_N * 8));
+    unsigned long long *span = (unsigned long long *)dev_spans;
+    unsigned long long *d_base = (unsigned long long *)m->d_carry.get() + 2, *d_nrec = d_base + 1;
+    if (spans_cap) HIP_TRY(hipMemsetAsync(span, 0, spans_cap * sizeof(tsx_hip_trim_span), st));
+    HIP_TRY(hipMemsetAsync(lo.get(), 0, (cap + 1) * TL_N * 8, st));
+    HIP_TRY(hipMemsetAsync(d_base, 0, 2 * sizeof(unsigned long long), st));
+    const uint8_t *base = (const uint8_t *)dev_text;
+    const size_t halo = (size_t)m->p.k - 1, WIN = (dev_window_bytes() + 63) & ~(size_t)63;   // whole bitmap words
+    for (size_t off = 0; off < n; off += WIN) {
+        const size_t own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
+        const int head_open = off > 0 ? -1 : 0;
+        const bool last = off + own >= n;
+        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;
+        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
+        if ((rc = query_line_pass(m, base + off, len, own, head_open, st)) != TSX_HIP_OK) return rc;
+        if ((rc = solid_launch(m, base + off, len, own, head_open, d_base, *rule, bits.get() + off / 64, st)) != TSX_HIP_OK) return rc;
+        const uint64_t ntiles = (own + TILE - 1) / TILE;
+        hipLaunchKernelGGL(trim_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
+                           base + off, (uint64_t)len, (uint64_t)own, head_open, (const uint32_t *)m->d_tile.get(), ntiles,
+                           (const unsigned long long *)d_base, (const uint32_t *)m->d_carry.get(), lshift, (uint64_t)off,
+                           last ? 1 : 0, lo.get(), cap);
+        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), last ? 1 : 0,
+                           base + n - 1, lpr, d_nrec);
+    }
+    if (n == 0)
+        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), 1,
+                           (const uint8_t *)nullptr, lpr, d_nrec);
+    if (cap && nwords) {
+        hipLaunchKernelGGL(trim_run_kernel, dim3(grid_for(m, nwords, 8)), dim3(NT), 0, st, (const unsigned long long *)bits.get(),
+                           nwords, (const unsigned long long *)lo.get(), (const unsigned long long *)d_nrec, (uint64_t)0, cap,
+                           (uint32_t)m->p.k, (int)rule->mode, span);
+        hipLaunchKernelGGL(trim_finalize_kernel, dim3(grid_for(m, cap, 8)), dim3(NT), 0, st, span, cap,
+                           (const unsigned long long *)d_nrec, (uint64_t)0);
+    }
+    HIP_TRY(hipGetLastError());
+    unsigned long long nrec = 0;
+    HIP_TRY(hipMemcpyAsync(&nrec, d_nrec, sizeof nrec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n_records) *n_records = (size_t)nrec;
+    return nrec > spans_cap ? TSX_HIP_ERANGE : TSX_HIP_OK;
+}
+
+// Scratch of one trim call that works on pieces.
+struct TrimBufs {
+    DevBuf<uint8_t> text;
+    DevBuf<unsigned long long> bits, lo, span, seg, src;
+    DevBuf<uint8_t> own_out;                       // the output, unless the caller gave a buffer:
+    uint8_t *out = nullptr; size_t out_have = 0;   // where it goes, and the room there
+    DevBuf<unsigned long long> info;               // cut, records, open, total, line base (0), kept, bases in, bases kept
+    PinBuf<unsigned long long> h_info;
+    PinBuf<uint8_t> h_out;
+    Event ev;
+    hipStream_t st;
+    explicit TrimBufs(hipStream_t s) : st(s) {}
+    ~TrimBufs() { (void)hipStreamSynchronize(st); }   // nothing queued may outlive the buffers
+    int init() {
+        TSX_TRY(info.alloc(8 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(info.get(), 0, 8 * sizeof(unsigned long long), st));
+        TSX_TRY(h_info.alloc(8 * sizeof(unsigned long long)));
+        return ev.create();
+    }
+};
+
+// One piece [0, len) of text in device memory that starts at a record boundary: the line pass and the record scan (waits
+// once, for the cut and the record count), then over its whole records [0, cut): bitmap, line offsets, runs, and either
+// the spans alone (b.span, finalized) or -- `copy` -- the segment lengths, their scan (total -> b.info[3], totals ->
+// b.info[5..7]) and the output in b.out (own_out grown to cut + 64, or the caller's buffer, never grown).  What follows
+// the wait is queued, not waited for.  Not last and no whole record: nrec = 0, nothing done.
+static int trim_piece(tsx_hip_map *m, TrimBufs &b, const uint8_t *d_text, uint64_t len, bool last,
+                      const tsx_hip_trim_rule &rule, bool copy, hipStream_t st, uint64_t &cut, uint64_t &nrec) {
+    cut = nrec = 0;
+    if (len == 0) return TSX_HIP_OK;
+    const uint32_t lpr = m->p.line_mask + 1, lshift = lpr == 4 ? 2u : 1u;
+    uint64_t ntiles = (len + TILE - 1) / TILE;
+    int rc;
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
+    if ((rc = query_line_pass(m, d_text, len, len, 0, st)) != TSX_HIP_OK) return rc;
+    hipLaunchKernelGGL(record_scan_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
+                       d_text, len, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), lpr, last ? 1 : 0,
+                       b.info.get(), (unsigned long long *)nullptr, (uint64_t)0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b.h_info.get(), b.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    cut = b.h_info.get()[0]; nrec = b.h_info.get()[1];
+    if (nrec == 0) return TSX_HIP_OK;
+    const uint64_t nwords = (cut + 63) / 64;
+    ntiles = (cut + TILE - 1) / TILE;
+    TSX_TRY(grow(st, b.bits, (nwords + 1) * 8));
+    TSX_TRY(grow(st, b.lo, nrec * TL_N * 8));
+    TSX_TRY(grow(st, b.span, nrec * sizeof(tsx_hip_trim_span)));
+    HIP_TRY(hipMemsetAsync(b.lo.get(), 0, nrec * TL_N * 8, st));
+    HIP_TRY(hipMemsetAsync(b.span.get(), 0, nrec * sizeof(tsx_hip_trim_span), st));
+    QmapScope qs(m);
+    if (m->minq) {   // a quality rule: the bitmap of the whole records (its line pass over [0, cut) rewrites d_tile with the same values)
+        if ((rc = build_qmap(m, d_text, cut, st)) != TSX_HIP_OK) return rc;
+        m->qmap_cur = m->d_qmap.get();
+    }
+    const unsigned long long *zero = b.info.get() + 4;
+    if ((rc = solid_launch(m, d_text, cut, cut, 0, zero, rule, b.bits.get(), st)) != TSX_HIP_OK) return rc;
+    // (the carry is read for an unterminated last line only: then cut = len and it holds the lines of [0, cut))
+    hipLaunchKernelGGL(trim_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
+                       d_text, cut, cut, 0, (const uint32_t *)m->d_tile.get(), ntiles, zero, (const uint32_t *)m->d_carry.get(),
+                       lshift, (uint64_t)0, last ? 1 : 0, b.lo.get(), nrec);
+    hipLaunchKernelGGL(trim_run_kernel, dim3(grid_for(m, nwords, 8)), dim3(NT), 0, st, (const unsigned long long *)b.bits.get(),
+                       nwords, (const unsigned long long *)b.lo.get(), (const unsigned long long *)nullptr, nrec, nrec,
+                       (uint32_t)m->p.k, (int)rule.mode, b.span.get());
+    if (!copy) {
+        hipLaunchKernelGGL(trim_finalize_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.span.get(), nrec,
+                           (const unsigned long long *)nullptr, nrec);
+        HIP_TRY(hipGetLastError());
+        return TSX_HIP_OK;
+    }
+    const uint64_t nseg = nrec * 4, nk = nseg + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    TSX_TRY(grow(st, b.seg, (nk + nchunks + 16) * sizeof(unsigned long long)));
+    TSX_TRY(grow(st, b.src, nseg * sizeof(unsigned long long)));
+    if (cut + 64 > b.out_have) {   // (as grow() finds it: a caller's buffer has the room, tsx_hip_trim_reads_device checks)
+        TSX_TRY(grow(st, b.own_out, cut + 64));
+        b.out = b.own_out.get(); b.out_have = b.own_out.cap();
+    }
+    unsigned long long *const seg = b.seg.get(), *const info = b.info.get();
+    HIP_TRY(hipMemsetAsync(seg + nseg, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(trim_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.span.get(),
+                       (const unsigned long long *)b.lo.get(), nrec, lpr, rule.min_len ? rule.min_len : (uint64_t)m->p.k, seg,
+                       b.src.get(), info + 5);
+    unsigned long long *chunk = seg + nk;
+    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)seg, nk,
+                       chunk);
+    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, info + 3);
+    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, seg, nk, (const unsigned long long *)chunk);
+    // (the copy grid covers the worst case; lanes past the total fall through)
+    hipLaunchKernelGGL(trim_copy_kernel, dim3(grid_for(m, (cut + 16) / 16 + 64, 8)), dim3(NT), 0, st, d_text, cut,
+                       (const unsigned long long *)b.src.get(), (const unsigned long long *)seg, nseg, b.out, (uint64_t)b.out_have);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// The host entry points, as query_host: the text in pieces cut at record boundaries; a piece without a whole record
+// grows until it holds one.  fd < 0: each piece's spans go to spans_out[rec_base ..] while they fit.  Else the output of
+// piece i is written to fd while the device works on piece i + 1.
+static int trim_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_trim_rule &rule, size_t chunk_bytes,
+                     tsx_hip_trim_span *spans_out, size_t spans_cap, size_t *n_records, int fd, tsx_hip_trim_totals *totals) {
+    if (!chunk_bytes) chunk_bytes = QUERY_CHUNK_DEFAULT;
+    chunk_bytes = std::min(chunk_bytes, QUERY_PIECE_MAX);
+    HIP_TRY(hipSetDevice(m->device));
+    join_foreign(m, false);
+    hipStream_t st = m->stream.get();
+    int rc = base_rule_ok(m);
+    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    TrimBufs b(st);
+    rc = b.init();
+    const unsigned long long *h_info = b.h_info.get();
+    tsx_hip_trim_totals t = {0, 0, 0, 0, 0};
+    uint64_t pending = 0;
+    bool have_pending = false;
+    for (size_t off = 0; off < n && rc == TSX_HIP_OK;) {
+        size_t len = std::min(chunk_bytes, n - off);
+        uint64_t cut = 0, nrec = 0;
+        for (;;) {
+            const bool last = off + len == n;
+            if ((rc = grow(st, b.text, len + 256)) != TSX_HIP_OK) break;
+            if (hipMemcpyAsync(b.text.get(), text + off, len, hipMemcpyHostToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            if ((rc = trim_piece(m, b, b.text.get(), len, last, rule, fd >= 0, st, cut, nrec)) != TSX_HIP_OK) break;
+            if (nrec || last) break;
+            if (len >= QUERY_PIECE_MAX) { g_last_error = "a record longer than 3.75 GiB"; rc = TSX_HIP_EINVAL; break; }
+            len = std::min(std::min(2 * len, n - off), QUERY_PIECE_MAX);
+        }
+        if (rc != TSX_HIP_OK) break;
+        if (fd < 0) {
+            if (t.records < spans_cap && nrec &&
+                (hipMemcpyAsync(spans_out + t.records, b.span.get(), std::min<uint64_t>(nrec, spans_cap - t.records) * sizeof(tsx_hip_trim_span),
+                                hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+                rc = TSX_HIP_EHIP;
+        } else if (nrec) {
+            if (hipMemcpyAsync(b.h_info.get() + 3, b.info.get() + 3, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipEventRecord(b.ev.get(), st) != hipSuccess)
+                rc = TSX_HIP_EHIP;
+            if (rc == TSX_HIP_OK && have_pending) {   // the previous piece's output, while the device works on this one
+                rc = write_all(fd, b.h_out.get(), pending);
+                if (rc == TSX_HIP_OK) t.bytes += pending;
+                have_pending = false;
+            }
+            if (rc == TSX_HIP_OK && hipEventSynchronize(b.ev.get()) != hipSuccess) rc = TSX_HIP_EHIP;
+            if (rc == TSX_HIP_OK && h_info[3] > cut + 1) { g_last_error = "trim output larger than its piece"; rc = TSX_HIP_EHIP; }
+            if (rc == TSX_HIP_OK) {
+                const uint64_t total = h_info[3];
+                t.kept += h_info[5]; t.bases_in += h_info[6]; t.bases_kept += h_info[7];
+                // (no wait: the copy that last filled it has been waited for, and written out above)
+                if (b.h_out.reserve(nullptr, total, total + total / 8 + 4096) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
+                if (rc == TSX_HIP_OK && total && (hipMemcpyAsync(b.h_out.get(), b.out, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                                                  hipStreamSynchronize(st) != hipSuccess))
+                    rc = TSX_HIP_EHIP;
+                pending = total;
+                have_pending = rc == TSX_HIP_OK;
+                // (the totals are per piece)
+                if (rc == TSX_HIP_OK && hipMemsetAsync(b.info.get() + 5, 0, 3 * sizeof(unsigned long long), st) != hipSuccess) rc = TSX_HIP_EHIP;
+            }
+        }
+        t.records += nrec;
+        off += cut;
+    }
+    if (rc == TSX_HIP_OK && have_pending) {
+        rc = write_all(fd, b.h_out.get(), pending);
+        if (rc == TSX_HIP_OK) t.bytes += pending;
+    }
+    if (n_records) *n_records = (size_t)t.records;
+    if (totals) *totals = t;
+    if (rc == TSX_HIP_OK && fd < 0 && t.records > spans_cap) rc = TSX_HIP_ERANGE;
+    return rc;
+}
+
+extern "C" int tsx_hip_trim_spans_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_trim_rule *rule,
+                                       tsx_hip_trim_span *spans_out, size_t spans_cap, size_t *n_records, size_t chunk_bytes) {
+    if (n_records) *n_records = 0;
+    if (!trim_rule_ok(m, rule) || (!text && n) || (!spans_out && spans_cap)) return TSX_HIP_EINVAL;
+    return trim_host(m, text, n, *rule, chunk_bytes, spans_out, spans_cap, n_records, -1, nullptr);
+}
+
+extern "C" int tsx_hip_trim_reads_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_trim_rule *rule, int fd,
+                                       size_t chunk_bytes, tsx_hip_trim_totals *totals) {
+    if (totals) *totals = tsx_hip_trim_totals{0, 0, 0, 0, 0};
+    if (!trim_rule_ok(m, rule) || (!text && n) || fd < 0) return TSX_HIP_EINVAL;
+    return trim_host(m, text, n, *rule, chunk_bytes, nullptr, 0, nullptr, fd, totals);
+}
+
+extern "C" int tsx_hip_trim_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_trim_rule *rule,
+                                         void *dev_out, size_t out_cap, tsx_hip_trim_totals *totals, void *stream) {
+    if (totals) *totals = tsx_hip_trim_totals{0, 0, 0, 0, 0};
+    if (!trim_rule_ok(m, rule) || (!dev_text && n) || ((uintptr_t)dev_text & 15) || !dev_out || ((uintptr_t)dev_out & 15) ||
+        n >= QUERY_PIECE_MAX)
+        return TSX_HIP_EINVAL;
+    if (out_cap < n + 64) return TSX_HIP_ERANGE;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    int rc = base_rule_ok(m);
+    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    TrimBufs b(st);
+    rc = b.init();
+    b.out = (uint8_t *)dev_out; b.out_have = out_cap;   // the copy writes the caller's buffer (never grown)
+    tsx_hip_trim_totals t = {0, 0, 0, 0, 0};
+    uint64_t cut = 0, nrec = 0;
+    if (rc == TSX_HIP_OK) rc = trim_piece(m, b, (const uint8_t *)dev_text, n, true, *rule, true, st, cut, nrec);
+    if (rc == TSX_HIP_OK && nrec) {
+        if (hipMemcpyAsync(b.h_info.get() + 3, b.info.get() + 3, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            rc = TSX_HIP_EHIP;
+        const unsigned long long *h = b.h_info.get();
+        if (rc == TSX_HIP_OK) { t.records = nrec; t.bytes = h[3]; t.kept = h[5]; t.bases_in = h[6]; t.bases_kept = h[7]; }
+        if (rc == TSX_HIP_OK && t.bytes > cut + 1) { g_last_error = "trim output larger than its text"; rc = TSX_HIP_EHIP; }
+    }
+    if (totals) *totals = t;
     return rc;
 }

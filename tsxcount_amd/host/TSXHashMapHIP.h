@@ -77,6 +77,32 @@ static std::pair<uint64_t, uint64_t> tsx_filter_reads(tsx_hip_map *pMap, const c
     fnCheck(rc);
     return std::make_pair(iKept, iWritten);
 }
+// Read trimming over one table (tsx_hip_trim_spans_host / tsx_hip_trim_reads_host).
+template <typename C>
+static std::vector<tsx_hip_trim_span> tsx_trim_spans(tsx_hip_map *pMap, const char *pText, size_t iBytes,
+                                                     const tsx_hip_trim_rule &oRule, size_t iChunkBytes, C fnCheck) {
+    std::vector<tsx_hip_trim_span> out(iBytes / 256 + 16);
+    size_t n = 0;
+    int rc = tsx_hip_trim_spans_host(pMap, pText, iBytes, &oRule, out.data(), out.size(), &n, iChunkBytes);
+    if (rc == TSX_HIP_ERANGE) {
+        out.resize(n);
+        rc = tsx_hip_trim_spans_host(pMap, pText, iBytes, &oRule, out.data(), n, &n, iChunkBytes);
+    }
+    fnCheck(rc);
+    out.resize(n);
+    return out;
+}
+template <typename C>
+static tsx_hip_trim_totals tsx_trim_reads(tsx_hip_map *pMap, const char *pText, size_t iBytes, const tsx_hip_trim_rule &oRule,
+                                          const std::string &sPath, size_t iChunkBytes, C fnCheck) {
+    const int fd = open(sPath.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) throw TSXException("could not open " + sPath + " for writing", TSX_HIP_EIO);
+    tsx_hip_trim_totals oTotals = {0, 0, 0, 0, 0};
+    int rc = tsx_hip_trim_reads_host(pMap, pText, iBytes, &oRule, fd, iChunkBytes, &oTotals);
+    if (close(fd) != 0 && rc == TSX_HIP_OK) rc = TSX_HIP_EIO;
+    fnCheck(rc);
+    return oTotals;
+}
 
 class TSXHashMapHIP {
 public:
@@ -199,6 +225,16 @@ public:
     std::pair<uint64_t, uint64_t> filterReads(const char *pText, size_t iBytes, const tsx_hip_filter_rule &oRule,
                                               const std::string &sPath, size_t iChunkBytes = 0) {
         return tsx_filter_reads(m_pMap, pText, iBytes, oRule, sPath, iChunkBytes, check);
+    }
+    // the kept span (start, length) of every record of a text under oRule (tsx_hip_trim_spans_host)
+    std::vector<tsx_hip_trim_span> trimSpans(const char *pText, size_t iBytes, const tsx_hip_trim_rule &oRule,
+                                             size_t iChunkBytes = 0) {
+        return tsx_trim_spans(m_pMap, pText, iBytes, oRule, iChunkBytes, check);
+    }
+    // the records of a text cut to their kept spans into sPath (created / truncated); returns the totals
+    tsx_hip_trim_totals trimReads(const char *pText, size_t iBytes, const tsx_hip_trim_rule &oRule, const std::string &sPath,
+                                  size_t iChunkBytes = 0) {
+        return tsx_trim_reads(m_pMap, pText, iBytes, oRule, sPath, iChunkBytes, check);
     }
 
     // set operation on two tables (tsx_hip_combine): this is A, oOther is B, the result goes into the empty table oOut

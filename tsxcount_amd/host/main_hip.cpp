@@ -45,6 +45,10 @@ struct arguments {
     uint64_t filter_lower = 2, filter_upper = UINT64_MAX, filter_min = 0;
     double filter_fraction = 1.0;
     bool filter_invert = false;
+    // read trimming after the count: --trim=OUT writes the records of --trim-input (default --input) cut to their solid
+    // stretch, --trim-spans=FILE one line index<TAB>start<TAB>length per record
+    std::string trim, trim_input, trim_spans, trim_mode = "longest";
+    uint64_t trim_lower = 2, trim_upper = UINT64_MAX, trim_min_len = 0;
     // k-mer databases: --save=DB after the count and the check, --load=DB[,DB2,...] before the count (summed)
     std::string save;
     std::vector<std::string> load;
@@ -72,6 +76,8 @@ static int usage() {
                  "                [--output=FILE [--lower=N] [--upper=N]] [--histo=FILE [--histo-max=H]]\n"
                  "                [--filter=OUT] [--read-stats=FILE] [--filter-input=FILE] [--filter-lower=N] [--filter-upper=N]\n"
                  "                [--filter-min=M] [--filter-fraction=F] [--filter-invert] [--save=DB] [--load=DB[,DB2,...]]\n"
+                 "                [--trim=OUT] [--trim-spans=FILE] [--trim-input=FILE] [--trim-lower=N] [--trim-upper=N]\n"
+                 "                [--trim-mode=longest|prefix] [--trim-min-len=N]\n"
                  "                [--with=DB[,DB2,...] [--op=intersect|union|subtract|diff] [--op-count=min|max|sum|left|right]\n"
                  "                 [--a-lower=N] [--a-upper=N] [--b-lower=N] [--b-upper=N] [--compare]]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
@@ -92,6 +98,12 @@ static int usage() {
                  "with at least M (default 0) k-mers in range that make at least the share F (default 1.0) of its k-mers.\n"
                  "--filter-invert writes the records that fail. --read-stats writes index<TAB>kmers<TAB>in_range<TAB>min<TAB>sum\n"
                  "per record of the same input. One GPU only.\n"
+                 "--trim writes the records of --trim-input (default: --input) cut to their solid stretch: a window is solid\n"
+                 "when its count lies in trim-lower..trim-upper (default 2..unbounded); --trim-mode=longest keeps the longest run\n"
+                 "of solid windows (the leftmost among equals), prefix the run that starts the read. Records that keep fewer\n"
+                 "than trim-min-len bases (default k) are dropped. --trim-spans writes index<TAB>start<TAB>length per record.\n"
+                 "Prints trim<TAB>records<TAB>kept<TAB>bases_in<TAB>bases_kept. One GPU only; --trim-input goes by its own file\n"
+                 "name and is never wrapped FASTA.\n"
                  "--save writes the table as a k-mer database after the count and the check. --load fills the table from\n"
                  "k-mer databases first (several are summed); the first sets k, l, s and the seed unless they are given, a\n"
                  "different l or s re-inserts every k-mer. --input is then optional: its reads are counted on top of the\n"
@@ -260,6 +272,69 @@ static int run_read_queries(tsx_hip_map *pMap, const arguments &a) {
     }
     if (map) munmap(map, n);
     return 0;
+}
+
+static bool wants_trim(const arguments &a) { return !a.trim.empty() || !a.trim_spans.empty(); }
+
+// --trim and --trim-spans on one table, where --filter runs.  The input loads as the filter's does.
+static int run_trim(tsx_hip_map *pMap, const arguments &a) {
+    auto check = [](int rc) {
+        if (rc == TSX_HIP_OK) return;
+        std::string msg = tsx_hip_strerror(rc);
+        if (rc == TSX_HIP_EHIP || rc == TSX_HIP_EIO || rc == TSX_HIP_ENOMEM) msg += std::string(" (") + tsx_hip_last_error() + ")";
+        throw TSXException(msg, rc);
+    };
+    const std::string path = a.trim_input.empty() ? a.input_path : a.trim_input;
+    std::vector<char> owned;
+    const char *text = nullptr;
+    size_t n = 0;
+    void *map = nullptr;
+    bool bgzf = false;
+    if (!load_input(path, owned, text, n, map, bgzf, true)) {
+        std::cerr << "Could not read " << path << std::endl;
+        return 3;
+    }
+    if (bgzf) {
+        size_t members = 0, tb = 0, got = 0;
+        check(tsx_hip_bgzf_index_host(text, n, &members, &tb));
+        std::vector<char> inflated(tb ? tb : 1);
+        check(tsx_hip_inflate_bgzf_host(a.device, text, n, inflated.data(), tb, &got));
+        munmap(map, n);
+        map = nullptr;
+        owned.swap(inflated);
+        owned.resize(got);
+        text = owned.data();
+        n = got;
+    }
+    check(tsx_hip_set_record_lines(pMap, is_fasta_path(path, is_wrapped(a) ? std::string() : a.format) ? 2 : 4));
+    tsx_hip_trim_rule rule;
+    rule.lower = a.trim_lower;
+    rule.upper = a.trim_upper;
+    rule.min_len = a.trim_min_len;
+    rule.mode = a.trim_mode == "prefix" ? TSX_HIP_TRIM_PREFIX : TSX_HIP_TRIM_LONGEST;
+    rule.reserved = 0;
+    if (!a.trim_spans.empty()) {
+        const std::vector<tsx_hip_trim_span> sp = tsx_trim_spans(pMap, text, n, rule, 0, check);
+        std::ofstream f(a.trim_spans);
+        for (size_t i = 0; i < sp.size(); ++i) f << i << '\t' << sp[i].start << '\t' << sp[i].length << '\n';
+        f.close();
+        if (!f) throw TSXException("could not write " + a.trim_spans, TSX_HIP_EIO);
+        std::cerr << "Wrote the kept spans of " << sp.size() << " records to " << a.trim_spans << std::endl;
+    }
+    if (!a.trim.empty()) {
+        const tsx_hip_trim_totals t = tsx_trim_reads(pMap, text, n, rule, a.trim, 0, check);
+        std::cout << "trim\t" << t.records << '\t' << t.kept << '\t' << t.bases_in << '\t' << t.bases_kept << std::endl;
+        std::cerr << "Wrote " << t.kept << " trimmed records (" << t.bytes << " bytes) to " << a.trim << std::endl;
+    }
+    if (map) munmap(map, n);
+    return 0;
+}
+
+// what follows the count, the check, the outputs and the set operation: the read queries, then the trim
+static int run_after(tsx_hip_map *pMap, const arguments &a) {
+    const int rq = wants_queries(a) ? run_read_queries(pMap, a) : 0;
+    const int rt = wants_trim(a) ? run_trim(pMap, a) : 0;
+    return rq ? rq : rt;
 }
 
 // --save, after the count and the check (one table only: a group refuses it earlier)
@@ -458,6 +533,13 @@ int main(int argc, char *argv[]) {
         else if (opt(argv[i], "filter-min", v)) a.filter_min = strtoull(v.c_str(), nullptr, 10);
         else if (opt(argv[i], "filter-fraction", v)) a.filter_fraction = atof(v.c_str());
         else if (opt(argv[i], "filter-invert", v)) a.filter_invert = true;
+        else if (opt(argv[i], "trim", v)) { a.trim = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "trim-spans", v)) { a.trim_spans = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "trim-input", v)) a.trim_input = v;
+        else if (opt(argv[i], "trim-lower", v)) a.trim_lower = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "trim-upper", v)) a.trim_upper = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "trim-mode", v)) a.trim_mode = v;
+        else if (opt(argv[i], "trim-min-len", v)) a.trim_min_len = strtoull(v.c_str(), nullptr, 10);
         else if (opt(argv[i], "read-stats", v)) { a.read_stats = v; if (v.empty()) return usage(); }
         else if (opt(argv[i], "devices", v)) {
             for (size_t at = 0; at < v.size();) {
@@ -587,6 +669,11 @@ int main(int argc, char *argv[]) {
                       << " (FASTQ, or FASTA with one sequence line per record)" << std::endl;
             return usage();
         }
+        if (wants_trim(a) && (a.trim_input.empty() || a.trim_input == a.input_path)) {
+            std::cerr << "--trim and --trim-spans do not read wrapped FASTA: give the reads to trim as --trim-input=FILE"
+                      << " (FASTQ, or FASTA with one sequence line per record)" << std::endl;
+            return usage();
+        }
         a.group = false;   // --gpus=1: the one table of this process
     }
     if (a.gpus < 1 || (a.comm != "rccl" && a.comm != "copy") || (!a.devices.empty() && (int)a.devices.size() != a.gpus)) return usage();
@@ -595,6 +682,17 @@ int main(int argc, char *argv[]) {
         std::cerr << "--filter and --read-stats run on one GPU only: every k-mer lives on one rank of a --gpus " << a.gpus
                   << " run, and per-rank queries are not combined yet. Count with --gpus=1 (or without --gpus) to filter."
                   << std::endl;
+        return usage();
+    }
+    if (a.trim_lower > a.trim_upper || (a.trim_mode != "longest" && a.trim_mode != "prefix")) return usage();
+    if (wants_trim(a) && a.gpus > 1) {
+        std::cerr << "--trim and --trim-spans run on one GPU only: every k-mer lives on one rank of a --gpus " << a.gpus
+                  << " run, and per-rank spans are not combined yet. Count with --gpus=1 (or without --gpus) to trim."
+                  << std::endl;
+        return usage();
+    }
+    if (wants_trim(a) && a.input_path.empty() && a.trim_input.empty()) {
+        std::cerr << "--trim and --trim-spans without --input need --trim-input=FILE" << std::endl;
         return usage();
     }
     if ((!a.save.empty() || !a.load.empty()) && a.gpus > 1) {
@@ -660,8 +758,8 @@ int main(int argc, char *argv[]) {
         if (map) munmap(map, n);
         if (a.with.empty()) {
             const int rc = report_and_check(oMap, a, dt);
-            if (!wants_queries(a)) return rc;
-            const int rq = run_read_queries(oMap.handle(), a);
+            if (!wants_queries(a) && !wants_trim(a)) return rc;
+            const int rq = run_after(oMap.handle(), a);
             return rc ? rc : rq;
         }
         // --with: B is built like its first database, OUT like A; the result takes A's place from here on
@@ -682,8 +780,8 @@ int main(int argc, char *argv[]) {
             std::cout << "compare-sums\t" << s.a_sum_both << '\t' << s.b_sum_both << std::endl;
         }
         if (a.op.empty()) {
-            if (!wants_queries(a)) return rc;
-            const int rq = run_read_queries(oMap.handle(), a);
+            if (!wants_queries(a) && !wants_trim(a)) return rc;
+            const int rq = run_after(oMap.handle(), a);
             return rc ? rc : rq;
         }
         std::cerr << "Creating the result table" << std::endl;
@@ -696,8 +794,8 @@ int main(int argc, char *argv[]) {
                   << s.a_in_range << ", second " << s.b_in_range << ", both " << s.both << " in range)" << std::endl;
         save_database(oOut, a);
         write_outputs(oOut, a);
-        if (!wants_queries(a)) return rc;
-        const int rq = run_read_queries(oOut.handle(), a);
+        if (!wants_queries(a) && !wants_trim(a)) return rc;
+        const int rq = run_after(oOut.handle(), a);
         return rc ? rc : rq;
     } catch (const TSXException &e) {
         std::cerr << "TSXException: " << e.what() << std::endl;
