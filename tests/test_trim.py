@@ -192,9 +192,9 @@ def T():
     return tsxcount_amd
 
 
-def genome_map(T, k=K, l=18, counted=COUNTED, **kw):
-    m = T.TSXHashMapHIP(l, 0, k, **kw)
-    m.set_path(1)
+def genome_map(T, k=K, l=18, counted=COUNTED, s=0, path=1, **kw):
+    m = T.TSXHashMapHIP(l, s, k, **kw)
+    m.set_path(path)
     m.set_record_lines(2)
     m.countFastq(counted)
     return m
