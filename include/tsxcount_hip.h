@@ -36,7 +36,8 @@ enum {
     TSX_HIP_ERANGE = -7,    /* output buffer too small */
     TSX_HIP_ELOCK = -8,     /* a multi-limb slot stayed locked past the spin bound: counts may be wrong */
     TSX_HIP_EIO = -9,       /* writing an output file failed (see tsx_hip_last_error) */
-    TSX_HIP_EFORMAT = -10   /* not a k-mer database, or a damaged one (see tsx_hip_last_error) */
+    TSX_HIP_EFORMAT = -10,  /* not a k-mer database, or a damaged one (see tsx_hip_last_error) */
+    TSX_HIP_EPAIR = -11     /* the mates of paired reads do not line up (see tsx_hip_last_error) */
 };
 
 /* Layout the library derived from (k, l, storagebits); see DESIGN.md. */
@@ -467,6 +468,56 @@ int tsx_hip_trim_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, co
                               void *dev_out, size_t out_cap, tsx_hip_trim_totals *totals, void *stream);
 int tsx_hip_trim_reads_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_trim_rule *rule, int fd,
                             size_t chunk_bytes, tsx_hip_trim_totals *totals);
+
+/*
+ * Paired reads kept in step (csrc/tsx_pairs.h; no reference counterpart -- khmer `--paired`, Trimmomatic PE, BBDuk
+ * in1/in2): the filter and the trim over mate pairs, so that the outputs line up record for record.  Records, lines,
+ * k-mers, c(x) and the base rule are those of tsx_hip_query_reads_*.
+ *   Two texts A and B (text2 != NULL): pair i is record i of A (mate 1) and record i of B (mate 2).  Record counts are
+ *     as tsx_hip_query_reads_host reports them (a trailing incomplete record is one record).
+ *   One interleaved text (text2 == NULL, n2 = 0): pair i is records 2 i and 2 i + 1.
+ * Different record counts in A and B, or an odd count in an interleaved text: TSX_HIP_EPAIR.
+ * check_names != 0: the NAME of a record is the part of its first line after the first byte ('@' or '>') up to the
+ *   first space or tab, or the line's end, with one trailing "/1" or "/2" removed.  Mates must have byte-equal names; the
+ *   first pair that does not gives TSX_HIP_EPAIR, and tsx_hip_last_error names the pair's index (from 0).  The names are
+ *   compared on the device.  check_names == 0: names are not looked at.
+ * On TSX_HIP_EPAIR the outputs hold, at most, whole pairs from the pieces before the one that failed.
+ * Filter: a mate's verdict is that of tsx_hip_filter_reads_* under the same rule, invert included.  pair_mode
+ *   TSX_HIP_PAIR_BOTH keeps a pair when both verdicts hold, TSX_HIP_PAIR_ANY when at least one does.  A kept pair writes
+ *   both mates whole, by the filter's write rules (the '\n' added for an unterminated last line of either text; empty
+ *   lines are not written).  Under BOTH a mate that passes while its partner fails is an ORPHAN; ANY has no orphans.
+ * Trim: each mate is trimmed on its own by the rule.  A mate SURVIVES when tsx_hip_trim_reads_* would write it (length
+ *   >= min_len, 0 = k).  A pair is kept when both survive, each mate written exactly as the single-end trim writes it; a
+ *   lone survivor is an orphan, written the same way.
+ * Outputs (tsx_hip_pair_io), everything in input order:
+ *   two texts    kept mates 1 to fd1, kept mates 2 to fd2 (both required); orphans of A to fd_single1, of B to
+ *                fd_single2 (each may be -1: those orphans are dropped, and still counted)
+ *   interleaved  kept pairs to fd1 as mate 1, mate 2; orphans to fd_single1 (may be -1); fd2 and fd_single2 must be -1
+ * totals (optional): pairs seen, pairs kept, orphans of each side (mate 1 / mate 2 for an interleaved text), bytes
+ * written per output (0 for a dropped one); for the trim also bases_in = bases of all sequence lines seen and
+ * bases_kept = bases of the kept pairs and the orphans (dropped orphans included); the filter leaves both 0.
+ * The texts are taken in pieces of chunk_bytes each (0 = 256 MiB; a record longer than a piece is taken whole); every
+ * round takes the same number of records from both; the device works on round i + 1 while the host writes round i.
+ * TSX_HIP_EINVAL, before any HIP call: what the single-end calls refuse (a map created with shard_bits > 0, lower >
+ * upper, fraction_ppm > 10^6, an unknown trim mode, reserved != 0), an unknown pair_mode, io == NULL, a required fd < 0,
+ * an fd that must be -1 and is not.  A failed write: TSX_HIP_EIO.
+ */
+#define TSX_HIP_PAIR_BOTH 0
+#define TSX_HIP_PAIR_ANY 1
+typedef struct tsx_hip_pair_io {
+    int fd1, fd2, fd_single1, fd_single2;
+} tsx_hip_pair_io;
+typedef struct tsx_hip_pair_totals {
+    uint64_t pairs, kept, single1, single2;
+    uint64_t bytes1, bytes2, bytes_single1, bytes_single2;
+    uint64_t bases_in, bases_kept;
+} tsx_hip_pair_totals;
+int tsx_hip_filter_pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *text2, size_t n2,
+                              const tsx_hip_filter_rule *rule, int pair_mode, int check_names, const tsx_hip_pair_io *io,
+                              size_t chunk_bytes, tsx_hip_pair_totals *totals);
+int tsx_hip_trim_pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *text2, size_t n2,
+                            const tsx_hip_trim_rule *rule, int check_names, const tsx_hip_pair_io *io, size_t chunk_bytes,
+                            tsx_hip_pair_totals *totals);
 
 /*
  * Table set operations (csrc/tsx_combine.h; no reference counterpart -- `kmc_tools simple`, `jellyfish merge --min/--max`):

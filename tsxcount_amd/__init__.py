@@ -17,6 +17,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tsxcount_hip.h")
 
 OK, EINVAL, ENODEVICE, ENOMEM, EHIP, EFULL, EOVERFLOW, ERANGE, ELOCK, EIO = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9
 EFORMAT = -10
+EPAIR = -11
 
 
 class TSXException(RuntimeError):
@@ -63,6 +64,20 @@ class TrimTotals(ctypes.Structure):
     """tsx_hip_trim_totals."""
     _fields_ = [("records", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("bases_in", ctypes.c_uint64),
                 ("bases_kept", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+class PairIO(ctypes.Structure):
+    """tsx_hip_pair_io: the four outputs of a pair call (-1 = none)."""
+    _fields_ = [("fd1", ctypes.c_int), ("fd2", ctypes.c_int), ("fd_single1", ctypes.c_int), ("fd_single2", ctypes.c_int)]
+
+
+class PairTotals(ctypes.Structure):
+    """tsx_hip_pair_totals."""
+    _fields_ = [(f, ctypes.c_uint64) for f in ("pairs", "kept", "single1", "single2", "bytes1", "bytes2", "bytes_single1",
+                                               "bytes_single2", "bases_in", "bases_kept")]
 
     def as_dict(self):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
@@ -122,6 +137,23 @@ def trim_rule(lower=2, upper=None, mode="longest", min_len=0):
     if int(lower) > upper:
         raise ValueError("trim range: lower %d > upper %d" % (int(lower), upper))
     return TrimRule(int(lower), upper, int(min_len), TRIM_MODES[mode], 0)
+
+
+PAIR_MODES = {"both": 0, "any": 1}
+
+
+def pair_name(header_line):
+    """The name of a record as the pair calls compare it (check_names): the header line after its first byte ('@' or
+    '>') up to the first space or tab, or the line's end, without one trailing "/1" or "/2"."""
+    line = bytes(header_line.encode() if isinstance(header_line, str) else header_line).split(b"\n")[0]
+    name = line[1:]
+    for i, c in enumerate(name):
+        if c in b" \t":
+            name = name[:i]
+            break
+    if name.endswith((b"/1", b"/2")):
+        name = name[:-2]
+    return name
 
 
 def combine_rule(op="intersect", counts="min", a_range=(1, None), b_range=(1, None)):
@@ -232,6 +264,10 @@ def lib():
     L.tsx_hip_trim_spans_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), vp, sz, ctypes.POINTER(sz), sz]
     L.tsx_hip_trim_reads_device.argtypes = [vp, vp, sz, ctypes.POINTER(TrimRule), vp, sz, ctypes.POINTER(TrimTotals), vp]
     L.tsx_hip_trim_reads_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), ci, sz, ctypes.POINTER(TrimTotals)]
+    L.tsx_hip_filter_pairs_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(FilterRule), ci, ci,
+                                            ctypes.POINTER(PairIO), sz, ctypes.POINTER(PairTotals)]
+    L.tsx_hip_trim_pairs_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), ci,
+                                          ctypes.POINTER(PairIO), sz, ctypes.POINTER(PairTotals)]
     L.tsx_hip_hash_apply.argtypes = [vp, u64p, u64p]
     L.tsx_hip_hash_invert.argtypes = [vp, u64p, u64p]
     L.tsx_hip_hash_rows.argtypes = [vp, u64p]
@@ -273,7 +309,7 @@ def _check(code):
     if code != OK:
         L = lib()
         msg = L.tsx_hip_strerror(code).decode()
-        if code in (EHIP, ENODEVICE, ENOMEM, EIO, EFORMAT):
+        if code in (EHIP, ENODEVICE, ENOMEM, EIO, EFORMAT, EPAIR):
             extra = L.tsx_hip_last_error().decode()
             if extra:
                 msg += " (" + extra + ")"
@@ -667,6 +703,58 @@ class TSXHashMapHIP:
                 os.close(fd)
         _check(rc)
         return tot.as_dict()
+
+    def _pairs(self, call, text1, text2, out1, out2, singles, chunk_bytes):
+        """The common part of filterPairs / trimPairs: the four outputs opened (paths) or taken (fds), the call, the
+        totals as a dict."""
+        b1 = bytes(text1)
+        b2 = None if text2 is None else bytes(text2)
+        s1, s2 = singles
+        if b2 is None and (out2 is not None or s2 is not None):
+            raise ValueError("an interleaved text has one output and one singles output")
+        if out1 is None or (b2 is not None and out2 is None):
+            raise ValueError("the kept pairs need an output for each input text")
+        opened, fds = [], []
+        try:
+            for o in (out1, out2, s1, s2):
+                if o is None:
+                    fds.append(-1)
+                elif isinstance(o, int):
+                    fds.append(o)
+                else:
+                    fds.append(os.open(o, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644))
+                    opened.append(fds[-1])
+            io, tot = PairIO(*fds), PairTotals()
+            rc = call(b1, len(b1), b2, 0 if b2 is None else len(b2), ctypes.byref(io), int(chunk_bytes), ctypes.byref(tot))
+        finally:
+            for fd in opened:
+                os.close(fd)
+        _check(rc)
+        return tot.as_dict()
+
+    def filterPairs(self, text1, text2, out1, out2=None, singles=(None, None), pairs="both", check_names=False, lower=2,
+                    upper=None, min_in_range=0, fraction=1.0, invert=False, chunk_bytes=0):
+        """The read filter over mate pairs (tsx_hip_filter_pairs_host): record i of text1 and record i of text2 are
+        one pair (text2=None: text1 is interleaved).  pairs="both" keeps a pair when both mates pass the rule, "any"
+        when one does; kept mates go to out1 / out2 (interleaved: both to out1), a mate that passes alone under "both"
+        to its singles output (None drops it).  Outputs are paths (created or truncated) or open file descriptors.
+        check_names compares the mates' names (pair_name).  Returns the totals as a dict (PairTotals)."""
+        if pairs not in PAIR_MODES:
+            raise ValueError("pairs must be one of %s, not %r" % (sorted(PAIR_MODES), pairs))
+        rule = filter_rule(lower, upper, min_in_range, fraction, invert)
+        return self._pairs(lambda b1, n1, b2, n2, io, chunk, tot: self._lib.tsx_hip_filter_pairs_host(
+            self.handle, b1, n1, b2, n2, ctypes.byref(rule), PAIR_MODES[pairs], 1 if check_names else 0, io, chunk, tot),
+            text1, text2, out1, out2, singles, chunk_bytes)
+
+    def trimPairs(self, text1, text2, out1, out2=None, singles=(None, None), check_names=False, lower=2, upper=None,
+                  mode="longest", min_len=0, chunk_bytes=0):
+        """The trim over mate pairs (tsx_hip_trim_pairs_host): each mate is trimmed as trimReads trims it; a pair whose
+        mates both survive goes to out1 / out2, a lone survivor to its singles output.  Arguments and result as
+        filterPairs; the totals also count bases_in and bases_kept."""
+        rule = trim_rule(lower, upper, mode, min_len)
+        return self._pairs(lambda b1, n1, b2, n2, io, chunk, tot: self._lib.tsx_hip_trim_pairs_host(
+            self.handle, b1, n1, b2, n2, ctypes.byref(rule), 1 if check_names else 0, io, chunk, tot),
+            text1, text2, out1, out2, singles, chunk_bytes)
 
     def trimSpansDevice(self, text_ptr, nbytes, spans_ptr, cap, rule, stream=None):
         """tsx_hip_trim_spans_device: the kept spans of the records of a device text into a device buffer of cap spans.

@@ -266,6 +266,13 @@ __global__ __launch_bounds__(NT) void record_scan_kernel(const uint8_t *buf, uin
     }
 }
 
+// The filter's rule for one record: in_range >= min_in_range and in_range * 10^6 >= ppm * kmers (exact, 128-bit products).
+__device__ __forceinline__ bool filter_pass(uint64_t km, uint64_t inr, uint64_t min_in, uint64_t ppm) {
+    const uint64_t ah = __umul64hi(inr, 1000000ULL), al = inr * 1000000ULL;
+    const uint64_t bh = __umul64hi(ppm, km), bl = ppm * km;
+    return (inr >= min_in) && (ah > bh || (ah == bh && al >= bl));
+}
+
 // The rule of tsx_hip_filter_reads_host: pass iff in_range >= min_in_range and in_range * 10^6 >= ppm * kmers (exact,
 // 128-bit products); invert writes the failures.  len[r] = bytes record r contributes: its span, plus the '\n' the text
 // lacks for the last record when nl_last; *kept counts the records written.
@@ -273,11 +280,7 @@ __global__ __launch_bounds__(NT) void filter_len_kernel(const unsigned long long
                                                         uint64_t nrec, uint64_t min_in, uint64_t ppm, int invert, int nl_last,
                                                         unsigned long long *len, unsigned long long *kept) {
     for (uint64_t r = (uint64_t)blockIdx.x * NT + threadIdx.x; r < nrec; r += (uint64_t)gridDim.x * NT) {
-        const uint64_t km = stats[r * QS_N + QS_KMERS], inr = stats[r * QS_N + QS_INRANGE];
-        const uint64_t ah = __umul64hi(inr, 1000000ULL), al = inr * 1000000ULL;
-        const uint64_t bh = __umul64hi(ppm, km), bl = ppm * km;
-        const bool frac = ah > bh || (ah == bh && al >= bl);
-        const bool pass = (inr >= min_in) && frac;
+        const bool pass = filter_pass(stats[r * QS_N + QS_KMERS], stats[r * QS_N + QS_INRANGE], min_in, ppm);
         uint64_t l = 0;
         if (pass != (invert != 0)) l = span[r * 2 + 1] - span[r * 2] + ((nl_last && r + 1 == nrec) ? 1 : 0);
         len[r] = l;

@@ -13,6 +13,7 @@
 #include "tsx_combine.h"
 #include "tsx_fasta.h"
 #include "tsx_trim.h"
+#include "tsx_pairs.h"
 #include "tsx_own.h"
 
 #include <mutex>
@@ -193,6 +194,7 @@ extern "C" const char *tsx_hip_strerror(int code) {
         case TSX_HIP_ELOCK: return "a multi-limb slot stayed locked past the spin bound";
         case TSX_HIP_EIO: return "writing the output failed";
         case TSX_HIP_EFORMAT: return "not a k-mer database, or a damaged one";
+        case TSX_HIP_EPAIR: return "the mates of a pair do not line up";
     }
     return "unknown";
 }
@@ -3906,28 +3908,28 @@ struct QueryBufs {
     }
 };
 
-// One piece [0, len) of text in device memory that starts at a record boundary: the line pass, the record scan (where
-// the last whole record ends, and the spans when `spans`), then -- when it holds a whole record -- the stats of its
-// records [0, nrec) in b.stats.  Waits once, for the cut.  Not last and no whole record: nrec = 0, nothing queried.
-static int query_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint64_t len, bool last, uint64_t lower,
-                       uint64_t upper, bool spans, hipStream_t st, uint64_t &cut, uint64_t &nrec, bool &open) {
-    cut = nrec = 0; open = false;
-    if (len == 0) return TSX_HIP_OK;
+// The scan half of a piece [0, len) of text in device memory that starts at a record boundary: the line pass and the
+// record scan into info[0..2] (cut, records, open), with the record spans when `span` is given.  Queued, not waited for.
+static int piece_scan(tsx_hip_map *m, const uint8_t *d_text, uint64_t len, bool last, unsigned long long *info,
+                      DevBuf<unsigned long long> *span, hipStream_t st) {
     const uint32_t lpr = m->p.line_mask + 1;
     const uint64_t ntiles = (len + TILE - 1) / TILE, span_cap = len / (2 * lpr) + 2;
     int rc;
     HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
     if ((rc = query_line_pass(m, d_text, len, len, 0, st)) != TSX_HIP_OK) return rc;
-    if (spans && (rc = grow(st, b.span, span_cap * 16)) != TSX_HIP_OK) return rc;
+    if (span && (rc = grow(st, *span, span_cap * 16)) != TSX_HIP_OK) return rc;
     hipLaunchKernelGGL(record_scan_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
                        d_text, len, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), lpr, last ? 1 : 0,
-                       b.info.get(), spans ? b.span.get() : nullptr, span_cap);
+                       info, span ? span->get() : (unsigned long long *)nullptr, span ? span_cap : (uint64_t)0);
     HIP_TRY(hipGetLastError());
-    const unsigned long long *h_info = b.h_info.get();
-    HIP_TRY(hipMemcpyAsync(b.h_info.get(), b.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    cut = h_info[0]; nrec = h_info[1]; open = h_info[2] != 0;
-    if (nrec == 0) return TSX_HIP_OK;
+    return TSX_HIP_OK;
+}
+
+// The query half: the stats of the records [0, nrec) of d_text[0, cut) in b.stats, after a line pass over a text that
+// starts with [0, cut) (the tile line counts).  Queued, not waited for.
+static int query_records(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint64_t cut, uint64_t nrec, uint64_t lower,
+                         uint64_t upper, hipStream_t st) {
+    int rc;
     if ((rc = grow(st, b.stats, nrec * sizeof(tsx_hip_read_stats))) != TSX_HIP_OK) return rc;
     HIP_TRY(hipMemsetAsync(b.stats.get(), 0, nrec * sizeof(tsx_hip_read_stats), st));
     QmapScope qs(m);
@@ -3938,6 +3940,41 @@ static int query_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint
     if ((rc = query_launch(m, d_text, cut, cut, 0, b.info.get() + 4, lower, upper, b.stats.get(), nrec, st)) != TSX_HIP_OK) return rc;
     hipLaunchKernelGGL(query_finalize_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.stats.get(), nrec,
                        (const unsigned long long *)nullptr, nrec);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// One piece [0, len) of text in device memory that starts at a record boundary: the line pass, the record scan (where
+// the last whole record ends, and the spans when `spans`), then -- when it holds a whole record -- the stats of its
+// records [0, nrec) in b.stats.  Waits once, for the cut.  Not last and no whole record: nrec = 0, nothing queried.
+static int query_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint64_t len, bool last, uint64_t lower,
+                       uint64_t upper, bool spans, hipStream_t st, uint64_t &cut, uint64_t &nrec, bool &open) {
+    cut = nrec = 0; open = false;
+    if (len == 0) return TSX_HIP_OK;
+    TSX_TRY(piece_scan(m, d_text, len, last, b.info.get(), spans ? &b.span : nullptr, st));
+    const unsigned long long *h_info = b.h_info.get();
+    HIP_TRY(hipMemcpyAsync(b.h_info.get(), b.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    cut = h_info[0]; nrec = h_info[1]; open = h_info[2] != 0;
+    if (nrec == 0) return TSX_HIP_OK;
+    return query_records(m, b, d_text, cut, nrec, lower, upper, st);
+}
+
+// The scan of nrec + 1 kept lengths in place (koff has room for the chunk sums behind them; the total goes to *total) and
+// the output they describe: the spans of d_text[0, cut) through filter_copy_kernel into out (out_have bytes >= cut + 64).
+static int filter_compact(tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, const unsigned long long *span,
+                          unsigned long long *koff, uint64_t nrec, unsigned long long *total, uint8_t *out, uint64_t out_have,
+                          hipStream_t st) {
+    const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    unsigned long long *chunk = koff + nk;
+    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)koff,
+                       nk, chunk);
+    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, total);
+    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, koff, nk,
+                       (const unsigned long long *)chunk);
+    // (the copy grid covers the worst case; lanes past the total fall through)
+    hipLaunchKernelGGL(filter_copy_kernel, dim3(grid_for(m, (cut + 16) / 16 + 64, 8)), dim3(NT), 0, st, d_text, cut,
+                       span, (const unsigned long long *)koff, nrec, out, out_have);
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
@@ -3959,17 +3996,7 @@ static int filter_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uin
     hipLaunchKernelGGL(filter_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, (const unsigned long long *)b.stats.get(),
                        span, nrec, rule.min_in_range, (uint64_t)rule.fraction_ppm, rule.invert,
                        open ? 1 : 0, koff, info + 5);
-    unsigned long long *chunk = koff + nk;
-    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)koff,
-                       nk, chunk);
-    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, info + 3);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, koff, nk,
-                       (const unsigned long long *)chunk);
-    // (the copy grid covers the worst case; lanes past the total fall through)
-    hipLaunchKernelGGL(filter_copy_kernel, dim3(grid_for(m, (cut + 16) / 16 + 64, 8)), dim3(NT), 0, st, d_text, cut,
-                       span, (const unsigned long long *)koff, nrec, b.out, (uint64_t)b.out_have);
-    HIP_TRY(hipGetLastError());
-    return TSX_HIP_OK;
+    return filter_compact(m, d_text, cut, span, koff, nrec, info + 3, b.out, (uint64_t)b.out_have, st);
 }
 
 static bool rule_ok(const tsx_hip_filter_rule *r) {
@@ -4190,6 +4217,7 @@ extern "C" int tsx_hip_trim_spans_device(tsx_hip_map *m, const void *dev_text, s
 struct TrimBufs {
     DevBuf<uint8_t> text;
     DevBuf<unsigned long long> bits, lo, span, seg, src;
+    DevBuf<unsigned long long> rspan;              // record spans (the pair calls cut by them)
     DevBuf<uint8_t> own_out;                       // the output, unless the caller gave a buffer:
     uint8_t *out = nullptr; size_t out_have = 0;   // where it goes, and the room there
     DevBuf<unsigned long long> info;               // cut, records, open, total, line base (0), kept, bases in, bases kept
@@ -4207,30 +4235,14 @@ struct TrimBufs {
     }
 };
 
-// One piece [0, len) of text in device memory that starts at a record boundary: the line pass and the record scan (waits
-// once, for the cut and the record count), then over its whole records [0, cut): bitmap, line offsets, runs, and either
-// the spans alone (b.span, finalized) or -- `copy` -- the segment lengths, their scan (total -> b.info[3], totals ->
-// b.info[5..7]) and the output in b.out (own_out grown to cut + 64, or the caller's buffer, never grown).  What follows
-// the wait is queued, not waited for.  Not last and no whole record: nrec = 0, nothing done.
-static int trim_piece(tsx_hip_map *m, TrimBufs &b, const uint8_t *d_text, uint64_t len, bool last,
-                      const tsx_hip_trim_rule &rule, bool copy, hipStream_t st, uint64_t &cut, uint64_t &nrec) {
-    cut = nrec = 0;
-    if (len == 0) return TSX_HIP_OK;
+// The records [0, nrec) of d_text[0, cut), after a line pass over a text that starts with [0, cut): bitmap, line offsets
+// and runs (b.span holds the packed runs).  `last`: [0, cut) ends the text, and d_carry holds its line ends (an
+// unterminated last line).  Queued, not waited for.
+static int trim_records(tsx_hip_map *m, TrimBufs &b, const uint8_t *d_text, uint64_t cut, uint64_t nrec, bool last,
+                        const tsx_hip_trim_rule &rule, hipStream_t st) {
     const uint32_t lpr = m->p.line_mask + 1, lshift = lpr == 4 ? 2u : 1u;
-    uint64_t ntiles = (len + TILE - 1) / TILE;
+    const uint64_t nwords = (cut + 63) / 64, ntiles = (cut + TILE - 1) / TILE;
     int rc;
-    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-    if ((rc = query_line_pass(m, d_text, len, len, 0, st)) != TSX_HIP_OK) return rc;
-    hipLaunchKernelGGL(record_scan_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
-                       d_text, len, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), lpr, last ? 1 : 0,
-                       b.info.get(), (unsigned long long *)nullptr, (uint64_t)0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b.h_info.get(), b.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    cut = b.h_info.get()[0]; nrec = b.h_info.get()[1];
-    if (nrec == 0) return TSX_HIP_OK;
-    const uint64_t nwords = (cut + 63) / 64;
-    ntiles = (cut + TILE - 1) / TILE;
     TSX_TRY(grow(st, b.bits, (nwords + 1) * 8));
     TSX_TRY(grow(st, b.lo, nrec * TL_N * 8));
     TSX_TRY(grow(st, b.span, nrec * sizeof(tsx_hip_trim_span)));
@@ -4250,34 +4262,70 @@ static int trim_piece(tsx_hip_map *m, TrimBufs &b, const uint8_t *d_text, uint64
     hipLaunchKernelGGL(trim_run_kernel, dim3(grid_for(m, nwords, 8)), dim3(NT), 0, st, (const unsigned long long *)b.bits.get(),
                        nwords, (const unsigned long long *)b.lo.get(), (const unsigned long long *)nullptr, nrec, nrec,
                        (uint32_t)m->p.k, (int)rule.mode, b.span.get());
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// Behind trim_records: the four segment lengths of every record in b.seg (4 nrec + 1 entries, the last 0, room for the
+// scan behind them), their sources in b.src, tot[0..2] += records written, bases in, bases kept.
+static int trim_lens(tsx_hip_map *m, TrimBufs &b, uint64_t nrec, const tsx_hip_trim_rule &rule, unsigned long long *tot,
+                     hipStream_t st) {
+    const uint32_t lpr = m->p.line_mask + 1;
+    const uint64_t nseg = nrec * 4, nk = nseg + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    TSX_TRY(grow(st, b.seg, (nk + nchunks + 16) * sizeof(unsigned long long)));
+    TSX_TRY(grow(st, b.src, nseg * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(b.seg.get() + nseg, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(trim_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.span.get(),
+                       (const unsigned long long *)b.lo.get(), nrec, lpr, rule.min_len ? rule.min_len : (uint64_t)m->p.k, b.seg.get(),
+                       b.src.get(), tot);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// The scan of nseg + 1 segment lengths in place (seg has room for the chunk sums behind them; the total goes to *total)
+// and the output they describe: d_text[0, cut) through trim_copy_kernel into out (out_have bytes >= cut + 64).
+static int trim_compact(tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, unsigned long long *seg, const unsigned long long *src,
+                        uint64_t nseg, unsigned long long *total, uint8_t *out, uint64_t out_have, hipStream_t st) {
+    const uint64_t nk = nseg + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    unsigned long long *chunk = seg + nk;
+    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)seg, nk,
+                       chunk);
+    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, total);
+    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, seg, nk, (const unsigned long long *)chunk);
+    // (the copy grid covers the worst case; lanes past the total fall through)
+    hipLaunchKernelGGL(trim_copy_kernel, dim3(grid_for(m, (cut + 16) / 16 + 64, 8)), dim3(NT), 0, st, d_text, cut,
+                       src, (const unsigned long long *)seg, nseg, out, out_have);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// One piece [0, len) of text in device memory that starts at a record boundary: the line pass and the record scan (waits
+// once, for the cut and the record count), then over its whole records [0, cut): bitmap, line offsets, runs, and either
+// the spans alone (b.span, finalized) or -- `copy` -- the segment lengths, their scan (total -> b.info[3], totals ->
+// b.info[5..7]) and the output in b.out (own_out grown to cut + 64, or the caller's buffer, never grown).  What follows
+// the wait is queued, not waited for.  Not last and no whole record: nrec = 0, nothing done.
+static int trim_piece(tsx_hip_map *m, TrimBufs &b, const uint8_t *d_text, uint64_t len, bool last,
+                      const tsx_hip_trim_rule &rule, bool copy, hipStream_t st, uint64_t &cut, uint64_t &nrec) {
+    cut = nrec = 0;
+    if (len == 0) return TSX_HIP_OK;
+    TSX_TRY(piece_scan(m, d_text, len, last, b.info.get(), nullptr, st));
+    HIP_TRY(hipMemcpyAsync(b.h_info.get(), b.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    cut = b.h_info.get()[0]; nrec = b.h_info.get()[1];
+    if (nrec == 0) return TSX_HIP_OK;
+    TSX_TRY(trim_records(m, b, d_text, cut, nrec, last, rule, st));
     if (!copy) {
         hipLaunchKernelGGL(trim_finalize_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.span.get(), nrec,
                            (const unsigned long long *)nullptr, nrec);
         HIP_TRY(hipGetLastError());
         return TSX_HIP_OK;
     }
-    const uint64_t nseg = nrec * 4, nk = nseg + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    TSX_TRY(grow(st, b.seg, (nk + nchunks + 16) * sizeof(unsigned long long)));
-    TSX_TRY(grow(st, b.src, nseg * sizeof(unsigned long long)));
+    TSX_TRY(trim_lens(m, b, nrec, rule, b.info.get() + 5, st));
     if (cut + 64 > b.out_have) {   // (as grow() finds it: a caller's buffer has the room, tsx_hip_trim_reads_device checks)
         TSX_TRY(grow(st, b.own_out, cut + 64));
         b.out = b.own_out.get(); b.out_have = b.own_out.cap();
     }
-    unsigned long long *const seg = b.seg.get(), *const info = b.info.get();
-    HIP_TRY(hipMemsetAsync(seg + nseg, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(trim_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.span.get(),
-                       (const unsigned long long *)b.lo.get(), nrec, lpr, rule.min_len ? rule.min_len : (uint64_t)m->p.k, seg,
-                       b.src.get(), info + 5);
-    unsigned long long *chunk = seg + nk;
-    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)seg, nk,
-                       chunk);
-    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, info + 3);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, seg, nk, (const unsigned long long *)chunk);
-    // (the copy grid covers the worst case; lanes past the total fall through)
-    hipLaunchKernelGGL(trim_copy_kernel, dim3(grid_for(m, (cut + 16) / 16 + 64, 8)), dim3(NT), 0, st, d_text, cut,
-                       (const unsigned long long *)b.src.get(), (const unsigned long long *)seg, nseg, b.out, (uint64_t)b.out_have);
-    HIP_TRY(hipGetLastError());
-    return TSX_HIP_OK;
+    return trim_compact(m, d_text, cut, b.seg.get(), b.src.get(), nrec * 4, b.info.get() + 3, b.out, (uint64_t)b.out_have, st);
 }
 
 // The host entry points, as query_host: the text in pieces cut at record boundaries; a piece without a whole record
@@ -4397,4 +4445,264 @@ extern "C" int tsx_hip_trim_reads_device(tsx_hip_map *m, const void *dev_text, s
     }
     if (totals) *totals = t;
     return rc;
+}
+
+// ---- paired reads: the filter and the trim over mate pairs (tsx_pairs.h) -----------------------------------------
+// One input text of a pair call: where the next piece starts, the piece on the device, and the scratch of the single-end
+// path that works on it (q for the filter, t for the trim; only one of them is initialised).
+struct PairSide {
+    QueryBufs q;
+    TrimBufs t;
+    const char *text = nullptr;
+    size_t n = 0, off = 0, len = 0;
+    bool last = false;
+    explicit PairSide(hipStream_t st) : q(st), t(st) {}
+};
+// One output of a pair call: the gated lengths (scanned in place), the compacted bytes and their pinned copy.
+struct PairOut {
+    DevBuf<unsigned long long> off;
+    DevBuf<uint8_t> out;
+    PinBuf<uint8_t> h_out;
+    int fd = -1;
+    bool used = false;      // the gate writes its lengths
+    uint64_t pending = 0, bytes = 0;
+};
+
+static int pair_fail(const std::string &what) {
+    g_last_error = what;
+    return TSX_HIP_EPAIR;
+}
+
+// Both pair calls (trule: the trim, else frule: the filter).  Outputs: 0 kept mates 1, 1 kept mates 2, 2 orphans of A,
+// 3 orphans of B; an interleaved text (text2 == NULL) uses 0 and 2 for both mates.  Every round: a piece of each text,
+// both scans, pair_cut_kernel and ONE wait for the record count R and the cuts; then records [0, R) of each piece through
+// the single-end kernels, the gate, one compaction per output.  The outputs of round i are written while the device
+// works on round i + 1.
+static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *text2, size_t n2, const tsx_hip_filter_rule *frule,
+                      const tsx_hip_trim_rule *trule, int any, int check_names, const tsx_hip_pair_io &io, size_t chunk_bytes,
+                      tsx_hip_pair_totals *totals) {
+    const bool trim = trule != nullptr, inter = text2 == nullptr;
+    const int ns = inter ? 1 : 2;
+    if (!chunk_bytes) chunk_bytes = QUERY_CHUNK_DEFAULT;
+    chunk_bytes = std::min(chunk_bytes, QUERY_PIECE_MAX);
+    HIP_TRY(hipSetDevice(m->device));
+    join_foreign(m, false);
+    hipStream_t st = m->stream.get();
+    int rc = base_rule_ok(m);
+    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    // (the sides are declared last: their destructors wait for the stream before anything here is released)
+    PairOut out[4];
+    DevBuf<unsigned long long> pinfo;
+    PinBuf<unsigned long long> h_pinfo;
+    Event ev;
+    PairSide side[2] = {PairSide(st), PairSide(st)};
+    side[0].text = text1; side[0].n = n1;
+    side[1].text = text2; side[1].n = inter ? 0 : n2;
+    out[0].fd = io.fd1; out[1].fd = io.fd2; out[2].fd = io.fd_single1; out[3].fd = io.fd_single2;
+    out[0].used = out[2].used = true;
+    out[1].used = out[3].used = !inter;
+    for (int i = 0; i < ns; ++i) TSX_TRY(trim ? side[i].t.init() : side[i].q.init());
+    TSX_TRY(pinfo.alloc(PI_N * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(pinfo.get(), 0, PI_N * sizeof(unsigned long long), st));
+    TSX_TRY(h_pinfo.alloc(PI_N * sizeof(unsigned long long)));
+    TSX_TRY(ev.create());
+    const unsigned long long *h = h_pinfo.get();
+    unsigned long long *const pi = pinfo.get();
+    auto textbuf = [&](PairSide &s) -> DevBuf<uint8_t> & { return trim ? s.t.text : s.q.text; };
+    auto infoof = [&](PairSide &s) { return trim ? s.t.info.get() : s.q.info.get(); };
+    auto spanof = [&](PairSide &s) -> DevBuf<unsigned long long> & { return trim ? s.t.rspan : s.q.span; };
+    // the piece [off, off + len) of a side to the device, and its scan (an empty piece: no records)
+    auto scan = [&](PairSide &s) -> int {
+        s.last = s.off + s.len == s.n;
+        if (s.len == 0) {
+            HIP_TRY(hipMemsetAsync(infoof(s), 0, 3 * sizeof(unsigned long long), st));
+            return TSX_HIP_OK;
+        }
+        TSX_TRY(grow(st, textbuf(s), s.len + 256));
+        HIP_TRY(hipMemcpyAsync(textbuf(s).get(), s.text + s.off, s.len, hipMemcpyHostToDevice, st));
+        return piece_scan(m, textbuf(s).get(), s.len, s.last, infoof(s), &spanof(s), st);
+    };
+    auto longer = [&](PairSide &s) -> int {   // a piece without a whole record (interleaved: a whole pair) grows
+        if (s.len >= QUERY_PIECE_MAX) { g_last_error = "a record longer than 3.75 GiB"; return TSX_HIP_EINVAL; }
+        s.len = std::min(std::min(2 * s.len, s.n - s.off), QUERY_PIECE_MAX);
+        return scan(s);
+    };
+    auto flush = [&]() -> int {   // the outputs of the round before, to their files
+        for (PairOut &o : out) {
+            if (o.fd < 0 || !o.pending) continue;
+            TSX_TRY(write_all(o.fd, o.h_out.get(), o.pending));
+            o.bytes += o.pending;
+            o.pending = 0;
+        }
+        return TSX_HIP_OK;
+    };
+    tsx_hip_pair_totals t;
+    memset(&t, 0, sizeof t);
+    bool have_pending = false;
+    while (rc == TSX_HIP_OK) {
+        bool rest = false;
+        for (int i = 0; i < ns; ++i) rest |= side[i].off < side[i].n;
+        if (!rest) break;
+        for (int i = 0; i < ns && rc == TSX_HIP_OK; ++i) {
+            side[i].len = std::min(chunk_bytes, side[i].n - side[i].off);
+            rc = scan(side[i]);
+        }
+        if (rc != TSX_HIP_OK) break;
+        for (;;) {
+            hipLaunchKernelGGL(pair_cut_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)infoof(side[0]),
+                               (const unsigned long long *)spanof(side[0]).get(),
+                               inter ? (const unsigned long long *)nullptr : (const unsigned long long *)infoof(side[1]),
+                               inter ? (const unsigned long long *)nullptr : (const unsigned long long *)spanof(side[1]).get(),
+                               side[0].last ? 1 : 0, pi);
+            if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_pinfo.get(), pi, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            bool again = false;
+            if (inter) {
+                if (h[PI_R] == 0 && !side[0].last) { rc = longer(side[0]); again = true; }
+            } else {
+                if (h[PI_RA] == 0 && !side[0].last) { rc = longer(side[0]); again = true; }
+                if (rc == TSX_HIP_OK && h[PI_RB] == 0 && !side[1].last) { rc = longer(side[1]); again = true; }
+            }
+            if (rc != TSX_HIP_OK || !again) break;
+        }
+        if (rc != TSX_HIP_OK) break;
+        const uint64_t R = h[PI_R], RA = h[PI_RA], RB = h[PI_RB];
+        const uint64_t cut[2] = {h[PI_CUT_A], h[PI_CUT_B]};
+        const bool open[2] = {h[PI_OPEN_A] != 0, h[PI_OPEN_B] != 0};
+        if (inter) {
+            if (side[0].last && (RA & 1)) {
+                rc = pair_fail("an interleaved text with an odd number of records (" + std::to_string(2 * t.pairs + RA) + ")");
+                break;
+            }
+            if (R == 0) break;   // (nothing but empty lines)
+        } else {
+            if (RA == 0 && RB == 0) break;   // (nothing but empty lines in either)
+            if (R == 0) {
+                rc = pair_fail(std::string("text ") + (RA ? "2" : "1") + " ends after " + std::to_string(t.pairs) +
+                               " records, text " + (RA ? "1" : "2") + " holds more");
+                break;
+            }
+        }
+        const uint64_t npairs = inter ? R / 2 : R;
+        const uint32_t stride = inter ? 2u : 1u, per = trim ? 4u : 1u;   // entries of a length array per record
+        // records [0, R) of each piece (the line pass again: the tile counts are the map's, and the other text's by now)
+        for (int i = 0; i < ns && rc == TSX_HIP_OK; ++i) {
+            PairSide &s = side[i];
+            const uint8_t *d_text = textbuf(s).get();
+            if (hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            if ((rc = query_line_pass(m, d_text, cut[i], cut[i], 0, st)) != TSX_HIP_OK) break;
+            if (trim) {
+                rc = trim_records(m, s.t, d_text, cut[i], R, s.last && cut[i] == s.len, *trule, st);
+                if (rc == TSX_HIP_OK) rc = trim_lens(m, s.t, R, *trule, pi + (i ? PI_TRIM_B : PI_TRIM_A), st);
+            } else {
+                rc = query_records(m, s.q, d_text, cut[i], R, frule->lower, frule->upper, st);
+            }
+        }
+        if (rc != TSX_HIP_OK) break;
+        const uint64_t ne = R * per, nk = ne + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+        for (PairOut &o : out) {
+            if (!o.used) continue;
+            if ((rc = grow(st, o.off, (nk + nchunks + 16) * sizeof(unsigned long long))) != TSX_HIP_OK) break;
+            if (hipMemsetAsync(o.off.get() + ne, 0, sizeof(unsigned long long), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        }
+        if (rc != TSX_HIP_OK) break;
+        PairSide &sb = side[inter ? 0 : 1];   // where mate 2 lives
+        unsigned long long *const keep_a = out[0].off.get(), *const single_a = out[2].off.get();
+        unsigned long long *const keep_b = inter ? keep_a + per : out[1].off.get();
+        unsigned long long *const single_b = inter ? single_a + per : out[3].off.get();
+        const unsigned long long *span_a = spanof(side[0]).get(), *span_b = inter ? span_a + 2 : spanof(side[1]).get();
+        if (check_names)
+            hipLaunchKernelGGL(pair_names_kernel, dim3(grid_for(m, npairs, 8)), dim3(NT), 0, st, (const uint8_t *)textbuf(side[0]).get(),
+                               span_a, (const uint8_t *)textbuf(sb).get(), span_b, npairs, stride, pi + PI_BAD);
+        if (trim) {
+            const unsigned long long *seg_a = side[0].t.seg.get(), *seg_b = inter ? seg_a + 4 : side[1].t.seg.get();
+            hipLaunchKernelGGL(pair_gate_trim_kernel, dim3(grid_for(m, npairs, 8)), dim3(NT), 0, st, seg_a, seg_b, npairs, stride,
+                               keep_a, keep_b, single_a, single_b, pi + PI_KEPT);
+        } else {
+            const unsigned long long *st_a = side[0].q.stats.get(), *st_b = inter ? st_a + QS_N : side[1].q.stats.get();
+            hipLaunchKernelGGL(pair_gate_filter_kernel, dim3(grid_for(m, npairs, 8)), dim3(NT), 0, st, st_a, span_a, st_b, span_b,
+                               npairs, stride, frule->min_in_range, (uint64_t)frule->fraction_ppm, frule->invert, any,
+                               (!inter && open[0]) ? 1 : 0, (inter ? open[0] : open[1]) ? 1 : 0, keep_a, keep_b, single_a, single_b,
+                               pi + PI_KEPT);
+        }
+        if (hipGetLastError() != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        for (int oi = 0; oi < 4 && rc == TSX_HIP_OK; ++oi) {
+            PairOut &o = out[oi];
+            if (!o.used || o.fd < 0) continue;
+            const int si = inter ? 0 : (oi & 1);
+            PairSide &s = side[si];
+            if ((rc = grow(st, o.out, cut[si] + 64)) != TSX_HIP_OK) break;
+            if (trim)
+                rc = trim_compact(m, textbuf(s).get(), cut[si], o.off.get(), s.t.src.get(), ne, pi + PI_TOTAL + oi, o.out.get(),
+                                  (uint64_t)o.out.cap(), st);
+            else
+                rc = filter_compact(m, textbuf(s).get(), cut[si], spanof(s).get(), o.off.get(), ne, pi + PI_TOTAL + oi, o.out.get(),
+                                    (uint64_t)o.out.cap(), st);
+        }
+        if (rc != TSX_HIP_OK) break;
+        if (hipMemcpyAsync(h_pinfo.get(), pi, PI_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipEventRecord(ev.get(), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        if (have_pending) {   // the previous round's outputs, while the device works on this one
+            have_pending = false;
+            if ((rc = flush()) != TSX_HIP_OK) break;
+        }
+        if (hipEventSynchronize(ev.get()) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+        if (h[PI_BAD]) {
+            rc = pair_fail("pair " + std::to_string(t.pairs + (uint64_t)~h[PI_BAD]) + ": the names of the mates differ");
+            break;
+        }
+        for (int oi = 0; oi < 4 && rc == TSX_HIP_OK; ++oi) {
+            PairOut &o = out[oi];
+            if (!o.used || o.fd < 0) continue;
+            const uint64_t total = h[PI_TOTAL + oi];
+            if (total > cut[inter ? 0 : (oi & 1)] + 1) { g_last_error = "pair output larger than its piece"; rc = TSX_HIP_EHIP; break; }
+            // (no wait: the copy that last filled it has been waited for, and written out above)
+            if (o.h_out.reserve(nullptr, total, total + total / 8 + 4096) != TSX_HIP_OK) { rc = TSX_HIP_ENOMEM; break; }
+            if (total && hipMemcpyAsync(o.h_out.get(), o.out.get(), total, hipMemcpyDeviceToHost, st) != hipSuccess) rc = TSX_HIP_EHIP;
+            o.pending = total;
+        }
+        // (the counters are per round)
+        if (rc == TSX_HIP_OK && (hipMemsetAsync(pi + PI_KEPT, 0, (PI_N - PI_KEPT) * sizeof(unsigned long long), st) != hipSuccess ||
+                                 hipStreamSynchronize(st) != hipSuccess))
+            rc = TSX_HIP_EHIP;
+        if (rc != TSX_HIP_OK) break;
+        have_pending = true;
+        t.pairs += npairs; t.kept += h[PI_KEPT]; t.single1 += h[PI_SINGLE_A]; t.single2 += h[PI_SINGLE_B];
+        t.bases_in += h[PI_TRIM_A + 1] + h[PI_TRIM_B + 1];
+        t.bases_kept += h[PI_TRIM_A + 2] + h[PI_TRIM_B + 2];
+        for (int i = 0; i < ns; ++i) side[i].off += cut[i];
+    }
+    // (after TSX_HIP_EPAIR too: whole pairs of the pieces before the one that failed)
+    if (have_pending && (rc == TSX_HIP_OK || rc == TSX_HIP_EPAIR)) {
+        const std::string why = g_last_error;
+        const int wrc = flush();
+        if (wrc != TSX_HIP_OK) rc = wrc; else g_last_error = why;
+    }
+    t.bytes1 = out[0].bytes; t.bytes2 = out[1].bytes; t.bytes_single1 = out[2].bytes; t.bytes_single2 = out[3].bytes;
+    if (totals) *totals = t;
+    return rc;
+}
+
+static bool pair_io_ok(const tsx_hip_pair_io *io, bool inter) {
+    if (!io || io->fd1 < 0) return false;
+    return inter ? (io->fd2 == -1 && io->fd_single2 == -1) : io->fd2 >= 0;
+}
+
+extern "C" int tsx_hip_filter_pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *text2, size_t n2,
+                                         const tsx_hip_filter_rule *rule, int pair_mode, int check_names, const tsx_hip_pair_io *io,
+                                         size_t chunk_bytes, tsx_hip_pair_totals *totals) {
+    if (totals) memset(totals, 0, sizeof *totals);
+    if (!rule_ok(rule) || !query_args_ok(m, rule->lower, rule->upper) || (!text1 && n1) || (!text2 && n2) ||
+        (pair_mode != TSX_HIP_PAIR_BOTH && pair_mode != TSX_HIP_PAIR_ANY) || !pair_io_ok(io, text2 == nullptr))
+        return TSX_HIP_EINVAL;
+    return pairs_host(m, text1, n1, text2, n2, rule, nullptr, pair_mode == TSX_HIP_PAIR_ANY ? 1 : 0, check_names, *io, chunk_bytes, totals);
+}
+
+extern "C" int tsx_hip_trim_pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *text2, size_t n2,
+                                       const tsx_hip_trim_rule *rule, int check_names, const tsx_hip_pair_io *io, size_t chunk_bytes,
+                                       tsx_hip_pair_totals *totals) {
+    if (totals) memset(totals, 0, sizeof *totals);
+    if (!trim_rule_ok(m, rule) || (!text1 && n1) || (!text2 && n2) || !pair_io_ok(io, text2 == nullptr)) return TSX_HIP_EINVAL;
+    return pairs_host(m, text1, n1, text2, n2, nullptr, rule, 0, check_names, *io, chunk_bytes, totals);
 }

@@ -103,6 +103,45 @@ static tsx_hip_trim_totals tsx_trim_reads(tsx_hip_map *pMap, const char *pText, 
     fnCheck(rc);
     return oTotals;
 }
+// The filter and the trim over mate pairs (tsx_hip_filter_pairs_host / tsx_hip_trim_pairs_host).  pText2 == nullptr: one
+// interleaved text.  Paths: kept mates 1, kept mates 2, orphans of text 1, orphans of text 2 -- created / truncated; an
+// empty path is no output (-1: allowed for the orphans, and for everything of text 2 with an interleaved text).
+// fnCall(io, totals) makes the call.
+template <typename F, typename C>
+static tsx_hip_pair_totals tsx_pairs_files(const std::string (&sPaths)[4], F fnCall, C fnCheck) {
+    int fds[4] = {-1, -1, -1, -1};
+    for (int i = 0; i < 4; ++i) {
+        if (sPaths[i].empty()) continue;
+        fds[i] = open(sPaths[i].c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fds[i] < 0) {
+            for (int j = 0; j < i; ++j) if (fds[j] >= 0) close(fds[j]);
+            throw TSXException("could not open " + sPaths[i] + " for writing", TSX_HIP_EIO);
+        }
+    }
+    const tsx_hip_pair_io io = {fds[0], fds[1], fds[2], fds[3]};
+    tsx_hip_pair_totals oTotals = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    int rc = fnCall(&io, &oTotals);
+    for (int i = 0; i < 4; ++i)
+        if (fds[i] >= 0 && close(fds[i]) != 0 && rc == TSX_HIP_OK) rc = TSX_HIP_EIO;
+    fnCheck(rc);
+    return oTotals;
+}
+template <typename C>
+static tsx_hip_pair_totals tsx_filter_pairs(tsx_hip_map *pMap, const char *pText1, size_t iBytes1, const char *pText2, size_t iBytes2,
+                                            const tsx_hip_filter_rule &oRule, int iPairMode, bool bCheckNames,
+                                            const std::string (&sPaths)[4], size_t iChunkBytes, C fnCheck) {
+    return tsx_pairs_files(sPaths, [&](const tsx_hip_pair_io *io, tsx_hip_pair_totals *t) {
+        return tsx_hip_filter_pairs_host(pMap, pText1, iBytes1, pText2, iBytes2, &oRule, iPairMode, bCheckNames ? 1 : 0, io, iChunkBytes, t);
+    }, fnCheck);
+}
+template <typename C>
+static tsx_hip_pair_totals tsx_trim_pairs(tsx_hip_map *pMap, const char *pText1, size_t iBytes1, const char *pText2, size_t iBytes2,
+                                          const tsx_hip_trim_rule &oRule, bool bCheckNames, const std::string (&sPaths)[4],
+                                          size_t iChunkBytes, C fnCheck) {
+    return tsx_pairs_files(sPaths, [&](const tsx_hip_pair_io *io, tsx_hip_pair_totals *t) {
+        return tsx_hip_trim_pairs_host(pMap, pText1, iBytes1, pText2, iBytes2, &oRule, bCheckNames ? 1 : 0, io, iChunkBytes, t);
+    }, fnCheck);
+}
 
 class TSXHashMapHIP {
 public:
@@ -236,6 +275,17 @@ public:
                                   size_t iChunkBytes = 0) {
         return tsx_trim_reads(m_pMap, pText, iBytes, oRule, sPath, iChunkBytes, check);
     }
+    // the filter / the trim over mate pairs (pText2 == nullptr: interleaved); sPaths as tsx_pairs_files takes them
+    tsx_hip_pair_totals filterPairs(const char *pText1, size_t iBytes1, const char *pText2, size_t iBytes2,
+                                    const tsx_hip_filter_rule &oRule, const std::string (&sPaths)[4],
+                                    int iPairMode = TSX_HIP_PAIR_BOTH, bool bCheckNames = false, size_t iChunkBytes = 0) {
+        return tsx_filter_pairs(m_pMap, pText1, iBytes1, pText2, iBytes2, oRule, iPairMode, bCheckNames, sPaths, iChunkBytes, check);
+    }
+    tsx_hip_pair_totals trimPairs(const char *pText1, size_t iBytes1, const char *pText2, size_t iBytes2,
+                                  const tsx_hip_trim_rule &oRule, const std::string (&sPaths)[4], bool bCheckNames = false,
+                                  size_t iChunkBytes = 0) {
+        return tsx_trim_pairs(m_pMap, pText1, iBytes1, pText2, iBytes2, oRule, bCheckNames, sPaths, iChunkBytes, check);
+    }
 
     // set operation on two tables (tsx_hip_combine): this is A, oOther is B, the result goes into the empty table oOut
     tsx_hip_combine_stats combine(TSXHashMapHIP &oOther, TSXHashMapHIP &oOut, const tsx_hip_combine_rule &oRule) {
@@ -312,7 +362,7 @@ private:
         if (rc == TSX_HIP_OK) return;
         std::string msg = tsx_hip_strerror(rc);
         if (rc == TSX_HIP_EHIP || rc == TSX_HIP_ENODEVICE || rc == TSX_HIP_ENOMEM || rc == TSX_HIP_EIO ||
-            rc == TSX_HIP_EFORMAT) {
+            rc == TSX_HIP_EFORMAT || rc == TSX_HIP_EPAIR) {
             msg += " (";
             msg += tsx_hip_last_error();
             msg += ")";

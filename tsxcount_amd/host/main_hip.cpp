@@ -48,6 +48,10 @@ struct arguments {
     // read trimming after the count: --trim=OUT writes the records of --trim-input (default --input) cut to their solid
     // stretch, --trim-spans=FILE one line index<TAB>start<TAB>length per record
     std::string trim, trim_input, trim_spans, trim_mode = "longest";
+    // paired reads: two comma-separated files in --filter-input / --trim-input (and as many outputs), or one interleaved
+    // file; orphans go to --filter-singles / --trim-singles; --pair-names compares the mates' names
+    std::string filter_singles, trim_singles, filter_pairs = "both";
+    bool filter_interleaved = false, trim_interleaved = false, pair_names = false;
     uint64_t trim_lower = 2, trim_upper = UINT64_MAX, trim_min_len = 0;
     // k-mer databases: --save=DB after the count and the check, --load=DB[,DB2,...] before the count (summed)
     std::string save;
@@ -78,6 +82,9 @@ static int usage() {
                  "                [--filter-min=M] [--filter-fraction=F] [--filter-invert] [--save=DB] [--load=DB[,DB2,...]]\n"
                  "                [--trim=OUT] [--trim-spans=FILE] [--trim-input=FILE] [--trim-lower=N] [--trim-upper=N]\n"
                  "                [--trim-mode=longest|prefix] [--trim-min-len=N]\n"
+                 "                [--filter-input=R1,R2 --filter=O1,O2] [--filter-singles=S1,S2] [--filter-pairs=both|any]\n"
+                 "                [--filter-interleaved] [--trim-input=R1,R2 --trim=O1,O2] [--trim-singles=S1,S2]\n"
+                 "                [--trim-interleaved] [--pair-names]\n"
                  "                [--with=DB[,DB2,...] [--op=intersect|union|subtract|diff] [--op-count=min|max|sum|left|right]\n"
                  "                 [--a-lower=N] [--a-upper=N] [--b-lower=N] [--b-upper=N] [--compare]]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
@@ -102,6 +109,15 @@ static int usage() {
                  "when its count lies in trim-lower..trim-upper (default 2..unbounded); --trim-mode=longest keeps the longest run\n"
                  "of solid windows (the leftmost among equals), prefix the run that starts the read. Records that keep fewer\n"
                  "than trim-min-len bases (default k) are dropped. --trim-spans writes index<TAB>start<TAB>length per record.\n"
+                 "Paired reads stay in step: --filter-input=R1,R2 --filter=O1,O2 (or --filter-interleaved with one file each)\n"
+                 "takes record i of R1 and record i of R2 as one pair (interleaved: records 2i and 2i+1). --filter-pairs=both\n"
+                 "(default) keeps a pair when both mates pass, any when one does; under both a mate that passes alone goes to\n"
+                 "--filter-singles=S1,S2 (interleaved: S), or is dropped. --trim-input=R1,R2 --trim=O1,O2 [--trim-singles=S1,S2]\n"
+                 "and --trim-interleaved do the same for the trim: a pair is kept when both mates are written, a lone survivor is\n"
+                 "an orphan. --pair-names compares the mates' names (the header up to the first blank, without a trailing /1 or\n"
+                 "/2). Different record counts, an odd interleaved file or differing names stop the run. Prints\n"
+                 "pairs<TAB>seen<TAB>kept<TAB>single1<TAB>single2 (the trim adds <TAB>bases_in<TAB>bases_kept). Each file goes by its\n"
+                 "own name (plain, .gz, BGZF); no --read-stats / --trim-spans, no wrapped FASTA, one GPU.\n"
                  "Prints trim<TAB>records<TAB>kept<TAB>bases_in<TAB>bases_kept. One GPU only; --trim-input goes by its own file\n"
                  "name and is never wrapped FASTA.\n"
                  "--save writes the table as a k-mer database after the count and the check. --load fills the table from\n"
@@ -214,6 +230,120 @@ static bool is_fasta_path(const std::string &path, const std::string &format) {
     b.input_path = path;
     b.format = format;
     return is_fasta(b);
+}
+
+static std::vector<std::string> split_commas(const std::string &s) {
+    std::vector<std::string> out;
+    size_t at = 0;
+    for (;;) {
+        const size_t c = s.find(',', at);
+        out.push_back(s.substr(at, c == std::string::npos ? c : c - at));
+        if (c == std::string::npos) return out;
+        at = c + 1;
+    }
+}
+static bool filter_paired(const arguments &a) { return a.filter_interleaved || a.filter_input.find(',') != std::string::npos; }
+static bool trim_paired(const arguments &a) { return a.trim_interleaved || a.trim_input.find(',') != std::string::npos; }
+
+// One text of a paired run, loaded as the filter's input is (a BGZF file is inflated on the device).
+struct pair_text {
+    std::vector<char> owned;
+    const char *text = nullptr;
+    size_t n = 0;
+    void *map = nullptr;
+    ~pair_text() { if (map) munmap(map, n); }
+    template <typename C>
+    bool load(const std::string &path, int device, C check) {
+        bool bgzf = false;
+        if (!load_input(path, owned, text, n, map, bgzf, true)) {
+            std::cerr << "Could not read " << path << std::endl;
+            return false;
+        }
+        if (bgzf) {
+            size_t members = 0, tb = 0, got = 0;
+            check(tsx_hip_bgzf_index_host(text, n, &members, &tb));
+            std::vector<char> inflated(tb ? tb : 1);
+            check(tsx_hip_inflate_bgzf_host(device, text, n, inflated.data(), tb, &got));
+            munmap(map, n);
+            map = nullptr;
+            owned.swap(inflated);
+            owned.resize(got);
+            text = owned.data();
+            n = got;
+        }
+        return true;
+    }
+};
+
+// --filter / --trim over mate pairs: two files or one interleaved file, where the single-end forms run.
+static int run_pairs(tsx_hip_map *pMap, const arguments &a, bool trim) {
+    auto check = [](int rc) {
+        if (rc == TSX_HIP_OK) return;
+        std::string msg = tsx_hip_strerror(rc);
+        if (rc == TSX_HIP_EHIP || rc == TSX_HIP_EIO || rc == TSX_HIP_ENOMEM || rc == TSX_HIP_EPAIR)
+            msg += std::string(" (") + tsx_hip_last_error() + ")";
+        throw TSXException(msg, rc);
+    };
+    const std::vector<std::string> in = split_commas(trim ? a.trim_input : a.filter_input);
+    const std::vector<std::string> out = split_commas(trim ? a.trim : a.filter);
+    const std::string &singles = trim ? a.trim_singles : a.filter_singles;
+    const std::vector<std::string> sg = singles.empty() ? std::vector<std::string>() : split_commas(singles);
+    const bool inter = in.size() == 1;
+    pair_text t1, t2;
+    if (!t1.load(in[0], a.device, check) || (!inter && !t2.load(in[1], a.device, check))) return 3;
+    const bool fa = is_fasta_path(in[0], is_wrapped(a) ? std::string() : a.format);
+    if (!inter && fa != is_fasta_path(in[1], is_wrapped(a) ? std::string() : a.format)) {
+        std::cerr << "paired input: " << in[0] << " and " << in[1] << " differ in format" << std::endl;
+        return 3;
+    }
+    check(tsx_hip_set_record_lines(pMap, fa ? 2 : 4));
+    const std::string paths[4] = {out[0], inter ? std::string() : out[1], sg.empty() ? std::string() : sg[0],
+                                  sg.size() > 1 ? sg[1] : std::string()};
+    tsx_hip_pair_totals t;
+    if (trim) {
+        tsx_hip_trim_rule rule;
+        rule.lower = a.trim_lower;
+        rule.upper = a.trim_upper;
+        rule.min_len = a.trim_min_len;
+        rule.mode = a.trim_mode == "prefix" ? TSX_HIP_TRIM_PREFIX : TSX_HIP_TRIM_LONGEST;
+        rule.reserved = 0;
+        t = tsx_trim_pairs(pMap, t1.text, t1.n, inter ? nullptr : t2.text, t2.n, rule, a.pair_names, paths, 0, check);
+        std::cout << "pairs\t" << t.pairs << '\t' << t.kept << '\t' << t.single1 << '\t' << t.single2 << '\t' << t.bases_in << '\t'
+                  << t.bases_kept << std::endl;
+    } else {
+        tsx_hip_filter_rule rule;
+        rule.lower = a.filter_lower;
+        rule.upper = a.filter_upper;
+        rule.min_in_range = a.filter_min;
+        rule.fraction_ppm = (uint32_t)std::llround(a.filter_fraction * 1e6);
+        rule.invert = a.filter_invert ? 1 : 0;
+        t = tsx_filter_pairs(pMap, t1.text, t1.n, inter ? nullptr : t2.text, t2.n, rule,
+                             a.filter_pairs == "any" ? TSX_HIP_PAIR_ANY : TSX_HIP_PAIR_BOTH, a.pair_names, paths, 0, check);
+        std::cout << "pairs\t" << t.pairs << '\t' << t.kept << '\t' << t.single1 << '\t' << t.single2 << std::endl;
+    }
+    std::cerr << "Wrote " << t.kept << " of " << t.pairs << " pairs (" << t.bytes1 + t.bytes2 << " bytes), " << t.single1 << " + "
+              << t.single2 << " single mates" << std::endl;
+    return 0;
+}
+
+// What the paired forms of --filter (trim = false) and --trim refuse; an empty string when all is well.
+static std::string pairs_refusal(const arguments &a, bool trim) {
+    const std::string opt = trim ? "--trim" : "--filter";
+    const std::string &in = trim ? a.trim_input : a.filter_input, &out = trim ? a.trim : a.filter;
+    const std::string &singles = trim ? a.trim_singles : a.filter_singles;
+    const bool inter = trim ? a.trim_interleaved : a.filter_interleaved;
+    const size_t want = inter ? 1 : 2;
+    if (!(trim ? a.trim_spans : a.read_stats).empty())
+        return (trim ? std::string("--trim-spans") : std::string("--read-stats")) + " does not go with paired input";
+    if (in.empty()) return opt + "-interleaved needs " + opt + "-input=FILE";
+    if (out.empty()) return "paired input needs " + opt + "=" + (inter ? "OUT" : "O1,O2");
+    if (split_commas(in).size() != want || split_commas(out).size() != want || (!singles.empty() && split_commas(singles).size() != want))
+        return opt + "-input, " + opt + " and " + opt + "-singles must name " + (inter ? "one file each with " + opt + "-interleaved"
+                                                                                  : "two files each (R1,R2)");
+    for (const std::string &p : split_commas(in + "," + out + (singles.empty() ? "" : "," + singles)))
+        if (p.empty()) return "an empty file name in the paired " + opt + " options";
+    if (a.gpus > 1) return "paired " + opt + " runs on one GPU only";
+    return "";
 }
 
 static bool wants_queries(const arguments &a) { return !a.filter.empty() || !a.read_stats.empty(); }
@@ -332,8 +462,8 @@ static int run_trim(tsx_hip_map *pMap, const arguments &a) {
 
 // what follows the count, the check, the outputs and the set operation: the read queries, then the trim
 static int run_after(tsx_hip_map *pMap, const arguments &a) {
-    const int rq = wants_queries(a) ? run_read_queries(pMap, a) : 0;
-    const int rt = wants_trim(a) ? run_trim(pMap, a) : 0;
+    const int rq = !wants_queries(a) ? 0 : filter_paired(a) ? run_pairs(pMap, a, false) : run_read_queries(pMap, a);
+    const int rt = !wants_trim(a) ? 0 : trim_paired(a) ? run_pairs(pMap, a, true) : run_trim(pMap, a);
     return rq ? rq : rt;
 }
 
@@ -540,6 +670,12 @@ int main(int argc, char *argv[]) {
         else if (opt(argv[i], "trim-upper", v)) a.trim_upper = strtoull(v.c_str(), nullptr, 10);
         else if (opt(argv[i], "trim-mode", v)) a.trim_mode = v;
         else if (opt(argv[i], "trim-min-len", v)) a.trim_min_len = strtoull(v.c_str(), nullptr, 10);
+        else if (opt(argv[i], "filter-singles", v)) a.filter_singles = v;
+        else if (opt(argv[i], "trim-singles", v)) a.trim_singles = v;
+        else if (opt(argv[i], "filter-pairs", v)) a.filter_pairs = v;
+        else if (opt(argv[i], "filter-interleaved", v)) a.filter_interleaved = true;
+        else if (opt(argv[i], "trim-interleaved", v)) a.trim_interleaved = true;
+        else if (opt(argv[i], "pair-names", v)) a.pair_names = true;
         else if (opt(argv[i], "read-stats", v)) { a.read_stats = v; if (v.empty()) return usage(); }
         else if (opt(argv[i], "devices", v)) {
             for (size_t at = 0; at < v.size();) {
@@ -675,6 +811,21 @@ int main(int argc, char *argv[]) {
             return usage();
         }
         a.group = false;   // --gpus=1: the one table of this process
+    }
+    if (a.filter_pairs != "both" && a.filter_pairs != "any") return usage();
+    for (int trim = 0; trim < 2; ++trim) {
+        const bool paired = trim ? trim_paired(a) : filter_paired(a);
+        const std::string &singles = trim ? a.trim_singles : a.filter_singles;
+        std::string why;
+        if (paired) why = pairs_refusal(a, trim != 0);
+        else if (!singles.empty()) why = std::string(trim ? "--trim-singles" : "--filter-singles") + " needs paired input (R1,R2 or the interleaved form)";
+        if (why.empty() && paired && is_wrapped(a))
+            for (const std::string &p : split_commas(trim ? a.trim_input : a.filter_input))
+                if (p == a.input_path) why = "paired input does not read wrapped FASTA: " + p;
+        if (!why.empty()) {
+            std::cerr << why << std::endl;
+            return usage();
+        }
     }
     if (a.gpus < 1 || (a.comm != "rccl" && a.comm != "copy") || (!a.devices.empty() && (int)a.devices.size() != a.gpus)) return usage();
     if (a.filter_lower > a.filter_upper || !(a.filter_fraction >= 0.0 && a.filter_fraction <= 1.0)) return usage();
