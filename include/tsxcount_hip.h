@@ -470,6 +470,53 @@ int tsx_hip_trim_reads_host(tsx_hip_map *m, const char *text, size_t n, const ts
                             size_t chunk_bytes, tsx_hip_trim_totals *totals);
 
 /*
+ * Read medians (csrc/tsx_median.h; no reference counterpart -- khmer `count-median` / `normalize-by-median`, KAT `sect`,
+ * `jellyfish query -s`): the count of every window of a text, and per record the median of them.  Records, lines,
+ * k-mers and c(x) are those of tsx_hip_query_reads_*; the table's base rule (tsx_hip_set_base_rule) decides which
+ * windows are k-mers, exactly as for tsx_hip_trim_*.  On a canonical table either strand finds the pair's count.
+ * PROFILE: one uint32_t per byte of the text.  Entry i is min(c(x), 0xFFFFFFFE) when a window that is a k-mer (on a
+ *   sequence line, under the base rule) starts at byte i, and TSX_HIP_NO_KMER otherwise: header, '+' and quality lines,
+ *   the last k - 1 bytes of a sequence line and its '\n', empty lines, windows the base rule drops.
+ * MEDIAN of a record: with v_0 <= ... <= v_(m-1) the profile entries of its k-mers, sorted (the saturated values; m =
+ *   `kmers`), the median is v_(m/2) (integer division: the upper middle for even m, khmer's convention), and 0 when
+ *   m = 0.  `kmers` counts k-mers under the base rule: it equals tsx_hip_read_stats.kmers when no base rule is set.
+ * MEDIAN RULE: a record passes iff lower <= median <= upper (a record with m = 0 is judged by its median 0); invert != 0
+ *   writes the records that fail.  What a written record is, the order and the '\n' handling are those of
+ *   tsx_hip_filter_reads_host.
+ * TSX_HIP_EINVAL for a map created with shard_bits > 0, and for a rule that is NULL, has lower > upper or reserved != 0.
+ *   count_profile_device  dev_text as tsx_hip_query_reads_device takes it; dev_profile: n uint32_t in device memory,
+ *                         every one written once.  WAITS for the stream.
+ *   count_profile_host    the same for text in host memory, in pieces cut at record boundaries (chunk_bytes 0 = 256 MiB,
+ *                         and at most TSX_HIP_PIECE_BYTES when that is set; a record longer than a piece is taken
+ *                         whole); profile positions are text positions.
+ *   median_reads_device   {kmers, median} of records [0, cap) to dev_medians (tsx_hip_read_median each).  The profile
+ *                         of the whole text (4 n bytes) and the line offsets are scratch of the call.  WAITS for the
+ *                         stream; more records than cap: TSX_HIP_ERANGE (the first cap are written).
+ *   median_reads_host     the same for text in host memory, in pieces.
+ *   filter_median_host    text in host memory in pieces; the device compacts piece i + 1 while the host writes piece i to
+ *                         fd.  Records kept and bytes written (optional).  A failed write: TSX_HIP_EIO.
+ * A record whose sequence line is longer than TSX_HIP_MEDIAN_LONG bases (environment, read per call; default 16384, at
+ * least 64) is selected by a whole workgroup instead of one wave; the results do not depend on it.
+ */
+#define TSX_HIP_NO_KMER 0xFFFFFFFFu
+typedef struct tsx_hip_read_median {
+    uint64_t kmers, median;
+} tsx_hip_read_median;
+typedef struct tsx_hip_median_rule {
+    uint64_t lower, upper;      /* the range of a passing median */
+    int32_t invert;             /* write the records that fail */
+    int32_t reserved;           /* 0 */
+} tsx_hip_median_rule;
+int tsx_hip_count_profile_device(tsx_hip_map *m, const void *dev_text, size_t n, void *dev_profile, void *stream);
+int tsx_hip_count_profile_host(tsx_hip_map *m, const char *text, size_t n, uint32_t *profile_out, size_t chunk_bytes);
+int tsx_hip_median_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, void *dev_medians, size_t cap,
+                                size_t *n_records, void *stream);
+int tsx_hip_median_reads_host(tsx_hip_map *m, const char *text, size_t n, tsx_hip_read_median *out, size_t cap,
+                              size_t *n_records, size_t chunk_bytes);
+int tsx_hip_filter_median_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_median_rule *rule, int fd,
+                               size_t chunk_bytes, uint64_t *kept_out, uint64_t *bytes_out);
+
+/*
  * Paired reads kept in step (csrc/tsx_pairs.h; no reference counterpart -- khmer `--paired`, Trimmomatic PE, BBDuk
  * in1/in2): the filter and the trim over mate pairs, so that the outputs line up record for record.  Records, lines,
  * k-mers, c(x) and the base rule are those of tsx_hip_query_reads_*.

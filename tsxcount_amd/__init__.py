@@ -60,6 +60,12 @@ class TrimRule(ctypes.Structure):
                 ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class MedianRule(ctypes.Structure):
+    """tsx_hip_median_rule: a record passes iff lower <= median <= upper; invert writes the failures."""
+    _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("invert", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class TrimTotals(ctypes.Structure):
     """tsx_hip_trim_totals."""
     _fields_ = [("records", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("bases_in", ctypes.c_uint64),
@@ -137,6 +143,25 @@ def trim_rule(lower=2, upper=None, mode="longest", min_len=0):
     if int(lower) > upper:
         raise ValueError("trim range: lower %d > upper %d" % (int(lower), upper))
     return TrimRule(int(lower), upper, int(min_len), TRIM_MODES[mode], 0)
+
+
+NO_KMER = 0xFFFFFFFF          # TSX_HIP_NO_KMER: the profile entry of a position where no k-mer starts
+READ_MEDIAN_DTYPE = np.dtype([("kmers", np.uint64), ("median", np.uint64)])
+
+
+def median_count(values):
+    """The median as medianReads reports it, on the CPU: element m // 2 of the m sorted values (the upper middle for
+    even m, khmer's convention), 0 without values.  Profile entries equal to NO_KMER are no values."""
+    v = sorted(int(x) for x in values if int(x) != NO_KMER)
+    return v[len(v) // 2] if v else 0
+
+
+def median_rule(lower=0, upper=None, invert=False):
+    """A MedianRule from the Python arguments.  Raises ValueError for lower > upper, before any GPU call."""
+    upper = (1 << 64) - 1 if upper is None else int(upper)
+    if int(lower) > upper:
+        raise ValueError("median range: lower %d > upper %d" % (int(lower), upper))
+    return MedianRule(int(lower), upper, 1 if invert else 0, 0)
 
 
 PAIR_MODES = {"both": 0, "any": 1}
@@ -264,6 +289,11 @@ def lib():
     L.tsx_hip_trim_spans_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), vp, sz, ctypes.POINTER(sz), sz]
     L.tsx_hip_trim_reads_device.argtypes = [vp, vp, sz, ctypes.POINTER(TrimRule), vp, sz, ctypes.POINTER(TrimTotals), vp]
     L.tsx_hip_trim_reads_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), ci, sz, ctypes.POINTER(TrimTotals)]
+    L.tsx_hip_count_profile_device.argtypes = [vp, vp, sz, vp, vp]
+    L.tsx_hip_count_profile_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz]
+    L.tsx_hip_median_reads_device.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(sz), vp]
+    L.tsx_hip_median_reads_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), sz]
+    L.tsx_hip_filter_median_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(MedianRule), ci, sz, u64p, u64p]
     L.tsx_hip_filter_pairs_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(FilterRule), ci, ci,
                                             ctypes.POINTER(PairIO), sz, ctypes.POINTER(PairTotals)]
     L.tsx_hip_trim_pairs_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), ci,
@@ -703,6 +733,65 @@ class TSXHashMapHIP:
                 os.close(fd)
         _check(rc)
         return tot.as_dict()
+
+    def countProfile(self, text, chunk_bytes=0):
+        """The count of every window of a FASTQ / FASTA text (tsx_hip_count_profile_host): numpy uint32[len(text)],
+        entry i = min(count, 0xFFFFFFFE) of the k-mer that starts at byte i, NO_KMER where none does."""
+        b = bytes(text)
+        out = np.empty(len(b), dtype=np.uint32)
+        _check(self._lib.tsx_hip_count_profile_host(self.handle, b, len(b), out.ctypes.data_as(ctypes.c_void_p),
+                                                    int(chunk_bytes)))
+        return out
+
+    def medianReads(self, text, chunk_bytes=0):
+        """The median k-mer count of every record of a FASTQ / FASTA text (tsx_hip_median_reads_host): a numpy
+        structured array (READ_MEDIAN_DTYPE: kmers, median), one entry per record in text order; the median is that of
+        median_count over the record's profile entries."""
+        b = bytes(text)
+        cap = len(b) // 256 + 16
+        for _ in range(2):
+            out = np.zeros(cap, dtype=READ_MEDIAN_DTYPE)
+            n = ctypes.c_size_t(0)
+            rc = self._lib.tsx_hip_median_reads_host(self.handle, b, len(b), out.ctypes.data_as(ctypes.c_void_p), cap,
+                                                     ctypes.byref(n), int(chunk_bytes))
+            if rc != ERANGE:
+                break
+            cap = n.value
+        _check(rc)
+        return out[:n.value]
+
+    def filterReadsByMedian(self, text, path_or_fd, lower=0, upper=None, invert=False, chunk_bytes=0):
+        """Write the records of `text` whose median k-mer count lies in [lower, upper] (tsx_hip_filter_median_host) to
+        a path (created or truncated) or an open file descriptor; invert writes the others.  Returns (records kept,
+        bytes written)."""
+        rule = median_rule(lower, upper, invert)
+        b = bytes(text)
+        kept, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        own = not isinstance(path_or_fd, int)
+        fd = os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd
+        try:
+            rc = self._lib.tsx_hip_filter_median_host(self.handle, b, len(b), ctypes.byref(rule), fd, int(chunk_bytes),
+                                                      ctypes.byref(kept), ctypes.byref(nbytes))
+        finally:
+            if own:
+                os.close(fd)
+        _check(rc)
+        return int(kept.value), int(nbytes.value)
+
+    def countProfileDevice(self, text_ptr, nbytes, profile_ptr, stream=None):
+        """tsx_hip_count_profile_device: the profile of a device text into a device buffer of nbytes uint32."""
+        vp = ctypes.c_void_p
+        _check(self._lib.tsx_hip_count_profile_device(self.handle, vp(text_ptr), nbytes, vp(profile_ptr),
+                                                      vp(stream) if stream else None))
+
+    def medianReadsDevice(self, text_ptr, nbytes, medians_ptr, cap, stream=None):
+        """tsx_hip_median_reads_device: {kmers, median} of the records of a device text into a device buffer of cap
+        entries.  Returns the record count (more than cap: TSXException ERANGE)."""
+        vp = ctypes.c_void_p
+        n = ctypes.c_size_t(0)
+        _check(self._lib.tsx_hip_median_reads_device(self.handle, vp(text_ptr), nbytes, vp(medians_ptr), cap, ctypes.byref(n),
+                                                     vp(stream) if stream else None))
+        return int(n.value)
 
     def _pairs(self, call, text1, text2, out1, out2, singles, chunk_bytes):
         """The common part of filterPairs / trimPairs: the four outputs opened (paths) or taken (fds), the call, the

@@ -13,6 +13,7 @@
 #include "tsx_combine.h"
 #include "tsx_fasta.h"
 #include "tsx_trim.h"
+#include "tsx_median.h"
 #include "tsx_pairs.h"
 #include "tsx_own.h"
 
@@ -4445,6 +4446,317 @@ extern "C" int tsx_hip_trim_reads_device(tsx_hip_map *m, const void *dev_text, s
     }
     if (totals) *totals = t;
     return rc;
+}
+
+// ---- read medians: the count of every window, the median of every record, the filter on it (tsx_median.h) ---------
+static const uint64_t MEDIAN_LONG_DEFAULT = 16384;   // bases of a sequence line above which a workgroup selects
+
+// TSX_HIP_MEDIAN_LONG, read per call (tests send reads through the workgroup form): at least 64.
+static uint64_t median_long_bases() {
+    uint64_t v = MEDIAN_LONG_DEFAULT;
+    if (const char *e = getenv("TSX_HIP_MEDIAN_LONG")) {
+        const long long x = atoll(e);
+        if (x >= 64) v = (uint64_t)x;
+    }
+    return v;
+}
+
+static bool median_rule_ok(const tsx_hip_median_rule *r) { return r && r->lower <= r->upper && r->reserved == 0; }
+
+// window_counts_kernel over the start positions [0, own_end) of d_text (n readable bytes), after query_line_pass.
+static int counts_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
+                         const unsigned long long *d_line_base, uint32_t *d_profile, hipStream_t st) {
+    if (own_end == 0) return TSX_HIP_OK;
+    const uint64_t ntiles = (own_end + TILE - 1) / TILE;
+    const size_t lut_bytes = m->lut.size() * 8;
+    const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 4);
+    DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((window_counts_kernel<WKV, CANV, BRV>), dim3(grid), dim3(NT),
+                                                        lut_bytes, st, m->p, d_text, n, own_end, head_open,
+                                                        (const uint32_t *)m->d_tile.get(), ntiles, d_line_base, d_profile,
+                                                        m->qmap_cur))));
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// Entries of the list of long records for a text of n bytes (the counter in front of them not counted).
+static uint64_t median_list_cap(uint64_t n, uint64_t long_len) { return n / (long_len + 1) + 2; }
+
+// Both selection kernels over the records [0, min(cap, *d_nrec or nrec)) with line offsets in lo: the wave form lists the
+// long records (list: the counter, then list_cap entries), the workgroup form takes them.  Queued, not waited for.
+static int median_select(tsx_hip_map *m, const uint32_t *d_profile, const unsigned long long *lo, const unsigned long long *d_nrec,
+                         uint64_t nrec, uint64_t cap, uint64_t long_len, unsigned long long *list, uint64_t list_cap,
+                         unsigned long long *med, hipStream_t st) {
+    if (cap == 0) return TSX_HIP_OK;
+    HIP_TRY(hipMemsetAsync(list, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(median_select_kernel, dim3((uint32_t)std::min<uint64_t>(cap, (uint64_t)m->cus * 32)), dim3(64), 0, st,
+                       d_profile, lo, d_nrec, nrec, cap, (uint32_t)m->p.k, long_len, list, list_cap, med);
+    hipLaunchKernelGGL(median_select_long_kernel, dim3((uint32_t)std::min<uint64_t>(list_cap, (uint64_t)m->cus * 4)), dim3(NT), 0, st,
+                       d_profile, lo, (const unsigned long long *)list, list_cap, (uint32_t)m->p.k, med);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// The windows of a device text, as tsx_hip_trim_spans_device walks them: every window writes its part of the profile
+// and, when `lo` is given, its line offsets (records < cap).  The record count is left in d_carry word 3.
+static int median_windows(tsx_hip_map *m, const uint8_t *base, size_t n, uint32_t *d_profile, unsigned long long *lo, uint64_t cap,
+                          hipStream_t st) {
+    int rc;
+    if (m->minq && (rc = build_qmap(m, base, n, st)) != TSX_HIP_OK) return rc;
+    const uint16_t *qmap = m->minq ? m->d_qmap.get() : nullptr;
+    QmapScope qs(m);
+    const uint32_t lpr = m->p.line_mask + 1, lshift = lpr == 4 ? 2u : 1u;
+    unsigned long long *d_base = (unsigned long long *)m->d_carry.get() + 2, *d_nrec = d_base + 1;
+    HIP_TRY(hipMemsetAsync(d_base, 0, 2 * sizeof(unsigned long long), st));
+    const size_t halo = (size_t)m->p.k - 1, WIN = (dev_window_bytes() + 63) & ~(size_t)63;
+    for (size_t off = 0; off < n; off += WIN) {
+        const size_t own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
+        const int head_open = off > 0 ? -1 : 0;
+        const bool last = off + own >= n;
+        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;
+        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
+        if ((rc = query_line_pass(m, base + off, len, own, head_open, st)) != TSX_HIP_OK) return rc;
+        if ((rc = counts_launch(m, base + off, len, own, head_open, d_base, d_profile + off, st)) != TSX_HIP_OK) return rc;
+        if (lo) {
+            const uint64_t ntiles = (own + TILE - 1) / TILE;
+            hipLaunchKernelGGL(trim_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
+                               base + off, (uint64_t)len, (uint64_t)own, head_open, (const uint32_t *)m->d_tile.get(), ntiles,
+                               (const unsigned long long *)d_base, (const uint32_t *)m->d_carry.get(), lshift, (uint64_t)off,
+                               last ? 1 : 0, lo, cap);
+        }
+        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), last ? 1 : 0,
+                           base + n - 1, lpr, d_nrec);
+    }
+    if (n == 0) {   // (no window has zeroed the carry of an earlier call)
+        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), 1,
+                           (const uint8_t *)nullptr, lpr, d_nrec);
+    }
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_count_profile_device(tsx_hip_map *m, const void *dev_text, size_t n, void *dev_profile, void *stream) {
+    if (!query_args_ok(m, 0, 0) || (!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_profile && n) || ((uintptr_t)dev_profile & 3))
+        return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    int rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    if ((rc = base_rule_ok(m)) != TSX_HIP_OK) return rc;
+    SyncAtExit wait(st);
+    if ((rc = median_windows(m, (const uint8_t *)dev_text, n, (uint32_t *)dev_profile, nullptr, 0, st)) != TSX_HIP_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return TSX_HIP_OK;
+}
+
+// The profile of the whole text and the line offsets stay on the device until the last window; then one selection.
+extern "C" int tsx_hip_median_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, void *dev_medians, size_t med_cap,
+                                           size_t *n_records, void *stream) {
+    if (n_records) *n_records = 0;
+    if (!query_args_ok(m, 0, 0) || (!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_medians && med_cap) ||
+        ((uintptr_t)dev_medians & 7))
+        return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    int rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    if ((rc = base_rule_ok(m)) != TSX_HIP_OK) return rc;
+    const uint32_t lpr = m->p.line_mask + 1;
+    // (a non-empty line and its '\n' are two bytes: no text holds more records than this)
+    const uint64_t cap = std::min<uint64_t>(med_cap, n / (2 * lpr) + 2);
+    const uint64_t long_len = median_long_bases(), list_cap = median_list_cap(n, long_len);
+    DevBuf<uint32_t> profile;
+    DevBuf<unsigned long long> lo, list;
+    SyncAtExit wait(st);
+    TSX_TRY(profile.alloc(((size_t)n + 16) * sizeof(uint32_t)));
+    TSX_TRY(lo.alloc((cap + 1) * TL_N * 8));
+    TSX_TRY(list.alloc((list_cap + 1) * 8));
+    HIP_TRY(hipMemsetAsync(lo.get(), 0, (cap + 1) * TL_N * 8, st));
+    if ((rc = median_windows(m, (const uint8_t *)dev_text, n, profile.get(), lo.get(), cap, st)) != TSX_HIP_OK) return rc;
+    const unsigned long long *d_nrec = (const unsigned long long *)m->d_carry.get() + 3;
+    if ((rc = median_select(m, profile.get(), lo.get(), d_nrec, 0, cap, long_len, list.get(), list_cap,
+                            (unsigned long long *)dev_medians, st)) != TSX_HIP_OK)
+        return rc;
+    unsigned long long nrec = 0;
+    HIP_TRY(hipMemcpyAsync(&nrec, d_nrec, sizeof nrec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n_records) *n_records = (size_t)nrec;
+    return nrec > med_cap ? TSX_HIP_ERANGE : TSX_HIP_OK;
+}
+
+// Scratch of one median call that works on pieces.
+struct MedianBufs {
+    DevBuf<uint8_t> text;
+    DevBuf<uint32_t> profile;
+    DevBuf<unsigned long long> lo, list, med, span, koff;
+    DevBuf<uint8_t> out;
+    DevBuf<unsigned long long> info;               // cut, records, open, total, line base (0), kept
+    PinBuf<unsigned long long> h_info;
+    PinBuf<uint8_t> h_out;
+    Event ev;
+    hipStream_t st;
+    explicit MedianBufs(hipStream_t s) : st(s) {}
+    ~MedianBufs() { (void)hipStreamSynchronize(st); }   // nothing queued may outlive the buffers
+    int init() {
+        TSX_TRY(info.alloc(8 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(info.get(), 0, 8 * sizeof(unsigned long long), st));
+        TSX_TRY(h_info.alloc(8 * sizeof(unsigned long long)));
+        return ev.create();
+    }
+};
+
+enum { MED_PROFILE = 0, MED_MEDIANS = 1, MED_FILTER = 2 };
+
+// One piece [0, len) of text in device memory that starts at a record boundary, behind the trim's front end: the line
+// pass and the record scan (waits once, for the cut and the record count), then over its whole records [0, cut) the
+// profile in b.profile and -- unless only the profile is asked for -- the line offsets and the medians in b.med.  What
+// follows the wait is queued, not waited for.  Not last and no whole record: nrec = 0, nothing done.
+static int median_piece(tsx_hip_map *m, MedianBufs &b, const uint8_t *d_text, uint64_t len, bool last, int what, uint64_t long_len,
+                        hipStream_t st, uint64_t &cut, uint64_t &nrec, bool &open) {
+    cut = nrec = 0; open = false;
+    if (len == 0) return TSX_HIP_OK;
+    TSX_TRY(piece_scan(m, d_text, len, last, b.info.get(), what == MED_FILTER ? &b.span : nullptr, st));
+    HIP_TRY(hipMemcpyAsync(b.h_info.get(), b.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    cut = b.h_info.get()[0]; nrec = b.h_info.get()[1]; open = b.h_info.get()[2] != 0;
+    if (nrec == 0) return TSX_HIP_OK;
+    const uint32_t lpr = m->p.line_mask + 1, lshift = lpr == 4 ? 2u : 1u;
+    const uint64_t ntiles = (cut + TILE - 1) / TILE;
+    int rc;
+    TSX_TRY(grow(st, b.profile, (cut + 16) * sizeof(uint32_t)));
+    QmapScope qs(m);
+    if (m->minq) {   // a quality rule: the bitmap of the whole records (its line pass over [0, cut) rewrites d_tile with the same values)
+        if ((rc = build_qmap(m, d_text, cut, st)) != TSX_HIP_OK) return rc;
+        m->qmap_cur = m->d_qmap.get();
+    }
+    const unsigned long long *zero = b.info.get() + 4;
+    if ((rc = counts_launch(m, d_text, cut, cut, 0, zero, b.profile.get(), st)) != TSX_HIP_OK) return rc;
+    if (what == MED_PROFILE) return TSX_HIP_OK;
+    const uint64_t list_cap = median_list_cap(cut, long_len);
+    TSX_TRY(grow(st, b.lo, nrec * TL_N * 8));
+    TSX_TRY(grow(st, b.med, nrec * sizeof(tsx_hip_read_median)));
+    TSX_TRY(grow(st, b.list, (list_cap + 1) * 8));
+    HIP_TRY(hipMemsetAsync(b.lo.get(), 0, nrec * TL_N * 8, st));
+    // (the carry is read for an unterminated last line only: then cut = len and it holds the lines of [0, cut))
+    hipLaunchKernelGGL(trim_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
+                       d_text, cut, cut, 0, (const uint32_t *)m->d_tile.get(), ntiles, zero, (const uint32_t *)m->d_carry.get(),
+                       lshift, (uint64_t)0, last ? 1 : 0, b.lo.get(), nrec);
+    return median_select(m, b.profile.get(), b.lo.get(), nullptr, nrec, nrec, long_len, b.list.get(), list_cap, b.med.get(), st);
+}
+
+// The host entry points, as trim_host: the text in pieces cut at record boundaries; a piece without a whole record grows
+// until it holds one.  MED_PROFILE: each piece's profile goes to profile_out + its offset.  MED_MEDIANS: each piece's
+// medians go to med_out[rec_base ..] while they fit.  MED_FILTER: the output of piece i is written to fd while the
+// device works on piece i + 1.
+static int median_host(tsx_hip_map *m, const char *text, size_t n, int what, size_t chunk_bytes, uint32_t *profile_out,
+                       tsx_hip_read_median *med_out, size_t med_cap, size_t *n_records, const tsx_hip_median_rule *rule, int fd,
+                       uint64_t *kept_out, uint64_t *bytes_out) {
+    if (!chunk_bytes) chunk_bytes = QUERY_CHUNK_DEFAULT;
+    if (m->piece_fixed) chunk_bytes = std::min(chunk_bytes, m->piece);
+    chunk_bytes = std::min(chunk_bytes, QUERY_PIECE_MAX);
+    HIP_TRY(hipSetDevice(m->device));
+    join_foreign(m, false);
+    hipStream_t st = m->stream.get();
+    int rc = base_rule_ok(m);
+    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
+    if (rc != TSX_HIP_OK) return rc;
+    MedianBufs b(st);
+    rc = b.init();
+    const unsigned long long *h_info = b.h_info.get();
+    const uint64_t long_len = median_long_bases();
+    uint64_t rec_base = 0, kept = 0, bytes = 0, pending = 0;
+    bool have_pending = false;
+    for (size_t off = 0; off < n && rc == TSX_HIP_OK;) {
+        size_t len = std::min(chunk_bytes, n - off);
+        uint64_t cut = 0, nrec = 0;
+        bool open = false;
+        for (;;) {
+            const bool last = off + len == n;
+            if ((rc = grow(st, b.text, len + 256)) != TSX_HIP_OK) break;
+            if (hipMemcpyAsync(b.text.get(), text + off, len, hipMemcpyHostToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            if ((rc = median_piece(m, b, b.text.get(), len, last, what, long_len, st, cut, nrec, open)) != TSX_HIP_OK) break;
+            if (nrec || last) break;
+            if (len >= QUERY_PIECE_MAX) { g_last_error = "a record longer than 3.75 GiB"; rc = TSX_HIP_EINVAL; break; }
+            len = std::min(std::min(2 * len, n - off), QUERY_PIECE_MAX);
+        }
+        if (rc != TSX_HIP_OK) break;
+        if (what == MED_PROFILE) {
+            if (nrec && (hipMemcpyAsync(profile_out + off, b.profile.get(), cut * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                         hipStreamSynchronize(st) != hipSuccess))
+                rc = TSX_HIP_EHIP;
+            // (a last piece without a record holds empty lines only)
+            if (!nrec) std::fill(profile_out + off, profile_out + off + cut, (uint32_t)TSX_HIP_NO_KMER);
+        } else if (what == MED_MEDIANS) {
+            if (rec_base < med_cap && nrec &&
+                (hipMemcpyAsync(med_out + rec_base, b.med.get(), std::min<uint64_t>(nrec, med_cap - rec_base) * sizeof(tsx_hip_read_median),
+                                hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
+                rc = TSX_HIP_EHIP;
+        } else if (nrec) {
+            const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+            if ((rc = grow(st, b.koff, (nk + nchunks + 16) * sizeof(unsigned long long))) != TSX_HIP_OK) break;
+            if ((rc = grow(st, b.out, cut + 64)) != TSX_HIP_OK) break;
+            if (hipMemsetAsync(b.koff.get() + nrec, 0, sizeof(unsigned long long), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
+            hipLaunchKernelGGL(median_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, (const unsigned long long *)b.med.get(),
+                               (const unsigned long long *)b.span.get(), nrec, rule->lower, rule->upper, rule->invert, open ? 1 : 0,
+                               b.koff.get(), b.info.get() + 5);
+            rc = filter_compact(m, b.text.get(), cut, b.span.get(), b.koff.get(), nrec, b.info.get() + 3, b.out.get(),
+                                (uint64_t)b.out.cap(), st);
+            if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.h_info.get() + 3, b.info.get() + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                                     hipEventRecord(b.ev.get(), st) != hipSuccess))
+                rc = TSX_HIP_EHIP;
+            if (rc == TSX_HIP_OK && have_pending) {   // the previous piece's output, while the device works on this one
+                rc = write_all(fd, b.h_out.get(), pending);
+                if (rc == TSX_HIP_OK) bytes += pending;
+                have_pending = false;
+            }
+            if (rc == TSX_HIP_OK && hipEventSynchronize(b.ev.get()) != hipSuccess) rc = TSX_HIP_EHIP;
+            if (rc == TSX_HIP_OK && h_info[3] > cut + 1) { g_last_error = "filter output larger than its piece"; rc = TSX_HIP_EHIP; }
+            if (rc == TSX_HIP_OK) {
+                const uint64_t total = h_info[3];
+                kept += h_info[5];
+                // (no wait: the copy that last filled it has been waited for, and written out above)
+                if (b.h_out.reserve(nullptr, total, total + total / 8 + 4096) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
+                if (rc == TSX_HIP_OK && total && (hipMemcpyAsync(b.h_out.get(), b.out.get(), total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                                                  hipStreamSynchronize(st) != hipSuccess))
+                    rc = TSX_HIP_EHIP;
+                pending = total;
+                have_pending = rc == TSX_HIP_OK;
+                // (the kept counter is per piece)
+                if (rc == TSX_HIP_OK && hipMemsetAsync(b.info.get() + 5, 0, sizeof(unsigned long long), st) != hipSuccess) rc = TSX_HIP_EHIP;
+            }
+        }
+        rec_base += nrec;
+        off += cut;
+    }
+    if (rc == TSX_HIP_OK && have_pending) {
+        rc = write_all(fd, b.h_out.get(), pending);
+        if (rc == TSX_HIP_OK) bytes += pending;
+    }
+    if (n_records) *n_records = (size_t)rec_base;
+    if (kept_out) *kept_out = kept;
+    if (bytes_out) *bytes_out = bytes;
+    if (rc == TSX_HIP_OK && what == MED_MEDIANS && rec_base > med_cap) rc = TSX_HIP_ERANGE;
+    return rc;
+}
+
+extern "C" int tsx_hip_count_profile_host(tsx_hip_map *m, const char *text, size_t n, uint32_t *profile_out, size_t chunk_bytes) {
+    if (!query_args_ok(m, 0, 0) || (!text && n) || (!profile_out && n)) return TSX_HIP_EINVAL;
+    return median_host(m, text, n, MED_PROFILE, chunk_bytes, profile_out, nullptr, 0, nullptr, nullptr, -1, nullptr, nullptr);
+}
+
+extern "C" int tsx_hip_median_reads_host(tsx_hip_map *m, const char *text, size_t n, tsx_hip_read_median *out, size_t cap,
+                                         size_t *n_records, size_t chunk_bytes) {
+    if (n_records) *n_records = 0;
+    if (!query_args_ok(m, 0, 0) || (!text && n) || (!out && cap)) return TSX_HIP_EINVAL;
+    return median_host(m, text, n, MED_MEDIANS, chunk_bytes, nullptr, out, cap, n_records, nullptr, -1, nullptr, nullptr);
+}
+
+extern "C" int tsx_hip_filter_median_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_median_rule *rule, int fd,
+                                          size_t chunk_bytes, uint64_t *kept_out, uint64_t *bytes_out) {
+    if (kept_out) *kept_out = 0;
+    if (bytes_out) *bytes_out = 0;
+    if (!median_rule_ok(rule) || !query_args_ok(m, 0, 0) || (!text && n) || fd < 0) return TSX_HIP_EINVAL;
+    return median_host(m, text, n, MED_FILTER, chunk_bytes, nullptr, nullptr, 0, nullptr, rule, fd, kept_out, bytes_out);
 }
 
 // ---- paired reads: the filter and the trim over mate pairs (tsx_pairs.h) -----------------------------------------

@@ -103,6 +103,39 @@ static tsx_hip_trim_totals tsx_trim_reads(tsx_hip_map *pMap, const char *pText, 
     fnCheck(rc);
     return oTotals;
 }
+// Read medians over one table (tsx_hip_count_profile_host / tsx_hip_median_reads_host / tsx_hip_filter_median_host).
+template <typename C>
+static std::vector<uint32_t> tsx_count_profile(tsx_hip_map *pMap, const char *pText, size_t iBytes, size_t iChunkBytes, C fnCheck) {
+    std::vector<uint32_t> out(iBytes);
+    fnCheck(tsx_hip_count_profile_host(pMap, pText, iBytes, out.data(), iChunkBytes));
+    return out;
+}
+template <typename C>
+static std::vector<tsx_hip_read_median> tsx_median_reads(tsx_hip_map *pMap, const char *pText, size_t iBytes, size_t iChunkBytes,
+                                                         C fnCheck) {
+    std::vector<tsx_hip_read_median> out(iBytes / 256 + 16);
+    size_t n = 0;
+    int rc = tsx_hip_median_reads_host(pMap, pText, iBytes, out.data(), out.size(), &n, iChunkBytes);
+    if (rc == TSX_HIP_ERANGE) {
+        out.resize(n);
+        rc = tsx_hip_median_reads_host(pMap, pText, iBytes, out.data(), n, &n, iChunkBytes);
+    }
+    fnCheck(rc);
+    out.resize(n);
+    return out;
+}
+template <typename C>
+static std::pair<uint64_t, uint64_t> tsx_filter_median(tsx_hip_map *pMap, const char *pText, size_t iBytes,
+                                                       const tsx_hip_median_rule &oRule, const std::string &sPath,
+                                                       size_t iChunkBytes, C fnCheck) {
+    const int fd = open(sPath.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) throw TSXException("could not open " + sPath + " for writing", TSX_HIP_EIO);
+    uint64_t iKept = 0, iWritten = 0;
+    int rc = tsx_hip_filter_median_host(pMap, pText, iBytes, &oRule, fd, iChunkBytes, &iKept, &iWritten);
+    if (close(fd) != 0 && rc == TSX_HIP_OK) rc = TSX_HIP_EIO;
+    fnCheck(rc);
+    return std::make_pair(iKept, iWritten);
+}
 // The filter and the trim over mate pairs (tsx_hip_filter_pairs_host / tsx_hip_trim_pairs_host).  pText2 == nullptr: one
 // interleaved text.  Paths: kept mates 1, kept mates 2, orphans of text 1, orphans of text 2 -- created / truncated; an
 // empty path is no output (-1: allowed for the orphans, and for everything of text 2 with an interleaved text).
@@ -264,6 +297,19 @@ public:
     std::pair<uint64_t, uint64_t> filterReads(const char *pText, size_t iBytes, const tsx_hip_filter_rule &oRule,
                                               const std::string &sPath, size_t iChunkBytes = 0) {
         return tsx_filter_reads(m_pMap, pText, iBytes, oRule, sPath, iChunkBytes, check);
+    }
+    // the count of every window of a text, one entry per byte (TSX_HIP_NO_KMER where no k-mer starts)
+    std::vector<uint32_t> countProfile(const char *pText, size_t iBytes, size_t iChunkBytes = 0) {
+        return tsx_count_profile(m_pMap, pText, iBytes, iChunkBytes, check);
+    }
+    // {kmers, median} of every record of a text (tsx_hip_median_reads_host)
+    std::vector<tsx_hip_read_median> medianReads(const char *pText, size_t iBytes, size_t iChunkBytes = 0) {
+        return tsx_median_reads(m_pMap, pText, iBytes, iChunkBytes, check);
+    }
+    // the records of a text whose median passes oRule into sPath (created / truncated); returns {records kept, bytes written}
+    std::pair<uint64_t, uint64_t> filterByMedian(const char *pText, size_t iBytes, const tsx_hip_median_rule &oRule,
+                                                 const std::string &sPath, size_t iChunkBytes = 0) {
+        return tsx_filter_median(m_pMap, pText, iBytes, oRule, sPath, iChunkBytes, check);
     }
     // the kept span (start, length) of every record of a text under oRule (tsx_hip_trim_spans_host)
     std::vector<tsx_hip_trim_span> trimSpans(const char *pText, size_t iBytes, const tsx_hip_trim_rule &oRule,

@@ -45,6 +45,10 @@ struct arguments {
     uint64_t filter_lower = 2, filter_upper = UINT64_MAX, filter_min = 0;
     double filter_fraction = 1.0;
     bool filter_invert = false;
+    // the median rule: --filter-median-lower / -upper switch --filter to it; --read-medians=FILE writes every record's median
+    std::string read_medians;
+    uint64_t filter_median_lower = 0, filter_median_upper = UINT64_MAX;
+    bool filter_median = false, filter_share = false;   // options of the median rule / of the share rule were given
     // read trimming after the count: --trim=OUT writes the records of --trim-input (default --input) cut to their solid
     // stretch, --trim-spans=FILE one line index<TAB>start<TAB>length per record
     std::string trim, trim_input, trim_spans, trim_mode = "longest";
@@ -80,6 +84,7 @@ static int usage() {
                  "                [--output=FILE [--lower=N] [--upper=N]] [--histo=FILE [--histo-max=H]]\n"
                  "                [--filter=OUT] [--read-stats=FILE] [--filter-input=FILE] [--filter-lower=N] [--filter-upper=N]\n"
                  "                [--filter-min=M] [--filter-fraction=F] [--filter-invert] [--save=DB] [--load=DB[,DB2,...]]\n"
+                 "                [--read-medians=FILE] [--filter-median-lower=N] [--filter-median-upper=N]\n"
                  "                [--trim=OUT] [--trim-spans=FILE] [--trim-input=FILE] [--trim-lower=N] [--trim-upper=N]\n"
                  "                [--trim-mode=longest|prefix] [--trim-min-len=N]\n"
                  "                [--filter-input=R1,R2 --filter=O1,O2] [--filter-singles=S1,S2] [--filter-pairs=both|any]\n"
@@ -105,6 +110,11 @@ static int usage() {
                  "with at least M (default 0) k-mers in range that make at least the share F (default 1.0) of its k-mers.\n"
                  "--filter-invert writes the records that fail. --read-stats writes index<TAB>kmers<TAB>in_range<TAB>min<TAB>sum\n"
                  "per record of the same input. One GPU only.\n"
+                 "--read-medians writes index<TAB>kmers<TAB>median per record of that input: the median count of the record's\n"
+                 "k-mers (the upper middle for an even number, 0 without k-mers). --filter-median-lower=N and / or\n"
+                 "--filter-median-upper=N switch --filter to the median rule: a record passes when its median lies in N..N\n"
+                 "(default 0..unbounded); --filter-invert applies, the other --filter-* rule options do not go with it. One GPU,\n"
+                 "single-end input, no wrapped FASTA.\n"
                  "--trim writes the records of --trim-input (default: --input) cut to their solid stretch: a window is solid\n"
                  "when its count lies in trim-lower..trim-upper (default 2..unbounded); --trim-mode=longest keeps the longest run\n"
                  "of solid windows (the leftmost among equals), prefix the run that starts the read. Records that keep fewer\n"
@@ -346,7 +356,8 @@ static std::string pairs_refusal(const arguments &a, bool trim) {
     return "";
 }
 
-static bool wants_queries(const arguments &a) { return !a.filter.empty() || !a.read_stats.empty(); }
+static bool wants_queries(const arguments &a) { return !a.filter.empty() || !a.read_stats.empty() || !a.read_medians.empty(); }
+static bool wants_medians(const arguments &a) { return !a.read_medians.empty() || a.filter_median; }
 
 // --filter and --read-stats on one table, after the count, the check and --output / --histo.  The input loads as the
 // counted one does; a BGZF file is inflated on the device.
@@ -390,7 +401,23 @@ static int run_read_queries(tsx_hip_map *pMap, const arguments &a) {
         if (!f) throw TSXException("could not write " + a.read_stats, TSX_HIP_EIO);
         std::cerr << "Wrote the k-mer stats of " << st.size() << " records to " << a.read_stats << std::endl;
     }
-    if (!a.filter.empty()) {
+    if (!a.read_medians.empty()) {
+        const std::vector<tsx_hip_read_median> md = tsx_median_reads(pMap, text, n, 0, check);
+        std::ofstream f(a.read_medians);
+        for (size_t i = 0; i < md.size(); ++i) f << i << '\t' << md[i].kmers << '\t' << md[i].median << '\n';
+        f.close();
+        if (!f) throw TSXException("could not write " + a.read_medians, TSX_HIP_EIO);
+        std::cerr << "Wrote the median k-mer counts of " << md.size() << " records to " << a.read_medians << std::endl;
+    }
+    if (!a.filter.empty() && a.filter_median) {
+        tsx_hip_median_rule rule;
+        rule.lower = a.filter_median_lower;
+        rule.upper = a.filter_median_upper;
+        rule.invert = a.filter_invert ? 1 : 0;
+        rule.reserved = 0;
+        const std::pair<uint64_t, uint64_t> r = tsx_filter_median(pMap, text, n, rule, a.filter, 0, check);
+        std::cerr << "Wrote " << r.first << " records (" << r.second << " bytes) to " << a.filter << std::endl;
+    } else if (!a.filter.empty()) {
         tsx_hip_filter_rule rule;
         rule.lower = a.filter_lower;
         rule.upper = a.filter_upper;
@@ -658,10 +685,13 @@ int main(int argc, char *argv[]) {
         else if (opt(argv[i], "histo-max", v)) a.histo_max = strtoull(v.c_str(), nullptr, 10);
         else if (opt(argv[i], "filter", v)) { a.filter = v; if (v.empty()) return usage(); }
         else if (opt(argv[i], "filter-input", v)) a.filter_input = v;
-        else if (opt(argv[i], "filter-lower", v)) a.filter_lower = strtoull(v.c_str(), nullptr, 10);
-        else if (opt(argv[i], "filter-upper", v)) a.filter_upper = strtoull(v.c_str(), nullptr, 10);
-        else if (opt(argv[i], "filter-min", v)) a.filter_min = strtoull(v.c_str(), nullptr, 10);
-        else if (opt(argv[i], "filter-fraction", v)) a.filter_fraction = atof(v.c_str());
+        else if (opt(argv[i], "filter-lower", v)) { a.filter_lower = strtoull(v.c_str(), nullptr, 10); a.filter_share = true; }
+        else if (opt(argv[i], "filter-upper", v)) { a.filter_upper = strtoull(v.c_str(), nullptr, 10); a.filter_share = true; }
+        else if (opt(argv[i], "filter-min", v)) { a.filter_min = strtoull(v.c_str(), nullptr, 10); a.filter_share = true; }
+        else if (opt(argv[i], "filter-fraction", v)) { a.filter_fraction = atof(v.c_str()); a.filter_share = true; }
+        else if (opt(argv[i], "filter-median-lower", v)) { a.filter_median_lower = strtoull(v.c_str(), nullptr, 10); a.filter_median = true; }
+        else if (opt(argv[i], "filter-median-upper", v)) { a.filter_median_upper = strtoull(v.c_str(), nullptr, 10); a.filter_median = true; }
+        else if (opt(argv[i], "read-medians", v)) { a.read_medians = v; if (v.empty()) return usage(); }
         else if (opt(argv[i], "filter-invert", v)) a.filter_invert = true;
         else if (opt(argv[i], "trim", v)) { a.trim = v; if (v.empty()) return usage(); }
         else if (opt(argv[i], "trim-spans", v)) { a.trim_spans = v; if (v.empty()) return usage(); }
@@ -789,6 +819,27 @@ int main(int argc, char *argv[]) {
     if (a.min_qual_char && is_fasta(a)) {
         std::cerr << "--min-qual-char needs FASTQ input: a FASTA record has no quality line" << std::endl;
         return usage();
+    }
+    if (wants_medians(a)) {   // what the median forms refuse, before the share rule's checks
+        std::string why;
+        if (a.filter_median && a.filter_share)
+            why = "--filter-median-lower / --filter-median-upper switch --filter to the median rule: they do not go with"
+                  " --filter-lower, --filter-upper, --filter-min or --filter-fraction";
+        else if (a.filter_median && a.filter.empty()) why = "--filter-median-lower / --filter-median-upper need --filter=OUT";
+        else if (a.filter_median && a.filter_median_lower > a.filter_median_upper) why = "--filter-median-lower is above --filter-median-upper";
+        else if (filter_paired(a))
+            why = "--read-medians and the median rule of --filter do not take paired input (two --filter-input files or"
+                  " --filter-interleaved): medians of mate pairs are not built yet";
+        else if (a.gpus > 1)
+            why = "--read-medians and the median rule of --filter run on one GPU only: every k-mer lives on one rank of a --gpus " +
+                  std::to_string(a.gpus) + " run. Count with --gpus=1 (or without --gpus)";
+        else if (is_wrapped(a) && (a.filter_input.empty() || a.filter_input == a.input_path))
+            why = "--read-medians and the median rule of --filter do not read wrapped FASTA: give the reads as --filter-input=FILE"
+                  " (FASTQ, or FASTA with one sequence line per record)";
+        if (!why.empty()) {
+            std::cerr << why << std::endl;
+            return usage();
+        }
     }
     if (is_wrapped(a)) {
         if (a.gpus > 1) {
