@@ -3839,9 +3839,56 @@ static int query_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint6
     return TSX_HIP_OK;
 }
 
-// Device texts in windows like tsx_hip_count_fastq_device; the line index of each window continues from a 64-bit
-// base on the device (the map's FASTQ scratch: word 0 of d_carry is the scan carry, words 2 and 3 the line base and
-// the record count).
+// A device text in windows like tsx_hip_count_fastq_device; the line index of each window continues from a 64-bit base
+// on the device (the map's FASTQ scratch: word 0 of d_carry is the scan carry, words 2 and 3 the line base and the
+// record count).  `round64`: windows of whole 64-byte words, for the callers that keep one bitmap word per 64 start
+// positions.  A quality rule: the bitmap of the whole text first, qmap_cur per window.  Every window: the scan
+// carry from zero, the line pass, then per_window(off, own, len, head_open, last, d_base) queues the call's kernels over
+// the start positions [off, off + own) (len readable bytes from off), then the base and the record count move on.  The
+// record count is left in d_carry word 3.  Queued, not waited for.
+template <class PerWindow>
+static int device_windows(tsx_hip_map *m, const uint8_t *base, size_t n, bool round64, hipStream_t st, PerWindow per_window) {
+    int rc;
+    if (m->minq && (rc = build_qmap(m, base, n, st)) != TSX_HIP_OK) return rc;
+    const uint16_t *qmap = m->minq ? m->d_qmap.get() : nullptr;
+    QmapScope qs(m);
+    const uint32_t lpr = m->p.line_mask + 1;
+    unsigned long long *d_base = (unsigned long long *)m->d_carry.get() + 2, *d_nrec = d_base + 1;
+    HIP_TRY(hipMemsetAsync(d_base, 0, 2 * sizeof(unsigned long long), st));
+    const size_t halo = (size_t)m->p.k - 1, WIN = round64 ? (dev_window_bytes() + 63) & ~(size_t)63 : dev_window_bytes();
+    auto window_end = [&](bool last, const uint8_t *tail) {
+        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), last ? 1 : 0,
+                           tail, lpr, d_nrec);
+    };
+    for (size_t off = 0; off < n; off += WIN) {
+        const size_t own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
+        const int head_open = off > 0 ? -1 : 0;
+        const bool last = off + own >= n;
+        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;   // (windows start at multiples of 16)
+        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
+        if ((rc = query_line_pass(m, base + off, len, own, head_open, st)) != TSX_HIP_OK) return rc;
+        if ((rc = per_window(off, own, len, head_open, last, (const unsigned long long *)d_base)) != TSX_HIP_OK) return rc;
+        window_end(last, base + n - 1);
+    }
+    if (n == 0) {   // (no window has zeroed the carry of an earlier call)
+        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
+        window_end(true, nullptr);
+    }
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// Behind device_windows and what the call queued after it: waits for the record count.  More records than the caller's
+// array holds: TSX_HIP_ERANGE.
+static int windows_records(tsx_hip_map *m, size_t cap, size_t *n_records, hipStream_t st) {
+    HIP_TRY(hipGetLastError());
+    unsigned long long nrec = 0;
+    HIP_TRY(hipMemcpyAsync(&nrec, (const unsigned long long *)m->d_carry.get() + 3, sizeof nrec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n_records) *n_records = (size_t)nrec;
+    return nrec > cap ? TSX_HIP_ERANGE : TSX_HIP_OK;
+}
+
 extern "C" int tsx_hip_query_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, uint64_t lower, uint64_t upper,
                                           void *dev_stats, size_t stats_cap, size_t *n_records, void *stream) {
     if (n_records) *n_records = 0;
@@ -3852,61 +3899,62 @@ extern "C" int tsx_hip_query_reads_device(tsx_hip_map *m, const void *dev_text, 
     int rc = ensure_zeroed(m, st);
     if (rc != TSX_HIP_OK) return rc;
     if ((rc = base_rule_ok(m)) != TSX_HIP_OK) return rc;
-    if (m->minq && (rc = build_qmap(m, (const uint8_t *)dev_text, n, st)) != TSX_HIP_OK) return rc;
-    const uint16_t *qmap = m->minq ? m->d_qmap.get() : nullptr;
-    QmapScope qs(m);
-    unsigned long long *stats = (unsigned long long *)dev_stats;
-    unsigned long long *d_base = (unsigned long long *)m->d_carry.get() + 2, *d_nrec = d_base + 1;
-    if (stats_cap) HIP_TRY(hipMemsetAsync(stats, 0, stats_cap * sizeof(tsx_hip_read_stats), st));
-    HIP_TRY(hipMemsetAsync(d_base, 0, 2 * sizeof(unsigned long long), st));
     const uint8_t *base = (const uint8_t *)dev_text;
-    const size_t halo = (size_t)m->p.k - 1, WIN = dev_window_bytes();
-    const uint32_t lpr = m->p.line_mask + 1;
-    for (size_t off = 0; off < n; off += WIN) {
-        const size_t own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
-        const int head_open = off > 0 ? -1 : 0;
-        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;   // (windows start at multiples of 16)
-        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-        if ((rc = query_line_pass(m, base + off, len, own, head_open, st)) != TSX_HIP_OK) return rc;
-        if ((rc = query_launch(m, base + off, len, own, head_open, d_base, lower, upper, stats, stats_cap, st)) != TSX_HIP_OK)
-            return rc;
-        const bool last = off + own >= n;
-        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), last ? 1 : 0,
-                           base + n - 1, lpr, d_nrec);
-    }
-    if (n == 0)
-        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), 1,
-                           (const uint8_t *)nullptr, lpr, d_nrec);
+    unsigned long long *stats = (unsigned long long *)dev_stats;
+    if (stats_cap) HIP_TRY(hipMemsetAsync(stats, 0, stats_cap * sizeof(tsx_hip_read_stats), st));
+    rc = device_windows(m, base, n, false, st,
+                        [&](size_t off, size_t own, size_t len, int head_open, bool, const unsigned long long *d_base) {
+                            return query_launch(m, base + off, len, own, head_open, d_base, lower, upper, stats, stats_cap, st);
+                        });
+    if (rc != TSX_HIP_OK) return rc;
     if (stats_cap)
         hipLaunchKernelGGL(query_finalize_kernel, dim3(grid_for(m, stats_cap, 8)), dim3(NT), 0, st, stats, (uint64_t)stats_cap,
-                           (const unsigned long long *)d_nrec, (uint64_t)0);
-    HIP_TRY(hipGetLastError());
-    unsigned long long nrec = 0;
-    HIP_TRY(hipMemcpyAsync(&nrec, d_nrec, sizeof nrec, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (n_records) *n_records = (size_t)nrec;
-    return nrec > stats_cap ? TSX_HIP_ERANGE : TSX_HIP_OK;
+                           (const unsigned long long *)m->d_carry.get() + 3, (uint64_t)0);
+    return windows_records(m, stats_cap, n_records, st);
 }
 
-// Scratch of one host query / filter call.
-struct QueryBufs {
+// Scratch common to the calls that work on a text piece by piece: the piece on the device, its record spans (for the
+// calls that cut by them), the words the scans and the filters report in, their pinned copy.  The scratch of a call
+// (QueryBufs, TrimBufs, MedianBufs) embeds it BEHIND its own buffers: the destructor here waits for the stream before
+// any of them is released.
+struct PieceBufs {
     DevBuf<uint8_t> text;
-    DevBuf<unsigned long long> stats, span, koff;
-    DevBuf<uint8_t> own_out;                       // the filter's output, unless the caller gave a buffer:
-    uint8_t *out = nullptr; size_t out_have = 0;   // where it goes, and the room there
-    DevBuf<unsigned long long> info;               // cut, records, open, total, line base (0), kept
+    DevBuf<unsigned long long> rspan;              // record spans
+    DevBuf<unsigned long long> info;               // cut, records, open, total, line base (0), kept; the trim: bases in, bases kept
     PinBuf<unsigned long long> h_info;
-    PinBuf<uint8_t> h_out;
-    Event ev;
+    Event ev;                                      // info[3..] has been copied back
     hipStream_t st;
-    explicit QueryBufs(hipStream_t s) : st(s) {}
-    ~QueryBufs() { (void)hipStreamSynchronize(st); }   // nothing queued may outlive the buffers
+    explicit PieceBufs(hipStream_t s) : st(s) {}
+    ~PieceBufs() { (void)hipStreamSynchronize(st); }   // nothing queued may outlive the buffers
     int init() {
         TSX_TRY(info.alloc(8 * sizeof(unsigned long long)));
         HIP_TRY(hipMemsetAsync(info.get(), 0, 8 * sizeof(unsigned long long), st));
         TSX_TRY(h_info.alloc(8 * sizeof(unsigned long long)));
         return ev.create();
     }
+};
+
+// Where the compacted output of a piece goes: the caller's buffer (never grown: the *_device entry points check that it
+// has the room) or, without one, `own`.
+struct OutBuf {
+    DevBuf<uint8_t> own;
+    uint8_t *out = nullptr; size_t have = 0;   // where it goes, and the room there
+    // room for the worst case of a piece cut at `cut`: cut + 1 bytes, rounded up
+    int room(hipStream_t st, uint64_t cut) {
+        if (cut + 64 > have) {   // (as grow() finds it)
+            TSX_TRY(grow(st, own, cut + 64));
+            out = own.get(); have = own.cap();
+        }
+        return TSX_HIP_OK;
+    }
+};
+
+// Scratch of one query / filter call that works on pieces.
+struct QueryBufs {
+    DevBuf<unsigned long long> stats, koff;
+    OutBuf out;        // the filter's output
+    PieceBufs p;
+    explicit QueryBufs(hipStream_t s) : p(s) {}
 };
 
 // The scan half of a piece [0, len) of text in device memory that starts at a record boundary: the line pass and the
@@ -3926,37 +3974,50 @@ static int piece_scan(tsx_hip_map *m, const uint8_t *d_text, uint64_t len, bool 
     return TSX_HIP_OK;
 }
 
+// The front end of every piece [0, len) of text in device memory that starts at a record boundary: piece_scan (the
+// spans in p.rspan when `spans`), then the ONE wait of a piece, for where its last whole record ends, its records and
+// whether the last one lacks its '\n'.  An empty piece: nothing.
+static int piece_front(tsx_hip_map *m, PieceBufs &p, const uint8_t *d_text, uint64_t len, bool last, bool spans, uint64_t &cut,
+                       uint64_t &nrec, bool &open) {
+    cut = nrec = 0; open = false;
+    if (len == 0) return TSX_HIP_OK;
+    TSX_TRY(piece_scan(m, d_text, len, last, p.info.get(), spans ? &p.rspan : nullptr, p.st));
+    const unsigned long long *h_info = p.h_info.get();
+    HIP_TRY(hipMemcpyAsync(p.h_info.get(), p.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, p.st));
+    HIP_TRY(hipStreamSynchronize(p.st));
+    cut = h_info[0]; nrec = h_info[1]; open = h_info[2] != 0;
+    return TSX_HIP_OK;
+}
+
+// A quality rule: the bitmap of the whole records d_text[0, cut) for the launches that follow (its line pass over
+// [0, cut) rewrites d_tile with the same values).  The caller holds a QmapScope.
+static int piece_qmap(tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, hipStream_t st) {
+    if (!m->minq) return TSX_HIP_OK;
+    TSX_TRY(build_qmap(m, d_text, cut, st));
+    m->qmap_cur = m->d_qmap.get();
+    return TSX_HIP_OK;
+}
+
 // The query half: the stats of the records [0, nrec) of d_text[0, cut) in b.stats, after a line pass over a text that
 // starts with [0, cut) (the tile line counts).  Queued, not waited for.
 static int query_records(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint64_t cut, uint64_t nrec, uint64_t lower,
                          uint64_t upper, hipStream_t st) {
-    int rc;
-    if ((rc = grow(st, b.stats, nrec * sizeof(tsx_hip_read_stats))) != TSX_HIP_OK) return rc;
+    TSX_TRY(grow(st, b.stats, nrec * sizeof(tsx_hip_read_stats)));
     HIP_TRY(hipMemsetAsync(b.stats.get(), 0, nrec * sizeof(tsx_hip_read_stats), st));
     QmapScope qs(m);
-    if (m->minq) {   // a quality rule: the bitmap of the whole records (its line pass over [0, cut) rewrites d_tile with the same values)
-        if ((rc = build_qmap(m, d_text, cut, st)) != TSX_HIP_OK) return rc;
-        m->qmap_cur = m->d_qmap.get();
-    }
-    if ((rc = query_launch(m, d_text, cut, cut, 0, b.info.get() + 4, lower, upper, b.stats.get(), nrec, st)) != TSX_HIP_OK) return rc;
+    TSX_TRY(piece_qmap(m, d_text, cut, st));
+    TSX_TRY(query_launch(m, d_text, cut, cut, 0, b.p.info.get() + 4, lower, upper, b.stats.get(), nrec, st));
     hipLaunchKernelGGL(query_finalize_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.stats.get(), nrec,
                        (const unsigned long long *)nullptr, nrec);
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
 
-// One piece [0, len) of text in device memory that starts at a record boundary: the line pass, the record scan (where
-// the last whole record ends, and the spans when `spans`), then -- when it holds a whole record -- the stats of its
-// records [0, nrec) in b.stats.  Waits once, for the cut.  Not last and no whole record: nrec = 0, nothing queried.
+// One piece: piece_front, then -- when it holds a whole record -- the stats of its records [0, nrec) in b.stats, queued
+// and not waited for.  Not last and no whole record: nrec = 0, nothing queried.
 static int query_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint64_t len, bool last, uint64_t lower,
                        uint64_t upper, bool spans, hipStream_t st, uint64_t &cut, uint64_t &nrec, bool &open) {
-    cut = nrec = 0; open = false;
-    if (len == 0) return TSX_HIP_OK;
-    TSX_TRY(piece_scan(m, d_text, len, last, b.info.get(), spans ? &b.span : nullptr, st));
-    const unsigned long long *h_info = b.h_info.get();
-    HIP_TRY(hipMemcpyAsync(b.h_info.get(), b.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    cut = h_info[0]; nrec = h_info[1]; open = h_info[2] != 0;
+    TSX_TRY(piece_front(m, b.p, d_text, len, last, spans, cut, nrec, open));
     if (nrec == 0) return TSX_HIP_OK;
     return query_records(m, b, d_text, cut, nrec, lower, upper, st);
 }
@@ -3980,105 +4041,155 @@ static int filter_compact(tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, c
     return TSX_HIP_OK;
 }
 
-// The filter behind query_piece: kept lengths, their scan (total -> b.info[3], kept records -> b.info[5]), the
-// compaction into b.out (own_out grown to the piece's worst case: cut + 1 bytes, rounded up -- or the caller's
-// buffer, never grown).  Queued, not waited for.
+// The filter behind query_piece: kept lengths, their scan (total -> info[3], kept records -> info[5]), the compaction
+// into b.out.  Queued, not waited for.
 static int filter_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint64_t cut, uint64_t nrec, bool open,
                         const tsx_hip_filter_rule &rule, hipStream_t st) {
     const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
     TSX_TRY(grow(st, b.koff, (nk + nchunks + 16) * sizeof(unsigned long long)));
-    if (cut + 64 > b.out_have) {   // (as grow() finds it: a caller's buffer has the room, tsx_hip_filter_reads_device checks)
-        TSX_TRY(grow(st, b.own_out, cut + 64));
-        b.out = b.own_out.get(); b.out_have = b.own_out.cap();
-    }
-    unsigned long long *const koff = b.koff.get(), *const info = b.info.get();
-    const unsigned long long *span = b.span.get();
+    TSX_TRY(b.out.room(st, cut));
+    unsigned long long *const koff = b.koff.get(), *const info = b.p.info.get();
+    const unsigned long long *span = b.p.rspan.get();
     HIP_TRY(hipMemsetAsync(koff + nrec, 0, sizeof(unsigned long long), st));
     hipLaunchKernelGGL(filter_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, (const unsigned long long *)b.stats.get(),
                        span, nrec, rule.min_in_range, (uint64_t)rule.fraction_ppm, rule.invert,
                        open ? 1 : 0, koff, info + 5);
-    return filter_compact(m, d_text, cut, span, koff, nrec, info + 3, b.out, (uint64_t)b.out_have, st);
+    return filter_compact(m, d_text, cut, span, koff, nrec, info + 3, b.out.out, (uint64_t)b.out.have, st);
 }
 
 static bool rule_ok(const tsx_hip_filter_rule *r) {
     return r && r->lower <= r->upper && r->fraction_ppm <= 1000000u;
 }
 
-// The host entry points: the text in pieces cut at record boundaries, chunk_bytes at a time.  A piece that holds no
-// whole record (a record longer than the piece) grows until it does.  stats mode (fd < 0): each piece's stats go to
-// stats_out[rec_base ..] while they fit.  filter mode: the output of piece i is written to fd while the device works on
-// piece i + 1.
-static int query_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, uint64_t upper, size_t chunk_bytes,
-                      tsx_hip_read_stats *stats_out, size_t stats_cap, size_t *n_records, const tsx_hip_filter_rule *rule,
-                      int fd, uint64_t *kept_out, uint64_t *bytes_out) {
+// What a host call does first: its piece size (0: the default; `piece_cap`: at most the map's TSX_HIP_PIECE_BYTES, which
+// only the median calls honour -- DESIGN.md §3), the device, the order behind a caller's stream, the base rule, the table.
+static int pieces_begin(tsx_hip_map *m, size_t &chunk_bytes, bool piece_cap) {
     if (!chunk_bytes) chunk_bytes = QUERY_CHUNK_DEFAULT;
+    if (piece_cap && m->piece_fixed) chunk_bytes = std::min(chunk_bytes, m->piece);
     chunk_bytes = std::min(chunk_bytes, QUERY_PIECE_MAX);
     HIP_TRY(hipSetDevice(m->device));
     join_foreign(m, false);
-    hipStream_t st = m->stream.get();
-    int rc = base_rule_ok(m);
-    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
-    if (rc != TSX_HIP_OK) return rc;
-    QueryBufs b(st);
-    rc = b.init();
-    const unsigned long long *h_info = b.h_info.get();
-    uint64_t rec_base = 0, kept = 0, bytes = 0, pending = 0;
-    bool have_pending = false;
-    for (size_t off = 0; off < n && rc == TSX_HIP_OK;) {
+    TSX_TRY(base_rule_ok(m));
+    return ensure_zeroed(m, m->stream.get());
+}
+
+// The piece text[0, len) to the device.  Queued, not waited for.
+static int piece_upload(PieceBufs &p, const char *text, size_t len) {
+    TSX_TRY(grow(p.st, p.text, len + 256));
+    HIP_TRY(hipMemcpyAsync(p.text.get(), text, len, hipMemcpyHostToDevice, p.st));
+    return TSX_HIP_OK;
+}
+
+// A piece that holds no whole record (a record longer than the piece) doubles, up to the `rest` of its text.
+static int piece_longer(size_t &len, size_t rest) {
+    if (len >= QUERY_PIECE_MAX) { g_last_error = "a record longer than 3.75 GiB"; return TSX_HIP_EINVAL; }
+    len = std::min(std::min(2 * len, rest), QUERY_PIECE_MAX);
+    return TSX_HIP_OK;
+}
+
+// The driver of the single-end host calls: the text in pieces cut at record boundaries, chunk_bytes at a time; a piece
+// without a whole record grows until it holds one.  Every piece goes to the device and through
+//   work(d_text, len, last, cut, nrec, open)     the call's *_piece: waits once, for the cut; the rest queued
+//   deliver(off, rec_base, cut, nrec, open)      the results of text[off, off + cut), records [rec_base, rec_base + nrec)
+// and the next one starts at the cut.  rec_base: the records of the pieces delivered (of a failed delivery too).
+template <class Work, class Deliver>
+static int host_pieces(tsx_hip_map *m, PieceBufs &p, const char *text, size_t n, size_t chunk_bytes, bool piece_cap,
+                       uint64_t &rec_base, Work work, Deliver deliver) {
+    TSX_TRY(pieces_begin(m, chunk_bytes, piece_cap));
+    TSX_TRY(p.init());
+    for (size_t off = 0; off < n;) {
         size_t len = std::min(chunk_bytes, n - off);
         uint64_t cut = 0, nrec = 0;
         bool open = false;
         for (;;) {
             const bool last = off + len == n;
-            if ((rc = grow(st, b.text, len + 256)) != TSX_HIP_OK) break;
-            if (hipMemcpyAsync(b.text.get(), text + off, len, hipMemcpyHostToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            if ((rc = query_piece(m, b, b.text.get(), len, last, lower, upper, rule != nullptr, st, cut, nrec, open)) != TSX_HIP_OK) break;
+            TSX_TRY(piece_upload(p, text + off, len));
+            TSX_TRY(work((const uint8_t *)p.text.get(), (uint64_t)len, last, cut, nrec, open));
             if (nrec || last) break;
-            if (len >= QUERY_PIECE_MAX) { g_last_error = "a record longer than 3.75 GiB"; rc = TSX_HIP_EINVAL; break; }
-            len = std::min(std::min(2 * len, n - off), QUERY_PIECE_MAX);
+            TSX_TRY(piece_longer(len, n - off));
         }
-        if (rc != TSX_HIP_OK) break;
-        if (!rule) {
-            if (rec_base < stats_cap && nrec &&
-                (hipMemcpyAsync(stats_out + rec_base, b.stats.get(), std::min<uint64_t>(nrec, stats_cap - rec_base) * sizeof(tsx_hip_read_stats),
-                                hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
-                rc = TSX_HIP_EHIP;
-        } else if (nrec) {
-            rc = filter_piece(m, b, b.text.get(), cut, nrec, open, *rule, st);
-            if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.h_info.get() + 3, b.info.get() + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                                     hipEventRecord(b.ev.get(), st) != hipSuccess))
-                rc = TSX_HIP_EHIP;
-            if (rc == TSX_HIP_OK && have_pending) {   // the previous piece's output, while the device works on this one
-                rc = write_all(fd, b.h_out.get(), pending);
-                if (rc == TSX_HIP_OK) bytes += pending;
-                have_pending = false;
-            }
-            if (rc == TSX_HIP_OK && hipEventSynchronize(b.ev.get()) != hipSuccess) rc = TSX_HIP_EHIP;
-            if (rc == TSX_HIP_OK && h_info[3] > cut + 1) { g_last_error = "filter output larger than its piece"; rc = TSX_HIP_EHIP; }
-            if (rc == TSX_HIP_OK) {
-                const uint64_t total = h_info[3];
-                kept += h_info[5];
-                // (no wait: the copy that last filled it has been waited for, and written out above)
-                if (b.h_out.reserve(nullptr, total, total + total / 8 + 4096) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
-                if (rc == TSX_HIP_OK && total && (hipMemcpyAsync(b.h_out.get(), b.out, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                                                  hipStreamSynchronize(st) != hipSuccess))
-                    rc = TSX_HIP_EHIP;
-                pending = total;
-                have_pending = rc == TSX_HIP_OK;
-                // (the kept counter is per piece)
-                if (rc == TSX_HIP_OK && hipMemsetAsync(b.info.get() + 5, 0, sizeof(unsigned long long), st) != hipSuccess) rc = TSX_HIP_EHIP;
-            }
-        }
+        const int rc = deliver(off, rec_base, cut, nrec, open);
         rec_base += nrec;
         off += cut;
+        if (rc != TSX_HIP_OK) return rc;
     }
-    if (rc == TSX_HIP_OK && have_pending) {
-        rc = write_all(fd, b.h_out.get(), pending);
-        if (rc == TSX_HIP_OK) bytes += pending;
+    return TSX_HIP_OK;
+}
+
+// Delivery to a caller's array of `cap` records: the records [rec_base, rec_base + nrec) of a piece, while they fit.
+template <class T>
+static int deliver_records(T *out, size_t cap, uint64_t rec_base, const void *d_rec, uint64_t nrec, hipStream_t st) {
+    if (rec_base >= cap || !nrec) return TSX_HIP_OK;
+    HIP_TRY(hipMemcpyAsync(out + rec_base, d_rec, std::min<uint64_t>(nrec, cap - rec_base) * sizeof(T), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return TSX_HIP_OK;
+}
+
+// Delivery to a file, behind the device: the output of piece i waits in a pinned buffer and is written to fd while the
+// device works on piece i + 1.  Declare it in FRONT of the scratch that waits for the stream when the call ends.
+struct WriteBehind {
+    PinBuf<uint8_t> h_out;
+    int fd = -1;
+    uint64_t pending = 0, bytes = 0;   // bytes that wait in h_out; bytes written
+    // what waits, to the file
+    int flush() {
+        if (fd < 0 || !pending) return TSX_HIP_OK;
+        TSX_TRY(write_all(fd, h_out.get(), pending));
+        bytes += pending;
+        pending = 0;
+        return TSX_HIP_OK;
     }
+    // `total` bytes at d_out into the pinned buffer: queued, the caller waits.  A piece cut at `cut` writes cut + 1 at most.
+    int stage(const uint8_t *d_out, uint64_t total, uint64_t cut, const char *what, hipStream_t st) {
+        if (total > cut + 1) { g_last_error = std::string(what) + " output larger than its piece"; return TSX_HIP_EHIP; }
+        // (no wait: the copy that last filled it has been waited for, and written out by flush())
+        if (h_out.reserve(nullptr, total, total + total / 8 + 4096) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+        if (total) HIP_TRY(hipMemcpyAsync(h_out.get(), d_out, total, hipMemcpyDeviceToHost, st));
+        pending = total;
+        return TSX_HIP_OK;
+    }
+    // One piece of a single-end call, behind the kernels that leave its output at d_out, its size in info[3] and
+    // `ncount` counters in info[5..]: the previous piece is written while they run, then this one is staged, its
+    // counters are added to count[] and start from zero again (they are per piece).
+    int piece(PieceBufs &p, const uint8_t *d_out, uint64_t cut, int ncount, uint64_t *count, const char *what) {
+        const unsigned long long *h_info = p.h_info.get();
+        HIP_TRY(hipMemcpyAsync(p.h_info.get() + 3, p.info.get() + 3, (2 + ncount) * sizeof(unsigned long long), hipMemcpyDeviceToHost, p.st));
+        HIP_TRY(hipEventRecord(p.ev.get(), p.st));
+        TSX_TRY(flush());   // the previous piece's output, while the device works on this one
+        HIP_TRY(hipEventSynchronize(p.ev.get()));
+        const uint64_t total = h_info[3];
+        TSX_TRY(stage(d_out, total, cut, what, p.st));
+        for (int i = 0; i < ncount; ++i) count[i] += h_info[5 + i];
+        if (total) HIP_TRY(hipStreamSynchronize(p.st));
+        HIP_TRY(hipMemsetAsync(p.info.get() + 5, 0, ncount * sizeof(unsigned long long), p.st));
+        return TSX_HIP_OK;
+    }
+};
+
+// Query and filter: the pieces of host_pieces.  stats mode (fd < 0): each piece's stats go to stats_out[rec_base ..]
+// while they fit.  filter mode: write-behind to fd.
+static int query_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, uint64_t upper, size_t chunk_bytes,
+                      tsx_hip_read_stats *stats_out, size_t stats_cap, size_t *n_records, const tsx_hip_filter_rule *rule,
+                      int fd, uint64_t *kept_out, uint64_t *bytes_out) {
+    hipStream_t st = m->stream.get();
+    WriteBehind wb;
+    wb.fd = fd;
+    QueryBufs b(st);
+    uint64_t rec_base = 0, kept = 0;
+    int rc = host_pieces(m, b.p, text, n, chunk_bytes, false, rec_base,
+        [&](const uint8_t *d_text, uint64_t len, bool last, uint64_t &cut, uint64_t &nrec, bool &open) {
+            return query_piece(m, b, d_text, len, last, lower, upper, rule != nullptr, st, cut, nrec, open);
+        },
+        [&](size_t, uint64_t base, uint64_t cut, uint64_t nrec, bool open) -> int {
+            if (!rule) return deliver_records(stats_out, stats_cap, base, b.stats.get(), nrec, st);
+            if (!nrec) return TSX_HIP_OK;
+            TSX_TRY(filter_piece(m, b, b.p.text.get(), cut, nrec, open, *rule, st));
+            return wb.piece(b.p, b.out.out, cut, 1, &kept, "filter");
+        });
+    if (rc == TSX_HIP_OK) rc = wb.flush();
     if (n_records) *n_records = (size_t)rec_base;
     if (kept_out) *kept_out = kept;
-    if (bytes_out) *bytes_out = bytes;
+    if (bytes_out) *bytes_out = wb.bytes;
     if (rc == TSX_HIP_OK && !rule && rec_base > stats_cap) rc = TSX_HIP_ERANGE;
     return rc;
 }
@@ -4112,17 +4223,17 @@ extern "C" int tsx_hip_filter_reads_device(tsx_hip_map *m, const void *dev_text,
     if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
     if (rc != TSX_HIP_OK) return rc;
     QueryBufs b(st);
-    rc = b.init();
-    b.out = (uint8_t *)dev_out; b.out_have = out_cap;   // the compaction writes the caller's buffer (never grown)
+    rc = b.p.init();
+    b.out.out = (uint8_t *)dev_out; b.out.have = out_cap;   // the compaction writes the caller's buffer (never grown)
     uint64_t cut = 0, nrec = 0, total = 0, kept = 0;
     bool open = false;
     if (rc == TSX_HIP_OK) rc = query_piece(m, b, (const uint8_t *)dev_text, n, true, rule->lower, rule->upper, true, st, cut, nrec, open);
     if (rc == TSX_HIP_OK && nrec) {
         rc = filter_piece(m, b, (const uint8_t *)dev_text, cut, nrec, open, *rule, st);
-        if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.h_info.get() + 3, b.info.get() + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.p.h_info.get() + 3, b.p.info.get() + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
                                  hipStreamSynchronize(st) != hipSuccess))
             rc = TSX_HIP_EHIP;
-        if (rc == TSX_HIP_OK) { total = b.h_info.get()[3]; kept = b.h_info.get()[5]; }
+        if (rc == TSX_HIP_OK) { total = b.p.h_info.get()[3]; kept = b.p.h_info.get()[5]; }
         if (rc == TSX_HIP_OK && total > cut + 1) { g_last_error = "filter output larger than its text"; rc = TSX_HIP_EHIP; }
     }
     if (out_bytes) *out_bytes = (size_t)total;
@@ -4152,8 +4263,21 @@ static int solid_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint6
     return TSX_HIP_OK;
 }
 
-// Spans of a device text in windows, as tsx_hip_query_reads_device: every window adds its words to one bitmap of the
-// whole text and its line offsets to one array; the runs are walked once, after the last window.
+// trim_lines_kernel over the start positions [0, own_end) of d_text (n readable bytes, `off` into its whole text), after
+// query_line_pass: the line offsets of the records < cap in lo.  `last`: the text ends here, and d_carry holds the line
+// ends up to there (an unterminated last line).
+static void lines_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
+                         const unsigned long long *d_line_base, uint64_t off, bool last, unsigned long long *lo, uint64_t cap,
+                         hipStream_t st) {
+    const uint64_t ntiles = (own_end + TILE - 1) / TILE;
+    const uint32_t lshift = m->p.line_mask == 3 ? 2u : 1u;
+    hipLaunchKernelGGL(trim_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
+                       d_text, n, own_end, head_open, (const uint32_t *)m->d_tile.get(), ntiles, d_line_base,
+                       (const uint32_t *)m->d_carry.get(), lshift, off, last ? 1 : 0, lo, cap);
+}
+
+// Spans of a device text in windows (device_windows): every window adds its words to one bitmap of the whole text and
+// its line offsets to one array; the runs are walked once, after the last window.
 extern "C" int tsx_hip_trim_spans_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_trim_rule *rule,
                                          void *dev_spans, size_t spans_cap, size_t *n_records, void *stream) {
     if (n_records) *n_records = 0;
@@ -4163,77 +4287,40 @@ extern "C" int tsx_hip_trim_spans_device(tsx_hip_map *m, const void *dev_text, s
     int rc = ensure_zeroed(m, st);
     if (rc != TSX_HIP_OK) return rc;
     if ((rc = base_rule_ok(m)) != TSX_HIP_OK) return rc;
-    if (m->minq && (rc = build_qmap(m, (const uint8_t *)dev_text, n, st)) != TSX_HIP_OK) return rc;
-    const uint16_t *qmap = m->minq ? m->d_qmap.get() : nullptr;
-    QmapScope qs(m);
-    const uint32_t lpr = m->p.line_mask + 1, lshift = lpr == 4 ? 2u : 1u;
+    const uint32_t lpr = m->p.line_mask + 1;
     // (a non-empty line and its '\n' are two bytes: no text holds more records than this)
     const uint64_t cap = std::min<uint64_t>(spans_cap, n / (2 * lpr) + 2), nwords = ((uint64_t)n + 63) / 64;
     DevBuf<unsigned long long> bits, lo;
     SyncAtExit wait(st);
     TSX_TRY(bits.alloc((nwords + 1) * 8));
     TSX_TRY(lo.alloc((cap + 1) * TL_N * 8));
+    const uint8_t *base = (const uint8_t *)dev_text;
     unsigned long long *span = (unsigned long long *)dev_spans;
-    unsigned long long *d_base = (unsigned long long *)m->d_carry.get() + 2, *d_nrec = d_base + 1;
     if (spans_cap) HIP_TRY(hipMemsetAsync(span, 0, spans_cap * sizeof(tsx_hip_trim_span), st));
     HIP_TRY(hipMemsetAsync(lo.get(), 0, (cap + 1) * TL_N * 8, st));
-    HIP_TRY(hipMemsetAsync(d_base, 0, 2 * sizeof(unsigned long long), st));
-    const uint8_t *base = (const uint8_t *)dev_text;
-    const size_t halo = (size_t)m->p.k - 1, WIN = (dev_window_bytes() + 63) & ~(size_t)63;   // whole bitmap words
-    for (size_t off = 0; off < n; off += WIN) {
-        const size_t own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
-        const int head_open = off > 0 ? -1 : 0;
-        const bool last = off + own >= n;
-        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;
-        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-        if ((rc = query_line_pass(m, base + off, len, own, head_open, st)) != TSX_HIP_OK) return rc;
-        if ((rc = solid_launch(m, base + off, len, own, head_open, d_base, *rule, bits.get() + off / 64, st)) != TSX_HIP_OK) return rc;
-        const uint64_t ntiles = (own + TILE - 1) / TILE;
-        hipLaunchKernelGGL(trim_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
-                           base + off, (uint64_t)len, (uint64_t)own, head_open, (const uint32_t *)m->d_tile.get(), ntiles,
-                           (const unsigned long long *)d_base, (const uint32_t *)m->d_carry.get(), lshift, (uint64_t)off,
-                           last ? 1 : 0, lo.get(), cap);
-        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), last ? 1 : 0,
-                           base + n - 1, lpr, d_nrec);
-    }
-    if (n == 0)
-        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), 1,
-                           (const uint8_t *)nullptr, lpr, d_nrec);
+    rc = device_windows(m, base, n, true, st,   // (whole bitmap words)
+                        [&](size_t off, size_t own, size_t len, int head_open, bool last, const unsigned long long *d_base) -> int {
+                            TSX_TRY(solid_launch(m, base + off, len, own, head_open, d_base, *rule, bits.get() + off / 64, st));
+                            lines_launch(m, base + off, len, own, head_open, d_base, off, last, lo.get(), cap, st);
+                            return TSX_HIP_OK;
+                        });
+    if (rc != TSX_HIP_OK) return rc;
     if (cap && nwords) {
+        const unsigned long long *d_nrec = (const unsigned long long *)m->d_carry.get() + 3;
         hipLaunchKernelGGL(trim_run_kernel, dim3(grid_for(m, nwords, 8)), dim3(NT), 0, st, (const unsigned long long *)bits.get(),
-                           nwords, (const unsigned long long *)lo.get(), (const unsigned long long *)d_nrec, (uint64_t)0, cap,
-                           (uint32_t)m->p.k, (int)rule->mode, span);
-        hipLaunchKernelGGL(trim_finalize_kernel, dim3(grid_for(m, cap, 8)), dim3(NT), 0, st, span, cap,
-                           (const unsigned long long *)d_nrec, (uint64_t)0);
+                           nwords, (const unsigned long long *)lo.get(), d_nrec, (uint64_t)0, cap, (uint32_t)m->p.k, (int)rule->mode,
+                           span);
+        hipLaunchKernelGGL(trim_finalize_kernel, dim3(grid_for(m, cap, 8)), dim3(NT), 0, st, span, cap, d_nrec, (uint64_t)0);
     }
-    HIP_TRY(hipGetLastError());
-    unsigned long long nrec = 0;
-    HIP_TRY(hipMemcpyAsync(&nrec, d_nrec, sizeof nrec, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (n_records) *n_records = (size_t)nrec;
-    return nrec > spans_cap ? TSX_HIP_ERANGE : TSX_HIP_OK;
+    return windows_records(m, spans_cap, n_records, st);
 }
 
 // Scratch of one trim call that works on pieces.
 struct TrimBufs {
-    DevBuf<uint8_t> text;
-    DevBuf<unsigned long long> bits, lo, span, seg, src;
-    DevBuf<unsigned long long> rspan;              // record spans (the pair calls cut by them)
-    DevBuf<uint8_t> own_out;                       // the output, unless the caller gave a buffer:
-    uint8_t *out = nullptr; size_t out_have = 0;   // where it goes, and the room there
-    DevBuf<unsigned long long> info;               // cut, records, open, total, line base (0), kept, bases in, bases kept
-    PinBuf<unsigned long long> h_info;
-    PinBuf<uint8_t> h_out;
-    Event ev;
-    hipStream_t st;
-    explicit TrimBufs(hipStream_t s) : st(s) {}
-    ~TrimBufs() { (void)hipStreamSynchronize(st); }   // nothing queued may outlive the buffers
-    int init() {
-        TSX_TRY(info.alloc(8 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(info.get(), 0, 8 * sizeof(unsigned long long), st));
-        TSX_TRY(h_info.alloc(8 * sizeof(unsigned long long)));
-        return ev.create();
-    }
+    DevBuf<unsigned long long> bits, lo, span, seg, src;   // (span: the packed runs, then the spans)
+    OutBuf out;        // the trimmed records
+    PieceBufs p;
+    explicit TrimBufs(hipStream_t s) : p(s) {}
 };
 
 // The records [0, nrec) of d_text[0, cut), after a line pass over a text that starts with [0, cut): bitmap, line offsets
@@ -4241,25 +4328,18 @@ struct TrimBufs {
 // unterminated last line).  Queued, not waited for.
 static int trim_records(tsx_hip_map *m, TrimBufs &b, const uint8_t *d_text, uint64_t cut, uint64_t nrec, bool last,
                         const tsx_hip_trim_rule &rule, hipStream_t st) {
-    const uint32_t lpr = m->p.line_mask + 1, lshift = lpr == 4 ? 2u : 1u;
-    const uint64_t nwords = (cut + 63) / 64, ntiles = (cut + TILE - 1) / TILE;
-    int rc;
+    const uint64_t nwords = (cut + 63) / 64;
     TSX_TRY(grow(st, b.bits, (nwords + 1) * 8));
     TSX_TRY(grow(st, b.lo, nrec * TL_N * 8));
     TSX_TRY(grow(st, b.span, nrec * sizeof(tsx_hip_trim_span)));
     HIP_TRY(hipMemsetAsync(b.lo.get(), 0, nrec * TL_N * 8, st));
     HIP_TRY(hipMemsetAsync(b.span.get(), 0, nrec * sizeof(tsx_hip_trim_span), st));
     QmapScope qs(m);
-    if (m->minq) {   // a quality rule: the bitmap of the whole records (its line pass over [0, cut) rewrites d_tile with the same values)
-        if ((rc = build_qmap(m, d_text, cut, st)) != TSX_HIP_OK) return rc;
-        m->qmap_cur = m->d_qmap.get();
-    }
-    const unsigned long long *zero = b.info.get() + 4;
-    if ((rc = solid_launch(m, d_text, cut, cut, 0, zero, rule, b.bits.get(), st)) != TSX_HIP_OK) return rc;
+    TSX_TRY(piece_qmap(m, d_text, cut, st));
+    const unsigned long long *zero = b.p.info.get() + 4;
+    TSX_TRY(solid_launch(m, d_text, cut, cut, 0, zero, rule, b.bits.get(), st));
     // (the carry is read for an unterminated last line only: then cut = len and it holds the lines of [0, cut))
-    hipLaunchKernelGGL(trim_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
-                       d_text, cut, cut, 0, (const uint32_t *)m->d_tile.get(), ntiles, zero, (const uint32_t *)m->d_carry.get(),
-                       lshift, (uint64_t)0, last ? 1 : 0, b.lo.get(), nrec);
+    lines_launch(m, d_text, cut, cut, 0, zero, 0, last, b.lo.get(), nrec, st);
     hipLaunchKernelGGL(trim_run_kernel, dim3(grid_for(m, nwords, 8)), dim3(NT), 0, st, (const unsigned long long *)b.bits.get(),
                        nwords, (const unsigned long long *)b.lo.get(), (const unsigned long long *)nullptr, nrec, nrec,
                        (uint32_t)m->p.k, (int)rule.mode, b.span.get());
@@ -4300,19 +4380,14 @@ static int trim_compact(tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, uns
     return TSX_HIP_OK;
 }
 
-// One piece [0, len) of text in device memory that starts at a record boundary: the line pass and the record scan (waits
-// once, for the cut and the record count), then over its whole records [0, cut): bitmap, line offsets, runs, and either
-// the spans alone (b.span, finalized) or -- `copy` -- the segment lengths, their scan (total -> b.info[3], totals ->
-// b.info[5..7]) and the output in b.out (own_out grown to cut + 64, or the caller's buffer, never grown).  What follows
-// the wait is queued, not waited for.  Not last and no whole record: nrec = 0, nothing done.
+// One piece: piece_front, then over its whole records [0, cut): bitmap, line offsets, runs, and either the spans alone
+// (b.span, finalized) or -- `copy` -- the segment lengths, their scan (total -> info[3], totals -> info[5..7]) and the
+// output in b.out.  What follows the wait is queued, not waited for.  Not last and no whole record: nrec = 0, nothing
+// done.
 static int trim_piece(tsx_hip_map *m, TrimBufs &b, const uint8_t *d_text, uint64_t len, bool last,
                       const tsx_hip_trim_rule &rule, bool copy, hipStream_t st, uint64_t &cut, uint64_t &nrec) {
-    cut = nrec = 0;
-    if (len == 0) return TSX_HIP_OK;
-    TSX_TRY(piece_scan(m, d_text, len, last, b.info.get(), nullptr, st));
-    HIP_TRY(hipMemcpyAsync(b.h_info.get(), b.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    cut = b.h_info.get()[0]; nrec = b.h_info.get()[1];
+    bool open;
+    TSX_TRY(piece_front(m, b.p, d_text, len, last, false, cut, nrec, open));
     if (nrec == 0) return TSX_HIP_OK;
     TSX_TRY(trim_records(m, b, d_text, cut, nrec, last, rule, st));
     if (!copy) {
@@ -4321,86 +4396,32 @@ static int trim_piece(tsx_hip_map *m, TrimBufs &b, const uint8_t *d_text, uint64
         HIP_TRY(hipGetLastError());
         return TSX_HIP_OK;
     }
-    TSX_TRY(trim_lens(m, b, nrec, rule, b.info.get() + 5, st));
-    if (cut + 64 > b.out_have) {   // (as grow() finds it: a caller's buffer has the room, tsx_hip_trim_reads_device checks)
-        TSX_TRY(grow(st, b.own_out, cut + 64));
-        b.out = b.own_out.get(); b.out_have = b.own_out.cap();
-    }
-    return trim_compact(m, d_text, cut, b.seg.get(), b.src.get(), nrec * 4, b.info.get() + 3, b.out, (uint64_t)b.out_have, st);
+    TSX_TRY(trim_lens(m, b, nrec, rule, b.p.info.get() + 5, st));
+    TSX_TRY(b.out.room(st, cut));
+    return trim_compact(m, d_text, cut, b.seg.get(), b.src.get(), nrec * 4, b.p.info.get() + 3, b.out.out, (uint64_t)b.out.have, st);
 }
 
-// The host entry points, as query_host: the text in pieces cut at record boundaries; a piece without a whole record
-// grows until it holds one.  fd < 0: each piece's spans go to spans_out[rec_base ..] while they fit.  Else the output of
-// piece i is written to fd while the device works on piece i + 1.
+// Spans and trimmed reads: the pieces of host_pieces.  fd < 0: each piece's spans go to spans_out[rec_base ..] while
+// they fit.  Else write-behind to fd.
 static int trim_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_trim_rule &rule, size_t chunk_bytes,
                      tsx_hip_trim_span *spans_out, size_t spans_cap, size_t *n_records, int fd, tsx_hip_trim_totals *totals) {
-    if (!chunk_bytes) chunk_bytes = QUERY_CHUNK_DEFAULT;
-    chunk_bytes = std::min(chunk_bytes, QUERY_PIECE_MAX);
-    HIP_TRY(hipSetDevice(m->device));
-    join_foreign(m, false);
     hipStream_t st = m->stream.get();
-    int rc = base_rule_ok(m);
-    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
-    if (rc != TSX_HIP_OK) return rc;
+    WriteBehind wb;
+    wb.fd = fd;
     TrimBufs b(st);
-    rc = b.init();
-    const unsigned long long *h_info = b.h_info.get();
-    tsx_hip_trim_totals t = {0, 0, 0, 0, 0};
-    uint64_t pending = 0;
-    bool have_pending = false;
-    for (size_t off = 0; off < n && rc == TSX_HIP_OK;) {
-        size_t len = std::min(chunk_bytes, n - off);
-        uint64_t cut = 0, nrec = 0;
-        for (;;) {
-            const bool last = off + len == n;
-            if ((rc = grow(st, b.text, len + 256)) != TSX_HIP_OK) break;
-            if (hipMemcpyAsync(b.text.get(), text + off, len, hipMemcpyHostToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            if ((rc = trim_piece(m, b, b.text.get(), len, last, rule, fd >= 0, st, cut, nrec)) != TSX_HIP_OK) break;
-            if (nrec || last) break;
-            if (len >= QUERY_PIECE_MAX) { g_last_error = "a record longer than 3.75 GiB"; rc = TSX_HIP_EINVAL; break; }
-            len = std::min(std::min(2 * len, n - off), QUERY_PIECE_MAX);
-        }
-        if (rc != TSX_HIP_OK) break;
-        if (fd < 0) {
-            if (t.records < spans_cap && nrec &&
-                (hipMemcpyAsync(spans_out + t.records, b.span.get(), std::min<uint64_t>(nrec, spans_cap - t.records) * sizeof(tsx_hip_trim_span),
-                                hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
-                rc = TSX_HIP_EHIP;
-        } else if (nrec) {
-            if (hipMemcpyAsync(b.h_info.get() + 3, b.info.get() + 3, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipEventRecord(b.ev.get(), st) != hipSuccess)
-                rc = TSX_HIP_EHIP;
-            if (rc == TSX_HIP_OK && have_pending) {   // the previous piece's output, while the device works on this one
-                rc = write_all(fd, b.h_out.get(), pending);
-                if (rc == TSX_HIP_OK) t.bytes += pending;
-                have_pending = false;
-            }
-            if (rc == TSX_HIP_OK && hipEventSynchronize(b.ev.get()) != hipSuccess) rc = TSX_HIP_EHIP;
-            if (rc == TSX_HIP_OK && h_info[3] > cut + 1) { g_last_error = "trim output larger than its piece"; rc = TSX_HIP_EHIP; }
-            if (rc == TSX_HIP_OK) {
-                const uint64_t total = h_info[3];
-                t.kept += h_info[5]; t.bases_in += h_info[6]; t.bases_kept += h_info[7];
-                // (no wait: the copy that last filled it has been waited for, and written out above)
-                if (b.h_out.reserve(nullptr, total, total + total / 8 + 4096) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
-                if (rc == TSX_HIP_OK && total && (hipMemcpyAsync(b.h_out.get(), b.out, total, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                                                  hipStreamSynchronize(st) != hipSuccess))
-                    rc = TSX_HIP_EHIP;
-                pending = total;
-                have_pending = rc == TSX_HIP_OK;
-                // (the totals are per piece)
-                if (rc == TSX_HIP_OK && hipMemsetAsync(b.info.get() + 5, 0, 3 * sizeof(unsigned long long), st) != hipSuccess) rc = TSX_HIP_EHIP;
-            }
-        }
-        t.records += nrec;
-        off += cut;
-    }
-    if (rc == TSX_HIP_OK && have_pending) {
-        rc = write_all(fd, b.h_out.get(), pending);
-        if (rc == TSX_HIP_OK) t.bytes += pending;
-    }
-    if (n_records) *n_records = (size_t)t.records;
-    if (totals) *totals = t;
-    if (rc == TSX_HIP_OK && fd < 0 && t.records > spans_cap) rc = TSX_HIP_ERANGE;
+    uint64_t records = 0, tot[3] = {0, 0, 0};   // kept, bases in, bases kept
+    int rc = host_pieces(m, b.p, text, n, chunk_bytes, false, records,
+        [&](const uint8_t *d_text, uint64_t len, bool last, uint64_t &cut, uint64_t &nrec, bool &) {
+            return trim_piece(m, b, d_text, len, last, rule, fd >= 0, st, cut, nrec);
+        },
+        [&](size_t, uint64_t base, uint64_t cut, uint64_t nrec, bool) -> int {
+            if (fd < 0) return deliver_records(spans_out, spans_cap, base, b.span.get(), nrec, st);
+            return nrec ? wb.piece(b.p, b.out.out, cut, 3, tot, "trim") : TSX_HIP_OK;
+        });
+    if (rc == TSX_HIP_OK) rc = wb.flush();
+    if (n_records) *n_records = (size_t)records;
+    if (totals) *totals = tsx_hip_trim_totals{records, tot[0], tot[1], tot[2], wb.bytes};
+    if (rc == TSX_HIP_OK && fd < 0 && records > spans_cap) rc = TSX_HIP_ERANGE;
     return rc;
 }
 
@@ -4431,16 +4452,16 @@ extern "C" int tsx_hip_trim_reads_device(tsx_hip_map *m, const void *dev_text, s
     if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
     if (rc != TSX_HIP_OK) return rc;
     TrimBufs b(st);
-    rc = b.init();
-    b.out = (uint8_t *)dev_out; b.out_have = out_cap;   // the copy writes the caller's buffer (never grown)
+    rc = b.p.init();
+    b.out.out = (uint8_t *)dev_out; b.out.have = out_cap;   // the copy writes the caller's buffer (never grown)
     tsx_hip_trim_totals t = {0, 0, 0, 0, 0};
     uint64_t cut = 0, nrec = 0;
     if (rc == TSX_HIP_OK) rc = trim_piece(m, b, (const uint8_t *)dev_text, n, true, *rule, true, st, cut, nrec);
     if (rc == TSX_HIP_OK && nrec) {
-        if (hipMemcpyAsync(b.h_info.get() + 3, b.info.get() + 3, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        if (hipMemcpyAsync(b.p.h_info.get() + 3, b.p.info.get() + 3, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
             rc = TSX_HIP_EHIP;
-        const unsigned long long *h = b.h_info.get();
+        const unsigned long long *h = b.p.h_info.get();
         if (rc == TSX_HIP_OK) { t.records = nrec; t.bytes = h[3]; t.kept = h[5]; t.bases_in = h[6]; t.bases_kept = h[7]; }
         if (rc == TSX_HIP_OK && t.bytes > cut + 1) { g_last_error = "trim output larger than its text"; rc = TSX_HIP_EHIP; }
     }
@@ -4496,43 +4517,16 @@ static int median_select(tsx_hip_map *m, const uint32_t *d_profile, const unsign
     return TSX_HIP_OK;
 }
 
-// The windows of a device text, as tsx_hip_trim_spans_device walks them: every window writes its part of the profile
-// and, when `lo` is given, its line offsets (records < cap).  The record count is left in d_carry word 3.
+// The windows of a device text (device_windows, whole 64-byte words as tsx_hip_trim_spans_device walks them): every window
+// writes its part of the profile and, when `lo` is given, its line offsets (records < cap).
 static int median_windows(tsx_hip_map *m, const uint8_t *base, size_t n, uint32_t *d_profile, unsigned long long *lo, uint64_t cap,
                           hipStream_t st) {
-    int rc;
-    if (m->minq && (rc = build_qmap(m, base, n, st)) != TSX_HIP_OK) return rc;
-    const uint16_t *qmap = m->minq ? m->d_qmap.get() : nullptr;
-    QmapScope qs(m);
-    const uint32_t lpr = m->p.line_mask + 1, lshift = lpr == 4 ? 2u : 1u;
-    unsigned long long *d_base = (unsigned long long *)m->d_carry.get() + 2, *d_nrec = d_base + 1;
-    HIP_TRY(hipMemsetAsync(d_base, 0, 2 * sizeof(unsigned long long), st));
-    const size_t halo = (size_t)m->p.k - 1, WIN = (dev_window_bytes() + 63) & ~(size_t)63;
-    for (size_t off = 0; off < n; off += WIN) {
-        const size_t own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
-        const int head_open = off > 0 ? -1 : 0;
-        const bool last = off + own >= n;
-        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;
-        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-        if ((rc = query_line_pass(m, base + off, len, own, head_open, st)) != TSX_HIP_OK) return rc;
-        if ((rc = counts_launch(m, base + off, len, own, head_open, d_base, d_profile + off, st)) != TSX_HIP_OK) return rc;
-        if (lo) {
-            const uint64_t ntiles = (own + TILE - 1) / TILE;
-            hipLaunchKernelGGL(trim_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
-                               base + off, (uint64_t)len, (uint64_t)own, head_open, (const uint32_t *)m->d_tile.get(), ntiles,
-                               (const unsigned long long *)d_base, (const uint32_t *)m->d_carry.get(), lshift, (uint64_t)off,
-                               last ? 1 : 0, lo, cap);
-        }
-        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), last ? 1 : 0,
-                           base + n - 1, lpr, d_nrec);
-    }
-    if (n == 0) {   // (no window has zeroed the carry of an earlier call)
-        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(query_window_kernel, dim3(1), dim3(64), 0, st, d_base, (const uint32_t *)m->d_carry.get(), 1,
-                           (const uint8_t *)nullptr, lpr, d_nrec);
-    }
-    HIP_TRY(hipGetLastError());
-    return TSX_HIP_OK;
+    return device_windows(m, base, n, true, st,
+                          [&](size_t off, size_t own, size_t len, int head_open, bool last, const unsigned long long *d_base) -> int {
+                              TSX_TRY(counts_launch(m, base + off, len, own, head_open, d_base, d_profile + off, st));
+                              if (lo) lines_launch(m, base + off, len, own, head_open, d_base, off, last, lo, cap, st);
+                              return TSX_HIP_OK;
+                          });
 }
 
 extern "C" int tsx_hip_count_profile_device(tsx_hip_map *m, const void *dev_text, size_t n, void *dev_profile, void *stream) {
@@ -4586,51 +4580,27 @@ extern "C" int tsx_hip_median_reads_device(tsx_hip_map *m, const void *dev_text,
 
 // Scratch of one median call that works on pieces.
 struct MedianBufs {
-    DevBuf<uint8_t> text;
     DevBuf<uint32_t> profile;
-    DevBuf<unsigned long long> lo, list, med, span, koff;
-    DevBuf<uint8_t> out;
-    DevBuf<unsigned long long> info;               // cut, records, open, total, line base (0), kept
-    PinBuf<unsigned long long> h_info;
-    PinBuf<uint8_t> h_out;
-    Event ev;
-    hipStream_t st;
-    explicit MedianBufs(hipStream_t s) : st(s) {}
-    ~MedianBufs() { (void)hipStreamSynchronize(st); }   // nothing queued may outlive the buffers
-    int init() {
-        TSX_TRY(info.alloc(8 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(info.get(), 0, 8 * sizeof(unsigned long long), st));
-        TSX_TRY(h_info.alloc(8 * sizeof(unsigned long long)));
-        return ev.create();
-    }
+    DevBuf<unsigned long long> lo, list, med, koff;
+    OutBuf out;        // the filter's output
+    PieceBufs p;
+    explicit MedianBufs(hipStream_t s) : p(s) {}
 };
 
 enum { MED_PROFILE = 0, MED_MEDIANS = 1, MED_FILTER = 2 };
 
-// One piece [0, len) of text in device memory that starts at a record boundary, behind the trim's front end: the line
-// pass and the record scan (waits once, for the cut and the record count), then over its whole records [0, cut) the
-// profile in b.profile and -- unless only the profile is asked for -- the line offsets and the medians in b.med.  What
-// follows the wait is queued, not waited for.  Not last and no whole record: nrec = 0, nothing done.
+// One piece: piece_front, then over its whole records [0, cut) the profile in b.profile and -- unless only the profile
+// is asked for -- the line offsets and the medians in b.med.  What follows the wait is queued, not waited for.  Not last
+// and no whole record: nrec = 0, nothing done.
 static int median_piece(tsx_hip_map *m, MedianBufs &b, const uint8_t *d_text, uint64_t len, bool last, int what, uint64_t long_len,
                         hipStream_t st, uint64_t &cut, uint64_t &nrec, bool &open) {
-    cut = nrec = 0; open = false;
-    if (len == 0) return TSX_HIP_OK;
-    TSX_TRY(piece_scan(m, d_text, len, last, b.info.get(), what == MED_FILTER ? &b.span : nullptr, st));
-    HIP_TRY(hipMemcpyAsync(b.h_info.get(), b.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    cut = b.h_info.get()[0]; nrec = b.h_info.get()[1]; open = b.h_info.get()[2] != 0;
+    TSX_TRY(piece_front(m, b.p, d_text, len, last, what == MED_FILTER, cut, nrec, open));
     if (nrec == 0) return TSX_HIP_OK;
-    const uint32_t lpr = m->p.line_mask + 1, lshift = lpr == 4 ? 2u : 1u;
-    const uint64_t ntiles = (cut + TILE - 1) / TILE;
-    int rc;
     TSX_TRY(grow(st, b.profile, (cut + 16) * sizeof(uint32_t)));
     QmapScope qs(m);
-    if (m->minq) {   // a quality rule: the bitmap of the whole records (its line pass over [0, cut) rewrites d_tile with the same values)
-        if ((rc = build_qmap(m, d_text, cut, st)) != TSX_HIP_OK) return rc;
-        m->qmap_cur = m->d_qmap.get();
-    }
-    const unsigned long long *zero = b.info.get() + 4;
-    if ((rc = counts_launch(m, d_text, cut, cut, 0, zero, b.profile.get(), st)) != TSX_HIP_OK) return rc;
+    TSX_TRY(piece_qmap(m, d_text, cut, st));
+    const unsigned long long *zero = b.p.info.get() + 4;
+    TSX_TRY(counts_launch(m, d_text, cut, cut, 0, zero, b.profile.get(), st));
     if (what == MED_PROFILE) return TSX_HIP_OK;
     const uint64_t list_cap = median_list_cap(cut, long_len);
     TSX_TRY(grow(st, b.lo, nrec * TL_N * 8));
@@ -4638,103 +4608,60 @@ static int median_piece(tsx_hip_map *m, MedianBufs &b, const uint8_t *d_text, ui
     TSX_TRY(grow(st, b.list, (list_cap + 1) * 8));
     HIP_TRY(hipMemsetAsync(b.lo.get(), 0, nrec * TL_N * 8, st));
     // (the carry is read for an unterminated last line only: then cut = len and it holds the lines of [0, cut))
-    hipLaunchKernelGGL(trim_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
-                       d_text, cut, cut, 0, (const uint32_t *)m->d_tile.get(), ntiles, zero, (const uint32_t *)m->d_carry.get(),
-                       lshift, (uint64_t)0, last ? 1 : 0, b.lo.get(), nrec);
+    lines_launch(m, d_text, cut, cut, 0, zero, 0, last, b.lo.get(), nrec, st);
     return median_select(m, b.profile.get(), b.lo.get(), nullptr, nrec, nrec, long_len, b.list.get(), list_cap, b.med.get(), st);
 }
 
-// The host entry points, as trim_host: the text in pieces cut at record boundaries; a piece without a whole record grows
-// until it holds one.  MED_PROFILE: each piece's profile goes to profile_out + its offset.  MED_MEDIANS: each piece's
-// medians go to med_out[rec_base ..] while they fit.  MED_FILTER: the output of piece i is written to fd while the
-// device works on piece i + 1.
+// The median filter behind median_piece, as filter_piece: kept lengths by the medians, their scan (total -> info[3], kept
+// records -> info[5]), the compaction into b.out.  Queued, not waited for.
+static int median_filter_piece(tsx_hip_map *m, MedianBufs &b, const uint8_t *d_text, uint64_t cut, uint64_t nrec, bool open,
+                               const tsx_hip_median_rule &rule, hipStream_t st) {
+    const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    TSX_TRY(grow(st, b.koff, (nk + nchunks + 16) * sizeof(unsigned long long)));
+    TSX_TRY(b.out.room(st, cut));
+    unsigned long long *const koff = b.koff.get(), *const info = b.p.info.get();
+    const unsigned long long *span = b.p.rspan.get();
+    HIP_TRY(hipMemsetAsync(koff + nrec, 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(median_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, (const unsigned long long *)b.med.get(),
+                       span, nrec, rule.lower, rule.upper, rule.invert, open ? 1 : 0, koff, info + 5);
+    return filter_compact(m, d_text, cut, span, koff, nrec, info + 3, b.out.out, (uint64_t)b.out.have, st);
+}
+
+// Profile, medians and the median filter: the pieces of host_pieces, at most TSX_HIP_PIECE_BYTES each when that is set.
+// MED_PROFILE: each piece's profile goes to profile_out + its offset.  MED_MEDIANS: each piece's medians go to
+// med_out[rec_base ..] while they fit.  MED_FILTER: write-behind to fd.
 static int median_host(tsx_hip_map *m, const char *text, size_t n, int what, size_t chunk_bytes, uint32_t *profile_out,
                        tsx_hip_read_median *med_out, size_t med_cap, size_t *n_records, const tsx_hip_median_rule *rule, int fd,
                        uint64_t *kept_out, uint64_t *bytes_out) {
-    if (!chunk_bytes) chunk_bytes = QUERY_CHUNK_DEFAULT;
-    if (m->piece_fixed) chunk_bytes = std::min(chunk_bytes, m->piece);
-    chunk_bytes = std::min(chunk_bytes, QUERY_PIECE_MAX);
-    HIP_TRY(hipSetDevice(m->device));
-    join_foreign(m, false);
     hipStream_t st = m->stream.get();
-    int rc = base_rule_ok(m);
-    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
-    if (rc != TSX_HIP_OK) return rc;
+    WriteBehind wb;
+    wb.fd = fd;
     MedianBufs b(st);
-    rc = b.init();
-    const unsigned long long *h_info = b.h_info.get();
     const uint64_t long_len = median_long_bases();
-    uint64_t rec_base = 0, kept = 0, bytes = 0, pending = 0;
-    bool have_pending = false;
-    for (size_t off = 0; off < n && rc == TSX_HIP_OK;) {
-        size_t len = std::min(chunk_bytes, n - off);
-        uint64_t cut = 0, nrec = 0;
-        bool open = false;
-        for (;;) {
-            const bool last = off + len == n;
-            if ((rc = grow(st, b.text, len + 256)) != TSX_HIP_OK) break;
-            if (hipMemcpyAsync(b.text.get(), text + off, len, hipMemcpyHostToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            if ((rc = median_piece(m, b, b.text.get(), len, last, what, long_len, st, cut, nrec, open)) != TSX_HIP_OK) break;
-            if (nrec || last) break;
-            if (len >= QUERY_PIECE_MAX) { g_last_error = "a record longer than 3.75 GiB"; rc = TSX_HIP_EINVAL; break; }
-            len = std::min(std::min(2 * len, n - off), QUERY_PIECE_MAX);
-        }
-        if (rc != TSX_HIP_OK) break;
-        if (what == MED_PROFILE) {
-            if (nrec && (hipMemcpyAsync(profile_out + off, b.profile.get(), cut * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                         hipStreamSynchronize(st) != hipSuccess))
-                rc = TSX_HIP_EHIP;
-            // (a last piece without a record holds empty lines only)
-            if (!nrec) std::fill(profile_out + off, profile_out + off + cut, (uint32_t)TSX_HIP_NO_KMER);
-        } else if (what == MED_MEDIANS) {
-            if (rec_base < med_cap && nrec &&
-                (hipMemcpyAsync(med_out + rec_base, b.med.get(), std::min<uint64_t>(nrec, med_cap - rec_base) * sizeof(tsx_hip_read_median),
-                                hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess))
-                rc = TSX_HIP_EHIP;
-        } else if (nrec) {
-            const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
-            if ((rc = grow(st, b.koff, (nk + nchunks + 16) * sizeof(unsigned long long))) != TSX_HIP_OK) break;
-            if ((rc = grow(st, b.out, cut + 64)) != TSX_HIP_OK) break;
-            if (hipMemsetAsync(b.koff.get() + nrec, 0, sizeof(unsigned long long), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            hipLaunchKernelGGL(median_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, (const unsigned long long *)b.med.get(),
-                               (const unsigned long long *)b.span.get(), nrec, rule->lower, rule->upper, rule->invert, open ? 1 : 0,
-                               b.koff.get(), b.info.get() + 5);
-            rc = filter_compact(m, b.text.get(), cut, b.span.get(), b.koff.get(), nrec, b.info.get() + 3, b.out.get(),
-                                (uint64_t)b.out.cap(), st);
-            if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.h_info.get() + 3, b.info.get() + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                                     hipEventRecord(b.ev.get(), st) != hipSuccess))
-                rc = TSX_HIP_EHIP;
-            if (rc == TSX_HIP_OK && have_pending) {   // the previous piece's output, while the device works on this one
-                rc = write_all(fd, b.h_out.get(), pending);
-                if (rc == TSX_HIP_OK) bytes += pending;
-                have_pending = false;
+    uint64_t rec_base = 0, kept = 0;
+    int rc = host_pieces(m, b.p, text, n, chunk_bytes, true, rec_base,
+        [&](const uint8_t *d_text, uint64_t len, bool last, uint64_t &cut, uint64_t &nrec, bool &open) {
+            return median_piece(m, b, d_text, len, last, what, long_len, st, cut, nrec, open);
+        },
+        [&](size_t off, uint64_t base, uint64_t cut, uint64_t nrec, bool open) -> int {
+            if (what == MED_MEDIANS) return deliver_records(med_out, med_cap, base, b.med.get(), nrec, st);
+            if (what == MED_PROFILE) {
+                if (nrec) {
+                    HIP_TRY(hipMemcpyAsync(profile_out + off, b.profile.get(), cut * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                    HIP_TRY(hipStreamSynchronize(st));
+                } else {   // (a last piece without a record holds empty lines only)
+                    std::fill(profile_out + off, profile_out + off + cut, (uint32_t)TSX_HIP_NO_KMER);
+                }
+                return TSX_HIP_OK;
             }
-            if (rc == TSX_HIP_OK && hipEventSynchronize(b.ev.get()) != hipSuccess) rc = TSX_HIP_EHIP;
-            if (rc == TSX_HIP_OK && h_info[3] > cut + 1) { g_last_error = "filter output larger than its piece"; rc = TSX_HIP_EHIP; }
-            if (rc == TSX_HIP_OK) {
-                const uint64_t total = h_info[3];
-                kept += h_info[5];
-                // (no wait: the copy that last filled it has been waited for, and written out above)
-                if (b.h_out.reserve(nullptr, total, total + total / 8 + 4096) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
-                if (rc == TSX_HIP_OK && total && (hipMemcpyAsync(b.h_out.get(), b.out.get(), total, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                                                  hipStreamSynchronize(st) != hipSuccess))
-                    rc = TSX_HIP_EHIP;
-                pending = total;
-                have_pending = rc == TSX_HIP_OK;
-                // (the kept counter is per piece)
-                if (rc == TSX_HIP_OK && hipMemsetAsync(b.info.get() + 5, 0, sizeof(unsigned long long), st) != hipSuccess) rc = TSX_HIP_EHIP;
-            }
-        }
-        rec_base += nrec;
-        off += cut;
-    }
-    if (rc == TSX_HIP_OK && have_pending) {
-        rc = write_all(fd, b.h_out.get(), pending);
-        if (rc == TSX_HIP_OK) bytes += pending;
-    }
+            if (!nrec) return TSX_HIP_OK;
+            TSX_TRY(median_filter_piece(m, b, b.p.text.get(), cut, nrec, open, *rule, st));
+            return wb.piece(b.p, b.out.out, cut, 1, &kept, "filter");
+        });
+    if (rc == TSX_HIP_OK) rc = wb.flush();
     if (n_records) *n_records = (size_t)rec_base;
     if (kept_out) *kept_out = kept;
-    if (bytes_out) *bytes_out = bytes;
+    if (bytes_out) *bytes_out = wb.bytes;
     if (rc == TSX_HIP_OK && what == MED_MEDIANS && rec_base > med_cap) rc = TSX_HIP_ERANGE;
     return rc;
 }
@@ -4760,24 +4687,23 @@ extern "C" int tsx_hip_filter_median_host(tsx_hip_map *m, const char *text, size
 }
 
 // ---- paired reads: the filter and the trim over mate pairs (tsx_pairs.h) -----------------------------------------
-// One input text of a pair call: where the next piece starts, the piece on the device, and the scratch of the single-end
-// path that works on it (q for the filter, t for the trim; only one of them is initialised).
+// One input text of a pair call: where the next piece starts, and the scratch of the single-end path that works on it
+// (q for the filter, t for the trim; p is the piece scratch of the one in use, the only one initialised).
 struct PairSide {
     QueryBufs q;
     TrimBufs t;
+    PieceBufs &p;
     const char *text = nullptr;
     size_t n = 0, off = 0, len = 0;
     bool last = false;
-    explicit PairSide(hipStream_t st) : q(st), t(st) {}
+    PairSide(hipStream_t st, bool trim) : q(st), t(st), p(trim ? t.p : q.p) {}
 };
-// One output of a pair call: the gated lengths (scanned in place), the compacted bytes and their pinned copy.
+// One output of a pair call: the gated lengths (scanned in place), the compacted bytes and their way to the file.
 struct PairOut {
     DevBuf<unsigned long long> off;
     DevBuf<uint8_t> out;
-    PinBuf<uint8_t> h_out;
-    int fd = -1;
+    WriteBehind w;
     bool used = false;      // the gate writes its lengths
-    uint64_t pending = 0, bytes = 0;
 };
 
 static int pair_fail(const std::string &what) {
@@ -4795,58 +4721,43 @@ static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *
                       tsx_hip_pair_totals *totals) {
     const bool trim = trule != nullptr, inter = text2 == nullptr;
     const int ns = inter ? 1 : 2;
-    if (!chunk_bytes) chunk_bytes = QUERY_CHUNK_DEFAULT;
-    chunk_bytes = std::min(chunk_bytes, QUERY_PIECE_MAX);
-    HIP_TRY(hipSetDevice(m->device));
-    join_foreign(m, false);
+    TSX_TRY(pieces_begin(m, chunk_bytes, false));
     hipStream_t st = m->stream.get();
-    int rc = base_rule_ok(m);
-    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
-    if (rc != TSX_HIP_OK) return rc;
+    int rc = TSX_HIP_OK;
     // (the sides are declared last: their destructors wait for the stream before anything here is released)
     PairOut out[4];
     DevBuf<unsigned long long> pinfo;
     PinBuf<unsigned long long> h_pinfo;
     Event ev;
-    PairSide side[2] = {PairSide(st), PairSide(st)};
+    PairSide side[2] = {PairSide(st, trim), PairSide(st, trim)};
     side[0].text = text1; side[0].n = n1;
     side[1].text = text2; side[1].n = inter ? 0 : n2;
-    out[0].fd = io.fd1; out[1].fd = io.fd2; out[2].fd = io.fd_single1; out[3].fd = io.fd_single2;
+    out[0].w.fd = io.fd1; out[1].w.fd = io.fd2; out[2].w.fd = io.fd_single1; out[3].w.fd = io.fd_single2;
     out[0].used = out[2].used = true;
     out[1].used = out[3].used = !inter;
-    for (int i = 0; i < ns; ++i) TSX_TRY(trim ? side[i].t.init() : side[i].q.init());
+    for (int i = 0; i < ns; ++i) TSX_TRY(side[i].p.init());
     TSX_TRY(pinfo.alloc(PI_N * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(pinfo.get(), 0, PI_N * sizeof(unsigned long long), st));
     TSX_TRY(h_pinfo.alloc(PI_N * sizeof(unsigned long long)));
     TSX_TRY(ev.create());
     const unsigned long long *h = h_pinfo.get();
     unsigned long long *const pi = pinfo.get();
-    auto textbuf = [&](PairSide &s) -> DevBuf<uint8_t> & { return trim ? s.t.text : s.q.text; };
-    auto infoof = [&](PairSide &s) { return trim ? s.t.info.get() : s.q.info.get(); };
-    auto spanof = [&](PairSide &s) -> DevBuf<unsigned long long> & { return trim ? s.t.rspan : s.q.span; };
     // the piece [off, off + len) of a side to the device, and its scan (an empty piece: no records)
     auto scan = [&](PairSide &s) -> int {
         s.last = s.off + s.len == s.n;
         if (s.len == 0) {
-            HIP_TRY(hipMemsetAsync(infoof(s), 0, 3 * sizeof(unsigned long long), st));
+            HIP_TRY(hipMemsetAsync(s.p.info.get(), 0, 3 * sizeof(unsigned long long), st));
             return TSX_HIP_OK;
         }
-        TSX_TRY(grow(st, textbuf(s), s.len + 256));
-        HIP_TRY(hipMemcpyAsync(textbuf(s).get(), s.text + s.off, s.len, hipMemcpyHostToDevice, st));
-        return piece_scan(m, textbuf(s).get(), s.len, s.last, infoof(s), &spanof(s), st);
+        TSX_TRY(piece_upload(s.p, s.text + s.off, s.len));
+        return piece_scan(m, s.p.text.get(), s.len, s.last, s.p.info.get(), &s.p.rspan, st);
     };
     auto longer = [&](PairSide &s) -> int {   // a piece without a whole record (interleaved: a whole pair) grows
-        if (s.len >= QUERY_PIECE_MAX) { g_last_error = "a record longer than 3.75 GiB"; return TSX_HIP_EINVAL; }
-        s.len = std::min(std::min(2 * s.len, s.n - s.off), QUERY_PIECE_MAX);
+        TSX_TRY(piece_longer(s.len, s.n - s.off));
         return scan(s);
     };
     auto flush = [&]() -> int {   // the outputs of the round before, to their files
-        for (PairOut &o : out) {
-            if (o.fd < 0 || !o.pending) continue;
-            TSX_TRY(write_all(o.fd, o.h_out.get(), o.pending));
-            o.bytes += o.pending;
-            o.pending = 0;
-        }
+        for (PairOut &o : out) TSX_TRY(o.w.flush());
         return TSX_HIP_OK;
     };
     tsx_hip_pair_totals t;
@@ -4862,10 +4773,10 @@ static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *
         }
         if (rc != TSX_HIP_OK) break;
         for (;;) {
-            hipLaunchKernelGGL(pair_cut_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)infoof(side[0]),
-                               (const unsigned long long *)spanof(side[0]).get(),
-                               inter ? (const unsigned long long *)nullptr : (const unsigned long long *)infoof(side[1]),
-                               inter ? (const unsigned long long *)nullptr : (const unsigned long long *)spanof(side[1]).get(),
+            hipLaunchKernelGGL(pair_cut_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)side[0].p.info.get(),
+                               (const unsigned long long *)side[0].p.rspan.get(),
+                               inter ? (const unsigned long long *)nullptr : (const unsigned long long *)side[1].p.info.get(),
+                               inter ? (const unsigned long long *)nullptr : (const unsigned long long *)side[1].p.rspan.get(),
                                side[0].last ? 1 : 0, pi);
             if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_pinfo.get(), pi, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
@@ -4901,7 +4812,7 @@ static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *
         // records [0, R) of each piece (the line pass again: the tile counts are the map's, and the other text's by now)
         for (int i = 0; i < ns && rc == TSX_HIP_OK; ++i) {
             PairSide &s = side[i];
-            const uint8_t *d_text = textbuf(s).get();
+            const uint8_t *d_text = s.p.text.get();
             if (hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
             if ((rc = query_line_pass(m, d_text, cut[i], cut[i], 0, st)) != TSX_HIP_OK) break;
             if (trim) {
@@ -4923,10 +4834,10 @@ static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *
         unsigned long long *const keep_a = out[0].off.get(), *const single_a = out[2].off.get();
         unsigned long long *const keep_b = inter ? keep_a + per : out[1].off.get();
         unsigned long long *const single_b = inter ? single_a + per : out[3].off.get();
-        const unsigned long long *span_a = spanof(side[0]).get(), *span_b = inter ? span_a + 2 : spanof(side[1]).get();
+        const unsigned long long *span_a = side[0].p.rspan.get(), *span_b = inter ? span_a + 2 : side[1].p.rspan.get();
         if (check_names)
-            hipLaunchKernelGGL(pair_names_kernel, dim3(grid_for(m, npairs, 8)), dim3(NT), 0, st, (const uint8_t *)textbuf(side[0]).get(),
-                               span_a, (const uint8_t *)textbuf(sb).get(), span_b, npairs, stride, pi + PI_BAD);
+            hipLaunchKernelGGL(pair_names_kernel, dim3(grid_for(m, npairs, 8)), dim3(NT), 0, st, (const uint8_t *)side[0].p.text.get(),
+                               span_a, (const uint8_t *)sb.p.text.get(), span_b, npairs, stride, pi + PI_BAD);
         if (trim) {
             const unsigned long long *seg_a = side[0].t.seg.get(), *seg_b = inter ? seg_a + 4 : side[1].t.seg.get();
             hipLaunchKernelGGL(pair_gate_trim_kernel, dim3(grid_for(m, npairs, 8)), dim3(NT), 0, st, seg_a, seg_b, npairs, stride,
@@ -4941,15 +4852,15 @@ static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *
         if (hipGetLastError() != hipSuccess) { rc = TSX_HIP_EHIP; break; }
         for (int oi = 0; oi < 4 && rc == TSX_HIP_OK; ++oi) {
             PairOut &o = out[oi];
-            if (!o.used || o.fd < 0) continue;
+            if (!o.used || o.w.fd < 0) continue;
             const int si = inter ? 0 : (oi & 1);
             PairSide &s = side[si];
             if ((rc = grow(st, o.out, cut[si] + 64)) != TSX_HIP_OK) break;
             if (trim)
-                rc = trim_compact(m, textbuf(s).get(), cut[si], o.off.get(), s.t.src.get(), ne, pi + PI_TOTAL + oi, o.out.get(),
+                rc = trim_compact(m, s.p.text.get(), cut[si], o.off.get(), s.t.src.get(), ne, pi + PI_TOTAL + oi, o.out.get(),
                                   (uint64_t)o.out.cap(), st);
             else
-                rc = filter_compact(m, textbuf(s).get(), cut[si], spanof(s).get(), o.off.get(), ne, pi + PI_TOTAL + oi, o.out.get(),
+                rc = filter_compact(m, s.p.text.get(), cut[si], s.p.rspan.get(), o.off.get(), ne, pi + PI_TOTAL + oi, o.out.get(),
                                     (uint64_t)o.out.cap(), st);
         }
         if (rc != TSX_HIP_OK) break;
@@ -4966,13 +4877,8 @@ static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *
         }
         for (int oi = 0; oi < 4 && rc == TSX_HIP_OK; ++oi) {
             PairOut &o = out[oi];
-            if (!o.used || o.fd < 0) continue;
-            const uint64_t total = h[PI_TOTAL + oi];
-            if (total > cut[inter ? 0 : (oi & 1)] + 1) { g_last_error = "pair output larger than its piece"; rc = TSX_HIP_EHIP; break; }
-            // (no wait: the copy that last filled it has been waited for, and written out above)
-            if (o.h_out.reserve(nullptr, total, total + total / 8 + 4096) != TSX_HIP_OK) { rc = TSX_HIP_ENOMEM; break; }
-            if (total && hipMemcpyAsync(o.h_out.get(), o.out.get(), total, hipMemcpyDeviceToHost, st) != hipSuccess) rc = TSX_HIP_EHIP;
-            o.pending = total;
+            if (!o.used || o.w.fd < 0) continue;
+            rc = o.w.stage(o.out.get(), h[PI_TOTAL + oi], cut[inter ? 0 : (oi & 1)], "pair", st);
         }
         // (the counters are per round)
         if (rc == TSX_HIP_OK && (hipMemsetAsync(pi + PI_KEPT, 0, (PI_N - PI_KEPT) * sizeof(unsigned long long), st) != hipSuccess ||
@@ -4991,7 +4897,7 @@ static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *
         const int wrc = flush();
         if (wrc != TSX_HIP_OK) rc = wrc; else g_last_error = why;
     }
-    t.bytes1 = out[0].bytes; t.bytes2 = out[1].bytes; t.bytes_single1 = out[2].bytes; t.bytes_single2 = out[3].bytes;
+    t.bytes1 = out[0].w.bytes; t.bytes2 = out[1].w.bytes; t.bytes_single1 = out[2].w.bytes; t.bytes_single2 = out[3].w.bytes;
     if (totals) *totals = t;
     return rc;
 }
