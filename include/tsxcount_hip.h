@@ -517,6 +517,57 @@ int tsx_hip_filter_median_host(tsx_hip_map *m, const char *text, size_t n, const
                                size_t chunk_bytes, uint64_t *kept_out, uint64_t *bytes_out);
 
 /*
+ * Table sizing (csrc/tsx_sketch.h; no reference counterpart -- ntCard / KmerStream in front of KMC, jellyfish grows its
+ * table): a HyperLogLog sketch of the k-mers a text WOULD put into a table, its estimate of their distinct number, and
+ * the l that holds them.  Nothing is counted and no table is read or written.
+ * ELEMENTS: every window the counting calls would count (records, lines and the base rule of tsx_hip_set_base_rule as
+ *   for tsx_hip_query_reads_*; non-ACGT bytes stand for the codes tsx_hip_encode gives them) is one element: the k-mer
+ *   x in the tsx_hip_encode layout, WK = tsx_hip_key_limbs(k) limbs; on a canonical map the lexicographically smaller of
+ *   x and rc(x) (tsx_hip_canonical_host).  NOT the table's hashed key: a sketch depends on neither l, storagebits nor
+ *   the seed, and sketches of several texts and maps combine by the register-wise maximum.  The distinct elements are
+ *   the slots the table would occupy (its key is a bijection of exactly this element).
+ * HASH: v = 0x9E3779B97F4A7C15; for t = 0 .. WK-1: v = mix64(v ^ x[t]), with the splitmix64 finaliser
+ *   mix64(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31.
+ * REGISTERS: 2^p of them, precision p = 10 .. 14; idx = v >> (64 - p), rank = 1 + clz((v << p) | 1 << (p - 1)) (1 ..
+ *   64 - p + 1), M[idx] = max(M[idx], rank).  One uint8_t per register on the host, one uint32_t on the device.
+ * ESTIMATE: m = 2^p, E = a m^2 / sum_j 2^-M[j] with a = 0.7213 / (1 + 1.079 / m); when E <= 2.5 m and V > 0 registers
+ *   are zero, E = m ln(m / V) (linear counting).  No large-range correction (a 64-bit hash).  The sum runs over a rank
+ *   histogram, ranks ascending.  Standard error 1.04 / sqrt(m): 0.81 % at p = 14.
+ * TSX_HIP_EINVAL, before any GPU call: precision outside 10 .. 14, a NULL map or regs, text NULL with n > 0, a device
+ * text that is not 16-byte aligned.  The map supplies k, the record lines, canonical and the base rule; it may be empty
+ * or filled, whole or a shard (shard_bits > 0).  Wrapped FASTA has no sketch (tsx_hip_set_record_lines takes 2 or 4).
+ *   sketch_host        text in host memory, in pieces cut at record boundaries (chunk_bytes 0 = 256 MiB, and at most
+ *                      TSX_HIP_PIECE_BYTES when that is set).  regs[2^p] is IN/OUT: the registers of the text are
+ *                      max-combined into it, so several texts accumulate into one sketch.  *totals (optional) is added
+ *                      to: kmers = the exact number of elements, records = the records read.
+ *   sketch_bgzf_host   the same for the image of a BGZF file, inflated on the device in batches (TSX_HIP_BGZF_BATCH).
+ *   sketch_device      dev_text as tsx_hip_query_reads_device takes it (windows of TSX_HIP_DEV_WINDOW); dev_regs:
+ *                      uint32_t[2^p] in device memory, in/out; dev_totals: two uint64_t {kmers, records} in device
+ *                      memory, added to, or NULL.  Queued on the stream, not waited for.
+ *   sketch_kmers_host  CPU only: the n elements kmers[i * WK ..] as given (the caller canonicalises), into regs.
+ *   sketch_estimate_host  CPU only: E of regs[2^p]; 0 for an all-zero sketch; < 0 for bad arguments (a register above
+ *                      64 - p + 1 among them).
+ *   suggest_l          CPU only: need = distinct * (1 + 5 * 1.04 / sqrt(2^p)) / (load_ppm / 1e6) -- five standard
+ *                      errors of margin at the load asked for -- and *l_out = the smallest l with 2^l >= need, at least
+ *                      4 and at most min(36, 2k - 1).  load_ppm 0 = 750000; above 900000: TSX_HIP_EINVAL.  When the
+ *                      upper bound leaves distinct / 2^l above 0.9: TSX_HIP_ERANGE, *l_out set to that bound.  (A long
+ *                      k-mer has no layout at a small l -- tsx_hip_create refuses k = 127 below l = 11: callers take the
+ *                      smallest l that creates, as tsxCount --l=auto and TSXHashMapHIP.sizedFor do.)
+ */
+typedef struct tsx_hip_sketch_totals {
+    uint64_t kmers, records;
+} tsx_hip_sketch_totals;
+int tsx_hip_sketch_host(tsx_hip_map *m, const char *text, size_t n, int precision, uint8_t *regs,
+                        tsx_hip_sketch_totals *totals, size_t chunk_bytes);
+int tsx_hip_sketch_bgzf_host(tsx_hip_map *m, const void *gz, size_t n, int precision, uint8_t *regs,
+                             tsx_hip_sketch_totals *totals);
+int tsx_hip_sketch_device(tsx_hip_map *m, const void *dev_text, size_t n, int precision, void *dev_regs, void *dev_totals,
+                          void *stream);
+int tsx_hip_sketch_kmers_host(int k, const uint64_t *kmers, size_t n, int precision, uint8_t *regs);
+double tsx_hip_sketch_estimate_host(const uint8_t *regs, int precision);
+int tsx_hip_suggest_l(int k, double distinct, int precision, uint32_t load_ppm, int *l_out);
+
+/*
  * Paired reads kept in step (csrc/tsx_pairs.h; no reference counterpart -- khmer `--paired`, Trimmomatic PE, BBDuk
  * in1/in2): the filter and the trim over mate pairs, so that the outputs line up record for record.  Records, lines,
  * k-mers, c(x) and the base rule are those of tsx_hip_query_reads_*.

@@ -89,6 +89,14 @@ class PairTotals(ctypes.Structure):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
 
 
+class SketchTotals(ctypes.Structure):
+    """tsx_hip_sketch_totals: what a sketch call saw."""
+    _fields_ = [("kmers", ctypes.c_uint64), ("records", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class DbInfo(ctypes.Structure):
     """tsx_hip_db_info: the header of a k-mer database file."""
     _fields_ = [("version", ctypes.c_uint32), ("k", ctypes.c_int32), ("l", ctypes.c_int32),
@@ -162,6 +170,89 @@ def median_rule(lower=0, upper=None, invert=False):
     if int(lower) > upper:
         raise ValueError("median range: lower %d > upper %d" % (int(lower), upper))
     return MedianRule(int(lower), upper, 1 if invert else 0, 0)
+
+
+SKETCH_PRECISIONS = range(10, 15)    # the p of a sketch: 2^p registers
+
+
+def _mix64(z):
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def sketch_registers(kmers, k, precision=14):
+    """The HyperLogLog registers of a set of k-mers, on the CPU with numpy alone (the definition the GPU sketch is tested
+    against): numpy uint8[2^precision].  kmers: encoded limbs, (n, key_limbs(k)) or flat, taken as given (canonicalise
+    first for a canonical map).  Per k-mer x: v = 0x9E3779B97F4A7C15, then v = mix64(v ^ limb) limb by limb (splitmix64's
+    finaliser); the register v >> (64 - p) is raised to 1 + the number of leading zeros of the remaining 64 - p bits (all
+    zero: 64 - p + 1)."""
+    p = int(precision)
+    if p not in SKETCH_PRECISIONS:
+        raise ValueError("sketch precision must be 10 .. 14, not %r" % (precision,))
+    wk = key_limbs(k)
+    a = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1, wk).copy()
+    if (2 * k) % 64:
+        a[:, wk - 1] &= np.uint64((1 << ((2 * k) % 64)) - 1)
+    regs = np.zeros(1 << p, dtype=np.uint8)
+    if not len(a):
+        return regs
+    with np.errstate(over="ignore"):
+        v = np.full(len(a), 0x9E3779B97F4A7C15, dtype=np.uint64)
+        for t in range(wk):
+            v = _mix64(v ^ a[:, t])
+    idx = (v >> np.uint64(64 - p)).astype(np.int64)
+    rest = v & np.uint64((1 << (64 - p)) - 1)
+    # leading zeros among 64 - p bits = (64 - p) - bit length; the bit length by halving (exact, no floating point)
+    length = np.zeros(len(a), dtype=np.int64)
+    for s in (32, 16, 8, 4, 2, 1):
+        big = (rest >> np.uint64(s)) != 0
+        length += np.where(big, s, 0)
+        rest = np.where(big, rest >> np.uint64(s), rest)
+    length += (rest != 0).astype(np.int64)
+    rank = (64 - p) - length + 1
+    np.maximum.at(regs, idx, rank.astype(np.uint8))
+    return regs
+
+
+def _sketch_precision(registers):
+    n = len(registers)
+    p = n.bit_length() - 1
+    if n != 1 << p or p not in SKETCH_PRECISIONS:
+        raise ValueError("a sketch has 2^10 .. 2^14 registers, not %d" % n)
+    return p
+
+
+def sketch_estimate(registers):
+    """The number of distinct k-mers a sketch stands for (tsx_hip_sketch_estimate_host): a float, 0.0 for an empty sketch."""
+    r = np.ascontiguousarray(registers, dtype=np.uint8)
+    L = lib()
+    e = L.tsx_hip_sketch_estimate_host(r.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _sketch_precision(r))
+    if e < 0:
+        raise TSXException(EINVAL, "a register above its highest rank")
+    return float(e)
+
+
+def suggest_l(distinct, k, load=0.75, precision=14):
+    """The l (log2 of the slot count) of the smallest table that holds `distinct` k-mers at `load` with a margin of five
+    standard errors of a sketch of 2^precision registers (tsx_hip_suggest_l): at least 4, at most min(36, 2k - 1).
+    Where that bound leaves the load above 0.9: TSXException ERANGE, its .l the bound."""
+    l = ctypes.c_int(0)
+    rc = lib().tsx_hip_suggest_l(int(k), float(distinct), int(precision), int(round(float(load) * 1e6)), ctypes.byref(l))
+    if rc == ERANGE:
+        e = TSXException(rc, "l cannot exceed %d for k=%d: %.0f distinct k-mers load it above 0.9" % (l.value, k, distinct))
+        e.l = int(l.value)
+        raise e
+    _check(rc)
+    return int(l.value)
+
+
+def merge_sketches(a, b):
+    """The sketch of the union of what two sketches of one precision saw: the register-wise maximum."""
+    a, b = np.asarray(a, dtype=np.uint8), np.asarray(b, dtype=np.uint8)
+    if a.shape != b.shape:
+        raise ValueError("sketches of different precision")
+    return np.maximum(a, b)
 
 
 PAIR_MODES = {"both": 0, "any": 1}
@@ -294,6 +385,14 @@ def lib():
     L.tsx_hip_median_reads_device.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(sz), vp]
     L.tsx_hip_median_reads_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), sz]
     L.tsx_hip_filter_median_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(MedianRule), ci, sz, u64p, u64p]
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    L.tsx_hip_sketch_host.argtypes = [vp, ctypes.c_char_p, sz, ci, u8p, ctypes.POINTER(SketchTotals), sz]
+    L.tsx_hip_sketch_bgzf_host.argtypes = [vp, vp, sz, ci, u8p, ctypes.POINTER(SketchTotals)]
+    L.tsx_hip_sketch_device.argtypes = [vp, vp, sz, ci, vp, vp, vp]
+    L.tsx_hip_sketch_kmers_host.argtypes = [ci, u64p, sz, ci, u8p]
+    L.tsx_hip_sketch_estimate_host.argtypes = [u8p, ci]
+    L.tsx_hip_sketch_estimate_host.restype = ctypes.c_double
+    L.tsx_hip_suggest_l.argtypes = [ci, ctypes.c_double, ci, ctypes.c_uint32, ctypes.POINTER(ci)]
     L.tsx_hip_filter_pairs_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(FilterRule), ci, ci,
                                             ctypes.POINTER(PairIO), sz, ctypes.POINTER(PairTotals)]
     L.tsx_hip_trim_pairs_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), ci,
@@ -792,6 +891,83 @@ class TSXHashMapHIP:
         _check(self._lib.tsx_hip_median_reads_device(self.handle, vp(text_ptr), nbytes, vp(medians_ptr), cap, ctypes.byref(n),
                                                      vp(stream) if stream else None))
         return int(n.value)
+
+    # --- table sizing -------------------------------------------------------
+    def _sketch_regs(self, precision, registers):
+        if int(precision) not in SKETCH_PRECISIONS:
+            raise ValueError("sketch precision must be 10 .. 14, not %r" % (precision,))
+        if registers is None:
+            return np.zeros(1 << int(precision), dtype=np.uint8)
+        r = np.array(registers, dtype=np.uint8)
+        if r.shape != (1 << int(precision),):
+            raise ValueError("registers: %d entries for precision %d" % (r.size, precision))
+        return r
+
+    def sketchKmers(self, text, precision=14, registers=None, chunk_bytes=0):
+        """The HyperLogLog sketch of the k-mers `text` would put into this map (tsx_hip_sketch_host): (registers, totals)
+        with registers numpy uint8[2^precision] -- those of sketch_registers over the k-mers the counting calls would
+        count -- and totals {kmers: their exact number, records}.  registers= accumulates into a copy of an existing
+        sketch.  The map gives k, the record lines, canonical and the base rule; its table is neither read nor written."""
+        r = self._sketch_regs(precision, registers)
+        b = bytes(text)
+        t = SketchTotals()
+        _check(self._lib.tsx_hip_sketch_host(self.handle, b, len(b), int(precision), r.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                             ctypes.byref(t), int(chunk_bytes)))
+        return r, t.as_dict()
+
+    def sketchKmersBgzf(self, gz, precision=14, registers=None):
+        """The same for the image of a blocked gzip (BGZF) file, inflated on the device (tsx_hip_sketch_bgzf_host)."""
+        r = self._sketch_regs(precision, registers)
+        b = bytes(gz)
+        t = SketchTotals()
+        _check_bgzf(self._lib.tsx_hip_sketch_bgzf_host(self.handle, b, len(b), int(precision),
+                                                       r.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(t)))
+        return r, t.as_dict()
+
+    def sketchKmersDevice(self, text_ptr, nbytes, regs_ptr, precision=14, totals_ptr=None, stream=None):
+        """tsx_hip_sketch_device: the sketch of a device text max-combined into uint32[2^precision] in device memory;
+        totals_ptr: two uint64 {kmers, records} in device memory, added to.  Queued, not waited for."""
+        vp = ctypes.c_void_p
+        _check(self._lib.tsx_hip_sketch_device(self.handle, vp(text_ptr), nbytes, int(precision), vp(regs_ptr),
+                                               vp(totals_ptr) if totals_ptr else None, vp(stream) if stream else None))
+
+    @classmethod
+    def _smallest(cls, iK, iStorageBits, **kw):
+        """A map of the smallest l that has a layout for iK and iStorageBits: 4, but a long k-mer needs its func bits to
+        fit four limbs (k = 127: l >= 11)."""
+        hi = min(36, 2 * iK - 1)
+        for l in range(min(4, hi), hi + 1):
+            try:
+                return cls(l, iStorageBits, iK, **kw)
+            except TSXException as e:
+                if e.code != EINVAL or l == hi:
+                    raise
+
+    @classmethod
+    def sizedFor(cls, text, iK, iStorageBits=0, load=0.75, precision=14, canonical=False, acgt_only=False, min_qual_char=None,
+                 lines=4, **kw):
+        """A map sized for `text`: the text is sketched on a minimal probe map that carries the counting mode, and the
+        map returned has the l that suggest_l gives for the estimate (at least the smallest l that has a layout for iK:
+        above 4 for k > 121 only).  Its .size_estimate is {kmers, distinct, l, load}
+        (load: the expected one, distinct / 2^l).  Nothing is counted."""
+        if lines not in (2, 4):
+            raise ValueError("lines: 4 (FASTQ) or 2 (FASTA, one sequence line per record); wrapped FASTA has no sketch")
+        dev = {n: kw[n] for n in ("device", "hash_seed") if n in kw}
+        probe = cls._smallest(iK, iStorageBits, canonical=canonical, acgt_only=acgt_only, min_qual_char=min_qual_char, **dev)
+        l_min = probe.l
+        try:
+            if lines != 4:
+                probe.set_record_lines(lines)
+            regs, tot = probe.sketchKmers(text, precision=precision)
+        finally:
+            probe.close()
+        distinct = sketch_estimate(regs)
+        l = max(l_min, suggest_l(distinct, iK, load=load, precision=precision))
+        m = cls(l, iStorageBits, iK, canonical=canonical, acgt_only=acgt_only, min_qual_char=min_qual_char, **kw)
+        if lines != 4:
+            m.set_record_lines(lines)
+        m.size_estimate = {"kmers": tot["kmers"], "distinct": distinct, "l": l, "load": distinct / float(1 << l)}
+        return m
 
     def _pairs(self, call, text1, text2, out1, out2, singles, chunk_bytes):
         """The common part of filterPairs / trimPairs: the four outputs opened (paths) or taken (fds), the call, the

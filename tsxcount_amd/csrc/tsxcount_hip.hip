@@ -14,6 +14,7 @@
 #include "tsx_fasta.h"
 #include "tsx_trim.h"
 #include "tsx_median.h"
+#include "tsx_sketch.h"
 #include "tsx_pairs.h"
 #include "tsx_own.h"
 
@@ -4062,7 +4063,7 @@ static bool rule_ok(const tsx_hip_filter_rule *r) {
 }
 
 // What a host call does first: its piece size (0: the default; `piece_cap`: at most the map's TSX_HIP_PIECE_BYTES, which
-// only the median calls honour -- DESIGN.md §3), the device, the order behind a caller's stream, the base rule, the table.
+// only the median and the sketch calls honour -- DESIGN.md §3), the device, the order behind a caller's stream, the base rule, the table.
 static int pieces_begin(tsx_hip_map *m, size_t &chunk_bytes, bool piece_cap) {
     if (!chunk_bytes) chunk_bytes = QUERY_CHUNK_DEFAULT;
     if (piece_cap && m->piece_fixed) chunk_bytes = std::min(chunk_bytes, m->piece);
@@ -4684,6 +4685,211 @@ extern "C" int tsx_hip_filter_median_host(tsx_hip_map *m, const char *text, size
     if (bytes_out) *bytes_out = 0;
     if (!median_rule_ok(rule) || !query_args_ok(m, 0, 0) || (!text && n) || fd < 0) return TSX_HIP_EINVAL;
     return median_host(m, text, n, MED_FILTER, chunk_bytes, nullptr, nullptr, 0, nullptr, rule, fd, kept_out, bytes_out);
+}
+
+// ---- table sizing: the HyperLogLog sketch of a text's k-mers, its estimate, the l that holds them (tsx_sketch.h) --
+static bool sketch_prec_ok(int precision) { return precision >= SKETCH_P_MIN && precision <= SKETCH_P_MAX; }
+
+// sketch_windows_kernel over the start positions [0, own_end) of d_text (n readable bytes), after query_line_pass.
+static int sketch_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
+                         const unsigned long long *d_line_base, int precision, uint32_t *d_regs, unsigned long long *d_kmers,
+                         hipStream_t st) {
+    if (own_end == 0) return TSX_HIP_OK;
+    const uint64_t ntiles = (own_end + TILE - 1) / TILE;
+    const size_t lds = (size_t)4 << precision;   // the workgroup's registers: two workgroups of 64 KiB + 3 KiB fit a CU's 160 KiB
+    const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 2);   // persistent: the fold is bounded by the grid
+    hipError_t attr = hipSuccess;
+    DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, {
+        auto kern = (sketch_windows_kernel<WKV, CANV, BRV>);
+        attr = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (attr == hipSuccess)
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, m->p, d_text, n, own_end, head_open,
+                               (const uint32_t *)m->d_tile.get(), ntiles, d_line_base, precision, d_regs, d_kmers, m->qmap_cur);
+    })));
+    HIP_TRY(attr);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_sketch_device(tsx_hip_map *m, const void *dev_text, size_t n, int precision, void *dev_regs,
+                                     void *dev_totals, void *stream) {
+    if (!m || !dev_regs || !sketch_prec_ok(precision) || (!dev_text && n) || ((uintptr_t)dev_text & 15) ||
+        ((uintptr_t)dev_regs & 3) || ((uintptr_t)dev_totals & 7))
+        return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    TSX_TRY(base_rule_ok(m));
+    const uint8_t *base = (const uint8_t *)dev_text;
+    unsigned long long *tot = (unsigned long long *)dev_totals;
+    unsigned long long *kmers = tot ? tot : (unsigned long long *)m->d_carry.get() + 4;   // (a word of the scratch nobody reads)
+    TSX_TRY(device_windows(m, base, n, false, st,
+                           [&](size_t off, size_t own, size_t len, int head_open, bool, const unsigned long long *d_base) {
+                               return sketch_launch(m, base + off, len, own, head_open, d_base, precision, (uint32_t *)dev_regs,
+                                                    kmers, st);
+                           }));
+    if (tot) hipLaunchKernelGGL(sketch_records_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)m->d_carry.get() + 3, tot);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// Scratch of one sketch call that works on pieces: the registers and {kmers, records} on the device, their pinned copy.
+struct SketchBufs {
+    DevBuf<uint32_t> regs;
+    DevBuf<unsigned long long> tot;
+    PinBuf<uint32_t> h_regs;             // the registers, then the two totals
+    PieceBufs p;
+    explicit SketchBufs(hipStream_t s) : p(s) {}
+    int init(int precision) {
+        const size_t nreg = (size_t)1 << precision;
+        TSX_TRY(regs.alloc(nreg * sizeof(uint32_t)));
+        TSX_TRY(tot.alloc(2 * sizeof(unsigned long long)));
+        TSX_TRY(h_regs.alloc(nreg * sizeof(uint32_t) + 2 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(regs.get(), 0, nreg * sizeof(uint32_t), p.st));
+        HIP_TRY(hipMemsetAsync(tot.get(), 0, 2 * sizeof(unsigned long long), p.st));
+        return TSX_HIP_OK;
+    }
+    // After the last piece: the registers come back once and are max-combined into the caller's, the totals added.
+    int collect(int precision, uint8_t *out, tsx_hip_sketch_totals *totals, uint64_t records) {
+        const size_t nreg = (size_t)1 << precision;
+        unsigned long long *h_tot = (unsigned long long *)(h_regs.get() + nreg);
+        HIP_TRY(hipMemcpyAsync(h_regs.get(), regs.get(), nreg * sizeof(uint32_t), hipMemcpyDeviceToHost, p.st));
+        HIP_TRY(hipMemcpyAsync(h_tot, tot.get(), sizeof(unsigned long long), hipMemcpyDeviceToHost, p.st));
+        HIP_TRY(hipStreamSynchronize(p.st));
+        for (size_t i = 0; i < nreg; ++i) out[i] = (uint8_t)std::max<uint32_t>(out[i], h_regs.get()[i]);
+        if (totals) { totals->kmers += h_tot[0]; totals->records += records; }
+        return TSX_HIP_OK;
+    }
+};
+
+// One piece: piece_front, then the sketch of its whole records [0, cut), queued and not waited for.  Not last and no
+// whole record: nrec = 0, nothing done.
+static int sketch_piece(tsx_hip_map *m, SketchBufs &b, const uint8_t *d_text, uint64_t len, bool last, int precision,
+                        hipStream_t st, uint64_t &cut, uint64_t &nrec, bool &open) {
+    TSX_TRY(piece_front(m, b.p, d_text, len, last, false, cut, nrec, open));
+    if (nrec == 0) return TSX_HIP_OK;
+    QmapScope qs(m);
+    TSX_TRY(piece_qmap(m, d_text, cut, st));
+    return sketch_launch(m, d_text, cut, cut, 0, b.p.info.get() + 4, precision, b.regs.get(), b.tot.get(), st);
+}
+
+extern "C" int tsx_hip_sketch_host(tsx_hip_map *m, const char *text, size_t n, int precision, uint8_t *regs,
+                                   tsx_hip_sketch_totals *totals, size_t chunk_bytes) {
+    if (!m || !regs || !sketch_prec_ok(precision) || (!text && n)) return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = m->stream.get();
+    SketchBufs b(st);
+    TSX_TRY(b.init(precision));
+    uint64_t rec_base = 0;
+    TSX_TRY(host_pieces(m, b.p, text, n, chunk_bytes, true, rec_base,
+        [&](const uint8_t *d_text, uint64_t len, bool last, uint64_t &cut, uint64_t &nrec, bool &open) {
+            return sketch_piece(m, b, d_text, len, last, precision, st, cut, nrec, open);
+        },
+        [&](size_t, uint64_t, uint64_t, uint64_t, bool) -> int { return TSX_HIP_OK; }));
+    return b.collect(precision, regs, totals, rec_base);
+}
+
+// The way tsx_hip_count_fastq_bgzf_host goes under a quality rule: batch by batch on the map's stream, every piece cut
+// at its last whole record, whose unfinished rest goes in front of the next batch's text (behind newlines that align the
+// piece to 16 bytes; empty lines are no lines).
+extern "C" int tsx_hip_sketch_bgzf_host(tsx_hip_map *m, const void *gz, size_t n, int precision, uint8_t *regs,
+                                        tsx_hip_sketch_totals *totals) {
+    if (!m || !regs || !sketch_prec_ok(precision) || (!gz && n)) return TSX_HIP_EINVAL;
+    BgzfIndex ix;
+    if (!bgzf_index((const uint8_t *)gz, n, ix)) { g_last_error = "not a BGZF file (no BC extra field in every gzip member)"; return TSX_HIP_EINVAL; }
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = m->stream.get();
+    join_foreign(m, false);
+    TSX_TRY(base_rule_ok(m));
+    BgzfDev dv;
+    DevBuf<uint8_t> txt, tail;
+    SketchBufs b(st);   // (last: its destructor waits for the stream before anything here is released)
+    TSX_TRY(b.init(precision));
+    TSX_TRY(b.p.init());
+    const size_t batch = bgzf_batch_bytes(), nm = ix.in_off.size();
+    uint64_t records = 0;
+    size_t r = 0;   // bytes of the carried record in `tail`
+    for (size_t m0 = 0; m0 < nm;) {
+        const size_t m1 = bgzf_next_batch(ix, m0, batch), nb = bgzf_batch_text(ix, m0, m1);
+        const bool last = m1 == nm;
+        const size_t ra = (r + 15) & ~(size_t)15, len = ra + nb;
+        TSX_TRY(grow(st, txt, len + 256));
+        uint8_t *const piece = txt.get();
+        TSX_TRY(inflate_batch((const uint8_t *)gz, n, ix, m0, m1, dv, piece + ra, st));
+        if (ra > r) HIP_TRY(hipMemsetAsync(piece, '\n', ra - r, st));
+        if (r) HIP_TRY(hipMemcpyAsync(piece + ra - r, tail.get(), r, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemsetAsync(piece + len, '\n', 256, st));
+        uint64_t cut = 0, nrec = 0;
+        bool open = false;
+        TSX_TRY(sketch_piece(m, b, piece, len, last, precision, st, cut, nrec, open));
+        records += nrec;
+        r = last ? 0 : len - (size_t)cut;
+        if (r) {
+            TSX_TRY(grow(st, tail, r));
+            HIP_TRY(hipMemcpyAsync(tail.get(), piece + cut, r, hipMemcpyDeviceToDevice, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));   // (txt is refilled next)
+        m0 = m1;
+    }
+    return b.collect(precision, regs, totals, records);
+}
+
+template <int WK>
+static void sketch_kmers(const uint64_t *kmers, size_t n, uint64_t top, int precision, uint8_t *regs) {
+    for (size_t i = 0; i < n; ++i) {
+        uint64_t x[WK];
+        for (int t = 0; t < WK; ++t) x[t] = kmers[i * WK + t];
+        x[WK - 1] &= top;
+        uint32_t idx, rank;
+        sketch_slot(sketch_hash<WK>(x), precision, idx, rank);
+        if (rank > regs[idx]) regs[idx] = (uint8_t)rank;
+    }
+}
+
+extern "C" int tsx_hip_sketch_kmers_host(int k, const uint64_t *kmers, size_t n, int precision, uint8_t *regs) {
+    if (k < 1 || k > 127 || !regs || !sketch_prec_ok(precision) || (!kmers && n)) return TSX_HIP_EINVAL;
+    const uint64_t top = ((2 * k) & 63) ? ((1ULL << ((2 * k) & 63)) - 1ULL) : ~0ULL;
+    switch ((2 * k + 63) / 64) {
+        case 1: sketch_kmers<1>(kmers, n, top, precision, regs); break;
+        case 2: sketch_kmers<2>(kmers, n, top, precision, regs); break;
+        case 3: sketch_kmers<3>(kmers, n, top, precision, regs); break;
+        default: sketch_kmers<4>(kmers, n, top, precision, regs); break;
+    }
+    return TSX_HIP_OK;
+}
+
+extern "C" double tsx_hip_sketch_estimate_host(const uint8_t *regs, int precision) {
+    if (!regs || !sketch_prec_ok(precision)) return -1.0;
+    const size_t nreg = (size_t)1 << precision;
+    const int top = 64 - precision + 1;
+    uint64_t hist[66] = {0};
+    for (size_t i = 0; i < nreg; ++i) {
+        if (regs[i] > top) return -1.0;
+        ++hist[regs[i]];
+    }
+    double sum = 0.0;   // ranks ascending: the order of the Python form
+    for (int r = 0; r <= top; ++r) sum += (double)hist[r] * std::ldexp(1.0, -r);
+    const double md = (double)nreg, alpha = 0.7213 / (1.0 + 1.079 / md);
+    double e = alpha * md * md / sum;
+    if (e <= 2.5 * md && hist[0] > 0) e = md * std::log(md / (double)hist[0]);
+    return e;
+}
+
+extern "C" int tsx_hip_suggest_l(int k, double distinct, int precision, uint32_t load_ppm, int *l_out) {
+    if (k < 1 || k > 127 || !l_out || !sketch_prec_ok(precision) || !(distinct >= 0.0) || !std::isfinite(distinct) ||
+        load_ppm > 900000u)
+        return TSX_HIP_EINVAL;
+    const double load = (load_ppm ? load_ppm : 750000u) / 1e6;
+    const double need = distinct * (1.0 + 5.0 * 1.04 / std::sqrt((double)((uint64_t)1 << precision))) / load;
+    int l = 0;
+    while (l < 64 && std::ldexp(1.0, l) < need) ++l;
+    l = std::max(4, l);
+    const int hi = std::min(36, 2 * k - 1);   // derive_layout's bound and the reference's 2k > l
+    if (l > hi) {
+        *l_out = hi;
+        return distinct / std::ldexp(1.0, hi) > 0.9 ? TSX_HIP_ERANGE : TSX_HIP_OK;
+    }
+    *l_out = l;
+    return TSX_HIP_OK;
 }
 
 // ---- paired reads: the filter and the trim over mate pairs (tsx_pairs.h) -----------------------------------------

@@ -13,6 +13,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <cstdint>
 #include <exception>
 #include <iostream>
@@ -331,6 +332,44 @@ public:
                                   const tsx_hip_trim_rule &oRule, const std::string (&sPaths)[4], bool bCheckNames = false,
                                   size_t iChunkBytes = 0) {
         return tsx_trim_pairs(m_pMap, pText1, iBytes1, pText2, iBytes2, oRule, bCheckNames, sPaths, iChunkBytes, check);
+    }
+
+    // table sizing (tsx_hip_sketch_*): the HyperLogLog registers of the k-mers a text would put into a table, max-combined
+    // into oRegs (2^iPrecision entries; an empty vector is sized and zeroed); returns the totals, added to *pTotals too.
+    // This map supplies k, the record lines, canonical and the base rule; its table is neither read nor written.
+    tsx_hip_sketch_totals sketchKmers(const char *pText, size_t iBytes, std::vector<uint8_t> &oRegs, int iPrecision = 14,
+                                      size_t iChunkBytes = 0) {
+        tsx_hip_sketch_totals t = {0, 0};
+        if (oRegs.empty() && iPrecision >= 0 && iPrecision < 31) oRegs.assign((size_t)1 << iPrecision, 0);
+        if (oRegs.size() != ((size_t)1 << (iPrecision & 31))) check(TSX_HIP_EINVAL);
+        check(tsx_hip_sketch_host(m_pMap, pText, iBytes, iPrecision, oRegs.data(), &t, iChunkBytes));
+        return t;
+    }
+    tsx_hip_sketch_totals sketchKmersBgzf(const void *pGz, size_t iBytes, std::vector<uint8_t> &oRegs, int iPrecision = 14) {
+        tsx_hip_sketch_totals t = {0, 0};
+        if (oRegs.empty() && iPrecision >= 0 && iPrecision < 31) oRegs.assign((size_t)1 << iPrecision, 0);
+        if (oRegs.size() != ((size_t)1 << (iPrecision & 31))) check(TSX_HIP_EINVAL);
+        const int rc = tsx_hip_sketch_bgzf_host(m_pMap, pGz, iBytes, iPrecision, oRegs.data(), &t);
+        if (rc == TSX_HIP_EINVAL && *tsx_hip_last_error()) throw TSXException(std::string("BGZF input: ") + tsx_hip_last_error(), rc);
+        check(rc);
+        return t;
+    }
+    // the distinct k-mers a sketch stands for (tsx_hip_sketch_estimate_host)
+    static double estimate(const std::vector<uint8_t> &oRegs) {
+        int p = 0;
+        while (p < 31 && ((size_t)1 << p) < oRegs.size()) ++p;
+        const double e = (((size_t)1 << p) == oRegs.size()) ? tsx_hip_sketch_estimate_host(oRegs.data(), p) : -1.0;
+        if (e < 0) check(TSX_HIP_EINVAL);
+        return e;
+    }
+    // the l that holds dDistinct k-mers at load dLoad with five standard errors of margin (tsx_hip_suggest_l); *pClamped:
+    // the bounds on l left the load above 0.9 (TSX_HIP_ERANGE), which throws when pClamped is null
+    static int suggestL(int iK, double dDistinct, double dLoad = 0.75, int iPrecision = 14, bool *pClamped = nullptr) {
+        int l = 0;
+        const int rc = tsx_hip_suggest_l(iK, dDistinct, iPrecision, (uint32_t)std::llround(dLoad * 1e6), &l);
+        if (pClamped) *pClamped = rc == TSX_HIP_ERANGE;
+        if (rc != TSX_HIP_ERANGE || !pClamped) check(rc);
+        return l;
     }
 
     // set operation on two tables (tsx_hip_combine): this is A, oOther is B, the result goes into the empty table oOut

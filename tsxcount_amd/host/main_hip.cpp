@@ -15,6 +15,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -67,6 +68,10 @@ struct arguments {
     uint64_t a_lower = 1, a_upper = UINT64_MAX, b_lower = 1, b_upper = UINT64_MAX;
     bool compare = false;
     bool given_k = false, given_l = false, given_s = false, given_seed = false;
+    // table sizing: --l=auto sketches --input first and counts into the l that holds its k-mers at --load-factor=F;
+    // --estimate prints that line and stops
+    bool l_auto = false, estimate = false;
+    double load_factor = 0.75;
 };
 
 static bool opt(const char *arg, const char *name, std::string &val) {
@@ -77,7 +82,8 @@ static bool opt(const char *arg, const char *name, std::string &val) {
 }
 
 static int usage() {
-    std::cerr << "Usage: tsxCount [--input=FASTQ|FASTA[.gz]] [--k=K] [--l=L] [--s=STORAGE] [--mode=HIP] [--threads=T]\n"
+    std::cerr << "Usage: tsxCount [--input=FASTQ|FASTA[.gz]] [--k=K] [--l=L|auto [--load-factor=F]] [--estimate] [--s=STORAGE]\n"
+                 "                [--mode=HIP] [--threads=T]\n"
                  "                [--check] [--checkabort] [--seed=S] [--device=D] [--format=fastq|fasta|fasta-wrapped] [--canonical]\n"
                  "                [--acgt-only] [--min-qual-char=C]\n"
                  "                [--gpus=N [--comm=rccl|copy] [--devices=a,b,...] [--exchange=merge|mini|auto]]\n"
@@ -93,6 +99,12 @@ static int usage() {
                  "                [--with=DB[,DB2,...] [--op=intersect|union|subtract|diff] [--op-count=min|max|sum|left|right]\n"
                  "                 [--a-lower=N] [--a-upper=N] [--b-lower=N] [--b-upper=N] [--compare]]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
+                 "--l=auto sizes the table itself: the input is sketched first (HyperLogLog, 2^14 registers, on the GPU), and l\n"
+                 "is the smallest table that holds the estimated distinct k-mers at load F (--load-factor, default 0.75, at most\n"
+                 "0.9) with a margin of five standard errors; it prints estimate<TAB>kmers<TAB>distinct<TAB>l<TAB>load, then counts.\n"
+                 "--estimate prints that line and stops: nothing is counted, --k is required, --l is ignored. Both take plain,\n"
+                 ".gz and BGZF input with --canonical, --acgt-only and --min-qual-char; one GPU, no --load / --with, no wrapped\n"
+                 "FASTA. l is at most min(36, 2k - 1): where that leaves the load above 0.9 a warning says so.\n"
                  "--format=fasta reads two lines per record (a header, ONE sequence line), as file names ending in .fa, .fasta\n"
                  "or .fna do. --format=fasta-wrapped reads FASTA whose sequences are wrapped over several lines (what genome and\n"
                  "assembly downloads look like): the lines of a record are joined on the GPU, k-mers across line breaks count.\n"
@@ -512,6 +524,43 @@ static int count_index(const std::string &s) {
          : s == "left" ? TSX_HIP_CNT_LEFT : s == "right" ? TSX_HIP_CNT_RIGHT : -1;
 }
 
+// --l=auto and --estimate: the input is sketched on a minimal probe map that carries its counting mode, the estimate of
+// its distinct k-mers picks l (a.l, for the count that follows), and one line says so:
+// estimate<TAB>kmers<TAB>distinct<TAB>l<TAB>load.
+static void size_input(arguments &a, const char *text, size_t n, bool bgzf) {
+    std::vector<uint8_t> regs;
+    tsx_hip_sketch_totals t;
+    // the probe map: the smallest l that has a layout (4; a long k-mer needs its func bits to fit four limbs: k = 127, l >= 11)
+    const int l_hi = std::min(36, 2 * a.k - 1);
+    int l_min = std::min(4, l_hi);
+    std::unique_ptr<TSXHashMapHIP> pProbe;
+    while (!pProbe) {
+        try {
+            pProbe.reset(new TSXHashMapHIP((uint8_t)l_min, (uint32_t)a.storagebits, (uint16_t)a.k, (uint8_t)a.threads, a.seed, a.device, 0));
+        } catch (const TSXException &e) {
+            if (e.code() != TSX_HIP_EINVAL || l_min >= l_hi) throw;
+            ++l_min;
+        }
+    }
+    if (is_fasta(a)) pProbe->setRecordLines(2);
+    if (a.canonical) pProbe->setCanonical(true);
+    if (a.acgt_only || a.min_qual_char) pProbe->setBaseRule(a.acgt_only, a.min_qual_char);
+    t = bgzf ? pProbe->sketchKmersBgzf(text, n, regs) : pProbe->sketchKmers(text, n, regs);
+    pProbe.reset();
+    const double distinct = TSXHashMapHIP::estimate(regs);
+    bool clamped = false;
+    a.l = std::max(l_min, TSXHashMapHIP::suggestL(a.k, distinct, a.load_factor, 14, &clamped));
+    const double load = distinct / std::ldexp(1.0, a.l);
+    char line[160];
+    snprintf(line, sizeof line, "estimate\t%llu\t%.0f\t%d\t%.3f", (unsigned long long)t.kmers, distinct, a.l, load);
+    std::cout << line << std::endl;
+    std::cerr << "Table sizing: about " << (unsigned long long)std::llround(distinct) << " distinct k-mers among " << t.kmers
+              << ", l=" << a.l << " (expected load " << load << ")" << std::endl;
+    if (clamped)
+        std::cerr << "Warning: l cannot exceed " << a.l << " for k=" << a.k << ": the expected load " << load
+                  << " is above 0.9, the count may end with a full table" << std::endl;
+}
+
 // "Added a total of ..." and the --check of main.cpp:224-396, for one table or a group of them
 template <typename Map>
 static int report_and_check(Map &oMap, const arguments &a, double dt, bool outputs = true) {
@@ -640,7 +689,12 @@ int main(int argc, char *argv[]) {
     for (int i = 1; i < argc; ++i) {
         std::string v;
         if (opt(argv[i], "k", v)) { a.k = atoi(v.c_str()); a.given_k = true; }
-        else if (opt(argv[i], "l", v)) { a.l = atoi(v.c_str()); a.given_l = true; }
+        else if (opt(argv[i], "l", v)) {
+            if (v == "auto") a.l_auto = true;
+            else { a.l = atoi(v.c_str()); a.given_l = true; a.l_auto = false; }
+        }
+        else if (opt(argv[i], "estimate", v)) a.estimate = true;
+        else if (opt(argv[i], "load-factor", v)) a.load_factor = atof(v.c_str());
         else if (opt(argv[i], "s", v)) { a.storagebits = atoi(v.c_str()); a.given_s = true; }
         else if (opt(argv[i], "threads", v)) a.threads = atoi(v.c_str());
         else if (opt(argv[i], "input", v)) a.input_path = v;
@@ -719,6 +773,22 @@ int main(int argc, char *argv[]) {
         else if (argv[i][0] == '-') { std::cerr << "unknown option " << argv[i] << std::endl; return usage(); }
     }
     std::transform(a.mode.begin(), a.mode.end(), a.mode.begin(), ::toupper);
+    if (a.l_auto || a.estimate) {   // what the table sizing refuses, before anything is read
+        const std::string o = a.estimate ? "--estimate" : "--l=auto";
+        std::string why;
+        if (a.estimate && !a.given_k) why = "--estimate needs --k=K: the number of distinct k-mers depends on it";
+        else if (a.input_path.empty()) why = o + " needs --input=FILE: it sketches the k-mers of the input";
+        else if (a.gpus > 1) why = o + " runs on one GPU only: the tables of a --gpus " + std::to_string(a.gpus) + " run are not sized by a sketch yet";
+        else if (!a.load.empty() || !a.with.empty())
+            why = o + " does not go with --load or --with: a database brings k-mers the sketch of --input has not seen";
+        else if (is_wrapped(a)) why = o + " does not read --format=fasta-wrapped: wrapped FASTA has no sketch yet";
+        else if (!(a.load_factor > 0.0 && a.load_factor <= 0.9)) why = "--load-factor is the load of the table " + o + " aims at: above 0, at most 0.9";
+        if (!why.empty()) {
+            std::cerr << why << std::endl;
+            return usage();
+        }
+        a.group = false;   // --gpus=1: the one table of this process
+    }
     if (a.input_path.empty() && a.load.empty()) return usage();
     // --load: the first database sets k, l, s and the seed unless they are given; every one must match the counting mode
     int overflow_l = 0;
@@ -787,7 +857,8 @@ int main(int argc, char *argv[]) {
 
     std::cout << "Running with parameters " << std::endl;
     std::cerr << "K=" << a.k << std::endl;
-    std::cerr << "L=" << a.l << std::endl;
+    if (a.l_auto || a.estimate) std::cerr << "L=auto" << std::endl;
+    else std::cerr << "L=" << a.l << std::endl;
     std::cerr << "StorageBits=" << a.storagebits << std::endl;
     std::cerr << "Check=" << (a.check ? "Yes" : "No") << std::endl;
     if (a.canonical) std::cerr << "Canonical=Yes" << std::endl;
@@ -913,6 +984,23 @@ int main(int argc, char *argv[]) {
     if (!a.save.empty() || !a.load.empty() || !a.with.empty()) a.group = false;   // --gpus=1: the one table of this process
     try {
         if (a.group) return run_group(a);
+        std::vector<char> owned;
+        const char *text = nullptr;
+        size_t n = 0;
+        void *map = nullptr;
+        bool bgzf = false, loaded = false;
+        if (a.l_auto || a.estimate) {   // the text is loaded once: the count below takes it as it is
+            if (!load_input(a.input_path, owned, text, n, map, bgzf, true)) {
+                std::cerr << "Could not read " << a.input_path << std::endl;
+                return 3;
+            }
+            loaded = true;
+            size_input(a, text, n, bgzf);
+            if (a.estimate) {
+                if (map) munmap(map, n);
+                return 0;
+            }
+        }
         std::cerr << "Creating TSXHashMap HIP" << std::endl;
         TSXHashMapHIP oMap((uint8_t)a.l, (uint32_t)a.storagebits, (uint16_t)a.k, (uint8_t)a.threads, a.seed, a.device, overflow_l);
         if (is_wrapped(a)) std::cerr << "Format=FASTA (wrapped, lines joined)" << std::endl;
@@ -920,12 +1008,7 @@ int main(int argc, char *argv[]) {
         if (a.canonical) oMap.setCanonical(true);
         if (a.acgt_only || a.min_qual_char) oMap.setBaseRule(a.acgt_only, a.min_qual_char);
         const bool wrapped = is_wrapped(a);
-        std::vector<char> owned;
-        const char *text = nullptr;
-        size_t n = 0;
-        void *map = nullptr;
-        bool bgzf = false;
-        if (!a.input_path.empty() && !load_input(a.input_path, owned, text, n, map, bgzf, true)) {
+        if (!loaded && !a.input_path.empty() && !load_input(a.input_path, owned, text, n, map, bgzf, true)) {
             std::cerr << "Could not read " << a.input_path << std::endl;
             return 3;
         }
