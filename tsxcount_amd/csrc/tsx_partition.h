@@ -1249,18 +1249,6 @@ __global__ __launch_bounds__(PART_NT) void add_hashed_kernel(TableParams p, cons
 // All lanes stay busy until the stream runs dry; the tail is one key's probe chain, not the sum of a lane's.
 constexpr int BK = 16;   // batches (of 64 keys) a wave holds in registers per pass
 
-__device__ __forceinline__ uint64_t pick_batch(const uint64_t (&B)[BK], uint32_t j) {   // j is wave-uniform
-    uint64_t v = 0;
-    switch (j) {
-        case 0: v = B[0]; break;   case 1: v = B[1]; break;   case 2: v = B[2]; break;   case 3: v = B[3]; break;
-        case 4: v = B[4]; break;   case 5: v = B[5]; break;   case 6: v = B[6]; break;   case 7: v = B[7]; break;
-        case 8: v = B[8]; break;   case 9: v = B[9]; break;   case 10: v = B[10]; break; case 11: v = B[11]; break;
-        case 12: v = B[12]; break; case 13: v = B[13]; break; case 14: v = B[14]; break; case 15: v = B[15]; break;
-        default: break;
-    }
-    return v;
-}
-
 // The batches of pass `pass` of one wave: batch j of the pass is batch t = wi + (pass*BK + j)*nw of the
 // wave group's list (`mine` keys at `base`); lane L holds key t*64 + L.
 __device__ __forceinline__ void load_batches(const uint64_t *base, uint32_t mine, uint32_t wi, uint32_t nw,
@@ -1384,7 +1372,7 @@ __global__ __launch_bounds__(1024) void build_segments_stream_kernel(TableParams
         for (uint32_t pass = 0; pass < npass; ++pass) {
             if (pass > 0) load_batches(base, mine, wi, nw, pass, lane, B);   // long lists only: not prefetched
             const uint32_t total = __builtin_amdgcn_readfirstlane(pass_total(mine, wi, nw, pass));   // (a scalar, said so)
-            uint32_t cb = 0, off = 0, taken = 0;    // wave-uniform: current batch, keys consumed of it, keys consumed in all
+            uint32_t taken = 0;    // wave-uniform: keys of the stream handed out so far
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the previous pass's reads of the ring are done
             // the batches must have arrived: the one wait for loads of this segment, spelled out so that the
             // prefetch below is issued behind it (and stays in flight), not in front of it
@@ -1429,14 +1417,14 @@ __global__ __launch_bounds__(1024) void build_segments_stream_kernel(TableParams
             };
             // ---- main phase: hand the next keys of the stream to the lanes that hold none, then probe.  After a
             // hand-out at least one lane holds a key: no exit test in here.
-            while (taken < total) {
+            auto round = [&]() {
                 const unsigned long long nm = __ballot(i == 0u);
                 if (nm) {
                     const uint32_t pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(nm >> 32),
                                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)nm, 0u));
-                    // stream position cb * 64 + off + pre, modulo the ring's 256 words (batch b sits in quarter b & 3):
+                    // stream position taken + pre, modulo the ring's 256 words (batch b sits in quarter b & 3):
                     // consecutive stream positions = consecutive words of the ring: no bank conflicts
-                    const uint64_t kf = ring[(((cb << 6) + off) + pre) & 255u];
+                    const uint64_t kf = ring[(taken + pre) & 255u];
                     const uint32_t left = total - taken;   // scalar
                     if (i == 0u && pre < left) {
                         i = 1u;
@@ -1451,16 +1439,20 @@ __global__ __launch_bounds__(1024) void build_segments_stream_kernel(TableParams
                             e0_hi = (uint32_t)(e0 >> 32);
                         }
                     }
-                    const uint32_t got = min((uint32_t)__builtin_popcountll(nm), left);
-                    taken = __builtin_amdgcn_readfirstlane(taken + got);
-                    off = __builtin_amdgcn_readfirstlane(off + got);
-                    if (off >= 64u) {   // batch cb is used up: its quarter of the ring takes batch cb + 4
-                        off -= 64u;
-                        cb = __builtin_amdgcn_readfirstlane(cb + 1u);
-                        ring[(((cb + 3u) & 3u) << 6) + lane] = pick_batch(B, cb + 3u);
-                    }
+                    taken = __builtin_amdgcn_readfirstlane(taken + min((uint32_t)__builtin_popcountll(nm), left));
                 }
                 probe();
+            };
+            // Batch-major: the batch boundary is the loop structure, so the batch registers are indexed by constants and
+            // the one counter `taken` is all the bookkeeping.  Rounds run while the wave is inside batch j; the round that
+            // crosses into batch j + 1 hands out its first keys already (they sit in the ring), then batch j's quarter of
+            // the ring takes batch j + 4.
+#pragma unroll
+            for (int j = 0; j < BK; ++j) {
+                const uint32_t lim = min((uint32_t)(j + 1) * 64u, total);
+                while (taken < lim) round();
+                if (taken >= total) break;
+                if (j + 4 < BK) ring[((uint32_t)(j & 3) << 6) + lane] = B[j + 4];
             }
             // ---- the stream is dry: the batch registers take the next segment's first batches
             if (pass + 1u == npass) {
