@@ -347,6 +347,57 @@ def test_seams_bgzf_batches(T, k, block, monkeypatch):
         a.close(); b.close()
 
 
+def long_record_text(seed=2024):
+    """About 40 short records, one record of 300 000 bases with a few qualities below '5', about 40 short records."""
+    rnd = random.Random(seed)
+
+    def rec(name, n, low):
+        qual = bytearray(b"I" * n)
+        for i in low:
+            qual[i] = ord("+")
+        return b"@%s\n%s\n+\n%s\n" % (name, bytes(rnd.choices(b"ACGT", k=n)), bytes(qual))
+
+    def short(tag):
+        return b"".join(rec(b"%s%d" % (tag, i), rnd.randint(60, 150), (rnd.randrange(60),) if i % 5 == 0 else ())
+                        for i in range(40))
+
+    return short(b"a") + rec(b"long", 300000, (7, 99999, 100010, 250000, 299990)) + short(b"b")
+
+
+@pytest.mark.gpu
+def test_bgzf_record_longer_than_a_batch(T, monkeypatch):
+    """A record that spans several of the smallest BGZF batches: the middle batches hold no whole record and are carried
+    whole under a quality rule (the count and the sketch); without the rule the long lines cross the double-buffered
+    batches.  Both give what the plain text gives on the host path, which sees the record whole."""
+    k, block = 31, 65280
+    text = long_record_text()
+    z = T.bgzf_compress(text, level=1, block=block)
+    monkeypatch.setenv("TSX_HIP_BGZF_BATCH", "1")      # clamped to the minimum, 128 KiB: two members a batch
+    monkeypatch.delenv("TSX_HIP_PIECE_BYTES", raising=False)
+    batch = 2 * block
+    nbatch = (len(text) + batch - 1) // batch
+    ends, pos = set(), 0
+    for _, _, r in records(text):
+        pos += len(r)
+        ends.add((pos - 1) // batch)
+    assert nbatch >= 5 and len(set(range(nbatch - 1)) - ends) >= 2      # middle batches without a record end
+    for mq in ("5", None):
+        kept, dropped = oracle(text, k, False, mq)
+        assert kept and bool(dropped) == bool(mq)
+        a = T.TSXHashMapHIP(21, 0, k, min_qual_char=mq)
+        b = T.TSXHashMapHIP(21, 0, k, min_qual_char=mq)
+        a.countFastq(text)
+        b.countFastqBgzf(z)
+        check_table(b, k, kept, dropped)
+        ka, ca = dump(a)
+        kb, cb = dump(b)
+        assert np.array_equal(ka, kb) and np.array_equal(ca, cb)
+        ra, ta = a.sketchKmers(text)
+        rb, tb = b.sketchKmersBgzf(z)
+        assert np.array_equal(ra, rb) and ta == tb and ta["kmers"] == sum(kept.values()), (ta, tb)
+        a.close(); b.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("k", [21, 32, 64])
 def test_canonical_and_rule_changes(T, k):

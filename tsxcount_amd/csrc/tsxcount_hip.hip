@@ -799,6 +799,10 @@ static int slab_bits(const tsx_hip_map *m) {
     if (nsegbits <= max_seg_bits() || p.wk != 1 || p.W != 1 || p.lg != p.l) return 0;
     return nsegbits - max_seg_bits();
 }
+// Whether a text of n bytes goes into the table slab by slab (count_slabs): the partitioned path where it pays off.
+static inline bool slab_build_wanted(const tsx_hip_map *m, size_t n) {
+    return slab_bits(m) && (m->path == 2 || (m->path == 0 && n * 32 >= m->lay.table_bytes));
+}
 static bool can_partition(const tsx_hip_map *m) {
     const TableParams &p = m->p;
     const int nsegbits = p.l - p.S;
@@ -1697,7 +1701,6 @@ extern "C" int tsx_hip_mini_owner_host(int k, int nranks, const uint64_t *kmers,
 // Walks n_desc packed descriptions (any GPU's), keeps the keys this shard owns and partitions them by radix level 1
 // into list set `slot` of `nslots` (slot 0 plans for est_total_keys owned keys in all).  dev_emit_sum += k-mer
 // occurrences kept.  Then tsx_hip_shard_build_l1_device.
-static int l1_supported(tsx_hip_map *m);
 // tsx_hip_shard_walk_device, and the walks of a table built slab by slab (count_slabs), canonical ones included
 static int shard_walk(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int long_desc, uint32_t slot, uint32_t nslots,
                       size_t est_total_keys, void *dev_emit_sum, void *stream) {
@@ -1939,214 +1942,74 @@ extern "C" int tsx_hip_get_timing(tsx_hip_map *m, double *line_ms, double *count
     return TSX_HIP_OK;
 }
 
-// ---- tables above 2^32 slots (l - S > 18): built slab by slab ----------------------------------------------------------
-// 1. every window of the text is DESCRIBED once (line pass + strip_desc_kernel, long descriptions: 32 bytes per 64 start
-//    positions), the descriptions of all windows stay in HBM;
-// 2. for every slab: the owner-filtered walk over every window's descriptions keeps the slab's keys and partitions them by
-//    radix level 1 (one set of sub-lists per window), then ONE level 2 + build for the slab -- a slab is to this loop what a
-//    shard is to a GPU of a multi-GPU run, and the per-slab view of the table parameters is a shard's view (l = slab bits,
-//    shard = slab number) with the table pointers moved to the slab and pos_base = its first slot.
-// The text is walked slab_count times (rolling work only, ~2 ms per 1e9 positions); every key makes its two trips once.
-static const size_t DEV_WINDOW_DEFAULT = (size_t)4 << 30;
-static size_t dev_window_bytes() {
-    size_t w = DEV_WINDOW_DEFAULT;
-    if (const char *e = getenv("TSX_HIP_DEV_WINDOW")) {  // tests exercise the window seams
-        const long long v = atoll(e);
-        if (v >= 4096) w = ((size_t)v + 15) & ~(size_t)15;
+// ==== text sources: how a text reaches the device -- host staging, BGZF batches, pieces cut at record boundaries =========
+
+// ---- host staging: two pinned and two device buffers of a piece each -----------------------------------------------------
+static int ensure_staging(tsx_hip_map *m, size_t n) {
+    const size_t bytes = std::min(m->piece, n) + STAGE_PAD + 128;
+    if (m->d_stage[1].cap() >= bytes) return TSX_HIP_OK;   // (allocated last: there when all of them are)
+    auto drop = [&] { for (int i = 0; i < 2; ++i) { m->h_stage[i].reset(); m->d_stage[i].reset(); } };
+    drop();   // grow: drop the smaller buffers first
+    int rc = m->copy_stream.get() ? TSX_HIP_OK : m->copy_stream.create();
+    for (int i = 0; i < 2 && rc == TSX_HIP_OK; ++i) {
+        if ((rc = m->h_stage[i].alloc(bytes)) == TSX_HIP_OK) rc = m->d_stage[i].alloc(bytes);
+        if (rc == TSX_HIP_OK) rc = m->stage_done[i].create();
+        if (rc == TSX_HIP_OK) rc = m->stage_in[i].create();
     }
-    return w;
+    if (rc != TSX_HIP_OK) drop();   // all four buffers or none
+    return rc;
 }
 
-// ---- base rule: the low-quality bitmap and texts cut at record boundaries (tsx_baserule.h) ------------------------
-static int query_line_pass(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open, hipStream_t st);
-static int ensure_staging(tsx_hip_map *m, size_t n);
-static void parallel_memcpy(uint8_t *dst, const char *src, size_t len);
-
-// min_qual_char reads the 4th line of a FASTQ record: FASTA tables refuse it.
-static int base_rule_ok(const tsx_hip_map *m) {
-    if (m->minq && m->p.line_mask != 3) {
-        g_last_error = "min_qual_char needs FASTQ records (4 lines): a FASTA text has no quality line";
-        return TSX_HIP_EINVAL;
+// Pageable -> pinned staging copy on several host threads: one thread moves ~10 GB/s,
+// the PCIe link ~55 GB/s.  Hardware threads - 2, at least 2 and at most 12.
+static void parallel_memcpy(uint8_t *dst, const char *src, size_t len) {
+    static const unsigned maxt = [] {   // (initialised once, also when rank threads copy at the same time)
+        const unsigned hw = std::thread::hardware_concurrency();
+        return std::min(12u, std::max(2u, hw > 2 ? hw - 2 : 2u));
+    }();
+    const size_t MIN_PER_THREAD = (size_t)8 << 20;
+    unsigned nthreads = (unsigned)std::min<size_t>(maxt, len / MIN_PER_THREAD);
+    if (nthreads <= 1) { memcpy(dst, src, len); return; }
+    std::vector<std::thread> th;
+    const size_t per = ((len / nthreads) + 4095) & ~(size_t)4095;
+    for (unsigned t = 0; t < nthreads; ++t) {
+        const size_t lo = std::min(len, (size_t)t * per), hi = (t + 1 == nthreads) ? len : std::min(len, lo + per);
+        if (hi > lo) th.emplace_back([=]() { memcpy(dst + lo, src + lo, hi - lo); });
     }
+    for (auto &x : th) x.join();
+}
+
+// The piece text[0, len) through h_stage[buf] into d_stage[buf], on stream `st`.  Queued, not waited for.
+static int stage_upload(tsx_hip_map *m, int buf, const char *text, size_t len, hipStream_t st) {
+    parallel_memcpy(m->h_stage[buf].get(), text, len);
+    HIP_TRY(hipMemcpyAsync(m->d_stage[buf].get(), m->h_stage[buf].get(), len, hipMemcpyHostToDevice, st));
     return TSX_HIP_OK;
 }
 
-// m->d_qmap.get() = the low-quality bitmap of d_text[0, n), a text that starts at a record boundary.  Uses the map's line
-// scratch (d_tile, word 0 of d_carry) and waits once, for the line count.  The scan launches get it as qmap_cur.
-static int build_qmap(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, hipStream_t st) {
-    if (n >= ((uint64_t)1 << 33)) { g_last_error = "min_qual_char: a text of 8 GiB or more"; return TSX_HIP_ERANGE; }
-    const size_t words = (size_t)(n + 15) / 16 + 16;
-    int rc = grow(st, m->d_qmap, words * 2);
-    if (rc != TSX_HIP_OK) return rc;
-    HIP_TRY(hipMemsetAsync(m->d_qmap.get(), 0, words * 2, st));
-    if (n == 0) return TSX_HIP_OK;
-    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-    if ((rc = query_line_pass(m, d_text, n, n, 0, st)) != TSX_HIP_OK) return rc;
-    uint32_t lines = 0;
-    HIP_TRY(hipMemcpyAsync(&lines, m->d_carry.get(), sizeof lines, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t nrec = (uint64_t)lines / 4 + 1, ntiles = (n + TILE - 1) / TILE;
-    if ((rc = grow(st, m->d_qrec, (size_t)nrec * QR_N * 8)) != TSX_HIP_OK) return rc;
-    HIP_TRY(hipMemsetAsync(m->d_qrec.get(), 0, (size_t)nrec * QR_N * 8, st));
-    hipLaunchKernelGGL(qual_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
-                       d_text, n, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), m->d_qrec.get(), nrec);
-    hipLaunchKernelGGL(qual_bits_kernel, dim3(grid_for(m, nrec * 16, 8)), dim3(NT), 0, st, d_text,
-                       (const unsigned long long *)m->d_qrec.get(), nrec, m->minq, m->d_qmap.get());
-    HIP_TRY(hipGetLastError());
-    return TSX_HIP_OK;
-}
-
-// qmap_cur is set only for the launches of one call: the rule may change between calls.
-struct QmapScope {
-    tsx_hip_map *m;
-    explicit QmapScope(tsx_hip_map *mm) : m(mm) {}
-    ~QmapScope() { m->qmap_cur = nullptr; }
-};
-
-// One piece d[0, len) of a text cut at record boundaries (a quality rule): where its last whole record ends (cut; the
-// whole piece when last; 0 when it holds no whole record), then the bitmap and the count of [0, cut).  Waits for the cut.
-static int count_record_piece(tsx_hip_map *m, const uint8_t *d, uint64_t len, bool last, hipStream_t st, uint64_t &cut) {
-    cut = last ? len : 0;
-    if (len == 0) return TSX_HIP_OK;
-    int rc;
-    if (!last) {
-        if ((rc = grow(st, m->d_qrec, 64)) != TSX_HIP_OK) return rc;
-        unsigned long long *info = m->d_qrec.get();   // (read back before build_qmap reuses it)
-        const uint64_t ntiles = (len + TILE - 1) / TILE;
-        HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-        HIP_TRY(hipMemsetAsync(info, 0, 4 * sizeof(unsigned long long), st));
-        if ((rc = query_line_pass(m, d, len, len, 0, st)) != TSX_HIP_OK) return rc;
-        hipLaunchKernelGGL(record_scan_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
-                           d, len, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), m->p.line_mask + 1, 0,
-                           info, (unsigned long long *)nullptr, (uint64_t)0);
-        HIP_TRY(hipGetLastError());
-        unsigned long long h[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(h, info, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        cut = h[1] ? h[0] : 0;
-        if (cut == 0) return TSX_HIP_OK;
-    }
-    if ((rc = build_qmap(m, d, cut, st)) != TSX_HIP_OK) return rc;
-    QmapScope qs(m);
-    m->qmap_cur = m->d_qmap.get();
-    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-    return run_fastq_piece(m, d, cut, cut, 0, st);
-}
-
-// tsx_hip_count_fastq_host under a quality rule: pieces of m->piece bytes cut at record boundaries, one at a time; the
-// next piece starts where the last whole record of this one ends.  A record longer than a piece: ERANGE.
-static int count_host_records(tsx_hip_map *m, const char *text, size_t n) {
-    int rc = ensure_staging(m, n);
-    if (rc != TSX_HIP_OK) return rc;
+// The driver of the host count calls without a quality rule: the text in pieces that own `piece` start positions and
+// carry `halo` more bytes, through the two staging buffers in turn.  Three legs overlap: this piece's host copy, the
+// previous piece's H2D copy (its own stream) and the kernels of the piece before that, which
+//   per_piece(d_piece, len, own, head_open)      queues on the map's stream (head_open: the piece starts inside a line).
+// Waits for the table when the last piece is queued (tsx_hip_sync).
+template <class PerPiece>
+static int staged_pieces(tsx_hip_map *m, const char *text, size_t n, size_t piece, size_t halo, PerPiece per_piece) {
+    TSX_TRY(ensure_staging(m, n));
     hipStream_t st = m->stream.get();
-    for (size_t off = 0; off < n;) {
-        const size_t len = std::min(m->piece, n - off);
-        const bool last = off + len == n;
-        parallel_memcpy(m->h_stage[0].get(), text + off, len);
-        HIP_TRY(hipMemcpyAsync(m->d_stage[0].get(), m->h_stage[0].get(), len, hipMemcpyHostToDevice, st));
-        uint64_t cut = 0;
-        if ((rc = count_record_piece(m, m->d_stage[0].get(), len, last, st, cut)) != TSX_HIP_OK) return rc;
-        if (cut == 0) {
-            g_last_error = "min_qual_char: a record longer than a host piece (" + std::to_string(m->piece) + " bytes)";
-            return TSX_HIP_ERANGE;
-        }
-        HIP_TRY(hipStreamSynchronize(st));   // (the staging buffers are reused by the next piece)
-        off += cut;
+    int buf = 0;
+    bool used[2] = {false, false};
+    for (size_t off = 0; off < n; off += piece, buf ^= 1) {
+        const size_t own = std::min(piece, n - off);
+        const size_t len = std::min(own + halo, n - off);
+        if (used[buf]) HIP_TRY(hipEventSynchronize(m->stage_done[buf].get()));
+        TSX_TRY(stage_upload(m, buf, text + off, len, m->copy_stream.get()));
+        HIP_TRY(hipEventRecord(m->stage_in[buf].get(), m->copy_stream.get()));
+        HIP_TRY(hipStreamWaitEvent(st, m->stage_in[buf].get(), 0));
+        const int head_open = (off > 0 && text[off - 1] != '\n') ? 1 : 0;
+        TSX_TRY(per_piece((const uint8_t *)m->d_stage[buf].get(), len, own, head_open));
+        HIP_TRY(hipEventRecord(m->stage_done[buf].get(), st));
+        used[buf] = true;
     }
     return tsx_hip_sync(m);
-}
-
-static int count_slabs(tsx_hip_map *m, const uint8_t *base, size_t n, hipStream_t st, const uint16_t *qmap) {
-    const int sb = slab_bits(m);
-    const uint32_t nslab = 1u << sb;
-    const size_t halo = (size_t)m->p.k - 1, WIN = dev_window_bytes();
-    const uint32_t nwin = (uint32_t)std::max<size_t>(1, (n + WIN - 1) / WIN);
-    // descriptions of all windows, back to back (window w at word offset doff[w] of 32-byte descriptions)
-    std::vector<size_t> doff(nwin + 1, 0);
-    for (uint32_t w = 0; w < nwin; ++w) doff[w + 1] = doff[w] + std::min(WIN, n - (size_t)w * WIN) / 64 + 4096;
-    // (scratch of the map, grown on demand: allocating and freeing gigabytes per call costs more than the kernels)
-    int rc = grow(st, m->d_slabdesc, doff[nwin] * 32 + (size_t)(nwin + 1) * 8);
-    if (rc != TSX_HIP_OK) return rc;
-    uint4 *d_desc = reinterpret_cast<uint4 *>(m->d_slabdesc.get());
-    unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(m->d_slabdesc.get() + doff[nwin] * 32);
-    auto done = [&](int code) { m->ev_open.clear(); return code; };
-    if (hipMemsetAsync(d_cnt, 0, (size_t)(nwin + 1) * 8, st) != hipSuccess) return done(TSX_HIP_EHIP);
-    for (uint32_t w = 0; w < nwin && rc == TSX_HIP_OK; ++w) {
-        const size_t off = (size_t)w * WIN, own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
-        DescOut dsc;
-        dsc.out = d_desc + doff[w] * 2; dsc.cap = doff[w + 1] - doff[w]; dsc.count = d_cnt + w; dsc.sum = d_cnt + nwin; dsc.long_desc = 1;
-        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;   // (windows start at multiples of 16)
-        rc = run_fastq_piece(m, base + off, len, own, off > 0 ? -1 : 0, st, ShardOut(), HotOut(), dsc);
-    }
-    m->qmap_cur = nullptr;
-    if (rc != TSX_HIP_OK) return done(rc);
-    std::vector<unsigned long long> cnt(nwin + 1);
-    if (hipMemcpyAsync(cnt.data(), d_cnt, (size_t)(nwin + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) return done(TSX_HIP_EHIP);
-    m->ev_open.clear();   // (the description calls queued timing tuples for a sharded build that never comes)
-    const uint64_t kmers = cnt[nwin];
-    if (kmers == 0) return done(TSX_HIP_OK);
-    const TableParams whole = m->p;
-    const bool fresh = m->fresh;
-    const size_t est = (size_t)(kmers / nslab + kmers / nslab / 8) + 65536;
-    for (uint32_t s = 0; s < nslab && rc == TSX_HIP_OK; ++s) {
-        TableParams &v = m->p;     // the slab's view
-        v = whole;
-        v.l = whole.l - sb;
-        v.slot_mask = (1ULL << v.l) - 1ULL;
-        v.shard = s;
-        v.pos_base = (uint64_t)s << v.l;
-        v.table = whole.table + ((uint64_t)s << v.l);
-        v.seg_dirty = whole.seg_dirty + ((uint64_t)s << (v.l - v.S));
-        m->fresh = fresh;
-        Event *ev = nullptr;
-        if (m->timing) {
-            if ((rc = next_timing_events(m, ev)) != TSX_HIP_OK) break;
-            for (int i = 0; i < 4; ++i) if (hipEventRecord(ev[i].get(), st) != hipSuccess) rc = TSX_HIP_EHIP;
-        }
-        for (uint32_t w = 0; w < nwin && rc == TSX_HIP_OK; ++w)
-            rc = shard_walk(m, d_desc + doff[w] * 2, (size_t)cnt[w], 1, w, nwin, est, nullptr, st);
-        if (rc == TSX_HIP_OK) {
-            if (!m->sh_pl || !m->sh_pl->fused) rc = TSX_HIP_EINVAL;
-            else rc = run_partition_build(m, *m->sh_pl, nullptr, nullptr, 0, st, ev);
-        }
-        if (rc == TSX_HIP_OK && ev && hipEventRecord(ev[7].get(), st) != hipSuccess) rc = TSX_HIP_EHIP;
-    }
-    m->p = whole;
-    if (rc == TSX_HIP_OK) m->fresh = false;
-    return done(rc);
-}
-
-// Device texts are processed in windows so that the partition scratch (about
-// 10 bytes per text byte) stays bounded; windows overlap by the k-1 byte halo
-// exactly like the host pieces.
-extern "C" int tsx_hip_count_fastq_device(tsx_hip_map *m, const void *dev_text, size_t n, void *stream) {
-    if (!m || (!dev_text && n) || ((uintptr_t)dev_text & 15)) return TSX_HIP_EINVAL;
-    if (m->p.lg != m->p.l) return TSX_HIP_EINVAL;   // a shard: keys of other owners must travel (shard_scan / shard_build)
-    if (n) m->used = true;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
-    const uint8_t *base = (const uint8_t *)dev_text;
-    // a quality rule: the bitmap of the whole (resident) text, read by each window at its offset
-    int rcq = base_rule_ok(m);
-    if (rcq == TSX_HIP_OK && m->minq) rcq = build_qmap(m, base, n, st);
-    if (rcq != TSX_HIP_OK) return rcq;
-    const uint16_t *qmap = m->minq ? m->d_qmap.get() : nullptr;
-    QmapScope qs(m);
-    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));
-    const size_t halo = (size_t)m->p.k - 1;
-    const size_t DEV_WINDOW = dev_window_bytes();
-    if (slab_bits(m) && (m->path == 2 || (m->path == 0 && n * 32 >= m->lay.table_bytes))) return count_slabs(m, base, n, st, qmap);
-    for (size_t off = 0; off < n || off == 0; off += DEV_WINDOW) {
-        const size_t own = std::min(DEV_WINDOW, n - off);
-        const size_t len = std::min(own + halo, n - off);
-        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;   // (windows start at multiples of 16)
-        // whether the previous window ends inside a line is read on the device (the byte in front of this one)
-        int rc = run_fastq_piece(m, base + off, len, own, off > 0 ? -1 : 0, st);
-        if (rc != TSX_HIP_OK) return rc;
-        if (n == 0) break;
-    }
-    return TSX_HIP_OK;
 }
 
 // ---- blocked gzip (BGZF) input: members found on the host, inflated on the device (tsx_inflate.h) ---------
@@ -2215,12 +2078,28 @@ static size_t bgzf_batch_bytes() {
     if (const char *e = getenv("TSX_HIP_BGZF_BATCH")) { const long long x = atoll(e); if (x > 0) v = (size_t)x; }
     return std::max<size_t>(v, (size_t)128 << 10);
 }
-// [m0, m1): the next batch from member m0 on -- members while the text stays within `batch` (or below 4 KiB)
-static size_t bgzf_next_batch(const BgzfIndex &ix, size_t m0, size_t batch) {
-    size_t m1 = m0, acc = 0;
-    while (m1 < ix.in_off.size() && (m1 == m0 || acc < 4096 || acc + ix.out_len[m1] <= batch)) acc += ix.out_len[m1++];
-    return m1;
-}
+// The batches of a file, in order: [m0, m1) is the current one -- members from m0 on while the text stays within `batch`
+// bytes (or below 4 KiB).  for (BgzfBatches b(ix, batch); !b.done(); b.next()) ...
+struct BgzfBatches {
+    const BgzfIndex &ix;
+    size_t batch, m0 = 0, m1 = 0;
+    BgzfBatches(const BgzfIndex &x, size_t bytes) : ix(x), batch(bytes) { m1 = end_from(0); }
+    size_t end_from(size_t a) const {
+        size_t b = a, acc = 0;
+        while (b < ix.in_off.size() && (b == a || acc < 4096 || acc + ix.out_len[b] <= batch)) acc += ix.out_len[b++];
+        return b;
+    }
+    bool done() const { return m0 == ix.in_off.size(); }
+    bool first() const { return m0 == 0; }
+    bool last() const { return m1 == ix.in_off.size(); }
+    size_t text() const { return (size_t)((m1 < ix.out_off.size() ? ix.out_off[m1] : ix.text_bytes) - ix.out_off[m0]); }   // its bytes of text
+    void next() { m0 = m1; m1 = end_from(m0); }
+    size_t biggest() const {   // the text of the largest batch of the file
+        size_t v = 0;
+        for (BgzfBatches b(ix, batch); !b.done(); b.next()) v = std::max(v, b.text());
+        return v;
+    }
+};
 
 // Inflates members [m0, m1) of gz: the text of member m0 starts at d_out[0].  Waits for the kernel and checks
 // every member's status (stored / fixed / dynamic blocks decoded, ISIZE and CRC-32 right).
@@ -2282,10 +2161,6 @@ static int inflate_batch(const uint8_t *gz, size_t n, const BgzfIndex &ix, size_
     return TSX_HIP_OK;
 }
 
-static inline size_t bgzf_batch_text(const BgzfIndex &ix, size_t m0, size_t m1) {
-    return (size_t)((m1 < ix.out_off.size() ? ix.out_off[m1] : ix.text_bytes) - ix.out_off[m0]);
-}
-
 extern "C" int tsx_hip_inflate_bgzf_host(int device, const void *gz, size_t n, void *out_host, size_t out_cap,
                                          size_t *out_bytes) {
     if ((!gz && n) || !out_bytes) return TSX_HIP_EINVAL;
@@ -2296,16 +2171,342 @@ extern "C" int tsx_hip_inflate_bgzf_host(int device, const void *gz, size_t n, v
     HIP_TRY(hipSetDevice(device));
     BgzfDev dv;
     DevBuf<uint8_t> d_out;
-    const size_t batch = bgzf_batch_bytes();
-    for (size_t m0 = 0; m0 < ix.in_off.size();) {
-        const size_t m1 = bgzf_next_batch(ix, m0, batch), nb = bgzf_batch_text(ix, m0, m1);
+    for (BgzfBatches b(ix, bgzf_batch_bytes()); !b.done(); b.next()) {
+        const size_t nb = b.text();
         TSX_TRY(grow((hipStream_t) nullptr, d_out, nb + 256));
-        TSX_TRY(inflate_batch((const uint8_t *)gz, n, ix, m0, m1, dv, d_out.get(), nullptr));
-        if (nb && hipMemcpy((uint8_t *)out_host + ix.out_off[m0], d_out.get(), nb, hipMemcpyDeviceToHost) != hipSuccess) {
+        TSX_TRY(inflate_batch((const uint8_t *)gz, n, ix, b.m0, b.m1, dv, d_out.get(), nullptr));
+        if (nb && hipMemcpy((uint8_t *)out_host + ix.out_off[b.m0], d_out.get(), nb, hipMemcpyDeviceToHost) != hipSuccess) {
             g_last_error = "hipMemcpy of the inflated text failed";
             return TSX_HIP_EHIP;
         }
-        m0 = m1;
+    }
+    return TSX_HIP_OK;
+}
+
+// ---- pieces cut at record boundaries, and the base rule's low-quality bitmap over them (tsx_baserule.h) -------------------
+// The line passes of run_fastq_piece (tile line ends, then their exclusive scan from *d_carry) over [0, own_end).
+static int query_line_pass(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open, hipStream_t st) {
+    const uint64_t ntiles = (own_end + TILE - 1) / TILE;
+    TSX_TRY(ensure_tiles(m, ntiles, st));
+    const int g1 = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8);
+    hipLaunchKernelGGL(line_count_kernel, dim3(g1), dim3(NT), 0, st, d_text, n, own_end, head_open, m->d_tile.get(), ntiles);
+    const uint64_t nchunks = (ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    uint32_t *chunk = m->d_tile.get() + m->tile_cap;
+    hipLaunchKernelGGL(line_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const uint32_t *)m->d_tile.get(),
+                       ntiles, chunk);
+    hipLaunchKernelGGL(line_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, m->d_carry.get());
+    hipLaunchKernelGGL(line_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, m->d_tile.get(), ntiles,
+                       (const uint32_t *)chunk);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// min_qual_char reads the 4th line of a FASTQ record: FASTA tables refuse it.
+static int base_rule_ok(const tsx_hip_map *m) {
+    if (m->minq && m->p.line_mask != 3) {
+        g_last_error = "min_qual_char needs FASTQ records (4 lines): a FASTA text has no quality line";
+        return TSX_HIP_EINVAL;
+    }
+    return TSX_HIP_OK;
+}
+
+// m->d_qmap.get() = the low-quality bitmap of d_text[0, n), a text that starts at a record boundary.  Uses the map's line
+// scratch (d_tile, word 0 of d_carry) and waits once, for the line count.  The scan launches get it as qmap_cur.
+static int build_qmap(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, hipStream_t st) {
+    if (n >= ((uint64_t)1 << 33)) { g_last_error = "min_qual_char: a text of 8 GiB or more"; return TSX_HIP_ERANGE; }
+    const size_t words = (size_t)(n + 15) / 16 + 16;
+    int rc = grow(st, m->d_qmap, words * 2);
+    if (rc != TSX_HIP_OK) return rc;
+    HIP_TRY(hipMemsetAsync(m->d_qmap.get(), 0, words * 2, st));
+    if (n == 0) return TSX_HIP_OK;
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
+    if ((rc = query_line_pass(m, d_text, n, n, 0, st)) != TSX_HIP_OK) return rc;
+    uint32_t lines = 0;
+    HIP_TRY(hipMemcpyAsync(&lines, m->d_carry.get(), sizeof lines, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t nrec = (uint64_t)lines / 4 + 1, ntiles = (n + TILE - 1) / TILE;
+    if ((rc = grow(st, m->d_qrec, (size_t)nrec * QR_N * 8)) != TSX_HIP_OK) return rc;
+    HIP_TRY(hipMemsetAsync(m->d_qrec.get(), 0, (size_t)nrec * QR_N * 8, st));
+    hipLaunchKernelGGL(qual_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
+                       d_text, n, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), m->d_qrec.get(), nrec);
+    hipLaunchKernelGGL(qual_bits_kernel, dim3(grid_for(m, nrec * 16, 8)), dim3(NT), 0, st, d_text,
+                       (const unsigned long long *)m->d_qrec.get(), nrec, m->minq, m->d_qmap.get());
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// qmap_cur is set only for the launches of one call: the rule may change between calls.
+struct QmapScope {
+    tsx_hip_map *m;
+    explicit QmapScope(tsx_hip_map *mm) : m(mm) {}
+    ~QmapScope() { m->qmap_cur = nullptr; }
+};
+
+// Scratch common to the calls that work on a text piece by piece: the piece on the device, its record spans (for the
+// calls that cut by them), the words the scans and the filters report in, their pinned copy.  The scratch of a call
+// (QueryBufs, TrimBufs, MedianBufs) embeds it BEHIND its own buffers: the destructor here waits for the stream before
+// any of them is released.
+struct PieceBufs {
+    DevBuf<uint8_t> text;
+    DevBuf<unsigned long long> rspan;              // record spans
+    DevBuf<unsigned long long> info;               // cut, records, open, total, line base (0), kept; the trim: bases in, bases kept
+    PinBuf<unsigned long long> h_info;
+    Event ev;                                      // info[3..] has been copied back
+    hipStream_t st;
+    explicit PieceBufs(hipStream_t s) : st(s) {}
+    ~PieceBufs() { (void)hipStreamSynchronize(st); }   // nothing queued may outlive the buffers
+    int init() {
+        TSX_TRY(info.alloc(8 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(info.get(), 0, 8 * sizeof(unsigned long long), st));
+        TSX_TRY(h_info.alloc(8 * sizeof(unsigned long long)));
+        return ev.create();
+    }
+};
+
+// The scan half of a piece [0, len) of text in device memory that starts at a record boundary: the line pass and the
+// record scan into info[0..2] (cut, records, open), with the record spans when `span` is given.  Queued, not waited for.
+static int piece_scan(tsx_hip_map *m, const uint8_t *d_text, uint64_t len, bool last, unsigned long long *info,
+                      DevBuf<unsigned long long> *span, hipStream_t st) {
+    const uint32_t lpr = m->p.line_mask + 1;
+    const uint64_t ntiles = (len + TILE - 1) / TILE, span_cap = len / (2 * lpr) + 2;
+    int rc;
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
+    if ((rc = query_line_pass(m, d_text, len, len, 0, st)) != TSX_HIP_OK) return rc;
+    if (span && (rc = grow(st, *span, span_cap * 16)) != TSX_HIP_OK) return rc;
+    hipLaunchKernelGGL(record_scan_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
+                       d_text, len, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), lpr, last ? 1 : 0,
+                       info, span ? span->get() : (unsigned long long *)nullptr, span ? span_cap : (uint64_t)0);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// The front end of every piece [0, len) of text in device memory that starts at a record boundary: piece_scan (the
+// spans in p.rspan when `spans`), then the ONE wait of a piece, for where its last whole record ends, its records and
+// whether the last one lacks its '\n'.  An empty piece: nothing.
+static int piece_front(tsx_hip_map *m, PieceBufs &p, const uint8_t *d_text, uint64_t len, bool last, bool spans, uint64_t &cut,
+                       uint64_t &nrec, bool &open) {
+    cut = nrec = 0; open = false;
+    if (len == 0) return TSX_HIP_OK;
+    TSX_TRY(piece_scan(m, d_text, len, last, p.info.get(), spans ? &p.rspan : nullptr, p.st));
+    const unsigned long long *h_info = p.h_info.get();
+    HIP_TRY(hipMemcpyAsync(p.h_info.get(), p.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, p.st));
+    HIP_TRY(hipStreamSynchronize(p.st));
+    cut = h_info[0]; nrec = h_info[1]; open = h_info[2] != 0;
+    return TSX_HIP_OK;
+}
+
+// A quality rule: the bitmap of the whole records d_text[0, cut) for the launches that follow (its line pass over
+// [0, cut) rewrites d_tile with the same values).  The caller holds a QmapScope.
+static int piece_qmap(tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, hipStream_t st) {
+    if (!m->minq) return TSX_HIP_OK;
+    TSX_TRY(build_qmap(m, d_text, cut, st));
+    m->qmap_cur = m->d_qmap.get();
+    return TSX_HIP_OK;
+}
+
+// The text of a BGZF file in pieces cut at record boundaries, batch by batch on `st`.  The unfinished last record of a
+// batch is carried into the next one instead of a k-1 byte halo: the batch is inflated behind it, behind newlines that
+// align the piece to 16 bytes (empty lines are no lines), and 256 newlines follow the text.  Then
+//   work(piece, len, last, cut)      queues the call's work on the whole records piece[0, cut) and waits once, for the cut
+// (the whole piece when last; 0 when the piece holds no whole record: it is carried whole).  What lies behind the cut is
+// the next carry; more than carry_max bytes of it (only a quality-rule count sets a limit): ERANGE.  On an inflate error
+// the work of the batches before it stands.  Nothing queued outlives the buffers: every way out waits for the stream.
+template <class Work>
+static int bgzf_record_pieces(const uint8_t *gz, size_t n, const BgzfIndex &ix, size_t carry_max, hipStream_t st, Work work) {
+    BgzfDev dv;
+    DevBuf<uint8_t> txt, tail;
+    SyncAtExit wait(st);
+    size_t r = 0;   // bytes of the carried record in `tail`
+    for (BgzfBatches b(ix, bgzf_batch_bytes()); !b.done(); b.next()) {
+        const size_t ra = (r + 15) & ~(size_t)15, len = ra + b.text();
+        TSX_TRY(grow(st, txt, len + 256));
+        uint8_t *const piece = txt.get();
+        TSX_TRY(inflate_batch(gz, n, ix, b.m0, b.m1, dv, piece + ra, st));
+        if (ra > r) HIP_TRY(hipMemsetAsync(piece, '\n', ra - r, st));
+        if (r) HIP_TRY(hipMemcpyAsync(piece + ra - r, tail.get(), r, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemsetAsync(piece + len, '\n', 256, st));
+        uint64_t cut = 0;
+        TSX_TRY(work(piece, (uint64_t)len, b.last(), cut));
+        r = b.last() ? 0 : len - (size_t)cut;
+        if (r > carry_max) {
+            g_last_error = "min_qual_char: a record longer than " + std::to_string(carry_max) + " bytes in a BGZF file";
+            return TSX_HIP_ERANGE;
+        }
+        if (r) {
+            TSX_TRY(grow(st, tail, r));
+            HIP_TRY(hipMemcpyAsync(tail.get(), piece + cut, r, hipMemcpyDeviceToDevice, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));   // (txt is refilled next)
+    }
+    return TSX_HIP_OK;
+}
+
+// ==== counting: a text into the table ======================================================================================
+
+// ---- tables above 2^32 slots (l - S > 18): built slab by slab ----------------------------------------------------------
+// 1. every window of the text is DESCRIBED once (line pass + strip_desc_kernel, long descriptions: 32 bytes per 64 start
+//    positions), the descriptions of all windows stay in HBM;
+// 2. for every slab: the owner-filtered walk over every window's descriptions keeps the slab's keys and partitions them by
+//    radix level 1 (one set of sub-lists per window), then ONE level 2 + build for the slab -- a slab is to this loop what a
+//    shard is to a GPU of a multi-GPU run, and the per-slab view of the table parameters is a shard's view (l = slab bits,
+//    shard = slab number) with the table pointers moved to the slab and pos_base = its first slot.
+// The text is walked slab_count times (rolling work only, ~2 ms per 1e9 positions); every key makes its two trips once.
+static const size_t DEV_WINDOW_DEFAULT = (size_t)4 << 30;
+static size_t dev_window_bytes() {
+    size_t w = DEV_WINDOW_DEFAULT;
+    if (const char *e = getenv("TSX_HIP_DEV_WINDOW")) {  // tests exercise the window seams
+        const long long v = atoll(e);
+        if (v >= 4096) w = ((size_t)v + 15) & ~(size_t)15;
+    }
+    return w;
+}
+
+// ---- a quality rule on a host text: counted piece by piece, cut at record boundaries ------------------------------------
+// One piece d[0, len) of a text cut at record boundaries (a quality rule): where its last whole record ends (cut; the
+// whole piece when last; 0 when it holds no whole record), then the bitmap and the count of [0, cut).  Waits for the cut.
+static int count_record_piece(tsx_hip_map *m, const uint8_t *d, uint64_t len, bool last, hipStream_t st, uint64_t &cut) {
+    cut = last ? len : 0;
+    if (len == 0) return TSX_HIP_OK;
+    if (!last) {
+        TSX_TRY(grow(st, m->d_qrec, 64));
+        unsigned long long *info = m->d_qrec.get();   // (read back before build_qmap reuses it)
+        TSX_TRY(piece_scan(m, d, len, false, info, nullptr, st));
+        unsigned long long h[2] = {0, 0};
+        HIP_TRY(hipMemcpyAsync(h, info, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        cut = h[1] ? h[0] : 0;
+        if (cut == 0) return TSX_HIP_OK;
+    }
+    QmapScope qs(m);
+    TSX_TRY(piece_qmap(m, d, cut, st));
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
+    return run_fastq_piece(m, d, cut, cut, 0, st);
+}
+
+// tsx_hip_count_fastq_host under a quality rule: pieces of m->piece bytes cut at record boundaries, one at a time (where
+// a piece starts depends on the cut of the one before: nothing to overlap); the next piece starts where the last whole
+// record of this one ends.  A record longer than a piece: ERANGE.
+static int count_host_records(tsx_hip_map *m, const char *text, size_t n) {
+    TSX_TRY(ensure_staging(m, n));
+    hipStream_t st = m->stream.get();
+    for (size_t off = 0; off < n;) {
+        const size_t len = std::min(m->piece, n - off);
+        const bool last = off + len == n;
+        TSX_TRY(stage_upload(m, 0, text + off, len, st));
+        uint64_t cut = 0;
+        TSX_TRY(count_record_piece(m, m->d_stage[0].get(), len, last, st, cut));
+        if (cut == 0) {
+            g_last_error = "min_qual_char: a record longer than a host piece (" + std::to_string(m->piece) + " bytes)";
+            return TSX_HIP_ERANGE;
+        }
+        HIP_TRY(hipStreamSynchronize(st));   // (the staging buffers are reused by the next piece)
+        off += cut;
+    }
+    return tsx_hip_sync(m);
+}
+
+// ---- FASTQ: the slab-by-slab build (above), device texts in windows, BGZF batches, host pieces ----------------------------
+static int count_slabs(tsx_hip_map *m, const uint8_t *base, size_t n, hipStream_t st, const uint16_t *qmap) {
+    const int sb = slab_bits(m);
+    const uint32_t nslab = 1u << sb;
+    const size_t halo = (size_t)m->p.k - 1, WIN = dev_window_bytes();
+    const uint32_t nwin = (uint32_t)std::max<size_t>(1, (n + WIN - 1) / WIN);
+    // descriptions of all windows, back to back (window w at word offset doff[w] of 32-byte descriptions)
+    std::vector<size_t> doff(nwin + 1, 0);
+    for (uint32_t w = 0; w < nwin; ++w) doff[w + 1] = doff[w] + std::min(WIN, n - (size_t)w * WIN) / 64 + 4096;
+    // (scratch of the map, grown on demand: allocating and freeing gigabytes per call costs more than the kernels)
+    int rc = grow(st, m->d_slabdesc, doff[nwin] * 32 + (size_t)(nwin + 1) * 8);
+    if (rc != TSX_HIP_OK) return rc;
+    uint4 *d_desc = reinterpret_cast<uint4 *>(m->d_slabdesc.get());
+    unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(m->d_slabdesc.get() + doff[nwin] * 32);
+    auto done = [&](int code) { m->ev_open.clear(); return code; };
+    if (hipMemsetAsync(d_cnt, 0, (size_t)(nwin + 1) * 8, st) != hipSuccess) return done(TSX_HIP_EHIP);
+    for (uint32_t w = 0; w < nwin && rc == TSX_HIP_OK; ++w) {
+        const size_t off = (size_t)w * WIN, own = std::min(WIN, n - off), len = std::min(own + halo, n - off);
+        DescOut dsc;
+        dsc.out = d_desc + doff[w] * 2; dsc.cap = doff[w + 1] - doff[w]; dsc.count = d_cnt + w; dsc.sum = d_cnt + nwin; dsc.long_desc = 1;
+        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;   // (windows start at multiples of 16)
+        rc = run_fastq_piece(m, base + off, len, own, off > 0 ? -1 : 0, st, ShardOut(), HotOut(), dsc);
+    }
+    m->qmap_cur = nullptr;
+    if (rc != TSX_HIP_OK) return done(rc);
+    std::vector<unsigned long long> cnt(nwin + 1);
+    if (hipMemcpyAsync(cnt.data(), d_cnt, (size_t)(nwin + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) return done(TSX_HIP_EHIP);
+    m->ev_open.clear();   // (the description calls queued timing tuples for a sharded build that never comes)
+    const uint64_t kmers = cnt[nwin];
+    if (kmers == 0) return done(TSX_HIP_OK);
+    const TableParams whole = m->p;
+    const bool fresh = m->fresh;
+    const size_t est = (size_t)(kmers / nslab + kmers / nslab / 8) + 65536;
+    for (uint32_t s = 0; s < nslab && rc == TSX_HIP_OK; ++s) {
+        TableParams &v = m->p;     // the slab's view
+        v = whole;
+        v.l = whole.l - sb;
+        v.slot_mask = (1ULL << v.l) - 1ULL;
+        v.shard = s;
+        v.pos_base = (uint64_t)s << v.l;
+        v.table = whole.table + ((uint64_t)s << v.l);
+        v.seg_dirty = whole.seg_dirty + ((uint64_t)s << (v.l - v.S));
+        m->fresh = fresh;
+        Event *ev = nullptr;
+        if (m->timing) {
+            if ((rc = next_timing_events(m, ev)) != TSX_HIP_OK) break;
+            for (int i = 0; i < 4; ++i) if (hipEventRecord(ev[i].get(), st) != hipSuccess) rc = TSX_HIP_EHIP;
+        }
+        for (uint32_t w = 0; w < nwin && rc == TSX_HIP_OK; ++w)
+            rc = shard_walk(m, d_desc + doff[w] * 2, (size_t)cnt[w], 1, w, nwin, est, nullptr, st);
+        if (rc == TSX_HIP_OK) {
+            if (!m->sh_pl || !m->sh_pl->fused) rc = TSX_HIP_EINVAL;
+            else rc = run_partition_build(m, *m->sh_pl, nullptr, nullptr, 0, st, ev);
+        }
+        if (rc == TSX_HIP_OK && ev && hipEventRecord(ev[7].get(), st) != hipSuccess) rc = TSX_HIP_EHIP;
+    }
+    m->p = whole;
+    if (rc == TSX_HIP_OK) m->fresh = false;
+    return done(rc);
+}
+
+// A table built slab by slab walks the whole text once per slab: the host forms send the text to the device in one piece
+// (newlines behind it) and call their device form.
+template <class DeviceForm>
+static int count_resident(tsx_hip_map *m, const char *text, size_t n, DeviceForm device_form) {
+    DevBuf<uint8_t> d_text;
+    TSX_TRY(d_text.alloc(n + 256));
+    SyncAtExit wait(m->stream.get());   // nothing queued may outlive the text
+    if (hipMemcpy(d_text.get(), text, n, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_text.get() + n, '\n', 256) != hipSuccess) return TSX_HIP_EHIP;
+    TSX_TRY(device_form(m, d_text.get(), n, nullptr));
+    return tsx_hip_sync(m);
+}
+
+// Device texts are processed in windows so that the partition scratch (about
+// 10 bytes per text byte) stays bounded; windows overlap by the k-1 byte halo
+// exactly like the host pieces.
+extern "C" int tsx_hip_count_fastq_device(tsx_hip_map *m, const void *dev_text, size_t n, void *stream) {
+    if (!m || (!dev_text && n) || ((uintptr_t)dev_text & 15)) return TSX_HIP_EINVAL;
+    if (m->p.lg != m->p.l) return TSX_HIP_EINVAL;   // a shard: keys of other owners must travel (shard_scan / shard_build)
+    if (n) m->used = true;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    const uint8_t *base = (const uint8_t *)dev_text;
+    // a quality rule: the bitmap of the whole (resident) text, read by each window at its offset
+    int rcq = base_rule_ok(m);
+    if (rcq == TSX_HIP_OK && m->minq) rcq = build_qmap(m, base, n, st);
+    if (rcq != TSX_HIP_OK) return rcq;
+    const uint16_t *qmap = m->minq ? m->d_qmap.get() : nullptr;
+    QmapScope qs(m);
+    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));
+    const size_t halo = (size_t)m->p.k - 1;
+    const size_t DEV_WINDOW = dev_window_bytes();
+    if (slab_build_wanted(m, n)) return count_slabs(m, base, n, st, qmap);
+    for (size_t off = 0; off < n || off == 0; off += DEV_WINDOW) {
+        const size_t own = std::min(DEV_WINDOW, n - off);
+        const size_t len = std::min(own + halo, n - off);
+        m->qmap_cur = qmap ? qmap + off / 16 : nullptr;   // (windows start at multiples of 16)
+        // whether the previous window ends inside a line is read on the device (the byte in front of this one)
+        int rc = run_fastq_piece(m, base + off, len, own, off > 0 ? -1 : 0, st);
+        if (rc != TSX_HIP_OK) return rc;
+        if (n == 0) break;
     }
     return TSX_HIP_OK;
 }
@@ -2322,46 +2523,9 @@ static const size_t BGZF_PRE = 256;   // >= k - 1, a multiple of 16
 static const size_t BGZF_CARRY = (size_t)8 << 20;
 
 static int count_bgzf_records(tsx_hip_map *m, const uint8_t *gz, size_t n, const BgzfIndex &ix, hipStream_t st) {
-    const size_t batch = bgzf_batch_bytes(), nm = ix.in_off.size(), head = BGZF_CARRY + 16;
-    size_t biggest = 0;
-    for (size_t m0 = 0; m0 < nm;) { const size_t m1 = bgzf_next_batch(ix, m0, batch); biggest = std::max(biggest, bgzf_batch_text(ix, m0, m1)); m0 = m1; }
-    BgzfDev dv;
-    DevBuf<uint8_t> txt, tail;
-    int rc = TSX_HIP_OK;
-    if (txt.alloc(head + biggest + 256) != TSX_HIP_OK || tail.alloc(head) != TSX_HIP_OK) {
-        g_last_error = "hipMalloc of a BGZF text buffer failed";
-        rc = TSX_HIP_ENOMEM;
-    }
-    uint8_t *const d_txt = txt.get(), *const d_tail = tail.get();
-    size_t r = 0;   // bytes of the carried record in d_tail
-    for (size_t m0 = 0; m0 < nm && rc == TSX_HIP_OK;) {
-        const size_t m1 = bgzf_next_batch(ix, m0, batch), nb = bgzf_batch_text(ix, m0, m1);
-        const bool last = m1 == nm;
-        if ((rc = inflate_batch(gz, n, ix, m0, m1, dv, d_txt + head, st)) != TSX_HIP_OK) break;
-        const size_t ra = (r + 15) & ~(size_t)15;
-        uint8_t *piece = d_txt + head - ra;
-        if ((ra > r && hipMemsetAsync(piece, '\n', ra - r, st) != hipSuccess) ||
-            (r && hipMemcpyAsync(piece + ra - r, d_tail, r, hipMemcpyDeviceToDevice, st) != hipSuccess) ||
-            hipMemsetAsync(d_txt + head + nb, '\n', 256, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        const size_t len = ra + nb;
-        uint64_t cut = 0;
-        if ((rc = count_record_piece(m, piece, len, last, st, cut)) != TSX_HIP_OK) break;
-        if (!last) {
-            const size_t rest = len - cut;
-            if (rest > BGZF_CARRY) {
-                g_last_error = "min_qual_char: a record longer than " + std::to_string(BGZF_CARRY) + " bytes in a BGZF file";
-                rc = TSX_HIP_ERANGE;
-                break;
-            }
-            if (rest && hipMemcpyAsync(d_tail, piece + cut, rest, hipMemcpyDeviceToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            r = rest;
-        }
-        if (hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }   // (d_txt is refilled next)
-        m0 = m1;
-    }
-    hipError_t e = hipStreamSynchronize(st);   // nothing queued may outlive the buffers
-    if (rc == TSX_HIP_OK && e != hipSuccess) { g_last_error = hipGetErrorString(e); rc = TSX_HIP_EHIP; }
-    return rc;
+    return bgzf_record_pieces(gz, n, ix, BGZF_CARRY, st, [&](const uint8_t *piece, uint64_t len, bool last, uint64_t &cut) {
+        return count_record_piece(m, piece, len, last, st, cut);
+    });
 }
 
 extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, size_t n) {
@@ -2376,18 +2540,17 @@ extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, siz
     if (int rcq = base_rule_ok(m)) return rcq;
     if (m->minq) return count_bgzf_records(m, (const uint8_t *)gz, n, ix, st);
     HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));
-    const size_t batch = bgzf_batch_bytes(), nm = ix.in_off.size(), head = BGZF_PRE + 16;
-    size_t biggest = 0;
-    for (size_t m0 = 0; m0 < nm;) { const size_t m1 = bgzf_next_batch(ix, m0, batch); biggest = std::max(biggest, bgzf_batch_text(ix, m0, m1)); m0 = m1; }
+    const size_t head = BGZF_PRE + 16;
+    BgzfBatches bt(ix, bgzf_batch_bytes());
     // (the inflate stream is declared first: it outlives the buffers it fills)
     Stream inflate_stream;
     Event counted[2];
     BgzfDev dv;
     DevBuf<uint8_t> txt[2];
-    const size_t buf_bytes = head + biggest + 256;
+    const size_t buf_bytes = head + bt.biggest() + 256;
     int rc = TSX_HIP_OK;
     for (int i = 0; i < 2 && rc == TSX_HIP_OK; ++i)   // (the second buffer only when a second batch exists)
-        if ((i == 0 || bgzf_next_batch(ix, 0, batch) < nm) && txt[i].alloc(buf_bytes) != TSX_HIP_OK) {
+        if ((i == 0 || !bt.last()) && txt[i].alloc(buf_bytes) != TSX_HIP_OK) {
             g_last_error = "hipMalloc of a BGZF text buffer failed";
             rc = TSX_HIP_ENOMEM;
         }
@@ -2403,13 +2566,13 @@ extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, siz
     size_t prev_len = 0;   // bytes of text in the previous batch's buffer, behind its head
     int b = 0;
     size_t nbatch = 0;
-    for (size_t m0 = 0; m0 < nm && rc == TSX_HIP_OK; b ^= 1, ++nbatch) {
-        const size_t m1 = bgzf_next_batch(ix, m0, batch), nb = bgzf_batch_text(ix, m0, m1);
-        const bool first = (m0 == 0), last = (m1 == nm);
+    for (; !bt.done() && rc == TSX_HIP_OK; bt.next(), b ^= 1, ++nbatch) {
+        const size_t nb = bt.text();
+        const bool first = bt.first(), last = bt.last();
         uint8_t *buf = d_txt[b];
         hipStream_t sti = st_inf ? st_inf : st;   // (one batch in all: everything on the map's stream)
         if (st_inf && nbatch >= 2 && hipStreamWaitEvent(st_inf, counted[b].get(), 0) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        rc = inflate_batch((const uint8_t *)gz, n, ix, m0, m1, dv, buf + head, sti);   // (returns when the text is there)
+        rc = inflate_batch((const uint8_t *)gz, n, ix, bt.m0, bt.m1, dv, buf + head, sti);   // (returns when the text is there)
         if (rc != TSX_HIP_OK) break;
         if (!first) {   // the end of the text so far (it may reach back into the previous buffer's own head)
             if (hipMemcpyAsync(buf, d_txt[b ^ 1] + prev_len, head, hipMemcpyDeviceToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
@@ -2424,46 +2587,11 @@ extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, siz
         rc = run_fastq_piece(m, buf + from, len, own, first ? 0 : -1, st);
         if (rc == TSX_HIP_OK && st_inf && hipEventRecord(counted[b].get(), st) != hipSuccess) rc = TSX_HIP_EHIP;
         prev_len = nb;
-        m0 = m1;
     }
     hipError_t e = hipStreamSynchronize(st);   // nothing queued may outlive the buffers
     if (st_inf) (void)hipStreamSynchronize(st_inf);
     if (rc == TSX_HIP_OK && e != hipSuccess) { g_last_error = hipGetErrorString(e); rc = TSX_HIP_EHIP; }
     return rc;
-}
-
-static int ensure_staging(tsx_hip_map *m, size_t n) {
-    const size_t bytes = std::min(m->piece, n) + STAGE_PAD + 128;
-    if (m->d_stage[1].cap() >= bytes) return TSX_HIP_OK;   // (allocated last: there when all of them are)
-    auto drop = [&] { for (int i = 0; i < 2; ++i) { m->h_stage[i].reset(); m->d_stage[i].reset(); } };
-    drop();   // grow: drop the smaller buffers first
-    int rc = m->copy_stream.get() ? TSX_HIP_OK : m->copy_stream.create();
-    for (int i = 0; i < 2 && rc == TSX_HIP_OK; ++i) {
-        if ((rc = m->h_stage[i].alloc(bytes)) == TSX_HIP_OK) rc = m->d_stage[i].alloc(bytes);
-        if (rc == TSX_HIP_OK) rc = m->stage_done[i].create();
-        if (rc == TSX_HIP_OK) rc = m->stage_in[i].create();
-    }
-    if (rc != TSX_HIP_OK) drop();   // all four buffers or none
-    return rc;
-}
-
-// Pageable -> pinned staging copy on several host threads: one thread moves ~10 GB/s,
-// the PCIe link ~55 GB/s.  Hardware threads - 2, at least 2 and at most 12.
-static void parallel_memcpy(uint8_t *dst, const char *src, size_t len) {
-    static const unsigned maxt = [] {   // (initialised once, also when rank threads copy at the same time)
-        const unsigned hw = std::thread::hardware_concurrency();
-        return std::min(12u, std::max(2u, hw > 2 ? hw - 2 : 2u));
-    }();
-    const size_t MIN_PER_THREAD = (size_t)8 << 20;
-    unsigned nthreads = (unsigned)std::min<size_t>(maxt, len / MIN_PER_THREAD);
-    if (nthreads <= 1) { memcpy(dst, src, len); return; }
-    std::vector<std::thread> th;
-    const size_t per = ((len / nthreads) + 4095) & ~(size_t)4095;
-    for (unsigned t = 0; t < nthreads; ++t) {
-        const size_t lo = std::min(len, (size_t)t * per), hi = (t + 1 == nthreads) ? len : std::min(len, lo + per);
-        if (hi > lo) th.emplace_back([=]() { memcpy(dst + lo, src + lo, hi - lo); });
-    }
-    for (auto &x : th) x.join();
 }
 
 extern "C" int tsx_hip_count_fastq_host(tsx_hip_map *m, const char *text, size_t n) {
@@ -2472,44 +2600,17 @@ extern "C" int tsx_hip_count_fastq_host(tsx_hip_map *m, const char *text, size_t
     if (n) m->used = true;
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipStreamSynchronize(m->stream.get()));
-    if (slab_bits(m) && (m->path == 2 || (m->path == 0 && n * 32 >= m->lay.table_bytes))) {
-        // a table built slab by slab walks the whole text once per slab: the text goes to the device in one piece
-        DevBuf<uint8_t> d_text;
-        TSX_TRY(d_text.alloc(n + 256));
-        SyncAtExit wait(m->stream.get());   // nothing queued may outlive the text
-        if (hipMemcpy(d_text.get(), text, n, hipMemcpyHostToDevice) != hipSuccess || hipMemset(d_text.get() + n, '\n', 256) != hipSuccess) return TSX_HIP_EHIP;
-        TSX_TRY(tsx_hip_count_fastq_device(m, d_text.get(), n, nullptr));
-        return tsx_hip_sync(m);
-    }
+    if (slab_build_wanted(m, n)) return count_resident(m, text, n, tsx_hip_count_fastq_device);
     int rc = base_rule_ok(m);
     if (rc != TSX_HIP_OK) return rc;
     if (m->minq) return count_host_records(m, text, n);
-    rc = ensure_staging(m, n);
-    if (rc != TSX_HIP_OK) return rc;
     hipStream_t st = m->stream.get();
     HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));
     // Pieces own m->piece start positions and carry a k-1 byte halo so that
     // windows beginning near the end of a piece see their last bytes.
-    const size_t halo = (size_t)m->p.k - 1;
-    int buf = 0;
-    bool used[2] = {false, false};
-    for (size_t off = 0; off < n; off += m->piece, buf ^= 1) {
-        const size_t own = std::min(m->piece, n - off);
-        const size_t len = std::min(own + halo, n - off);
-        // three legs overlap: this piece's host copy, the previous piece's H2D copy (its own stream)
-        // and the kernels of the piece before that
-        if (used[buf]) HIP_TRY(hipEventSynchronize(m->stage_done[buf].get()));
-        parallel_memcpy(m->h_stage[buf].get(), text + off, len);
-        HIP_TRY(hipMemcpyAsync(m->d_stage[buf].get(), m->h_stage[buf].get(), len, hipMemcpyHostToDevice, m->copy_stream.get()));
-        HIP_TRY(hipEventRecord(m->stage_in[buf].get(), m->copy_stream.get()));
-        HIP_TRY(hipStreamWaitEvent(st, m->stage_in[buf].get(), 0));
-        const int head_open = (off > 0 && text[off - 1] != '\n') ? 1 : 0;
-        rc = run_fastq_piece(m, m->d_stage[buf].get(), len, own, head_open, st);
-        if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipEventRecord(m->stage_done[buf].get(), st));
-        used[buf] = true;
-    }
-    return tsx_hip_sync(m);
+    return staged_pieces(m, text, n, m->piece, (size_t)m->p.k - 1, [&](const uint8_t *d_piece, size_t len, size_t own, int head_open) {
+        return run_fastq_piece(m, d_piece, len, own, head_open, st);
+    });
 }
 
 // ---- wrapped FASTA: sequence lines joined on the device (tsx_fasta.h), then counted as two-line text ----------------
@@ -2565,9 +2666,6 @@ static int fasta_begin(tsx_hip_map *m, hipStream_t st) {   // the carry of a new
     HIP_TRY(hipMemsetAsync(m->d_fa_carry.get(), 0, FA_CARRY_BYTES + FA_INFO_WORDS * 4, st));
     return TSX_HIP_OK;
 }
-static inline bool slab_build_wanted(const tsx_hip_map *m, size_t n) {
-    return slab_bits(m) && (m->path == 2 || (m->path == 0 && n * 32 >= m->lay.table_bytes));
-}
 
 // One piece of a wrapped text, behind the carry: unwrapped into the map's scratch and counted at its upper-bound length
 // (what the unwrap did not write there is newlines: empty lines), so that nothing is read back.
@@ -2618,35 +2716,14 @@ extern "C" int tsx_hip_count_fasta_host(tsx_hip_map *m, const char *text, size_t
     if (n) m->used = true;
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipStreamSynchronize(m->stream.get()));
-    if (slab_build_wanted(m, n)) {   // the whole text resident, as tsx_hip_count_fastq_host does for such a table
-        DevBuf<uint8_t> d_text;
-        TSX_TRY(d_text.alloc(n + 256));
-        SyncAtExit wait(m->stream.get());   // nothing queued may outlive the text
-        if (hipMemcpy(d_text.get(), text, n, hipMemcpyHostToDevice) != hipSuccess) return TSX_HIP_EHIP;
-        TSX_TRY(tsx_hip_count_fasta_device(m, d_text.get(), n, nullptr));
-        return tsx_hip_sync(m);
-    }
-    int rc = ensure_staging(m, n);
-    if (rc != TSX_HIP_OK) return rc;
+    if (slab_build_wanted(m, n)) return count_resident(m, text, n, tsx_hip_count_fasta_device);
     hipStream_t st = m->stream.get();
-    if ((rc = fasta_begin(m, st)) != TSX_HIP_OK) return rc;
+    TSX_TRY(fasta_begin(m, st));
     FastaScope fs(m);
     // pieces are cut anywhere and overlap nowhere: what a k-mer across the cut needs travels in the carry
-    const size_t piece = std::min(m->piece, FA_PIECE_MAX);
-    int buf = 0;
-    bool used[2] = {false, false};
-    for (size_t off = 0; off < n; off += piece, buf ^= 1) {
-        const size_t len = std::min(piece, n - off);
-        if (used[buf]) HIP_TRY(hipEventSynchronize(m->stage_done[buf].get()));
-        parallel_memcpy(m->h_stage[buf].get(), text + off, len);
-        HIP_TRY(hipMemcpyAsync(m->d_stage[buf].get(), m->h_stage[buf].get(), len, hipMemcpyHostToDevice, m->copy_stream.get()));
-        HIP_TRY(hipEventRecord(m->stage_in[buf].get(), m->copy_stream.get()));
-        HIP_TRY(hipStreamWaitEvent(st, m->stage_in[buf].get(), 0));
-        if ((rc = fasta_count_piece(m, m->d_stage[buf].get(), len, st)) != TSX_HIP_OK) return rc;
-        HIP_TRY(hipEventRecord(m->stage_done[buf].get(), st));
-        used[buf] = true;
-    }
-    return tsx_hip_sync(m);
+    return staged_pieces(m, text, n, std::min(m->piece, FA_PIECE_MAX), 0, [&](const uint8_t *d_piece, size_t len, size_t, int) {
+        return fasta_count_piece(m, d_piece, len, st);
+    });
 }
 
 // Batch after batch on the map's stream: inflated, unwrapped behind the carry, counted.
@@ -2662,18 +2739,14 @@ extern "C" int tsx_hip_count_fasta_bgzf_host(tsx_hip_map *m, const void *gz, siz
     int rc = fasta_begin(m, st);
     if (rc != TSX_HIP_OK) return rc;
     FastaScope fs(m);
-    const size_t batch = std::min(bgzf_batch_bytes(), FA_PIECE_MAX), nm = ix.in_off.size();
-    size_t biggest = 0;
-    for (size_t m0 = 0; m0 < nm;) { const size_t m1 = bgzf_next_batch(ix, m0, batch); biggest = std::max(biggest, bgzf_batch_text(ix, m0, m1)); m0 = m1; }
+    BgzfBatches bt(ix, std::min(bgzf_batch_bytes(), FA_PIECE_MAX));
     BgzfDev dv;
     DevBuf<uint8_t> txt;
-    if (txt.alloc(biggest + 256) != TSX_HIP_OK) { g_last_error = "hipMalloc of a BGZF text buffer failed"; return TSX_HIP_ENOMEM; }
+    if (txt.alloc(bt.biggest() + 256) != TSX_HIP_OK) { g_last_error = "hipMalloc of a BGZF text buffer failed"; return TSX_HIP_ENOMEM; }
     uint8_t *const d_txt = txt.get();
-    for (size_t m0 = 0; m0 < nm && rc == TSX_HIP_OK;) {
-        const size_t m1 = bgzf_next_batch(ix, m0, batch);
-        rc = inflate_batch((const uint8_t *)gz, n, ix, m0, m1, dv, d_txt, st);   // (behind the count of the batch before)
-        if (rc == TSX_HIP_OK) rc = fasta_count_piece(m, d_txt, bgzf_batch_text(ix, m0, m1), st);
-        m0 = m1;
+    for (; !bt.done() && rc == TSX_HIP_OK; bt.next()) {
+        rc = inflate_batch((const uint8_t *)gz, n, ix, bt.m0, bt.m1, dv, d_txt, st);   // (behind the count of the batch before)
+        if (rc == TSX_HIP_OK) rc = fasta_count_piece(m, d_txt, bt.text(), st);
     }
     hipError_t e = hipStreamSynchronize(st);   // nothing queued may outlive the buffers
     if (rc == TSX_HIP_OK && e != hipSuccess) { g_last_error = hipGetErrorString(e); rc = TSX_HIP_EHIP; }
@@ -3806,23 +3879,6 @@ static bool query_args_ok(const tsx_hip_map *m, uint64_t lower, uint64_t upper) 
     return m && lower <= upper && m->p.lg == m->p.l;
 }
 
-// The line passes of run_fastq_piece (tile line ends, then their exclusive scan from *d_carry) over [0, own_end).
-static int query_line_pass(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open, hipStream_t st) {
-    const uint64_t ntiles = (own_end + TILE - 1) / TILE;
-    TSX_TRY(ensure_tiles(m, ntiles, st));
-    const int g1 = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8);
-    hipLaunchKernelGGL(line_count_kernel, dim3(g1), dim3(NT), 0, st, d_text, n, own_end, head_open, m->d_tile.get(), ntiles);
-    const uint64_t nchunks = (ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    uint32_t *chunk = m->d_tile.get() + m->tile_cap;
-    hipLaunchKernelGGL(line_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const uint32_t *)m->d_tile.get(),
-                       ntiles, chunk);
-    hipLaunchKernelGGL(line_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, m->d_carry.get());
-    hipLaunchKernelGGL(line_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, m->d_tile.get(), ntiles,
-                       (const uint32_t *)chunk);
-    HIP_TRY(hipGetLastError());
-    return TSX_HIP_OK;
-}
-
 // query_reads_kernel over the start positions [0, own_end) of d_text (n readable bytes), after query_line_pass.
 static int query_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
                         const unsigned long long *d_line_base, uint64_t lower, uint64_t upper, unsigned long long *d_stats,
@@ -3914,27 +3970,6 @@ extern "C" int tsx_hip_query_reads_device(tsx_hip_map *m, const void *dev_text, 
     return windows_records(m, stats_cap, n_records, st);
 }
 
-// Scratch common to the calls that work on a text piece by piece: the piece on the device, its record spans (for the
-// calls that cut by them), the words the scans and the filters report in, their pinned copy.  The scratch of a call
-// (QueryBufs, TrimBufs, MedianBufs) embeds it BEHIND its own buffers: the destructor here waits for the stream before
-// any of them is released.
-struct PieceBufs {
-    DevBuf<uint8_t> text;
-    DevBuf<unsigned long long> rspan;              // record spans
-    DevBuf<unsigned long long> info;               // cut, records, open, total, line base (0), kept; the trim: bases in, bases kept
-    PinBuf<unsigned long long> h_info;
-    Event ev;                                      // info[3..] has been copied back
-    hipStream_t st;
-    explicit PieceBufs(hipStream_t s) : st(s) {}
-    ~PieceBufs() { (void)hipStreamSynchronize(st); }   // nothing queued may outlive the buffers
-    int init() {
-        TSX_TRY(info.alloc(8 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(info.get(), 0, 8 * sizeof(unsigned long long), st));
-        TSX_TRY(h_info.alloc(8 * sizeof(unsigned long long)));
-        return ev.create();
-    }
-};
-
 // Where the compacted output of a piece goes: the caller's buffer (never grown: the *_device entry points check that it
 // has the room) or, without one, `own`.
 struct OutBuf {
@@ -3957,47 +3992,6 @@ struct QueryBufs {
     PieceBufs p;
     explicit QueryBufs(hipStream_t s) : p(s) {}
 };
-
-// The scan half of a piece [0, len) of text in device memory that starts at a record boundary: the line pass and the
-// record scan into info[0..2] (cut, records, open), with the record spans when `span` is given.  Queued, not waited for.
-static int piece_scan(tsx_hip_map *m, const uint8_t *d_text, uint64_t len, bool last, unsigned long long *info,
-                      DevBuf<unsigned long long> *span, hipStream_t st) {
-    const uint32_t lpr = m->p.line_mask + 1;
-    const uint64_t ntiles = (len + TILE - 1) / TILE, span_cap = len / (2 * lpr) + 2;
-    int rc;
-    HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-    if ((rc = query_line_pass(m, d_text, len, len, 0, st)) != TSX_HIP_OK) return rc;
-    if (span && (rc = grow(st, *span, span_cap * 16)) != TSX_HIP_OK) return rc;
-    hipLaunchKernelGGL(record_scan_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
-                       d_text, len, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), lpr, last ? 1 : 0,
-                       info, span ? span->get() : (unsigned long long *)nullptr, span ? span_cap : (uint64_t)0);
-    HIP_TRY(hipGetLastError());
-    return TSX_HIP_OK;
-}
-
-// The front end of every piece [0, len) of text in device memory that starts at a record boundary: piece_scan (the
-// spans in p.rspan when `spans`), then the ONE wait of a piece, for where its last whole record ends, its records and
-// whether the last one lacks its '\n'.  An empty piece: nothing.
-static int piece_front(tsx_hip_map *m, PieceBufs &p, const uint8_t *d_text, uint64_t len, bool last, bool spans, uint64_t &cut,
-                       uint64_t &nrec, bool &open) {
-    cut = nrec = 0; open = false;
-    if (len == 0) return TSX_HIP_OK;
-    TSX_TRY(piece_scan(m, d_text, len, last, p.info.get(), spans ? &p.rspan : nullptr, p.st));
-    const unsigned long long *h_info = p.h_info.get();
-    HIP_TRY(hipMemcpyAsync(p.h_info.get(), p.info.get(), 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, p.st));
-    HIP_TRY(hipStreamSynchronize(p.st));
-    cut = h_info[0]; nrec = h_info[1]; open = h_info[2] != 0;
-    return TSX_HIP_OK;
-}
-
-// A quality rule: the bitmap of the whole records d_text[0, cut) for the launches that follow (its line pass over
-// [0, cut) rewrites d_tile with the same values).  The caller holds a QmapScope.
-static int piece_qmap(tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, hipStream_t st) {
-    if (!m->minq) return TSX_HIP_OK;
-    TSX_TRY(build_qmap(m, d_text, cut, st));
-    m->qmap_cur = m->d_qmap.get();
-    return TSX_HIP_OK;
-}
 
 // The query half: the stats of the records [0, nrec) of d_text[0, cut) in b.stats, after a line pass over a text that
 // starts with [0, cut) (the tile line counts).  Queued, not waited for.
@@ -4788,9 +4782,7 @@ extern "C" int tsx_hip_sketch_host(tsx_hip_map *m, const char *text, size_t n, i
     return b.collect(precision, regs, totals, rec_base);
 }
 
-// The way tsx_hip_count_fastq_bgzf_host goes under a quality rule: batch by batch on the map's stream, every piece cut
-// at its last whole record, whose unfinished rest goes in front of the next batch's text (behind newlines that align the
-// piece to 16 bytes; empty lines are no lines).
+// The pieces of bgzf_record_pieces, without a limit on the carried record.
 extern "C" int tsx_hip_sketch_bgzf_host(tsx_hip_map *m, const void *gz, size_t n, int precision, uint8_t *regs,
                                         tsx_hip_sketch_totals *totals) {
     if (!m || !regs || !sketch_prec_ok(precision) || (!gz && n)) return TSX_HIP_EINVAL;
@@ -4800,36 +4792,17 @@ extern "C" int tsx_hip_sketch_bgzf_host(tsx_hip_map *m, const void *gz, size_t n
     hipStream_t st = m->stream.get();
     join_foreign(m, false);
     TSX_TRY(base_rule_ok(m));
-    BgzfDev dv;
-    DevBuf<uint8_t> txt, tail;
-    SketchBufs b(st);   // (last: its destructor waits for the stream before anything here is released)
+    SketchBufs b(st);
     TSX_TRY(b.init(precision));
     TSX_TRY(b.p.init());
-    const size_t batch = bgzf_batch_bytes(), nm = ix.in_off.size();
     uint64_t records = 0;
-    size_t r = 0;   // bytes of the carried record in `tail`
-    for (size_t m0 = 0; m0 < nm;) {
-        const size_t m1 = bgzf_next_batch(ix, m0, batch), nb = bgzf_batch_text(ix, m0, m1);
-        const bool last = m1 == nm;
-        const size_t ra = (r + 15) & ~(size_t)15, len = ra + nb;
-        TSX_TRY(grow(st, txt, len + 256));
-        uint8_t *const piece = txt.get();
-        TSX_TRY(inflate_batch((const uint8_t *)gz, n, ix, m0, m1, dv, piece + ra, st));
-        if (ra > r) HIP_TRY(hipMemsetAsync(piece, '\n', ra - r, st));
-        if (r) HIP_TRY(hipMemcpyAsync(piece + ra - r, tail.get(), r, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemsetAsync(piece + len, '\n', 256, st));
-        uint64_t cut = 0, nrec = 0;
+    TSX_TRY(bgzf_record_pieces((const uint8_t *)gz, n, ix, SIZE_MAX, st, [&](const uint8_t *piece, uint64_t len, bool last, uint64_t &cut) -> int {
+        uint64_t nrec = 0;
         bool open = false;
         TSX_TRY(sketch_piece(m, b, piece, len, last, precision, st, cut, nrec, open));
         records += nrec;
-        r = last ? 0 : len - (size_t)cut;
-        if (r) {
-            TSX_TRY(grow(st, tail, r));
-            HIP_TRY(hipMemcpyAsync(tail.get(), piece + cut, r, hipMemcpyDeviceToDevice, st));
-        }
-        HIP_TRY(hipStreamSynchronize(st));   // (txt is refilled next)
-        m0 = m1;
-    }
+        return TSX_HIP_OK;
+    }));
     return b.collect(precision, regs, totals, records);
 }
 
