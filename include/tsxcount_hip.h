@@ -568,6 +568,64 @@ double tsx_hip_sketch_estimate_host(const uint8_t *regs, int precision);
 int tsx_hip_suggest_l(int k, double distinct, int precision, uint32_t load_ppm, int *l_out);
 
 /*
+ * Counting only the k-mers seen twice (csrc/tsx_prefilter.h; no reference counterpart -- jellyfish --bf-size, BFCounter,
+ * KMC -ci2): a prefilter that belongs to a map, filled in a first pass over the input; the counting calls consult it in a
+ * second pass over the same input, so that a k-mer that occurs once takes no slot of the table.
+ * ELEMENT and HASH: exactly the sketch's (above): the k-mer x in the tsx_hip_encode layout, WK limbs, on a canonical map
+ *   the lexicographically smaller strand; windows, records and the base rule are those of the counting calls;
+ *   v = sketch hash of x.  The filters depend on neither l, storagebits nor the seed.
+ * FILTERS: two blocked Bloom filters of 64-bit words.  A ("seen") has 2^bits bits, B ("seen again") 2^(bits - 2);
+ *   12 <= bits <= 38.  WORD of a key: v >> (64 - (bits - 6)) in A, v >> (64 - (bits - 8)) in B.  MASK, the same in both:
+ *   the OR of 1 << ((v >> s) & 63) for s = 0, 6, 12, 18 (one to four bits).  In a filter: (word & mask) == mask.
+ * PASS 1 (prefilter_add_*): every window ORs its mask into A (one returning 64-bit atomic); when A already held the
+ *   mask -- or the window's equal neighbour just did the same -- it ORs the mask into B.  Several calls accumulate.
+ * PASS 2 (while armed): tsx_hip_count_fastq_host / _device / _bgzf_host insert the windows whose mask is in B and skip
+ *   the others.  They take the atomic insert path whatever tsx_hip_set_path says.  Not gated: tsx_hip_add_kmers_*,
+ *   tsx_hip_load_host, tsx_hip_combine, every read call.  tsx_hip_get_stats' kmers counts the inserted windows only.
+ * CONTRACT: after pass 1 and pass 2 over the same input, EVERY k-mer that occurs at least twice is in the table with its
+ *   exact count.  A k-mer that occurs once is absent, or -- a false positive of B -- present with count 1.  So a dump
+ *   with lower >= 2, histogram bins >= 2 and every read call with a lower bound >= 2 are those of an unfiltered count;
+ *   the false-positive rate decides the slots saved, never a count.
+ * STREAMS: B must be complete before pass 2 reads it, and the library sees to that itself.  prefilter_create returns
+ *   with the filters zeroed (it waits).  An armed counting call first orders its stream behind the map's own stream and
+ *   behind the stream of the last *_device call on this map, so pass 1 through any prefilter_add_* followed by pass 2
+ *   through any counting call needs nothing from the caller.  Only a caller that runs pass 1 on SEVERAL streams of its
+ *   own at once joins them (or calls tsx_hip_sync, which waits for the last one) before the armed count.
+ * tsx_hip_clear empties the table and leaves the prefilter alone: the filters, armed or not, and the totals of
+ *   prefilter_stats (admitted / skipped keep adding up over several counts) last until prefilter_create or _free.
+ * TSX_HIP_EINVAL, before any GPU call: bits outside 12 .. 38; add, arm(1) or read without a filter; an armed count on a
+ *   map created with shard_bits > 0 or on a table that is built slab by slab (above 2^32 slots); armed wrapped-FASTA
+ *   counting (tsx_hip_count_fasta_*); a device text that is not 16-byte aligned; tsx_hip_group_count_fastq_host while
+ *   a map of the group is armed (each GPU sees a share of the records only).
+ *   prefilter_create    allocates and zeroes A (2^bits / 8 bytes) and B (a quarter), zeroes the totals, disarms.  A second
+ *                       call replaces them.  prefilter_free releases them and disarms.
+ *   prefilter_add_host  pass 1 over a text in host memory, in pieces cut at record boundaries (chunk_bytes 0 = 256 MiB,
+ *                       and at most TSX_HIP_PIECE_BYTES when that is set).  _add_bgzf_host: the image of a BGZF file.
+ *   prefilter_add_device  dev_text as tsx_hip_sketch_device takes it; queued on the stream, not waited for.
+ *   prefilter_arm       on != 0: the FASTQ counting calls run pass 2 until it is taken back.
+ *   prefilter_stats     bits; seen = windows of pass 1; seen_again = those that found their k-mer in A (or in the lane
+ *                       below); admitted / skipped = windows of pass 2 that were inserted / kept out; set_bits_a / _b =
+ *                       the filters' fill.  Without a filter: all zero.
+ *   prefilter_read      which = 0: A, 1: B; nwords must be the filter's 2^(bits - 6) / 2^(bits - 8) (else TSX_HIP_ERANGE).
+ *   prefilter_mask_host CPU only, the definition: word indexes and mask of ONE k-mer as given (the caller canonicalises).
+ */
+typedef struct tsx_hip_prefilter_totals {
+    uint64_t bits, seen, seen_again, admitted, skipped, set_bits_a, set_bits_b;
+} tsx_hip_prefilter_totals;
+int tsx_hip_prefilter_create(tsx_hip_map *m, int bits);
+int tsx_hip_prefilter_free(tsx_hip_map *m);
+int tsx_hip_prefilter_add_host(tsx_hip_map *m, const char *text, size_t n, size_t chunk_bytes);
+int tsx_hip_prefilter_add_bgzf_host(tsx_hip_map *m, const void *gz, size_t n);
+int tsx_hip_prefilter_add_device(tsx_hip_map *m, const void *dev_text, size_t n, void *stream);
+int tsx_hip_prefilter_arm(tsx_hip_map *m, int on);
+int tsx_hip_prefilter_armed(const tsx_hip_map *m);   /* 1 or 0 */
+int tsx_hip_prefilter_bits(const tsx_hip_map *m);    /* the bits of the map's filter, 0 without one; host state, no GPU call */
+int tsx_hip_prefilter_stats(tsx_hip_map *m, tsx_hip_prefilter_totals *out);
+int tsx_hip_prefilter_read(tsx_hip_map *m, int which, uint64_t *words_out, size_t nwords);
+int tsx_hip_prefilter_mask_host(int k, const uint64_t *kmer_limbs, int bits, uint64_t *word_a, uint64_t *word_b,
+                                uint64_t *mask);
+
+/*
  * Paired reads kept in step (csrc/tsx_pairs.h; no reference counterpart -- khmer `--paired`, Trimmomatic PE, BBDuk
  * in1/in2): the filter and the trim over mate pairs, so that the outputs line up record for record.  Records, lines,
  * k-mers, c(x) and the base rule are those of tsx_hip_query_reads_*.

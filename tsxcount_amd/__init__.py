@@ -97,6 +97,14 @@ class SketchTotals(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class PrefilterTotals(ctypes.Structure):
+    """tsx_hip_prefilter_totals: the size of a map's prefilter, what its two passes saw, its fill."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("bits", "seen", "seen_again", "admitted", "skipped", "set_bits_a", "set_bits_b")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
 class DbInfo(ctypes.Structure):
     """tsx_hip_db_info: the header of a k-mer database file."""
     _fields_ = [("version", ctypes.c_uint32), ("k", ctypes.c_int32), ("l", ctypes.c_int32),
@@ -255,6 +263,32 @@ def merge_sketches(a, b):
     return np.maximum(a, b)
 
 
+PREFILTER_BITS = range(12, 39)    # a prefilter's size: filter A has 2^bits bits, filter B 2^(bits - 2)
+
+
+def prefilter_masks(kmers, k, bits):
+    """Where a set of k-mers sits in a prefilter of 2^bits bits, on the CPU with numpy alone (the definition the GPU
+    filter is tested against): (word_a, word_b, mask), three numpy uint64 arrays.  kmers: encoded limbs, (n, key_limbs(k))
+    or flat, taken as given (canonicalise first for a canonical map).  Per k-mer: v = the hash of sketch_registers; the
+    64-bit word of filter A is v >> (64 - (bits - 6)), that of filter B v >> (64 - (bits - 8)); the mask, the same in
+    both, is the OR of 1 << ((v >> s) & 63) for s = 0, 6, 12, 18.  In a filter: word & mask == mask."""
+    b = int(bits)
+    if b not in PREFILTER_BITS:
+        raise ValueError("prefilter bits must be 12 .. 38, not %r" % (bits,))
+    wk = key_limbs(k)
+    a = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1, wk).copy()
+    if (2 * k) % 64:
+        a[:, wk - 1] &= np.uint64((1 << ((2 * k) % 64)) - 1)
+    with np.errstate(over="ignore"):
+        v = np.full(len(a), 0x9E3779B97F4A7C15, dtype=np.uint64)
+        for t in range(wk):
+            v = _mix64(v ^ a[:, t])
+    mask = np.zeros(len(a), dtype=np.uint64)
+    for s in (0, 6, 12, 18):
+        mask |= np.uint64(1) << ((v >> np.uint64(s)) & np.uint64(63))
+    return v >> np.uint64(64 - (b - 6)), v >> np.uint64(64 - (b - 8)), mask
+
+
 PAIR_MODES = {"both": 0, "any": 1}
 
 
@@ -393,6 +427,17 @@ def lib():
     L.tsx_hip_sketch_estimate_host.argtypes = [u8p, ci]
     L.tsx_hip_sketch_estimate_host.restype = ctypes.c_double
     L.tsx_hip_suggest_l.argtypes = [ci, ctypes.c_double, ci, ctypes.c_uint32, ctypes.POINTER(ci)]
+    L.tsx_hip_prefilter_create.argtypes = [vp, ci]
+    L.tsx_hip_prefilter_free.argtypes = [vp]
+    L.tsx_hip_prefilter_add_host.argtypes = [vp, ctypes.c_char_p, sz, sz]
+    L.tsx_hip_prefilter_add_bgzf_host.argtypes = [vp, vp, sz]
+    L.tsx_hip_prefilter_add_device.argtypes = [vp, vp, sz, vp]
+    L.tsx_hip_prefilter_arm.argtypes = [vp, ci]
+    L.tsx_hip_prefilter_armed.argtypes = [vp]
+    L.tsx_hip_prefilter_bits.argtypes = [vp]
+    L.tsx_hip_prefilter_stats.argtypes = [vp, ctypes.POINTER(PrefilterTotals)]
+    L.tsx_hip_prefilter_read.argtypes = [vp, ci, u64p, sz]
+    L.tsx_hip_prefilter_mask_host.argtypes = [ci, u64p, ci, u64p, u64p, u64p]
     L.tsx_hip_filter_pairs_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(FilterRule), ci, ci,
                                             ctypes.POINTER(PairIO), sz, ctypes.POINTER(PairTotals)]
     L.tsx_hip_trim_pairs_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), ci,
@@ -968,6 +1013,87 @@ class TSXHashMapHIP:
             m.set_record_lines(lines)
         m.size_estimate = {"kmers": tot["kmers"], "distinct": distinct, "l": l, "load": distinct / float(1 << l)}
         return m
+
+    # --- counting only the k-mers seen twice ----------------------------------
+    def _prefilter_for(self, bits):
+        """A filter for pass 1: the map's, when it has one and bits is None; else a new one of `bits` (None: l + 6, so that
+        filter A takes the bytes of a one-limb table of 2^l slots; clamped to 12 .. 38)."""
+        if bits is None:
+            if self.prefilter_bits:
+                return
+            bits = min(max(self.l + 6, PREFILTER_BITS[0]), PREFILTER_BITS[-1])
+        self.createPrefilter(bits)
+
+    def createPrefilter(self, bits):
+        """A new, empty prefilter of 2^bits bits (tsx_hip_prefilter_create; 12 .. 38), disarmed; replaces the one the map has."""
+        _check(self._lib.tsx_hip_prefilter_create(self.handle, int(bits)))
+
+    def freePrefilter(self):
+        _check(self._lib.tsx_hip_prefilter_free(self.handle))
+
+    def prefilter(self, text, bits=None, chunk_bytes=0):
+        """Pass 1 of a count that keeps out the k-mers seen once (tsx_hip_prefilter_add_host): the k-mers of `text` -- those
+        the counting calls would count -- into the map's prefilter.  bits: a new filter of that size first; None: the
+        filter the map has (several texts accumulate), a new one of l + 6 bits when it has none.  Then armPrefilter()
+        and count the same input: every k-mer that occurs twice is in the table with its exact count, one that occurs once
+        is absent or, seldom, there with count 1.  The table is neither read nor written here."""
+        self._prefilter_for(bits)
+        b = bytes(text)
+        _check(self._lib.tsx_hip_prefilter_add_host(self.handle, b, len(b), int(chunk_bytes)))
+
+    def prefilterBgzf(self, gz, bits=None):
+        """The same for the image of a blocked gzip (BGZF) file, inflated on the device (tsx_hip_prefilter_add_bgzf_host)."""
+        self._prefilter_for(bits)
+        b = bytes(gz)
+        _check_bgzf(self._lib.tsx_hip_prefilter_add_bgzf_host(self.handle, b, len(b)))
+
+    def prefilterDevice(self, text_ptr, nbytes, bits=None, stream=None):
+        """tsx_hip_prefilter_add_device: pass 1 over a device text (16-byte aligned).  Queued, not waited for (bits given:
+        creating the filter waits for its zeroing first).  An armed count orders itself behind it, on any stream."""
+        self._prefilter_for(bits)
+        vp = ctypes.c_void_p
+        _check(self._lib.tsx_hip_prefilter_add_device(self.handle, vp(text_ptr), nbytes, vp(stream) if stream else None))
+
+    def armPrefilter(self, on=True):
+        """While on, countFastq / countFastqDevice / countFastqBgzf insert only the windows the prefilter has seen twice
+        (tsx_hip_prefilter_arm).  addKmers, load, combine and the read calls are not gated."""
+        _check(self._lib.tsx_hip_prefilter_arm(self.handle, 1 if on else 0))
+
+    @property
+    def prefilter_bits(self):
+        """The bits of the map's prefilter, 0 without one (tsx_hip_prefilter_bits: host state, no GPU call)."""
+        return int(self._lib.tsx_hip_prefilter_bits(self.handle))
+
+    @property
+    def prefilter_stats(self):
+        """{bits, seen, seen_again, admitted, skipped, set_bits_a, set_bits_b} (tsx_hip_prefilter_stats); all zero without
+        a filter.  Waits for the map's work and counts the set bits of both filters on the GPU: not for a hot loop."""
+        t = PrefilterTotals()
+        _check(self._lib.tsx_hip_prefilter_stats(self.handle, ctypes.byref(t)))
+        return t.as_dict()
+
+    def prefilterWords(self, which):
+        """The 64-bit words of filter 'a' (seen) or 'b' (seen again) as numpy uint64 (tsx_hip_prefilter_read)."""
+        if which not in ("a", "b"):
+            raise ValueError("which: 'a' or 'b', not %r" % (which,))
+        bits = self.prefilter_bits
+        if not bits:
+            raise TSXException(EINVAL, "the map has no prefilter")
+        out = np.zeros(1 << (bits - (6 if which == "a" else 8)), dtype=np.uint64)
+        _check(self._lib.tsx_hip_prefilter_read(self.handle, 0 if which == "a" else 1, _p(out), out.size))
+        return out
+
+    def countTwice(self, text, bits=None):
+        """Count `text` without its singletons: a new prefilter, pass 1, the armed count, disarmed again.  Returns
+        prefilter_stats."""
+        self.createPrefilter(min(max(self.l + 6, PREFILTER_BITS[0]), PREFILTER_BITS[-1]) if bits is None else bits)
+        self.prefilter(text)
+        self.armPrefilter(True)
+        try:
+            self.countFastq(text)
+        finally:
+            self.armPrefilter(False)
+        return self.prefilter_stats
 
     def _pairs(self, call, text1, text2, out1, out2, singles, chunk_bytes):
         """The common part of filterPairs / trimPairs: the four outputs opened (paths) or taken (fds), the call, the

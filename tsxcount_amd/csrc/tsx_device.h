@@ -214,6 +214,32 @@ __device__ __forceinline__ void hash_key(const TableParams &p, LutPtr lut, const
     }
 }
 
+// The hash of a k-mer as an ELEMENT (the tsx_hip_encode layout, canonical maps: after lex_canonical) -- what the sketch
+// (tsx_sketch.h) and the prefilter (tsx_prefilter.h) see of it.  Not the table's key: it depends on neither l, s nor the seed.
+template <int WK>
+__host__ __device__ __forceinline__ uint64_t sketch_hash(const uint64_t (&x)[WK]) {
+    uint64_t v = 0x9E3779B97F4A7C15ULL;
+#pragma unroll
+    for (int t = 0; t < WK; ++t) v = mix64(v ^ x[t]);
+    return v;
+}
+
+// The prefilter's definition (tsx_prefilter.h): two blocked Bloom filters of 64-bit words, A of 2^bits bits and B of
+// 2^(bits - 2).  A key touches ONE word of each -- the top bits of its hash pick it -- and the same mask in both: up to
+// four bits (they may coincide) named by the low 24 bits of the hash.  In the filter: (word & mask) == mask.
+constexpr int PF_BITS_MIN = 12, PF_BITS_MAX = 38;
+__host__ __device__ __forceinline__ uint64_t pf_mask(uint64_t v) {
+    return (1ULL << (v & 63)) | (1ULL << ((v >> 6) & 63)) | (1ULL << ((v >> 12) & 63)) | (1ULL << ((v >> 18) & 63));
+}
+__host__ __device__ __forceinline__ uint64_t pf_word_a(uint64_t v, int bits) { return v >> (64 - (bits - 6)); }
+__host__ __device__ __forceinline__ uint64_t pf_word_b(uint64_t v, int bits) { return v >> (64 - (bits - 8)); }
+// What a counting kernel that consults the filter gets (pass 2): B, and the two totals it adds to.
+struct PfView {
+    const unsigned long long *b;
+    unsigned long long *admitted, *skipped;
+    int bits;
+};
+
 // The mirror roll (canonical walks, one-limb keys): the reverse complement of the next window is
 // rc(x') = comp(in) + z^2 (rc(x) - comp(out) z^(2k-2)), so h(rc x') = z^2 h(rc x) + c comp(in) - c comp(out) z^2k:
 // a shift the other way and one lookup in the 64-entry table p.roll[MROLL1_AT + (top two bits of h(rc x) | out << 2 |

@@ -233,11 +233,14 @@ __device__ __forceinline__ bool kmer_eq(const uint64_t (&a)[WK], const uint64_t 
 //      insert carrying the slot's total.
 // CANON (canonical counting): the key of a k-mer is min(h(x), h(rc x)); the LDS dedup still merges equal k-mers only.
 // BR (base rule): rule_bits16 breaks windows as newlines do.
-template <int WK, bool CANON = false, bool BR = false>
+// PF (pass 2 of the prefilter, tsx_prefilter.h): a run leader whose mask is not in filter B -- its k-mer was seen once
+// at most -- takes no dedup slot and inserts nothing; its run's windows are counted as skipped, the others as admitted,
+// and only these reach ST_KMERS.  B is complete before this kernel starts and only read here.
+template <int WK, bool CANON = false, bool BR = false, bool PF = false>
 __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableParams p, const uint8_t *buf, uint64_t n,
                                                          uint64_t own_end, int head_open,
                                                          const uint32_t *tile_line, uint64_t ntiles,
-                                                         const uint16_t *qmap = nullptr) {
+                                                         const uint16_t *qmap = nullptr, PfView pf = PfView()) {
     __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
     __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
     __shared__ uint64_t s_le[TILE / 64];
@@ -254,6 +257,7 @@ __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableP
     if (tid < 3) s_nl[(TILE + HALO) / 64 + tid] = ~0ULL;
     if (tid < 2) s_codes[(TILE + HALO) / 32 + tid] = 0;
     unsigned long long added = 0;
+    [[maybe_unused]] unsigned long long skipped = 0;   // PF: windows of the runs the filter kept out
     const uint32_t k = (uint32_t)p.k;
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t base = tile * TILE;
@@ -321,8 +325,21 @@ __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableP
                 const unsigned long long bnd = __ballot(leader || !valid);
                 const unsigned long long above = (lane == 63) ? 0ULL : (bnd >> (lane + 1));
                 const uint32_t runlen = (above ? (uint32_t)__builtin_ctzll(above) : (uint32_t)(63 - lane)) + 1u;
-                added += valid ? 1ULL : 0ULL;
-                if (leader) {
+                bool admit = leader;
+                if constexpr (PF) {
+                    if (leader) {
+                        uint64_t e[WK];
+#pragma unroll
+                        for (int t = 0; t < WK; ++t) e[t] = x[t];
+                        if constexpr (CANON) lex_canonical<WK>(e, p.n);
+                        const uint64_t v = sketch_hash<WK>(e), mask = pf_mask(v);
+                        admit = (pf.b[pf_word_b(v, pf.bits)] & mask) == mask;
+                        if (admit) added += runlen; else skipped += runlen;
+                    }
+                } else {
+                    added += valid ? 1ULL : 0ULL;
+                }
+                if (admit) {
                     hash_key<CANON, WK>(p, (const uint64_t *)s_lut, x, hk[j]);
                     uint32_t slot = (uint32_t)(mix64(hk[j][0] ^ (WK > 1 ? hk[j][WK - 1] : 0)) >> 40) & (DSLOTS - 1);
                     slot_of[j] = -2; direct_cnt[j] = runlen;
@@ -363,6 +380,11 @@ __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableP
     }
     for (int d = 32; d > 0; d >>= 1) added += __shfl_down(added, d, 64);
     if (lane == 0 && added) atomicAdd(&p.stats[ST_KMERS], added);
+    if constexpr (PF) {
+        for (int d = 32; d > 0; d >>= 1) skipped += __shfl_down(skipped, d, 64);
+        if (lane == 0 && added) atomicAdd(pf.admitted, added);
+        if (lane == 0 && skipped) atomicAdd(pf.skipped, skipped);
+    }
 }
 
 // ---- the scan in two kernels: describe the strips, then walk them ------------------------------------------

@@ -581,6 +581,9 @@ extern "C" int tsx_hip_group_merge(tsx_hip_group *g) {
 // countKMers for N GPUs (main.cpp:104-218 + the merge): text -> record shards -> per-GPU tables -> merged tables.
 extern "C" int tsx_hip_group_count_fastq_host(tsx_hip_group *g, const char *text, size_t n) {
     if (!g || (!text && n)) return TSX_HIP_EINVAL;
+    // each GPU sees one shard of the records: a k-mer's two occurrences may lie in two shards, no per-map filter finds them
+    for (int r = 0; r < g->n; ++r)
+        if (tsx_hip_prefilter_armed(g->maps[r]) == 1) { g_multi_error = "a map of the group has a prefilter armed (one GPU only)"; return TSX_HIP_EINVAL; }
     const std::vector<size_t> cuts = cut_records(text, n, g->n, g->lines_per_record);
     if (g->exchange == 1) {
         size_t max_len = 0;

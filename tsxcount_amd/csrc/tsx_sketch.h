@@ -19,13 +19,7 @@ namespace tsx {
 
 constexpr int SKETCH_P_MIN = 10, SKETCH_P_MAX = 14;
 
-template <int WK>
-__host__ __device__ __forceinline__ uint64_t sketch_hash(const uint64_t (&x)[WK]) {
-    uint64_t v = 0x9E3779B97F4A7C15ULL;
-#pragma unroll
-    for (int t = 0; t < WK; ++t) v = mix64(v ^ x[t]);
-    return v;
-}
+// (sketch_hash: tsx_device.h -- the prefilter consulted by count_fastq_kernel hashes the same element)
 // The register a hash raises and the rank it raises it to (1 .. 64 - p + 1).
 __host__ __device__ __forceinline__ void sketch_slot(uint64_t v, int prec, uint32_t &idx, uint32_t &rank) {
     idx = (uint32_t)(v >> (64 - prec));

@@ -15,6 +15,7 @@
 #include "tsx_trim.h"
 #include "tsx_median.h"
 #include "tsx_sketch.h"
+#include "tsx_prefilter.h"
 #include "tsx_pairs.h"
 #include "tsx_own.h"
 
@@ -162,6 +163,12 @@ struct tsx_hip_map {
     DevBuf<uint8_t> d_fa_out;
     DevBuf<uint32_t> d_fa_ws;
     DevBuf<uint32_t> d_fa_carry;
+    // prefilter (tsx_prefilter.h): filter A of 2^pf_bits bits, B of a quarter, the totals (PfTotal); pf_bits 0 = none
+    DevBuf<unsigned long long> pf_a, pf_b, pf_tot;
+    int pf_bits = 0;
+    bool pf_armed = false;               // the FASTQ counting calls consult B (tsx_hip_prefilter_arm)
+    Event pf_ev;                         // what the map's stream holds for the filters, for a caller's stream to wait for
+    PfView pf_view() const { return PfView{pf_b.get(), pf_tot.get() + PF_ADMITTED, pf_tot.get() + PF_SKIPPED, pf_bits}; }
     Event clear_ev, join_ev;
     bool clear_ev_set = false;
     hipStream_t foreign = nullptr;       // (a caller's: not owned)
@@ -1129,6 +1136,8 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
     const uint64_t shard_cap = sh.send_cap;
     unsigned long long *shard_counts = sh.counts;
     if (own_end == 0) return TSX_HIP_OK;
+    // (the counting entry points refuse these before they queue anything: prefilter_count_ok)
+    if (m->pf_armed && (shard_send || dsc.out || dsc.owners)) return TSX_HIP_EINVAL;
     const uint64_t ntiles = (own_end + TILE - 1) / TILE;
     TSX_TRY(ensure_tiles(m, ntiles, st));
     Event *ev = nullptr;
@@ -1194,14 +1203,21 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
     // once (2 x table bytes at worst), the atomic path pays ~60 ps per k-mer.
     const TableParams &p = m->p;
     // (a table built slab by slab takes its partitioned path in count_slabs, over the whole text at once)
-    const bool use_part = shard_send || (can_partition(m) && !slab_bits(m) &&
-                                         (m->path == 2 || (m->path == 0 && own_end * 32 >= m->lay.table_bytes)));
+    // An armed prefilter: the atomic path whatever the ratio of text to table (the partitioned walk does not consult B).
+    const bool use_part = !m->pf_armed && (shard_send || (can_partition(m) && !slab_bits(m) &&
+                                         (m->path == 2 || (m->path == 0 && own_end * 32 >= m->lay.table_bytes))));
     if (!use_part) {
         int rcz = ensure_zeroed(m, st);
         if (rcz != TSX_HIP_OK) return rcz;
-        DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV, BRV>), dim3(g3), dim3(NT),
-                                                            lut_bytes, st, m->p, d_text, n, own_end, head_open,
-                                                            (const uint32_t *)m->d_tile.get(), ntiles, m->qmap_cur))));
+        if (m->pf_armed) {
+            DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV, BRV, true>), dim3(g3), dim3(NT),
+                                                                lut_bytes, st, m->p, d_text, n, own_end, head_open,
+                                                                (const uint32_t *)m->d_tile.get(), ntiles, m->qmap_cur, m->pf_view()))));
+        } else {
+            DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV, BRV>), dim3(g3), dim3(NT),
+                                                                lut_bytes, st, m->p, d_text, n, own_end, head_open,
+                                                                (const uint32_t *)m->d_tile.get(), ntiles, m->qmap_cur))));
+        }
         HIP_TRY(hipGetLastError());
         if (ev) for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i].get(), st));
         return TSX_HIP_OK;
@@ -2482,11 +2498,34 @@ static int count_resident(tsx_hip_map *m, const char *text, size_t n, DeviceForm
 // Device texts are processed in windows so that the partition scratch (about
 // 10 bytes per text byte) stays bounded; windows overlap by the k-1 byte halo
 // exactly like the host pieces.
+// An armed prefilter (tsx_prefilter.h) is consulted by the atomic path of a whole table alone.  Checked before anything
+// is queued.
+// Pass 1 writes the filters on whatever stream it was given, pass 2 reads B on whatever stream it is given.  Before
+// pick_stream of an armed count: the map's stream goes behind the last caller's stream (join_foreign), and a caller's
+// `stream` behind the map's -- so B is complete before it is read, whichever streams the two passes ran on.
+static int prefilter_order(tsx_hip_map *m, void *stream) {
+    join_foreign(m, false);
+    if (stream && (hipStream_t)stream != m->stream.get()) {
+        HIP_TRY(hipEventRecord(m->pf_ev.get(), m->stream.get()));
+        HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, m->pf_ev.get(), 0));
+    }
+    return TSX_HIP_OK;
+}
+
+static int prefilter_count_ok(const tsx_hip_map *m) {
+    if (!m->pf_armed) return TSX_HIP_OK;
+    if (m->p.lg != m->p.l) { g_last_error = "prefilter armed: a map created with shard_bits > 0"; return TSX_HIP_EINVAL; }
+    if (slab_bits(m)) { g_last_error = "prefilter armed: a table above 2^32 slots is built slab by slab, without the filter"; return TSX_HIP_EINVAL; }
+    return TSX_HIP_OK;
+}
+
 extern "C" int tsx_hip_count_fastq_device(tsx_hip_map *m, const void *dev_text, size_t n, void *stream) {
     if (!m || (!dev_text && n) || ((uintptr_t)dev_text & 15)) return TSX_HIP_EINVAL;
+    TSX_TRY(prefilter_count_ok(m));
     if (m->p.lg != m->p.l) return TSX_HIP_EINVAL;   // a shard: keys of other owners must travel (shard_scan / shard_build)
     if (n) m->used = true;
     HIP_TRY(hipSetDevice(m->device));
+    if (m->pf_armed) TSX_TRY(prefilter_order(m, stream));   // behind pass 1, on whichever stream it ran
     hipStream_t st = pick_stream(m, stream);
     const uint8_t *base = (const uint8_t *)dev_text;
     // a quality rule: the bitmap of the whole (resident) text, read by each window at its offset
@@ -2530,6 +2569,7 @@ static int count_bgzf_records(tsx_hip_map *m, const uint8_t *gz, size_t n, const
 
 extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, size_t n) {
     if (!m || (!gz && n)) return TSX_HIP_EINVAL;
+    TSX_TRY(prefilter_count_ok(m));
     if (m->p.lg != m->p.l) return TSX_HIP_EINVAL;   // see tsx_hip_count_fastq_device
     if (n) m->used = true;
     BgzfIndex ix;
@@ -2596,9 +2636,11 @@ extern "C" int tsx_hip_count_fastq_bgzf_host(tsx_hip_map *m, const void *gz, siz
 
 extern "C" int tsx_hip_count_fastq_host(tsx_hip_map *m, const char *text, size_t n) {
     if (!m || (!text && n)) return TSX_HIP_EINVAL;
+    TSX_TRY(prefilter_count_ok(m));
     if (m->p.lg != m->p.l) return TSX_HIP_EINVAL;   // see tsx_hip_count_fastq_device
     if (n) m->used = true;
     HIP_TRY(hipSetDevice(m->device));
+    if (m->pf_armed) join_foreign(m, false);   // behind a pass 1 on a caller's stream
     HIP_TRY(hipStreamSynchronize(m->stream.get()));
     if (slab_build_wanted(m, n)) return count_resident(m, text, n, tsx_hip_count_fastq_device);
     int rc = base_rule_ok(m);
@@ -2659,6 +2701,7 @@ struct FastaScope {
 static int fasta_args_ok(const tsx_hip_map *m) {
     if (m->p.lg != m->p.l) { g_last_error = "wrapped FASTA: a map created with shard_bits > 0"; return TSX_HIP_EINVAL; }
     if (m->minq) { g_last_error = "wrapped FASTA: min_qual_char needs FASTQ records (a FASTA text has no quality line)"; return TSX_HIP_EINVAL; }
+    if (m->pf_armed) { g_last_error = "wrapped FASTA: a prefilter is armed (pass 1 reads FASTQ or two-line records)"; return TSX_HIP_EINVAL; }
     return TSX_HIP_OK;
 }
 static int fasta_begin(tsx_hip_map *m, hipStream_t st) {   // the carry of a new text: at a line start, no open record
@@ -4862,6 +4905,184 @@ extern "C" int tsx_hip_suggest_l(int k, double distinct, int precision, uint32_t
         return distinct / std::ldexp(1.0, hi) > 0.9 ? TSX_HIP_ERANGE : TSX_HIP_OK;
     }
     *l_out = l;
+    return TSX_HIP_OK;
+}
+
+// ---- counting only the k-mers seen twice: the prefilter of a map, its two passes (tsx_prefilter.h) -------------------
+static bool prefilter_bits_ok(int bits) { return bits >= PF_BITS_MIN && bits <= PF_BITS_MAX; }
+static inline size_t pf_words_a(int bits) { return (size_t)1 << (bits - 6); }
+static inline size_t pf_words_b(int bits) { return (size_t)1 << (bits - 8); }
+
+extern "C" int tsx_hip_prefilter_create(tsx_hip_map *m, int bits) {
+    if (!m || !prefilter_bits_ok(bits)) return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    join_foreign(m, false);
+    hipStream_t st = m->stream.get();
+    HIP_TRY(hipStreamSynchronize(st));   // (filters that are replaced may still be read)
+    m->pf_bits = 0; m->pf_armed = false;
+    int rc = m->pf_a.alloc(pf_words_a(bits) * 8);
+    if (rc == TSX_HIP_OK) rc = m->pf_b.alloc(pf_words_b(bits) * 8);
+    if (rc == TSX_HIP_OK && !m->pf_tot.get()) rc = m->pf_tot.alloc(PF_NTOT * sizeof(unsigned long long));
+    if (rc == TSX_HIP_OK && !m->pf_ev.get()) rc = m->pf_ev.create();
+    if (rc != TSX_HIP_OK) { m->pf_a.reset(); m->pf_b.reset(); return rc; }
+    HIP_TRY(hipMemsetAsync(m->pf_a.get(), 0, pf_words_a(bits) * 8, st));
+    HIP_TRY(hipMemsetAsync(m->pf_b.get(), 0, pf_words_b(bits) * 8, st));
+    HIP_TRY(hipMemsetAsync(m->pf_tot.get(), 0, PF_NTOT * sizeof(unsigned long long), st));
+    // waited for: pass 1 may come on a caller's stream, which nothing else orders behind this one (creating is not hot)
+    HIP_TRY(hipStreamSynchronize(st));
+    m->pf_bits = bits;
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_prefilter_free(tsx_hip_map *m) {
+    if (!m) return TSX_HIP_EINVAL;
+    if (!m->pf_bits) return TSX_HIP_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    join_foreign(m, true);
+    HIP_TRY(hipStreamSynchronize(m->stream.get()));
+    m->pf_bits = 0; m->pf_armed = false;
+    m->pf_a.reset(); m->pf_b.reset();
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_prefilter_arm(tsx_hip_map *m, int on) {
+    if (!m || (on && !m->pf_bits)) return TSX_HIP_EINVAL;
+    m->pf_armed = on != 0;
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_prefilter_bits(const tsx_hip_map *m) {
+    if (!m) return TSX_HIP_EINVAL;
+    return m->pf_bits;
+}
+
+extern "C" int tsx_hip_prefilter_armed(const tsx_hip_map *m) {
+    if (!m) return TSX_HIP_EINVAL;
+    return m->pf_armed ? 1 : 0;
+}
+
+// prefilter_windows_kernel over the start positions [0, own_end) of d_text (n readable bytes), after query_line_pass.
+static int prefilter_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
+                            const unsigned long long *d_line_base, hipStream_t st) {
+    if (own_end == 0) return TSX_HIP_OK;
+    const uint64_t ntiles = (own_end + TILE - 1) / TILE;
+    const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8);
+    DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((prefilter_windows_kernel<WKV, CANV, BRV>), dim3(grid), dim3(NT), 0,
+                                                        st, m->p, d_text, n, own_end, head_open, (const uint32_t *)m->d_tile.get(),
+                                                        ntiles, d_line_base, m->pf_bits, m->pf_a.get(), m->pf_b.get(),
+                                                        m->pf_tot.get(), m->qmap_cur))));
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// One piece: piece_front, then pass 1 over its whole records [0, cut), queued and not waited for.  Not last and no
+// whole record: nrec = 0, nothing done.
+static int prefilter_piece(tsx_hip_map *m, PieceBufs &p, const uint8_t *d_text, uint64_t len, bool last, hipStream_t st,
+                           uint64_t &cut, uint64_t &nrec, bool &open) {
+    TSX_TRY(piece_front(m, p, d_text, len, last, false, cut, nrec, open));
+    if (nrec == 0) return TSX_HIP_OK;
+    QmapScope qs(m);
+    TSX_TRY(piece_qmap(m, d_text, cut, st));
+    return prefilter_launch(m, d_text, cut, cut, 0, p.info.get() + 4, st);
+}
+
+extern "C" int tsx_hip_prefilter_add_host(tsx_hip_map *m, const char *text, size_t n, size_t chunk_bytes) {
+    if (!m || !m->pf_bits || (!text && n)) return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = m->stream.get();
+    PieceBufs p(st);
+    uint64_t rec_base = 0;
+    return host_pieces(m, p, text, n, chunk_bytes, true, rec_base,
+        [&](const uint8_t *d_text, uint64_t len, bool last, uint64_t &cut, uint64_t &nrec, bool &open) {
+            return prefilter_piece(m, p, d_text, len, last, st, cut, nrec, open);
+        },
+        [&](size_t, uint64_t, uint64_t, uint64_t, bool) -> int { return TSX_HIP_OK; });
+}
+
+// The pieces of bgzf_record_pieces, without a limit on the carried record.
+extern "C" int tsx_hip_prefilter_add_bgzf_host(tsx_hip_map *m, const void *gz, size_t n) {
+    if (!m || !m->pf_bits || (!gz && n)) return TSX_HIP_EINVAL;
+    BgzfIndex ix;
+    if (!bgzf_index((const uint8_t *)gz, n, ix)) { g_last_error = "not a BGZF file (no BC extra field in every gzip member)"; return TSX_HIP_EINVAL; }
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = m->stream.get();
+    join_foreign(m, false);
+    TSX_TRY(base_rule_ok(m));
+    PieceBufs p(st);
+    TSX_TRY(p.init());
+    return bgzf_record_pieces((const uint8_t *)gz, n, ix, SIZE_MAX, st, [&](const uint8_t *piece, uint64_t len, bool last, uint64_t &cut) -> int {
+        uint64_t nrec = 0;
+        bool open = false;
+        return prefilter_piece(m, p, piece, len, last, st, cut, nrec, open);
+    });
+}
+
+extern "C" int tsx_hip_prefilter_add_device(tsx_hip_map *m, const void *dev_text, size_t n, void *stream) {
+    if (!m || !m->pf_bits || (!dev_text && n) || ((uintptr_t)dev_text & 15)) return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    TSX_TRY(base_rule_ok(m));
+    const uint8_t *base = (const uint8_t *)dev_text;
+    return device_windows(m, base, n, false, st,
+                          [&](size_t off, size_t own, size_t len, int head_open, bool, const unsigned long long *d_base) {
+                              return prefilter_launch(m, base + off, len, own, head_open, d_base, st);
+                          });
+}
+
+extern "C" int tsx_hip_prefilter_stats(tsx_hip_map *m, tsx_hip_prefilter_totals *out) {
+    if (!m || !out) return TSX_HIP_EINVAL;
+    memset(out, 0, sizeof *out);
+    if (!m->pf_bits) return TSX_HIP_OK;
+    HIP_TRY(hipSetDevice(m->device));
+    join_foreign(m, true);
+    hipStream_t st = m->stream.get();
+    unsigned long long *tot = m->pf_tot.get();
+    HIP_TRY(hipMemsetAsync(tot + PF_SET_A, 0, 2 * sizeof(unsigned long long), st));
+    const uint64_t na = pf_words_a(m->pf_bits), nb = pf_words_b(m->pf_bits);
+    hipLaunchKernelGGL(prefilter_fill_kernel, dim3(grid_for(m, na, 8)), dim3(NT), 0, st, (const unsigned long long *)m->pf_a.get(), na,
+                       (const unsigned long long *)m->pf_b.get(), nb, tot);
+    HIP_TRY(hipGetLastError());
+    unsigned long long h[PF_NTOT];
+    HIP_TRY(hipMemcpyAsync(h, tot, sizeof h, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out->bits = (uint64_t)m->pf_bits;
+    out->seen = h[PF_SEEN]; out->seen_again = h[PF_AGAIN]; out->admitted = h[PF_ADMITTED]; out->skipped = h[PF_SKIPPED];
+    out->set_bits_a = h[PF_SET_A]; out->set_bits_b = h[PF_SET_B];
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_prefilter_read(tsx_hip_map *m, int which, uint64_t *words_out, size_t nwords) {
+    if (!m || !m->pf_bits || which < 0 || which > 1 || (!words_out && nwords)) return TSX_HIP_EINVAL;
+    const size_t have = which ? pf_words_b(m->pf_bits) : pf_words_a(m->pf_bits);
+    if (nwords != have) return TSX_HIP_ERANGE;
+    HIP_TRY(hipSetDevice(m->device));
+    join_foreign(m, true);
+    HIP_TRY(hipMemcpyAsync(words_out, which ? m->pf_b.get() : m->pf_a.get(), have * 8, hipMemcpyDeviceToHost, m->stream.get()));
+    HIP_TRY(hipStreamSynchronize(m->stream.get()));
+    return TSX_HIP_OK;
+}
+
+template <int WK>
+static void prefilter_mask_of(const uint64_t *kmer, uint64_t top, int bits, uint64_t *word_a, uint64_t *word_b, uint64_t *mask) {
+    uint64_t x[WK];
+    for (int t = 0; t < WK; ++t) x[t] = kmer[t];
+    x[WK - 1] &= top;
+    const uint64_t v = sketch_hash<WK>(x);
+    if (word_a) *word_a = pf_word_a(v, bits);
+    if (word_b) *word_b = pf_word_b(v, bits);
+    if (mask) *mask = pf_mask(v);
+}
+
+extern "C" int tsx_hip_prefilter_mask_host(int k, const uint64_t *kmer_limbs, int bits, uint64_t *word_a, uint64_t *word_b,
+                                           uint64_t *mask) {
+    if (k < 1 || k > 127 || !kmer_limbs || !prefilter_bits_ok(bits)) return TSX_HIP_EINVAL;
+    const uint64_t top = ((2 * k) & 63) ? ((1ULL << ((2 * k) & 63)) - 1ULL) : ~0ULL;
+    switch ((2 * k + 63) / 64) {
+        case 1: prefilter_mask_of<1>(kmer_limbs, top, bits, word_a, word_b, mask); break;
+        case 2: prefilter_mask_of<2>(kmer_limbs, top, bits, word_a, word_b, mask); break;
+        case 3: prefilter_mask_of<3>(kmer_limbs, top, bits, word_a, word_b, mask); break;
+        default: prefilter_mask_of<4>(kmer_limbs, top, bits, word_a, word_b, mask); break;
+    }
     return TSX_HIP_OK;
 }
 

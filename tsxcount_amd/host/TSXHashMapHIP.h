@@ -354,6 +354,26 @@ public:
         check(rc);
         return t;
     }
+    // counting only the k-mers seen twice (tsx_hip_prefilter_*): pass 1 puts the k-mers of a text into the map's prefilter
+    // (iBits != 0: a new filter of 2^iBits bits first; 0: the one the map has -- several texts accumulate); while armed,
+    // the FASTQ counting calls insert only what the filter has seen twice.  After both passes over the same input every
+    // k-mer that occurs twice has its exact count; one that occurs once is absent or, seldom, there with count 1.
+    void prefilter(const char *pText, size_t iBytes, int iBits = 0, size_t iChunkBytes = 0) {
+        if (iBits) check(tsx_hip_prefilter_create(m_pMap, iBits));
+        check(tsx_hip_prefilter_add_host(m_pMap, pText, iBytes, iChunkBytes));
+    }
+    void prefilterBgzf(const void *pGz, size_t iBytes, int iBits = 0) {
+        if (iBits) check(tsx_hip_prefilter_create(m_pMap, iBits));
+        const int rc = tsx_hip_prefilter_add_bgzf_host(m_pMap, pGz, iBytes);
+        if (rc == TSX_HIP_EINVAL && *tsx_hip_last_error()) throw TSXException(std::string("BGZF input: ") + tsx_hip_last_error(), rc);
+        check(rc);
+    }
+    void armPrefilter(bool bOn = true) { check(tsx_hip_prefilter_arm(m_pMap, bOn ? 1 : 0)); }
+    tsx_hip_prefilter_totals prefilterStats() {
+        tsx_hip_prefilter_totals t;
+        check(tsx_hip_prefilter_stats(m_pMap, &t));
+        return t;
+    }
     // the distinct k-mers a sketch stands for (tsx_hip_sketch_estimate_host)
     static double estimate(const std::vector<uint8_t> &oRegs) {
         int p = 0;

@@ -72,6 +72,9 @@ struct arguments {
     // --estimate prints that line and stops
     bool l_auto = false, estimate = false;
     double load_factor = 0.75;
+    // --min-count=2: two passes over --input, the first into a prefilter of 2^prefilter_bits bits (0: l + 6), so that k-mers
+    // seen once take no slot
+    int min_count = 1, prefilter_bits = 0;
 };
 
 static bool opt(const char *arg, const char *name, std::string &val) {
@@ -83,6 +86,7 @@ static bool opt(const char *arg, const char *name, std::string &val) {
 
 static int usage() {
     std::cerr << "Usage: tsxCount [--input=FASTQ|FASTA[.gz]] [--k=K] [--l=L|auto [--load-factor=F]] [--estimate] [--s=STORAGE]\n"
+                 "                [--min-count=1|2 [--prefilter-bits=B]]\n"
                  "                [--mode=HIP] [--threads=T]\n"
                  "                [--check] [--checkabort] [--seed=S] [--device=D] [--format=fastq|fasta|fasta-wrapped] [--canonical]\n"
                  "                [--acgt-only] [--min-qual-char=C]\n"
@@ -105,6 +109,13 @@ static int usage() {
                  "--estimate prints that line and stops: nothing is counted, --k is required, --l is ignored. Both take plain,\n"
                  ".gz and BGZF input with --canonical, --acgt-only and --min-qual-char; one GPU, no --load / --with, no wrapped\n"
                  "FASTA. l is at most min(36, 2k - 1): where that leaves the load above 0.9 a warning says so.\n"
+                 "--min-count=2 keeps the k-mers that occur once out of the table: the input is read twice, first into a Bloom\n"
+                 "prefilter of 2^B bits (--prefilter-bits=B, 12 .. 38, default l + 6) and a second one a quarter its size, then\n"
+                 "counted; only k-mers the filter has seen twice are inserted. Every k-mer that occurs twice or more has its exact\n"
+                 "count; one that occurs once is absent or, seldom, there with count 1: --output --lower=2, --histo from 2 on,\n"
+                 "--filter and --trim at their default lower bound are those of a plain count. It prints\n"
+                 "prefilter<TAB>bits<TAB>kmers<TAB>seen_again<TAB>admitted<TAB>skipped. One GPU; no --check, --load, --l=auto or\n"
+                 "wrapped FASTA. A --save made this way holds no complete set of the k-mers seen once.\n"
                  "--format=fasta reads two lines per record (a header, ONE sequence line), as file names ending in .fa, .fasta\n"
                  "or .fna do. --format=fasta-wrapped reads FASTA whose sequences are wrapped over several lines (what genome and\n"
                  "assembly downloads look like): the lines of a record are joined on the GPU, k-mers across line breaks count.\n"
@@ -695,6 +706,16 @@ int main(int argc, char *argv[]) {
         }
         else if (opt(argv[i], "estimate", v)) a.estimate = true;
         else if (opt(argv[i], "load-factor", v)) a.load_factor = atof(v.c_str());
+        else if (opt(argv[i], "min-count", v)) {
+            if (v != "1" && v != "2") { std::cerr << "--min-count takes 1 (count every k-mer) or 2 (keep k-mers seen once out of the table)" << std::endl; return usage(); }
+            a.min_count = atoi(v.c_str());
+        }
+        else if (opt(argv[i], "prefilter-bits", v)) {
+            char *end = nullptr;
+            const long b = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || b < 12 || b > 38) { std::cerr << "--prefilter-bits is the log2 of the prefilter's size in bits: a number 12 .. 38" << std::endl; return usage(); }
+            a.prefilter_bits = (int)b;
+        }
         else if (opt(argv[i], "s", v)) { a.storagebits = atoi(v.c_str()); a.given_s = true; }
         else if (opt(argv[i], "threads", v)) a.threads = atoi(v.c_str());
         else if (opt(argv[i], "input", v)) a.input_path = v;
@@ -788,6 +809,23 @@ int main(int argc, char *argv[]) {
             return usage();
         }
         a.group = false;   // --gpus=1: the one table of this process
+    }
+    if (a.min_count == 2) {   // what the two-pass count refuses, before anything is read
+        std::string why;
+        if (a.input_path.empty()) why = "--min-count=2 needs --input=FILE: it reads the input twice";
+        else if (a.gpus > 1) why = "--min-count=2 runs on one GPU only: each GPU of a --gpus " + std::to_string(a.gpus) + " run sees a share of the reads, and a k-mer's two occurrences may lie in two shares";
+        else if (is_wrapped(a)) why = "--min-count=2 does not read --format=fasta-wrapped: the prefilter reads FASTQ or two-line FASTA records";
+        else if (a.check) why = "--min-count=2 does not go with --check: the reference's count file holds the k-mers seen once";
+        else if (!a.load.empty()) why = "--min-count=2 does not go with --load: a database's k-mers were never shown to the prefilter";
+        else if (a.l_auto || a.estimate) why = "--min-count=2 does not go with --l=auto or --estimate: the sketch sizes the table for all k-mers, those seen once included";
+        if (!why.empty()) {
+            std::cerr << why << std::endl;
+            return usage();
+        }
+        a.group = false;   // --gpus=1: the one table of this process
+    } else if (a.prefilter_bits) {
+        std::cerr << "--prefilter-bits needs --min-count=2" << std::endl;
+        return usage();
     }
     if (a.input_path.empty() && a.load.empty()) return usage();
     // --load: the first database sets k, l, s and the seed unless they are given; every one must match the counting mode
@@ -1017,6 +1055,22 @@ int main(int argc, char *argv[]) {
             const uint64_t iEntries = oMap.loadDatabase(db);
             std::cerr << "Loaded " << iEntries << " kmers from " << db << std::endl;
         }
+        if (a.min_count == 2) {   // pass 1: the input into the prefilter; the count below is pass 2
+            const int bits = a.prefilter_bits ? a.prefilter_bits : std::min(38, std::max(12, a.l + 6));
+            if (bgzf) {
+                try {
+                    oMap.prefilterBgzf(text, n, bits);
+                } catch (const TSXException &e) {   // (as the count below: without room for the batches, through zlib)
+                    if (e.code() != TSX_HIP_ENOMEM) throw;
+                    std::cerr << "BGZF on the device: " << e.what() << " -- reading through zlib instead" << std::endl;
+                    if (!read_gz(a.input_path, owned)) { std::cerr << "Could not read " << a.input_path << std::endl; return 3; }
+                    if (map) munmap(map, n);
+                    map = nullptr; text = owned.data(); n = owned.size(); bgzf = false;
+                }
+            }
+            if (!bgzf) oMap.prefilter(text, n, bits);
+            oMap.armPrefilter(true);
+        }
         if (a.input_path.empty()) {
             // nothing to count: the loaded tables are the result
         } else if (bgzf) {
@@ -1041,6 +1095,13 @@ int main(int argc, char *argv[]) {
         }
         double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (map) munmap(map, n);
+        if (a.min_count == 2) {
+            oMap.armPrefilter(false);
+            const tsx_hip_prefilter_totals pt = oMap.prefilterStats();
+            std::cout << "prefilter\t" << pt.bits << '\t' << pt.seen << '\t' << pt.seen_again << '\t' << pt.admitted << '\t' << pt.skipped << std::endl;
+            std::cerr << "Prefilter: " << pt.skipped << " of " << pt.seen << " k-mer occurrences kept out of the table; filter fill "
+                      << pt.set_bits_a << " / 2^" << pt.bits << " and " << pt.set_bits_b << " / 2^" << (pt.bits - 2) << " bits" << std::endl;
+        }
         if (a.with.empty()) {
             const int rc = report_and_check(oMap, a, dt);
             if (!wants_queries(a) && !wants_trim(a)) return rc;
