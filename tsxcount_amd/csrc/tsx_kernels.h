@@ -218,6 +218,121 @@ __device__ __forceinline__ bool kmer_eq(const uint64_t (&a)[WK], const uint64_t 
     return e;
 }
 
+// ---- the tile front end: what every kernel that walks a text tile by tile does first ---------------------------------
+// A tile loop reads:  lds_barrier (previous tile's LDS fully consumed); tile_stage(tile_load(..)); lds_barrier; then, per
+// start position pp of the tile, window_valid -> extract_kmer -> run_leader / run_length.  The two strip_desc kernels
+// share the LDS block, load and stage only: they test sixteen windows per lane with bit smears of their own.
+
+// The LDS block of a tile.  LB: what a kernel keeps of the line index at the start of every 16 bytes -- uint8_t, the low
+// two bits (all the record rule needs when the line base is 0), or uint32_t, the whole index (added to *line_base).
+template <typename LB>
+struct alignas(16) TileLds {   // (a multiple of 16 bytes: what follows it in LDS stays 16-byte aligned)
+    uint64_t codes[(TILE + HALO) / 32 + 2];   // 2-bit codes of tile + halo; two zero words behind (extract_kmer reads on)
+    uint64_t nl[(TILE + HALO) / 64 + 3];      // newline and base-rule break flags; three ~0 words behind (the window funnel)
+    uint64_t le[TILE / 64];                   // line-end flags of the tile
+    LB lb[TILE / 16];
+    uint32_t wsum[NT / 64];                   // line ends per wave
+    __device__ __forceinline__ void set_sentinels(int tid) {   // once per kernel: no stage writes them
+        if (tid < 3) nl[(TILE + HALO) / 64 + tid] = ~0ULL;
+        if (tid < 2) codes[(TILE + HALO) / 32 + tid] = 0;
+    }
+};
+
+// What a lane reads of a tile: its 16 bytes, 16 bytes of the halo (lanes < HALO / 16), whether the byte before its 16 is
+// a newline, and the line index at the tile's start.
+struct TileText {
+    uint4 v, hv;   // (hv: set in lanes < HALO / 16 only)
+    bool pnl;
+    uint32_t line;
+};
+__device__ __forceinline__ TileText tile_load(const uint8_t *buf, uint64_t n, int head_open, const uint32_t *tile_line,
+                                              uint64_t tile, int tid) {
+    const uint64_t off = tile * TILE + (uint64_t)tid * 16;
+    TileText t;
+    t.v = load16(buf, off, n);
+    if (tid < HALO / 16) t.hv = load16(buf, off + TILE, n);
+    t.pnl = prev_is_nl(buf, off, n, head_open);
+    t.line = tile_line[tile];
+    return t;
+}
+
+// Classify into the LDS block (BR: the base rule's break bits join the newline flags), then the workgroup prefix sum of
+// line ends -> lb.  One barrier inside; the caller's barrier behind it makes the block readable.
+template <bool BR, typename LB>
+__device__ __forceinline__ void tile_stage(TileLds<LB> &s, const TileText &t, const TableParams &p, const uint16_t *qmap,
+                                           uint64_t base, uint64_t n, int tid) {
+    uint32_t nl, le, code;
+    classify16(t.v, t.pnl, nl, le, code);
+    if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, t.v, base + (uint64_t)tid * 16, n);
+    reinterpret_cast<uint32_t *>(s.codes)[tid] = code;
+    reinterpret_cast<uint16_t *>(s.nl)[tid] = (uint16_t)nl;
+    reinterpret_cast<uint16_t *>(s.le)[tid] = (uint16_t)le;
+    if (tid < HALO / 16) {
+        uint32_t hnl, hle, hcode;
+        classify16(t.hv, false, hnl, hle, hcode);
+        if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, t.hv, base + TILE + (uint64_t)tid * 16, n);
+        reinterpret_cast<uint32_t *>(s.codes)[TILE / 16 + tid] = hcode;
+        reinterpret_cast<uint16_t *>(s.nl)[TILE / 16 + tid] = (uint16_t)hnl;
+    }
+    const uint32_t c = __popc(le);
+    const uint32_t inc = wave_incl_scan(c);
+    if ((tid & 63) == 63) s.wsum[tid >> 6] = inc;
+    lds_barrier();
+    uint32_t woff = t.line;
+    for (int w = 0; w < (tid >> 6); ++w) woff += s.wsum[w];
+    constexpr uint32_t keep = sizeof(LB) == 1 ? 3u : ~0u;
+    s.lb[tid] = (LB)((woff + inc - c) & keep);
+}
+
+// Line index (as lb counts it) of byte pp of the tile: that of its 16-byte group + the line ends before it in the group.
+template <typename LB>
+__device__ __forceinline__ uint32_t tile_line_of(const TileLds<LB> &s, uint32_t pp) {
+    const uint32_t grp = pp >> 4;
+    const uint32_t le_before = reinterpret_cast<const uint16_t *>(s.le)[grp] & ((1u << (pp & 15)) - 1u);
+    return (uint32_t)s.lb[grp] + __popc(le_before);
+}
+
+// Which bytes start a k-mer (createKMers, testExecution.h:15-36; FastXReader.h:71-77): the byte lies in the sequence line
+// of a record ((lbase + line) & line_mask == 1), no newline or break bit in [pp, pp + k), the window ends inside the text
+// and starts in the part of it this call owns.  The kernel-invariant part is set up once per kernel.
+struct WindowRule {
+    uint64_t need0, need1, n, own_end, lbase;
+    uint32_t k, line_mask;
+    __device__ __forceinline__ WindowRule(const TableParams &p, uint64_t n_, uint64_t own_end_, uint64_t lbase_)
+        : n(n_), own_end(own_end_), lbase(lbase_), k((uint32_t)p.k), line_mask(p.line_mask) {
+        need0 = (k >= 64) ? ~0ULL : ((1ULL << k) - 1ULL);
+        need1 = (k > 64) ? ((k >= 128) ? ~0ULL : ((1ULL << (k - 64)) - 1ULL)) : 0ULL;
+    }
+};
+template <typename LB>
+__device__ __forceinline__ bool window_valid(const TileLds<LB> &s, const WindowRule &r, uint64_t base, uint32_t pp,
+                                             uint32_t &line) {
+    const uint64_t gpos = base + pp;
+    line = tile_line_of(s, pp);
+    const uint32_t w = pp >> 6, o = pp & 63;
+    uint64_t m0 = s.nl[w] >> o, m1 = s.nl[w + 1] >> o;
+    if (o) { m0 |= s.nl[w + 1] << (64 - o); m1 |= s.nl[w + 2] << (64 - o); }
+    return (((r.lbase + line) & r.line_mask) == 1u) && ((m0 & r.need0) == 0) && ((m1 & r.need1) == 0) &&
+           (gpos + r.k <= r.n) && (gpos < r.own_end);
+}
+
+// Run-length merge across the wave (lanes hold consecutive positions): a leader is a valid window that differs from the
+// one in the lane below.  Called by whole waves.
+template <int WK>
+__device__ __forceinline__ bool run_leader(const uint64_t (&x)[WK], bool valid, int lane) {
+    uint64_t xp[WK];
+#pragma unroll
+    for (int t = 0; t < WK; ++t) xp[t] = __shfl_up((unsigned long long)x[t], 1, 64);
+    const bool prev_valid = __shfl_up((int)valid, 1, 64) != 0;
+    return valid && (lane == 0 || !prev_valid || !kmer_eq<WK>(x, xp));
+}
+// Lanes from this one to the end of its run, itself included: runs start at `start` lanes and end before invalid ones.
+__device__ __forceinline__ uint32_t run_length(bool start, bool valid, int lane) {
+    const unsigned long long bnd = __ballot(start || !valid);
+    const unsigned long long above = (lane == 63) ? 0ULL : (bnd >> (lane + 1));
+    return (above ? (uint32_t)__builtin_ctzll(above) : (uint32_t)(63 - lane)) + 1u;
+}
+
 // Pass 3: the hot path.  Per tile of TILE bytes:
 //   1. 16 B/lane coalesced loads; classify into newline / line-end bit masks
 //      and a packed 2-bit code array in LDS (no byte ever re-read from HBM
@@ -241,11 +356,7 @@ __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableP
                                                          uint64_t own_end, int head_open,
                                                          const uint32_t *tile_line, uint64_t ntiles,
                                                          const uint16_t *qmap = nullptr, PfView pf = PfView()) {
-    __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
-    __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
-    __shared__ uint64_t s_le[TILE / 64];
-    __shared__ uint8_t s_lb[TILE / 16];
-    __shared__ uint32_t s_wsum[NT / 64];
+    __shared__ TileLds<uint8_t> s;
     __shared__ uint32_t s_dpos[DSLOTS];
     __shared__ uint32_t s_dcnt[DSLOTS];
     extern __shared__ uint64_t s_lut[];
@@ -254,40 +365,14 @@ __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableP
     const int lut_words = p.groups * (1 << p.g) * WK;
     for (int i = tid; i < lut_words; i += NT) s_lut[i] = p.lut[i];
     for (int i = tid; i < DSLOTS; i += NT) { s_dpos[i] = 0; s_dcnt[i] = 0; }
-    if (tid < 3) s_nl[(TILE + HALO) / 64 + tid] = ~0ULL;
-    if (tid < 2) s_codes[(TILE + HALO) / 32 + tid] = 0;
+    s.set_sentinels(tid);
     unsigned long long added = 0;
     [[maybe_unused]] unsigned long long skipped = 0;   // PF: windows of the runs the filter kept out
-    const uint32_t k = (uint32_t)p.k;
+    const WindowRule rule(p, n, own_end, 0);
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t base = tile * TILE;
         lds_barrier();  // previous tile's LDS fully consumed
-        {
-            const uint64_t off = base + (uint64_t)tid * 16;
-            uint32_t nl, le, code;
-            const uint4 v = load16(buf, off, n);
-            classify16(v, prev_is_nl(buf, off, n, head_open), nl, le, code);
-            if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, v, off, n);
-            reinterpret_cast<uint32_t *>(s_codes)[tid] = code;
-            reinterpret_cast<uint16_t *>(s_nl)[tid] = (uint16_t)nl;
-            reinterpret_cast<uint16_t *>(s_le)[tid] = (uint16_t)le;
-            if (tid < HALO / 16) {
-                const uint64_t hoff = base + TILE + (uint64_t)tid * 16;
-                uint32_t hnl, hle, hcode;
-                const uint4 hv = load16(buf, hoff, n);
-                classify16(hv, false, hnl, hle, hcode);
-                if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, hv, hoff, n);
-                reinterpret_cast<uint32_t *>(s_codes)[TILE / 16 + tid] = hcode;
-                reinterpret_cast<uint16_t *>(s_nl)[TILE / 16 + tid] = (uint16_t)hnl;
-            }
-            const uint32_t c = __popc(le);
-            const uint32_t inc = wave_incl_scan(c);
-            if (lane == 63) s_wsum[tid >> 6] = inc;
-            lds_barrier();
-            uint32_t woff = tile_line[tile];
-            for (int w = 0; w < (tid >> 6); ++w) woff += s_wsum[w];
-            s_lb[tid] = (uint8_t)((woff + inc - c) & 3u);
-        }
+        tile_stage<BR>(s, tile_load(buf, n, head_open, tile_line, tile, tid), p, qmap, base, n, tid);
         lds_barrier();
 
         for (int round = 0; round < TILE / BATCH; ++round) {
@@ -297,34 +382,16 @@ __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableP
 #pragma unroll
             for (int j = 0; j < PER_THREAD; ++j) {
                 const uint32_t pp = (uint32_t)(round * BATCH + j * NT + tid);
-                const uint64_t gpos = base + pp;
-                // line index of this byte: group base + line ends before it in the group
-                const uint32_t grp = pp >> 4;
-                const uint32_t le_before = reinterpret_cast<const uint16_t *>(s_le)[grp] & ((1u << (pp & 15)) - 1u);
-                const uint32_t line = (uint32_t)s_lb[grp] + __popc(le_before);
-                // no newline inside [pp, pp+k)
-                const uint32_t w = pp >> 6, o = pp & 63;
-                uint64_t m0 = s_nl[w] >> o, m1 = s_nl[w + 1] >> o;
-                if (o) { m0 |= s_nl[w + 1] << (64 - o); m1 |= s_nl[w + 2] << (64 - o); }
-                const uint64_t need0 = (k >= 64) ? ~0ULL : ((1ULL << k) - 1ULL);
-                const uint64_t need1 = (k > 64) ? ((k >= 128) ? ~0ULL : ((1ULL << (k - 64)) - 1ULL)) : 0ULL;
-                const bool valid = ((line & p.line_mask) == 1u) && ((m0 & need0) == 0) && ((m1 & need1) == 0) &&
-                                   (gpos + k <= n) && (gpos < own_end);
+                uint32_t line;
+                const bool valid = window_valid(s, rule, base, pp, line);
                 slot_of[j] = -1; direct_cnt[j] = 0;
                 // header, '+' and quality lines make up half of a FASTQ text: a wave whose 64
                 // consecutive positions hold no k-mer start skips extraction, hashing and dedup
                 if (__ballot(valid) == 0ULL) continue;
                 uint64_t x[WK];
-                extract_kmer<WK>(s_codes, pp, p.top_mask, x);
-                // run-length merge across the wave: lanes hold consecutive positions
-                uint64_t xp[WK];
-#pragma unroll
-                for (int t = 0; t < WK; ++t) xp[t] = __shfl_up((unsigned long long)x[t], 1, 64);
-                const bool prev_valid = __shfl_up((int)valid, 1, 64) != 0;
-                const bool leader = valid && (lane == 0 || !prev_valid || !kmer_eq<WK>(x, xp));
-                const unsigned long long bnd = __ballot(leader || !valid);
-                const unsigned long long above = (lane == 63) ? 0ULL : (bnd >> (lane + 1));
-                const uint32_t runlen = (above ? (uint32_t)__builtin_ctzll(above) : (uint32_t)(63 - lane)) + 1u;
+                extract_kmer<WK>(s.codes, pp, p.top_mask, x);
+                const bool leader = run_leader<WK>(x, valid, lane);
+                const uint32_t runlen = run_length(leader, valid, lane);
                 bool admit = leader;
                 if constexpr (PF) {
                     if (leader) {
@@ -351,7 +418,7 @@ __global__ __launch_bounds__(NT, WK == 1 ? 3 : 2) void count_fastq_kernel(TableP
                             break;
                         }
                         uint64_t y[WK];
-                        extract_kmer<WK>(s_codes, old - 1u, p.top_mask, y);
+                        extract_kmer<WK>(s.codes, old - 1u, p.top_mask, y);
                         if (kmer_eq<WK>(x, y)) {
                             atomicAdd(&s_dcnt[slot], runlen);
                             slot_of[j] = -1;
@@ -407,14 +474,9 @@ __global__ __launch_bounds__(NT, 5) void strip_desc_kernel(TableParams p, const 
                                                            const uint16_t *qmap = nullptr) {
     // long_desc (the exchange of a sharded run): FOUR neighbouring strips in one description of 32 bytes -- 96 bases
     // + 64 validity bits, half the bytes per start position (the 32 bases behind a strip's own 16 are shared).
-    __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
-    __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
-    __shared__ uint64_t s_le[TILE / 64];
-    __shared__ uint8_t s_lb[TILE / 16];
-    __shared__ uint32_t s_wsum[NT / 64];
+    __shared__ TileLds<uint8_t> s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < 3) s_nl[(TILE + HALO) / 64 + tid] = ~0ULL;
-    if (tid < 2) s_codes[(TILE + HALO) / 32 + tid] = 0;
+    s.set_sentinels(tid);
     unsigned long long added = 0;
     unsigned long long hacc = 0;   // HOMOUT: homopolymer occurrences, 16 bits per base (flushed before a field can fill up)
     const uint32_t k = (uint32_t)p.k;
@@ -424,56 +486,18 @@ __global__ __launch_bounds__(NT, 5) void strip_desc_kernel(TableParams p, const 
     const uint64_t start_lim = min(own_end, (n >= k) ? n - k + 1 : 0ULL);
     const uint64_t lt = (1ULL << lane) - 1ULL;
 
-    uint4 cur = make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au), hcur = cur;
-    bool cur_pnl = true;
-    uint32_t cur_line = 0;
-    if ((uint64_t)blockIdx.x < ntiles) {
-        const uint64_t off = (uint64_t)blockIdx.x * TILE + (uint64_t)tid * 16;
-        cur_line = tile_line[blockIdx.x];
-        cur = load16(buf, off, n);
-        cur_pnl = prev_is_nl(buf, off, n, head_open);
-        if (tid < HALO / 16) hcur = load16(buf, (uint64_t)blockIdx.x * TILE + TILE + (uint64_t)tid * 16, n);
-    }
+    TileText cur = {};
+    if ((uint64_t)blockIdx.x < ntiles) cur = tile_load(buf, n, head_open, tile_line, blockIdx.x, tid);
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t base = tile * TILE;
         lds_barrier();  // previous tile's LDS fully consumed
-        {
-            uint32_t nl, le, code;
-            classify16(cur, cur_pnl, nl, le, code);
-            if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, cur, base + (uint64_t)tid * 16, n);
-            reinterpret_cast<uint32_t *>(s_codes)[tid] = code;
-            reinterpret_cast<uint16_t *>(s_nl)[tid] = (uint16_t)nl;
-            reinterpret_cast<uint16_t *>(s_le)[tid] = (uint16_t)le;
-            if (tid < HALO / 16) {
-                uint32_t hnl, hle, hcode;
-                classify16(hcur, false, hnl, hle, hcode);
-                if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, hcur, base + TILE + (uint64_t)tid * 16, n);
-                reinterpret_cast<uint32_t *>(s_codes)[TILE / 16 + tid] = hcode;
-                reinterpret_cast<uint16_t *>(s_nl)[TILE / 16 + tid] = (uint16_t)hnl;
-            }
-            const uint32_t c = __popc(le);
-            const uint32_t inc = wave_incl_scan(c);
-            if (lane == 63) s_wsum[wave] = inc;
-            lds_barrier();
-            uint32_t woff = cur_line;
-            for (int w = 0; w < wave; ++w) woff += s_wsum[w];
-            s_lb[tid] = (uint8_t)((woff + inc - c) & 3u);
-        }
-        {
-            const uint64_t nt = tile + gridDim.x;
-            if (nt < ntiles) {
-                const uint64_t off = nt * TILE + (uint64_t)tid * 16;
-                cur_line = tile_line[nt];
-                cur = load16(buf, off, n);
-                cur_pnl = prev_is_nl(buf, off, n, head_open);
-                if (tid < HALO / 16) hcur = load16(buf, nt * TILE + TILE + (uint64_t)tid * 16, n);
-            }
-        }
+        tile_stage<BR>(s, cur, p, qmap, base, n, tid);
+        if (tile + gridDim.x < ntiles) cur = tile_load(buf, n, head_open, tile_line, tile + gridDim.x, tid);   // a tile ahead
         lds_barrier();
         // ---- this lane's strip: start positions s .. s+15 of the tile -----------
         const uint32_t s0 = (uint32_t)tid * 16;
-        const uint32_t *codes32 = reinterpret_cast<const uint32_t *>(s_codes);
-        const uint32_t *nl32 = reinterpret_cast<const uint32_t *>(s_nl);
+        const uint32_t *codes32 = reinterpret_cast<const uint32_t *>(s.codes);
+        const uint32_t *nl32 = reinterpret_cast<const uint32_t *>(s.nl);
         uint64_t m;
         {
             const uint32_t w = (uint32_t)tid >> 1, sh = ((uint32_t)tid & 1u) * 16u;
@@ -484,8 +508,8 @@ __global__ __launch_bounds__(NT, 5) void strip_desc_kernel(TableParams p, const 
         uint32_t span = 1;
         while (span * 2 <= k) { r |= r >> span; span *= 2; }
         if (span < k) r |= r >> (k - span);
-        const uint32_t e16 = reinterpret_cast<const uint16_t *>(s_le)[tid];
-        const uint32_t lb = s_lb[tid];
+        const uint32_t e16 = reinterpret_cast<const uint16_t *>(s.le)[tid];
+        const uint32_t lb = s.lb[tid];
         uint32_t c0 = e16 << 1; c0 ^= c0 << 1; c0 ^= c0 << 2; c0 ^= c0 << 4; c0 ^= c0 << 8;
         uint32_t c1 = (e16 & c0) << 1; c1 ^= c1 << 1; c1 ^= c1 << 2; c1 ^= c1 << 4; c1 ^= c1 << 8;
         const uint32_t l0 = (lb & 1u) ? 0xFFFFu : 0u, l1 = (lb & 2u) ? 0xFFFFu : 0u;
@@ -813,14 +837,9 @@ __global__ __launch_bounds__(NT, 4) void strip_desc_wide_kernel(TableParams p, c
                                                                 uint4 *desc, uint64_t desc_cap, unsigned long long *desc_cnt,
                                                                 const uint16_t *qmap = nullptr) {
     constexpr int DU = WideDescU4<WK>::value;
-    __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
-    __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
-    __shared__ uint64_t s_le[TILE / 64];
-    __shared__ uint8_t s_lb[TILE / 16];
-    __shared__ uint32_t s_wsum[NT / 64];
+    __shared__ TileLds<uint8_t> s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < 3) s_nl[(TILE + HALO) / 64 + tid] = ~0ULL;
-    if (tid < 2) s_codes[(TILE + HALO) / 32 + tid] = 0;
+    s.set_sentinels(tid);
     unsigned long long added = 0;
     const uint32_t k = (uint32_t)p.k;
     const uint32_t region = blockIdx.x * (NT / 64) + wave;
@@ -830,56 +849,18 @@ __global__ __launch_bounds__(NT, 4) void strip_desc_wide_kernel(TableParams p, c
     const uint64_t lt = (1ULL << lane) - 1ULL;
 
     // text loaded one tile ahead, as in strip_desc_kernel
-    uint4 cur = make_uint4(0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au, 0x0A0A0A0Au), hcur = cur;
-    bool cur_pnl = true;
-    uint32_t cur_line = 0;
-    if ((uint64_t)blockIdx.x < ntiles) {
-        const uint64_t off = (uint64_t)blockIdx.x * TILE + (uint64_t)tid * 16;
-        cur_line = tile_line[blockIdx.x];
-        cur = load16(buf, off, n);
-        cur_pnl = prev_is_nl(buf, off, n, head_open);
-        if (tid < HALO / 16) hcur = load16(buf, (uint64_t)blockIdx.x * TILE + TILE + (uint64_t)tid * 16, n);
-    }
+    TileText cur = {};
+    if ((uint64_t)blockIdx.x < ntiles) cur = tile_load(buf, n, head_open, tile_line, blockIdx.x, tid);
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t base = tile * TILE;
         lds_barrier();  // previous tile's LDS fully consumed
-        {
-            uint32_t nl, le, code;
-            classify16(cur, cur_pnl, nl, le, code);
-            if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, cur, base + (uint64_t)tid * 16, n);
-            reinterpret_cast<uint32_t *>(s_codes)[tid] = code;
-            reinterpret_cast<uint16_t *>(s_nl)[tid] = (uint16_t)nl;
-            reinterpret_cast<uint16_t *>(s_le)[tid] = (uint16_t)le;
-            if (tid < HALO / 16) {
-                uint32_t hnl, hle, hcode;
-                classify16(hcur, false, hnl, hle, hcode);
-                if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, hcur, base + TILE + (uint64_t)tid * 16, n);
-                reinterpret_cast<uint32_t *>(s_codes)[TILE / 16 + tid] = hcode;
-                reinterpret_cast<uint16_t *>(s_nl)[TILE / 16 + tid] = (uint16_t)hnl;
-            }
-            const uint32_t c = __popc(le);
-            const uint32_t inc = wave_incl_scan(c);
-            if (lane == 63) s_wsum[wave] = inc;
-            lds_barrier();
-            uint32_t woff = cur_line;   // lines before the tile, loaded a tile ahead like its text
-            for (int w = 0; w < wave; ++w) woff += s_wsum[w];
-            s_lb[tid] = (uint8_t)((woff + inc - c) & 3u);
-        }
-        {
-            const uint64_t nt = tile + gridDim.x;
-            if (nt < ntiles) {
-                const uint64_t off = nt * TILE + (uint64_t)tid * 16;
-                cur_line = tile_line[nt];
-                cur = load16(buf, off, n);
-                cur_pnl = prev_is_nl(buf, off, n, head_open);
-                if (tid < HALO / 16) hcur = load16(buf, nt * TILE + TILE + (uint64_t)tid * 16, n);
-            }
-        }
+        tile_stage<BR>(s, cur, p, qmap, base, n, tid);
+        if (tile + gridDim.x < ntiles) cur = tile_load(buf, n, head_open, tile_line, tile + gridDim.x, tid);   // a tile ahead
         lds_barrier();
 
         const uint32_t s0 = (uint32_t)tid * 16;
-        const uint32_t *codes32 = reinterpret_cast<const uint32_t *>(s_codes);
-        const uint32_t *nl32 = reinterpret_cast<const uint32_t *>(s_nl);
+        const uint32_t *codes32 = reinterpret_cast<const uint32_t *>(s.codes);
+        const uint32_t *nl32 = reinterpret_cast<const uint32_t *>(s.nl);
         // newline flags of bytes [s0, s0 + 160): a window of position j <= 15 reaches byte s0 + 15 + k - 1 <= s0 + 141
         uint64_t r[3];
         {
@@ -895,8 +876,8 @@ __global__ __launch_bounds__(NT, 4) void strip_desc_wide_kernel(TableParams p, c
             while (span * 2 <= k) { shr_or3(r, span); span *= 2; }
             if (span < k) shr_or3(r, k - span);
         }
-        const uint32_t e16 = reinterpret_cast<const uint16_t *>(s_le)[tid];
-        const uint32_t lb = s_lb[tid];
+        const uint32_t e16 = reinterpret_cast<const uint16_t *>(s.le)[tid];
+        const uint32_t lb = s.lb[tid];
         uint32_t c0 = e16 << 1; c0 ^= c0 << 1; c0 ^= c0 << 2; c0 ^= c0 << 4; c0 ^= c0 << 8;
         uint32_t c1 = (e16 & c0) << 1; c1 ^= c1 << 1; c1 ^= c1 << 2; c1 ^= c1 << 4; c1 ^= c1 << 8;
         const uint32_t l0 = (lb & 1u) ? 0xFFFFu : 0u, l1 = (lb & 2u) ? 0xFFFFu : 0u;
@@ -910,7 +891,7 @@ __global__ __launch_bounds__(NT, 4) void strip_desc_wide_kernel(TableParams p, c
         if (hb) {
             if (vm) {
                 uint64_t x[WK];
-                extract_kmer<WK>(s_codes, s0, p.top_mask, x);
+                extract_kmer<WK>(s.codes, s0, p.top_mask, x);
                 uint32_t inc;
                 {
                     const uint32_t o = 2u * k, ws = o >> 5, sh = o & 31u;

@@ -1,7 +1,7 @@
 // tsx_median.h -- the median k-mer abundance of reads (gfx950, wave64): the count of every window of a text, the
 // median of every record's counts, and the filter on it.
 //
-//   window_counts_kernel       solid_bits_kernel up to the shuffle that hands followers their leader's count; then one
+//   window_counts_kernel       the tile front end (tsx_kernels.h) and the lookup schedule (tsx_query.h); then one
 //                              uint32 per start position: min(c, 0xFFFFFFFE) for a k-mer under the base rule, else
 //                              TSX_HIP_NO_KMER (a coalesced 256-byte store per wave and position group)
 //   median_select_kernel       one wave per record: radix select of rank m / 2 among the record's profile entries, most
@@ -27,99 +27,30 @@ __global__ __launch_bounds__(NT, 2) void window_counts_kernel(TableParams p, con
                                                               int head_open, const uint32_t *tile_line, uint64_t ntiles,
                                                               const unsigned long long *line_base, uint32_t *profile,
                                                               const uint16_t *qmap = nullptr) {
-    __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
-    __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
-    __shared__ uint64_t s_le[TILE / 64];
-    __shared__ uint32_t s_lb[TILE / 16];
-    __shared__ uint32_t s_wsum[NT / 64];
+    __shared__ TileLds<uint32_t> s;
     extern __shared__ uint64_t s_lut[];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int lut_words = p.groups * (1 << p.g) * WK;
     for (int i = tid; i < lut_words; i += NT) s_lut[i] = p.lut[i];
-    if (tid < 3) s_nl[(TILE + HALO) / 64 + tid] = ~0ULL;
-    if (tid < 2) s_codes[(TILE + HALO) / 32 + tid] = 0;
-    const uint32_t k = (uint32_t)p.k;
-    const uint64_t lbase = *line_base;
-    const uint64_t need0 = (k >= 64) ? ~0ULL : ((1ULL << k) - 1ULL);
-    const uint64_t need1 = (k > 64) ? ((k >= 128) ? ~0ULL : ((1ULL << (k - 64)) - 1ULL)) : 0ULL;
-    const unsigned long long below = (lane == 0) ? 0ULL : (~0ULL >> (64 - lane));   // lanes < lane
+    s.set_sentinels(tid);
+    const WindowRule rule(p, n, own_end, *line_base);
     const uint64_t wr_end = min(own_end, n);
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t base = tile * TILE;
         lds_barrier();  // previous tile's LDS fully consumed
-        {
-            const uint64_t off = base + (uint64_t)tid * 16;
-            uint32_t nl, le, code;
-            const uint4 v = load16(buf, off, n);
-            classify16(v, prev_is_nl(buf, off, n, head_open), nl, le, code);
-            if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, v, off, n);
-            reinterpret_cast<uint32_t *>(s_codes)[tid] = code;
-            reinterpret_cast<uint16_t *>(s_nl)[tid] = (uint16_t)nl;
-            reinterpret_cast<uint16_t *>(s_le)[tid] = (uint16_t)le;
-            if (tid < HALO / 16) {
-                const uint64_t hoff = base + TILE + (uint64_t)tid * 16;
-                uint32_t hnl, hle, hcode;
-                const uint4 hv = load16(buf, hoff, n);
-                classify16(hv, false, hnl, hle, hcode);
-                if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, hv, hoff, n);
-                reinterpret_cast<uint32_t *>(s_codes)[TILE / 16 + tid] = hcode;
-                reinterpret_cast<uint16_t *>(s_nl)[TILE / 16 + tid] = (uint16_t)hnl;
-            }
-            const uint32_t c = __popc(le);
-            const uint32_t inc = wave_incl_scan(c);
-            if (lane == 63) s_wsum[tid >> 6] = inc;
-            lds_barrier();
-            uint32_t woff = tile_line[tile];
-            for (int w = 0; w < (tid >> 6); ++w) woff += s_wsum[w];
-            s_lb[tid] = woff + inc - c;
-        }
+        tile_stage<BR>(s, tile_load(buf, n, head_open, tile_line, tile, tid), p, qmap, base, n, tid);
         lds_barrier();
 
         for (int round = 0; round < TILE / BATCH; ++round) {
-            uint64_t hk[PER_THREAD][WK];
-            uint64_t v1[PER_THREAD];
-            uint32_t vbits = 0, lbits = 0;   // bit j: position j is valid / a run leader
+            ProbeRound<WK> pr;
+            probe_round_issue<CANON, WK>(p, (const uint64_t *)s_lut, s, rule, base, round, tid, pr);
 #pragma unroll
             for (int j = 0; j < PER_THREAD; ++j) {
-                const uint32_t pp = (uint32_t)(round * BATCH + j * NT + tid);
-                const uint64_t gpos = base + pp;
-                const uint32_t grp = pp >> 4;
-                const uint32_t le_before = reinterpret_cast<const uint16_t *>(s_le)[grp] & ((1u << (pp & 15)) - 1u);
-                const uint32_t line = s_lb[grp] + __popc(le_before);
-                const uint32_t w = pp >> 6, o = pp & 63;
-                uint64_t m0 = s_nl[w] >> o, m1 = s_nl[w + 1] >> o;
-                if (o) { m0 |= s_nl[w + 1] << (64 - o); m1 |= s_nl[w + 2] << (64 - o); }
-                const bool valid = (((lbase + line) & p.line_mask) == 1u) && ((m0 & need0) == 0) && ((m1 & need1) == 0) &&
-                                   (gpos + k <= n) && (gpos < own_end);
-                v1[j] = 0;
-                if (__ballot(valid) == 0ULL) continue;
-                uint64_t x[WK];
-                extract_kmer<WK>(s_codes, pp, p.top_mask, x);
-                uint64_t xp[WK];
-#pragma unroll
-                for (int t = 0; t < WK; ++t) xp[t] = __shfl_up((unsigned long long)x[t], 1, 64);
-                const bool prev_valid = __shfl_up((int)valid, 1, 64) != 0;
-                const bool leader = valid && (lane == 0 || !prev_valid || !kmer_eq<WK>(x, xp));
-                vbits |= valid ? (1u << j) : 0u;
-                lbits |= leader ? (1u << j) : 0u;
-                if (leader) {
-                    hash_key<CANON, WK>(p, (const uint64_t *)s_lut, x, hk[j]);
-                    v1[j] = first_probe<WK>(p, hk[j]);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < PER_THREAD; ++j) {
-                const bool valid = (vbits >> j) & 1u, leader = (lbits >> j) & 1u;
+                const bool valid = (pr.vbits >> j) & 1u;
+                uint64_t c;
                 uint32_t out = NO_KMER;
-                if (__ballot(valid) != 0ULL) {
-                    uint64_t c = leader ? lookup_rest<WK>(p, hk[j], v1[j]) : 0;
-                    // followers: the nearest leader at or below the lane holds the same k-mer
-                    const unsigned long long lmask = __ballot(leader) & (below | (1ULL << lane));
-                    const int src = lmask ? 63 - __builtin_clzll(lmask) : lane;
-                    c = __shfl((unsigned long long)c, src, 64);
-                    if (valid) out = (uint32_t)min(c, (uint64_t)(NO_KMER - 1u));
-                }
+                if (probe_round_count<WK>(p, pr, j, lane, c) != 0ULL && valid) out = (uint32_t)min(c, (uint64_t)(NO_KMER - 1u));
                 const uint64_t gpos = base + (uint64_t)(round * BATCH + j * NT + tid);
                 if (gpos < wr_end) profile[gpos] = out;
             }

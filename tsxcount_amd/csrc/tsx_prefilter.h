@@ -2,7 +2,7 @@
 // in a first pass over the input and consulted by the counting calls in a second one, so that a k-mer that occurs once --
 // on real reads most distinct k-mers: sequencing errors -- takes no slot of the table.
 //
-//   prefilter_windows_kernel   pass 1: the tile front end of sketch_windows_kernel up to the run leaders; a leader ORs the
+//   prefilter_windows_kernel   pass 1: the tile front end (tsx_kernels.h) up to the run lengths; a leader ORs the
 //                              mask of its k-mer into filter A ("seen") and, when A already held it or the run has
 //                              followers, into filter B ("seen again").  Adds its exact totals: windows seen, windows
 //                              that found their k-mer seen before.
@@ -36,80 +36,34 @@ __global__ __launch_bounds__(NT, 2) void prefilter_windows_kernel(TableParams p,
                                                                   unsigned long long *fa, unsigned long long *fb,
                                                                   unsigned long long *tot,
                                                                   const uint16_t *qmap = nullptr) {
-    __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
-    __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
-    __shared__ uint64_t s_le[TILE / 64];
-    __shared__ uint32_t s_lb[TILE / 16];
-    __shared__ uint32_t s_wsum[NT / 64];
+    __shared__ TileLds<uint32_t> s;
     __shared__ unsigned long long s_wtot[2][NT / 64];
 
     const int tid = threadIdx.x, lane = tid & 63;
-    if (tid < 3) s_nl[(TILE + HALO) / 64 + tid] = ~0ULL;
-    if (tid < 2) s_codes[(TILE + HALO) / 32 + tid] = 0;
-    const uint32_t k = (uint32_t)p.k;
-    const uint64_t lbase = *line_base;
-    const uint64_t need0 = (k >= 64) ? ~0ULL : ((1ULL << k) - 1ULL);
-    const uint64_t need1 = (k > 64) ? ((k >= 128) ? ~0ULL : ((1ULL << (k - 64)) - 1ULL)) : 0ULL;
+    s.set_sentinels(tid);
+    const WindowRule rule(p, n, own_end, *line_base);
     unsigned long long nvalid = 0;   // valid windows this wave has seen (the same in every lane)
     unsigned long long nagain = 0;   // windows that found their k-mer seen before (per lane: the leaders add their runs)
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t base = tile * TILE;
         lds_barrier();  // previous tile's LDS fully consumed
-        {
-            const uint64_t off = base + (uint64_t)tid * 16;
-            uint32_t nl, le, code;
-            const uint4 v = load16(buf, off, n);
-            classify16(v, prev_is_nl(buf, off, n, head_open), nl, le, code);
-            if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, v, off, n);
-            reinterpret_cast<uint32_t *>(s_codes)[tid] = code;
-            reinterpret_cast<uint16_t *>(s_nl)[tid] = (uint16_t)nl;
-            reinterpret_cast<uint16_t *>(s_le)[tid] = (uint16_t)le;
-            if (tid < HALO / 16) {
-                const uint64_t hoff = base + TILE + (uint64_t)tid * 16;
-                uint32_t hnl, hle, hcode;
-                const uint4 hv = load16(buf, hoff, n);
-                classify16(hv, false, hnl, hle, hcode);
-                if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, hv, hoff, n);
-                reinterpret_cast<uint32_t *>(s_codes)[TILE / 16 + tid] = hcode;
-                reinterpret_cast<uint16_t *>(s_nl)[TILE / 16 + tid] = (uint16_t)hnl;
-            }
-            const uint32_t c = __popc(le);
-            const uint32_t inc = wave_incl_scan(c);
-            if (lane == 63) s_wsum[tid >> 6] = inc;
-            lds_barrier();
-            uint32_t woff = tile_line[tile];
-            for (int w = 0; w < (tid >> 6); ++w) woff += s_wsum[w];
-            s_lb[tid] = woff + inc - c;
-        }
+        tile_stage<BR>(s, tile_load(buf, n, head_open, tile_line, tile, tid), p, qmap, base, n, tid);
         lds_barrier();
 
         for (int round = 0; round < TILE / BATCH; ++round) {
 #pragma unroll
             for (int j = 0; j < PER_THREAD; ++j) {
                 const uint32_t pp = (uint32_t)(round * BATCH + j * NT + tid);
-                const uint64_t gpos = base + pp;
-                const uint32_t grp = pp >> 4;
-                const uint32_t le_before = reinterpret_cast<const uint16_t *>(s_le)[grp] & ((1u << (pp & 15)) - 1u);
-                const uint32_t line = s_lb[grp] + __popc(le_before);
-                const uint32_t w = pp >> 6, o = pp & 63;
-                uint64_t m0 = s_nl[w] >> o, m1 = s_nl[w + 1] >> o;
-                if (o) { m0 |= s_nl[w + 1] << (64 - o); m1 |= s_nl[w + 2] << (64 - o); }
-                const bool valid = (((lbase + line) & p.line_mask) == 1u) && ((m0 & need0) == 0) && ((m1 & need1) == 0) &&
-                                   (gpos + k <= n) && (gpos < own_end);
+                uint32_t line;
+                const bool valid = window_valid(s, rule, base, pp, line);
                 const unsigned long long vm = __ballot(valid);
                 if (vm == 0ULL) continue;
                 nvalid += (unsigned long long)__popcll(vm);
                 uint64_t x[WK];
-                extract_kmer<WK>(s_codes, pp, p.top_mask, x);
-                uint64_t xp[WK];
-#pragma unroll
-                for (int t = 0; t < WK; ++t) xp[t] = __shfl_up((unsigned long long)x[t], 1, 64);
-                const bool prev_valid = __shfl_up((int)valid, 1, 64) != 0;
-                const bool leader = valid && (lane == 0 || !prev_valid || !kmer_eq<WK>(x, xp));
+                extract_kmer<WK>(s.codes, pp, p.top_mask, x);
+                const bool leader = run_leader<WK>(x, valid, lane);
                 // the run a leader stands for, as in count_fastq_kernel: itself and the equal windows in the lanes above
-                const unsigned long long bnd = __ballot(leader || !valid);
-                const unsigned long long above = (lane == 63) ? 0ULL : (bnd >> (lane + 1));
-                const uint32_t runlen = (above ? (uint32_t)__builtin_ctzll(above) : (uint32_t)(63 - lane)) + 1u;
+                const uint32_t runlen = run_length(leader, valid, lane);
                 if (leader) {
                     if constexpr (CANON) lex_canonical<WK>(x, p.n);
                     const uint64_t v = sketch_hash<WK>(x), mask = pf_mask(v);

@@ -1,7 +1,7 @@
 // tsx_query.h -- read queries against a filled table (gfx950, wave64): per-record k-mer statistics and the read filter.
 //
-//   query_reads_kernel     the tile front end of count_fastq_kernel with the FULL line index, then per start position:
-//                          run-length merge, hash_key, a lookup in place of the insert, and a segmented per-record
+//   query_reads_kernel     the tile front end (tsx_kernels.h) with the FULL line index and the lookup schedule below
+//                          (run-length merge, hash_key, a lookup in place of the insert), then a segmented per-record
 //                          reduction across the wave that ends in one set of global atomics per (wave, record) run
 //   query_finalize_kernel  min_count of every record: the kernel keeps ~min under atomicMax; 0 for records without k-mers
 //   query_window_kernel    device texts in windows: the line base of the next window, the record count after the last
@@ -46,12 +46,61 @@ __device__ inline uint64_t lookup_rest(const TableParams &p, const uint64_t (&h)
     return 0;
 }
 
-// Per tile, as count_fastq_kernel: classify into LDS, workgroup prefix sum of line ends.  The line index is kept whole
+// The lookup schedule of a round of BATCH start positions (query_reads_kernel, solid_bits_kernel, window_counts_kernel).
+// probe_round_issue: for every position of the lane the window test, extraction and the run-leader test; leaders hash
+// and issue their first probe load -- all PER_THREAD loads before any is waited for.  It leaves bit j of vbits / lbits
+// (position j is valid / a run leader) and, for leaders, hk[j] and v1[j].
+template <int WK>
+struct ProbeRound {
+    uint64_t hk[PER_THREAD][WK];
+    uint64_t v1[PER_THREAD];
+    uint32_t vbits, lbits;
+};
+template <bool CANON, int WK>
+__device__ __forceinline__ void probe_round_issue(const TableParams &p, const uint64_t *lut, const TileLds<uint32_t> &s,
+                                                  const WindowRule &rule, uint64_t base, int round, int tid,
+                                                  ProbeRound<WK> &pr) {
+    pr.vbits = 0; pr.lbits = 0;
+#pragma unroll
+    for (int j = 0; j < PER_THREAD; ++j) {
+        const uint32_t pp = (uint32_t)(round * BATCH + j * NT + tid);
+        uint32_t line;
+        const bool valid = window_valid(s, rule, base, pp, line);
+        pr.v1[j] = 0;
+        if (__ballot(valid) == 0ULL) continue;
+        uint64_t x[WK];
+        extract_kmer<WK>(s.codes, pp, p.top_mask, x);
+        const bool leader = run_leader<WK>(x, valid, tid & 63);
+        pr.vbits |= valid ? (1u << j) : 0u;
+        pr.lbits |= leader ? (1u << j) : 0u;
+        if (leader) {
+            hash_key<CANON, WK>(p, lut, x, pr.hk[j]);
+            pr.v1[j] = first_probe<WK>(p, pr.hk[j]);
+        }
+    }
+}
+// probe_round_count: position j of the round.  Returns the ballot of the valid lanes; when it is not empty, c is the
+// count of the lane's k-mer for every valid lane: leaders finish their probe, followers (equal k-mer in the lane below)
+// take the count of the nearest leader at or below them by shuffle.  Called by whole waves.
+template <int WK>
+__device__ __forceinline__ unsigned long long probe_round_count(const TableParams &p, const ProbeRound<WK> &pr, int j,
+                                                                int lane, uint64_t &c) {
+    const bool valid = (pr.vbits >> j) & 1u, leader = (pr.lbits >> j) & 1u;
+    const unsigned long long vmask = __ballot(valid);
+    c = 0;
+    if (vmask == 0ULL) return vmask;
+    if (leader) c = lookup_rest<WK>(p, pr.hk[j], pr.v1[j]);
+    const unsigned long long lmask = __ballot(leader) & (~0ULL >> (63 - lane));   // leaders at or below the lane
+    const int src = lmask ? 63 - __builtin_clzll(lmask) : lane;
+    c = __shfl((unsigned long long)c, src, 64);
+    return vmask;
+}
+
+// Per tile the front end (tile_load, tile_stage).  The line index is kept whole
 // (32 bits: one window holds fewer than 2^32 lines) and offset by *line_base (lines of the earlier windows), so that
 // the record of a window is (line_base + line) >> lshift.  Then per round of BATCH start positions:
-//   A. every lane: validity, extraction, the run-length leader test of the count kernel; leaders hash and issue their
-//      first probe load -- all PER_THREAD positions before any of them is used;
-//   B. leaders finish their probe; followers (equal k-mer in the lane below) take the leader's count by shuffle; the
+//   A. probe_round_issue;
+//   B. per position probe_round_count; the
 //      valid lanes of a wave form runs, one run per record (positions of one record are contiguous, those of two
 //      records are separated by invalid positions); a segmented suffix reduction leaves the run's kmers, in_range,
 //      sum and min at its first lane, which adds them to the record with four global atomics.
@@ -63,101 +112,32 @@ __global__ __launch_bounds__(NT, 2) void query_reads_kernel(TableParams p, const
                                                             const unsigned long long *line_base, uint32_t lshift,
                                                             uint64_t lower, uint64_t upper, unsigned long long *stats,
                                                             uint64_t cap, const uint16_t *qmap = nullptr) {
-    __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
-    __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
-    __shared__ uint64_t s_le[TILE / 64];
-    __shared__ uint32_t s_lb[TILE / 16];
-    __shared__ uint32_t s_wsum[NT / 64];
+    __shared__ TileLds<uint32_t> s;
     extern __shared__ uint64_t s_lut[];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int lut_words = p.groups * (1 << p.g) * WK;
     for (int i = tid; i < lut_words; i += NT) s_lut[i] = p.lut[i];
-    if (tid < 3) s_nl[(TILE + HALO) / 64 + tid] = ~0ULL;
-    if (tid < 2) s_codes[(TILE + HALO) / 32 + tid] = 0;
-    const uint32_t k = (uint32_t)p.k;
-    const uint64_t lbase = *line_base;
-    const uint64_t need0 = (k >= 64) ? ~0ULL : ((1ULL << k) - 1ULL);
-    const uint64_t need1 = (k > 64) ? ((k >= 128) ? ~0ULL : ((1ULL << (k - 64)) - 1ULL)) : 0ULL;
-    const unsigned long long below = (lane == 0) ? 0ULL : (~0ULL >> (64 - lane));   // lanes < lane
+    s.set_sentinels(tid);
+    const WindowRule rule(p, n, own_end, *line_base);
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t base = tile * TILE;
         lds_barrier();  // previous tile's LDS fully consumed
-        {
-            const uint64_t off = base + (uint64_t)tid * 16;
-            uint32_t nl, le, code;
-            const uint4 v = load16(buf, off, n);
-            classify16(v, prev_is_nl(buf, off, n, head_open), nl, le, code);
-            if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, v, off, n);
-            reinterpret_cast<uint32_t *>(s_codes)[tid] = code;
-            reinterpret_cast<uint16_t *>(s_nl)[tid] = (uint16_t)nl;
-            reinterpret_cast<uint16_t *>(s_le)[tid] = (uint16_t)le;
-            if (tid < HALO / 16) {
-                const uint64_t hoff = base + TILE + (uint64_t)tid * 16;
-                uint32_t hnl, hle, hcode;
-                const uint4 hv = load16(buf, hoff, n);
-                classify16(hv, false, hnl, hle, hcode);
-                if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, hv, hoff, n);
-                reinterpret_cast<uint32_t *>(s_codes)[TILE / 16 + tid] = hcode;
-                reinterpret_cast<uint16_t *>(s_nl)[TILE / 16 + tid] = (uint16_t)hnl;
-            }
-            const uint32_t c = __popc(le);
-            const uint32_t inc = wave_incl_scan(c);
-            if (lane == 63) s_wsum[tid >> 6] = inc;
-            lds_barrier();
-            uint32_t woff = tile_line[tile];
-            for (int w = 0; w < (tid >> 6); ++w) woff += s_wsum[w];
-            s_lb[tid] = woff + inc - c;
-        }
+        tile_stage<BR>(s, tile_load(buf, n, head_open, tile_line, tile, tid), p, qmap, base, n, tid);
         lds_barrier();
 
         for (int round = 0; round < TILE / BATCH; ++round) {
-            uint64_t hk[PER_THREAD][WK];
-            uint64_t v1[PER_THREAD];
-            uint32_t vbits = 0, lbits = 0;   // bit j: position j is valid / a run leader
+            ProbeRound<WK> pr;
+            probe_round_issue<CANON, WK>(p, (const uint64_t *)s_lut, s, rule, base, round, tid, pr);
 #pragma unroll
             for (int j = 0; j < PER_THREAD; ++j) {
-                const uint32_t pp = (uint32_t)(round * BATCH + j * NT + tid);
-                const uint64_t gpos = base + pp;
-                const uint32_t grp = pp >> 4;
-                const uint32_t le_before = reinterpret_cast<const uint16_t *>(s_le)[grp] & ((1u << (pp & 15)) - 1u);
-                const uint32_t line = s_lb[grp] + __popc(le_before);
-                const uint32_t w = pp >> 6, o = pp & 63;
-                uint64_t m0 = s_nl[w] >> o, m1 = s_nl[w + 1] >> o;
-                if (o) { m0 |= s_nl[w + 1] << (64 - o); m1 |= s_nl[w + 2] << (64 - o); }
-                const bool valid = (((lbase + line) & p.line_mask) == 1u) && ((m0 & need0) == 0) && ((m1 & need1) == 0) &&
-                                   (gpos + k <= n) && (gpos < own_end);
-                v1[j] = 0;
-                if (__ballot(valid) == 0ULL) continue;
-                uint64_t x[WK];
-                extract_kmer<WK>(s_codes, pp, p.top_mask, x);
-                uint64_t xp[WK];
-#pragma unroll
-                for (int t = 0; t < WK; ++t) xp[t] = __shfl_up((unsigned long long)x[t], 1, 64);
-                const bool prev_valid = __shfl_up((int)valid, 1, 64) != 0;
-                const bool leader = valid && (lane == 0 || !prev_valid || !kmer_eq<WK>(x, xp));
-                vbits |= valid ? (1u << j) : 0u;
-                lbits |= leader ? (1u << j) : 0u;
-                if (leader) {
-                    hash_key<CANON, WK>(p, (const uint64_t *)s_lut, x, hk[j]);
-                    v1[j] = first_probe<WK>(p, hk[j]);
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < PER_THREAD; ++j) {
-                const bool valid = (vbits >> j) & 1u, leader = (lbits >> j) & 1u;
-                const unsigned long long vmask = __ballot(valid);
+                const bool valid = (pr.vbits >> j) & 1u;
+                uint64_t c;
+                const unsigned long long vmask = probe_round_count<WK>(p, pr, j, lane, c);
                 if (vmask == 0ULL) continue;
-                uint64_t c = leader ? lookup_rest<WK>(p, hk[j], v1[j]) : 0;
-                // followers: the nearest leader at or below the lane holds the same k-mer
-                const unsigned long long lmask = __ballot(leader) & (below | (1ULL << lane));
-                const int src = lmask ? 63 - __builtin_clzll(lmask) : lane;
-                c = __shfl((unsigned long long)c, src, 64);
                 // runs of valid lanes: head = first lane of a run; seg = lanes from this one to the end of its run
                 const bool head = valid && (lane == 0 || !((vmask >> (lane - 1)) & 1ULL));
-                const unsigned long long bnd = __ballot(head || !valid);
-                const unsigned long long above = (lane == 63) ? 0ULL : (bnd >> (lane + 1));
-                const uint32_t seg = above ? (uint32_t)__builtin_ctzll(above) + 1u : (uint32_t)(64 - lane);
+                const uint32_t seg = run_length(head, valid, lane);
                 unsigned long long sum = valid ? c : 0ULL, mn = valid ? c : ~0ULL;
                 uint32_t inr = (valid && c >= lower && c <= upper) ? 1u : 0u;
 #pragma unroll
@@ -167,16 +147,14 @@ __global__ __launch_bounds__(NT, 2) void query_reads_kernel(TableParams p, const
                     if ((uint32_t)d < seg) { sum += os; mn = om < mn ? om : mn; inr += oi; }
                 }
                 if (head) {
-                    const uint32_t pp = (uint32_t)(round * BATCH + j * NT + tid), grp = pp >> 4;
-                    const uint32_t line = s_lb[grp] +
-                                          __popc(reinterpret_cast<const uint16_t *>(s_le)[grp] & ((1u << (pp & 15)) - 1u));
-                    const uint64_t rec = (lbase + line) >> lshift;
+                    const uint32_t line = tile_line_of(s, (uint32_t)(round * BATCH + j * NT + tid));
+                    const uint64_t rec = (rule.lbase + line) >> lshift;
                     if (rec < cap) {
-                        unsigned long long *s = stats + rec * QS_N;
-                        atomicAdd(s + QS_KMERS, (unsigned long long)seg);
-                        if (inr) atomicAdd(s + QS_INRANGE, (unsigned long long)inr);
-                        atomicAdd(s + QS_SUM, sum);
-                        atomicMax(s + QS_MIN, ~mn);
+                        unsigned long long *st = stats + rec * QS_N;
+                        atomicAdd(st + QS_KMERS, (unsigned long long)seg);
+                        if (inr) atomicAdd(st + QS_INRANGE, (unsigned long long)inr);
+                        atomicAdd(st + QS_SUM, sum);
+                        atomicMax(st + QS_MIN, ~mn);
                     }
                 }
             }

@@ -1,7 +1,7 @@
 // tsx_sketch.h -- table sizing (gfx950, wave64): a HyperLogLog sketch of the k-mers a text would put into a table, so
 // that the slot count can be chosen before anything is counted.
 //
-//   sketch_windows_kernel      the tile front end of window_counts_kernel up to extract_kmer; then, instead of a table
+//   sketch_windows_kernel      the tile front end (tsx_kernels.h) up to the run leaders; then, instead of a table
 //                              lookup, the k-mer (its lexicographically smaller strand on a canonical map) is hashed and
 //                              raises one of 2^p registers kept in LDS.  Every workgroup folds its registers into the
 //                              global ones when it ends, and adds its exact number of valid windows.
@@ -33,11 +33,7 @@ __global__ __launch_bounds__(NT, 2) void sketch_windows_kernel(TableParams p, co
                                                                int head_open, const uint32_t *tile_line, uint64_t ntiles,
                                                                const unsigned long long *line_base, int prec, uint32_t *regs,
                                                                unsigned long long *kmers, const uint16_t *qmap = nullptr) {
-    __shared__ uint64_t s_codes[(TILE + HALO) / 32 + 2];
-    __shared__ uint64_t s_nl[(TILE + HALO) / 64 + 3];
-    __shared__ uint64_t s_le[TILE / 64];
-    __shared__ uint32_t s_lb[TILE / 16];
-    __shared__ uint32_t s_wsum[NT / 64];
+    __shared__ TileLds<uint32_t> s;
     __shared__ unsigned long long s_wvalid[NT / 64];
     extern __shared__ uint64_t s_dyn[];
     uint32_t *const s_reg = reinterpret_cast<uint32_t *>(s_dyn);
@@ -45,68 +41,28 @@ __global__ __launch_bounds__(NT, 2) void sketch_windows_kernel(TableParams p, co
     const int tid = threadIdx.x, lane = tid & 63;
     const uint32_t nreg = 1u << prec;
     for (uint32_t i = tid; i < nreg; i += NT) s_reg[i] = 0;
-    if (tid < 3) s_nl[(TILE + HALO) / 64 + tid] = ~0ULL;
-    if (tid < 2) s_codes[(TILE + HALO) / 32 + tid] = 0;
-    const uint32_t k = (uint32_t)p.k;
-    const uint64_t lbase = *line_base;
-    const uint64_t need0 = (k >= 64) ? ~0ULL : ((1ULL << k) - 1ULL);
-    const uint64_t need1 = (k > 64) ? ((k >= 128) ? ~0ULL : ((1ULL << (k - 64)) - 1ULL)) : 0ULL;
+    s.set_sentinels(tid);
+    const WindowRule rule(p, n, own_end, *line_base);
     unsigned long long nvalid = 0;   // valid windows this wave has seen (the same in every lane)
     for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t base = tile * TILE;
         lds_barrier();  // previous tile's LDS fully consumed (the first tile: the registers are zero)
-        {
-            const uint64_t off = base + (uint64_t)tid * 16;
-            uint32_t nl, le, code;
-            const uint4 v = load16(buf, off, n);
-            classify16(v, prev_is_nl(buf, off, n, head_open), nl, le, code);
-            if constexpr (BR) nl |= rule_bits16<BR>(p, qmap, v, off, n);
-            reinterpret_cast<uint32_t *>(s_codes)[tid] = code;
-            reinterpret_cast<uint16_t *>(s_nl)[tid] = (uint16_t)nl;
-            reinterpret_cast<uint16_t *>(s_le)[tid] = (uint16_t)le;
-            if (tid < HALO / 16) {
-                const uint64_t hoff = base + TILE + (uint64_t)tid * 16;
-                uint32_t hnl, hle, hcode;
-                const uint4 hv = load16(buf, hoff, n);
-                classify16(hv, false, hnl, hle, hcode);
-                if constexpr (BR) hnl |= rule_bits16<BR>(p, qmap, hv, hoff, n);
-                reinterpret_cast<uint32_t *>(s_codes)[TILE / 16 + tid] = hcode;
-                reinterpret_cast<uint16_t *>(s_nl)[TILE / 16 + tid] = (uint16_t)hnl;
-            }
-            const uint32_t c = __popc(le);
-            const uint32_t inc = wave_incl_scan(c);
-            if (lane == 63) s_wsum[tid >> 6] = inc;
-            lds_barrier();
-            uint32_t woff = tile_line[tile];
-            for (int w = 0; w < (tid >> 6); ++w) woff += s_wsum[w];
-            s_lb[tid] = woff + inc - c;
-        }
+        tile_stage<BR>(s, tile_load(buf, n, head_open, tile_line, tile, tid), p, qmap, base, n, tid);
         lds_barrier();
 
         for (int round = 0; round < TILE / BATCH; ++round) {
 #pragma unroll
             for (int j = 0; j < PER_THREAD; ++j) {
                 const uint32_t pp = (uint32_t)(round * BATCH + j * NT + tid);
-                const uint64_t gpos = base + pp;
-                const uint32_t grp = pp >> 4;
-                const uint32_t le_before = reinterpret_cast<const uint16_t *>(s_le)[grp] & ((1u << (pp & 15)) - 1u);
-                const uint32_t line = s_lb[grp] + __popc(le_before);
-                const uint32_t w = pp >> 6, o = pp & 63;
-                uint64_t m0 = s_nl[w] >> o, m1 = s_nl[w + 1] >> o;
-                if (o) { m0 |= s_nl[w + 1] << (64 - o); m1 |= s_nl[w + 2] << (64 - o); }
-                const bool valid = (((lbase + line) & p.line_mask) == 1u) && ((m0 & need0) == 0) && ((m1 & need1) == 0) &&
-                                   (gpos + k <= n) && (gpos < own_end);
+                uint32_t line;
+                const bool valid = window_valid(s, rule, base, pp, line);
                 const unsigned long long vm = __ballot(valid);
                 if (vm == 0ULL) continue;
                 nvalid += (unsigned long long)__popcll(vm);
                 uint64_t x[WK];
-                extract_kmer<WK>(s_codes, pp, p.top_mask, x);
-                uint64_t xp[WK];
-#pragma unroll
-                for (int t = 0; t < WK; ++t) xp[t] = __shfl_up((unsigned long long)x[t], 1, 64);
-                const bool prev_valid = __shfl_up((int)valid, 1, 64) != 0;
+                extract_kmer<WK>(s.codes, pp, p.top_mask, x);
                 // a window equal to the one in the lane below has its hash: leaders only
-                const bool leader = valid && (lane == 0 || !prev_valid || !kmer_eq<WK>(x, xp));
+                const bool leader = run_leader<WK>(x, valid, lane);
                 if (leader) {
                     if constexpr (CANON) lex_canonical<WK>(x, p.n);
                     uint32_t idx, rank;
