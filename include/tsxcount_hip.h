@@ -722,6 +722,9 @@ int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b, const tsx_
 int tsx_hip_hash_apply(const tsx_hip_map *m, const uint64_t *kmer, uint64_t *key_out);
 int tsx_hip_hash_invert(const tsx_hip_map *m, const uint64_t *key, uint64_t *kmer_out);
 int tsx_hip_hash_rows(const tsx_hip_map *m, uint64_t *rows_out /* 2k x key_limbs */);
+/* One-limb keys (k <= 32): the 16 x 16 table by 4-bit groups that the walk hashes a strip's first window with, as a map
+ * made with (k, l, hash_seed) gets it: lut_out[grp * 16 + v] = M * ((v << 4 grp) & (2^2k - 1)).  Host only, no GPU call. */
+int tsx_hip_lut4_host(int k, int l, uint64_t hash_seed, uint64_t *lut_out /* 256 */);
 
 /*
  * Multi-GPU counting with a sharded table (k <= 32).  Reads shard across the GPUs;

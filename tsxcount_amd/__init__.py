@@ -445,6 +445,7 @@ def lib():
     L.tsx_hip_hash_apply.argtypes = [vp, u64p, u64p]
     L.tsx_hip_hash_invert.argtypes = [vp, u64p, u64p]
     L.tsx_hip_hash_rows.argtypes = [vp, u64p]
+    L.tsx_hip_lut4_host.argtypes = [ci, ci, ctypes.c_uint64, u64p]
     L.tsx_hip_set_timing.argtypes = [vp, ci]
     L.tsx_hip_get_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                      ctypes.POINTER(ctypes.c_double), u64p]

@@ -642,7 +642,13 @@ __global__ __launch_bounds__(256) void desc_pack_kernel(const uint4 *desc, uint6
 // the descriptor regions g, g + G, ... (a region = what one wave of strip_desc_kernel wrote).
 // CANON (canonical counting): the hash of the reverse complement rolls alongside (mirror_step, tsx_device.h) and the
 // key of a position is the smaller of the two; the homopolymer keys are those of the pairs A/T and C/G.
-template <int NT, bool CANON = false>   // 512 threads, two workgroups per CU (up to 256 level-1 lists); 1024 threads where 512 lists leave room for one
+// LOCAL: the form of a plain one-GPU count (walk_local_form below says when the host may take it): every key stays, the
+// descriptions are short and lie region by region, nothing is appended, a flush follows every quarter strip.  The owner
+// test, the `emitted` count, the long-description selects, the flush cadence, the packed-run arithmetic and the
+// append reads are not compiled into it; every store address and every barrier is the general form's.
+// Both forms: the loops that depend on k alone (first-window hash, homopolymer smear, the word select of `inc`) are
+// unrolled with constant shifts behind wave-uniform guards.
+template <int NT, bool CANON = false, bool LOCAL = false>   // 512 threads, two workgroups per CU (up to 256 level-1 lists); 1024 threads where 512 lists leave room for one
 __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const uint4 *desc, uint64_t desc_cap,
                                                             const unsigned long long *desc_cnt, uint32_t nregions,
                                                             uint64_t *dst, uint64_t dst_cap, unsigned long long *dst_cnt,
@@ -652,8 +658,9 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
                                                             unsigned long long *emit_sum, int long_desc, uint32_t flush_q) {
     // own_flags: low two bits = 0 local run, 1 keep only the keys this shard owns, 2 minimizer exchange (below); 4 = this launch
     // APPENDS to the sub-lists and the overflow queue an earlier launch of the same step left (windows of a sharded step)
-    const int own_only = own_flags & 3;
-    const bool append = (own_flags & 4) != 0;
+    const int own_only = LOCAL ? 0 : own_flags & 3;
+    const bool append = !LOCAL && (own_flags & 4) != 0;
+    if constexpr (LOCAL) { n_packed = 0; dst_g0 = 0; long_desc = 0; }
     constexpr int HOT_N = 8;
     __shared__ uint64_t s_hot_key[(NT / 64) * HOT_N];
     __shared__ uint32_t s_hot_cnt[(NT / 64) * HOT_N];
@@ -683,6 +690,7 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
     const uint32_t gl = dst_g0 + wg;
     auto word_of = [&](uint32_t b, uint32_t at) -> uint64_t * { return dst + ((uint64_t)(b * dst_gtot + gl) * (uint64_t)cap32 + at); };
     auto is_mine = [&](uint64_t hk) -> bool {
+        if constexpr (LOCAL) return true;
         if (own_only != 1) return true;
         const uint64_t h1[1] = {hk};
         return owner_shard<1>(p, h1) == p.shard;
@@ -712,7 +720,24 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
     unsigned long long emitted = 0; // sharded runs: k-mer occurrences this GPU kept (sum over GPUs == k-mers scanned)
     uint32_t spilled = 0;
     const uint32_t k = (uint32_t)p.k;
-    const uint32_t ngrp = (2u * k + 3u) / 4u;
+    // what depends on k alone: the word and the bit at which base k of a strip starts (`inc`), and whether x has a high dword
+    const uint32_t inc_ws = (2u * k) >> 5, inc_sh = (2u * k) & 31u;
+    const bool two_dwords = k > 16u;
+    // The hash of a strip's first window: XOR over the 4-bit groups of x of s_lut4[16 * group + nibble], every group
+    // at a constant bit offset and a constant LDS offset.  NO guard per group: the groups at and above 2k bits are looked
+    // up as well.  x is masked by top_mask, so their nibble is 0, and the mapping is GF(2)-linear, so entry 0 of every
+    // group's table is 0 (tests/test_walk_forms.py pins it).  One wave-uniform test skips the high dword when k <= 16.
+    auto first_hash = [&](uint64_t x) -> uint64_t {
+        const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+        uint64_t hx = 0;
+#pragma unroll
+        for (int grp = 0; grp < 8; ++grp) hx ^= s_lut4[grp * 16 + __builtin_amdgcn_ubfe(xl, 4 * grp, 4)];
+        if (two_dwords) {
+#pragma unroll
+            for (int grp = 0; grp < 8; ++grp) hx ^= s_lut4[128 + grp * 16 + __builtin_amdgcn_ubfe(xh, 4 * grp, 4)];
+        }
+        return hx;
+    };
 
     const TableParams *pk = (const TableParams *)__builtin_amdgcn_kernarg_segment_ptr();
     // a key that found its sub-list full: spill cache (a hot key hits it), overflow queue, deferred list
@@ -801,8 +826,10 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
 
     lds_barrier();
     for (uint32_t r = blockIdx.x; r < nregions; r += gridDim.x) {
-        const uint32_t nr = n_packed ? (uint32_t)(((uint64_t)r * desc_cap < n_packed) ? min(desc_cap, n_packed - (uint64_t)r * desc_cap) : 0ULL)
-                                     : (uint32_t)min((uint64_t)desc_cnt[r], desc_cap);
+        uint32_t nr;
+        if constexpr (LOCAL) nr = (uint32_t)min((uint64_t)desc_cnt[r], desc_cap);
+        else nr = n_packed ? (uint32_t)(((uint64_t)r * desc_cap < n_packed) ? min(desc_cap, n_packed - (uint64_t)r * desc_cap) : 0ULL)
+                           : (uint32_t)min((uint64_t)desc_cnt[r], desc_cap);
         // long descriptions (32 bytes, four strips each; a batch is NT / 4 of them): lanes 4q .. 4q+3 read the same one
         const uint32_t per = long_desc ? NT / 4 : NT, me = long_desc ? tid >> 2 : tid;
         const uint4 *rd = desc + (uint64_t)r * desc_cap * (long_desc ? 2u : 1u);
@@ -819,7 +846,7 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
                 }
             }
             uint32_t cw0 = d.x, cw1 = d.y, cw2 = d.z, vm = d.w & 0xFFFFu;   // (bit 16: strip_desc_kernel's neighbour mark)
-            if (long_desc) {   // strip t of the four: bases 16 t .. 16 t + 47, validity bits 16 t .. 16 t + 15
+            if (!LOCAL && long_desc) {   // strip t of the four: bases 16 t .. 16 t + 47, validity bits 16 t .. 16 t + 15
                 const uint32_t t = tid & 3u;
                 const uint32_t w0 = d.x, w1 = d.y, w2 = d.z, w3 = d.w, w4 = d2.x, w5 = d2.y;
                 cw0 = (t == 0u) ? w0 : (t == 1u) ? w1 : (t == 2u) ? w2 : w3;
@@ -835,30 +862,32 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
                 const uint64_t lo = (uint64_t)cw0 | ((uint64_t)cw1 << 32), hi = cw2;
                 if (vm) {
                     const uint64_t x = lo & p.top_mask;
-                    for (uint32_t grp = 0; grp < ngrp; ++grp) h ^= s_lut4[grp * 16u + ((uint32_t)(x >> (4u * grp)) & 15u)];
+                    h = first_hash(x);
                     if constexpr (CANON) {
                         const uint64_t xa[1] = {x};
                         uint64_t r[1];
                         revcomp<1>(xa, p.n, r);
-                        for (uint32_t grp = 0; grp < ngrp; ++grp) hr ^= s_lut4[grp * 16u + ((uint32_t)(r[0] >> (4u * grp)) & 15u)];
+                        hr = first_hash(r[0]);
                     }
                 }
-                {
-                    const uint32_t o = 2u * k, ws = o >> 5, sh = o & 31u;
-                    const uint32_t w0 = (ws == 0u) ? cw0 : (ws == 1u) ? cw1 : cw2;
-                    const uint32_t w1 = (ws == 0u) ? cw1 : (ws == 1u) ? cw2 : 0u;
-                    inc = __funnelshift_r(w0, w1, sh);
-                }
+                // the bases that enter behind the first window: 32 bits from bit 2k of the strip's 96 (uniform branches)
+                if (inc_ws == 0u) inc = __funnelshift_r(cw0, cw1, inc_sh);
+                else if (inc_ws == 1u) inc = __funnelshift_r(cw1, cw2, inc_sh);
+                else inc = cw2 >> inc_sh;
             uint32_t homm = 0;   // bit j: the k-mer at strip position j is a homopolymer
-            if (own_only != 2) {   // (own_only 2, minimizer exchange: the sender took them out and counted them)
+            if (LOCAL || own_only != 2) {   // (own_only 2, minimizer exchange: the sender took them out and counted them)
                 const uint64_t dlo = lo ^ ((lo >> 2) | (hi << 62)), dhi = hi ^ (hi >> 2);
                 uint64_t rlo = (dlo | (dlo >> 1)) & 0x5555555555555555ULL, rhi = (dhi | (dhi >> 1)) & 0x5555555555555555ULL;
+                // smear over k - 1 neighbours: doubling steps of 1, 2, 4, 8, 16 at constant shifts while they fit
+                // (k is wave-uniform), then one step of what is left
                 uint32_t span = 1;
-                while (span * 2 <= k - 1) {
-                    const uint32_t sh = 2u * span;
-                    rlo |= (rlo >> sh) | (rhi << (64u - sh));
-                    rhi |= rhi >> sh;
-                    span *= 2;
+#pragma unroll
+                for (uint32_t st = 1; st <= 16u; st *= 2) {
+                    if (st * 2 <= k - 1) {
+                        rlo |= (rlo >> (2u * st)) | (rhi << (64u - 2u * st));
+                        rhi |= rhi >> (2u * st);
+                        span = st * 2;
+                    }
                 }
                 if (span < k - 1) {
                     const uint32_t sh = 2u * (k - 1 - span);
@@ -884,7 +913,7 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
                     if (__ballot(tot != 0u) == 0ULL) continue;
                     for (int d = 32; d > 0; d >>= 1) tot += __shfl_xor(tot, d, 64);
                     if (lane == 0 && is_mine(s_homh[b])) {
-                        emitted += tot;
+                        if constexpr (!LOCAL) emitted += tot;
                         const uint64_t key = s_homh[b];
                         uint64_t *hkey = s_hot_key + wave * HOT_N;
                         uint32_t *hcnt = s_hot_cnt + wave * HOT_N;
@@ -917,7 +946,7 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
                         }
                     }
                     uint32_t m4 = s4;   // positions of this quarter whose keys this GPU keeps
-                    if (own_only) {
+                    if constexpr (!LOCAL) if (own_only) {
                         if (own_only == 1) {
 #pragma unroll
                             for (int j = 0; j < 4; ++j)
@@ -952,7 +981,7 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
                 // GPU of a sharded run keeps one key in N: it flushes every flush_q quarters (N >= 4: once per batch) --
                 // three barriers and a pass over the rings less for each one skipped; a ring that fills up all the same
                 // sends its keys straight to the list.
-                if ((((j0 >> 2) + 1u) % flush_q) == 0u) {
+                if (LOCAL || (((j0 >> 2) + 1u) % flush_q) == 0u) {
                     lds_barrier();
                     flush(false, !waited);
                     waited = true;
@@ -968,7 +997,7 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
     if (tid < OVF_N && s_ovc[tid]) defer_append1(pk, s_ovk[tid] ^ OVF_SALT, s_ovc[tid]);
     if (tid == 0 && ovq_cnt) ovq_cnt[blockIdx.x] = min(s_ovn, ovq_cap);
     if (tid < (NT / 64) * HOT_N && s_hot_cnt[tid]) defer_append1(pk, s_hot_key[tid], s_hot_cnt[tid]);
-    if (emit_sum) {
+    if constexpr (!LOCAL) if (emit_sum) {
         for (int d = 32; d > 0; d >>= 1) emitted += __shfl_down(emitted, d, 64);
         if (lane == 0 && emitted) atomicAdd(emit_sum, emitted);
     }
@@ -977,6 +1006,13 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
         if (added) atomicAdd(&p.stats[ST_KMERS], added);
         if (spilled) atomicAdd(&p.stats[ST_FALLBACK], (unsigned long long)spilled);
     }
+}
+
+// Whether a launch of walk_part_kernel may take the LOCAL form -- decided from the launch's own arguments: every key
+// stays, nothing is appended, short descriptions region by region, a flush per quarter strip, nobody asks for the sum.
+inline bool walk_local_form(int own_flags, uint64_t n_packed, int long_desc, uint32_t flush_q, const void *emit_sum,
+                            uint32_t dst_g0) {
+    return own_flags == 0 && n_packed == 0 && !long_desc && flush_q == 1u && emit_sum == nullptr && dst_g0 == 0u;
 }
 
 // Inserts the overflow queues partition_ring_kernel left behind (one queue of `cap` records per

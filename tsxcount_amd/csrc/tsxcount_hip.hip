@@ -478,6 +478,18 @@ static void make_lut(const tsx_hip_map *m, const std::vector<uint64_t> &rows, st
         }
 }
 
+// One-limb keys: the mapping as a LUT by 4-bit groups, entry [grp * 16 + v] = M * ((v << 4 grp) & top_mask).  M is
+// linear, so entry 0 of every group is 0 -- walk_part_kernel looks up all 16 groups of a masked window and relies on it.
+static void make_lut4(const tsx_hip_map *m, std::vector<uint64_t> &lut4) {
+    lut4.assign(256, 0);
+    for (int grp = 0; grp < 16; ++grp)
+        for (uint64_t v = 0; v < 16; ++v) {
+            uint64_t x = (v << (4 * grp)) & m->p.top_mask, y = 0;
+            apply_rows(m, m->rows, &x, &y);
+            lut4[grp * 16 + v] = y;
+        }
+}
+
 // ---- layout -------------------------------------------------------------------
 static int derive_layout(tsx_hip_map *m, int k, int l, int s, int overflow_l, int shard_bits, int shard_index) {
     if (k < 1 || k > 127 || l < 4 || l > 36 || s < 0 || s > 32) return TSX_HIP_EINVAL;
@@ -599,15 +611,7 @@ extern "C" int tsx_hip_create_shard(tsx_hip_map **out, int k, int l, int storage
         // one-limb keys: the same mapping as a LUT by 4-bit groups (16 x 16 entries = 2 KiB) behind the roll
         // table -- walk_part_kernel has no LDS to spare for the 8-bit-group LUT (16 KiB)
         std::vector<uint64_t> lut4;
-        if (p.wk == 1) {
-            lut4.assign(256, 0);
-            for (int grp = 0; grp < 16; ++grp)
-                for (uint64_t v = 0; v < 16; ++v) {
-                    uint64_t x = (v << (4 * grp)) & p.top_mask, y = 0;
-                    apply_rows(m, m->rows, &x, &y);
-                    lut4[grp * 16 + v] = y;
-                }
-        }
+        if (p.wk == 1) make_lut4(m, lut4);
         // the mirror roll of the canonical walks behind both (MROLL1_AT / 64 * key_limbs words in, tsx_device.h)
         const void *msrc = (p.wk == 1) ? (const void *)m->mroll : (const void *)m->mroll_wide.data();
         TSX_TRY(m->d_roll.alloc(2 * bytes + lut4.size() * 8));
@@ -927,11 +931,36 @@ static int plan_partition(tsx_hip_map *m, uint64_t maxrec, int g, bool own_log, 
         HIP_TRY(hipFuncSetAttribute((const void *)walk_log_wide_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10));
         HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<SP_NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
         HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<SP_NT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<1024, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<SP_NT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
+        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<1024, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
         HIP_TRY(hipFuncSetAttribute((const void *)walk_log_wide_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10));
         HIP_TRY(hipFuncSetAttribute((const void *)walk_log_wide_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10));
         m->attr_done = true;
     }
     return TSX_HIP_OK;
+}
+
+// One launch of walk_part_kernel.  The form is picked from the launch's own arguments: LOCAL for what a plain one-GPU
+// count passes (walk_local_form, tsx_partition.h), the general form for everything else; 1024 threads where 512 lists
+// leave room for one workgroup per CU.
+static void launch_walk_part(tsx_hip_map *m, uint32_t grid, size_t lds, hipStream_t st, const TableParams &pp, const uint4 *desc,
+                             uint64_t desc_cap, const unsigned long long *desc_cnt, uint32_t nregions, uint64_t *dst,
+                             uint64_t dst_cap, unsigned long long *dst_cnt, uint32_t nb, uint32_t shift, uint64_t *ovq_all,
+                             uint32_t *ovq_cnt, uint32_t ovq_cap, uint64_t n_packed, uint32_t dst_g0, uint32_t dst_gtot,
+                             int own_flags, unsigned long long *emit_sum, int long_desc, uint32_t flush_q) {
+#define TSX_WALK(NTV, CANV, LOCV)                                                                                              \
+    hipLaunchKernelGGL((walk_part_kernel<NTV, CANV, LOCV>), dim3(grid), dim3(NTV), lds, st, pp, desc, desc_cap, desc_cnt,      \
+                       nregions, dst, dst_cap, dst_cnt, nb, shift, ovq_all, ovq_cnt, ovq_cap, n_packed, dst_g0, dst_gtot,      \
+                       own_flags, emit_sum, long_desc, flush_q)
+    const bool local = walk_local_form(own_flags, n_packed, long_desc, flush_q, emit_sum, dst_g0);
+    if (lds > ((size_t)80 << 10)) {   // 512 lists: one workgroup per CU, 1024 threads
+        if (local) { DISPATCH_CANON(m, TSX_WALK(1024, CANV, true)); } else { DISPATCH_CANON(m, TSX_WALK(1024, CANV, false)); }
+    } else {
+        if (local) { DISPATCH_CANON(m, TSX_WALK(SP_NT, CANV, true)); } else { DISPATCH_CANON(m, TSX_WALK(SP_NT, CANV, false)); }
+    }
+#undef TSX_WALK
 }
 
 // The window-wise level 1 of a sharded run plans with its own sub-list buffer and counters in the map's place.
@@ -1278,19 +1307,10 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
                                head_open, (const uint32_t *)m->d_tile.get(), ntiles, (uint4 *)m->d_buf[0].get(), desc_cap, pl.c_log,
                                (unsigned long long *)nullptr, lng, (unsigned long long *)nullptr, m->qmap_cur));
             HIP_TRY(hipGetLastError());
-            if (lds > ((size_t)80 << 10)) {   // 512 lists: one workgroup per CU, 1024 threads
-                DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<1024, CANV>), dim3(pl.G1), dim3(1024), lds, st, pp,
-                                   (const uint4 *)m->d_buf[0].get(), desc_cap,
-                                   (const unsigned long long *)pl.c_log, (uint32_t)gdreg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
-                                   (uint32_t)(p.l - pl.b1), m->d_ovq.get() + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt.get() + nq2, OVQ_CAP,
-                                   (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, 1u));
-            } else {
-                DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<SP_NT, CANV>), dim3(pl.G1), dim3(SP_NT), lds, st, pp,
-                                   (const uint4 *)m->d_buf[0].get(), desc_cap,
-                                   (const unsigned long long *)pl.c_log, (uint32_t)gdreg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
-                                   (uint32_t)(p.l - pl.b1), m->d_ovq.get() + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt.get() + nq2, OVQ_CAP,
-                                   (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, 1u));
-            }
+            launch_walk_part(m, pl.G1, lds, st, pp, (const uint4 *)m->d_buf[0].get(), desc_cap,
+                             (const unsigned long long *)pl.c_log, (uint32_t)gdreg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
+                             (uint32_t)(p.l - pl.b1), m->d_ovq.get() + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt.get() + nq2, OVQ_CAP,
+                             (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, 1u);
         }
     } else if (p.wk == 1) {
         // key log form (sharded scans, one-level tables), the scan in two kernels as well: descriptions into buffer 1
@@ -1771,19 +1791,11 @@ static int shard_walk(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int l
     pp.defer = m->defer();
     const size_t lds = (size_t)pl.nb1 * (((size_t)8 << SP_CAPBITS) + 8 + 8 + 4 + 4);
     // (a canonical map gets here only from count_slabs: the exchanges refuse it)
-    if (lds > ((size_t)80 << 10)) {   // 512 lists: one workgroup per CU, 1024 threads
-        DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<1024, CANV>), dim3(gw), dim3(1024), lds, st, pp, (const uint4 *)dev_desc, chunk,
-                           (const unsigned long long *)nullptr, gw, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
-                           (uint32_t)(m->p.l - pl.b1), m->d_ovq.get() + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
-                           m->d_ovq_cnt.get() + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
-                           (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q));
-    } else {
-        DISPATCH_CANON(m, hipLaunchKernelGGL((walk_part_kernel<SP_NT, CANV>), dim3(gw), dim3(SP_NT), lds, st, pp, (const uint4 *)dev_desc, chunk,
-                           (const unsigned long long *)nullptr, gw, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
-                           (uint32_t)(m->p.l - pl.b1), m->d_ovq.get() + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
-                           m->d_ovq_cnt.get() + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
-                           (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q));
-    }
+    launch_walk_part(m, gw, lds, st, pp, (const uint4 *)dev_desc, chunk,
+                     (const unsigned long long *)nullptr, gw, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
+                     (uint32_t)(m->p.l - pl.b1), m->d_ovq.get() + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
+                     m->d_ovq_cnt.get() + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
+                     (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q);
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
@@ -3817,6 +3829,20 @@ extern "C" int tsx_hip_hash_invert(const tsx_hip_map *m, const uint64_t *key, ui
 extern "C" int tsx_hip_hash_rows(const tsx_hip_map *m, uint64_t *rows_out) {
     if (!m || !rows_out) return TSX_HIP_EINVAL;
     memcpy(rows_out, m->rows.data(), m->rows.size() * 8);
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_lut4_host(int k, int l, uint64_t hash_seed, uint64_t *lut_out) {
+    if (!lut_out || k > 32) return TSX_HIP_EINVAL;
+    tsx_hip_map t;   // host state only: layout and mapping, no device is touched
+    const int rc = derive_layout(&t, k, l, 0, 0, 0, 0);
+    if (rc != TSX_HIP_OK) return rc;
+    t.seed = hash_seed;
+    const int rm = make_mapping(&t);
+    if (rm != TSX_HIP_OK) return rm;
+    std::vector<uint64_t> lut4;
+    make_lut4(&t, lut4);
+    memcpy(lut_out, lut4.data(), lut4.size() * 8);
     return TSX_HIP_OK;
 }
 
