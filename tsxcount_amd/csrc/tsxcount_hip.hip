@@ -181,8 +181,10 @@ struct tsx_hip_map {
 };
 
 static const size_t STAGE_PAD = 256;
-static const int EV_N = 8;   // timing events per piece: before pass 1, before the scan, after it, start of the partition
-                             // phase, after level 1, after level 2, after the build kernel, after the inserts behind it
+// The timing events of one tuple (a piece, a window, a slab), in stream order: before the line pass, before the scan or
+// the description, after it, start of the partition phase (later than the scan's end only in a sharded run: the exchange
+// lies between), after level 1, after level 2, after the build kernel, after the inserts behind it.
+enum TimingEvent { EV_BEGIN = 0, EV_SCAN, EV_SCAN_END, EV_PART, EV_L1_END, EV_L2_END, EV_BUILD_END, EV_END, EV_N };
 static bool can_partition(const tsx_hip_map *m);
 static int clear_impl(tsx_hip_map *m, bool full);
 static int ensure_zeroed(tsx_hip_map *m, hipStream_t st);
@@ -821,15 +823,38 @@ static bool can_partition(const tsx_hip_map *m) {
     const int sb = slab_bits(m);
     return sb >= 1 && sb <= 4;
 }
-// workgroups of level 2 per level-1 bucket (plan_partition's cpr2) for the map's geometry
-static uint32_t level2_cpr(const tsx_hip_map *m) {
-    const int nsegbits = m->p.l - m->p.S;
+
+// ---- the geometry of the partitioned path, each rule written down once ----------------------------------------------------
+// Radix bits of level 1 / level 2 for 2^nsegbits segments (b2 == 0: one level).  The fan-out per level is capped at 512:
+// the histogram of the scan kernel and the ring staging live in LDS.
+struct RadixBits { int b1, b2; };
+static inline RadixBits radix_bits(int nsegbits) {
     const int b1 = std::min(9, (nsegbits <= 8) ? nsegbits : (nsegbits + 1) / 2);
-    if (nsegbits - b1 <= 0) return 1;
-    uint32_t c = std::min<uint32_t>(8, std::max<uint32_t>(1, (uint32_t)(m->cus * 8) / (1u << b1)));
+    return RadixBits{b1, nsegbits - b1};
+}
+// Workgroups of level 2 per level-1 bucket, each with a sub-list per segment: a power of two (the build gives every sub-list 16 / cpr2 waves).
+static inline uint32_t cpr2_for(int cus, RadixBits rb) {
+    if (rb.b2 <= 0) return 1;
+    uint32_t c = std::min<uint32_t>(8, std::max<uint32_t>(1, (uint32_t)(cus * 8) / (1u << rb.b1)));
     while (c & (c - 1)) c &= c - 1;
     return c;
 }
+static uint32_t level2_cpr(const tsx_hip_map *m) { return cpr2_for(m->cus, radix_bits(m->p.l - m->p.S)); }
+// Ring depth of partition_ring_kernel (log2 words): PART_FLUSH-1 words may stay behind a flush, plus one batch of arrivals.
+static inline uint32_t ring_bits(uint32_t nb) {
+    const uint32_t mean = std::max<uint32_t>(1, RING_NT * PART_WPT / nb);
+    uint32_t bits = 4;
+    while ((1u << bits) < PART_FLUSH + 2 * mean && bits < 6) ++bits;
+    return bits;
+}
+// A level 1 over RECEIVED keys (sharded entry points): 32-word rings -- 16 words may stay behind a flush, 8 arrive per batch.
+static const uint32_t RECV_RING_BITS = 5;
+// Dynamic LDS of partition_ring_kernel: per list a ring of 2^bits words + 36 bytes of cursors, limits and descriptors.
+static inline size_t ring_lds_bytes(uint32_t nb, uint32_t bits) { return (size_t)nb * (((size_t)8 << bits) + 36); }
+// Dynamic LDS of walk_part_kernel: per level-1 list a ring, flush descriptor, tail|head, cursor, job.
+static inline size_t walk_lds_bytes(uint32_t nb1) { return (size_t)nb1 * (((size_t)8 << SP_CAPBITS) + 8 + 8 + 4 + 4); }
+// Above this much LDS one workgroup fits a CU: the ring and walk kernels run with 1024 threads then (16 waves either way).
+static const size_t ONE_WG_LDS = (size_t)80 << 10;
 
 // Grow-only scratch: room for `need` bytes, an eighth + 4 KiB more when it has to be allocated anew.
 template <typename B>
@@ -851,6 +876,38 @@ static int ensure_deferred(tsx_hip_map *m, uint64_t maxrec, hipStream_t st) {
     return rc;
 }
 
+// The dynamic-LDS limits of the partition, walk and build kernels, once per map, hence per device: the attribute belongs
+// to the device's copy of the kernel.  Every instantiation the launchers below can pick stands in one of these lists.
+template <typename... K>
+static int set_max_lds(int bytes, K... kernels) {
+    for (const void *f : {(const void *)kernels...})
+        HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    return TSX_HIP_OK;
+}
+template <int RW>
+static int set_ring_lds(int bytes) {
+    return set_max_lds(bytes, partition_ring_kernel<RW>, partition_ring_kernel<RW, 1024>, partition_ring_kernel<RW, RING_NT, true>,
+                       partition_ring_kernel<RW, 1024, true>);
+}
+template <int NTV>
+static int set_walk_lds(int bytes) {
+    return set_max_lds(bytes, walk_part_kernel<NTV>, walk_part_kernel<NTV, true>, walk_part_kernel<NTV, false, true>,
+                       walk_part_kernel<NTV, true, true>);
+}
+static int set_partition_attrs(tsx_hip_map *m) {
+    if (m->attr_done) return TSX_HIP_OK;
+    const int big = 150 << 10, seg = (128 << 10) + (32 << 10);
+    TSX_TRY(set_ring_lds<1>(big)); TSX_TRY(set_ring_lds<2>(big)); TSX_TRY(set_ring_lds<4>(big));
+    TSX_TRY(set_walk_lds<SP_NT>(big)); TSX_TRY(set_walk_lds<1024>(big));
+    TSX_TRY(set_max_lds(seg, build_segments_stream_kernel<false>, build_segments_stream_kernel<true>,
+                        build_segments_wide_stream_kernel<1>, build_segments_wide_stream_kernel<2>,
+                        build_segments_wide_stream_kernel<3>, build_segments_wide_stream_kernel<4>));
+    TSX_TRY(set_max_lds(64 << 10, walk_log_wide_kernel<3>, walk_log_wide_kernel<4>, walk_log_wide_kernel<3, true>,
+                        walk_log_wide_kernel<4, true>));
+    m->attr_done = true;
+    return TSX_HIP_OK;
+}
+
 // maxrec: upper bound of records; g: number of source regions; own_log: the records come from
 // this map's scan kernel (needs the log buffer); hist_nb_override: sharded scan.
 static int plan_partition(tsx_hip_map *m, uint64_t maxrec, int g, bool own_log, uint32_t hist_nb_override,
@@ -860,17 +917,14 @@ static int plan_partition(tsx_hip_map *m, uint64_t maxrec, int g, bool own_log, 
     pl.g = g;
     pl.rw = rec_words(p.wk);
     pl.nseg = 1u << nsegbits;
-    // fan-out per level is capped at 512 (histogram of the scan kernel and ring staging live in LDS)
-    pl.b1 = std::min(9, (nsegbits <= 8) ? nsegbits : (nsegbits + 1) / 2);
-    pl.b2 = nsegbits - pl.b1;
+    const RadixBits rb = radix_bits(nsegbits);
+    pl.b1 = rb.b1; pl.b2 = rb.b2;
     pl.nb1 = 1u << pl.b1; pl.nb2 = 1u << pl.b2;
     pl.hist_nb = hist_nb_override ? hist_nb_override : pl.nb1;
     auto even = [](uint64_t v) { return (v + 1) & ~1ULL; };
     pl.log_cap = even(maxrec / g + maxrec / g / 3 + 2048);
     if (const char *e = getenv("TSX_HIP_LOG_CAP")) pl.log_cap = even(std::max(16, atoi(e)));  // tests: force region overflow
-    // level 2 runs cpr2 workgroups per level-1 bucket; each owns one sub-list per segment
-    pl.cpr2 = pl.b2 ? (uint32_t)std::min<uint32_t>(8, std::max<uint32_t>(1, (uint32_t)(m->cus * 8) / pl.nb1)) : 1;
-    while (pl.cpr2 & (pl.cpr2 - 1)) pl.cpr2 &= pl.cpr2 - 1;   // a power of two: the build gives every sub-list 16/cpr2 waves
+    pl.cpr2 = cpr2_for(m->cus, rb);
     if (pl.b2) if (const char *e = getenv("TSX_HIP_CPR2")) pl.cpr2 = (uint32_t)std::min(8, std::max(1, atoi(e)));
     const uint64_t per_sub = maxrec / pl.nseg / pl.cpr2;
     // multiple of 16 records: every sub-list starts on a 128-B line
@@ -905,62 +959,98 @@ static int plan_partition(tsx_hip_map *m, uint64_t maxrec, int g, bool own_log, 
     pl.d_offs = pl.c_l1 + (size_t)pl.nb1 * pl.G1;
     pl.d_hist = reinterpret_cast<uint32_t *>(pl.d_offs + mat);
     HIP_TRY(hipMemsetAsync(m->d_cnt.get(), 0, pl.cnt_need * 8, st));
-    if (!m->attr_done) {   // per map, hence per device: the attribute belongs to the device's copy of the kernel
-        const int big = 150 << 10, seg = 128 << 10;
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<1, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<1, RING_NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<2, RING_NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<4, RING_NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<1, 1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<2, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<4, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<2, 1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)partition_ring_kernel<4, 1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)build_segments_stream_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
-        HIP_TRY(hipFuncSetAttribute((const void *)build_segments_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
-        HIP_TRY(hipFuncSetAttribute((const void *)build_segments_wide_stream_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
-        HIP_TRY(hipFuncSetAttribute((const void *)build_segments_wide_stream_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
-        HIP_TRY(hipFuncSetAttribute((const void *)build_segments_wide_stream_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
-        HIP_TRY(hipFuncSetAttribute((const void *)build_segments_wide_stream_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, seg + (32 << 10)));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<SP_NT>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_log_wide_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_log_wide_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<SP_NT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<SP_NT, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<1024, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<SP_NT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_part_kernel<1024, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_log_wide_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10));
-        HIP_TRY(hipFuncSetAttribute((const void *)walk_log_wide_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 << 10));
-        m->attr_done = true;
-    }
+    TSX_TRY(set_partition_attrs(m));
     return TSX_HIP_OK;
 }
 
 // One launch of walk_part_kernel.  The form is picked from the launch's own arguments: LOCAL for what a plain one-GPU
 // count passes (walk_local_form, tsx_partition.h), the general form for everything else; 1024 threads where 512 lists
 // leave room for one workgroup per CU.
-static void launch_walk_part(tsx_hip_map *m, uint32_t grid, size_t lds, hipStream_t st, const TableParams &pp, const uint4 *desc,
-                             uint64_t desc_cap, const unsigned long long *desc_cnt, uint32_t nregions, uint64_t *dst,
-                             uint64_t dst_cap, unsigned long long *dst_cnt, uint32_t nb, uint32_t shift, uint64_t *ovq_all,
-                             uint32_t *ovq_cnt, uint32_t ovq_cap, uint64_t n_packed, uint32_t dst_g0, uint32_t dst_gtot,
-                             int own_flags, unsigned long long *emit_sum, int long_desc, uint32_t flush_q) {
+// The launch records below carry the kernel's own parameter names, in the kernel's order; a field left alone is the
+// "absent" value (null, 0, one piece).  Each kernel family has ONE launcher that hands the fields over.
+struct WalkPartLaunch {
+    uint32_t grid = 0;
+    const uint4 *desc = nullptr; uint64_t desc_cap = 0; const unsigned long long *desc_cnt = nullptr; uint32_t nregions = 0;
+    uint64_t *dst = nullptr; uint64_t dst_cap = 0; unsigned long long *dst_cnt = nullptr; uint32_t nb = 0, shift = 0;
+    uint64_t *ovq_all = nullptr; uint32_t *ovq_cnt = nullptr; uint32_t ovq_cap = 0; uint64_t n_packed = 0;
+    uint32_t dst_g0 = 0, dst_gtot = 0; int own_flags = 0; unsigned long long *emit_sum = nullptr; int long_desc = 0; uint32_t flush_q = 0;
+};
+static void launch_walk_part(tsx_hip_map *m, hipStream_t st, const TableParams &pp, const WalkPartLaunch &a) {
+    const size_t lds = walk_lds_bytes(a.nb);
 #define TSX_WALK(NTV, CANV, LOCV)                                                                                              \
-    hipLaunchKernelGGL((walk_part_kernel<NTV, CANV, LOCV>), dim3(grid), dim3(NTV), lds, st, pp, desc, desc_cap, desc_cnt,      \
-                       nregions, dst, dst_cap, dst_cnt, nb, shift, ovq_all, ovq_cnt, ovq_cap, n_packed, dst_g0, dst_gtot,      \
-                       own_flags, emit_sum, long_desc, flush_q)
-    const bool local = walk_local_form(own_flags, n_packed, long_desc, flush_q, emit_sum, dst_g0);
-    if (lds > ((size_t)80 << 10)) {   // 512 lists: one workgroup per CU, 1024 threads
+    hipLaunchKernelGGL((walk_part_kernel<NTV, CANV, LOCV>), dim3(a.grid), dim3(NTV), lds, st, pp, a.desc, a.desc_cap,          \
+                       a.desc_cnt, a.nregions, a.dst, a.dst_cap, a.dst_cnt, a.nb, a.shift, a.ovq_all, a.ovq_cnt, a.ovq_cap,    \
+                       a.n_packed, a.dst_g0, a.dst_gtot, a.own_flags, a.emit_sum, a.long_desc, a.flush_q)
+    const bool local = walk_local_form(a.own_flags, a.n_packed, a.long_desc, a.flush_q, a.emit_sum, a.dst_g0);
+    if (lds > ONE_WG_LDS) {   // 512 lists
         if (local) { DISPATCH_CANON(m, TSX_WALK(1024, CANV, true)); } else { DISPATCH_CANON(m, TSX_WALK(1024, CANV, false)); }
     } else {
         if (local) { DISPATCH_CANON(m, TSX_WALK(SP_NT, CANV, true)); } else { DISPATCH_CANON(m, TSX_WALK(SP_NT, CANV, false)); }
     }
 #undef TSX_WALK
+}
+
+// Launch with the record width as a compile-time constant.
+#define DISPATCH_RW(rw, CALL)                        \
+    switch (rw) {                                    \
+        case 1: { constexpr int RWV = 1; CALL; } break; \
+        case 2: { constexpr int RWV = 2; CALL; } break; \
+        default: { constexpr int RWV = 4; CALL; } break; \
+    }
+
+// One launch of partition_ring_kernel: the only dispatch over the record width, the workgroup size and SKEW.
+struct RingLaunch {
+    uint32_t grid = 0;
+    int rw = 1;               // words per record
+    bool skew = false;        // the SKEW form (level 2)
+    bool fixed_nt = false;    // RING_NT threads whatever the rings take (a level 1 over received keys); else 1024 above ONE_WG_LDS
+    const uint64_t *src = nullptr; const unsigned long long *src_start = nullptr, *src_cnt = nullptr; uint64_t src_cap = 0;
+    uint32_t nregions = 0, cpr = 1; uint64_t *dst = nullptr; const unsigned long long *offs = nullptr, *offs_base = nullptr;
+    unsigned long long *dst_cnt = nullptr; uint64_t dst_cap = 0; uint32_t nb = 0, shift = 0, capbits = 0;
+    uint64_t *ovq_all = nullptr; uint32_t *ovq_cnt = nullptr; uint32_t ovq_cap = 0;
+    const unsigned long long *src_pcnt = nullptr; uint32_t src_np = 0; uint64_t src_pcap = 0; int dst_bm = 0;
+    unsigned long long *key_sum = nullptr; uint32_t dst_r0 = 0, dst_nr = 0; int fmt = 0; uint32_t dch = 0; const uint32_t *skew_flag = nullptr;
+};
+static void launch_ring(hipStream_t st, const TableParams &pp, const RingLaunch &a) {
+    const size_t lds = ring_lds_bytes(a.nb, a.capbits);
+#define TSX_RING(RWV, NTV, SK)                                                                                                 \
+    hipLaunchKernelGGL((partition_ring_kernel<RWV, NTV, SK>), dim3(a.grid), dim3(NTV), lds, st, pp, a.src, a.src_start,        \
+                       a.src_cnt, a.src_cap, a.nregions, a.cpr, a.dst, a.offs, a.offs_base, a.dst_cnt, a.dst_cap, a.nb,        \
+                       a.shift, a.capbits, a.ovq_all, a.ovq_cnt, a.ovq_cap, a.src_pcnt, a.src_np, a.src_pcap, a.dst_bm,        \
+                       a.key_sum, a.dst_r0, a.dst_nr, a.fmt, a.dch, a.skew_flag)
+    // (512 lists: the rings leave room for one workgroup per CU -- 1024 threads then, 16 waves either way)
+    if (!a.fixed_nt && lds > ONE_WG_LDS) {
+        if (a.skew) { DISPATCH_RW(a.rw, TSX_RING(RWV, 1024, true)); } else { DISPATCH_RW(a.rw, TSX_RING(RWV, 1024, false)); }
+    } else {
+        if (a.skew) { DISPATCH_RW(a.rw, TSX_RING(RWV, RING_NT, true)); } else { DISPATCH_RW(a.rw, TSX_RING(RWV, RING_NT, false)); }
+    }
+#undef TSX_RING
+}
+
+// walk_log_kernel (one-limb keys) / walk_log_wide_kernel (the last four fields do not exist there and stay absent).
+struct WalkLogLaunch {
+    uint32_t grid = 0;
+    const uint4 *desc = nullptr; uint64_t desc_cap = 0; const unsigned long long *desc_cnt = nullptr; uint32_t nregions = 0;
+    uint64_t *log = nullptr; uint64_t log_cap = 0; unsigned long long *log_cnt = nullptr; uint32_t *hist = nullptr;
+    uint32_t hist_nb = 0, hist_shift = 0; uint64_t n_packed = 0; int long_desc = 0, own_only = 0; unsigned long long *emit_sum = nullptr;
+};
+static void launch_walk_log(tsx_hip_map *m, hipStream_t st, const TableParams &pp, const WalkLogLaunch &a) {
+    const size_t lut_bytes = m->lut.size() * 8;
+#define TSX_WALK_WIDE(WKV)                                                                                                     \
+    DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_wide_kernel<WKV, CANV>), dim3(a.grid), dim3(NT), lut_bytes, st, pp, a.desc, \
+                                         a.desc_cap, a.desc_cnt, a.nregions, a.log, a.log_cap, a.log_cnt, a.hist, a.hist_nb,   \
+                                         a.hist_shift))
+    switch (m->p.wk) {
+        case 1:
+            DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_kernel<CANV>), dim3(a.grid), dim3(NT), lut_bytes, st, pp, a.desc,
+                                                 a.desc_cap, a.desc_cnt, a.nregions, a.log, a.log_cap, a.log_cnt, a.hist,
+                                                 a.hist_nb, a.hist_shift, a.n_packed, a.long_desc, a.own_only, a.emit_sum));
+            break;
+        case 2: TSX_WALK_WIDE(2); break;
+        case 3: TSX_WALK_WIDE(3); break;
+        default: TSX_WALK_WIDE(4); break;
+    }
+#undef TSX_WALK_WIDE
 }
 
 // The window-wise level 1 of a sharded run plans with its own sub-list buffer and counters in the map's place.
@@ -983,13 +1073,45 @@ static int ensure_ovq(tsx_hip_map *m, size_t nq, int rw, hipStream_t st) {
 // queues of a map whose records are rw words wide (the skew flags lie behind their counters)
 static inline size_t ovq_queues(const tsx_hip_map *m, int rw) { return m->d_ovq.cap() / ((size_t)OVQ_CAP * 8 * rw); }
 
-// Launch with the record width as a compile-time constant.
-#define DISPATCH_RW(rw, CALL)                        \
-    switch (rw) {                                    \
-        case 1: { constexpr int RWV = 1; CALL; } break; \
-        case 2: { constexpr int RWV = 2; CALL; } break; \
-        default: { constexpr int RWV = 4; CALL; } break; \
-    }
+// Level-1 lists per slot of a sharded step: two workgroups per CU while the pieces of a bucket stay within what a
+// level-2 workgroup walks.
+static uint32_t shard_lists_per_slot(const tsx_hip_map *m, uint32_t nslots) {
+    uint32_t gw = (uint32_t)m->cus * 2;
+    while (gw > 32 && (uint64_t)gw * nslots > (uint64_t)PART_MAX_PIECES * level2_cpr(m)) gw /= 2;
+    return gw;
+}
+// The sharded level 1 of a step, window by window (or slot by slot).  first: the step begins -- plan `sets` sets of `rw`
+// lists for maxrec records into sh_pl, make room in the deferred list and the overflow queues, clear their counters, and
+// remember the step's shape; a later window or slot must find that shape (`windows`) and a fused plan.
+static int sharded_l1_step(tsx_hip_map *m, bool first, uint32_t rw, uint32_t sets, uint32_t windows, uint64_t maxrec,
+                           hipStream_t st) {
+    if (!m->sh_pl) m->sh_pl.reset(new PartPlan());
+    PartPlan &pl = *m->sh_pl;
+    if (!first) return (m->sh_windows != windows || !pl.fused) ? TSX_HIP_EINVAL : TSX_HIP_OK;
+    m->sh_rw = rw;
+    m->sh_windows = windows;
+    TSX_TRY(plan_sharded_l1(m, maxrec, (int)(rw * sets), st, pl));
+    if (!pl.fused) return TSX_HIP_EINVAL;
+    TSX_TRY(ensure_deferred(m, maxrec, st));
+    HIP_TRY(hipMemsetAsync(m->d_def_n.get(), 0, 8, st));
+    const size_t nq = (size_t)pl.nb1 * pl.cpr2 + pl.G1;
+    TSX_TRY(ensure_ovq(m, nq, pl.rw, st));
+    HIP_TRY(hipMemsetAsync(m->d_ovq_cnt.get(), 0, nq * 4, st));   // (also the queues of windows that never run)
+    return TSX_HIP_OK;
+}
+// A level 1 over received one-limb keys: `grid` workgroups, each with a fixed-capacity sub-list per bucket among the
+// plan's G1 (as level 2 keeps them -- no histogram pass) and an overflow queue, the first of them queue `list0` behind
+// level 2's.  The caller names the source and which lists the workgroups fill (dst_r0, dst_nr).
+static RingLaunch recv_level1(const tsx_hip_map *m, const PartPlan &pl, uint32_t grid, uint32_t list0) {
+    RingLaunch r;
+    r.grid = grid; r.fixed_nt = true;
+    r.dst = pl.buf1; r.dst_cnt = pl.c_l1; r.dst_cap = pl.cap1;
+    r.nb = pl.nb1; r.shift = (uint32_t)(m->p.l - pl.b1); r.capbits = RECV_RING_BITS;
+    const size_t q0 = (size_t)pl.nb1 * pl.cpr2 + list0;
+    r.ovq_all = m->d_ovq.get() + q0 * OVQ_CAP; r.ovq_cnt = m->d_ovq_cnt.get() + q0; r.ovq_cap = OVQ_CAP;
+    r.dst_bm = 1;
+    return r;
+}
 
 // Radix level 1 (+ level 2), the segment build, then everything that waited for the build (overflow
 // queues, deferred list).  Source records: g regions of `src`, either src_cap apart with fills c_log (a
@@ -1003,35 +1125,21 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
     const TableParams &p = m->p;
     pp.defer = m->defer();
     const int rw = pl.rw;
-    // ring depth in words: PART_FLUSH-1 words may stay behind a flush, plus one batch of arrivals (mean = batch / nb)
-    auto ring_bits = [](uint32_t nb) {
-        const uint32_t mean = std::max<uint32_t>(1, RING_NT * PART_WPT / nb);
-        uint32_t bits = 4;
-        while ((1u << bits) < PART_FLUSH + 2 * mean && bits < 6) ++bits;
-        return bits;
-    };
-    auto part_lds = [](uint32_t nb, uint32_t bits) { return (size_t)nb * (((size_t)8 << bits) + 36); };
     if (!pl.fused) {
     hipLaunchKernelGGL(offsets_rows_kernel, dim3(pl.nb1), dim3(1024), 0, st, (const uint32_t *)pl.d_hist, pl.d_offs,
                        (uint32_t)pl.g, pl.c_bcnt);
     hipLaunchKernelGGL(offsets_finish_kernel, dim3(1), dim3(1024), 0, st, pl.nb1, pl.c_bstart, pl.c_bcnt);
     {   // level 1: every region -> packed array ordered by the top b1 bits of the home slot
-        const uint32_t bits = ring_bits(pl.nb1);
-#define TSX_LEVEL1(RWV, NTV)                                                                                                   \
-        hipLaunchKernelGGL((partition_ring_kernel<RWV, NTV>), dim3(pl.g), dim3(NTV), part_lds(pl.nb1, bits), st,                 \
-                           pp, src, region_start, (const unsigned long long *)pl.c_log, src_cap, (uint32_t)pl.g, 1u,             \
-                           pl.buf1, (const unsigned long long *)pl.d_offs, (const unsigned long long *)pl.c_bstart,              \
-                           (unsigned long long *)nullptr, (uint64_t)0, pl.nb1, (uint32_t)(p.l - pl.b1), bits,                    \
-                           (uint64_t *)nullptr, (uint32_t *)nullptr, 0u, (const unsigned long long *)nullptr, 0u, (uint64_t)0,   \
-                           0, (unsigned long long *)nullptr, 0u, 0u, 0, 0u, (const uint32_t *)nullptr)
-        // (512 lists: the rings leave room for one workgroup per CU -- 1024 threads then, 16 waves either way)
-        if (part_lds(pl.nb1, bits) > ((size_t)80 << 10)) { DISPATCH_RW(rw, TSX_LEVEL1(RWV, 1024)); }
-        else { DISPATCH_RW(rw, TSX_LEVEL1(RWV, RING_NT)); }
-#undef TSX_LEVEL1
+        RingLaunch r;
+        r.grid = (uint32_t)pl.g; r.rw = rw;
+        r.src = src; r.src_start = region_start; r.src_cnt = pl.c_log; r.src_cap = src_cap; r.nregions = (uint32_t)pl.g;
+        r.dst = pl.buf1; r.offs = pl.d_offs; r.offs_base = pl.c_bstart;
+        r.nb = pl.nb1; r.shift = (uint32_t)(p.l - pl.b1); r.capbits = ring_bits(pl.nb1);
+        launch_ring(st, pp, r);
         HIP_TRY(hipGetLastError());
     }
     }   // (fused: walk_part_kernel has left the level-1 sub-lists in buffer 1)
-    if (ev) HIP_TRY(hipEventRecord(ev[4].get(), st));
+    if (ev) HIP_TRY(hipEventRecord(ev[EV_L1_END].get(), st));
     const uint64_t *lists = pl.buf1;
     const unsigned long long *lists_start = pl.c_bstart, *lists_cnt = pl.c_bcnt;
     uint64_t lists_cap = 0;
@@ -1041,7 +1149,6 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
     // slots reads them and the fields fit: slot image in bits [0, R + F), first probe position above
     const int pre = (pl.b2 && p.wk == 1 && p.W == 1 && p.R + p.F >= 32 && p.R + p.F + p.S <= 64) ? 1 : 0;
     if (pl.b2) {  // level 2: cpr2 workgroups per level-1 bucket, each with its own sub-list per segment
-        const uint32_t bits = ring_bits(pl.nb2);
         nq2 = pl.nb1 * pl.cpr2;   // one overflow queue per workgroup (the fused scan's queues follow them)
         // records per private chunk of the deferred list (mass spills of skewed input, see partition_ring_kernel): a
         // quarter of the list shared out over the workgroups, a power of two in 64 .. 4096; 0: the list is too small
@@ -1059,25 +1166,21 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
         DISPATCH_RW(rw, hipLaunchKernelGGL((skew_probe_kernel<RWV>), dim3(pl.nb1), dim3(256), 0, st, (const uint64_t *)pl.buf1,
                                            (const unsigned long long *)pl.c_bstart, (const unsigned long long *)pl.c_bcnt,
                                            (const unsigned long long *)(pl.fused ? pl.c_l1 : nullptr), pl.G1, pl.cap1, d_skew));
-        // (512 lists of one-word records: the rings leave room for one workgroup per CU -- 1024 threads then)
-#define TSX_LEVEL2(RWV, NTV, SK, BITS)                                                                                          \
-        hipLaunchKernelGGL((partition_ring_kernel<RWV, NTV, SK>), dim3(pl.nb1 * pl.cpr2), dim3(NTV), part_lds(pl.nb2, BITS), st,  \
-                           pp, (const uint64_t *)pl.buf1, (const unsigned long long *)pl.c_bstart,                              \
-                           (const unsigned long long *)pl.c_bcnt, (uint64_t)0, pl.nb1, pl.cpr2, m->d_buf[0].get(),                    \
-                           (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, pl.c_seg, pl.cap_sub,      \
-                           pl.nb2, (uint32_t)p.S, BITS, m->d_ovq.get(), m->d_ovq_cnt.get(), OVQ_CAP,                                         \
-                           (const unsigned long long *)(pl.fused ? pl.c_l1 : nullptr), pl.G1, pl.cap1, 0,                       \
-                           (unsigned long long *)nullptr, 0u, 0u, pre, dch, (const uint32_t *)d_skew)
-        if (part_lds(pl.nb2, bits) > ((size_t)80 << 10)) {
-            DISPATCH_RW(rw, TSX_LEVEL2(RWV, 1024, false, bits); TSX_LEVEL2(RWV, 1024, true, bits));
-        } else {
-            DISPATCH_RW(rw, TSX_LEVEL2(RWV, RING_NT, false, bits); TSX_LEVEL2(RWV, RING_NT, true, bits));
-        }
-#undef TSX_LEVEL2
+        RingLaunch r;
+        r.grid = pl.nb1 * pl.cpr2; r.rw = rw;
+        r.src = pl.buf1; r.src_start = pl.c_bstart; r.src_cnt = pl.c_bcnt; r.nregions = pl.nb1; r.cpr = pl.cpr2;
+        r.dst = m->d_buf[0].get(); r.dst_cnt = pl.c_seg; r.dst_cap = pl.cap_sub;
+        r.nb = pl.nb2; r.shift = (uint32_t)p.S; r.capbits = ring_bits(pl.nb2);
+        r.ovq_all = m->d_ovq.get(); r.ovq_cnt = m->d_ovq_cnt.get(); r.ovq_cap = OVQ_CAP;
+        r.src_pcnt = pl.fused ? pl.c_l1 : nullptr; r.src_np = pl.G1; r.src_pcap = pl.cap1;
+        r.fmt = pre; r.dch = dch; r.skew_flag = d_skew;
+        launch_ring(st, pp, r);
+        r.skew = true;
+        launch_ring(st, pp, r);
         HIP_TRY(hipGetLastError());
         lists = m->d_buf[0].get(); lists_start = nullptr; lists_cnt = pl.c_seg; lists_cap = pl.cap_sub; pieces = pl.cpr2;
     }
-    if (ev) HIP_TRY(hipEventRecord(ev[5].get(), st));
+    if (ev) HIP_TRY(hipEventRecord(ev[EV_L2_END].get(), st));
     const int fresh = m->fresh ? 1 : 0;
     const int gb = (int)std::min<uint32_t>(pl.nseg, (uint32_t)m->cus * 16);
     const size_t seg_bytes = ((size_t)8 << p.S) * p.W;
@@ -1099,7 +1202,7 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
     }
     HIP_TRY(hipGetLastError());
     m->fresh = false;   // every segment has been written: built, or zeroed
-    if (ev) HIP_TRY(hipEventRecord(ev[6].get(), st));
+    if (ev) HIP_TRY(hipEventRecord(ev[EV_BUILD_END].get(), st));
     // Records that found their sub-list filled up by a hot key, and the deferred list: inserted now, by the
     // whole chip, into a table whose segments are all in place.
     if (nq2) {
@@ -1148,7 +1251,8 @@ static int ensure_tiles(tsx_hip_map *m, uint64_t ntiles, hipStream_t st) {
     return TSX_HIP_OK;
 }
 
-// The next EV_N timing events of the map (created with timing on first use).
+// ---- stage timing: tuples of EV_N events (TimingEvent) on the launch stream ----------------------------------------------
+// The next tuple of the map (its events are created on first use).
 static int next_timing_events(tsx_hip_map *m, Event *&ev) {
     while (m->ev_used + EV_N > m->ev.size()) {
         m->ev.emplace_back();
@@ -1158,100 +1262,208 @@ static int next_timing_events(tsx_hip_map *m, Event *&ev) {
     ev = &m->ev[m->ev_used]; m->ev_used += EV_N;
     return TSX_HIP_OK;
 }
+// Events first .. last of a tuple, back to back.
+static int timing_record(Event *ev, int first, int last, hipStream_t st) {
+    for (int i = first; i <= last; ++i) HIP_TRY(hipEventRecord(ev[i].get(), st));
+    return TSX_HIP_OK;
+}
+// Opens a tuple and records its first event; ev stays null where timing is off, and every helper below takes that.
+static int timing_open(tsx_hip_map *m, Event *&ev, hipStream_t st) {
+    ev = nullptr;
+    if (!m->timing) return TSX_HIP_OK;
+    TSX_TRY(next_timing_events(m, ev));
+    return timing_record(ev, EV_BEGIN, EV_BEGIN, st);
+}
+// Nothing more of the tuple happens in this call: every event from `from` to the end.
+static int timing_close(Event *ev, int from, hipStream_t st) { return ev ? timing_record(ev, from, EV_END, st) : TSX_HIP_OK; }
+// The same, and the tuple is parked in ev_open: its partition phase runs in a later call, which records those events again.
+static int timing_close_parked(tsx_hip_map *m, Event *ev, int from, hipStream_t st) {
+    TSX_TRY(timing_close(ev, from, st));
+    if (ev) m->ev_open.push_back((long)(ev - m->ev.data()));
+    return TSX_HIP_OK;
+}
+// The oldest parked tuple, or null: timing off, none parked, or parked before the tuples were reset.
+static Event *timing_parked(tsx_hip_map *m) {
+    if (!m->timing || m->ev_open.empty() || (size_t)m->ev_open.front() + EV_N > m->ev_used) return nullptr;
+    return &m->ev[(size_t)m->ev_open.front()];
+}
+// ... taken off the list (a stale one is dropped as well).
+static Event *timing_take_parked(tsx_hip_map *m) {
+    Event *ev = timing_parked(m);
+    if (!m->ev_open.empty()) m->ev_open.pop_front();
+    return ev;
+}
 
-static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
-                           hipStream_t st, ShardOut sh = ShardOut(), HotOut hot = HotOut(), DescOut dsc = DescOut()) {
-    uint64_t *shard_send = sh.send;
-    const uint64_t shard_cap = sh.send_cap;
-    unsigned long long *shard_counts = sh.counts;
-    if (own_end == 0) return TSX_HIP_OK;
-    // (the counting entry points refuse these before they queue anything: prefilter_count_ok)
-    if (m->pf_armed && (shard_send || dsc.out || dsc.owners)) return TSX_HIP_EINVAL;
+// The first walk of a sharded step: what its tuple counts as level 1 starts here (the walks, up to the start of level 2).
+static int timing_walks_begin(tsx_hip_map *m, hipStream_t st) {
+    Event *ev = timing_parked(m);
+    if (ev) { TSX_TRY(timing_record(ev, EV_PART, EV_PART, st)); m->sh_ev3 = true; }
+    return TSX_HIP_OK;
+}
+
+// ---- one text piece on the device: line pass, then describe / count / scan -------------------------------------------------
+struct PieceText { const uint8_t *text; uint64_t n, own_end; int head_open; uint64_t ntiles; };
+
+// The line pass (tile line ends, then their exclusive scan from *d_carry) over the start positions [0, own_end) of
+// d_text (n readable bytes).
+static int line_pass(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open, hipStream_t st) {
     const uint64_t ntiles = (own_end + TILE - 1) / TILE;
     TSX_TRY(ensure_tiles(m, ntiles, st));
-    Event *ev = nullptr;
-    if (m->timing) {
-        TSX_TRY(next_timing_events(m, ev));
-        HIP_TRY(hipEventRecord(ev[0].get(), st));
-    }
     const int g1 = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8);
     hipLaunchKernelGGL(line_count_kernel, dim3(g1), dim3(NT), 0, st, d_text, n, own_end, head_open, m->d_tile.get(), ntiles);
-    {
-        const uint64_t nchunks = (ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
-        uint32_t *chunk = m->d_tile.get() + m->tile_cap;
-        hipLaunchKernelGGL(line_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st,
-                           (const uint32_t *)m->d_tile.get(), ntiles, chunk);
-        hipLaunchKernelGGL(line_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, m->d_carry.get());
-        hipLaunchKernelGGL(line_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, m->d_tile.get(), ntiles,
-                           (const uint32_t *)chunk);
-    }
-    if (ev) HIP_TRY(hipEventRecord(ev[1].get(), st));
-    if (dsc.out || dsc.owners) {
-        const int gdd = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8), gdr = gdd * (NT / 64);
-        const uint32_t du = dsc.long_desc ? 2u : 1u;   // 16-byte units per description (long: four strips in 32 bytes)
-        const uint64_t dcap = ((ntiles + gdd - 1) / gdd) * (dsc.long_desc ? 16 : 64);
-        TSX_TRY(grow(st, m->d_buf[1], (size_t)gdr * dcap * du * 16));
-        // region sizes | region offsets | total
-        TSX_TRY(grow(st, m->d_desc_cnt, ((size_t)2 * gdr + 16) * 8 + (size_t)MZ_MAX_RANKS * m->cus * MZ_WG_PER_CU * 4 + 64));
-        unsigned long long *d_cnt = m->d_desc_cnt.get(), *d_offs = d_cnt + gdr, *d_tot = d_offs + gdr;
-        if (dsc.owners) {   // homopolymers leave here already: counted in the four words behind the chunk counters
-            unsigned long long *d_hom = d_cnt + 2 * (size_t)gdr + 8 + ((size_t)MZ_MAX_RANKS * m->cus * MZ_WG_PER_CU + 1) / 2;
-            HIP_TRY(hipMemsetAsync(d_hom, 0, 32, st));
-            hipLaunchKernelGGL(strip_desc_kernel<true>, dim3(gdd), dim3(NT), 0, st, m->p, d_text, n, own_end, head_open,
-                               (const uint32_t *)m->d_tile.get(), ntiles, (uint4 *)m->d_buf[1].get(), dcap, d_cnt, dsc.sum, 0, d_hom);
-        } else
-        DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_kernel<false, BRV>), dim3(gdd), dim3(NT), 0, st, m->p, d_text, n, own_end,
-                           head_open, (const uint32_t *)m->d_tile.get(), ntiles, (uint4 *)m->d_buf[1].get(), dcap, d_cnt, dsc.sum,
-                           dsc.long_desc, (unsigned long long *)nullptr, m->qmap_cur));
-        if (dsc.owners) {   // owner = f(minimizer): the regions stay where they are, mini_split hands them out by owner
-            HIP_TRY(hipGetLastError());
-            m->mz_regions = (uint32_t)gdr; m->mz_dcap = dcap;
-            if (ev) {
-                for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i].get(), st));
-                m->ev_open.push_back((long)(ev - m->ev.data()));
-            }
-            return TSX_HIP_OK;
-        }
-        hipLaunchKernelGGL(desc_prefix_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long *)d_cnt, (uint32_t)gdr,
-                           d_offs, d_tot, dcap, (uint64_t)dsc.cap, m->p.stats);
-        hipLaunchKernelGGL(desc_pack_kernel, dim3(std::min(gdr, m->cus * 8)), dim3(256), 0, st, (const uint4 *)m->d_buf[1].get(), dcap,
-                           (const unsigned long long *)d_cnt, (const unsigned long long *)d_offs, (uint32_t)gdr, dsc.out,
-                           dsc.cap * du, du);
+    const uint64_t nchunks = (ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    uint32_t *chunk = m->d_tile.get() + m->tile_cap;
+    hipLaunchKernelGGL(line_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const uint32_t *)m->d_tile.get(),
+                       ntiles, chunk);
+    hipLaunchKernelGGL(line_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, m->d_carry.get());
+    hipLaunchKernelGGL(line_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, m->d_tile.get(), ntiles,
+                       (const uint32_t *)chunk);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// strip_desc_kernel without a homopolymer output: `grid` workgroups describe the piece, one region of desc_cap per wave.
+static void launch_strip_desc(tsx_hip_map *m, int grid, hipStream_t st, const TableParams &pp, const PieceText &t, uint4 *desc,
+                              uint64_t desc_cap, unsigned long long *desc_cnt, unsigned long long *kmer_sum, int long_desc) {
+    DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_kernel<false, BRV>), dim3(grid), dim3(NT), 0, st, pp, t.text, t.n, t.own_end,
+                                      t.head_open, (const uint32_t *)m->d_tile.get(), t.ntiles, desc, desc_cap, desc_cnt, kmer_sum,
+                                      long_desc, (unsigned long long *)nullptr, m->qmap_cur));
+}
+
+// The piece is only DESCRIBED: packed into dsc.out, or (dsc.owners) left region by region in buffer 1 for mini_split.
+// Whatever partitions and builds follows in other calls: the tuple is closed here and parked for them.
+static int describe_piece(tsx_hip_map *m, const PieceText &t, const DescOut &dsc, Event *ev, hipStream_t st) {
+    const uint64_t ntiles = t.ntiles;
+    const int gdd = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8), gdr = gdd * (NT / 64);
+    const uint32_t du = dsc.long_desc ? 2u : 1u;   // 16-byte units per description (long: four strips in 32 bytes)
+    const uint64_t dcap = ((ntiles + gdd - 1) / gdd) * (dsc.long_desc ? 16 : 64);
+    TSX_TRY(grow(st, m->d_buf[1], (size_t)gdr * dcap * du * 16));
+    // region sizes | region offsets | total
+    TSX_TRY(grow(st, m->d_desc_cnt, ((size_t)2 * gdr + 16) * 8 + (size_t)MZ_MAX_RANKS * m->cus * MZ_WG_PER_CU * 4 + 64));
+    unsigned long long *d_cnt = m->d_desc_cnt.get(), *d_offs = d_cnt + gdr, *d_tot = d_offs + gdr;
+    uint4 *regions = (uint4 *)m->d_buf[1].get();
+    if (dsc.owners) {   // owner = f(minimizer): the regions stay where they are, mini_split hands them out by owner
+        // homopolymers leave here already: counted in the four words behind the chunk counters
+        unsigned long long *d_hom = d_cnt + 2 * (size_t)gdr + 8 + ((size_t)MZ_MAX_RANKS * m->cus * MZ_WG_PER_CU + 1) / 2;
+        HIP_TRY(hipMemsetAsync(d_hom, 0, 32, st));
+        hipLaunchKernelGGL(strip_desc_kernel<true>, dim3(gdd), dim3(NT), 0, st, m->p, t.text, t.n, t.own_end, t.head_open,
+                           (const uint32_t *)m->d_tile.get(), ntiles, regions, dcap, d_cnt, dsc.sum, 0, d_hom);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(dsc.count, d_tot, 8, hipMemcpyDeviceToDevice, st));
-        if (ev) {   // the walks, level 2 and the build follow in other calls, which record 3..7 of the first window's tuple again
-            for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i].get(), st));
-            m->ev_open.push_back((long)(ev - m->ev.data()));
-        }
-        return TSX_HIP_OK;
+        m->mz_regions = (uint32_t)gdr; m->mz_dcap = dcap;
+        return timing_close_parked(m, ev, EV_SCAN_END, st);
     }
+    launch_strip_desc(m, gdd, st, m->p, t, regions, dcap, d_cnt, dsc.sum, dsc.long_desc);
+    hipLaunchKernelGGL(desc_prefix_kernel, dim3(1), dim3(1024), 0, st, (const unsigned long long *)d_cnt, (uint32_t)gdr,
+                       d_offs, d_tot, dcap, (uint64_t)dsc.cap, m->p.stats);
+    hipLaunchKernelGGL(desc_pack_kernel, dim3(std::min(gdr, m->cus * 8)), dim3(256), 0, st, (const uint4 *)regions, dcap,
+                       (const unsigned long long *)d_cnt, (const unsigned long long *)d_offs, (uint32_t)gdr, dsc.out,
+                       dsc.cap * du, du);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(dsc.count, d_tot, 8, hipMemcpyDeviceToDevice, st));
+    return timing_close_parked(m, ev, EV_SCAN_END, st);
+}
+
+// The atomic path: count_fastq_kernel inserts every k-mer where it finds it (an armed prefilter is consulted here alone).
+static int count_piece_atomic(tsx_hip_map *m, const PieceText &t, Event *ev, hipStream_t st) {
+    TSX_TRY(ensure_zeroed(m, st));
     const size_t lut_bytes = m->lut.size() * 8;
-    const int g3 = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 3);
-
-    // Which insert path?  The partitioned path rewrites every touched segment
-    // once (2 x table bytes at worst), the atomic path pays ~60 ps per k-mer.
-    const TableParams &p = m->p;
-    // (a table built slab by slab takes its partitioned path in count_slabs, over the whole text at once)
-    // An armed prefilter: the atomic path whatever the ratio of text to table (the partitioned walk does not consult B).
-    const bool use_part = !m->pf_armed && (shard_send || (can_partition(m) && !slab_bits(m) &&
-                                         (m->path == 2 || (m->path == 0 && own_end * 32 >= m->lay.table_bytes))));
-    if (!use_part) {
-        int rcz = ensure_zeroed(m, st);
-        if (rcz != TSX_HIP_OK) return rcz;
-        if (m->pf_armed) {
-            DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV, BRV, true>), dim3(g3), dim3(NT),
-                                                                lut_bytes, st, m->p, d_text, n, own_end, head_open,
-                                                                (const uint32_t *)m->d_tile.get(), ntiles, m->qmap_cur, m->pf_view()))));
-        } else {
-            DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV, BRV>), dim3(g3), dim3(NT),
-                                                                lut_bytes, st, m->p, d_text, n, own_end, head_open,
-                                                                (const uint32_t *)m->d_tile.get(), ntiles, m->qmap_cur))));
-        }
-        HIP_TRY(hipGetLastError());
-        if (ev) for (int i = 2; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i].get(), st));
-        return TSX_HIP_OK;
+    const int g3 = (int)std::min<uint64_t>(t.ntiles, (uint64_t)m->cus * 3);
+    if (m->pf_armed) {
+        DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV, BRV, true>), dim3(g3), dim3(NT),
+                                                            lut_bytes, st, m->p, t.text, t.n, t.own_end, t.head_open,
+                                                            (const uint32_t *)m->d_tile.get(), t.ntiles, m->qmap_cur, m->pf_view()))));
+    } else {
+        DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_fastq_kernel<WKV, CANV, BRV>), dim3(g3), dim3(NT),
+                                                            lut_bytes, st, m->p, t.text, t.n, t.own_end, t.head_open,
+                                                            (const uint32_t *)m->d_tile.get(), t.ntiles, m->qmap_cur))));
     }
+    HIP_TRY(hipGetLastError());
+    return timing_close(ev, EV_SCAN_END, st);
+}
 
+// The scan fused with radix level 1 (local runs, one-limb keys, two radix levels), in two kernels: strip descriptions
+// (16 B per strip with a k-mer start, one region per wave, in buffer 0 -- level 2 overwrites it later), then the walk with
+// every lane busy.  All keys stay on this GPU: a ring flush per quarter strip (flush_q = 1).
+static int scan_fused(tsx_hip_map *m, const PieceText &t, const PartPlan &pl, const TableParams &pp, int gd, hipStream_t st) {
+    const int gdreg = gd * (NT / 64);
+    const uint32_t nq2 = pl.nb1 * pl.cpr2;
+    TSX_TRY(ensure_ovq(m, (size_t)nq2 + pl.G1, pl.rw, st));
+    // (TSX_HIP_LOCAL_LONG=1: four strips per 32-byte description, as in the exchange of a sharded run)
+    const char *ll_env = getenv("TSX_HIP_LOCAL_LONG");
+    const int lng = ll_env ? (atoi(ll_env) != 0) : 0;
+    const uint64_t desc_cap = ((t.ntiles + gd - 1) / gd) * (lng ? 16 : 64);
+    TSX_TRY(grow(st, m->d_buf[0], (size_t)gdreg * desc_cap * (lng ? 32 : 16)));
+    launch_strip_desc(m, gd, st, pp, t, (uint4 *)m->d_buf[0].get(), desc_cap, pl.c_log, nullptr, lng);
+    HIP_TRY(hipGetLastError());
+    WalkPartLaunch w;
+    w.grid = pl.G1;
+    w.desc = (const uint4 *)m->d_buf[0].get(); w.desc_cap = desc_cap; w.desc_cnt = pl.c_log; w.nregions = (uint32_t)gdreg;
+    w.dst = pl.buf1; w.dst_cap = pl.cap1; w.dst_cnt = pl.c_l1;
+    w.nb = pl.nb1; w.shift = (uint32_t)(m->p.l - pl.b1);
+    w.ovq_all = m->d_ovq.get() + (size_t)nq2 * OVQ_CAP; w.ovq_cnt = m->d_ovq_cnt.get() + nq2; w.ovq_cap = OVQ_CAP;
+    w.dst_gtot = pl.G1; w.long_desc = lng; w.flush_q = 1u;
+    launch_walk_part(m, st, pp, w);
+    return TSX_HIP_OK;
+}
+
+// The key log form (sharded scans, one-level tables, multi-limb keys), in two kernels as well: descriptions into buffer 1
+// (level 1 fills it only afterwards; multi-limb: first k-mer + entering bases + validity), then the walk with every lane
+// busy into the wave's log region, with the histogram by level-1 bucket -- or by owner GPU for a sharded scan.
+static int scan_key_log(tsx_hip_map *m, const PieceText &t, PartPlan &pl, const TableParams &pp, int gs, int gd,
+                        uint32_t hist_nb, uint32_t hist_shift, hipStream_t st) {
+    const int wk = m->p.wk, gdreg = gd * (NT / 64);
+    const int du = (2 * wk + 2 + 3) / 4;   // 16-byte units per description (one-limb keys: 1)
+    const uint64_t desc_cap = ((t.ntiles + gd - 1) / gd) * 64;
+    TSX_TRY(grow(st, m->d_buf[1], (size_t)gdreg * desc_cap * du * 16));
+    pl.buf1 = m->d_buf[1].get();
+    TSX_TRY(grow(st, m->d_desc_cnt, (size_t)gdreg * 8));
+    uint4 *regions = (uint4 *)m->d_buf[1].get();
+#define TSX_DESC_WIDE(WKV)                                                                                                     \
+    DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_wide_kernel<WKV, BRV>), dim3(gd), dim3(NT), 0, st, pp, t.text, t.n, t.own_end, \
+                                      t.head_open, (const uint32_t *)m->d_tile.get(), t.ntiles, regions, desc_cap,            \
+                                      m->d_desc_cnt.get(), m->qmap_cur))
+    switch (wk) {
+        case 1:
+            launch_strip_desc(m, gd, st, pp, t, regions, desc_cap, m->d_desc_cnt.get(), nullptr, 0);
+            HIP_TRY(hipGetLastError());
+            break;
+        case 2: TSX_DESC_WIDE(2); break;
+        case 3: TSX_DESC_WIDE(3); break;
+        default: TSX_DESC_WIDE(4); break;
+    }
+#undef TSX_DESC_WIDE
+    WalkLogLaunch w;
+    w.grid = (uint32_t)gs;
+    w.desc = regions; w.desc_cap = desc_cap; w.desc_cnt = m->d_desc_cnt.get(); w.nregions = (uint32_t)gdreg;
+    w.log = m->d_buf[0].get(); w.log_cap = pl.log_cap; w.log_cnt = pl.c_log;
+    w.hist = pl.d_hist; w.hist_nb = hist_nb; w.hist_shift = hist_shift;
+    launch_walk_log(m, st, pp, w);
+    return TSX_HIP_OK;
+}
+
+// Sharded scan, level 0: every log region split by owner into the caller's send buffer (exact offsets).
+static int split_by_owner(tsx_hip_map *m, const PartPlan &pl, int greg, uint32_t nown, const ShardOut &sh, hipStream_t st) {
+    if ((uint64_t)greg * pl.log_cap > sh.send_cap || (sh.own && (uint64_t)greg * pl.log_cap > sh.own_cap)) return TSX_HIP_ERANGE;
+    hipLaunchKernelGGL(offsets_rows_kernel, dim3(nown), dim3(1024), 0, st, (const uint32_t *)pl.d_hist, pl.d_offs,
+                       (uint32_t)greg, pl.c_bcnt);
+    hipLaunchKernelGGL(offsets_finish_kernel, dim3(1), dim3(1024), 0, st, nown, pl.c_bstart, pl.c_bcnt);
+    hipLaunchKernelGGL(split_owner_kernel, dim3(std::min(greg, m->cus * 8)), dim3(PART_NT), 0, st,
+                       (const uint64_t *)m->d_buf[0].get(), (const unsigned long long *)pl.c_log, pl.log_cap,
+                       (uint32_t)greg, sh.send, (const unsigned long long *)pl.d_offs,
+                       (const unsigned long long *)pl.c_bstart, (const unsigned long long *)pl.c_bcnt, nown,
+                       (uint32_t)m->p.l, sh.own, m->p.shard, sh.key_sum);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(sh.counts, pl.c_bcnt, nown * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+    return TSX_HIP_OK;
+}
+
+// The partitioned path: scan into level-1 sub-lists or a key log, then level 1 / level 2 / build -- or, for a sharded scan
+// (sh.send), the split by owner: hot keys go to `hot`, and the partition phase follows in tsx_hip_shard_build_device.
+static int count_piece_partitioned(tsx_hip_map *m, const PieceText &t, const ShardOut &sh, const HotOut &hot, Event *ev,
+                                   hipStream_t st) {
+    const TableParams &p = m->p;
+    const uint64_t own_end = t.own_end, ntiles = t.ntiles;
+    const bool sharded = sh.send != nullptr;
     // FASTQ: the quality line is as long as the sequence, at most half of the bytes start a k-mer; FASTA: all may
     const uint64_t maxrec = (p.line_mask == 3 ? own_end / 2 : own_end) + 65536;
     const uint32_t nown = 1u << (p.lg - p.l);
@@ -1270,111 +1482,68 @@ static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, ui
     // strip_desc_kernel: 52 VGPRs, 2.4 KiB of LDS -- eight workgroups per CU (five: 3.9 ms for both kernels, eight: 3.7)
     const int desc_wgs = 8;
     const int gd = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * desc_wgs), gdreg = gd * (NT / 64);
-    const bool want_fuse = fuse && !shard_send && p.wk == 1;
+    const bool want_fuse = fuse && !sharded && p.wk == 1;
 
-    int rc = plan_partition(m, maxrec, (want_fuse && fuse == 2) ? std::max(greg, gdreg) : greg, true, shard_send ? nown : 0, st,
+    int rc = plan_partition(m, maxrec, (want_fuse && fuse == 2) ? std::max(greg, gdreg) : greg, true, sharded ? nown : 0, st,
                             pl, want_fuse ? g_sp : 0);
     if (rc == TSX_HIP_OK && want_fuse && !pl.fused)   // a one-level table: the key log form, planned for its own regions
         rc = plan_partition(m, maxrec, greg, true, 0, st, pl, 0);
     if (rc != TSX_HIP_OK) return rc;
     // what cannot take the fast route: the caller's hot list (sharded scan), else the map's deferred list
     TableParams pp = m->p;
-    if (shard_send) {
+    if (sharded) {
         pp.defer = DeferList{hot.keys, hot.cnts, hot.n, hot.cap};
     } else {
-        rc = ensure_deferred(m, maxrec, st);
-        if (rc != TSX_HIP_OK) return rc;
+        TSX_TRY(ensure_deferred(m, maxrec, st));
         HIP_TRY(hipMemsetAsync(m->d_def_n.get(), 0, 8, st));
         pp.defer = m->defer();
     }
-    // scan -> key log + histogram by level-1 bucket, or by owner GPU for a sharded scan
-    const uint32_t hist_nb = shard_send ? nown : pl.nb1, hist_shift = (uint32_t)(shard_send ? p.l : p.l - pl.b1);
-    if (pl.fused) {
-        const uint32_t nq2 = pl.nb1 * pl.cpr2;
-        rc = ensure_ovq(m, (size_t)nq2 + pl.G1, pl.rw, st);
-        if (rc != TSX_HIP_OK) return rc;
-        const size_t lds = (size_t)pl.nb1 * (((size_t)8 << SP_CAPBITS) + 8 + 8 + 4 + 4);   // ring, flush descriptor, tail|head, cursor, job
-        {
-            // two kernels: strip descriptions (16 B per strip with a k-mer start, one region per wave, in buffer 0 --
-            // level 2 overwrites it later), then the walk with every lane busy
-            // all keys stay on this GPU: a ring flush per quarter strip (flush_q = 1)
-            // (TSX_HIP_LOCAL_LONG=1: four strips per 32-byte description, as in the exchange of a sharded run)
-            const char *ll_env = getenv("TSX_HIP_LOCAL_LONG");
-            const int lng = ll_env ? (atoi(ll_env) != 0) : 0;
-            const uint64_t desc_cap = ((ntiles + gd - 1) / gd) * (lng ? 16 : 64);
-            TSX_TRY(grow(st, m->d_buf[0], (size_t)gdreg * desc_cap * (lng ? 32 : 16)));
-            DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_kernel<false, BRV>), dim3(gd), dim3(NT), 0, st, pp, d_text, n, own_end,
-                               head_open, (const uint32_t *)m->d_tile.get(), ntiles, (uint4 *)m->d_buf[0].get(), desc_cap, pl.c_log,
-                               (unsigned long long *)nullptr, lng, (unsigned long long *)nullptr, m->qmap_cur));
-            HIP_TRY(hipGetLastError());
-            launch_walk_part(m, pl.G1, lds, st, pp, (const uint4 *)m->d_buf[0].get(), desc_cap,
-                             (const unsigned long long *)pl.c_log, (uint32_t)gdreg, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
-                             (uint32_t)(p.l - pl.b1), m->d_ovq.get() + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt.get() + nq2, OVQ_CAP,
-                             (uint64_t)0, 0u, pl.G1, 0, (unsigned long long *)nullptr, lng, 1u);
-        }
-    } else if (p.wk == 1) {
-        // key log form (sharded scans, one-level tables), the scan in two kernels as well: descriptions into buffer 1
-        // (level 1 fills it only afterwards), then the walk with every lane busy into the wave's log region
-        const uint64_t desc_cap = ((ntiles + gd - 1) / gd) * 64;
-        TSX_TRY(grow(st, m->d_buf[1], (size_t)gdreg * desc_cap * 16));
-        pl.buf1 = m->d_buf[1].get();
-        TSX_TRY(grow(st, m->d_desc_cnt, (size_t)gdreg * 8));
-        DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_kernel<false, BRV>), dim3(gd), dim3(NT), 0, st, pp, d_text, n, own_end,
-                           head_open, (const uint32_t *)m->d_tile.get(), ntiles, (uint4 *)m->d_buf[1].get(), desc_cap, m->d_desc_cnt.get(),
-                           (unsigned long long *)nullptr, 0, (unsigned long long *)nullptr, m->qmap_cur));
-        HIP_TRY(hipGetLastError());
-        DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_kernel<CANV>), dim3(gs), dim3(NT), lut_bytes, st, pp,
-                           (const uint4 *)m->d_buf[1].get(), desc_cap,
-                           (const unsigned long long *)m->d_desc_cnt.get(), (uint32_t)gdreg, m->d_buf[0].get(), pl.log_cap,
-                           pl.c_log, pl.d_hist, hist_nb, hist_shift, (uint64_t)0, 0, 0, (unsigned long long *)nullptr));
-    } else {
-        // multi-limb keys, two kernels as well: descriptions (first k-mer + entering bases + validity) into buffer 1,
-        // then the walk with every lane busy
-        const int du = (2 * p.wk + 2 + 3) / 4;
-        const uint64_t desc_cap = ((ntiles + gd - 1) / gd) * 64;
-        TSX_TRY(grow(st, m->d_buf[1], (size_t)gdreg * desc_cap * du * 16));
-        pl.buf1 = m->d_buf[1].get();
-        TSX_TRY(grow(st, m->d_desc_cnt, (size_t)gdreg * 8));
-#define TSX_WIDE2(WKV)                                                                                                      \
-        DISPATCH_BR(m, hipLaunchKernelGGL((strip_desc_wide_kernel<WKV, BRV>), dim3(gd), dim3(NT), 0, st, pp, d_text, n,      \
-                           own_end, head_open, (const uint32_t *)m->d_tile.get(), ntiles, (uint4 *)m->d_buf[1].get(), desc_cap,         \
-                           m->d_desc_cnt.get(), m->qmap_cur));                                                                     \
-        DISPATCH_CANON(m, hipLaunchKernelGGL((walk_log_wide_kernel<WKV, CANV>), dim3(gs), dim3(NT), lut_bytes, st, pp,     \
-                           (const uint4 *)m->d_buf[1].get(),                                                                       \
-                           desc_cap, (const unsigned long long *)m->d_desc_cnt.get(), (uint32_t)gdreg, m->d_buf[0].get(),                \
-                           pl.log_cap, pl.c_log, pl.d_hist, hist_nb, hist_shift))
-        switch (p.wk) {
-            case 2: TSX_WIDE2(2); break;
-            case 3: TSX_WIDE2(3); break;
-            default: TSX_WIDE2(4); break;
-        }
-#undef TSX_WIDE2
-    }
+    if (pl.fused) { TSX_TRY(scan_fused(m, t, pl, pp, gd, st)); }
+    else { TSX_TRY(scan_key_log(m, t, pl, pp, gs, gd, sharded ? nown : pl.nb1, (uint32_t)(sharded ? p.l : p.l - pl.b1), st)); }
     HIP_TRY(hipGetLastError());
-    if (ev) { HIP_TRY(hipEventRecord(ev[2].get(), st)); HIP_TRY(hipEventRecord(ev[3].get(), st)); }
-    if (shard_send) {
-        // level 0: split every log region by owner into the caller's send buffer (exact offsets)
-        if ((uint64_t)greg * pl.log_cap > shard_cap || (sh.own && (uint64_t)greg * pl.log_cap > sh.own_cap))
-            return TSX_HIP_ERANGE;
-        hipLaunchKernelGGL(offsets_rows_kernel, dim3(nown), dim3(1024), 0, st, (const uint32_t *)pl.d_hist, pl.d_offs,
-                           (uint32_t)greg, pl.c_bcnt);
-        hipLaunchKernelGGL(offsets_finish_kernel, dim3(1), dim3(1024), 0, st, nown, pl.c_bstart, pl.c_bcnt);
-        hipLaunchKernelGGL(split_owner_kernel, dim3(std::min(greg, m->cus * 8)), dim3(PART_NT), 0, st,
-                           (const uint64_t *)m->d_buf[0].get(), (const unsigned long long *)pl.c_log, pl.log_cap,
-                           (uint32_t)greg, shard_send, (const unsigned long long *)pl.d_offs,
-                           (const unsigned long long *)pl.c_bstart, (const unsigned long long *)pl.c_bcnt, nown,
-                           (uint32_t)p.l, sh.own, p.shard, sh.key_sum);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(shard_counts, pl.c_bcnt, nown * sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
-    } else {
-        rc = run_partition_build(m, pl, m->d_buf[0].get(), nullptr, pl.log_cap, st, ev);
-        if (rc != TSX_HIP_OK) return rc;
+    if (ev) TSX_TRY(timing_record(ev, EV_SCAN_END, EV_PART, st));
+    if (sharded) {
+        TSX_TRY(split_by_owner(m, pl, greg, nown, sh, st));
+        return timing_close_parked(m, ev, EV_PART, st);   // (tsx_hip_shard_build_device records the partition phase again)
     }
-    if (ev && shard_send) {   // the partition phase follows in tsx_hip_shard_build_device, which records 3..6 again
-        for (int i = 3; i < EV_N; ++i) HIP_TRY(hipEventRecord(ev[i].get(), st));
-        m->ev_open.push_back((long)(ev - m->ev.data()));
-    }
-    if (ev && !shard_send) HIP_TRY(hipEventRecord(ev[7].get(), st));
+    TSX_TRY(run_partition_build(m, pl, m->d_buf[0].get(), nullptr, pl.log_cap, st, ev));
+    return timing_close(ev, EV_END, st);
+}
+
+// One FASTQ piece already on the device: the line pass, then one of the above.
+static int run_fastq_piece(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
+                           hipStream_t st, ShardOut sh = ShardOut(), HotOut hot = HotOut(), DescOut dsc = DescOut()) {
+    if (own_end == 0) return TSX_HIP_OK;
+    const bool describe = dsc.out || dsc.owners;
+    // (the counting entry points refuse these before they queue anything: prefilter_count_ok)
+    if (m->pf_armed && (sh.send || describe)) return TSX_HIP_EINVAL;
+    const PieceText t{d_text, n, own_end, head_open, (own_end + TILE - 1) / TILE};
+    TSX_TRY(ensure_tiles(m, t.ntiles, st));   // (before the tuple opens: its first event lies behind a reallocation)
+    Event *ev = nullptr;
+    TSX_TRY(timing_open(m, ev, st));
+    TSX_TRY(line_pass(m, d_text, n, own_end, head_open, st));
+    if (ev) TSX_TRY(timing_record(ev, EV_SCAN, EV_SCAN, st));
+    if (describe) return describe_piece(m, t, dsc, ev, st);
+    // Which insert path?  The partitioned path rewrites every touched segment once (2 x table bytes at worst), the atomic
+    // path pays ~60 ps per k-mer.  (A table built slab by slab takes its partitioned path in count_slabs, over the whole
+    // text at once.)  An armed prefilter: the atomic path whatever the ratio of text to table (the partitioned walk does
+    // not consult B).
+    const bool use_part = !m->pf_armed && (sh.send || (can_partition(m) && !slab_bits(m) &&
+                                         (m->path == 2 || (m->path == 0 && own_end * 32 >= m->lay.table_bytes))));
+    return use_part ? count_piece_partitioned(m, t, sh, hot, ev, st) : count_piece_atomic(m, t, ev, st);
+}
+
+// The common opening of the device entry points of the exchanges (tsx_hip_shard_* / tsx_hip_mini_*): canonical tables
+// and tables with a base rule are refused, the map counts as used, then the entry point's own argument tests
+// (`args_rc`: a callable that returns their code, run only on a map that exists), then the device and the stream.
+template <class ArgTests>
+static int exch_entry(tsx_hip_map *m, void *stream, hipStream_t &st, ArgTests args_rc) {
+    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
+    if (!m) return TSX_HIP_EINVAL;
+    m->used = true;
+    TSX_TRY(args_rc());
+    HIP_TRY(hipSetDevice(m->device));
+    st = pick_stream(m, stream);
     return TSX_HIP_OK;
 }
 
@@ -1383,15 +1552,14 @@ extern "C" int tsx_hip_shard_scan_window_device(tsx_hip_map *m, const void *dev_
                                                 size_t own_cap_keys, void *dev_send_counts, void *dev_hot_keys,
                                                 void *dev_hot_counts, size_t hot_cap, void *dev_hot_n,
                                                 void *dev_key_sum, void *stream) {
-    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
-    if (m) m->used = true;
-    if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_send || !dev_send_counts ||
-        !dev_hot_keys || !dev_hot_counts || !dev_hot_n || win_off > n_total || win_len > n_total - win_off)
-        return TSX_HIP_EINVAL;
-    if (m->p.wk != 1 || m->p.W != 1) return TSX_HIP_EINVAL;  // one-limb keys only (k <= 32)
-    if (win_len >= ((size_t)4 << 30)) return TSX_HIP_ERANGE;  // one window per call
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
+    hipStream_t st;
+    TSX_TRY(exch_entry(m, stream, st, [&]() -> int {
+        if ((!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_send || !dev_send_counts ||
+            !dev_hot_keys || !dev_hot_counts || !dev_hot_n || win_off > n_total || win_len > n_total - win_off)
+            return TSX_HIP_EINVAL;
+        if (m->p.wk != 1 || m->p.W != 1) return TSX_HIP_EINVAL;  // one-limb keys only (k <= 32)
+        return win_len >= ((size_t)4 << 30) ? TSX_HIP_ERANGE : TSX_HIP_OK;  // one window per call
+    }));
     if (win_off == 0) HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));   // line index restarts with the text
     HIP_TRY(hipMemsetAsync(dev_hot_n, 0, 8, st));
     HIP_TRY(hipMemsetAsync(dev_send_counts, 0, sizeof(unsigned long long) << (m->p.lg - m->p.l), st));
@@ -1479,33 +1647,23 @@ extern "C" int tsx_hip_shard_build_pieces_device(tsx_hip_map *m, const void *dev
     // region table: starts into c_rstart, sizes into c_log (plan_partition laid them out back to back: [c_log | c_rstart])
     HIP_TRY(hipMemcpyAsync(pl.c_rstart, m->h_regions.data(), (size_t)g * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(pl.c_log, m->h_regions.data() + g, (size_t)g * 8, hipMemcpyHostToDevice, st));
-    Event *ev = nullptr;
-    if (m->timing && !m->ev_open.empty() && (size_t)m->ev_open.front() + EV_N <= m->ev_used) {
-        ev = &m->ev[(size_t)m->ev_open.front()];
-        HIP_TRY(hipEventRecord(ev[3].get(), st));   // the histogram of the received keys counts as level 1
-    }
-    if (!m->ev_open.empty()) m->ev_open.pop_front();
+    Event *ev = timing_take_parked(m);
+    if (ev) TSX_TRY(timing_record(ev, EV_PART, EV_PART, st));   // the histogram of the received keys counts as level 1
     if (pl.fused) {
-        const uint32_t nq2 = pl.nb1 * pl.cpr2;
-        rc = ensure_ovq(m, (size_t)nq2 + pl.G1, pl.rw, st);
-        if (rc != TSX_HIP_OK) return rc;
+        TSX_TRY(ensure_ovq(m, (size_t)pl.nb1 * pl.cpr2 + pl.G1, pl.rw, st));
         TableParams pp = m->p;
         pp.defer = m->defer();
-        const uint32_t bits = 5;   // 32-word rings: 16 words may stay behind a flush, 8 arrive per batch on average
-        hipLaunchKernelGGL((partition_ring_kernel<1>), dim3(g), dim3(RING_NT), (size_t)pl.nb1 * (((size_t)8 << bits) + 36), st,
-                           pp, keys, (const unsigned long long *)pl.c_rstart, (const unsigned long long *)pl.c_log, (uint64_t)0,
-                           (uint32_t)g, 1u, pl.buf1, (const unsigned long long *)nullptr,
-                           (const unsigned long long *)nullptr, pl.c_l1, pl.cap1, pl.nb1, (uint32_t)(m->p.l - pl.b1), bits,
-                           m->d_ovq.get() + (size_t)nq2 * OVQ_CAP, m->d_ovq_cnt.get() + nq2, OVQ_CAP,
-                           (const unsigned long long *)nullptr, 0u, (uint64_t)0, 1, key_sum, 0u, (uint32_t)g, 0, 0u, (const uint32_t *)nullptr);
+        RingLaunch r = recv_level1(m, pl, (uint32_t)g, 0);
+        r.src = keys; r.src_start = pl.c_rstart; r.src_cnt = pl.c_log; r.nregions = (uint32_t)g;
+        r.key_sum = key_sum; r.dst_nr = (uint32_t)g;
+        launch_ring(st, pp, r);
     } else {
         hipLaunchKernelGGL(hist_kernel, dim3(g), dim3(PART_NT), 0, st, keys, (uint32_t)g, pl.nb1, (uint32_t)(m->p.l - pl.b1),
                            pl.d_hist, (const unsigned long long *)pl.c_rstart, (const unsigned long long *)pl.c_log, key_sum);
     }
     HIP_TRY(hipGetLastError());
-    rc = run_partition_build(m, pl, keys, pl.c_rstart, 0, st, ev);
-    if (rc == TSX_HIP_OK && ev) HIP_TRY(hipEventRecord(ev[7].get(), st));
-    return rc;
+    TSX_TRY(run_partition_build(m, pl, keys, pl.c_rstart, 0, st, ev));
+    return timing_close(ev, EV_END, st);
 }
 
 extern "C" int tsx_hip_shard_build_device(tsx_hip_map *m, const void *dev_keys, size_t n_keys, void *dev_key_sum,
@@ -1523,43 +1681,23 @@ extern "C" int tsx_hip_shard_build_device(tsx_hip_map *m, const void *dev_keys, 
 // windows is still running); only level 2 and the build wait for the last window.
 static int l1_supported(tsx_hip_map *m) {
     if (!m || !can_partition(m) || m->p.wk != 1 || m->p.W != 1) return 0;
-    const int nsegbits = m->p.l - m->p.S;
-    const int b1 = std::min(9, (nsegbits <= 8) ? nsegbits : (nsegbits + 1) / 2);
-    return nsegbits - b1 > 0 ? 1 : 0;
+    return radix_bits(m->p.l - m->p.S).b2 > 0 ? 1 : 0;
 }
 
 extern "C" int tsx_hip_shard_l1_supported(tsx_hip_map *m) { return exch_refused(m) ? 0 : l1_supported(m); }
 
 extern "C" int tsx_hip_shard_l1_window_device(tsx_hip_map *m, const void *dev_keys, size_t n_keys, uint32_t window,
                                               uint32_t nwindows, size_t est_total_keys, void *dev_key_sum, void *stream) {
-    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
-    if (m) m->used = true;
-    if (!m || (!dev_keys && n_keys) || ((uintptr_t)dev_keys & 7) || nwindows == 0 || window >= nwindows) return TSX_HIP_EINVAL;
-    if (!l1_supported(m)) return TSX_HIP_EINVAL;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
-    if (!m->sh_pl) m->sh_pl.reset(new PartPlan());
+    hipStream_t st;
+    TSX_TRY(exch_entry(m, stream, st, [&]() -> int {
+        if ((!dev_keys && n_keys) || ((uintptr_t)dev_keys & 7) || nwindows == 0 || window >= nwindows) return TSX_HIP_EINVAL;
+        return l1_supported(m) ? TSX_HIP_OK : TSX_HIP_EINVAL;
+    }));
+    // one workgroup per region, two workgroups per CU: every window's launch fills the chip once
+    const uint32_t rw0 = (uint32_t)std::min<uint64_t>((uint64_t)m->cus * 2, (uint64_t)PART_MAX_PIECES * level2_cpr(m) / nwindows);
+    TSX_TRY(sharded_l1_step(m, window == 0, rw0, nwindows, nwindows, std::max<uint64_t>(est_total_keys, n_keys) + 65536, st));
     PartPlan &pl = *m->sh_pl;
-    if (window == 0) {
-        // one workgroup per region, two workgroups per CU: every window's launch fills the chip once
-        m->sh_rw = (uint32_t)std::min<uint64_t>((uint64_t)m->cus * 2, (uint64_t)PART_MAX_PIECES * level2_cpr(m) / nwindows);
-        m->sh_windows = nwindows;
-        const int g1 = (int)(m->sh_rw * nwindows);
-        const uint64_t maxrec = std::max<uint64_t>(est_total_keys, n_keys) + 65536;
-        int rc = plan_sharded_l1(m, maxrec, g1, st, pl);
-        if (rc != TSX_HIP_OK) return rc;
-        if (!pl.fused) return TSX_HIP_EINVAL;
-        rc = ensure_deferred(m, maxrec, st);
-        if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_def_n.get(), 0, 8, st));
-        const uint32_t nq2 = pl.nb1 * pl.cpr2;
-        rc = ensure_ovq(m, (size_t)nq2 + pl.G1, pl.rw, st);
-        if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_ovq_cnt.get(), 0, ((size_t)nq2 + pl.G1) * 4, st));   // queues of windows that never run
-        m->h_regions.assign((size_t)2 * g1, 0);
-    } else if (m->sh_windows != nwindows || !pl.fused) {
-        return TSX_HIP_EINVAL;
-    }
+    if (window == 0) m->h_regions.assign((size_t)2 * pl.G1, 0);
     if (n_keys == 0) return TSX_HIP_OK;
     // the window's keys in sh_rw equal runs
     const uint32_t rw = m->sh_rw, g1 = pl.G1;
@@ -1575,14 +1713,10 @@ extern "C" int tsx_hip_shard_l1_window_device(tsx_hip_map *m, const void *dev_ke
     HIP_TRY(hipMemcpyAsync(dc, hc, (size_t)rw * 8, hipMemcpyHostToDevice, st));
     TableParams pp = m->p;
     pp.defer = m->defer();
-    const uint32_t nq2 = pl.nb1 * pl.cpr2, bits = 5;
-    hipLaunchKernelGGL((partition_ring_kernel<1>), dim3(rw), dim3(RING_NT), (size_t)pl.nb1 * (((size_t)8 << bits) + 36), st, pp,
-                       (const uint64_t *)dev_keys, (const unsigned long long *)ds, (const unsigned long long *)dc, (uint64_t)0, rw,
-                       1u, pl.buf1, (const unsigned long long *)nullptr, (const unsigned long long *)nullptr, pl.c_l1,
-                       pl.cap1, pl.nb1, (uint32_t)(m->p.l - pl.b1), bits,
-                       m->d_ovq.get() + ((size_t)nq2 + (size_t)window * rw) * OVQ_CAP, m->d_ovq_cnt.get() + nq2 + (size_t)window * rw, OVQ_CAP,
-                       (const unsigned long long *)nullptr, 0u, (uint64_t)0, 1, (unsigned long long *)dev_key_sum,
-                       window * rw, g1, 0, 0u, (const uint32_t *)nullptr);
+    RingLaunch r = recv_level1(m, pl, rw, window * rw);
+    r.src = (const uint64_t *)dev_keys; r.src_start = ds; r.src_cnt = dc; r.nregions = rw;
+    r.key_sum = (unsigned long long *)dev_key_sum; r.dst_r0 = window * rw; r.dst_nr = g1;
+    launch_ring(st, pp, r);
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
@@ -1603,16 +1737,15 @@ extern "C" int tsx_hip_shard_desc_capacity(tsx_hip_map *m, size_t text_bytes, in
 extern "C" int tsx_hip_shard_desc_window_device(tsx_hip_map *m, const void *dev_text, size_t n_total, size_t win_off,
                                                 size_t win_len, int long_desc, void *dev_desc, size_t desc_cap,
                                                 void *dev_count, void *dev_kmer_sum, void *stream) {
-    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
-    if (m) m->used = true;
-    if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_desc || ((uintptr_t)dev_desc & 15) ||
-        !dev_count || win_off > n_total || win_len > n_total - win_off)
-        return TSX_HIP_EINVAL;
-    if (!l1_supported(m)) return TSX_HIP_EINVAL;
-    if (win_len >= ((size_t)4 << 30)) return TSX_HIP_ERANGE;
-    if (desc_cap < win_len / (long_desc ? 64 : 16) + 1) return TSX_HIP_ERANGE;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
+    hipStream_t st;
+    TSX_TRY(exch_entry(m, stream, st, [&]() -> int {
+        if ((!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_desc || ((uintptr_t)dev_desc & 15) ||
+            !dev_count || win_off > n_total || win_len > n_total - win_off)
+            return TSX_HIP_EINVAL;
+        if (!l1_supported(m)) return TSX_HIP_EINVAL;
+        if (win_len >= ((size_t)4 << 30)) return TSX_HIP_ERANGE;
+        return desc_cap < win_len / (long_desc ? 64 : 16) + 1 ? TSX_HIP_ERANGE : TSX_HIP_OK;
+    }));
     if (win_off == 0) HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, 64, st));
     HIP_TRY(hipMemsetAsync(dev_count, 0, 8, st));
     if (win_len == 0) return TSX_HIP_OK;
@@ -1685,44 +1818,43 @@ static int mini_describe(tsx_hip_map *m, const void *dev_text, size_t n_total, s
 
 extern "C" int tsx_hip_mini_describe_device(tsx_hip_map *m, const void *dev_text, size_t n_total, size_t off, size_t len,
                                             void *dev_kmer_sum, void *stream) {
-    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
-    if (m) m->used = true;
-    if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (off & 15) || off > n_total || len > n_total - off)
-        return TSX_HIP_EINVAL;
-    if (!tsx_hip_mini_supported(m)) return TSX_HIP_EINVAL;
-    if (len >= ((size_t)4 << 30)) return TSX_HIP_ERANGE;
-    HIP_TRY(hipSetDevice(m->device));
-    return mini_describe(m, dev_text, n_total, off, len, dev_kmer_sum, pick_stream(m, stream));
+    hipStream_t st;
+    TSX_TRY(exch_entry(m, stream, st, [&]() -> int {
+        if ((!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (off & 15) || off > n_total || len > n_total - off)
+            return TSX_HIP_EINVAL;
+        if (!tsx_hip_mini_supported(m)) return TSX_HIP_EINVAL;
+        return len >= ((size_t)4 << 30) ? TSX_HIP_ERANGE : TSX_HIP_OK;
+    }));
+    return mini_describe(m, dev_text, n_total, off, len, dev_kmer_sum, st);
 }
 
 extern "C" int tsx_hip_mini_split_device(tsx_hip_map *m, uint32_t part, uint32_t nparts, int nranks, void *dev_desc,
                                          size_t cap_per_owner, void *dev_counts, void *stream) {
-    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
-    if (m) m->used = true;
-    if (!m || nparts == 0 || part >= nparts || !dev_desc || ((uintptr_t)dev_desc & 15) || !dev_counts || nranks < 1 ||
-        nranks > MZ_MAX_RANKS)
-        return TSX_HIP_EINVAL;
-    if (!tsx_hip_mini_supported(m)) return TSX_HIP_EINVAL;
-    if (m->mz_regions && cap_per_owner < mini_part_cap(m, m->mz_len, nparts)) return TSX_HIP_ERANGE;
-    HIP_TRY(hipSetDevice(m->device));
-    return mini_split(m, part, nparts, nranks, dev_desc, cap_per_owner, dev_counts, pick_stream(m, stream));
+    hipStream_t st;
+    TSX_TRY(exch_entry(m, stream, st, [&]() -> int {
+        if (nparts == 0 || part >= nparts || !dev_desc || ((uintptr_t)dev_desc & 15) || !dev_counts || nranks < 1 ||
+            nranks > MZ_MAX_RANKS)
+            return TSX_HIP_EINVAL;
+        if (!tsx_hip_mini_supported(m)) return TSX_HIP_EINVAL;
+        return (m->mz_regions && cap_per_owner < mini_part_cap(m, m->mz_len, nparts)) ? TSX_HIP_ERANGE : TSX_HIP_OK;
+    }));
+    return mini_split(m, part, nparts, nranks, dev_desc, cap_per_owner, dev_counts, st);
 }
 
 extern "C" int tsx_hip_mini_window_device(tsx_hip_map *m, const void *dev_text, size_t n_total, size_t win_off, size_t win_len,
                                           int nranks, void *dev_desc, size_t cap_per_owner, void *dev_counts,
                                           void *dev_kmer_sum, void *stream) {
-    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
-    if (m) m->used = true;
-    if (!m || (!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_desc || ((uintptr_t)dev_desc & 15) ||
-        !dev_counts || win_off > n_total || win_len > n_total - win_off || nranks < 1 || nranks > MZ_MAX_RANKS)
-        return TSX_HIP_EINVAL;
-    if (!tsx_hip_mini_supported(m)) return TSX_HIP_EINVAL;
-    if (win_len >= ((size_t)4 << 30)) return TSX_HIP_ERANGE;
-    size_t need = 0;
-    tsx_hip_mini_capacity(m, win_len, nranks, &need);
-    if (cap_per_owner < need) return TSX_HIP_ERANGE;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
+    hipStream_t st;
+    TSX_TRY(exch_entry(m, stream, st, [&]() -> int {
+        if ((!dev_text && n_total) || ((uintptr_t)dev_text & 15) || (win_off & 15) || !dev_desc || ((uintptr_t)dev_desc & 15) ||
+            !dev_counts || win_off > n_total || win_len > n_total - win_off || nranks < 1 || nranks > MZ_MAX_RANKS)
+            return TSX_HIP_EINVAL;
+        if (!tsx_hip_mini_supported(m)) return TSX_HIP_EINVAL;
+        if (win_len >= ((size_t)4 << 30)) return TSX_HIP_ERANGE;
+        size_t need = 0;
+        tsx_hip_mini_capacity(m, win_len, nranks, &need);
+        return cap_per_owner < need ? TSX_HIP_ERANGE : TSX_HIP_OK;
+    }));
     int rc = mini_describe(m, dev_text, n_total, win_off, win_len, dev_kmer_sum, st);
     if (rc != TSX_HIP_OK) return rc;
     return mini_split(m, 0, 1, nranks, dev_desc, cap_per_owner, dev_counts, st);
@@ -1744,8 +1876,6 @@ static int shard_walk(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int l
     if (!l1_supported(m)) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
-    if (!m->sh_pl) m->sh_pl.reset(new PartPlan());
-    PartPlan &pl = *m->sh_pl;
     // long_desc & 2: what the minimizer exchange sent to a map with shard_bits = 0 -- every key stays, homopolymers were
     // taken out by the sender, about half of a description's 16 positions are valid (a flush every second quarter), and
     // the windows of a step APPEND to one set of level-1 sub-lists (level 2 then reads as many pieces as on one GPU)
@@ -1754,33 +1884,12 @@ static int shard_walk(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int l
     if (mini && m->p.lg != m->p.l) return TSX_HIP_EINVAL;
     const uint32_t caller_slots = nslots, caller_slot = slot;
     if (mini) { nslots = 1; slot = 0; }
-    if (caller_slot == 0) {
-        // lists per slot: two workgroups per CU while the pieces of a bucket stay within what a level-2 workgroup walks
-        uint32_t gw = (uint32_t)m->cus * 2;
-        while (gw > 32 && (uint64_t)gw * nslots > (uint64_t)PART_MAX_PIECES * level2_cpr(m)) gw /= 2;
-        m->sh_rw = gw;
-        m->sh_windows = caller_slots;
-        const int g1 = (int)(gw * nslots);
-        const uint64_t maxrec = est_total_keys + 65536;
-        int rc = plan_sharded_l1(m, maxrec, g1, st, pl);
-        if (rc != TSX_HIP_OK) return rc;
-        if (!pl.fused) return TSX_HIP_EINVAL;
-        rc = ensure_deferred(m, maxrec, st);
-        if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_def_n.get(), 0, 8, st));
-        const uint32_t nq2 = pl.nb1 * pl.cpr2;
-        rc = ensure_ovq(m, (size_t)nq2 + pl.G1, pl.rw, st);
-        if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_ovq_cnt.get(), 0, ((size_t)nq2 + pl.G1) * 4, st));
-    } else if (m->sh_windows != caller_slots || !pl.fused) {
-        return TSX_HIP_EINVAL;
-    }
-    if (caller_slot == 0 && m->timing && !m->ev_open.empty() && (size_t)m->ev_open.front() + EV_N <= m->ev_used) {
-        HIP_TRY(hipEventRecord(m->ev[(size_t)m->ev_open.front() + 3].get(), st));   // "level 1" = the walks, up to the start of level 2
-        m->sh_ev3 = true;
-    }
+    const bool first = caller_slot == 0;
+    TSX_TRY(sharded_l1_step(m, first, first ? shard_lists_per_slot(m, nslots) : 0, nslots, caller_slots, est_total_keys + 65536, st));
+    const PartPlan &pl = *m->sh_pl;
+    if (first) TSX_TRY(timing_walks_begin(m, st));
     if (n_desc == 0) return TSX_HIP_OK;
-    const uint32_t gw = m->sh_rw, nq2 = pl.nb1 * pl.cpr2;
+    const uint32_t gw = m->sh_rw;
     const uint64_t chunk = (n_desc + gw - 1) / gw;   // descriptions per workgroup
     // this GPU keeps one key in 2^shard_bits: a ring flush every 1, 2 or 4 quarter strips (walk_part_kernel); every 2
     // in the minimizer exchange
@@ -1789,13 +1898,17 @@ static int shard_walk(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int l
     const int own_mode = mini ? (2 | (caller_slot > 0 ? 4 : 0)) : 1;
     TableParams pp = m->p;
     pp.defer = m->defer();
-    const size_t lds = (size_t)pl.nb1 * (((size_t)8 << SP_CAPBITS) + 8 + 8 + 4 + 4);
     // (a canonical map gets here only from count_slabs: the exchanges refuse it)
-    launch_walk_part(m, gw, lds, st, pp, (const uint4 *)dev_desc, chunk,
-                     (const unsigned long long *)nullptr, gw, pl.buf1, pl.cap1, pl.c_l1, pl.nb1,
-                     (uint32_t)(m->p.l - pl.b1), m->d_ovq.get() + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP,
-                     m->d_ovq_cnt.get() + nq2 + (size_t)slot * gw, OVQ_CAP, (uint64_t)n_desc, slot * gw, pl.G1, own_mode,
-                     (unsigned long long *)dev_emit_sum, long_desc ? 1 : 0, flush_q);
+    WalkPartLaunch w;
+    w.grid = gw;
+    w.desc = (const uint4 *)dev_desc; w.desc_cap = chunk; w.nregions = gw;
+    w.dst = pl.buf1; w.dst_cap = pl.cap1; w.dst_cnt = pl.c_l1;
+    w.nb = pl.nb1; w.shift = (uint32_t)(m->p.l - pl.b1);
+    const size_t q0 = (size_t)pl.nb1 * pl.cpr2 + (size_t)slot * gw;   // the slot's overflow queues, behind level 2's
+    w.ovq_all = m->d_ovq.get() + q0 * OVQ_CAP; w.ovq_cnt = m->d_ovq_cnt.get() + q0; w.ovq_cap = OVQ_CAP;
+    w.n_packed = (uint64_t)n_desc; w.dst_g0 = slot * gw; w.dst_gtot = pl.G1; w.own_flags = own_mode;
+    w.emit_sum = (unsigned long long *)dev_emit_sum; w.long_desc = long_desc ? 1 : 0; w.flush_q = flush_q;
+    launch_walk_part(m, st, pp, w);
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
@@ -1813,38 +1926,15 @@ extern "C" int tsx_hip_shard_walk_device(tsx_hip_map *m, const void *dev_desc, s
 // reads the wave logs as pieces (512 workgroups, each streaming ten of them) into list set `slot` of `nslots`.
 extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc, size_t n_desc, int long_desc, uint32_t slot,
                                            uint32_t nslots, size_t est_total_keys, void *dev_emit_sum, void *stream) {
-    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
-    if (m) m->used = true;
-    if (!m || (!dev_desc && n_desc) || ((uintptr_t)dev_desc & 15) || nslots == 0 || slot >= nslots) return TSX_HIP_EINVAL;
-    if (!l1_supported(m)) return TSX_HIP_EINVAL;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
-    if (!m->sh_pl) m->sh_pl.reset(new PartPlan());
-    PartPlan &pl = *m->sh_pl;
-    if (slot == 0) {
-        uint32_t gw = (uint32_t)m->cus * 2;
-        while (gw > 32 && (uint64_t)gw * nslots > (uint64_t)PART_MAX_PIECES * level2_cpr(m)) gw /= 2;
-        m->sh_rw = gw;
-        m->sh_windows = nslots;
-        const int g1 = (int)(gw * nslots);
-        const uint64_t maxrec = est_total_keys + 65536;
-        int rc = plan_sharded_l1(m, maxrec, g1, st, pl);
-        if (rc != TSX_HIP_OK) return rc;
-        if (!pl.fused) return TSX_HIP_EINVAL;
-        rc = ensure_deferred(m, maxrec, st);
-        if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_def_n.get(), 0, 8, st));
-        const uint32_t nq2 = pl.nb1 * pl.cpr2;
-        rc = ensure_ovq(m, (size_t)nq2 + pl.G1, pl.rw, st);
-        if (rc != TSX_HIP_OK) return rc;
-        HIP_TRY(hipMemsetAsync(m->d_ovq_cnt.get(), 0, ((size_t)nq2 + pl.G1) * 4, st));
-    } else if (m->sh_windows != nslots || !pl.fused) {
-        return TSX_HIP_EINVAL;
-    }
-    if (slot == 0 && m->timing && !m->ev_open.empty() && (size_t)m->ev_open.front() + EV_N <= m->ev_used) {
-        HIP_TRY(hipEventRecord(m->ev[(size_t)m->ev_open.front() + 3].get(), st));
-        m->sh_ev3 = true;
-    }
+    hipStream_t st;
+    TSX_TRY(exch_entry(m, stream, st, [&]() -> int {
+        if ((!dev_desc && n_desc) || ((uintptr_t)dev_desc & 15) || nslots == 0 || slot >= nslots) return TSX_HIP_EINVAL;
+        return l1_supported(m) ? TSX_HIP_OK : TSX_HIP_EINVAL;
+    }));
+    const bool first = slot == 0;
+    TSX_TRY(sharded_l1_step(m, first, first ? shard_lists_per_slot(m, nslots) : 0, nslots, nslots, est_total_keys + 65536, st));
+    const PartPlan &pl = *m->sh_pl;
+    if (first) TSX_TRY(timing_walks_begin(m, st));
     if (n_desc == 0) return TSX_HIP_OK;
     // the wave logs of this slot: the map's own scratch (buffer 0), planned for what this slot may keep
     const int gs = (int)m->cus * SCAN_WG_PER_CU, greg = gs * (NT / 64);
@@ -1855,40 +1945,34 @@ extern "C" int tsx_hip_shard_filter_device(tsx_hip_map *m, const void *dev_desc,
     TableParams pp = m->p;
     pp.defer = m->defer();
     const uint64_t chunk = (n_desc + greg - 1) / greg;   // descriptions per wave
-    hipLaunchKernelGGL(walk_log_kernel<false>, dim3(gs), dim3(NT), m->lut.size() * 8, st, pp, (const uint4 *)dev_desc, chunk,
-                       (const unsigned long long *)nullptr, (uint32_t)greg, m->d_buf[0].get(), lp.log_cap, lp.c_log, lp.d_hist,
-                       lp.nb1, (uint32_t)(m->p.l - lp.b1), (uint64_t)n_desc, long_desc ? 1 : 0, 1,
-                       (unsigned long long *)dev_emit_sum);
+    WalkLogLaunch w;
+    w.grid = (uint32_t)gs;
+    w.desc = (const uint4 *)dev_desc; w.desc_cap = chunk; w.nregions = (uint32_t)greg;
+    w.log = m->d_buf[0].get(); w.log_cap = lp.log_cap; w.log_cnt = lp.c_log;
+    w.hist = lp.d_hist; w.hist_nb = lp.nb1; w.hist_shift = (uint32_t)(m->p.l - lp.b1);
+    w.n_packed = (uint64_t)n_desc; w.long_desc = long_desc ? 1 : 0; w.own_only = 1; w.emit_sum = (unsigned long long *)dev_emit_sum;
+    launch_walk_log(m, st, pp, w);
     HIP_TRY(hipGetLastError());
-    const uint32_t gw = m->sh_rw, nq2 = pl.nb1 * pl.cpr2, bits = 5;
-    hipLaunchKernelGGL((partition_ring_kernel<1>), dim3(gw), dim3(RING_NT), (size_t)pl.nb1 * (((size_t)8 << bits) + 36), st, pp,
-                       (const uint64_t *)m->d_buf[0].get(), (const unsigned long long *)nullptr, (const unsigned long long *)nullptr,
-                       (uint64_t)0, 1u, gw, pl.buf1, (const unsigned long long *)nullptr, (const unsigned long long *)nullptr,
-                       pl.c_l1, pl.cap1, pl.nb1, (uint32_t)(m->p.l - pl.b1), bits,
-                       m->d_ovq.get() + ((size_t)nq2 + (size_t)slot * gw) * OVQ_CAP, m->d_ovq_cnt.get() + nq2 + (size_t)slot * gw, OVQ_CAP,
-                       (const unsigned long long *)lp.c_log, (uint32_t)greg, lp.log_cap, 1, (unsigned long long *)nullptr, slot,
-                       nslots, 0, 0u, (const uint32_t *)nullptr);
+    // level 1 reads the wave logs as pieces of ONE region, its gw workgroups sharing them out (cpr), into list set `slot`
+    const uint32_t gw = m->sh_rw;
+    RingLaunch r = recv_level1(m, pl, gw, slot * gw);
+    r.src = m->d_buf[0].get(); r.nregions = 1; r.cpr = gw;
+    r.src_pcnt = lp.c_log; r.src_np = (uint32_t)greg; r.src_pcap = lp.log_cap;
+    r.dst_r0 = slot; r.dst_nr = nslots;
+    launch_ring(st, pp, r);
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
 
 // level 2 + build over the sub-lists the windows' level-1 launches have filled
 extern "C" int tsx_hip_shard_build_l1_device(tsx_hip_map *m, void *stream) {
-    if (exch_refused(m)) return TSX_HIP_EINVAL;   // canonical / base rule: single-table and merge paths only
-    if (m) m->used = true;
-    if (!m || !m->sh_pl || !m->sh_pl->fused) return TSX_HIP_EINVAL;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
-    Event *ev = nullptr;
-    if (m->timing && !m->ev_open.empty() && (size_t)m->ev_open.front() + EV_N <= m->ev_used) {
-        ev = &m->ev[(size_t)m->ev_open.front()];
-        if (!m->sh_ev3) HIP_TRY(hipEventRecord(ev[3].get(), st));
-    }
+    hipStream_t st;
+    TSX_TRY(exch_entry(m, stream, st, [&]() -> int { return (!m->sh_pl || !m->sh_pl->fused) ? TSX_HIP_EINVAL : TSX_HIP_OK; }));
+    Event *ev = timing_take_parked(m);
+    if (ev && !m->sh_ev3) TSX_TRY(timing_record(ev, EV_PART, EV_PART, st));   // (else the first walk of the step has)
     m->sh_ev3 = false;
-    if (!m->ev_open.empty()) m->ev_open.pop_front();
-    int rc = run_partition_build(m, *m->sh_pl, nullptr, nullptr, 0, st, ev);
-    if (rc == TSX_HIP_OK && ev) HIP_TRY(hipEventRecord(ev[7].get(), st));
-    return rc;
+    TSX_TRY(run_partition_build(m, *m->sh_pl, nullptr, nullptr, 0, st, ev));
+    return timing_close(ev, EV_END, st);
 }
 
 extern "C" int tsx_hip_add_hashed_device(tsx_hip_map *m, const void *dev_keys, const void *dev_counts, size_t n,
@@ -1943,12 +2027,14 @@ extern "C" int tsx_hip_get_stage_timing(tsx_hip_map *m, double *stage_ms, uint64
     HIP_TRY(hipSetDevice(m->device));
     double acc[7] = {0, 0, 0, 0, 0, 0, 0};
     // line, scan, level 1, level 2, build kernel, gap, inserts after the build (overflow queues + deferred list)
-    static const int from[7] = {0, 1, 3, 4, 5, 2, 6}, to[7] = {1, 2, 4, 5, 6, 3, 7};
+    static const struct { TimingEvent from, to; } stage[7] = {
+        {EV_BEGIN, EV_SCAN},         {EV_SCAN, EV_SCAN_END}, {EV_PART, EV_L1_END},    {EV_L1_END, EV_L2_END},
+        {EV_L2_END, EV_BUILD_END}, {EV_SCAN_END, EV_PART}, {EV_BUILD_END, EV_END}};
     for (size_t i = 0; i + EV_N <= m->ev_used; i += EV_N) {
-        HIP_TRY(hipEventSynchronize(m->ev[i + 7].get()));
+        HIP_TRY(hipEventSynchronize(m->ev[i + EV_END].get()));
         for (int sgm = 0; sgm < 7; ++sgm) {
             float t = 0;
-            HIP_TRY(hipEventElapsedTime(&t, m->ev[i + from[sgm]].get(), m->ev[i + to[sgm]].get()));
+            HIP_TRY(hipEventElapsedTime(&t, m->ev[i + stage[sgm].from].get(), m->ev[i + stage[sgm].to].get()));
             acc[sgm] += t;
         }
     }
@@ -2212,23 +2298,6 @@ extern "C" int tsx_hip_inflate_bgzf_host(int device, const void *gz, size_t n, v
 }
 
 // ---- pieces cut at record boundaries, and the base rule's low-quality bitmap over them (tsx_baserule.h) -------------------
-// The line passes of run_fastq_piece (tile line ends, then their exclusive scan from *d_carry) over [0, own_end).
-static int query_line_pass(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open, hipStream_t st) {
-    const uint64_t ntiles = (own_end + TILE - 1) / TILE;
-    TSX_TRY(ensure_tiles(m, ntiles, st));
-    const int g1 = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8);
-    hipLaunchKernelGGL(line_count_kernel, dim3(g1), dim3(NT), 0, st, d_text, n, own_end, head_open, m->d_tile.get(), ntiles);
-    const uint64_t nchunks = (ntiles + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    uint32_t *chunk = m->d_tile.get() + m->tile_cap;
-    hipLaunchKernelGGL(line_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const uint32_t *)m->d_tile.get(),
-                       ntiles, chunk);
-    hipLaunchKernelGGL(line_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, m->d_carry.get());
-    hipLaunchKernelGGL(line_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, m->d_tile.get(), ntiles,
-                       (const uint32_t *)chunk);
-    HIP_TRY(hipGetLastError());
-    return TSX_HIP_OK;
-}
-
 // min_qual_char reads the 4th line of a FASTQ record: FASTA tables refuse it.
 static int base_rule_ok(const tsx_hip_map *m) {
     if (m->minq && m->p.line_mask != 3) {
@@ -2248,7 +2317,7 @@ static int build_qmap(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, hipStre
     HIP_TRY(hipMemsetAsync(m->d_qmap.get(), 0, words * 2, st));
     if (n == 0) return TSX_HIP_OK;
     HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-    if ((rc = query_line_pass(m, d_text, n, n, 0, st)) != TSX_HIP_OK) return rc;
+    if ((rc = line_pass(m, d_text, n, n, 0, st)) != TSX_HIP_OK) return rc;
     uint32_t lines = 0;
     HIP_TRY(hipMemcpyAsync(&lines, m->d_carry.get(), sizeof lines, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -2299,7 +2368,7 @@ static int piece_scan(tsx_hip_map *m, const uint8_t *d_text, uint64_t len, bool 
     const uint64_t ntiles = (len + TILE - 1) / TILE, span_cap = len / (2 * lpr) + 2;
     int rc;
     HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-    if ((rc = query_line_pass(m, d_text, len, len, 0, st)) != TSX_HIP_OK) return rc;
+    if ((rc = line_pass(m, d_text, len, len, 0, st)) != TSX_HIP_OK) return rc;
     if (span && (rc = grow(st, *span, span_cap * 16)) != TSX_HIP_OK) return rc;
     hipLaunchKernelGGL(record_scan_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
                        d_text, len, (const uint32_t *)m->d_tile.get(), ntiles, (const uint32_t *)m->d_carry.get(), lpr, last ? 1 : 0,
@@ -2477,18 +2546,16 @@ static int count_slabs(tsx_hip_map *m, const uint8_t *base, size_t n, hipStream_
         v.table = whole.table + ((uint64_t)s << v.l);
         v.seg_dirty = whole.seg_dirty + ((uint64_t)s << (v.l - v.S));
         m->fresh = fresh;
-        Event *ev = nullptr;
-        if (m->timing) {
-            if ((rc = next_timing_events(m, ev)) != TSX_HIP_OK) break;
-            for (int i = 0; i < 4; ++i) if (hipEventRecord(ev[i].get(), st) != hipSuccess) rc = TSX_HIP_EHIP;
-        }
+        Event *ev = nullptr;   // the slab's own tuple: no line pass, no scan -- its walks count as level 1
+        if ((rc = timing_open(m, ev, st)) != TSX_HIP_OK) break;
+        if (ev) rc = timing_record(ev, EV_SCAN, EV_PART, st);
         for (uint32_t w = 0; w < nwin && rc == TSX_HIP_OK; ++w)
             rc = shard_walk(m, d_desc + doff[w] * 2, (size_t)cnt[w], 1, w, nwin, est, nullptr, st);
         if (rc == TSX_HIP_OK) {
             if (!m->sh_pl || !m->sh_pl->fused) rc = TSX_HIP_EINVAL;
             else rc = run_partition_build(m, *m->sh_pl, nullptr, nullptr, 0, st, ev);
         }
-        if (rc == TSX_HIP_OK && ev && hipEventRecord(ev[7].get(), st) != hipSuccess) rc = TSX_HIP_EHIP;
+        if (rc == TSX_HIP_OK) rc = timing_close(ev, EV_END, st);
     }
     m->p = whole;
     if (rc == TSX_HIP_OK) m->fresh = false;
@@ -3948,7 +4015,7 @@ static bool query_args_ok(const tsx_hip_map *m, uint64_t lower, uint64_t upper) 
     return m && lower <= upper && m->p.lg == m->p.l;
 }
 
-// query_reads_kernel over the start positions [0, own_end) of d_text (n readable bytes), after query_line_pass.
+// query_reads_kernel over the start positions [0, own_end) of d_text (n readable bytes), after line_pass.
 static int query_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
                         const unsigned long long *d_line_base, uint64_t lower, uint64_t upper, unsigned long long *d_stats,
                         uint64_t cap, hipStream_t st) {
@@ -3992,7 +4059,7 @@ static int device_windows(tsx_hip_map *m, const uint8_t *base, size_t n, bool ro
         const bool last = off + own >= n;
         m->qmap_cur = qmap ? qmap + off / 16 : nullptr;   // (windows start at multiples of 16)
         HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
-        if ((rc = query_line_pass(m, base + off, len, own, head_open, st)) != TSX_HIP_OK) return rc;
+        if ((rc = line_pass(m, base + off, len, own, head_open, st)) != TSX_HIP_OK) return rc;
         if ((rc = per_window(off, own, len, head_open, last, (const unsigned long long *)d_base)) != TSX_HIP_OK) return rc;
         window_end(last, base + n - 1);
     }
@@ -4311,7 +4378,7 @@ static bool trim_rule_ok(const tsx_hip_map *m, const tsx_hip_trim_rule *r) {
            r->reserved == 0;
 }
 
-// solid_bits_kernel over the start positions [0, own_end) of d_text (n readable bytes), after query_line_pass.
+// solid_bits_kernel over the start positions [0, own_end) of d_text (n readable bytes), after line_pass.
 static int solid_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
                         const unsigned long long *d_line_base, const tsx_hip_trim_rule &rule, unsigned long long *d_bits,
                         hipStream_t st) {
@@ -4328,7 +4395,7 @@ static int solid_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint6
 }
 
 // trim_lines_kernel over the start positions [0, own_end) of d_text (n readable bytes, `off` into its whole text), after
-// query_line_pass: the line offsets of the records < cap in lo.  `last`: the text ends here, and d_carry holds the line
+// line_pass: the line offsets of the records < cap in lo.  `last`: the text ends here, and d_carry holds the line
 // ends up to there (an unterminated last line).
 static void lines_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
                          const unsigned long long *d_line_base, uint64_t off, bool last, unsigned long long *lo, uint64_t cap,
@@ -4548,7 +4615,7 @@ static uint64_t median_long_bases() {
 
 static bool median_rule_ok(const tsx_hip_median_rule *r) { return r && r->lower <= r->upper && r->reserved == 0; }
 
-// window_counts_kernel over the start positions [0, own_end) of d_text (n readable bytes), after query_line_pass.
+// window_counts_kernel over the start positions [0, own_end) of d_text (n readable bytes), after line_pass.
 static int counts_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
                          const unsigned long long *d_line_base, uint32_t *d_profile, hipStream_t st) {
     if (own_end == 0) return TSX_HIP_OK;
@@ -4753,7 +4820,7 @@ extern "C" int tsx_hip_filter_median_host(tsx_hip_map *m, const char *text, size
 // ---- table sizing: the HyperLogLog sketch of a text's k-mers, its estimate, the l that holds them (tsx_sketch.h) --
 static bool sketch_prec_ok(int precision) { return precision >= SKETCH_P_MIN && precision <= SKETCH_P_MAX; }
 
-// sketch_windows_kernel over the start positions [0, own_end) of d_text (n readable bytes), after query_line_pass.
+// sketch_windows_kernel over the start positions [0, own_end) of d_text (n readable bytes), after line_pass.
 static int sketch_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
                          const unsigned long long *d_line_base, int precision, uint32_t *d_regs, unsigned long long *d_kmers,
                          hipStream_t st) {
@@ -4987,7 +5054,7 @@ extern "C" int tsx_hip_prefilter_armed(const tsx_hip_map *m) {
     return m->pf_armed ? 1 : 0;
 }
 
-// prefilter_windows_kernel over the start positions [0, own_end) of d_text (n readable bytes), after query_line_pass.
+// prefilter_windows_kernel over the start positions [0, own_end) of d_text (n readable bytes), after line_pass.
 static int prefilter_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
                             const unsigned long long *d_line_base, hipStream_t st) {
     if (own_end == 0) return TSX_HIP_OK;
@@ -5240,7 +5307,7 @@ static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *
             PairSide &s = side[i];
             const uint8_t *d_text = s.p.text.get();
             if (hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            if ((rc = query_line_pass(m, d_text, cut[i], cut[i], 0, st)) != TSX_HIP_OK) break;
+            if ((rc = line_pass(m, d_text, cut[i], cut[i], 0, st)) != TSX_HIP_OK) break;
             if (trim) {
                 rc = trim_records(m, s.t, d_text, cut[i], R, s.last && cut[i] == s.len, *trule, st);
                 if (rc == TSX_HIP_OK) rc = trim_lens(m, s.t, R, *trule, pi + (i ? PI_TRIM_B : PI_TRIM_A), st);
