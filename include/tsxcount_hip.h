@@ -517,6 +517,48 @@ int tsx_hip_filter_median_host(tsx_hip_map *m, const char *text, size_t n, const
                                size_t chunk_bytes, uint64_t *kept_out, uint64_t *bytes_out);
 
 /*
+ * Digital normalization (csrc/tsx_normalize.h; no reference counterpart -- khmer `normalize-by-median`): the records of
+ * a text are kept while the median count of their k-mers, among the records kept so far, is below a cutoff, and only
+ * the k-mers of kept records are counted.  Records, lines, k-mers, the base rule and canonical keys are those of
+ * tsx_hip_median_reads_*; records are numbered from 0 over the whole text.
+ * ROUNDS: with R = round_records >= 1, round j holds the records [j R, (j + 1) R); the last round may be short.  For
+ *   each round in order: every record of the round gets its median (the MEDIAN above: saturated counts, v_(m/2), 0 for a
+ *   record without k-mers) against the table as it stands; a record is KEPT iff median < cutoff; after the whole round is
+ *   judged, every k-mer occurrence of its kept records is added to the table.  R = 1 is khmer's sequential rule.
+ *   The result depends on R and on nothing else: not on chunk_bytes, TSX_HIP_PIECE_BYTES, TSX_HIP_DEV_WINDOW or
+ *   TSX_HIP_MEDIAN_LONG.  TSX_HIP_NORMALIZE_ROUND (65536) is the R of the tools; it is part of the result's definition.
+ *   cutoff = 0 keeps nothing and leaves the table as it was; cutoff = UINT64_MAX keeps everything and leaves the table
+ *   of tsx_hip_count_fastq_host.  The table need not be empty at the start.
+ * OUTPUT: kept records are written whole, in input order, exactly as tsx_hip_filter_reads_host writes a record.
+ * TOTALS: records and kept records, the k-mers of all records (kmers_seen) and of the kept ones (kmers_added), rounds.
+ * The k-mers go in by the atomic insert path into a whole table: TSX_HIP_EINVAL (with a tsx_hip_last_error text) for a
+ *   map created with shard_bits > 0, a table above 2^32 slots (built slab by slab), an armed prefilter, a NULL rule,
+ *   round_records == 0 or reserved != 0.  A full table is reported as by the counting calls (tsx_hip_sync).
+ *   normalize_host    text in host memory, in pieces cut at ROUND boundaries (chunk_bytes 0 = 256 MiB, at most
+ *                     TSX_HIP_PIECE_BYTES when that is set; a round longer than a piece is taken whole).  fd >= 0: the
+ *                     kept records go to fd, piece i written while the device works on piece i + 1 (a failed write:
+ *                     TSX_HIP_EIO); fd = -1: no output.  keep_out (NULL, or keep_cap bytes): 1 for a kept record, else
+ *                     0.  More records than keep_cap: TSX_HIP_ERANGE; the first keep_cap entries are written and the
+ *                     table is complete.
+ *   normalize_device  dev_text as tsx_hip_median_reads_device takes it; dev_keep: keep_cap bytes in device memory, as
+ *                     keep_out.  The profile of the whole text and the line offsets are scratch of the call.  WAITS for
+ *                     the stream.
+ */
+#define TSX_HIP_NORMALIZE_ROUND 65536u
+typedef struct tsx_hip_normalize_rule {
+    uint64_t cutoff;            /* keep a record iff its median < cutoff */
+    uint64_t round_records;     /* R >= 1 */
+    int32_t reserved[2];        /* 0 */
+} tsx_hip_normalize_rule;
+typedef struct tsx_hip_normalize_totals {
+    uint64_t records, kept, kmers_seen, kmers_added, rounds;
+} tsx_hip_normalize_totals;
+int tsx_hip_normalize_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_normalize_rule *rule, int fd,
+                           uint8_t *keep_out, size_t keep_cap, size_t chunk_bytes, tsx_hip_normalize_totals *totals);
+int tsx_hip_normalize_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_normalize_rule *rule,
+                             void *dev_keep, size_t keep_cap, tsx_hip_normalize_totals *totals, void *stream);
+
+/*
  * Table sizing (csrc/tsx_sketch.h; no reference counterpart -- ntCard / KmerStream in front of KMC, jellyfish grows its
  * table): a HyperLogLog sketch of the k-mers a text WOULD put into a table, its estimate of their distinct number, and
  * the l that holds them.  Nothing is counted and no table is read or written.

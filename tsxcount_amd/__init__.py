@@ -66,6 +66,22 @@ class MedianRule(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class NormalizeRule(ctypes.Structure):
+    """tsx_hip_normalize_rule: a record is kept iff its median < cutoff; rounds of round_records records."""
+    _fields_ = [("cutoff", ctypes.c_uint64), ("round_records", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 2)]
+
+
+class NormalizeTotals(ctypes.Structure):
+    """tsx_hip_normalize_totals."""
+    _fields_ = [(f, ctypes.c_uint64) for f in ("records", "kept", "kmers_seen", "kmers_added", "rounds")]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+NORMALIZE_ROUND = 65536   # TSX_HIP_NORMALIZE_ROUND: part of the result's definition
+
+
 class TrimTotals(ctypes.Structure):
     """tsx_hip_trim_totals."""
     _fields_ = [("records", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("bases_in", ctypes.c_uint64),
@@ -180,7 +196,16 @@ def median_rule(lower=0, upper=None, invert=False):
     return MedianRule(int(lower), upper, 1 if invert else 0, 0)
 
 
-SKETCH_PRECISIONS = range(10, 15)    # the p of a sketch: 2^p registers
+def normalize_rule(cutoff=20, round_records=NORMALIZE_ROUND):
+    """A NormalizeRule from the Python arguments.  Raises ValueError for round_records < 1, before any GPU call."""
+    if int(round_records) < 1:
+        raise ValueError("normalize: round_records %d < 1" % int(round_records))
+    if int(cutoff) < 0:
+        raise ValueError("normalize: cutoff %d < 0" % int(cutoff))
+    return NormalizeRule(min(int(cutoff), (1 << 64) - 1), int(round_records), (ctypes.c_int32 * 2)(0, 0))
+
+
+SKETCH_PRECISIONS = range(10, 15)   # the p of a sketch: 2^p registers
 
 
 def _mix64(z):
@@ -419,6 +444,10 @@ def lib():
     L.tsx_hip_median_reads_device.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(sz), vp]
     L.tsx_hip_median_reads_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), sz]
     L.tsx_hip_filter_median_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(MedianRule), ci, sz, u64p, u64p]
+    L.tsx_hip_normalize_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(NormalizeRule), ci, vp, sz, sz,
+                                         ctypes.POINTER(NormalizeTotals)]
+    L.tsx_hip_normalize_device.argtypes = [vp, vp, sz, ctypes.POINTER(NormalizeRule), vp, sz,
+                                           ctypes.POINTER(NormalizeTotals), vp]
     u8p = ctypes.POINTER(ctypes.c_uint8)
     L.tsx_hip_sketch_host.argtypes = [vp, ctypes.c_char_p, sz, ci, u8p, ctypes.POINTER(SketchTotals), sz]
     L.tsx_hip_sketch_bgzf_host.argtypes = [vp, vp, sz, ci, u8p, ctypes.POINTER(SketchTotals)]
@@ -937,6 +966,50 @@ class TSXHashMapHIP:
         _check(self._lib.tsx_hip_median_reads_device(self.handle, vp(text_ptr), nbytes, vp(medians_ptr), cap, ctypes.byref(n),
                                                      vp(stream) if stream else None))
         return int(n.value)
+
+    # --- digital normalization ----------------------------------------------
+    def _check_normalize(self, rc):
+        if rc == EINVAL:   # a refusal: the library says which
+            raise TSXException(rc, self._lib.tsx_hip_last_error().decode() or self._lib.tsx_hip_strerror(rc).decode())
+        _check(rc)
+
+    def normalizeReads(self, text, path_or_fd=None, cutoff=20, round_records=NORMALIZE_ROUND, keep=False, chunk_bytes=0):
+        """Digital normalization (tsx_hip_normalize_host): the records of `text` in rounds of round_records; a record is
+        kept iff the median count of its k-mers, in the table as it stands when its round starts, is below cutoff, and
+        the k-mers of a round's kept records are counted when the round has been judged.  The kept records go to a
+        path (created or truncated) or an open file descriptor; None: no output.  Returns the totals (records, kept,
+        kmers_seen, kmers_added, rounds) as a dict; keep=True adds `keep`, a numpy bool array with one entry per
+        record."""
+        rule = normalize_rule(cutoff, round_records)
+        b = bytes(text)
+        tot = NormalizeTotals()
+        own = path_or_fd is not None and not isinstance(path_or_fd, int)
+        fd = -1 if path_or_fd is None else (os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd)
+        flags = np.zeros(len(b) // 2 + 2 if keep else 0, dtype=np.uint8)   # (a record holds two bytes at least)
+        try:
+            rc = self._lib.tsx_hip_normalize_host(self.handle, b, len(b), ctypes.byref(rule), fd,
+                                                  flags.ctypes.data_as(ctypes.c_void_p) if keep else None, flags.size,
+                                                  int(chunk_bytes), ctypes.byref(tot))
+        finally:
+            if own:
+                os.close(fd)
+        self._check_normalize(rc)
+        out = tot.as_dict()
+        if keep:
+            out["keep"] = flags[:out["records"]].astype(bool)
+        return out
+
+    def normalizeReadsDevice(self, text_ptr, nbytes, keep_ptr, keep_cap, cutoff=20, round_records=NORMALIZE_ROUND, stream=None):
+        """tsx_hip_normalize_device: the same for a device text; one byte per record into a device buffer of keep_cap
+        bytes (keep_ptr None: no flags).  Returns the totals as a dict (more records than keep_cap: TSXException
+        ERANGE, the table is complete)."""
+        vp = ctypes.c_void_p
+        rule = normalize_rule(cutoff, round_records)
+        tot = NormalizeTotals()
+        self._check_normalize(self._lib.tsx_hip_normalize_device(self.handle, vp(text_ptr), nbytes, ctypes.byref(rule),
+                                                                 vp(keep_ptr) if keep_ptr else None, keep_cap,
+                                                                 ctypes.byref(tot), vp(stream) if stream else None))
+        return tot.as_dict()
 
     # --- table sizing -------------------------------------------------------
     def _sketch_regs(self, precision, registers):

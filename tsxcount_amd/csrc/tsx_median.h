@@ -22,10 +22,11 @@ constexpr int MED_REG = 8;                  // profile entries a lane of the wav
 
 // solid_bits_kernel with the count kept: profile[i] for the start positions i < min(own_end, n) of buf -- `profile` is
 // the entry of position 0 of buf.  Every entry is written once, by the window that owns it; nothing at or past n.
+// The tiles [tile0, ntiles) only: the whole text passes 0, a round of the normalization (tsx_normalize.h) its own range.
 template <int WK, bool CANON = false, bool BR = false>
 __global__ __launch_bounds__(NT, 2) void window_counts_kernel(TableParams p, const uint8_t *buf, uint64_t n, uint64_t own_end,
-                                                              int head_open, const uint32_t *tile_line, uint64_t ntiles,
-                                                              const unsigned long long *line_base, uint32_t *profile,
+                                                              int head_open, const uint32_t *tile_line, uint64_t tile0,
+                                                              uint64_t ntiles, const unsigned long long *line_base, uint32_t *profile,
                                                               const uint16_t *qmap = nullptr) {
     __shared__ TileLds<uint32_t> s;
     extern __shared__ uint64_t s_lut[];
@@ -36,7 +37,7 @@ __global__ __launch_bounds__(NT, 2) void window_counts_kernel(TableParams p, con
     s.set_sentinels(tid);
     const WindowRule rule(p, n, own_end, *line_base);
     const uint64_t wr_end = min(own_end, n);
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    for (uint64_t tile = tile0 + blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t base = tile * TILE;
         lds_barrier();  // previous tile's LDS fully consumed
         tile_stage<BR>(s, tile_load(buf, n, head_open, tile_line, tile, tid), p, qmap, base, n, tid);
@@ -139,19 +140,19 @@ __device__ __forceinline__ void wave_select(const uint32_t *pv, uint32_t nw, uin
     median = prefix;
 }
 
-// med[r] = {m, median} of record r < min(cap, *d_nrec or nrec): its values are the entries of profile[s, e - k + 1) that
+// med[r] = {m, median} of record rec0 <= r < min(cap, *d_nrec or nrec): its values are the entries of profile[s, e - k + 1) that
 // are not NO_KMER, (s, e) its sequence line in lo (trim_lines_kernel; positions of the profile).  One wave -- one
 // workgroup of 64 lanes -- per record.  A record whose sequence line is longer than long_len is not selected here: its
 // index goes to list[1 + atomicAdd(list, 1)] for median_select_long_kernel (list_cap entries; a text of n bytes holds
 // fewer than n / long_len such lines).  Reads of the profile stay inside [s, e - k + 1).
 __global__ __launch_bounds__(64) void median_select_kernel(const uint32_t *profile, const unsigned long long *lo,
-                                                           const unsigned long long *d_nrec, uint64_t nrec, uint64_t cap,
-                                                           uint32_t k, uint64_t long_len, unsigned long long *list,
+                                                           const unsigned long long *d_nrec, uint64_t rec0, uint64_t nrec,
+                                                           uint64_t cap, uint32_t k, uint64_t long_len, unsigned long long *list,
                                                            uint64_t list_cap, unsigned long long *med) {
     __shared__ __attribute__((aligned(16))) uint32_t s_h[256];
     const int lane = threadIdx.x;
     const uint64_t R = min(cap, d_nrec ? (uint64_t)*d_nrec : nrec);
-    for (uint64_t r = blockIdx.x; r < R; r += gridDim.x) {
+    for (uint64_t r = rec0 + blockIdx.x; r < R; r += gridDim.x) {
         const uint64_t s = lo[r * TL_N + 2], e = lo[r * TL_N + 3];
         uint32_t m = 0, median = 0;
         if (e >= s + k) {

@@ -13,7 +13,7 @@
 #include "tsx_combine.h"
 #include "tsx_fasta.h"
 #include "tsx_trim.h"
-#include "tsx_median.h"
+#include "tsx_normalize.h"
 #include "tsx_sketch.h"
 #include "tsx_prefilter.h"
 #include "tsx_pairs.h"
@@ -169,6 +169,7 @@ struct tsx_hip_map {
     bool pf_armed = false;               // the FASTQ counting calls consult B (tsx_hip_prefilter_arm)
     Event pf_ev;                         // what the map's stream holds for the filters, for a caller's stream to wait for
     PfView pf_view() const { return PfView{pf_b.get(), pf_tot.get() + PF_ADMITTED, pf_tot.get() + PF_SKIPPED, pf_bits}; }
+    uint64_t norm_tiles = 0, norm_skipped = 0;   // the last normalization: tiles its count launches covered, tiles the gate skipped
     Event clear_ev, join_ev;
     bool clear_ev_set = false;
     hipStream_t foreign = nullptr;       // (a caller's: not owned)
@@ -3016,14 +3017,16 @@ extern "C" int tsx_hip_get_counts_host(tsx_hip_map *m, const uint64_t *kmers, si
 }
 
 // Words 0-2: the owners alive in this process (tsx_own.h) -- device buffers, pinned buffers, events + streams; tests
-// take differences.  Word 7: entries of the deferred list of the last partitioned pass.  Words 3-6 are spare and
-// read 0.  Not part of include/tsxcount_hip.h.
+// take differences.  Word 7: entries of the deferred list of the last partitioned pass.  Words 3 and 4: the tiles the
+// count launches of the map's last normalization covered, and those of them the record gate skipped.  Words 5-6 are
+// spare and read 0.  Not part of include/tsxcount_hip.h.
 extern "C" int tsx_hip_debug_counters(tsx_hip_map *m, uint64_t *out8) {
     if (!m || !out8) return TSX_HIP_EINVAL;
     HIP_TRY(hipSetDevice(m->device));
     HIP_TRY(hipStreamSynchronize(m->stream.get()));
     for (int i = 0; i < 8; ++i) out8[i] = 0;
     out8[0] = (uint64_t)g_live_dev.load(); out8[1] = (uint64_t)g_live_pin.load(); out8[2] = (uint64_t)g_live_sync.load();
+    out8[3] = m->norm_tiles; out8[4] = m->norm_skipped;
     if (m->d_def_n.get()) {
         unsigned long long dn = 0;
         HIP_TRY(hipMemcpy(&dn, m->d_def_n.get(), 8, hipMemcpyDeviceToHost));
@@ -4615,17 +4618,25 @@ static uint64_t median_long_bases() {
 
 static bool median_rule_ok(const tsx_hip_median_rule *r) { return r && r->lower <= r->upper && r->reserved == 0; }
 
-// window_counts_kernel over the start positions [0, own_end) of d_text (n readable bytes), after line_pass.
+// A range of the tiles of a text that has had its line pass: the tiles [first, first + count) of tile_line (NULL: the
+// map's d_tile).  ALL_TILES: every tile of the launch, what the calls on whole pieces and windows pass.
+struct TileSpan { uint64_t first, count; const uint32_t *tile_line; };
+static const TileSpan ALL_TILES = {0, ~0ULL, nullptr};
+
+// window_counts_kernel over the start positions [0, own_end) of d_text (n readable bytes), after line_pass: those of the
+// tiles `ts`.
 static int counts_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
-                         const unsigned long long *d_line_base, uint32_t *d_profile, hipStream_t st) {
-    if (own_end == 0) return TSX_HIP_OK;
+                         const unsigned long long *d_line_base, uint32_t *d_profile, const TileSpan &ts, hipStream_t st) {
+    if (own_end == 0 || ts.count == 0) return TSX_HIP_OK;
     const uint64_t ntiles = (own_end + TILE - 1) / TILE;
+    const uint64_t t0 = std::min(ts.first, ntiles), t1 = t0 + std::min(ts.count, ntiles - t0);
+    if (t0 == t1) return TSX_HIP_OK;
+    const uint32_t *tile_line = ts.tile_line ? ts.tile_line : (const uint32_t *)m->d_tile.get();
     const size_t lut_bytes = m->lut.size() * 8;
-    const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 4);
+    const int grid = (int)std::min<uint64_t>(t1 - t0, (uint64_t)m->cus * 4);
     DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((window_counts_kernel<WKV, CANV, BRV>), dim3(grid), dim3(NT),
-                                                        lut_bytes, st, m->p, d_text, n, own_end, head_open,
-                                                        (const uint32_t *)m->d_tile.get(), ntiles, d_line_base, d_profile,
-                                                        m->qmap_cur))));
+                                                        lut_bytes, st, m->p, d_text, n, own_end, head_open, tile_line, t0, t1,
+                                                        d_line_base, d_profile, m->qmap_cur))));
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
@@ -4633,15 +4644,15 @@ static int counts_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint
 // Entries of the list of long records for a text of n bytes (the counter in front of them not counted).
 static uint64_t median_list_cap(uint64_t n, uint64_t long_len) { return n / (long_len + 1) + 2; }
 
-// Both selection kernels over the records [0, min(cap, *d_nrec or nrec)) with line offsets in lo: the wave form lists the
-// long records (list: the counter, then list_cap entries), the workgroup form takes them.  Queued, not waited for.
+// Both selection kernels over the records [rec0, min(cap, *d_nrec or nrec)) with line offsets in lo: the wave form lists
+// the long records (list: the counter, then list_cap entries), the workgroup form takes them.  Queued, not waited for.
 static int median_select(tsx_hip_map *m, const uint32_t *d_profile, const unsigned long long *lo, const unsigned long long *d_nrec,
-                         uint64_t nrec, uint64_t cap, uint64_t long_len, unsigned long long *list, uint64_t list_cap,
+                         uint64_t rec0, uint64_t nrec, uint64_t cap, uint64_t long_len, unsigned long long *list, uint64_t list_cap,
                          unsigned long long *med, hipStream_t st) {
-    if (cap == 0) return TSX_HIP_OK;
+    if (cap <= rec0) return TSX_HIP_OK;
     HIP_TRY(hipMemsetAsync(list, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(median_select_kernel, dim3((uint32_t)std::min<uint64_t>(cap, (uint64_t)m->cus * 32)), dim3(64), 0, st,
-                       d_profile, lo, d_nrec, nrec, cap, (uint32_t)m->p.k, long_len, list, list_cap, med);
+    hipLaunchKernelGGL(median_select_kernel, dim3((uint32_t)std::min<uint64_t>(cap - rec0, (uint64_t)m->cus * 32)), dim3(64), 0, st,
+                       d_profile, lo, d_nrec, rec0, nrec, cap, (uint32_t)m->p.k, long_len, list, list_cap, med);
     hipLaunchKernelGGL(median_select_long_kernel, dim3((uint32_t)std::min<uint64_t>(list_cap, (uint64_t)m->cus * 4)), dim3(NT), 0, st,
                        d_profile, lo, (const unsigned long long *)list, list_cap, (uint32_t)m->p.k, med);
     HIP_TRY(hipGetLastError());
@@ -4654,7 +4665,7 @@ static int median_windows(tsx_hip_map *m, const uint8_t *base, size_t n, uint32_
                           hipStream_t st) {
     return device_windows(m, base, n, true, st,
                           [&](size_t off, size_t own, size_t len, int head_open, bool last, const unsigned long long *d_base) -> int {
-                              TSX_TRY(counts_launch(m, base + off, len, own, head_open, d_base, d_profile + off, st));
+                              TSX_TRY(counts_launch(m, base + off, len, own, head_open, d_base, d_profile + off, ALL_TILES, st));
                               if (lo) lines_launch(m, base + off, len, own, head_open, d_base, off, last, lo, cap, st);
                               return TSX_HIP_OK;
                           });
@@ -4699,7 +4710,7 @@ extern "C" int tsx_hip_median_reads_device(tsx_hip_map *m, const void *dev_text,
     HIP_TRY(hipMemsetAsync(lo.get(), 0, (cap + 1) * TL_N * 8, st));
     if ((rc = median_windows(m, (const uint8_t *)dev_text, n, profile.get(), lo.get(), cap, st)) != TSX_HIP_OK) return rc;
     const unsigned long long *d_nrec = (const unsigned long long *)m->d_carry.get() + 3;
-    if ((rc = median_select(m, profile.get(), lo.get(), d_nrec, 0, cap, long_len, list.get(), list_cap,
+    if ((rc = median_select(m, profile.get(), lo.get(), d_nrec, 0, 0, cap, long_len, list.get(), list_cap,
                             (unsigned long long *)dev_medians, st)) != TSX_HIP_OK)
         return rc;
     unsigned long long nrec = 0;
@@ -4731,7 +4742,7 @@ static int median_piece(tsx_hip_map *m, MedianBufs &b, const uint8_t *d_text, ui
     QmapScope qs(m);
     TSX_TRY(piece_qmap(m, d_text, cut, st));
     const unsigned long long *zero = b.p.info.get() + 4;
-    TSX_TRY(counts_launch(m, d_text, cut, cut, 0, zero, b.profile.get(), st));
+    TSX_TRY(counts_launch(m, d_text, cut, cut, 0, zero, b.profile.get(), ALL_TILES, st));
     if (what == MED_PROFILE) return TSX_HIP_OK;
     const uint64_t list_cap = median_list_cap(cut, long_len);
     TSX_TRY(grow(st, b.lo, nrec * TL_N * 8));
@@ -4740,7 +4751,7 @@ static int median_piece(tsx_hip_map *m, MedianBufs &b, const uint8_t *d_text, ui
     HIP_TRY(hipMemsetAsync(b.lo.get(), 0, nrec * TL_N * 8, st));
     // (the carry is read for an unterminated last line only: then cut = len and it holds the lines of [0, cut))
     lines_launch(m, d_text, cut, cut, 0, zero, 0, last, b.lo.get(), nrec, st);
-    return median_select(m, b.profile.get(), b.lo.get(), nullptr, nrec, nrec, long_len, b.list.get(), list_cap, b.med.get(), st);
+    return median_select(m, b.profile.get(), b.lo.get(), nullptr, 0, nrec, nrec, long_len, b.list.get(), list_cap, b.med.get(), st);
 }
 
 // The median filter behind median_piece, as filter_piece: kept lengths by the medians, their scan (total -> info[3], kept
@@ -4815,6 +4826,280 @@ extern "C" int tsx_hip_filter_median_host(tsx_hip_map *m, const char *text, size
     if (bytes_out) *bytes_out = 0;
     if (!median_rule_ok(rule) || !query_args_ok(m, 0, 0) || (!text && n) || fd < 0) return TSX_HIP_EINVAL;
     return median_host(m, text, n, MED_FILTER, chunk_bytes, nullptr, nullptr, 0, nullptr, rule, fd, kept_out, bytes_out);
+}
+
+// ---- digital normalization: rounds of records judged by their medians, the kept ones counted (tsx_normalize.h) ----
+// What the atomic insert path into a whole table asks of the map and the rule.  No GPU call.
+static int normalize_args_ok(const tsx_hip_map *m, const tsx_hip_normalize_rule *r) {
+    if (!m) return TSX_HIP_EINVAL;
+    if (m->p.lg != m->p.l) { g_last_error = "normalize: a map created with shard_bits > 0"; return TSX_HIP_EINVAL; }
+    if (slab_bits(m)) { g_last_error = "normalize: a table above 2^32 slots is built slab by slab, not by the atomic path"; return TSX_HIP_EINVAL; }
+    if (m->pf_armed) { g_last_error = "normalize: a prefilter is armed"; return TSX_HIP_EINVAL; }
+    if (!r) { g_last_error = "normalize: no rule"; return TSX_HIP_EINVAL; }
+    if (r->round_records == 0) { g_last_error = "normalize: round_records = 0"; return TSX_HIP_EINVAL; }
+    if (r->reserved[0] || r->reserved[1]) { g_last_error = "normalize: reserved != 0"; return TSX_HIP_EINVAL; }
+    return TSX_HIP_OK;
+}
+
+// A window of a text whose line pass is kept: `own` start positions from byte `off` of the whole text (len readable
+// bytes), the tile line counts and the line base the pass left, the window's part of a quality bitmap.  A host piece is
+// one such window at off 0.
+struct NormWindow {
+    const uint8_t *text;
+    uint64_t off, own, len;
+    int head_open;
+    const uint32_t *tile_line;
+    const unsigned long long *line_base;
+    const uint16_t *qmap;
+};
+
+// Scratch of a normalization that both forms use.
+struct NormBufs {
+    DevBuf<uint32_t> keep;                         // one bit per record
+    DevBuf<unsigned long long> bounds, tiles;      // where the rounds start; tiles the gate skipped
+    PinBuf<unsigned long long> h_bounds;
+    uint64_t covered = 0;                          // tiles the count launches covered
+};
+
+// count_kept_kernel over the tiles [t0, t1) of a window, for the records [r0, r1).
+static int kept_launch(tsx_hip_map *m, const NormWindow &w, uint64_t t0, uint64_t t1, const uint32_t *keep, uint64_t r0,
+                       uint64_t r1, unsigned long long *skipped, hipStream_t st) {
+    const size_t lut_bytes = m->lut.size() * 8;
+    const int grid = (int)std::min<uint64_t>(t1 - t0, (uint64_t)m->cus * 3);
+    const uint64_t tiles_all = (w.own + TILE - 1) / TILE;
+    const uint32_t lshift = m->p.line_mask == 3 ? 2u : 1u;
+    DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_kept_kernel<WKV, CANV, BRV>), dim3(grid), dim3(NT),
+                                                        lut_bytes, st, m->p, w.text, w.len, w.own, w.head_open, w.tile_line, t0, t1,
+                                                        tiles_all, w.line_base, lshift, keep, r0, r1, skipped, m->qmap_cur))));
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// The rounds of the records [0, nrec) of a text that lies in the windows win[0, nwin) (in text order; its records end
+// at byte `end`), R records each: per round the profile of its tiles, the medians of its records, the keep rule, the
+// count of the kept.  profile: the entry of byte 0 of the text; lo: the line offsets of the records (text positions).
+// span / len: the record spans and the kept lengths for filter_compact (both NULL: no output); keep_bytes: one byte per
+// record < bytes_cap, or NULL.  totals: NT_N device words that grow.  Waits once, for the round bounds; the rounds are
+// queued.  The caller holds a QmapScope.
+static int normalize_rounds(tsx_hip_map *m, NormBufs &nb, const NormWindow *win, size_t nwin, uint64_t end, uint64_t nrec, uint64_t R,
+                            uint64_t cutoff, uint32_t *profile, const unsigned long long *lo, const unsigned long long *span,
+                            unsigned long long *len, bool nl_last, uint8_t *keep_bytes, uint64_t bytes_cap,
+                            unsigned long long *list, uint64_t list_cap, unsigned long long *med, unsigned long long *totals,
+                            uint64_t long_len, hipStream_t st, uint64_t &rounds) {
+    if (nrec == 0) return TSX_HIP_OK;
+    const uint64_t nrounds = (nrec - 1) / R + 1;
+    TSX_TRY(grow(st, nb.keep, ((nrec + 31) / 32 + 1) * sizeof(uint32_t)));
+    TSX_TRY(grow(st, nb.bounds, (nrounds + 1) * 8));
+    TSX_TRY(nb.h_bounds.reserve(&st, (nrounds + 1) * 8, (nrounds + 1) * 8 + 4096));
+    HIP_TRY(hipMemsetAsync(nb.keep.get(), 0, ((nrec + 31) / 32 + 1) * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(round_bounds_kernel, dim3(grid_for(m, nrounds + 1, 8)), dim3(NT), 0, st, lo, (uint64_t)0, R, nrounds, end,
+                       nb.bounds.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(nb.h_bounds.get(), nb.bounds.get(), (nrounds + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const unsigned long long *hb = nb.h_bounds.get();
+    size_t w0 = 0;   // the first window that reaches into the round
+    for (uint64_t j = 0; j < nrounds; ++j) {
+        const uint64_t r0 = j * R, r1 = nrec - r0 > R ? r0 + R : nrec, b0 = hb[j], b1 = hb[j + 1];
+        while (w0 + 1 < nwin && win[w0].off + win[w0].own <= b0) ++w0;
+        // the window's tiles that hold start positions of [b0, b1)
+        auto tiles_of = [&](const NormWindow &w, uint64_t &t0, uint64_t &t1) {
+            const uint64_t a = std::max(b0, w.off) - w.off, b = std::min(b1, w.off + w.own) - w.off;
+            t0 = a / TILE; t1 = (b + TILE - 1) / TILE;
+        };
+        for (size_t wi = w0; wi < nwin && win[wi].off < b1; ++wi) {
+            const NormWindow &w = win[wi];
+            uint64_t t0, t1;
+            tiles_of(w, t0, t1);
+            m->qmap_cur = w.qmap;
+            TSX_TRY(counts_launch(m, w.text, w.len, w.own, w.head_open, w.line_base, profile + w.off, TileSpan{t0, t1 - t0, w.tile_line}, st));
+        }
+        TSX_TRY(median_select(m, profile, lo, nullptr, r0, r1, r1, long_len, list, list_cap, med, st));
+        hipLaunchKernelGGL(normalize_keep_kernel, dim3(grid_for(m, r1 - r0, 8)), dim3(NT), 0, st, (const unsigned long long *)med, span,
+                           r0, r1, nrec, cutoff, nl_last ? 1 : 0, nb.keep.get(), len, keep_bytes, bytes_cap, totals);
+        HIP_TRY(hipGetLastError());
+        if (cutoff == 0) continue;   // (nothing is kept: nothing to count)
+        for (size_t wi = w0; wi < nwin && win[wi].off < b1; ++wi) {
+            const NormWindow &w = win[wi];
+            uint64_t t0, t1;
+            tiles_of(w, t0, t1);
+            if (t0 == t1) continue;
+            m->qmap_cur = w.qmap;
+            TSX_TRY(kept_launch(m, w, t0, t1, nb.keep.get(), r0, r1, nb.tiles.get(), st));
+            nb.covered += t1 - t0;
+        }
+    }
+    rounds += nrounds;
+    return TSX_HIP_OK;
+}
+
+// What both forms do first and last with the gate's tile counters (tsx_hip_debug_counters).
+static int normalize_tiles_begin(NormBufs &nb, hipStream_t st) {
+    TSX_TRY(nb.tiles.alloc(sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(nb.tiles.get(), 0, sizeof(unsigned long long), st));
+    return TSX_HIP_OK;
+}
+static int normalize_tiles_end(tsx_hip_map *m, NormBufs &nb, hipStream_t st) {
+    unsigned long long sk = 0;
+    HIP_TRY(hipMemcpyAsync(&sk, nb.tiles.get(), sizeof sk, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    m->norm_tiles = nb.covered; m->norm_skipped = sk;
+    return TSX_HIP_OK;
+}
+
+// The host form: the pieces of host_pieces, each cut back to its last whole round -- rounds are numbered from the
+// record index over the whole text, every piece starts at a multiple of R, and what lies behind the cut is the head of
+// the next piece.  A piece that holds no whole round grows, as one that holds no whole record does (host_pieces:
+// nrec = 0), so a round longer than a piece is taken whole; the last piece takes what is left, a short round included.
+// Compaction and write-behind once per piece.
+static int normalize_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_normalize_rule &rule, int fd, uint8_t *keep_out,
+                          size_t keep_cap, size_t chunk_bytes, tsx_hip_normalize_totals &tot) {
+    hipStream_t st = m->stream.get();
+    WriteBehind wb;
+    wb.fd = fd;
+    NormBufs nb;
+    DevBuf<uint8_t> keepb;
+    MedianBufs b(st);
+    const uint64_t long_len = median_long_bases(), R = rule.round_records;
+    uint64_t rec_base = 0, count[NT_N] = {0, 0, 0}, rounds = 0;
+    bool began = false;
+    int rc = host_pieces(m, b.p, text, n, chunk_bytes, true, rec_base,
+        [&](const uint8_t *d_text, uint64_t len, bool last, uint64_t &cut, uint64_t &nrec, bool &open) -> int {
+            TSX_TRY(piece_front(m, b.p, d_text, len, last, true, cut, nrec, open));
+            const uint64_t whole = nrec / R * R;
+            if (last || whole == nrec) return TSX_HIP_OK;
+            if (whole == 0) { cut = 0; nrec = 0; return TSX_HIP_OK; }   // no whole round: the piece grows
+            unsigned long long c = 0;   // record `whole` starts the next piece
+            HIP_TRY(hipMemcpyAsync(&c, b.p.rspan.get() + 2 * whole, sizeof c, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            cut = c; nrec = whole; open = false;
+            return TSX_HIP_OK;
+        },
+        [&](size_t, uint64_t base, uint64_t cut, uint64_t nrec, bool open) -> int {
+            if (!nrec) return TSX_HIP_OK;
+            if (!began) { TSX_TRY(normalize_tiles_begin(nb, st)); began = true; }
+            const uint8_t *d_text = b.p.text.get();
+            const uint64_t list_cap = median_list_cap(cut, long_len), nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+            TSX_TRY(grow(st, b.profile, (cut + 16) * sizeof(uint32_t)));
+            TSX_TRY(grow(st, b.lo, nrec * TL_N * 8));
+            TSX_TRY(grow(st, b.med, nrec * sizeof(tsx_hip_read_median)));
+            TSX_TRY(grow(st, b.list, (list_cap + 1) * 8));
+            if (fd >= 0) {
+                TSX_TRY(grow(st, b.koff, (nk + nchunks + 16) * sizeof(unsigned long long)));
+                TSX_TRY(b.out.room(st, cut));
+            }
+            if (keep_out) TSX_TRY(grow(st, keepb, nrec));
+            QmapScope qs(m);
+            TSX_TRY(piece_qmap(m, d_text, cut, st));
+            unsigned long long *const info = b.p.info.get();
+            HIP_TRY(hipMemsetAsync(b.lo.get(), 0, nrec * TL_N * 8, st));
+            // (the carry is read for an unterminated last line only: then the piece is the last one, whole)
+            lines_launch(m, d_text, cut, cut, 0, info + 4, 0, open, b.lo.get(), nrec, st);
+            const NormWindow w = {d_text, 0, cut, cut, 0, (const uint32_t *)m->d_tile.get(), info + 4, m->qmap_cur};
+            TSX_TRY(normalize_rounds(m, nb, &w, 1, cut, nrec, R, rule.cutoff, b.profile.get(), b.lo.get(),
+                                     fd >= 0 ? b.p.rspan.get() : nullptr, fd >= 0 ? b.koff.get() : nullptr, open,
+                                     keep_out ? keepb.get() : nullptr, nrec, b.list.get(), list_cap, b.med.get(), info + 5, long_len, st,
+                                     rounds));
+            if (fd >= 0) {
+                HIP_TRY(hipMemsetAsync(b.koff.get() + nrec, 0, sizeof(unsigned long long), st));
+                TSX_TRY(filter_compact(m, d_text, cut, b.p.rspan.get(), b.koff.get(), nrec, info + 3, b.out.out, (uint64_t)b.out.have, st));
+                TSX_TRY(wb.piece(b.p, b.out.out, cut, NT_N, count, "normalize"));
+            } else {
+                unsigned long long *h = b.p.h_info.get();
+                HIP_TRY(hipMemcpyAsync(h + 5, info + 5, NT_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                for (int i = 0; i < NT_N; ++i) count[i] += h[5 + i];
+                HIP_TRY(hipMemsetAsync(info + 5, 0, NT_N * sizeof(unsigned long long), st));
+            }
+            return deliver_records(keep_out, keep_out ? keep_cap : 0, base, keepb.get(), nrec, st);
+        });
+    if (rc == TSX_HIP_OK) rc = wb.flush();
+    if (began) { const int rc2 = normalize_tiles_end(m, nb, st); if (rc == TSX_HIP_OK) rc = rc2; }
+    tot.records = rec_base; tot.kept = count[NT_KEPT]; tot.kmers_seen = count[NT_SEEN]; tot.kmers_added = count[NT_ADDED];
+    tot.rounds = rounds;
+    if (rc == TSX_HIP_OK && keep_out && rec_base > keep_cap) rc = TSX_HIP_ERANGE;
+    return rc;
+}
+
+extern "C" int tsx_hip_normalize_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_normalize_rule *rule, int fd,
+                                      uint8_t *keep_out, size_t keep_cap, size_t chunk_bytes, tsx_hip_normalize_totals *totals) {
+    tsx_hip_normalize_totals tot = {0, 0, 0, 0, 0};
+    if (totals) *totals = tot;
+    TSX_TRY(normalize_args_ok(m, rule));
+    if ((!text && n) || (!keep_out && keep_cap)) return TSX_HIP_EINVAL;
+    m->norm_tiles = m->norm_skipped = 0;
+    if (n && rule->cutoff) m->used = true;
+    const int rc = normalize_host(m, text, n, *rule, fd, keep_out, keep_cap, chunk_bytes, tot);
+    if (totals) *totals = tot;
+    return rc;
+}
+
+// The device form.  device_windows makes the line pass of every window; its tile line counts, its line base and the
+// line offsets of its records are kept for the whole text, so that a round -- records by their index over the whole
+// text, wherever the window seams fall -- finds the tiles of each window it reaches into.  Then the rounds, as for a
+// host piece.
+extern "C" int tsx_hip_normalize_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_normalize_rule *rule,
+                                        void *dev_keep, size_t keep_cap, tsx_hip_normalize_totals *totals, void *stream) {
+    tsx_hip_normalize_totals tot = {0, 0, 0, 0, 0};
+    if (totals) *totals = tot;
+    TSX_TRY(normalize_args_ok(m, rule));
+    if ((!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_keep && keep_cap)) return TSX_HIP_EINVAL;
+    m->norm_tiles = m->norm_skipped = 0;
+    if (n && rule->cutoff) m->used = true;
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    TSX_TRY(ensure_zeroed(m, st));
+    TSX_TRY(base_rule_ok(m));
+    const uint8_t *base = (const uint8_t *)dev_text;
+    const uint32_t lpr = m->p.line_mask + 1;
+    const uint64_t cap = n / (2 * lpr) + 2;   // (no text holds more records: tsx_hip_median_reads_device)
+    const uint64_t long_len = median_long_bases(), list_cap = median_list_cap(n, long_len);
+    const size_t WIN = (dev_window_bytes() + 63) & ~(size_t)63, nwin = n ? (n - 1) / WIN + 1 : 0;
+    const uint64_t tiles_win = (WIN + TILE - 1) / TILE;   // room per window
+    NormBufs nb;
+    DevBuf<uint32_t> profile, tile_all;
+    DevBuf<unsigned long long> lo, list, med, bases, totals_d;
+    SyncAtExit wait(st);
+    TSX_TRY(normalize_tiles_begin(nb, st));
+    TSX_TRY(profile.alloc(((size_t)n + 16) * sizeof(uint32_t)));
+    TSX_TRY(lo.alloc((cap + 1) * TL_N * 8));
+    TSX_TRY(list.alloc((list_cap + 1) * 8));
+    TSX_TRY(med.alloc((cap + 1) * sizeof(tsx_hip_read_median)));
+    TSX_TRY(tile_all.alloc((nwin * tiles_win + 1) * sizeof(uint32_t)));
+    TSX_TRY(bases.alloc((nwin + 1) * 8));
+    TSX_TRY(totals_d.alloc(NT_N * 8));
+    HIP_TRY(hipMemsetAsync(lo.get(), 0, (cap + 1) * TL_N * 8, st));
+    HIP_TRY(hipMemsetAsync(totals_d.get(), 0, NT_N * 8, st));
+    std::vector<NormWindow> win;
+    int rc = device_windows(m, base, n, true, st,
+                            [&](size_t off, size_t own, size_t len, int head_open, bool last, const unsigned long long *d_base) -> int {
+                                const size_t wi = win.size();
+                                uint32_t *tl = tile_all.get() + wi * tiles_win;
+                                lines_launch(m, base + off, len, own, head_open, d_base, off, last, lo.get(), cap, st);
+                                HIP_TRY(hipMemcpyAsync(tl, m->d_tile.get(), ((own + TILE - 1) / TILE) * sizeof(uint32_t),
+                                                       hipMemcpyDeviceToDevice, st));
+                                HIP_TRY(hipMemcpyAsync(bases.get() + wi, d_base, 8, hipMemcpyDeviceToDevice, st));
+                                win.push_back(NormWindow{base + off, off, own, len, head_open, tl, bases.get() + wi, m->qmap_cur});
+                                return TSX_HIP_OK;
+                            });
+    if (rc != TSX_HIP_OK) return rc;
+    unsigned long long nrec = 0;
+    HIP_TRY(hipMemcpyAsync(&nrec, (const unsigned long long *)m->d_carry.get() + 3, sizeof nrec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    uint64_t rounds = 0;
+    {
+        QmapScope qs(m);
+        rc = normalize_rounds(m, nb, win.data(), win.size(), n, nrec, rule->round_records, rule->cutoff, profile.get(), lo.get(), nullptr,
+                              nullptr, false, (uint8_t *)dev_keep, keep_cap, list.get(), list_cap, med.get(), totals_d.get(), long_len,
+                              st, rounds);
+    }
+    if (rc != TSX_HIP_OK) return rc;
+    unsigned long long h[NT_N] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, totals_d.get(), sizeof h, hipMemcpyDeviceToHost, st));
+    TSX_TRY(normalize_tiles_end(m, nb, st));   // (waits)
+    tot.records = nrec; tot.kept = h[NT_KEPT]; tot.kmers_seen = h[NT_SEEN]; tot.kmers_added = h[NT_ADDED]; tot.rounds = rounds;
+    if (totals) *totals = tot;
+    return nrec > keep_cap && dev_keep ? TSX_HIP_ERANGE : TSX_HIP_OK;
 }
 
 // ---- table sizing: the HyperLogLog sketch of a text's k-mers, its estimate, the l that holds them (tsx_sketch.h) --

@@ -137,6 +137,23 @@ static std::pair<uint64_t, uint64_t> tsx_filter_median(tsx_hip_map *pMap, const 
     fnCheck(rc);
     return std::make_pair(iKept, iWritten);
 }
+// Digital normalization (tsx_hip_normalize_host): the kept records into sPath (created / truncated; empty: no output).
+template <typename C>
+static tsx_hip_normalize_totals tsx_normalize_reads(tsx_hip_map *pMap, const char *pText, size_t iBytes,
+                                                    const tsx_hip_normalize_rule &oRule, const std::string &sPath,
+                                                    size_t iChunkBytes, C fnCheck) {
+    int fd = -1;
+    if (!sPath.empty()) {
+        fd = open(sPath.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0) throw TSXException("could not open " + sPath + " for writing", TSX_HIP_EIO);
+    }
+    tsx_hip_normalize_totals oTotals;
+    int rc = tsx_hip_normalize_host(pMap, pText, iBytes, &oRule, fd, nullptr, 0, iChunkBytes, &oTotals);
+    if (fd >= 0 && close(fd) != 0 && rc == TSX_HIP_OK) rc = TSX_HIP_EIO;
+    if (rc == TSX_HIP_EINVAL) throw TSXException(std::string("normalize: ") + tsx_hip_last_error(), rc);
+    fnCheck(rc);
+    return oTotals;
+}
 // The filter and the trim over mate pairs (tsx_hip_filter_pairs_host / tsx_hip_trim_pairs_host).  pText2 == nullptr: one
 // interleaved text.  Paths: kept mates 1, kept mates 2, orphans of text 1, orphans of text 2 -- created / truncated; an
 // empty path is no output (-1: allowed for the orphans, and for everything of text 2 with an interleaved text).
@@ -311,6 +328,14 @@ public:
     std::pair<uint64_t, uint64_t> filterByMedian(const char *pText, size_t iBytes, const tsx_hip_median_rule &oRule,
                                                  const std::string &sPath, size_t iChunkBytes = 0) {
         return tsx_filter_median(m_pMap, pText, iBytes, oRule, sPath, iChunkBytes, check);
+    }
+    // digital normalization: records kept while their median is below iCutoff, in rounds of iRoundRecords; the kept
+    // records into sPath (empty: no output), their k-mers into the table; returns the totals
+    tsx_hip_normalize_totals normalizeReads(const char *pText, size_t iBytes, uint64_t iCutoff = 20,
+                                            uint64_t iRoundRecords = TSX_HIP_NORMALIZE_ROUND, const std::string &sPath = std::string(),
+                                            size_t iChunkBytes = 0) {
+        const tsx_hip_normalize_rule oRule = {iCutoff, iRoundRecords, {0, 0}};
+        return tsx_normalize_reads(m_pMap, pText, iBytes, oRule, sPath, iChunkBytes, check);
     }
     // the kept span (start, length) of every record of a text under oRule (tsx_hip_trim_spans_host)
     std::vector<tsx_hip_trim_span> trimSpans(const char *pText, size_t iBytes, const tsx_hip_trim_rule &oRule,

@@ -75,6 +75,11 @@ struct arguments {
     // --min-count=2: two passes over --input, the first into a prefilter of 2^prefilter_bits bits (0: l + 6), so that k-mers
     // seen once take no slot
     int min_count = 1, prefilter_bits = 0;
+    // digital normalization: --normalize=OUT counts --input through tsx_hip_normalize_host instead of the plain count and
+    // writes the kept records to OUT
+    std::string normalize;
+    uint64_t normalize_cutoff = 20, normalize_round = TSX_HIP_NORMALIZE_ROUND;
+    bool normalize_opts = false;   // --normalize-cutoff / --normalize-round were given
 };
 
 static bool opt(const char *arg, const char *name, std::string &val) {
@@ -95,6 +100,7 @@ static int usage() {
                  "                [--filter=OUT] [--read-stats=FILE] [--filter-input=FILE] [--filter-lower=N] [--filter-upper=N]\n"
                  "                [--filter-min=M] [--filter-fraction=F] [--filter-invert] [--save=DB] [--load=DB[,DB2,...]]\n"
                  "                [--read-medians=FILE] [--filter-median-lower=N] [--filter-median-upper=N]\n"
+                 "                [--normalize=OUT [--normalize-cutoff=20] [--normalize-round=65536]]\n"
                  "                [--trim=OUT] [--trim-spans=FILE] [--trim-input=FILE] [--trim-lower=N] [--trim-upper=N]\n"
                  "                [--trim-mode=longest|prefix] [--trim-min-len=N]\n"
                  "                [--filter-input=R1,R2 --filter=O1,O2] [--filter-singles=S1,S2] [--filter-pairs=both|any]\n"
@@ -138,6 +144,15 @@ static int usage() {
                  "--filter-median-upper=N switch --filter to the median rule: a record passes when its median lies in N..N\n"
                  "(default 0..unbounded); --filter-invert applies, the other --filter-* rule options do not go with it. One GPU,\n"
                  "single-end input, no wrapped FASTA.\n"
+                 "--normalize=OUT counts --input by digital normalization (khmer's normalize-by-median) instead of the plain\n"
+                 "count: the records are taken in rounds of --normalize-round (default 65536) records; a record is kept when the\n"
+                 "median count of its k-mers, among the records kept in the rounds before, is below --normalize-cutoff (default\n"
+                 "20), and only the k-mers of kept records are counted. The kept records go to OUT, whole and in input order; it\n"
+                 "prints normalize<TAB>records<TAB>kept<TAB>kmers_seen<TAB>kmers_added<TAB>rounds. --normalize-round=1 is khmer's\n"
+                 "sequential rule; the result depends on the round size. --output, --histo, --save, --filter, --trim,\n"
+                 "--read-medians and --with then see the table of the kept reads; --load first normalizes on top of a saved\n"
+                 "table. Plain, .gz and BGZF input; --canonical, --acgt-only and --min-qual-char apply. One GPU, single-end; no\n"
+                 "--check, --min-count=2, --l=auto / --estimate or wrapped FASTA.\n"
                  "--trim writes the records of --trim-input (default: --input) cut to their solid stretch: a window is solid\n"
                  "when its count lies in trim-lower..trim-upper (default 2..unbounded); --trim-mode=longest keeps the longest run\n"
                  "of solid windows (the leftmost among equals), prefix the run that starts the read. Records that keep fewer\n"
@@ -767,6 +782,18 @@ int main(int argc, char *argv[]) {
         else if (opt(argv[i], "filter-median-lower", v)) { a.filter_median_lower = strtoull(v.c_str(), nullptr, 10); a.filter_median = true; }
         else if (opt(argv[i], "filter-median-upper", v)) { a.filter_median_upper = strtoull(v.c_str(), nullptr, 10); a.filter_median = true; }
         else if (opt(argv[i], "read-medians", v)) { a.read_medians = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "normalize", v)) { a.normalize = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "normalize-cutoff", v) || opt(argv[i], "normalize-round", v)) {
+            char *end = nullptr;
+            const unsigned long long x = strtoull(v.c_str(), &end, 10);
+            const bool round = std::string(argv[i]).compare(0, 17, "--normalize-round") == 0;
+            if (v.empty() || *end || v[0] == '-' || (round && x == 0)) {
+                std::cerr << (round ? "--normalize-round takes a number of records, 1 or more" : "--normalize-cutoff takes a count, 0 or more") << std::endl;
+                return usage();
+            }
+            (round ? a.normalize_round : a.normalize_cutoff) = x;
+            a.normalize_opts = true;
+        }
         else if (opt(argv[i], "filter-invert", v)) a.filter_invert = true;
         else if (opt(argv[i], "trim", v)) { a.trim = v; if (v.empty()) return usage(); }
         else if (opt(argv[i], "trim-spans", v)) { a.trim_spans = v; if (v.empty()) return usage(); }
@@ -794,6 +821,24 @@ int main(int argc, char *argv[]) {
         else if (argv[i][0] == '-') { std::cerr << "unknown option " << argv[i] << std::endl; return usage(); }
     }
     std::transform(a.mode.begin(), a.mode.end(), a.mode.begin(), ::toupper);
+    if (!a.normalize.empty() || a.normalize_opts) {   // what the normalization refuses, before anything is read
+        std::string why;
+        if (a.normalize.empty()) why = "--normalize-cutoff and --normalize-round need --normalize=OUT";
+        else if (a.input_path.empty()) why = "--normalize needs --input=FILE: it counts the input's reads while it picks them";
+        else if (a.check) why = "--normalize does not go with --check: the reference's count file holds the k-mers of every read";
+        else if (a.gpus > 1) why = "--normalize runs on one GPU only: a read is judged against the reads kept before it, and each GPU of a --gpus " + std::to_string(a.gpus) + " run sees a share of them";
+        else if (a.min_count == 2) why = "--normalize does not go with --min-count=2: normalization inserts by the atomic path, without the prefilter";
+        else if (a.l_auto || a.estimate) why = "--normalize does not go with --l=auto or --estimate: the sketch sizes the table for the k-mers of every read, not of the kept ones";
+        else if (is_wrapped(a)) why = "--normalize does not read --format=fasta-wrapped: a wrapped record has no single sequence line to judge";
+        else if (a.input_path.find(',') != std::string::npos || a.filter_interleaved || a.trim_interleaved ||
+                 a.filter_input.find(',') != std::string::npos || a.trim_input.find(',') != std::string::npos)
+            why = "--normalize does not go with paired options (two files in --input, --filter-input or --trim-input, or an interleaved one): mates are not judged together yet";
+        if (!why.empty()) {
+            std::cerr << why << std::endl;
+            return usage();
+        }
+        a.group = false;   // --gpus=1: the one table of this process
+    }
     if (a.l_auto || a.estimate) {   // what the table sizing refuses, before anything is read
         const std::string o = a.estimate ? "--estimate" : "--l=auto";
         std::string why;
@@ -1073,6 +1118,25 @@ int main(int argc, char *argv[]) {
         }
         if (a.input_path.empty()) {
             // nothing to count: the loaded tables are the result
+        } else if (!a.normalize.empty()) {
+            if (bgzf) {   // inflated on the device, as the read queries read a BGZF file
+                size_t members = 0, tb = 0, got = 0;
+                int rc = tsx_hip_bgzf_index_host(text, n, &members, &tb);
+                std::vector<char> inflated(tb ? tb : 1);
+                if (rc == TSX_HIP_OK) rc = tsx_hip_inflate_bgzf_host(a.device, text, n, inflated.data(), tb, &got);
+                if (rc != TSX_HIP_OK) throw TSXException(std::string(tsx_hip_strerror(rc)) + " (" + tsx_hip_last_error() + ")", rc);
+                munmap(map, n);
+                map = nullptr;
+                owned.swap(inflated);
+                owned.resize(got);
+                text = owned.data();
+                n = got;
+            }
+            const tsx_hip_normalize_totals nt = oMap.normalizeReads(text, n, a.normalize_cutoff, a.normalize_round, a.normalize);
+            std::cout << "normalize\t" << nt.records << '\t' << nt.kept << '\t' << nt.kmers_seen << '\t' << nt.kmers_added << '\t'
+                      << nt.rounds << std::endl;
+            std::cerr << "Normalization kept " << nt.kept << " of " << nt.records << " records (cutoff " << a.normalize_cutoff
+                      << ", rounds of " << a.normalize_round << ") in " << a.normalize << std::endl;
         } else if (bgzf) {
             try {
                 if (wrapped) oMap.countFastaBgzf(text, n);
