@@ -8,6 +8,7 @@ import ctypes
 import os
 import subprocess
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -245,15 +246,58 @@ def test_error_returns_release_what_they_hold(T, probe, text, want, monkeypatch,
         rule = T.filter_rule(1, None, 0, 1.0, False)
         return lib.tsx_hip_filter_reads_host(m.handle, text, len(text), ctypes.byref(rule), ro, 100000, None, None)
 
+    def save_ro():                                               # fails at the header, before any staging
+        return lib.tsx_hip_save_host(m.handle, ro, DB_CHUNK, None, None)
+
+    def reader_gone(write, nbytes):
+        """write(fd) into a pipe whose reader takes exactly nbytes and closes: the next write(2) fails with EPIPE (Python
+        leaves SIGPIPE ignored; the ctypes call releases the GIL, so the reader runs)."""
+        def f():
+            r, w = os.pipe()
+
+            def read():
+                left = nbytes
+                while left:
+                    got = os.read(r, min(left, 1 << 20))
+                    if not got:
+                        break
+                    left -= len(got)
+                os.close(r)
+            t = threading.Thread(target=read)
+            t.start()
+            try:
+                return write(w)
+            finally:
+                os.close(w)
+                t.join()
+        return f
+
+    # the first chunk is out and a later one queued on the device when the write fails
+    save_gone = reader_gone(lambda w: lib.tsx_hip_save_host(m.handle, w, DB_CHUNK, None, None), second)
+    write_gone = reader_gone(lambda w: lib.tsx_hip_write_counts_host(m.handle, w, 1, (1 << 64) - 1, WRITE_CHUNK, None, None),
+                             WRITE_CHUNK // 2)
+
+    monkeypatch.setenv("TSX_HIP_COMBINE_PATH", "1")              # the staged path, in chunks of 256 slots
+    monkeypatch.setenv("TSX_HIP_COMBINE_CHUNK_BYTES", "4096")
+    small = T.TSXHashMapHIP(8, 0, K, hash_seed=1)
+    union = T.combine_rule("union", "max")
+
+    def combine_small():
+        small.clear()
+        return lib.tsx_hip_combine(small.handle, m.handle, m.handle, ctypes.byref(union), None)
+
     cases = [("write_counts, read-only fd", write_ro, T.EIO), ("load, truncated", load(cut), T.EFORMAT),
              ("load, flipped byte", load(flip), T.EFORMAT), ("unwrap, short buffer", unwrap_short, T.ERANGE),
-             ("bgzf, damaged member", bgzf_damaged, T.EINVAL), ("filter, read-only fd", filter_ro, T.EIO)]
+             ("bgzf, damaged member", bgzf_damaged, T.EINVAL), ("filter, read-only fd", filter_ro, T.EIO),
+             ("save, read-only fd", save_ro, T.EIO), ("save, reader gone", save_gone, T.EIO),
+             ("write_counts, reader gone", write_gone, T.EIO), ("combine, out too small", combine_small, T.EFULL)]
     for name, call, code in cases:
         call()                                                  # (scratch the call leaves with a map grows here)
         before = counters(T, probe)
         assert call() == code, name
         assert counters(T, probe) == before, name
     os.close(ro)
+    small.close()
     for x in (m, other):                                        # still counting correctly
         x.clear()
         x.countFastq(text)

@@ -3221,8 +3221,59 @@ static int write_all(int fd, const uint8_t *p, size_t n) {
     return TSX_HIP_OK;
 }
 
-// The table as text, chunk by chunk: a chunk is floor(chunk_bytes / line_max) slots, so its text always fits.  Two device
-// and two pinned host buffers: the device formats chunk i + 1 while chunk i is written to fd.
+// The table written in chunks of `per` slots, one chunk ahead: the device makes chunk i + 1 while the host writes chunk i.
+// Two device and two pinned payload buffers (the second pair only when a second chunk exists), the device words a chunk's
+// making needs (its two result words among them) and the pinned mirror of those two.  Stream order:
+//   make(0) res(0) | payload(0) make(1) res(1) | payload(1) make(2) res(2) | ...
+struct ChunkAhead {
+    struct Range { size_t at, n; };   // bytes of a payload buffer
+    const uint64_t slots, per;
+    DevBuf<uint8_t> dev[2];
+    PinBuf<uint8_t> host[2];
+    DevBuf<unsigned long long> dev_res;
+    PinBuf<unsigned long long> host_res;
+    Event res_ready, payload_ready;
+    SyncAtExit wait;   // nothing queued may outlive the buffers
+    ChunkAhead(hipStream_t st, uint64_t slots_, uint64_t per_) : slots(slots_), per(per_), wait(st) {}
+
+    int init(size_t buf, size_t dev_words) {
+        if (dev_res.alloc(dev_words * 8) != TSX_HIP_OK || host_res.alloc(2 * 8) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+        for (int b = 0; b < (slots > per ? 2 : 1); ++b)
+            if (dev[b].alloc(buf) != TSX_HIP_OK || host[b].alloc(buf) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+        if (res_ready.create() != TSX_HIP_OK || payload_ready.create() != TSX_HIP_OK) return TSX_HIP_EHIP;
+        return TSX_HIP_OK;
+    }
+    // For the chunk of slots [lo, hi), each returning a TSX_HIP_* code (the first that is not OK ends the run and is returned):
+    // make(lo, hi, payload, words, mirror)  queues it into the device payload buffer and its two result words into the mirror
+    // fetch(lo, hi, res, ranges)            checks its result words and names the (at most two) ranges to copy back
+    // emit(lo, hi, res, payload, ranges)    writes it from the host payload buffer, once the copy has landed
+    template <typename Make, typename Fetch, typename Emit>
+    int run(Make make, Fetch fetch, Emit emit) {
+        const hipStream_t st = wait.st;
+        auto queue = [&](uint64_t lo, uint8_t *payload) -> int {
+            TSX_TRY(make(lo, std::min(slots, lo + per), payload, dev_res.get(), host_res.get()));
+            HIP_TRY(hipEventRecord(res_ready.get(), st));
+            return TSX_HIP_OK;
+        };
+        TSX_TRY(queue(0, dev[0].get()));
+        for (uint64_t lo = 0, b = 0; lo < slots; lo += per, b ^= 1) {
+            const uint64_t hi = std::min(slots, lo + per);
+            HIP_TRY(hipEventSynchronize(res_ready.get()));
+            const unsigned long long res[2] = {host_res.get()[0], host_res.get()[1]};   // (the next chunk's overwrite the mirror)
+            Range r[2] = {{0, 0}, {0, 0}};
+            TSX_TRY(fetch(lo, hi, res, r));
+            for (const Range &x : r)
+                if (x.n) HIP_TRY(hipMemcpyAsync(host[b].get() + x.at, dev[b].get() + x.at, x.n, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipEventRecord(payload_ready.get(), st));
+            if (hi < slots) TSX_TRY(queue(hi, dev[b ^ 1].get()));
+            HIP_TRY(hipEventSynchronize(payload_ready.get()));
+            TSX_TRY(emit(lo, hi, res, host[b].get(), r));
+        }
+        return TSX_HIP_OK;
+    }
+};
+
+// The table as text: a chunk is floor(chunk_bytes / line_max) slots, so its text always fits.
 extern "C" int tsx_hip_write_counts_host(tsx_hip_map *m, int fd, uint64_t lower, uint64_t upper, size_t chunk_bytes,
                                          uint64_t *lines_out, uint64_t *bytes_out) {
     if (lines_out) *lines_out = 0;
@@ -3230,51 +3281,30 @@ extern "C" int tsx_hip_write_counts_host(tsx_hip_map *m, int fd, uint64_t lower,
     if (!m || fd < 0 || lower > upper || (chunk_bytes && chunk_bytes < line_max(m))) return TSX_HIP_EINVAL;
     if (!chunk_bytes) chunk_bytes = WRITE_CHUNK_DEFAULT;
     const uint64_t slots = m->lay.slots, per = chunk_bytes / line_max(m);
-    const uint64_t nchunks = (slots + per - 1) / per;
     const size_t buf = (size_t)std::min<uint64_t>(per, slots) * line_max(m);
-    const int nbuf = nchunks > 1 ? 2 : 1;
     HIP_TRY(hipSetDevice(m->device));
     join_foreign(m, false);
     hipStream_t st = m->stream.get();
-    int rc = ensure_zeroed(m, st);
-    if (rc != TSX_HIP_OK) return rc;
-    DevBuf<uint8_t> dev_text[2];
-    PinBuf<uint8_t> host_text[2];
-    DevBuf<unsigned long long> dev_cnt;
-    PinBuf<unsigned long long> host_cnt;
-    Event cnt_ready, txt_ready;
-    SyncAtExit wait(st);   // nothing queued may outlive the buffers
-    if (dev_cnt.alloc(2 * sizeof(unsigned long long)) != TSX_HIP_OK || host_cnt.alloc(2 * sizeof(unsigned long long)) != TSX_HIP_OK)
-        return TSX_HIP_ENOMEM;
-    for (int b = 0; b < nbuf; ++b)   // (the second pair only when a second chunk exists)
-        if (dev_text[b].alloc(buf) != TSX_HIP_OK || host_text[b].alloc(buf) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
-    if (cnt_ready.create() != TSX_HIP_OK || txt_ready.create() != TSX_HIP_OK) return TSX_HIP_EHIP;
-    uint8_t *const d_text[2] = {dev_text[0].get(), dev_text[1].get()}, *const h_text[2] = {host_text[0].get(), host_text[1].get()};
-    unsigned long long *const d_cnt = dev_cnt.get(), *const h_cnt = host_cnt.get();
-    const hipEvent_t ev_cnt = cnt_ready.get(), ev_txt = txt_ready.get();
-    // stream order: fmt(0) cnt(0) | txt(0) fmt(1) cnt(1) | txt(1) fmt(2) cnt(2) | ...
-    auto queue_chunk = [&](uint64_t i) {
-        const uint64_t lo = i * per, hi = std::min(slots, lo + per);
-        int r = format_launch(m, lo, hi, lower, upper, d_text[i & 1], buf, d_cnt, d_cnt + 1, st);
-        if (r == TSX_HIP_OK && (hipMemcpyAsync(h_cnt, d_cnt, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                                hipEventRecord(ev_cnt, st) != hipSuccess))
-            r = TSX_HIP_EHIP;
-        return r;
-    };
+    TSX_TRY(ensure_zeroed(m, st));
+    ChunkAhead ahead(st, slots, per);
+    TSX_TRY(ahead.init(buf, 2));
     uint64_t lines = 0, bytes = 0;
-    if (rc == TSX_HIP_OK) rc = queue_chunk(0);
-    for (uint64_t i = 0; i < nchunks && rc == TSX_HIP_OK; ++i) {
-        const int b = (int)(i & 1);
-        if (hipEventSynchronize(ev_cnt) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        const uint64_t nb = h_cnt[0], nl = h_cnt[1];
-        if (nb > buf) { rc = TSX_HIP_ERANGE; break; }   // cannot happen: a chunk's text fits by construction
-        if ((nb && hipMemcpyAsync(h_text[b], d_text[b], nb, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-            hipEventRecord(ev_txt, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        if (i + 1 < nchunks && (rc = queue_chunk(i + 1)) != TSX_HIP_OK) break;
-        if (hipEventSynchronize(ev_txt) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        rc = write_all(fd, h_text[b], nb);
-        if (rc == TSX_HIP_OK) { lines += nl; bytes += nb; }
-    }
+    const int rc = ahead.run(
+        [&](uint64_t lo, uint64_t hi, uint8_t *d_text, unsigned long long *d_cnt, unsigned long long *h_cnt) -> int {
+            TSX_TRY(format_launch(m, lo, hi, lower, upper, d_text, buf, d_cnt, d_cnt + 1, st));
+            HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, 2 * 8, hipMemcpyDeviceToHost, st));
+            return TSX_HIP_OK;
+        },
+        [&](uint64_t, uint64_t, const unsigned long long *cnt, ChunkAhead::Range *r) -> int {   // cnt: bytes, lines
+            if (cnt[0] > buf) return TSX_HIP_ERANGE;   // cannot happen: a chunk's text fits by construction
+            r[0].n = (size_t)cnt[0];
+            return TSX_HIP_OK;
+        },
+        [&](uint64_t, uint64_t, const unsigned long long *cnt, const uint8_t *text, const ChunkAhead::Range *) -> int {
+            TSX_TRY(write_all(fd, text, (size_t)cnt[0]));
+            bytes += cnt[0]; lines += cnt[1];
+            return TSX_HIP_OK;
+        });
     if (lines_out) *lines_out = lines;
     if (bytes_out) *bytes_out = bytes;
     return rc;
@@ -3333,36 +3363,24 @@ static int db_parse_header(const uint8_t *b, tsx_hip_db_info *out, uint64_t *car
     return TSX_HIP_OK;
 }
 
-// read(2) until n bytes are in or the file ends: the bytes read; -1 on an error (g_last_error says which).
-static ssize_t db_read(int fd, void *p, size_t n) {
+// read(2) -- or, with at >= 0, pread(2) from that offset, which leaves the file position alone -- until n bytes are in: a
+// file that ends before is EFORMAT ("truncated (<what>)"), an error of the call EIO (g_last_error says which).
+static int db_read_exact(int fd, void *p, size_t n, const char *what, off_t at = -1) {
     size_t got = 0;
     while (got < n) {
-        const ssize_t r = read(fd, (uint8_t *)p + got, n - got);
+        const ssize_t r = at < 0 ? read(fd, (uint8_t *)p + got, n - got) : pread(fd, (uint8_t *)p + got, n - got, at + (off_t)got);
         if (r < 0 && errno == EINTR) continue;
-        if (r < 0) { g_last_error = std::string("read: ") + strerror(errno); return -1; }
-        if (r == 0) break;
+        if (r < 0) { g_last_error = std::string(at < 0 ? "read: " : "pread: ") + strerror(errno); return TSX_HIP_EIO; }
+        if (r == 0) return db_fail(std::string("k-mer database truncated (") + what + ")");
         got += (size_t)r;
     }
-    return (ssize_t)got;
-}
-static int db_read_exact(int fd, void *p, size_t n, const char *what) {
-    const ssize_t r = db_read(fd, p, n);
-    if (r < 0) return TSX_HIP_EIO;
-    if ((size_t)r != n) return db_fail(std::string("k-mer database truncated (") + what + ")");
     return TSX_HIP_OK;
 }
 
 extern "C" int tsx_hip_db_read_info(int fd, tsx_hip_db_info *out) {
     if (fd < 0 || !out) return TSX_HIP_EINVAL;
     uint8_t b[DB_HEADER];
-    size_t got = 0;
-    while (got < DB_HEADER) {
-        const ssize_t r = pread(fd, b + got, DB_HEADER - got, (off_t)got);
-        if (r < 0 && errno == EINTR) continue;
-        if (r < 0) { g_last_error = std::string("pread: ") + strerror(errno); return TSX_HIP_EIO; }
-        if (r == 0) return db_fail("k-mer database truncated (header)");
-        got += (size_t)r;
-    }
+    TSX_TRY(db_read_exact(fd, b, DB_HEADER, "header", 0));
     return db_parse_header(b, out, nullptr);
 }
 
@@ -3373,113 +3391,103 @@ static uint64_t db_span(size_t chunk_bytes, int W) {
 }
 static inline uint64_t db_tiles(uint64_t lo, uint64_t hi) { return (hi - lo + DB_TILE - 1) / DB_TILE; }
 
+// The n carry records of the secondary array, sorted by slot (the file does not depend on the array's probe order).
+static int db_gather_carry(tsx_hip_map *m, uint64_t n, std::vector<uint64_t> &carry) {
+    const int RW = 2 + m->p.W;
+    carry.assign((size_t)n * RW, 0);
+    if (!n) return TSX_HIP_OK;
+    hipStream_t st = m->stream.get();
+    DevBuf<uint64_t> rec;
+    SyncAtExit wait(st);
+    TSX_TRY(rec.alloc(carry.size() * 8 + 8));
+    uint64_t *const d_rec = rec.get();
+    unsigned long long *const d_n = (unsigned long long *)(d_rec + carry.size());
+    unsigned long long h_n = 0;
+    HIP_TRY(hipMemsetAsync(d_n, 0, 8, st));
+    hipLaunchKernelGGL(db_carry_gather_kernel, dim3(grid_for(m, m->p.sec_mask + 1, 8)), dim3(NT), 0, st, m->p, d_rec, n, d_n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(carry.data(), d_rec, carry.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_n != n) { g_last_error = "secondary array changed during the save"; return TSX_HIP_EHIP; }
+    std::vector<uint64_t> order(n), sorted(carry.size());
+    for (uint64_t i = 0; i < n; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return carry[a * RW] < carry[b * RW]; });
+    for (uint64_t i = 0; i < n; ++i) memcpy(&sorted[i * RW], &carry[order[i] * RW], (size_t)RW * 8);
+    carry.swap(sorted);
+    return TSX_HIP_OK;
+}
+
+// What the header says of a map and its stats.
+static tsx_hip_db_info db_info_of(const tsx_hip_map *m, const tsx_hip_stats &s) {
+    tsx_hip_db_info info;
+    memset(&info, 0, sizeof info);
+    info.version = DB_VERSION; info.k = m->p.k; info.l = m->p.l; info.entry_limbs = m->p.W; info.func_bits = m->p.F;
+    info.reprobe_bits = m->p.R; info.count_bits = m->p.C; info.seg_bits = m->p.S; info.overflow_l = m->lay.overflow_l;
+    info.canonical = m->canon ? 1 : 0; info.acgt_only = m->p.acgt_only ? 1 : 0; info.min_qual_char = (int32_t)m->minq;
+    info.hash_seed = m->seed; info.kmers_added = s.kmers_added; info.distinct = s.distinct; info.count_sum = s.count_sum;
+    info.carry_records = s.overflow_used;
+    return info;
+}
+
+// The chunks of span slots each: head, bitmap, entries.  A payload buffer holds the bitmap of a full span, then the entries.
+static int db_write_chunks(tsx_hip_map *m, int fd, uint64_t span, uint64_t &entries, uint64_t &bytes) {
+    const int W = m->p.W;
+    const uint64_t ntmax = db_tiles(0, span);
+    hipStream_t st = m->stream.get();
+    ChunkAhead ahead(st, m->lay.slots, span);
+    TSX_TRY(ahead.init((size_t)(span / 64 + span * W) * 8, ntmax + 2));   // (device words: tile offsets, then the checksum)
+    return ahead.run(
+        [&](uint64_t lo, uint64_t hi, uint8_t *d_buf, unsigned long long *d_tile, unsigned long long *h_res) -> int {
+            const uint64_t nt = db_tiles(lo, hi);
+            uint64_t *bm = (uint64_t *)d_buf, *ent = bm + span / 64;
+            unsigned long long *const d_sum = d_tile + ntmax + 1;
+            HIP_TRY(hipMemsetAsync(d_sum, 0, 8, st));
+            hipLaunchKernelGGL(db_count_table_kernel, dim3((unsigned)nt), dim3(NT), 0, st, m->p, lo, hi, d_tile);
+            hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(NT), 0, st, d_tile, nt);
+            hipLaunchKernelGGL(db_pack_kernel, dim3((unsigned)nt), dim3(NT), 0, st, m->p, lo, hi, (const unsigned long long *)d_tile,
+                               bm, ent, span, d_sum);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(h_res, d_tile + nt, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(h_res + 1, d_sum, 8, hipMemcpyDeviceToHost, st));
+            return TSX_HIP_OK;
+        },
+        [&](uint64_t lo, uint64_t hi, const unsigned long long *res, ChunkAhead::Range *r) -> int {   // res: entries, checksum
+            if (res[0] > hi - lo) return TSX_HIP_ERANGE;   // cannot happen: a tile counts at most its slots
+            r[0] = {0, (size_t)((hi - lo + 63) / 64) * 8};
+            r[1] = {(size_t)(span / 64) * 8, (size_t)res[0] * W * 8};
+            return TSX_HIP_OK;
+        },
+        [&](uint64_t lo, uint64_t hi, const unsigned long long *res, const uint8_t *h_buf, const ChunkAhead::Range *r) -> int {
+            const uint64_t ch[4] = {lo, hi, res[0], res[1]};
+            TSX_TRY(write_all(fd, (const uint8_t *)ch, DB_CHUNK_HEAD));
+            TSX_TRY(write_all(fd, h_buf + r[0].at, r[0].n));
+            TSX_TRY(write_all(fd, h_buf + r[1].at, r[1].n));
+            bytes += DB_CHUNK_HEAD + r[0].n + r[1].n;
+            entries += res[0];
+            return TSX_HIP_OK;
+        });
+}
+
 extern "C" int tsx_hip_save_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uint64_t *entries_out, uint64_t *bytes_out) {
     if (entries_out) *entries_out = 0;
     if (bytes_out) *bytes_out = 0;
     if (!m || fd < 0) return TSX_HIP_EINVAL;
     if (m->p.lg != m->p.l) { g_last_error = "a shard of a multi-GPU table is not saved"; return TSX_HIP_EINVAL; }
     if (!chunk_bytes) chunk_bytes = DB_CHUNK_DEFAULT;
-    const int W = m->p.W;
     const uint64_t slots = m->lay.slots;
-    const uint64_t span = std::min<uint64_t>(db_span(chunk_bytes, W), (slots + 63) & ~63ULL);
+    const uint64_t span = std::min<uint64_t>(db_span(chunk_bytes, m->p.W), (slots + 63) & ~63ULL);
     if (span == 0) return TSX_HIP_EINVAL;
     tsx_hip_stats s;
-    int rc = tsx_hip_get_stats(m, &s);   // (zeroes a lazily cleared table; waits for everything queued)
-    if (rc != TSX_HIP_OK) return rc;
-    hipStream_t st = m->stream.get();
-    // carry records, sorted by slot (the file does not depend on the secondary array's probe order)
-    const int RW = 2 + W;
-    std::vector<uint64_t> carry((size_t)s.overflow_used * RW);
-    if (s.overflow_used) {
-        DevBuf<uint64_t> rec;
-        TSX_TRY(rec.alloc(carry.size() * 8 + 8));
-        uint64_t *const d_rec = rec.get();
-        unsigned long long *const d_n = (unsigned long long *)(d_rec + carry.size());
-        unsigned long long h_n = 0;
-        rc = TSX_HIP_OK;
-        if (hipMemsetAsync(d_n, 0, 8, st) != hipSuccess) rc = TSX_HIP_EHIP;
-        if (rc == TSX_HIP_OK) {
-            hipLaunchKernelGGL(db_carry_gather_kernel, dim3(grid_for(m, m->p.sec_mask + 1, 8)), dim3(NT), 0, st, m->p, d_rec,
-                               (uint64_t)s.overflow_used, d_n);
-            if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(carry.data(), d_rec, carry.size() * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipMemcpyAsync(&h_n, d_n, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-                rc = TSX_HIP_EHIP;
-        }
-        if (rc != TSX_HIP_OK) return rc;
-        if (h_n != s.overflow_used) { g_last_error = "secondary array changed during the save"; return TSX_HIP_EHIP; }
-        std::vector<uint64_t> order(s.overflow_used), sorted(carry.size());
-        for (uint64_t i = 0; i < s.overflow_used; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return carry[a * RW] < carry[b * RW]; });
-        for (uint64_t i = 0; i < s.overflow_used; ++i) memcpy(&sorted[i * RW], &carry[order[i] * RW], (size_t)RW * 8);
-        carry.swap(sorted);
-    }
-    tsx_hip_db_info info;
-    memset(&info, 0, sizeof info);
-    info.version = DB_VERSION; info.k = m->p.k; info.l = m->p.l; info.entry_limbs = W; info.func_bits = m->p.F;
-    info.reprobe_bits = m->p.R; info.count_bits = m->p.C; info.seg_bits = m->p.S; info.overflow_l = m->lay.overflow_l;
-    info.canonical = m->canon ? 1 : 0; info.acgt_only = m->p.acgt_only ? 1 : 0; info.min_qual_char = (int32_t)m->minq;
-    info.hash_seed = m->seed; info.kmers_added = s.kmers_added; info.distinct = s.distinct; info.count_sum = s.count_sum;
-    info.carry_records = s.overflow_used;
+    TSX_TRY(tsx_hip_get_stats(m, &s));   // (zeroes a lazily cleared table; waits for everything queued)
+    std::vector<uint64_t> carry;
+    TSX_TRY(db_gather_carry(m, s.overflow_used, carry));
     uint8_t head[DB_HEADER];
-    db_header_bytes(info, db_fnv(carry.data(), carry.size() * 8), head);
-    uint64_t bytes = 0, entries = 0;
-    rc = write_all(fd, head, DB_HEADER);
-    if (rc == TSX_HIP_OK && !carry.empty()) rc = write_all(fd, (const uint8_t *)carry.data(), carry.size() * 8);
-    if (rc != TSX_HIP_OK) return rc;
-    bytes += DB_HEADER + carry.size() * 8;
-
-    // chunks: stream order  pack(0) res(0) | payload(0) pack(1) res(1) | payload(1) pack(2) ...  -- the device packs
-    // chunk i + 1 while the host writes chunk i (tsx_hip_write_counts_host does the same with text)
-    const uint64_t nchunks = (slots + span - 1) / span, ntmax = db_tiles(0, span);
-    const size_t buf = (size_t)(span / 64 + span * W) * 8;
-    const int nbuf = nchunks > 1 ? 2 : 1;
-    DevBuf<uint64_t> dev_buf[2];
-    PinBuf<uint64_t> host_buf[2];
-    DevBuf<unsigned long long> dev_tile;
-    PinBuf<unsigned long long> host_res;
-    Event res_ready, buf_ready;
-    if (dev_tile.alloc((ntmax + 2) * 8) != TSX_HIP_OK || host_res.alloc(2 * 8) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
-    for (int b = 0; b < nbuf && rc == TSX_HIP_OK; ++b)   // (the second pair only when a second chunk exists)
-        if (dev_buf[b].alloc(buf) != TSX_HIP_OK || host_buf[b].alloc(buf) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
-    if (rc == TSX_HIP_OK && (res_ready.create() != TSX_HIP_OK || buf_ready.create() != TSX_HIP_OK)) rc = TSX_HIP_EHIP;
-    uint64_t *const d_buf[2] = {dev_buf[0].get(), dev_buf[1].get()}, *const h_buf[2] = {host_buf[0].get(), host_buf[1].get()};
-    unsigned long long *const d_tile = dev_tile.get(), *const d_sum = d_tile ? d_tile + ntmax + 1 : nullptr, *const h_res = host_res.get();
-    const hipEvent_t ev_res = res_ready.get(), ev_buf = buf_ready.get();
-    auto queue_chunk = [&](uint64_t i) {
-        const uint64_t lo = i * span, hi = std::min(slots, lo + span), nt = db_tiles(lo, hi);
-        uint64_t *bm = d_buf[i & 1], *ent = bm + span / 64;
-        if (hipMemsetAsync(d_sum, 0, 8, st) != hipSuccess) return TSX_HIP_EHIP;
-        hipLaunchKernelGGL(db_count_table_kernel, dim3((unsigned)nt), dim3(NT), 0, st, m->p, lo, hi, d_tile);
-        hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(NT), 0, st, d_tile, nt);
-        hipLaunchKernelGGL(db_pack_kernel, dim3((unsigned)nt), dim3(NT), 0, st, m->p, lo, hi, (const unsigned long long *)d_tile,
-                           bm, ent, span, d_sum);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(h_res, d_tile + nt, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(h_res + 1, d_sum, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(ev_res, st) != hipSuccess)
-            return TSX_HIP_EHIP;
-        return TSX_HIP_OK;
-    };
-    if (rc == TSX_HIP_OK) rc = queue_chunk(0);
-    for (uint64_t i = 0; i < nchunks && rc == TSX_HIP_OK; ++i) {
-        const int b = (int)(i & 1);
-        const uint64_t lo = i * span, hi = std::min(slots, lo + span), nbm = (hi - lo + 63) / 64;
-        if (hipEventSynchronize(ev_res) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        const uint64_t n = h_res[0], sum = h_res[1];
-        if (n > hi - lo) { rc = TSX_HIP_ERANGE; break; }   // cannot happen: a tile counts at most its slots
-        const size_t bmb = (size_t)nbm * 8, entb = (size_t)n * W * 8;
-        if (hipMemcpyAsync(h_buf[b], d_buf[b], bmb, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            (entb && hipMemcpyAsync(h_buf[b] + span / 64, d_buf[b] + span / 64, entb, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-            hipEventRecord(ev_buf, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        if (i + 1 < nchunks && (rc = queue_chunk(i + 1)) != TSX_HIP_OK) break;
-        uint64_t ch[4] = {lo, hi, n, sum};
-        rc = write_all(fd, (const uint8_t *)ch, DB_CHUNK_HEAD);
-        if (hipEventSynchronize(ev_buf) != hipSuccess && rc == TSX_HIP_OK) rc = TSX_HIP_EHIP;
-        if (rc == TSX_HIP_OK) rc = write_all(fd, (const uint8_t *)h_buf[b], bmb);
-        if (rc == TSX_HIP_OK && entb) rc = write_all(fd, (const uint8_t *)(h_buf[b] + span / 64), entb);
-        if (rc == TSX_HIP_OK) { bytes += DB_CHUNK_HEAD + bmb + entb; entries += n; }
-    }
-    (void)hipStreamSynchronize(st);   // nothing queued may outlive the buffers
+    db_header_bytes(db_info_of(m, s), db_fnv(carry.data(), carry.size() * 8), head);
+    TSX_TRY(write_all(fd, head, DB_HEADER));
+    TSX_TRY(write_all(fd, (const uint8_t *)carry.data(), carry.size() * 8));
+    uint64_t bytes = DB_HEADER + carry.size() * 8, entries = 0;
+    int rc = db_write_chunks(m, fd, span, entries, bytes);
     if (rc == TSX_HIP_OK) {
         const uint64_t end[4] = {slots, slots, 0, 0};
         rc = write_all(fd, (const uint8_t *)end, DB_CHUNK_HEAD);
@@ -3529,175 +3537,228 @@ static int db_source_params(const tsx_hip_db_info &d, TableParams &sp, DevBuf<ui
     return TSX_HIP_OK;
 }
 
+// The header of the file at fd, and whether map m can take its k-mers at all.
+static int db_read_header(const tsx_hip_map *m, int fd, tsx_hip_db_info *d, uint64_t *carry_sum) {
+    uint8_t head[DB_HEADER];
+    TSX_TRY(db_read_exact(fd, head, DB_HEADER, "header"));
+    TSX_TRY(db_parse_header(head, d, carry_sum));
+    if (d->k != m->p.k || d->canonical != (m->canon ? 1 : 0) || d->acgt_only != (m->p.acgt_only ? 1 : 0) ||
+        d->min_qual_char != (int)m->minq) {
+        g_last_error = "the database was counted with a different k, canonical mode or base rule than this table";
+        return TSX_HIP_EINVAL;
+    }
+    return TSX_HIP_OK;
+}
+
+// Host only: the carry records from *next on with a slot below hi (they are sorted by slot, so a chunk's come in order)
+// against chunk [lo, hi) of n entries, hbm its bitmap and hent its entries of W words.  Slot pos must be occupied and hold
+// the record's words; a popcount of the bitmap up to pos gives the entry's index.  In-slot counts of 0 are counted into
+// *zero_carried and compared with the device's count of them (DbLoad::finish), so that no entry's total count is 0.
+static int db_match_carry(const uint64_t *rec, uint64_t nrec, uint64_t *next, int W, int cshift, uint64_t lo, uint64_t hi,
+                          uint64_t n, const uint64_t *hbm, const uint64_t *hent, uint64_t *zero_carried) {
+    const int RW = 2 + W;
+    uint64_t w = 0, before = 0;   // set bits of the words before w
+    *zero_carried = 0;
+    for (; *next < nrec && rec[*next * RW] < hi; ++*next) {
+        const uint64_t *r = &rec[*next * RW];
+        const uint64_t off = r[0] - lo, wc = off >> 6;
+        for (; w < wc; ++w) before += (uint64_t)__builtin_popcountll(hbm[w]);
+        const uint64_t bit = 1ULL << (off & 63);
+        const uint64_t idx = before + (uint64_t)__builtin_popcountll(hbm[wc] & (bit - 1ULL));
+        if (!(hbm[wc] & bit) || idx >= n || memcmp(&hent[idx * W], r + 2, (size_t)W * 8) != 0)
+            return db_fail("k-mer database: a carry record does not match the entry at its slot");
+        *zero_carried += (hent[idx * W] >> cshift) == 0 ? 1 : 0;
+    }
+    return TSX_HIP_OK;
+}
+
+// One load, step by step (tsx_hip_load_host calls them in order).  A step that fails returns at once: the stages left
+// busy are waited for (the wait is declared behind every owner), not inspected.  The map is left as the steps before
+// left it -- used, not fresh, a table placed in part -- and clear recovers it.
+struct DbLoad {
+    tsx_hip_map *const m;
+    const int fd;
+    const tsx_hip_db_info d;
+    const uint64_t carry_sum;
+    const size_t chunk_bytes;
+    const hipStream_t st;
+    // placed as it is, slot by slot: an empty table of the database's geometry and seed.  Else every k-mer is re-inserted.
+    const bool direct;
+    const int W, RW, WK;
+    const uint64_t slots;
+    TableParams sp;                      // the database's layout (the table's own when direct)
+    unsigned long long kmers_before = 0;
+    std::vector<uint64_t> rec;           // the carry records: each is checked against the chunk that holds its pos
+    uint64_t next_carry = 0, expect_lo = 0, entries = 0;
+    DevBuf<uint64_t> d_ilut, carry;
+    DbStage sg[2];
+    SyncAtExit wait;
+
+    DbLoad(tsx_hip_map *m_, int fd_, const tsx_hip_db_info &d_, uint64_t carry_sum_, size_t chunk_bytes_)
+        : m(m_), fd(fd_), d(d_), carry_sum(carry_sum_), chunk_bytes(chunk_bytes_), st(m_->stream.get()),
+          direct(!m_->used && d_.l == m_->p.l && d_.entry_limbs == m_->p.W && d_.func_bits == m_->p.F &&
+                 d_.reprobe_bits == m_->p.R && d_.count_bits == m_->p.C && d_.seg_bits == m_->p.S && d_.hash_seed == m_->seed),
+          W(d_.entry_limbs), RW(2 + d_.entry_limbs), WK(m_->p.wk), slots(1ULL << d_.l), wait(m_->stream.get()) {}
+
+    int begin() {
+        TSX_TRY(db_source_params(d, sp, direct ? nullptr : &d_ilut));
+        // the table: a direct load writes every slot, so a lazily cleared table needs no memset
+        if (direct) { sp = m->p; m->fresh = false; }
+        else TSX_TRY(ensure_zeroed(m, st));
+        m->used = true;
+        HIP_TRY(hipMemcpyAsync(&kmers_before, m->p.stats + ST_KMERS, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return TSX_HIP_OK;
+    }
+
+    // Read, checksum, every record sane and the slots ascending; then uploaded and placed or re-inserted.
+    int carry_section() {
+        if (!d.carry_records) return TSX_HIP_OK;
+        rec.resize((size_t)d.carry_records * RW);
+        TSX_TRY(db_read_exact(fd, rec.data(), rec.size() * 8, "carry records"));
+        if (db_fnv(rec.data(), rec.size() * 8) != carry_sum) return db_fail("k-mer database carry records checksum mismatch");
+        for (uint64_t i = 0; i < d.carry_records; ++i) {
+            const uint64_t *r = &rec[i * RW];
+            const uint64_t rp = r[2] & ((1ULL << sp.R) - 1ULL);
+            if (r[0] >= slots || r[1] == 0 || r[2] == 0 || rp == 0 || rp > sp.max_reprobes || (r[2] & sp.lock_bit))
+                return db_fail("k-mer database: malformed carry record");
+            if (i > 0 && r[0] <= r[-RW]) return db_fail("k-mer database: carry records not sorted by slot or not unique");
+        }
+        const size_t kx = direct ? 0 : (size_t)d.carry_records * (WK + 1);
+        if (carry.alloc((rec.size() + kx) * 8) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+        uint64_t *const d_carry = carry.get();
+        HIP_TRY(hipMemcpyAsync(d_carry, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, st));
+        const int grid = grid_for(m, d.carry_records, 8);
+        uint64_t *kx_k = d_carry + rec.size(), *kx_c = kx_k + (size_t)d.carry_records * WK;
+        if (direct) {
+            hipLaunchKernelGGL((db_carry_kernel<true, 1>), dim3(grid), dim3(NT), 0, st, m->p, sp, (const uint64_t *)d_carry,
+                               (uint64_t)d.carry_records, (uint64_t *)nullptr, (uint64_t *)nullptr);
+        } else {
+            DISPATCH_WK(m, hipLaunchKernelGGL((db_carry_kernel<false, WKV>), dim3(grid), dim3(NT), 0, st, m->p, sp,
+                                              (const uint64_t *)d_carry, (uint64_t)d.carry_records, kx_k, kx_c));
+        }
+        HIP_TRY(hipGetLastError());
+        if (!direct) TSX_TRY(tsx_hip_add_kmers_device(m, kx_k, kx_c, (size_t)d.carry_records, nullptr));
+        HIP_TRY(hipStreamSynchronize(st));
+        return TSX_HIP_OK;
+    }
+
+    // The next chunk head ch = {lo, hi, entries, checksum}: the chunks tile the table in order, the end marker closes it.
+    int chunk_head(uint64_t *ch) {
+        TSX_TRY(db_read_exact(fd, ch, DB_CHUNK_HEAD, "no end marker"));
+        const uint64_t lo = ch[0], hi = ch[1], n = ch[2];
+        if (lo != expect_lo || hi > slots || (lo == hi && (lo != slots || n != 0)) || n > hi - lo || ((hi - lo) & 63 && hi != slots))
+            return db_fail("k-mer database: chunks do not tile the table");
+        expect_lo = hi;
+        return TSX_HIP_OK;
+    }
+
+    // The chunk behind head ch into an idle stage: room for it, its bytes from the file, its carry records matched.
+    int read_chunk(DbStage &s, const uint64_t *ch) {
+        const uint64_t lo = ch[0], hi = ch[1], n = ch[2];
+        const uint64_t nbm = (hi - lo + 63) / 64, nt = db_tiles(lo, hi);
+        const size_t bytes = (size_t)(nbm + n * W) * 8;
+        // grow-only; chunk_bytes is the first size.  (No wait: s.done has been waited for, nothing reads the stage.)
+        const size_t want = std::max(bytes, std::min(chunk_bytes, (size_t)(slots / 64 + slots * W) * 8));
+        if (bytes > s.d.cap()) s.h.reset();   // (both or none: d is allocated last)
+        if (s.h.reserve(nullptr, bytes, want) != TSX_HIP_OK || s.d.reserve(nullptr, bytes, want) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+        TSX_TRY(s.d_tile.reserve(nullptr, (nt + 1) * 8, (nt + 1) * 8));
+        const size_t kxb = (size_t)std::max<uint64_t>(1, n) * (WK + 1) * 8;
+        if (!direct) TSX_TRY(s.d_kx.reserve(nullptr, kxb, kxb));
+        TSX_TRY(db_read_exact(fd, s.h.get(), bytes, "chunk"));
+        s.n = n; s.sum = ch[3];
+        const uint64_t *hbm = (const uint64_t *)s.h.get();
+        return db_match_carry(rec.data(), d.carry_records, &next_carry, W, sp.cshift, lo, hi, n, hbm, hbm + nbm, &s.zero_carried);
+    }
+
+    // Queue the staged chunk [lo, hi): copy, entries per tile counted and scanned, entries placed or turned into k-mers
+    // and re-inserted, the result words back.
+    int queue_chunk(DbStage &s, uint64_t lo, uint64_t hi) {
+        const uint64_t n = s.n, nbm = (hi - lo + 63) / 64, nt = db_tiles(lo, hi);
+        const uint64_t *bm = (const uint64_t *)s.d.get(), *ent = bm + nbm;
+        uint64_t *kx_k = s.d_kx.get(), *kx_c = kx_k ? kx_k + n * WK : nullptr;
+        unsigned long long *const s_tile = s.d_tile.get(), *const s_res = s.d_res.get();
+        const unsigned nb = (unsigned)((nt + NT / 64 - 1) / (NT / 64));
+        HIP_TRY(hipMemcpyAsync(s.d.get(), s.h.get(), (size_t)(nbm + n * W) * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(s_res, 0, DB_RES_N * 8, st));
+        hipLaunchKernelGGL(db_count_bitmap_kernel, dim3(nb), dim3(NT), 0, st, bm, nbm, nt, s_tile);
+        hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(NT), 0, st, s_tile, nt);
+        if (direct) {
+            hipLaunchKernelGGL((db_load_kernel<true, 1>), dim3((unsigned)nt), dim3(NT), 0, st, m->p, sp, lo, hi, bm, ent, n,
+                               (const unsigned long long *)s_tile, (uint64_t *)nullptr, (uint64_t *)nullptr, s_res);
+        } else {
+            DISPATCH_WK(m, hipLaunchKernelGGL((db_load_kernel<false, WKV>), dim3((unsigned)nt), dim3(NT), 0, st, m->p, sp, lo, hi,
+                                              bm, ent, n, (const unsigned long long *)s_tile, kx_k, kx_c, s_res));
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(s_res + DB_RES_TOTAL, s_tile + nt, 8, hipMemcpyDeviceToDevice, st));
+        if (!direct && n) TSX_TRY(tsx_hip_add_kmers_device(m, kx_k, kx_c, (size_t)n, nullptr));
+        HIP_TRY(hipMemcpyAsync(s.h_res.get(), s_res, DB_RES_N * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(s.done.get(), st));
+        s.busy = true;
+        return TSX_HIP_OK;
+    }
+
+    // The result of a chunk whose work has finished.
+    int finish(DbStage &s) {
+        s.busy = false;
+        const unsigned long long *res = s.h_res.get();
+        if (res[DB_RES_TOTAL] != s.n) return db_fail("k-mer database chunk: bitmap and entry count disagree");
+        if (res[DB_RES_BAD]) return db_fail("k-mer database chunk: malformed entries");
+        if (res[DB_RES_SUM] != s.sum) return db_fail("k-mer database chunk checksum mismatch");
+        if (res[DB_RES_ZERO] != s.zero_carried) return db_fail("k-mer database chunk: an entry with count 0");
+        entries += s.n;
+        return TSX_HIP_OK;
+    }
+
+    // Chunk by chunk up to the end marker: the host reads chunk i + 1 while the device places chunk i.
+    int chunks() {
+        for (DbStage &s : sg)
+            if (s.done.create() != TSX_HIP_OK || s.d_res.alloc(DB_RES_N * 8) != TSX_HIP_OK || s.h_res.alloc(DB_RES_N * 8) != TSX_HIP_OK)
+                return TSX_HIP_ENOMEM;
+        for (uint64_t i = 0;; ++i) {
+            DbStage &s = sg[i & 1];
+            if (s.busy) {
+                HIP_TRY(hipEventSynchronize(s.done.get()));
+                TSX_TRY(finish(s));
+            }
+            uint64_t ch[4];
+            TSX_TRY(chunk_head(ch));
+            if (ch[0] == slots) break;
+            TSX_TRY(read_chunk(s, ch));
+            TSX_TRY(queue_chunk(s, ch[0], ch[1]));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+        for (DbStage &s : sg)
+            if (s.busy) TSX_TRY(finish(s));
+        return TSX_HIP_OK;
+    }
+
+    int end() {
+        if (entries != d.distinct) return db_fail("k-mer database: entry count differs from the header");
+        // kmers_added grows by the database's (the re-insert has added the sum of the counts instead)
+        const unsigned long long ka = kmers_before + d.kmers_added;
+        HIP_TRY(hipMemcpyAsync(m->p.stats + ST_KMERS, &ka, 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return tsx_hip_sync(m);
+    }
+};
+
 extern "C" int tsx_hip_load_host(tsx_hip_map *m, int fd, size_t chunk_bytes, uint64_t *entries_out) {
     if (entries_out) *entries_out = 0;
     if (!m || fd < 0) return TSX_HIP_EINVAL;
     if (m->p.lg != m->p.l) { g_last_error = "a shard of a multi-GPU table does not load a database"; return TSX_HIP_EINVAL; }
-    if (!chunk_bytes) chunk_bytes = DB_CHUNK_DEFAULT;
-    uint8_t head[DB_HEADER];
-    int rc = db_read_exact(fd, head, DB_HEADER, "header");
     tsx_hip_db_info d;
     uint64_t carry_sum = 0;
-    if (rc == TSX_HIP_OK) rc = db_parse_header(head, &d, &carry_sum);
-    if (rc != TSX_HIP_OK) return rc;
-    if (d.k != m->p.k || d.canonical != (m->canon ? 1 : 0) || d.acgt_only != (m->p.acgt_only ? 1 : 0) ||
-        d.min_qual_char != (int)m->minq) {
-        g_last_error = "the database was counted with a different k, canonical mode or base rule than this table";
-        return TSX_HIP_EINVAL;
-    }
+    TSX_TRY(db_read_header(m, fd, &d, &carry_sum));
     HIP_TRY(hipSetDevice(m->device));
     join_foreign(m, false);
-    hipStream_t st = m->stream.get();
-    TableParams sp;
-    DevBuf<uint64_t> d_ilut;
-    const bool direct = !m->used && d.l == m->p.l && d.entry_limbs == m->p.W && d.func_bits == m->p.F &&
-                        d.reprobe_bits == m->p.R && d.count_bits == m->p.C && d.seg_bits == m->p.S && d.hash_seed == m->seed;
-    rc = db_source_params(d, sp, direct ? nullptr : &d_ilut);
-    if (rc != TSX_HIP_OK) return rc;
-    if (direct) sp = m->p;
-    const int W = d.entry_limbs, RW = 2 + W, WK = m->p.wk;
-    const uint64_t slots = 1ULL << d.l;
-    unsigned long long kmers_before = 0;
-    DbStage sg[2];
-    DevBuf<uint64_t> carry;
-    uint64_t *d_carry = nullptr;
-    std::vector<uint64_t> rec;   // the carry records: each is checked against the chunk that holds its pos
-    uint64_t entries = 0;
-    do {
-        // the table: a direct load writes every slot, so a lazily cleared table needs no memset
-        if (direct) m->fresh = false;
-        else if ((rc = ensure_zeroed(m, st)) != TSX_HIP_OK) break;
-        m->used = true;
-        if (hipMemcpyAsync(&kmers_before, m->p.stats + ST_KMERS, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        // carry section
-        if (d.carry_records) {
-            rec.resize((size_t)d.carry_records * RW);
-            if ((rc = db_read_exact(fd, rec.data(), rec.size() * 8, "carry records")) != TSX_HIP_OK) break;
-            if (db_fnv(rec.data(), rec.size() * 8) != carry_sum) { rc = db_fail("k-mer database carry records checksum mismatch"); break; }
-            for (uint64_t i = 0; i < d.carry_records && rc == TSX_HIP_OK; ++i) {
-                const uint64_t *r = &rec[i * RW];
-                const uint64_t rp = r[2] & ((1ULL << sp.R) - 1ULL);
-                if (r[0] >= slots || r[1] == 0 || r[2] == 0 || rp == 0 || rp > sp.max_reprobes || (r[2] & sp.lock_bit))
-                    rc = db_fail("k-mer database: malformed carry record");
-                else if (i > 0 && r[0] <= r[-RW])
-                    rc = db_fail("k-mer database: carry records not sorted by slot or not unique");
-            }
-            if (rc != TSX_HIP_OK) break;
-            const size_t kx = direct ? 0 : (size_t)d.carry_records * (WK + 1);
-            if (carry.alloc((rec.size() + kx) * 8) != TSX_HIP_OK) { rc = TSX_HIP_ENOMEM; break; }
-            d_carry = carry.get();
-            if (hipMemcpyAsync(d_carry, rec.data(), rec.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            const int grid = grid_for(m, d.carry_records, 8);
-            uint64_t *kx_k = d_carry + rec.size(), *kx_c = kx_k + (size_t)d.carry_records * WK;
-            if (direct) {
-                hipLaunchKernelGGL((db_carry_kernel<true, 1>), dim3(grid), dim3(NT), 0, st, m->p, sp, (const uint64_t *)d_carry,
-                                   (uint64_t)d.carry_records, (uint64_t *)nullptr, (uint64_t *)nullptr);
-            } else {
-                DISPATCH_WK(m, hipLaunchKernelGGL((db_carry_kernel<false, WKV>), dim3(grid), dim3(NT), 0, st, m->p, sp,
-                                                  (const uint64_t *)d_carry, (uint64_t)d.carry_records, kx_k, kx_c));
-            }
-            if (hipGetLastError() != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            if (!direct && (rc = tsx_hip_add_kmers_device(m, kx_k, kx_c, (size_t)d.carry_records, nullptr)) != TSX_HIP_OK) break;
-            if (hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        }
-        // chunks: the host reads chunk i + 1 while the device places chunk i
-        for (int b = 0; b < 2 && rc == TSX_HIP_OK; ++b) {
-            if (sg[b].done.create() != TSX_HIP_OK || sg[b].d_res.alloc(DB_RES_N * 8) != TSX_HIP_OK ||
-                sg[b].h_res.alloc(DB_RES_N * 8) != TSX_HIP_OK) rc = TSX_HIP_ENOMEM;
-        }
-        auto finish = [&](DbStage &s) -> int {   // the result of a chunk whose work has finished
-            s.busy = false;
-            const unsigned long long *res = s.h_res.get();
-            if (res[DB_RES_TOTAL] != s.n) return db_fail("k-mer database chunk: bitmap and entry count disagree");
-            if (res[DB_RES_BAD]) return db_fail("k-mer database chunk: malformed entries");
-            if (res[DB_RES_SUM] != s.sum) return db_fail("k-mer database chunk checksum mismatch");
-            if (res[DB_RES_ZERO] != s.zero_carried) return db_fail("k-mer database chunk: an entry with count 0");
-            entries += s.n;
-            return TSX_HIP_OK;
-        };
-        uint64_t expect_lo = 0, next_carry = 0;
-        bool ended = false;
-        for (uint64_t i = 0; rc == TSX_HIP_OK && !ended; ++i) {
-            DbStage &s = sg[i & 1];
-            if (s.busy) {
-                if (hipEventSynchronize(s.done.get()) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-                if ((rc = finish(s)) != TSX_HIP_OK) break;
-            }
-            uint64_t ch[4];
-            if ((rc = db_read_exact(fd, ch, DB_CHUNK_HEAD, "no end marker")) != TSX_HIP_OK) break;
-            const uint64_t lo = ch[0], hi = ch[1], n = ch[2];
-            if (lo != expect_lo || hi > slots || (lo == hi && (lo != slots || n != 0)) || n > hi - lo ||
-                ((hi - lo) & 63 && hi != slots)) { rc = db_fail("k-mer database: chunks do not tile the table"); break; }
-            if (lo == slots) { ended = true; break; }
-            expect_lo = hi;
-            const uint64_t nbm = (hi - lo + 63) / 64, nt = db_tiles(lo, hi);
-            const size_t bytes = (size_t)(nbm + n * W) * 8;
-            // grow-only; chunk_bytes is the first size.  (No wait: s.done has been waited for, nothing reads the stage.)
-            const size_t want = std::max(bytes, std::min(chunk_bytes, (size_t)(slots / 64 + slots * W) * 8));
-            if (bytes > s.d.cap()) s.h.reset();   // (both or none: d is allocated last)
-            if (s.h.reserve(nullptr, bytes, want) != TSX_HIP_OK || s.d.reserve(nullptr, bytes, want) != TSX_HIP_OK) { rc = TSX_HIP_ENOMEM; break; }
-            if ((rc = s.d_tile.reserve(nullptr, (nt + 1) * 8, (nt + 1) * 8)) != TSX_HIP_OK) break;
-            const size_t kxb = (size_t)std::max<uint64_t>(1, n) * (WK + 1) * 8;
-            if (!direct && (rc = s.d_kx.reserve(nullptr, kxb, kxb)) != TSX_HIP_OK) break;
-            if ((rc = db_read_exact(fd, s.h.get(), bytes, "chunk")) != TSX_HIP_OK) break;
-            s.n = n; s.sum = ch[3];
-            // the carry records of this chunk (sorted, so they come in order): slot pos must be occupied and hold the
-            // record's words; a popcount of the bitmap up to pos gives the entry's index.  In-slot counts of 0 are
-            // counted here and compared with the device's count of them, so that no entry's total count is 0.
-            {
-                const uint64_t *hbm = (const uint64_t *)s.h.get(), *hent = hbm + nbm;
-                uint64_t w = 0, before = 0;   // set bits of the words before w
-                s.zero_carried = 0;
-                for (; next_carry < d.carry_records && rec[next_carry * RW] < hi; ++next_carry) {
-                    const uint64_t *r = &rec[next_carry * RW];
-                    const uint64_t off = r[0] - lo, wc = off >> 6;
-                    for (; w < wc; ++w) before += (uint64_t)__builtin_popcountll(hbm[w]);
-                    const uint64_t bit = 1ULL << (off & 63);
-                    const uint64_t idx = before + (uint64_t)__builtin_popcountll(hbm[wc] & (bit - 1ULL));
-                    if (!(hbm[wc] & bit) || idx >= n || memcmp(&hent[idx * W], r + 2, (size_t)W * 8) != 0) {
-                        rc = db_fail("k-mer database: a carry record does not match the entry at its slot");
-                        break;
-                    }
-                    s.zero_carried += (hent[idx * W] >> sp.cshift) == 0 ? 1 : 0;
-                }
-                if (rc != TSX_HIP_OK) break;
-            }
-            const uint64_t *bm = (const uint64_t *)s.d.get(), *ent = bm + nbm;
-            uint64_t *kx_k = s.d_kx.get(), *kx_c = kx_k ? kx_k + n * WK : nullptr;
-            unsigned long long *const s_tile = s.d_tile.get(), *const s_res = s.d_res.get();
-            const unsigned nb = (unsigned)((nt + NT / 64 - 1) / (NT / 64));
-            if (hipMemcpyAsync(s.d.get(), s.h.get(), bytes, hipMemcpyHostToDevice, st) != hipSuccess ||
-                hipMemsetAsync(s_res, 0, DB_RES_N * 8, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            hipLaunchKernelGGL(db_count_bitmap_kernel, dim3(nb), dim3(NT), 0, st, bm, nbm, nt, s_tile);
-            hipLaunchKernelGGL(db_scan_kernel, dim3(1), dim3(NT), 0, st, s_tile, nt);
-            if (direct) {
-                hipLaunchKernelGGL((db_load_kernel<true, 1>), dim3((unsigned)nt), dim3(NT), 0, st, m->p, sp, lo, hi, bm, ent, n,
-                                   (const unsigned long long *)s_tile, (uint64_t *)nullptr, (uint64_t *)nullptr, s_res);
-            } else {
-                DISPATCH_WK(m, hipLaunchKernelGGL((db_load_kernel<false, WKV>), dim3((unsigned)nt), dim3(NT), 0, st, m->p, sp, lo, hi,
-                                                  bm, ent, n, (const unsigned long long *)s_tile, kx_k, kx_c, s_res));
-            }
-            if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(s_res + DB_RES_TOTAL, s_tile + nt, 8, hipMemcpyDeviceToDevice, st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            if (!direct && n && (rc = tsx_hip_add_kmers_device(m, kx_k, kx_c, (size_t)n, nullptr)) != TSX_HIP_OK) break;
-            if (hipMemcpyAsync(s.h_res.get(), s_res, DB_RES_N * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipEventRecord(s.done.get(), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            s.busy = true;
-        }
-        (void)hipStreamSynchronize(st);
-        for (int b = 0; b < 2; ++b)
-            if (sg[b].busy) { const int r = finish(sg[b]); if (rc == TSX_HIP_OK) rc = r; }
-        if (rc != TSX_HIP_OK) break;
-        if (entries != d.distinct) { rc = db_fail("k-mer database: entry count differs from the header"); break; }
-        // kmers_added grows by the database's (the re-insert has added the sum of the counts instead)
-        const unsigned long long ka = kmers_before + d.kmers_added;
-        if (hipMemcpyAsync(m->p.stats + ST_KMERS, &ka, 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        rc = tsx_hip_sync(m);
-    } while (0);
-    (void)hipStreamSynchronize(st);   // nothing queued may outlive the stages
-    if (entries_out) *entries_out = entries;
+    DbLoad ld(m, fd, d, carry_sum, chunk_bytes ? chunk_bytes : DB_CHUNK_DEFAULT);
+    int rc = ld.begin();
+    if (rc == TSX_HIP_OK) rc = ld.carry_section();
+    if (rc == TSX_HIP_OK) rc = ld.chunks();
+    if (rc == TSX_HIP_OK) rc = ld.end();
+    if (entries_out) *entries_out = ld.entries;
     return rc;
 }
 
@@ -3712,27 +3773,15 @@ static bool combine_aligned(const tsx_hip_map *x, const tsx_hip_map *y) {
            x->p.S == y->p.S && x->seed == y->seed;
 }
 
-// Staging of the paths that go through k-mers: two chunks, so that add_kmers_kernel inserts one (on OUT's stream)
-// while the sweep fills the other (on A's).
-struct CombineStage {
-    DevBuf<uint64_t> d_kmers[2], d_counts[2];
-    DevBuf<unsigned long long> d_n;   // entries staged per chunk
-    PinBuf<unsigned long long> h_n;
-    Event swept[2], inserted[2];
-    bool waiting[2] = {false, false}, reuse[2] = {false, false};
-};
-
-extern "C" int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b, const tsx_hip_combine_rule *rule,
-                               tsx_hip_combine_stats *stats_out) {
-    if (stats_out) memset(stats_out, 0, sizeof *stats_out);
+// The arguments and whether the tables can be combined at all.
+static int combine_check(const tsx_hip_map *out, const tsx_hip_map *a, const tsx_hip_map *b, const tsx_hip_combine_rule *rule) {
     if (!a || !b || !rule) return combine_fail("combine: a, b and the rule are needed");
     if (rule->op < TSX_HIP_OP_INTERSECT || rule->op > TSX_HIP_OP_DIFF) return combine_fail("combine: unknown op");
     if (rule->count_mode < TSX_HIP_CNT_MIN || rule->count_mode > TSX_HIP_CNT_RIGHT) return combine_fail("combine: unknown count mode");
-    const uint64_t a_lo = std::max<uint64_t>(1, rule->a_lower), b_lo = std::max<uint64_t>(1, rule->b_lower);
-    if (a_lo > rule->a_upper || b_lo > rule->b_upper) return combine_fail("combine: lower > upper");
+    if (std::max<uint64_t>(1, rule->a_lower) > rule->a_upper || std::max<uint64_t>(1, rule->b_lower) > rule->b_upper)
+        return combine_fail("combine: lower > upper");
     if (out && (out == a || out == b)) return combine_fail("combine: out is one of the inputs");
-    tsx_hip_map *maps[3] = {a, b, out};
-    for (tsx_hip_map *m : maps) {
+    for (const tsx_hip_map *m : {a, b, out}) {
         if (!m) continue;
         if (m->p.lg != m->p.l) return combine_fail("combine: a shard of a multi-GPU table");
         if (m->device != a->device) return combine_fail("combine: the tables are on different devices");
@@ -3741,127 +3790,181 @@ extern "C" int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b,
         if (m->p.acgt_only != a->p.acgt_only || m->minq != a->minq) return combine_fail("combine: the tables differ in base rule");
     }
     if (out && out->used) return combine_fail("combine: out is not empty");
+    return TSX_HIP_OK;
+}
+
+// Which sweep runs and where its survivors go.  TSX_HIP_COMBINE_PATH: 0 = by the tables (default), 1 = the general path,
+// 2 = the aligned path; TSX_HIP_COMBINE_CHUNK_BYTES: the bytes of one staging chunk.  (Tests use the paths as each
+// other's reference.)
+struct CombinePath {
+    bool aligned;          // A and B are joined slot against slot
+    bool fused;            // ... and the survivors go into OUT by hashed key: no staging
+    uint64_t chunk_slots;  // slots swept into one staging chunk
+};
+static int combine_path(const tsx_hip_map *out, const tsx_hip_map *a, const tsx_hip_map *b, CombinePath *cp) {
     int path = 0;
     if (const char *e = getenv("TSX_HIP_COMBINE_PATH")) path = atoi(e);
     const bool ab_aligned = combine_aligned(a, b);
     if (path < 0 || path > 2) return combine_fail("combine: TSX_HIP_COMBINE_PATH is 0, 1 or 2");
     if (path == 2 && !ab_aligned) return combine_fail("combine: the aligned path needs A and B of one l, slot layout, segment bits and seed");
-    const bool aligned = path == 2 || (path == 0 && ab_aligned);
-    const bool fused = aligned && out && combine_aligned(a, out);   // survivors go in by hashed key: no staging
+    cp->aligned = path == 2 || (path == 0 && ab_aligned);
+    cp->fused = cp->aligned && out && combine_aligned(a, out);
     size_t chunk_bytes = COMBINE_CHUNK_DEFAULT;
     if (const char *e = getenv("TSX_HIP_COMBINE_CHUNK_BYTES")) { const long long v = atoll(e); if (v > 0) chunk_bytes = (size_t)v; }
-    const int WK = a->p.wk;
     const uint64_t max_slots = std::max(a->lay.slots, b->lay.slots);
-    const uint64_t chunk_slots = std::min<uint64_t>(max_slots, std::max<uint64_t>(64, (chunk_bytes / ((size_t)(WK + 1) * 8)) & ~(uint64_t)63));
+    cp->chunk_slots = std::min<uint64_t>(max_slots, std::max<uint64_t>(64, (chunk_bytes / ((size_t)(a->p.wk + 1) * 8)) & ~(uint64_t)63));
+    return TSX_HIP_OK;
+}
 
+// Staging of the paths that go through k-mers: two chunks, so that add_kmers_kernel inserts one (on OUT's stream)
+// while the sweep fills the other (on the sweep stream sw).
+struct CombineStage {
+    DevBuf<uint64_t> d_kmers[2], d_counts[2];
+    DevBuf<unsigned long long> d_n;   // entries staged per chunk
+    PinBuf<unsigned long long> h_n;
+    Event swept[2], inserted[2];
+    bool waiting[2] = {false, false}, reuse[2] = {false, false};
+    uint64_t chunk = 0;               // chunks swept so far: the next one goes into buffer chunk & 1
+
+    int init(uint64_t chunk_slots, int WK) {
+        if (d_n.alloc(2 * 8) != TSX_HIP_OK || h_n.alloc(2 * 8) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+        for (int i = 0; i < 2; ++i) {
+            if (d_kmers[i].alloc((size_t)chunk_slots * WK * 8) != TSX_HIP_OK || d_counts[i].alloc((size_t)chunk_slots * 8) != TSX_HIP_OK) {
+                g_last_error = "combine: staging";
+                return TSX_HIP_ENOMEM;
+            }
+            if (swept[i].create() != TSX_HIP_OK || inserted[i].create() != TSX_HIP_OK) return TSX_HIP_EHIP;
+        }
+        return TSX_HIP_OK;
+    }
+    // the chunk in buffer i has been swept: insert it into OUT
+    int insert_chunk(int i, tsx_hip_map *out) {
+        waiting[i] = false;
+        HIP_TRY(hipEventSynchronize(swept[i].get()));
+        const unsigned long long n = h_n.get()[i];
+        if (n == 0) return TSX_HIP_OK;
+        TSX_TRY(tsx_hip_add_kmers_device(out, d_kmers[i].get(), d_counts[i].get(), (size_t)n, nullptr));
+        HIP_TRY(hipEventRecord(inserted[i].get(), out->stream.get()));
+        reuse[i] = true;
+        return TSX_HIP_OK;
+    }
+    // the next buffer, free for a sweep on sw: what it held is on its way into OUT, its counter is zeroed
+    int next_buffer(hipStream_t sw, tsx_hip_map *out) {
+        const int i = (int)(chunk & 1);
+        if (waiting[i]) TSX_TRY(insert_chunk(i, out));
+        if (reuse[i]) HIP_TRY(hipStreamWaitEvent(sw, inserted[i].get(), 0));
+        HIP_TRY(hipMemsetAsync(d_n.get() + i, 0, 8, sw));
+        return TSX_HIP_OK;
+    }
+    // that buffer's sweep is queued: its count comes back, and the chunk before it is inserted while it is swept
+    int sweep_queued(hipStream_t sw, tsx_hip_map *out) {
+        const int i = (int)(chunk & 1);
+        HIP_TRY(hipMemcpyAsync(h_n.get() + i, d_n.get() + i, 8, hipMemcpyDeviceToHost, sw));
+        HIP_TRY(hipEventRecord(swept[i].get(), sw));
+        waiting[i] = true;
+        ++chunk;
+        return waiting[chunk & 1] ? insert_chunk((int)(chunk & 1), out) : TSX_HIP_OK;
+    }
+    // after the last sweep: the (at most two) chunks still waiting, the older one first
+    int drain(tsx_hip_map *out) {
+        for (int i = 0; i < 2; ++i)
+            if (waiting[(chunk + i) & 1]) TSX_TRY(insert_chunk((int)((chunk + i) & 1), out));
+        return TSX_HIP_OK;
+    }
+};
+
+// The sweep's arguments for a side (0: src = A, 1: src = B); a_sec / b_sec: the table has carried counts.
+static CombineArgs combine_args(const tsx_hip_combine_rule *rule, int side, bool a_sec, bool b_sec, int emit) {
+    const uint64_t a_lo = std::max<uint64_t>(1, rule->a_lower), b_lo = std::max<uint64_t>(1, rule->b_lower);
+    CombineArgs ca;
+    ca.op = rule->op; ca.mode = rule->count_mode; ca.side = side; ca.emit = emit;
+    ca.src_sec = side == 0 ? a_sec : b_sec; ca.oth_sec = side == 0 ? b_sec : a_sec;
+    ca.s_lo = side == 0 ? a_lo : b_lo; ca.s_hi = side == 0 ? rule->a_upper : rule->b_upper;
+    ca.o_lo = side == 0 ? b_lo : a_lo; ca.o_hi = side == 0 ? rule->b_upper : rule->a_upper;
+    return ca;
+}
+
+// combine_sweep_kernel over slots [lo, hi) of src on stream sw; dk, dc, dn: the staging buffer and its counter (emit == 1).
+static int combine_sweep_launch(const tsx_hip_map *a, bool aligned, const TableParams &src, const TableParams &oth,
+                                const TableParams &po, const CombineArgs &ca, uint64_t lo, uint64_t hi, uint64_t *dk, uint64_t *dc,
+                                unsigned long long *dn, unsigned long long *d_res, hipStream_t sw) {
+    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((hi - lo + CB_TILE - 1) / CB_TILE, (uint64_t)a->cus * 8));
+    if (aligned) {
+        DISPATCH_WK(a, hipLaunchKernelGGL((combine_sweep_kernel<WKV, false, true>), dim3(grid), dim3(NT), 0, sw, src, oth, po, ca,
+                                          lo, hi, dk, dc, (uint64_t)(hi - lo), dn, d_res));
+    } else {
+        DISPATCH_CANON(a, DISPATCH_WK(a, hipLaunchKernelGGL((combine_sweep_kernel<WKV, CANV, false>), dim3(grid), dim3(NT), 0, sw,
+                                                            src, oth, po, ca, lo, hi, dk, dc, (uint64_t)(hi - lo), dn, d_res)));
+    }
+    if (hipGetLastError() != hipSuccess) { g_last_error = "combine_sweep_kernel launch"; return TSX_HIP_EHIP; }
+    return TSX_HIP_OK;
+}
+
+// One side's sweep: the whole table at once, or (ca.emit == 1) chunk by chunk through the staging.
+static int combine_sweep_side(const tsx_hip_map *a, const tsx_hip_map *src, const tsx_hip_map *oth, tsx_hip_map *out,
+                              const CombinePath &cp, const CombineArgs &ca, CombineStage &sg, unsigned long long *d_res,
+                              hipStream_t sw) {
+    const uint64_t slots = src->lay.slots, span = ca.emit == 1 ? cp.chunk_slots : slots;
+    const TableParams &po = out ? out->p : src->p;
+    for (uint64_t lo = 0; lo < slots; lo += span) {
+        const uint64_t hi = std::min(slots, lo + span);
+        if (ca.emit != 1) {
+            TSX_TRY(combine_sweep_launch(a, cp.aligned, src->p, oth->p, po, ca, lo, hi, nullptr, nullptr, nullptr, d_res, sw));
+            continue;
+        }
+        const int i = (int)(sg.chunk & 1);
+        TSX_TRY(sg.next_buffer(sw, out));
+        TSX_TRY(combine_sweep_launch(a, cp.aligned, src->p, oth->p, po, ca, lo, hi, sg.d_kmers[i].get(), sg.d_counts[i].get(),
+                                     sg.d_n.get() + i, d_res, sw));
+        TSX_TRY(sg.sweep_queued(sw, out));
+    }
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b, const tsx_hip_combine_rule *rule,
+                               tsx_hip_combine_stats *stats_out) {
+    if (stats_out) memset(stats_out, 0, sizeof *stats_out);
+    TSX_TRY(combine_check(out, a, b, rule));
+    CombinePath cp;
+    TSX_TRY(combine_path(out, a, b, &cp));
     HIP_TRY(hipSetDevice(a->device));
     // behind everything queued on the three maps; lazily cleared tables are zeroed before anyone reads them
-    for (tsx_hip_map *m : maps) {
+    for (tsx_hip_map *m : {a, b, out}) {
         if (!m) continue;
         join_foreign(m, true);
-        int rcz = ensure_zeroed(m, m->stream.get());
-        if (rcz != TSX_HIP_OK) return rcz;
+        TSX_TRY(ensure_zeroed(m, m->stream.get()));
         HIP_TRY(hipStreamSynchronize(m->stream.get()));
     }
     unsigned long long a_carry = 0, b_carry = 0;
     HIP_TRY(hipMemcpy(&a_carry, a->p.stats + ST_CARRY, 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&b_carry, b->p.stats + ST_CARRY, 8, hipMemcpyDeviceToHost));
 
-    hipStream_t sw = a->stream.get();                  // the sweeps
-    hipStream_t ins = out ? out->stream.get() : sw;    // the inserts of staged chunks
+    hipStream_t sw = a->stream.get();   // the sweeps; the inserts of staged chunks run on OUT's stream
     CombineStage sg;
     DevBuf<unsigned long long> res;
-    unsigned long long *d_res = nullptr;
+    SyncAtExit wait_sw(sw), wait_out(out ? out->stream.get() : sw);   // nothing queued may outlive the staging
+    if (res.alloc(CB_N * 8) != TSX_HIP_OK) return TSX_HIP_ENOMEM;
+    HIP_TRY(hipMemsetAsync(res.get(), 0, CB_N * 8, sw));
+    const bool staging = out && !cp.fused;
+    if (staging) TSX_TRY(sg.init(cp.chunk_slots, a->p.wk));
+    for (int side = 0; side < 2; ++side) {
+        // B's sweep writes only for UNION; for the other ops it counts b_in_range
+        const bool writes = out && (side == 0 || rule->op == TSX_HIP_OP_UNION);
+        if (side == 1 && !writes && !stats_out) break;
+        const CombineArgs ca = combine_args(rule, side, a_carry != 0, b_carry != 0, !writes ? 0 : cp.fused ? 2 : 1);
+        if (ca.emit == 2) out->used = true;   // (the sweep itself inserts; OUT's stream is idle, see above)
+        TSX_TRY(combine_sweep_side(a, side == 0 ? a : b, side == 0 ? b : a, out, cp, ca, sg, res.get(), sw));
+    }
+    if (staging) TSX_TRY(sg.drain(out));
     unsigned long long h_res[CB_N] = {0};
-    int rc = TSX_HIP_OK;
-    const bool staging = out && !fused;
-    do {
-        if (res.alloc(CB_N * 8) != TSX_HIP_OK) { rc = TSX_HIP_ENOMEM; break; }
-        d_res = res.get();
-        if (hipMemsetAsync(d_res, 0, CB_N * 8, sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        if (staging) {
-            if (sg.d_n.alloc(2 * 8) != TSX_HIP_OK || sg.h_n.alloc(2 * 8) != TSX_HIP_OK) { rc = TSX_HIP_ENOMEM; break; }
-            for (int i = 0; i < 2 && rc == TSX_HIP_OK; ++i) {
-                if (sg.d_kmers[i].alloc((size_t)chunk_slots * WK * 8) != TSX_HIP_OK ||
-                    sg.d_counts[i].alloc((size_t)chunk_slots * 8) != TSX_HIP_OK) { g_last_error = "combine: staging"; rc = TSX_HIP_ENOMEM; }
-                else if (sg.swept[i].create() != TSX_HIP_OK || sg.inserted[i].create() != TSX_HIP_OK) rc = TSX_HIP_EHIP;
-            }
-            if (rc != TSX_HIP_OK) break;
-        }
-        // the chunk in buffer i has been swept: insert it into OUT
-        auto insert_chunk = [&](int i) -> int {
-            sg.waiting[i] = false;
-            if (hipEventSynchronize(sg.swept[i].get()) != hipSuccess) return TSX_HIP_EHIP;
-            const unsigned long long n = sg.h_n.get()[i];
-            if (n == 0) return TSX_HIP_OK;
-            const int r = tsx_hip_add_kmers_device(out, sg.d_kmers[i].get(), sg.d_counts[i].get(), (size_t)n, nullptr);
-            if (r != TSX_HIP_OK) return r;
-            if (hipEventRecord(sg.inserted[i].get(), ins) != hipSuccess) return TSX_HIP_EHIP;
-            sg.reuse[i] = true;
-            return TSX_HIP_OK;
-        };
-        uint64_t chunk = 0;
-        for (int side = 0; side < 2 && rc == TSX_HIP_OK; ++side) {
-            tsx_hip_map *src = side == 0 ? a : b, *oth = side == 0 ? b : a;
-            CombineArgs ca;
-            ca.op = rule->op; ca.mode = rule->count_mode; ca.side = side;
-            ca.src_sec = (side == 0 ? a_carry : b_carry) != 0; ca.oth_sec = (side == 0 ? b_carry : a_carry) != 0;
-            ca.s_lo = side == 0 ? a_lo : b_lo; ca.s_hi = side == 0 ? rule->a_upper : rule->b_upper;
-            ca.o_lo = side == 0 ? b_lo : a_lo; ca.o_hi = side == 0 ? rule->b_upper : rule->a_upper;
-            // B's sweep writes only for UNION; for the other ops it counts b_in_range
-            const bool writes = out && (side == 0 || rule->op == TSX_HIP_OP_UNION);
-            ca.emit = !writes ? 0 : fused ? 2 : 1;
-            if (side == 1 && !writes && !stats_out) break;
-            const uint64_t slots = src->lay.slots;
-            const uint64_t span = ca.emit == 1 ? chunk_slots : slots;
-            if (ca.emit == 2) out->used = true;   // (the sweep itself inserts; OUT's stream is idle, see above)
-            for (uint64_t lo = 0; lo < slots && rc == TSX_HIP_OK; lo += span) {
-                const uint64_t hi = std::min(slots, lo + span);
-                const int i = (int)(chunk & 1);
-                uint64_t *dk = nullptr, *dc = nullptr;
-                unsigned long long *dn = nullptr;
-                if (ca.emit == 1) {
-                    if (sg.waiting[i] && (rc = insert_chunk(i)) != TSX_HIP_OK) break;
-                    if (sg.reuse[i] && hipStreamWaitEvent(sw, sg.inserted[i].get(), 0) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-                    dk = sg.d_kmers[i].get(); dc = sg.d_counts[i].get(); dn = sg.d_n.get() + i;
-                    if (hipMemsetAsync(dn, 0, 8, sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-                }
-                const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((hi - lo + CB_TILE - 1) / CB_TILE, (uint64_t)a->cus * 8));
-                const TableParams &po = out ? out->p : src->p;
-                if (aligned) {
-                    DISPATCH_WK(a, hipLaunchKernelGGL((combine_sweep_kernel<WKV, false, true>), dim3(grid), dim3(NT), 0, sw, src->p,
-                                                      oth->p, po, ca, lo, hi, dk, dc, (uint64_t)(hi - lo), dn, d_res));
-                } else {
-                    DISPATCH_CANON(a, DISPATCH_WK(a, hipLaunchKernelGGL((combine_sweep_kernel<WKV, CANV, false>), dim3(grid), dim3(NT),
-                                                                        0, sw, src->p, oth->p, po, ca, lo, hi, dk, dc,
-                                                                        (uint64_t)(hi - lo), dn, d_res)));
-                }
-                if (hipGetLastError() != hipSuccess) { g_last_error = "combine_sweep_kernel launch"; rc = TSX_HIP_EHIP; break; }
-                if (ca.emit == 1) {
-                    if (hipMemcpyAsync(sg.h_n.get() + i, dn, 8, hipMemcpyDeviceToHost, sw) != hipSuccess ||
-                        hipEventRecord(sg.swept[i].get(), sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-                    sg.waiting[i] = true;
-                    ++chunk;
-                    const int prev = (int)(chunk & 1);   // the chunk before this one: insert it while this one is swept
-                    if (sg.waiting[prev]) rc = insert_chunk(prev);
-                }
-            }
-        }
-        for (int i = 0; i < 2 && rc == TSX_HIP_OK; ++i)
-            if (sg.waiting[(chunk + i) & 1]) rc = insert_chunk((int)((chunk + i) & 1));
-        if (rc != TSX_HIP_OK) break;
-        if (hipMemcpyAsync(h_res, d_res, CB_N * 8, hipMemcpyDeviceToHost, sw) != hipSuccess ||
-            hipStreamSynchronize(sw) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        if (out) rc = tsx_hip_sync(out);
-    } while (0);
-    (void)hipStreamSynchronize(sw);   // nothing queued may outlive the staging
-    if (out) (void)hipStreamSynchronize(ins);
+    HIP_TRY(hipMemcpyAsync(h_res, res.get(), CB_N * 8, hipMemcpyDeviceToHost, sw));
+    HIP_TRY(hipStreamSynchronize(sw));
     if (stats_out) {
         stats_out->a_in_range = h_res[CB_A_IN]; stats_out->b_in_range = h_res[CB_B_IN]; stats_out->both = h_res[CB_BOTH];
         stats_out->a_sum_both = h_res[CB_A_SUM]; stats_out->b_sum_both = h_res[CB_B_SUM];
         stats_out->out_entries = h_res[CB_OUT_N]; stats_out->out_count_sum = h_res[CB_OUT_SUM];
     }
-    return rc;
+    return out ? tsx_hip_sync(out) : TSX_HIP_OK;
 }
 
 extern "C" int tsx_hip_owner_host(const tsx_hip_map *m, const uint64_t *kmer, int nranks) {
