@@ -759,6 +759,33 @@ typedef struct tsx_hip_combine_stats {
 int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b, const tsx_hip_combine_rule *rule,
                     tsx_hip_combine_stats *stats_out /* optional */);
 
+/*
+ * Joint k-mer spectrum of two tables (csrc/tsx_joint.h; no reference counterpart -- KAT `comp`, the spectra-cn matrix):
+ * how many distinct k-mers occur i times in A and j times in B, for every pair (i, j), binned on the device.
+ *   A, B     two whole tables (none created with shard_bits > 0) on one device that agree in k, canonical mode and base
+ *            rule; l, storage bits, overflow_l and hash seed may differ (the conditions of tsx_hip_combine).  a == b is
+ *            allowed.
+ *   a(x)     getKmerCount(x) in A, b(x) in B: in-slot field plus carries from the secondary array, 0 when x is absent;
+ *            on canonical tables x stands for its strand pair, as in tsx_hip_combine.
+ *   bins     na, nb >= 2; bin_a(c) = min(c, na - 1), bin_b(c) = min(c, nb - 1): the last bin of each side pools every
+ *            larger count, as tsx_hip_histogram_* does.  na * nb <= 2^24.
+ *   matrix   uint64, row-major, na x nb: M[i * nb + j] = the number of distinct x in A u B (a(x) > 0 or b(x) > 0) with
+ *            bin_a(a(x)) = i and bin_b(b(x)) = j.  M[0] = 0.  Row 0 is what only B holds, column 0 what only A holds;
+ *            the sums of rows i >= 1 are A's abundance histogram, the sums of columns j >= 1 are B's.  There are no
+ *            count ranges: a range is a sum over cells.
+ *   _device  zeroes dev_matrix (na * nb * 8 bytes, device memory), waits for what is queued on both maps' streams, and
+ *            queues the sweeps on `stream` (NULL = A's own): it returns without waiting for them.  What A's and B's own
+ *            streams do next is ordered behind them.
+ *   _host    the same into host memory; waits for the result.
+ * A and B are left as they are, bit for bit (a lazily cleared table is zeroed first, as everywhere).  The two paths of
+ * tsx_hip_combine apply, with identical results, and TSX_HIP_COMBINE_PATH picks one in the same way.
+ * TSX_HIP_EINVAL (tsx_hip_last_error says which): a NULL map or matrix, a map created with shard_bits > 0, maps on
+ * different devices, a different k, canonical mode or base rule, na < 2, nb < 2, na * nb > 2^24, a forced path that does
+ * not apply.
+ */
+int tsx_hip_joint_histogram_device(tsx_hip_map *a, tsx_hip_map *b, size_t na, size_t nb, void *dev_matrix, void *stream);
+int tsx_hip_joint_histogram_host(tsx_hip_map *a, tsx_hip_map *b, uint64_t *matrix_out, size_t na, size_t nb);
+
 /* IBijectiveFunction::apply / inv_apply (IBijectiveFunction.h:26-27) on the host,
  * and the matrix rows (row i <-> output bit 2k-1-i, BijectiveKMapping.h:202-256). */
 int tsx_hip_hash_apply(const tsx_hip_map *m, const uint64_t *kmer, uint64_t *key_out);

@@ -340,6 +340,25 @@ def combine_rule(op="intersect", counts="min", a_range=(1, None), b_range=(1, No
                        int(b_range[0]), top if b_range[1] is None else int(b_range[1]))
 
 
+JOINT_MAX_CELLS = 1 << 24   # cells of a joint histogram (tsx_hip_joint_histogram_*)
+
+
+def joint_histogram(A, B, bins_a=1002, bins_b=1002):
+    """The definition of TSXHashMapHIP.jointHistogram on the CPU: A and B map k-mer -> count (any hashable key; a count
+    of 0 is an absent k-mer).  Returns numpy uint64[bins_a, bins_b]: [i, j] = the k-mers x of A u B with
+    min(A[x], bins_a - 1) == i and min(B[x], bins_b - 1) == j."""
+    if bins_a < 2 or bins_b < 2 or bins_a * bins_b > JOINT_MAX_CELLS:
+        raise ValueError("joint_histogram: 2 <= bins and bins_a * bins_b <= 2^24")
+    keys = list(set(A) | set(B))
+    m = np.zeros((bins_a, bins_b), dtype=np.uint64)
+    if keys:
+        a = np.minimum(np.array([int(A.get(x, 0)) for x in keys], dtype=np.uint64), np.uint64(bins_a - 1)).astype(np.int64)
+        b = np.minimum(np.array([int(B.get(x, 0)) for x in keys], dtype=np.uint64), np.uint64(bins_b - 1)).astype(np.int64)
+        np.add.at(m, (a, b), np.uint64(1))
+        m[0, 0] = 0   # in neither: not a k-mer of A u B
+    return m
+
+
 def build():
     """Compile the library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     import subprocess
@@ -429,6 +448,8 @@ def lib():
     L.tsx_hip_save_host.argtypes = [vp, ci, sz, u64p, u64p]
     L.tsx_hip_load_host.argtypes = [vp, ci, sz, u64p]
     L.tsx_hip_combine.argtypes = [vp, vp, vp, ctypes.POINTER(CombineRule), ctypes.POINTER(CombineStats)]
+    L.tsx_hip_joint_histogram_device.argtypes = [vp, vp, sz, sz, vp, vp]
+    L.tsx_hip_joint_histogram_host.argtypes = [vp, vp, u64p, sz, sz]
     L.tsx_hip_group_histogram_host.argtypes = [vp, u64p, sz]
     L.tsx_hip_group_write_counts_host.argtypes = [vp, ci, u64, u64, sz, u64p, u64p]
     L.tsx_hip_query_reads_device.argtypes = [vp, vp, sz, u64, u64, vp, sz, ctypes.POINTER(sz), vp]
@@ -835,6 +856,26 @@ class TSXHashMapHIP:
         union = st["a_in_range"] + st["b_in_range"] - st["both"]
         st["jaccard"] = st["both"] / union if union else 0.0
         return st
+
+    def _check_joint(self, rc):
+        if rc == EINVAL:
+            raise TSXException(rc, self._lib.tsx_hip_last_error().decode() or self._lib.tsx_hip_strerror(rc).decode())
+        _check(rc)
+
+    def jointHistogram(self, other, bins_a=1002, bins_b=1002):
+        """Joint k-mer spectrum of two tables (tsx_hip_joint_histogram_host; KAT `comp`): self is A, `other` is B.
+        Returns numpy uint64[bins_a, bins_b]: [i, j] = distinct k-mers counted i times in A and j times in B, the last
+        bin of each side pooling every larger count; [0, 0] is 0.  joint_histogram() states the definition."""
+        out = np.zeros((int(bins_a), int(bins_b)) if 0 < bins_a * bins_b <= JOINT_MAX_CELLS else (0, 0), dtype=np.uint64)
+        self._check_joint(self._lib.tsx_hip_joint_histogram_host(self.handle, other.handle, _p(out), int(bins_a), int(bins_b)))
+        return out
+
+    def jointHistogramDevice(self, other, matrix_ptr, bins_a=1002, bins_b=1002, stream=None):
+        """tsx_hip_joint_histogram_device: the matrix into uint64[bins_a * bins_b] in device memory (zeroed by the call),
+        queued on `stream` (None = this map's own); returns without waiting."""
+        vp = ctypes.c_void_p
+        self._check_joint(self._lib.tsx_hip_joint_histogram_device(self.handle, other.handle, int(bins_a), int(bins_b),
+                                                                   vp(matrix_ptr), vp(stream) if stream else None))
 
     def queryReads(self, text, lower=1, upper=None, chunk_bytes=0):
         """Per-record k-mer stats of a FASTQ / FASTA text against the table (tsx_hip_query_reads_host): a numpy

@@ -11,6 +11,7 @@
 #include "tsx_baserule.h"
 #include "tsx_db.h"
 #include "tsx_combine.h"
+#include "tsx_joint.h"
 #include "tsx_fasta.h"
 #include "tsx_trim.h"
 #include "tsx_normalize.h"
@@ -3965,6 +3966,88 @@ extern "C" int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b,
         stats_out->out_entries = h_res[CB_OUT_N]; stats_out->out_count_sum = h_res[CB_OUT_SUM];
     }
     return out ? tsx_hip_sync(out) : TSX_HIP_OK;
+}
+
+// ---- joint spectrum of two tables (tsx_joint.h) ------------------------------------------------------------------
+static const size_t JOINT_MAX_CELLS = (size_t)1 << 24;
+
+static int joint_check(const tsx_hip_map *a, const tsx_hip_map *b, size_t na, size_t nb) {
+    if (!a || !b) return combine_fail("joint histogram: a and b are needed");
+    if (a->p.lg != a->p.l || b->p.lg != b->p.l) return combine_fail("joint histogram: a shard of a multi-GPU table");
+    if (b->device != a->device) return combine_fail("joint histogram: the tables are on different devices");
+    if (b->p.k != a->p.k) return combine_fail("joint histogram: the tables differ in k");
+    if (b->canon != a->canon) return combine_fail("joint histogram: the tables differ in canonical mode");
+    if (b->p.acgt_only != a->p.acgt_only || b->minq != a->minq) return combine_fail("joint histogram: the tables differ in base rule");
+    if (na < 2 || nb < 2) return combine_fail("joint histogram: fewer than 2 bins");
+    if (na > JOINT_MAX_CELLS || nb > JOINT_MAX_CELLS || na * nb > JOINT_MAX_CELLS) return combine_fail("joint histogram: more than 2^24 cells");
+    return TSX_HIP_OK;
+}
+
+// joint_histogram_kernel over every slot of src on stream st.
+static int joint_launch(const tsx_hip_map *a, bool aligned, const tsx_hip_map *src, const tsx_hip_map *oth, const JointArgs &ja,
+                        size_t na, size_t nb, unsigned long long *d_matrix, hipStream_t st) {
+    const uint64_t slots = src->lay.slots, tiles = (slots + JH_TILE - 1) / JH_TILE;
+    uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)a->cus * 8));
+    // A workgroup's corner is u32: bound the slots one workgroup sweeps below 2^31.
+    auto per_wg = [&](uint64_t g) { return (tiles + g - 1) / g * JH_TILE; };
+    while (per_wg(grid) >= (1ULL << 31) && grid < (1ULL << 30)) grid *= 2;
+    if (per_wg(grid) >= (1ULL << 31)) return combine_fail("joint histogram: the table is too large");
+    if (aligned) {
+        DISPATCH_WK(a, hipLaunchKernelGGL((joint_histogram_kernel<WKV, false, true>), dim3((unsigned)grid), dim3(NT), 0, st, src->p,
+                                          oth->p, ja, (uint64_t)0, slots, (uint32_t)na, (uint32_t)nb, d_matrix));
+    } else {
+        DISPATCH_CANON(a, DISPATCH_WK(a, hipLaunchKernelGGL((joint_histogram_kernel<WKV, CANV, false>), dim3((unsigned)grid), dim3(NT),
+                                                            0, st, src->p, oth->p, ja, (uint64_t)0, slots, (uint32_t)na,
+                                                            (uint32_t)nb, d_matrix)));
+    }
+    if (hipGetLastError() != hipSuccess) { g_last_error = "joint_histogram_kernel launch"; return TSX_HIP_EHIP; }
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_joint_histogram_device(tsx_hip_map *a, tsx_hip_map *b, size_t na, size_t nb, void *dev_matrix, void *stream) {
+    TSX_TRY(joint_check(a, b, na, nb));
+    if (!dev_matrix) return combine_fail("joint histogram: no matrix");
+    CombinePath cp;
+    TSX_TRY(combine_path(nullptr, a, b, &cp));
+    HIP_TRY(hipSetDevice(a->device));
+    // behind everything queued on the two maps; lazily cleared tables are zeroed before anyone reads them
+    for (tsx_hip_map *m : {a, b}) {
+        join_foreign(m, true);
+        TSX_TRY(ensure_zeroed(m, m->stream.get()));
+        HIP_TRY(hipStreamSynchronize(m->stream.get()));
+    }
+    unsigned long long a_carry = 0, b_carry = 0;
+    HIP_TRY(hipMemcpy(&a_carry, a->p.stats + ST_CARRY, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&b_carry, b->p.stats + ST_CARRY, 8, hipMemcpyDeviceToHost));
+    hipStream_t st = pick_stream(a, stream);   // (both maps' streams are idle: nothing for st to wait for)
+    unsigned long long *d_matrix = (unsigned long long *)dev_matrix;
+    HIP_TRY(hipMemsetAsync(d_matrix, 0, na * nb * sizeof(unsigned long long), st));
+    for (int side = 0; side < (a == b ? 1 : 2); ++side) {
+        JointArgs ja;
+        ja.side = side;
+        ja.src_sec = (side == 0 ? a_carry : b_carry) != 0;
+        ja.oth_sec = (side == 0 ? b_carry : a_carry) != 0;
+        TSX_TRY(joint_launch(a, cp.aligned, side == 0 ? a : b, side == 0 ? b : a, ja, na, nb, d_matrix, st));
+    }
+    // what B's own stream does next goes behind the sweeps (A: pick_stream remembers a caller's stream)
+    if (st != b->stream.get() && b->join_ev.get()) {
+        HIP_TRY(hipEventRecord(b->join_ev.get(), st));
+        HIP_TRY(hipStreamWaitEvent(b->stream.get(), b->join_ev.get(), 0));
+    }
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_joint_histogram_host(tsx_hip_map *a, tsx_hip_map *b, uint64_t *matrix_out, size_t na, size_t nb) {
+    TSX_TRY(joint_check(a, b, na, nb));
+    if (!matrix_out) return combine_fail("joint histogram: no matrix");
+    HIP_TRY(hipSetDevice(a->device));
+    DevBuf<uint64_t> d;
+    TSX_TRY(d.alloc(na * nb * sizeof(uint64_t)));
+    SyncAtExit wait_a(a->stream.get());   // nothing queued may outlive the matrix
+    TSX_TRY(tsx_hip_joint_histogram_device(a, b, na, nb, d.get(), nullptr));
+    HIP_TRY(hipMemcpyAsync(matrix_out, d.get(), na * nb * sizeof(uint64_t), hipMemcpyDeviceToHost, a->stream.get()));
+    HIP_TRY(hipStreamSynchronize(a->stream.get()));
+    return TSX_HIP_OK;
 }
 
 extern "C" int tsx_hip_owner_host(const tsx_hip_map *m, const uint64_t *kmer, int nranks) {

@@ -431,6 +431,14 @@ public:
         const uint64_t iUnion = s.a_in_range + s.b_in_range - s.both;
         return iUnion ? (double)s.both / (double)iUnion : 0.0;
     }
+    // joint spectrum of two tables (tsx_hip_joint_histogram_host): this is A, oOther is B; oMatrix[i * iNb + j] = distinct
+    // k-mers counted i times here and j times there, the last bin of each side pooling every larger count
+    void jointHistogram(TSXHashMapHIP &oOther, size_t iNa, size_t iNb, std::vector<uint64_t> &oMatrix) {
+        oMatrix.assign(iNa && iNb <= ((size_t)1 << 24) / iNa ? iNa * iNb : 0, 0);   // (a refused size allocates nothing)
+        const int rc = tsx_hip_joint_histogram_host(m_pMap, oOther.m_pMap, oMatrix.data(), iNa, iNb);
+        if (rc == TSX_HIP_EINVAL) throw TSXException(tsx_hip_last_error(), rc);   // (the refusal says which argument)
+        check(rc);
+    }
 
     // FASTXreader<FASTAEntry> (FastXReader.h:97-116) reads two lines per record, FASTQEntry (:62-95) four
     void setRecordLines(int iLines) { check(tsx_hip_set_record_lines(m_pMap, iLines)); }

@@ -9,6 +9,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -67,6 +68,11 @@ struct arguments {
     std::string op, op_count = "min";
     uint64_t a_lower = 1, a_upper = UINT64_MAX, b_lower = 1, b_upper = UINT64_MAX;
     bool compare = false;
+    // joint spectrum of the two tables: --joint-histo=FILE writes how many k-mers occur a times in A and b times in B,
+    // counts 0..H per side and one bin H+1 for everything above (--joint-max-a / --joint-max-b), as lines or as a matrix
+    std::string joint_histo, joint_format = "sparse";
+    uint64_t joint_max_a = 1000, joint_max_b = 1000;
+    bool joint_opts = false;   // --joint-max-a / --joint-max-b / --joint-format were given
     bool given_k = false, given_l = false, given_s = false, given_seed = false;
     // table sizing: --l=auto sketches --input first and counts into the l that holds its k-mers at --load-factor=F;
     // --estimate prints that line and stops
@@ -107,7 +113,8 @@ static int usage() {
                  "                [--filter-interleaved] [--trim-input=R1,R2 --trim=O1,O2] [--trim-singles=S1,S2]\n"
                  "                [--trim-interleaved] [--pair-names]\n"
                  "                [--with=DB[,DB2,...] [--op=intersect|union|subtract|diff] [--op-count=min|max|sum|left|right]\n"
-                 "                 [--a-lower=N] [--a-upper=N] [--b-lower=N] [--b-upper=N] [--compare]]\n"
+                 "                 [--a-lower=N] [--a-upper=N] [--b-lower=N] [--b-upper=N] [--compare]\n"
+                 "                 [--joint-histo=FILE [--joint-max-a=H] [--joint-max-b=H] [--joint-format=sparse|matrix]]]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
                  "--l=auto sizes the table itself: the input is sketched first (HyperLogLog, 2^14 registers, on the GPU), and l\n"
                  "is the smallest table that holds the estimated distinct k-mers at load F (--load-factor, default 0.75, at most\n"
@@ -180,7 +187,13 @@ static int usage() {
                  "only the k-mers of A / B counted that often. The result takes the table's place for --output, --histo,\n"
                  "--save, --filter and --read-stats. --compare prints compare<TAB>a<TAB>b<TAB>both<TAB>jaccard (distinct k-mers\n"
                  "of A, of B, of both, Jaccard index) and the summed counts of the shared k-mers. B must match A's k,\n"
-                 "--canonical, --acgt-only and --min-qual-char. One GPU only."
+                 "--canonical, --acgt-only and --min-qual-char. One GPU only.\n"
+                 "--joint-histo=FILE writes the joint spectrum of A and B (before --op replaces the table): how many distinct\n"
+                 "k-mers occur a times in A and b times in B, 0 for a table that lacks the k-mer. --joint-max-a=H and\n"
+                 "--joint-max-b=H (default 1000) give counts 0..H and one bin H+1 for everything above, per side.\n"
+                 "--joint-format=sparse (default) writes a<TAB>b<TAB>k-mers for every pair that occurs, ordered by a, then b;\n"
+                 "matrix writes a comment line, then H+2 lines of H+2 numbers, the line being the count in A. It prints\n"
+                 "joint<TAB>a_only<TAB>b_only<TAB>both (distinct k-mers). It needs --with; one GPU only."
               << std::endl;
     return 1;
 }
@@ -540,6 +553,29 @@ static void save_database(TSXHashMapHIP &oMap, const arguments &a) {
 }
 static void save_database(TSXHashMapHIPGroup &, const arguments &) {}
 
+// --joint-histo: the joint spectrum of A and B as a file, and its three sums on stdout
+static void write_joint(TSXHashMapHIP &oA, TSXHashMapHIP &oB, const arguments &a) {
+    const size_t na = (size_t)a.joint_max_a + 2, nb = (size_t)a.joint_max_b + 2;
+    std::vector<uint64_t> m;
+    oA.jointHistogram(oB, na, nb, m);
+    uint64_t a_only = 0, b_only = 0, both = 0;
+    std::ofstream f(a.joint_histo);
+    if (a.joint_format == "matrix")
+        f << "# rows: count in A 0.." << na - 1 << ", columns: count in B\n";
+    for (size_t i = 0; i < na; ++i) {
+        for (size_t j = 0; j < nb; ++j) {
+            const uint64_t n = m[i * nb + j];
+            (i == 0 ? b_only : j == 0 ? a_only : both) += n;
+            if (a.joint_format == "matrix") f << n << (j + 1 < nb ? '\t' : '\n');
+            else if (n) f << i << '\t' << j << '\t' << n << '\n';
+        }
+    }
+    f.close();
+    if (!f) throw TSXException("could not write " + a.joint_histo, TSX_HIP_EIO);
+    std::cout << "joint\t" << a_only << '\t' << b_only << '\t' << both << std::endl;
+    std::cerr << "Wrote the joint histogram to " << a.joint_histo << std::endl;
+}
+
 // --op / --op-count by name: the TSX_HIP_OP_* / TSX_HIP_CNT_* value, -1 for none given, -2 / -1 for an unknown one
 static int op_index(const std::string &s) {
     return s.empty() ? -1 : s == "intersect" ? TSX_HIP_OP_INTERSECT : s == "union" ? TSX_HIP_OP_UNION
@@ -757,6 +793,25 @@ int main(int argc, char *argv[]) {
         else if (opt(argv[i], "b-lower", v)) a.b_lower = strtoull(v.c_str(), nullptr, 10);
         else if (opt(argv[i], "b-upper", v)) a.b_upper = strtoull(v.c_str(), nullptr, 10);
         else if (opt(argv[i], "compare", v)) a.compare = true;
+        else if (opt(argv[i], "joint-histo", v)) { a.joint_histo = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "joint-max-a", v) || opt(argv[i], "joint-max-b", v)) {
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long h = strtoull(v.c_str(), &end, 10);
+            // (H + 2)^2 <= 2^24 for either side: H <= 4094
+            if (v.empty() || *end || errno || v[0] == '-' || h < 1 || h > 4094) {
+                std::cerr << "--joint-max-a / --joint-max-b take the largest count with a bin of its own: a number 1 .. 4094"
+                          << std::endl;
+                return usage();
+            }
+            (std::string(argv[i]).compare(0, 13, "--joint-max-a") == 0 ? a.joint_max_a : a.joint_max_b) = h;
+            a.joint_opts = true;
+        }
+        else if (opt(argv[i], "joint-format", v)) {
+            if (v != "sparse" && v != "matrix") { std::cerr << "--joint-format is sparse or matrix" << std::endl; return usage(); }
+            a.joint_format = v;
+            a.joint_opts = true;
+        }
         else if (opt(argv[i], "format", v)) a.format = v;
         else if (opt(argv[i], "device", v)) a.device = atoi(v.c_str());
         else if (opt(argv[i], "gpus", v)) { a.gpus = atoi(v.c_str()); a.group = true; }
@@ -907,8 +962,20 @@ int main(int argc, char *argv[]) {
         std::cerr << "--op and --compare need a second table: --with=DB[,DB2,...]" << std::endl;
         return usage();
     }
-    if (!a.with.empty() && a.op.empty() && !a.compare) {
-        std::cerr << "--with needs --op or --compare" << std::endl;
+    if ((!a.joint_histo.empty() || a.joint_opts) && a.with.empty()) {
+        std::cerr << "--joint-histo needs a second table: --with=DB[,DB2,...]" << std::endl;
+        return usage();
+    }
+    if (a.joint_opts && a.joint_histo.empty()) {
+        std::cerr << "--joint-max-a, --joint-max-b and --joint-format go with --joint-histo=FILE" << std::endl;
+        return usage();
+    }
+    if (!a.joint_histo.empty() && a.gpus > 1) {
+        std::cerr << "--joint-histo works on one GPU only: a --gpus " << a.gpus << " run keeps one table per GPU" << std::endl;
+        return usage();
+    }
+    if (!a.with.empty() && a.op.empty() && !a.compare && a.joint_histo.empty()) {
+        std::cerr << "--with needs --op, --compare or --joint-histo" << std::endl;
         return usage();
     }
     if (!a.with.empty() && a.gpus > 1) {
@@ -1189,6 +1256,7 @@ int main(int argc, char *argv[]) {
                       << TSXHashMapHIP::jaccard(s) << std::endl;
             std::cout << "compare-sums\t" << s.a_sum_both << '\t' << s.b_sum_both << std::endl;
         }
+        if (!a.joint_histo.empty()) write_joint(oMap, oWith, a);
         if (a.op.empty()) {
             if (!wants_queries(a) && !wants_trim(a)) return rc;
             const int rq = run_after(oMap.handle(), a);
