@@ -15,9 +15,11 @@ conftest.python_counts of the text (or the dictionary a case builds itself); not
   (e) text-space twins  kmer_eq of the atomic scan kernel and of the sketch kernel
   (f) strand ties       key_less / key_min / lex_canonical of canonical tables
 
-Not reached, on purpose (see twin_design): the spill cache of the skewed level-2 form, the "homeless" merge of
-partition_ring_kernel and the hot-key cache of the walk need a skewed bucket or homopolymers; the multi-GPU exchanges
-and tables above 2^32 slots are out of scope too."""
+The compares behind a full list -- the spill cache of the skewed level-2 form, the "homeless" merge of
+partition_ring_kernel, the sub-list-full exit of the fused walk -- need a skewed bucket: tests/test_twin_keys_skew.py
+counts families through them, tests/test_twin_keys_skew_cpu.py shows on a model that those texts tell a wrong compare
+from a right one.  Not reached (see twin_design): the walk's per-wave hot-key cache holds homopolymer keys only, so no
+twin can be designed into it (a totals case there); the multi-GPU exchanges and tables above 2^32 slots are out of scope."""
 import functools
 import os
 import random

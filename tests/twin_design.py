@@ -13,9 +13,20 @@ with them.  These families make it occur at every compare site of the table:
                   run-length leader test of the scan, sketch and query kernels compares a window with the one before)
     strand_ties   k-mers whose two strand keys h(x), h(rc x) agree in the whole top limb and differ below it (key_less)
 
-What these do NOT reach, on purpose: the spill cache of the skewed level-2 form (spill_record), the "homeless" merge of
-partition_ring_kernel and the hot-key cache of the walk.  Those compare keys too, but only a skewed bucket or
-homopolymers get there; designing such texts is a second piece of work."""
+The compares behind a full list -- the spill cache of the skewed level-2 form (spill_record), the "homeless" merge of
+partition_ring_kernel, the one-place cache of the fused walk's sub-list-full exit -- see keys only when a bucket is
+skewed.  For them (tests/test_twin_keys_skew_cpu.py, tests/test_twin_keys_skew.py):
+
+    hot_h0_families  h0_twins of which two start at one place of the spill cache (spill_places restates its place function)
+    half_twins       one-word keys of one segment that agree outside one 32-bit half of the word
+    skew_text        one k-mer per read, the family interleaved, then one member back to back, then interleaved again,
+                     between ordinary synthetic reads
+    model_counts     a Python model of the two compare sites with the compare as a parameter: what a weakened compare
+                     would do to such a text -- the kernels themselves are never made wrong
+
+What these do NOT reach: the walk's per-wave hot-key cache holds the four homopolymer keys only (s_homh), so no twin can be
+designed into it (it gets a totals case); the plain (not SKEW) form's one-probe cache sees these families only where the
+skew probe does not flag their bucket; the multi-GPU exchanges and tables above 2^32 slots are out of scope."""
 import random
 
 import numpy as np
@@ -79,19 +90,24 @@ def key_twins(lay, inv, home, T, field, seed, taken=()):
     raise ValueError("no family found")
 
 
-def h0_twins(k, inv, T, t, seed, taken=(), accept=None):
+def h0_twins(k, inv, T, t, seed, taken=(), accept=None, fix=None):
     """T k-mers whose hashed keys agree in every 64-bit limb except limb t (1 <= t < key limbs), where they all differ:
     one h[0], hence one home slot.  accept(key) -> bool, when given, picks among the candidates (a test may steer the
-    keys further).  Returns (k-mers, hashed keys as ints)."""
+    keys further); fix = (mask, value) sets the bits of the common part under mask (outside limb t) to value.
+    Returns (k-mers, hashed keys as ints)."""
     wk = (2 * k + 63) // 64
     if not 1 <= t < wk:
         raise ValueError("limb %d of %d" % (t, wk))
     width = min(64, 2 * k - 64 * t)
     if (1 << width) < T:
         raise ValueError("limb %d holds %d key bits: no %d different values" % (t, width, T))
+    if fix is not None and fix[0] & (((1 << width) - 1) << (64 * t)):
+        raise ValueError("fix reaches into limb %d" % t)
     rng = random.Random(seed)
     for _ in range(64):
         base = rng.getrandbits(2 * k) & ~(((1 << width) - 1) << (64 * t))
+        if fix is not None:
+            base = (base & ~fix[0]) | (fix[1] & fix[0])
         keys, seen = [], set()
         for _ in range(4096 * T):
             v = rng.getrandbits(width)
@@ -232,3 +248,196 @@ def random_rows(k, seed):
             return rows
         except ValueError:
             continue
+
+
+# ---- the compares behind a full list: spill cache, homeless merge ------------------------------------------------------------
+
+PHI = 0x9E3779B97F4A7C15
+M32 = (1 << 32) - 1
+OVF_N = 64            # places of the spill cache (tsx_partition.h)
+OVF_PROBES = 4        # places spill_record looks at for one key
+OVQ_CAP = 2048        # records of one workgroup's overflow queue (tsxcount_hip.hip)
+
+
+def mix64(z):
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & kmerdb.M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & kmerdb.M64
+    return z ^ (z >> 31)
+
+
+def rec_words(k):
+    """Words of a record of the partitioned path: the key limbs padded to 1, 2 or 4."""
+    wk = (2 * k + 63) // 64
+    return wk if wk <= 2 else 4
+
+
+def record(key, k):
+    return tuple((key >> (64 * t)) & kmerdb.M64 for t in range(rec_words(k)))
+
+
+def record_places(w):
+    """The places of the spill cache spill_record probes for the record w (a tuple of words), in order.  The walk's
+    sub-list-full exit (one-word records) looks at the first of them only."""
+    mixin = w[0]
+    for x in w[1:]:
+        mixin ^= (x * PHI) & kmerdb.M64
+    s = (mix64(mixin) >> 40) & (OVF_N - 1)
+    return [(s + i) & (OVF_N - 1) for i in range(OVF_PROBES)]
+
+
+def spill_places(key, k):
+    return record_places(record(key, k))
+
+
+def meeting_pairs(keys, k):
+    """Pairs of keys that START at one place of the spill cache.  Their probe sequences are the same, places are never
+    given back, so whichever of the two is admitted first sits at a place the other one looks at before it finds a free
+    one: the compare of the other words (one-word records: of the whole word) runs between two different keys whatever
+    the order of the claims -- unless strangers hold all four places, and then neither is cached."""
+    first = [spill_places(key, k)[0] for key in keys]
+    return [(i, j) for i in range(len(keys)) for j in range(i + 1, len(keys)) if first[i] == first[j]]
+
+
+def overlapping_pairs(keys, k):
+    """Pairs of keys whose four-place probe windows share a place (the weaker condition: they MAY meet)."""
+    win = [set(spill_places(key, k)) for key in keys]
+    return [(i, j) for i in range(len(keys)) for j in range(i + 1, len(keys)) if win[i] & win[j]]
+
+
+def radix_split(l, S):
+    """(b1, b2): the radix bits of level 1 and level 2 for 2^(l - S) segments, as radix_bits of tsxcount_hip.hip."""
+    n = l - S
+    b1 = min(9, n if n <= 8 else (n + 1) // 2)
+    return b1, n - b1
+
+
+def list_of(key, l, S):
+    """(level-1 bucket, level-2 list) of a hashed key: partition_ring_kernel takes bq = (w[0] >> shift) & (nb - 1) with
+    shift = l - b1, nb = 2^b1 at level 1 and shift = S, nb = 2^b2 at level 2 (run_partition_build): bits S .. l - 1 of
+    word 0 together, the number of the key's segment."""
+    b1, b2 = radix_split(l, S)
+    return (key >> (l - b1)) & ((1 << b1) - 1), (key >> S) & ((1 << b2) - 1)
+
+
+def hot_h0_families(k, inv, T, t, seed, taken=(), accept=None, fix=None, rows=None, canonical=False):
+    """h0_twins(k, inv, T, t) -- T k-mers whose records agree in every 64-bit word but word t, so one level-1 bucket, one
+    segment, one set of level-2 sub-lists -- of which at least two start at one place of the spill cache (meeting_pairs).
+    canonical (needs the map's rows): every member's own strand carries the smaller key, so the record after the strand
+    choice is the designed key, and no member is another's reverse complement.  ValueError when no seed gives that."""
+    for attempt in range(400):
+        try:
+            kmers, keys = h0_twins(k, inv, T * (4 if canonical else 1), t, seed * 1000 + attempt, taken, accept, fix)
+        except ValueError as e:
+            if "limb" in str(e):          # the shape has no such family: no other seed will find one
+                raise
+            continue
+        if canonical:
+            hr = kmerdb.table_keys([kmerdb.revcomp(x) for x in kmers], rows, k)
+            keep = [i for i in range(len(keys)) if keys[i] < hr[i]][:T]
+            if len(keep) < T:
+                continue
+            kmers, keys = [kmers[i] for i in keep], [keys[i] for i in keep]
+            if {kmerdb.revcomp(x) for x in kmers} & set(kmers):
+                continue
+        if not meeting_pairs(keys, k):
+            continue
+        words = [record(key, k) for key in keys]
+        assert all(len({w[u] for w in words}) == (T if u == t else 1) for u in range(rec_words(k))), "not twins in word %d" % t
+        return kmers, keys
+    raise ValueError("no family of %d twins in word %d meets in the spill cache" % (T, t))
+
+
+def half_twins(k, inv, T, half, l, S, seed, taken=()):
+    """T k-mers of one-word keys (k <= 32) whose hashed keys agree in every bit outside one 32-bit half of the word ("lo":
+    bits 0 .. 31, "hi": bits 32 .. 2k - 1) and in the bits that pick the list at both radix levels (list_of: bits
+    S .. l - 1), and of which two start at one place of the spill cache.  Returns (k-mers, keys)."""
+    n = 2 * k
+    if n > 64 or half not in ("lo", "hi"):
+        raise ValueError("half twins are for one-word records: k = %d, half %r" % (k, half))
+    a, b = (0, min(32, n)) if half == "lo" else (32, n)
+    free = (((1 << b) - 1) & ~((1 << a) - 1)) & ~(((1 << l) - 1) & ~((1 << S) - 1)) if b > a else 0
+    if (1 << bin(free).count("1")) < 4 * T:
+        raise ValueError("the %s half of a %d-bit key leaves no %d values outside the list bits" % (half, n, T))
+    for attempt in range(400):
+        rng = random.Random(seed * 1000 + attempt)
+        base = rng.getrandbits(n) & ~free
+        vals = set()
+        while len(vals) < T:
+            vals.add(rng.getrandbits(n) & free)
+        keys = [base | v for v in sorted(vals, key=lambda v: rng.random())]
+        if not meeting_pairs(keys, k):
+            continue
+        kmers = kmerdb.keys_to_kmers(keys, inv, k)
+        if not _usable(kmers, taken):
+            continue
+        assert len({list_of(key, l, S) for key in keys}) == 1, "the family does not share one list"
+        other = ~(M32 if half == "lo" else M32 << 32)
+        assert len({key & other for key in keys}) == 1 and len(set(keys)) == T
+        return kmers, keys
+    raise ValueError("no family found")
+
+
+def skew_text(members, rounds, b2b, tail, cold_before=b"", cold_after=b"", strand=None):
+    """(text, the family's reads in text order).  Every family read is exactly one k-mer: one window per read, so the
+    records reach the kernels in the order of the text.  `rounds` times the members interleaved (A, B, C, ..., A, B, C, ...:
+    twins sit in neighbouring lanes of a wave's batch, and a member comes back within 64 records when there are at most
+    32 of them), then member 0 `b2b` times back to back (a run of equal records: combined records of d >= 2 certainly
+    form), then `tail` rounds interleaved again (twins that come AFTER the admission).  strand(x, round) may pick the
+    strand a round shows (canonical cases); cold_before / cold_after: FASTQ texts around the family."""
+    show = strand if strand is not None else (lambda x, r: x)
+    seqs = [show(x, r) for r in range(rounds) for x in members]
+    seqs += [show(members[0], j) for j in range(b2b)]
+    seqs += [show(x, r) for r in range(tail) for x in members]
+    fam = b"".join(b"@t%d\n%s\n+\n%s\n" % (i, s, b"I" * len(s)) for i, s in enumerate(seqs))
+    return cold_before + fam + cold_after, seqs
+
+
+COMPARES = {
+    "exact": lambda a, b: a == b,
+    "word 0 only": lambda a, b: a[0] == b[0],
+    "low halves only": lambda a, b: all((x & M32) == (y & M32) for x, y in zip(a, b)),
+    "high halves only": lambda a, b: all((x >> 32) == (y >> 32) for x, y in zip(a, b)),
+}
+
+
+def all_words_but(t):
+    return lambda a, b: all(x == y for u, (x, y) in enumerate(zip(a, b)) if u != t)
+
+
+def model_counts(recs, cap, same):
+    """A model of what one level-2 workgroup of the SKEW form does with the records `recs` (tuples of words, in order) of
+    one segment whose list holds `cap` records, with the key compare `same(a, b)` as a parameter.  The first cap records
+    stay in the list.  The others are homeless: in runs of 64 (a wave's lanes), twice, the first record left is compared
+    with all the others and those that are `same` leave as one entry with their number; the rest go one by one.  What
+    leaves goes to the cache: 64 places, four probed per record (record_places), a free place is taken only by an entry
+    of two or more, an entry that is `same` as the one in the place adds to it; what is not cached is inserted on its own
+    (overflow queue, deferred list).  Returns {record: count}.  With the exact compare that is the plain count of recs."""
+    from collections import Counter
+    out = Counter(recs[:cap])
+    cache = [None] * OVF_N
+
+    def spill(rec, d):
+        for p in record_places(rec):
+            if cache[p] is None:
+                if d < 2:
+                    break
+                cache[p] = [rec, d]
+                return
+            if same(cache[p][0], rec):
+                cache[p][1] += d
+                return
+        out[rec] += d
+
+    for i in range(cap, len(recs), 64):
+        run = list(recs[i:i + 64])
+        for _ in range(2):
+            if run:
+                first = run[0]
+                spill(first, sum(1 for r in run if same(r, first)))
+                run = [r for r in run if not same(r, first)]
+        for r in run:
+            spill(r, 1)
+    for e in cache:
+        if e is not None:
+            out[e[0]] += e[1]
+    return out
