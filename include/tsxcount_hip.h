@@ -786,6 +786,68 @@ int tsx_hip_combine(tsx_hip_map *out, tsx_hip_map *a, tsx_hip_map *b, const tsx_
 int tsx_hip_joint_histogram_device(tsx_hip_map *a, tsx_hip_map *b, size_t na, size_t nb, void *dev_matrix, void *stream);
 int tsx_hip_joint_histogram_host(tsx_hip_map *a, tsx_hip_map *b, uint64_t *matrix_out, size_t na, size_t nb);
 
+/*
+ * Read binning by two tables (csrc/tsx_bin.h; no reference counterpart -- trio binning with hapmers as Canu and Merqury
+ * do it, BBSplit, xenograft sorting): ONE scan of a text against two tables, per record the windows that hit A and the
+ * windows that hit B, and from those the table the record belongs to.  Records, lines, k-mers, the stand-in code,
+ * canonical keys and the base rule are those of tsx_hip_query_reads_*.
+ *   A, B     two whole tables (none created with shard_bits > 0) on one device that agree in k, canonical mode and base
+ *            rule; l, storage bits, overflow_l and hash seed may differ (the conditions of tsx_hip_combine).  a == b is
+ *            allowed.  a(x) and b(x) are getKmerCount(x) in A and in B, carries from the secondary array included, 0
+ *            when x is absent.
+ *   stats    per record (tsx_hip_bin_stats): kmers as in tsx_hip_read_stats (under a base rule only the windows that are
+ *            k-mers); hits_a = the windows with a_lower <= a(x) <= a_upper, with multiplicity; hits_b the same for B
+ *            with b_lower .. b_upper; hits_both = the windows in range in both.  A lower bound of 0 is taken as 1, as
+ *            in tsx_hip_combine.
+ *   rule     qa = hits_a >= min_hits, qb = hits_b >= min_hits;
+ *            wins_a = qa && hits_a > hits_b && hits_a * 1000 >= ratio_milli * hits_b, wins_b its mirror image;
+ *            1000 <= ratio_milli <= 1000000 (the products fit 64 bits: a sequence line is shorter than 4 GiB).
+ *            min_hits = 1 and ratio_milli = 1000 are the plain rule: more hits wins, ties win nothing.
+ *   class    TSX_HIP_BIN_A if wins_a, TSX_HIP_BIN_B if wins_b (they cannot hold together), TSX_HIP_BIN_NONE if neither qa
+ *            nor qb, TSX_HIP_BIN_AMBIGUOUS otherwise.  A record without k-mers is NONE when min_hits >= 1; min_hits = 0
+ *            is legal and makes every record at least AMBIGUOUS.
+ *   output   tsx_hip_bin_io names one file descriptor per class; -1 counts the class and writes nothing.  A written
+ *            record is its bytes exactly as tsx_hip_filter_reads_* writes a kept record (the added '\n' included, empty
+ *            lines not written).  Every output is in input order; every record lands in exactly one class.
+ *   totals   records, n[class], bytes[class] (0 for a dropped output).
+ *   bin_stats_device  dev_text as tsx_hip_query_reads_device takes it; the stats of records [0, stats_cap) to dev_stats
+ *                     (zeroed by the call), queued on `stream` (NULL = A's own).  WAITS and reports the record count;
+ *                     more records than stats_cap: TSX_HIP_ERANGE (the first stats_cap are written).
+ *   bin_stats_host    text in host memory, in pieces as tsx_hip_query_reads_host (chunk_bytes, 0 = 256 MiB); stats_out
+ *                     and, when class_out is not NULL, one class byte per record, for records [0, stats_cap).
+ *   bin_reads_host    the same pieces; the device compacts the outputs of a piece while the host writes those of the
+ *                     piece before.  A failed write: TSX_HIP_EIO.
+ * The calls wait for what is queued on both maps' own streams before they start.  A and B are left as they are, bit for
+ * bit (a lazily cleared table is zeroed first, as everywhere).
+ * TSX_HIP_EINVAL before any device call (tsx_hip_last_error says which): a NULL rule, lower > upper on either side,
+ * ratio_milli outside 1000 .. 10^6, reserved != 0, io == NULL or every fd of io equal to -1, a NULL map, a map created
+ * with shard_bits > 0, maps on different devices, a different k, canonical mode or base rule.
+ */
+enum { TSX_HIP_BIN_A = 0, TSX_HIP_BIN_B = 1, TSX_HIP_BIN_AMBIGUOUS = 2, TSX_HIP_BIN_NONE = 3 };
+typedef struct tsx_hip_bin_stats {
+    uint64_t kmers, hits_a, hits_b, hits_both;
+} tsx_hip_bin_stats;
+typedef struct tsx_hip_bin_rule {
+    uint64_t a_lower, a_upper;   /* the count range of a hit in A */
+    uint64_t b_lower, b_upper;   /* ... in B */
+    uint64_t min_hits;           /* hits a side needs to qualify */
+    uint32_t ratio_milli;        /* the winner's hits are at least this many thousandths of the loser's */
+    int32_t reserved;            /* 0 */
+} tsx_hip_bin_rule;
+typedef struct tsx_hip_bin_io {
+    int fd_a, fd_b, fd_ambiguous, fd_none;
+} tsx_hip_bin_io;
+typedef struct tsx_hip_bin_totals {
+    uint64_t records, n[4], bytes[4];   /* n and bytes by class */
+} tsx_hip_bin_totals;
+int tsx_hip_bin_stats_device(tsx_hip_map *a, tsx_hip_map *b, const void *dev_text, size_t n, const tsx_hip_bin_rule *rule,
+                             void *dev_stats, size_t stats_cap, size_t *n_records, void *stream);
+int tsx_hip_bin_stats_host(tsx_hip_map *a, tsx_hip_map *b, const char *text, size_t n, const tsx_hip_bin_rule *rule,
+                           tsx_hip_bin_stats *stats_out, uint8_t *class_out /* optional, one byte per record */,
+                           size_t stats_cap, size_t *n_records, size_t chunk_bytes);
+int tsx_hip_bin_reads_host(tsx_hip_map *a, tsx_hip_map *b, const char *text, size_t n, const tsx_hip_bin_rule *rule,
+                           const tsx_hip_bin_io *io, size_t chunk_bytes, tsx_hip_bin_totals *totals /* optional */);
+
 /* IBijectiveFunction::apply / inv_apply (IBijectiveFunction.h:26-27) on the host,
  * and the matrix rows (row i <-> output bit 2k-1-i, BijectiveKMapping.h:202-256). */
 int tsx_hip_hash_apply(const tsx_hip_map *m, const uint64_t *kmer, uint64_t *key_out);

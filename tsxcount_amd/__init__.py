@@ -359,6 +359,55 @@ def joint_histogram(A, B, bins_a=1002, bins_b=1002):
     return m
 
 
+class BinRule(ctypes.Structure):
+    """tsx_hip_bin_rule."""
+    _fields_ = [("a_lower", ctypes.c_uint64), ("a_upper", ctypes.c_uint64), ("b_lower", ctypes.c_uint64),
+                ("b_upper", ctypes.c_uint64), ("min_hits", ctypes.c_uint64), ("ratio_milli", ctypes.c_uint32),
+                ("reserved", ctypes.c_int32)]
+
+
+class BinIO(ctypes.Structure):
+    """tsx_hip_bin_io: one file descriptor per class, -1 = counted and not written."""
+    _fields_ = [("fd_a", ctypes.c_int), ("fd_b", ctypes.c_int), ("fd_ambiguous", ctypes.c_int), ("fd_none", ctypes.c_int)]
+
+
+class BinTotals(ctypes.Structure):
+    """tsx_hip_bin_totals."""
+    _fields_ = [("records", ctypes.c_uint64), ("n", ctypes.c_uint64 * 4), ("bytes", ctypes.c_uint64 * 4)]
+
+    def as_dict(self):
+        return {"records": int(self.records), "n": [int(v) for v in self.n], "bytes": [int(v) for v in self.bytes]}
+
+
+BIN_A, BIN_B, BIN_AMBIGUOUS, BIN_NONE = 0, 1, 2, 3   # TSX_HIP_BIN_*: the class of a record
+BIN_NAMES = ("a", "b", "ambiguous", "none")
+BIN_STATS_DTYPE = np.dtype([("kmers", np.uint64), ("hits_a", np.uint64), ("hits_b", np.uint64), ("hits_both", np.uint64)])
+
+
+def bin_class(hits_a, hits_b, min_hits=1, ratio_milli=1000):
+    """The class rule of the bin calls on the CPU (plain integers): a side qualifies with hits >= min_hits and wins when
+    it qualifies, has more hits than the other and hits * 1000 >= ratio_milli * the other's; no side qualifies: BIN_NONE;
+    nobody wins: BIN_AMBIGUOUS."""
+    ha, hb, mh, rm = int(hits_a), int(hits_b), int(min_hits), int(ratio_milli)
+    if not 1000 <= rm <= 1000000:
+        raise ValueError("bin_class: 1000 <= ratio_milli <= 1000000")
+    qa, qb = ha >= mh, hb >= mh
+    if qa and ha > hb and ha * 1000 >= rm * hb:
+        return BIN_A
+    if qb and hb > ha and hb * 1000 >= rm * ha:
+        return BIN_B
+    return BIN_AMBIGUOUS if (qa or qb) else BIN_NONE
+
+
+def bin_rule(a_range=(1, None), b_range=(1, None), min_hits=1, ratio=1.0):
+    """A BinRule from the Python arguments: each range as (lower, upper) with None = no upper bound, the ratio as a
+    number >= 1 (three decimal places kept)."""
+    top = (1 << 64) - 1
+    return BinRule(int(a_range[0]), top if a_range[1] is None else int(a_range[1]),
+                   int(b_range[0]), top if b_range[1] is None else int(b_range[1]),
+                   int(min_hits), min(max(int(round(float(ratio) * 1000)), 0), (1 << 32) - 1), 0)
+
+
 def build():
     """Compile the library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     import subprocess
@@ -450,6 +499,10 @@ def lib():
     L.tsx_hip_combine.argtypes = [vp, vp, vp, ctypes.POINTER(CombineRule), ctypes.POINTER(CombineStats)]
     L.tsx_hip_joint_histogram_device.argtypes = [vp, vp, sz, sz, vp, vp]
     L.tsx_hip_joint_histogram_host.argtypes = [vp, vp, u64p, sz, sz]
+    L.tsx_hip_bin_stats_device.argtypes = [vp, vp, vp, sz, ctypes.POINTER(BinRule), vp, sz, ctypes.POINTER(sz), vp]
+    L.tsx_hip_bin_stats_host.argtypes = [vp, vp, ctypes.c_char_p, sz, ctypes.POINTER(BinRule), vp, vp, sz, ctypes.POINTER(sz), sz]
+    L.tsx_hip_bin_reads_host.argtypes = [vp, vp, ctypes.c_char_p, sz, ctypes.POINTER(BinRule), ctypes.POINTER(BinIO), sz,
+                                         ctypes.POINTER(BinTotals)]
     L.tsx_hip_group_histogram_host.argtypes = [vp, u64p, sz]
     L.tsx_hip_group_write_counts_host.argtypes = [vp, ci, u64, u64, sz, u64p, u64p]
     L.tsx_hip_query_reads_device.argtypes = [vp, vp, sz, u64, u64, vp, sz, ctypes.POINTER(sz), vp]
@@ -876,6 +929,64 @@ class TSXHashMapHIP:
         vp = ctypes.c_void_p
         self._check_joint(self._lib.tsx_hip_joint_histogram_device(self.handle, other.handle, int(bins_a), int(bins_b),
                                                                    vp(matrix_ptr), vp(stream) if stream else None))
+
+    def binStats(self, other, text, a_range=(1, None), b_range=(1, None), min_hits=1, ratio=1.0, chunk_bytes=0):
+        """Hits of every record of a FASTQ / FASTA text in two tables, in one scan (tsx_hip_bin_stats_host): self is A,
+        `other` is B.  Returns (stats, classes): a numpy structured array (BIN_STATS_DTYPE: kmers, hits_a, hits_b,
+        hits_both) and a uint8 array of BIN_A / BIN_B / BIN_AMBIGUOUS / BIN_NONE, one entry per record in text order.
+        A window hits a table when its count there lies in the table's range; bin_class() states the class rule."""
+        b = bytes(text)
+        rule = bin_rule(a_range, b_range, min_hits, ratio)
+        cap = len(b) // 256 + 16
+        for _ in range(2):
+            out = np.zeros(cap, dtype=BIN_STATS_DTYPE)
+            cls = np.zeros(cap, dtype=np.uint8)
+            n = ctypes.c_size_t(0)
+            rc = self._lib.tsx_hip_bin_stats_host(self.handle, other.handle, b, len(b), ctypes.byref(rule),
+                                                  out.ctypes.data_as(ctypes.c_void_p), cls.ctypes.data_as(ctypes.c_void_p), cap,
+                                                  ctypes.byref(n), int(chunk_bytes))
+            if rc != ERANGE:
+                break
+            cap = n.value
+        self._check_joint(rc)
+        return out[:n.value], cls[:n.value]
+
+    def binStatsDevice(self, other, text_ptr, nbytes, stats_ptr, cap, a_range=(1, None), b_range=(1, None), min_hits=1,
+                       ratio=1.0, stream=None):
+        """tsx_hip_bin_stats_device: the bin stats of the records of a device text into a device buffer of cap records
+        (4 uint64 each).  Waits; returns the record count (more than cap: TSXException ERANGE)."""
+        vp = ctypes.c_void_p
+        rule = bin_rule(a_range, b_range, min_hits, ratio)
+        n = ctypes.c_size_t(0)
+        self._check_joint(self._lib.tsx_hip_bin_stats_device(self.handle, other.handle, vp(text_ptr), nbytes, ctypes.byref(rule),
+                                                             vp(stats_ptr), cap, ctypes.byref(n), vp(stream) if stream else None))
+        return int(n.value)
+
+    def binReads(self, other, text, out_a=None, out_b=None, out_ambiguous=None, out_none=None, a_range=(1, None),
+                 b_range=(1, None), min_hits=1, ratio=1.0, chunk_bytes=0):
+        """Split the records of `text` by the table they hit more (tsx_hip_bin_reads_host): self is A, `other` is B.
+        Each output is a path (created or truncated), an open file descriptor, or None (the class is counted and not
+        written); at least one is needed.  Returns the totals as a dict: records, n[class], bytes[class]."""
+        b = bytes(text)
+        rule = bin_rule(a_range, b_range, min_hits, ratio)
+        opened, fds = [], []
+        try:
+            for o in (out_a, out_b, out_ambiguous, out_none):
+                if o is None:
+                    fds.append(-1)
+                elif isinstance(o, int):
+                    fds.append(o)
+                else:
+                    fds.append(os.open(o, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644))
+                    opened.append(fds[-1])
+            io, tot = BinIO(*fds), BinTotals()
+            rc = self._lib.tsx_hip_bin_reads_host(self.handle, other.handle, b, len(b), ctypes.byref(rule), ctypes.byref(io),
+                                                  int(chunk_bytes), ctypes.byref(tot))
+        finally:
+            for fd in opened:
+                os.close(fd)
+        self._check_joint(rc)
+        return tot.as_dict()
 
     def queryReads(self, text, lower=1, upper=None, chunk_bytes=0):
         """Per-record k-mer stats of a FASTQ / FASTA text against the table (tsx_hip_query_reads_host): a numpy

@@ -12,6 +12,7 @@
 #include "tsx_db.h"
 #include "tsx_combine.h"
 #include "tsx_joint.h"
+#include "tsx_bin.h"
 #include "tsx_fasta.h"
 #include "tsx_trim.h"
 #include "tsx_normalize.h"
@@ -4559,6 +4560,218 @@ extern "C" int tsx_hip_filter_reads_device(tsx_hip_map *m, const void *dev_text,
     if (out_bytes) *out_bytes = (size_t)total;
     if (kept_out) *kept_out = kept;
     return rc;
+}
+
+// ---- read binning by two tables: hits in A and in B per record, one output per class (tsx_bin.h) ------------------
+static int bin_fail(const char *why) { g_last_error = why; return TSX_HIP_EINVAL; }
+
+// What the bin calls refuse, before any device call: the rule first, then the tables (the conditions of tsx_hip_combine).
+static int bin_rule_check(const tsx_hip_bin_rule *r) {
+    if (!r) return bin_fail("bin: no rule");
+    if (std::max<uint64_t>(1, r->a_lower) > r->a_upper) return bin_fail("bin: a_lower > a_upper");
+    if (std::max<uint64_t>(1, r->b_lower) > r->b_upper) return bin_fail("bin: b_lower > b_upper");
+    if (r->ratio_milli < 1000u || r->ratio_milli > 1000000u) return bin_fail("bin: ratio_milli outside 1000 .. 1000000");
+    if (r->reserved != 0) return bin_fail("bin: reserved is not 0");
+    return TSX_HIP_OK;
+}
+static int bin_check(const tsx_hip_map *a, const tsx_hip_map *b, const tsx_hip_bin_rule *r) {
+    TSX_TRY(bin_rule_check(r));
+    if (!a || !b) return bin_fail("bin: a and b are needed");
+    if (a->p.lg != a->p.l || b->p.lg != b->p.l) return bin_fail("bin: a shard of a multi-GPU table");
+    if (b->device != a->device) return bin_fail("bin: the tables are on different devices");
+    if (b->p.k != a->p.k) return bin_fail("bin: the tables differ in k");
+    if (b->canon != a->canon) return bin_fail("bin: the tables differ in canonical mode");
+    if (b->p.acgt_only != a->p.acgt_only || b->minq != a->minq) return bin_fail("bin: the tables differ in base rule");
+    return base_rule_ok(a);
+}
+static int bin_io_check(const tsx_hip_bin_io *io) {
+    if (!io) return bin_fail("bin: no outputs (io is NULL)");
+    if (io->fd_a == -1 && io->fd_b == -1 && io->fd_ambiguous == -1 && io->fd_none == -1)
+        return bin_fail("bin: every output of io is -1");
+    return TSX_HIP_OK;
+}
+
+// Behind everything queued on the two maps (a caller's stream of an earlier call too); lazily cleared tables are zeroed
+// before anyone reads them.  Both maps' streams are idle afterwards: B's has nothing left for A's to wait for.
+static int bin_begin(tsx_hip_map *a, tsx_hip_map *b) {
+    HIP_TRY(hipSetDevice(a->device));
+    for (tsx_hip_map *m : {a, b}) {
+        join_foreign(m, true);
+        TSX_TRY(ensure_zeroed(m, m->stream.get()));
+        if (m->join_ev.get()) {   // (B's stream in front of A's by an event, then the wait the contract asks for)
+            HIP_TRY(hipEventRecord(m->join_ev.get(), m->stream.get()));
+            HIP_TRY(hipStreamWaitEvent(a->stream.get(), m->join_ev.get(), 0));
+        }
+        HIP_TRY(hipStreamSynchronize(m->stream.get()));
+    }
+    return TSX_HIP_OK;
+}
+
+// bin_reads_kernel over the start positions [0, own_end) of d_text (n readable bytes), after line_pass on A's scratch.
+// One LUT when A and B hash alike (the same seed makes the same mapping for one k).
+static int bin_launch(tsx_hip_map *a, const tsx_hip_map *b, const uint8_t *d_text, uint64_t n, uint64_t own_end, int head_open,
+                      const unsigned long long *d_line_base, const tsx_hip_bin_rule &r, unsigned long long *d_stats, uint64_t cap,
+                      hipStream_t st) {
+    if (own_end == 0) return TSX_HIP_OK;
+    const uint64_t ntiles = (own_end + TILE - 1) / TILE;
+    const bool one = a->seed == b->seed && a->lut == b->lut;
+    const size_t lds = a->lut.size() * 8 * (one ? 1 : 2);
+    const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)a->cus * 4);
+    const uint32_t lshift = a->p.line_mask == 3 ? 2u : 1u;
+    const BinRanges rg = {std::max<uint64_t>(1, r.a_lower), r.a_upper, std::max<uint64_t>(1, r.b_lower), r.b_upper};
+    hipError_t attr = hipSuccess;
+#define TSX_BIN(FORMV)                                                                                                       \
+    {                                                                                                                        \
+        auto kern = (bin_reads_kernel<WKV, CANV, BRV, FORMV>);                                                               \
+        attr = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
+        if (attr == hipSuccess)                                                                                              \
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a->p, b->p, d_text, n, own_end, head_open,               \
+                               (const uint32_t *)a->d_tile.get(), ntiles, d_line_base, lshift, rg, d_stats, cap, a->qmap_cur); \
+    }
+    if (one) { DISPATCH_BR(a, DISPATCH_CANON(a, DISPATCH_WK(a, TSX_BIN(BIN_ONE_LUT)))); }
+    else { DISPATCH_BR(a, DISPATCH_CANON(a, DISPATCH_WK(a, TSX_BIN(BIN_TWO_LUT)))); }
+#undef TSX_BIN
+    HIP_TRY(attr);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_bin_stats_device(tsx_hip_map *a, tsx_hip_map *b, const void *dev_text, size_t n, const tsx_hip_bin_rule *rule,
+                                        void *dev_stats, size_t stats_cap, size_t *n_records, void *stream) {
+    if (n_records) *n_records = 0;
+    TSX_TRY(bin_check(a, b, rule));
+    if ((!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_stats && stats_cap)) return bin_fail("bin: the text or the stats pointer");
+    TSX_TRY(bin_begin(a, b));
+    hipStream_t st = pick_stream(a, stream);
+    const uint8_t *base = (const uint8_t *)dev_text;
+    unsigned long long *stats = (unsigned long long *)dev_stats;
+    if (stats_cap) HIP_TRY(hipMemsetAsync(stats, 0, stats_cap * sizeof(tsx_hip_bin_stats), st));
+    TSX_TRY(device_windows(a, base, n, false, st,
+                           [&](size_t off, size_t own, size_t len, int head_open, bool, const unsigned long long *d_base) {
+                               return bin_launch(a, b, base + off, len, own, head_open, d_base, *rule, stats, stats_cap, st);
+                           }));
+    return windows_records(a, stats_cap, n_records, st);
+}
+
+// One output of a bin call: the lengths of its class (scanned in place) and the compacted bytes.
+struct BinOut {
+    DevBuf<unsigned long long> off;
+    OutBuf out;
+};
+// Scratch of one bin call that works on pieces.  words: the records of each class [0..4), the bytes of each output [4..8).
+struct BinBufs {
+    DevBuf<unsigned long long> stats;
+    DevBuf<uint8_t> cls;
+    DevBuf<unsigned long long> words;
+    PinBuf<unsigned long long> h_words;
+    BinOut out[4];
+    PieceBufs p;
+    explicit BinBufs(hipStream_t s) : p(s) {}
+    int init() {
+        TSX_TRY(words.alloc(8 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(words.get(), 0, 8 * sizeof(unsigned long long), p.st));
+        return h_words.alloc(8 * sizeof(unsigned long long));
+    }
+};
+
+// One piece: piece_front, then -- when it holds a whole record -- the stats and the classes of its records [0, nrec),
+// queued and not waited for.
+static int bin_piece(tsx_hip_map *a, const tsx_hip_map *b, BinBufs &bb, const uint8_t *d_text, uint64_t len, bool last,
+                     const tsx_hip_bin_rule &r, bool spans, hipStream_t st, uint64_t &cut, uint64_t &nrec, bool &open) {
+    TSX_TRY(piece_front(a, bb.p, d_text, len, last, spans, cut, nrec, open));
+    if (nrec == 0) return TSX_HIP_OK;
+    TSX_TRY(grow(st, bb.stats, nrec * sizeof(tsx_hip_bin_stats)));
+    TSX_TRY(grow(st, bb.cls, nrec));
+    HIP_TRY(hipMemsetAsync(bb.stats.get(), 0, nrec * sizeof(tsx_hip_bin_stats), st));
+    QmapScope qs(a);
+    TSX_TRY(piece_qmap(a, d_text, cut, st));
+    TSX_TRY(bin_launch(a, b, d_text, cut, cut, 0, bb.p.info.get() + 4, r, bb.stats.get(), nrec, st));
+    hipLaunchKernelGGL(bin_class_kernel, dim3(grid_for(a, nrec, 8)), dim3(NT), 0, st, (const unsigned long long *)bb.stats.get(),
+                       nrec, r.min_hits, r.ratio_milli, bb.cls.get(), bb.words.get());
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// Stats (io == NULL: each piece's stats and classes go to the caller's arrays while they fit) and binned reads (one
+// write-behind per wanted output: piece i + 1 is scanned and compacted while piece i's outputs are written).
+static int bin_host(tsx_hip_map *a, tsx_hip_map *b, const char *text, size_t n, const tsx_hip_bin_rule &r, size_t chunk_bytes,
+                    tsx_hip_bin_stats *stats_out, uint8_t *class_out, size_t stats_cap, size_t *n_records,
+                    const tsx_hip_bin_io *io, tsx_hip_bin_totals *totals) {
+    TSX_TRY(bin_begin(a, b));
+    hipStream_t st = a->stream.get();
+    WriteBehind wb[4];
+    if (io) { wb[0].fd = io->fd_a; wb[1].fd = io->fd_b; wb[2].fd = io->fd_ambiguous; wb[3].fd = io->fd_none; }
+    BinBufs bb(st);
+    tsx_hip_bin_totals t;
+    memset(&t, 0, sizeof t);
+    uint64_t rec_base = 0;
+    int rc = bb.init();
+    if (rc == TSX_HIP_OK) rc = host_pieces(a, bb.p, text, n, chunk_bytes, false, rec_base,
+        [&](const uint8_t *d_text, uint64_t len, bool last, uint64_t &cut, uint64_t &nrec, bool &open) {
+            return bin_piece(a, b, bb, d_text, len, last, r, io != nullptr, st, cut, nrec, open);
+        },
+        [&](size_t, uint64_t base, uint64_t cut, uint64_t nrec, bool open) -> int {
+            if (!io) {
+                TSX_TRY(deliver_records(stats_out, stats_cap, base, bb.stats.get(), nrec, st));
+                return class_out ? deliver_records(class_out, stats_cap, base, bb.cls.get(), nrec, st) : TSX_HIP_OK;
+            }
+            if (!nrec) return TSX_HIP_OK;
+            const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+            unsigned long long *const words = bb.words.get();
+            const unsigned long long *h = bb.h_words.get();
+            for (uint32_t c = 0; c < 4; ++c) {   // the existing scan and copy kernels, once per wanted output
+                if (wb[c].fd < 0) continue;
+                BinOut &o = bb.out[c];
+                TSX_TRY(grow(st, o.off, (nk + nchunks + 16) * sizeof(unsigned long long)));
+                TSX_TRY(o.out.room(st, cut));
+                HIP_TRY(hipMemsetAsync(o.off.get() + nrec, 0, sizeof(unsigned long long), st));
+                hipLaunchKernelGGL(bin_len_kernel, dim3(grid_for(a, nrec, 8)), dim3(NT), 0, st, (const uint8_t *)bb.cls.get(),
+                                   (const unsigned long long *)bb.p.rspan.get(), nrec, c, open ? 1 : 0, o.off.get());
+                TSX_TRY(filter_compact(a, bb.p.text.get(), cut, bb.p.rspan.get(), o.off.get(), nrec, words + 4 + c, o.out.out,
+                                       (uint64_t)o.out.have, st));
+            }
+            HIP_TRY(hipMemcpyAsync(bb.h_words.get(), words, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipEventRecord(bb.p.ev.get(), st));
+            for (WriteBehind &w : wb) TSX_TRY(w.flush());   // the previous piece's outputs, while the device works on this one
+            HIP_TRY(hipEventSynchronize(bb.p.ev.get()));
+            bool any = false;
+            for (uint32_t c = 0; c < 4; ++c) {
+                t.n[c] += h[c];
+                if (wb[c].fd < 0) continue;
+                TSX_TRY(wb[c].stage(bb.out[c].out.out, h[4 + c], cut, "bin", st));
+                any |= h[4 + c] != 0;
+            }
+            if (any) HIP_TRY(hipStreamSynchronize(st));
+            HIP_TRY(hipMemsetAsync(words, 0, 8 * sizeof(unsigned long long), st));   // (the words are per piece)
+            return TSX_HIP_OK;
+        });
+    for (WriteBehind &w : wb)
+        if (rc == TSX_HIP_OK) rc = w.flush();
+    if (n_records) *n_records = (size_t)rec_base;
+    t.records = rec_base;
+    for (int c = 0; c < 4; ++c) t.bytes[c] = wb[c].bytes;
+    if (totals) *totals = t;
+    if (rc == TSX_HIP_OK && !io && rec_base > stats_cap) rc = TSX_HIP_ERANGE;
+    return rc;
+}
+
+extern "C" int tsx_hip_bin_stats_host(tsx_hip_map *a, tsx_hip_map *b, const char *text, size_t n, const tsx_hip_bin_rule *rule,
+                                      tsx_hip_bin_stats *stats_out, uint8_t *class_out, size_t stats_cap, size_t *n_records,
+                                      size_t chunk_bytes) {
+    if (n_records) *n_records = 0;
+    TSX_TRY(bin_check(a, b, rule));
+    if ((!text && n) || (!stats_out && stats_cap)) return bin_fail("bin: the text or the stats pointer");
+    return bin_host(a, b, text, n, *rule, chunk_bytes, stats_out, class_out, stats_cap, n_records, nullptr, nullptr);
+}
+
+extern "C" int tsx_hip_bin_reads_host(tsx_hip_map *a, tsx_hip_map *b, const char *text, size_t n, const tsx_hip_bin_rule *rule,
+                                      const tsx_hip_bin_io *io, size_t chunk_bytes, tsx_hip_bin_totals *totals) {
+    if (totals) memset(totals, 0, sizeof *totals);
+    TSX_TRY(bin_rule_check(rule));
+    TSX_TRY(bin_io_check(io));
+    TSX_TRY(bin_check(a, b, rule));
+    if (!text && n) return bin_fail("bin: no text");
+    return bin_host(a, b, text, n, *rule, chunk_bytes, nullptr, nullptr, 0, nullptr, io, totals);
 }
 
 // ---- read trimming: the solid stretch of every record (tsx_trim.h) ------------------------------------------------

@@ -440,6 +440,51 @@ public:
         check(rc);
     }
 
+    // read binning by two tables (tsx_hip_bin_stats_host): this is A, oOther is B; per record the windows that hit each
+    // table, and (pClasses) its class TSX_HIP_BIN_*
+    std::vector<tsx_hip_bin_stats> binStats(TSXHashMapHIP &oOther, const char *pText, size_t iBytes, const tsx_hip_bin_rule &oRule,
+                                            std::vector<uint8_t> *pClasses = nullptr, size_t iChunkBytes = 0) {
+        // a first guess of 256 bytes per record; a text with shorter records is binned again with the exact count
+        std::vector<tsx_hip_bin_stats> out(iBytes / 256 + 16);
+        std::vector<uint8_t> cls(pClasses ? out.size() : 0);
+        size_t n = 0;
+        int rc = tsx_hip_bin_stats_host(m_pMap, oOther.m_pMap, pText, iBytes, &oRule, out.data(), pClasses ? cls.data() : nullptr,
+                                        out.size(), &n, iChunkBytes);
+        if (rc == TSX_HIP_ERANGE) {
+            out.resize(n);
+            if (pClasses) cls.resize(n);
+            rc = tsx_hip_bin_stats_host(m_pMap, oOther.m_pMap, pText, iBytes, &oRule, out.data(), pClasses ? cls.data() : nullptr, n,
+                                        &n, iChunkBytes);
+        }
+        if (rc == TSX_HIP_EINVAL) throw TSXException(tsx_hip_last_error(), rc);   // (the refusal says which argument)
+        check(rc);
+        out.resize(n);
+        if (pClasses) { cls.resize(n); pClasses->swap(cls); }
+        return out;
+    }
+    // tsx_hip_bin_reads_host: the records of the text split by class into sPaths (a, b, ambiguous, none; created /
+    // truncated; an empty path counts the class and writes nothing)
+    tsx_hip_bin_totals binReads(TSXHashMapHIP &oOther, const char *pText, size_t iBytes, const tsx_hip_bin_rule &oRule,
+                                const std::string (&sPaths)[4], size_t iChunkBytes = 0) {
+        int fds[4] = {-1, -1, -1, -1};
+        for (int i = 0; i < 4; ++i) {
+            if (sPaths[i].empty()) continue;
+            fds[i] = open(sPaths[i].c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+            if (fds[i] < 0) {
+                for (int j = 0; j < i; ++j) if (fds[j] >= 0) close(fds[j]);
+                throw TSXException("could not open " + sPaths[i] + " for writing", TSX_HIP_EIO);
+            }
+        }
+        const tsx_hip_bin_io io = {fds[0], fds[1], fds[2], fds[3]};
+        tsx_hip_bin_totals oTotals;
+        int rc = tsx_hip_bin_reads_host(m_pMap, oOther.m_pMap, pText, iBytes, &oRule, &io, iChunkBytes, &oTotals);
+        for (int i = 0; i < 4; ++i)
+            if (fds[i] >= 0 && close(fds[i]) != 0 && rc == TSX_HIP_OK) rc = TSX_HIP_EIO;
+        if (rc == TSX_HIP_EINVAL) throw TSXException(tsx_hip_last_error(), rc);
+        check(rc);
+        return oTotals;
+    }
+
     // FASTXreader<FASTAEntry> (FastXReader.h:97-116) reads two lines per record, FASTQEntry (:62-95) four
     void setRecordLines(int iLines) { check(tsx_hip_set_record_lines(m_pMap, iLines)); }
     // canonical counting: a k-mer and its reverse complement share one counter (empty table only)

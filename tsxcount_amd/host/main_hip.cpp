@@ -73,6 +73,12 @@ struct arguments {
     std::string joint_histo, joint_format = "sparse";
     uint64_t joint_max_a = 1000, joint_max_b = 1000;
     bool joint_opts = false;   // --joint-max-a / --joint-max-b / --joint-format were given
+    // read binning by the two tables: the records of --bin-input (default --input) go to --bin-a / --bin-b /
+    // --bin-ambiguous / --bin-none by the table they hit more; --bin-stats=FILE writes the hits of every record
+    std::string bin_a, bin_b, bin_ambiguous, bin_none, bin_input, bin_stats;
+    uint64_t bin_min_hits = 1;
+    uint32_t bin_ratio_milli = 1000;
+    bool bin_opts = false;     // --bin-min-hits / --bin-ratio were given
     bool given_k = false, given_l = false, given_s = false, given_seed = false;
     // table sizing: --l=auto sketches --input first and counts into the l that holds its k-mers at --load-factor=F;
     // --estimate prints that line and stops
@@ -114,7 +120,9 @@ static int usage() {
                  "                [--trim-interleaved] [--pair-names]\n"
                  "                [--with=DB[,DB2,...] [--op=intersect|union|subtract|diff] [--op-count=min|max|sum|left|right]\n"
                  "                 [--a-lower=N] [--a-upper=N] [--b-lower=N] [--b-upper=N] [--compare]\n"
-                 "                 [--joint-histo=FILE [--joint-max-a=H] [--joint-max-b=H] [--joint-format=sparse|matrix]]]\n"
+                 "                 [--joint-histo=FILE [--joint-max-a=H] [--joint-max-b=H] [--joint-format=sparse|matrix]]\n"
+                 "                 [--bin-a=OUT] [--bin-b=OUT] [--bin-ambiguous=OUT] [--bin-none=OUT] [--bin-input=FILE]\n"
+                 "                 [--bin-stats=FILE] [--bin-min-hits=N] [--bin-ratio=R]]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
                  "--l=auto sizes the table itself: the input is sketched first (HyperLogLog, 2^14 registers, on the GPU), and l\n"
                  "is the smallest table that holds the estimated distinct k-mers at load F (--load-factor, default 0.75, at most\n"
@@ -193,7 +201,17 @@ static int usage() {
                  "--joint-max-b=H (default 1000) give counts 0..H and one bin H+1 for everything above, per side.\n"
                  "--joint-format=sparse (default) writes a<TAB>b<TAB>k-mers for every pair that occurs, ordered by a, then b;\n"
                  "matrix writes a comment line, then H+2 lines of H+2 numbers, the line being the count in A. It prints\n"
-                 "joint<TAB>a_only<TAB>b_only<TAB>both (distinct k-mers). It needs --with; one GPU only."
+                 "joint<TAB>a_only<TAB>b_only<TAB>both (distinct k-mers). It needs --with; one GPU only.\n"
+                 "--bin-a=OUT and --bin-b=OUT split the records of --bin-input (default: --input; plain, .gz or BGZF) by the\n"
+                 "table they belong to, in one scan against A and B (before --op replaces the table): a k-mer of a read hits A\n"
+                 "when its count there lies in --a-lower..--a-upper, B with --b-lower..--b-upper. A read goes to the table it\n"
+                 "hits more, given at least --bin-min-hits=N hits (default 1) and at least R times the other table's hits\n"
+                 "(--bin-ratio=R, a decimal 1 .. 1000, default 1, three places kept); ties and reads no side wins go to\n"
+                 "--bin-ambiguous=OUT, reads that reach N hits in neither table to --bin-none=OUT. An output that is not named\n"
+                 "is counted and not written. --bin-stats=FILE writes\n"
+                 "index<TAB>kmers<TAB>hits_a<TAB>hits_b<TAB>hits_both<TAB>class per record (class: a, b, ambiguous, none). It\n"
+                 "prints bin<TAB>records<TAB>a<TAB>b<TAB>ambiguous<TAB>none. It needs --with; single-end input, no wrapped\n"
+                 "FASTA, one GPU only."
               << std::endl;
     return 1;
 }
@@ -576,6 +594,75 @@ static void write_joint(TSXHashMapHIP &oA, TSXHashMapHIP &oB, const arguments &a
     std::cerr << "Wrote the joint histogram to " << a.joint_histo << std::endl;
 }
 
+// --bin-ratio: digits[.digits], 1 .. 1000, in thousandths (the decimals behind the third are dropped)
+static bool parse_ratio_milli(const std::string &v, uint32_t &milli) {
+    size_t i = 0;
+    uint64_t whole = 0, frac = 0;
+    int places = 0;
+    for (; i < v.size() && v[i] >= '0' && v[i] <= '9'; ++i) whole = std::min<uint64_t>(whole * 10 + (uint64_t)(v[i] - '0'), 1000000);
+    if (i == 0) return false;
+    if (i < v.size() && v[i] == '.') {
+        const size_t dot = i++;
+        for (; i < v.size() && v[i] >= '0' && v[i] <= '9'; ++i)
+            if (places < 3) { frac = frac * 10 + (uint64_t)(v[i] - '0'); ++places; }
+        if (i == dot + 1) return false;
+    }
+    if (i != v.size()) return false;
+    for (; places < 3; ++places) frac *= 10;
+    const uint64_t m = whole * 1000 + frac;
+    if (m < 1000 || m > 1000000) return false;
+    milli = (uint32_t)m;
+    return true;
+}
+
+static bool wants_bin(const arguments &a) {
+    return !a.bin_a.empty() || !a.bin_b.empty() || !a.bin_ambiguous.empty() || !a.bin_none.empty() || !a.bin_stats.empty();
+}
+static bool wants_bin_reads(const arguments &a) {
+    return !a.bin_a.empty() || !a.bin_b.empty() || !a.bin_ambiguous.empty() || !a.bin_none.empty();
+}
+
+// --bin-*: the records of --bin-input by the table they hit more, where --compare and --joint-histo run
+static int run_bin(TSXHashMapHIP &oA, TSXHashMapHIP &oB, const arguments &a) {
+    auto check = [](int rc) {
+        if (rc == TSX_HIP_OK) return;
+        throw TSXException(std::string(tsx_hip_strerror(rc)) + " (" + tsx_hip_last_error() + ")", rc);
+    };
+    const std::string path = a.bin_input.empty() ? a.input_path : a.bin_input;
+    pair_text t;   // (loaded as every read query's input: a BGZF file is inflated on the device)
+    if (!t.load(path, a.device, check)) return 3;
+    oA.setRecordLines(is_fasta_path(path, is_wrapped(a) ? std::string() : a.format) ? 2 : 4);
+    const tsx_hip_bin_rule rule = {a.a_lower, a.a_upper, a.b_lower, a.b_upper, a.bin_min_hits, a.bin_ratio_milli, 0};
+    static const char *const names[4] = {"a", "b", "ambiguous", "none"};
+    uint64_t records = 0, n[4] = {0, 0, 0, 0};
+    if (!a.bin_stats.empty()) {
+        std::vector<uint8_t> cls;
+        const std::vector<tsx_hip_bin_stats> st = oA.binStats(oB, t.text, t.n, rule, &cls);
+        std::ofstream f(a.bin_stats);
+        for (size_t i = 0; i < st.size(); ++i) {
+            f << i << '\t' << st[i].kmers << '\t' << st[i].hits_a << '\t' << st[i].hits_b << '\t' << st[i].hits_both << '\t'
+              << names[cls[i] & 3] << '\n';
+            ++n[cls[i] & 3];
+        }
+        f.close();
+        if (!f) throw TSXException("could not write " + a.bin_stats, TSX_HIP_EIO);
+        records = st.size();
+        std::cerr << "Wrote the bin stats of " << st.size() << " records to " << a.bin_stats << std::endl;
+    }
+    if (wants_bin_reads(a)) {
+        const std::string paths[4] = {a.bin_a, a.bin_b, a.bin_ambiguous, a.bin_none};
+        const tsx_hip_bin_totals bt = oA.binReads(oB, t.text, t.n, rule, paths);
+        records = bt.records;
+        for (int c = 0; c < 4; ++c) {
+            n[c] = bt.n[c];
+            if (!paths[c].empty())
+                std::cerr << "Wrote " << bt.n[c] << " records (" << bt.bytes[c] << " bytes) to " << paths[c] << std::endl;
+        }
+    }
+    std::cout << "bin\t" << records << '\t' << n[0] << '\t' << n[1] << '\t' << n[2] << '\t' << n[3] << std::endl;
+    return 0;
+}
+
 // --op / --op-count by name: the TSX_HIP_OP_* / TSX_HIP_CNT_* value, -1 for none given, -2 / -1 for an unknown one
 static int op_index(const std::string &s) {
     return s.empty() ? -1 : s == "intersect" ? TSX_HIP_OP_INTERSECT : s == "union" ? TSX_HIP_OP_UNION
@@ -812,6 +899,26 @@ int main(int argc, char *argv[]) {
             a.joint_format = v;
             a.joint_opts = true;
         }
+        else if (opt(argv[i], "bin-a", v)) { a.bin_a = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "bin-b", v)) { a.bin_b = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "bin-ambiguous", v)) { a.bin_ambiguous = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "bin-none", v)) { a.bin_none = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "bin-input", v)) { a.bin_input = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "bin-stats", v)) { a.bin_stats = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "bin-min-hits", v)) {
+            char *end = nullptr;
+            errno = 0;
+            a.bin_min_hits = strtoull(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno || v[0] == '-') { std::cerr << "--bin-min-hits takes a number" << std::endl; return usage(); }
+            a.bin_opts = true;
+        }
+        else if (opt(argv[i], "bin-ratio", v)) {
+            if (!parse_ratio_milli(v, a.bin_ratio_milli)) {
+                std::cerr << "--bin-ratio takes a decimal 1 .. 1000 (three places are kept), not '" << v << "'" << std::endl;
+                return usage();
+            }
+            a.bin_opts = true;
+        }
         else if (opt(argv[i], "format", v)) a.format = v;
         else if (opt(argv[i], "device", v)) a.device = atoi(v.c_str());
         else if (opt(argv[i], "gpus", v)) { a.gpus = atoi(v.c_str()); a.group = true; }
@@ -974,8 +1081,30 @@ int main(int argc, char *argv[]) {
         std::cerr << "--joint-histo works on one GPU only: a --gpus " << a.gpus << " run keeps one table per GPU" << std::endl;
         return usage();
     }
-    if (!a.with.empty() && a.op.empty() && !a.compare && a.joint_histo.empty()) {
-        std::cerr << "--with needs --op, --compare or --joint-histo" << std::endl;
+    {   // read binning: what the options alone tell
+        const bool any_bin = wants_bin(a) || !a.bin_input.empty() || a.bin_opts;
+        std::string why;
+        if (any_bin && a.with.empty())
+            why = "--bin-a, --bin-b, --bin-ambiguous, --bin-none and --bin-stats need a second table: --with=DB[,DB2,...]";
+        else if (any_bin && !wants_bin(a))
+            why = "--bin-input, --bin-min-hits and --bin-ratio go with --bin-a, --bin-b, --bin-ambiguous, --bin-none or --bin-stats";
+        else if (any_bin && a.gpus > 1)
+            why = "--bin-a, --bin-b and --bin-stats run on one GPU only: a --gpus " + std::to_string(a.gpus) + " run keeps one table per GPU";
+        else if (any_bin && a.bin_input.find(',') != std::string::npos)
+            why = "--bin-input takes one file: paired reads are not binned yet";
+        else if (any_bin && is_wrapped(a) && (a.bin_input.empty() || a.bin_input == a.input_path))
+            why = "--bin-a, --bin-b and --bin-stats do not read wrapped FASTA: give the reads to bin as --bin-input=FILE"
+                  " (FASTQ, or FASTA with one sequence line per record)";
+        else if (any_bin && a.input_path.empty() && a.bin_input.empty())
+            why = "--bin-a, --bin-b and --bin-stats without --input need --bin-input=FILE";
+        if (!why.empty()) {
+            std::cerr << why << std::endl;
+            return usage();
+        }
+    }
+    if (!a.with.empty() && a.op.empty() && !a.compare && a.joint_histo.empty() && !wants_bin(a)) {
+        std::cerr << "--with needs --op, --compare, --joint-histo or a --bin-a / --bin-b / --bin-ambiguous / --bin-none / --bin-stats"
+                  << " output" << std::endl;
         return usage();
     }
     if (!a.with.empty() && a.gpus > 1) {
@@ -1257,6 +1386,8 @@ int main(int argc, char *argv[]) {
             std::cout << "compare-sums\t" << s.a_sum_both << '\t' << s.b_sum_both << std::endl;
         }
         if (!a.joint_histo.empty()) write_joint(oMap, oWith, a);
+        const int rb = wants_bin(a) ? run_bin(oMap, oWith, a) : 0;
+        if (rb) return rc ? rc : rb;
         if (a.op.empty()) {
             if (!wants_queries(a) && !wants_trim(a)) return rc;
             const int rq = run_after(oMap.handle(), a);
