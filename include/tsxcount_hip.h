@@ -848,6 +848,63 @@ int tsx_hip_bin_stats_host(tsx_hip_map *a, tsx_hip_map *b, const char *text, siz
 int tsx_hip_bin_reads_host(tsx_hip_map *a, tsx_hip_map *b, const char *text, size_t n, const tsx_hip_bin_rule *rule,
                            const tsx_hip_bin_io *io, size_t chunk_bytes, tsx_hip_bin_totals *totals /* optional */);
 
+/*
+ * Heterozygous k-mer pairs of one table (csrc/tsx_het.h; no reference counterpart -- Smudgeplot's `hetkmers`): the pairs
+ * of k-mers of the table that differ only in their middle base, by the two counts of each pair.
+ *   c(x)      getKmerCount(x): in-slot field plus carries, as tsx_hip_joint_histogram_* reads it.  x is in range when
+ *             rule->lower <= c(x) <= rule->upper; a k-mer out of range counts as absent everywhere below (the a_range
+ *             convention of tsx_hip_combine).
+ *   middle    base p = (k - 1) / 2: bits 2p, 2p + 1 of the tsx_hip_encode layout, limb p / 32.  k must be odd (so that the
+ *             middle base stays the middle base under reverse complement and the relation is symmetric).
+ *   family    of x: the in-range table keys among x and its three middle-base variants; on a canonical table every variant
+ *             is taken to its strand pair's key first, and duplicates are dropped (flanks that are reverse complements of
+ *             each other, AC?GT, have only two keys: A/T in the middle and C/G).
+ *   pair      an unordered set of two distinct members of one family.  mode 0 (unique, Smudgeplot's rule) counts a pair
+ *             only when its family has exactly two members; mode 1 (all) counts every pair of every family, up to 6 per
+ *             family.  Each pair is counted once.
+ *   matrix    uint64, row-major, n_minor x n_major, n_minor, n_major >= 2, n_minor * n_major <= 2^24:
+ *             M[min(cmin, n_minor - 1) * n_major + min(cmax, n_major - 1)] = the pairs {x, y} with cmin = min(c(x), c(y))
+ *             and cmax = max(c(x), c(y)).
+ *   stats     kmers_in_range; paired = k-mers in at least one counted pair; pairs; families_2 / families_3plus = families
+ *             of exactly 2 / of 3 or 4 members, each counted once whatever the mode.
+ *   record    of the pair list: 2 * key_limbs + 2 uint64 -- minor k-mer (key_limbs words, tsx_hip_encode layout), major
+ *             k-mer, minor count, major count.  Minor is the lower count, on a tie the k-mer whose text is smaller.  K-mers
+ *             are reported as dumps report them (canonical tables: the smaller strand).  The order is unspecified.
+ *   _histogram_device  zeroes dev_matrix (n_minor * n_major * 8 bytes) and dev_stats (sizeof(tsx_hip_het_stats), both device
+ *             memory), waits for what is queued on the map's stream and queues the sweep on `stream` (NULL = the map's
+ *             own): it returns without waiting for it.
+ *   _histogram_host    the same into host memory (stats_out optional); waits for the result.
+ *   _pairs_device      the pairs owned by slots [slot_lo, slot_hi) -- every pair is owned by exactly one slot, so that
+ *             disjoint ranges that cover the table give every pair once -- into dev_pairs (cap records); *dev_n (uint64,
+ *             device) receives their number.  Waits for the result; more pairs than cap: TSX_HIP_ERANGE, the first cap
+ *             records are written and *dev_n is the true total.  S slots own at most S pairs in mode 0, 3 S in mode 1.
+ *   tsx_hip_write_het_pairs_host  the list as text, minor_kmer<TAB>minor_count<TAB>major_kmer<TAB>major_count per line, to
+ *             fd, chunk by chunk (the device makes chunk i + 1 while the host writes chunk i).  chunk_bytes bounds the text
+ *             of a chunk (0 = 256 MiB); a chunk is at least 64 slots, less room than that is TSX_HIP_EINVAL.
+ * The table is left as it is, bit for bit (a lazily cleared table is zeroed first, as everywhere).
+ * TSX_HIP_EINVAL before any device call (tsx_hip_last_error says which): a NULL map, rule or output, even k, a map created
+ * with shard_bits > 0, lower > upper, an unknown mode, reserved != 0, fewer than 2 bins on a side, more than 2^24 cells,
+ * slot_lo > slot_hi or a range beyond the table.
+ */
+#define TSX_HIP_HET_UNIQUE 0
+#define TSX_HIP_HET_ALL 1
+typedef struct tsx_hip_het_rule {
+    uint64_t lower, upper;
+    int32_t mode;       /* TSX_HIP_HET_UNIQUE or TSX_HIP_HET_ALL */
+    int32_t reserved;   /* 0 */
+} tsx_hip_het_rule;
+typedef struct tsx_hip_het_stats {
+    uint64_t kmers_in_range, paired, pairs, families_2, families_3plus;
+} tsx_hip_het_stats;
+int tsx_hip_het_histogram_device(tsx_hip_map *m, const tsx_hip_het_rule *rule, size_t n_minor, size_t n_major, void *dev_matrix,
+                                 void *dev_stats, void *stream);
+int tsx_hip_het_histogram_host(tsx_hip_map *m, const tsx_hip_het_rule *rule, uint64_t *matrix_out, size_t n_minor, size_t n_major,
+                               tsx_hip_het_stats *stats_out /* optional */);
+int tsx_hip_het_pairs_device(tsx_hip_map *m, const tsx_hip_het_rule *rule, uint64_t slot_lo, uint64_t slot_hi, void *dev_pairs,
+                             size_t cap, void *dev_n, void *stream);
+int tsx_hip_write_het_pairs_host(tsx_hip_map *m, const tsx_hip_het_rule *rule, int fd, size_t chunk_bytes, uint64_t *pairs_out,
+                                 uint64_t *bytes_out);
+
 /* IBijectiveFunction::apply / inv_apply (IBijectiveFunction.h:26-27) on the host,
  * and the matrix rows (row i <-> output bit 2k-1-i, BijectiveKMapping.h:202-256). */
 int tsx_hip_hash_apply(const tsx_hip_map *m, const uint64_t *kmer, uint64_t *key_out);

@@ -359,6 +359,90 @@ def joint_histogram(A, B, bins_a=1002, bins_b=1002):
     return m
 
 
+class HetRule(ctypes.Structure):
+    """tsx_hip_het_rule"""
+    _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class HetStats(ctypes.Structure):
+    """tsx_hip_het_stats"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("kmers_in_range", "paired", "pairs", "families_2", "families_3plus")]
+
+
+HET_MODES = {"unique": 0, "all": 1}
+
+
+def het_pair_dtype(k):
+    """A record of the pair list of a table of k-mers (tsx_hip_het_pairs_device): k-mers as key_limbs(k) limbs."""
+    w = (2 * k + 63) // 64
+    return np.dtype([("minor", np.uint64, (w,)), ("major", np.uint64, (w,)), ("minor_count", np.uint64), ("major_count", np.uint64)])
+
+
+HET_PAIR_DTYPE = het_pair_dtype(31)   # one-limb keys (k <= 32); het_pair_dtype(k) for any k
+
+
+def het_rule(lower=1, upper=None, mode="unique"):
+    if mode not in HET_MODES:
+        raise ValueError("het pairs: mode is 'unique' or 'all', got %r" % (mode,))
+    return HetRule(int(lower), (1 << 64) - 1 if upper is None else int(upper), HET_MODES[mode], 0)
+
+
+def het_pairs(D, k, lower=1, upper=None, mode="unique", canonical=False):
+    """The definition of TSXHashMapHIP.hetPairs / hetHistogram on the CPU (Smudgeplot's hetkmers).  D maps k-mer string ->
+    count, as a dump reports it (canonical: the smaller strand); k is odd.  A k-mer counted outside [lower, upper] is absent.
+    The family of x is x and those of its three middle-base variants (canonical: each taken to its smaller strand) that D
+    holds in range.  A pair is two members of one family: mode 'unique' counts the pair of a family of exactly two, 'all'
+    every pair of every family.  Returns (pairs, stats): pairs a list of (minor k-mer, its count, major k-mer, its count),
+    minor being the lower count and on a tie the smaller string, each pair once, sorted; stats the dict of
+    kmers_in_range, paired, pairs, families_2, families_3plus (families of exactly 2 / of 3 or 4, each counted once)."""
+    if k % 2 == 0:
+        raise ValueError("het_pairs: k must be odd (an even k has no middle base)")
+    if mode not in HET_MODES:
+        raise ValueError("het_pairs: mode is 'unique' or 'all', got %r" % (mode,))
+    top = (1 << 64) - 1 if upper is None else int(upper)
+    low = max(int(lower), 1)
+    canon = (lambda x: min(x, revcomp(x))) if canonical else (lambda x: x)   # (what canonical() gives for a string)
+    R = {}
+    for x, c in D.items():
+        x = x.decode() if isinstance(x, bytes) else x   # (k-mers come back as str)
+        if len(x) != k:
+            raise ValueError("het_pairs: %r is no %d-mer" % (x, k))
+        if low <= int(c) <= top:
+            R[canon(x)] = int(c)
+    p = (k - 1) // 2
+    families = set()
+    for x in R:
+        fam = {x}
+        for b in "ACGT":
+            y = canon(x[:p] + b + x[p + 1:])
+            if y in R:
+                fam.add(y)
+        families.add(tuple(sorted(fam)))
+    pairs, paired = [], set()
+    for fam in families:
+        if len(fam) < 2 or (mode == "unique" and len(fam) != 2):
+            continue
+        for i in range(len(fam)):
+            for j in range(i + 1, len(fam)):
+                a, b = sorted((fam[i], fam[j]), key=lambda x: (R[x], x))
+                pairs.append((a, R[a], b, R[b]))
+        paired.update(fam)
+    stats = {"kmers_in_range": len(R), "paired": len(paired), "pairs": len(pairs),
+             "families_2": sum(1 for f in families if len(f) == 2), "families_3plus": sum(1 for f in families if len(f) > 2)}
+    return sorted(pairs), stats
+
+
+def het_histogram(pairs, bins_minor=1002, bins_major=1002):
+    """The matrix of TSXHashMapHIP.hetHistogram from het_pairs' list: numpy uint64[bins_minor, bins_major], [i, j] = the
+    pairs with min(minor count, bins_minor - 1) == i and min(major count, bins_major - 1) == j."""
+    if bins_minor < 2 or bins_major < 2 or bins_minor * bins_major > JOINT_MAX_CELLS:
+        raise ValueError("het_histogram: 2 <= bins and bins_minor * bins_major <= 2^24")
+    m = np.zeros((bins_minor, bins_major), dtype=np.uint64)
+    for _, cmin, _, cmax in pairs:
+        m[min(int(cmin), bins_minor - 1), min(int(cmax), bins_major - 1)] += np.uint64(1)
+    return m
+
+
 class BinRule(ctypes.Structure):
     """tsx_hip_bin_rule."""
     _fields_ = [("a_lower", ctypes.c_uint64), ("a_upper", ctypes.c_uint64), ("b_lower", ctypes.c_uint64),
@@ -499,6 +583,10 @@ def lib():
     L.tsx_hip_combine.argtypes = [vp, vp, vp, ctypes.POINTER(CombineRule), ctypes.POINTER(CombineStats)]
     L.tsx_hip_joint_histogram_device.argtypes = [vp, vp, sz, sz, vp, vp]
     L.tsx_hip_joint_histogram_host.argtypes = [vp, vp, u64p, sz, sz]
+    L.tsx_hip_het_histogram_device.argtypes = [vp, ctypes.POINTER(HetRule), sz, sz, vp, vp, vp]
+    L.tsx_hip_het_histogram_host.argtypes = [vp, ctypes.POINTER(HetRule), u64p, sz, sz, ctypes.POINTER(HetStats)]
+    L.tsx_hip_het_pairs_device.argtypes = [vp, ctypes.POINTER(HetRule), u64, u64, vp, sz, vp, vp]
+    L.tsx_hip_write_het_pairs_host.argtypes = [vp, ctypes.POINTER(HetRule), ci, sz, u64p, u64p]
     L.tsx_hip_bin_stats_device.argtypes = [vp, vp, vp, sz, ctypes.POINTER(BinRule), vp, sz, ctypes.POINTER(sz), vp]
     L.tsx_hip_bin_stats_host.argtypes = [vp, vp, ctypes.c_char_p, sz, ctypes.POINTER(BinRule), vp, vp, sz, ctypes.POINTER(sz), sz]
     L.tsx_hip_bin_reads_host.argtypes = [vp, vp, ctypes.c_char_p, sz, ctypes.POINTER(BinRule), ctypes.POINTER(BinIO), sz,
@@ -987,6 +1075,74 @@ class TSXHashMapHIP:
                 os.close(fd)
         self._check_joint(rc)
         return tot.as_dict()
+
+    def hetHistogram(self, bins_minor=1002, bins_major=1002, lower=1, upper=None, mode="unique"):
+        """Heterozygous k-mer pairs of this table by their two counts (tsx_hip_het_histogram_host; Smudgeplot's hetkmers):
+        the pairs of k-mers counted in [lower, upper] that differ only in their middle base.  mode 'unique' counts the pair
+        of a family of exactly two, 'all' every pair of every family.  Returns (numpy uint64[bins_minor, bins_major], stats):
+        [i, j] = pairs whose lower count is i and whose higher count is j, the last bin of each side pooling every larger
+        count; stats is the dict of het_pairs().  het_pairs() and het_histogram() state the definition.  k must be odd."""
+        rule = het_rule(lower, upper, mode)
+        ok = bins_minor > 0 and bins_major > 0 and bins_minor * bins_major <= JOINT_MAX_CELLS
+        out = np.zeros((int(bins_minor), int(bins_major)) if ok else (0, 0), dtype=np.uint64)
+        st = HetStats()
+        self._check_joint(self._lib.tsx_hip_het_histogram_host(self.handle, ctypes.byref(rule), _p(out), int(bins_minor),
+                                                               int(bins_major), ctypes.byref(st)))
+        return out, {n: int(getattr(st, n)) for n, _ in HetStats._fields_}
+
+    def hetHistogramDevice(self, matrix_ptr, stats_ptr, bins_minor=1002, bins_major=1002, lower=1, upper=None, mode="unique",
+                           stream=None):
+        """tsx_hip_het_histogram_device: the matrix into uint64[bins_minor * bins_major] and the five totals into uint64[5],
+        both in device memory (zeroed by the call), queued on `stream` (None = this map's own); returns without waiting."""
+        vp = ctypes.c_void_p
+        rule = het_rule(lower, upper, mode)
+        self._check_joint(self._lib.tsx_hip_het_histogram_device(self.handle, ctypes.byref(rule), int(bins_minor), int(bins_major),
+                                                                 vp(matrix_ptr), vp(stats_ptr), vp(stream) if stream else None))
+
+    def hetPairs(self, lower=1, upper=None, mode="unique", slot_lo=0, slot_hi=None, range_slots=1 << 20):
+        """The heterozygous pairs themselves (tsx_hip_het_pairs_device, range_slots slots a call): a numpy structured
+        array het_pair_dtype(k) -- minor, major (k-mers as limbs, as a dump reports them), minor_count, major_count -- in
+        no particular order.  The record's width follows the key width, so the dtype is het_pair_dtype(self.k); it equals
+        HET_PAIR_DTYPE only for one-limb keys (k <= 32).  slot_lo / slot_hi: only the pairs those slots own (every pair is owned by one slot)."""
+        import torch
+        rule = het_rule(lower, upper, mode)
+        dt = het_pair_dtype(self.k)
+        hi = int(self.layout.slots) if slot_hi is None else int(slot_hi)
+        step = max(1, int(range_slots))
+        cap = min(step, max(hi - int(slot_lo), 1)) * (3 if mode == "all" else 1)
+        words = dt.itemsize // 8
+        buf = torch.empty(cap * words + 1, dtype=torch.int64, device=torch.device("cuda", self.device))
+        st = torch.cuda.Stream(buf.device)   # a stream of its own: torch's default one does not wait for the map's
+        vp = ctypes.c_void_p
+        parts = []
+        lo = int(slot_lo)
+        while True:
+            top = min(hi, lo + step)
+            self._check_joint(self._lib.tsx_hip_het_pairs_device(self.handle, ctypes.byref(rule), lo, top, vp(buf.data_ptr()), cap,
+                                                                 vp(buf.data_ptr() + cap * words * 8), vp(st.cuda_stream)))
+            n = int(buf[cap * words].item())
+            if n:
+                parts.append(buf[:n * words].cpu().numpy().view(np.uint64).view(dt).copy())
+            lo = top
+            if lo >= hi:
+                break
+        return np.concatenate(parts) if parts else np.zeros(0, dtype=dt)
+
+    def writeHetPairs(self, path_or_fd, lower=1, upper=None, mode="unique", chunk_bytes=0):
+        """The pairs as "minor_kmer<TAB>minor_count<TAB>major_kmer<TAB>major_count" lines (tsx_hip_write_het_pairs_host) to
+        a path (created or truncated) or an open file descriptor, in no particular order.  Returns (pairs, bytes)."""
+        rule = het_rule(lower, upper, mode)
+        pairs, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        own = not isinstance(path_or_fd, int)
+        fd = os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd
+        try:
+            rc = self._lib.tsx_hip_write_het_pairs_host(self.handle, ctypes.byref(rule), fd, int(chunk_bytes), ctypes.byref(pairs),
+                                                        ctypes.byref(nbytes))
+        finally:
+            if own:
+                os.close(fd)
+        self._check_joint(rc)
+        return int(pairs.value), int(nbytes.value)
 
     def queryReads(self, text, lower=1, upper=None, chunk_bytes=0):
         """Per-record k-mer stats of a FASTQ / FASTA text against the table (tsx_hip_query_reads_host): a numpy

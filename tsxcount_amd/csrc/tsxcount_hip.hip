@@ -12,6 +12,7 @@
 #include "tsx_db.h"
 #include "tsx_combine.h"
 #include "tsx_joint.h"
+#include "tsx_het.h"
 #include "tsx_bin.h"
 #include "tsx_fasta.h"
 #include "tsx_trim.h"
@@ -4049,6 +4050,185 @@ extern "C" int tsx_hip_joint_histogram_host(tsx_hip_map *a, tsx_hip_map *b, uint
     HIP_TRY(hipMemcpyAsync(matrix_out, d.get(), na * nb * sizeof(uint64_t), hipMemcpyDeviceToHost, a->stream.get()));
     HIP_TRY(hipStreamSynchronize(a->stream.get()));
     return TSX_HIP_OK;
+}
+
+// ---- heterozygous pairs of one table (tsx_het.h; DESIGN.md §3 "Heterozygous pairs") ------------------------------
+static int het_check(const tsx_hip_map *m, const tsx_hip_het_rule *rule) {
+    if (!m || !rule) return combine_fail("het pairs: a map and a rule are needed");
+    if (!(m->p.k & 1)) return combine_fail("het pairs: even k (no middle base)");
+    if (m->p.lg != m->p.l) return combine_fail("het pairs: a map created with shard_bits > 0");
+    if (rule->lower > rule->upper) return combine_fail("het pairs: lower > upper");
+    if (rule->mode != TSX_HIP_HET_UNIQUE && rule->mode != TSX_HIP_HET_ALL) return combine_fail("het pairs: unknown mode");
+    if (rule->reserved != 0) return combine_fail("het pairs: reserved must be 0");
+    return TSX_HIP_OK;
+}
+static int het_check_bins(size_t n_minor, size_t n_major) {
+    if (n_minor < 2 || n_major < 2) return combine_fail("het histogram: fewer than 2 bins");
+    if (n_minor > JOINT_MAX_CELLS || n_major > JOINT_MAX_CELLS || n_minor * n_major > JOINT_MAX_CELLS)
+        return combine_fail("het histogram: more than 2^24 cells");
+    return TSX_HIP_OK;
+}
+
+// The kernel's view of the rule: the range, the mode, the middle base and H_d = A * (d << 2p) for d = 1..3.
+static HetArgs het_args(const tsx_hip_map *m, const tsx_hip_het_rule *rule, bool sec) {
+    HetArgs ha;
+    memset(&ha, 0, sizeof ha);
+    ha.lower = std::max<uint64_t>(rule->lower, 1);
+    ha.upper = rule->upper;
+    ha.mode = rule->mode;
+    ha.sec = sec ? 1 : 0;
+    const int bit = 2 * ((m->p.k - 1) / 2);
+    ha.mid_limb = bit >> 6;
+    ha.mid_shift = bit & 63;
+    for (uint64_t d = 1; d <= 3; ++d) {
+        uint64_t x[4] = {0, 0, 0, 0};
+        x[ha.mid_limb] = d << ha.mid_shift;
+        apply_rows(m, m->rows, x, ha.hd[d - 1]);
+    }
+    return ha;
+}
+
+// Everything queued on the map has finished, a lazily cleared table is zeroed; *sec = the table ever carried.
+static int het_settle(tsx_hip_map *m, bool *sec) {
+    join_foreign(m, true);
+    TSX_TRY(ensure_zeroed(m, m->stream.get()));
+    HIP_TRY(hipStreamSynchronize(m->stream.get()));
+    unsigned long long carry = 0;
+    HIP_TRY(hipMemcpy(&carry, m->p.stats + ST_CARRY, 8, hipMemcpyDeviceToHost));
+    *sec = carry != 0;
+    return TSX_HIP_OK;
+}
+
+// het_sweep_kernel over slots [lo, hi) on stream st: the matrix and stats form (d_pairs == nullptr && !list) or the list form.
+static int het_launch(const tsx_hip_map *m, const HetArgs &ha, bool list, uint64_t lo, uint64_t hi, size_t n_minor, size_t n_major,
+                      unsigned long long *d_matrix, unsigned long long *d_stats, uint64_t *d_pairs, uint64_t cap,
+                      unsigned long long *d_n, hipStream_t st) {
+    if (hi == lo) return TSX_HIP_OK;
+    const uint64_t tiles = (hi - lo + HET_TILE - 1) / HET_TILE;
+    uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)m->cus * 8));
+    // A workgroup's corner and a lane's sums are u32: bound the slots one workgroup sweeps below 2^31.
+    auto per_wg = [&](uint64_t g) { return (tiles + g - 1) / g * HET_TILE; };
+    while (per_wg(grid) >= (1ULL << 31) && grid < (1ULL << 30)) grid *= 2;
+    if (per_wg(grid) >= (1ULL << 31)) return combine_fail("het pairs: the table is too large");
+    if (list) {
+        DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((het_sweep_kernel<WKV, CANV, true>), dim3((unsigned)grid), dim3(NT), 0, st,
+                                                            m->p, ha, lo, hi, 0u, 0u, (unsigned long long *)nullptr,
+                                                            (unsigned long long *)nullptr, d_pairs, cap, d_n)));
+    } else {
+        DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((het_sweep_kernel<WKV, CANV, false>), dim3((unsigned)grid), dim3(NT), 0, st,
+                                                            m->p, ha, lo, hi, (uint32_t)n_minor, (uint32_t)n_major, d_matrix, d_stats,
+                                                            (uint64_t *)nullptr, (uint64_t)0, (unsigned long long *)nullptr)));
+    }
+    if (hipGetLastError() != hipSuccess) { g_last_error = "het_sweep_kernel launch"; return TSX_HIP_EHIP; }
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_het_histogram_device(tsx_hip_map *m, const tsx_hip_het_rule *rule, size_t n_minor, size_t n_major,
+                                            void *dev_matrix, void *dev_stats, void *stream) {
+    TSX_TRY(het_check(m, rule));
+    TSX_TRY(het_check_bins(n_minor, n_major));
+    if (!dev_matrix || !dev_stats) return combine_fail("het histogram: no matrix or no stats");
+    HIP_TRY(hipSetDevice(m->device));
+    bool sec = false;
+    TSX_TRY(het_settle(m, &sec));
+    hipStream_t st = pick_stream(m, stream);   // (the map's stream is idle: nothing for st to wait for)
+    HIP_TRY(hipMemsetAsync(dev_matrix, 0, n_minor * n_major * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(dev_stats, 0, sizeof(tsx_hip_het_stats), st));
+    static_assert(sizeof(tsx_hip_het_stats) == HS_N * 8, "tsx_hip_het_stats is the kernel's HS_N totals");
+    return het_launch(m, het_args(m, rule, sec), false, 0, m->lay.slots, n_minor, n_major, (unsigned long long *)dev_matrix,
+                      (unsigned long long *)dev_stats, nullptr, 0, nullptr, st);
+}
+
+extern "C" int tsx_hip_het_histogram_host(tsx_hip_map *m, const tsx_hip_het_rule *rule, uint64_t *matrix_out, size_t n_minor,
+                                          size_t n_major, tsx_hip_het_stats *stats_out) {
+    TSX_TRY(het_check(m, rule));
+    TSX_TRY(het_check_bins(n_minor, n_major));
+    if (!matrix_out) return combine_fail("het histogram: no matrix");
+    HIP_TRY(hipSetDevice(m->device));
+    const size_t cells = n_minor * n_major;
+    DevBuf<uint64_t> d;
+    TSX_TRY(d.alloc((cells + HS_N) * sizeof(uint64_t)));
+    SyncAtExit wait(m->stream.get());   // nothing queued may outlive the matrix
+    TSX_TRY(tsx_hip_het_histogram_device(m, rule, n_minor, n_major, d.get(), d.get() + cells, nullptr));
+    tsx_hip_het_stats s;
+    HIP_TRY(hipMemcpyAsync(matrix_out, d.get(), cells * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream.get()));
+    HIP_TRY(hipMemcpyAsync(&s, d.get() + cells, sizeof s, hipMemcpyDeviceToHost, m->stream.get()));
+    HIP_TRY(hipStreamSynchronize(m->stream.get()));
+    if (stats_out) *stats_out = s;
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_het_pairs_device(tsx_hip_map *m, const tsx_hip_het_rule *rule, uint64_t slot_lo, uint64_t slot_hi,
+                                        void *dev_pairs, size_t cap, void *dev_n, void *stream) {
+    TSX_TRY(het_check(m, rule));
+    if (!dev_n || (!dev_pairs && cap)) return combine_fail("het pairs: no output");
+    if (slot_lo > slot_hi || slot_hi > m->lay.slots) return combine_fail("het pairs: slot range");
+    HIP_TRY(hipSetDevice(m->device));
+    bool sec = false;
+    TSX_TRY(het_settle(m, &sec));
+    hipStream_t st = pick_stream(m, stream);
+    HIP_TRY(hipMemsetAsync(dev_n, 0, sizeof(unsigned long long), st));
+    TSX_TRY(het_launch(m, het_args(m, rule, sec), true, slot_lo, slot_hi, 0, 0, nullptr, nullptr, (uint64_t *)dev_pairs, (uint64_t)cap,
+                       (unsigned long long *)dev_n, st));
+    unsigned long long n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, dev_n, sizeof n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return n > cap ? TSX_HIP_ERANGE : TSX_HIP_OK;
+}
+
+// The pair list as text.  A chunk of S slots owns at most S pairs (unique) or 3 S (all): its records and its text always fit.
+extern "C" int tsx_hip_write_het_pairs_host(tsx_hip_map *m, const tsx_hip_het_rule *rule, int fd, size_t chunk_bytes,
+                                            uint64_t *pairs_out, uint64_t *bytes_out) {
+    if (pairs_out) *pairs_out = 0;
+    if (bytes_out) *bytes_out = 0;
+    TSX_TRY(het_check(m, rule));
+    if (fd < 0) return combine_fail("het pairs: no output");
+    const int k = m->p.k, wk = m->p.wk;
+    const size_t line = 2 * ((size_t)k + 21) + 2, per_slot = rule->mode == TSX_HIP_HET_ALL ? 3 : 1;   // 2 x (bases, TAB, 20 digits), newline
+    const size_t rec_words = 2 * (size_t)wk + 2;
+    if (!chunk_bytes) chunk_bytes = WRITE_CHUNK_DEFAULT;
+    const uint64_t slots = m->lay.slots, per = std::min<uint64_t>(chunk_bytes / (line * per_slot), slots);
+    if (per < std::min<uint64_t>(64, slots)) return combine_fail("het pairs: chunk_bytes holds fewer than 64 slots");
+    const uint64_t cap = per * per_slot;
+    HIP_TRY(hipSetDevice(m->device));
+    bool sec = false;
+    TSX_TRY(het_settle(m, &sec));
+    const HetArgs ha = het_args(m, rule, sec);
+    hipStream_t st = m->stream.get();
+    ChunkAhead ahead(st, slots, per);
+    TSX_TRY(ahead.init((size_t)cap * rec_words * 8, 2));
+    std::vector<uint8_t> text;
+    uint64_t pairs = 0, bytes = 0;
+    const int rc = ahead.run(
+        [&](uint64_t lo, uint64_t hi, uint8_t *d_rec, unsigned long long *d_n, unsigned long long *h_n) -> int {
+            HIP_TRY(hipMemsetAsync(d_n, 0, 2 * 8, st));
+            TSX_TRY(het_launch(m, ha, true, lo, hi, 0, 0, nullptr, nullptr, (uint64_t *)d_rec, cap, d_n, st));
+            HIP_TRY(hipMemcpyAsync(h_n, d_n, 2 * 8, hipMemcpyDeviceToHost, st));
+            return TSX_HIP_OK;
+        },
+        [&](uint64_t, uint64_t, const unsigned long long *n, ChunkAhead::Range *r) -> int {
+            if (n[0] > cap) return TSX_HIP_ERANGE;   // cannot happen: a slot owns at most per_slot pairs
+            r[0].n = (size_t)n[0] * rec_words * 8;
+            return TSX_HIP_OK;
+        },
+        [&](uint64_t, uint64_t, const unsigned long long *n, const uint8_t *h_rec, const ChunkAhead::Range *) -> int {
+            text.resize((size_t)n[0] * line + 8);   // (+ the NUL that decode and snprintf put behind what they write)
+            size_t at = 0;
+            for (uint64_t i = 0; i < n[0]; ++i) {
+                const uint64_t *rec = (const uint64_t *)h_rec + i * rec_words;
+                for (int side = 0; side < 2; ++side) {
+                    tsx_hip_decode(rec + side * wk, k, (char *)text.data() + at);
+                    at += (size_t)k;
+                    at += (size_t)snprintf((char *)text.data() + at, 24, "\t%llu%c", (unsigned long long)rec[2 * wk + side], side ? '\n' : '\t');
+                }
+            }
+            TSX_TRY(write_all(fd, text.data(), at));
+            bytes += at; pairs += n[0];
+            return TSX_HIP_OK;
+        });
+    if (pairs_out) *pairs_out = pairs;
+    if (bytes_out) *bytes_out = bytes;
+    return rc;
 }
 
 extern "C" int tsx_hip_owner_host(const tsx_hip_map *m, const uint64_t *kmer, int nranks) {

@@ -440,6 +440,27 @@ public:
         check(rc);
     }
 
+    // heterozygous k-mer pairs of this table (tsx_hip_het_histogram_host): oMatrix[i * iNmajor + j] = pairs of k-mers that
+    // differ only in their middle base, counted i (the lower count) and j times, the last bin of each side pooling every
+    // larger count; k must be odd
+    tsx_hip_het_stats hetHistogram(const tsx_hip_het_rule &oRule, size_t iNminor, size_t iNmajor, std::vector<uint64_t> &oMatrix) {
+        oMatrix.assign(iNminor && iNmajor <= ((size_t)1 << 24) / iNminor ? iNminor * iNmajor : 0, 0);   // (a refused size allocates nothing)
+        tsx_hip_het_stats s = {0, 0, 0, 0, 0};
+        const int rc = tsx_hip_het_histogram_host(m_pMap, &oRule, oMatrix.data(), iNminor, iNmajor, &s);
+        if (rc == TSX_HIP_EINVAL) throw TSXException(tsx_hip_last_error(), rc);   // (the refusal says which argument)
+        check(rc);
+        return s;
+    }
+    // the pairs as minor_kmer<TAB>minor_count<TAB>major_kmer<TAB>major_count lines, the file created / truncated; returns the pairs
+    uint64_t writeHetPairs(const std::string &sPath, const tsx_hip_het_rule &oRule) {
+        return tsx_write_counts_file(sPath, [&](int fd, uint64_t *l, uint64_t *b) {
+            return tsx_hip_write_het_pairs_host(m_pMap, &oRule, fd, 0, l, b);
+        }, [&](int rc) {
+            if (rc == TSX_HIP_EINVAL) throw TSXException(tsx_hip_last_error(), rc);
+            check(rc);
+        });
+    }
+
     // read binning by two tables (tsx_hip_bin_stats_host): this is A, oOther is B; per record the windows that hit each
     // table, and (pClasses) its class TSX_HIP_BIN_*
     std::vector<tsx_hip_bin_stats> binStats(TSXHashMapHIP &oOther, const char *pText, size_t iBytes, const tsx_hip_bin_rule &oRule,

@@ -73,6 +73,11 @@ struct arguments {
     std::string joint_histo, joint_format = "sparse";
     uint64_t joint_max_a = 1000, joint_max_b = 1000;
     bool joint_opts = false;   // --joint-max-a / --joint-max-b / --joint-format were given
+    // heterozygous pairs of the table: --het-histo=FILE writes how many pairs of k-mers that differ only in their middle
+    // base are counted (minor, major) times, counts 0..H per side and one bin H+1 above (--het-max); --het-pairs=FILE the pairs
+    std::string het_histo, het_pairs, het_format = "sparse", het_mode = "unique";
+    uint64_t het_max = 1000, het_lower = 1, het_upper = UINT64_MAX;
+    bool het_opts = false;     // --het-max / --het-format / --het-lower / --het-upper / --het-mode were given
     // read binning by the two tables: the records of --bin-input (default --input) go to --bin-a / --bin-b /
     // --bin-ambiguous / --bin-none by the table they hit more; --bin-stats=FILE writes the hits of every record
     std::string bin_a, bin_b, bin_ambiguous, bin_none, bin_input, bin_stats;
@@ -123,6 +128,8 @@ static int usage() {
                  "                 [--joint-histo=FILE [--joint-max-a=H] [--joint-max-b=H] [--joint-format=sparse|matrix]]\n"
                  "                 [--bin-a=OUT] [--bin-b=OUT] [--bin-ambiguous=OUT] [--bin-none=OUT] [--bin-input=FILE]\n"
                  "                 [--bin-stats=FILE] [--bin-min-hits=N] [--bin-ratio=R]]\n"
+                 "                [--het-histo=FILE [--het-max=H] [--het-format=sparse|matrix]] [--het-pairs=FILE]\n"
+                 "                [--het-lower=N] [--het-upper=N] [--het-mode=unique|all]\n"
                  "Count k-mers on an MI355X. --check compares with FASTQ.<k>.count (kmer<TAB>count per line).\n"
                  "--l=auto sizes the table itself: the input is sketched first (HyperLogLog, 2^14 registers, on the GPU), and l\n"
                  "is the smallest table that holds the estimated distinct k-mers at load F (--load-factor, default 0.75, at most\n"
@@ -211,7 +218,17 @@ static int usage() {
                  "is counted and not written. --bin-stats=FILE writes\n"
                  "index<TAB>kmers<TAB>hits_a<TAB>hits_b<TAB>hits_both<TAB>class per record (class: a, b, ambiguous, none). It\n"
                  "prints bin<TAB>records<TAB>a<TAB>b<TAB>ambiguous<TAB>none. It needs --with; single-end input, no wrapped\n"
-                 "FASTA, one GPU only."
+                 "FASTA, one GPU only.\n"
+                 "--het-histo=FILE writes the heterozygous k-mer pairs of the table (Smudgeplot's hetkmers): how many pairs of\n"
+                 "k-mers that differ only in their middle base are counted `minor` and `major` times (minor <= major), over the\n"
+                 "k-mers counted --het-lower=N (default 1) to --het-upper=N times. --het-mode=unique (default) counts a pair only\n"
+                 "when no third k-mer shares its flanks, all counts every pair. --het-max=H (default 1000, at most 4094) gives\n"
+                 "counts 0..H and one bin H+1 above, per side; --het-format=sparse (default) writes minor<TAB>major<TAB>pairs for\n"
+                 "every cell that occurs, ordered by minor, then major; matrix writes a comment line, then H+2 lines of H+2\n"
+                 "numbers, the line being the minor count. --het-pairs=FILE writes the pairs themselves as\n"
+                 "minor_kmer<TAB>minor_count<TAB>major_kmer<TAB>major_count. Either prints\n"
+                 "het<TAB>kmers<TAB>paired<TAB>pairs<TAB>families2<TAB>families3plus. They run where --histo runs, on the table\n"
+                 "as --load / --input leave it and before --op replaces it. k must be odd; one GPU only."
               << std::endl;
     return 1;
 }
@@ -283,6 +300,39 @@ static std::string revcomp(const std::string &s) {
     std::string r(s.rbegin(), s.rend());
     for (char &c : r) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c;
     return r;
+}
+
+// --het-histo and --het-pairs: the heterozygous pairs of the table as files, and their totals on stdout
+static void write_het(TSXHashMapHIP &oMap, const arguments &a) {
+    if (a.het_histo.empty() && a.het_pairs.empty()) return;
+    const tsx_hip_het_rule oRule = {a.het_lower, a.het_upper, a.het_mode == "all" ? TSX_HIP_HET_ALL : TSX_HIP_HET_UNIQUE, 0};
+    const size_t nb = (size_t)a.het_max + 2;
+    std::vector<uint64_t> m;
+    const tsx_hip_het_stats s = oMap.hetHistogram(oRule, nb, nb, m);
+    if (!a.het_histo.empty()) {
+        std::ofstream f(a.het_histo);
+        if (a.het_format == "matrix") f << "# rows: minor count 0.." << nb - 1 << ", columns: major count\n";
+        for (size_t i = 0; i < nb; ++i) {
+            for (size_t j = 0; j < nb; ++j) {
+                const uint64_t n = m[i * nb + j];
+                if (a.het_format == "matrix") f << n << (j + 1 < nb ? '\t' : '\n');
+                else if (n) f << i << '\t' << j << '\t' << n << '\n';
+            }
+        }
+        f.close();
+        if (!f) throw TSXException("could not write " + a.het_histo, TSX_HIP_EIO);
+        std::cerr << "Wrote the het pair histogram to " << a.het_histo << std::endl;
+    }
+    if (!a.het_pairs.empty()) {
+        const uint64_t iPairs = oMap.writeHetPairs(a.het_pairs, oRule);
+        std::cerr << "Wrote " << iPairs << " het pairs to " << a.het_pairs << std::endl;
+    }
+    std::cout << "het\t" << s.kmers_in_range << '\t' << s.paired << '\t' << s.pairs << '\t' << s.families_2 << '\t'
+              << s.families_3plus << std::endl;
+}
+static void write_het(TSXHashMapHIPGroup &, const arguments &a) {   // (main refuses --gpus > 1 and runs --gpus=1 on the one table)
+    if (!a.het_histo.empty() || !a.het_pairs.empty())
+        throw TSXException("--het-histo and --het-pairs need the one table of a one-GPU run, not a group", TSX_HIP_EINVAL);
 }
 
 // --output and --histo, for one table or a group of them (after the count and the check)
@@ -789,6 +839,7 @@ static int report_and_check(Map &oMap, const arguments &a, double dt, bool outpu
         save_database(oMap, a);
         write_outputs(oMap, a);
     }
+    write_het(oMap, a);   // (of the table as it is now, whatever --op makes of it later)
     oMap.print_stats();
     return rc;
 }
@@ -918,6 +969,41 @@ int main(int argc, char *argv[]) {
                 return usage();
             }
             a.bin_opts = true;
+        }
+        else if (opt(argv[i], "het-histo", v)) { a.het_histo = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "het-pairs", v)) { a.het_pairs = v; if (v.empty()) return usage(); }
+        else if (opt(argv[i], "het-max", v)) {
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long h = strtoull(v.c_str(), &end, 10);
+            // (H + 2)^2 <= 2^24: H <= 4094
+            if (v.empty() || *end || errno || v[0] == '-' || h < 1 || h > 4094) {
+                std::cerr << "--het-max takes the largest count with a bin of its own: a number 1 .. 4094" << std::endl;
+                return usage();
+            }
+            a.het_max = h;
+            a.het_opts = true;
+        }
+        else if (opt(argv[i], "het-format", v)) {
+            if (v != "sparse" && v != "matrix") { std::cerr << "--het-format is sparse or matrix" << std::endl; return usage(); }
+            a.het_format = v;
+            a.het_opts = true;
+        }
+        else if (opt(argv[i], "het-mode", v)) {
+            if (v != "unique" && v != "all") { std::cerr << "--het-mode is unique or all" << std::endl; return usage(); }
+            a.het_mode = v;
+            a.het_opts = true;
+        }
+        else if (opt(argv[i], "het-lower", v) || opt(argv[i], "het-upper", v)) {
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long c = strtoull(v.c_str(), &end, 10);
+            if (v.empty() || *end || errno || v[0] == '-') {
+                std::cerr << "--het-lower / --het-upper take a count: a number 0 .. 2^64 - 1" << std::endl;
+                return usage();
+            }
+            (std::string(argv[i]).compare(0, 11, "--het-lower") == 0 ? a.het_lower : a.het_upper) = c;
+            a.het_opts = true;
         }
         else if (opt(argv[i], "format", v)) a.format = v;
         else if (opt(argv[i], "device", v)) a.device = atoi(v.c_str());
@@ -1076,6 +1162,19 @@ int main(int argc, char *argv[]) {
     if (a.joint_opts && a.joint_histo.empty()) {
         std::cerr << "--joint-max-a, --joint-max-b and --joint-format go with --joint-histo=FILE" << std::endl;
         return usage();
+    }
+    if (a.het_opts && a.het_histo.empty() && a.het_pairs.empty()) {
+        std::cerr << "--het-max, --het-format, --het-lower, --het-upper and --het-mode go with --het-histo=FILE or --het-pairs=FILE" << std::endl;
+        return usage();
+    }
+    if (!a.het_histo.empty() || !a.het_pairs.empty()) {
+        if (a.gpus > 1) {
+            std::cerr << "--het-histo and --het-pairs work on one GPU only: a --gpus " << a.gpus << " run keeps one table per GPU, and a"
+                      << " k-mer's partners may live on another" << std::endl;
+            return usage();
+        }
+        if (a.het_lower > a.het_upper) { std::cerr << "--het-lower is above --het-upper" << std::endl; return usage(); }
+        a.group = false;   // --gpus=1: the one table of this process
     }
     if (!a.joint_histo.empty() && a.gpus > 1) {
         std::cerr << "--joint-histo works on one GPU only: a --gpus " << a.gpus << " run keeps one table per GPU" << std::endl;
@@ -1258,6 +1357,10 @@ int main(int argc, char *argv[]) {
     }
     if (wants_queries(a) && a.input_path.empty() && a.filter_input.empty()) {
         std::cerr << "--filter and --read-stats without --input need --filter-input=FILE" << std::endl;
+        return usage();
+    }
+    if ((!a.het_histo.empty() || !a.het_pairs.empty()) && !(a.k & 1)) {
+        std::cerr << "--het-histo and --het-pairs need an odd k: a " << a.k << "-mer has no middle base" << std::endl;
         return usage();
     }
     if (!a.save.empty() || !a.load.empty() || !a.with.empty()) a.group = false;   // --gpus=1: the one table of this process
