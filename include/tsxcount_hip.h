@@ -913,6 +913,18 @@ int tsx_hip_hash_rows(const tsx_hip_map *m, uint64_t *rows_out /* 2k x key_limbs
 /* One-limb keys (k <= 32): the 16 x 16 table by 4-bit groups that the walk hashes a strip's first window with, as a map
  * made with (k, l, hash_seed) gets it: lut_out[grp * 16 + v] = M * ((v << 4 grp) & (2^2k - 1)).  Host only, no GPU call. */
 int tsx_hip_lut4_host(int k, int l, uint64_t hash_seed, uint64_t *lut_out /* 256 */);
+/* The level-1 sub-lists of the partitioned path (walk fused with radix level 1): list (b, g) -- bucket b of nb, walk
+ * workgroup g of G -- holds at most cap records and starts at record tsx_hip_sublist_first() of its buffer, numbered
+ * bucket-major (b * G + g) or, after a plain one-GPU count, workgroup-major (g * nb + b); its size is published at the
+ * same number.  tsx_hip_level1_sizes_host: shape and order of the lists the LAST such count of the map left and, with
+ * sizes_out (room for nb * G), their published sizes in that order -- valid until the map counts again.  For tests. */
+typedef struct tsx_hip_level1_shape {
+    uint32_t nb, G, cpr2;   /* cpr2: level-2 workgroups per bucket; workgroup c reads pieces c, c + cpr2, ... as one stream */
+    int wg_major;
+    uint64_t cap;
+} tsx_hip_level1_shape;
+uint64_t tsx_hip_sublist_first(uint32_t nb, uint32_t G, int wg_major, uint32_t b, uint32_t g, uint64_t cap);
+int tsx_hip_level1_sizes_host(tsx_hip_map *m, tsx_hip_level1_shape *shape_out, uint64_t *sizes_out /* optional */, size_t cap);
 
 /*
  * Multi-GPU counting with a sharded table (k <= 32).  Reads shard across the GPUs;

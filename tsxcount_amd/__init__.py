@@ -121,6 +121,12 @@ class PrefilterTotals(ctypes.Structure):
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
+class Level1Shape(ctypes.Structure):
+    """tsx_hip_level1_shape: the level-1 sub-lists the last plain partitioned count of a map left."""
+    _fields_ = [("nb", ctypes.c_uint32), ("G", ctypes.c_uint32), ("cpr2", ctypes.c_uint32), ("wg_major", ctypes.c_int),
+                ("cap", ctypes.c_uint64)]
+
+
 class DbInfo(ctypes.Structure):
     """tsx_hip_db_info: the header of a k-mer database file."""
     _fields_ = [("version", ctypes.c_uint32), ("k", ctypes.c_int32), ("l", ctypes.c_int32),
@@ -637,6 +643,9 @@ def lib():
     L.tsx_hip_hash_invert.argtypes = [vp, u64p, u64p]
     L.tsx_hip_hash_rows.argtypes = [vp, u64p]
     L.tsx_hip_lut4_host.argtypes = [ci, ci, ctypes.c_uint64, u64p]
+    L.tsx_hip_sublist_first.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ci, ctypes.c_uint32, ctypes.c_uint32, u64]
+    L.tsx_hip_sublist_first.restype = u64
+    L.tsx_hip_level1_sizes_host.argtypes = [vp, ctypes.POINTER(Level1Shape), u64p, sz]
     L.tsx_hip_set_timing.argtypes = [vp, ci]
     L.tsx_hip_get_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                      ctypes.POINTER(ctypes.c_double), u64p]

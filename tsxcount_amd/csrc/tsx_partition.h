@@ -22,6 +22,7 @@
 // build has written its segments, so a freshly cleared table needs no memset.
 #pragma once
 #include "tsx_kernels.h"
+#include "tsx_layout.h"
 #include <type_traits>
 
 namespace tsx {
@@ -186,12 +187,13 @@ __device__ __forceinline__ void spill_record(const TableParams *pk, TSX_LDS Spil
 template <int RW>
 __global__ __launch_bounds__(256) void skew_probe_kernel(const uint64_t *src, const unsigned long long *src_start,
                                                          const unsigned long long *src_cnt, const unsigned long long *src_pcnt,
-                                                         uint32_t src_np, uint64_t src_pcap, uint32_t *flag) {
+                                                         uint32_t src_np, uint64_t src_pcap, int src_wgm, uint32_t *flag) {
     constexpr uint32_t TN = 8192, SAMPLE = 4096, HOT = 4, MANY = 8;
     __shared__ uint64_t s_tag[TN];
     __shared__ uint32_t s_num[TN];
     __shared__ uint32_t s_seen, s_mass;
     const uint32_t tid = threadIdx.x, r = blockIdx.x;
+    const SubListOrder po = sublist_order(gridDim.x, src_np, src_wgm);   // pieces: the sub-lists of the fused walk (tsx_layout.h)
     for (uint32_t t = tid; t < TN; t += 256) { s_tag[t] = 0; s_num[t] = 0; }
     if (tid == 0) { s_seen = 0; s_mass = 0; }
     __syncthreads();
@@ -200,8 +202,9 @@ __global__ __launch_bounds__(256) void skew_probe_kernel(const uint64_t *src, co
         uint64_t at = ~0ULL;   // record index in src
         if (src_pcnt) {        // run i / 16 of the sample comes from piece (i / 16) * src_np / (SAMPLE / 16)
             const uint32_t run = i >> 4, g = (uint32_t)(((uint64_t)run * src_np) / (SAMPLE / 16));
-            const uint64_t pa = (uint64_t)r * src_np + g, cnt = min((uint64_t)src_pcnt[pa], src_pcap);
-            if (cnt >= 16) at = pa * src_pcap + (mix64(pa + 0x51ED) % (cnt - 15)) + (i & 15u);
+            const uint64_t pa = (uint64_t)r * src_np + g;   // (names the piece for the pseudo-random place, whatever the order)
+            const uint64_t cnt = min((uint64_t)src_pcnt[sublist_number(po, r, g)], src_pcap);
+            if (cnt >= 16) at = sublist_first(po, r, g, src_pcap) + (mix64(pa + 0x51ED) % (cnt - 15)) + (i & 15u);
         } else {
             const uint64_t cnt = src_cnt[r];
             if (cnt > i) at = (uint64_t)src_start[r] + (cnt > SAMPLE ? (mix64(r + 0x51ED) % (cnt - SAMPLE + 1)) : 0) + i;
@@ -242,8 +245,8 @@ __global__ __launch_bounds__(NT) void partition_ring_kernel(
     uint64_t src_cap, uint32_t nregions, uint32_t cpr, uint64_t *dst, const unsigned long long *offs,
     const unsigned long long *offs_base, unsigned long long *dst_cnt, uint64_t dst_cap, uint32_t nb, uint32_t shift,
     uint32_t capbits, uint64_t *ovq_all, uint32_t *ovq_cnt, uint32_t ovq_cap,
-    const unsigned long long *src_pcnt, uint32_t src_np, uint64_t src_pcap, int dst_bm, unsigned long long *key_sum,
-    uint32_t dst_r0, uint32_t dst_nr, int fmt, uint32_t dch, const uint32_t *skew_flag) {
+    const unsigned long long *src_pcnt, uint32_t src_np, uint64_t src_pcap, int src_wgm, int dst_bm,
+    unsigned long long *key_sum, uint32_t dst_r0, uint32_t dst_nr, int fmt, uint32_t dch, const uint32_t *skew_flag) {
     constexpr int RPT = (PART_WPT >= RW) ? PART_WPT / RW : 1;   // records per thread per batch
     extern __shared__ uint64_t s_part[];  // rings | cursors | limits | flush descriptors | tails | heads | jobs
     const uint32_t CAP = 1u << capbits, cmask = CAP - 1;
@@ -277,9 +280,10 @@ __global__ __launch_bounds__(NT) void partition_ring_kernel(
     }
     lds_barrier();
     // The source region r: a contiguous run of records (src_start/src_cnt, or src_cap apart), or -- src_pcnt
-    // given -- src_np PIECES of at most src_pcap records each, piece g at ((r * src_np + g) * src_pcap) with
-    // src_pcnt[r * src_np + g] records (the sub-lists walk_part_kernel's workgroups keep per level-1 bucket);
-    // workgroup c of the region then takes pieces c, c + cpr, ... as one stream.
+    // given -- src_np PIECES of at most src_pcap records each: piece g is sub-list (r, g) of tsx_layout.h, in the
+    // order src_wgm names (bucket-major: at ((r * src_np + g) * src_pcap) with src_pcnt[r * src_np + g] records;
+    // workgroup-major after the walk of a plain one-GPU count) -- the sub-lists walk_part_kernel's workgroups keep
+    // per level-1 bucket; workgroup c of the region then takes pieces c, c + cpr, ... as one stream.
     const uint64_t n = src_pcnt ? 0 : (src_start ? (uint64_t)src_cnt[r] : min((uint64_t)src_cnt[r], src_cap));   // records
     const uint64_t region_first = src_pcnt ? 0 : (src_start ? (uint64_t)src_start[r] : (uint64_t)r * src_cap);
     constexpr uint32_t BATCH_REC = (uint32_t)NT * RPT;
@@ -416,9 +420,10 @@ __global__ __launch_bounds__(NT) void partition_ring_kernel(
     // the sizes of this workgroup's pieces (c, c + cpr, ...) wait in LDS: the stream logic below is on the
     // critical path of every batch and must not go to memory
     __shared__ uint32_t s_pc[PART_MAX_PIECES];
+    const SubListOrder po = sublist_order(nregions, src_np, src_wgm);
     if (src_pcnt) {
         for (uint32_t i = tid; c + i * cpr < src_np && i < (uint32_t)PART_MAX_PIECES; i += NT)
-            s_pc[i] = (uint32_t)min((uint64_t)src_pcnt[(uint64_t)r * src_np + c + i * cpr], src_pcap);
+            s_pc[i] = (uint32_t)min((uint64_t)src_pcnt[sublist_number(po, r, c + i * cpr)], src_pcap);
         lds_barrier();
     }
     const uint32_t npw = (src_pcnt && c < src_np) ? min((src_np - c + cpr - 1) / cpr, (uint32_t)PART_MAX_PIECES) : 0u;
@@ -442,10 +447,10 @@ __global__ __launch_bounds__(NT) void partition_ring_kernel(
         }
         if (pi >= npw) { d.first = 0; d.rem = 0; d.nvalid = 0; return d; }
         const uint32_t left = pcnt(pi) - poff, cb = pcnt(pi + 1);
-        const uint64_t pa = (uint64_t)r * src_np + c + (uint64_t)pi * cpr;   // number of the piece among all
-        d.first = pa * src_pcap + poff;
+        const uint32_t g = c + pi * cpr;   // the piece, and the next one of this stream: g + cpr
+        d.first = sublist_first(po, r, g, src_pcap) + poff;
         d.rem = min(left, BATCH_REC);
-        d.delta = (pa + cpr) * src_pcap - (d.first + left);
+        d.delta = sublist_first(po, r, g + cpr, src_pcap) - (d.first + left);
         d.nvalid = (uint32_t)min((uint64_t)BATCH_REC, (uint64_t)left + cb);
         if (left > BATCH_REC) poff += BATCH_REC;
         else { ++pi; poff = d.nvalid - left; }
@@ -586,8 +591,9 @@ __global__ __launch_bounds__(NT) void partition_ring_kernel(
 // A key log that level 1 reads again costs 12.9 GB and a 3 ms launch per 1e9 k-mers for nothing but a histogram.
 // walk_part_kernel keeps the level-1 staging rings next to the walk: the keys of a strip go straight into the ring of
 // their level-1 bucket, bursts of 128 B leave for the workgroup's own sub-list of that bucket (fixed capacity dst_cap,
-// list (b, g) at ((b * G + g) * dst_cap), its size in dst_cnt[b * G + g]; what does not fit: spill cache / overflow
-// queue / deferred list, as in level 2).  Level 2 reads a bucket as the G pieces the workgroups left
+// list (b, g) at number * dst_cap, its size in dst_cnt[number], the number by tsx_layout.h: b * G + g, or g * nb + b
+// where the launch says dst_wgm; what does not fit: spill cache / overflow queue / deferred list, as in level 2).
+// Level 2 reads a bucket as the G pieces the workgroups left
 // (partition_ring_kernel, src_pcnt).  512 threads, two workgroups per CU: the rings take 64 KiB, the LUT of the first
 // window is the 4-bit-group one (2 KiB, 16 lookups per strip instead of 8) so that two workgroups fit.
 constexpr int SP_NT = 512;
@@ -655,7 +661,8 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
                                                             uint32_t nb, uint32_t shift, uint64_t *ovq_all,
                                                             uint32_t *ovq_cnt, uint32_t ovq_cap, uint64_t n_packed,
                                                             uint32_t dst_g0, uint32_t dst_gtot, int own_flags,
-                                                            unsigned long long *emit_sum, int long_desc, uint32_t flush_q) {
+                                                            unsigned long long *emit_sum, int long_desc, uint32_t flush_q,
+                                                            int dst_wgm) {
     // own_flags: low two bits = 0 local run, 1 keep only the keys this shard owns, 2 minimizer exchange (below); 4 = this launch
     // APPENDS to the sub-lists and the overflow queue an earlier launch of the same step left (windows of a sharded step)
     const int own_only = LOCAL ? 0 : own_flags & 3;
@@ -687,8 +694,11 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
     // array of n_packed entries cut into runs of desc_cap; only the keys this GPU owns are kept (own_only); the launch
     // fills lists (b, dst_g0 + g) of dst_gtot per bucket.  Local runs: n_packed = 0, dst_g0 = 0, dst_gtot = G.
     // own_only 2 (minimizer exchange, a table of this GPU's own): every key stays and is counted in emit_sum; no homopolymers.
+    // dst_wgm: the lists are numbered workgroup-major (tsx_layout.h; launch_walk_part says so for the LOCAL form alone)
     const uint32_t gl = dst_g0 + wg;
-    auto word_of = [&](uint32_t b, uint32_t at) -> uint64_t * { return dst + ((uint64_t)(b * dst_gtot + gl) * (uint64_t)cap32 + at); };
+    const SubListOrder ord = sublist_order(nb, dst_gtot, dst_wgm);
+    const uint32_t li0 = sublist_number(ord, 0, gl);   // list (b, gl) has the number li0 + b * ord.step_b
+    auto word_of = [&](uint32_t b, uint32_t at) -> uint64_t * { return dst + ((uint64_t)(li0 + b * ord.step_b) * (uint64_t)cap32 + at); };
     auto is_mine = [&](uint64_t hk) -> bool {
         if constexpr (LOCAL) return true;
         if (own_only != 1) return true;
@@ -714,7 +724,7 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
     if (tid < OVF_N) { s_ovk[tid] = 0; s_ovc[tid] = 0; }
     if (tid < 2) s_njobs[tid] = 0;
     if (tid == 0) s_ovn = (append && ovq_cnt) ? ovq_cnt[blockIdx.x] : 0u;
-    for (uint32_t b = tid; b < nb; b += NT) { s_cur[b] = append ? (uint32_t)dst_cnt[(uint64_t)b * dst_gtot + dst_g0 + blockIdx.x] : 0u; s_th[b] = 0; }
+    for (uint32_t b = tid; b < nb; b += NT) { s_cur[b] = append ? (uint32_t)dst_cnt[li0 + b * ord.step_b] : 0u; s_th[b] = 0; }
     uint64_t *ovq = ovq_all ? ovq_all + (size_t)blockIdx.x * ovq_cap : nullptr;
     unsigned long long added = 0;   // (k-mers are counted by strip_desc_kernel)
     unsigned long long emitted = 0; // sharded runs: k-mer occurrences this GPU kept (sum over GPUs == k-mers scanned)
@@ -993,7 +1003,7 @@ __global__ __launch_bounds__(NT, 4) void walk_part_kernel(TableParams p, const u
     lds_barrier();
     flush(true, false);
     lds_barrier();
-    for (uint32_t b = tid; b < nb; b += NT) dst_cnt[(uint64_t)b * dst_gtot + gl] = min(s_cur[b], cap32);
+    for (uint32_t b = tid; b < nb; b += NT) dst_cnt[li0 + b * ord.step_b] = min(s_cur[b], cap32);
     if (tid < OVF_N && s_ovc[tid]) defer_append1(pk, s_ovk[tid] ^ OVF_SALT, s_ovc[tid]);
     if (tid == 0 && ovq_cnt) ovq_cnt[blockIdx.x] = min(s_ovn, ovq_cap);
     if (tid < (NT / 64) * HOT_N && s_hot_cnt[tid]) defer_append1(pk, s_hot_key[tid], s_hot_cnt[tid]);

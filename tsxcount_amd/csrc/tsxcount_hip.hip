@@ -79,13 +79,19 @@ struct PartPlan {
     uint32_t *d_hist;
     size_t cnt_need;
     // walk fused with level 1 (walk_part_kernel): G1 workgroups, each with a sub-list of cap1 records per level-1
-    // bucket in buffer 1 (list (b, g) at (b * G1 + g) * cap1), sizes in c_l1[b * G1 + g]
+    // bucket in buffer 1: list (b, g) at number * cap1, its size in c_l1[number], the number by tsx_layout.h --
+    // b * G1 + g, or g * nb1 + b (l1_wgm) once the LOCAL walk of a plain one-GPU count has filled them
     bool fused;
+    bool l1_wgm;
     uint32_t G1;
     uint64_t cap1;
     unsigned long long *c_l1;
     uint64_t *buf1;              // buffer 1 of this plan (the map's, or the window-wise sharded level 1's own)
 };
+
+// What the last fused walk of a plain count left (tsx_hip_level1_sizes_host): where its list sizes lie in d_cnt, and the
+// shape and order of the lists.
+struct L1Seen { size_t at = 0; uint32_t nb = 0, G = 0, cpr2 = 0; uint64_t cap = 0; int wg_major = 0; };
 
 // Ownership (tsx_own.h): every device buffer, pinned buffer, event and stream of a map is a member that releases
 // itself -- adding one is adding a member, nothing else.  The capacities are the owners' (bytes).  TableParams only
@@ -139,6 +145,7 @@ struct tsx_hip_map {
     int path = 0;                    // 0 auto, 1 atomic, 2 partitioned (tsx_hip_set_path / TSX_HIP_PATH)
     DevBuf<uint64_t> d_buf[2];
     DevBuf<unsigned long long> d_cnt;      // [log regions | level-1 lists | segment lists]
+    L1Seen l1_seen;
     // optional per-pass timing (HIP events on the launch stream)
     DevBuf<uint64_t> d_small;        // scratch of tsx_hip_get_counts_host / tsx_hip_lookup_host for a few k-mers
     bool attr_done = false;          // dynamic-LDS limits of the partition / build kernels set on this map's device
@@ -937,6 +944,7 @@ static int plan_partition(tsx_hip_map *m, uint64_t maxrec, int g, bool own_log, 
     pl.fused = fused_g > 0 && pl.b2 > 0 && p.wk == 1 && (fused_g + pl.cpr2 - 1) / pl.cpr2 <= (uint32_t)PART_MAX_PIECES;
     pl.G1 = pl.fused ? (uint32_t)fused_g : 0;
     pl.cap1 = 0;
+    pl.l1_wgm = false;   // (whoever fills the lists says otherwise: scan_fused)
     if (pl.fused) {
         const uint64_t per1 = maxrec / pl.nb1 / pl.G1;
         pl.cap1 = (per1 + per1 / 4 + 6 * (uint64_t)std::sqrt((double)per1 + 1.0) + 64 + 15) & ~15ULL;
@@ -978,14 +986,18 @@ struct WalkPartLaunch {
     uint64_t *dst = nullptr; uint64_t dst_cap = 0; unsigned long long *dst_cnt = nullptr; uint32_t nb = 0, shift = 0;
     uint64_t *ovq_all = nullptr; uint32_t *ovq_cnt = nullptr; uint32_t ovq_cap = 0; uint64_t n_packed = 0;
     uint32_t dst_g0 = 0, dst_gtot = 0; int own_flags = 0; unsigned long long *emit_sum = nullptr; int long_desc = 0; uint32_t flush_q = 0;
+    int dst_wgm = 0;   // set by launch_walk_part: the lists are numbered workgroup-major (tsx_layout.h) -- the LOCAL form, and it alone
 };
-static void launch_walk_part(tsx_hip_map *m, hipStream_t st, const TableParams &pp, const WalkPartLaunch &a) {
+static void launch_walk_part(tsx_hip_map *m, hipStream_t st, const TableParams &pp, WalkPartLaunch &a) {
     const size_t lds = walk_lds_bytes(a.nb);
 #define TSX_WALK(NTV, CANV, LOCV)                                                                                              \
     hipLaunchKernelGGL((walk_part_kernel<NTV, CANV, LOCV>), dim3(a.grid), dim3(NTV), lds, st, pp, a.desc, a.desc_cap,          \
                        a.desc_cnt, a.nregions, a.dst, a.dst_cap, a.dst_cnt, a.nb, a.shift, a.ovq_all, a.ovq_cnt, a.ovq_cap,    \
-                       a.n_packed, a.dst_g0, a.dst_gtot, a.own_flags, a.emit_sum, a.long_desc, a.flush_q)
+                       a.n_packed, a.dst_g0, a.dst_gtot, a.own_flags, a.emit_sum, a.long_desc, a.flush_q, a.dst_wgm)
     const bool local = walk_local_form(a.own_flags, a.n_packed, a.long_desc, a.flush_q, a.emit_sum, a.dst_g0);
+    // The LOCAL form fills all G lists of every bucket in one launch and nothing is appended to them later: it keeps a
+    // workgroup's lists side by side.  The general form fills list sets launch by launch and stays bucket-major.
+    a.dst_wgm = local ? 1 : 0;
     if (lds > ONE_WG_LDS) {   // 512 lists
         if (local) { DISPATCH_CANON(m, TSX_WALK(1024, CANV, true)); } else { DISPATCH_CANON(m, TSX_WALK(1024, CANV, false)); }
     } else {
@@ -1012,7 +1024,9 @@ struct RingLaunch {
     uint32_t nregions = 0, cpr = 1; uint64_t *dst = nullptr; const unsigned long long *offs = nullptr, *offs_base = nullptr;
     unsigned long long *dst_cnt = nullptr; uint64_t dst_cap = 0; uint32_t nb = 0, shift = 0, capbits = 0;
     uint64_t *ovq_all = nullptr; uint32_t *ovq_cnt = nullptr; uint32_t ovq_cap = 0;
-    const unsigned long long *src_pcnt = nullptr; uint32_t src_np = 0; uint64_t src_pcap = 0; int dst_bm = 0;
+    const unsigned long long *src_pcnt = nullptr; uint32_t src_np = 0; uint64_t src_pcap = 0;
+    int src_wgm = 0;          // the pieces are sub-lists numbered workgroup-major (tsx_layout.h): what follows a LOCAL walk
+    int dst_bm = 0;
     unsigned long long *key_sum = nullptr; uint32_t dst_r0 = 0, dst_nr = 0; int fmt = 0; uint32_t dch = 0; const uint32_t *skew_flag = nullptr;
 };
 static void launch_ring(hipStream_t st, const TableParams &pp, const RingLaunch &a) {
@@ -1020,8 +1034,8 @@ static void launch_ring(hipStream_t st, const TableParams &pp, const RingLaunch 
 #define TSX_RING(RWV, NTV, SK)                                                                                                 \
     hipLaunchKernelGGL((partition_ring_kernel<RWV, NTV, SK>), dim3(a.grid), dim3(NTV), lds, st, pp, a.src, a.src_start,        \
                        a.src_cnt, a.src_cap, a.nregions, a.cpr, a.dst, a.offs, a.offs_base, a.dst_cnt, a.dst_cap, a.nb,        \
-                       a.shift, a.capbits, a.ovq_all, a.ovq_cnt, a.ovq_cap, a.src_pcnt, a.src_np, a.src_pcap, a.dst_bm,        \
-                       a.key_sum, a.dst_r0, a.dst_nr, a.fmt, a.dch, a.skew_flag)
+                       a.shift, a.capbits, a.ovq_all, a.ovq_cnt, a.ovq_cap, a.src_pcnt, a.src_np, a.src_pcap, a.src_wgm,       \
+                       a.dst_bm, a.key_sum, a.dst_r0, a.dst_nr, a.fmt, a.dch, a.skew_flag)
     // (512 lists: the rings leave room for one workgroup per CU -- 1024 threads then, 16 waves either way)
     if (!a.fixed_nt && lds > ONE_WG_LDS) {
         if (a.skew) { DISPATCH_RW(a.rw, TSX_RING(RWV, 1024, true)); } else { DISPATCH_RW(a.rw, TSX_RING(RWV, 1024, false)); }
@@ -1169,14 +1183,15 @@ static int run_partition_build(tsx_hip_map *m, const PartPlan &pl, const uint64_
         uint32_t *d_skew = m->d_ovq_cnt.get() + ovq_queues(m, rw);   // (ensure_ovq keeps one spare counter behind the queues')
         DISPATCH_RW(rw, hipLaunchKernelGGL((skew_probe_kernel<RWV>), dim3(pl.nb1), dim3(256), 0, st, (const uint64_t *)pl.buf1,
                                            (const unsigned long long *)pl.c_bstart, (const unsigned long long *)pl.c_bcnt,
-                                           (const unsigned long long *)(pl.fused ? pl.c_l1 : nullptr), pl.G1, pl.cap1, d_skew));
+                                           (const unsigned long long *)(pl.fused ? pl.c_l1 : nullptr), pl.G1, pl.cap1,
+                                           pl.l1_wgm ? 1 : 0, d_skew));
         RingLaunch r;
         r.grid = pl.nb1 * pl.cpr2; r.rw = rw;
         r.src = pl.buf1; r.src_start = pl.c_bstart; r.src_cnt = pl.c_bcnt; r.nregions = pl.nb1; r.cpr = pl.cpr2;
         r.dst = m->d_buf[0].get(); r.dst_cnt = pl.c_seg; r.dst_cap = pl.cap_sub;
         r.nb = pl.nb2; r.shift = (uint32_t)p.S; r.capbits = ring_bits(pl.nb2);
         r.ovq_all = m->d_ovq.get(); r.ovq_cnt = m->d_ovq_cnt.get(); r.ovq_cap = OVQ_CAP;
-        r.src_pcnt = pl.fused ? pl.c_l1 : nullptr; r.src_np = pl.G1; r.src_pcap = pl.cap1;
+        r.src_pcnt = pl.fused ? pl.c_l1 : nullptr; r.src_np = pl.G1; r.src_pcap = pl.cap1; r.src_wgm = pl.l1_wgm ? 1 : 0;
         r.fmt = pre; r.dch = dch; r.skew_flag = d_skew;
         launch_ring(st, pp, r);
         r.skew = true;
@@ -1388,7 +1403,7 @@ static int count_piece_atomic(tsx_hip_map *m, const PieceText &t, Event *ev, hip
 // The scan fused with radix level 1 (local runs, one-limb keys, two radix levels), in two kernels: strip descriptions
 // (16 B per strip with a k-mer start, one region per wave, in buffer 0 -- level 2 overwrites it later), then the walk with
 // every lane busy.  All keys stay on this GPU: a ring flush per quarter strip (flush_q = 1).
-static int scan_fused(tsx_hip_map *m, const PieceText &t, const PartPlan &pl, const TableParams &pp, int gd, hipStream_t st) {
+static int scan_fused(tsx_hip_map *m, const PieceText &t, PartPlan &pl, const TableParams &pp, int gd, hipStream_t st) {
     const int gdreg = gd * (NT / 64);
     const uint32_t nq2 = pl.nb1 * pl.cpr2;
     TSX_TRY(ensure_ovq(m, (size_t)nq2 + pl.G1, pl.rw, st));
@@ -1407,6 +1422,8 @@ static int scan_fused(tsx_hip_map *m, const PieceText &t, const PartPlan &pl, co
     w.ovq_all = m->d_ovq.get() + (size_t)nq2 * OVQ_CAP; w.ovq_cnt = m->d_ovq_cnt.get() + nq2; w.ovq_cap = OVQ_CAP;
     w.dst_gtot = pl.G1; w.long_desc = lng; w.flush_q = 1u;
     launch_walk_part(m, st, pp, w);
+    pl.l1_wgm = w.dst_wgm != 0;   // level 2 and the skew probe read the lists in the order the walk left them
+    m->l1_seen = L1Seen{(size_t)(pl.c_l1 - m->d_cnt.get()), pl.nb1, pl.G1, pl.cpr2, pl.cap1, w.dst_wgm};
     return TSX_HIP_OK;
 }
 
@@ -4280,6 +4297,22 @@ extern "C" int tsx_hip_lut4_host(int k, int l, uint64_t hash_seed, uint64_t *lut
     std::vector<uint64_t> lut4;
     make_lut4(&t, lut4);
     memcpy(lut_out, lut4.data(), lut4.size() * 8);
+    return TSX_HIP_OK;
+}
+
+extern "C" uint64_t tsx_hip_sublist_first(uint32_t nb, uint32_t G, int wg_major, uint32_t b, uint32_t g, uint64_t cap) {
+    return sublist_first(sublist_order(nb, G, wg_major), b, g, cap);
+}
+extern "C" int tsx_hip_level1_sizes_host(tsx_hip_map *m, tsx_hip_level1_shape *shape_out, uint64_t *sizes_out, size_t cap) {
+    if (!m || !shape_out) return TSX_HIP_EINVAL;
+    const L1Seen &s = m->l1_seen;
+    const size_t n = (size_t)s.nb * s.G;
+    *shape_out = tsx_hip_level1_shape{s.nb, s.G, s.cpr2, s.wg_major, s.cap};
+    if (!sizes_out) return TSX_HIP_OK;
+    if (n == 0 || cap < n || (s.at + n) * 8 > m->d_cnt.cap()) return TSX_HIP_EINVAL;
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipStreamSynchronize(m->stream.get()));
+    HIP_TRY(hipMemcpy(sizes_out, m->d_cnt.get() + s.at, n * 8, hipMemcpyDeviceToHost));
     return TSX_HIP_OK;
 }
 
