@@ -55,7 +55,7 @@ def main():
     ap.add_argument("--lib", default=None)
     a = ap.parse_args()
     if a.lib:
-        T.LIB_PATH = os.path.abspath(a.lib)
+        T._abi.LIB_PATH = T.LIB_PATH = os.path.abspath(a.lib)   # (lib() reads its own module's)
     dev = torch.device("cuda", 0)
     torch.zeros(1, device=dev)
     A = counted(a, 0, dev)

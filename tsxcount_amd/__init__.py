@@ -1,2156 +1,36 @@
 """tsxcount_amd -- MI355X (gfx950) k-mer counting hash map behind tsxCount's --mode=HIP.
 
 The product is ``lib/libtsxcount_hip.so`` (hand-written HIP, C ABI in
-``include/tsxcount_hip.h``).  This module is the thin host-side mirror of the
+``include/tsxcount_hip.h``).  This package is the thin host-side mirror of the
 reference's ``TSXHashMap`` surface over that ABI (ctypes), used by the tests
 and the bench.  There is no CPU fallback: without the built library the
-import fails, and without a GPU ``TSXHashMapHIP(...)`` raises.
+first call fails, and without a GPU ``TSXHashMapHIP(...)`` raises.
+
+Where things live (everything below is re-exported here, ``import tsxcount_amd as T`` is the surface):
+
+_abi     the mirror of the C ABI: error codes, structures, dtypes, rule builders, the signature table, lib(), _check
+models   the CPU statements of what the device computes (what the tests compare it against)
+table    TSXHashMapHIP, sketch_estimate, suggest_l
+group    TSXHashMapHIPGroup
+textio   BGZF, wrapped FASTA, cut_records, the synth entry points, database_info
 """
-import ctypes
-import os
-
-import numpy as np
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "lib", "libtsxcount_hip.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tsxcount_hip.h")
-
-OK, EINVAL, ENODEVICE, ENOMEM, EHIP, EFULL, EOVERFLOW, ERANGE, ELOCK, EIO = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9
-EFORMAT = -10
-EPAIR = -11
-
-
-class TSXException(RuntimeError):
-    """Mirror of TSXException (TSXHashMap.h:28-47); carries the C-ABI code."""
-
-    def __init__(self, code, what):
-        super().__init__(what)
-        self.code = code
-
-
-class Layout(ctypes.Structure):
-    _fields_ = [("k", ctypes.c_int32), ("l", ctypes.c_int32), ("key_limbs", ctypes.c_int32),
-                ("entry_limbs", ctypes.c_int32), ("func_bits", ctypes.c_int32),
-                ("reprobe_bits", ctypes.c_int32), ("count_bits", ctypes.c_int32),
-                ("overflow_l", ctypes.c_int32), ("shard_bits", ctypes.c_int32), ("shard_index", ctypes.c_int32),
-                ("max_reprobes", ctypes.c_uint32),
-                ("slots", ctypes.c_uint64), ("table_bytes", ctypes.c_uint64)]
-
-
-class Stats(ctypes.Structure):
-    _fields_ = [("kmers_added", ctypes.c_uint64), ("insert_failures", ctypes.c_uint64),
-                ("overflow_carries", ctypes.c_uint64), ("overflow_failures", ctypes.c_uint64),
-                ("distinct", ctypes.c_uint64), ("overflow_used", ctypes.c_uint64),
-                ("lock_timeouts", ctypes.c_uint64), ("fallback_inserts", ctypes.c_uint64),
-                ("count_sum", ctypes.c_uint64)]
-
-    def as_dict(self):
-        return {f: int(getattr(self, f)) for f, _ in self._fields_}
-
-
-class FilterRule(ctypes.Structure):
-    """tsx_hip_filter_rule: a record passes iff in_range >= min_in_range and in_range * 10^6 >= fraction_ppm * kmers."""
-    _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("min_in_range", ctypes.c_uint64),
-                ("fraction_ppm", ctypes.c_uint32), ("invert", ctypes.c_int32)]
-
-
-class TrimRule(ctypes.Structure):
-    """tsx_hip_trim_rule: a window is solid when lower <= count <= upper; mode picks the run that is kept."""
-    _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("min_len", ctypes.c_uint64),
-                ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32)]
-
-
-class MedianRule(ctypes.Structure):
-    """tsx_hip_median_rule: a record passes iff lower <= median <= upper; invert writes the failures."""
-    _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("invert", ctypes.c_int32),
-                ("reserved", ctypes.c_int32)]
-
-
-class NormalizeRule(ctypes.Structure):
-    """tsx_hip_normalize_rule: a record is kept iff its median < cutoff; rounds of round_records records."""
-    _fields_ = [("cutoff", ctypes.c_uint64), ("round_records", ctypes.c_uint64), ("reserved", ctypes.c_int32 * 2)]
-
-
-class NormalizeTotals(ctypes.Structure):
-    """tsx_hip_normalize_totals."""
-    _fields_ = [(f, ctypes.c_uint64) for f in ("records", "kept", "kmers_seen", "kmers_added", "rounds")]
-
-    def as_dict(self):
-        return {f: int(getattr(self, f)) for f, _ in self._fields_}
-
-
-NORMALIZE_ROUND = 65536   # TSX_HIP_NORMALIZE_ROUND: part of the result's definition
-
-
-class TrimTotals(ctypes.Structure):
-    """tsx_hip_trim_totals."""
-    _fields_ = [("records", ctypes.c_uint64), ("kept", ctypes.c_uint64), ("bases_in", ctypes.c_uint64),
-                ("bases_kept", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
-
-    def as_dict(self):
-        return {f: int(getattr(self, f)) for f, _ in self._fields_}
-
-
-class PairIO(ctypes.Structure):
-    """tsx_hip_pair_io: the four outputs of a pair call (-1 = none)."""
-    _fields_ = [("fd1", ctypes.c_int), ("fd2", ctypes.c_int), ("fd_single1", ctypes.c_int), ("fd_single2", ctypes.c_int)]
-
-
-class PairTotals(ctypes.Structure):
-    """tsx_hip_pair_totals."""
-    _fields_ = [(f, ctypes.c_uint64) for f in ("pairs", "kept", "single1", "single2", "bytes1", "bytes2", "bytes_single1",
-                                               "bytes_single2", "bases_in", "bases_kept")]
-
-    def as_dict(self):
-        return {f: int(getattr(self, f)) for f, _ in self._fields_}
-
-
-class SketchTotals(ctypes.Structure):
-    """tsx_hip_sketch_totals: what a sketch call saw."""
-    _fields_ = [("kmers", ctypes.c_uint64), ("records", ctypes.c_uint64)]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_}
-
-
-class PrefilterTotals(ctypes.Structure):
-    """tsx_hip_prefilter_totals: the size of a map's prefilter, what its two passes saw, its fill."""
-    _fields_ = [(n, ctypes.c_uint64) for n in ("bits", "seen", "seen_again", "admitted", "skipped", "set_bits_a", "set_bits_b")]
-
-    def as_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_}
-
-
-class Level1Shape(ctypes.Structure):
-    """tsx_hip_level1_shape: the level-1 sub-lists the last plain partitioned count of a map left."""
-    _fields_ = [("nb", ctypes.c_uint32), ("G", ctypes.c_uint32), ("cpr2", ctypes.c_uint32), ("wg_major", ctypes.c_int),
-                ("cap", ctypes.c_uint64)]
-
-
-class DbInfo(ctypes.Structure):
-    """tsx_hip_db_info: the header of a k-mer database file."""
-    _fields_ = [("version", ctypes.c_uint32), ("k", ctypes.c_int32), ("l", ctypes.c_int32),
-                ("entry_limbs", ctypes.c_int32), ("func_bits", ctypes.c_int32), ("reprobe_bits", ctypes.c_int32),
-                ("count_bits", ctypes.c_int32), ("seg_bits", ctypes.c_int32), ("overflow_l", ctypes.c_int32),
-                ("canonical", ctypes.c_int32), ("acgt_only", ctypes.c_int32), ("min_qual_char", ctypes.c_int32),
-                ("hash_seed", ctypes.c_uint64), ("kmers_added", ctypes.c_uint64), ("distinct", ctypes.c_uint64),
-                ("count_sum", ctypes.c_uint64), ("carry_records", ctypes.c_uint64)]
-
-    def as_dict(self):
-        return {f: int(getattr(self, f)) for f, _ in self._fields_}
-
-
-class CombineRule(ctypes.Structure):
-    """tsx_hip_combine_rule: the op, the count mode and the count range of each input."""
-    _fields_ = [("op", ctypes.c_int32), ("count_mode", ctypes.c_int32), ("a_lower", ctypes.c_uint64),
-                ("a_upper", ctypes.c_uint64), ("b_lower", ctypes.c_uint64), ("b_upper", ctypes.c_uint64)]
-
-
-class CombineStats(ctypes.Structure):
-    """tsx_hip_combine_stats."""
-    _fields_ = [("a_in_range", ctypes.c_uint64), ("b_in_range", ctypes.c_uint64), ("both", ctypes.c_uint64),
-                ("a_sum_both", ctypes.c_uint64), ("b_sum_both", ctypes.c_uint64), ("out_entries", ctypes.c_uint64),
-                ("out_count_sum", ctypes.c_uint64)]
-
-    def as_dict(self):
-        return {f: int(getattr(self, f)) for f, _ in self._fields_}
-
-
-COMBINE_OPS = {"intersect": 0, "union": 1, "subtract": 2, "diff": 3}
-COMBINE_COUNTS = {"min": 0, "max": 1, "sum": 2, "left": 3, "right": 4}
-
-READ_STATS_DTYPE = np.dtype([("kmers", np.uint64), ("in_range", np.uint64), ("min_count", np.uint64), ("sum_count", np.uint64)])
-
-
-def filter_rule(lower=2, upper=None, min_in_range=0, fraction=1.0, invert=False):
-    """A FilterRule from the Python arguments (fraction: share of a record's k-mers that must be in range, 0..1)."""
-    return FilterRule(int(lower), (1 << 64) - 1 if upper is None else int(upper), int(min_in_range),
-                      int(round(float(fraction) * 1e6)), 1 if invert else 0)
-
-
-TRIM_MODES = {"longest": 0, "prefix": 1}
-TRIM_SPAN_DTYPE = np.dtype([("start", np.uint64), ("length", np.uint64)])
-
-
-def trim_rule(lower=2, upper=None, mode="longest", min_len=0):
-    """A TrimRule from the Python arguments (mode by name, TRIM_MODES).  Raises ValueError for an unknown mode and for
-    lower > upper, before any GPU call."""
-    if mode not in TRIM_MODES:
-        raise ValueError("trim mode must be one of %s, not %r" % (sorted(TRIM_MODES), mode))
-    upper = (1 << 64) - 1 if upper is None else int(upper)
-    if int(lower) > upper:
-        raise ValueError("trim range: lower %d > upper %d" % (int(lower), upper))
-    return TrimRule(int(lower), upper, int(min_len), TRIM_MODES[mode], 0)
-
-
-NO_KMER = 0xFFFFFFFF          # TSX_HIP_NO_KMER: the profile entry of a position where no k-mer starts
-READ_MEDIAN_DTYPE = np.dtype([("kmers", np.uint64), ("median", np.uint64)])
-
-
-def median_count(values):
-    """The median as medianReads reports it, on the CPU: element m // 2 of the m sorted values (the upper middle for
-    even m, khmer's convention), 0 without values.  Profile entries equal to NO_KMER are no values."""
-    v = sorted(int(x) for x in values if int(x) != NO_KMER)
-    return v[len(v) // 2] if v else 0
-
-
-def median_rule(lower=0, upper=None, invert=False):
-    """A MedianRule from the Python arguments.  Raises ValueError for lower > upper, before any GPU call."""
-    upper = (1 << 64) - 1 if upper is None else int(upper)
-    if int(lower) > upper:
-        raise ValueError("median range: lower %d > upper %d" % (int(lower), upper))
-    return MedianRule(int(lower), upper, 1 if invert else 0, 0)
-
-
-def normalize_rule(cutoff=20, round_records=NORMALIZE_ROUND):
-    """A NormalizeRule from the Python arguments.  Raises ValueError for round_records < 1, before any GPU call."""
-    if int(round_records) < 1:
-        raise ValueError("normalize: round_records %d < 1" % int(round_records))
-    if int(cutoff) < 0:
-        raise ValueError("normalize: cutoff %d < 0" % int(cutoff))
-    return NormalizeRule(min(int(cutoff), (1 << 64) - 1), int(round_records), (ctypes.c_int32 * 2)(0, 0))
-
-
-SKETCH_PRECISIONS = range(10, 15)   # the p of a sketch: 2^p registers
-
-
-def _mix64(z):
-    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return z ^ (z >> np.uint64(31))
-
-
-def sketch_registers(kmers, k, precision=14):
-    """The HyperLogLog registers of a set of k-mers, on the CPU with numpy alone (the definition the GPU sketch is tested
-    against): numpy uint8[2^precision].  kmers: encoded limbs, (n, key_limbs(k)) or flat, taken as given (canonicalise
-    first for a canonical map).  Per k-mer x: v = 0x9E3779B97F4A7C15, then v = mix64(v ^ limb) limb by limb (splitmix64's
-    finaliser); the register v >> (64 - p) is raised to 1 + the number of leading zeros of the remaining 64 - p bits (all
-    zero: 64 - p + 1)."""
-    p = int(precision)
-    if p not in SKETCH_PRECISIONS:
-        raise ValueError("sketch precision must be 10 .. 14, not %r" % (precision,))
-    wk = key_limbs(k)
-    a = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1, wk).copy()
-    if (2 * k) % 64:
-        a[:, wk - 1] &= np.uint64((1 << ((2 * k) % 64)) - 1)
-    regs = np.zeros(1 << p, dtype=np.uint8)
-    if not len(a):
-        return regs
-    with np.errstate(over="ignore"):
-        v = np.full(len(a), 0x9E3779B97F4A7C15, dtype=np.uint64)
-        for t in range(wk):
-            v = _mix64(v ^ a[:, t])
-    idx = (v >> np.uint64(64 - p)).astype(np.int64)
-    rest = v & np.uint64((1 << (64 - p)) - 1)
-    # leading zeros among 64 - p bits = (64 - p) - bit length; the bit length by halving (exact, no floating point)
-    length = np.zeros(len(a), dtype=np.int64)
-    for s in (32, 16, 8, 4, 2, 1):
-        big = (rest >> np.uint64(s)) != 0
-        length += np.where(big, s, 0)
-        rest = np.where(big, rest >> np.uint64(s), rest)
-    length += (rest != 0).astype(np.int64)
-    rank = (64 - p) - length + 1
-    np.maximum.at(regs, idx, rank.astype(np.uint8))
-    return regs
-
-
-def _sketch_precision(registers):
-    n = len(registers)
-    p = n.bit_length() - 1
-    if n != 1 << p or p not in SKETCH_PRECISIONS:
-        raise ValueError("a sketch has 2^10 .. 2^14 registers, not %d" % n)
-    return p
-
-
-def sketch_estimate(registers):
-    """The number of distinct k-mers a sketch stands for (tsx_hip_sketch_estimate_host): a float, 0.0 for an empty sketch."""
-    r = np.ascontiguousarray(registers, dtype=np.uint8)
-    L = lib()
-    e = L.tsx_hip_sketch_estimate_host(r.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _sketch_precision(r))
-    if e < 0:
-        raise TSXException(EINVAL, "a register above its highest rank")
-    return float(e)
-
-
-def suggest_l(distinct, k, load=0.75, precision=14):
-    """The l (log2 of the slot count) of the smallest table that holds `distinct` k-mers at `load` with a margin of five
-    standard errors of a sketch of 2^precision registers (tsx_hip_suggest_l): at least 4, at most min(36, 2k - 1).
-    Where that bound leaves the load above 0.9: TSXException ERANGE, its .l the bound."""
-    l = ctypes.c_int(0)
-    rc = lib().tsx_hip_suggest_l(int(k), float(distinct), int(precision), int(round(float(load) * 1e6)), ctypes.byref(l))
-    if rc == ERANGE:
-        e = TSXException(rc, "l cannot exceed %d for k=%d: %.0f distinct k-mers load it above 0.9" % (l.value, k, distinct))
-        e.l = int(l.value)
-        raise e
-    _check(rc)
-    return int(l.value)
-
-
-def merge_sketches(a, b):
-    """The sketch of the union of what two sketches of one precision saw: the register-wise maximum."""
-    a, b = np.asarray(a, dtype=np.uint8), np.asarray(b, dtype=np.uint8)
-    if a.shape != b.shape:
-        raise ValueError("sketches of different precision")
-    return np.maximum(a, b)
-
-
-PREFILTER_BITS = range(12, 39)    # a prefilter's size: filter A has 2^bits bits, filter B 2^(bits - 2)
-
-
-def prefilter_masks(kmers, k, bits):
-    """Where a set of k-mers sits in a prefilter of 2^bits bits, on the CPU with numpy alone (the definition the GPU
-    filter is tested against): (word_a, word_b, mask), three numpy uint64 arrays.  kmers: encoded limbs, (n, key_limbs(k))
-    or flat, taken as given (canonicalise first for a canonical map).  Per k-mer: v = the hash of sketch_registers; the
-    64-bit word of filter A is v >> (64 - (bits - 6)), that of filter B v >> (64 - (bits - 8)); the mask, the same in
-    both, is the OR of 1 << ((v >> s) & 63) for s = 0, 6, 12, 18.  In a filter: word & mask == mask."""
-    b = int(bits)
-    if b not in PREFILTER_BITS:
-        raise ValueError("prefilter bits must be 12 .. 38, not %r" % (bits,))
-    wk = key_limbs(k)
-    a = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1, wk).copy()
-    if (2 * k) % 64:
-        a[:, wk - 1] &= np.uint64((1 << ((2 * k) % 64)) - 1)
-    with np.errstate(over="ignore"):
-        v = np.full(len(a), 0x9E3779B97F4A7C15, dtype=np.uint64)
-        for t in range(wk):
-            v = _mix64(v ^ a[:, t])
-    mask = np.zeros(len(a), dtype=np.uint64)
-    for s in (0, 6, 12, 18):
-        mask |= np.uint64(1) << ((v >> np.uint64(s)) & np.uint64(63))
-    return v >> np.uint64(64 - (b - 6)), v >> np.uint64(64 - (b - 8)), mask
-
-
-PAIR_MODES = {"both": 0, "any": 1}
-
-
-def pair_name(header_line):
-    """The name of a record as the pair calls compare it (check_names): the header line after its first byte ('@' or
-    '>') up to the first space or tab, or the line's end, without one trailing "/1" or "/2"."""
-    line = bytes(header_line.encode() if isinstance(header_line, str) else header_line).split(b"\n")[0]
-    name = line[1:]
-    for i, c in enumerate(name):
-        if c in b" \t":
-            name = name[:i]
-            break
-    if name.endswith((b"/1", b"/2")):
-        name = name[:-2]
-    return name
-
-
-def combine_rule(op="intersect", counts="min", a_range=(1, None), b_range=(1, None)):
-    """A CombineRule from the Python arguments: op and counts by name (COMBINE_OPS, COMBINE_COUNTS) or number, each
-    range as (lower, upper) with None = no upper bound."""
-    top = (1 << 64) - 1
-    return CombineRule(int(COMBINE_OPS.get(op, op)), int(COMBINE_COUNTS.get(counts, counts)),
-                       int(a_range[0]), top if a_range[1] is None else int(a_range[1]),
-                       int(b_range[0]), top if b_range[1] is None else int(b_range[1]))
-
-
-JOINT_MAX_CELLS = 1 << 24   # cells of a joint histogram (tsx_hip_joint_histogram_*)
-
-
-def joint_histogram(A, B, bins_a=1002, bins_b=1002):
-    """The definition of TSXHashMapHIP.jointHistogram on the CPU: A and B map k-mer -> count (any hashable key; a count
-    of 0 is an absent k-mer).  Returns numpy uint64[bins_a, bins_b]: [i, j] = the k-mers x of A u B with
-    min(A[x], bins_a - 1) == i and min(B[x], bins_b - 1) == j."""
-    if bins_a < 2 or bins_b < 2 or bins_a * bins_b > JOINT_MAX_CELLS:
-        raise ValueError("joint_histogram: 2 <= bins and bins_a * bins_b <= 2^24")
-    keys = list(set(A) | set(B))
-    m = np.zeros((bins_a, bins_b), dtype=np.uint64)
-    if keys:
-        a = np.minimum(np.array([int(A.get(x, 0)) for x in keys], dtype=np.uint64), np.uint64(bins_a - 1)).astype(np.int64)
-        b = np.minimum(np.array([int(B.get(x, 0)) for x in keys], dtype=np.uint64), np.uint64(bins_b - 1)).astype(np.int64)
-        np.add.at(m, (a, b), np.uint64(1))
-        m[0, 0] = 0   # in neither: not a k-mer of A u B
-    return m
-
-
-class HetRule(ctypes.Structure):
-    """tsx_hip_het_rule"""
-    _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("mode", ctypes.c_int32), ("reserved", ctypes.c_int32)]
-
-
-class HetStats(ctypes.Structure):
-    """tsx_hip_het_stats"""
-    _fields_ = [(n, ctypes.c_uint64) for n in ("kmers_in_range", "paired", "pairs", "families_2", "families_3plus")]
-
-
-HET_MODES = {"unique": 0, "all": 1}
-
-
-def het_pair_dtype(k):
-    """A record of the pair list of a table of k-mers (tsx_hip_het_pairs_device): k-mers as key_limbs(k) limbs."""
-    w = (2 * k + 63) // 64
-    return np.dtype([("minor", np.uint64, (w,)), ("major", np.uint64, (w,)), ("minor_count", np.uint64), ("major_count", np.uint64)])
-
-
-HET_PAIR_DTYPE = het_pair_dtype(31)   # one-limb keys (k <= 32); het_pair_dtype(k) for any k
-
-
-def het_rule(lower=1, upper=None, mode="unique"):
-    if mode not in HET_MODES:
-        raise ValueError("het pairs: mode is 'unique' or 'all', got %r" % (mode,))
-    return HetRule(int(lower), (1 << 64) - 1 if upper is None else int(upper), HET_MODES[mode], 0)
-
-
-def het_pairs(D, k, lower=1, upper=None, mode="unique", canonical=False):
-    """The definition of TSXHashMapHIP.hetPairs / hetHistogram on the CPU (Smudgeplot's hetkmers).  D maps k-mer string ->
-    count, as a dump reports it (canonical: the smaller strand); k is odd.  A k-mer counted outside [lower, upper] is absent.
-    The family of x is x and those of its three middle-base variants (canonical: each taken to its smaller strand) that D
-    holds in range.  A pair is two members of one family: mode 'unique' counts the pair of a family of exactly two, 'all'
-    every pair of every family.  Returns (pairs, stats): pairs a list of (minor k-mer, its count, major k-mer, its count),
-    minor being the lower count and on a tie the smaller string, each pair once, sorted; stats the dict of
-    kmers_in_range, paired, pairs, families_2, families_3plus (families of exactly 2 / of 3 or 4, each counted once)."""
-    if k % 2 == 0:
-        raise ValueError("het_pairs: k must be odd (an even k has no middle base)")
-    if mode not in HET_MODES:
-        raise ValueError("het_pairs: mode is 'unique' or 'all', got %r" % (mode,))
-    top = (1 << 64) - 1 if upper is None else int(upper)
-    low = max(int(lower), 1)
-    canon = (lambda x: min(x, revcomp(x))) if canonical else (lambda x: x)   # (what canonical() gives for a string)
-    R = {}
-    for x, c in D.items():
-        x = x.decode() if isinstance(x, bytes) else x   # (k-mers come back as str)
-        if len(x) != k:
-            raise ValueError("het_pairs: %r is no %d-mer" % (x, k))
-        if low <= int(c) <= top:
-            R[canon(x)] = int(c)
-    p = (k - 1) // 2
-    families = set()
-    for x in R:
-        fam = {x}
-        for b in "ACGT":
-            y = canon(x[:p] + b + x[p + 1:])
-            if y in R:
-                fam.add(y)
-        families.add(tuple(sorted(fam)))
-    pairs, paired = [], set()
-    for fam in families:
-        if len(fam) < 2 or (mode == "unique" and len(fam) != 2):
-            continue
-        for i in range(len(fam)):
-            for j in range(i + 1, len(fam)):
-                a, b = sorted((fam[i], fam[j]), key=lambda x: (R[x], x))
-                pairs.append((a, R[a], b, R[b]))
-        paired.update(fam)
-    stats = {"kmers_in_range": len(R), "paired": len(paired), "pairs": len(pairs),
-             "families_2": sum(1 for f in families if len(f) == 2), "families_3plus": sum(1 for f in families if len(f) > 2)}
-    return sorted(pairs), stats
-
-
-def het_histogram(pairs, bins_minor=1002, bins_major=1002):
-    """The matrix of TSXHashMapHIP.hetHistogram from het_pairs' list: numpy uint64[bins_minor, bins_major], [i, j] = the
-    pairs with min(minor count, bins_minor - 1) == i and min(major count, bins_major - 1) == j."""
-    if bins_minor < 2 or bins_major < 2 or bins_minor * bins_major > JOINT_MAX_CELLS:
-        raise ValueError("het_histogram: 2 <= bins and bins_minor * bins_major <= 2^24")
-    m = np.zeros((bins_minor, bins_major), dtype=np.uint64)
-    for _, cmin, _, cmax in pairs:
-        m[min(int(cmin), bins_minor - 1), min(int(cmax), bins_major - 1)] += np.uint64(1)
-    return m
-
-
-class BinRule(ctypes.Structure):
-    """tsx_hip_bin_rule."""
-    _fields_ = [("a_lower", ctypes.c_uint64), ("a_upper", ctypes.c_uint64), ("b_lower", ctypes.c_uint64),
-                ("b_upper", ctypes.c_uint64), ("min_hits", ctypes.c_uint64), ("ratio_milli", ctypes.c_uint32),
-                ("reserved", ctypes.c_int32)]
-
-
-class BinIO(ctypes.Structure):
-    """tsx_hip_bin_io: one file descriptor per class, -1 = counted and not written."""
-    _fields_ = [("fd_a", ctypes.c_int), ("fd_b", ctypes.c_int), ("fd_ambiguous", ctypes.c_int), ("fd_none", ctypes.c_int)]
-
-
-class BinTotals(ctypes.Structure):
-    """tsx_hip_bin_totals."""
-    _fields_ = [("records", ctypes.c_uint64), ("n", ctypes.c_uint64 * 4), ("bytes", ctypes.c_uint64 * 4)]
-
-    def as_dict(self):
-        return {"records": int(self.records), "n": [int(v) for v in self.n], "bytes": [int(v) for v in self.bytes]}
-
-
-BIN_A, BIN_B, BIN_AMBIGUOUS, BIN_NONE = 0, 1, 2, 3   # TSX_HIP_BIN_*: the class of a record
-BIN_NAMES = ("a", "b", "ambiguous", "none")
-BIN_STATS_DTYPE = np.dtype([("kmers", np.uint64), ("hits_a", np.uint64), ("hits_b", np.uint64), ("hits_both", np.uint64)])
-
-
-def bin_class(hits_a, hits_b, min_hits=1, ratio_milli=1000):
-    """The class rule of the bin calls on the CPU (plain integers): a side qualifies with hits >= min_hits and wins when
-    it qualifies, has more hits than the other and hits * 1000 >= ratio_milli * the other's; no side qualifies: BIN_NONE;
-    nobody wins: BIN_AMBIGUOUS."""
-    ha, hb, mh, rm = int(hits_a), int(hits_b), int(min_hits), int(ratio_milli)
-    if not 1000 <= rm <= 1000000:
-        raise ValueError("bin_class: 1000 <= ratio_milli <= 1000000")
-    qa, qb = ha >= mh, hb >= mh
-    if qa and ha > hb and ha * 1000 >= rm * hb:
-        return BIN_A
-    if qb and hb > ha and hb * 1000 >= rm * ha:
-        return BIN_B
-    return BIN_AMBIGUOUS if (qa or qb) else BIN_NONE
-
-
-def bin_rule(a_range=(1, None), b_range=(1, None), min_hits=1, ratio=1.0):
-    """A BinRule from the Python arguments: each range as (lower, upper) with None = no upper bound, the ratio as a
-    number >= 1 (three decimal places kept)."""
-    top = (1 << 64) - 1
-    return BinRule(int(a_range[0]), top if a_range[1] is None else int(a_range[1]),
-                   int(b_range[0]), top if b_range[1] is None else int(b_range[1]),
-                   int(min_hits), min(max(int(round(float(ratio) * 1000)), 0), (1 << 32) - 1), 0)
-
-
-def build():
-    """Compile the library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    import subprocess
-    subprocess.check_call(["make", "-C", os.path.join(_HERE, "csrc"), "all"], stdout=subprocess.DEVNULL)
-
-
-_lib = None
-
-
-def lib():
-    """Load libtsxcount_hip.so; raises if it has not been built (no fallback)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError("tsxcount_amd: %s is missing; run tsxcount_amd.build() "
-                          "(hipcc --offload-arch=gfx950). There is no CPU fallback." % LIB_PATH)
-    L = ctypes.CDLL(LIB_PATH)
-    vp, u64, sz, ci = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int
-    u64p = ctypes.POINTER(ctypes.c_uint64)
-    L.tsx_hip_strerror.restype = ctypes.c_char_p
-    L.tsx_hip_strerror.argtypes = [ci]
-    L.tsx_hip_last_error.restype = ctypes.c_char_p
-    L.tsx_hip_key_limbs.argtypes = [ci]
-    L.tsx_hip_encode.argtypes = [ctypes.c_char_p, ci, u64p]
-    L.tsx_hip_decode.argtypes = [u64p, ci, ctypes.c_char_p]
-    L.tsx_hip_create.argtypes = [ctypes.POINTER(vp), ci, ci, ci, ci, u64, ci]
-    L.tsx_hip_create_shard.argtypes = [ctypes.POINTER(vp), ci, ci, ci, ci, u64, ci, ci, ci]
-    L.tsx_hip_shard_send_capacity.argtypes = [vp, sz, ctypes.POINTER(sz)]
-    L.tsx_hip_shard_scan_device.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp]
-    L.tsx_hip_shard_scan_window_device.argtypes = [vp, vp, sz, sz, sz, vp, sz, vp, sz, vp, vp, vp, sz, vp, vp, vp]
-    L.tsx_hip_shard_build_device.argtypes = [vp, vp, sz, vp, vp]
-    L.tsx_hip_shard_build_pieces_device.argtypes = [vp, vp, u64p, u64p, sz, vp, vp]
-    L.tsx_hip_add_hashed_device.argtypes = [vp, vp, vp, sz, vp]
-    L.tsx_hip_bgzf_index_host.argtypes = [vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
-    L.tsx_hip_inflate_bgzf_host.argtypes = [ctypes.c_int, vp, sz, vp, sz, ctypes.POINTER(sz)]
-    L.tsx_hip_count_fastq_bgzf_host.argtypes = [vp, vp, sz]
-    L.tsx_hip_shard_l1_supported.argtypes = [vp]
-    L.tsx_hip_shard_l1_window_device.argtypes = [vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp]
-    L.tsx_hip_shard_build_l1_device.argtypes = [vp, vp]
-    L.tsx_hip_shard_desc_capacity.argtypes = [vp, sz, ctypes.c_int, ctypes.POINTER(sz)]
-    L.tsx_hip_shard_desc_window_device.argtypes = [vp, vp, sz, sz, sz, ctypes.c_int, vp, sz, vp, vp, vp]
-    L.tsx_hip_shard_walk_device.argtypes = [vp, vp, sz, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp]
-    L.tsx_hip_shard_filter_device.argtypes = [vp, vp, sz, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp]
-    L.tsx_hip_mini_supported.argtypes = [vp]
-    L.tsx_hip_mini_capacity.argtypes = [vp, sz, ctypes.c_int, ctypes.POINTER(sz)]
-    L.tsx_hip_mini_window_device.argtypes = [vp, vp, sz, sz, sz, ctypes.c_int, vp, sz, vp, vp, vp]
-    L.tsx_hip_mini_part_capacity.argtypes = [vp, sz, ctypes.c_uint32, ctypes.POINTER(sz)]
-    L.tsx_hip_mini_describe_device.argtypes = [vp, vp, sz, sz, sz, vp, vp]
-    L.tsx_hip_mini_split_device.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, vp, sz, vp, vp]
-    L.tsx_hip_mini_owner_host.argtypes = [ci, ci, u64p, sz, ctypes.POINTER(ctypes.c_uint32)]
-    L.tsx_hip_destroy.argtypes = [vp]
-    L.tsx_hip_destroy.restype = None
-    L.tsx_hip_get_layout.argtypes = [vp, ctypes.POINTER(Layout)]
-    L.tsx_hip_clear.argtypes = [vp]
-    L.tsx_hip_set_canonical.argtypes = [vp, ci]
-    L.tsx_hip_canonical.argtypes = [vp]
-    L.tsx_hip_canonical_host.argtypes = [ci, u64p, sz, u64p]
-    L.tsx_hip_group_set_canonical.argtypes = [vp, ci]
-    L.tsx_hip_set_base_rule.argtypes = [vp, ci, ci]
-    L.tsx_hip_get_base_rule.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
-    L.tsx_hip_group_set_base_rule.argtypes = [vp, ci, ci]
-    L.tsx_hip_sync.argtypes = [vp]
-    L.tsx_hip_count_fastq_host.argtypes = [vp, ctypes.c_char_p, sz]
-    L.tsx_hip_count_fastq_device.argtypes = [vp, vp, sz, vp]
-    L.tsx_hip_count_fasta_host.argtypes = [vp, ctypes.c_char_p, sz]
-    L.tsx_hip_count_fasta_device.argtypes = [vp, vp, sz, vp]
-    L.tsx_hip_count_fasta_bgzf_host.argtypes = [vp, vp, sz]
-    L.tsx_hip_unwrap_fasta_host.argtypes = [ci, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz)]
-    L.tsx_hip_add_kmers_host.argtypes = [vp, u64p, u64p, sz]
-    L.tsx_hip_add_kmers_device.argtypes = [vp, vp, vp, sz, vp]
-    L.tsx_hip_get_counts_host.argtypes = [vp, u64p, sz, u64p]
-    L.tsx_hip_get_counts_device.argtypes = [vp, vp, sz, vp, vp]
-    L.tsx_hip_lookup_host.argtypes = [vp, u64p, sz, u64p, u64p]
-    L.tsx_hip_kmer_starts_host.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), sz]
-    L.tsx_hip_get_stats.argtypes = [vp, ctypes.POINTER(Stats)]
-    L.tsx_hip_dump_host.argtypes = [vp, u64p, u64p, sz, ctypes.POINTER(sz)]
-    L.tsx_hip_dump_device.argtypes = [vp, vp, vp, sz, vp, vp]
-    L.tsx_hip_partition_device.argtypes = [vp, ci, vp, vp, sz, vp, vp]
-    L.tsx_hip_dump_range_device.argtypes = [vp, u64, u64, vp, vp, sz, vp, vp]
-    L.tsx_hip_owner_host.argtypes = [vp, u64p, ci]
-    L.tsx_hip_histogram_device.argtypes = [vp, u64, u64, sz, vp, vp]
-    L.tsx_hip_histogram_host.argtypes = [vp, u64p, sz]
-    L.tsx_hip_format_counts_device.argtypes = [vp, u64, u64, u64, u64, vp, sz, vp, vp, vp]
-    L.tsx_hip_write_counts_host.argtypes = [vp, ci, u64, u64, sz, u64p, u64p]
-    L.tsx_hip_db_read_info.argtypes = [ci, ctypes.POINTER(DbInfo)]
-    L.tsx_hip_save_host.argtypes = [vp, ci, sz, u64p, u64p]
-    L.tsx_hip_load_host.argtypes = [vp, ci, sz, u64p]
-    L.tsx_hip_combine.argtypes = [vp, vp, vp, ctypes.POINTER(CombineRule), ctypes.POINTER(CombineStats)]
-    L.tsx_hip_joint_histogram_device.argtypes = [vp, vp, sz, sz, vp, vp]
-    L.tsx_hip_joint_histogram_host.argtypes = [vp, vp, u64p, sz, sz]
-    L.tsx_hip_het_histogram_device.argtypes = [vp, ctypes.POINTER(HetRule), sz, sz, vp, vp, vp]
-    L.tsx_hip_het_histogram_host.argtypes = [vp, ctypes.POINTER(HetRule), u64p, sz, sz, ctypes.POINTER(HetStats)]
-    L.tsx_hip_het_pairs_device.argtypes = [vp, ctypes.POINTER(HetRule), u64, u64, vp, sz, vp, vp]
-    L.tsx_hip_write_het_pairs_host.argtypes = [vp, ctypes.POINTER(HetRule), ci, sz, u64p, u64p]
-    L.tsx_hip_bin_stats_device.argtypes = [vp, vp, vp, sz, ctypes.POINTER(BinRule), vp, sz, ctypes.POINTER(sz), vp]
-    L.tsx_hip_bin_stats_host.argtypes = [vp, vp, ctypes.c_char_p, sz, ctypes.POINTER(BinRule), vp, vp, sz, ctypes.POINTER(sz), sz]
-    L.tsx_hip_bin_reads_host.argtypes = [vp, vp, ctypes.c_char_p, sz, ctypes.POINTER(BinRule), ctypes.POINTER(BinIO), sz,
-                                         ctypes.POINTER(BinTotals)]
-    L.tsx_hip_group_histogram_host.argtypes = [vp, u64p, sz]
-    L.tsx_hip_group_write_counts_host.argtypes = [vp, ci, u64, u64, sz, u64p, u64p]
-    L.tsx_hip_query_reads_device.argtypes = [vp, vp, sz, u64, u64, vp, sz, ctypes.POINTER(sz), vp]
-    L.tsx_hip_query_reads_host.argtypes = [vp, ctypes.c_char_p, sz, u64, u64, vp, sz, ctypes.POINTER(sz), sz]
-    L.tsx_hip_filter_reads_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(FilterRule), ci, sz, u64p, u64p]
-    L.tsx_hip_filter_reads_device.argtypes = [vp, vp, sz, ctypes.POINTER(FilterRule), vp, sz, ctypes.POINTER(sz), u64p, vp]
-    L.tsx_hip_trim_spans_device.argtypes = [vp, vp, sz, ctypes.POINTER(TrimRule), vp, sz, ctypes.POINTER(sz), vp]
-    L.tsx_hip_trim_spans_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), vp, sz, ctypes.POINTER(sz), sz]
-    L.tsx_hip_trim_reads_device.argtypes = [vp, vp, sz, ctypes.POINTER(TrimRule), vp, sz, ctypes.POINTER(TrimTotals), vp]
-    L.tsx_hip_trim_reads_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), ci, sz, ctypes.POINTER(TrimTotals)]
-    L.tsx_hip_count_profile_device.argtypes = [vp, vp, sz, vp, vp]
-    L.tsx_hip_count_profile_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz]
-    L.tsx_hip_median_reads_device.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(sz), vp]
-    L.tsx_hip_median_reads_host.argtypes = [vp, ctypes.c_char_p, sz, vp, sz, ctypes.POINTER(sz), sz]
-    L.tsx_hip_filter_median_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(MedianRule), ci, sz, u64p, u64p]
-    L.tsx_hip_normalize_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(NormalizeRule), ci, vp, sz, sz,
-                                         ctypes.POINTER(NormalizeTotals)]
-    L.tsx_hip_normalize_device.argtypes = [vp, vp, sz, ctypes.POINTER(NormalizeRule), vp, sz,
-                                           ctypes.POINTER(NormalizeTotals), vp]
-    u8p = ctypes.POINTER(ctypes.c_uint8)
-    L.tsx_hip_sketch_host.argtypes = [vp, ctypes.c_char_p, sz, ci, u8p, ctypes.POINTER(SketchTotals), sz]
-    L.tsx_hip_sketch_bgzf_host.argtypes = [vp, vp, sz, ci, u8p, ctypes.POINTER(SketchTotals)]
-    L.tsx_hip_sketch_device.argtypes = [vp, vp, sz, ci, vp, vp, vp]
-    L.tsx_hip_sketch_kmers_host.argtypes = [ci, u64p, sz, ci, u8p]
-    L.tsx_hip_sketch_estimate_host.argtypes = [u8p, ci]
-    L.tsx_hip_sketch_estimate_host.restype = ctypes.c_double
-    L.tsx_hip_suggest_l.argtypes = [ci, ctypes.c_double, ci, ctypes.c_uint32, ctypes.POINTER(ci)]
-    L.tsx_hip_prefilter_create.argtypes = [vp, ci]
-    L.tsx_hip_prefilter_free.argtypes = [vp]
-    L.tsx_hip_prefilter_add_host.argtypes = [vp, ctypes.c_char_p, sz, sz]
-    L.tsx_hip_prefilter_add_bgzf_host.argtypes = [vp, vp, sz]
-    L.tsx_hip_prefilter_add_device.argtypes = [vp, vp, sz, vp]
-    L.tsx_hip_prefilter_arm.argtypes = [vp, ci]
-    L.tsx_hip_prefilter_armed.argtypes = [vp]
-    L.tsx_hip_prefilter_bits.argtypes = [vp]
-    L.tsx_hip_prefilter_stats.argtypes = [vp, ctypes.POINTER(PrefilterTotals)]
-    L.tsx_hip_prefilter_read.argtypes = [vp, ci, u64p, sz]
-    L.tsx_hip_prefilter_mask_host.argtypes = [ci, u64p, ci, u64p, u64p, u64p]
-    L.tsx_hip_filter_pairs_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(FilterRule), ci, ci,
-                                            ctypes.POINTER(PairIO), sz, ctypes.POINTER(PairTotals)]
-    L.tsx_hip_trim_pairs_host.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.POINTER(TrimRule), ci,
-                                          ctypes.POINTER(PairIO), sz, ctypes.POINTER(PairTotals)]
-    L.tsx_hip_hash_apply.argtypes = [vp, u64p, u64p]
-    L.tsx_hip_hash_invert.argtypes = [vp, u64p, u64p]
-    L.tsx_hip_hash_rows.argtypes = [vp, u64p]
-    L.tsx_hip_lut4_host.argtypes = [ci, ci, ctypes.c_uint64, u64p]
-    L.tsx_hip_sublist_first.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ci, ctypes.c_uint32, ctypes.c_uint32, u64]
-    L.tsx_hip_sublist_first.restype = u64
-    L.tsx_hip_level1_sizes_host.argtypes = [vp, ctypes.POINTER(Level1Shape), u64p, sz]
-    L.tsx_hip_set_timing.argtypes = [vp, ci]
-    L.tsx_hip_get_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                                     ctypes.POINTER(ctypes.c_double), u64p]
-    L.tsx_hip_get_stage_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_double), u64p]
-    L.tsx_hip_set_path.argtypes = [vp, ci]
-    L.tsx_hip_set_record_lines.argtypes = [vp, ci]
-    L.tsx_hip_synth_fastq_device.argtypes = [u64, u64, u64, ci, vp, sz, u64p, u64p, u64p, ci, vp]
-    L.tsx_hip_synth_zipf_device.argtypes = [u64, u64, ctypes.c_uint32, ctypes.c_uint32, u64p, vp, sz, u64p, ci, vp]
-    L.tsx_hip_group_create.argtypes = [ctypes.POINTER(vp), ci, ctypes.POINTER(ci), ci, ci, ci, ci, u64, ci]
-    L.tsx_hip_group_destroy.argtypes = [vp]
-    L.tsx_hip_group_destroy.restype = None
-    L.tsx_hip_group_size.argtypes = [vp]
-    L.tsx_hip_group_map.argtypes = [vp, ci]
-    L.tsx_hip_group_map.restype = vp
-    L.tsx_hip_group_comm_name.argtypes = [vp]
-    L.tsx_hip_group_comm_name.restype = ctypes.c_char_p
-    L.tsx_hip_group_last_error.restype = ctypes.c_char_p
-    L.tsx_hip_group_set_record_lines.argtypes = [vp, ci]
-    L.tsx_hip_group_clear.argtypes = [vp]
-    L.tsx_hip_group_count_fastq_host.argtypes = [vp, ctypes.c_char_p, sz]
-    L.tsx_hip_group_merge.argtypes = [vp]
-    L.tsx_hip_group_get_counts_host.argtypes = [vp, u64p, sz, u64p]
-    L.tsx_hip_group_get_stats.argtypes = [vp, ctypes.POINTER(Stats)]
-    L.tsx_hip_group_exchanged_entries.argtypes = [vp]
-    L.tsx_hip_group_set_exchange.argtypes = [vp, ci]
-    L.tsx_hip_group_exchange.argtypes = [vp]
-    L.tsx_hip_group_exchanged_entries.restype = u64
-    L.tsx_hip_group_exchange_rounds.argtypes = [vp]
-    L.tsx_hip_group_exchange_rounds.restype = ctypes.c_uint32
-    L.tsx_hip_cut_records_host.argtypes = [ctypes.c_char_p, sz, ci, ci, ctypes.POINTER(sz)]
-    vpp = ctypes.POINTER(vp)
-    L.tsx_hip_seq_stats_host.argtypes = [vp, ctypes.c_char_p, sz, u64, u64, sz, vpp]
-    L.tsx_hip_seq_missing_host.argtypes = [vp, ctypes.c_char_p, sz, u64, u64, sz, vpp]
-    L.tsx_hip_seq_stats_bgzf_host.argtypes = [vp, vp, sz, u64, u64, vpp]
-    L.tsx_hip_seq_missing_bgzf_host.argtypes = [vp, vp, sz, u64, u64, vpp]
-    L.tsx_hip_seq_stats_device.argtypes = [vp, vp, sz, u64, u64, vpp, vp]
-    L.tsx_hip_seq_missing_device.argtypes = [vp, vp, sz, u64, u64, vpp, vp]
-    L.tsx_hip_seq_result_count.argtypes = [vp]
-    L.tsx_hip_seq_result_count.restype = sz
-    L.tsx_hip_seq_result_stats.argtypes = [vp]
-    L.tsx_hip_seq_result_stats.restype = vp
-    L.tsx_hip_seq_result_names.argtypes = [vp, vpp]
-    L.tsx_hip_seq_result_names.restype = vp
-    L.tsx_hip_seq_result_intervals.argtypes = [vp, vpp]
-    L.tsx_hip_seq_result_intervals.restype = sz
-    L.tsx_hip_seq_result_free.argtypes = [vp]
-    L.tsx_hip_seq_result_free.restype = None
-    L.tsx_hip_seq_write_stats.argtypes = [vp, ci, ci]
-    L.tsx_hip_seq_write_missing.argtypes = [vp, ci]
-    _lib = L
-    return L
-
-
-def _check(code):
-    if code != OK:
-        L = lib()
-        msg = L.tsx_hip_strerror(code).decode()
-        if code in (EHIP, ENODEVICE, ENOMEM, EIO, EFORMAT, EPAIR):
-            extra = L.tsx_hip_last_error().decode()
-            if extra:
-                msg += " (" + extra + ")"
-        raise TSXException(code, msg)
-
-
-def _check_bgzf(code):
-    """A refused BGZF image: the library says which member and why (tsx_hip_last_error)."""
-    if code == EINVAL:
-        L = lib()
-        raise TSXException(code, L.tsx_hip_last_error().decode() or L.tsx_hip_strerror(code).decode())
-    _check(code)
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
-
-
-def key_limbs(k):
-    return (2 * k + 63) // 64
-
-
-def encode(seq, k=None):
-    """TSXSeqUtils::fromSequence (SequenceUtils.h:86-160) -> uint64 limbs."""
-    s = seq.encode() if isinstance(seq, str) else bytes(seq)
-    k = len(s) if k is None else k
-    out = np.zeros(key_limbs(k), dtype=np.uint64)
-    _check(lib().tsx_hip_encode(s, k, _p(out)))
-    return out
-
-
-def decode(limbs, k):
-    """TSXSeqUtils::toSequence (SequenceUtils.h:47-84)."""
-    a = np.ascontiguousarray(limbs, dtype=np.uint64)
-    buf = ctypes.create_string_buffer(k + 1)
-    _check(lib().tsx_hip_decode(_p(a), k, buf))
-    return buf.value.decode()
-
-
-_COMP = str.maketrans("ACGT", "TGCA")
-
-
-def revcomp(seq):
-    """Reverse complement of an ACGT string (other bytes: see canonical())."""
-    return seq[::-1].translate(_COMP)
-
-
-def canonical(kmers, k):
-    """The lexicographically smaller of each k-mer and its reverse complement (A < C < G < T), what a canonical
-    table's dump reports.  A string gives a string; encoded limbs ((n, key_limbs) or flat) give limbs
-    (tsx_hip_canonical_host: the complement is taken on the 2-bit code, so any byte has one)."""
-    if isinstance(kmers, (str, bytes)):
-        return decode(canonical(encode(kmers, k), k), k)
-    a = np.ascontiguousarray(kmers, dtype=np.uint64)
-    out = np.zeros_like(a)
-    n = a.size // key_limbs(k)
-    _check(lib().tsx_hip_canonical_host(k, _p(a), n, _p(out)))
-    return out
-
-
-def min_qual_code(min_qual_char):
-    """The byte of a min_qual_char argument: None or 0 = off, a one-character str (e.g. '5') or an int 1 .. 255."""
-    if min_qual_char is None:
-        return 0
-    if isinstance(min_qual_char, (bytes, str)):
-        b = min_qual_char.encode("latin-1") if isinstance(min_qual_char, str) else min_qual_char
-        if len(b) != 1:
-            raise ValueError("min_qual_char: one character, got %r" % (min_qual_char,))
-        return b[0]
-    if isinstance(min_qual_char, bool) or not isinstance(min_qual_char, (int, np.integer)):
-        raise TypeError("min_qual_char: a one-character str or an int, got %r" % (min_qual_char,))
-    if not 0 <= int(min_qual_char) <= 255:
-        raise ValueError("min_qual_char: 0 .. 255, got %d" % min_qual_char)
-    return int(min_qual_char)
-
-
-def encode_many(seqs, k):
-    out = np.zeros((len(seqs), key_limbs(k)), dtype=np.uint64)
-    for i, s in enumerate(seqs):
-        out[i] = encode(s, k)
-    return out
-
-
-class TSXHashMapHIP:
-    """Host mirror of TSXHashMap / TSXHashMapCAS for --mode=HIP.
-
-    Constructor arguments follow TSXHashMap(iL, iStorageBits, iK)
-    (TSXHashMap.h:79); method names follow the reference class.
-    """
-
-    def __init__(self, iL, iStorageBits, iK, iThreads=0, hash_seed=1, overflow_l=0, device=0, shard_bits=0,
-                 shard_index=0, canonical=False, acgt_only=False, min_qual_char=None):
-        min_qual_code(min_qual_char)   # (argument errors before anything is allocated)
-        self._h = ctypes.c_void_p()
-        self._lib = lib()
-        _check(self._lib.tsx_hip_create_shard(ctypes.byref(self._h), iK, iL, iStorageBits, overflow_l,
-                                              hash_seed, device, shard_bits, shard_index))
-        self.layout = Layout()
-        _check(self._lib.tsx_hip_get_layout(self._h, ctypes.byref(self.layout)))
-        self.k, self.l, self.wk, self.device = iK, iL, self.layout.key_limbs, device
-        self.hash_seed = hash_seed
-        self.combine_stats = None
-        self._lines = 4
-        if canonical:
-            self.set_canonical(True)
-        if acgt_only or min_qual_char:
-            self.set_base_rule(acgt_only, min_qual_char)
-
-    @property
-    def base_rule(self):
-        """(acgt_only, min_qual_char) in effect: min_qual_char as a one-character str, None when off."""
-        a, q = ctypes.c_int(), ctypes.c_int()
-        _check(self._lib.tsx_hip_get_base_rule(self.handle, ctypes.byref(a), ctypes.byref(q)))
-        return bool(a.value), (chr(q.value) if q.value else None)
-
-    def set_base_rule(self, acgt_only=False, min_qual_char=None):
-        """Which windows count as k-mers (tsx_hip_set_base_rule): acgt_only drops windows with a byte outside ACGTacgt,
-        min_qual_char (a one-character str or an int) those with a base whose quality byte is below it or missing.
-        Keys do not change, so the rule may change between calls; FASTQ only for min_qual_char."""
-        q = min_qual_code(min_qual_char)
-        if q and self._lines != 4:
-            raise ValueError("min_qual_char needs FASTQ records: a FASTA text has no quality line")
-        _check(self._lib.tsx_hip_set_base_rule(self.handle, 1 if acgt_only else 0, q))
-
-    @property
-    def canonical(self):
-        """True when x and its reverse complement share one counter (tsx_hip_set_canonical)."""
-        return self._lib.tsx_hip_canonical(self.handle) == 1
-
-    def set_canonical(self, on=True):
-        """Canonical counting on or off; an empty table only (just created or after clear())."""
-        _check(self._lib.tsx_hip_set_canonical(self.handle, 1 if on else 0))
-
-    def close(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            self._lib.tsx_hip_destroy(h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # interpreter teardown: ctypes may already be gone
-            pass
-
-    @property
-    def handle(self):
-        if self._h is None:
-            raise TSXException(EINVAL, "map is closed")
-        return self._h
-
-    # --- reference surface -------------------------------------------------
-    def getK(self):
-        return self.k
-
-    def getMaxElements(self):
-        return int(self.layout.slots)
-
-    def addKmer(self, kmer):
-        """TSXHashMap::addKmer (TSXHashMap.h:182); kmer = limbs or sequence."""
-        self.addKmers(self._as_kmers([kmer]))
-        return True
-
-    def addKmers(self, kmers, counts=None):
-        a = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1, self.wk)
-        c = None
-        if counts is not None:
-            c = np.ascontiguousarray(counts, dtype=np.uint64)
-            assert c.shape[0] == a.shape[0]
-        _check(self._lib.tsx_hip_add_kmers_host(self._h, _p(a), _p(c) if c is not None else None, a.shape[0]))
-
-    def getKmerCount(self, kmer=None):
-        """getKmerCount(kmer) (TSXHashMap.h:548) or getKmerCount() (:645)."""
-        if kmer is None:
-            return self.stats()["distinct"]
-        return int(self.getKmerCounts(self._as_kmers([kmer]))[0])
-
-    def getKmerCounts(self, kmers):
-        a = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1, self.wk)
-        out = np.zeros(a.shape[0], dtype=np.uint64)
-        _check(self._lib.tsx_hip_get_counts_host(self._h, _p(a), a.shape[0], _p(out)))
-        return out
-
-    def getKmerCountDebug(self, kmers):
-        """getKmerCountDebug (TSXHashMap.h:477): (counts, slots); slot = 2^64-1 for absent k-mers."""
-        a = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1, self.wk)
-        out = np.zeros(a.shape[0], dtype=np.uint64)
-        pos = np.zeros(a.shape[0], dtype=np.uint64)
-        _check(self._lib.tsx_hip_lookup_host(self._h, _p(a), a.shape[0], _p(out), _p(pos)))
-        return out, pos
-
-    def getKmerStarts(self):
-        """getKmerStarts (TSXHashMap.h:650) as a numpy bool array over the 2^l slots."""
-        nb = (int(self.layout.slots) + 7) // 8
-        bits = np.zeros(nb, dtype=np.uint8)
-        _check(self._lib.tsx_hip_kmer_starts_host(self._h, bits.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), nb))
-        return np.unpackbits(bits, bitorder="little")[:int(self.layout.slots)].astype(bool)
-
-    def getAllKmers(self):
-        """TSXHashMap::getAllKmers (TSXHashMap.h:660) with counts; order unspecified."""
-        n = self.stats()["distinct"]
-        kmers = np.zeros((max(n, 1), self.wk), dtype=np.uint64)
-        counts = np.zeros(max(n, 1), dtype=np.uint64)
-        got = ctypes.c_size_t(0)
-        _check(self._lib.tsx_hip_dump_host(self._h, _p(kmers), _p(counts), max(n, 1), ctypes.byref(got)))
-        return kmers[:got.value], counts[:got.value]
-
-    def dumpRangeDevice(self, slot_lo, slot_hi, kmers_ptr, counts_ptr, cap, n_ptr, stream=None):
-        """getAllKmers for the slots [slot_lo, slot_hi) into device buffers (tsx_hip_dump_range_device)."""
-        vp = ctypes.c_void_p
-        _check(self._lib.tsx_hip_dump_range_device(self._h, slot_lo, slot_hi, vp(kmers_ptr), vp(counts_ptr), cap,
-                                                   vp(n_ptr), vp(stream) if stream else None))
-
-    def getCountHistogram(self, nbins=10002, slot_lo=0, slot_hi=None):
-        """Abundance histogram (numpy uint64, nbins): [c] = k-mers counted c times, the last bin pools every count
-        >= nbins - 1.  The whole table, or the slots [slot_lo, slot_hi) (tsx_hip_histogram_device on a torch buffer)."""
-        out = np.zeros(nbins, dtype=np.uint64)
-        if slot_lo == 0 and slot_hi is None:
-            _check(self._lib.tsx_hip_histogram_host(self._h, _p(out), nbins))
-            return out
-        import torch
-        hi = int(self.layout.slots) if slot_hi is None else int(slot_hi)
-        buf = torch.empty(max(nbins, 1), dtype=torch.int64, device=torch.device("cuda", self.device))
-        st = torch.cuda.Stream(buf.device)   # a stream of its own: torch's default one does not wait for the map's
-        _check(self._lib.tsx_hip_histogram_device(self._h, int(slot_lo), hi, nbins, ctypes.c_void_p(buf.data_ptr()),
-                                                  ctypes.c_void_p(st.cuda_stream)))
-        st.synchronize()
-        out[:] = buf.cpu().numpy().view(np.uint64)
-        return out
-
-    def writeCounts(self, path, lower=1, upper=None, chunk_bytes=0):
-        """Every k-mer whose count lies in [lower, upper] as "kmer<TAB>count" lines (the .count format of
-        count_kmers.py / main.cpp:224-396), in no particular order.  Returns (lines, bytes)."""
-        return _write_counts(self._lib.tsx_hip_write_counts_host, self.handle, _check, path, lower, upper, chunk_bytes)
-
-    def saveDatabase(self, path_or_fd, chunk_bytes=0):
-        """The table as a k-mer database (tsx_hip_save_host) to a path (created or truncated) or an open file descriptor
-        (written from its current position).  Returns (entries, bytes written)."""
-        entries, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        own = not isinstance(path_or_fd, int)
-        fd = os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd
-        try:
-            rc = self._lib.tsx_hip_save_host(self.handle, fd, int(chunk_bytes), ctypes.byref(entries), ctypes.byref(nbytes))
-        finally:
-            if own:
-                os.close(fd)
-        _check(rc)
-        return int(entries.value), int(nbytes.value)
-
-    def addDatabase(self, path_or_fd, chunk_bytes=0):
-        """Load a k-mer database into this table (tsx_hip_load_host): placed as it is into an empty table of the same
-        geometry and seed, otherwise every k-mer is added with its count (a merge).  Returns the entries read.  After an
-        error the table's content is unspecified: clear() recovers it."""
-        entries = ctypes.c_uint64(0)
-        own = not isinstance(path_or_fd, int)
-        fd = os.open(path_or_fd, os.O_RDONLY) if own else path_or_fd
-        try:
-            rc = self._lib.tsx_hip_load_host(self.handle, fd, int(chunk_bytes), ctypes.byref(entries))
-        finally:
-            if own:
-                os.close(fd)
-        _check(rc)
-        return int(entries.value)
-
-    @classmethod
-    def fromDatabase(cls, path, iL=None, iStorageBits=None, device=0, chunk_bytes=0):
-        """A new table holding a k-mer database: k, seed, counting mode and base rule come from the file; l and the
-        storage bits too unless given (a different geometry loads through the re-insert path)."""
-        info = database_info(path)
-        same = iL in (None, info["l"]) and iStorageBits in (None, info["count_bits"])
-        m = cls(info["l"] if iL is None else iL, info["count_bits"] if iStorageBits is None else iStorageBits, info["k"],
-                hash_seed=info["hash_seed"], overflow_l=info["overflow_l"] if same else 0, device=device,
-                canonical=bool(info["canonical"]), acgt_only=bool(info["acgt_only"]), min_qual_char=info["min_qual_char"] or None)
-        try:
-            m.addDatabase(path, chunk_bytes)
-        except Exception:
-            m.close()
-            raise
-        return m
-
-    def _combine(self, other, rule, out):
-        st = CombineStats()
-        rc = self._lib.tsx_hip_combine(out.handle if out is not None else None, self.handle, other.handle,
-                                       ctypes.byref(rule), ctypes.byref(st))
-        if rc == EINVAL:
-            raise TSXException(rc, self._lib.tsx_hip_last_error().decode() or self._lib.tsx_hip_strerror(rc).decode())
-        _check(rc)
-        return st.as_dict()
-
-    def combine(self, other, op="intersect", counts="min", a_range=(1, None), b_range=(1, None), out=None, iL=None,
-                iStorageBits=None, hash_seed=None):
-        """Set operation on two tables (tsx_hip_combine): self is A, `other` is B.  op: "intersect", "union",
-        "subtract" (A's k-mers that B lacks) or "diff" (count differences a - b > 0); counts: "min", "max", "sum",
-        "left", "right" where a k-mer is in both; a_range / b_range: (lower, upper) of the counts that take part.
-        Returns the result table with .combine_stats set: `out` (an empty map) when given, else a new map created like
-        self -- same l, storage bits and seed unless iL / iStorageBits / hash_seed say otherwise."""
-        rule = combine_rule(op, counts, a_range, b_range)
-        made = out is None
-        if made:
-            same = iL in (None, self.l) and iStorageBits in (None, self.layout.count_bits)
-            acgt, minq = self.base_rule
-            out = TSXHashMapHIP(self.l if iL is None else iL,
-                                self.layout.count_bits if iStorageBits is None else iStorageBits, self.k,
-                                hash_seed=self.hash_seed if hash_seed is None else hash_seed,
-                                overflow_l=self.layout.overflow_l if same else 0, device=self.device,
-                                canonical=self.canonical, acgt_only=acgt, min_qual_char=minq)
-        try:
-            out.combine_stats = self._combine(other, rule, out)
-        except Exception:
-            if made:
-                out.close()
-            raise
-        return out
-
-    def compare(self, other, a_range=(1, None), b_range=(1, None)):
-        """How two tables overlap (tsx_hip_combine without an output table): the combine stats of an intersection
-        -- a_in_range, b_in_range, both, a_sum_both, b_sum_both, ... -- plus `jaccard` = both / (a + b - both)."""
-        st = self._combine(other, combine_rule("intersect", "min", a_range, b_range), None)
-        union = st["a_in_range"] + st["b_in_range"] - st["both"]
-        st["jaccard"] = st["both"] / union if union else 0.0
-        return st
-
-    def _check_joint(self, rc):
-        if rc == EINVAL:
-            raise TSXException(rc, self._lib.tsx_hip_last_error().decode() or self._lib.tsx_hip_strerror(rc).decode())
-        _check(rc)
-
-    def jointHistogram(self, other, bins_a=1002, bins_b=1002):
-        """Joint k-mer spectrum of two tables (tsx_hip_joint_histogram_host; KAT `comp`): self is A, `other` is B.
-        Returns numpy uint64[bins_a, bins_b]: [i, j] = distinct k-mers counted i times in A and j times in B, the last
-        bin of each side pooling every larger count; [0, 0] is 0.  joint_histogram() states the definition."""
-        out = np.zeros((int(bins_a), int(bins_b)) if 0 < bins_a * bins_b <= JOINT_MAX_CELLS else (0, 0), dtype=np.uint64)
-        self._check_joint(self._lib.tsx_hip_joint_histogram_host(self.handle, other.handle, _p(out), int(bins_a), int(bins_b)))
-        return out
-
-    def jointHistogramDevice(self, other, matrix_ptr, bins_a=1002, bins_b=1002, stream=None):
-        """tsx_hip_joint_histogram_device: the matrix into uint64[bins_a * bins_b] in device memory (zeroed by the call),
-        queued on `stream` (None = this map's own); returns without waiting."""
-        vp = ctypes.c_void_p
-        self._check_joint(self._lib.tsx_hip_joint_histogram_device(self.handle, other.handle, int(bins_a), int(bins_b),
-                                                                   vp(matrix_ptr), vp(stream) if stream else None))
-
-    def binStats(self, other, text, a_range=(1, None), b_range=(1, None), min_hits=1, ratio=1.0, chunk_bytes=0):
-        """Hits of every record of a FASTQ / FASTA text in two tables, in one scan (tsx_hip_bin_stats_host): self is A,
-        `other` is B.  Returns (stats, classes): a numpy structured array (BIN_STATS_DTYPE: kmers, hits_a, hits_b,
-        hits_both) and a uint8 array of BIN_A / BIN_B / BIN_AMBIGUOUS / BIN_NONE, one entry per record in text order.
-        A window hits a table when its count there lies in the table's range; bin_class() states the class rule."""
-        b = bytes(text)
-        rule = bin_rule(a_range, b_range, min_hits, ratio)
-        cap = len(b) // 256 + 16
-        for _ in range(2):
-            out = np.zeros(cap, dtype=BIN_STATS_DTYPE)
-            cls = np.zeros(cap, dtype=np.uint8)
-            n = ctypes.c_size_t(0)
-            rc = self._lib.tsx_hip_bin_stats_host(self.handle, other.handle, b, len(b), ctypes.byref(rule),
-                                                  out.ctypes.data_as(ctypes.c_void_p), cls.ctypes.data_as(ctypes.c_void_p), cap,
-                                                  ctypes.byref(n), int(chunk_bytes))
-            if rc != ERANGE:
-                break
-            cap = n.value
-        self._check_joint(rc)
-        return out[:n.value], cls[:n.value]
-
-    def binStatsDevice(self, other, text_ptr, nbytes, stats_ptr, cap, a_range=(1, None), b_range=(1, None), min_hits=1,
-                       ratio=1.0, stream=None):
-        """tsx_hip_bin_stats_device: the bin stats of the records of a device text into a device buffer of cap records
-        (4 uint64 each).  Waits; returns the record count (more than cap: TSXException ERANGE)."""
-        vp = ctypes.c_void_p
-        rule = bin_rule(a_range, b_range, min_hits, ratio)
-        n = ctypes.c_size_t(0)
-        self._check_joint(self._lib.tsx_hip_bin_stats_device(self.handle, other.handle, vp(text_ptr), nbytes, ctypes.byref(rule),
-                                                             vp(stats_ptr), cap, ctypes.byref(n), vp(stream) if stream else None))
-        return int(n.value)
-
-    def binReads(self, other, text, out_a=None, out_b=None, out_ambiguous=None, out_none=None, a_range=(1, None),
-                 b_range=(1, None), min_hits=1, ratio=1.0, chunk_bytes=0):
-        """Split the records of `text` by the table they hit more (tsx_hip_bin_reads_host): self is A, `other` is B.
-        Each output is a path (created or truncated), an open file descriptor, or None (the class is counted and not
-        written); at least one is needed.  Returns the totals as a dict: records, n[class], bytes[class]."""
-        b = bytes(text)
-        rule = bin_rule(a_range, b_range, min_hits, ratio)
-        opened, fds = [], []
-        try:
-            for o in (out_a, out_b, out_ambiguous, out_none):
-                if o is None:
-                    fds.append(-1)
-                elif isinstance(o, int):
-                    fds.append(o)
-                else:
-                    fds.append(os.open(o, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644))
-                    opened.append(fds[-1])
-            io, tot = BinIO(*fds), BinTotals()
-            rc = self._lib.tsx_hip_bin_reads_host(self.handle, other.handle, b, len(b), ctypes.byref(rule), ctypes.byref(io),
-                                                  int(chunk_bytes), ctypes.byref(tot))
-        finally:
-            for fd in opened:
-                os.close(fd)
-        self._check_joint(rc)
-        return tot.as_dict()
-
-    def hetHistogram(self, bins_minor=1002, bins_major=1002, lower=1, upper=None, mode="unique"):
-        """Heterozygous k-mer pairs of this table by their two counts (tsx_hip_het_histogram_host; Smudgeplot's hetkmers):
-        the pairs of k-mers counted in [lower, upper] that differ only in their middle base.  mode 'unique' counts the pair
-        of a family of exactly two, 'all' every pair of every family.  Returns (numpy uint64[bins_minor, bins_major], stats):
-        [i, j] = pairs whose lower count is i and whose higher count is j, the last bin of each side pooling every larger
-        count; stats is the dict of het_pairs().  het_pairs() and het_histogram() state the definition.  k must be odd."""
-        rule = het_rule(lower, upper, mode)
-        ok = bins_minor > 0 and bins_major > 0 and bins_minor * bins_major <= JOINT_MAX_CELLS
-        out = np.zeros((int(bins_minor), int(bins_major)) if ok else (0, 0), dtype=np.uint64)
-        st = HetStats()
-        self._check_joint(self._lib.tsx_hip_het_histogram_host(self.handle, ctypes.byref(rule), _p(out), int(bins_minor),
-                                                               int(bins_major), ctypes.byref(st)))
-        return out, {n: int(getattr(st, n)) for n, _ in HetStats._fields_}
-
-    def hetHistogramDevice(self, matrix_ptr, stats_ptr, bins_minor=1002, bins_major=1002, lower=1, upper=None, mode="unique",
-                           stream=None):
-        """tsx_hip_het_histogram_device: the matrix into uint64[bins_minor * bins_major] and the five totals into uint64[5],
-        both in device memory (zeroed by the call), queued on `stream` (None = this map's own); returns without waiting."""
-        vp = ctypes.c_void_p
-        rule = het_rule(lower, upper, mode)
-        self._check_joint(self._lib.tsx_hip_het_histogram_device(self.handle, ctypes.byref(rule), int(bins_minor), int(bins_major),
-                                                                 vp(matrix_ptr), vp(stats_ptr), vp(stream) if stream else None))
-
-    def hetPairs(self, lower=1, upper=None, mode="unique", slot_lo=0, slot_hi=None, range_slots=1 << 20):
-        """The heterozygous pairs themselves (tsx_hip_het_pairs_device, range_slots slots a call): a numpy structured
-        array het_pair_dtype(k) -- minor, major (k-mers as limbs, as a dump reports them), minor_count, major_count -- in
-        no particular order.  The record's width follows the key width, so the dtype is het_pair_dtype(self.k); it equals
-        HET_PAIR_DTYPE only for one-limb keys (k <= 32).  slot_lo / slot_hi: only the pairs those slots own (every pair is owned by one slot)."""
-        import torch
-        rule = het_rule(lower, upper, mode)
-        dt = het_pair_dtype(self.k)
-        hi = int(self.layout.slots) if slot_hi is None else int(slot_hi)
-        step = max(1, int(range_slots))
-        cap = min(step, max(hi - int(slot_lo), 1)) * (3 if mode == "all" else 1)
-        words = dt.itemsize // 8
-        buf = torch.empty(cap * words + 1, dtype=torch.int64, device=torch.device("cuda", self.device))
-        st = torch.cuda.Stream(buf.device)   # a stream of its own: torch's default one does not wait for the map's
-        vp = ctypes.c_void_p
-        parts = []
-        lo = int(slot_lo)
-        while True:
-            top = min(hi, lo + step)
-            self._check_joint(self._lib.tsx_hip_het_pairs_device(self.handle, ctypes.byref(rule), lo, top, vp(buf.data_ptr()), cap,
-                                                                 vp(buf.data_ptr() + cap * words * 8), vp(st.cuda_stream)))
-            n = int(buf[cap * words].item())
-            if n:
-                parts.append(buf[:n * words].cpu().numpy().view(np.uint64).view(dt).copy())
-            lo = top
-            if lo >= hi:
-                break
-        return np.concatenate(parts) if parts else np.zeros(0, dtype=dt)
-
-    def writeHetPairs(self, path_or_fd, lower=1, upper=None, mode="unique", chunk_bytes=0):
-        """The pairs as "minor_kmer<TAB>minor_count<TAB>major_kmer<TAB>major_count" lines (tsx_hip_write_het_pairs_host) to
-        a path (created or truncated) or an open file descriptor, in no particular order.  Returns (pairs, bytes)."""
-        rule = het_rule(lower, upper, mode)
-        pairs, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        own = not isinstance(path_or_fd, int)
-        fd = os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd
-        try:
-            rc = self._lib.tsx_hip_write_het_pairs_host(self.handle, ctypes.byref(rule), fd, int(chunk_bytes), ctypes.byref(pairs),
-                                                        ctypes.byref(nbytes))
-        finally:
-            if own:
-                os.close(fd)
-        self._check_joint(rc)
-        return int(pairs.value), int(nbytes.value)
-
-    def queryReads(self, text, lower=1, upper=None, chunk_bytes=0):
-        """Per-record k-mer stats of a FASTQ / FASTA text against the table (tsx_hip_query_reads_host): a numpy
-        structured array (READ_STATS_DTYPE: kmers, in_range, min_count, sum_count), one entry per record in text
-        order; in_range counts the k-mers whose count lies in [lower, upper]."""
-        b = bytes(text)
-        upper = (1 << 64) - 1 if upper is None else int(upper)
-        cap = len(b) // 256 + 16
-        for _ in range(2):
-            out = np.zeros(cap, dtype=READ_STATS_DTYPE)
-            n = ctypes.c_size_t(0)
-            rc = self._lib.tsx_hip_query_reads_host(self.handle, b, len(b), int(lower), upper, out.ctypes.data_as(ctypes.c_void_p),
-                                                    cap, ctypes.byref(n), int(chunk_bytes))
-            if rc != ERANGE:
-                break
-            cap = n.value
-        _check(rc)
-        return out[:n.value]
-
-    # --- sequence queries: the sequences of a wrapped FASTA (csrc/tsx_seq.h) ---------------------------------------
-    def _seq_call(self, fn, args, use):
-        """Runs one tsx_hip_seq_* entry point and hands its result to use(res) before it is freed."""
-        res = ctypes.c_void_p(None)
-        rc = fn(self.handle, *args, ctypes.byref(res))
-        if rc == EINVAL:   # a refusal: the library says which
-            raise TSXException(rc, self._lib.tsx_hip_last_error().decode() or self._lib.tsx_hip_strerror(rc).decode())
-        _check(rc)
-        try:
-            return use(res)
-        finally:
-            self._lib.tsx_hip_seq_result_free(res)
-
-    def _seq_stats_of(self, res):
-        L = self._lib
-        n = L.tsx_hip_seq_result_count(res)
-        stats = np.zeros(n, dtype=SEQ_STATS_DTYPE)
-        if n:
-            ctypes.memmove(stats.ctypes.data, L.tsx_hip_seq_result_stats(res), n * SEQ_STATS_DTYPE.itemsize)
-        offs = ctypes.c_void_p(None)
-        blob = L.tsx_hip_seq_result_names(res, ctypes.byref(offs))
-        off = np.zeros(n + 1, dtype=np.uint64)
-        ctypes.memmove(off.ctypes.data, offs.value, (n + 1) * 8)
-        raw = ctypes.string_at(blob, int(off[n])) if int(off[n]) else b""
-        return [raw[int(off[i]):int(off[i + 1])] for i in range(n)], stats
-
-    def _seq_intervals_of(self, res):
-        iv = ctypes.c_void_p(None)
-        n = self._lib.tsx_hip_seq_result_intervals(res, ctypes.byref(iv))
-        out = np.zeros(n, dtype=SEQ_INTERVAL_DTYPE)
-        if n:
-            ctypes.memmove(out.ctypes.data, iv.value, n * SEQ_INTERVAL_DTYPE.itemsize)
-        return out
-
-    @staticmethod
-    def _seq_range(lower, upper):
-        return int(lower), (1 << 64) - 1 if upper is None else int(upper)
-
-    def querySequences(self, text, lower=1, upper=None, chunk_bytes=0):
-        """Per-sequence k-mer stats of a wrapped FASTA text against the table (tsx_hip_seq_stats_host): (names, stats)
-        -- a list of bytes and a numpy structured array (SEQ_STATS_DTYPE), one entry per record of fasta_records(text);
-        what sequence_stats states on the CPU."""
-        b = bytes(text)
-        lo, up = self._seq_range(lower, upper)
-        return self._seq_call(self._lib.tsx_hip_seq_stats_host, (b, len(b), lo, up, int(chunk_bytes)), self._seq_stats_of)
-
-    def missingIntervals(self, text, lower=1, upper=None, chunk_bytes=0):
-        """The maximal runs of missing k-mers of every sequence (tsx_hip_seq_missing_host): a numpy structured array
-        (SEQ_INTERVAL_DTYPE: seq, start, end), ordered by sequence, then start; what missing_intervals states."""
-        b = bytes(text)
-        lo, up = self._seq_range(lower, upper)
-        return self._seq_call(self._lib.tsx_hip_seq_missing_host, (b, len(b), lo, up, int(chunk_bytes)), self._seq_intervals_of)
-
-    def querySequencesBgzf(self, gz, lower=1, upper=None):
-        """querySequences for the image of a blocked gzip (BGZF) file."""
-        b = bytes(gz)
-        lo, up = self._seq_range(lower, upper)
-        return self._seq_call(self._lib.tsx_hip_seq_stats_bgzf_host, (b, len(b), lo, up), self._seq_stats_of)
-
-    def missingIntervalsBgzf(self, gz, lower=1, upper=None):
-        """missingIntervals for the image of a blocked gzip (BGZF) file."""
-        b = bytes(gz)
-        lo, up = self._seq_range(lower, upper)
-        return self._seq_call(self._lib.tsx_hip_seq_missing_bgzf_host, (b, len(b), lo, up), self._seq_intervals_of)
-
-    def querySequencesDevice(self, text_ptr, nbytes, lower=1, upper=None, missing=False, stream=None):
-        """querySequences for a wrapped FASTA text resident on the device (16-byte aligned): (names, stats), and the
-        intervals as a third item when missing is set (tsx_hip_seq_stats_device / tsx_hip_seq_missing_device)."""
-        lo, up = self._seq_range(lower, upper)
-        vp = ctypes.c_void_p
-        fn = self._lib.tsx_hip_seq_missing_device if missing else self._lib.tsx_hip_seq_stats_device
-
-        def call(handle, *a):
-            return fn(handle, *a, vp(stream) if stream else None)
-        use = (lambda r: self._seq_stats_of(r) + (self._seq_intervals_of(r),)) if missing else self._seq_stats_of
-        return self._seq_call(call, (vp(text_ptr), nbytes, lo, up), use)
-
-    def _seq_write(self, text, path_or_fd, lower, upper, chunk_bytes, missing):
-        b = bytes(text)
-        lo, up = self._seq_range(lower, upper)
-        own = not isinstance(path_or_fd, int)
-        fd = os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd
-        fn = self._lib.tsx_hip_seq_missing_host if missing else self._lib.tsx_hip_seq_stats_host
-
-        def use(res):
-            if missing:
-                _check(self._lib.tsx_hip_seq_write_missing(res, fd))
-                return len(self._seq_intervals_of(res))
-            _check(self._lib.tsx_hip_seq_write_stats(res, self.k, fd))
-            return int(self._lib.tsx_hip_seq_result_count(res))
-        try:
-            return self._seq_call(fn, (b, len(b), lo, up, int(chunk_bytes)), use)
-        finally:
-            if own:
-                os.close(fd)
-
-    def writeSequenceStats(self, text, path_or_fd, lower=1, upper=None, chunk_bytes=0):
-        """One line per sequence to a path or an open file descriptor: name, length, kmers, present, missing, min, sum,
-        qv (tsx_hip_seq_write_stats).  Returns the number of sequences."""
-        return self._seq_write(text, path_or_fd, lower, upper, chunk_bytes, False)
-
-    def writeMissing(self, text, path_or_fd, lower=1, upper=None, chunk_bytes=0):
-        """The missing intervals as BED (name, start, end) to a path or an open file descriptor.  Returns their number."""
-        return self._seq_write(text, path_or_fd, lower, upper, chunk_bytes, True)
-
-    def filterReads(self, text, path_or_fd, lower=2, upper=None, min_in_range=0, fraction=1.0, invert=False, chunk_bytes=0):
-        """Write the records of `text` whose k-mers pass the rule (tsx_hip_filter_reads_host) to a path (created or
-        truncated) or an open file descriptor.  Returns (records kept, bytes written)."""
-        b = bytes(text)
-        rule = filter_rule(lower, upper, min_in_range, fraction, invert)
-        kept, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        own = not isinstance(path_or_fd, int)
-        fd = os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd
-        try:
-            rc = self._lib.tsx_hip_filter_reads_host(self.handle, b, len(b), ctypes.byref(rule), fd, int(chunk_bytes),
-                                                     ctypes.byref(kept), ctypes.byref(nbytes))
-        finally:
-            if own:
-                os.close(fd)
-        _check(rc)
-        return int(kept.value), int(nbytes.value)
-
-    def trimSpans(self, text, lower=2, upper=None, mode="longest", chunk_bytes=0):
-        """The kept span of every record of a FASTQ / FASTA text (tsx_hip_trim_spans_host): a numpy structured array
-        (TRIM_SPAN_DTYPE: start, length in bases of the sequence line), one entry per record in text order.  A window
-        is solid when its count lies in [lower, upper]; mode "longest" keeps the longest run of solid windows (the
-        leftmost among equals), "prefix" the run that starts the read."""
-        rule = trim_rule(lower, upper, mode)
-        b = bytes(text)
-        cap = len(b) // 256 + 16
-        for _ in range(2):
-            out = np.zeros(cap, dtype=TRIM_SPAN_DTYPE)
-            n = ctypes.c_size_t(0)
-            rc = self._lib.tsx_hip_trim_spans_host(self.handle, b, len(b), ctypes.byref(rule), out.ctypes.data_as(ctypes.c_void_p),
-                                                   cap, ctypes.byref(n), int(chunk_bytes))
-            if rc != ERANGE:
-                break
-            cap = n.value
-        _check(rc)
-        return out[:n.value]
-
-    def trimReads(self, text, path_or_fd, lower=2, upper=None, mode="longest", min_len=0, chunk_bytes=0):
-        """Write the records of `text` cut to their kept spans (tsx_hip_trim_reads_host) to a path (created or
-        truncated) or an open file descriptor; records that keep fewer than min_len bases (0 = k) are dropped.  Returns
-        the totals as a dict: records, kept, bases_in, bases_kept, bytes."""
-        rule = trim_rule(lower, upper, mode, min_len)
-        b = bytes(text)
-        tot = TrimTotals()
-        own = not isinstance(path_or_fd, int)
-        fd = os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd
-        try:
-            rc = self._lib.tsx_hip_trim_reads_host(self.handle, b, len(b), ctypes.byref(rule), fd, int(chunk_bytes),
-                                                   ctypes.byref(tot))
-        finally:
-            if own:
-                os.close(fd)
-        _check(rc)
-        return tot.as_dict()
-
-    def countProfile(self, text, chunk_bytes=0):
-        """The count of every window of a FASTQ / FASTA text (tsx_hip_count_profile_host): numpy uint32[len(text)],
-        entry i = min(count, 0xFFFFFFFE) of the k-mer that starts at byte i, NO_KMER where none does."""
-        b = bytes(text)
-        out = np.empty(len(b), dtype=np.uint32)
-        _check(self._lib.tsx_hip_count_profile_host(self.handle, b, len(b), out.ctypes.data_as(ctypes.c_void_p),
-                                                    int(chunk_bytes)))
-        return out
-
-    def medianReads(self, text, chunk_bytes=0):
-        """The median k-mer count of every record of a FASTQ / FASTA text (tsx_hip_median_reads_host): a numpy
-        structured array (READ_MEDIAN_DTYPE: kmers, median), one entry per record in text order; the median is that of
-        median_count over the record's profile entries."""
-        b = bytes(text)
-        cap = len(b) // 256 + 16
-        for _ in range(2):
-            out = np.zeros(cap, dtype=READ_MEDIAN_DTYPE)
-            n = ctypes.c_size_t(0)
-            rc = self._lib.tsx_hip_median_reads_host(self.handle, b, len(b), out.ctypes.data_as(ctypes.c_void_p), cap,
-                                                     ctypes.byref(n), int(chunk_bytes))
-            if rc != ERANGE:
-                break
-            cap = n.value
-        _check(rc)
-        return out[:n.value]
-
-    def filterReadsByMedian(self, text, path_or_fd, lower=0, upper=None, invert=False, chunk_bytes=0):
-        """Write the records of `text` whose median k-mer count lies in [lower, upper] (tsx_hip_filter_median_host) to
-        a path (created or truncated) or an open file descriptor; invert writes the others.  Returns (records kept,
-        bytes written)."""
-        rule = median_rule(lower, upper, invert)
-        b = bytes(text)
-        kept, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        own = not isinstance(path_or_fd, int)
-        fd = os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd
-        try:
-            rc = self._lib.tsx_hip_filter_median_host(self.handle, b, len(b), ctypes.byref(rule), fd, int(chunk_bytes),
-                                                      ctypes.byref(kept), ctypes.byref(nbytes))
-        finally:
-            if own:
-                os.close(fd)
-        _check(rc)
-        return int(kept.value), int(nbytes.value)
-
-    def countProfileDevice(self, text_ptr, nbytes, profile_ptr, stream=None):
-        """tsx_hip_count_profile_device: the profile of a device text into a device buffer of nbytes uint32."""
-        vp = ctypes.c_void_p
-        _check(self._lib.tsx_hip_count_profile_device(self.handle, vp(text_ptr), nbytes, vp(profile_ptr),
-                                                      vp(stream) if stream else None))
-
-    def medianReadsDevice(self, text_ptr, nbytes, medians_ptr, cap, stream=None):
-        """tsx_hip_median_reads_device: {kmers, median} of the records of a device text into a device buffer of cap
-        entries.  Returns the record count (more than cap: TSXException ERANGE)."""
-        vp = ctypes.c_void_p
-        n = ctypes.c_size_t(0)
-        _check(self._lib.tsx_hip_median_reads_device(self.handle, vp(text_ptr), nbytes, vp(medians_ptr), cap, ctypes.byref(n),
-                                                     vp(stream) if stream else None))
-        return int(n.value)
-
-    # --- digital normalization ----------------------------------------------
-    def _check_normalize(self, rc):
-        if rc == EINVAL:   # a refusal: the library says which
-            raise TSXException(rc, self._lib.tsx_hip_last_error().decode() or self._lib.tsx_hip_strerror(rc).decode())
-        _check(rc)
-
-    def normalizeReads(self, text, path_or_fd=None, cutoff=20, round_records=NORMALIZE_ROUND, keep=False, chunk_bytes=0):
-        """Digital normalization (tsx_hip_normalize_host): the records of `text` in rounds of round_records; a record is
-        kept iff the median count of its k-mers, in the table as it stands when its round starts, is below cutoff, and
-        the k-mers of a round's kept records are counted when the round has been judged.  The kept records go to a
-        path (created or truncated) or an open file descriptor; None: no output.  Returns the totals (records, kept,
-        kmers_seen, kmers_added, rounds) as a dict; keep=True adds `keep`, a numpy bool array with one entry per
-        record."""
-        rule = normalize_rule(cutoff, round_records)
-        b = bytes(text)
-        tot = NormalizeTotals()
-        own = path_or_fd is not None and not isinstance(path_or_fd, int)
-        fd = -1 if path_or_fd is None else (os.open(path_or_fd, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644) if own else path_or_fd)
-        flags = np.zeros(len(b) // 2 + 2 if keep else 0, dtype=np.uint8)   # (a record holds two bytes at least)
-        try:
-            rc = self._lib.tsx_hip_normalize_host(self.handle, b, len(b), ctypes.byref(rule), fd,
-                                                  flags.ctypes.data_as(ctypes.c_void_p) if keep else None, flags.size,
-                                                  int(chunk_bytes), ctypes.byref(tot))
-        finally:
-            if own:
-                os.close(fd)
-        self._check_normalize(rc)
-        out = tot.as_dict()
-        if keep:
-            out["keep"] = flags[:out["records"]].astype(bool)
-        return out
-
-    def normalizeReadsDevice(self, text_ptr, nbytes, keep_ptr, keep_cap, cutoff=20, round_records=NORMALIZE_ROUND, stream=None):
-        """tsx_hip_normalize_device: the same for a device text; one byte per record into a device buffer of keep_cap
-        bytes (keep_ptr None: no flags).  Returns the totals as a dict (more records than keep_cap: TSXException
-        ERANGE, the table is complete)."""
-        vp = ctypes.c_void_p
-        rule = normalize_rule(cutoff, round_records)
-        tot = NormalizeTotals()
-        self._check_normalize(self._lib.tsx_hip_normalize_device(self.handle, vp(text_ptr), nbytes, ctypes.byref(rule),
-                                                                 vp(keep_ptr) if keep_ptr else None, keep_cap,
-                                                                 ctypes.byref(tot), vp(stream) if stream else None))
-        return tot.as_dict()
-
-    # --- table sizing -------------------------------------------------------
-    def _sketch_regs(self, precision, registers):
-        if int(precision) not in SKETCH_PRECISIONS:
-            raise ValueError("sketch precision must be 10 .. 14, not %r" % (precision,))
-        if registers is None:
-            return np.zeros(1 << int(precision), dtype=np.uint8)
-        r = np.array(registers, dtype=np.uint8)
-        if r.shape != (1 << int(precision),):
-            raise ValueError("registers: %d entries for precision %d" % (r.size, precision))
-        return r
-
-    def sketchKmers(self, text, precision=14, registers=None, chunk_bytes=0):
-        """The HyperLogLog sketch of the k-mers `text` would put into this map (tsx_hip_sketch_host): (registers, totals)
-        with registers numpy uint8[2^precision] -- those of sketch_registers over the k-mers the counting calls would
-        count -- and totals {kmers: their exact number, records}.  registers= accumulates into a copy of an existing
-        sketch.  The map gives k, the record lines, canonical and the base rule; its table is neither read nor written."""
-        r = self._sketch_regs(precision, registers)
-        b = bytes(text)
-        t = SketchTotals()
-        _check(self._lib.tsx_hip_sketch_host(self.handle, b, len(b), int(precision), r.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                             ctypes.byref(t), int(chunk_bytes)))
-        return r, t.as_dict()
-
-    def sketchKmersBgzf(self, gz, precision=14, registers=None):
-        """The same for the image of a blocked gzip (BGZF) file, inflated on the device (tsx_hip_sketch_bgzf_host)."""
-        r = self._sketch_regs(precision, registers)
-        b = bytes(gz)
-        t = SketchTotals()
-        _check_bgzf(self._lib.tsx_hip_sketch_bgzf_host(self.handle, b, len(b), int(precision),
-                                                       r.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(t)))
-        return r, t.as_dict()
-
-    def sketchKmersDevice(self, text_ptr, nbytes, regs_ptr, precision=14, totals_ptr=None, stream=None):
-        """tsx_hip_sketch_device: the sketch of a device text max-combined into uint32[2^precision] in device memory;
-        totals_ptr: two uint64 {kmers, records} in device memory, added to.  Queued, not waited for."""
-        vp = ctypes.c_void_p
-        _check(self._lib.tsx_hip_sketch_device(self.handle, vp(text_ptr), nbytes, int(precision), vp(regs_ptr),
-                                               vp(totals_ptr) if totals_ptr else None, vp(stream) if stream else None))
-
-    @classmethod
-    def _smallest(cls, iK, iStorageBits, **kw):
-        """A map of the smallest l that has a layout for iK and iStorageBits: 4, but a long k-mer needs its func bits to
-        fit four limbs (k = 127: l >= 11)."""
-        hi = min(36, 2 * iK - 1)
-        for l in range(min(4, hi), hi + 1):
-            try:
-                return cls(l, iStorageBits, iK, **kw)
-            except TSXException as e:
-                if e.code != EINVAL or l == hi:
-                    raise
-
-    @classmethod
-    def sizedFor(cls, text, iK, iStorageBits=0, load=0.75, precision=14, canonical=False, acgt_only=False, min_qual_char=None,
-                 lines=4, **kw):
-        """A map sized for `text`: the text is sketched on a minimal probe map that carries the counting mode, and the
-        map returned has the l that suggest_l gives for the estimate (at least the smallest l that has a layout for iK:
-        above 4 for k > 121 only).  Its .size_estimate is {kmers, distinct, l, load}
-        (load: the expected one, distinct / 2^l).  Nothing is counted."""
-        if lines not in (2, 4):
-            raise ValueError("lines: 4 (FASTQ) or 2 (FASTA, one sequence line per record); wrapped FASTA has no sketch")
-        dev = {n: kw[n] for n in ("device", "hash_seed") if n in kw}
-        probe = cls._smallest(iK, iStorageBits, canonical=canonical, acgt_only=acgt_only, min_qual_char=min_qual_char, **dev)
-        l_min = probe.l
-        try:
-            if lines != 4:
-                probe.set_record_lines(lines)
-            regs, tot = probe.sketchKmers(text, precision=precision)
-        finally:
-            probe.close()
-        distinct = sketch_estimate(regs)
-        l = max(l_min, suggest_l(distinct, iK, load=load, precision=precision))
-        m = cls(l, iStorageBits, iK, canonical=canonical, acgt_only=acgt_only, min_qual_char=min_qual_char, **kw)
-        if lines != 4:
-            m.set_record_lines(lines)
-        m.size_estimate = {"kmers": tot["kmers"], "distinct": distinct, "l": l, "load": distinct / float(1 << l)}
-        return m
-
-    # --- counting only the k-mers seen twice ----------------------------------
-    def _prefilter_for(self, bits):
-        """A filter for pass 1: the map's, when it has one and bits is None; else a new one of `bits` (None: l + 6, so that
-        filter A takes the bytes of a one-limb table of 2^l slots; clamped to 12 .. 38)."""
-        if bits is None:
-            if self.prefilter_bits:
-                return
-            bits = min(max(self.l + 6, PREFILTER_BITS[0]), PREFILTER_BITS[-1])
-        self.createPrefilter(bits)
-
-    def createPrefilter(self, bits):
-        """A new, empty prefilter of 2^bits bits (tsx_hip_prefilter_create; 12 .. 38), disarmed; replaces the one the map has."""
-        _check(self._lib.tsx_hip_prefilter_create(self.handle, int(bits)))
-
-    def freePrefilter(self):
-        _check(self._lib.tsx_hip_prefilter_free(self.handle))
-
-    def prefilter(self, text, bits=None, chunk_bytes=0):
-        """Pass 1 of a count that keeps out the k-mers seen once (tsx_hip_prefilter_add_host): the k-mers of `text` -- those
-        the counting calls would count -- into the map's prefilter.  bits: a new filter of that size first; None: the
-        filter the map has (several texts accumulate), a new one of l + 6 bits when it has none.  Then armPrefilter()
-        and count the same input: every k-mer that occurs twice is in the table with its exact count, one that occurs once
-        is absent or, seldom, there with count 1.  The table is neither read nor written here."""
-        self._prefilter_for(bits)
-        b = bytes(text)
-        _check(self._lib.tsx_hip_prefilter_add_host(self.handle, b, len(b), int(chunk_bytes)))
-
-    def prefilterBgzf(self, gz, bits=None):
-        """The same for the image of a blocked gzip (BGZF) file, inflated on the device (tsx_hip_prefilter_add_bgzf_host)."""
-        self._prefilter_for(bits)
-        b = bytes(gz)
-        _check_bgzf(self._lib.tsx_hip_prefilter_add_bgzf_host(self.handle, b, len(b)))
-
-    def prefilterDevice(self, text_ptr, nbytes, bits=None, stream=None):
-        """tsx_hip_prefilter_add_device: pass 1 over a device text (16-byte aligned).  Queued, not waited for (bits given:
-        creating the filter waits for its zeroing first).  An armed count orders itself behind it, on any stream."""
-        self._prefilter_for(bits)
-        vp = ctypes.c_void_p
-        _check(self._lib.tsx_hip_prefilter_add_device(self.handle, vp(text_ptr), nbytes, vp(stream) if stream else None))
-
-    def armPrefilter(self, on=True):
-        """While on, countFastq / countFastqDevice / countFastqBgzf insert only the windows the prefilter has seen twice
-        (tsx_hip_prefilter_arm).  addKmers, load, combine and the read calls are not gated."""
-        _check(self._lib.tsx_hip_prefilter_arm(self.handle, 1 if on else 0))
-
-    @property
-    def prefilter_bits(self):
-        """The bits of the map's prefilter, 0 without one (tsx_hip_prefilter_bits: host state, no GPU call)."""
-        return int(self._lib.tsx_hip_prefilter_bits(self.handle))
-
-    @property
-    def prefilter_stats(self):
-        """{bits, seen, seen_again, admitted, skipped, set_bits_a, set_bits_b} (tsx_hip_prefilter_stats); all zero without
-        a filter.  Waits for the map's work and counts the set bits of both filters on the GPU: not for a hot loop."""
-        t = PrefilterTotals()
-        _check(self._lib.tsx_hip_prefilter_stats(self.handle, ctypes.byref(t)))
-        return t.as_dict()
-
-    def prefilterWords(self, which):
-        """The 64-bit words of filter 'a' (seen) or 'b' (seen again) as numpy uint64 (tsx_hip_prefilter_read)."""
-        if which not in ("a", "b"):
-            raise ValueError("which: 'a' or 'b', not %r" % (which,))
-        bits = self.prefilter_bits
-        if not bits:
-            raise TSXException(EINVAL, "the map has no prefilter")
-        out = np.zeros(1 << (bits - (6 if which == "a" else 8)), dtype=np.uint64)
-        _check(self._lib.tsx_hip_prefilter_read(self.handle, 0 if which == "a" else 1, _p(out), out.size))
-        return out
-
-    def countTwice(self, text, bits=None):
-        """Count `text` without its singletons: a new prefilter, pass 1, the armed count, disarmed again.  Returns
-        prefilter_stats."""
-        self.createPrefilter(min(max(self.l + 6, PREFILTER_BITS[0]), PREFILTER_BITS[-1]) if bits is None else bits)
-        self.prefilter(text)
-        self.armPrefilter(True)
-        try:
-            self.countFastq(text)
-        finally:
-            self.armPrefilter(False)
-        return self.prefilter_stats
-
-    def _pairs(self, call, text1, text2, out1, out2, singles, chunk_bytes):
-        """The common part of filterPairs / trimPairs: the four outputs opened (paths) or taken (fds), the call, the
-        totals as a dict."""
-        b1 = bytes(text1)
-        b2 = None if text2 is None else bytes(text2)
-        s1, s2 = singles
-        if b2 is None and (out2 is not None or s2 is not None):
-            raise ValueError("an interleaved text has one output and one singles output")
-        if out1 is None or (b2 is not None and out2 is None):
-            raise ValueError("the kept pairs need an output for each input text")
-        opened, fds = [], []
-        try:
-            for o in (out1, out2, s1, s2):
-                if o is None:
-                    fds.append(-1)
-                elif isinstance(o, int):
-                    fds.append(o)
-                else:
-                    fds.append(os.open(o, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644))
-                    opened.append(fds[-1])
-            io, tot = PairIO(*fds), PairTotals()
-            rc = call(b1, len(b1), b2, 0 if b2 is None else len(b2), ctypes.byref(io), int(chunk_bytes), ctypes.byref(tot))
-        finally:
-            for fd in opened:
-                os.close(fd)
-        _check(rc)
-        return tot.as_dict()
-
-    def filterPairs(self, text1, text2, out1, out2=None, singles=(None, None), pairs="both", check_names=False, lower=2,
-                    upper=None, min_in_range=0, fraction=1.0, invert=False, chunk_bytes=0):
-        """The read filter over mate pairs (tsx_hip_filter_pairs_host): record i of text1 and record i of text2 are
-        one pair (text2=None: text1 is interleaved).  pairs="both" keeps a pair when both mates pass the rule, "any"
-        when one does; kept mates go to out1 / out2 (interleaved: both to out1), a mate that passes alone under "both"
-        to its singles output (None drops it).  Outputs are paths (created or truncated) or open file descriptors.
-        check_names compares the mates' names (pair_name).  Returns the totals as a dict (PairTotals)."""
-        if pairs not in PAIR_MODES:
-            raise ValueError("pairs must be one of %s, not %r" % (sorted(PAIR_MODES), pairs))
-        rule = filter_rule(lower, upper, min_in_range, fraction, invert)
-        return self._pairs(lambda b1, n1, b2, n2, io, chunk, tot: self._lib.tsx_hip_filter_pairs_host(
-            self.handle, b1, n1, b2, n2, ctypes.byref(rule), PAIR_MODES[pairs], 1 if check_names else 0, io, chunk, tot),
-            text1, text2, out1, out2, singles, chunk_bytes)
-
-    def trimPairs(self, text1, text2, out1, out2=None, singles=(None, None), check_names=False, lower=2, upper=None,
-                  mode="longest", min_len=0, chunk_bytes=0):
-        """The trim over mate pairs (tsx_hip_trim_pairs_host): each mate is trimmed as trimReads trims it; a pair whose
-        mates both survive goes to out1 / out2, a lone survivor to its singles output.  Arguments and result as
-        filterPairs; the totals also count bases_in and bases_kept."""
-        rule = trim_rule(lower, upper, mode, min_len)
-        return self._pairs(lambda b1, n1, b2, n2, io, chunk, tot: self._lib.tsx_hip_trim_pairs_host(
-            self.handle, b1, n1, b2, n2, ctypes.byref(rule), 1 if check_names else 0, io, chunk, tot),
-            text1, text2, out1, out2, singles, chunk_bytes)
-
-    def trimSpansDevice(self, text_ptr, nbytes, spans_ptr, cap, rule, stream=None):
-        """tsx_hip_trim_spans_device: the kept spans of the records of a device text into a device buffer of cap spans.
-        Returns the record count (more than cap: TSXException ERANGE)."""
-        vp = ctypes.c_void_p
-        n = ctypes.c_size_t(0)
-        _check(self._lib.tsx_hip_trim_spans_device(self.handle, vp(text_ptr), nbytes, ctypes.byref(rule), vp(spans_ptr), cap,
-                                                   ctypes.byref(n), vp(stream) if stream else None))
-        return int(n.value)
-
-    def trimReadsDevice(self, text_ptr, nbytes, out_ptr, out_cap, rule, stream=None):
-        """tsx_hip_trim_reads_device: the trimmed records of a device text into a device buffer.  Returns the totals."""
-        vp = ctypes.c_void_p
-        tot = TrimTotals()
-        _check(self._lib.tsx_hip_trim_reads_device(self.handle, vp(text_ptr), nbytes, ctypes.byref(rule), vp(out_ptr), out_cap,
-                                                   ctypes.byref(tot), vp(stream) if stream else None))
-        return tot.as_dict()
-
-    def queryReadsDevice(self, text_ptr, nbytes, stats_ptr, cap, lower=1, upper=None, stream=None):
-        """tsx_hip_query_reads_device: stats of the records of a device text into a device buffer of cap records.
-        Returns the record count (more than cap: TSXException ERANGE)."""
-        vp = ctypes.c_void_p
-        n = ctypes.c_size_t(0)
-        _check(self._lib.tsx_hip_query_reads_device(self.handle, vp(text_ptr), nbytes, int(lower),
-                                                    (1 << 64) - 1 if upper is None else int(upper), vp(stats_ptr), cap,
-                                                    ctypes.byref(n), vp(stream) if stream else None))
-        return int(n.value)
-
-    def filterReadsDevice(self, text_ptr, nbytes, out_ptr, out_cap, rule, stream=None):
-        """tsx_hip_filter_reads_device: the passing records of a device text into a device buffer.  Returns (records
-        kept, bytes)."""
-        vp = ctypes.c_void_p
-        nb, kept = ctypes.c_size_t(0), ctypes.c_uint64(0)
-        _check(self._lib.tsx_hip_filter_reads_device(self.handle, vp(text_ptr), nbytes, ctypes.byref(rule), vp(out_ptr), out_cap,
-                                                     ctypes.byref(nb), ctypes.byref(kept), vp(stream) if stream else None))
-        return int(kept.value), int(nb.value)
-
-    def getKmerCountsDevice(self, kmers_ptr, n, out_ptr, stream=None):
-        vp = ctypes.c_void_p
-        _check(self._lib.tsx_hip_get_counts_device(self._h, vp(kmers_ptr), n, vp(out_ptr),
-                                                   vp(stream) if stream else None))
-
-    def print_stats(self):
-        s = self.stats()
-        import sys
-        print("Used fields: %d" % s["distinct"], file=sys.stderr)
-        print("Available fields: %d" % self.getMaxElements(), file=sys.stderr)
-        print("k=%d l=%d entry limbs=%d storage bits=%d" % (self.k, self.l, self.layout.entry_limbs,
-                                                          self.layout.count_bits), file=sys.stderr)
-        return s
-
-    # --- counting path -----------------------------------------------------
-    def countFastq(self, data):
-        """countKMers (main.cpp:104-218) for one FASTQ text held in host memory."""
-        b = bytes(data)
-        _check(self._lib.tsx_hip_count_fastq_host(self._h, b, len(b)))
-
-    def countFastqBgzf(self, gz):
-        """The same for the image of a blocked gzip (BGZF) file: members inflated on the device (tsx_inflate.h)."""
-        b = bytes(gz)
-        _check_bgzf(self._lib.tsx_hip_count_fastq_bgzf_host(self._h, b, len(b)))
-
-    def countFastqDevice(self, dev_ptr, nbytes, stream=None):
-        _check(self._lib.tsx_hip_count_fastq_device(self._h, ctypes.c_void_p(dev_ptr), nbytes,
-                                                    ctypes.c_void_p(stream) if stream else None))
-
-    def _check_fasta(self, rc):
-        if rc == EINVAL:   # a refusal: the library says which
-            raise TSXException(rc, self._lib.tsx_hip_last_error().decode() or self._lib.tsx_hip_strerror(rc).decode())
-        _check(rc)
-
-    def countFasta(self, data):
-        """Count a wrapped (multi-line) FASTA text held in host memory: the sequence lines of a record are joined on the
-        device (csrc/tsx_fasta.h), the k-mers are those of join_fasta(data) read as two-line records.  Works whatever
-        set_record_lines says and leaves it alone."""
-        b = bytes(data)
-        self._check_fasta(self._lib.tsx_hip_count_fasta_host(self.handle, b, len(b)))
-
-    def countFastaBgzf(self, gz):
-        """The same for the image of a blocked gzip (BGZF) file."""
-        b = bytes(gz)
-        self._check_fasta(self._lib.tsx_hip_count_fasta_bgzf_host(self.handle, b, len(b)))
-
-    def countFastaDevice(self, dev_ptr, nbytes, stream=None):
-        """The same for a text resident on the device (16-byte aligned); queued, call sync() before reading."""
-        self._check_fasta(self._lib.tsx_hip_count_fasta_device(self.handle, ctypes.c_void_p(dev_ptr), nbytes,
-                                                               ctypes.c_void_p(stream) if stream else None))
-
-    def clear(self):
-        _check(self._lib.tsx_hip_clear(self._h))
-
-    def sync(self):
-        _check(self._lib.tsx_hip_sync(self._h))
-
-    def stats(self):
-        s = Stats()
-        _check(self._lib.tsx_hip_get_stats(self._h, ctypes.byref(s)))
-        return s.as_dict()
-
-    def set_timing(self, enable=True):
-        _check(self._lib.tsx_hip_set_timing(self._h, 1 if enable else 0))
-
-    def get_timing(self):
-        """(line-pass ms, count_fastq_kernel ms, partition+build ms, pieces) since the last call."""
-        a, b, c, n = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_uint64(0)
-        _check(self._lib.tsx_hip_get_timing(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
-                                            ctypes.byref(n)))
-        return a.value, b.value, c.value, int(n.value)
-
-    def get_stage_timing(self):
-        """({stage: ms}, pieces) since the last call; stages: line, scan, level1, level2, build, gap, post
-        (gap = scan end to partition start: the owner split and the key exchange of a sharded run;
-        post = overflow queues + deferred list, inserted after the build kernel)."""
-        ms, n = (ctypes.c_double * 7)(), ctypes.c_uint64(0)
-        _check(self._lib.tsx_hip_get_stage_timing(self._h, ms, ctypes.byref(n)))
-        return dict(zip(("line", "scan", "level1", "level2", "build", "gap", "post"), [float(x) for x in ms])), int(n.value)
-
-    def set_record_lines(self, lines):
-        """4 = FASTQ records (default), 2 = FASTA as FASTXreader<FASTAEntry> reads it (tsx_hip_set_record_lines)."""
-        if lines != 4 and self.base_rule[1] is not None:
-            raise ValueError("min_qual_char needs FASTQ records: a FASTA text has no quality line")
-        _check(self._lib.tsx_hip_set_record_lines(self._h, lines))
-        self._lines = lines
-
-    def set_path(self, path):
-        """0 auto, 1 atomic, 2 partitioned (tsx_hip_set_path)."""
-        _check(self._lib.tsx_hip_set_path(self._h, {"auto": 0, "atomic": 1, "partitioned": 2}.get(path, path)))
-
-    # --- mapping -------------------------------------------------------------
-    def hash_rows(self):
-        out = np.zeros((2 * self.k, self.wk), dtype=np.uint64)
-        _check(self._lib.tsx_hip_hash_rows(self._h, _p(out)))
-        return out
-
-    def hash_apply(self, kmer):
-        a = np.ascontiguousarray(kmer, dtype=np.uint64)
-        out = np.zeros(self.wk, dtype=np.uint64)
-        _check(self._lib.tsx_hip_hash_apply(self._h, _p(a), _p(out)))
-        return out
-
-    def hash_invert(self, key):
-        a = np.ascontiguousarray(key, dtype=np.uint64)
-        out = np.zeros(self.wk, dtype=np.uint64)
-        _check(self._lib.tsx_hip_hash_invert(self._h, _p(a), _p(out)))
-        return out
-
-    def owner(self, kmer, nranks):
-        a = np.ascontiguousarray(kmer, dtype=np.uint64)
-        return int(self._lib.tsx_hip_owner_host(self._h, _p(a), nranks))
-
-    def _as_kmers(self, items):
-        out = np.zeros((len(items), self.wk), dtype=np.uint64)
-        for i, it in enumerate(items):
-            out[i] = encode(it, self.k) if isinstance(it, (str, bytes)) else np.asarray(it, dtype=np.uint64)
-        return out
-
-
-def _write_counts(fn, handle, check, path, lower, upper, chunk_bytes):
-    """tsx_hip_write_counts_host / tsx_hip_group_write_counts_host into the file `path` (created or truncated)."""
-    upper = (1 << 64) - 1 if upper is None else int(upper)
-    lines, nbytes = ctypes.c_uint64(0), ctypes.c_uint64(0)
-    fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
-    try:
-        rc = fn(handle, fd, int(lower), upper, int(chunk_bytes), ctypes.byref(lines), ctypes.byref(nbytes))
-    finally:
-        os.close(fd)
-    check(rc)
-    return int(lines.value), int(nbytes.value)
-
-
-def database_info(path_or_fd):
-    """The header of a k-mer database file as a dict (tsx_hip_db_read_info; no GPU needed)."""
-    info = DbInfo()
-    own = not isinstance(path_or_fd, int)
-    fd = os.open(path_or_fd, os.O_RDONLY) if own else path_or_fd
-    try:
-        rc = lib().tsx_hip_db_read_info(fd, ctypes.byref(info))
-    finally:
-        if own:
-            os.close(fd)
-    _check(rc)
-    return info.as_dict()
-
-
-def cut_records(text, parts, lines_per_record=4):
-    """Where the multi-GPU host cuts a text: parts + 1 offsets, every one a record boundary of the reference's reader."""
-    b = bytes(text)
-    out = (ctypes.c_size_t * (parts + 1))()
-    _check(lib().tsx_hip_cut_records_host(b, len(b), parts, lines_per_record, out))
-    return [int(x) for x in out]
-
-
-class TSXHashMapHIPGroup:
-    """One table per GPU of this node behind one object (tsx_hip_group_*, csrc/tsx_multi.cpp): countFastq cuts the text
-    into record shards, every GPU counts its own, the tables are merged (comm "rccl": RCCL, one GPU per rank; "copy":
-    device copies, ranks may share a GPU), lookups go to the owner of each k-mer."""
-
-    def __init__(self, gpus, iL, iStorageBits, iK, hash_seed=1, devices=None, comm="rccl", exchange="merge",
-                 canonical=False, acgt_only=False, min_qual_char=None):
-        min_qual_code(min_qual_char)
-        self._lib = lib()
-        self._h = ctypes.c_void_p()
-        dv = (ctypes.c_int * gpus)(*devices) if devices is not None else None
-        rc = self._lib.tsx_hip_group_create(ctypes.byref(self._h), gpus, dv, iK, iL, iStorageBits, 0, hash_seed,
-                                            {"rccl": 0, "copy": 1}[comm])
-        self._check(rc)
-        self.k, self.wk, self.gpus = iK, key_limbs(iK), gpus
-        if canonical:   # (the minimizer exchange refuses it)
-            self._check(self._lib.tsx_hip_group_set_canonical(self._h, 1))
-        self.canonical = bool(canonical)
-        self._lines = 4
-        self._rule = (False, None)
-        if acgt_only or min_qual_char:   # (the minimizer exchange refuses it)
-            self.set_base_rule(acgt_only, min_qual_char)
-        if exchange != "merge":      # "mini": the minimizer exchange (20 <= k <= 32), nothing is merged afterwards
-            self._check(self._lib.tsx_hip_group_set_exchange(self._h, {"merge": 0, "mini": 1}[exchange]))
-        self.exchange = exchange
-
-    @property
-    def base_rule(self):
-        """(acgt_only, min_qual_char) on every rank's table (see TSXHashMapHIP.set_base_rule)."""
-        return self._rule
-
-    def set_base_rule(self, acgt_only=False, min_qual_char=None):
-        q = min_qual_code(min_qual_char)
-        if q and self._lines != 4:
-            raise ValueError("min_qual_char needs FASTQ records: a FASTA text has no quality line")
-        self._check(self._lib.tsx_hip_group_set_base_rule(self._h, 1 if acgt_only else 0, q))
-        self._rule = (bool(acgt_only), chr(q) if q else None)
-
-    def _check(self, rc):
-        if rc != OK:
-            raise TSXException(rc, self._lib.tsx_hip_strerror(rc).decode() + " (" + self._lib.tsx_hip_group_last_error().decode() + ")")
-
-    def close(self):
-        if self._h:
-            self._lib.tsx_hip_group_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def comm_name(self):
-        return self._lib.tsx_hip_group_comm_name(self._h).decode()
-
-    def set_record_lines(self, lines):
-        if lines != 4 and self._rule[1] is not None:
-            raise ValueError("min_qual_char needs FASTQ records: a FASTA text has no quality line")
-        self._check(self._lib.tsx_hip_group_set_record_lines(self._h, lines))
-        self._lines = lines
-
-    def clear(self):
-        self._check(self._lib.tsx_hip_group_clear(self._h))
-
-    def countFastq(self, data):
-        b = bytes(data)
-        self._check(self._lib.tsx_hip_group_count_fastq_host(self._h, b, len(b)))
-
-    def getKmerCounts(self, kmers):
-        k = np.ascontiguousarray(np.asarray(kmers, dtype=np.uint64).reshape(-1, self.wk))
-        out = np.zeros(k.shape[0], dtype=np.uint64)
-        self._check(self._lib.tsx_hip_group_get_counts_host(self._h, _p(k), k.shape[0], _p(out)))
-        return out
-
-    def stats(self):
-        s = Stats()
-        self._check(self._lib.tsx_hip_group_get_stats(self._h, ctypes.byref(s)))
-        return s.as_dict()
-
-    def getCountHistogram(self, nbins=10002):
-        """The abundance histogram of the whole group (the sum of the ranks'; see TSXHashMapHIP.getCountHistogram)."""
-        out = np.zeros(nbins, dtype=np.uint64)
-        self._check(self._lib.tsx_hip_group_histogram_host(self._h, _p(out), nbins))
-        return out
-
-    def writeCounts(self, path, lower=1, upper=None, chunk_bytes=0):
-        """Every k-mer of the group in [lower, upper] as "kmer<TAB>count" lines, rank after rank.  Returns (lines, bytes)."""
-        return _write_counts(self._lib.tsx_hip_group_write_counts_host, self._h, self._check, path, lower, upper, chunk_bytes)
-
-    def rank_stats(self, rank):
-        s = Stats()
-        _check(self._lib.tsx_hip_get_stats(self._lib.tsx_hip_group_map(self._h, rank), ctypes.byref(s)))
-        return s.as_dict()
-
-    def exchanged_entries(self):
-        return int(self._lib.tsx_hip_group_exchanged_entries(self._h))
-
-    def exchange_rounds(self):
-        """Rounds of the last countFastq: pieces x shares of the minimizer exchange (TSX_HIP_MZ_PIECE / TSX_HIP_MZ_SHARE
-        shrink both), 0 for the merge."""
-        return int(self._lib.tsx_hip_group_exchange_rounds(self._h))
-
-
-def join_fasta(text):
-    """The canonical two-line form of a wrapped (multi-line) FASTA text, on the CPU: the statement of the record rules
-    that countFasta / unwrap_fasta follow.  The text is split at b"\\n" and empty lines are dropped; a line whose first
-    byte is b">" is a header; the sequence of a record is every other line up to the next header (or the end) joined in
-    order; lines in front of the first header are a record of their own; a record without a sequence byte vanishes; a
-    b">" elsewhere in a line and b"\\r" are ordinary bytes.  The result is b">\\n" + sequence + b"\\n" per record:
-    header text is dropped (nothing downstream of counting reads it)."""
-    out, seq = [], []
-    for line in bytes(text).split(b"\n"):
-        if not line:
-            continue
-        if line[:1] == b">":
-            if seq:
-                out.append(b">\n" + b"".join(seq) + b"\n")
-            seq = []
-        else:
-            seq.append(line)
-    if seq:
-        out.append(b">\n" + b"".join(seq) + b"\n")
-    return b"".join(out)
-
-
-def unwrap_fasta(text, device=0):
-    """join_fasta(text) computed on the GPU (tsx_hip_unwrap_fasta_host: the whole text as one piece)."""
-    b = bytes(text)
-    cap = len(b) + 2
-    out = ctypes.create_string_buffer(max(cap, 1))
-    got = ctypes.c_size_t(0)
-    _check(lib().tsx_hip_unwrap_fasta_host(device, b, len(b), out, cap, ctypes.byref(got)))
-    return out.raw[:got.value]
-
-
-# ---- sequence queries: the definitions, on the CPU (numpy / stdlib only) ------------------------------------------------
-SEQ_NAME_MAX = 255
-SEQ_STATS_DTYPE = np.dtype([("length", np.uint64), ("kmers", np.uint64), ("present", np.uint64), ("min_count", np.uint64),
-                            ("sum_count", np.uint64)])
-SEQ_INTERVAL_DTYPE = np.dtype([("seq", np.uint64), ("start", np.uint64), ("end", np.uint64)])
-_BASE_CODE = bytes(b"ACGT"[((b >> 1) ^ (b >> 2)) & 3] for b in range(256))   # what the table sees of a byte
-_ACGT = frozenset(b"ACGTacgt")
-_COMP_B = bytes.maketrans(b"ACGT", b"TGCA")
-
-
-def fasta_records(text):
-    """[(name, sequence)] of a wrapped FASTA text, with the record rules of join_fasta: split at b"\\n", empty lines
-    dropped, a line whose first byte is b">" is a header, a record's sequence is every other line up to the next header
-    joined, lines in front of the first header are a record with the empty name, a record without a sequence byte
-    vanishes, b"\\r" and an inner b">" are ordinary bytes.  The name is the header behind b">" up to the first space or
-    tab, cut to SEQ_NAME_MAX bytes.  b"".join(b">\\n" + s + b"\\n" for _, s in fasta_records(t)) == join_fasta(t)."""
-    out, name, seq = [], b"", []
-    for line in bytes(text).split(b"\n"):
-        if not line:
-            continue
-        if line[:1] == b">":
-            if seq:
-                out.append((name, b"".join(seq)))
-            seq = []
-            h = line[1:]
-            cut = min([i for i in (h.find(b" "), h.find(b"\t")) if i >= 0] or [len(h)])
-            name = h[:min(cut, SEQ_NAME_MAX)]
-        else:
-            seq.append(line)
-    if seq:
-        out.append((name, b"".join(seq)))
-    return out
-
-
-def _seq_table(D, canonical):
-    """D ({k-mer bytes: count}) with its keys as the table holds them: folded through base_code, and onto the smaller
-    strand when canonical."""
-    T = {}
-    for x, c in D.items():
-        x = bytes(x).translate(_BASE_CODE)
-        if canonical:
-            x = min(x, x[::-1].translate(_COMP_B))
-        T[x] = T.get(x, 0) + int(c)
-    return T
-
-
-def _seq_window_counts(seq, T, k, canonical, acgt_only):
-    """Per start position of `seq`: the count of its window in T (_seq_table), or None where the base rule drops the
-    window."""
-    s = bytes(seq).translate(_BASE_CODE)
-    bad = [0]
-    for b in bytes(seq):
-        bad.append(bad[-1] + (1 if (acgt_only and b not in _ACGT) else 0))
-    out = []
-    for i in range(len(s) - k + 1):
-        if bad[i + k] - bad[i]:
-            out.append(None)
-            continue
-        x = s[i:i + k]
-        if canonical:
-            x = min(x, x[::-1].translate(_COMP_B))
-        out.append(T.get(x, 0))
-    return out
-
-
-def sequence_stats(records, D, k, lower=1, upper=None, canonical=False, acgt_only=False):
-    """Per record of fasta_records: (length, kmers, present, min_count, sum_count).  kmers: the windows that are k-mers
-    under the table's base rule (as queryReads); present: those whose count in D lies in lower..upper; min_count and
-    sum_count as in tsx_hip_read_stats (sum modulo 2^64, min 0 without k-mers)."""
-    upper = (1 << 64) - 1 if upper is None else int(upper)
-    out, tab = [], _seq_table(D, canonical)
-    for _, seq in records:
-        cs = [c for c in _seq_window_counts(seq, tab, k, canonical, acgt_only) if c is not None]
-        out.append((len(seq), len(cs), sum(lower <= c <= upper for c in cs), min(cs) if cs else 0, sum(cs) % (1 << 64)))
-    return out
-
-
-def missing_intervals(records, D, k, lower=1, upper=None, canonical=False, acgt_only=False):
-    """[(seq_index, start, end)]: every maximal run of consecutive start positions s..e whose windows are k-mers with a
-    count outside lower..upper, as the half-open base interval [s, e + k) of the joined sequence.  A window the base
-    rule drops is neither present nor missing and ends a run.  Ordered by sequence, then start."""
-    upper = (1 << 64) - 1 if upper is None else int(upper)
-    out, tab = [], _seq_table(D, canonical)
-    for r, (_, seq) in enumerate(records):
-        start = None
-        cs = _seq_window_counts(seq, tab, k, canonical, acgt_only)
-        for i, c in enumerate(cs + [None]):
-            miss = c is not None and not (lower <= c <= upper)
-            if miss and start is None:
-                start = i
-            elif not miss and start is not None:
-                out.append((r, start, i - 1 + k))
-                start = None
-    return out
-
-
-def kmer_qv(present, kmers, k):
-    """Merqury's consensus quality: -10 log10(1 - (present / kmers)^(1 / k)).  None without k-mers, inf when all are
-    present."""
-    import math
-    if kmers == 0:
-        return None
-    if present == kmers:
-        return math.inf
-    if present == 0:
-        return 0.0
-    return -10.0 * math.log10(1.0 - (float(present) / float(kmers)) ** (1.0 / k))
-
-
-def bgzf_index(gz):
-    """(members, text bytes) of a BGZF image, or None when the buffer is not BGZF."""
-    b = bytes(gz)
-    nm, nb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    rc = lib().tsx_hip_bgzf_index_host(b, len(b), ctypes.byref(nm), ctypes.byref(nb))
-    return (nm.value, nb.value) if rc == OK else None
-
-
-def bgzf_inflate(gz, device=0):
-    """Inflate a BGZF image on the device and return the text (tests, tools)."""
-    b = bytes(gz)
-    ix = bgzf_index(b)
-    if ix is None:
-        raise TSXException(EINVAL, "not a BGZF image")
-    out = ctypes.create_string_buffer(max(ix[1], 1))
-    got = ctypes.c_size_t(0)
-    _check_bgzf(lib().tsx_hip_inflate_bgzf_host(device, b, len(b), out, ix[1], ctypes.byref(got)))
-    return out.raw[:got.value]
-
-
-def bgzf_compress(data, level=6, block=65280):
-    """BGZF writer (the layout `bgzip` produces: SAM specification section 4.1) -- for tests and tools; zlib does
-    the deflate, one gzip member with a BC extra field per `block` bytes, the empty end-of-file member last."""
-    import struct
-    import zlib
-    out = bytearray()
-    data = bytes(data)
-    for i in range(0, len(data), block):
-        chunk = data[i:i + block]
-        c = zlib.compressobj(level, zlib.DEFLATED, -15)
-        raw = c.compress(chunk) + c.flush()
-        assert len(raw) + 26 <= 65536
-        out += (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, len(raw) + 25)
-                + raw + struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk)))
-    out += bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
-    return bytes(out)
-
-
-def synth_sizes(seed, first_read, n_reads, k, want_polya=False):
-    """Byte and k-mer totals of tsx_hip_synth_fastq_device without generating."""
-    nb, nk, npa = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
-    _check(lib().tsx_hip_synth_fastq_device(seed, first_read, n_reads, k, None, 0, ctypes.byref(nb),
-                                            ctypes.byref(nk), ctypes.byref(npa) if want_polya else None, 0, None))
-    return int(nb.value), int(nk.value), int(npa.value)
-
-
-def synth_fastq_device(seed, first_read, n_reads, k, dev_ptr, cap, device=0, stream=None):
-    nb, nk = ctypes.c_uint64(0), ctypes.c_uint64(0)
-    _check(lib().tsx_hip_synth_fastq_device(seed, first_read, n_reads, k, ctypes.c_void_p(dev_ptr), cap,
-                                            ctypes.byref(nb), ctypes.byref(nk), None, device,
-                                            ctypes.c_void_p(stream) if stream else None))
-    return int(nb.value), int(nk.value)
-
-
-def synth_zipf_device(seed, n_reads, read_len, thr, dev_ptr=None, cap=0, device=0, stream=None):
-    """Zipf-skewed reads straight into device memory (tsx_hip_synth_zipf_device; thr from synth.zipf_thresholds).
-    Returns the byte count; dev_ptr None = sizing call."""
-    thr = np.ascontiguousarray(thr, dtype=np.uint64)
-    nb = ctypes.c_uint64(0)
-    _check(lib().tsx_hip_synth_zipf_device(seed, n_reads, read_len, len(thr), _p(thr), ctypes.c_void_p(dev_ptr) if dev_ptr else None,
-                                           cap, ctypes.byref(nb), device, ctypes.c_void_p(stream) if stream else None))
-    return int(nb.value)
+import ctypes  # noqa: F401 -- ctypes, os and np stay reachable as attributes of the package (tests use T.ctypes)
+import os  # noqa: F401
+
+import numpy as np  # noqa: F401
+
+from ._abi import (BIN_A, BIN_AMBIGUOUS, BIN_B, BIN_NAMES, BIN_NONE, BIN_STATS_DTYPE, COMBINE_COUNTS, COMBINE_OPS, EFORMAT,
+                   EFULL, EHIP, EINVAL, EIO, ELOCK, ENODEVICE, ENOMEM, EOVERFLOW, EPAIR, ERANGE, HEADER_PATH, HET_MODES,
+                   HET_PAIR_DTYPE, JOINT_MAX_CELLS, LIB_PATH, NO_KMER, NORMALIZE_ROUND, OK, PAIR_MODES, PREFILTER_BITS,
+                   READ_MEDIAN_DTYPE, READ_STATS_DTYPE, SEQ_INTERVAL_DTYPE, SEQ_NAME_MAX, SEQ_STATS_DTYPE, SKETCH_PRECISIONS,
+                   TRIM_MODES, TRIM_SPAN_DTYPE, BinIO, BinRule, BinTotals, CombineRule, CombineStats, DbInfo, FilterRule,
+                   HetRule, HetStats, Layout, Level1Shape, MedianRule, NormalizeRule, NormalizeTotals, PairIO, PairTotals,
+                   PrefilterTotals, SketchTotals, Stats, TrimRule, TrimTotals, TSXException, _check, _p, bin_rule, build,
+                   canonical, combine_rule, decode, encode, encode_many, filter_rule, het_pair_dtype, het_rule, key_limbs, lib,
+                   median_rule, min_qual_code, normalize_rule, revcomp, trim_rule)
+from .group import TSXHashMapHIPGroup
+from .models import (bin_class, fasta_records, het_histogram, het_pairs, join_fasta, joint_histogram, kmer_qv, median_count,
+                     merge_sketches, missing_intervals, pair_name, prefilter_masks, sequence_stats, sketch_registers)
+from .table import TSXHashMapHIP, sketch_estimate, suggest_l
+from .textio import (bgzf_compress, bgzf_index, bgzf_inflate, cut_records, database_info, synth_fastq_device, synth_sizes,
+                     synth_zipf_device, unwrap_fasta)
