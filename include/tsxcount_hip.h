@@ -473,6 +473,36 @@ void tsx_hip_seq_result_free(tsx_hip_seq_result *res);
 int tsx_hip_seq_write_stats(const tsx_hip_seq_result *res, int k, int fd);
 int tsx_hip_seq_write_missing(const tsx_hip_seq_result *res, int fd);
 /*
+ * Coverage tracks (csrc/tsx_track.h; no reference counterpart -- KAT sect, the copy-number track next to Merqury's
+ * spectra-cn): the k-mer counts of every sequence in bins along it.  Sequences, names, length, k-mers, c(x), lower..upper
+ * and "present" are those of tsx_hip_seq_stats_*.  A sequence of length L has ceil(L / window) bins (none for L = 0); bin
+ * b covers the START positions [b * window, min((b + 1) * window, L)) of the joined sequence.  Per bin (tsx_hip_seq_bin):
+ *   kmers      start positions of the bin whose window is a k-mer (the last k - 1 of a sequence never are)
+ *   present    those with lower <= c <= upper
+ *   min_count, max_count  the smallest and the largest c, both 0 when kmers = 0;  sum_count  the sum of c mod 2^64
+ * A sequence's bins sum to its tsx_hip_seq_stats row.  The track calls fill the stats and the names as the _stats_ calls
+ * do, and no intervals; the result does not depend on where the pieces of the text are cut.  Refused with
+ * TSX_HIP_EINVAL (tsx_hip_last_error says which): what the _stats_ calls refuse, and a window outside 64 .. 2^32.
+ *   tsx_hip_seq_result_bins    the bins of all sequences back to back; those of sequence i are [first[i], first[i + 1])
+ *                              (count + 1 offsets).  Returns their number; a result without a track: 0 and NULL.
+ *   tsx_hip_seq_result_window  the window of the result's track, 0 for a result without one.
+ *   tsx_hip_seq_write_track    one line per bin to fd: name, start, end, kmers, present, min, max, mean, tab-separated;
+ *                              mean = sum / kmers as %.4f, "NA" when kmers = 0; an empty name is written "*".  A result
+ *                              without a track: TSX_HIP_EINVAL; a failed write: TSX_HIP_EIO.
+ */
+typedef struct tsx_hip_seq_bin {
+    uint64_t kmers, present, min_count, max_count, sum_count;
+} tsx_hip_seq_bin;
+int tsx_hip_seq_track_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, uint64_t upper, uint64_t window,
+                           size_t chunk_bytes, tsx_hip_seq_result **res);
+int tsx_hip_seq_track_bgzf_host(tsx_hip_map *m, const void *gz, size_t n, uint64_t lower, uint64_t upper, uint64_t window,
+                                tsx_hip_seq_result **res);
+int tsx_hip_seq_track_device(tsx_hip_map *m, const void *dev_text, size_t n, uint64_t lower, uint64_t upper, uint64_t window,
+                             tsx_hip_seq_result **res, void *stream);
+size_t tsx_hip_seq_result_bins(const tsx_hip_seq_result *res, const tsx_hip_seq_bin **bins, const uint64_t **first);
+uint64_t tsx_hip_seq_result_window(const tsx_hip_seq_result *res);
+int tsx_hip_seq_write_track(const tsx_hip_seq_result *res, int fd);
+/*
  * Read trimming (csrc/tsx_trim.h; no reference counterpart -- khmer `filter-abund` / `trim-low-abund`, Quake, Lighter):
  * keep of every record the stretch of its sequence whose k-mers are trusted.  Records, lines, k-mers and c(x) are those
  * of tsx_hip_query_reads_*, and the table's base rule (tsx_hip_set_base_rule) decides which windows are k-mers at all.

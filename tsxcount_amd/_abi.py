@@ -421,6 +421,12 @@ def _signatures():
         "tsx_hip_seq_result_free": (None, [vp]),
         "tsx_hip_seq_write_stats": (ci, [vp, ci, ci]),
         "tsx_hip_seq_write_missing": (ci, [vp, ci]),
+        "tsx_hip_seq_track_host": (ci, [vp, ccp, sz, u64, u64, u64, sz, vpp]),
+        "tsx_hip_seq_track_bgzf_host": (ci, [vp, vp, sz, u64, u64, u64, vpp]),
+        "tsx_hip_seq_track_device": (ci, [vp, vp, sz, u64, u64, u64, vpp, vp]),
+        "tsx_hip_seq_result_bins": (sz, [vp, vpp, vpp]),
+        "tsx_hip_seq_result_window": (u64, [vp]),
+        "tsx_hip_seq_write_track": (ci, [vp, ci]),
     }
 
 

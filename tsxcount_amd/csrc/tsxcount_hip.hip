@@ -16,6 +16,7 @@
 #include "tsx_bin.h"
 #include "tsx_fasta.h"
 #include "tsx_seq.h"
+#include "tsx_track.h"
 #include "tsx_trim.h"
 #include "tsx_normalize.h"
 #include "tsx_sketch.h"
@@ -4782,6 +4783,9 @@ struct tsx_hip_seq_result {
     std::string names;
     std::vector<uint64_t> name_off{0};
     std::vector<tsx_hip_seq_interval> iv;
+    uint64_t window = 0;                 // the track's window; 0: no track
+    std::vector<tsx_hip_seq_bin> bins;   // the bins of sequence i: [first[i], first[i + 1])
+    std::vector<uint64_t> first{0};
 };
 
 static const size_t SEQ_NAME_BATCH = 65536;   // headers described per launch of seq_names_kernel
@@ -4801,6 +4805,7 @@ struct SeqRun {
     hipStream_t st;
     uint64_t lower, upper;
     bool want_missing;
+    uint64_t window;   // > 0: the track call -- seq_track_kernel in place of seq_stats_kernel, the stats out of the bins
     tsx_hip_seq_result *res;
     uint32_t where = 0, q = 0, nb = 0;
     std::string pend;
@@ -4810,7 +4815,8 @@ struct SeqRun {
     std::vector<SeqName> ent;
     std::vector<tsx_hip_seq_stats> rows_h;
     std::vector<tsx_hip_seq_interval> frag_h;
-    DevBuf<unsigned long long> rows, frag;
+    std::vector<tsx_hip_seq_bin> bins_h;
+    DevBuf<unsigned long long> rows, frag, bins, row_of;
     DevBuf<uint32_t> hpos;
     DevBuf<SeqName> hent;
     // words of its own, on the device and pinned: 0 = fragments of a launch, 1 = headers of a piece, 2 and 3 = the three
@@ -4823,8 +4829,8 @@ struct SeqRun {
         TSX_TRY(h_words.alloc(4 * sizeof(unsigned long long)));
         return p.init();
     }
-    SeqRun(tsx_hip_map *mm, hipStream_t s, uint64_t lo, uint64_t up, bool miss, tsx_hip_seq_result *r)
-        : m(mm), st(s), lower(lo), upper(up), want_missing(miss), res(r), p(s) {}
+    SeqRun(tsx_hip_map *mm, hipStream_t s, uint64_t lo, uint64_t up, bool miss, uint64_t win, tsx_hip_seq_result *r)
+        : m(mm), st(s), lower(lo), upper(up), want_missing(miss), window(win), res(r), p(s) { r->window = win; }
 };
 
 static int seq_fail(const char *why) { g_last_error = why; return TSX_HIP_EINVAL; }
@@ -4921,9 +4927,91 @@ static void seq_merge_fragments(SeqRun &R) {
     R.frag_h.clear();
 }
 
+// ---- coverage tracks: the bins of a piece (tsx_track.h) ------------------------------------------------------------
+static uint64_t track_rows_of(uint64_t off, uint64_t len, uint64_t W) { return (off + len + W - 1) / W - off / W; }
+
+// The track kernel over the unwrapped piece two[0, ub) of nrec records: the rows per record and their prefix, the zeroed
+// bin rows (bounded by ub / W + nrec + 1 without a wait), the kernel, the finalize.  Queued, not waited for.
+static int track_launch(SeqRun &R, const uint8_t *two, uint64_t ub, uint64_t nrec, uint64_t row0_off) {
+    tsx_hip_map *m = R.m;
+    hipStream_t st = R.st;
+    const uint64_t W = R.window, cap = ub / W + nrec + 1;
+    const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    TSX_TRY(grow(st, R.row_of, (nk + nchunks + 16) * sizeof(unsigned long long)));
+    TSX_TRY(grow(st, R.bins, cap * sizeof(tsx_hip_seq_bin)));
+    HIP_TRY(hipMemsetAsync(R.bins.get(), 0, cap * sizeof(tsx_hip_seq_bin), st));
+    const unsigned long long *span = R.p.rspan.get(), *d_base = R.p.info.get() + 4;
+    unsigned long long *row_of = R.row_of.get(), *chunk = row_of + nk, *d_total = R.words.get();
+    hipLaunchKernelGGL(track_rows_kernel, dim3(grid_for(m, nk, 8)), dim3(NT), 0, st, span, nrec, W, row0_off, row_of);
+    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)row_of, nk, chunk);
+    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, d_total);
+    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, row_of, nk, (const unsigned long long *)chunk);
+    HIP_TRY(hipGetLastError());
+    const uint64_t ntiles = (ub + TILE - 1) / TILE;
+    const size_t lut_bytes = m->lut.size() * 8;
+    const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 4);
+    const uint32_t magic = (uint32_t)(((uint64_t)1 << 32) / W + 1);
+    DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((seq_track_kernel<WKV, CANV, BRV>), dim3(grid), dim3(NT), lut_bytes,
+                                                        st, m->p, two, ub, (const uint32_t *)m->d_tile.get(), ntiles, d_base, R.lower,
+                                                        R.upper, R.bins.get(), cap, nrec, span, (const unsigned long long *)row_of, W,
+                                                        magic, row0_off, row0_off / W))));
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(track_finalize_kernel, dim3(grid_for(m, cap, 8)), dim3(NT), 0, st, R.bins.get(), (const unsigned long long *)d_total, cap);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(R.h_words.get(), d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    return TSX_HIP_OK;
+}
+
+static void track_combine(tsx_hip_seq_bin &a, const tsx_hip_seq_bin &b) {
+    if (b.kmers) a.min_count = a.kmers ? std::min(a.min_count, b.min_count) : b.min_count;
+    a.max_count = std::max(a.max_count, b.max_count);
+    a.kmers += b.kmers; a.present += b.present; a.sum_count += b.sum_count;
+}
+
+// Behind the piece's wait (R.rows_h holds the lengths, the device total is in R.h_words): the bin rows of the piece come
+// back, every record's stats are summed out of its rows, and the rows join the result -- record 0 of a piece that goes on
+// with the open sequence lands on that sequence's bins from bin row0_off / W on (rows it has already are combined, the
+// carried bases start in them), every other record appends.
+static int track_merge(SeqRun &R, uint64_t nrec, bool q_in, uint64_t carried, uint64_t row0_off) {
+    const uint64_t W = R.window;
+    tsx_hip_seq_result &res = *R.res;
+    uint64_t total = 0;
+    for (uint64_t r = 0; r < nrec; ++r) total += track_rows_of(r == 0 ? row0_off : 0, R.rows_h[r].length + (r == 0 ? carried : 0), W);
+    if (total != *R.h_words.get() || total > R.bins.cap() / sizeof(tsx_hip_seq_bin)) {
+        g_last_error = "sequence track: the host and the device disagree on the bin rows of a piece";
+        return TSX_HIP_EHIP;
+    }
+    R.bins_h.resize(total);
+    if (total) HIP_TRY(hipMemcpy(R.bins_h.data(), R.bins.get(), total * sizeof(tsx_hip_seq_bin), hipMemcpyDeviceToHost));
+    size_t at = 0;
+    for (uint64_t r = 0; r < nrec; ++r) {
+        const uint64_t off = r == 0 ? row0_off : 0;
+        const uint64_t rows = track_rows_of(off, R.rows_h[r].length + (r == 0 ? carried : 0), W);
+        tsx_hip_seq_bin sum = {0, 0, 0, 0, 0};
+        for (uint64_t i = 0; i < rows; ++i) track_combine(sum, R.bins_h[at + i]);
+        tsx_hip_seq_stats &s = R.rows_h[r];
+        s.kmers = sum.kmers; s.present = sum.present; s.min_count = sum.min_count; s.sum_count = sum.sum_count;
+        if (r == 0 && q_in) {
+            const size_t seq0 = (size_t)res.first[res.first.size() - 2];   // where the open sequence's bins start
+            for (uint64_t i = 0; i < rows; ++i) {
+                const size_t g = seq0 + (size_t)(off / W + i);
+                if (g < res.bins.size()) track_combine(res.bins[g], R.bins_h[at + i]);
+                else res.bins.push_back(R.bins_h[at + i]);
+            }
+            res.first.back() = res.bins.size();
+        } else {
+            res.bins.insert(res.bins.end(), R.bins_h.begin() + at, R.bins_h.begin() + at + rows);
+            res.first.push_back(res.bins.size());
+        }
+        at += rows;
+    }
+    return TSX_HIP_OK;
+}
+
 // One piece of the wrapped text, behind the carry: names, the unwrap, the record scan of the two-line text (the one wait
 // for its record count), the stats kernel (per fragment-buffer's worth of tiles when the missing runs are wanted), and
-// the rows of the piece merged into the result.
+// the rows of the piece merged into the result.  A track call (R.window) runs the track kernel in place of the stats kernel
+// and fills the piece's rows from its bins (track_launch, track_merge).
 static int seq_piece(SeqRun &R, const uint8_t *d_text, uint64_t n) {
     if (n == 0) return TSX_HIP_OK;
     tsx_hip_map *m = R.m;
@@ -4958,7 +5046,8 @@ static int seq_piece(SeqRun &R, const uint8_t *d_text, uint64_t n) {
     const size_t frag_cap = R.want_missing ? seq_frag_cap() : 0;
     if (R.want_missing) TSX_TRY(grow(st, R.frag, frag_cap * sizeof(tsx_hip_seq_interval)));
     const uint64_t step = R.want_missing ? frag_cap / SEQ_TILE_FRAGS : ntiles;
-    for (uint64_t t0 = 0; t0 < ntiles; t0 += step) {
+    if (R.window) TSX_TRY(track_launch(R, two, ub, nrec, row0_off));
+    for (uint64_t t0 = 0; t0 < ntiles && !R.window; t0 += step) {
         const uint64_t t1 = std::min(ntiles, t0 + step);
         const int grid = (int)std::min<uint64_t>(t1 - t0, (uint64_t)m->cus * 4);
         unsigned long long *d_frag = R.want_missing ? R.frag.get() : (unsigned long long *)nullptr;
@@ -4982,6 +5071,7 @@ static int seq_piece(SeqRun &R, const uint8_t *d_text, uint64_t n) {
     R.rows_h.resize(nrec);
     HIP_TRY(hipMemcpyAsync(R.rows_h.data(), R.rows.get(), nrec * sizeof(tsx_hip_seq_stats), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    if (R.window) TSX_TRY(track_merge(R, nrec, q_in != 0, nb_in, row0_off));
     size_t j = 0;
     if (q_in) {   // record 0 goes on with the open sequence
         tsx_hip_seq_stats &a = S.back();
@@ -5013,7 +5103,7 @@ static int seq_end(int rc, tsx_hip_seq_result **res) {
 }
 
 static int seq_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, uint64_t upper, size_t chunk_bytes, bool missing,
-                    tsx_hip_seq_result **res) {
+                    uint64_t window, tsx_hip_seq_result **res) {
     if (!res) return TSX_HIP_EINVAL;
     *res = nullptr;
     if (int rca = seq_args_ok(m, lower, upper)) return rca;
@@ -5025,7 +5115,7 @@ static int seq_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, 
     if (m->piece_fixed) chunk_bytes = std::min(chunk_bytes, m->piece);
     chunk_bytes = std::min(chunk_bytes, FA_PIECE_MAX);
     FastaScope fs(m);
-    SeqRun R(m, st, lower, upper, missing, *res);
+    SeqRun R(m, st, lower, upper, missing, window, *res);
     int rc = R.init();
     // pieces are cut anywhere and overlap nowhere: what a sequence across the cut needs travels in the carries
     for (size_t off = 0; off < n && rc == TSX_HIP_OK; off += chunk_bytes) {
@@ -5036,7 +5126,8 @@ static int seq_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, 
     return seq_end(rc, res);
 }
 
-static int seq_bgzf(tsx_hip_map *m, const void *gz, size_t n, uint64_t lower, uint64_t upper, bool missing, tsx_hip_seq_result **res) {
+static int seq_bgzf(tsx_hip_map *m, const void *gz, size_t n, uint64_t lower, uint64_t upper, bool missing, uint64_t window,
+                    tsx_hip_seq_result **res) {
     if (!res) return TSX_HIP_EINVAL;
     *res = nullptr;
     if (int rca = seq_args_ok(m, lower, upper)) return rca;
@@ -5050,7 +5141,7 @@ static int seq_bgzf(tsx_hip_map *m, const void *gz, size_t n, uint64_t lower, ui
     BgzfBatches bt(ix, std::min(bgzf_batch_bytes(), FA_PIECE_MAX));
     BgzfDev dv;
     DevBuf<uint8_t> txt;
-    SeqRun R(m, st, lower, upper, missing, *res);   // (behind txt: its PieceBufs waits for the stream first)
+    SeqRun R(m, st, lower, upper, missing, window, *res);   // (behind txt: its PieceBufs waits for the stream first)
     int rc = R.init();
     if (rc == TSX_HIP_OK && txt.alloc(bt.biggest() + 256) != TSX_HIP_OK) { g_last_error = "hipMalloc of a BGZF text buffer failed"; rc = TSX_HIP_ENOMEM; }
     for (; rc == TSX_HIP_OK && !bt.done(); bt.next()) {
@@ -5062,7 +5153,7 @@ static int seq_bgzf(tsx_hip_map *m, const void *gz, size_t n, uint64_t lower, ui
 }
 
 static int seq_device(tsx_hip_map *m, const void *dev_text, size_t n, uint64_t lower, uint64_t upper, bool missing,
-                      tsx_hip_seq_result **res, void *stream) {
+                      uint64_t window, tsx_hip_seq_result **res, void *stream) {
     if (!res) return TSX_HIP_EINVAL;
     *res = nullptr;
     if (int rca = seq_args_ok(m, lower, upper)) return rca;
@@ -5070,7 +5161,7 @@ static int seq_device(tsx_hip_map *m, const void *dev_text, size_t n, uint64_t l
     hipStream_t st = pick_stream(m, stream);
     TSX_TRY(seq_begin(m, lower, upper, res, st));
     FastaScope fs(m);
-    SeqRun R(m, st, lower, upper, missing, *res);
+    SeqRun R(m, st, lower, upper, missing, window, *res);
     int rc = R.init();
     const uint8_t *base = (const uint8_t *)dev_text;
     const size_t WIN = std::min(dev_window_bytes(), FA_PIECE_MAX);
@@ -5080,28 +5171,60 @@ static int seq_device(tsx_hip_map *m, const void *dev_text, size_t n, uint64_t l
 
 extern "C" int tsx_hip_seq_stats_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, uint64_t upper, size_t chunk_bytes,
                                       tsx_hip_seq_result **res) {
-    return seq_host(m, text, n, lower, upper, chunk_bytes, false, res);
+    return seq_host(m, text, n, lower, upper, chunk_bytes, false, 0, res);
 }
 extern "C" int tsx_hip_seq_missing_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, uint64_t upper, size_t chunk_bytes,
                                         tsx_hip_seq_result **res) {
-    return seq_host(m, text, n, lower, upper, chunk_bytes, true, res);
+    return seq_host(m, text, n, lower, upper, chunk_bytes, true, 0, res);
 }
 extern "C" int tsx_hip_seq_stats_bgzf_host(tsx_hip_map *m, const void *gz, size_t n, uint64_t lower, uint64_t upper,
                                            tsx_hip_seq_result **res) {
-    return seq_bgzf(m, gz, n, lower, upper, false, res);
+    return seq_bgzf(m, gz, n, lower, upper, false, 0, res);
 }
 extern "C" int tsx_hip_seq_missing_bgzf_host(tsx_hip_map *m, const void *gz, size_t n, uint64_t lower, uint64_t upper,
                                              tsx_hip_seq_result **res) {
-    return seq_bgzf(m, gz, n, lower, upper, true, res);
+    return seq_bgzf(m, gz, n, lower, upper, true, 0, res);
 }
 extern "C" int tsx_hip_seq_stats_device(tsx_hip_map *m, const void *dev_text, size_t n, uint64_t lower, uint64_t upper,
                                         tsx_hip_seq_result **res, void *stream) {
-    return seq_device(m, dev_text, n, lower, upper, false, res, stream);
+    return seq_device(m, dev_text, n, lower, upper, false, 0, res, stream);
 }
 extern "C" int tsx_hip_seq_missing_device(tsx_hip_map *m, const void *dev_text, size_t n, uint64_t lower, uint64_t upper,
                                           tsx_hip_seq_result **res, void *stream) {
-    return seq_device(m, dev_text, n, lower, upper, true, res, stream);
+    return seq_device(m, dev_text, n, lower, upper, true, 0, res, stream);
 }
+
+// The track calls: what the stats calls refuse first, then the window.
+static int track_args_ok(const tsx_hip_map *m, uint64_t lower, uint64_t upper, uint64_t window) {
+    if (int rca = seq_args_ok(m, lower, upper)) return rca;
+    if (window < 64 || window > ((uint64_t)1 << 32)) return seq_fail("sequence track: window outside 64 .. 2^32");
+    return TSX_HIP_OK;
+}
+extern "C" int tsx_hip_seq_track_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower, uint64_t upper, uint64_t window,
+                                      size_t chunk_bytes, tsx_hip_seq_result **res) {
+    if (res) *res = nullptr;
+    if (int rca = track_args_ok(m, lower, upper, window)) return rca;
+    return seq_host(m, text, n, lower, upper, chunk_bytes, false, window, res);
+}
+extern "C" int tsx_hip_seq_track_bgzf_host(tsx_hip_map *m, const void *gz, size_t n, uint64_t lower, uint64_t upper, uint64_t window,
+                                           tsx_hip_seq_result **res) {
+    if (res) *res = nullptr;
+    if (int rca = track_args_ok(m, lower, upper, window)) return rca;
+    return seq_bgzf(m, gz, n, lower, upper, false, window, res);
+}
+extern "C" int tsx_hip_seq_track_device(tsx_hip_map *m, const void *dev_text, size_t n, uint64_t lower, uint64_t upper, uint64_t window,
+                                        tsx_hip_seq_result **res, void *stream) {
+    if (res) *res = nullptr;
+    if (int rca = track_args_ok(m, lower, upper, window)) return rca;
+    return seq_device(m, dev_text, n, lower, upper, false, window, res, stream);
+}
+extern "C" size_t tsx_hip_seq_result_bins(const tsx_hip_seq_result *res, const tsx_hip_seq_bin **bins, const uint64_t **first) {
+    const bool track = res && res->window;   // (a result without a track keeps no offsets)
+    if (bins) *bins = track ? res->bins.data() : nullptr;
+    if (first) *first = track ? res->first.data() : nullptr;
+    return track ? res->bins.size() : 0;
+}
+extern "C" uint64_t tsx_hip_seq_result_window(const tsx_hip_seq_result *res) { return res ? res->window : 0; }
 
 extern "C" size_t tsx_hip_seq_result_count(const tsx_hip_seq_result *res) { return res ? res->stats.size() : 0; }
 extern "C" const tsx_hip_seq_stats *tsx_hip_seq_result_stats(const tsx_hip_seq_result *res) { return res ? res->stats.data() : nullptr; }
@@ -5156,6 +5279,29 @@ extern "C" int tsx_hip_seq_write_missing(const tsx_hip_seq_result *res, int fd) 
         snprintf(num, sizeof num, "\t%llu\t%llu\n", (unsigned long long)v.start, (unsigned long long)v.end);
         out += num;
         if (out.size() >= ((size_t)1 << 20)) { TSX_TRY(write_all(fd, (const uint8_t *)out.data(), out.size())); out.clear(); }
+    }
+    return write_all(fd, (const uint8_t *)out.data(), out.size());
+}
+
+extern "C" int tsx_hip_seq_write_track(const tsx_hip_seq_result *res, int fd) {
+    if (!res || fd < 0) return TSX_HIP_EINVAL;
+    if (!res->window) return seq_fail("sequence track: the result holds no track");
+    std::string out;
+    char num[200], mean[40];
+    const uint64_t W = res->window;
+    for (size_t i = 0; i < res->stats.size(); ++i) {
+        const uint64_t L = res->stats[i].length;
+        for (uint64_t b = 0, at = res->first[i]; at < res->first[i + 1]; ++b, ++at) {
+            const tsx_hip_seq_bin &v = res->bins[(size_t)at];
+            if (v.kmers) snprintf(mean, sizeof mean, "%.4f", (double)v.sum_count / (double)v.kmers);
+            else snprintf(mean, sizeof mean, "NA");
+            seq_name_text(res, i, out);
+            snprintf(num, sizeof num, "\t%llu\t%llu\t%llu\t%llu\t%llu\t%llu\t%s\n", (unsigned long long)(b * W),
+                     (unsigned long long)std::min((b + 1) * W, L), (unsigned long long)v.kmers, (unsigned long long)v.present,
+                     (unsigned long long)v.min_count, (unsigned long long)v.max_count, mean);
+            out += num;
+            if (out.size() >= ((size_t)1 << 20)) { TSX_TRY(write_all(fd, (const uint8_t *)out.data(), out.size())); out.clear(); }
+        }
     }
     return write_all(fd, (const uint8_t *)out.data(), out.size());
 }

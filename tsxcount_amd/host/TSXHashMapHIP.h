@@ -103,6 +103,15 @@ struct TSXSequenceResult {
         const size_t n = tsx_hip_seq_result_intervals(p, &iv);
         return std::vector<tsx_hip_seq_interval>(iv, iv + n);
     }
+    // a track (sequenceTrack): its window, 0 without one; the bins of sequence i
+    uint64_t window() const { return tsx_hip_seq_result_window(p); }
+    std::vector<tsx_hip_seq_bin> bins(size_t i) const {
+        const tsx_hip_seq_bin *b = nullptr;
+        const uint64_t *first = nullptr;
+        tsx_hip_seq_result_bins(p, &b, &first);
+        if (!b || !first || i >= size()) return std::vector<tsx_hip_seq_bin>();
+        return std::vector<tsx_hip_seq_bin>(b + first[i], b + first[i + 1]);
+    }
 };
 // bBgzf: pText is the image of a BGZF file; bMissing: the intervals too
 template <typename C>
@@ -135,6 +144,18 @@ static void tsx_write_sequence_stats(const TSXSequenceResult &r, int iK, const s
 template <typename C>
 static void tsx_write_sequence_missing(const TSXSequenceResult &r, const std::string &sPath, C fnCheck) {
     tsx_write_sequence_file(sPath, [&](int fd) { return tsx_hip_seq_write_missing(r.p, fd); }, fnCheck);
+}
+// the coverage track of a wrapped FASTA text (tsx_hip_seq_track_host) and its file: one line per bin
+template <typename C>
+static TSXSequenceResult tsx_sequence_track(tsx_hip_map *pMap, const char *pText, size_t iBytes, uint64_t iWindow, uint64_t iLower,
+                                            uint64_t iUpper, size_t iChunkBytes, C fnCheck) {
+    TSXSequenceResult r;
+    fnCheck(tsx_hip_seq_track_host(pMap, pText, iBytes, iLower, iUpper, iWindow, iChunkBytes, &r.p));
+    return r;
+}
+template <typename C>
+static void tsx_write_sequence_track(const TSXSequenceResult &r, const std::string &sPath, C fnCheck) {
+    tsx_write_sequence_file(sPath, [&](int fd) { return tsx_hip_seq_write_track(r.p, fd); }, fnCheck);
 }
 // Read trimming over one table (tsx_hip_trim_spans_host / tsx_hip_trim_reads_host).
 template <typename C>
@@ -397,6 +418,18 @@ public:
         const TSXSequenceResult r = missingIntervals(pText, iBytes, iLower, iUpper, iChunkBytes);
         tsx_write_sequence_missing(r, sPath, check);
         return r.intervals().size();
+    }
+    // the coverage track: stats and names as querySequences, and per sequence its bins of iWindow start positions
+    TSXSequenceResult sequenceTrack(const char *pText, size_t iBytes, uint64_t iWindow, uint64_t iLower = 1,
+                                    uint64_t iUpper = UINT64_MAX, size_t iChunkBytes = 0) {
+        return tsx_sequence_track(m_pMap, pText, iBytes, iWindow, iLower, iUpper, iChunkBytes, check);
+    }
+    // name, start, end, kmers, present, min, max, mean per bin into sPath; returns the sequences
+    size_t writeSequenceTrack(const char *pText, size_t iBytes, const std::string &sPath, uint64_t iWindow, uint64_t iLower = 1,
+                              uint64_t iUpper = UINT64_MAX, size_t iChunkBytes = 0) {
+        const TSXSequenceResult r = sequenceTrack(pText, iBytes, iWindow, iLower, iUpper, iChunkBytes);
+        tsx_write_sequence_track(r, sPath, check);
+        return r.size();
     }
     // the count of every window of a text, one entry per byte (TSX_HIP_NO_KMER where no k-mer starts)
     std::vector<uint32_t> countProfile(const char *pText, size_t iBytes, size_t iChunkBytes = 0) {
