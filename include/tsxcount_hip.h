@@ -553,6 +553,60 @@ int tsx_hip_trim_reads_host(tsx_hip_map *m, const char *text, size_t n, const ts
                             size_t chunk_bytes, tsx_hip_trim_totals *totals);
 
 /*
+ * Read correction (csrc/tsx_correct.h; no reference counterpart -- Quake, Musket, Lighter, BFC): undo single
+ * substitutions that the k-mer spectrum identifies exactly.  Records, lines and SOLID windows are those of
+ * tsx_hip_trim_* (a k-mer under the table's base rule whose count lies in lower..upper).  A sequence line of length L
+ * has n = L - k + 1 windows.  Of the maximal runs [a, b] of non-solid windows, w = b - a + 1, a run is a SITE with
+ * suspect base p when
+ *   interior  a > 0, b < n - 1 and w == k:   p = b
+ *   head      a == 0, b < n - 1 and w <= k:  p = b
+ *   tail      a > 0, b == n - 1 and w <= k:  p = a + k - 1
+ * and w >= min_windows; no other run is one (the whole read, an interior run shorter or longer than k, n < 2).  The
+ * windows that hold p are exactly a..b, so sites never share a window and each is judged on the original text: no passes,
+ * no order.  A site whose byte at p is not in ACGTacgt is UNFIXABLE.  Alternative d = 1..3 replaces the code c of that
+ * byte by c ^ d and is GOOD when every window a..b is solid with the replacement.  Exactly one good alternative: the site
+ * is CORRECTED, the byte becomes "ACGT"[c ^ d] in the case of the original; two or three: AMBIGUOUS; none: UNFIXABLE;
+ * both untouched.  Every other byte of the text stays as it is; one call is one round.
+ * TSX_HIP_EINVAL (tsx_hip_last_error says which) for a map created with shard_bits > 0, a table with min_qual_char set
+ * (its dropped windows would make every low-quality base a site for ever), lower > upper, min_windows outside 1..k,
+ * reserved != 0, a NULL rule.
+ *   correct_sites_device  dev_text as tsx_hip_trim_spans_device takes it; the corrections [0, cap) to dev_corrections
+ *                         (tsx_hip_correction each, in no order).  WAITS for the stream; more corrections than cap:
+ *                         TSX_HIP_ERANGE (cap of them are written, *n_corrections says how many there are).
+ *   correct_sites_host    text in host memory in pieces cut at record boundaries (chunk_bytes 0 = 256 MiB, at most
+ *                         TSX_HIP_PIECE_BYTES); the corrections sorted by (record, pos); more than cap: TSX_HIP_ERANGE
+ *                         with the first cap of that order written.
+ *   correct_reads_device  the n bytes of dev_text with the corrections applied into dev_out (out_cap >= n, else
+ *                         TSX_HIP_ERANGE; dev_out may be dev_text).  Waits for the stream.
+ *   correct_reads_host    the same to fd, piece by piece behind the device; exactly n bytes.  A failed write: TSX_HIP_EIO.
+ * totals (optional): records seen, sites = corrected + ambiguous + unfixable, bytes written (0 for the sites calls).
+ */
+typedef struct tsx_hip_correct_rule {
+    uint64_t lower, upper;      /* the count range of a solid window */
+    uint32_t min_windows;       /* a run of fewer non-solid windows is no site (1..k) */
+    uint32_t reserved;          /* 0 */
+} tsx_hip_correct_rule;
+typedef struct tsx_hip_correction {
+    uint64_t record;            /* the record's index in the text */
+    uint32_t pos;               /* the base's offset in its sequence line */
+    uint8_t from, to;           /* the byte that was there, the byte that replaces it */
+    uint16_t windows;           /* w: the non-solid windows the correction makes solid */
+} tsx_hip_correction;
+typedef struct tsx_hip_correct_totals {
+    uint64_t records, sites, corrected, ambiguous, unfixable, bytes;
+} tsx_hip_correct_totals;
+int tsx_hip_correct_sites_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_correct_rule *rule,
+                                 void *dev_corrections, size_t cap, size_t *n_corrections, tsx_hip_correct_totals *totals,
+                                 void *stream);
+int tsx_hip_correct_sites_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_correct_rule *rule,
+                               tsx_hip_correction *corrections_out, size_t cap, size_t *n_corrections,
+                               tsx_hip_correct_totals *totals, size_t chunk_bytes);
+int tsx_hip_correct_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_correct_rule *rule,
+                                 void *dev_out, size_t out_cap, tsx_hip_correct_totals *totals, void *stream);
+int tsx_hip_correct_reads_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_correct_rule *rule, int fd,
+                               size_t chunk_bytes, tsx_hip_correct_totals *totals);
+
+/*
  * Read medians (csrc/tsx_median.h; no reference counterpart -- khmer `count-median` / `normalize-by-median`, KAT `sect`,
  * `jellyfish query -s`): the count of every window of a text, and per record the median of them.  Records, lines,
  * k-mers and c(x) are those of tsx_hip_query_reads_*; the table's base rule (tsx_hip_set_base_rule) decides which

@@ -82,6 +82,17 @@ class TrimTotals(_Totals):
                 ("bases_kept", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
 
 
+class CorrectRule(ctypes.Structure):
+    """tsx_hip_correct_rule: a window is solid when lower <= count <= upper; a run of fewer than min_windows is no site."""
+    _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("min_windows", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class CorrectTotals(_Totals):
+    """tsx_hip_correct_totals."""
+    _fields_ = [(f, ctypes.c_uint64) for f in ("records", "sites", "corrected", "ambiguous", "unfixable", "bytes")]
+
+
 class PairIO(ctypes.Structure):
     """tsx_hip_pair_io: the four outputs of a pair call (-1 = none)."""
     _fields_ = [("fd1", ctypes.c_int), ("fd2", ctypes.c_int), ("fd_single1", ctypes.c_int), ("fd_single2", ctypes.c_int)]
@@ -377,6 +388,10 @@ def _signatures():
         "tsx_hip_prefilter_read": (ci, [vp, ci, u64p, sz]),
         "tsx_hip_prefilter_mask_host": (ci, [ci, u64p, ci, u64p, u64p, u64p]),
         "tsx_hip_filter_pairs_host": (ci, [vp, ccp, sz, ccp, sz, P(FilterRule), ci, ci, P(PairIO), sz, P(PairTotals)]),
+        "tsx_hip_correct_sites_device": (ci, [vp, vp, sz, P(CorrectRule), vp, sz, szp, P(CorrectTotals), vp]),
+        "tsx_hip_correct_sites_host": (ci, [vp, ccp, sz, P(CorrectRule), vp, sz, szp, P(CorrectTotals), sz]),
+        "tsx_hip_correct_reads_device": (ci, [vp, vp, sz, P(CorrectRule), vp, sz, P(CorrectTotals), vp]),
+        "tsx_hip_correct_reads_host": (ci, [vp, ccp, sz, P(CorrectRule), ci, sz, P(CorrectTotals)]),
         "tsx_hip_trim_pairs_host": (ci, [vp, ccp, sz, ccp, sz, P(TrimRule), ci, P(PairIO), sz, P(PairTotals)]),
         "tsx_hip_hash_apply": (ci, [vp, u64p, u64p]),
         "tsx_hip_hash_invert": (ci, [vp, u64p, u64p]),

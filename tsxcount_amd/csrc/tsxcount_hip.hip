@@ -18,6 +18,7 @@
 #include "tsx_seq.h"
 #include "tsx_track.h"
 #include "tsx_trim.h"
+#include "tsx_correct.h"
 #include "tsx_normalize.h"
 #include "tsx_sketch.h"
 #include "tsx_prefilter.h"
@@ -130,6 +131,12 @@ struct tsx_hip_map {
     const uint16_t *qmap_cur = nullptr;  // the bitmap at the text the next scan launches read (set per call, else null)
     DevBuf<unsigned long long> d_qrec;   // line spans per record behind it, and record cuts
     bool used = false;                   // something was inserted since the map was created or cleared
+    // read correction (tsx_correct.h): grow-only scratch, kept between calls
+    struct CorrectScratch {
+        DevBuf<unsigned long long> bits, lo, nsites, tot;   // bitmap, line offsets, the site cursor, a device call's totals
+        DevBuf<CorrectSite> sites;
+        DevBuf<CorrectionRec> corr;
+    } correct;
     // FASTQ scratch
     DevBuf<uint32_t> d_tile;             // tile counts, then one partial sum per SCAN_CHUNK tiles
     uint64_t tile_cap = 0;               // tiles it has room for: where the partial sums start (ensure_tiles)
@@ -5744,6 +5751,254 @@ extern "C" int tsx_hip_trim_reads_device(tsx_hip_map *m, const void *dev_text, s
     }
     if (totals) *totals = t;
     return rc;
+}
+
+// ---- read correction: single substitutions undone from the spectrum (tsx_correct.h) ----------------------------------
+static_assert(sizeof(tsx_hip_correction) == sizeof(CorrectionRec) && sizeof(tsx_hip_correct_totals) == 48 &&
+                  sizeof(tsx_hip_correct_rule) == 24, "the correction records of the ABI are the kernels'");
+static int correct_fail(const char *why) { g_last_error = why; return TSX_HIP_EINVAL; }
+static int correct_check(const tsx_hip_map *m, const tsx_hip_correct_rule *r) {
+    if (!m) return correct_fail("correct: no map");
+    if (!r) return correct_fail("correct: no rule");
+    if (m->p.lg != m->p.l) return correct_fail("correct: a map created with shard_bits > 0");
+    if (m->minq) return correct_fail("correct: a table with min_qual_char set (every low-quality base would be a site for ever)");
+    if (r->lower > r->upper) return correct_fail("correct: lower > upper");
+    if (r->min_windows < 1 || r->min_windows > (uint32_t)m->p.k) return correct_fail("correct: min_windows outside 1..k");
+    if (r->reserved != 0) return correct_fail("correct: reserved must be 0");
+    return TSX_HIP_OK;
+}
+
+// Sites of a text of `len` bytes: a bound that cannot be exceeded.  A record of n >= 2 windows holds at most
+// (n - 3) / (k + 1) + 2 sites (interior runs are k windows long, a solid window between any two runs) and takes at least
+// n + k + 2 bytes (a header byte, two line ends, the last of which the text's end may stand for); the ratio is largest
+// for n = 2.
+static uint64_t correct_site_cap(uint64_t len, int k) { return 2 * len / ((uint64_t)k + 4) + 4; }
+
+// Scratch of one correction call: the map's (bitmap, line offsets, site list, corrections: kept between calls, so that a
+// call on a text no larger than an earlier one allocates nothing), the output copy and the piece scratch.
+struct CorrectBufs {
+    tsx_hip_map::CorrectScratch &s;
+    OutBuf out;
+    PieceBufs p;
+    CorrectBufs(tsx_hip_map *m, hipStream_t st) : s(m->correct), p(st) {}
+};
+
+// Behind the bitmap and the line offsets (positions of d_text; records [0, min(cap, *d_nrec or nrec)), the first of them
+// record rec_base of the text): the site pass and the probe pass.  tot: CT_N zeroed device words, tot[CT_CORRECTED] the
+// cursor of corr (corr_cap entries).  Queued, not waited for.
+static int correct_passes(tsx_hip_map *m, CorrectBufs &b, const uint8_t *d_text, uint64_t len, const unsigned long long *bits,
+                          const unsigned long long *lo, const unsigned long long *d_nrec, uint64_t nrec, uint64_t cap,
+                          uint64_t rec_base, const tsx_hip_correct_rule &rule, CorrectionRec *corr, uint64_t corr_cap,
+                          unsigned long long *tot, hipStream_t st) {
+    const uint64_t site_cap = correct_site_cap(len, m->p.k);
+    TSX_TRY(grow(st, b.s.sites, site_cap * sizeof(CorrectSite)));
+    TSX_TRY(grow(st, b.s.nsites, sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(b.s.nsites.get(), 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(correct_sites_kernel, dim3(grid_for(m, cap, 8)), dim3(NT), 0, st, bits, lo, d_nrec, nrec, cap,
+                       (uint32_t)m->p.k, rule.min_windows, b.s.sites.get(), site_cap, b.s.nsites.get());
+    HIP_TRY(hipGetLastError());
+    // the probe kernel reads A * (d << 2j) as a LUT entry: a 2-bit field must not straddle a LUT group
+    if (m->p.g != 4 && m->p.g != 8) { g_last_error = "correct: a hash LUT of groups other than 4 or 8 bits"; return TSX_HIP_EINVAL; }
+    const CorrectArgs ca = {rule.lower, rule.upper, rec_base, len};
+    const size_t lut_bytes = m->lut.size() * 8;
+    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((site_cap + NT / 64 - 1) / (NT / 64), (uint64_t)m->cus * 8));
+#define CORRECT_PROBE(AOV)                                                                                                      \
+    DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((correct_probe_kernel<WKV, CANV, AOV>), dim3(grid), dim3(NT), lut_bytes, \
+                                                        st, m->p, ca, d_text, lo, (const CorrectSite *)b.s.sites.get(),           \
+                                                        (const unsigned long long *)b.s.nsites.get(), site_cap, corr, corr_cap, tot)))
+    if (m->p.acgt_only) { CORRECT_PROBE(true); } else { CORRECT_PROBE(false); }
+#undef CORRECT_PROBE
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+static void correct_apply_launch(tsx_hip_map *m, const CorrectionRec *corr, const unsigned long long *n_corr, uint64_t corr_cap,
+                                 const unsigned long long *lo, uint64_t rec_base, uint8_t *out, uint64_t out_n,
+                                 unsigned long long *total, hipStream_t st) {
+    hipLaunchKernelGGL(correct_apply_kernel, dim3(grid_for(m, corr_cap, 8)), dim3(NT), 0, st, corr, n_corr, corr_cap, lo, rec_base,
+                       out, out_n, total, out_n);
+}
+
+// One piece: piece_front, then over its whole records [0, cut): bitmap, line offsets, sites, probes (totals in
+// info[5..7], the corrections in b.corr) and -- `copy` -- the text with them applied in b.out (its size -> info[3]).
+// What follows the wait is queued, not waited for.  Not last and no whole record: nrec = 0 and cut = 0, nothing done; a
+// last piece without a record (empty lines): nrec = 0, cut = len, and `copy` stages its bytes as they are.
+static int correct_piece(tsx_hip_map *m, CorrectBufs &b, const uint8_t *d_text, uint64_t len, bool last, uint64_t rec_base,
+                         const tsx_hip_correct_rule &rule, bool copy, hipStream_t st, uint64_t &cut, uint64_t &nrec) {
+    bool open;
+    TSX_TRY(piece_front(m, b.p, d_text, len, last, false, cut, nrec, open));
+    if (nrec == 0) {
+        // a last piece of empty lines only: its bytes are output all the same (the apply launch only reports the size)
+        if (copy && cut) {
+            TSX_TRY(b.out.room(st, cut));
+            HIP_TRY(hipMemcpyAsync(b.out.out, d_text, cut, hipMemcpyDeviceToDevice, st));
+            correct_apply_launch(m, nullptr, b.p.info.get() + 5 + CT_CORRECTED, 0, nullptr, rec_base, b.out.out, cut, b.p.info.get() + 3, st);
+            HIP_TRY(hipGetLastError());
+        }
+        return TSX_HIP_OK;
+    }
+    const uint64_t nwords = (cut + 63) / 64, corr_cap = correct_site_cap(cut, m->p.k);
+    TSX_TRY(grow(st, b.s.bits, (nwords + 1) * 8));
+    TSX_TRY(grow(st, b.s.lo, nrec * TL_N * 8));
+    TSX_TRY(grow(st, b.s.corr, corr_cap * sizeof(CorrectionRec)));
+    HIP_TRY(hipMemsetAsync(b.s.lo.get(), 0, nrec * TL_N * 8, st));
+    const unsigned long long *zero = b.p.info.get() + 4;
+    const tsx_hip_trim_rule solid = {rule.lower, rule.upper, 0, TSX_HIP_TRIM_LONGEST, 0};
+    TSX_TRY(solid_launch(m, d_text, cut, cut, 0, zero, solid, b.s.bits.get(), st));
+    // (the carry is read for an unterminated last line only: then cut = len and it holds the lines of [0, cut))
+    lines_launch(m, d_text, cut, cut, 0, zero, 0, last, b.s.lo.get(), nrec, st);
+    unsigned long long *tot = b.p.info.get() + 5;
+    TSX_TRY(correct_passes(m, b, d_text, cut, b.s.bits.get(), b.s.lo.get(), nullptr, nrec, nrec, rec_base, rule, b.s.corr.get(), corr_cap,
+                           tot, st));
+    if (copy) {
+        TSX_TRY(b.out.room(st, cut));
+        HIP_TRY(hipMemcpyAsync(b.out.out, d_text, cut, hipMemcpyDeviceToDevice, st));
+        correct_apply_launch(m, b.s.corr.get(), tot + CT_CORRECTED, corr_cap, b.s.lo.get(), rec_base, b.out.out, cut, b.p.info.get() + 3, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return TSX_HIP_OK;
+}
+
+static void correct_totals(tsx_hip_correct_totals *t, uint64_t records, const uint64_t *tot, uint64_t bytes) {
+    if (t) *t = tsx_hip_correct_totals{records, tot[0] + tot[1] + tot[2], tot[CT_CORRECTED], tot[CT_AMBIGUOUS], tot[CT_UNFIXABLE], bytes};
+}
+
+// Sites and corrected reads of a host text: the pieces of host_pieces (at most TSX_HIP_PIECE_BYTES each).  fd < 0: the
+// corrections of every piece are gathered and sorted by (record, pos), the first `cap` go to corr_out.  Else the pieces,
+// corrected, go to fd through the write-behind.
+static int correct_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_correct_rule &rule, size_t chunk_bytes,
+                        tsx_hip_correction *corr_out, size_t cap, size_t *n_corr, int fd, tsx_hip_correct_totals *totals) {
+    hipStream_t st = m->stream.get();
+    WriteBehind wb;
+    wb.fd = fd;
+    std::vector<tsx_hip_correction> all;
+    CorrectBufs b(m, st);
+    uint64_t records = 0, tot[CT_N] = {0, 0, 0};
+    int rc = host_pieces(m, b.p, text, n, chunk_bytes, true, records,
+        [&](const uint8_t *d_text, uint64_t len, bool last, uint64_t &cut, uint64_t &nrec, bool &) {
+            return correct_piece(m, b, d_text, len, last, records, rule, fd >= 0, st, cut, nrec);
+        },
+        [&](size_t, uint64_t, uint64_t cut, uint64_t nrec, bool) -> int {
+            if (fd >= 0) return cut ? wb.piece(b.p, b.out.out, cut, CT_N, tot, "correct") : TSX_HIP_OK;
+            if (!nrec) return TSX_HIP_OK;
+            unsigned long long *h = b.p.h_info.get();
+            HIP_TRY(hipMemcpyAsync(h + 5, b.p.info.get() + 5, CT_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            const uint64_t nc = h[5 + CT_CORRECTED];
+            for (int i = 0; i < CT_N; ++i) tot[i] += h[5 + i];
+            if (nc) {
+                const size_t at = all.size();
+                all.resize(at + nc);
+                HIP_TRY(hipMemcpyAsync(all.data() + at, b.s.corr.get(), nc * sizeof(tsx_hip_correction), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+            }
+            HIP_TRY(hipMemsetAsync(b.p.info.get() + 5, 0, CT_N * sizeof(unsigned long long), st));
+            return TSX_HIP_OK;
+        });
+    if (rc == TSX_HIP_OK) rc = wb.flush();
+    correct_totals(totals, records, tot, wb.bytes);
+    if (fd < 0) {
+        std::sort(all.begin(), all.end(), [](const tsx_hip_correction &x, const tsx_hip_correction &y) {
+            return x.record != y.record ? x.record < y.record : x.pos < y.pos;
+        });
+        if (n_corr) *n_corr = all.size();
+        if (corr_out && cap) memcpy(corr_out, all.data(), std::min(all.size(), cap) * sizeof(tsx_hip_correction));
+        if (rc == TSX_HIP_OK && all.size() > cap) rc = TSX_HIP_ERANGE;
+    }
+    return rc;
+}
+
+extern "C" int tsx_hip_correct_sites_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_correct_rule *rule,
+                                          tsx_hip_correction *corrections_out, size_t cap, size_t *n_corrections,
+                                          tsx_hip_correct_totals *totals, size_t chunk_bytes) {
+    if (n_corrections) *n_corrections = 0;
+    if (totals) *totals = tsx_hip_correct_totals{0, 0, 0, 0, 0, 0};
+    TSX_TRY(correct_check(m, rule));
+    if ((!text && n) || (!corrections_out && cap)) return correct_fail("correct: the text or the corrections pointer");
+    return correct_host(m, text, n, *rule, chunk_bytes, corrections_out, cap, n_corrections, -1, totals);
+}
+
+extern "C" int tsx_hip_correct_reads_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_correct_rule *rule, int fd,
+                                          size_t chunk_bytes, tsx_hip_correct_totals *totals) {
+    if (totals) *totals = tsx_hip_correct_totals{0, 0, 0, 0, 0, 0};
+    TSX_TRY(correct_check(m, rule));
+    if ((!text && n) || fd < 0) return correct_fail("correct: the text or the output descriptor");
+    return correct_host(m, text, n, *rule, chunk_bytes, nullptr, 0, nullptr, fd, totals);
+}
+
+// A device text in windows (device_windows, whole bitmap words, as tsx_hip_trim_spans_device): one bitmap and one array of
+// line offsets of the whole text; the sites and the probes once, after the last window.  dev_corr (cap entries, may be
+// null with cap 0): the corrections, in no order.  dev_out: the text with them applied (the corrections are then kept in
+// scratch, all of them).  WAITS for the stream.
+static int correct_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_correct_rule &rule, void *dev_corr,
+                          size_t cap, size_t *n_corr, void *dev_out, tsx_hip_correct_totals *totals, void *stream) {
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t st = pick_stream(m, stream);
+    TSX_TRY(ensure_zeroed(m, st));
+    const uint32_t lpr = m->p.line_mask + 1;
+    // (a non-empty line and its '\n' are two bytes: no text holds more records than this)
+    const uint64_t rcap = n / (2 * lpr) + 2, nwords = ((uint64_t)n + 63) / 64;
+    CorrectBufs b(m, st);
+    DevBuf<unsigned long long> &tot = b.s.tot;
+    SyncAtExit wait(st);
+    TSX_TRY(grow(st, b.s.bits, (nwords + 1) * 8));
+    TSX_TRY(grow(st, b.s.lo, (rcap + 1) * TL_N * 8));
+    TSX_TRY(grow(st, tot, CT_N * 8));
+    HIP_TRY(hipMemsetAsync(b.s.lo.get(), 0, (rcap + 1) * TL_N * 8, st));
+    HIP_TRY(hipMemsetAsync(tot.get(), 0, CT_N * 8, st));
+    const uint8_t *base = (const uint8_t *)dev_text;
+    const tsx_hip_trim_rule solid = {rule.lower, rule.upper, 0, TSX_HIP_TRIM_LONGEST, 0};
+    TSX_TRY(device_windows(m, base, n, true, st,
+                           [&](size_t off, size_t own, size_t len, int head_open, bool last, const unsigned long long *d_base) -> int {
+                               TSX_TRY(solid_launch(m, base + off, len, own, head_open, d_base, solid, b.s.bits.get() + off / 64, st));
+                               lines_launch(m, base + off, len, own, head_open, d_base, off, last, b.s.lo.get(), rcap, st);
+                               return TSX_HIP_OK;
+                           }));
+    CorrectionRec *corr = (CorrectionRec *)dev_corr;
+    uint64_t corr_cap = cap;
+    if (dev_out) {
+        corr_cap = correct_site_cap(n, m->p.k);
+        TSX_TRY(grow(st, b.s.corr, corr_cap * sizeof(CorrectionRec)));
+        corr = b.s.corr.get();
+    }
+    unsigned long long h[CT_N + 1] = {0, 0, 0, 0};
+    if (n) {
+        const unsigned long long *d_nrec = (const unsigned long long *)m->d_carry.get() + 3;
+        TSX_TRY(correct_passes(m, b, base, n, b.s.bits.get(), b.s.lo.get(), d_nrec, 0, rcap, 0, rule, corr, corr_cap, tot.get(), st));
+        if (dev_out) {
+            if (dev_out != dev_text) HIP_TRY(hipMemcpyAsync(dev_out, dev_text, n, hipMemcpyDeviceToDevice, st));
+            correct_apply_launch(m, corr, tot.get() + CT_CORRECTED, corr_cap, b.s.lo.get(), 0, (uint8_t *)dev_out, n, nullptr, st);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(h, tot.get(), CT_N * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(h + CT_N, (const unsigned long long *)m->d_carry.get() + 3, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t t3[CT_N] = {h[0], h[1], h[2]};
+    correct_totals(totals, h[CT_N], t3, dev_out ? n : 0);
+    if (n_corr) *n_corr = (size_t)h[CT_CORRECTED];
+    return (!dev_out && h[CT_CORRECTED] > cap) ? TSX_HIP_ERANGE : TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_correct_sites_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_correct_rule *rule,
+                                            void *dev_corrections, size_t cap, size_t *n_corrections,
+                                            tsx_hip_correct_totals *totals, void *stream) {
+    if (n_corrections) *n_corrections = 0;
+    if (totals) *totals = tsx_hip_correct_totals{0, 0, 0, 0, 0, 0};
+    TSX_TRY(correct_check(m, rule));
+    if ((!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_corrections && cap) || ((uintptr_t)dev_corrections & 7))
+        return correct_fail("correct: the text (16-byte aligned) or the corrections pointer");
+    return correct_device(m, dev_text, n, *rule, dev_corrections, cap, n_corrections, nullptr, totals, stream);
+}
+
+extern "C" int tsx_hip_correct_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, const tsx_hip_correct_rule *rule,
+                                            void *dev_out, size_t out_cap, tsx_hip_correct_totals *totals, void *stream) {
+    if (totals) *totals = tsx_hip_correct_totals{0, 0, 0, 0, 0, 0};
+    TSX_TRY(correct_check(m, rule));
+    if ((!dev_text && n) || ((uintptr_t)dev_text & 15) || !dev_out)
+        return correct_fail("correct: the text (16-byte aligned) or the output pointer");
+    if (out_cap < n) return TSX_HIP_ERANGE;
+    return correct_device(m, dev_text, n, *rule, nullptr, 0, nullptr, dev_out, totals, stream);
 }
 
 // ---- read medians: the count of every window, the median of every record, the filter on it (tsx_median.h) ---------

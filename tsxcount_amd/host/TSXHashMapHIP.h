@@ -462,6 +462,27 @@ public:
                                   size_t iChunkBytes = 0) {
         return tsx_trim_reads(m_pMap, pText, iBytes, oRule, sPath, iChunkBytes, check);
     }
+    // the single substitutions the spectrum undoes in a text (tsx_hip_correct_sites_host), sorted by (record, pos)
+    std::vector<tsx_hip_correction> correctionSites(const char *pText, size_t iBytes, const tsx_hip_correct_rule &oRule,
+                                                    tsx_hip_correct_totals *pTotals = nullptr, size_t iChunkBytes = 0) {
+        std::vector<tsx_hip_correction> out(iBytes / 256 + 16);
+        size_t n = 0;
+        int rc = tsx_hip_correct_sites_host(m_pMap, pText, iBytes, &oRule, out.data(), out.size(), &n, pTotals, iChunkBytes);
+        if (rc == TSX_HIP_ERANGE) {
+            out.resize(n);
+            rc = tsx_hip_correct_sites_host(m_pMap, pText, iBytes, &oRule, out.data(), n, &n, pTotals, iChunkBytes);
+        }
+        check(rc);
+        out.resize(n);
+        return out;
+    }
+    // the text with them applied, byte for byte as long, to an open descriptor (tsx_hip_correct_reads_host)
+    tsx_hip_correct_totals correctReads(const char *pText, size_t iBytes, int iFd, const tsx_hip_correct_rule &oRule,
+                                        size_t iChunkBytes = 0) {
+        tsx_hip_correct_totals t = {0, 0, 0, 0, 0, 0};
+        check(tsx_hip_correct_reads_host(m_pMap, pText, iBytes, &oRule, iFd, iChunkBytes, &t));
+        return t;
+    }
     // the filter / the trim over mate pairs (pText2 == nullptr: interleaved); sPaths as tsx_pairs_files takes them
     tsx_hip_pair_totals filterPairs(const char *pText1, size_t iBytes1, const char *pText2, size_t iBytes2,
                                     const tsx_hip_filter_rule &oRule, const std::string (&sPaths)[4],
