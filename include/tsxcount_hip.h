@@ -1042,6 +1042,71 @@ int tsx_hip_het_pairs_device(tsx_hip_map *m, const tsx_hip_het_rule *rule, uint6
 int tsx_hip_write_het_pairs_host(tsx_hip_map *m, const tsx_hip_het_rule *rule, int fd, size_t chunk_bytes, uint64_t *pairs_out,
                                  uint64_t *bytes_out);
 
+/*
+ * Unitigs: the compacted de Bruijn graph of one table (csrc/tsx_unitig.h; no reference counterpart -- BCALM2, Cuttlefish).
+ *   node      a k-mer x of the table with rule->lower <= c(x) <= rule->upper (c as above); a k-mer out of range is absent.
+ *             On a canonical table a node stands for both strands.
+ *   oriented  a node read as a string s: on a canonical table a node has two, s and rc(s), on a plain table one.  succ(s)
+ *             is the set of strings s[1:] + c, c in ACGT, that are nodes (either strand, on a canonical table), pred(s) the
+ *             set of strings c + s[:-1] that are.
+ *   edge      s -> t, t in succ(s), is compactable when |succ(s)| = 1, |pred(t)| = 1 and t is not the node of s (no
+ *             AAAA -> AAAA, no hairpin s -> rc(s)).
+ *   unitig    a maximal chain s1 -> ... -> sm of compactable edges, spelled as s1 followed by the last base of each later
+ *             string: m + k - 1 bases that hold m k-mers.  On a canonical table every chain exists on both strands and the
+ *             lexicographically smaller spelling is reported; k must be odd there (no k-mer is its own reverse
+ *             complement, so a chain never meets a node twice).  A chain that closes on itself -- an isolated cycle -- is cut
+ *             at a node of the library's choice, spelled the same way and marked circular; its strand is free as well.
+ *             Every node lies in exactly one unitig, once; the set of unitigs depends on the node set alone.
+ *   record    tsx_hip_unitig: the sequence is bytes [offset, offset + length) of the sequence buffer (ASCII, no separator;
+ *             the records tile the buffer in no particular order), kmers = m, sum_count = the exact sum of the m counts
+ *             (modulo 2^64).  The order of the records is unspecified.
+ *   totals    nodes; unitigs; circular; bases = the sum of the lengths; longest = the most bases of one unitig; isolated =
+ *             nodes without any neighbour; tips = nodes with neighbours on one side only; branching = nodes with more than
+ *             one neighbour on a side; sum_count over all nodes; degree[5 * in + out] = nodes by |pred| and |succ| of the
+ *             strand a dump reports.
+ *   tsx_hip_unitig_stats     the totals alone: the degree sweep and the walks, nothing spelled.
+ *   tsx_hip_unitigs_device   sequences to dev_seq (seq_cap bytes) and records to dev_records (record_cap records), both device
+ *                            memory, on `stream` (NULL = the map's own).  WAITS for the result.  *n_unitigs and *seq_bytes
+ *                            always receive what the result needs; a cap below that: TSX_HIP_ERANGE, and neither buffer
+ *                            holds anything of use (nothing is written past the caps).
+ *   tsx_hip_unitigs_host     the same into host memory.
+ *   tsx_hip_write_unitigs_host  FASTA to fd, one record per unitig with BCALM's header, `>INDEX LN:i:<bases> KC:i:<sum_count>
+ *                            km:f:<sum_count / kmers as %.1f>`, ` CL:i:1` behind it for a circular one, the sequence on one
+ *                            line.  Written chunk by chunk behind the copies from the device.  A failed write: TSX_HIP_EIO.
+ * Extra device memory for the length of a call: one byte and one bit per slot, 8 bytes per unitig, and for the _host and
+ * write calls the records (40 bytes each) and the sequences; the record room of those two is min(record_cap, nodes), and
+ * when that passes 256 MiB the walks run once more, in front, so that it is the unitigs.  TSX_HIP_ENOMEM when it does not
+ * fit.  The table is left as it is.
+ * TSX_HIP_EINVAL before any device call (tsx_hip_last_error says which): a NULL map, rule or output, a map created with
+ * shard_bits > 0, lower > upper, flags or reserved != 0, even k on a canonical table.  TSX_HIP_EHIP with "unitigs: the table
+ * is not consistent" when a walk ran into its bound of nodes + 1 steps (no device loop depends on the table to end).
+ */
+typedef struct tsx_hip_unitig_rule {
+    uint64_t lower, upper;
+    uint32_t flags;      /* 0 */
+    uint32_t reserved;   /* 0 */
+} tsx_hip_unitig_rule;
+typedef struct tsx_hip_unitig {
+    uint64_t offset, length, kmers, sum_count, circular;
+} tsx_hip_unitig;
+typedef struct tsx_hip_unitig_totals {
+    uint64_t nodes, unitigs, circular, bases, longest, isolated, tips, branching, sum_count;
+    uint64_t degree[25];
+} tsx_hip_unitig_totals;
+int tsx_hip_unitig_stats(tsx_hip_map *m, const tsx_hip_unitig_rule *rule, tsx_hip_unitig_totals *totals);
+int tsx_hip_unitigs_device(tsx_hip_map *m, const tsx_hip_unitig_rule *rule, void *dev_seq, size_t seq_cap, void *dev_records,
+                           size_t record_cap, size_t *n_unitigs, size_t *seq_bytes, tsx_hip_unitig_totals *totals /* optional */,
+                           void *stream);
+int tsx_hip_unitigs_host(tsx_hip_map *m, const tsx_hip_unitig_rule *rule, void *seq_out, size_t seq_cap,
+                         tsx_hip_unitig *records_out, size_t record_cap, size_t *n_unitigs, size_t *seq_bytes,
+                         tsx_hip_unitig_totals *totals /* optional */);
+int tsx_hip_write_unitigs_host(tsx_hip_map *m, const tsx_hip_unitig_rule *rule, int fd, tsx_hip_unitig_totals *totals /* optional */);
+/* A DIAGNOSTIC for scripts/unitig_rate.py, with no promise of stability: it may change or go in any release.  What the
+ * steps of this thread's last unitig call took, in milliseconds of host clock (every step waits for its totals):
+ * ms_out[0] the degree sweep, [1] the walk of the starts (both of them when the walks ran twice), [2] the spelling walk,
+ * [3] the cycle pass. */
+int tsx_hip_unitig_last_timing(double *ms_out);
+
 /* IBijectiveFunction::apply / inv_apply (IBijectiveFunction.h:26-27) on the host,
  * and the matrix rows (row i <-> output bit 2k-1-i, BijectiveKMapping.h:202-256). */
 int tsx_hip_hash_apply(const tsx_hip_map *m, const uint64_t *kmer, uint64_t *key_out);

@@ -15,6 +15,7 @@ group    TSXHashMapHIPGroup
 textio   BGZF, wrapped FASTA, cut_records, the synth entry points, database_info
 track    coverage tracks (binned k-mer counts along each sequence); reached as tsxcount_amd.track, not re-exported
 correct  read correction (single substitutions undone from the spectrum); reached as tsxcount_amd.correct, not re-exported
+unitig   unitigs (the compacted de Bruijn graph of a table); reached as tsxcount_amd.unitig, not re-exported
 """
 import ctypes  # noqa: F401 -- ctypes, os and np stay reachable as attributes of the package (tests use T.ctypes)
 import os  # noqa: F401
@@ -32,6 +33,7 @@ from ._abi import (BIN_A, BIN_AMBIGUOUS, BIN_B, BIN_NAMES, BIN_NONE, BIN_STATS_D
                    median_rule, min_qual_code, normalize_rule, revcomp, trim_rule)
 from . import correct  # noqa: F401 -- the submodule only: its names are no part of the package's surface
 from . import track  # noqa: F401 -- the submodule only: its names are no part of the package's surface
+from . import unitig  # noqa: F401 -- the submodule only: its names are no part of the package's surface
 from .group import TSXHashMapHIPGroup
 from .models import (bin_class, fasta_records, het_histogram, het_pairs, join_fasta, joint_histogram, kmer_qv, median_count,
                      merge_sketches, missing_intervals, pair_name, prefilter_masks, sequence_stats, sketch_registers)

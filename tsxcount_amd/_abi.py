@@ -93,6 +93,22 @@ class CorrectTotals(_Totals):
     _fields_ = [(f, ctypes.c_uint64) for f in ("records", "sites", "corrected", "ambiguous", "unfixable", "bytes")]
 
 
+class UnitigRule(ctypes.Structure):
+    """tsx_hip_unitig_rule: a k-mer is a node when lower <= count <= upper; flags must be 0."""
+    _fields_ = [("lower", ctypes.c_uint64), ("upper", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class UnitigTotals(ctypes.Structure):
+    """tsx_hip_unitig_totals; degree[5 * in + out] counts the nodes by in- and out-degree."""
+    _fields_ = [(f, ctypes.c_uint64) for f in ("nodes", "unitigs", "circular", "bases", "longest", "isolated", "tips",
+                                               "branching", "sum_count")] + [("degree", ctypes.c_uint64 * 25)]
+
+    def as_dict(self):
+        d = {f: int(getattr(self, f)) for f, _ in self._fields_[:-1]}
+        d["degree"] = [int(v) for v in self.degree]
+        return d
+
+
 class PairIO(ctypes.Structure):
     """tsx_hip_pair_io: the four outputs of a pair call (-1 = none)."""
     _fields_ = [("fd1", ctypes.c_int), ("fd2", ctypes.c_int), ("fd_single1", ctypes.c_int), ("fd_single2", ctypes.c_int)]
@@ -392,6 +408,11 @@ def _signatures():
         "tsx_hip_correct_sites_host": (ci, [vp, ccp, sz, P(CorrectRule), vp, sz, szp, P(CorrectTotals), sz]),
         "tsx_hip_correct_reads_device": (ci, [vp, vp, sz, P(CorrectRule), vp, sz, P(CorrectTotals), vp]),
         "tsx_hip_correct_reads_host": (ci, [vp, ccp, sz, P(CorrectRule), ci, sz, P(CorrectTotals)]),
+        "tsx_hip_unitig_stats": (ci, [vp, P(UnitigRule), P(UnitigTotals)]),
+        "tsx_hip_unitigs_device": (ci, [vp, P(UnitigRule), vp, sz, vp, sz, szp, szp, P(UnitigTotals), vp]),
+        "tsx_hip_unitigs_host": (ci, [vp, P(UnitigRule), vp, sz, vp, sz, szp, szp, P(UnitigTotals)]),
+        "tsx_hip_write_unitigs_host": (ci, [vp, P(UnitigRule), ci, P(UnitigTotals)]),
+        "tsx_hip_unitig_last_timing": (ci, [dblp]),
         "tsx_hip_trim_pairs_host": (ci, [vp, ccp, sz, ccp, sz, P(TrimRule), ci, P(PairIO), sz, P(PairTotals)]),
         "tsx_hip_hash_apply": (ci, [vp, u64p, u64p]),
         "tsx_hip_hash_invert": (ci, [vp, u64p, u64p]),

@@ -13,6 +13,7 @@
 #include "tsx_combine.h"
 #include "tsx_joint.h"
 #include "tsx_het.h"
+#include "tsx_unitig.h"
 #include "tsx_bin.h"
 #include "tsx_fasta.h"
 #include "tsx_seq.h"
@@ -32,6 +33,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cerrno>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <deque>
@@ -4255,6 +4257,290 @@ extern "C" int tsx_hip_write_het_pairs_host(tsx_hip_map *m, const tsx_hip_het_ru
     if (pairs_out) *pairs_out = pairs;
     if (bytes_out) *bytes_out = bytes;
     return rc;
+}
+
+// ---- unitigs: the compacted de Bruijn graph of one table (tsx_unitig.h; DESIGN.md §3 "Unitigs") --------------------------
+static int unitig_check(const tsx_hip_map *m, const tsx_hip_unitig_rule *rule) {
+    if (!m || !rule) return combine_fail("unitigs: a map and a rule are needed");
+    if (m->p.lg != m->p.l) return combine_fail("unitigs: a map created with shard_bits > 0");
+    if (rule->lower > rule->upper) return combine_fail("unitigs: lower > upper");
+    if (rule->flags != 0 || rule->reserved != 0) return combine_fail("unitigs: flags and reserved must be 0");
+    if (m->canon && !(m->p.k & 1)) return combine_fail("unitigs: even k on a canonical table");
+    return TSX_HIP_OK;
+}
+static_assert(sizeof(tsx_hip_unitig_totals) == UT_PUBLIC * 8, "tsx_hip_unitig_totals is the kernels' first UT_PUBLIC totals");
+static_assert(sizeof(tsx_hip_unitig) == sizeof(UnitigRec), "tsx_hip_unitig is the kernels' record");
+
+// What the steps of the last unitig call of this thread took, in ms (host clock; every step waits for its totals): the
+// degree sweep, the walk of the starts, the spelling walk, the cycle pass (tsx_hip_unitig_last_timing).
+static thread_local double g_unitig_ms[4] = {0, 0, 0, 0};
+
+// One call's scratch and its three steps, all on st: degrees() = stage 1, walks() = stages 2 and 4, spell() = stage 3.
+// Each waits for its totals (h).  Extra device memory: one byte and one bit per slot, 8 bytes per record asked for.
+struct UnitigRun {
+    tsx_hip_map *m;
+    hipStream_t st;
+    UnitigArgs ua;
+    uint64_t slots = 0, grid = 1, rec_room = 0;
+    DevBuf<uint8_t> side;
+    DevBuf<uint32_t> covered;
+    DevBuf<unsigned long long> tot;
+    DevBuf<uint64_t> start;
+    unsigned long long h[UT_N];
+    double t0 = 0;   // host clock at the start of the step under way: every step ends waiting for its totals
+
+    static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    void timed(int stage) { const double t = now_ms(); g_unitig_ms[stage] += t - t0; t0 = t; }
+
+    int totals() {
+        HIP_TRY(hipMemcpyAsync(h, tot.get(), sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (h[UT_ERROR]) { g_last_error = "unitigs: the table is not consistent"; return TSX_HIP_EHIP; }
+        return TSX_HIP_OK;
+    }
+    void publish(tsx_hip_unitig_totals *out) const { if (out) memcpy(out, h, sizeof *out); }
+
+    int degrees(const tsx_hip_unitig_rule *rule, bool sec) {
+        memset(&ua, 0, sizeof ua);
+        memset(h, 0, sizeof h);
+        for (double &v : g_unitig_ms) v = 0;
+        ua.lower = std::max<uint64_t>(rule->lower, 1);
+        ua.upper = rule->upper;
+        ua.sec = sec ? 1 : 0;
+        ua.top_shift = (2 * (m->p.k - 1)) & 63;
+        for (uint64_t c = 1; c <= 3; ++c) {
+            uint64_t x[4] = {0, 0, 0, 0};
+            x[0] = c;
+            apply_rows(m, m->rows, x, ua.lo[c]);
+            x[0] = 0;
+            x[m->p.wk - 1] = c << ua.top_shift;
+            apply_rows(m, m->rows, x, ua.hi[c]);
+        }
+        slots = m->lay.slots;
+        const uint64_t tiles = (slots + UNITIG_TILE - 1) / UNITIG_TILE;
+        grid = std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)m->cus * 8));
+        auto per_wg = [&](uint64_t g) { return (tiles + g - 1) / g * UNITIG_TILE; };   // the lanes' sums are u32
+        while (per_wg(grid) >= (1ULL << 31) && grid < (1ULL << 30)) grid *= 2;
+        if (per_wg(grid) >= (1ULL << 31)) return combine_fail("unitigs: the table is too large");
+        TSX_TRY(side.alloc((size_t)slots));
+        TSX_TRY(covered.alloc((size_t)((slots + 31) / 32) * 4));
+        TSX_TRY(tot.alloc(UT_N * 8));
+        HIP_TRY(hipMemsetAsync(covered.get(), 0, covered.cap(), st));
+        HIP_TRY(hipMemsetAsync(tot.get(), 0, UT_N * 8, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        t0 = now_ms();
+        DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((unitig_degree_kernel<WKV, CANV>), dim3((unsigned)grid), dim3(NT), 0, st, m->p,
+                                                            ua, slots, side.get(), tot.get())));
+        if (hipGetLastError() != hipSuccess) { g_last_error = "unitig_degree_kernel launch"; return TSX_HIP_EHIP; }
+        TSX_TRY(totals());
+        timed(0);
+        ua.bound = h[UT_NODES] + 1;
+        return TSX_HIP_OK;
+    }
+
+    // d_rec: room for rec_cap records (null: totals only).  At most min(rec_cap, nodes) are written.
+    int walks(UnitigRec *d_rec, uint64_t rec_cap) {
+        rec_room = d_rec ? std::min<uint64_t>(rec_cap, h[UT_NODES]) : 0;
+        TSX_TRY(start.alloc((size_t)std::max<uint64_t>(rec_room, 1) * 8));
+        t0 = now_ms();
+        DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((unitig_walk_kernel<WKV, CANV>), dim3((unsigned)grid), dim3(NT), 0, st, m->p, ua,
+                                                            slots, side.get(), covered.get(), tot.get(), d_rec, start.get(), rec_room)));
+        if (hipGetLastError() != hipSuccess) { g_last_error = "unitig_walk_kernel launch"; return TSX_HIP_EHIP; }
+        TSX_TRY(totals());
+        timed(1);
+        DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((unitig_cycle_kernel<WKV, CANV>), dim3((unsigned)grid), dim3(NT), 0, st, m->p, ua,
+                                                            slots, side.get(), covered.get(), tot.get(), d_rec, start.get(), rec_room)));
+        if (hipGetLastError() != hipSuccess) { g_last_error = "unitig_cycle_kernel launch"; return TSX_HIP_EHIP; }
+        TSX_TRY(totals());
+        timed(3);
+        return TSX_HIP_OK;
+    }
+
+    // What walks() left is undone -- the covered bits and the four totals the walks add to -- so that it can run again.
+    int forget_walks() {
+        static_assert(UT_UNITIGS == 1 && UT_CIRCULAR == 2 && UT_BASES == 3 && UT_LONGEST == 4, "the walks' totals are words 1..4");
+        HIP_TRY(hipMemsetAsync(covered.get(), 0, covered.cap(), st));
+        HIP_TRY(hipMemsetAsync(tot.get() + UT_UNITIGS, 0, 4 * 8, st));
+        return TSX_HIP_OK;
+    }
+
+    // The records are all there (unitigs <= rec_room) and seq_cap >= bases: the caller has checked.
+    int spell(const UnitigRec *d_rec, uint8_t *d_seq, uint64_t seq_cap) {
+        const uint64_t n = h[UT_UNITIGS];
+        if (n > rec_room) { g_last_error = "unitigs: the table is not consistent"; return TSX_HIP_EHIP; }
+        if (n == 0) return TSX_HIP_OK;
+        const int g = grid_for(m, n, 8);
+        t0 = now_ms();
+        DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((unitig_spell_kernel<WKV, CANV>), dim3(g), dim3(NT), 0, st, m->p, ua, side.get(),
+                                                            d_rec, start.get(), n, seq_cap, d_seq, tot.get())));
+        if (hipGetLastError() != hipSuccess) { g_last_error = "unitig_spell_kernel launch"; return TSX_HIP_EHIP; }
+        TSX_TRY(totals());
+        timed(2);
+        return TSX_HIP_OK;
+    }
+};
+
+// The map is settled and the run has its stream; a caller's stream is waited for before the scratch goes away.
+static int unitig_begin(tsx_hip_map *m, const tsx_hip_unitig_rule *rule, void *stream, UnitigRun &run) {
+    HIP_TRY(hipSetDevice(m->device));
+    bool sec = false;
+    TSX_TRY(het_settle(m, &sec));
+    run.m = m;
+    run.st = pick_stream(m, stream);
+    return run.degrees(rule, sec);
+}
+
+extern "C" int tsx_hip_unitig_last_timing(double *ms_out) {
+    if (!ms_out) return TSX_HIP_EINVAL;
+    for (int i = 0; i < 4; ++i) ms_out[i] = g_unitig_ms[i];
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_unitig_stats(tsx_hip_map *m, const tsx_hip_unitig_rule *rule, tsx_hip_unitig_totals *totals) {
+    TSX_TRY(unitig_check(m, rule));
+    if (!totals) return combine_fail("unitigs: no totals");
+    UnitigRun run;
+    SyncAtExit wait(m->stream.get());
+    TSX_TRY(unitig_begin(m, rule, nullptr, run));
+    TSX_TRY(run.walks(nullptr, 0));
+    run.publish(totals);
+    return TSX_HIP_OK;
+}
+
+extern "C" int tsx_hip_unitigs_device(tsx_hip_map *m, const tsx_hip_unitig_rule *rule, void *dev_seq, size_t seq_cap, void *dev_records,
+                                      size_t record_cap, size_t *n_unitigs, size_t *seq_bytes, tsx_hip_unitig_totals *totals,
+                                      void *stream) {
+    TSX_TRY(unitig_check(m, rule));
+    if (!n_unitigs || !seq_bytes || (!dev_seq && seq_cap) || (!dev_records && record_cap)) return combine_fail("unitigs: no output");
+    *n_unitigs = *seq_bytes = 0;
+    UnitigRun run;
+    SyncAtExit wait(stream ? (hipStream_t)stream : m->stream.get());
+    TSX_TRY(unitig_begin(m, rule, stream, run));
+    TSX_TRY(run.walks(record_cap ? (UnitigRec *)dev_records : nullptr, record_cap));
+    *n_unitigs = (size_t)run.h[UT_UNITIGS];
+    *seq_bytes = (size_t)run.h[UT_BASES];
+    run.publish(totals);
+    if (run.h[UT_UNITIGS] > record_cap || run.h[UT_BASES] > seq_cap) return TSX_HIP_ERANGE;
+    return run.spell((const UnitigRec *)dev_records, (uint8_t *)dev_seq, seq_cap);
+}
+
+// Record room (40 + 8 bytes a record) above which the walks run once for the number of unitigs before they run for the
+// records: below it the room is simply min(record_cap, nodes).  TSX_HIP_UNITIG_SIZING_BYTES: tests take the sizing walk
+// on small tables.
+static uint64_t unitig_sizing_bytes() {
+    if (const char *e = getenv("TSX_HIP_UNITIG_SIZING_BYTES")) return strtoull(e, nullptr, 10);
+    return (uint64_t)256 << 20;
+}
+
+// Stages 1, 2 and 4 with records, then the sequences in a buffer of exactly their size.  The record room is
+// min(record_cap, nodes); when that is large the walks first run without records and the room is the unitigs (one walk
+// more, 48 bytes a unitig instead of 48 bytes a node).  ERANGE (sizes reported, nothing spelled) when a cap is too small.
+static int unitig_make(tsx_hip_map *m, const tsx_hip_unitig_rule *rule, uint64_t seq_cap, uint64_t record_cap, UnitigRun &run,
+                       DevBuf<UnitigRec> &d_rec, DevBuf<uint8_t> &d_seq) {
+    TSX_TRY(unitig_begin(m, rule, nullptr, run));
+    uint64_t room = std::min<uint64_t>(record_cap, run.h[UT_NODES]);
+    if (room > unitig_sizing_bytes() / (sizeof(UnitigRec) + 8)) {
+        TSX_TRY(run.walks(nullptr, 0));
+        if (run.h[UT_UNITIGS] > record_cap || run.h[UT_BASES] > seq_cap) return TSX_HIP_ERANGE;
+        room = run.h[UT_UNITIGS];
+        TSX_TRY(run.forget_walks());
+    }
+    TSX_TRY(d_rec.alloc((size_t)std::max<uint64_t>(room, 1) * sizeof(UnitigRec)));
+    TSX_TRY(run.walks(room ? d_rec.get() : nullptr, room));
+    if (run.h[UT_UNITIGS] > record_cap || run.h[UT_BASES] > seq_cap) return TSX_HIP_ERANGE;
+    TSX_TRY(d_seq.alloc((size_t)std::max<uint64_t>(run.h[UT_BASES], 1)));
+    return run.spell(d_rec.get(), d_seq.get(), run.h[UT_BASES]);
+}
+
+extern "C" int tsx_hip_unitigs_host(tsx_hip_map *m, const tsx_hip_unitig_rule *rule, void *seq_out, size_t seq_cap,
+                                    tsx_hip_unitig *records_out, size_t record_cap, size_t *n_unitigs, size_t *seq_bytes,
+                                    tsx_hip_unitig_totals *totals) {
+    TSX_TRY(unitig_check(m, rule));
+    if (!n_unitigs || !seq_bytes || (!seq_out && seq_cap) || (!records_out && record_cap)) return combine_fail("unitigs: no output");
+    *n_unitigs = *seq_bytes = 0;
+    UnitigRun run;
+    DevBuf<UnitigRec> d_rec;
+    DevBuf<uint8_t> d_seq;
+    SyncAtExit wait(m->stream.get());
+    const int rc = unitig_make(m, rule, seq_cap, record_cap, run, d_rec, d_seq);
+    if (rc != TSX_HIP_OK && rc != TSX_HIP_ERANGE) return rc;
+    *n_unitigs = (size_t)run.h[UT_UNITIGS];
+    *seq_bytes = (size_t)run.h[UT_BASES];
+    run.publish(totals);
+    if (rc != TSX_HIP_OK) return rc;
+    hipStream_t st = m->stream.get();
+    if (*n_unitigs) HIP_TRY(hipMemcpyAsync(records_out, d_rec.get(), *n_unitigs * sizeof(UnitigRec), hipMemcpyDeviceToHost, st));
+    if (*seq_bytes) HIP_TRY(hipMemcpyAsync(seq_out, d_seq.get(), *seq_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return TSX_HIP_OK;
+}
+
+// FASTA behind the device: the records come over whole and are put in the order of their offsets -- they tile the
+// sequence buffer -- then the sequences follow in pieces of whole records through two pinned buffers, piece i + 1 on its
+// way while piece i is formatted and written.
+extern "C" int tsx_hip_write_unitigs_host(tsx_hip_map *m, const tsx_hip_unitig_rule *rule, int fd, tsx_hip_unitig_totals *totals) {
+    TSX_TRY(unitig_check(m, rule));
+    if (fd < 0) return combine_fail("unitigs: no output");
+    UnitigRun run;
+    DevBuf<UnitigRec> d_rec;
+    DevBuf<uint8_t> d_seq;
+    PinBuf<uint8_t> pin[2];
+    Event ready[2];
+    SyncAtExit wait(m->stream.get());
+    TSX_TRY(unitig_make(m, rule, ~0ULL, ~0ULL, run, d_rec, d_seq));
+    run.publish(totals);
+    const uint64_t n = run.h[UT_UNITIGS], bases = run.h[UT_BASES];
+    if (n == 0) return TSX_HIP_OK;
+    hipStream_t st = m->stream.get();
+    std::vector<UnitigRec> rec((size_t)n);
+    HIP_TRY(hipMemcpyAsync(rec.data(), d_rec.get(), (size_t)n * sizeof(UnitigRec), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::sort(rec.begin(), rec.end(), [](const UnitigRec &x, const UnitigRec &y) { return x.offset < y.offset; });
+    uint64_t at = 0;
+    for (const UnitigRec &u : rec) {   // the records tile [0, bases)
+        if (u.offset != at || u.length > bases - at) { g_last_error = "unitigs: the table is not consistent"; return TSX_HIP_EHIP; }
+        at += u.length;
+    }
+    const uint64_t piece = std::min<uint64_t>(bases, std::max<uint64_t>(WRITE_CHUNK_DEFAULT / 4, run.h[UT_LONGEST]));
+    for (int i = 0; i < 2; ++i) { TSX_TRY(pin[i].alloc((size_t)piece)); TSX_TRY(ready[i].create()); }
+    // [r0, r1): the records of the piece that starts at record r0
+    auto piece_end = [&](uint64_t r0) {
+        uint64_t r1 = r0, bytes = 0;
+        while (r1 < n && bytes + rec[(size_t)r1].length <= piece) bytes += rec[(size_t)r1++].length;
+        return r1;
+    };
+    auto fetch = [&](uint64_t r0, uint64_t r1, int b) -> int {
+        const uint64_t lo = rec[(size_t)r0].offset, hi = rec[(size_t)r1 - 1].offset + rec[(size_t)r1 - 1].length;
+        HIP_TRY(hipMemcpyAsync(pin[b].get(), d_seq.get() + lo, (size_t)(hi - lo), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(ready[b].get(), st));
+        return TSX_HIP_OK;
+    };
+    std::vector<uint8_t> text;
+    uint64_t r0 = 0, r1 = piece_end(0);
+    TSX_TRY(fetch(r0, r1, 0));
+    for (int b = 0; r0 < n; b ^= 1) {
+        const uint64_t r2 = r1 < n ? piece_end(r1) : r1;
+        if (r1 < n) TSX_TRY(fetch(r1, r2, b ^ 1));
+        HIP_TRY(hipEventSynchronize(ready[b].get()));
+        const uint64_t base = rec[(size_t)r0].offset;
+        size_t need = 0;
+        for (uint64_t r = r0; r < r1; ++r) need += (size_t)rec[(size_t)r].length + 128;
+        text.resize(need);
+        size_t w = 0;
+        for (uint64_t r = r0; r < r1; ++r) {
+            const UnitigRec &u = rec[(size_t)r];
+            w += (size_t)snprintf((char *)text.data() + w, 120, ">%llu LN:i:%llu KC:i:%llu km:f:%.1f%s\n", (unsigned long long)r,
+                                  (unsigned long long)u.length, (unsigned long long)u.sum_count,
+                                  (double)u.sum_count / (double)u.kmers, u.circular ? " CL:i:1" : "");
+            memcpy(text.data() + w, pin[b].get() + (u.offset - base), (size_t)u.length);
+            w += (size_t)u.length;
+            text[w++] = '\n';
+        }
+        TSX_TRY(write_all(fd, text.data(), w));
+        r0 = r1;
+        r1 = r2;
+    }
+    return TSX_HIP_OK;
 }
 
 extern "C" int tsx_hip_owner_host(const tsx_hip_map *m, const uint64_t *kmer, int nranks) {

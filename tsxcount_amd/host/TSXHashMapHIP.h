@@ -597,6 +597,45 @@ public:
         });
     }
 
+    // unitigs of this table, the compacted de Bruijn graph (tsx_hip_unitig_stats): the totals alone, nothing spelled
+    tsx_hip_unitig_totals unitigStats(const tsx_hip_unitig_rule &oRule) {
+        tsx_hip_unitig_totals t = tsx_hip_unitig_totals();
+        const int rc = tsx_hip_unitig_stats(m_pMap, &oRule, &t);
+        if (rc == TSX_HIP_EINVAL) throw TSXException(tsx_hip_last_error(), rc);   // (the refusal says which argument)
+        check(rc);
+        return t;
+    }
+    // the unitigs themselves (tsx_hip_unitigs_host): the sequence of record r is sSeq.substr(r.offset, r.length); a first
+    // guess of the room, then once more with the sizes the library reports
+    tsx_hip_unitig_totals unitigs(const tsx_hip_unitig_rule &oRule, std::string &sSeq, std::vector<tsx_hip_unitig> &oRecords) {
+        tsx_hip_unitig_totals t = tsx_hip_unitig_totals();
+        size_t n = 0, iBytes = 0;
+        sSeq.assign((size_t)1 << 18, '\0');
+        oRecords.assign((size_t)1 << 12, tsx_hip_unitig());
+        int rc = tsx_hip_unitigs_host(m_pMap, &oRule, &sSeq[0], sSeq.size(), oRecords.data(), oRecords.size(), &n, &iBytes, &t);
+        if (rc == TSX_HIP_ERANGE) {
+            sSeq.assign(iBytes + 1, '\0');
+            oRecords.assign(n + 1, tsx_hip_unitig());
+            rc = tsx_hip_unitigs_host(m_pMap, &oRule, &sSeq[0], sSeq.size(), oRecords.data(), oRecords.size(), &n, &iBytes, &t);
+        }
+        if (rc == TSX_HIP_EINVAL) throw TSXException(tsx_hip_last_error(), rc);
+        check(rc);
+        sSeq.resize(iBytes);
+        oRecords.resize(n);
+        return t;
+    }
+    // the unitigs as FASTA with BCALM's header (tsx_hip_write_unitigs_host), the file created / truncated
+    tsx_hip_unitig_totals writeUnitigs(const std::string &sPath, const tsx_hip_unitig_rule &oRule) {
+        tsx_hip_unitig_totals t = tsx_hip_unitig_totals();
+        tsx_write_counts_file(sPath, [&](int fd, uint64_t *, uint64_t *) {
+            return tsx_hip_write_unitigs_host(m_pMap, &oRule, fd, &t);
+        }, [&](int rc) {
+            if (rc == TSX_HIP_EINVAL) throw TSXException(tsx_hip_last_error(), rc);
+            check(rc);
+        });
+        return t;
+    }
+
     // read binning by two tables (tsx_hip_bin_stats_host): this is A, oOther is B; per record the windows that hit each
     // table, and (pClasses) its class TSX_HIP_BIN_*
     std::vector<tsx_hip_bin_stats> binStats(TSXHashMapHIP &oOther, const char *pText, size_t iBytes, const tsx_hip_bin_rule &oRule,
