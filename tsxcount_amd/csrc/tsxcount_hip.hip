@@ -2339,6 +2339,11 @@ static int base_rule_ok(const tsx_hip_map *m) {
     return TSX_HIP_OK;
 }
 
+// A non-empty line and its '\n' are two bytes: no text of n bytes holds more records than this.
+static uint64_t max_records(const tsx_hip_map *m, uint64_t n) { return n / (2 * ((uint64_t)m->p.line_mask + 1)) + 2; }
+// What turns a line index into a record index: 4 lines a record (FASTQ) or 2.
+static uint32_t line_shift(const tsx_hip_map *m) { return m->p.line_mask == 3 ? 2u : 1u; }
+
 // m->d_qmap.get() = the low-quality bitmap of d_text[0, n), a text that starts at a record boundary.  Uses the map's line
 // scratch (d_tile, word 0 of d_carry) and waits once, for the line count.  The scan launches get it as qmap_cur.
 static int build_qmap(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, hipStream_t st) {
@@ -2397,7 +2402,7 @@ struct PieceBufs {
 static int piece_scan(tsx_hip_map *m, const uint8_t *d_text, uint64_t len, bool last, unsigned long long *info,
                       DevBuf<unsigned long long> *span, hipStream_t st) {
     const uint32_t lpr = m->p.line_mask + 1;
-    const uint64_t ntiles = (len + TILE - 1) / TILE, span_cap = len / (2 * lpr) + 2;
+    const uint64_t ntiles = (len + TILE - 1) / TILE, span_cap = max_records(m, len);
     int rc;
     HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
     if ((rc = line_pass(m, d_text, len, len, 0, st)) != TSX_HIP_OK) return rc;
@@ -4721,7 +4726,7 @@ static int query_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint6
     const uint64_t ntiles = (own_end + TILE - 1) / TILE;
     const size_t lut_bytes = m->lut.size() * 8;
     const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 4);
-    const uint32_t lshift = m->p.line_mask == 3 ? 2u : 1u;
+    const uint32_t lshift = line_shift(m);
     DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((query_reads_kernel<WKV, CANV, BRV>), dim3(grid), dim3(NT),
                                                         lut_bytes, st, m->p, d_text, n, own_end, head_open,
                                                         (const uint32_t *)m->d_tile.get(), ntiles, d_line_base, lshift, lower, upper,
@@ -4780,24 +4785,30 @@ static int windows_records(tsx_hip_map *m, size_t cap, size_t *n_records, hipStr
     return nrec > cap ? TSX_HIP_ERANGE : TSX_HIP_OK;
 }
 
+// What the device entry points of the read calls do first: the device, the stream (a caller's, or the map's behind it),
+// a lazily cleared table zeroed before anyone reads it, the base rule.  In this order for every call: one that is refused
+// for its base rule has zeroed a lazily cleared table on its way, which the next call would have done.
+static int device_begin(tsx_hip_map *m, void *stream, hipStream_t &st) {
+    HIP_TRY(hipSetDevice(m->device));
+    st = pick_stream(m, stream);
+    TSX_TRY(ensure_zeroed(m, st));
+    return base_rule_ok(m);
+}
+
 extern "C" int tsx_hip_query_reads_device(tsx_hip_map *m, const void *dev_text, size_t n, uint64_t lower, uint64_t upper,
                                           void *dev_stats, size_t stats_cap, size_t *n_records, void *stream) {
     if (n_records) *n_records = 0;
     if (!query_args_ok(m, lower, upper) || (!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_stats && stats_cap))
         return TSX_HIP_EINVAL;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
-    int rc = ensure_zeroed(m, st);
-    if (rc != TSX_HIP_OK) return rc;
-    if ((rc = base_rule_ok(m)) != TSX_HIP_OK) return rc;
+    hipStream_t st;
+    TSX_TRY(device_begin(m, stream, st));
     const uint8_t *base = (const uint8_t *)dev_text;
     unsigned long long *stats = (unsigned long long *)dev_stats;
     if (stats_cap) HIP_TRY(hipMemsetAsync(stats, 0, stats_cap * sizeof(tsx_hip_read_stats), st));
-    rc = device_windows(m, base, n, false, st,
-                        [&](size_t off, size_t own, size_t len, int head_open, bool, const unsigned long long *d_base) {
-                            return query_launch(m, base + off, len, own, head_open, d_base, lower, upper, stats, stats_cap, st);
-                        });
-    if (rc != TSX_HIP_OK) return rc;
+    TSX_TRY(device_windows(m, base, n, false, st,
+                           [&](size_t off, size_t own, size_t len, int head_open, bool, const unsigned long long *d_base) {
+                               return query_launch(m, base + off, len, own, head_open, d_base, lower, upper, stats, stats_cap, st);
+                           }));
     if (stats_cap)
         hipLaunchKernelGGL(query_finalize_kernel, dim3(grid_for(m, stats_cap, 8)), dim3(NT), 0, st, stats, (uint64_t)stats_cap,
                            (const unsigned long long *)m->d_carry.get() + 3, (uint64_t)0);
@@ -4819,10 +4830,59 @@ struct OutBuf {
     }
 };
 
+// Room in `buf` for n + 1 lengths that are scanned in place: one partial sum per SCAN_CHUNK of them lies behind them.
+static int scan_room(hipStream_t st, DevBuf<unsigned long long> &buf, uint64_t n) {
+    const uint64_t nk = n + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    return grow(st, buf, (nk + nchunks + 16) * sizeof(unsigned long long));
+}
+
+// The scan of the n + 1 lengths at `off` in place (scan_room behind them): offsets, their total to *total.  Queued.
+static int scan_lengths(unsigned long long *off, uint64_t n, unsigned long long *total, hipStream_t st) {
+    const uint64_t nk = n + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    unsigned long long *chunk = off + nk;
+    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)off, nk, chunk);
+    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, total);
+    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, off, nk, (const unsigned long long *)chunk);
+    HIP_TRY(hipGetLastError());
+    return TSX_HIP_OK;
+}
+
+// One compaction of a piece: the lengths a call's kernel writes (one or more per record; several arrays may share the
+// buffer: the caller hands out entry ranges), scanned in place into offsets, and the output they describe.
+struct Compaction {
+    DevBuf<unsigned long long> off;
+    OutBuf out;
+    // room for n + 1 entries and their chunk sums, entry n zeroed (the scan reads it): the array, for the call's kernel
+    int lengths(hipStream_t st, uint64_t n, unsigned long long *&len) {
+        TSX_TRY(scan_room(st, off, n));
+        HIP_TRY(hipMemsetAsync(off.get() + n, 0, sizeof(unsigned long long), st));
+        len = off.get();
+        return TSX_HIP_OK;
+    }
+    // What both copy steps are: room in out for a piece cut at `cut`, the scan (the total goes to *total), then `kern` moves
+    // d_text[0, cut) into out by what `by` holds -- the copy grid covers the worst case, lanes past the total fall through.
+    // Queued, not waited for.
+    template <class Kernel>
+    int copy(Kernel kern, tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, const unsigned long long *by, uint64_t n,
+             unsigned long long *total, hipStream_t st) {
+        TSX_TRY(out.room(st, cut));
+        TSX_TRY(scan_lengths(off.get(), n, total, st));
+        hipLaunchKernelGGL(kern, dim3(grid_for(m, (cut + 16) / 16 + 64, 8)), dim3(NT), 0, st, d_text, cut, by,
+                           (const unsigned long long *)off.get(), n, out.out, (uint64_t)out.have);
+        HIP_TRY(hipGetLastError());
+        return TSX_HIP_OK;
+    }
+    // by the record spans; by segments, each with its source in src
+    int copy_spans(tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, const unsigned long long *span, uint64_t n,
+                   unsigned long long *total, hipStream_t st) { return copy(filter_copy_kernel, m, d_text, cut, span, n, total, st); }
+    int copy_segments(tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, const unsigned long long *src, uint64_t n,
+                      unsigned long long *total, hipStream_t st) { return copy(trim_copy_kernel, m, d_text, cut, src, n, total, st); }
+};
+
 // Scratch of one query / filter call that works on pieces.
 struct QueryBufs {
-    DevBuf<unsigned long long> stats, koff;
-    OutBuf out;        // the filter's output
+    DevBuf<unsigned long long> stats;
+    Compaction c;      // the filter's kept lengths and its output
     PieceBufs p;
     explicit QueryBufs(hipStream_t s) : p(s) {}
 };
@@ -4851,39 +4911,17 @@ static int query_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint
     return query_records(m, b, d_text, cut, nrec, lower, upper, st);
 }
 
-// The scan of nrec + 1 kept lengths in place (koff has room for the chunk sums behind them; the total goes to *total) and
-// the output they describe: the spans of d_text[0, cut) through filter_copy_kernel into out (out_have bytes >= cut + 64).
-static int filter_compact(tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, const unsigned long long *span,
-                          unsigned long long *koff, uint64_t nrec, unsigned long long *total, uint8_t *out, uint64_t out_have,
-                          hipStream_t st) {
-    const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    unsigned long long *chunk = koff + nk;
-    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)koff,
-                       nk, chunk);
-    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, total);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, koff, nk,
-                       (const unsigned long long *)chunk);
-    // (the copy grid covers the worst case; lanes past the total fall through)
-    hipLaunchKernelGGL(filter_copy_kernel, dim3(grid_for(m, (cut + 16) / 16 + 64, 8)), dim3(NT), 0, st, d_text, cut,
-                       span, (const unsigned long long *)koff, nrec, out, out_have);
-    HIP_TRY(hipGetLastError());
-    return TSX_HIP_OK;
-}
-
 // The filter behind query_piece: kept lengths, their scan (total -> info[3], kept records -> info[5]), the compaction
-// into b.out.  Queued, not waited for.
+// into b.c.out.  Queued, not waited for.
 static int filter_piece(tsx_hip_map *m, QueryBufs &b, const uint8_t *d_text, uint64_t cut, uint64_t nrec, bool open,
                         const tsx_hip_filter_rule &rule, hipStream_t st) {
-    const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    TSX_TRY(grow(st, b.koff, (nk + nchunks + 16) * sizeof(unsigned long long)));
-    TSX_TRY(b.out.room(st, cut));
-    unsigned long long *const koff = b.koff.get(), *const info = b.p.info.get();
+    unsigned long long *koff, *const info = b.p.info.get();
     const unsigned long long *span = b.p.rspan.get();
-    HIP_TRY(hipMemsetAsync(koff + nrec, 0, sizeof(unsigned long long), st));
+    TSX_TRY(b.c.lengths(st, nrec, koff));
     hipLaunchKernelGGL(filter_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, (const unsigned long long *)b.stats.get(),
                        span, nrec, rule.min_in_range, (uint64_t)rule.fraction_ppm, rule.invert,
                        open ? 1 : 0, koff, info + 5);
-    return filter_compact(m, d_text, cut, span, koff, nrec, info + 3, b.out.out, (uint64_t)b.out.have, st);
+    return b.c.copy_spans(m, d_text, cut, span, nrec, info + 3, st);
 }
 
 static bool rule_ok(const tsx_hip_filter_rule *r) {
@@ -4977,23 +5015,53 @@ struct WriteBehind {
         pending = total;
         return TSX_HIP_OK;
     }
-    // One piece of a single-end call, behind the kernels that leave its output at d_out, its size in info[3] and
-    // `ncount` counters in info[5..]: the previous piece is written while they run, then this one is staged, its
-    // counters are added to count[] and start from zero again (they are per piece).
+    // One round (a piece; a round of pairs) of a call with the outputs w[0, nout) (fd < 0: not wanted), behind the kernels
+    // that leave the outputs on the device and their sizes and counters in the call's words.  In two steps, so that a
+    // call can look at the words in between.
+    // Step 1: nwords of d_words to their pinned copy.  The previous round's outputs are written to their files between
+    // the event record and the event wait: while the device works on this round.
+    static int words_back(WriteBehind *w, int nout, const unsigned long long *d_words, unsigned long long *h_words, size_t nwords,
+                          hipEvent_t ev, hipStream_t st) {
+        HIP_TRY(hipMemcpyAsync(h_words, d_words, nwords * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(ev, st));
+        for (int i = 0; i < nout; ++i) TSX_TRY(w[i].flush());
+        HIP_TRY(hipEventSynchronize(ev));
+        return TSX_HIP_OK;
+    }
+    // Step 2: output i is staged from d_out[i], size[i] bytes of a piece cut at cut[i]; a wait when there are bytes; then
+    // the nzero words at d_zero start from zero again (sizes and counters are per round).
+    static int stage_all(WriteBehind *w, int nout, const uint8_t *const *d_out, const unsigned long long *size, const uint64_t *cut,
+                         const char *what, unsigned long long *d_zero, size_t nzero, hipStream_t st) {
+        bool any = false;
+        for (int i = 0; i < nout; ++i) {
+            if (w[i].fd < 0) continue;
+            TSX_TRY(w[i].stage(d_out[i], size[i], cut[i], what, st));
+            any |= size[i] != 0;
+        }
+        if (any) HIP_TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipMemsetAsync(d_zero, 0, nzero * sizeof(unsigned long long), st));
+        return TSX_HIP_OK;
+    }
+    // One piece of a single-end call: the output at d_out, its size in info[3] and `ncount` counters in info[5..], which
+    // are added to count[].
     int piece(PieceBufs &p, const uint8_t *d_out, uint64_t cut, int ncount, uint64_t *count, const char *what) {
         const unsigned long long *h_info = p.h_info.get();
-        HIP_TRY(hipMemcpyAsync(p.h_info.get() + 3, p.info.get() + 3, (2 + ncount) * sizeof(unsigned long long), hipMemcpyDeviceToHost, p.st));
-        HIP_TRY(hipEventRecord(p.ev.get(), p.st));
-        TSX_TRY(flush());   // the previous piece's output, while the device works on this one
-        HIP_TRY(hipEventSynchronize(p.ev.get()));
-        const uint64_t total = h_info[3];
-        TSX_TRY(stage(d_out, total, cut, what, p.st));
+        TSX_TRY(words_back(this, 1, p.info.get() + 3, p.h_info.get() + 3, 2 + ncount, p.ev.get(), p.st));
+        TSX_TRY(stage_all(this, 1, &d_out, h_info + 3, &cut, what, p.info.get() + 5, ncount, p.st));
         for (int i = 0; i < ncount; ++i) count[i] += h_info[5 + i];
-        if (total) HIP_TRY(hipStreamSynchronize(p.st));
-        HIP_TRY(hipMemsetAsync(p.info.get() + 5, 0, ncount * sizeof(unsigned long long), p.st));
         return TSX_HIP_OK;
     }
 };
+
+// The last step of the calls that leave one piece's output in a caller's device buffer: info[3, 3 + nwords) to the pinned
+// copy (h: set once they are there), the wait, and a total above cut + 1 refused.
+static int piece_words(PieceBufs &p, int nwords, uint64_t cut, const char *what, const unsigned long long *&h) {
+    HIP_TRY(hipMemcpyAsync(p.h_info.get() + 3, p.info.get() + 3, nwords * sizeof(unsigned long long), hipMemcpyDeviceToHost, p.st));
+    HIP_TRY(hipStreamSynchronize(p.st));
+    h = p.h_info.get();
+    if (h[3] > cut + 1) { g_last_error = std::string(what) + " output larger than its text"; return TSX_HIP_EHIP; }
+    return TSX_HIP_OK;
+}
 
 // Query and filter: the pieces of host_pieces.  stats mode (fd < 0): each piece's stats go to stats_out[rec_base ..]
 // while they fit.  filter mode: write-behind to fd.
@@ -5013,7 +5081,7 @@ static int query_host(tsx_hip_map *m, const char *text, size_t n, uint64_t lower
             if (!rule) return deliver_records(stats_out, stats_cap, base, b.stats.get(), nrec, st);
             if (!nrec) return TSX_HIP_OK;
             TSX_TRY(filter_piece(m, b, b.p.text.get(), cut, nrec, open, *rule, st));
-            return wb.piece(b.p, b.out.out, cut, 1, &kept, "filter");
+            return wb.piece(b.p, b.c.out.out, cut, 1, &kept, "filter");
         });
     if (rc == TSX_HIP_OK) rc = wb.flush();
     if (n_records) *n_records = (size_t)rec_base;
@@ -5046,27 +5114,19 @@ extern "C" int tsx_hip_filter_reads_device(tsx_hip_map *m, const void *dev_text,
         !dev_out || ((uintptr_t)dev_out & 15) || n >= QUERY_PIECE_MAX)
         return TSX_HIP_EINVAL;
     if (out_cap < n + 64) return TSX_HIP_ERANGE;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
-    int rc = base_rule_ok(m);
-    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
-    if (rc != TSX_HIP_OK) return rc;
+    hipStream_t st;
+    TSX_TRY(device_begin(m, stream, st));
     QueryBufs b(st);
-    rc = b.p.init();
-    b.out.out = (uint8_t *)dev_out; b.out.have = out_cap;   // the compaction writes the caller's buffer (never grown)
-    uint64_t cut = 0, nrec = 0, total = 0, kept = 0;
+    int rc = b.p.init();
+    b.c.out.out = (uint8_t *)dev_out; b.c.out.have = out_cap;   // the compaction writes the caller's buffer (never grown)
+    uint64_t cut = 0, nrec = 0;
     bool open = false;
+    const unsigned long long *h = nullptr;
     if (rc == TSX_HIP_OK) rc = query_piece(m, b, (const uint8_t *)dev_text, n, true, rule->lower, rule->upper, true, st, cut, nrec, open);
-    if (rc == TSX_HIP_OK && nrec) {
-        rc = filter_piece(m, b, (const uint8_t *)dev_text, cut, nrec, open, *rule, st);
-        if (rc == TSX_HIP_OK && (hipMemcpyAsync(b.p.h_info.get() + 3, b.p.info.get() + 3, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                                 hipStreamSynchronize(st) != hipSuccess))
-            rc = TSX_HIP_EHIP;
-        if (rc == TSX_HIP_OK) { total = b.p.h_info.get()[3]; kept = b.p.h_info.get()[5]; }
-        if (rc == TSX_HIP_OK && total > cut + 1) { g_last_error = "filter output larger than its text"; rc = TSX_HIP_EHIP; }
-    }
-    if (out_bytes) *out_bytes = (size_t)total;
-    if (kept_out) *kept_out = kept;
+    if (rc == TSX_HIP_OK && nrec) rc = filter_piece(m, b, (const uint8_t *)dev_text, cut, nrec, open, *rule, st);
+    if (rc == TSX_HIP_OK && nrec) rc = piece_words(b.p, 3, cut, "filter", h);
+    if (out_bytes && h) *out_bytes = (size_t)h[3];
+    if (kept_out && h) *kept_out = h[5];
     return rc;
 }
 
@@ -5229,17 +5289,13 @@ static int track_launch(SeqRun &R, const uint8_t *two, uint64_t ub, uint64_t nre
     tsx_hip_map *m = R.m;
     hipStream_t st = R.st;
     const uint64_t W = R.window, cap = ub / W + nrec + 1;
-    const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    TSX_TRY(grow(st, R.row_of, (nk + nchunks + 16) * sizeof(unsigned long long)));
+    TSX_TRY(scan_room(st, R.row_of, nrec));
     TSX_TRY(grow(st, R.bins, cap * sizeof(tsx_hip_seq_bin)));
     HIP_TRY(hipMemsetAsync(R.bins.get(), 0, cap * sizeof(tsx_hip_seq_bin), st));
     const unsigned long long *span = R.p.rspan.get(), *d_base = R.p.info.get() + 4;
-    unsigned long long *row_of = R.row_of.get(), *chunk = row_of + nk, *d_total = R.words.get();
-    hipLaunchKernelGGL(track_rows_kernel, dim3(grid_for(m, nk, 8)), dim3(NT), 0, st, span, nrec, W, row0_off, row_of);
-    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)row_of, nk, chunk);
-    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, d_total);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, row_of, nk, (const unsigned long long *)chunk);
-    HIP_TRY(hipGetLastError());
+    unsigned long long *row_of = R.row_of.get(), *d_total = R.words.get();
+    hipLaunchKernelGGL(track_rows_kernel, dim3(grid_for(m, nrec + 1, 8)), dim3(NT), 0, st, span, nrec, W, row0_off, row_of);
+    TSX_TRY(scan_lengths(row_of, nrec, d_total, st));
     const uint64_t ntiles = (ub + TILE - 1) / TILE;
     const size_t lut_bytes = m->lut.size() * 8;
     const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 4);
@@ -5654,7 +5710,7 @@ static int bin_launch(tsx_hip_map *a, const tsx_hip_map *b, const uint8_t *d_tex
     const bool one = a->seed == b->seed && a->lut == b->lut;
     const size_t lds = a->lut.size() * 8 * (one ? 1 : 2);
     const int grid = (int)std::min<uint64_t>(ntiles, (uint64_t)a->cus * 4);
-    const uint32_t lshift = a->p.line_mask == 3 ? 2u : 1u;
+    const uint32_t lshift = line_shift(a);
     const BinRanges rg = {std::max<uint64_t>(1, r.a_lower), r.a_upper, std::max<uint64_t>(1, r.b_lower), r.b_upper};
     hipError_t attr = hipSuccess;
 #define TSX_BIN(FORMV)                                                                                                       \
@@ -5690,18 +5746,13 @@ extern "C" int tsx_hip_bin_stats_device(tsx_hip_map *a, tsx_hip_map *b, const vo
     return windows_records(a, stats_cap, n_records, st);
 }
 
-// One output of a bin call: the lengths of its class (scanned in place) and the compacted bytes.
-struct BinOut {
-    DevBuf<unsigned long long> off;
-    OutBuf out;
-};
 // Scratch of one bin call that works on pieces.  words: the records of each class [0..4), the bytes of each output [4..8).
 struct BinBufs {
     DevBuf<unsigned long long> stats;
     DevBuf<uint8_t> cls;
     DevBuf<unsigned long long> words;
     PinBuf<unsigned long long> h_words;
-    BinOut out[4];
+    Compaction out[4];   // one per class: its lengths and its bytes
     PieceBufs p;
     explicit BinBufs(hipStream_t s) : p(s) {}
     int init() {
@@ -5753,34 +5804,22 @@ static int bin_host(tsx_hip_map *a, tsx_hip_map *b, const char *text, size_t n, 
                 return class_out ? deliver_records(class_out, stats_cap, base, bb.cls.get(), nrec, st) : TSX_HIP_OK;
             }
             if (!nrec) return TSX_HIP_OK;
-            const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
             unsigned long long *const words = bb.words.get();
             const unsigned long long *h = bb.h_words.get();
+            const uint8_t *d_out[4] = {nullptr, nullptr, nullptr, nullptr};
+            const uint64_t cuts[4] = {cut, cut, cut, cut};
             for (uint32_t c = 0; c < 4; ++c) {   // the existing scan and copy kernels, once per wanted output
                 if (wb[c].fd < 0) continue;
-                BinOut &o = bb.out[c];
-                TSX_TRY(grow(st, o.off, (nk + nchunks + 16) * sizeof(unsigned long long)));
-                TSX_TRY(o.out.room(st, cut));
-                HIP_TRY(hipMemsetAsync(o.off.get() + nrec, 0, sizeof(unsigned long long), st));
+                unsigned long long *len;
+                TSX_TRY(bb.out[c].lengths(st, nrec, len));
                 hipLaunchKernelGGL(bin_len_kernel, dim3(grid_for(a, nrec, 8)), dim3(NT), 0, st, (const uint8_t *)bb.cls.get(),
-                                   (const unsigned long long *)bb.p.rspan.get(), nrec, c, open ? 1 : 0, o.off.get());
-                TSX_TRY(filter_compact(a, bb.p.text.get(), cut, bb.p.rspan.get(), o.off.get(), nrec, words + 4 + c, o.out.out,
-                                       (uint64_t)o.out.have, st));
+                                   (const unsigned long long *)bb.p.rspan.get(), nrec, c, open ? 1 : 0, len);
+                TSX_TRY(bb.out[c].copy_spans(a, bb.p.text.get(), cut, bb.p.rspan.get(), nrec, words + 4 + c, st));
+                d_out[c] = bb.out[c].out.out;
             }
-            HIP_TRY(hipMemcpyAsync(bb.h_words.get(), words, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipEventRecord(bb.p.ev.get(), st));
-            for (WriteBehind &w : wb) TSX_TRY(w.flush());   // the previous piece's outputs, while the device works on this one
-            HIP_TRY(hipEventSynchronize(bb.p.ev.get()));
-            bool any = false;
-            for (uint32_t c = 0; c < 4; ++c) {
-                t.n[c] += h[c];
-                if (wb[c].fd < 0) continue;
-                TSX_TRY(wb[c].stage(bb.out[c].out.out, h[4 + c], cut, "bin", st));
-                any |= h[4 + c] != 0;
-            }
-            if (any) HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipMemsetAsync(words, 0, 8 * sizeof(unsigned long long), st));   // (the words are per piece)
-            return TSX_HIP_OK;
+            TSX_TRY(WriteBehind::words_back(wb, 4, words, bb.h_words.get(), 8, bb.p.ev.get(), st));
+            for (uint32_t c = 0; c < 4; ++c) t.n[c] += h[c];
+            return WriteBehind::stage_all(wb, 4, d_out, h + 4, cuts, "bin", words, 8, st);
         });
     for (WriteBehind &w : wb)
         if (rc == TSX_HIP_OK) rc = w.flush();
@@ -5840,7 +5879,7 @@ static void lines_launch(tsx_hip_map *m, const uint8_t *d_text, uint64_t n, uint
                          const unsigned long long *d_line_base, uint64_t off, bool last, unsigned long long *lo, uint64_t cap,
                          hipStream_t st) {
     const uint64_t ntiles = (own_end + TILE - 1) / TILE;
-    const uint32_t lshift = m->p.line_mask == 3 ? 2u : 1u;
+    const uint32_t lshift = line_shift(m);
     hipLaunchKernelGGL(trim_lines_kernel, dim3((uint32_t)std::min<uint64_t>(ntiles, (uint64_t)m->cus * 8)), dim3(NT), 0, st,
                        d_text, n, own_end, head_open, (const uint32_t *)m->d_tile.get(), ntiles, d_line_base,
                        (const uint32_t *)m->d_carry.get(), lshift, off, last ? 1 : 0, lo, cap);
@@ -5852,14 +5891,9 @@ extern "C" int tsx_hip_trim_spans_device(tsx_hip_map *m, const void *dev_text, s
                                          void *dev_spans, size_t spans_cap, size_t *n_records, void *stream) {
     if (n_records) *n_records = 0;
     if (!trim_rule_ok(m, rule) || (!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_spans && spans_cap)) return TSX_HIP_EINVAL;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
-    int rc = ensure_zeroed(m, st);
-    if (rc != TSX_HIP_OK) return rc;
-    if ((rc = base_rule_ok(m)) != TSX_HIP_OK) return rc;
-    const uint32_t lpr = m->p.line_mask + 1;
-    // (a non-empty line and its '\n' are two bytes: no text holds more records than this)
-    const uint64_t cap = std::min<uint64_t>(spans_cap, n / (2 * lpr) + 2), nwords = ((uint64_t)n + 63) / 64;
+    hipStream_t st;
+    TSX_TRY(device_begin(m, stream, st));
+    const uint64_t cap = std::min<uint64_t>(spans_cap, max_records(m, n)), nwords = ((uint64_t)n + 63) / 64;
     DevBuf<unsigned long long> bits, lo;
     SyncAtExit wait(st);
     TSX_TRY(bits.alloc((nwords + 1) * 8));
@@ -5868,13 +5902,12 @@ extern "C" int tsx_hip_trim_spans_device(tsx_hip_map *m, const void *dev_text, s
     unsigned long long *span = (unsigned long long *)dev_spans;
     if (spans_cap) HIP_TRY(hipMemsetAsync(span, 0, spans_cap * sizeof(tsx_hip_trim_span), st));
     HIP_TRY(hipMemsetAsync(lo.get(), 0, (cap + 1) * TL_N * 8, st));
-    rc = device_windows(m, base, n, true, st,   // (whole bitmap words)
-                        [&](size_t off, size_t own, size_t len, int head_open, bool last, const unsigned long long *d_base) -> int {
-                            TSX_TRY(solid_launch(m, base + off, len, own, head_open, d_base, *rule, bits.get() + off / 64, st));
-                            lines_launch(m, base + off, len, own, head_open, d_base, off, last, lo.get(), cap, st);
-                            return TSX_HIP_OK;
-                        });
-    if (rc != TSX_HIP_OK) return rc;
+    TSX_TRY(device_windows(m, base, n, true, st,   // (whole bitmap words)
+                           [&](size_t off, size_t own, size_t len, int head_open, bool last, const unsigned long long *d_base) -> int {
+                               TSX_TRY(solid_launch(m, base + off, len, own, head_open, d_base, *rule, bits.get() + off / 64, st));
+                               lines_launch(m, base + off, len, own, head_open, d_base, off, last, lo.get(), cap, st);
+                               return TSX_HIP_OK;
+                           }));
     if (cap && nwords) {
         const unsigned long long *d_nrec = (const unsigned long long *)m->d_carry.get() + 3;
         hipLaunchKernelGGL(trim_run_kernel, dim3(grid_for(m, nwords, 8)), dim3(NT), 0, st, (const unsigned long long *)bits.get(),
@@ -5887,8 +5920,8 @@ extern "C" int tsx_hip_trim_spans_device(tsx_hip_map *m, const void *dev_text, s
 
 // Scratch of one trim call that works on pieces.
 struct TrimBufs {
-    DevBuf<unsigned long long> bits, lo, span, seg, src;   // (span: the packed runs, then the spans)
-    OutBuf out;        // the trimmed records
+    DevBuf<unsigned long long> bits, lo, span, src;   // (span: the packed runs, then the spans; src: where a segment starts)
+    Compaction c;      // the segment lengths and the trimmed records
     PieceBufs p;
     explicit TrimBufs(hipStream_t s) : p(s) {}
 };
@@ -5917,42 +5950,24 @@ static int trim_records(tsx_hip_map *m, TrimBufs &b, const uint8_t *d_text, uint
     return TSX_HIP_OK;
 }
 
-// Behind trim_records: the four segment lengths of every record in b.seg (4 nrec + 1 entries, the last 0, room for the
-// scan behind them), their sources in b.src, tot[0..2] += records written, bases in, bases kept.
+// Behind trim_records: the four segment lengths of every record in b.c (4 nrec + 1 entries, the last 0), their sources
+// in b.src, tot[0..2] += records written, bases in, bases kept.
 static int trim_lens(tsx_hip_map *m, TrimBufs &b, uint64_t nrec, const tsx_hip_trim_rule &rule, unsigned long long *tot,
                      hipStream_t st) {
     const uint32_t lpr = m->p.line_mask + 1;
-    const uint64_t nseg = nrec * 4, nk = nseg + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    TSX_TRY(grow(st, b.seg, (nk + nchunks + 16) * sizeof(unsigned long long)));
-    TSX_TRY(grow(st, b.src, nseg * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(b.seg.get() + nseg, 0, sizeof(unsigned long long), st));
+    unsigned long long *seg;
+    TSX_TRY(b.c.lengths(st, nrec * 4, seg));
+    TSX_TRY(grow(st, b.src, nrec * 4 * sizeof(unsigned long long)));
     hipLaunchKernelGGL(trim_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, b.span.get(),
-                       (const unsigned long long *)b.lo.get(), nrec, lpr, rule.min_len ? rule.min_len : (uint64_t)m->p.k, b.seg.get(),
+                       (const unsigned long long *)b.lo.get(), nrec, lpr, rule.min_len ? rule.min_len : (uint64_t)m->p.k, seg,
                        b.src.get(), tot);
-    HIP_TRY(hipGetLastError());
-    return TSX_HIP_OK;
-}
-
-// The scan of nseg + 1 segment lengths in place (seg has room for the chunk sums behind them; the total goes to *total)
-// and the output they describe: d_text[0, cut) through trim_copy_kernel into out (out_have bytes >= cut + 64).
-static int trim_compact(tsx_hip_map *m, const uint8_t *d_text, uint64_t cut, unsigned long long *seg, const unsigned long long *src,
-                        uint64_t nseg, unsigned long long *total, uint8_t *out, uint64_t out_have, hipStream_t st) {
-    const uint64_t nk = nseg + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    unsigned long long *chunk = seg + nk;
-    hipLaunchKernelGGL(u64_chunk_sum_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, (const unsigned long long *)seg, nk,
-                       chunk);
-    hipLaunchKernelGGL(u64_chunk_scan_kernel, dim3(1), dim3(1024), 0, st, chunk, nchunks, total);
-    hipLaunchKernelGGL(u64_scan_kernel, dim3((uint32_t)nchunks), dim3(SCAN_CHUNK), 0, st, seg, nk, (const unsigned long long *)chunk);
-    // (the copy grid covers the worst case; lanes past the total fall through)
-    hipLaunchKernelGGL(trim_copy_kernel, dim3(grid_for(m, (cut + 16) / 16 + 64, 8)), dim3(NT), 0, st, d_text, cut,
-                       src, (const unsigned long long *)seg, nseg, out, out_have);
     HIP_TRY(hipGetLastError());
     return TSX_HIP_OK;
 }
 
 // One piece: piece_front, then over its whole records [0, cut): bitmap, line offsets, runs, and either the spans alone
 // (b.span, finalized) or -- `copy` -- the segment lengths, their scan (total -> info[3], totals -> info[5..7]) and the
-// output in b.out.  What follows the wait is queued, not waited for.  Not last and no whole record: nrec = 0, nothing
+// output in b.c.out.  What follows the wait is queued, not waited for.  Not last and no whole record: nrec = 0, nothing
 // done.
 static int trim_piece(tsx_hip_map *m, TrimBufs &b, const uint8_t *d_text, uint64_t len, bool last,
                       const tsx_hip_trim_rule &rule, bool copy, hipStream_t st, uint64_t &cut, uint64_t &nrec) {
@@ -5967,8 +5982,7 @@ static int trim_piece(tsx_hip_map *m, TrimBufs &b, const uint8_t *d_text, uint64
         return TSX_HIP_OK;
     }
     TSX_TRY(trim_lens(m, b, nrec, rule, b.p.info.get() + 5, st));
-    TSX_TRY(b.out.room(st, cut));
-    return trim_compact(m, d_text, cut, b.seg.get(), b.src.get(), nrec * 4, b.p.info.get() + 3, b.out.out, (uint64_t)b.out.have, st);
+    return b.c.copy_segments(m, d_text, cut, b.src.get(), nrec * 4, b.p.info.get() + 3, st);
 }
 
 // Spans and trimmed reads: the pieces of host_pieces.  fd < 0: each piece's spans go to spans_out[rec_base ..] while
@@ -5986,7 +6000,7 @@ static int trim_host(tsx_hip_map *m, const char *text, size_t n, const tsx_hip_t
         },
         [&](size_t, uint64_t base, uint64_t cut, uint64_t nrec, bool) -> int {
             if (fd < 0) return deliver_records(spans_out, spans_cap, base, b.span.get(), nrec, st);
-            return nrec ? wb.piece(b.p, b.out.out, cut, 3, tot, "trim") : TSX_HIP_OK;
+            return nrec ? wb.piece(b.p, b.c.out.out, cut, 3, tot, "trim") : TSX_HIP_OK;
         });
     if (rc == TSX_HIP_OK) rc = wb.flush();
     if (n_records) *n_records = (size_t)records;
@@ -6016,26 +6030,16 @@ extern "C" int tsx_hip_trim_reads_device(tsx_hip_map *m, const void *dev_text, s
         n >= QUERY_PIECE_MAX)
         return TSX_HIP_EINVAL;
     if (out_cap < n + 64) return TSX_HIP_ERANGE;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
-    int rc = base_rule_ok(m);
-    if (rc == TSX_HIP_OK) rc = ensure_zeroed(m, st);
-    if (rc != TSX_HIP_OK) return rc;
+    hipStream_t st;
+    TSX_TRY(device_begin(m, stream, st));
     TrimBufs b(st);
-    rc = b.p.init();
-    b.out.out = (uint8_t *)dev_out; b.out.have = out_cap;   // the copy writes the caller's buffer (never grown)
-    tsx_hip_trim_totals t = {0, 0, 0, 0, 0};
+    int rc = b.p.init();
+    b.c.out.out = (uint8_t *)dev_out; b.c.out.have = out_cap;   // the copy writes the caller's buffer (never grown)
     uint64_t cut = 0, nrec = 0;
+    const unsigned long long *h = nullptr;
     if (rc == TSX_HIP_OK) rc = trim_piece(m, b, (const uint8_t *)dev_text, n, true, *rule, true, st, cut, nrec);
-    if (rc == TSX_HIP_OK && nrec) {
-        if (hipMemcpyAsync(b.p.h_info.get() + 3, b.p.info.get() + 3, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            rc = TSX_HIP_EHIP;
-        const unsigned long long *h = b.p.h_info.get();
-        if (rc == TSX_HIP_OK) { t.records = nrec; t.bytes = h[3]; t.kept = h[5]; t.bases_in = h[6]; t.bases_kept = h[7]; }
-        if (rc == TSX_HIP_OK && t.bytes > cut + 1) { g_last_error = "trim output larger than its text"; rc = TSX_HIP_EHIP; }
-    }
-    if (totals) *totals = t;
+    if (rc == TSX_HIP_OK && nrec) rc = piece_words(b.p, 5, cut, "trim", h);
+    if (totals && h) *totals = tsx_hip_trim_totals{nrec, h[5], h[6], h[7], h[3]};
     return rc;
 }
 
@@ -6221,9 +6225,7 @@ static int correct_device(tsx_hip_map *m, const void *dev_text, size_t n, const 
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t st = pick_stream(m, stream);
     TSX_TRY(ensure_zeroed(m, st));
-    const uint32_t lpr = m->p.line_mask + 1;
-    // (a non-empty line and its '\n' are two bytes: no text holds more records than this)
-    const uint64_t rcap = n / (2 * lpr) + 2, nwords = ((uint64_t)n + 63) / 64;
+    const uint64_t rcap = max_records(m, n), nwords = ((uint64_t)n + 63) / 64;
     CorrectBufs b(m, st);
     DevBuf<unsigned long long> &tot = b.s.tot;
     SyncAtExit wait(st);
@@ -6358,13 +6360,10 @@ static int median_windows(tsx_hip_map *m, const uint8_t *base, size_t n, uint32_
 extern "C" int tsx_hip_count_profile_device(tsx_hip_map *m, const void *dev_text, size_t n, void *dev_profile, void *stream) {
     if (!query_args_ok(m, 0, 0) || (!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_profile && n) || ((uintptr_t)dev_profile & 3))
         return TSX_HIP_EINVAL;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
-    int rc = ensure_zeroed(m, st);
-    if (rc != TSX_HIP_OK) return rc;
-    if ((rc = base_rule_ok(m)) != TSX_HIP_OK) return rc;
+    hipStream_t st;
+    TSX_TRY(device_begin(m, stream, st));
     SyncAtExit wait(st);
-    if ((rc = median_windows(m, (const uint8_t *)dev_text, n, (uint32_t *)dev_profile, nullptr, 0, st)) != TSX_HIP_OK) return rc;
+    TSX_TRY(median_windows(m, (const uint8_t *)dev_text, n, (uint32_t *)dev_profile, nullptr, 0, st));
     HIP_TRY(hipStreamSynchronize(st));
     return TSX_HIP_OK;
 }
@@ -6376,14 +6375,9 @@ extern "C" int tsx_hip_median_reads_device(tsx_hip_map *m, const void *dev_text,
     if (!query_args_ok(m, 0, 0) || (!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_medians && med_cap) ||
         ((uintptr_t)dev_medians & 7))
         return TSX_HIP_EINVAL;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
-    int rc = ensure_zeroed(m, st);
-    if (rc != TSX_HIP_OK) return rc;
-    if ((rc = base_rule_ok(m)) != TSX_HIP_OK) return rc;
-    const uint32_t lpr = m->p.line_mask + 1;
-    // (a non-empty line and its '\n' are two bytes: no text holds more records than this)
-    const uint64_t cap = std::min<uint64_t>(med_cap, n / (2 * lpr) + 2);
+    hipStream_t st;
+    TSX_TRY(device_begin(m, stream, st));
+    const uint64_t cap = std::min<uint64_t>(med_cap, max_records(m, n));
     const uint64_t long_len = median_long_bases(), list_cap = median_list_cap(n, long_len);
     DevBuf<uint32_t> profile;
     DevBuf<unsigned long long> lo, list;
@@ -6392,11 +6386,9 @@ extern "C" int tsx_hip_median_reads_device(tsx_hip_map *m, const void *dev_text,
     TSX_TRY(lo.alloc((cap + 1) * TL_N * 8));
     TSX_TRY(list.alloc((list_cap + 1) * 8));
     HIP_TRY(hipMemsetAsync(lo.get(), 0, (cap + 1) * TL_N * 8, st));
-    if ((rc = median_windows(m, (const uint8_t *)dev_text, n, profile.get(), lo.get(), cap, st)) != TSX_HIP_OK) return rc;
+    TSX_TRY(median_windows(m, (const uint8_t *)dev_text, n, profile.get(), lo.get(), cap, st));
     const unsigned long long *d_nrec = (const unsigned long long *)m->d_carry.get() + 3;
-    if ((rc = median_select(m, profile.get(), lo.get(), d_nrec, 0, 0, cap, long_len, list.get(), list_cap,
-                            (unsigned long long *)dev_medians, st)) != TSX_HIP_OK)
-        return rc;
+    TSX_TRY(median_select(m, profile.get(), lo.get(), d_nrec, 0, 0, cap, long_len, list.get(), list_cap, (unsigned long long *)dev_medians, st));
     unsigned long long nrec = 0;
     HIP_TRY(hipMemcpyAsync(&nrec, d_nrec, sizeof nrec, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -6407,8 +6399,8 @@ extern "C" int tsx_hip_median_reads_device(tsx_hip_map *m, const void *dev_text,
 // Scratch of one median call that works on pieces.
 struct MedianBufs {
     DevBuf<uint32_t> profile;
-    DevBuf<unsigned long long> lo, list, med, koff;
-    OutBuf out;        // the filter's output
+    DevBuf<unsigned long long> lo, list, med;
+    Compaction c;      // the filter's kept lengths and its output
     PieceBufs p;
     explicit MedianBufs(hipStream_t s) : p(s) {}
 };
@@ -6439,18 +6431,15 @@ static int median_piece(tsx_hip_map *m, MedianBufs &b, const uint8_t *d_text, ui
 }
 
 // The median filter behind median_piece, as filter_piece: kept lengths by the medians, their scan (total -> info[3], kept
-// records -> info[5]), the compaction into b.out.  Queued, not waited for.
+// records -> info[5]), the compaction into b.c.out.  Queued, not waited for.
 static int median_filter_piece(tsx_hip_map *m, MedianBufs &b, const uint8_t *d_text, uint64_t cut, uint64_t nrec, bool open,
                                const tsx_hip_median_rule &rule, hipStream_t st) {
-    const uint64_t nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    TSX_TRY(grow(st, b.koff, (nk + nchunks + 16) * sizeof(unsigned long long)));
-    TSX_TRY(b.out.room(st, cut));
-    unsigned long long *const koff = b.koff.get(), *const info = b.p.info.get();
+    unsigned long long *koff, *const info = b.p.info.get();
     const unsigned long long *span = b.p.rspan.get();
-    HIP_TRY(hipMemsetAsync(koff + nrec, 0, sizeof(unsigned long long), st));
+    TSX_TRY(b.c.lengths(st, nrec, koff));
     hipLaunchKernelGGL(median_len_kernel, dim3(grid_for(m, nrec, 8)), dim3(NT), 0, st, (const unsigned long long *)b.med.get(),
                        span, nrec, rule.lower, rule.upper, rule.invert, open ? 1 : 0, koff, info + 5);
-    return filter_compact(m, d_text, cut, span, koff, nrec, info + 3, b.out.out, (uint64_t)b.out.have, st);
+    return b.c.copy_spans(m, d_text, cut, span, nrec, info + 3, st);
 }
 
 // Profile, medians and the median filter: the pieces of host_pieces, at most TSX_HIP_PIECE_BYTES each when that is set.
@@ -6482,7 +6471,7 @@ static int median_host(tsx_hip_map *m, const char *text, size_t n, int what, siz
             }
             if (!nrec) return TSX_HIP_OK;
             TSX_TRY(median_filter_piece(m, b, b.p.text.get(), cut, nrec, open, *rule, st));
-            return wb.piece(b.p, b.out.out, cut, 1, &kept, "filter");
+            return wb.piece(b.p, b.c.out.out, cut, 1, &kept, "filter");
         });
     if (rc == TSX_HIP_OK) rc = wb.flush();
     if (n_records) *n_records = (size_t)rec_base;
@@ -6551,7 +6540,7 @@ static int kept_launch(tsx_hip_map *m, const NormWindow &w, uint64_t t0, uint64_
     const size_t lut_bytes = m->lut.size() * 8;
     const int grid = (int)std::min<uint64_t>(t1 - t0, (uint64_t)m->cus * 3);
     const uint64_t tiles_all = (w.own + TILE - 1) / TILE;
-    const uint32_t lshift = m->p.line_mask == 3 ? 2u : 1u;
+    const uint32_t lshift = line_shift(m);
     DISPATCH_BR(m, DISPATCH_CANON(m, DISPATCH_WK(m, hipLaunchKernelGGL((count_kept_kernel<WKV, CANV, BRV>), dim3(grid), dim3(NT),
                                                         lut_bytes, st, m->p, w.text, w.len, w.own, w.head_open, w.tile_line, t0, t1,
                                                         tiles_all, w.line_base, lshift, keep, r0, r1, skipped, m->qmap_cur))));
@@ -6562,8 +6551,8 @@ static int kept_launch(tsx_hip_map *m, const NormWindow &w, uint64_t t0, uint64_
 // The rounds of the records [0, nrec) of a text that lies in the windows win[0, nwin) (in text order; its records end
 // at byte `end`), R records each: per round the profile of its tiles, the medians of its records, the keep rule, the
 // count of the kept.  profile: the entry of byte 0 of the text; lo: the line offsets of the records (text positions).
-// span / len: the record spans and the kept lengths for filter_compact (both NULL: no output); keep_bytes: one byte per
-// record < bytes_cap, or NULL.  totals: NT_N device words that grow.  Waits once, for the round bounds; the rounds are
+// span / len: the record spans and the kept lengths for Compaction::copy_spans (both NULL: no output); keep_bytes: one
+// byte per record < bytes_cap, or NULL.  totals: NT_N device words that grow.  Waits once, for the round bounds; the rounds are
 // queued.  The caller holds a QmapScope.
 static int normalize_rounds(tsx_hip_map *m, NormBufs &nb, const NormWindow *win, size_t nwin, uint64_t end, uint64_t nrec, uint64_t R,
                             uint64_t cutoff, uint32_t *profile, const unsigned long long *lo, const unsigned long long *span,
@@ -6663,15 +6652,13 @@ static int normalize_host(tsx_hip_map *m, const char *text, size_t n, const tsx_
             if (!nrec) return TSX_HIP_OK;
             if (!began) { TSX_TRY(normalize_tiles_begin(nb, st)); began = true; }
             const uint8_t *d_text = b.p.text.get();
-            const uint64_t list_cap = median_list_cap(cut, long_len), nk = nrec + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
+            const uint64_t list_cap = median_list_cap(cut, long_len);
+            unsigned long long *koff = nullptr;   // the kept lengths, when there is an output
             TSX_TRY(grow(st, b.profile, (cut + 16) * sizeof(uint32_t)));
             TSX_TRY(grow(st, b.lo, nrec * TL_N * 8));
             TSX_TRY(grow(st, b.med, nrec * sizeof(tsx_hip_read_median)));
             TSX_TRY(grow(st, b.list, (list_cap + 1) * 8));
-            if (fd >= 0) {
-                TSX_TRY(grow(st, b.koff, (nk + nchunks + 16) * sizeof(unsigned long long)));
-                TSX_TRY(b.out.room(st, cut));
-            }
+            if (fd >= 0) TSX_TRY(b.c.lengths(st, nrec, koff));
             if (keep_out) TSX_TRY(grow(st, keepb, nrec));
             QmapScope qs(m);
             TSX_TRY(piece_qmap(m, d_text, cut, st));
@@ -6681,13 +6668,12 @@ static int normalize_host(tsx_hip_map *m, const char *text, size_t n, const tsx_
             lines_launch(m, d_text, cut, cut, 0, info + 4, 0, open, b.lo.get(), nrec, st);
             const NormWindow w = {d_text, 0, cut, cut, 0, (const uint32_t *)m->d_tile.get(), info + 4, m->qmap_cur};
             TSX_TRY(normalize_rounds(m, nb, &w, 1, cut, nrec, R, rule.cutoff, b.profile.get(), b.lo.get(),
-                                     fd >= 0 ? b.p.rspan.get() : nullptr, fd >= 0 ? b.koff.get() : nullptr, open,
+                                     fd >= 0 ? b.p.rspan.get() : nullptr, koff, open,
                                      keep_out ? keepb.get() : nullptr, nrec, b.list.get(), list_cap, b.med.get(), info + 5, long_len, st,
                                      rounds));
             if (fd >= 0) {
-                HIP_TRY(hipMemsetAsync(b.koff.get() + nrec, 0, sizeof(unsigned long long), st));
-                TSX_TRY(filter_compact(m, d_text, cut, b.p.rspan.get(), b.koff.get(), nrec, info + 3, b.out.out, (uint64_t)b.out.have, st));
-                TSX_TRY(wb.piece(b.p, b.out.out, cut, NT_N, count, "normalize"));
+                TSX_TRY(b.c.copy_spans(m, d_text, cut, b.p.rspan.get(), nrec, info + 3, st));
+                TSX_TRY(wb.piece(b.p, b.c.out.out, cut, NT_N, count, "normalize"));
             } else {
                 unsigned long long *h = b.p.h_info.get();
                 HIP_TRY(hipMemcpyAsync(h + 5, info + 5, NT_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
@@ -6730,13 +6716,10 @@ extern "C" int tsx_hip_normalize_device(tsx_hip_map *m, const void *dev_text, si
     if ((!dev_text && n) || ((uintptr_t)dev_text & 15) || (!dev_keep && keep_cap)) return TSX_HIP_EINVAL;
     m->norm_tiles = m->norm_skipped = 0;
     if (n && rule->cutoff) m->used = true;
-    HIP_TRY(hipSetDevice(m->device));
-    hipStream_t st = pick_stream(m, stream);
-    TSX_TRY(ensure_zeroed(m, st));
-    TSX_TRY(base_rule_ok(m));
+    hipStream_t st;
+    TSX_TRY(device_begin(m, stream, st));
     const uint8_t *base = (const uint8_t *)dev_text;
-    const uint32_t lpr = m->p.line_mask + 1;
-    const uint64_t cap = n / (2 * lpr) + 2;   // (no text holds more records: tsx_hip_median_reads_device)
+    const uint64_t cap = max_records(m, n);
     const uint64_t long_len = median_long_bases(), list_cap = median_list_cap(n, long_len);
     const size_t WIN = (dev_window_bytes() + 63) & ~(size_t)63, nwin = n ? (n - 1) / WIN + 1 : 0;
     const uint64_t tiles_win = (WIN + TILE - 1) / TILE;   // room per window
@@ -7160,52 +7143,53 @@ struct PairSide {
     bool last = false;
     PairSide(hipStream_t st, bool trim) : q(st), t(st), p(trim ? t.p : q.p) {}
 };
-// One output of a pair call: the gated lengths (scanned in place), the compacted bytes and their way to the file.
-struct PairOut {
-    DevBuf<unsigned long long> off;
-    DevBuf<uint8_t> out;
-    WriteBehind w;
-    bool used = false;      // the gate writes its lengths
-};
+static int pair_fail(const std::string &what) { g_last_error = what; return TSX_HIP_EPAIR; }
 
-static int pair_fail(const std::string &what) {
-    g_last_error = what;
-    return TSX_HIP_EPAIR;
-}
-
-// Both pair calls (trule: the trim, else frule: the filter).  Outputs: 0 kept mates 1, 1 kept mates 2, 2 orphans of A,
+// One pair call (trule: the trim, else frule: the filter).  Outputs: 0 kept mates 1, 1 kept mates 2, 2 orphans of A,
 // 3 orphans of B; an interleaved text (text2 == NULL) uses 0 and 2 for both mates.  Every round: a piece of each text,
 // both scans, pair_cut_kernel and ONE wait for the record count R and the cuts; then records [0, R) of each piece through
 // the single-end kernels, the gate, one compaction per output.  The outputs of round i are written while the device
-// works on round i + 1.
-static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *text2, size_t n2, const tsx_hip_filter_rule *frule,
-                      const tsx_hip_trim_rule *trule, int any, int check_names, const tsx_hip_pair_io &io, size_t chunk_bytes,
-                      tsx_hip_pair_totals *totals) {
-    const bool trim = trule != nullptr, inter = text2 == nullptr;
-    const int ns = inter ? 1 : 2;
-    TSX_TRY(pieces_begin(m, chunk_bytes, false));
-    hipStream_t st = m->stream.get();
-    int rc = TSX_HIP_OK;
-    // (the sides are declared last: their destructors wait for the stream before anything here is released)
-    PairOut out[4];
+// works on round i + 1.  One method per step of a round; run() is the rounds, finish() every way out.
+struct PairRun {
+    tsx_hip_map *m;
+    hipStream_t st;
+    const tsx_hip_filter_rule *frule;
+    const tsx_hip_trim_rule *trule;
+    int any, check_names;
+    size_t chunk_bytes;
+    bool trim, inter;
+    int ns;                     // texts
+    uint32_t stride, per;       // records of a text per pair; entries of a length array per record
+    tsx_hip_pair_totals t;
+    uint64_t R = 0, cut[2] = {0, 0};      // what the round agreed on: the records it takes of each piece, where the pieces end
+    bool open[2] = {false, false};
+    WriteBehind wb[4];          // (fd < 0: not wanted, or not used)
+    Compaction out[4];          // the gated lengths of an output (scanned in place) and its bytes
     DevBuf<unsigned long long> pinfo;
     PinBuf<unsigned long long> h_pinfo;
     Event ev;
-    PairSide side[2] = {PairSide(st, trim), PairSide(st, trim)};
-    side[0].text = text1; side[0].n = n1;
-    side[1].text = text2; side[1].n = inter ? 0 : n2;
-    out[0].w.fd = io.fd1; out[1].w.fd = io.fd2; out[2].w.fd = io.fd_single1; out[3].w.fd = io.fd_single2;
-    out[0].used = out[2].used = true;
-    out[1].used = out[3].used = !inter;
-    for (int i = 0; i < ns; ++i) TSX_TRY(side[i].p.init());
-    TSX_TRY(pinfo.alloc(PI_N * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(pinfo.get(), 0, PI_N * sizeof(unsigned long long), st));
-    TSX_TRY(h_pinfo.alloc(PI_N * sizeof(unsigned long long)));
-    TSX_TRY(ev.create());
-    const unsigned long long *h = h_pinfo.get();
-    unsigned long long *const pi = pinfo.get();
-    // the piece [off, off + len) of a side to the device, and its scan (an empty piece: no records)
-    auto scan = [&](PairSide &s) -> int {
+    PairSide side[2];   // (the sides are declared last: their destructors wait for the stream before anything above is released)
+
+    PairRun(tsx_hip_map *mm, const tsx_hip_filter_rule *fr, const tsx_hip_trim_rule *tr, int any_, int names, size_t chunk, bool inter_)
+        : m(mm), st(mm->stream.get()), frule(fr), trule(tr), any(any_), check_names(names), chunk_bytes(chunk), trim(tr != nullptr),
+          inter(inter_), ns(inter_ ? 1 : 2), stride(inter_ ? 2u : 1u), per(tr ? 4u : 1u),
+          side{PairSide(mm->stream.get(), tr != nullptr), PairSide(mm->stream.get(), tr != nullptr)} {
+        memset(&t, 0, sizeof t);
+    }
+    bool used(int oi) const { return !inter || !(oi & 1); }   // the gate writes its lengths
+    int init(const char *text1, size_t n1, const char *text2, size_t n2, const tsx_hip_pair_io &io) {
+        side[0].text = text1; side[0].n = n1;
+        side[1].text = text2; side[1].n = inter ? 0 : n2;
+        const int fd[4] = {io.fd1, io.fd2, io.fd_single1, io.fd_single2};
+        for (int oi = 0; oi < 4; ++oi) wb[oi].fd = used(oi) ? fd[oi] : -1;
+        for (int i = 0; i < ns; ++i) TSX_TRY(side[i].p.init());
+        TSX_TRY(pinfo.alloc(PI_N * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(pinfo.get(), 0, PI_N * sizeof(unsigned long long), st));
+        TSX_TRY(h_pinfo.alloc(PI_N * sizeof(unsigned long long)));
+        return ev.create();
+    }
+    // The piece [off, off + len) of a side to the device, and its scan (an empty piece: no records).
+    int scan(PairSide &s) {
         s.last = s.off + s.len == s.n;
         if (s.len == 0) {
             HIP_TRY(hipMemsetAsync(s.p.info.get(), 0, 3 * sizeof(unsigned long long), st));
@@ -7213,95 +7197,81 @@ static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *
         }
         TSX_TRY(piece_upload(s.p, s.text + s.off, s.len));
         return piece_scan(m, s.p.text.get(), s.len, s.last, s.p.info.get(), &s.p.rspan, st);
-    };
-    auto longer = [&](PairSide &s) -> int {   // a piece without a whole record (interleaved: a whole pair) grows
+    }
+    int longer(PairSide &s) {   // a piece without a whole record (interleaved: a whole pair) grows
         TSX_TRY(piece_longer(s.len, s.n - s.off));
         return scan(s);
-    };
-    auto flush = [&]() -> int {   // the outputs of the round before, to their files
-        for (PairOut &o : out) TSX_TRY(o.w.flush());
-        return TSX_HIP_OK;
-    };
-    tsx_hip_pair_totals t;
-    memset(&t, 0, sizeof t);
-    bool have_pending = false;
-    while (rc == TSX_HIP_OK) {
-        bool rest = false;
-        for (int i = 0; i < ns; ++i) rest |= side[i].off < side[i].n;
-        if (!rest) break;
-        for (int i = 0; i < ns && rc == TSX_HIP_OK; ++i) {
-            side[i].len = std::min(chunk_bytes, side[i].n - side[i].off);
-            rc = scan(side[i]);
-        }
-        if (rc != TSX_HIP_OK) break;
-        for (;;) {
+    }
+
+    // The cut: pair_cut_kernel and the one wait of a round, again while a side that holds no whole record (pair) can
+    // grow.  done: nothing but empty lines is left.  Texts that are out of step: TSX_HIP_EPAIR.
+    int agree(bool &done) {
+        const unsigned long long *h = h_pinfo.get();
+        for (bool again = true; again;) {
             hipLaunchKernelGGL(pair_cut_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)side[0].p.info.get(),
                                (const unsigned long long *)side[0].p.rspan.get(),
                                inter ? (const unsigned long long *)nullptr : (const unsigned long long *)side[1].p.info.get(),
                                inter ? (const unsigned long long *)nullptr : (const unsigned long long *)side[1].p.rspan.get(),
-                               side[0].last ? 1 : 0, pi);
-            if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h_pinfo.get(), pi, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            bool again = false;
-            if (inter) {
-                if (h[PI_R] == 0 && !side[0].last) { rc = longer(side[0]); again = true; }
-            } else {
-                if (h[PI_RA] == 0 && !side[0].last) { rc = longer(side[0]); again = true; }
-                if (rc == TSX_HIP_OK && h[PI_RB] == 0 && !side[1].last) { rc = longer(side[1]); again = true; }
-            }
-            if (rc != TSX_HIP_OK || !again) break;
+                               side[0].last ? 1 : 0, pinfo.get());
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(h_pinfo.get(), pinfo.get(), 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            again = false;
+            if (h[inter ? PI_R : PI_RA] == 0 && !side[0].last) { TSX_TRY(longer(side[0])); again = true; }
+            if (!inter && h[PI_RB] == 0 && !side[1].last) { TSX_TRY(longer(side[1])); again = true; }
         }
-        if (rc != TSX_HIP_OK) break;
-        const uint64_t R = h[PI_R], RA = h[PI_RA], RB = h[PI_RB];
-        const uint64_t cut[2] = {h[PI_CUT_A], h[PI_CUT_B]};
-        const bool open[2] = {h[PI_OPEN_A] != 0, h[PI_OPEN_B] != 0};
+        const uint64_t RA = h[PI_RA], RB = h[PI_RB];
+        R = h[PI_R];
+        cut[0] = h[PI_CUT_A]; cut[1] = h[PI_CUT_B];
+        open[0] = h[PI_OPEN_A] != 0; open[1] = h[PI_OPEN_B] != 0;
         if (inter) {
-            if (side[0].last && (RA & 1)) {
-                rc = pair_fail("an interleaved text with an odd number of records (" + std::to_string(2 * t.pairs + RA) + ")");
-                break;
-            }
-            if (R == 0) break;   // (nothing but empty lines)
-        } else {
-            if (RA == 0 && RB == 0) break;   // (nothing but empty lines in either)
-            if (R == 0) {
-                rc = pair_fail(std::string("text ") + (RA ? "2" : "1") + " ends after " + std::to_string(t.pairs) +
-                               " records, text " + (RA ? "1" : "2") + " holds more");
-                break;
-            }
+            if (side[0].last && (RA & 1))
+                return pair_fail("an interleaved text with an odd number of records (" + std::to_string(2 * t.pairs + RA) + ")");
+            done = R == 0;   // (nothing but empty lines)
+            return TSX_HIP_OK;
         }
-        const uint64_t npairs = inter ? R / 2 : R;
-        const uint32_t stride = inter ? 2u : 1u, per = trim ? 4u : 1u;   // entries of a length array per record
-        // records [0, R) of each piece (the line pass again: the tile counts are the map's, and the other text's by now)
-        for (int i = 0; i < ns && rc == TSX_HIP_OK; ++i) {
+        done = RA == 0 && RB == 0;   // (nothing but empty lines in either)
+        if (!done && R == 0)
+            return pair_fail(std::string("text ") + (RA ? "2" : "1") + " ends after " + std::to_string(t.pairs) +
+                             " records, text " + (RA ? "1" : "2") + " holds more");
+        return TSX_HIP_OK;
+    }
+
+    // Records [0, R) of each piece through the single-end kernels (the line pass again: the tile counts are the map's, and
+    // the other text's by now).
+    int records() {
+        for (int i = 0; i < ns; ++i) {
             PairSide &s = side[i];
             const uint8_t *d_text = s.p.text.get();
-            if (hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-            if ((rc = line_pass(m, d_text, cut[i], cut[i], 0, st)) != TSX_HIP_OK) break;
+            HIP_TRY(hipMemsetAsync(m->d_carry.get(), 0, sizeof(uint32_t), st));
+            TSX_TRY(line_pass(m, d_text, cut[i], cut[i], 0, st));
             if (trim) {
-                rc = trim_records(m, s.t, d_text, cut[i], R, s.last && cut[i] == s.len, *trule, st);
-                if (rc == TSX_HIP_OK) rc = trim_lens(m, s.t, R, *trule, pi + (i ? PI_TRIM_B : PI_TRIM_A), st);
+                TSX_TRY(trim_records(m, s.t, d_text, cut[i], R, s.last && cut[i] == s.len, *trule, st));
+                TSX_TRY(trim_lens(m, s.t, R, *trule, pinfo.get() + (i ? PI_TRIM_B : PI_TRIM_A), st));
             } else {
-                rc = query_records(m, s.q, d_text, cut[i], R, frule->lower, frule->upper, st);
+                TSX_TRY(query_records(m, s.q, d_text, cut[i], R, frule->lower, frule->upper, st));
             }
         }
-        if (rc != TSX_HIP_OK) break;
-        const uint64_t ne = R * per, nk = ne + 1, nchunks = (nk + SCAN_CHUNK - 1) / SCAN_CHUNK;
-        for (PairOut &o : out) {
-            if (!o.used) continue;
-            if ((rc = grow(st, o.off, (nk + nchunks + 16) * sizeof(unsigned long long))) != TSX_HIP_OK) break;
-            if (hipMemsetAsync(o.off.get() + ne, 0, sizeof(unsigned long long), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        }
-        if (rc != TSX_HIP_OK) break;
+        return TSX_HIP_OK;
+    }
+
+    // The names, and the gate: what each mate gives to every output that is used.  An interleaved text keeps both mates'
+    // lengths in one array: mate 2's entries are mate 1's moved on by one record.
+    int gate() {
+        const uint64_t npairs = R / stride, ne = R * per;
+        unsigned long long *const pi = pinfo.get(), *len[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int oi = 0; oi < 4; ++oi)
+            if (used(oi)) TSX_TRY(out[oi].lengths(st, ne, len[oi]));
         PairSide &sb = side[inter ? 0 : 1];   // where mate 2 lives
-        unsigned long long *const keep_a = out[0].off.get(), *const single_a = out[2].off.get();
-        unsigned long long *const keep_b = inter ? keep_a + per : out[1].off.get();
-        unsigned long long *const single_b = inter ? single_a + per : out[3].off.get();
+        unsigned long long *const keep_a = len[0], *const single_a = len[2];
+        unsigned long long *const keep_b = inter ? keep_a + per : len[1];
+        unsigned long long *const single_b = inter ? single_a + per : len[3];
         const unsigned long long *span_a = side[0].p.rspan.get(), *span_b = inter ? span_a + 2 : side[1].p.rspan.get();
         if (check_names)
             hipLaunchKernelGGL(pair_names_kernel, dim3(grid_for(m, npairs, 8)), dim3(NT), 0, st, (const uint8_t *)side[0].p.text.get(),
                                span_a, (const uint8_t *)sb.p.text.get(), span_b, npairs, stride, pi + PI_BAD);
         if (trim) {
-            const unsigned long long *seg_a = side[0].t.seg.get(), *seg_b = inter ? seg_a + 4 : side[1].t.seg.get();
+            const unsigned long long *seg_a = side[0].t.c.off.get(), *seg_b = inter ? seg_a + 4 : side[1].t.c.off.get();
             hipLaunchKernelGGL(pair_gate_trim_kernel, dim3(grid_for(m, npairs, 8)), dim3(NT), 0, st, seg_a, seg_b, npairs, stride,
                                keep_a, keep_b, single_a, single_b, pi + PI_KEPT);
         } else {
@@ -7311,57 +7281,79 @@ static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *
                                (!inter && open[0]) ? 1 : 0, (inter ? open[0] : open[1]) ? 1 : 0, keep_a, keep_b, single_a, single_b,
                                pi + PI_KEPT);
         }
-        if (hipGetLastError() != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        for (int oi = 0; oi < 4 && rc == TSX_HIP_OK; ++oi) {
-            PairOut &o = out[oi];
-            if (!o.used || o.w.fd < 0) continue;
+        HIP_TRY(hipGetLastError());
+        return TSX_HIP_OK;
+    }
+
+    // One compaction per wanted output, out of the text its mates live in; the sizes go to pinfo[PI_TOTAL ..].
+    int compact() {
+        const uint64_t ne = R * per;
+        for (int oi = 0; oi < 4; ++oi) {
+            if (wb[oi].fd < 0) continue;
             const int si = inter ? 0 : (oi & 1);
             PairSide &s = side[si];
-            if ((rc = grow(st, o.out, cut[si] + 64)) != TSX_HIP_OK) break;
-            if (trim)
-                rc = trim_compact(m, s.p.text.get(), cut[si], o.off.get(), s.t.src.get(), ne, pi + PI_TOTAL + oi, o.out.get(),
-                                  (uint64_t)o.out.cap(), st);
-            else
-                rc = filter_compact(m, s.p.text.get(), cut[si], s.p.rspan.get(), o.off.get(), ne, pi + PI_TOTAL + oi, o.out.get(),
-                                    (uint64_t)o.out.cap(), st);
+            unsigned long long *total = pinfo.get() + PI_TOTAL + oi;
+            if (trim) TSX_TRY(out[oi].copy_segments(m, s.p.text.get(), cut[si], s.t.src.get(), ne, total, st));
+            else TSX_TRY(out[oi].copy_spans(m, s.p.text.get(), cut[si], s.p.rspan.get(), ne, total, st));
         }
-        if (rc != TSX_HIP_OK) break;
-        if (hipMemcpyAsync(h_pinfo.get(), pi, PI_N * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipEventRecord(ev.get(), st) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        if (have_pending) {   // the previous round's outputs, while the device works on this one
-            have_pending = false;
-            if ((rc = flush()) != TSX_HIP_OK) break;
-        }
-        if (hipEventSynchronize(ev.get()) != hipSuccess) { rc = TSX_HIP_EHIP; break; }
-        if (h[PI_BAD]) {
-            rc = pair_fail("pair " + std::to_string(t.pairs + (uint64_t)~h[PI_BAD]) + ": the names of the mates differ");
-            break;
-        }
-        for (int oi = 0; oi < 4 && rc == TSX_HIP_OK; ++oi) {
-            PairOut &o = out[oi];
-            if (!o.used || o.w.fd < 0) continue;
-            rc = o.w.stage(o.out.get(), h[PI_TOTAL + oi], cut[inter ? 0 : (oi & 1)], "pair", st);
-        }
+        return TSX_HIP_OK;
+    }
+
+    // The write-behind round.  The names are looked at between its two steps: a round with a bad pair stages nothing.
+    int deliver() {
+        const unsigned long long *h = h_pinfo.get();
+        TSX_TRY(WriteBehind::words_back(wb, 4, pinfo.get(), h_pinfo.get(), PI_N, ev.get(), st));
+        if (h[PI_BAD]) return pair_fail("pair " + std::to_string(t.pairs + (uint64_t)~h[PI_BAD]) + ": the names of the mates differ");
+        const uint8_t *d_out[4];
+        uint64_t cuts[4];
+        for (int oi = 0; oi < 4; ++oi) { d_out[oi] = out[oi].out.out; cuts[oi] = cut[inter ? 0 : (oi & 1)]; }
         // (the counters are per round)
-        if (rc == TSX_HIP_OK && (hipMemsetAsync(pi + PI_KEPT, 0, (PI_N - PI_KEPT) * sizeof(unsigned long long), st) != hipSuccess ||
-                                 hipStreamSynchronize(st) != hipSuccess))
-            rc = TSX_HIP_EHIP;
-        if (rc != TSX_HIP_OK) break;
-        have_pending = true;
-        t.pairs += npairs; t.kept += h[PI_KEPT]; t.single1 += h[PI_SINGLE_A]; t.single2 += h[PI_SINGLE_B];
+        TSX_TRY(WriteBehind::stage_all(wb, 4, d_out, h + PI_TOTAL, cuts, "pair", pinfo.get() + PI_KEPT, PI_N - PI_KEPT, st));
+        t.pairs += R / stride; t.kept += h[PI_KEPT]; t.single1 += h[PI_SINGLE_A]; t.single2 += h[PI_SINGLE_B];
         t.bases_in += h[PI_TRIM_A + 1] + h[PI_TRIM_B + 1];
         t.bases_kept += h[PI_TRIM_A + 2] + h[PI_TRIM_B + 2];
         for (int i = 0; i < ns; ++i) side[i].off += cut[i];
+        return TSX_HIP_OK;
     }
-    // (after TSX_HIP_EPAIR too: whole pairs of the pieces before the one that failed)
-    if (have_pending && (rc == TSX_HIP_OK || rc == TSX_HIP_EPAIR)) {
+
+    int run() {
+        for (;;) {
+            bool rest = false, done = false;
+            for (int i = 0; i < ns; ++i) rest |= side[i].off < side[i].n;
+            if (!rest) return TSX_HIP_OK;
+            for (int i = 0; i < ns; ++i) {
+                side[i].len = std::min(chunk_bytes, side[i].n - side[i].off);
+                TSX_TRY(scan(side[i]));
+            }
+            TSX_TRY(agree(done));
+            if (done) return TSX_HIP_OK;
+            TSX_TRY(records());
+            TSX_TRY(gate());
+            TSX_TRY(compact());
+            TSX_TRY(deliver());
+        }
+    }
+
+    // Every way out: the totals; and what waits goes to its files after TSX_HIP_EPAIR too -- whole pairs of the rounds
+    // before the one that failed -- with the error's text kept.
+    int finish(int rc, tsx_hip_pair_totals *totals) {
         const std::string why = g_last_error;
-        const int wrc = flush();
-        if (wrc != TSX_HIP_OK) rc = wrc; else g_last_error = why;
+        for (WriteBehind &w : wb)
+            if (rc == TSX_HIP_OK || rc == TSX_HIP_EPAIR) { const int wrc = w.flush(); if (wrc != TSX_HIP_OK) rc = wrc; }
+        if (rc == TSX_HIP_OK || rc == TSX_HIP_EPAIR) g_last_error = why;
+        t.bytes1 = wb[0].bytes; t.bytes2 = wb[1].bytes; t.bytes_single1 = wb[2].bytes; t.bytes_single2 = wb[3].bytes;
+        if (totals) *totals = t;
+        return rc;
     }
-    t.bytes1 = out[0].w.bytes; t.bytes2 = out[1].w.bytes; t.bytes_single1 = out[2].w.bytes; t.bytes_single2 = out[3].w.bytes;
-    if (totals) *totals = t;
-    return rc;
+};
+
+static int pairs_host(tsx_hip_map *m, const char *text1, size_t n1, const char *text2, size_t n2, const tsx_hip_filter_rule *frule,
+                      const tsx_hip_trim_rule *trule, int any, int check_names, const tsx_hip_pair_io &io, size_t chunk_bytes,
+                      tsx_hip_pair_totals *totals) {
+    TSX_TRY(pieces_begin(m, chunk_bytes, false));   // (ahead of the run: a call refused here has built and waited for nothing)
+    PairRun run(m, frule, trule, any, check_names, chunk_bytes, text2 == nullptr);
+    const int rc = run.init(text1, n1, text2, n2, io);
+    return run.finish(rc == TSX_HIP_OK ? run.run() : rc, totals);
 }
 
 static bool pair_io_ok(const tsx_hip_pair_io *io, bool inter) {
